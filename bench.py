@@ -19,6 +19,11 @@ the GPU is never re-executed), relays rank 0's JSON line and exits with the laun
 U[108,430], SURVEY §8-d seed 3 + rank) with continuous batching on its 32 slots; every finished utterance is decoded to
 audio by a worker thread on the codec's own stream while the others go on (the pipeline of synthesizer.py:483-584 across a
 batch), all of it inside the timed region; value = all ranks' frames / wall, rtf = wall / audio seconds.
+
+A plain run only sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own: the
+roofline of one decode frame (HIP-event-timed graph replays), the batch probes (`configs`) and the CPU baseline.
+`--dump-outputs DIR` (headline config): after the timed steps, the last step's token matrix (tokens.npy, float64) and
+waveform (audio.npy, float32) as the caller of that path receives them; the inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -278,6 +283,60 @@ def lockstep_probe(eng, tok, B, n_frames=128, prompt_len=48):
     return int(n.sum()), dt
 
 
+def frame_roofline(eng, args, prompt):
+    """Roofline of the step's dominant kernel chain: ONE decode frame (slow stack, vocabulary head, semantic draw, fast
+    codebook loop), timed live with HIP events on the engine's stream.  achieved = algorithmic bytes of a frame
+    (1.303 GB of weights + 114 688 B of K/V per cached position) / measured frame time.  Returns (roofline, engine flags)."""
+    sp = eng._sampling(0.7, 0.8, 1.1, seed=7, ban_eos=True)
+    fb = frame_bytes(args)
+    eng.prefill(prompt, sp)
+    NPF = 48
+    ms_graph, seg, nodes = eng.profile_frame(NPF, sp)
+    flags = eng.engine_state()[0]
+    pos_mid = PROMPT_LEN + NPF            # mean cached positions over the profiled frames (about)
+    per_frame_bytes = fb["total"] + KV_BYTES_PER_POS * pos_mid
+    frame_ms = ms_graph / NPF
+    achieved = per_frame_bytes / (frame_ms * 1e-3) / 1e9
+    # HBM-side bytes per frame: NOT measured by this run - the newest committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
+    # over this bench with eager frames (FT_NO_GRAPH; counters and stream capture do not go together), profiles/README.md
+    traffic, traffic_source = None, None
+    for rr in ("r04", "r03", "r02"):
+        tpath = os.path.join(ROOT, "profiles", rr + "_traffic.json")
+        if os.path.exists(tpath):
+            traffic = json.load(open(tpath)).get("hbm_bytes_per_frame")
+            traffic_source = f"profiles/{rr}_traffic.json (rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE, separate passes, eager frames; not this run)"
+            break
+    parts = {}
+    for name, ms_k, nbytes in (("slow_stack", seg[0], fb["slow"] + KV_BYTES_PER_POS * pos_mid), ("head_and_draw", seg[1], fb["head"]),
+                               ("fast_loop", seg[2], fb["fast"])):
+        per = ms_k / max(NPF - 1, 1)
+        parts[name] = {"ms": round(per, 4), "algorithmic_GB": round(nbytes / 1e9, 4),
+                       "GBps": round(nbytes / (per * 1e-3) / 1e9, 1) if per > 0 else None}
+    roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+            "kernel": ("one decode frame = ft::slow_engine_kernel + vocabulary head gemv + semantic draw + ft::fast_engine_kernel"
+                       if flags == 3 else "one decode frame (launch path: gemv / attention / sampler kernels)"),
+            "launches_per_frame": nodes, "bytes_per_frame": int(per_frame_bytes), "frame_us": round(frame_ms * 1e3, 2),
+            "frame_ms": round(frame_ms, 4), "frame_path": eng.frame_path(), "parts": parts}
+    try:   # sub-field kept from round 1: the HBM-streamed GEMV launches of the launch path alone
+        ms, launches, nbytes = eng.profile_gemv(20, sp)
+        roof["gemv_launch_path"] = {"GBps": round(nbytes / (ms * 1e-3) / 1e9, 1), "launches": launches,
+                                    "avg_us_per_launch": round(ms * 1e3 / max(launches, 1), 3)}
+    except Exception as e:  # noqa: BLE001
+        print(f"[bench] gemv sub-profile skipped: {e}", file=sys.stderr)
+    return roof, flags
+
+
+def dump_outputs(d, tokens, audio):
+    """--dump-outputs: what the timed path handed its caller in the last timed step - the (11, prompt + frames) token
+    matrix of eng.generate (float64: every id exact) and the codec's (1, samples) waveform (float32, as decoded)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "tokens.npy"), np.asarray(tokens, dtype=np.float64))
+    if audio is not None:
+        np.save(os.path.join(d, "audio.npy"), np.asarray(audio, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -285,12 +344,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg4"],
                     help="cfg2 = BASELINE configs[1] (the headline: batch 1, 10 s); cfg4 = configs[3] (32 mixed-length slots per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batch-probe", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the frame roofline, the batch probes and the CPU baseline (each outside the timed region)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-batch-probe", action="store_true", help="with --full: leave out the batch probes")
     ap.add_argument("--cpu-frames", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's tokens and waveform to DIR/*.npy (headline config)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU only: the ranks form a gloo group and rank 0 prints how many it saw (tests/test_bench_launcher.py)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.config != "cfg2":
+        ap.error("--dump-outputs: the headline config (cfg2) only")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a, sys.argv[1:]))
@@ -420,10 +487,11 @@ def main():
         seq = eng.generate(prompt, N_FRAMES, seed=i, poll=N_FRAMES, **kw)
         t1 = time.perf_counter()
         n = seq.shape[1] - prompt.shape[1]
+        audio = None
         if codec is not None:
-            codec.decode(seq[1:, prompt.shape[1]:][None])
+            audio = codec.decode(seq[1:, prompt.shape[1]:][None])
         t2 = time.perf_counter()
-        return n, t1 - t0, t2 - t1
+        return n, t1 - t0, t2 - t1, seq, audio
 
     for i in range(a.warmup):
         step(1000 + i)
@@ -434,7 +502,7 @@ def main():
     frames = 0
     ar_s = cod_s = 0.0
     for i in range(a.steps):
-        n, ta, tc = step(i)
+        n, ta, tc, seq, audio = step(i)
         frames += n
         ar_s += ta
         cod_s += tc
@@ -455,16 +523,13 @@ def main():
         ar_max = ar_s
         frames_total = float(frames)
 
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, seq, audio)
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
         return
 
-    # ---- roofline of the step's dominant kernel chain: ONE decode frame (slow stack, vocabulary head, semantic draw, fast
-    # codebook loop), timed live with HIP events on the engine's stream.  achieved = algorithmic bytes of a frame
-    # (1.303 GB of weights + 114 688 B of K/V per cached position) / measured frame time.
-    sp = eng._sampling(0.7, 0.8, 1.1, seed=7, ban_eos=True)
-    fb = frame_bytes(args)
     if os.environ.get("FT_NO_GRAPH"):
         # counter runs (rocprofv3 --pmc, profiles/README.md) launch every frame eagerly; the profiler does not survive
         # a stream capture, and the roofline block measures the captured graph: leave it out of such a run
@@ -478,42 +543,7 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    eng.prefill(prompt, sp)
-    NPF = 48
-    ms_graph, seg, nodes = eng.profile_frame(NPF, sp)
     flags = eng.engine_state()[0]
-    pos_mid = PROMPT_LEN + NPF            # mean cached positions over the profiled frames (about)
-    per_frame_bytes = fb["total"] + KV_BYTES_PER_POS * pos_mid
-    frame_ms = ms_graph / NPF
-    achieved = per_frame_bytes / (frame_ms * 1e-3) / 1e9
-    # HBM-side bytes per frame: NOT measured by this run - the newest committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
-    # over this bench with eager frames (FT_NO_GRAPH; counters and stream capture do not go together), profiles/README.md
-    traffic, traffic_source = None, None
-    for rr in ("r04", "r03", "r02"):
-        tpath = os.path.join(ROOT, "profiles", rr + "_traffic.json")
-        if os.path.exists(tpath):
-            traffic = json.load(open(tpath)).get("hbm_bytes_per_frame")
-            traffic_source = f"profiles/{rr}_traffic.json (rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE, separate passes, eager frames; not this run)"
-            break
-    parts = {}
-    for name, ms_k, nbytes in (("slow_stack", seg[0], fb["slow"] + KV_BYTES_PER_POS * pos_mid), ("head_and_draw", seg[1], fb["head"]),
-                               ("fast_loop", seg[2], fb["fast"])):
-        per = ms_k / max(NPF - 1, 1)
-        parts[name] = {"ms": round(per, 4), "algorithmic_GB": round(nbytes / 1e9, 4),
-                       "GBps": round(nbytes / (per * 1e-3) / 1e9, 1) if per > 0 else None}
-    roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-            "kernel": ("one decode frame = ft::slow_engine_kernel + vocabulary head gemv + semantic draw + ft::fast_engine_kernel"
-                       if flags == 3 else "one decode frame (launch path: gemv / attention / sampler kernels)"),
-            "launches_per_frame": nodes, "bytes_per_frame": int(per_frame_bytes), "frame_us": round(frame_ms * 1e3, 2),
-            "frame_ms": round(frame_ms, 4), "frame_path": eng.frame_path(), "parts": parts}
-    try:   # sub-field kept from round 1: the HBM-streamed GEMV launches of the launch path alone
-        ms, launches, nbytes = eng.profile_gemv(20, sp)
-        roof["gemv_launch_path"] = {"GBps": round(nbytes / (ms * 1e-3) / 1e9, 1), "launches": launches,
-                                    "avg_us_per_launch": round(ms * 1e3 / max(launches, 1), 3)}
-    except Exception as e:  # noqa: BLE001
-        print(f"[bench] gemv sub-profile skipped: {e}", file=sys.stderr)
-
     audio_s = frames_total * 2048 / 44100.0
     tok_s = frames_total / elapsed  # whole step (prefill + decode + codec) over all ranks
     out = {
@@ -529,12 +559,15 @@ def main():
         "ar_tokens_per_s": round(frames_total / (ar_max if world > 1 else ar_s), 2),
         "rtf": round(elapsed / audio_s * world, 5) if codec is not None else None,
         "codec_ms_per_step": round(cod_s / a.steps * 1e3, 3) if codec is not None else None,
-        "roofline": roof,
+        "roofline": None,
     }
-    # ---- extras, outside the timed region and never part of `value`, each with its own wall clock and frame count:
-    # BASELINE configs[2] (32 slots, mixed lengths, continuous batching) and configs[4] (voice cloning, B = 8, streamed)
+    # ---- --full: the frame roofline and extras, outside the timed region and never part of `value`, each with its own
+    # wall clock and frame count: BASELINE configs[2] (32 slots, mixed lengths, continuous batching) and configs[4]
+    # (voice cloning, B = 8, streamed), the CPU baseline
+    if a.full:
+        out["roofline"], out["config"]["frame_engine"] = frame_roofline(eng, args, prompt)
     out["configs"] = {}
-    if world == 1 and not a.no_batch_probe:
+    if a.full and world == 1 and not a.no_batch_probe:
         try:
             eng.close()
             margs = s1_mini_args(max_seq_len=4096)
@@ -571,7 +604,7 @@ def main():
             out["configs"]["configs[4] voice cloning B=8 streamed"] = voice_cloning_probe(sd, tok, im_end, local_rank)
         except Exception as e:  # noqa: BLE001
             print(f"[bench] batch probes skipped: {type(e).__name__}: {e}", file=sys.stderr)
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         cpu_sd = {k: v.cpu() for k, v in sd.items()}
         out["cpu_baseline"] = cpu_baseline(args.__dict__, cpu_sd, prompt, tok, frames=a.cpu_frames)
     else:

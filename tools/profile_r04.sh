@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r04
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-batch-probe > $O/stats.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-batch-probe > $O/stats.log 2>&1 || exit 1
 echo stats done
 export FT_NO_GRAPH=1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-batch-probe > $O/fetch.log 2>&1 || exit 2
@@ -25,6 +25,6 @@ python3 tools/summarize_rocprof.py stats $O/b32 $O/b32_kernel_stats.md || exit 6
 python3 tools/summarize_rocprof.py stats $O/pf780 $O/pf780_kernel_stats.md || exit 6
 python3 tools/summarize_rocprof.py mfma $O/mfma_pf $O/pmc_mfma_prefill.md || exit 6
 python3 tools/summarize_rocprof.py traffic $O/fetch $O/write $O/traffic.md || exit 6
-python3 bench.py > $O/bench.json 2> $O/bench.err || exit 8
+python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 8
 python3 bench.py --config cfg4 --steps 3 --warmup 1 > $O/cfg4_n1.json 2> $O/cfg4.err || exit 9
 echo bench done
