@@ -3,7 +3,7 @@ feature_lengths)` (fish_tts/models/vocoder.py:906-912), on top of the C ABI."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -153,6 +153,42 @@ class CodecHipEngine:
     def stream(self) -> "CodecStream":
         """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode."""
         return CodecStream(self)
+
+    MAX_STREAMS_PER_CALL = 64     # ft_codec_stream_decode_many
+
+    def decode_streams(self, streams: Sequence["CodecStream"], chunks: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """The next chunk of each of several distinct streams of this engine, in one pass through the codec per native
+        call (ft_codec_stream_decode_many): chunks[j] (n_codebooks+1, T_j) integer -> float32 (T_j * frame_len,), bit
+        for bit what streams[j].decode(chunks[j]) gives.  More than 64 streams, or more than max_frames frames together,
+        take several calls (the streams of calls that went through stay advanced if a later one fails)."""
+        streams = list(streams)
+        chunks = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in chunks]
+        if len(streams) != len(chunks):
+            raise ValueError("decode_streams: one chunk per stream")
+        for c in chunks:
+            assert c.ndim == 2 and c.shape[0] == self.R, c.shape
+        out: List[np.ndarray] = []
+        i = 0
+        while i < len(streams):
+            j, total = i, 0
+            while j < len(streams) and j - i < self.MAX_STREAMS_PER_CALL and (j == i or total + chunks[j].shape[1] <= self.max_frames):
+                total += chunks[j].shape[1]
+                j += 1
+            group = streams[i:j]
+            lens = np.array([c.shape[1] for c in chunks[i:j]], dtype=np.int32)
+            codes = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in chunks[i:j]]))
+            handles = (C.c_void_p * len(group))(*[s._h.value for s in group])
+            audio = np.empty(int(lens.sum()) * self.frame_len, dtype=np.float32)
+            self._check(self.lib.ft_codec_stream_decode_many(self._h, len(group), handles, codes.ctypes.data_as(C.c_void_p),
+                                                             lens.ctypes.data_as(C.c_void_p), audio.ctypes.data_as(C.c_void_p)),
+                        "ft_codec_stream_decode_many")
+            off = 0
+            for s, T in zip(group, lens):
+                s.frames += int(T)
+                out.append(audio[off:off + int(T) * self.frame_len])
+                off += int(T) * self.frame_len
+            i = j
+        return out
 
     def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None) -> np.ndarray:
         """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len)."""

@@ -48,6 +48,12 @@ struct CodecState {
     bf16_t* big[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t big_elems = 0, big_margin = 0;
     int frame_len = 0, up_total = 1;
+    // batched streamed decode (ft_codec_stream_decode_many): its own conv buffers and q k v work buffer (a carried-row
+    // margin in front of every chunk) and a device table of chunks, carries and codes; allocated on its first call
+    bf16_t* mbig[4] = {nullptr, nullptr, nullptr, nullptr};
+    bf16_t* mqkv = nullptr;
+    unsigned char* mtab = nullptr;
+    int mcarry = 0;           // carries per stream (convolution tails + one K/V per transformer layer)
     // ---- encode side
     struct EncUnit { float *a0, *a2; ConvW c7, c1; };
     struct EncBlock { EncUnit u[3]; float* a3; ConvW sc; int s, cin, cout; std::vector<TfLayer> tf; float* tf_norm = nullptr; };
@@ -528,6 +534,9 @@ struct GemmIO {
     long msel = 0;     // rows the kernel VARIANT is chosen for (0 = M): a streamed decode picks, for every chunk length, the variant
                        // a whole utterance of nominal length takes, so that its results do not depend on the chunking
     int t_min = 0;     // TapGemmP::t_min
+    // batched streamed decode: nz chunks on blockIdx.z (TapGemmP::seg); M / T_in are then the longest chunk's rows
+    const int4* seg = nullptr;
+    int nz = 1, seg_m = 1, seg_xg = 0, seg_og = 0;
 };
 
 static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
@@ -537,6 +546,7 @@ static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
     p.M = io.M; p.N = w.N; p.K = w.K; p.bias = w.bias; p.n_mod = w.n_mod; p.act = io.act; p.gamma = io.gamma;
     p.resid_f32 = io.resid_f32; p.resid_bf = io.resid_bf; p.ldr = io.ldr; p.out_f32 = io.out_f32; p.out_bf = io.out_bf;
     p.out_act = io.out_act; p.alpha = io.alpha; p.ldo = io.ldo; p.t_min = io.t_min;
+    p.seg = io.seg; p.seg_m = io.seg_m; p.seg_xg = io.seg_xg; p.seg_og = io.seg_og;
     const long Msel = io.msel > 0 ? io.msel : io.M;
     int halo = 0;
     for (int i = 0; i < w.ntap; ++i) halo = std::max(halo, -w.offs[i]);
@@ -549,12 +559,12 @@ static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
     if (w.ntap == 1 && w.offs[0] == 0 && Msel <= skinny_m && w.N <= skinny_n && io.T_in >= io.M && w.K % 128 == 0 && w.N % 2 == 0 &&
         (io.act == ACT_NONE || io.act == ACT_SWIGLU || io.act == ACT_GELU) && !io.out_act) {
         p.ldw = 0;
-        skinny_gemm_launch<4>(p, (io.M + 63) / 64, st);
+        skinny_gemm_launch<4>(p, (io.M + 63) / 64, st, io.nz);
         return;
     }
     if (w.K % 32 == 0 && halo <= 56) {  // pipelined kernel: A stripe shared by the taps, B double-buffered
 #define FT_TG(BM_, BN_, BK_)                                                                                   \
-    tapgemm64_kernel<BM_, BN_, BK_><<<dim3((io.M + BM_ - 1) / BM_, (w.N + BN_ - 1) / BN_, 1), 256,              \
+    tapgemm64_kernel<BM_, BN_, BK_><<<dim3((io.M + BM_ - 1) / BM_, (w.N + BN_ - 1) / BN_, io.nz), 256,          \
                                       std::max((size_t)((BM_ + 56) + 2 * BN_) * (BK_ + 8) * 2,                  \
                                                (size_t)(BM_ / 2) * (BN_ + 4) * 4), st>>>(p)
         // 64-row tiles on 4 waves below 4096 rows: the 4-wave 128 x 128 instantiation spills registers and, at these sizes,
@@ -570,7 +580,7 @@ static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
         static DevOnce once8_;                                                                                    \
         once8_.run([] { hipFuncSetAttribute((const void*)tapgemm64_kernel<BM_, BN_, BK_, NWM_, NWN_>,             \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8_); });          \
-        tapgemm64_kernel<BM_, BN_, BK_, NWM_, NWN_><<<dim3((io.M + BM_ - 1) / BM_, (w.N + BN_ - 1) / BN_, 1),     \
+        tapgemm64_kernel<BM_, BN_, BK_, NWM_, NWN_><<<dim3((io.M + BM_ - 1) / BM_, (w.N + BN_ - 1) / BN_, io.nz), \
                                                       64 * NWM_ * NWN_, lds8_, st>>>(p);                          \
     } while (0)
         constexpr long tile8_m = 4096, wide_m = 30000;
@@ -593,10 +603,10 @@ static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
         }
 #undef FT_TG
     } else if (w.N >= 128) {
-        const dim3 grid((io.M + 127) / 128, (w.N + 127) / 128, 1);
+        const dim3 grid((io.M + 127) / 128, (w.N + 127) / 128, io.nz);
         tapgemm_kernel<128, 128, 2, 2><<<grid, 256, 0, st>>>(p);
     } else {
-        const dim3 grid((io.M + 127) / 128, (w.N + 63) / 64, 1);
+        const dim3 grid((io.M + 127) / 128, (w.N + 63) / 64, io.nz);
         tapgemm_kernel<128, 64, 4, 1><<<grid, 256, 0, st>>>(p);
     }
 }
@@ -732,7 +742,8 @@ extern "C" ft_status ft_codec_stream_begin(ft_ctx* ctx, ft_codec_stream** out) {
         void* v = nullptr;
         if (hipMalloc(&v, n * sizeof(bf16_t) + 64) != hipSuccess) return false;
         sc->owned.push_back(v);
-        if (hipMemset(v, 0, n * sizeof(bf16_t) + 64) != hipSuccess) return false;
+        // on the codec's own (non-blocking) stream: a null-stream memset is not ordered before this context's kernels
+        if (hipMemsetAsync(v, 0, n * sizeof(bf16_t) + 64, s->stream) != hipSuccess) return false;
         *q = (bf16_t*)v;
         return true;
     };
@@ -757,6 +768,7 @@ extern "C" ft_status ft_codec_stream_begin(ft_ctx* ctx, ft_codec_stream** out) {
     }
     tail(6, s->c_last);
     for (const auto& t : sc->tails) ok = ok && (size_t)t.H * t.C <= s->big_margin && t.C % 8 == 0;
+    ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
     if (!ok) {
         for (void* v : sc->owned) hipFree(v);
         delete sc;
@@ -803,6 +815,198 @@ extern "C" void ft_codec_stream_end(ft_ctx* ctx, ft_codec_stream* sc) {
             if (s->streams[i] == sc) { s->streams.erase(s->streams.begin() + (long)i); break; }
     }
     delete sc;
+}
+
+// ---- batched streamed decode (ft_codec_stream_decode_many): one chunk of each of n streams in one pass through the
+// codec.  Chunk j holds frames [P_j, P_j + L_j) of the call (P_j = L_0 + .. + L_{j-1}).  The transformer runs on compact
+// rows (its norms and linears are per row, the window attention per (query, head)); the q k v work buffer leaves W1 rows
+// in front of every chunk for its carried K/V, every convolution buffer MANY_GAP rows for its carried halo rows.  The
+// kernels take their chunk from blockIdx.z (TapGemmP::seg, SegZ) and run the arithmetic of ft_codec_stream_decode: the
+// variants of the nominal utterance (msel), the same K split and reduction order; only grid extents and row bases change.
+// Launches per call do not depend on n.
+constexpr int MANY_MAX_STREAMS = 64;
+constexpr int MANY_GAP = 64;    // rows in front of every chunk at every convolution stage (largest halo: 54 rows)
+
+static size_t many_seg_bytes() { return (size_t)MANY_MAX_STREAMS * sizeof(int4); }
+static size_t many_carry_bytes(int ncarry) { return (size_t)MANY_MAX_STREAMS * ncarry * 2 * sizeof(bf16_t*); }
+
+// The workspace of the batched decode (see fishtts_hip.h for its size), allocated once.
+static ft_status many_alloc(ft_ctx* ctx, int ncarry) {
+    const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
+    if (s->mtab) return FT_OK;
+    const int D = c.latent_dim, HD = c.tf_n_head * c.tf_head_dim, W1 = std::max(c.tf_window - 1, 0);
+    // widest row of a convolution-stage buffer: the ConvNeXt hidden (4 D), the decoder input (decoder_dim)
+    const size_t cmax = std::max({(size_t)4 * D, (size_t)c.decoder_dim, (size_t)D});
+    const size_t big = s->big_elems + (size_t)MANY_GAP * (MANY_MAX_STREAMS - 1) * cmax;
+    bf16_t* b[4];
+    for (int i = 0; i < 4; ++i) FT_TRY(cmalloc(ctx, &b[i], big + s->big_margin));
+    bf16_t* q = nullptr;
+    FT_TRY(cmalloc(ctx, &q, ((size_t)c.max_frames + (size_t)MANY_MAX_STREAMS * W1) * 3 * HD));
+    unsigned char* t = nullptr;
+    FT_TRY(cmalloc(ctx, &t, many_seg_bytes() + many_carry_bytes(ncarry) + (size_t)(c.n_codebooks + 1) * c.max_frames * sizeof(int)));
+    for (int i = 0; i < 4; ++i) s->mbig[i] = b[i] + s->big_margin;
+    s->mqkv = q;
+    s->mcarry = ncarry;
+    s->mtab = t;    // last: after a failed allocation the workspace stays unset (what was allocated goes with the context)
+    return FT_OK;
+}
+
+static ft_status decode_many(ft_ctx* ctx, int n, ft_codec_stream* const* scs, const int32_t* codes_host, const int32_t* lens,
+                             float* audio_host) {
+    const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    const int D = c.latent_dim, H = c.tf_n_head, hd = c.tf_head_dim, HD = H * hd, R = c.n_codebooks + 1;
+    const long Tn = STREAM_NOMINAL_FRAMES;
+    const int W1 = c.tf_window - 1;
+    const int ntail = (int)scs[0]->tails.size(), ncarry = ntail + c.n_tf_layer;
+    FT_TRY(many_alloc(ctx, ncarry));
+    if (s->mcarry != ncarry) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: carry count out of step");
+    // host side of the device table: chunks {P, L, t0, nh}, carries [n][ncarry][read, write], codes [R][sum L]
+    std::vector<int> P(n + 1, 0);
+    int Lmax = 0;
+    for (int j = 0; j < n; ++j) {
+        P[j + 1] = P[j] + lens[j];
+        Lmax = std::max(Lmax, (int)lens[j]);
+    }
+    const int Ts = P[n];
+    const size_t seg_b = many_seg_bytes(), car_b = many_carry_bytes(ncarry);
+    std::vector<unsigned char> tab(seg_b + car_b + (size_t)R * Ts * sizeof(int));
+    int4* seg = reinterpret_cast<int4*>(tab.data());
+    bf16_t** car = reinterpret_cast<bf16_t**>(tab.data() + seg_b);
+    int* hc = reinterpret_cast<int*>(tab.data() + seg_b + car_b);
+    for (int j = 0; j < n; ++j) {
+        const ft_codec_stream* sc = scs[j];
+        seg[j] = make_int4(P[j], lens[j], sc->t0, std::min(sc->t0, W1));
+        bf16_t** cj = car + (size_t)j * ncarry * 2;
+        for (int i = 0; i < ntail; ++i) { cj[2 * i] = sc->tails[i].buf[sc->par]; cj[2 * i + 1] = sc->tails[i].buf[sc->par ^ 1]; }
+        for (int l = 0; l < c.n_tf_layer; ++l) {
+            cj[2 * (ntail + l)] = sc->kv[sc->par][l];
+            cj[2 * (ntail + l) + 1] = sc->kv[sc->par ^ 1][l];
+        }
+        const int32_t* src = codes_host + (size_t)R * P[j];
+        for (int r = 0; r < R; ++r) memcpy(hc + (size_t)r * Ts + P[j], src + (size_t)r * lens[j], lens[j] * sizeof(int));
+    }
+    FT_HIP(ctx, hipMemcpyAsync(s->mtab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
+    const int4* segd = reinterpret_cast<const int4*>(s->mtab);
+    bf16_t* const* card = reinterpret_cast<bf16_t* const*>(s->mtab + seg_b);
+    const int* codes_d = reinterpret_cast<const int*>(s->mtab + seg_b + car_b);
+    auto Z = [&](int m, int g, int ci = 0) {
+        SegZ z;
+        z.seg = segd; z.carry = card; z.ncarry = ncarry; z.ci = ci; z.m = m; z.g = g;
+        return z;
+    };
+    // a GEMM over the chunks: m rows per frame, xg / og gap rows in front of every chunk of X / of the output
+    auto seg_io = [&](GemmIO& io, int m, int xg, int og) {
+        io.T_in = io.M = Lmax * m;
+        io.seg = segd; io.nz = n; io.seg_m = m; io.seg_xg = xg; io.seg_og = og;
+    };
+    int ti = 0;                                               // next carried convolution tail (the order of decode_one)
+    auto roll = [&](bf16_t* x, int m, int Hh, int C) {
+        if (Hh == 0) return 0;
+        tail_roll_kernel<<<dim3(gridfor((long)Hh * C / 8), 1, n), 256, 0, st>>>(x, nullptr, nullptr, 0, Hh, C, Z(m, MANY_GAP, ti++));
+        return -Hh;
+    };
+    RvqP rq{codes_d, s->tables, c.n_codebooks, c.semantic_codebook_size, c.codebook_size, D, Ts, s->x};
+    rvq_gather_kernel<<<dim3(Ts, 1), 256, 0, st>>>(rq);
+    // post transformer on compact rows; chunk z's q k v rows start at P_z + z * W1 of qkv_c (its carried K/V in front)
+    bf16_t* qkv_c = s->mqkv + (size_t)W1 * 3 * HD;
+    for (int l = 0; l < c.n_tf_layer; ++l) {
+        const TfLayer& t = s->tf[l];
+        rmsnorm_rows_kernel<<<Ts, 256, 0, st>>>(RowNormP{s->x, t.n1, c.tf_norm_eps, D, s->xn, nullptr});
+        { GemmIO io{s->xn, D, 0, 0}; io.out_bf = qkv_c; io.ldo = 3 * HD; io.msel = Tn; seg_io(io, 1, 0, W1); gemm(st, t.qkv, io); }
+        rope_qk_kernel<<<dim3(gridfor((long)Lmax * 2 * H * (hd / 2)), 1, n), 256, 0, st>>>(qkv_c, s->rope, Lmax, H, hd, 0, Z(1, W1));
+        if (W1 > 0) {
+            kv_carry_in_kernel<<<dim3(gridfor((long)W1 * 2 * HD / 8), 1, n), 256, 0, st>>>(qkv_c, nullptr, 0, W1, HD, Z(1, W1, ntail + l));
+            kv_carry_out_kernel<<<dim3(gridfor((long)W1 * 2 * HD / 8), 1, n), 256, 0, st>>>(qkv_c, nullptr, 0, 0, W1, HD, Z(1, W1, ntail + l));
+        }
+        window_attn_kernel<<<dim3((Lmax * H + 3) / 4, 1, n), 256, 0, st>>>(
+            WinAttnP{qkv_c, s->y, 0, H, hd, c.tf_window, 1.0f / sqrtf((float)hd), 0, Z(1, W1)});
+        { GemmIO io{s->y, HD, Ts, Ts}; io.gamma = t.g1; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm(st, t.wo, io); }
+        rmsnorm_rows_kernel<<<Ts, 256, 0, st>>>(RowNormP{s->x, t.n2, c.tf_norm_eps, D, s->xn, nullptr});
+        { GemmIO io{s->xn, D, Ts, Ts}; io.act = ACT_SWIGLU; io.out_bf = s->g; io.ldo = c.tf_ffn; io.msel = Tn; gemm(st, t.w13, io); }
+        { GemmIO io{s->g, c.tf_ffn, Ts, Ts}; io.gamma = t.g2; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm(st, t.w2, io); }
+    }
+    bf16_t *z = s->mbig[0], *u = s->mbig[1], *nb = s->mbig[2], *h = s->mbig[3];
+    rmsnorm_rows_kernel<<<Ts, 256, 0, st>>>(RowNormP{s->x, s->tf_norm, c.tf_norm_eps, D, z, nullptr});
+    int m = 1, xg = 0;                                        // rows per frame; gap rows of the input (compact after the transformer)
+    long Tnc = Tn;
+    for (const UpStage& us : s->up) {
+        { GemmIO io{z, D, 0, 0}; io.out_bf = u; io.ldo = us.ct.N; io.msel = Tnc; seg_io(io, m, xg, MANY_GAP / us.f); gemm(st, us.ct, io); }
+        m *= us.f;
+        Tnc *= us.f;
+        xg = MANY_GAP;
+        DwLnP dp{u, us.dw_w, us.dw_b, us.ln_w, us.ln_b, Lmax * m, D, nb, roll(u, m, 6, D)};
+        dp.z = Z(m, MANY_GAP);
+        dwconv_ln_kernel<<<dim3(Lmax * m, 1, n), 256, D * sizeof(float), st>>>(dp);
+        { GemmIO io{nb, D, 0, 0}; io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; io.msel = Tnc; seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, us.pw1, io); }
+        { GemmIO io{h, 4 * D, 0, 0}; io.gamma = us.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D; io.msel = Tnc;
+          seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, us.pw2, io); }
+    }
+    bf16_t *a = u, *r = nb, *hs = h, *a2 = z;
+    { GemmIO io{z, D, 0, 0}; io.out_act = a; io.alpha = s->blocks[0].a0; io.ldo = c.decoder_dim; io.msel = Tnc;
+      io.t_min = roll(z, m, halo_of(s->conv_in), D); seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, s->conv_in, io); }
+    for (size_t bi = 0; bi < s->blocks.size(); ++bi) {
+        const DecBlock& b = s->blocks[bi];
+        { GemmIO io{a, b.cin, 0, 0}; io.out_bf = r; io.out_act = a2; io.alpha = b.u[0].a0; io.ldo = b.ct.N; io.msel = Tnc;
+          io.t_min = roll(a, m, halo_of(b.ct), b.cin); seg_io(io, m, MANY_GAP, MANY_GAP / b.s); gemm(st, b.ct, io); }
+        m *= b.s;
+        Tnc *= b.s;
+        for (int ui = 0; ui < 3; ++ui) {
+            const ResUnitW& ru = b.u[ui];
+            { GemmIO io{a2, b.cout, 0, 0}; io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cout; io.msel = Tnc;
+              io.t_min = roll(a2, m, halo_of(ru.c7), b.cout); seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, ru.c7, io); }
+            const float* next_alpha = ui < 2 ? b.u[ui + 1].a0 : (bi + 1 < s->blocks.size() ? s->blocks[bi + 1].a0 : s->a_last);
+            bf16_t* act_dst = ui < 2 ? a2 : a;
+            { GemmIO io{hs, b.cout, 0, 0}; io.resid_bf = r; io.ldr = b.cout; io.out_bf = ui < 2 ? r : nullptr;
+              io.out_act = act_dst; io.alpha = next_alpha; io.ldo = b.cout; io.msel = Tnc; seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, ru.c1, io); }
+        }
+    }
+    // m = frame_len here: chunk z's samples land at P_z * frame_len, the chunks back to back as the caller wants them
+    FinalConvP fp{a, s->w_last, s->b_last, Lmax * m, s->c_last, s->audio, roll(a, m, 6, s->c_last)};
+    fp.z = Z(m, MANY_GAP);
+    final_conv_tanh_kernel<<<dim3(std::max(16, 2048 / n), 1, n), 256, 0, st>>>(fp);
+    FT_HIP(ctx, hipMemcpyAsync(audio_host, s->audio, (size_t)Ts * s->frame_len * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("codec launch: ") + hipGetErrorString(e));
+    if (ti != ntail) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: carry bookkeeping out of step");
+    for (int j = 0; j < n; ++j) {
+        scs[j]->t0 += lens[j];
+        scs[j]->par ^= 1;
+    }
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
+                                                 const int32_t* lens, float* audio) {
+    if (!ctx) return FT_ERR_ARG;
+    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    if (n < 1 || !streams || !codes || !lens || !audio) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: bad argument");
+    if (n > MANY_MAX_STREAMS) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many: more than 64 streams in one call");
+    const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
+    if (s->up.empty()) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many: needs an up-sampling stage");
+    for (const DecBlock& b : s->blocks)
+        if (MANY_GAP % b.s) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many: decoder rates must divide 64");
+    long total = 0;
+    for (int j = 0; j < n; ++j) {
+        const ft_codec_stream* sc = streams[j];
+        if (!sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: null stream");
+        if (lens[j] < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: a chunk of less than one frame");
+        if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: a stream belongs to another (or a destroyed) context");
+        for (int i = 0; i < j; ++i)
+            if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: a stream named twice");
+        if (lens[j] > c.max_frames || sc->t0 + lens[j] > c.max_frames)
+            return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many: stream longer than max_frames (rope table)");
+        total += lens[j];
+    }
+    if (total > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many: chunks longer than max_frames together");
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    return decode_many(ctx, n, streams, codes, lens, audio);
 }
 
 extern "C" ft_status ft_codec_decode(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,

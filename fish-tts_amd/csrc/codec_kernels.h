@@ -52,9 +52,59 @@ struct TapGemmP {
     float* ss_out;
     int ss_nblk, ss_ld;
     float eps;
+    // batched streamed decode (ft_codec_stream_decode_many): blockIdx.z is one stream's chunk, seg[z] = {P, L, t0, nh}
+    // (SegZ).  The chunk has M = T_in = L * seg_m rows; its X rows start at P * seg_m + z * seg_xg, its output and
+    // residual rows at P * seg_m + z * seg_og (the gap rows between chunks hold carried halo rows).  null: one item.
+    const int4* seg;
+    int seg_m, seg_xg, seg_og;
     // (measured and removed: the RMSNorm of the OUTPUT rows by the block that finishes last - write-through stores, a
     // returning ticket atomic and the last block's trip to the memory side cost more than the ~5 us norm launch they
     // replaced: 4.67 against 3.54 ms per 32-row frame)
+};
+
+// The chunk of blockIdx.z in a batched streamed decode (the skinny kernel): M, T_in and the row bases of X / residual /
+// outputs become the chunk's, so the per-element arithmetic is that of the same chunk decoded alone.  false: the block
+// lies past the chunk.
+__device__ __forceinline__ bool tap_segment(TapGemmP& p, int m0) {
+    if (!p.seg) return true;
+    const int4 s = p.seg[blockIdx.z];
+    p.M = p.T_in = s.y * p.seg_m;
+    if (m0 >= p.M) return false;
+    const long xr = (long)s.x * p.seg_m + (long)blockIdx.z * p.seg_xg;
+    const long orow = (long)s.x * p.seg_m + (long)blockIdx.z * p.seg_og;
+    p.X += xr * p.ldx;
+    if (p.resid_f32) p.resid_f32 += orow * p.ldr;
+    if (p.resid_bf) p.resid_bf += orow * p.ldr;
+    if (p.out_f32) p.out_f32 += orow * p.ldo;
+    if (p.out_bf) p.out_bf += orow * p.ldo;
+    if (p.out_act) p.out_act += orow * p.ldo;
+    return true;
+}
+
+// The tap kernels keep p as it came (their lambdas capture it by reference: a modified copy lands in scratch) and read
+// the item's rows and row bases from here: one batch item b (x / r / o_bstride) or the chunk of blockIdx.z (seg).
+struct TapSeg { int M, T_in; size_t xo, ro, oo; };
+__device__ __forceinline__ TapSeg tap_seg(const TapGemmP& p, int b) {
+    if (!p.seg) return TapSeg{p.M, p.T_in, (size_t)b * p.x_bstride, (size_t)b * p.r_bstride, (size_t)b * p.o_bstride};
+    const int4 s = p.seg[blockIdx.z];
+    const long xr = (long)s.x * p.seg_m + (long)blockIdx.z * p.seg_xg;
+    const long orow = (long)s.x * p.seg_m + (long)blockIdx.z * p.seg_og;
+    const int M = s.y * p.seg_m;
+    return TapSeg{M, M, (size_t)(xr * p.ldx), (size_t)(orow * p.ldr), (size_t)(orow * p.ldo)};
+}
+
+// The same for the row kernels of a batched streamed decode: seg[blockIdx.z] = {P, L, t0, nh} (frames [P, P + L) of the
+// call, rope position t0, nh carried K/V rows); at a stage of m rows per frame the chunk's rows start at P * m + z * g.
+// carry[(z * ncarry + ci) * 2 + {0, 1}]: the carry this chunk reads and the one it leaves for the next chunk.
+struct SegZ {
+    const int4* seg = nullptr;       // null: one item (the plain launch)
+    bf16_t* const* carry = nullptr;
+    int ncarry = 0, ci = 0;
+    int m = 1, g = 0;
+    __device__ __forceinline__ int4 get() const { return seg[blockIdx.z]; }
+    __device__ __forceinline__ long row0(const int4& s) const { return (long)s.x * m + (long)blockIdx.z * g; }
+    __device__ __forceinline__ bf16_t* carry_in() const { return carry[((long)blockIdx.z * ncarry + ci) * 2]; }
+    __device__ __forceinline__ bf16_t* carry_out() const { return carry[((long)blockIdx.z * ncarry + ci) * 2 + 1]; }
 };
 
 // offs[] lives in the kernel arguments: a runtime index would force the whole struct into scratch
@@ -75,7 +125,7 @@ __device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erf
 
 template <int TM, int TN>
 __device__ __forceinline__ void tapgemm_epilogue(const TapGemmP& p, f32x4 (&acc)[TM][TN], const int mw, const int nw,
-                                                 const int b, const int fr, const int fq) {
+                                                 const TapSeg& ts, const int fr, const int fq) {
     // epilogue: lane holds C[row = 4*fq + r][col = fr] of each 16x16 tile
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -93,25 +143,25 @@ __device__ __forceinline__ void tapgemm_epilogue(const TapGemmP& p, f32x4 (&acc)
                 if (p.act == ACT_SWIGLU) {
                     // columns (2i, 2i+1) = (gate, up): partner value sits in the neighbouring lane
                     const float other = dpp_f<DPP_XOR1>(v);
-                    if ((fr & 1) == 0 && nv && t < p.M) {
+                    if ((fr & 1) == 0 && nv && t < ts.M) {
                         const float gate = v, up = other;
                         float sg = gate / (1.0f + expf(-gate));
                         if (p.round_lin) sg = round_bf16(sg);
                         const float o = sg * up;
-                        const size_t oi = (size_t)b * p.o_bstride + (size_t)t * p.ldo + (n >> 1);
+                        const size_t oi = ts.oo + (size_t)t * p.ldo + (n >> 1);
                         if (p.out_bf) p.out_bf[oi] = f32_to_bf16_bits(o);
                         if (p.out_f32) p.out_f32[oi] = p.round_f32_out ? round_bf16(o) : o;
                     }
                     continue;
                 }
-                if (!nv || t >= p.M) continue;
+                if (!nv || t >= ts.M) continue;
                 if (p.act == ACT_GELU) v = gelu_f(v);
                 else if (p.act == ACT_TANH) v = tanhf(v);
                 if (p.gamma) v *= p.gamma[nm];
-                const size_t ri = (size_t)b * p.r_bstride + (size_t)t * p.ldr + n;
+                const size_t ri = ts.ro + (size_t)t * p.ldr + n;
                 if (p.resid_f32) v += p.resid_f32[ri];
                 if (p.resid_bf) v += bf16_bits_to_f32(p.resid_bf[ri]);
-                const size_t oi = (size_t)b * p.o_bstride + (size_t)t * p.ldo + n;
+                const size_t oi = ts.oo + (size_t)t * p.ldo + n;
                 if (p.out_f32) p.out_f32[oi] = p.round_f32_out ? round_bf16(v) : v;
                 if (p.out_bf) p.out_bf[oi] = f32_to_bf16_bits(v);
                 if (p.out_act) p.out_act[oi] = f32_to_bf16_bits(snake_f(v, p.alpha[nm]));
@@ -132,8 +182,10 @@ __global__ __launch_bounds__(256) void tapgemm_kernel(TapGemmP p) {
     __shared__ __attribute__((aligned(16))) bf16_t Bs[BN * LDS_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, b = blockIdx.z;
-    const bf16_t* X = p.X + (size_t)b * p.x_bstride;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, b = p.seg ? 0 : blockIdx.z;
+    const TapSeg ts = tap_seg(p, b);
+    if (m0 >= ts.M) return;
+    const bf16_t* X = p.X + ts.xo;
     f32x4 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -149,7 +201,7 @@ __global__ __launch_bounds__(256) void tapgemm_kernel(TapGemmP p) {
                 const int r = c >> 2, q = c & 3;
                 const int t = m0 + r + off;
                 U4 v = U4{0u, 0u, 0u, 0u};
-                if (m0 + r < p.M && t >= p.t_min && t < p.T_in)
+                if (m0 + r < ts.M && t >= p.t_min && t < ts.T_in)
                     v = *reinterpret_cast<const U4*>(X + (size_t)t * p.ldx + k0 + q * 8);
                 *reinterpret_cast<U4*>(&As[r * LDS_LD + q * 8]) = v;
             }
@@ -175,7 +227,7 @@ __global__ __launch_bounds__(256) void tapgemm_kernel(TapGemmP p) {
             __syncthreads();
         }
     }
-    tapgemm_epilogue<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, b, fr, fq);
+    tapgemm_epilogue<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, ts, fr, fq);
 }
 
 // Epilogue through LDS: the accumulators (column-per-lane) are transposed so that each lane finishes 8 consecutive
@@ -183,7 +235,7 @@ __global__ __launch_bounds__(256) void tapgemm_kernel(TapGemmP p) {
 // bandwidth-bound: 2-byte scattered stores were the bottleneck).  NWM passes of BM/NWM rows.
 template <int BM, int BN, int TM, int TN, int NWM = 2, int NWN = 2>
 __device__ __forceinline__ void tapgemm_epilogue_lds(const TapGemmP& p, f32x4 (&acc)[TM][TN], float* Cs, const int m0,
-                                                     const int n0, const int b, const int wm, const int wn,
+                                                     const int n0, const TapSeg& ts, const int wm, const int wn,
                                                      const int fr, const int fq) {
     constexpr int LDC = BN + 4;
     constexpr int WM = BM / NWM, WN = BN / NWN;
@@ -205,7 +257,7 @@ __device__ __forceinline__ void tapgemm_epilogue_lds(const TapGemmP& p, f32x4 (&
         for (int v = tid; v < WM * (BN / 8); v += NTHR) {
             const int row = v / (BN / 8), c8 = (v % (BN / 8)) * 8;
             const int t = m0 + pass * WM + row, n = n0 + c8;
-            if (t >= p.M || n >= p.N) continue;
+            if (t >= ts.M || n >= p.N) continue;
             const int nm = n % p.n_mod;
             float x[8];
             const float4 c0 = *reinterpret_cast<const float4*>(&Cs[row * LDC + c8]);
@@ -230,7 +282,7 @@ __device__ __forceinline__ void tapgemm_epilogue_lds(const TapGemmP& p, f32x4 (&
 #pragma unroll
                 for (int j = 0; j < 8; ++j) x[j] *= p.gamma[nm + j];
             }
-            const size_t ri = (size_t)b * p.r_bstride + (size_t)t * p.ldr + n;
+            const size_t ri = ts.ro + (size_t)t * p.ldr + n;
             if (p.resid_f32) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) x[j] += p.resid_f32[ri + j];
@@ -241,7 +293,7 @@ __device__ __forceinline__ void tapgemm_epilogue_lds(const TapGemmP& p, f32x4 (&
 #pragma unroll
                 for (int j = 0; j < 8; ++j) x[j] += rv[j];
             }
-            const size_t oi = (size_t)b * p.o_bstride + (size_t)t * p.ldo + n;
+            const size_t oi = ts.oo + (size_t)t * p.ldo + n;
             if (p.out_f32) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) p.out_f32[oi + j] = p.round_f32_out ? round_bf16(x[j]) : x[j];
@@ -292,8 +344,10 @@ __global__ __launch_bounds__(64 * NWM * NWN) void tapgemm64_kernel(TapGemmP p) {
     bf16_t* Bs1 = Bs0 + BN * LD;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / NWN, wn = wave % NWN;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, b = blockIdx.z;
-    const bf16_t* X = p.X + (size_t)b * p.x_bstride;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, b = p.seg ? 0 : blockIdx.z;
+    const TapSeg ts = tap_seg(p, b);
+    if (m0 >= ts.M) return;
+    const bf16_t* X = p.X + ts.xo;
     int offmin = 0;
 #pragma unroll
     for (int t = 0; t < 8; ++t) offmin = (t < p.ntap) ? min(offmin, p.offs[t]) : offmin;
@@ -335,7 +389,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void tapgemm64_kernel(TapGemmP p) {
         for (int u = 0; u < ACH; ++u) {
             const int c = tid + NTHR * u, r = c / QPR, q = c % QPR;
             const int t = m0 + offmin + r;
-            areg[u] = (c < srows * QPR && t >= p.t_min && t < p.T_in)
+            areg[u] = (c < srows * QPR && t >= p.t_min && t < ts.T_in)
                           ? *reinterpret_cast<const U4*>(X + (size_t)t * p.ldx + kc * BK + q * 8) : U4{0u, 0u, 0u, 0u};
         }
     };
@@ -385,10 +439,10 @@ __global__ __launch_bounds__(64 * NWM * NWN) void tapgemm64_kernel(TapGemmP p) {
     if constexpr (TM * TN >= 16) {
         // 128x128: instantiating the lane epilogue here makes the compiler keep all 16 accumulator tiles in scratch for
         // the whole kernel (272 B/lane); the host selects this tile only for layers the vector epilogue covers
-        tapgemm_epilogue_lds<BM, BN, TM, TN, NWM, NWN>(p, acc, reinterpret_cast<float*>(lds), m0, n0, b, wm, wn, fr, fq);
+        tapgemm_epilogue_lds<BM, BN, TM, TN, NWM, NWN>(p, acc, reinterpret_cast<float*>(lds), m0, n0, ts, wm, wn, fr, fq);
     } else {
-        if (vec_ok) tapgemm_epilogue_lds<BM, BN, TM, TN, NWM, NWN>(p, acc, reinterpret_cast<float*>(lds), m0, n0, b, wm, wn, fr, fq);
-        else tapgemm_epilogue<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, b, fr, fq);
+        if (vec_ok) tapgemm_epilogue_lds<BM, BN, TM, TN, NWM, NWN>(p, acc, reinterpret_cast<float*>(lds), m0, n0, ts, wm, wn, fr, fq);
+        else tapgemm_epilogue<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, ts, fr, fq);
     }
 }
 
@@ -475,8 +529,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, MINW) void lingemm_kernel(TapGemmP 
         }
     }
     const bool vec_ok = p.act != ACT_SWIGLU && (p.N % 8) == 0 && (p.n_mod % 8) == 0 && (p.ldo % 8) == 0 && (p.ldr % 8) == 0;
-    if (vec_ok) tapgemm_epilogue_lds<BM, BN, TM, TN, NWM, NWN>(p, acc, reinterpret_cast<float*>(lds), m0, n0, 0, wm, wn, fr, fq);
-    else { __syncthreads(); tapgemm_epilogue<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, 0, fr, fq); }
+    const TapSeg ts = tap_seg(p, 0);
+    if (vec_ok) tapgemm_epilogue_lds<BM, BN, TM, TN, NWM, NWN>(p, acc, reinterpret_cast<float*>(lds), m0, n0, ts, wm, wn, fr, fq);
+    else { __syncthreads(); tapgemm_epilogue<TM, TN>(p, acc, m0 + wm * WM, n0 + wn * WN, ts, fr, fq); }
 }
 template <int BM, int BN, int NWM>
 constexpr size_t lingemm_lds_bytes() {
@@ -727,6 +782,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_kernel(TapGemmP p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fq = lane >> 4;
     const int n0 = blockIdx.x * 16, m0 = blockIdx.y * (16 * TS);
+    if (!tap_segment(p, m0)) return;
     const int kw = wave * kper;
     const int nch = kper / (32 * CH);
     const int rem = (kper / 32) % CH;              // k-steps of a last partial chunk
@@ -911,8 +967,8 @@ static inline int skinny_waves(int N, int K, int TS) {
     return 4;
 }
 template <int TS>
-static inline void skinny_gemm_launch(const TapGemmP& p, int gy, hipStream_t st) {
-    const dim3 grid((p.N + 15) / 16, gy);
+static inline void skinny_gemm_launch(const TapGemmP& p, int gy, hipStream_t st, int gz = 1) {
+    const dim3 grid((p.N + 15) / 16, gy, gz);
     int nw = skinny_waves(p.N, p.K, TS);
     if (p.gain && TS == 4) nw = 4;   // the fused norm's extra registers: keep the 64-row variant off the spill edge
 #define FT_SK(NWV, NORMV, XV)                                                                                       \
@@ -1004,7 +1060,13 @@ static __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(RowNormP p) {
 }
 
 // ---- RoPE on the q and k thirds of a [T][3*H*hd] bf16 buffer, in place (vocoder.py:145-156)
-static __global__ void rope_qk_kernel(bf16_t* qkv, const float* tab, int T, int H, int hd, int pos0 = 0) {
+static __global__ void rope_qk_kernel(bf16_t* qkv, const float* tab, int T, int H, int hd, int pos0 = 0, SegZ z = SegZ{}) {
+    if (z.seg) {   // chunk z: its rows, its rope position
+        const int4 s = z.get();
+        qkv += z.row0(s) * 3 * H * hd;
+        T = s.y;
+        pos0 = s.z;
+    }
     const int hp = hd >> 1;
     const long n = (long)T * 2 * H * hp;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -1027,11 +1089,19 @@ struct WinAttnP {
     int T, H, hd, window;
     float scale;
     int t0;             // first query row (0; streamed decode: rows [0, t0) are the carried K/V of earlier chunks); y row = t - t0
+    SegZ z;             // batched streamed decode: chunk z's qkv rows (carried rows in front) and its compact y rows
 };
 static __global__ __launch_bounds__(256) void window_attn_kernel(WinAttnP p) {
     __shared__ float q_s[4][128];
     __shared__ float p_s[4][512];   // window <= 512 (the encoder's transformer, vocoder.py:516)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (p.z.seg) {
+        const int4 s = p.z.get();
+        p.qkv += (p.z.row0(s) - s.w) * 3 * p.H * p.hd;
+        p.y += (size_t)s.x * p.H * p.hd;
+        p.T = s.w + s.y;
+        p.t0 = s.w;
+    }
     const long item = (long)blockIdx.x * 4 + wave;
     if (item >= (long)(p.T - p.t0) * p.H) return;
     const int t = p.t0 + (int)(item / p.H), h = (int)(item % p.H);
@@ -1082,11 +1152,18 @@ struct DwLnP {
     int T, C;
     bf16_t* out;       // [T][C]
     int t_min;         // lowest readable row of x (as TapGemmP::t_min)
+    SegZ z;            // batched streamed decode: chunk z's rows of x and out
 };
 static __global__ __launch_bounds__(256) void dwconv_ln_kernel(DwLnP p) {
     __shared__ float red[8];
     extern __shared__ float ybuf[];  // [C]
     const int t = blockIdx.x;
+    if (p.z.seg) {
+        const int4 s = p.z.get();
+        if (t >= s.y * p.z.m) return;
+        p.x += p.z.row0(s) * p.C;
+        p.out += p.z.row0(s) * p.C;
+    }
     float s1 = 0.f;
     for (int c = threadIdx.x; c < p.C; c += 256) {
         float a = p.b[c];
@@ -1121,8 +1198,15 @@ struct FinalConvP {
     int T, C;
     float* audio;      // [T]
     int t_min;         // lowest readable row of xs (as TapGemmP::t_min)
+    SegZ z;            // batched streamed decode: chunk z's rows of xs; its audio at P * m (chunks back to back)
 };
 static __global__ __launch_bounds__(256) void final_conv_tanh_kernel(FinalConvP p) {
+    if (p.z.seg) {
+        const int4 s = p.z.get();
+        p.xs += p.z.row0(s) * p.C;
+        p.audio += (long)s.x * p.z.m;
+        p.T = s.y * p.z.m;
+    }
     // 16 lanes per output sample, 16 samples per block step.  C % 8 == 0 and C <= 128: lane `sub` owns channels
     // 8 sub .. 8 sub + 7 - one 16-byte load per tap and sample, its 7 x 8 weights stay in registers (the first version read
     // 2-byte elements with a 32-byte stride: 150 us for 85 MB)
@@ -1342,7 +1426,15 @@ static __global__ void snake_rows_kernel(const float* x, const float* alpha, bf1
 // A causal convolution of halo H reads rows [-H, 0) of its input: the last H rows of the input of all earlier chunks.
 // tail_roll_kernel (a) copies the carried rows in front of the chunk (x[-H .. 0)) and (b) leaves the carry of the NEXT chunk:
 // the last H rows of (carried rows ++ this chunk's T rows).  16-byte pieces; C % 8 == 0.
-static __global__ void tail_roll_kernel(bf16_t* x, const bf16_t* tail_in, bf16_t* tail_out, int T, int H, int C) {
+static __global__ void tail_roll_kernel(bf16_t* x, const bf16_t* tail_in, bf16_t* tail_out, int T, int H, int C,
+                                        SegZ z = SegZ{}) {
+    if (z.seg) {   // chunk z: its rows, its stream's carry
+        const int4 s = z.get();
+        x += z.row0(s) * C;
+        T = s.y * z.m;
+        tail_in = z.carry_in();
+        tail_out = z.carry_out();
+    }
     const int per = C / 8;
     const long n = (long)H * per;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -1358,7 +1450,14 @@ static __global__ void tail_roll_kernel(bf16_t* x, const bf16_t* tail_in, bf16_t
 // The K and V of the last nh rows before a chunk (window attention): kv_in [W1][2 * HD] -> rows [0, nh) of the qkv work
 // buffer (its k and v thirds; carried rows sit at the END of kv_in), and the carry of the next chunk from rows
 // [nh + T - nh2, nh + T) of the work buffer.  Two launches (the second reads what the GEMM wrote after the first).
-static __global__ void kv_carry_in_kernel(bf16_t* qkv, const bf16_t* kv_in, int nh, int W1, int HD) {
+// Batched (z.seg): qkv points at the row of chunk 0's first query row (SegZ rows), nh and the carry are chunk z's.
+static __global__ void kv_carry_in_kernel(bf16_t* qkv, const bf16_t* kv_in, int nh, int W1, int HD, SegZ z = SegZ{}) {
+    if (z.seg) {
+        const int4 s = z.get();
+        nh = s.w;
+        qkv += (z.row0(s) - nh) * 3 * HD;
+        kv_in = z.carry_in();
+    }
     const int per = 2 * HD / 8;
     const long n = (long)nh * per;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -1367,7 +1466,15 @@ static __global__ void kv_carry_in_kernel(bf16_t* qkv, const bf16_t* kv_in, int 
             *reinterpret_cast<const U4*>(kv_in + (size_t)(W1 - nh + r) * 2 * HD + q * 8);
     }
 }
-static __global__ void kv_carry_out_kernel(const bf16_t* qkv, bf16_t* kv_out, int rows, int nh2, int W1, int HD) {
+static __global__ void kv_carry_out_kernel(const bf16_t* qkv, bf16_t* kv_out, int rows, int nh2, int W1, int HD,
+                                           SegZ z = SegZ{}) {
+    if (z.seg) {
+        const int4 s = z.get();
+        qkv += (z.row0(s) - s.w) * 3 * HD;
+        rows = s.w + s.y;
+        nh2 = min(W1, rows);
+        kv_out = z.carry_out();
+    }
     const int per = 2 * HD / 8;
     const long n = (long)nh2 * per;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {

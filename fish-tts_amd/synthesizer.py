@@ -11,7 +11,7 @@ import time
 import wave
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Iterator, List, Literal, Optional
+from typing import Iterator, List, Literal, Optional, Tuple
 
 import numpy as np
 
@@ -250,14 +250,13 @@ class FishTTS:
             raise RuntimeError("No audio generated")
         return self._decode_to_wav(np.concatenate(codes_list, axis=1))
 
-    def synthesize_batch(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
-                         temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
-                         max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None) -> List[bytes]:
-        """Extension (BASELINE configs[2]): many texts -> WAV bytes each, decoded `max_batch` at a time in lock step
-        with refill (fish_tts_amd.batch); utterance i uses seed + i, or seeds[i] when `seeds` is given (a sharded run
-        passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
-        semantics as synthesize()."""
-        from .batch import Utterance, run_batch, run_batch_streams
+    def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
+                          repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]]):
+        """The engines and Utterances of a batch run (synthesize_batch, synthesize_batch_stream); call with _gen_lock
+        held.  More engines than the first one when batch_streams > 1 and the texts outnumber max_batch (created on first
+        use, kept); a voice's K/V prefix from the cache, spread over the engines; utterance i draws with seed + i, or
+        seeds[i]."""
+        from .batch import Utterance
         from .prompt import build_prompt_split
         assert 0 < top_p <= 1, "top_p must be in (0, 1]"
         assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
@@ -266,23 +265,35 @@ class FishTTS:
             raise ValueError("seeds must have one entry per text")
         prompt_text, prompt_tokens = self._get_prompt_data(references)
         ncb = self._engine.args.num_codebooks
+        utts = []
+        engines = [self._engine]
+        if self._batch_streams > 1 and len(texts) > self._max_batch:
+            while len(self._more_engines) < self._batch_streams - 1:      # created on first use, kept
+                self._more_engines.append(self._engine_factory())
+            engines += self._more_engines
+        for i, text in enumerate(texts):
+            enc, n_prefix = build_prompt_split(self._tokenizer, text, prompt_text, prompt_tokens, ncb)
+            if enc.shape[1] > self._engine.args.max_seq_len - 2048:
+                raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
+            prefix = None
+            if self._prefix_cache is not None and n_prefix >= self._prefix_cache.min_positions:
+                # a saved prefix lives in one engine's memory and pins its utterance there: spread them evenly
+                prefix = self._prefix_cache.get(engines[i % len(engines)], enc[:, :n_prefix])
+            utts.append(Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seeds[i] if seeds is not None else seed + i,
+                                  prefix=prefix))
+        return engines, utts
+
+    def synthesize_batch(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
+                         temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
+                         max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None) -> List[bytes]:
+        """Extension (BASELINE configs[2]): many texts -> WAV bytes each, decoded `max_batch` at a time in lock step
+        with refill (fish_tts_amd.batch); utterance i uses seed + i, or seeds[i] when `seeds` is given (a sharded run
+        passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
+        semantics as synthesize()."""
+        from .batch import run_batch, run_batch_streams
         with self._gen_lock:
-            utts = []
-            engines = [self._engine]
-            if self._batch_streams > 1 and len(texts) > self._max_batch:
-                while len(self._more_engines) < self._batch_streams - 1:      # created on first use, kept
-                    self._more_engines.append(self._engine_factory())
-                engines += self._more_engines
-            for i, text in enumerate(texts):
-                enc, n_prefix = build_prompt_split(self._tokenizer, text, prompt_text, prompt_tokens, ncb)
-                if enc.shape[1] > self._engine.args.max_seq_len - 2048:
-                    raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
-                prefix = None
-                if self._prefix_cache is not None and n_prefix >= self._prefix_cache.min_positions:
-                    # a saved prefix lives in one engine's memory and pins its utterance there: spread them evenly
-                    prefix = self._prefix_cache.get(engines[i % len(engines)], enc[:, :n_prefix])
-                utts.append(Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seeds[i] if seeds is not None else seed + i,
-                                      prefix=prefix))
+            engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
+                                                   seed, seeds)
             if len(engines) > 1:
                 run_batch_streams(engines, utts)
             else:
@@ -294,6 +305,36 @@ class FishTTS:
                 raise RuntimeError("No audio generated")
             out.append(self._decode_to_wav(codes))
         return out
+
+    def synthesize_batch_stream(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
+                                chunk_tokens: int = 20, min_first_chunk: int = 10, temperature: float = 0.7,
+                                top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
+                                seed: int = 0, seeds: Optional[List[int]] = None) -> Iterator[Tuple[int, bytes]]:
+        """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
+        PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
+        `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
+        utterances interleave as they become ready.  The codes of utterance i are those synthesize_batch decodes (same
+        engines, seeds, K/V prefixes); its PCM concatenates to one stateful streamed decode of them (CodecStream), bit
+        for bit, whatever else is in flight: the codec worker decodes every ready chunk in one batched call
+        (CodecHipEngine.decode_streams, one chunk per utterance).  Generation holds _gen_lock on its own thread;
+        abandoning the generator stops it within one burst and releases the lock (fish_tts_amd.batch_stream)."""
+        from .batch import run_batch, run_batch_streams
+        from .batch_stream import stream_utterances
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        texts = list(texts)
+
+        def run(on_frames, on_done) -> None:
+            with self._gen_lock:
+                engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty,
+                                                       max_tokens, seed, seeds)
+                if len(engines) > 1:
+                    run_batch_streams(engines, utts, on_frames=on_frames, on_done=on_done)
+                else:
+                    run_batch(self._engine, utts, on_frames=on_frames, on_done=on_done)
+
+        return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
+                                 min_first_chunk=min_first_chunk)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:

@@ -157,6 +157,19 @@ typedef struct ft_codec_stream ft_codec_stream;
 ft_status ft_codec_stream_begin(ft_ctx* ctx, ft_codec_stream** out);
 ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* st, const int32_t* codes, int32_t T, float* audio);
 void ft_codec_stream_end(ft_ctx* ctx, ft_codec_stream* st);
+/* One chunk of each of n distinct streams of this context, in ONE pass through the codec (the kernels take the chunk from
+ * the grid's z dimension: the launches do not depend on n).  codes: n blocks back to back, block j = (n_codebooks+1) x
+ * lens[j] int32 row-major (host); audio: lens[j] * frame_len float32 per stream, back to back (host).  Stream j's samples
+ * and carried state are, bit for bit, those ft_codec_stream_decode gives for the same chunk; streams may stand at
+ * different positions and chunks differ in length.  Limits: 1 <= n <= 64, lens[j] >= 1, sum(lens) <= max_frames,
+ * t0 + lens[j] <= max_frames.  Every argument is checked before any device work; a refused call changes no stream:
+ * FT_ERR_ARG (bad n, lens[j] < 1, a null pointer, a stream named twice), FT_ERR_STATE (a stream of another or a destroyed
+ * context), FT_ERR_TOO_LONG (n > 64, a stream past max_frames, sum(lens) > max_frames).  The first call allocates the
+ * batch workspace: 4 conv buffers of (max_frames x the widest per-frame row + 63 x 64 rows of max(4 latent_dim,
+ * decoder_dim)) bf16 each, a q k v buffer of (max_frames + 64 (tf_window - 1)) x 3 n_head head_dim bf16 and a table of
+ * chunks, carry pointers and codes (< 1 MB); it lives as long as the context. */
+ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
+                                      const int32_t* lens, float* audio);
 /* Codec encode = vocoder.encode(audio, lengths) of encode_reference (synthesizer.py:325-357, vocoder.py:885-904):
  * mono f32 audio at the codec sample rate (host), right-padded to whole frames -> codes (num_codebooks+1) x T'
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */
