@@ -225,6 +225,11 @@ class ARHipEngine:
         """Marks a slot idle (finished) for lock-step decoding until its next prefill."""
         self._check(self.lib.ft_ar_park(self._h, slot), "ft_ar_park")
 
+    def move_slot(self, src: int, dst: int) -> None:
+        """Moves the live utterance of slot `src` to slot `dst` between decode calls (K/V, frame store, position, ...: one
+        launch, ft_ar_slot_move); `src` is left parked.  Its later frames are those it would have drawn in `src`."""
+        self._check(self.lib.ft_ar_slot_move(self._h, int(src), int(dst)), "ft_ar_slot_move")
+
     # ---- reference-prefix K/V reuse (SURVEY.md §8-f F1)
     def kv_save(self, n_pos: int, slot: int = 0) -> "KVPrefix":
         h = C.c_void_p()

@@ -31,6 +31,39 @@ def pcm16(audio: np.ndarray) -> bytes:
     return (audio * 32767).astype(np.int16).tobytes()
 
 
+class ChunkCutter:
+    """One utterance's codes cut into chunks as its generated columns arrive: exactly `min_first_chunk` frames, then
+    `chunk_tokens` frames each, then the remainder (`ready`).  `add` takes (R, k) generated columns, rows 1.. being the
+    codes.  hold_back=True: the codes of Utterance.codes() - the last column stays back until the next one arrives, and
+    `finish` drops it (inference.py:839); hold_back=False: every column (FishTTS.synthesize_stream's chunks)."""
+
+    def __init__(self, chunk_tokens: int, min_first_chunk: int, hold_back: bool = True):
+        self.chunk_tokens, self.min_first_chunk, self.hold = chunk_tokens, min_first_chunk, 1 if hold_back else 0
+        self.pend: list = []              # columns not yet in a chunk (the held-back one last)
+        self.first = True
+        self.ready: deque = deque()       # cut chunks waiting for the codec
+        self.done = False                 # no more columns will come
+
+    def add(self, block: np.ndarray) -> None:
+        if self.done:
+            return
+        self.pend.extend(np.asarray(block)[1:].T)
+        while True:
+            thr = self.min_first_chunk if self.first else self.chunk_tokens
+            if len(self.pend) - self.hold < thr:
+                return
+            self.ready.append(np.stack(self.pend[:thr], axis=1))
+            del self.pend[:thr]
+            self.first = False
+
+    def finish(self) -> None:
+        rest = self.pend[:len(self.pend) - self.hold]
+        if rest:
+            self.ready.append(np.stack(rest, axis=1))
+        self.pend = []
+        self.done = True
+
+
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                       min_first_chunk: int = 10) -> Iterator[Tuple[int, bytes]]:
     """Yields (i, pcm) chunks of the n utterances `run` generates, in the order they become ready, and (i, b"") once
@@ -40,45 +73,24 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
     if chunk_tokens < 1 or min_first_chunk < 1:
         raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
     cv = threading.Condition()
-    pend: List[list] = [[] for _ in range(n)]          # columns not yet in a chunk (the held-back one last)
-    first = [True] * n
-    ready: List[deque] = [deque() for _ in range(n)]    # cut chunks waiting for the codec
-    done = [False] * n                                  # no more columns will come
+    cuts = [ChunkCutter(chunk_tokens, min_first_chunk) for _ in range(n)]
     ended = [False] * n                                 # end mark handed out (worker only)
     streams: List[Optional[object]] = [None] * n
     errors: List[BaseException] = []
     state = {"stop": False, "produced": False}
     out: "queue.Queue" = queue.Queue()
 
-    def cut(i: int) -> None:
-        while True:
-            thr = min_first_chunk if first[i] else chunk_tokens
-            if len(pend[i]) - 1 < thr:                  # the last column stays back
-                return
-            ready[i].append(np.stack(pend[i][:thr], axis=1))
-            del pend[i][:thr]
-            first[i] = False
-
-    def finish(i: int) -> None:
-        if pend[i][:-1]:
-            ready[i].append(np.stack(pend[i][:-1], axis=1))
-        pend[i] = []
-        done[i] = True
-
     def on_frames(i: int, block: np.ndarray) -> None:
         with cv:
             if state["stop"]:
                 raise _Stopped()
-            if done[i]:
-                return
-            pend[i].extend(np.asarray(block)[1:].T)
-            cut(i)
+            cuts[i].add(block)
             cv.notify_all()
 
     def on_done(i: int) -> None:
         with cv:
-            if not done[i]:
-                finish(i)
+            if not cuts[i].done:
+                cuts[i].finish()
             cv.notify_all()
 
     def producer() -> None:
@@ -102,19 +114,19 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                     while True:
                         if state["stop"]:
                             return
-                        batch = [i for i in range(n) if ready[i]]
-                        ends = [i for i in range(n) if done[i] and not ready[i] and not ended[i]]
+                        batch = [i for i in range(n) if cuts[i].ready]
+                        ends = [i for i in range(n) if cuts[i].done and not cuts[i].ready and not ended[i]]
                         if batch or ends:
                             break
                         if state["produced"]:
                             if all(ended):
                                 return
-                            for i in range(n):          # (a generation that ended without on_done for some)
-                                if not done[i]:
-                                    finish(i)
+                            for c in cuts:              # (a generation that ended without on_done for some)
+                                if not c.done:
+                                    c.finish()
                             continue
                         cv.wait()
-                    chunks = [ready[i].popleft() for i in batch]
+                    chunks = [cuts[i].ready.popleft() for i in batch]
                 for i in ends:                          # after the utterance's last chunk went out
                     if streams[i] is not None:
                         streams[i].close()

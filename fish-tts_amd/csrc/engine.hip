@@ -2030,6 +2030,102 @@ extern "C" ft_status ft_ar_park(ft_ctx* ctx, int32_t slot) {
     return FT_OK;
 }
 
+// ---- moving a live utterance to another slot (ft_ar_slot_move): ONE launch.  Workgroups [0, nkv) copy the slow stack's
+// K/V rows [0, n_pos) of the slot, one workgroup per (layer, K | V, kv head, chunk of positions), in 16-byte pieces; the
+// per-layer cache bases travel in the kernel's argument block (a table the kernel reads with scalar loads, as the frame
+// engine reads its layer table).  The last workgroup (with `state` set) copies everything else a later frame of the slot
+// reads - its row of the frame store (prompt and generated columns: the repetition-penalty window), position, input column,
+// the column under construction, frame count, done flag and sampling row - and leaves `from` parked as ft_ar_park leaves it.
+// Each element of `from` is read and rewritten by the same thread.  The codebook loop's K/V is rebuilt every frame.
+constexpr int SLOT_MOVE_MAX_LAYERS = 64;     // cache bases per launch (deeper models: one launch per 64 layers)
+struct SlotMoveP {
+    char* kv[2 * SLOT_MOVE_MAX_LAYERS];   // [layer][K | V] cache bases of the layers of this launch
+    size_t slot_bytes;       // one slot of one layer's K or V cache: Hkv x n_slots x hd elements
+    size_t head_bytes;       // one kv head's cached positions: n_slots x hd elements
+    int row16;               // 16-byte pieces per cached position (hd x esz / 16)
+    int hkv, chunk, nchunk, nkv, n_pos, from, to, state;
+    int *seq, *pos, *tok, *tokn, *nf, *done, *ctl;
+    int seq_row, R, ctl_words, im_end;
+};
+
+static __global__ __launch_bounds__(256) void slot_move_kernel(SlotMoveP p) {
+    const int b = blockIdx.x;
+    if (b < p.nkv) {
+        const int ci = b % p.nchunk, rest = b / p.nchunk;
+        const int head = rest % p.hkv, lk = rest / p.hkv;
+        const int p0 = ci * p.chunk, np = min(p.chunk, p.n_pos - p0);
+        char* base = p.kv[lk] + (size_t)head * p.head_bytes + (size_t)p0 * p.row16 * 16;
+        const U4* src = reinterpret_cast<const U4*>(base + (size_t)p.from * p.slot_bytes);
+        U4* dst = reinterpret_cast<U4*>(base + (size_t)p.to * p.slot_bytes);
+        const int n = np * p.row16;
+        for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+        return;
+    }
+    if (!p.state) return;
+    int* sf = p.seq + (size_t)p.from * p.seq_row;
+    int* st = p.seq + (size_t)p.to * p.seq_row;
+    for (int i = threadIdx.x; i < p.seq_row; i += blockDim.x) {
+        const int v = sf[i];
+        st[i] = v;
+        sf[i] = i == 0 ? p.im_end : 0;      // parked: one stored frame = <|im_end|>
+    }
+    for (int i = threadIdx.x; i < p.R; i += blockDim.x) {
+        const size_t f = (size_t)p.from * p.R + i, t = (size_t)p.to * p.R + i;
+        const int a = p.tok[f], c = p.tokn[f];
+        p.tok[t] = a; p.tokn[t] = c;
+        p.tok[f] = 0;                       // parked: a harmless input column
+    }
+    for (int i = threadIdx.x; i < p.ctl_words; i += blockDim.x)
+        p.ctl[(size_t)p.to * p.ctl_words + i] = p.ctl[(size_t)p.from * p.ctl_words + i];
+    if (threadIdx.x == 0) {
+        const int ps = p.pos[p.from], nf = p.nf[p.from], dn = p.done[p.from];
+        p.pos[p.to] = ps; p.nf[p.to] = nf; p.done[p.to] = dn;
+        p.pos[p.from] = 0; p.nf[p.from] = 1; p.done[p.from] = 1;
+    }
+}
+
+// Between ft_ar_decode calls (and after a fill) only: the recovery of a frame-engine time-out needs nothing more here - it
+// takes slot 0's position, frame count and done flag from the device at the start of every ft_ar_decode call (pos0, nf0,
+// done0) and ft_ar_prefill_at / ft_ar_first_frames reset the slot they serve, so a moved utterance is rewound from its new
+// slot like any other.  The host keeps no other per-slot state.
+extern "C" ft_status ft_ar_slot_move(ft_ctx* ctx, int32_t from, int32_t to) {
+    FT_TRY(ar_ready(ctx));
+    const ft_ar_config& c = ctx->c;
+    if (from < 0 || from >= c.max_batch || to < 0 || to >= c.max_batch || from == to)
+        return ft_fail(ctx, FT_ERR_ARG, "ft_ar_slot_move: bad slot (out of range, or from == to)");
+    const int R = c.num_codebooks + 1;
+    // the positions to carry: read behind every earlier call on the stream (an ft_ar_decode returns with it drained)
+    FT_HIP(ctx, hipMemcpyAsync(ctx->h_pin, ctx->d_pos + from, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int n_pos = std::max(0, std::min(ctx->h_pin[0], ctx->n_slots));
+    static_assert(sizeof(RowCtl) % sizeof(int) == 0, "the sampling row moves as whole words");
+    SlotMoveP p{};
+    p.slot_bytes = ctx->cache_m_stride * ctx->esz;
+    p.head_bytes = (size_t)ctx->n_slots * c.head_dim * ctx->esz;
+    p.row16 = (int)((size_t)c.head_dim * ctx->esz / 16);     // head_dim >= 8 (ar_validate): a position is >= 16 bytes
+    p.hkv = c.n_local_heads;
+    p.chunk = std::max(1, 1024 / p.row16);                    // ~16 KB per workgroup, four pieces per thread
+    p.nchunk = std::max(1, (n_pos + p.chunk - 1) / p.chunk);
+    p.n_pos = n_pos; p.from = from; p.to = to;
+    p.seq = ctx->d_seq; p.pos = ctx->d_pos; p.tok = ctx->d_tok; p.tokn = ctx->d_tokn; p.nf = ctx->d_nf; p.done = ctx->d_done;
+    p.ctl = reinterpret_cast<int*>(ctx->d_ctl);
+    p.seq_row = R * ctx->cap; p.R = R; p.ctl_words = (int)(sizeof(RowCtl) / sizeof(int)); p.im_end = c.im_end_id;
+    for (int l0 = 0; l0 < c.n_layer; l0 += SLOT_MOVE_MAX_LAYERS) {
+        const int nl = std::min(SLOT_MOVE_MAX_LAYERS, c.n_layer - l0);
+        for (int i = 0; i < nl; ++i) {
+            p.kv[2 * i] = (char*)ctx->layers[l0 + i].kc;
+            p.kv[2 * i + 1] = (char*)ctx->layers[l0 + i].vc;
+        }
+        p.nkv = n_pos > 0 ? 2 * nl * p.hkv * p.nchunk : 0;
+        p.state = l0 + nl == c.n_layer;                      // the per-slot state moves with the last layers
+        const int grid = p.nkv + (p.state ? 1 : 0);
+        if (grid == 0) continue;
+        slot_move_kernel<<<grid, 256, 0, ctx->stream>>>(p);
+        FT_HIP(ctx, hipGetLastError());
+    }
+    return FT_OK;
+}
+
 extern "C" ft_status ft_ar_set_noise(ft_ctx* ctx, const float* q, int64_t n_rows, int64_t row_len) {
     if (!ctx || !ctx->has_ar) return FT_ERR_ARG;
     FT_HIP(ctx, hipSetDevice(ctx->device));

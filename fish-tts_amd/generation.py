@@ -57,13 +57,14 @@ class PrefixCache:
         self.capacity, self.min_positions = capacity, min_positions
         self._entries = {}  # key -> KVPrefix, insertion order = recency
 
-    def get(self, engine: ARHipEngine, prefix_cols: np.ndarray):
+    def get(self, engine: ARHipEngine, prefix_cols: np.ndarray, slot: Optional[int] = None):
+        """`slot`: the slot a missing entry is built in (default: the engine's default, slot 0)."""
         import hashlib
         cols = np.ascontiguousarray(prefix_cols, dtype=np.int32)
         key = (id(engine), cols.shape[1], hashlib.sha1(cols.tobytes()).hexdigest())
         hit = self._entries.pop(key, None)
         if hit is None or not hit.handle:
-            hit = engine.build_prefix(cols)
+            hit = engine.build_prefix(cols) if slot is None else engine.build_prefix(cols, slot)
         self._entries[key] = hit
         while len(self._entries) > self.capacity:
             self._entries.pop(next(iter(self._entries))).free()

@@ -77,6 +77,7 @@ class FishTTS:
         self._prefill_cache = _PrefillCache()
         self._prefill_lock = threading.Lock()
         self._gen_lock = threading.Lock()  # AR calls on one context are serialised
+        self._server = None                # an open BatchServer (serve()): it holds _gen_lock and serves synthesize*
         self._gpu_index = gpu_index
         if device != "cuda":
             raise RuntimeError("fish_tts_amd runs the hot path on an MI355X only: device must be 'cuda' "
@@ -184,7 +185,12 @@ class FishTTS:
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         audio = self._read_wav(audio_bytes)
-        codes = self._vocoder.encode(audio)
+        srv = getattr(self, "_server", None)
+        if srv is not None:
+            with srv.codec_lock:              # the server's codec worker shares the codec context
+                codes = self._vocoder.encode(audio)
+        else:
+            codes = self._vocoder.encode(audio)
         return VoiceProfile(codes=codes.astype(np.int64), text=text)
 
     @staticmethod
@@ -233,8 +239,15 @@ class FishTTS:
     # ------------------------------------------------------------------ synthesis
     def synthesize(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                    top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048) -> bytes:
-        """Text -> WAV bytes (synthesizer.py:431-481)."""
+        """Text -> WAV bytes (synthesizer.py:431-481).  While a BatchServer is open (serve()) the call joins its batch."""
         from .generation import generate_long
+        from .serve import ServerClosed
+        srv = getattr(self, "_server", None)
+        if srv is not None:
+            try:
+                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens)
+            except ServerClosed:
+                pass                          # closed meanwhile: served here, once the server has let go of _gen_lock
         prompt_text, prompt_tokens = self._get_prompt_data(references)
         codes_list = []
         with self._gen_lock:
@@ -291,6 +304,7 @@ class FishTTS:
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
         semantics as synthesize()."""
         from .batch import run_batch, run_batch_streams
+        self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
                                                    seed, seeds)
@@ -320,6 +334,7 @@ class FishTTS:
         abandoning the generator stops it within one burst and releases the lock (fish_tts_amd.batch_stream)."""
         from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
+        self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         texts = list(texts)
@@ -349,8 +364,28 @@ class FishTTS:
         kernel variants of a nominal 215-frame utterance: bit-equal at about that length, relative RMS <= 2e-2 measured at
         60 and 300 frames).  One stream carries at most `max_frames` frames (2056 here: the codec's rotation table); a
         longer synthesis starts a fresh stream there - that one boundary is decoded from zero state, as the reference
-        decodes every chunk."""
+        decodes every chunk.
+
+        While a BatchServer is open (serve()) the request joins its batch (BatchServer.synthesize_stream)."""
         from .generation import generate_long
+        from .serve import ServerClosed
+        srv = getattr(self, "_server", None)
+        if srv is not None:
+            chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, **kwargs)
+            try:
+                try:
+                    first = next(chunks)      # the request is queued here
+                except ServerClosed:
+                    chunks = None             # closed meanwhile: served here, once the server has let go of _gen_lock
+                except StopIteration:
+                    return
+                if chunks is not None:
+                    yield first
+                    yield from chunks
+                    return
+            finally:
+                if chunks is not None:
+                    chunks.close()            # (an abandoned stream cancels its request)
         seamless = bool(kwargs.get("seamless", False))
         prompt_text, prompt_tokens = self._get_prompt_data(references)
         codes_queue: "queue.Queue" = queue.Queue(maxsize=3)
@@ -478,6 +513,52 @@ class FishTTS:
         worker.join()
         if error_holder:
             raise error_holder[0]
+
+    # ------------------------------------------------------------------ continuous batching (extension)
+    def serve(self, burst: int = 8) -> "BatchServer":
+        """Extension: a BatchServer (fish_tts_amd.serve) over this instance's first AR engine - concurrent synthesize /
+        synthesize_stream calls, from any number of threads, join one continuous lock-step batch (max_batch slots) at
+        the next burst boundary and stream their audio back.  While it is open, this instance's own synthesize and
+        synthesize_stream are served by it, synthesize_batch and synthesize_batch_stream raise RuntimeError.  A context
+        manager; after close() the instance behaves exactly as before.  Waits for a running synthesis to end."""
+        from .serve import BatchServer
+        if getattr(self, "_server", None) is not None:
+            raise RuntimeError("a BatchServer is already open on this instance")
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        self._gen_lock.acquire()            # held while the server owns the engine; released by _server_closed
+        try:
+            self._server = BatchServer(self._engine, self._vocoder, burst, prepare=self._serve_prepare,
+                                       decode_wav=self._decode_to_wav, decode_pcm=self._decode_to_pcm,
+                                       prefix_cache=self._prefix_cache, on_close=self._server_closed)
+        except BaseException:
+            self._gen_lock.release()
+            raise
+        return self._server
+
+    def _server_closed(self, server) -> None:
+        if self._server is server:
+            self._server = None
+            self._gen_lock.release()
+
+    def _no_server(self, what: str) -> None:
+        if getattr(self, "_server", None) is not None:
+            raise RuntimeError(f"{what} is not available while a BatchServer is open (serve()): close it first, or "
+                               "send the texts through the server")
+
+    def _serve_prepare(self, text: str, references, temperature: float, top_p: float, repetition_penalty: float,
+                       max_tokens: int, seed: int):
+        """A BatchServer request on the caller's thread: the prompt as generate_long builds and checks it."""
+        from .batch import Utterance
+        from .prompt import build_prompt_split
+        assert 0 < top_p <= 1, "top_p must be in (0, 1]"
+        assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
+        assert 0 < temperature < 2, "temperature must be in (0, 2)"
+        prompt_text, prompt_tokens = self._get_prompt_data(references)
+        enc, n_prefix = build_prompt_split(self._tokenizer, text, prompt_text, prompt_tokens, self._engine.args.num_codebooks)
+        if enc.shape[1] > self._engine.args.max_seq_len - 2048:
+            raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
+        return Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seed), n_prefix
 
     # ------------------------------------------------------------------ codes -> audio (synthesizer.py:586-648)
     def _decode_to_wav(self, codes: np.ndarray) -> bytes:

@@ -116,6 +116,14 @@ ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32_t* slots, 
  * <|im_end|> freeze the same way on the device, so a host scheduler can refill finished slots between
  * ft_ar_decode bursts (continuous batching; the reference serves one utterance at a time, synthesizer.py:431). */
 ft_status ft_ar_park(ft_ctx* ctx, int32_t slot);
+/* Moves the live utterance of slot `from` to slot `to` between ft_ar_decode calls (a continuous-batching scheduler keeps
+ * its active slots at [0, n) so that a lock-step step of width n - and a lone survivor on slot 0, the batch-1 frame
+ * engine - serves them; the reference serves one utterance at a time, synthesizer.py:431).  Carried: the slow stack's K/V
+ * rows [0, pos) of every layer, the slot's row of the frame store (the repetition-penalty window reads it), position,
+ * input column, frame count, done flag and sampling row; `from` is left parked (as ft_ar_park leaves it), `to`'s former
+ * content is overwritten.  One launch, stream-ordered after every earlier call.  Refused before any device work, both
+ * slots unchanged: FT_ERR_ARG (a slot out of range, from == to), FT_ERR_STATE (a context without the AR model). */
+ft_status ft_ar_slot_move(ft_ctx* ctx, int32_t from, int32_t to);
 /* Reference-prefix KV reuse (the reference keeps the reference tensors in
  * `_prefill_cache` but re-prefills them on every call: synthesizer.py:363-429, inference.py:779-793,
  * 353-362).  The prompt prefix [<|interleave|>, (<|speaker:0|>, ref text, ref codes, <|im_end|>)*] does
