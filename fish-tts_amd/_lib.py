@@ -74,6 +74,12 @@ SYMBOLS = {
     "ft_codec_stream_decode": (C.c_int32, [_P, _P, _P, C.c_int32, _P]),
     "ft_codec_stream_end": (None, [_P, _P]),
     "ft_codec_stream_decode_many": (C.c_int32, [_P, C.c_int32, _P, _P, _P, _P]),
+    "ft_resample_filter": (C.c_int32, [C.c_int32, _P, _P, _P, _P]),
+    "ft_resampled_len": (C.c_int64, [C.c_int32, C.c_int64]),
+    "ft_codec_decode_at": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
+    "ft_codec_stream_begin_at": (C.c_int32, [_P, C.c_int32, C.POINTER(_P)]),
+    "ft_codec_stream_decode_many_at": (C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "ft_test_resample": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
     "ft_codec_encode": (C.c_int32, [_P, _P, C.c_int64, _P, _P]),
     "ft_codec_enc_frame_len": (C.c_int32, [_P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),

@@ -11,7 +11,11 @@ The codec side needs `stream()` (a CodecStream: `frames`, `close()`), `decode_st
 of several distinct streams in one pass, codec_engine.CodecHipEngine) and `max_frames`.  Each time the worker wakes it
 decodes every ready chunk in one decode_streams call, at most one chunk per utterance; each utterance's chunks go through
 its own stream, so its PCM concatenates to one streamed decode of its codes whatever else is in flight.  A stream that
-would pass `max_frames` starts afresh (as synthesize_stream does)."""
+would pass `max_frames` starts afresh (as synthesize_stream does).
+
+With `sample_rate` the streams are `stream(sample_rate)` (their output resampled on the device) and decode_streams takes
+one final flag per chunk: an utterance's last chunk is decoded with final=True, or, when its end is known only after its
+last chunk went out, the stream's `finish()` gives the held-back tail; either way the tail is out before (i, b"")."""
 from __future__ import annotations
 
 import queue
@@ -65,7 +69,7 @@ class ChunkCutter:
 
 
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
-                      min_first_chunk: int = 10) -> Iterator[Tuple[int, bytes]]:
+                      min_first_chunk: int = 10, sample_rate: Optional[int] = None) -> Iterator[Tuple[int, bytes]]:
     """Yields (i, pcm) chunks of the n utterances `run` generates, in the order they become ready, and (i, b"") once
     after utterance i's last chunk.  `run` is called on a producer thread, the codec on a worker thread; abandoning the
     generator stops the producer at its next block of frames and joins both threads.  An exception of either thread is
@@ -127,7 +131,10 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                             continue
                         cv.wait()
                     chunks = [cuts[i].ready.popleft() for i in batch]
+                    final = [cuts[i].done and not cuts[i].ready for i in batch]
                 for i in ends:                          # after the utterance's last chunk went out
+                    if sample_rate is not None and streams[i] is not None and not streams[i].finished:
+                        out.put((i, pcm16(streams[i].finish())))       # the resampler's tail
                     if streams[i] is not None:
                         streams[i].close()
                         streams[i] = None
@@ -139,9 +146,14 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                     s = streams[i]
                     if s is None or s.frames + c.shape[1] > codec.max_frames:   # the rotation table ends there
                         if s is not None:
+                            if sample_rate is not None:
+                                out.put((i, pcm16(s.finish())))
                             s.close()
-                        streams[i] = codec.stream()
-                audio = codec.decode_streams([streams[i] for i in batch], chunks)
+                        streams[i] = codec.stream() if sample_rate is None else codec.stream(sample_rate)
+                if sample_rate is None:
+                    audio = codec.decode_streams([streams[i] for i in batch], chunks)
+                else:
+                    audio = codec.decode_streams([streams[i] for i in batch], chunks, final)
                 for i, a in zip(batch, audio):
                     out.put((i, pcm16(a)))
         except BaseException as e:  # noqa: BLE001

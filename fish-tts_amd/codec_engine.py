@@ -13,6 +13,32 @@ from .ar_engine import HipError, _rope_table
 from .config import CodecArgs
 
 
+CODEC_RATE = 44100     # the codec's own sample rate (Fi of the resampler)
+
+
+def output_rate(sample_rate: Optional[int]) -> Optional[int]:
+    """A caller's `sample_rate=`: None for the codec's own rate (None or 44100: no resampler), else the rate - an integer
+    in [8000, 48000] whose reduced L = rate / gcd(rate, 44100) is at most 640 (ft_resample_filter).  Anything else raises
+    ValueError (before any device work)."""
+    if sample_rate is None:
+        return None
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)):
+        raise ValueError(f"sample_rate must be an integer, got {sample_rate!r}")
+    rate = int(sample_rate)
+    if rate == CODEC_RATE:
+        return None
+    if not -(1 << 31) <= rate < (1 << 31) or L.load().ft_resample_filter(rate, None, None, None, None) != L.FT_OK:
+        raise ValueError(f"unsupported sample_rate {rate}: integers in [8000, 48000] whose ratio to 44100 reduces to "
+                         "L / M with L <= 640 (8000, 11025, 12000, 16000, 22050, 24000, 32000, 48000, ...)")
+    return rate
+
+
+def resampled_len(sample_rate: Optional[int], n: int) -> int:
+    """Samples that n codec samples give at sample_rate: ceil(n L / M)."""
+    rate = output_rate(sample_rate)
+    return int(n) if rate is None else int(L.load().ft_resampled_len(rate, int(n)))
+
+
 def fold_weight_norm(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """codec.pth stores weight-normed convs as parametrizations.weight.original0 (g) / original1 (v)
     (vocoder.py:423-429,457-463: torch weight_norm, dim=0).  Fold them to plain `.weight` tensors and
@@ -150,23 +176,31 @@ class CodecHipEngine:
                                                  codes.ctypes.data_as(C.c_void_p)), "ft_codec_rvq_encode")
         return codes
 
-    def stream(self) -> "CodecStream":
-        """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode."""
-        return CodecStream(self)
+    def stream(self, sample_rate: Optional[int] = None) -> "CodecStream":
+        """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode.
+        `sample_rate` (output_rate): the stream's output is resampled on the device; it holds back the samples whose
+        filter taps reach past the input so far, until a later chunk, decode(final=True) or finish()."""
+        return CodecStream(self, sample_rate)
 
     MAX_STREAMS_PER_CALL = 64     # ft_codec_stream_decode_many
 
-    def decode_streams(self, streams: Sequence["CodecStream"], chunks: Sequence[np.ndarray]) -> List[np.ndarray]:
+    def decode_streams(self, streams: Sequence["CodecStream"], chunks: Sequence[np.ndarray],
+                       final: Optional[Sequence[bool]] = None) -> List[np.ndarray]:
         """The next chunk of each of several distinct streams of this engine, in one pass through the codec per native
         call (ft_codec_stream_decode_many): chunks[j] (n_codebooks+1, T_j) integer -> float32 (T_j * frame_len,), bit
         for bit what streams[j].decode(chunks[j]) gives.  More than 64 streams, or more than max_frames frames together,
-        take several calls (the streams of calls that went through stay advanced if a later one fails)."""
+        take several calls (the streams of calls that went through stay advanced if a later one fails).
+        Streams at other rates (stream(sample_rate=...)) may be mixed in (ft_codec_stream_decode_many_at): theirs are
+        the resampled samples the chunk completes, bit for bit what streams[j].decode(chunks[j], final[j]) gives;
+        final[j] also emits the stream's tail and closes it for decoding (a chunk of 0 frames is allowed then)."""
         streams = list(streams)
         chunks = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in chunks]
         if len(streams) != len(chunks):
             raise ValueError("decode_streams: one chunk per stream")
         for c in chunks:
             assert c.ndim == 2 and c.shape[0] == self.R, c.shape
+        if final is not None or any(s.rate is not None for s in streams):
+            return self._decode_streams_at(streams, chunks, [False] * len(streams) if final is None else list(final))
         out: List[np.ndarray] = []
         i = 0
         while i < len(streams):
@@ -190,8 +224,52 @@ class CodecHipEngine:
             i = j
         return out
 
-    def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None) -> np.ndarray:
-        """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len)."""
+    def _decode_streams_at(self, streams, chunks, final) -> List[np.ndarray]:
+        if len(final) != len(streams):
+            raise ValueError("decode_streams: one final flag per stream")
+        out: List[np.ndarray] = []
+        i = 0
+        while i < len(streams):
+            j, total = i, 0
+            while j < len(streams) and j - i < self.MAX_STREAMS_PER_CALL and (j == i or total + chunks[j].shape[1] <= self.max_frames):
+                total += chunks[j].shape[1]
+                j += 1
+            group = streams[i:j]
+            lens = np.array([c.shape[1] for c in chunks[i:j]], dtype=np.int32)
+            fin = np.array([1 if f else 0 for f in final[i:j]], dtype=np.int32)
+            codes = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in chunks[i:j]]))
+            handles = (C.c_void_p * len(group))(*[s._h.value for s in group])
+            # room for everything each stream can emit: its outputs up to the end of the chunk, less those it gave
+            cap = sum(s._cap(int(T) * self.frame_len) for s, T in zip(group, lens))
+            audio = np.empty(max(cap, 1), dtype=np.float32)
+            out_lens = np.zeros(len(group), dtype=np.int64)
+            self._check(self.lib.ft_codec_stream_decode_many_at(
+                self._h, len(group), handles, codes.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+                fin.ctypes.data_as(C.c_void_p), audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
+                "ft_codec_stream_decode_many_at")
+            off = 0
+            for s, T, n, f in zip(group, lens, out_lens, fin):
+                s._advance(int(T), int(n), bool(f))
+                out.append(audio[off:off + int(n)])
+                off += int(n)
+            i = j
+        return out
+
+    def test_resample(self, x: np.ndarray, sample_rate: int) -> np.ndarray:
+        """Test hook (ft_test_resample): the resampler alone on a waveform at the codec rate (zeros around it)."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        rate = int(sample_rate)
+        y = np.empty(max(1, int(self.lib.ft_resampled_len(rate, len(x)))), dtype=np.float32)
+        n = C.c_int64(0)
+        self._check(self.lib.ft_test_resample(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate,
+                                              y.ctypes.data_as(C.c_void_p), C.byref(n)), "ft_test_resample")
+        return y[:n.value]
+
+    def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, sample_rate: Optional[int] = None) -> np.ndarray:
+        """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len).
+        `sample_rate` (output_rate): resampled on the device, (B, max_b resampled_len(lens[b] * frame_len)); row b holds
+        resampled_len(sample_rate, lens[b] * frame_len) samples, zeros after them."""
+        rate = output_rate(sample_rate)
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
@@ -199,6 +277,15 @@ class CodecHipEngine:
         B, R, T = codes.shape
         assert R == self.R, codes.shape
         lens_a = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+        if rate is not None:
+            width = max(resampled_len(rate, int(n) * self.frame_len) for n in lens_a)
+            audio = np.empty((B, max(width, 1)), dtype=np.float32)
+            out_lens = np.zeros(B, dtype=np.int64)
+            self._check(self.lib.ft_codec_decode_at(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
+                                                    lens_a.ctypes.data_as(C.c_void_p), rate,
+                                                    audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
+                        "ft_codec_decode_at")
+            return audio[:, :width]
         audio = np.empty((B, T * self.frame_len), dtype=np.float32)
         self._check(self.lib.ft_codec_decode(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
                                              lens_a.ctypes.data_as(C.c_void_p), audio.ctypes.data_as(C.c_void_p)),
@@ -211,18 +298,45 @@ class CodecStream:
     here the causal codec's context - the last 127 frames' K/V of every transformer layer, the last rows of every
     convolution input - is carried)."""
 
-    def __init__(self, engine: CodecHipEngine):
+    def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None):
         self.engine = engine
+        self.rate = output_rate(sample_rate)      # None: the codec's own rate
         self._h = C.c_void_p()
-        engine._check(engine.lib.ft_codec_stream_begin(engine._h, C.byref(self._h)), "ft_codec_stream_begin")
+        if self.rate is None:
+            engine._check(engine.lib.ft_codec_stream_begin(engine._h, C.byref(self._h)), "ft_codec_stream_begin")
+        else:
+            engine._check(engine.lib.ft_codec_stream_begin_at(engine._h, self.rate, C.byref(self._h)), "ft_codec_stream_begin_at")
         self.frames = 0
+        self.samples_out = 0       # resampled samples handed out so far (a stream at another rate)
+        self.finished = False      # its tail went out: no further chunk
         engine._streams.add(self)      # the engine ends its open streams before it destroys the native context
 
-    def decode(self, codes: np.ndarray) -> np.ndarray:
-        """codes (n_codebooks+1, T) integer -> float32 (T * frame_len,): the next T frames of the stream."""
+    def _cap(self, n_in: int) -> int:
+        """Most samples the next call can give for n_in more codec samples."""
+        if self.rate is None:
+            return n_in
+        return resampled_len(self.rate, self.frames * self.engine.frame_len + n_in) - self.samples_out
+
+    def _advance(self, T: int, n_out: int, final: bool) -> None:
+        self.frames += T
+        self.samples_out += n_out
+        self.finished = self.finished or (final and self.rate is not None)
+
+    def finish(self) -> np.ndarray:
+        """The held-back tail of a stream at another rate (the input taken as zero past its end); the stream takes no
+        further chunk.  Empty at the codec's own rate, and once the tail went out."""
+        if self.rate is None or self.finished:
+            return np.zeros(0, dtype=np.float32)
+        return self.engine.decode_streams([self], [np.zeros((self.engine.R, 0), dtype=np.int32)], [True])[0]
+
+    def decode(self, codes: np.ndarray, final: bool = False) -> np.ndarray:
+        """codes (n_codebooks+1, T) integer -> float32 (T * frame_len,): the next T frames of the stream.  At another
+        rate: the resampled samples these frames complete; final=True also gives the tail (finish)."""
         e = self.engine
         codes = np.ascontiguousarray(np.asarray(codes), dtype=np.int32)
         assert codes.ndim == 2 and codes.shape[0] == e.R, codes.shape
+        if self.rate is not None:
+            return e.decode_streams([self], [codes], [final])[0]
         T = codes.shape[1]
         audio = np.empty(T * e.frame_len, dtype=np.float32)
         e._check(e.lib.ft_codec_stream_decode(e._h, self._h, codes.ctypes.data_as(C.c_void_p), T,

@@ -3,8 +3,10 @@
 #include <string.h>
 
 #include <algorithm>
-
+#include <cmath>
+#include <map>
 #include <mutex>
+#include <numeric>
 
 #include "codec_kernels.h"
 #include "engine.h"
@@ -54,6 +56,13 @@ struct CodecState {
     bf16_t* mqkv = nullptr;
     unsigned char* mtab = nullptr;
     int mcarry = 0;           // carries per stream (convolution tails + one K/V per transformer layer)
+    // resampler (ft_codec_decode_at, ft_codec_stream_*_at): one [L][K] table per output rate, uploaded on its first use;
+    // an output buffer and a segment table, allocated on the first resampled call
+    struct RsTab { int L = 1, M = 1, K = 0; float* w = nullptr; };
+    std::map<int, RsTab> rs_tabs;
+    float* rs_out = nullptr;
+    size_t rs_cap = 0;
+    RsSeg* rs_seg = nullptr;
     // ---- encode side
     struct EncUnit { float *a0, *a2; ConvW c7, c1; };
     struct EncBlock { EncUnit u[3]; float* a3; ConvW sc; int s, cin, cout; std::vector<TfLayer> tf; float* tf_norm = nullptr; };
@@ -623,6 +632,14 @@ struct ft_codec_stream {
     std::vector<bf16_t*> kv[2];                    // per transformer layer: [window - 1][2 * H * hd], newest rows last
     struct Tail { bf16_t* buf[2]; int H, C; };
     std::vector<Tail> tails;                       // in the order decode_one consumes them
+    // resampled output (ft_codec_stream_begin_at; rate 0: the codec's own rate, no resampler): the last K input samples,
+    // two copies (a call reads one and writes the other), and the input / output sample counters
+    int rate = 0;
+    const CodecState::RsTab* rs = nullptr;
+    float* rcarry[2] = {nullptr, nullptr};
+    int rpar = 0;
+    long long nin = 0, nout = 0;
+    bool finished = false;                         // its tail went out (final): no further chunk
     std::vector<void*> owned;
 };
 
@@ -638,7 +655,110 @@ static int halo_of(const ConvW& w) {
     return h;
 }
 
-static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, int T, float* audio_host, ft_codec_stream* sc = nullptr) {
+// ---- resampler (RsSeg, resample_kernel): filter design on the host in float64, a Kaiser-windowed sinc at the up-sampled
+// rate L Fi cut off at 0.465 Fmin (pass band to 0.43 Fmin, stop band from 0.5 Fmin, Fmin = min(Fi, Fo)), designed for 75 dB.
+// Tap t of phase p is the prototype at j = p + (K/2 - 1 - t) L up-sampled samples from the output instant, gain L (the
+// zero-stuffed input).  Rates: integers in [8000, 48000] whose reduced L is at most 640; the codec's own rate has K = 0.
+constexpr int RS_FI = 44100, RS_MIN_RATE = 8000, RS_MAX_RATE = 48000, RS_MAX_L = 640, RS_MAX_SEGS = 64;
+
+static double bessel_i0(double x) {
+    double sum = 1.0, term = 1.0;
+    const double q = x * x / 4.0;
+    for (int k = 1; k < 500 && term > 1e-17 * sum; ++k) {
+        term *= q / ((double)k * k);
+        sum += term;
+    }
+    return sum;
+}
+
+// Validates `rate` (an error message, or null) and gives L, M, K; fills w ([L][K] float32) when non-null.
+static const char* rs_design(int rate, int* L, int* M, int* K, std::vector<float>* w) {
+    if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return "sample rate outside [8000, 48000]";
+    const int g = std::gcd(rate, RS_FI), l = rate / g, m = RS_FI / g;
+    if (l > RS_MAX_L) return "sample rate: rate / gcd(rate, 44100) exceeds 640";
+    *L = l;
+    *M = m;
+    *K = 0;
+    if (rate == RS_FI) return nullptr;
+    const double A = 75.0, beta = 0.1102 * (A - 8.7), fmin = std::min(rate, RS_FI);
+    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * RS_FI / fmin);
+    k += k & 1;
+    if ((255L * m + l - 1) / l + k + 1 > RS_LDS) return "sample rate: filter window exceeds the resampler's LDS stage";
+    *K = k;
+    if (!w) return nullptr;
+    const double fc = 0.465 * fmin / ((double)l * RS_FI), half = 0.5 * k * l, ib = bessel_i0(beta);
+    w->assign((size_t)l * k, 0.f);
+    for (int p = 0; p < l; ++p)
+        for (int t = 0; t < k; ++t) {
+            const double j = p + (double)(k / 2 - 1 - t) * l, r = j / half, x = M_PI * 2.0 * fc * j;
+            const double sinc = j == 0 ? 1.0 : std::sin(x) / x;
+            (*w)[(size_t)p * k + t] = (float)(2.0 * fc * l * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / ib);
+        }
+    return nullptr;
+}
+
+// Outputs available after `nin` input samples: all of them at the end of the input (final), else those whose taps all
+// lie within it (floor(n M / L) + K/2 < nin).
+static long long rs_ready(const CodecState::RsTab& t, long long nin, bool final) {
+    if (t.K == 0) return nin;
+    const long long a = final ? nin : nin - t.K / 2;
+    return a > 0 ? (a * t.L + t.M - 1) / t.M : 0;
+}
+
+// The device table of `rate` (uploaded on its first use); the caller holds s->mu.
+static ft_status rs_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) {
+    CodecState* s = ctx->codec;
+    auto it = s->rs_tabs.find(rate);
+    if (it == s->rs_tabs.end()) {
+        CodecState::RsTab t;
+        std::vector<float> w;
+        if (const char* e = rs_design(rate, &t.L, &t.M, &t.K, &w)) return ft_fail(ctx, FT_ERR_ARG, e);
+        if (t.K > 0) {
+            FT_TRY(cmalloc(ctx, &t.w, w.size()));
+            FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        it = s->rs_tabs.emplace(rate, t).first;
+    }
+    *out = &it->second;
+    return FT_OK;
+}
+
+// The output buffer and segment table, allocated once: max_frames of input at the highest rate, plus what streams hold
+// back (K/2 L/M + 1 < RS_LDS outputs each).
+static ft_status rs_alloc(ft_ctx* ctx) {
+    CodecState* s = ctx->codec;
+    if (s->rs_seg) return FT_OK;
+    const size_t in = (size_t)ctx->cc.max_frames * s->frame_len;
+    const size_t cap = (in * RS_MAX_RATE + RS_FI - 1) / RS_FI + (size_t)RS_MAX_SEGS * RS_LDS;
+    FT_TRY(cmalloc(ctx, &s->rs_out, cap));
+    RsSeg* t = nullptr;
+    FT_TRY(cmalloc(ctx, &t, (size_t)RS_MAX_SEGS));
+    s->rs_cap = cap;
+    s->rs_seg = t;
+    return FT_OK;
+}
+
+// Resamples `segs` (their inputs written earlier on the codec's stream) into rs_out, back to back, and queues the copy of
+// all their outputs to `host`; the caller synchronizes (and keeps `segs` alive until then).
+static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host) {
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    long long off = 0, mx = 0;
+    for (RsSeg& g : segs) {
+        g.y = s->rs_out + off;
+        off += g.n_out;
+        mx = std::max(mx, (long long)g.n_out);
+    }
+    FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, segs.data(), segs.size() * sizeof(RsSeg), hipMemcpyHostToDevice, st));
+    const int gx = (int)std::max(1LL, std::min(2048LL, (mx + RS_THREADS - 1) / RS_THREADS));
+    resample_kernel<<<dim3(gx, 1, (unsigned)segs.size()), RS_THREADS, 0, st>>>(s->rs_seg);
+    if (off > 0) FT_HIP(ctx, hipMemcpyAsync(host, s->rs_out, (size_t)off * sizeof(float), hipMemcpyDeviceToHost, st));
+    return FT_OK;
+}
+
+// `rs`: resample the waveform (segment 0, its input set here) and copy the resampled samples instead.
+static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, int T, float* audio_host, ft_codec_stream* sc = nullptr,
+                            std::vector<RsSeg>* rs = nullptr) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     hipStream_t st = s->stream;
@@ -715,7 +835,12 @@ static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, i
     }
     FinalConvP fp{a, s->w_last, s->b_last, Tc, s->c_last, s->audio, roll(a, Tc, 6, s->c_last)};
     final_conv_tanh_kernel<<<2048, 256, 0, st>>>(fp);
-    FT_HIP(ctx, hipMemcpyAsync(audio_host, s->audio, (size_t)Tc * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (rs) {
+        (*rs)[0].x = s->audio;
+        FT_TRY(rs_enqueue(ctx, *rs, audio_host));
+    } else {
+        FT_HIP(ctx, hipMemcpyAsync(audio_host, s->audio, (size_t)Tc * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
     FT_HIP(ctx, hipStreamSynchronize(st));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("codec launch: ") + hipGetErrorString(e));
@@ -789,6 +914,7 @@ extern "C" ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* sc, co
     if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
     if (!codes || !audio || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode: bad argument");
     if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: the stream belongs to another (or a destroyed) context");
+    if (sc->rate) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
     const ft_codec_config& c = ctx->cc;
     if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: chunk longer than max_frames");
     if (sc->t0 + T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: stream longer than max_frames (rope table)");
@@ -852,8 +978,9 @@ static ft_status many_alloc(ft_ctx* ctx, int ncarry) {
     return FT_OK;
 }
 
+// `rs`: resample the chunks (ft_codec_stream_decode_many_at: the segments' inputs set by the caller) and copy those samples.
 static ft_status decode_many(ft_ctx* ctx, int n, ft_codec_stream* const* scs, const int32_t* codes_host, const int32_t* lens,
-                             float* audio_host) {
+                             float* audio_host, std::vector<RsSeg>* rs = nullptr) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     hipStream_t st = s->stream;
@@ -967,7 +1094,8 @@ static ft_status decode_many(ft_ctx* ctx, int n, ft_codec_stream* const* scs, co
     FinalConvP fp{a, s->w_last, s->b_last, Lmax * m, s->c_last, s->audio, roll(a, m, 6, s->c_last)};
     fp.z = Z(m, MANY_GAP);
     final_conv_tanh_kernel<<<dim3(std::max(16, 2048 / n), 1, n), 256, 0, st>>>(fp);
-    FT_HIP(ctx, hipMemcpyAsync(audio_host, s->audio, (size_t)Ts * s->frame_len * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (rs) FT_TRY(rs_enqueue(ctx, *rs, audio_host));
+    else FT_HIP(ctx, hipMemcpyAsync(audio_host, s->audio, (size_t)Ts * s->frame_len * sizeof(float), hipMemcpyDeviceToHost, st));
     FT_HIP(ctx, hipStreamSynchronize(st));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("codec launch: ") + hipGetErrorString(e));
@@ -997,6 +1125,7 @@ extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_code
         if (!sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: null stream");
         if (lens[j] < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: a chunk of less than one frame");
         if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: a stream belongs to another (or a destroyed) context");
+        if (sc->rate) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
         for (int i = 0; i < j; ++i)
             if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: a stream named twice");
         if (lens[j] > c.max_frames || sc->t0 + lens[j] > c.max_frames)
@@ -1030,6 +1159,222 @@ extern "C" ft_status ft_codec_decode(ft_ctx* ctx, const int32_t* codes, int32_t 
         if (Tb == 0) continue;
         FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
     }
+    return FT_OK;
+}
+
+// ---- resampled output (fishtts_hip.h: ft_resample_filter .. ft_codec_stream_decode_many_at, ft_test_resample)
+extern "C" ft_status ft_resample_filter(int32_t sample_rate, int32_t* L, int32_t* M, int32_t* K, float* table) {
+    int l = 1, m = 1, k = 0;
+    std::vector<float> w;
+    if (rs_design(sample_rate, &l, &m, &k, table ? &w : nullptr)) return FT_ERR_ARG;
+    if (L) *L = l;
+    if (M) *M = m;
+    if (K) *K = k;
+    if (table && !w.empty()) memcpy(table, w.data(), w.size() * sizeof(float));
+    return FT_OK;
+}
+
+extern "C" int64_t ft_resampled_len(int32_t sample_rate, int64_t n_in) {
+    int l = 1, m = 1, k = 0;
+    if (n_in < 0 || rs_design(sample_rate, &l, &m, &k, nullptr)) return -1;
+    return (n_in * l + m - 1) / m;
+}
+
+static ft_status rs_refuse(ft_ctx* ctx, const char* fn, int rate) {
+    int l, m, k;
+    const char* e = rs_design(rate, &l, &m, &k, nullptr);
+    return e ? ft_fail(ctx, FT_ERR_ARG, std::string(fn) + ": " + e + " (" + std::to_string(rate) + ")") : FT_OK;
+}
+
+extern "C" ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                        int32_t sample_rate, float* audio, int64_t* out_lens) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(rs_refuse(ctx, "ft_codec_decode_at", sample_rate));
+    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    if (!codes || !audio || !out_lens || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode_at: bad argument");
+    const ft_codec_config& c = ctx->cc;
+    if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_decode_at: T exceeds max_frames");
+    CodecState* s = ctx->codec;
+    const int R = c.n_codebooks + 1;
+    std::vector<int64_t> ol(B);
+    int64_t stride = 0;
+    for (int b = 0; b < B; ++b) {
+        const int Tb = lens ? lens[b] : T;
+        if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode_at: bad length");
+        ol[b] = ft_resampled_len(sample_rate, (int64_t)Tb * s->frame_len);
+        stride = std::max(stride, ol[b]);
+    }
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    const CodecState::RsTab* t = nullptr;
+    FT_TRY(rs_table(ctx, sample_rate, &t));
+    if (t->K > 0) FT_TRY(rs_alloc(ctx));
+    for (int b = 0; b < B; ++b) {
+        const int Tb = lens ? lens[b] : T;
+        float* out = audio + (size_t)b * stride;
+        out_lens[b] = ol[b];
+        if (ol[b] < stride) memset(out + ol[b], 0, (size_t)(stride - ol[b]) * sizeof(float));
+        if (Tb == 0) continue;
+        if (t->K == 0) {
+            FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
+            continue;
+        }
+        // a fresh input: zeros before it, zeros after it (the whole tail)
+        std::vector<RsSeg> g(1, RsSeg{nullptr, t->w, nullptr, nullptr, nullptr, 0, 0, Tb * s->frame_len, (int)ol[b], t->L, t->M, t->K, 0});
+        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, &g));
+    }
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, ft_codec_stream** out) {
+    if (!ctx || !out) return FT_ERR_ARG;
+    FT_TRY(rs_refuse(ctx, "ft_codec_stream_begin_at", sample_rate));
+    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    CodecState* s = ctx->codec;
+    const CodecState::RsTab* t = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        FT_HIP(ctx, hipSetDevice(ctx->device));
+        FT_TRY(rs_table(ctx, sample_rate, &t));
+        if (t->K > 0) FT_TRY(rs_alloc(ctx));
+    }
+    ft_codec_stream* sc = nullptr;
+    FT_TRY(ft_codec_stream_begin(ctx, &sc));
+    if (t->K == 0) {
+        *out = sc;
+        return FT_OK;
+    }
+    bool ok = true;   // (as ft_codec_stream_begin: the stream is not visible to other calls yet)
+    for (int k = 0; k < 2 && ok; ++k) {
+        void* v = nullptr;
+        ok = hipMalloc(&v, (size_t)t->K * sizeof(float)) == hipSuccess;
+        if (!ok) break;
+        sc->owned.push_back(v);
+        sc->rcarry[k] = (float*)v;
+        ok = hipMemsetAsync(v, 0, (size_t)t->K * sizeof(float), s->stream) == hipSuccess;   // the input before the first sample
+    }
+    ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        ft_codec_stream_end(ctx, sc);
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_codec_stream_begin_at: could not set up the resampler carry");
+    }
+    sc->rate = sample_rate;
+    sc->rs = t;
+    *out = sc;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
+                                                    const int32_t* lens, const int32_t* final, float* audio, int64_t* out_lens) {
+    if (!ctx) return FT_ERR_ARG;
+    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    if (n < 1 || !streams || !codes || !lens || !audio || !out_lens)
+        return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: bad argument");
+    if (n > MANY_MAX_STREAMS) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: more than 64 streams in one call");
+    const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
+    if (s->up.empty()) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many_at: needs an up-sampling stage");
+    for (const DecBlock& b : s->blocks)
+        if (MANY_GAP % b.s) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many_at: decoder rates must divide 64");
+    const int fl = s->frame_len;
+    long total = 0;
+    long long total_out = 0;
+    bool any_rate = false;
+    std::vector<long long> no(n);
+    for (int j = 0; j < n; ++j) {
+        const ft_codec_stream* sc = streams[j];
+        const bool fin = final && final[j];
+        if (!sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: null stream");
+        if (lens[j] < 0 || (lens[j] == 0 && !fin))
+            return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: a chunk of less than one frame (zero only with final)");
+        if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: a stream belongs to another (or a destroyed) context");
+        if (sc->finished) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: a stream whose final chunk went out");
+        for (int i = 0; i < j; ++i)
+            if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: a stream named twice");
+        if (lens[j] > c.max_frames || sc->t0 + lens[j] > c.max_frames)
+            return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: stream longer than max_frames (rope table)");
+        total += lens[j];
+        const long long nin = (long long)lens[j] * fl;
+        no[j] = sc->rs ? rs_ready(*sc->rs, sc->nin + nin, fin) - sc->nout : nin;
+        total_out += no[j];
+        any_rate = any_rate || sc->rs;
+    }
+    if (total > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: chunks longer than max_frames together");
+    if (any_rate && (size_t)total_out > s->rs_cap) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: output buffer");
+    // the codec runs over the streams with frames (their code blocks are back to back, as the call's)
+    std::vector<ft_codec_stream*> cs;
+    std::vector<int32_t> cl;
+    for (int j = 0; j < n; ++j)
+        if (lens[j] > 0) { cs.push_back(streams[j]); cl.push_back(lens[j]); }
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!any_rate) {   // the codec's rate only: ft_codec_stream_decode_many
+        if (!cs.empty()) FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio));
+        for (int j = 0; j < n; ++j) out_lens[j] = no[j];
+        return FT_OK;
+    }
+    std::vector<RsSeg> segs(n);
+    long long P = 0;
+    for (int j = 0; j < n; ++j) {
+        const ft_codec_stream* sc = streams[j];
+        RsSeg& g = segs[j];
+        g = RsSeg{s->audio + P * fl, nullptr, nullptr, nullptr, nullptr, sc->nin, sc->nout, lens[j] * fl, (int)no[j], 1, 1, 0, 0};
+        if (sc->rs) {
+            g.w = sc->rs->w; g.L = sc->rs->L; g.M = sc->rs->M; g.K = sc->rs->K;
+            g.carry_rd = sc->rcarry[sc->rpar];
+            g.carry_wr = sc->rcarry[sc->rpar ^ 1];
+        }
+        P += lens[j];
+    }
+    if (!cs.empty()) {
+        FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio, &segs));
+    } else {   // tails only
+        FT_TRY(rs_enqueue(ctx, segs, audio));
+        FT_HIP(ctx, hipStreamSynchronize(s->stream));
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("resample launch: ") + hipGetErrorString(e));
+    }
+    for (int j = 0; j < n; ++j) {
+        ft_codec_stream* sc = streams[j];
+        out_lens[j] = no[j];
+        if (!sc->rs) continue;
+        sc->nin += (long long)lens[j] * fl;
+        sc->nout += no[j];
+        sc->rpar ^= 1;
+        sc->finished = final && final[j];
+    }
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(rs_refuse(ctx, "ft_test_resample", sample_rate));
+    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    if (!x || !y || !n_out || n < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_resample: bad argument");
+    CodecState* s = ctx->codec;
+    if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_resample: longer than max_frames of audio");
+    const int64_t no = ft_resampled_len(sample_rate, n);
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    const CodecState::RsTab* t = nullptr;
+    FT_TRY(rs_table(ctx, sample_rate, &t));
+    *n_out = no;
+    if (t->K == 0) {
+        memcpy(y, x, (size_t)n * sizeof(float));
+        return FT_OK;
+    }
+    FT_TRY(rs_alloc(ctx));
+    FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    std::vector<RsSeg> g(1, RsSeg{s->audio, t->w, nullptr, nullptr, nullptr, 0, 0, (int)n, (int)no, t->L, t->M, t->K, 0});
+    FT_TRY(rs_enqueue(ctx, g, y));
+    FT_HIP(ctx, hipStreamSynchronize(s->stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("resample launch: ") + hipGetErrorString(e));
     return FT_OK;
 }
 

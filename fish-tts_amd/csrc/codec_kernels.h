@@ -1484,4 +1484,63 @@ static __global__ void kv_carry_out_kernel(const bf16_t* qkv, bf16_t* kv_out, in
     }
 }
 
+// ---- polyphase FIR resampler (ft_codec_decode_at, ft_codec_stream_decode_many_at): from the codec rate Fi to Fo = Fi L / M.
+// Output n is the value at input time n M / L (zero phase): with u = n M, i0 = u / L, p = u % L,
+//   y[n] = sum_{t < K} w[p][t] * x[i0 - K/2 + 1 + t],
+// summed in f32 in this order whatever the chunking and however many segments share the launch.  A segment is one stream's
+// (or one utterance's) part of the call; it sits on blockIdx.z.  Input indices below the segment's first sample come from
+// its carry (the K samples before it; none: zeros), indices past its last one are zeros (the final tail).  The block
+// stages its outputs' input window in LDS: (255 M + L - 1) / L + K + 1 <= RS_LDS is checked with the table.
+struct RsSeg {
+    const float* x;          // input samples [nin, nin + n_in) (device; unused when n_in = 0)
+    const float* w;          // [L][K]; null: the native rate, y = x
+    const float* carry_rd;   // input samples [nin - K, nin); null: zeros
+    float* carry_wr;         // receives input samples [nin + n_in - K, nin + n_in); null: not kept
+    float* y;                // outputs [nout, nout + n_out)
+    long long nin, nout;
+    int n_in, n_out, L, M, K, pad;
+};
+constexpr int RS_THREADS = 256, RS_LDS = 2048;
+
+__device__ inline float rs_in(const RsSeg& s, long long i) {
+    if (i < s.nin) {
+        const long long c = i - (s.nin - s.K);
+        return s.carry_rd && c >= 0 ? s.carry_rd[c] : 0.f;
+    }
+    if (i < s.nin + s.n_in) return s.x[i - s.nin];
+    return 0.f;
+}
+
+static __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const RsSeg* segs) {
+    __shared__ float xs[RS_LDS];
+    const RsSeg s = segs[blockIdx.z];
+    if (!s.w) {
+        for (long i = (long)blockIdx.x * RS_THREADS + threadIdx.x; i < s.n_out; i += (long)gridDim.x * RS_THREADS) s.y[i] = s.x[i];
+        return;
+    }
+    // the carry of the next call: a buffer this launch does not read (double-buffered by the caller)
+    if (blockIdx.x == 0 && s.carry_wr) {
+        const long long e = s.nin + s.n_in - s.K;
+        for (int k = threadIdx.x; k < s.K; k += RS_THREADS) s.carry_wr[k] = rs_in(s, e + k);
+    }
+    const int h = s.K / 2;
+    for (long b0 = (long)blockIdx.x * RS_THREADS; b0 < s.n_out; b0 += (long)gridDim.x * RS_THREADS) {
+        const long long na = s.nout + b0, nb = s.nout + min((long)s.n_out, b0 + RS_THREADS) - 1;
+        const long long ia = na * s.M / s.L - h + 1;
+        const int span = (int)(nb * s.M / s.L + h - ia + 1);
+        __syncthreads();
+        for (int k = threadIdx.x; k < span && k < RS_LDS; k += RS_THREADS) xs[k] = rs_in(s, ia + k);
+        __syncthreads();
+        const long n = b0 + threadIdx.x;
+        if (n < s.n_out) {
+            const long long u = (s.nout + n) * s.M, i0 = u / s.L;
+            const float* wp = s.w + (size_t)(u - i0 * s.L) * s.K;
+            const float* xp = xs + (i0 - h + 1 - ia);
+            float acc = 0.f;
+            for (int t = 0; t < s.K; ++t) acc += wp[t] * xp[t];
+            s.y[n] = acc;
+        }
+    }
+}
+
 }  // namespace ft

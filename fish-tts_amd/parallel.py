@@ -54,15 +54,18 @@ def deal_utterances(lengths: Sequence[int], world: int) -> List[List[int]]:
     return out
 
 
-def synthesize_sharded(tts, texts: Sequence[str], dst: int = 0, **kw):
+def synthesize_sharded(tts, texts: Sequence[str], dst: int = 0, sample_rate: Optional[int] = None, **kw):
     """BASELINE configs[3] (a large batch across the GPUs of one node): every rank (one process per GPU, its own
     `FishTTS(max_batch=...)`) synthesises the share `deal_utterances` gives it - texts dealt by length, longest first -
     in its own lock-step batch; rank `dst` receives the WAV bytes of all texts in input order (others get None).  The
-    only communication is the final gather of results; nothing crosses GPUs while decoding."""
+    only communication is the final gather of results; nothing crosses GPUs while decoding.  `sample_rate`: as
+    FishTTS.synthesize_batch."""
     import torch.distributed as dist
     world, rank = dist.get_world_size(), dist.get_rank()
     share = deal_utterances([len(t) for t in texts], world)[rank]
     seed = kw.pop("seed", 0)
+    if sample_rate is not None:
+        kw["sample_rate"] = sample_rate
     # utterance i draws with seed + i whatever the world size and whatever else its rank was dealt
     wavs = tts.synthesize_batch([texts[i] for i in share], seeds=[seed + i for i in share], **kw) if share else []
     gathered = [None] * world if rank == dst else None

@@ -239,13 +239,25 @@ class FishTTS:
     # ------------------------------------------------------------------ synthesis
     def synthesize(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                    top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048) -> bytes:
-        """Text -> WAV bytes (synthesizer.py:431-481).  While a BatchServer is open (serve()) the call joins its batch."""
+        """Text -> WAV bytes (synthesizer.py:431-481).  While a BatchServer is open (serve()) the call joins its batch.
+        The reference's signature; synthesize_at also takes an output sample rate."""
+        return self.synthesize_at(text, references, temperature, top_p, repetition_penalty, max_tokens)
+
+    def synthesize_at(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
+                      top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
+                      sample_rate: Optional[int] = None) -> bytes:
+        """Extension: synthesize() with the WAV at `sample_rate` (resampled on the GPU; None or 44100: the codec's own
+        rate, byte for byte synthesize()'s result; an unsupported rate raises ValueError before any work -
+        codec_engine.output_rate)."""
         from .generation import generate_long
         from .serve import ServerClosed
+        rate = output_rate(sample_rate)
         srv = getattr(self, "_server", None)
         if srv is not None:
             try:
-                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens)
+                if rate is None:
+                    return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens)
+                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens, sample_rate=rate)
             except ServerClosed:
                 pass                          # closed meanwhile: served here, once the server has let go of _gen_lock
         prompt_text, prompt_tokens = self._get_prompt_data(references)
@@ -261,7 +273,9 @@ class FishTTS:
                     break
         if not codes_list:
             raise RuntimeError("No audio generated")
-        return self._decode_to_wav(np.concatenate(codes_list, axis=1))
+        if rate is None:
+            return self._decode_to_wav(np.concatenate(codes_list, axis=1))
+        return self._decode_to_wav(np.concatenate(codes_list, axis=1), rate)
 
     def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
                           repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]]):
@@ -298,12 +312,14 @@ class FishTTS:
 
     def synthesize_batch(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
                          temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
-                         max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None) -> List[bytes]:
+                         max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None,
+                         sample_rate: Optional[int] = None) -> List[bytes]:
         """Extension (BASELINE configs[2]): many texts -> WAV bytes each, decoded `max_batch` at a time in lock step
         with refill (fish_tts_amd.batch); utterance i uses seed + i, or seeds[i] when `seeds` is given (a sharded run
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
-        semantics as synthesize()."""
+        semantics as synthesize(), `sample_rate` included."""
         from .batch import run_batch, run_batch_streams
+        rate = output_rate(sample_rate)
         self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
@@ -317,13 +333,14 @@ class FishTTS:
             codes = u.codes()
             if codes.shape[1] == 0:
                 raise RuntimeError("No audio generated")
-            out.append(self._decode_to_wav(codes))
+            out.append(self._decode_to_wav(codes) if rate is None else self._decode_to_wav(codes, rate))
         return out
 
     def synthesize_batch_stream(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
                                 chunk_tokens: int = 20, min_first_chunk: int = 10, temperature: float = 0.7,
                                 top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
-                                seed: int = 0, seeds: Optional[List[int]] = None) -> Iterator[Tuple[int, bytes]]:
+                                seed: int = 0, seeds: Optional[List[int]] = None,
+                                sample_rate: Optional[int] = None) -> Iterator[Tuple[int, bytes]]:
         """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
         PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
         `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
@@ -331,9 +348,12 @@ class FishTTS:
         engines, seeds, K/V prefixes); its PCM concatenates to one stateful streamed decode of them (CodecStream), bit
         for bit, whatever else is in flight: the codec worker decodes every ready chunk in one batched call
         (CodecHipEngine.decode_streams, one chunk per utterance).  Generation holds _gen_lock on its own thread;
-        abandoning the generator stops it within one burst and releases the lock (fish_tts_amd.batch_stream)."""
+        abandoning the generator stops it within one burst and releases the lock (fish_tts_amd.batch_stream).
+        `sample_rate` (as synthesize_at): each utterance's stream resamples on the GPU; the chunk before its (i, b"") holds
+        the resampler's tail, so its PCM concatenates to the resampled waveform of one streamed decode."""
         from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
+        rate = output_rate(sample_rate)
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
@@ -348,8 +368,11 @@ class FishTTS:
                 else:
                     run_batch(self._engine, utts, on_frames=on_frames, on_done=on_done)
 
+        if rate is None:
+            return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
+                                     min_first_chunk=min_first_chunk)
         return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
-                                 min_first_chunk=min_first_chunk)
+                                 min_first_chunk=min_first_chunk, sample_rate=rate)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
@@ -366,9 +389,14 @@ class FishTTS:
         longer synthesis starts a fresh stream there - that one boundary is decoded from zero state, as the reference
         decodes every chunk.
 
-        While a BatchServer is open (serve()) the request joins its batch (BatchServer.synthesize_stream)."""
+        While a BatchServer is open (serve()) the request joins its batch (BatchServer.synthesize_stream).
+
+        Extension `sample_rate=` (keyword, as synthesize_at; checked at the first next()): seamless=False chunks are
+        resampled each on its own, as independent waveforms; a seamless stream resamples through one carried resampler
+        (a last PCM chunk holds its tail), so its chunks concatenate to the resampled waveform of one streamed decode."""
         from .generation import generate_long
         from .serve import ServerClosed
+        rate = output_rate(kwargs.get("sample_rate"))
         srv = getattr(self, "_server", None)
         if srv is not None:
             chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, **kwargs)
@@ -398,19 +426,23 @@ class FishTTS:
                 if seamless:
                     if self._vocoder is None:
                         raise RuntimeError("Vocoder not loaded")
-                    stream = self._vocoder.stream()     # carried state: K/V of the last 127 frames, conv tails
+                    stream = self._vocoder.stream(rate)  # carried state: K/V of the last 127 frames, conv tails
                 while True:
                     codes = codes_queue.get()
                     if codes is None:
                         break
                     if stream is None:
-                        audio_queue.put(self._decode_to_pcm(codes))
+                        audio_queue.put(self._decode_to_pcm(codes) if rate is None else self._decode_to_pcm(codes, rate))
                     else:
                         codes = np.asarray(codes)
                         if stream.frames + codes.shape[1] > self._vocoder.max_frames:   # the rotation table ends here
+                            if rate is not None:                # the old stream's resampler tail first
+                                audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())
                             stream.close()
-                            stream = self._vocoder.stream()
+                            stream = self._vocoder.stream(rate)
                         audio_queue.put((stream.decode(codes) * 32767).astype(np.int16).tobytes())
+                if stream is not None and rate is not None:
+                    audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())   # the resampler's tail
             except Exception as e:  # noqa: BLE001
                 error_holder.append(e)
             finally:
@@ -561,20 +593,24 @@ class FishTTS:
         return Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seed), n_prefix
 
     # ------------------------------------------------------------------ codes -> audio (synthesizer.py:586-648)
-    def _decode_to_wav(self, codes: np.ndarray) -> bytes:
-        return self._to_wav_bytes(self._decode_codes(codes))
+    def _decode_to_wav(self, codes: np.ndarray, sample_rate: Optional[int] = None) -> bytes:
+        if sample_rate is None:
+            return self._to_wav_bytes(self._decode_codes(codes))
+        return self._to_wav_bytes(self._decode_codes(codes, sample_rate), sample_rate)
 
-    def _decode_to_pcm(self, codes: np.ndarray) -> bytes:
-        audio = self._decode_codes(codes)
+    def _decode_to_pcm(self, codes: np.ndarray, sample_rate: Optional[int] = None) -> bytes:
+        audio = self._decode_codes(codes) if sample_rate is None else self._decode_codes(codes, sample_rate)
         return (audio * 32767).astype(np.int16).tobytes()  # no clip on the PCM path (synthesizer.py:594)
 
-    def _decode_codes(self, codes: np.ndarray) -> np.ndarray:
+    def _decode_codes(self, codes: np.ndarray, sample_rate: Optional[int] = None) -> np.ndarray:
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
-        return np.squeeze(self._vocoder.decode(codes))
+        if sample_rate is None:
+            return np.squeeze(self._vocoder.decode(codes))
+        return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate), axis=0)
 
     @staticmethod
     def _to_wav_bytes(audio: np.ndarray, sample_rate: int = 44100) -> bytes:
@@ -595,6 +631,12 @@ class FishTTS:
     @property
     def precision(self) -> str:
         return self._precision
+
+
+def output_rate(sample_rate: Optional[int]) -> Optional[int]:
+    """codec_engine.output_rate (imported when first needed, as the engines are)."""
+    from .codec_engine import output_rate as check
+    return check(sample_rate)
 
 
 def get_instance(model_dir=None, device: Literal["cpu", "cuda"] = "cuda",

@@ -178,6 +178,38 @@ void ft_codec_stream_end(ft_ctx* ctx, ft_codec_stream* st);
  * chunks, carry pointers and codes (< 1 MB); it lives as long as the context. */
 ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
                                       const int32_t* lens, float* audio);
+/* Resampled output.  The codec runs at Fi = 44100 Hz; these calls give its waveform at a caller-chosen rate Fo through a
+ * polyphase FIR resampler on the device (Fo / Fi reduced to L / M; output n is the value at input time n M / L, the
+ * filter's delay compensated).  Weights: a Kaiser-windowed sinc, pass band to 0.43 min(Fi, Fo) (<= 0.01 dB ripple), stop
+ * band from 0.5 min(Fi, Fo) (>= 70 dB), designed once per rate on the host in float64 and kept as float32 [L][K] (phase p,
+ * tap t: output n with n M = i0 L + p sums w[p][t] x[i0 - K/2 + 1 + t] over t = 0 .. K-1 in that order, in float32).
+ * Accepted rates: integers in [8000, 48000] whose L is at most 640 (8000, 11025, 12000, 16000, 22050, 24000, 32000,
+ * 48000 among them); 44100 takes the codec's own path and runs no resampler.  Anything else is FT_ERR_ARG before any
+ * device work.  The reference returns 44.1 kHz only (synthesizer.py:431-481). */
+/* Host only (no context, no device): validates the rate; L, M, K (K = 0 at 44100) and, if `table` is non-null, the
+ * L x K weights.  Any output pointer may be NULL. */
+ft_status ft_resample_filter(int32_t sample_rate, int32_t* L, int32_t* M, int32_t* K, float* table);
+/* ceil(n_in L / M) - the samples n_in codec samples give at sample_rate; -1 for a refused rate. */
+int64_t ft_resampled_len(int32_t sample_rate, int64_t n_in);
+/* ft_codec_decode at sample_rate: utterance b yields out_lens[b] = ft_resampled_len(sample_rate, lens[b] * frame_len)
+ * samples (zeros before and after it), zero-padded past its end; audio: B x max(out_lens) float32 (host). */
+ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                             int32_t sample_rate, float* audio, int64_t* out_lens);
+/* A streamed decode whose output is at sample_rate (44100: ft_codec_stream_begin).  Besides the codec's carries, such a
+ * stream keeps the last K input samples (two copies: a call reads one and writes the other) and its input / output
+ * sample counters.  ft_codec_stream_decode and ft_codec_stream_decode_many refuse it (FT_ERR_STATE). */
+ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, ft_codec_stream** out);
+/* ft_codec_stream_decode_many for streams of any rate, mixed in one call.  A chunk emits the outputs whose taps all lie
+ * within the input seen so far (floor(n M / L) + K/2 < samples in); final[j] = 1 (final may be NULL: none) also emits
+ * the rest, the input taken as zero past its end - the stream's outputs then number ft_resampled_len(rate, samples in) -
+ * and closes the stream (a later chunk is FT_ERR_STATE).  lens[j] = 0 is allowed with final[j] = 1 (the tail alone).
+ * audio: the streams' outputs back to back, out_lens[j] samples each; stream j emits at most
+ * ft_resampled_len(rate, samples in after the chunk) minus what it emitted before.  A 44100 stream emits its chunk's
+ * samples as ft_codec_stream_decode_many does (final changes nothing there).  Each stream's samples do not depend on
+ * the chunking or on the other streams of the call.  Refusals (FT_ERR_ARG, FT_ERR_STATE, FT_ERR_TOO_LONG) as
+ * ft_codec_stream_decode_many, before any device work, every stream unchanged. */
+ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
+                                         const int32_t* lens, const int32_t* final, float* audio, int64_t* out_lens);
 /* Codec encode = vocoder.encode(audio, lengths) of encode_reference (synthesizer.py:325-357, vocoder.py:885-904):
  * mono f32 audio at the codec sample rate (host), right-padded to whole frames -> codes (num_codebooks+1) x T'
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */

@@ -45,6 +45,10 @@ ft_status ft_test_engine_fault(ft_ctx* ctx, int32_t which, int32_t wg, int32_t s
 ft_status ft_test_sample(ft_ctx* ctx, const float* logits, int32_t cb, const ft_sampling* sp,
                          const int32_t* window, const float* q, int32_t* out_index);
 
+/* Test hook: the resampler of ft_codec_decode_at on a host waveform x of n <= max_frames * frame_len samples at 44100
+ * (zeros before and after it) -> y: *n_out = ft_resampled_len(sample_rate, n) samples. */
+ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
