@@ -61,7 +61,9 @@ def contiguous_runs(slots: Sequence[int]) -> list:
 
 
 class ARHipEngine:
-    """One GPU context holding the dual-AR weights, KV caches and the captured frame graph."""
+    """One GPU context holding the dual-AR weights, KV caches and the captured frame graph.  Batch-1 frames: the
+    persistent frame engine (bf16) or launches; lock-step batches of >= 5 rows: five MFMA launches per layer in bf16 and
+    fp16, the multi-row GEMV launches in fp32 (frame_path() says which)."""
 
     def __init__(self, args: DualARModelArgs, semantic_begin_id: int, semantic_end_id: int, im_end_id: int,
                  precision: str = "bf16", device: int = 0, max_batch: int = 1, max_new_tokens: int = 2048,
@@ -158,7 +160,9 @@ class ARHipEngine:
         logger.info("batch-1 decode frames: %s", self.frame_path())
 
     def frame_path(self) -> str:
-        """Which path the batch-1 frames take (persistent frame engine or launches) and why."""
+        """Which path the batch-1 frames take (persistent frame engine or launches) and why, then what a lock-step batch
+        runs on: "MFMA launches" (bf16 and fp16 at the widths csrc/wide_kernels.h covers, from 5 rows) or the multi-row
+        GEMV launches.  batch.run_batch and serve.BatchServer key their 2..4-row rule on that text."""
         return self.lib.ft_ar_frame_path(self._h).decode()
 
     def inject_engine_fault(self, which: int = 0, workgroup: int = 0, skip: int = 0) -> None:

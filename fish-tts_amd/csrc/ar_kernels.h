@@ -310,7 +310,7 @@ struct EmbedP {
     float* x;
     int ldx, D, ncb, cbsize, vocab, sem_begin, sem_end, scale;
     float inv_div;  // (float)sqrt(ncb+1), used as a divisor
-    bf16_t* xo;     // optional octet-major bf16 copy of x (lock-step batches: the residual stream of wide_kernels.h)
+    bf16_t* xo;     // optional octet-major 16-bit copy of x (lock-step batches: the residual stream of wide_kernels.h; fp16 bits in fp16 models)
     int xo_ldm;
 };
 
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void embed_kernel(EmbedP p) {
         float x = rb<ROUND>(ld_elem(emb, (size_t)t0 * p.D + d) + vq);
         if (p.scale && is_vq) x = rb<ROUND>(x / p.inv_div);
         p.x[(size_t)m * p.ldx + d] = x;
-        if (p.xo) p.xo[xo_index(m, d, p.xo_ldm)] = f32_to_bf16_bits(x);
+        if (p.xo) p.xo[xo_index(m, d, p.xo_ldm)] = h16_bits<WT>(x);
     }
 }
 
@@ -378,7 +378,7 @@ struct AttnP {
     // prefill: grid.z indexes prompt positions (pos = pos_off + z, one shared cache); pass 1 appends K/V
     // for every position (kv_only), pass 2 attends reading every key from the cache (no_append)
     int row_is_pos, kv_only, no_append;
-    bf16_t* y_bf;    // optional bf16 copy of y
+    bf16_t* y_bf;    // optional 16-bit copy of y (bf16; fp16 bits in fp16 models, which use it for wide batches only)
     int y_xo_ldm;    // > 0: y_bf is octet-major Xo[H * hd / 8][y_xo_ldm][8] (wide_kernels.h), and y may be null
     bf16_t* q_out;   // kv_only pass: the normalised, rotated queries [row][H*hd] for the MFMA prompt attention
     const int2* row_sp;  // ragged prompt pass of several slots (prefill_rope_append_kernel): row -> (slot, cache position);
@@ -542,7 +542,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnP p) {
         if (p.nsplit == 1) {
             const float yo = rb<ROUND>(O / L);
             if (p.y) p.y[(size_t)m * p.ldy + head * hd + e] = yo;
-            if (p.y_bf) p.y_bf[p.y_xo_ldm ? xo_index(m, head * hd + e, p.y_xo_ldm) : (size_t)m * p.ldy + head * hd + e] = f32_to_bf16_bits(yo);
+            if (p.y_bf) p.y_bf[p.y_xo_ldm ? xo_index(m, head * hd + e, p.y_xo_ldm) : (size_t)m * p.ldy + head * hd + e] = h16_bits<WT>(yo);
         } else {
             const size_t pi = ((size_t)m * p.H + head) * p.nsplit + split;
             p.part_o[pi * hd + e] = O;
@@ -605,16 +605,16 @@ __global__ __launch_bounds__(256) void prefill_rope_append_kernel(AttnP p) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Slow-layer decode attention of WIDE lock-step batches (bf16, wide_kernels.h): one block per (kv head, row) walks the row's
+// Slow-layer decode attention of WIDE lock-step batches (bf16 or fp16, wide_kernels.h): one block per (kv head, row) walks the row's
 // whole context.  Same inputs, rounding points and cache append as attn_decode_kernel (q/k nn.RMSNorm, interleaved RoPE,
 // f32 scores and probabilities, one rounding of y), but the softmax is taken in two passes - all scores to LDS, the
 // exact maximum, then the weighted sum - instead of an online softmax per lane group: no exponentials or rescaling on
 // the per-position chain, every K row of up to 128 positions (and the first V rows) in flight from the first
 // instruction.  Sums run in another order than the single-utterance kernel; wide batches are judged against the oracle
-// with the bf16 margin (tests/test_ar_gpu.py: test_wide_batch_vs_oracle), not bit for bit.
+// with the precision's margin (tests/test_ar_gpu.py: test_wide_batch_vs_oracle, tests/test_wide_fp16_gpu.py), not bit for bit.
 // LDS: (G + 2) HD + 16 G + NSLOT G HD + G n_sc floats, n_sc >= the longest context + 1.
 // ------------------------------------------------------------------------------------------
-template <int G, int HD>
+template <int G, int HD, typename WT = bf16_t, int ROUND = RND_BF16>
 __global__ __launch_bounds__(256) void attn_wide_kernel(AttnP p, int n_sc) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int LPP = HD / 8, PPW = 64 / LPP, NSLOT = 4 * PPW, U = 8, HP = HD / 2;
@@ -629,10 +629,10 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(AttnP p, int n_sc) {
     float* sc = acc_s + NSLOT * G * HD;     // [G][n_sc]
     const int pos = p.pos[m] + p.pos_off;   // cached positions 0 .. pos-1, the new one is pos
     const int n = pos + 1;
-    bf16_t* kc = reinterpret_cast<bf16_t*>(p.kc) + (size_t)m * p.cache_m_stride + (size_t)kvh * p.n_slots * HD;
-    bf16_t* vc = reinterpret_cast<bf16_t*>(p.vc) + (size_t)m * p.cache_m_stride + (size_t)kvh * p.n_slots * HD;
+    WT* kc = reinterpret_cast<WT*>(p.kc) + (size_t)m * p.cache_m_stride + (size_t)kvh * p.n_slots * HD;
+    WT* vc = reinterpret_cast<WT*>(p.vc) + (size_t)m * p.cache_m_stride + (size_t)kvh * p.n_slots * HD;
     U4 kraw[U], vraw[U];
-    auto load_rows = [&](const bf16_t* base, U4 (&r)[U], int base0) {
+    auto load_rows = [&](const WT* base, U4 (&r)[U], int base0) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = base0 + u * NSLOT + slot;
@@ -643,11 +643,11 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(AttnP p, int n_sc) {
     load_rows(vc, vraw, 0);
     // ---- q heads of this group, new k, new v (attn_decode_kernel phase 1; the rotation entries are requested with the inputs)
     const float* qkv = p.qkv + (size_t)m * p.ldq;
-    const bf16_t* qn = reinterpret_cast<const bf16_t*>(p.qn);
-    const bf16_t* kn = reinterpret_cast<const bf16_t*>(p.kn);
+    const WT* qn = reinterpret_cast<const WT*>(p.qn);
+    const WT* kn = reinterpret_cast<const WT*>(p.kn);
     for (int item = wave; item < G + 2; item += 4) {
         const float* src;
-        const bf16_t* gain = nullptr;
+        const WT* gain = nullptr;
         float* dst;
         if (item < G) { src = qkv + (size_t)(kvh * G + item) * HD; gain = qn; dst = q_s + item * HD; }
         else if (item == G) { src = qkv + (size_t)(p.H + kvh) * HD; gain = kn; dst = k_new; }
@@ -664,19 +664,19 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(AttnP p, int n_sc) {
             if (gain) {
                 const float ss = wave_sum(x0 * x0 + x1 * x1);
                 const float inv = rsqrt_exact(ss / (float)HD + p.eps);
-                x0 = round_bf16((x0 * inv) * g0);
-                x1 = round_bf16((x1 * inv) * g1);
+                x0 = rb<ROUND>((x0 * inv) * g0);
+                x1 = rb<ROUND>((x1 * inv) * g1);
             }
             if (lane < HP) {
-                dst[2 * lane] = round_bf16(x0 * c - x1 * sn);
-                dst[2 * lane + 1] = round_bf16(x1 * c + x0 * sn);
+                dst[2 * lane] = rb<ROUND>(x0 * c - x1 * sn);
+                dst[2 * lane + 1] = rb<ROUND>(x1 * c + x0 * sn);
             }
         }
     }
     __syncthreads();
     for (int e = tid; e < HD; e += 256) {      // llama.py:142-149
-        kc[(size_t)pos * HD + e] = f32_to_bf16_bits(k_new[e]);
-        vc[(size_t)pos * HD + e] = f32_to_bf16_bits(v_new[e]);
+        st_elem(kc, (size_t)pos * HD + e, k_new[e]);
+        st_elem(vc, (size_t)pos * HD + e, v_new[e]);
     }
     // ---- pass 1: scores of every position, the maximum per head
     float qr[G][8];
@@ -694,7 +694,7 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(AttnP p, int n_sc) {
             if (base0 + u * NSLOT >= n) break;
             const int j = base0 + u * NSLOT + slot;
             float kv[8];
-            Vec<bf16_t>::unpack(kraw[u], kv);
+            Vec<WT>::unpack(kraw[u], kv);
             if (j == pos) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) kv[e] = k_new[gl * 8 + e];
@@ -750,7 +750,7 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(AttnP p, int n_sc) {
             const int j = base0 + u * NSLOT + slot;
             if (j < n) {
                 float vv[8];
-                Vec<bf16_t>::unpack(vraw[u], vv);
+                Vec<WT>::unpack(vraw[u], vv);
                 if (j == pos) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) vv[e] = v_new[gl * 8 + e];
@@ -775,10 +775,10 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(AttnP p, int n_sc) {
 #pragma unroll
         for (int sl = 0; sl < NSLOT; ++sl) O += acc_s[(size_t)(sl * G + g) * HD + e];
         const float L = ((red[4 * G + g] + red[5 * G + g]) + red[6 * G + g]) + red[7 * G + g];
-        const float yo = round_bf16(O / L);
+        const float yo = rb<ROUND>(O / L);
         const int head = kvh * G + g;
         if (p.y) p.y[(size_t)m * p.ldy + head * HD + e] = yo;
-        if (p.y_bf) p.y_bf[p.y_xo_ldm ? xo_index(m, head * HD + e, p.y_xo_ldm) : (size_t)m * p.ldy + head * HD + e] = f32_to_bf16_bits(yo);
+        if (p.y_bf) p.y_bf[p.y_xo_ldm ? xo_index(m, head * HD + e, p.y_xo_ldm) : (size_t)m * p.ldy + head * HD + e] = h16_bits<WT>(yo);
     }
 }
 constexpr int attn_wide_lds_floats(int G, int HD, int n_sc) { return (G + 2) * HD + 8 * G + 4 * (64 / (HD / 8)) * G * HD + G * n_sc; }
@@ -866,7 +866,7 @@ __global__ __launch_bounds__(256) void attn_combine_rows_kernel(AttnP a) {
         }
         if (a.y_bf) {
             bf16_t* yb = a.y_bf + (a.y_xo_ldm ? xo_index(m, k, a.y_xo_ldm) : (size_t)m * a.ldy + k);   // k % 4 == 0: inside one octet
-            yb[0] = f32_to_bf16_bits(y0); yb[1] = f32_to_bf16_bits(y1); yb[2] = f32_to_bf16_bits(y2); yb[3] = f32_to_bf16_bits(y3);
+            yb[0] = h16_bits_r<ROUND>(y0); yb[1] = h16_bits_r<ROUND>(y1); yb[2] = h16_bits_r<ROUND>(y2); yb[3] = h16_bits_r<ROUND>(y3);
         }
     }
 }
@@ -889,7 +889,7 @@ struct FastAttnP {
     int c;              // codebook position of this step (0..ncb-1)
     int H, Hkv, hd, ncb;
     float eps, scale;
-    bf16_t* y_bf;       // optional bf16 copy of y (operand of the MFMA Wo GEMM in wide batches)
+    bf16_t* y_bf;       // optional 16-bit copy of y (operand of the MFMA Wo GEMM in wide batches; fp16 bits in fp16 models)
     int y_xo_ldm;       // > 0: y_bf is octet-major Xo[H * hd / 8][y_xo_ldm][8] (wide_kernels.h), and y may be null
     // paired pass of a wide batch (pair_M > 0, c == 0): grid.y = 2 pair_M; block y < pair_M is utterance y at position 0 (row y
     // of qkv / y_bf), block y >= pair_M is utterance y - pair_M at position 1 (row pair_off + y - pair_M).  The position-1
@@ -1027,7 +1027,7 @@ __global__ __launch_bounds__(64) void fast_attn_kernel(FastAttnP a, float* y, in
         if (d < hd) {
             const float yo = rb<ROUND>(o[e]);
             if (y) y[(size_t)m * ldy + (size_t)h * hd + d] = yo;
-            if (a.y_bf) a.y_bf[a.y_xo_ldm ? xo_index(m, h * hd + d, a.y_xo_ldm) : (size_t)m * ldy + (size_t)h * hd + d] = f32_to_bf16_bits(yo);
+            if (a.y_bf) a.y_bf[a.y_xo_ldm ? xo_index(m, h * hd + d, a.y_xo_ldm) : (size_t)m * ldy + (size_t)h * hd + d] = h16_bits<WT>(yo);
         }
     }
 }
@@ -1068,11 +1068,11 @@ struct SampP {
     int* tok;         // [M][ncb+1] input column of the next slow step
     int* pos;
     int* done;
-    bf16_t* femb_xo;  // optional octet-major bf16 copy of femb (lock-step batches, wide_kernels.h)
+    bf16_t* femb_xo;  // optional octet-major 16-bit copy of femb (lock-step batches, wide_kernels.h; fp16 bits in fp16 models)
     int femb_ldm;
     // wide batches: layer 0's q k v of the NEXT codebook step is a row of a table indexed by the drawn code (its input is
     // that code's embedding): the draw leaves the row where the step's attention reads it, and the step skips that launch
-    const bf16_t* qkv0_tab;   // [codes][qkv0_n] or null
+    const bf16_t* qkv0_tab;   // [codes][qkv0_n] or null (16-bit elements of the model's type)
     float* qkv0_out;          // [M][qkv0_n]
     int qkv0_n;
 };
@@ -1178,13 +1178,13 @@ __device__ __forceinline__ void finish_draw(const SampP& p, const int m, const i
     for (int d = tid; d < p.Df; d += T) {
         const float v = ld_elem(fe, (size_t)code * p.Df + d);
         p.femb[(size_t)m * p.Df + d] = v;
-        if (p.femb_xo) p.femb_xo[xo_index(m, d, p.femb_ldm)] = f32_to_bf16_bits(v);
+        if (p.femb_xo) p.femb_xo[xo_index(m, d, p.femb_ldm)] = h16_bits<WT>(v);
     }
     if (tab16) {
         float* qo = p.qkv0_out + (size_t)m * p.qkv0_n;
         auto put8 = [&](int d, const U4& r) {
             float v[8];
-            Vec<bf16_t>::unpack(r, v);
+            Vec<typename H16<WT>::T>::unpack(r, v);
             *reinterpret_cast<float4*>(qo + d) = float4{v[0], v[1], v[2], v[3]};
             *reinterpret_cast<float4*>(qo + d + 4) = float4{v[4], v[5], v[6], v[7]};
         };
@@ -1197,7 +1197,7 @@ __device__ __forceinline__ void finish_draw(const SampP& p, const int m, const i
             put8(d, *reinterpret_cast<const U4*>(p.qkv0_tab + (size_t)code * p.qkv0_n + d));
     } else if (p.qkv0_tab) {
         for (int d = tid; d < p.qkv0_n; d += T)
-            p.qkv0_out[(size_t)m * p.qkv0_n + d] = bf16_bits_to_f32(p.qkv0_tab[(size_t)code * p.qkv0_n + d]);
+            p.qkv0_out[(size_t)m * p.qkv0_n + d] = ld_elem(reinterpret_cast<const typename H16<WT>::T*>(p.qkv0_tab), (size_t)code * p.qkv0_n + d);
     }
     if (p.last) {
         // a slot that has emitted <|im_end|> (or is parked) stays frozen while the rest of the lock-step batch

@@ -49,6 +49,14 @@ __device__ __forceinline__ uint16_t f32_to_f16_bits(float x) {
 enum { RND_NONE = 0, RND_BF16 = 1, RND_F16 = 2 };
 template <int ROUND> __device__ __forceinline__ float rb(float x) { return ROUND == 1 ? round_bf16(x) : ROUND == 2 ? round_f16(x) : x; }
 
+// the 16-bit operand copies of the wide lock-step batches (wide_kernels.h) are kept as raw bits: fp16 models write IEEE
+// half there, every other instantiation bf16 (H16<WT>::T is the element type those bits then have)
+template <typename WT> struct H16 { typedef bf16_t T; };
+template <> struct H16<f16_t> { typedef f16_t T; };
+template <typename WT> __device__ __forceinline__ uint16_t h16_bits(float x) { return f32_to_bf16_bits(x); }
+template <> __device__ __forceinline__ uint16_t h16_bits<f16_t>(float x) { return f32_to_f16_bits(x); }
+template <int ROUND> __device__ __forceinline__ uint16_t h16_bits_r(float x) { return ROUND == RND_F16 ? f32_to_f16_bits(x) : f32_to_bf16_bits(x); }
+
 // element load/store for the storage types the engine supports (bf16 bits, fp16, f32)
 __device__ __forceinline__ float ld_elem(const bf16_t* p, size_t i) { return bf16_bits_to_f32(p[i]); }
 __device__ __forceinline__ float ld_elem(const f16_t* p, size_t i) { return f16_bits_to_f32(p[i].bits); }

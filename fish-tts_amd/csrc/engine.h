@@ -72,8 +72,9 @@ struct ft_ctx {
     int4* pf_seqs = nullptr;
     int2* pf_rows = nullptr;
     // lock-step batches of >= wide_min utterances run every Linear as one MFMA launch with the row operations folded in
-    // (wide_kernels.h); their activations are octet-major bf16 Xo[width / 8][xo_ldm][8]: residual streams of the slow and
-    // the fast stack, the drawn codes' embeddings, the attention output, the SwiGLU vector
+    // (wide_kernels.h); their activations are octet-major 16-bit elements Xo[width / 8][xo_ldm][8] (bf16 or fp16 bits by the
+    // model's precision, declared bf16_t): residual streams of the slow and the fast stack, the drawn codes' embeddings, the
+    // attention output, the SwiGLU vector
     ft::bf16_t *xo_x = nullptr, *xo_xf = nullptr, *xo_femb = nullptr, *xo_y = nullptr, *xo_g = nullptr;
     ft::bf16_t* wide_qkv0_tab = nullptr;   // [fastV][fast qkv width]: layer 0's q k v of the codebook steps >= 2 by drawn code (wide batches)
     int xo_ldm = 0;     // rows of an octet: 2 x xo_pair
@@ -81,7 +82,7 @@ struct ft_ctx {
     bool no_attn_wide = false;   // FT_NO_ATTN_WIDE: wide batches keep the online-softmax attention kernel of the single rows
     bool no_head_stream = false; // FT_NO_HEAD_STREAM: the vocabulary head of a wide batch on the general wide launch
     bool no_pair = false;   // FT_NO_PAIR: codebook positions 0 and 1 as two passes (the comparison a parity test makes)
-    int wide_min = 5;   // measured: the MFMA path wins from 5 rows (B=5: 2.79 vs 3.33 ms per frame), B <= 4 keeps the bit-exact multi-row GEMV
+    int wide_min = 5;   // measured: the MFMA path wins from 5 rows (B=5: 2.79 vs 3.33 ms per frame in bf16, 4.11 vs 5.58 in fp16), B <= 4 keeps the bit-exact multi-row GEMV
     bool wide_ok = false;
     bool prefill_v0 = false;
     int prefill_gemm_mode = 2;

@@ -203,8 +203,11 @@ static ft_status ar_alloc(ft_ctx* ctx) {
         FT_TRY(dmalloc(ctx, &ctx->pf_qbf, S * c.n_head * c.head_dim));
         FT_TRY(dmalloc(ctx, &ctx->pf_seqs, M));
         FT_TRY(dmalloc(ctx, &ctx->pf_rows, S));
+    }
+    if (c.dtype == FT_F16 || !ctx->prefill_v0) {
         // wide lock-step batches (wide_kernels.h): no fast-layer f32 bias copies exist; every contraction width must be one
         // the kernel is instantiated for, every output width a whole number of its tiles
+        // (both 16-bit types; the pf_* prompt buffers above are bf16 only: ft_ar_prefill_slow_many)
         const int HD = c.n_head * c.head_dim, HDf = c.fast_n_head * c.fast_head_dim;
         ctx->wide_ok = !getenv("FT_NO_WIDE") && !c.fast_attention_qkv_bias && !c.fast_attention_o_bias && c.fast_dim == c.dim &&
                        wide_k_ok(c.dim) && wide_k_ok(HD) && wide_k_ok(c.intermediate_size) && wide_k_ok(HDf) && wide_k_ok(c.fast_intermediate_size) &&
@@ -408,16 +411,20 @@ static ft_status ar_finalize(ft_ctx* ctx) {
         return FT_OK;
     };
     FT_TRY(fill(ctx->layers, "layers.", c.intermediate_size, c.dim));
-    if (!ctx->prefill_v0) {
+    if (!ctx->prefill_v0 || ctx->wide_ok) {      // f32 bias copies of the MFMA epilogues (prompt pass: bf16; wide batches: both 16-bit types)
         const int qkvN = (c.n_head + 2 * c.n_local_heads) * c.head_dim;
+        auto to_f32 = [&](const void* b, float* o, int n) {
+            if (c.dtype == FT_F16) convert_kernel<f16_t, float><<<(n + 255) / 256, 256, 0, ctx->stream>>>((const f16_t*)b, o, n);
+            else convert_kernel<bf16_t, float><<<(n + 255) / 256, 256, 0, ctx->stream>>>((const bf16_t*)b, o, n);
+        };
         for (auto& l : ctx->layers) {
             if (l.bqkv) {
                 FT_HIP(ctx, hipMalloc((void**)&l.bqkv_f32, qkvN * sizeof(float)));
-                convert_kernel<bf16_t, float><<<(qkvN + 255) / 256, 256, 0, ctx->stream>>>((const bf16_t*)l.bqkv, l.bqkv_f32, qkvN);
+                to_f32(l.bqkv, l.bqkv_f32, qkvN);
             }
             if (l.bo) {
                 FT_HIP(ctx, hipMalloc((void**)&l.bo_f32, c.dim * sizeof(float)));
-                convert_kernel<bf16_t, float><<<(c.dim + 255) / 256, 256, 0, ctx->stream>>>((const bf16_t*)l.bo, l.bo_f32, c.dim);
+                to_f32(l.bo, l.bo_f32, c.dim);
             }
         }
         FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -723,10 +730,10 @@ struct PfX {   // fused RMSNorm hooks of the skinny kernel (codec_kernels.h TapG
 static void pf_gemm(Launch& L, const bf16_t* X, long ldx, int S, const void* W, const float* bias, int N, int K,
                     int act, const float* resid, float* out_f32, bf16_t* out_bf, long ldo, int round_out,
                     const PfX& fx = PfX());
-// A lock-step batch of >= wide_min rows (bf16): every Linear is ONE M-row MFMA launch (weights read once for the whole
+// A lock-step batch of >= wide_min rows (bf16 or fp16): every Linear is ONE M-row MFMA launch (weights read once for the whole
 // batch) with the RMSNorm / SwiGLU / residual add folded in (wide_kernels.h): five launches per layer.
 static bool wide_batch(const Launch& L) {
-    return L.ctx->wide_ok && L.ctx->c.dtype == FT_BF16 && L.M >= L.ctx->wide_min && L.M <= 64 && !L.gemv_only && !L.ctx->prof;
+    return L.ctx->wide_ok && L.M >= L.ctx->wide_min && L.M <= 64 && !L.gemv_only && !L.ctx->prof;
 }
 
 // Codebook positions 0 and 1 of a wide batch in ONE pass of 2 M rows (both inputs are known once the semantic token is drawn:
@@ -740,21 +747,23 @@ static bool wide_pair(const Launch& L) {
 // two 16-row weight tiles per workgroup where the fused norm's arithmetic would otherwise be paid per 16 rows of a long
 // matrix (W13 always, Wqkv from 17 batch rows), both 16-row batch tiles in one workgroup only where the weights
 // dominate (W13, the vocabulary head); everything else splits the batch rows over workgroups.
+// WT: the model's 16-bit element type; the octet-major buffers of the context are raw 16-bit storage (declared bf16_t)
+template <typename WT>
 static void wide_gemm(Launch& L, const bf16_t* X, const void* W, const float* bias, int N, int K, const void* gain, int epi,
                       float* out_f32, long ldo, bf16_t* out_xo, const bf16_t* resid_xo, int rows = 0, bool vocab_head = false) {
     const int M = rows > 0 ? rows : L.M;
-    WideP p{};
-    p.X = X; p.ldm = L.ctx->xo_ldm; p.W = (const bf16_t*)W; p.ldw = K; p.gain = (const bf16_t*)gain; p.eps = L.ctx->c.norm_eps;
-    p.bias = bias; p.M = M; p.N = N; p.K = K; p.out_f32 = out_f32; p.ldo = ldo; p.out_xo = out_xo; p.ldm_o = L.ctx->xo_ldm;
-    p.resid_xo = resid_xo;
+    WidePT<WT> p{};
+    p.X = (const WT*)X; p.ldm = L.ctx->xo_ldm; p.W = (const WT*)W; p.ldw = K; p.gain = (const WT*)gain; p.eps = L.ctx->c.norm_eps;
+    p.bias = bias; p.M = M; p.N = N; p.K = K; p.out_f32 = out_f32; p.ldo = ldo; p.out_xo = (WT*)out_xo; p.ldm_o = L.ctx->xo_ldm;
+    p.resid_xo = (const WT*)resid_xo;
     bool ok;
     if (epi == WEPI_RESID) ok = wide_gemm_launch<1, 1, false, WEPI_RESID>(p, L.s);
     else if (epi == WEPI_SWIGLU) ok = M > 16 ? wide_gemm_launch<2, 2, true, WEPI_SWIGLU>(p, L.s) : wide_gemm_launch<1, 2, true, WEPI_SWIGLU>(p, L.s);
     else if (vocab_head && M <= 32 && K == 1024 && N % 16 == 0 && N >= 4096 && !L.ctx->no_head_stream) {
         // the vocabulary head: activations normalised once per workgroup, weights streamed per wave (wide_head_kernel)
         static DevOnce once;
-        once.run([] { hipFuncSetAttribute((const void*)wide_head_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_head_lds<1024>()); });
-        wide_head_kernel<1024><<<256, 512, wide_head_lds<1024>(), L.s>>>(p);
+        once.run([] { hipFuncSetAttribute((const void*)wide_head_kernel<1024, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_head_lds<1024>()); });
+        wide_head_kernel<1024, WT><<<256, 512, wide_head_lds<1024>(), L.s>>>(p);
         ok = true;
     }
     else if (N >= 32768) ok = M > 16 ? wide_gemm_launch<2, 2, true, WEPI_STORE>(p, L.s) : wide_gemm_launch<1, 2, true, WEPI_STORE>(p, L.s);
@@ -764,28 +773,31 @@ static void wide_gemm(Launch& L, const bf16_t* X, const void* W, const float* bi
     L.chk();
 }
 
-// f32 rows -> octet-major bf16 (the values are bf16-exact): the residual stream a prompt pass left in ctx->x
+// f32 rows -> octet-major 16-bit elements (the values are exact in the model's type): the residual stream a prompt pass left in ctx->x
+template <typename WT>
 static __global__ __launch_bounds__(256) void xo_from_rows_kernel(const float* x, int ldx, int D, bf16_t* xo, int ldm) {
     const int m = blockIdx.y;
-    for (int d = blockIdx.x * 256 + threadIdx.x; d < D; d += gridDim.x * 256) xo[xo_index(m, d, ldm)] = f32_to_bf16_bits(x[(size_t)m * ldx + d]);
+    for (int d = blockIdx.x * 256 + threadIdx.x; d < D; d += gridDim.x * 256) xo[xo_index(m, d, ldm)] = h16_bits<WT>(x[(size_t)m * ldx + d]);
 }
 
-// bf16 rows [row][D] -> octet-major operand rows (table build below)
-static __global__ __launch_bounds__(256) void xo_from_bf16_rows_kernel(const bf16_t* x, int D, bf16_t* xo, int ldm, int rows) {
+// 16-bit rows [row][D] -> octet-major operand rows (table build below; a copy of bits, either type)
+static __global__ __launch_bounds__(256) void xo_from_h16_rows_kernel(const bf16_t* x, int D, bf16_t* xo, int ldm, int rows) {
     const int m = blockIdx.y;
     if (m >= rows) return;
     for (int d = blockIdx.x * 256 + threadIdx.x; d < D; d += gridDim.x * 256) xo[xo_index(m, d, ldm)] = x[(size_t)m * D + d];
 }
-static __global__ void f32_to_bf16_kernel(const float* x, bf16_t* o, long n) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) o[i] = f32_to_bf16_bits(x[i]);
+template <typename WT>
+static __global__ void f32_to_h16_kernel(const float* x, bf16_t* o, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) o[i] = h16_bits<WT>(x[i]);
 }
 
 // Wide batches: the table of layer 0's q k v for every code a codebook draw can select (codes < fastV), built at load with
 // the very launch that would compute those rows in a frame (the rows of a lock-step GEMM do not depend on each other, so a
 // table row carries the bits the launch would produce): 4 MB at the s1-mini widths, one launch less per codebook step.
-static ft_status wide_qkv0_build(ft_ctx* ctx) {
+template <typename WT>
+static ft_status wide_qkv0_build_t(ft_ctx* ctx) {
     const ft_ar_config& c = ctx->c;
-    if (!ctx->wide_ok || c.dtype != FT_BF16 || getenv("FT_NO_QKV0") || c.num_codebooks <= 2 || c.n_fast_layer < 1) return FT_OK;
+    if (!ctx->wide_ok || getenv("FT_NO_QKV0") || c.num_codebooks <= 2 || c.n_fast_layer < 1) return FT_OK;
     const int Df = c.fast_dim, qkvN = (c.fast_n_head + 2 * c.fast_n_local_heads) * c.fast_head_dim, V = ctx->fastV;
     const FtLayer& l0 = ctx->flayers[0];
     if (l0.bqkv) return FT_OK;
@@ -802,16 +814,21 @@ static ft_status wide_qkv0_build(ft_ctx* ctx) {
     bool ok = true;
     for (int c0 = 0; c0 < V && ok; c0 += CH) {
         const int rows = std::min(CH, V - c0);
-        xo_from_bf16_rows_kernel<<<dim3((Df + 255) / 256, rows), 256, 0, ctx->stream>>>((const bf16_t*)ctx->fast_emb + (size_t)c0 * Df, Df, xo, CH, rows);
-        WideP p{};
-        p.X = xo; p.ldm = CH; p.W = (const bf16_t*)l0.wqkv; p.ldw = Df; p.gain = (const bf16_t*)l0.attn_norm; p.eps = c.norm_eps;
+        xo_from_h16_rows_kernel<<<dim3((Df + 255) / 256, rows), 256, 0, ctx->stream>>>((const bf16_t*)ctx->fast_emb + (size_t)c0 * Df, Df, xo, CH, rows);
+        WidePT<WT> p{};
+        p.X = (const WT*)xo; p.ldm = CH; p.W = (const WT*)l0.wqkv; p.ldw = Df; p.gain = (const WT*)l0.attn_norm; p.eps = c.norm_eps;
         p.M = rows; p.N = qkvN; p.K = Df; p.out_f32 = out; p.ldo = qkvN;
         ok = wide_gemm_launch<1, 1, true, WEPI_STORE>(p, ctx->stream);
-        f32_to_bf16_kernel<<<256, 256, 0, ctx->stream>>>(out, ctx->wide_qkv0_tab + (size_t)c0 * qkvN, (long)rows * qkvN);
+        f32_to_h16_kernel<WT><<<256, 256, 0, ctx->stream>>>(out, ctx->wide_qkv0_tab + (size_t)c0 * qkvN, (long)rows * qkvN);
     }
     ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess && hipGetLastError() == hipSuccess;
     hipFree(xo); hipFree(out);
     if (!ok) { hipFree(ctx->wide_qkv0_tab); ctx->wide_qkv0_tab = nullptr; (void)hipGetLastError(); }
+    return FT_OK;
+}
+static ft_status wide_qkv0_build(ft_ctx* ctx) {
+    if (ctx->c.dtype == FT_BF16) return wide_qkv0_build_t<bf16_t>(ctx);
+    if (ctx->c.dtype == FT_F16) return wide_qkv0_build_t<f16_t>(ctx);
     return FT_OK;
 }
 
@@ -1027,14 +1044,14 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
     for (int li = 0; li < c.n_layer; ++li) {
         const FtLayer& l = ctx->layers[li];
         if (wide) {
-            if constexpr (ROUND == RND_BF16) {
+            if constexpr (ROUND != RND_NONE) {
                 // five launches per layer (wide_kernels.h): the residual stream xo, the attention output and the SwiGLU vector
-                // travel octet-major in bf16; q k v stay f32 rows for the attention kernel
+                // travel octet-major in the 16-bit type; q k v stay f32 rows for the attention kernel
                 const int D = c.dim, HD = c.n_head * c.head_dim, F = c.intermediate_size, M = L.M, ldm = ctx->xo_ldm;
                 bf16_t* xo = ctx->xo_x + (size_t)m0 * 8;
                 bf16_t* yo = ctx->xo_y + (size_t)m0 * 8;
                 bf16_t* go = ctx->xo_g + (size_t)m0 * 8;
-                wide_gemm(L, xo, l.wqkv, l.bqkv_f32, (int)qkvN, D, l.attn_norm, WEPI_STORE, qkv, (long)qkvN, nullptr, nullptr);
+                wide_gemm<WT>(L, xo, l.wqkv, l.bqkv_f32, (int)qkvN, D, l.attn_norm, WEPI_STORE, qkv, (long)qkvN, nullptr, nullptr);
                 AttnP a{};
                 a.qkv = qkv; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->rope;
                 a.kc = (char*)l.kc + (size_t)m0 * ctx->cache_m_stride * ctx->esz;
@@ -1050,9 +1067,9 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
                 if (!ctx->no_attn_wide && (long)M * c.n_local_heads >= 128 && c.head_dim == 128 && (Gq == 1 || Gq == 2 || Gq == 4) && wlds <= 65536) {
                     a.nsplit = 1;
                     const dim3 grid(c.n_local_heads, 1, M);
-                    if (Gq == 1) attn_wide_kernel<1, 128><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
-                    else if (Gq == 2) attn_wide_kernel<2, 128><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
-                    else attn_wide_kernel<4, 128><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
+                    if (Gq == 1) attn_wide_kernel<1, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
+                    else if (Gq == 2) attn_wide_kernel<2, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
+                    else attn_wide_kernel<4, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
                     L.chk();
                 } else {
                     int ns = 1;
@@ -1063,9 +1080,9 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
                     attn_decode<WT, ROUND>(L, a);
                     if (ns > 1) { attn_combine_rows_kernel<ROUND><<<M, 256, 0, L.s>>>(a); L.chk(); }
                 }
-                wide_gemm(L, yo, l.wo, l.bo_f32, D, HD, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
-                wide_gemm(L, xo, l.w13, nullptr, 2 * F, D, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr);
-                wide_gemm(L, go, l.w2, nullptr, D, F, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
+                wide_gemm<WT>(L, yo, l.wo, l.bo_f32, D, HD, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
+                wide_gemm<WT>(L, xo, l.w13, nullptr, 2 * F, D, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr);
+                wide_gemm<WT>(L, go, l.w2, nullptr, D, F, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
             }
             continue;
         }
@@ -1128,12 +1145,12 @@ static void enqueue_head(Launch& L) {
     const ft_ar_config& c = ctx->c;
     if (wide_batch(L)) {
         if (L.tail_only) {
-            xo_from_rows_kernel<<<dim3((c.dim + 255) / 256, L.M), 256, 0, L.s>>>(ctx->x + (size_t)L.m0 * c.dim, c.dim, c.dim,
+            xo_from_rows_kernel<WT><<<dim3((c.dim + 255) / 256, L.M), 256, 0, L.s>>>(ctx->x + (size_t)L.m0 * c.dim, c.dim, c.dim,
                                                                              ctx->xo_x + (size_t)L.m0 * 8, ctx->xo_ldm);
             L.chk();
         }
-        if constexpr (ROUND == RND_BF16)
-            wide_gemm(L, ctx->xo_x + (size_t)L.m0 * 8, ctx->head, nullptr, c.vocab_size, c.dim, ctx->norm, WEPI_STORE,
+        if constexpr (ROUND != RND_NONE)
+            wide_gemm<WT>(L, ctx->xo_x + (size_t)L.m0 * 8, ctx->head, nullptr, c.vocab_size, c.dim, ctx->norm, WEPI_STORE,
                       ctx->logits + (size_t)L.m0 * c.vocab_size, c.vocab_size, nullptr, nullptr, 0, true);
         return;
     }
@@ -1215,7 +1232,7 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
             const FtLayer& l = ctx->flayers[li];
             const float* xl = li == 0 ? xin : xf;
             if (wide) {
-                if constexpr (ROUND == RND_BF16) {
+                if constexpr (ROUND != RND_NONE) {
                     // as the slow layers; layer 0 reads the slow stack's residual stream (position 0) or the drawn code's embedding
                     // pair: rows [0, M) at position 0 and rows [xo_pair, xo_pair + M) at position 1 (cb == 1) in one pass
                     const int HDf = Hf * hdf, Ff = c.fast_intermediate_size, M = L.M, ldm = ctx->xo_ldm;
@@ -1227,7 +1244,7 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
                     const bf16_t* xlo = li == 0 ? xin_o : xfo;
                     // layer 0 of steps >= 2: the draw of the previous step left this step's q k v (wide_qkv0_build)
                     if (!(li == 0 && cb >= 2 && !pair && ctx->wide_qkv0_tab))
-                        wide_gemm(L, xlo, l.wqkv, nullptr, (int)qkvN, Df, l.attn_norm, WEPI_STORE, qkvf, (long)qkvN, nullptr, nullptr, rows);
+                        wide_gemm<WT>(L, xlo, l.wqkv, nullptr, (int)qkvN, Df, l.attn_norm, WEPI_STORE, qkvf, (long)qkvN, nullptr, nullptr, rows);
                     FastAttnP a{};
                     a.qkv = qkvf; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->frope;
                     a.kc = (char*)l.kc + (size_t)m0 * ctx->fcache_m_stride * ctx->esz;
@@ -1238,9 +1255,9 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
                     a.pair_M = pair ? M : 0; a.pair_off = ctx->xo_pair;
                     fast_attn_kernel<WT, ROUND><<<dim3(Hf, pair ? 2 * M : M), 64, 0, L.s>>>(a, nullptr, HDf);
                     L.chk();
-                    wide_gemm(L, yo, l.wo, nullptr, Df, HDf, nullptr, WEPI_RESID, nullptr, 0, xfo, xlo, rows);
-                    wide_gemm(L, xfo, l.w13, nullptr, 2 * Ff, Df, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr, rows);
-                    wide_gemm(L, go, l.w2, nullptr, Df, Ff, nullptr, WEPI_RESID, nullptr, 0, xfo, xfo, rows);
+                    wide_gemm<WT>(L, yo, l.wo, nullptr, Df, HDf, nullptr, WEPI_RESID, nullptr, 0, xfo, xlo, rows);
+                    wide_gemm<WT>(L, xfo, l.w13, nullptr, 2 * Ff, Df, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr, rows);
+                    wide_gemm<WT>(L, go, l.w2, nullptr, Df, Ff, nullptr, WEPI_RESID, nullptr, 0, xfo, xfo, rows);
                 }
                 continue;
             }
@@ -1276,8 +1293,8 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
         }
         if (cb == 0) return;  // logits of position 0 are discarded (inference.py:122)
         if (wide) {
-            if constexpr (ROUND == RND_BF16)
-                wide_gemm(L, (c.n_fast_layer > 0 ? ctx->xo_xf : ctx->xo_femb) + (size_t)(m0 + (pair ? ctx->xo_pair : 0)) * 8, ctx->fast_out, nullptr,
+            if constexpr (ROUND != RND_NONE)
+                wide_gemm<WT>(L, (c.n_fast_layer > 0 ? ctx->xo_xf : ctx->xo_femb) + (size_t)(m0 + (pair ? ctx->xo_pair : 0)) * 8, ctx->fast_out, nullptr,
                           ctx->fastV, Df, ctx->fast_norm, WEPI_STORE, ctx->flog + (size_t)m0 * ctx->fastV, ctx->fastV, nullptr, nullptr);
             enqueue_sample<WT, ROUND>(L, cb, cb == c.num_codebooks - 1);
             return;
@@ -1618,7 +1635,7 @@ extern "C" ft_status ft_ar_prefill_slow(ft_ctx* ctx, int32_t slot, const int32_t
 // weights once for all of them (a 48-position prompt alone is bound by the weight stream: 32 of them cost 32 streams) -
 // while the K/V append goes by (slot, position) of each row and the attention by sequence (grid.z).  Like the lock-step
 // frames of that width the products then sum in another order than a prompt pass on its own (another tile kernel from
-// 129 rows): judged against the oracle with the bf16 margin.  Fewer prompts, other precisions and shapes: one by one,
+// 129 rows): judged against the oracle with the bf16 margin.  Fewer prompts, other precisions (fp16 included) and shapes: one by one,
 // bit-equal to ft_ar_prefill_slow.  More rows than the workspace holds (max_seq_len): several passes.
 extern "C" ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32_t* slots, const int32_t* prompts,
                                              const int32_t* Lps, const int32_t* pos0s) {
@@ -1640,7 +1657,8 @@ extern "C" ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32
         }
         off[i + 1] = off[i] + (size_t)R * Lps[i];
     }
-    const bool ragged = !ctx->prefill_v0 && ctx->wide_ok && n >= ctx->wide_min && (c.head_dim == 64 || c.head_dim == 128) &&
+    // bf16 only (the pf_* workspace and the prompt kernels): fp16 runs its lock-step frames on the MFMA launches, its prompts one by one
+    const bool ragged = c.dtype == FT_BF16 && !ctx->prefill_v0 && ctx->wide_ok && n >= ctx->wide_min && (c.head_dim == 64 || c.head_dim == 128) &&
                         !getenv("FT_PREFILL_ATTN_V0") && !getenv("FT_NO_RAGGED_PREFILL");
     if (!ragged) {
         for (int i = 0; i < n; ++i) FT_TRY(ft_ar_prefill_slow(ctx, slots[i], prompts + off[i], Lps[i], pos0s[i]));
@@ -1993,7 +2011,7 @@ extern "C" const char* ft_ar_frame_path(const ft_ctx* ctx) {
     if (!ctx) return "";
     // batch-1 frames, then what a lock-step batch of >= wide_min rows runs on
     ft_ctx* c = const_cast<ft_ctx*>(ctx);
-    c->path_str = ctx->eng_why + (ctx->wide_ok && ctx->c.dtype == FT_BF16
+    c->path_str = ctx->eng_why + (ctx->wide_ok
                                       ? "; lock-step batches of >= 5 rows: MFMA launches with fused row operations (five per layer)"
                                       : "; lock-step batches: multi-row GEMV launches");
     return c->path_str.c_str();

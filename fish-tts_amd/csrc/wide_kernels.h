@@ -1,6 +1,8 @@
-// Lock-step batches of 5..64 utterances (bf16): every Linear of a decode frame as ONE weight-streaming MFMA launch with
+// Lock-step batches of 5..64 utterances (bf16 or fp16): every Linear of a decode frame as ONE weight-streaming MFMA launch with
 // the neighbouring row operations folded in, five launches per transformer layer (llama.py:229-283, 322-331):
 //     RMSNorm + Wqkv | qk-norm, RoPE, K/V append, attention | Wo + residual | RMSNorm + W13 + SwiGLU | W2 + residual
+// Everything below is written over the 16-bit element type WT (bf16_t | f16_t, WideT<WT>): the layouts, the work split and
+// the rounding points are the same, the f16 form uses v_mfma_f32_16x16x32_f16 and round_f16 where the bf16 form rounds.
 //
 // Activation operands live in HBM in OCTET-MAJOR form  Xo[k / 8][ldm][8]  (bf16): the 16-byte piece (8 consecutive k) of
 // row m sits beside the same piece of row m + 1.  A v_mfma_f32_16x16x32_bf16 A-fragment (16 rows x 8 k per 16 lanes)
@@ -19,32 +21,65 @@
 namespace ft {
 
 typedef short wk_bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 wk_f16x8 __attribute__((ext_vector_type(8)));
 typedef float wk_f32x4 __attribute__((ext_vector_type(4)));
 
 enum { WEPI_STORE = 0, WEPI_SWIGLU = 1, WEPI_RESID = 2 };
 
-struct WideP {
-    const bf16_t* X;        // Xo[K / 8][ldm][8], row 0 = the batch's first row
+template <typename WT>
+struct WidePT {
+    const WT* X;        // Xo[K / 8][ldm][8], row 0 = the batch's first row
     int ldm;
-    const bf16_t* W;        // [N][ldw]
+    const WT* W;            // [N][ldw]
     long ldw;
-    const bf16_t* gain;     // NORM: RMSNorm gain [K]
+    const WT* gain;         // NORM: RMSNorm gain [K]
     float eps;
     const float* bias;      // [N] or null
     int M, N, K;
-    float* out_f32;         // WEPI_STORE: [M][ldo] f32 holding bf16-rounded values
+    float* out_f32;         // WEPI_STORE: [M][ldo] f32 holding WT-rounded values
     long ldo;
-    bf16_t* out_xo;         // WEPI_SWIGLU: Xo[(N / 2) / 8][ldm_o][8]; WEPI_RESID: Xo[N / 8][ldm_o][8]
+    WT* out_xo;             // WEPI_SWIGLU: Xo[(N / 2) / 8][ldm_o][8]; WEPI_RESID: Xo[N / 8][ldm_o][8]
     int ldm_o;
-    const bf16_t* resid_xo; // WEPI_RESID: the residual stream (same form and stride as out_xo; may alias it)
+    const WT* resid_xo;     // WEPI_RESID: the residual stream (same form and stride as out_xo; may alias it)
 };
+typedef WidePT<bf16_t> WideP;
 
 typedef float wk_f2 __attribute__((ext_vector_type(2)));
 typedef __bf16 wk_b2 __attribute__((ext_vector_type(2)));
+typedef _Float16 wk_h2 __attribute__((ext_vector_type(2)));
 
 // two packed bf16 -> two f32 lanes of a packed-f32 operand; and back with one v_cvt_pk_bf16_f32 (round to nearest even)
 __device__ __forceinline__ wk_f2 wk_unpack2(uint32_t w) { return wk_f2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; }
 __device__ __forceinline__ uint32_t wk_pack2(wk_f2 v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, wk_b2)); }
+// the f16 twins: v_cvt_f32_f16 per half; back with two v_cvt_f16_f32 (round to nearest even, overflow to infinity =
+// round_f16 of common.h) and a pack - NOT the packed convert v_cvt_pkrtz_f16_f32, which truncates
+__device__ __forceinline__ wk_f2 wk_unpack2_f16(uint32_t w) { return __builtin_convertvector(__builtin_bit_cast(wk_h2, w), wk_f2); }
+__device__ __forceinline__ uint32_t wk_pack2_f16(wk_f2 v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, wk_h2)); }
+
+// what the kernels need to know about the element type
+template <typename WT> struct WideT;
+template <> struct WideT<bf16_t> {
+    static constexpr int ROUND = RND_BF16;
+    __device__ static __forceinline__ wk_f2 unpack2(uint32_t w) { return wk_unpack2(w); }
+    __device__ static __forceinline__ uint32_t pack2(wk_f2 v) { return wk_pack2(v); }
+    __device__ static __forceinline__ wk_f32x4 mfma(const U4& a, const U4& b, wk_f32x4 acc) {
+        wk_bf16x8 av, bv;
+        __builtin_memcpy(&av, &a, 16);
+        __builtin_memcpy(&bv, &b, 16);
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc, 0, 0, 0);
+    }
+};
+template <> struct WideT<f16_t> {
+    static constexpr int ROUND = RND_F16;
+    __device__ static __forceinline__ wk_f2 unpack2(uint32_t w) { return wk_unpack2_f16(w); }
+    __device__ static __forceinline__ uint32_t pack2(wk_f2 v) { return wk_pack2_f16(v); }
+    __device__ static __forceinline__ wk_f32x4 mfma(const U4& a, const U4& b, wk_f32x4 acc) {
+        wk_f16x8 av, bv;
+        __builtin_memcpy(&av, &a, 16);
+        __builtin_memcpy(&bv, &b, 16);
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc, 0, 0, 0);
+    }
+};
 
 // NT = 16-row weight tiles per workgroup (they share the workgroup's normalised operand registers: the RMSNorm arithmetic,
 // ~5 vector instructions per element, is paid once per NT * 16 weight rows)
@@ -59,8 +94,10 @@ struct WideNoSync {
     __device__ __forceinline__ void wait() const {}
     __device__ __forceinline__ void signal() const {}
 };
-template <int TS, int NT, int NW, int KS, bool NORM, int EPI, typename SYNC = WideNoSync>
-__device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, const int by, float* lds, const SYNC& sync = SYNC()) {
+template <int TS, int NT, int NW, int KS, bool NORM, int EPI, typename SYNC = WideNoSync, typename WT = bf16_t>
+__device__ __forceinline__ void wide_gemm_body(const WidePT<WT>& p, const int bx, const int by, float* lds, const SYNC& sync = SYNC()) {
+    typedef WideT<WT> T;
+    constexpr int ROUND = T::ROUND;
     float (*ssw)[TS * 16] = reinterpret_cast<float (*)[TS * 16]>(lds);
     float (*Cs)[TS * 16][NT * 16 + 1] = reinterpret_cast<float (*)[TS * 16][NT * 16 + 1]>(lds + NW * TS * 16);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -73,7 +110,7 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
     auto issue_w = [&] {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            const bf16_t* wrow = p.W + (size_t)(n0 + t * 16 + fr) * p.ldw + kw + fq * 8;
+            const WT* wrow = p.W + (size_t)(n0 + t * 16 + fr) * p.ldw + kw + fq * 8;
 #pragma unroll
             for (int s = 0; s < KS; ++s) w[t][s] = *reinterpret_cast<const U4*>(wrow + s * 32);
         }
@@ -83,7 +120,7 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
     for (int j = 0; j < TS; ++j) {
         const int row = m0 + j * 16 + fr;
         const bool on = row < p.M;
-        const bf16_t* xr = p.X + ((size_t)((kw >> 3) + fq) * p.ldm + (on ? row : 0)) * 8;
+        const WT* xr = p.X + ((size_t)((kw >> 3) + fq) * p.ldm + (on ? row : 0)) * 8;
 #pragma unroll
         for (int s = 0; s < KS; ++s)
             x[j][s] = on ? *reinterpret_cast<const U4*>(xr + (size_t)s * 4 * p.ldm * 8) : U4{0u, 0u, 0u, 0u};
@@ -95,14 +132,14 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
     if constexpr (!SYNC::weights_first) issue_w();
     // the residual values this thread adds in the epilogue (element e of the tile -> thread e % threads), requested now
     constexpr int EPT = (TS * NT * 256 + NW * 64 - 1) / (NW * 64);
-    bf16_t rs[EPT];
+    WT rs[EPT];
     if constexpr (EPI == WEPI_RESID) {
 #pragma unroll
         for (int i = 0; i < EPT; ++i) {
             const int e = tid + i * NW * 64;
             const int row = e / (NT * 16), c = e % (NT * 16);
             const int m = m0 + row, n = n0 + c;
-            rs[i] = (e < TS * NT * 256 && m < p.M) ? p.resid_xo[((size_t)(n >> 3) * p.ldm_o + m) * 8 + (n & 7)] : (bf16_t)0;
+            rs[i] = (e < TS * NT * 256 && m < p.M) ? p.resid_xo[((size_t)(n >> 3) * p.ldm_o + m) * 8 + (n & 7)] : WT{};
         }
     }
     if constexpr (NORM) {
@@ -114,7 +151,7 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
             for (int s = 0; s < KS; ++s) {
                 const uint32_t* xw = reinterpret_cast<const uint32_t*>(&x[j][s]);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { const wk_f2 v = wk_unpack2(xw[e]); ss2 = __builtin_elementwise_fma(v, v, ss2); }
+                for (int e = 0; e < 4; ++e) { const wk_f2 v = T::unpack2(xw[e]); ss2 = __builtin_elementwise_fma(v, v, ss2); }
             }
             float ss = ss2.x + ss2.y;
             ss += __shfl_xor(ss, 16);
@@ -136,7 +173,7 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
                 const uint32_t* gw = reinterpret_cast<const uint32_t*>(&g[s]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    xw[e] = wk_pack2(wk_unpack2(wk_pack2(wk_unpack2(xw[e]) * inv2)) * wk_unpack2(gw[e]));
+                    xw[e] = T::pack2(T::unpack2(T::pack2(T::unpack2(xw[e]) * inv2)) * T::unpack2(gw[e]));
             }
         }
     }
@@ -149,14 +186,8 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
     for (int s = 0; s < KS; ++s) {
 #pragma unroll
         for (int j = 0; j < TS; ++j) {
-            wk_bf16x8 a;
-            __builtin_memcpy(&a, &x[j][s], 16);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                wk_bf16x8 b;
-                __builtin_memcpy(&b, &w[t][s], 16);
-                acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[j][t], 0, 0, 0);
-            }
+            for (int t = 0; t < NT; ++t) acc[j][t] = T::mfma(x[j][s], w[t][s], acc[j][t]);
         }
     }
     // lane holds C[row = j*16 + 4*fq + r][n = t*16 + fr]
@@ -177,20 +208,20 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
 #pragma unroll
         for (int q = 1; q < NW; ++q) v += Cs[q][row][c];
         if (p.bias) v += p.bias[n];
-        v = round_bf16(v);                        // the nn.Linear output of a bf16 model
+        v = rb<ROUND>(v);                         // the nn.Linear output of a 16-bit model
         if constexpr (EPI == WEPI_SWIGLU) {
             // weight rows (2i, 2i+1) = (gate, up) of column i: the partner sits in the neighbouring lane (llama.py:322-331)
             const float other = dpp_f<DPP_XOR1>(v);
             if ((c & 1) == 0 && m < p.M) {
-                const float sg = round_bf16(v / (1.0f + expf(-v)));
+                const float sg = rb<ROUND>(v / (1.0f + expf(-v)));
                 const int gc = n >> 1;
-                p.out_xo[((size_t)(gc >> 3) * p.ldm_o + m) * 8 + (gc & 7)] = f32_to_bf16_bits(sg * other);
+                st_elem(p.out_xo, ((size_t)(gc >> 3) * p.ldm_o + m) * 8 + (gc & 7), sg * other);
             }
         } else if constexpr (EPI == WEPI_RESID) {
             if (m < p.M) {
                 const size_t oi = ((size_t)(n >> 3) * p.ldm_o + m) * 8 + (n & 7);
-                v += bf16_bits_to_f32(rs[i]);
-                p.out_xo[oi] = f32_to_bf16_bits(v);
+                v += ld_elem(rs, i);
+                st_elem(p.out_xo, oi, v);
             }
         } else {
             if (m < p.M) p.out_f32[(size_t)m * p.ldo + n] = v;
@@ -199,8 +230,8 @@ __device__ __forceinline__ void wide_gemm_body(const WideP& p, const int bx, con
     sync.signal();
 }
 
-template <int TS, int NT, int NW, int KS, bool NORM, int EPI>
-__global__ __launch_bounds__(NW * 64) void wide_gemm_kernel(WideP p) {
+template <int TS, int NT, int NW, int KS, bool NORM, int EPI, typename WT = bf16_t>
+__global__ __launch_bounds__(NW * 64) void wide_gemm_kernel(WidePT<WT> p) {
     __shared__ float lds[wide_lds_floats<TS, NT, NW>()];
     wide_gemm_body<TS, NT, NW, KS, NORM, EPI>(p, blockIdx.x, blockIdx.y, lds);
 }
@@ -217,8 +248,9 @@ __global__ __launch_bounds__(NW * 64) void wide_gemm_kernel(WideP p) {
 // bytes apart and fall into four different bank groups (at 512 bytes they share one: a four-way conflict on every read).
 // ------------------------------------------------------------------------------------------
 constexpr int WH_ROW = 36;
-template <int K>
-__global__ __launch_bounds__(512) void wide_head_kernel(WideP p) {
+template <int K, typename WT = bf16_t>
+__global__ __launch_bounds__(512) void wide_head_kernel(WidePT<WT> p) {
+    typedef WideT<WT> T;
     extern __shared__ __attribute__((aligned(16))) unsigned char hl[];
     constexpr int KS = K / 32, HALF = KS / 2, OCT = K / 8;
     static_assert(KS % 2 == 0, "two halves of the K-steps per tile");
@@ -242,7 +274,7 @@ __global__ __launch_bounds__(512) void wide_head_kernel(WideP p) {
         for (int i = 0; i < PER; ++i) {
             const uint32_t* xw = reinterpret_cast<const uint32_t*>(&xr[i]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { const wk_f2 v = wk_unpack2(xw[e]); ss2 = __builtin_elementwise_fma(v, v, ss2); }
+            for (int e = 0; e < 4; ++e) { const wk_f2 v = T::unpack2(xw[e]); ss2 = __builtin_elementwise_fma(v, v, ss2); }
         }
         float ss = ss2.x + ss2.y;
         ss += __shfl_xor(ss, 32);
@@ -260,7 +292,7 @@ __global__ __launch_bounds__(512) void wide_head_kernel(WideP p) {
             uint32_t* xw = reinterpret_cast<uint32_t*>(&xr[i]);
             const uint32_t* gw = reinterpret_cast<const uint32_t*>(&g);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) xw[e] = wk_pack2(wk_unpack2(wk_pack2(wk_unpack2(xw[e]) * inv2)) * wk_unpack2(gw[e]));
+            for (int e = 0; e < 4; ++e) xw[e] = T::pack2(T::unpack2(T::pack2(T::unpack2(xw[e]) * inv2)) * T::unpack2(gw[e]));
             xn[o * WH_ROW + row] = xr[i];
         }
         __syncthreads();
@@ -269,7 +301,7 @@ __global__ __launch_bounds__(512) void wide_head_kernel(WideP p) {
     const int ntiles = p.N / 16;
     U4 wa[HALF], wb[HALF];
     auto issue = [&](U4 (&w)[HALF], int t, int half) {
-        const bf16_t* wrow = p.W + (size_t)(min(t, ntiles - 1) * 16 + fr) * p.ldw + half * HALF * 32 + fq * 8;
+        const WT* wrow = p.W + (size_t)(min(t, ntiles - 1) * 16 + fr) * p.ldw + half * HALF * 32 + fq * 8;
 #pragma unroll
         for (int s = 0; s < HALF; ++s) w[s] = *reinterpret_cast<const U4*>(wrow + s * 32);
     };
@@ -281,14 +313,10 @@ __global__ __launch_bounds__(512) void wide_head_kernel(WideP p) {
         const U4* xz = xn + z;
 #pragma unroll
         for (int s = 0; s < HALF; ++s) {
-            wk_bf16x8 b;
-            __builtin_memcpy(&b, &w[s], 16);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                wk_bf16x8 a;
                 const U4 av = xz[((half * HALF + s) * 4 + fq) * WH_ROW + j * 16 + fr];
-                __builtin_memcpy(&a, &av, 16);
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[j], 0, 0, 0);
+                acc[j] = T::mfma(av, w[s], acc[j]);
             }
         }
     };
@@ -311,7 +339,7 @@ __global__ __launch_bounds__(512) void wide_head_kernel(WideP p) {
                 if (m < p.M) {
                     float v = acc[j][r];
                     if (p.bias) v += p.bias[t * 16 + fr];
-                    p.out_f32[(size_t)m * p.ldo + t * 16 + fr] = round_bf16(v);
+                    p.out_f32[(size_t)m * p.ldo + t * 16 + fr] = rb<T::ROUND>(v);
                 }
             }
     }
@@ -320,13 +348,13 @@ template <int K>
 static inline size_t wide_head_lds() { return (size_t)(K / 8) * WH_ROW * 16 + 8 * 32 * sizeof(float); }
 
 // K split: 128..256 contraction elements per wave where the width allows (one memory round trip, registers for every load)
-template <int TS, int NT, bool NORM, int EPI>
-static inline bool wide_gemm_launch(const WideP& p, hipStream_t st) {
+template <int TS, int NT, bool NORM, int EPI, typename WT>
+static inline bool wide_gemm_launch(const WidePT<WT>& p, hipStream_t st) {
     if (p.N % (NT * 16) != 0 || p.M < 1) return false;
     const dim3 grid(p.N / (NT * 16), (p.M + TS * 16 - 1) / (TS * 16));
-    if (p.K == 1024) wide_gemm_kernel<TS, NT, 8, 4, NORM, EPI><<<grid, 512, 0, st>>>(p);
-    else if (p.K == 2048) wide_gemm_kernel<TS, NT, 8, 8, NORM, EPI><<<grid, 512, 0, st>>>(p);
-    else if (p.K == 3072) wide_gemm_kernel<TS, NT, 12, 8, NORM, EPI><<<grid, 768, 0, st>>>(p);
+    if (p.K == 1024) wide_gemm_kernel<TS, NT, 8, 4, NORM, EPI, WT><<<grid, 512, 0, st>>>(p);
+    else if (p.K == 2048) wide_gemm_kernel<TS, NT, 8, 8, NORM, EPI, WT><<<grid, 512, 0, st>>>(p);
+    else if (p.K == 3072) wide_gemm_kernel<TS, NT, 12, 8, NORM, EPI, WT><<<grid, 768, 0, st>>>(p);
     else return false;
     return true;
 }

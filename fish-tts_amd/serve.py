@@ -22,7 +22,7 @@ frames, then `chunk_tokens`, the last generated column held back) and every read
 call, one CodecStream per request; seamless=False chunks are FishTTS.synthesize_stream's (every generated column, each
 chunk decoded from zero state); a non-streaming request's WAV is decoded when it ends.  Per request the codes are those of
 a single run with the same seed - the draws depend on (seed, frame, codebook, index), not on the slot or the schedule: bit
-for bit on an engine of up to 4 slots, within the bf16 evaluation-order margin of the MFMA launches beyond (batch.py).
+for bit on an engine of up to 4 slots, within the evaluation-order margin of the MFMA launches beyond (bf16 and fp16, batch.py).
 
 Requests may ask for another output rate (sample_rate=): their WAVs and zero-state chunks are resampled on the device one
 by one; their seamless streams resample through their CodecStream, in the same decode_streams call as every other ready

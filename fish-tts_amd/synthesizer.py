@@ -53,7 +53,9 @@ class FishTTS:
                  precision: Literal["bf16", "fp16", "fp32"] = "bf16", warmup: bool = True, *,
                  _synthetic: Optional[dict] = None, gpu_index: int = 0, cache_reference_kv: bool = True,
                  max_batch: int = 1, batch_streams: int = 1):
-        """`max_batch` (extension): utterance slots for synthesize_batch (lock-step batch with refill).
+        """`max_batch` (extension): utterance slots for synthesize_batch (lock-step batch with refill).  From 5 slots, at
+        the model widths the kernels cover, `precision` "bf16" and "fp16" run the batch's frames on the MFMA launches
+        (five per layer); "fp32" and narrower engines on the multi-row GEMV launches (ARHipEngine.frame_path()).
         `batch_streams` (extension): synthesize_batch of more than `max_batch` texts runs that many lock-step batches
         side by side (one engine - context, stream, weight copy - per batch, created on first use): a lock-step frame
         leaves most of the chip idle, so independent batches overlap (batch.run_batch_streams; three is the measured

@@ -1,5 +1,7 @@
 """Lock-step batch scaling probe (BASELINE configs[2]): B utterances decoded in one captured graph.
-   python tools/batch_probe.py 1 2 4 8 16"""
+   python tools/batch_probe.py 1 2 4 8 16
+   python tools/batch_probe.py --precision fp16 5 8 32"""
+import argparse
 import os
 import sys
 import time
@@ -15,13 +17,17 @@ from fish_tts_amd.config import s1_mini_args  # noqa: E402
 from fish_tts_amd.tokenizer import ByteTokenizer  # noqa: E402
 from fish_tts_amd.weights import random_state_dict  # noqa: E402
 
-Bs = [int(x) for x in sys.argv[1:]] or [1, 2, 4, 8]
+ap = argparse.ArgumentParser()
+ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
+ap.add_argument("Bs", nargs="*", type=int)
+opt = ap.parse_args()
+Bs = opt.Bs or [1, 2, 4, 8]
 args = s1_mini_args(max_seq_len=1024)
 tok = ByteTokenizer()
 sd = random_state_dict(args, seed=0)
 frames = 128
 for B in Bs:
-    eng = ARHipEngine(args, tok.semantic_begin_id, tok.semantic_end_id, tok.get_token_id("<|im_end|>"), precision="bf16",
+    eng = ARHipEngine(args, tok.semantic_begin_id, tok.semantic_end_id, tok.get_token_id("<|im_end|>"), precision=opt.precision,
                       max_batch=B, max_new_tokens=frames + 8)
     eng.load_state_dict(sd)
     g = torch.Generator().manual_seed(1)
@@ -35,5 +41,5 @@ for B in Bs:
         t0 = time.perf_counter()
         fr, n = eng.decode(frames, sps, poll=frames)
         dt = time.perf_counter() - t0
-    print(f"B={B:3d}: {frames * B / dt:9.1f} tok/s aggregate, {dt / frames * 1e3:7.3f} ms per lock-step frame, n={n.tolist()[:4]}")
+    print(f"{opt.precision} B={B:3d}: {frames * B / dt:9.1f} tok/s aggregate, {dt / frames * 1e3:7.3f} ms per lock-step frame, n={n.tolist()[:4]}; {eng.frame_path().split('; ')[-1]}")
     eng.close()
