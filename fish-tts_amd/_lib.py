@@ -92,6 +92,13 @@ SYMBOLS = {
     "ft_ar_frame_path": (C.c_char_p, [_P]),
     "ft_test_engine_fault": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "ft_test_sample": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(ft_sampling), _P, _P, _P]),
+    "ft_test_codec_trace_arm": (C.c_int32, [_P, C.c_int32, C.c_int32]),
+    "ft_test_codec_trace_count": (C.c_int32, [_P]),
+    "ft_test_codec_trace_variants": (C.c_int32, []),
+    "ft_test_codec_trace_variant": (C.c_char_p, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ft_test_codec_trace_launch": (C.c_int32, [_P, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    "ft_test_codec_trace_buffer": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int64), _P]),
 }
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",

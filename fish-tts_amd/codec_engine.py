@@ -176,6 +176,48 @@ class CodecHipEngine:
                                                  codes.ctypes.data_as(C.c_void_p)), "ft_codec_rvq_encode")
         return codes
 
+    TRACE_KINDS = ("bf", "act", "f32")    # ft_test_codec_trace_buffer kinds: main bf16 output, Snake'd copy, f32 output
+
+    def trace_variants(self) -> List[dict]:
+        """Test hook: the GEMM instantiations gemm() can pick, by id: name and row / column tile."""
+        out = []
+        for i in range(self.lib.ft_test_codec_trace_variants()):
+            bm, bn = C.c_int32(0), C.c_int32(0)
+            name = self.lib.ft_test_codec_trace_variant(i, C.byref(bm), C.byref(bn))
+            out.append({"id": i, "name": name.decode(), "bm": bm.value, "bn": bn.value})
+        return out
+
+    def trace(self, call, first: int = 0, count: int = 0):
+        """Test hook (ft_test_codec_trace_*): run call() - ONE decode of one item or ONE encode - traced.  Returns
+        (call's result, launches): per launch in launch order a dict name / rows / cols / variant / halo / ntap / K and,
+        for launches [first, first + count), "out": {"bf" | "act" | "f32": (rows, cols) array}, bf16 as uint16 bits."""
+        self._check(self.lib.ft_test_codec_trace_arm(self._h, int(first), int(count)), "ft_test_codec_trace_arm")
+        res = call()
+        n = self.lib.ft_test_codec_trace_count(self._h)
+        if n < 0:
+            raise HipError("codec trace: a copy failed or a launch wrote with a row stride other than its columns")
+        launches = []
+        name = C.create_string_buffer(96)
+        info = (C.c_int32 * 8)()
+        for i in range(n):
+            self._check(self.lib.ft_test_codec_trace_launch(self._h, i, name, 96, info), "ft_test_codec_trace_launch")
+            rec = {"name": name.value.decode(), "rows": info[0], "cols": info[1], "variant": info[2], "halo": info[4],
+                   "ntap": info[5], "K": info[6], "kinds": [], "out": {}}
+            for j in range(info[3]):
+                kind, f32, elems = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+                self._check(self.lib.ft_test_codec_trace_buffer(self._h, i, j, C.byref(kind), C.byref(f32), C.byref(elems), None),
+                            "ft_test_codec_trace_buffer")
+                k = self.TRACE_KINDS[kind.value]
+                rec["kinds"].append(k)
+                if info[7]:
+                    a = np.empty((info[0], info[1]), dtype=np.float32 if f32.value else np.uint16)
+                    assert a.size == elems.value, (rec["name"], a.shape, elems.value)
+                    self._check(self.lib.ft_test_codec_trace_buffer(self._h, i, j, C.byref(kind), C.byref(f32), C.byref(elems),
+                                                                    a.ctypes.data_as(C.c_void_p)), "ft_test_codec_trace_buffer")
+                    rec["out"][k] = a
+            launches.append(rec)
+        return res, launches
+
     def stream(self, sample_rate: Optional[int] = None) -> "CodecStream":
         """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode.
         `sample_rate` (output_rate): the stream's output is resampled on the device; it holds back the samples whose

@@ -1,4 +1,5 @@
 // DAC codec decode (DAC.decode, vocoder.py:906-912) on the tap-GEMM kernels of codec_kernels.h.
+#include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -80,6 +81,13 @@ struct CodecState {
     int* enc_codes = nullptr;
     int hop = 1, enc_frame_len = 0;
     long max_samples = 0;
+    // ---- test hook (fishtts_hip_test.h, ft_test_codec_trace_*): `trace` is non-null only inside a traced one-shot
+    // decode / encode; every launch site tests it once
+    struct TraceBuf { int kind = 0, f32 = 0; long elems = 0; std::vector<char> data; };   // kind: 0 out_bf, 1 out_act, 2 out_f32
+    struct TraceRec { std::string name; int rows = 0, cols = 0, variant = -1, halo = 0, ntap = 0, K = 0; bool held = false; std::vector<TraceBuf> bufs; };
+    struct Trace { int first = 0, count = 0; bool armed = false, failed = false; std::vector<TraceRec> recs; };
+    Trace tstore;
+    Trace* trace = nullptr;
 };
 
 static std::string cname(const char* fmt, int a = 0, int b = 0) {
@@ -548,7 +556,18 @@ struct GemmIO {
     int nz = 1, seg_m = 1, seg_xg = 0, seg_og = 0;
 };
 
-static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
+// Returns the id of the instantiation it launched (GEMM_VARIANTS; the launch trace of fishtts_hip_test.h reports it).
+struct GemmVariant { const char* name; int bm, bn; };
+static const GemmVariant GEMM_VARIANTS[] = {
+    {"skinny_gemm<4>", 64, 16},
+    {"tapgemm64<64,64,64>", 64, 64}, {"tapgemm64<64,64,32>", 64, 64}, {"tapgemm64<64,96,64>", 64, 96},
+    {"tapgemm64<64,96,32>", 64, 96}, {"tapgemm64<128,64,64>", 128, 64}, {"tapgemm64<128,64,32>", 128, 64},
+    {"tapgemm64<128,192,32,2,4>", 128, 192}, {"tapgemm64<256,96,32,4,2>", 256, 96}, {"tapgemm64<128,128,64,2,4>", 128, 128},
+    {"tapgemm64<128,128,32,2,4>", 128, 128}, {"tapgemm64<128,96,64,4,2>", 128, 96}, {"tapgemm64<128,96,32,4,2>", 128, 96},
+    {"tapgemm<128,128,2,2>", 128, 128}, {"tapgemm<128,64,4,1>", 128, 64}};
+constexpr int N_GEMM_VARIANTS = (int)(sizeof(GEMM_VARIANTS) / sizeof(GEMM_VARIANTS[0]));
+
+static int gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
     TapGemmP p{};
     p.X = io.X; p.ldx = io.ldx; p.x_bstride = 0; p.T_in = io.T_in; p.W = w.w; p.ntap = w.ntap;
     for (int i = 0; i < w.ntap; ++i) p.offs[i] = w.offs[i];
@@ -569,7 +588,7 @@ static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
         (io.act == ACT_NONE || io.act == ACT_SWIGLU || io.act == ACT_GELU) && !io.out_act) {
         p.ldw = 0;
         skinny_gemm_launch<4>(p, (io.M + 63) / 64, st, io.nz);
-        return;
+        return 0;
     }
     if (w.K % 32 == 0 && halo <= 56) {  // pipelined kernel: A stripe shared by the taps, B double-buffered
 #define FT_TG(BM_, BN_, BK_)                                                                                   \
@@ -596,29 +615,90 @@ static void gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
         if (vec_ok && Msel >= tile8_m && (w.N % 128 == 0 || w.N % 96 == 0)) {
             // full-width tiles where the whole N fits one block column (A read once): 128 x 192 (N = 192, 384), 256 x 96 (N = 96)
             // (256 x 128 x 32 on 8 waves was measured slower: 4.76 against 4.57 ms per 215-frame decode)
-            if (Msel >= wide_m && w.N % 192 == 0) { FT_TG8(128, 192, 32, 2, 4); return; }
-            if (Msel >= wide_m && w.N == 96) { FT_TG8(256, 96, 32, 4, 2); return; }
-            if (w.N % 128 == 0) { if (k64) FT_TG8(128, 128, 64, 2, 4); else FT_TG8(128, 128, 32, 2, 4); }
-            else { if (k64) FT_TG8(128, 96, 64, 4, 2); else FT_TG8(128, 96, 32, 4, 2); }
-            return;
+            if (Msel >= wide_m && w.N % 192 == 0) { FT_TG8(128, 192, 32, 2, 4); return 7; }
+            if (Msel >= wide_m && w.N == 96) { FT_TG8(256, 96, 32, 4, 2); return 8; }
+            if (w.N % 128 == 0) { if (k64) FT_TG8(128, 128, 64, 2, 4); else FT_TG8(128, 128, 32, 2, 4); return k64 ? 9 : 10; }
+            if (k64) FT_TG8(128, 96, 64, 4, 2); else FT_TG8(128, 96, 32, 4, 2);
+            return k64 ? 11 : 12;
         }
 #undef FT_TG8
         if (w.N % 128 == 0 || (w.N % 96 != 0 && w.N > 96)) {
             if (k64) FT_TG(64, 64, 64); else FT_TG(64, 64, 32);
+            return k64 ? 1 : 2;
         } else if (w.N % 96 == 0) {
             if (k64) FT_TG(64, 96, 64); else FT_TG(64, 96, 32);
+            return k64 ? 3 : 4;
         } else {
             if (k64) FT_TG(128, 64, 64); else FT_TG(128, 64, 32);
+            return k64 ? 5 : 6;
         }
 #undef FT_TG
     } else if (w.N >= 128) {
         const dim3 grid((io.M + 127) / 128, (w.N + 127) / 128, io.nz);
         tapgemm_kernel<128, 128, 2, 2><<<grid, 256, 0, st>>>(p);
-    } else {
-        const dim3 grid((io.M + 127) / 128, (w.N + 63) / 64, io.nz);
-        tapgemm_kernel<128, 64, 4, 1><<<grid, 256, 0, st>>>(p);
+        return 13;
+    }
+    const dim3 grid((io.M + 127) / 128, (w.N + 63) / 64, io.nz);
+    tapgemm_kernel<128, 64, 4, 1><<<grid, 256, 0, st>>>(p);
+    return 14;
+}
+
+// ---- launch trace (test hook).  A traced call appends one record per launch, in launch order; the launches of the armed
+// range also copy what they wrote to the host at that point of the stream (the work buffers are reused later).  The copy
+// reads only: a traced call computes what an untraced one does.
+struct TraceOut { int kind; const void* p; int f32; };
+static std::string tname(const char* fmt, ...) {
+    char buf[96];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
+static void trace_rec(CodecState* s, hipStream_t st, const std::string& name, long rows, long cols, int variant, int halo, int ntap,
+                      int K, std::initializer_list<TraceOut> outs) {
+    CodecState::Trace& t = *s->trace;
+    const int idx = (int)t.recs.size();
+    t.recs.emplace_back();
+    CodecState::TraceRec& r = t.recs.back();
+    r.name = name; r.rows = (int)rows; r.cols = (int)cols; r.variant = variant; r.halo = halo; r.ntap = ntap; r.K = K;
+    r.held = idx >= t.first && idx < t.first + t.count;
+    for (const TraceOut& o : outs) {
+        if (!o.p) continue;
+        r.bufs.emplace_back();
+        CodecState::TraceBuf& b = r.bufs.back();
+        b.kind = o.kind; b.f32 = o.f32; b.elems = rows * cols;
+        if (!r.held) continue;
+        b.data.resize((size_t)b.elems * (o.f32 ? 4 : 2));
+        if (hipMemcpyAsync(b.data.data(), o.p, b.data.size(), hipMemcpyDeviceToHost, st) != hipSuccess) t.failed = true;
+    }
+    if (r.held && hipStreamSynchronize(st) != hipSuccess) t.failed = true;
+}
+// gemm() and its record: rows x columns as written (a SwiGLU launch writes N / 2 columns; a transposed convolution's
+// [M][s * Cout] is the [M * s][Cout] output)
+static void gemm_t(CodecState* s, hipStream_t st, const ConvW& w, const GemmIO& io, const char* fmt, int a = 0, int b = 0, const char* pfx = "") {
+    const int id = gemm(st, w, io);
+    if (s->trace) {
+        const long cols = io.act == ACT_SWIGLU ? w.N / 2 : w.N;
+        if (io.ldo != cols) s->trace->failed = true;
+        int halo = 0;
+        for (int i = 0; i < w.ntap; ++i) halo = std::max(halo, -w.offs[i]);
+        trace_rec(s, st, tname(fmt, pfx, a, b), io.M, cols, id, halo, w.ntap, w.K,
+                  {{0, io.out_bf, 0}, {1, io.out_act, 0}, {2, io.out_f32, 1}});
     }
 }
+struct TraceScope {   // a traced call: armed -> active for this call only
+    CodecState* s;
+    explicit TraceScope(CodecState* s_, bool eligible) : s(s_) {
+        if (!s->tstore.armed) return;
+        s->tstore.armed = false;
+        if (!eligible) return;
+        s->tstore.recs.clear();
+        s->tstore.failed = false;
+        s->trace = &s->tstore;
+    }
+    ~TraceScope() { s->trace = nullptr; }
+};
 
 // ---- streamed decode state (ft_codec_stream_*): what the causal codec needs from earlier chunks, two copies of each
 // (a chunk reads one and leaves the other).  The codec is strictly causal: the window-128 attention reads the K / V of
@@ -780,61 +860,70 @@ static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, i
     FT_HIP(ctx, hipMemcpyAsync(s->codes, hc.data(), hc.size() * sizeof(int), hipMemcpyHostToDevice, st));
     RvqP rq{s->codes, s->tables, c.n_codebooks, c.semantic_codebook_size, c.codebook_size, D, T, s->x};
     rvq_gather_kernel<<<dim3(T, 1), 256, 0, st>>>(rq);
+    if (s->trace) trace_rec(s, st, "rvq", T, D, -1, 0, 0, 0, {{2, s->x, 1}});
     // post transformer (vocoder.py:338-354): residual stream f32, GEMM operands bf16
     bf16_t* qkv_c = s->qkv + (size_t)nh * 3 * HD;             // this chunk's rows of the q k v work buffer
     for (int l = 0; l < c.n_tf_layer; ++l) {
         const TfLayer& t = s->tf[l];
         rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{s->x, t.n1, c.tf_norm_eps, D, s->xn, nullptr});
-        { GemmIO io{s->xn, D, T, T}; io.out_bf = qkv_c; io.ldo = 3 * HD; io.msel = Tn; gemm(st, t.qkv, io); }
+        if (s->trace) trace_rec(s, st, tname("post.%d.norm1", l), T, D, -1, 0, 0, 0, {{0, s->xn, 0}});
+        { GemmIO io{s->xn, D, T, T}; io.out_bf = qkv_c; io.ldo = 3 * HD; io.msel = Tn; gemm_t(s, st, t.qkv, io, "%s%d.qkv", l, 0, "post."); }
         rope_qk_kernel<<<gridfor((long)T * 2 * H * (hd / 2)), 256, 0, st>>>(qkv_c, s->rope, T, H, hd, sc ? sc->t0 : 0);
+        if (s->trace) trace_rec(s, st, tname("post.%d.rope", l), T, 3 * HD, -1, 0, 0, 0, {{0, qkv_c, 0}});
         if (sc) {
             if (nh > 0) kv_carry_in_kernel<<<gridfor((long)nh * 2 * HD / 8), 256, 0, st>>>(s->qkv, sc->kv[sc->par][l], nh, W1, HD);
             const int nh2 = std::min(W1, nh + T);
             if (nh2 > 0) kv_carry_out_kernel<<<gridfor((long)nh2 * 2 * HD / 8), 256, 0, st>>>(s->qkv, sc->kv[sc->par ^ 1][l], nh + T, nh2, W1, HD);
         }
         window_attn_kernel<<<(T * H + 3) / 4, 256, 0, st>>>(WinAttnP{s->qkv, s->y, nh + T, H, hd, c.tf_window, 1.0f / sqrtf((float)hd), nh});
-        { GemmIO io{s->y, HD, T, T}; io.gamma = t.g1; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm(st, t.wo, io); }
+        if (s->trace) trace_rec(s, st, tname("post.%d.attn", l), T, HD, -1, 0, 0, 0, {{0, s->y, 0}});
+        { GemmIO io{s->y, HD, T, T}; io.gamma = t.g1; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm_t(s, st, t.wo, io, "%s%d.wo", l, 0, "post."); }
         rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{s->x, t.n2, c.tf_norm_eps, D, s->xn, nullptr});
-        { GemmIO io{s->xn, D, T, T}; io.act = ACT_SWIGLU; io.out_bf = s->g; io.ldo = c.tf_ffn; io.msel = Tn; gemm(st, t.w13, io); }
-        { GemmIO io{s->g, c.tf_ffn, T, T}; io.gamma = t.g2; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm(st, t.w2, io); }
+        if (s->trace) trace_rec(s, st, tname("post.%d.norm2", l), T, D, -1, 0, 0, 0, {{0, s->xn, 0}});
+        { GemmIO io{s->xn, D, T, T}; io.act = ACT_SWIGLU; io.out_bf = s->g; io.ldo = c.tf_ffn; io.msel = Tn; gemm_t(s, st, t.w13, io, "%s%d.w13", l, 0, "post."); }
+        { GemmIO io{s->g, c.tf_ffn, T, T}; io.gamma = t.g2; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm_t(s, st, t.w2, io, "%s%d.w2", l, 0, "post."); }
     }
     bf16_t *z = s->big[0], *u = s->big[1], *n = s->big[2], *h = s->big[3];
     rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{s->x, s->tf_norm, c.tf_norm_eps, D, z, nullptr});
+    if (s->trace) trace_rec(s, st, "post.norm", T, D, -1, 0, 0, 0, {{0, z, 0}});
     int Tc = T;
     long Tnc = Tn;                                            // nominal rows at the current rate
     for (const UpStage& us : s->up) {  // vocoder.py:737-748: convT k=s=2, then ConvNeXt
-        { GemmIO io{z, D, Tc, Tc}; io.out_bf = u; io.ldo = us.ct.N; io.msel = Tnc; gemm(st, us.ct, io); }
+        const int uj = (int)(&us - s->up.data());
+        { GemmIO io{z, D, Tc, Tc}; io.out_bf = u; io.ldo = us.ct.N; io.msel = Tnc; gemm_t(s, st, us.ct, io, "%sup.%d.ct", uj); }
         Tc *= us.f;
         Tnc *= us.f;
         const int tm = roll(u, Tc, 6, D);                     // depthwise causal k = 7
         dwconv_ln_kernel<<<Tc, 256, D * sizeof(float), st>>>(DwLnP{u, us.dw_w, us.dw_b, us.ln_w, us.ln_b, Tc, D, n, tm});
-        { GemmIO io{n, D, Tc, Tc}; io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; io.msel = Tnc; gemm(st, us.pw1, io); }
-        { GemmIO io{h, 4 * D, Tc, Tc}; io.gamma = us.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D; io.msel = Tnc; gemm(st, us.pw2, io); }
+        if (s->trace) trace_rec(s, st, tname("up.%d.dwln", uj), Tc, D, -1, 6, 7, 0, {{0, n, 0}});
+        { GemmIO io{n, D, Tc, Tc}; io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; io.msel = Tnc; gemm_t(s, st, us.pw1, io, "%sup.%d.pw1", uj); }
+        { GemmIO io{h, 4 * D, Tc, Tc}; io.gamma = us.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D; io.msel = Tnc; gemm_t(s, st, us.pw2, io, "%sup.%d.pw2", uj); }
     }
     // decoder (vocoder.py:605-640).  Buffers: a = snake'd input of the next conv, r = raw residual
     bf16_t *a = u, *r = n, *hs = h, *a2 = z;
     { GemmIO io{z, D, Tc, Tc}; io.out_act = a; io.alpha = s->blocks[0].a0; io.ldo = c.decoder_dim; io.msel = Tnc;
-      io.t_min = roll(z, Tc, halo_of(s->conv_in), D); gemm(st, s->conv_in, io); }
+      io.t_min = roll(z, Tc, halo_of(s->conv_in), D); gemm_t(s, st, s->conv_in, io, "%sdec.in"); }
     // note: conv_in reads z and writes a (= big[1]); z (= big[0]) is free afterwards
     for (size_t bi = 0; bi < s->blocks.size(); ++bi) {
         const DecBlock& b = s->blocks[bi];
         // transposed conv: raw -> r, snake'd by unit 0 -> a2
         { GemmIO io{a, b.cin, Tc, Tc}; io.out_bf = r; io.out_act = a2; io.alpha = b.u[0].a0; io.ldo = b.ct.N; io.msel = Tnc;
-          io.t_min = roll(a, Tc, halo_of(b.ct), b.cin); gemm(st, b.ct, io); }
+          io.t_min = roll(a, Tc, halo_of(b.ct), b.cin); gemm_t(s, st, b.ct, io, "%sdec.%d.ct", (int)bi); }
         Tc *= b.s;
         Tnc *= b.s;
         for (int ui = 0; ui < 3; ++ui) {
             const ResUnitW& ru = b.u[ui];
             { GemmIO io{a2, b.cout, Tc, Tc}; io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cout; io.msel = Tnc;
-              io.t_min = roll(a2, Tc, halo_of(ru.c7), b.cout); gemm(st, ru.c7, io); }
+              io.t_min = roll(a2, Tc, halo_of(ru.c7), b.cout); gemm_t(s, st, ru.c7, io, "%sdec.%d.u%d.c7", (int)bi, ui); }
             const float* next_alpha = ui < 2 ? b.u[ui + 1].a0 : (bi + 1 < s->blocks.size() ? s->blocks[bi + 1].a0 : s->a_last);
             bf16_t* act_dst = ui < 2 ? a2 : a;  // the last unit feeds the next block's transposed conv / the output conv
             { GemmIO io{hs, b.cout, Tc, Tc}; io.resid_bf = r; io.ldr = b.cout; io.out_bf = ui < 2 ? r : nullptr;
-              io.out_act = act_dst; io.alpha = next_alpha; io.ldo = b.cout; io.msel = Tnc; gemm(st, ru.c1, io); }
+              io.out_act = act_dst; io.alpha = next_alpha; io.ldo = b.cout; io.msel = Tnc; gemm_t(s, st, ru.c1, io, "%sdec.%d.u%d.c1", (int)bi, ui); }
         }
     }
     FinalConvP fp{a, s->w_last, s->b_last, Tc, s->c_last, s->audio, roll(a, Tc, 6, s->c_last)};
     final_conv_tanh_kernel<<<2048, 256, 0, st>>>(fp);
+    if (s->trace) trace_rec(s, st, "final", Tc, 1, -1, 6, 7, s->c_last, {{2, s->audio, 1}});
     if (rs) {
         (*rs)[0].x = s->audio;
         FT_TRY(rs_enqueue(ctx, *rs, audio_host));
@@ -1151,6 +1240,7 @@ extern "C" ft_status ft_codec_decode(ft_ctx* ctx, const int32_t* codes, int32_t 
     FT_HIP(ctx, hipSetDevice(ctx->device));
     const int R = c.n_codebooks + 1;
     const size_t alen = (size_t)T * s->frame_len;
+    TraceScope traced(s, B == 1);
     for (int b = 0; b < B; ++b) {
         int Tb = lens ? lens[b] : T;
         if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode: bad length");
@@ -1382,20 +1472,27 @@ extern "C" ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, in
 // RMSNorm goes to out_bf and/or out_f32.
 static void run_transformer(ft_ctx* ctx, hipStream_t st, const std::vector<TfLayer>& layers, const float* final_norm,
                             float* x, int T, int D, int H, int hd, int ffn, int window, const float* rope,
-                            bf16_t* xn, bf16_t* qkv, bf16_t* y, bf16_t* g, bf16_t* out_bf, float* out_f32) {
+                            bf16_t* xn, bf16_t* qkv, bf16_t* y, bf16_t* g, bf16_t* out_bf, float* out_f32, const char* pfx) {
     const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
     const int HD = H * hd;
     for (const TfLayer& t : layers) {
+        const int l = (int)(&t - layers.data());
         rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, t.n1, c.tf_norm_eps, D, xn, nullptr});
-        { GemmIO io{xn, D, T, T}; io.out_bf = qkv; io.ldo = 3 * HD; gemm(st, t.qkv, io); }
+        if (s->trace) trace_rec(s, st, tname("%s%d.norm1", pfx, l), T, D, -1, 0, 0, 0, {{0, xn, 0}});
+        { GemmIO io{xn, D, T, T}; io.out_bf = qkv; io.ldo = 3 * HD; gemm_t(s, st, t.qkv, io, "%s%d.qkv", l, 0, pfx); }
         rope_qk_kernel<<<gridfor((long)T * 2 * H * (hd / 2)), 256, 0, st>>>(qkv, rope, T, H, hd);
+        if (s->trace) trace_rec(s, st, tname("%s%d.rope", pfx, l), T, 3 * HD, -1, 0, 0, 0, {{0, qkv, 0}});
         window_attn_kernel<<<(T * H + 3) / 4, 256, 0, st>>>(WinAttnP{qkv, y, T, H, hd, window, 1.0f / sqrtf((float)hd)});
-        { GemmIO io{y, HD, T, T}; io.gamma = t.g1; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm(st, t.wo, io); }
+        if (s->trace) trace_rec(s, st, tname("%s%d.attn", pfx, l), T, HD, -1, 0, 0, 0, {{0, y, 0}});
+        { GemmIO io{y, HD, T, T}; io.gamma = t.g1; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm_t(s, st, t.wo, io, "%s%d.wo", l, 0, pfx); }
         rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, t.n2, c.tf_norm_eps, D, xn, nullptr});
-        { GemmIO io{xn, D, T, T}; io.act = ACT_SWIGLU; io.out_bf = g; io.ldo = ffn; gemm(st, t.w13, io); }
-        { GemmIO io{g, ffn, T, T}; io.gamma = t.g2; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm(st, t.w2, io); }
+        if (s->trace) trace_rec(s, st, tname("%s%d.norm2", pfx, l), T, D, -1, 0, 0, 0, {{0, xn, 0}});
+        { GemmIO io{xn, D, T, T}; io.act = ACT_SWIGLU; io.out_bf = g; io.ldo = ffn; gemm_t(s, st, t.w13, io, "%s%d.w13", l, 0, pfx); }
+        { GemmIO io{g, ffn, T, T}; io.gamma = t.g2; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm_t(s, st, t.w2, io, "%s%d.w2", l, 0, pfx); }
     }
     rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, final_norm, c.tf_norm_eps, D, out_bf, out_f32});
+    if (s->trace) trace_rec(s, st, tname("%snorm", pfx), T, D, -1, 0, 0, 0, {{0, out_bf, 0}, {2, out_f32, 1}});
 }
 
 static ft_status rvq_search(ft_ctx* ctx, hipStream_t st, const float* z, int T, int* codes_dev) {
@@ -1440,6 +1537,7 @@ extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_
     FT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = s->stream;
     const int D = c.latent_dim, H = c.tf_n_head, hd = c.tf_head_dim, R = c.n_codebooks + 1;
+    TraceScope traced(s, true);
     FT_HIP(ctx, hipMemsetAsync(s->enc_audio, 0, (size_t)T0 * sizeof(float), st));
     FT_HIP(ctx, hipMemcpyAsync(s->enc_audio, audio, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, st));
     // Encoder (vocoder.py:539-575).  r = raw residual stream, a = Snake'd operand of the next conv, hs = inner buffer
@@ -1448,48 +1546,54 @@ extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_
     {
         EncInP ep{s->enc_audio, s->enc_w0, s->enc_b0, s->enc[0].u[0].a0, T, c.encoder_dim, r, a};
         enc_conv_in_kernel<<<gridfor(T * c.encoder_dim), 256, 0, st>>>(ep);
+        if (s->trace) trace_rec(s, st, "enc.in", T, c.encoder_dim, -1, 6, 7, 1, {{0, r, 0}, {1, a, 0}});
     }
     for (size_t bi = 0; bi < s->enc.size(); ++bi) {
         const CodecState::EncBlock& b = s->enc[bi];
         for (int ui = 0; ui < 3; ++ui) {
             const CodecState::EncUnit& ru = b.u[ui];
-            { GemmIO io{a, b.cin, (int)T, (int)T}; io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cin; gemm(st, ru.c7, io); }
+            { GemmIO io{a, b.cin, (int)T, (int)T}; io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cin; gemm_t(s, st, ru.c7, io, "%senc.%d.u%d.c7", (int)bi, ui); }
             const float* next_alpha = ui < 2 ? b.u[ui + 1].a0 : b.a3;
             { GemmIO io{hs, b.cin, (int)T, (int)T}; io.resid_bf = r; io.ldr = b.cin; io.out_bf = ui < 2 ? r : nullptr;
-              io.out_act = a; io.alpha = next_alpha; io.ldo = b.cin; gemm(st, ru.c1, io); }
+              io.out_act = a; io.alpha = next_alpha; io.ldo = b.cin; gemm_t(s, st, ru.c1, io, "%senc.%d.u%d.c1", (int)bi, ui); }
         }
         // strided conv on the [T/s][s*cin] view of a; raw output to o (no transformer) or to the f32 stream
         const long Tn = T / b.s;
         const bool has_tf = !b.tf.empty();
-        { GemmIO io{a, (long)b.s * b.cin, (int)Tn, (int)Tn}; if (has_tf) io.out_f32 = s->enc_x; else io.out_bf = o; io.ldo = b.cout; gemm(st, b.sc, io); }
+        { GemmIO io{a, (long)b.s * b.cin, (int)Tn, (int)Tn}; if (has_tf) io.out_f32 = s->enc_x; else io.out_bf = o; io.ldo = b.cout; gemm_t(s, st, b.sc, io, "%senc.%d.sc", (int)bi); }
         T = Tn;
         if (has_tf)
             run_transformer(ctx, st, b.tf, b.tf_norm, s->enc_x, (int)T, b.cout, b.cout / 64, 64, 3 * b.cout, c.enc_tf_window,
-                            s->rope_enc, s->e_xn, s->e_qkv, s->e_y, s->e_g, o, nullptr);
+                            s->rope_enc, s->e_xn, s->e_qkv, s->e_y, s->e_g, o, nullptr, tname("enc.%d.tf.", (int)bi).c_str());
         const float* alpha_next = bi + 1 < s->enc.size() ? s->enc[bi + 1].u[0].a0 : s->enc_a_last;
         snake_bf_rows_kernel<<<gridfor(T * b.cout), 256, 0, st>>>(o, alpha_next, a, T * b.cout, b.cout);
+        if (s->trace) trace_rec(s, st, tname("enc.%d.snake", (int)bi), T, b.cout, -1, 0, 0, 0, {{1, a, 0}});
         std::swap(r, o);  // the raw output is the next block's residual stream
     }
     bf16_t* z = hs;   // [T][D]
-    { GemmIO io{a, s->enc[s->enc.size() - 1].cout, (int)T, (int)T}; io.out_bf = z; io.ldo = D; gemm(st, s->enc_out, io); }
+    { GemmIO io{a, s->enc[s->enc.size() - 1].cout, (int)T, (int)T}; io.out_bf = z; io.ldo = D; gemm_t(s, st, s->enc_out, io, "%senc.out"); }
     // quantizer.downsample (vocoder.py:724-735): strided conv k = s = 2, ConvNeXt
     bf16_t *u = r, *n = a, *h = o;
     for (size_t j = 0; j < s->down.size(); ++j) {
         const UpStage& ds = s->down[j];
         const long Tn = T / ds.f;
-        { GemmIO io{z, (long)ds.f * D, (int)Tn, (int)Tn}; io.out_bf = u; io.ldo = D; gemm(st, ds.ct, io); }
+        { GemmIO io{z, (long)ds.f * D, (int)Tn, (int)Tn}; io.out_bf = u; io.ldo = D; gemm_t(s, st, ds.ct, io, "%sdown.%d.sc", (int)j); }
         T = Tn;
         dwconv_ln_kernel<<<(int)T, 256, D * sizeof(float), st>>>(DwLnP{u, ds.dw_w, ds.dw_b, ds.ln_w, ds.ln_b, (int)T, D, n});
-        { GemmIO io{n, D, (int)T, (int)T}; io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; gemm(st, ds.pw1, io); }
+        if (s->trace) trace_rec(s, st, tname("down.%d.dwln", (int)j), T, D, -1, 6, 7, 0, {{0, n, 0}});
+        { GemmIO io{n, D, (int)T, (int)T}; io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; gemm_t(s, st, ds.pw1, io, "%sdown.%d.pw1", (int)j); }
         const bool last = j + 1 == s->down.size();
         { GemmIO io{h, 4 * D, (int)T, (int)T}; io.gamma = ds.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D;
-          if (last) io.out_f32 = s->enc_x; gemm(st, ds.pw2, io); }
+          if (last) io.out_f32 = s->enc_x; gemm_t(s, st, ds.pw2, io, "%sdown.%d.pw2", (int)j); }
     }
-    if (s->down.empty()) bf16_rows_to_f32_kernel<<<gridfor(T * D), 256, 0, st>>>(z, s->enc_x, T * D);
+    if (s->down.empty()) {
+        bf16_rows_to_f32_kernel<<<gridfor(T * D), 256, 0, st>>>(z, s->enc_x, T * D);
+        if (s->trace) trace_rec(s, st, "down.f32", T, D, -1, 0, 0, 0, {{2, s->enc_x, 1}});
+    }
     if (T != Tf) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_encode: stage rates do not multiply to the frame length");
     // pre_module (window-limited transformer), then the residual quantiser search
     run_transformer(ctx, st, s->pre, s->pre_norm, s->enc_x, (int)T, D, H, hd, c.tf_ffn, c.tf_window, s->rope,
-                    s->e_xn, s->e_qkv, s->e_y, s->e_g, nullptr, s->enc_zq);
+                    s->e_xn, s->e_qkv, s->e_y, s->e_g, nullptr, s->enc_zq, "pre.");
     FT_TRY(rvq_search(ctx, st, s->enc_zq, (int)T, s->enc_codes));
     FT_HIP(ctx, hipMemcpyAsync(codes, s->enc_codes, (size_t)R * T * sizeof(int), hipMemcpyDeviceToHost, st));
     FT_HIP(ctx, hipStreamSynchronize(st));
@@ -1502,3 +1606,54 @@ extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_
 extern "C" int32_t ft_codec_enc_frame_len(const ft_ctx* ctx) { return ctx && ctx->codec ? ctx->codec->enc_frame_len : 0; }
 
 extern "C" int32_t ft_codec_frame_len(const ft_ctx* ctx) { return ctx && ctx->codec ? ctx->codec->frame_len : 0; }
+
+// ---- launch trace hooks (fishtts_hip_test.h)
+extern "C" ft_status ft_test_codec_trace_arm(ft_ctx* ctx, int32_t first, int32_t count) {
+    if (!ctx) return FT_ERR_ARG;
+    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    if (first < 0 || count < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_codec_trace_arm: bad range");
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    s->tstore.recs.clear();
+    s->tstore.first = first; s->tstore.count = count; s->tstore.armed = true; s->tstore.failed = false;
+    return FT_OK;
+}
+extern "C" int32_t ft_test_codec_trace_count(ft_ctx* ctx) {
+    if (!ctx || !ctx->codec) return -1;
+    std::lock_guard<std::mutex> lock(ctx->codec->mu);
+    return ctx->codec->tstore.failed ? -1 : (int32_t)ctx->codec->tstore.recs.size();
+}
+extern "C" int32_t ft_test_codec_trace_variants(void) { return N_GEMM_VARIANTS; }
+extern "C" const char* ft_test_codec_trace_variant(int32_t id, int32_t* bm, int32_t* bn) {
+    if (id < 0 || id >= N_GEMM_VARIANTS) return nullptr;
+    if (bm) *bm = GEMM_VARIANTS[id].bm;
+    if (bn) *bn = GEMM_VARIANTS[id].bn;
+    return GEMM_VARIANTS[id].name;
+}
+extern "C" ft_status ft_test_codec_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t cap, int32_t* info) {
+    if (!ctx || !ctx->codec || !name || cap < 1 || !info) return FT_ERR_ARG;
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (i < 0 || i >= (int)s->tstore.recs.size()) return ft_fail(ctx, FT_ERR_ARG, "ft_test_codec_trace_launch: no such launch");
+    const CodecState::TraceRec& r = s->tstore.recs[i];
+    snprintf(name, (size_t)cap, "%s", r.name.c_str());
+    info[0] = r.rows; info[1] = r.cols; info[2] = r.variant; info[3] = (int32_t)r.bufs.size();
+    info[4] = r.halo; info[5] = r.ntap; info[6] = r.K; info[7] = r.held ? 1 : 0;
+    return FT_OK;
+}
+extern "C" ft_status ft_test_codec_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t* kind, int32_t* is_f32, int64_t* elems,
+                                                void* dst) {
+    if (!ctx || !ctx->codec || !kind || !is_f32 || !elems) return FT_ERR_ARG;
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (i < 0 || i >= (int)s->tstore.recs.size() || j < 0 || j >= (int)s->tstore.recs[i].bufs.size())
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_codec_trace_buffer: no such buffer");
+    CodecState::TraceBuf& b = s->tstore.recs[i].bufs[j];
+    *kind = b.kind; *is_f32 = b.f32; *elems = b.elems;
+    if (dst) {
+        if (b.data.empty()) return ft_fail(ctx, FT_ERR_STATE, "ft_test_codec_trace_buffer: launch outside the armed range");
+        memcpy(dst, b.data.data(), b.data.size());
+        std::vector<char>().swap(b.data);   // handed over: a 215-frame stage is tens of MB
+    }
+    return FT_OK;
+}

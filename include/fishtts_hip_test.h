@@ -49,6 +49,28 @@ ft_status ft_test_sample(ft_ctx* ctx, const float* logits, int32_t cb, const ft_
  * (zeros before and after it) -> y: *n_out = ft_resampled_len(sample_rate, n) samples. */
 ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out);
 
+/* Test hook: a launch trace of the codec.  ft_test_codec_trace_arm makes the NEXT ft_codec_decode (B = 1; any other
+ * B disarms it untraced) or ft_codec_encode on this context record one entry per kernel launch of the one-shot path, in
+ * launch order: a stable stage name ("post.2.wo", "up.1.pw1", "dec.3.u2.c7", "enc.2.sc", ...), the rows and columns
+ * it wrote and, for a GEMM launch, the id of the instantiation picked (0 .. ft_test_codec_trace_variants() - 1, -1 for
+ * the other kernels).  Launches [first, first + count) also keep a host copy of every buffer they wrote (bf16 as bf16,
+ * f32 as f32, rows x cols dense), taken at that point of the stream because the work buffers are reused; the range
+ * exists because a 215-frame trace held whole is several GB.  Recording only reads: the traced call's result equals
+ * the untraced one bit for bit.  Off (one null-pointer test per launch) unless armed; the trace stays readable until
+ * the next arm.
+ * ft_test_codec_trace_count: launches the last traced call recorded (-1: a copy failed).
+ * ft_test_codec_trace_variant: name and row / column tile of an instantiation id (NULL: no such id).
+ * ft_test_codec_trace_launch: info[8] = {rows, cols, variant, buffers, halo rows, taps, K per tap, 1 if held}.
+ * ft_test_codec_trace_buffer: buffer j of launch i: kind (0 out_bf / main output, 1 out_act (Snake'd copy), 2 out_f32),
+ * is_f32, element count; dst != NULL receives the values (once: the copy is released). */
+ft_status ft_test_codec_trace_arm(ft_ctx* ctx, int32_t first, int32_t count);
+int32_t ft_test_codec_trace_count(ft_ctx* ctx);
+int32_t ft_test_codec_trace_variants(void);
+const char* ft_test_codec_trace_variant(int32_t id, int32_t* bm, int32_t* bn);
+ft_status ft_test_codec_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t cap, int32_t* info);
+ft_status ft_test_codec_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t* kind, int32_t* is_f32, int64_t* elems,
+                                     void* dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,261 @@
+"""Pins tests/codec_stage_ref.py on the CPU: (1) chained freely in float64 it IS the codec (the oracle, and through it
+the reference project's own output); (2) its checker passes an honest float32 / bf16 emulation of the device with zero
+flagged elements and flags every one of a list of subtle emulated kernel bugs at the right stage and rows - the proof
+that tests/test_codec_stages_gpu.py would fail if a kernel were subtly wrong."""
+import dataclasses
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import codec as C
+from tests import codec_stage_ref as R
+from tests.golden.make_golden_codec import tiny_codec_shape
+
+G = os.path.join(os.path.dirname(__file__), "golden")
+
+
+def encode_shape():
+    """The shape of tests/test_codec_gpu.py's encode tests (smallest widths the MFMA tiles take)."""
+    return C.CodecShape(n_codebooks=3, codebook_size=64, semantic_codebook_size=128, codebook_dim=8, latent_dim=512,
+                        n_tf_layer=2, tf_n_head=8, tf_head_dim=64, tf_ffn=768, tf_window=8, tf_block_size=256,
+                        upsample=[2, 2], decoder_dim=128, rates=[4, 4], encoder_dim=32, encoder_rates=[2, 2, 2, 2],
+                        encoder_tf_layers=[0, 0, 1, 1], enc_tf_window=16, enc_tf_block_size=1024)
+
+
+def rand_codes(shape, T, seed):
+    g = torch.Generator().manual_seed(seed)
+    codes = torch.zeros(shape.n_codebooks + 1, T, dtype=torch.long)
+    codes[0] = torch.randint(0, shape.semantic_codebook_size, (T,), generator=g)
+    codes[1:] = torch.randint(0, shape.codebook_size, (shape.n_codebooks, T), generator=g)
+    return codes
+
+
+def test_audio(n, seed=5):
+    g = torch.Generator().manual_seed(seed)
+    t = torch.arange(n).float()
+    return (0.4 * torch.sin(2 * np.pi * t / 37.0) + 0.2 * torch.randn(n, generator=g)).numpy()
+
+
+test_audio.__test__ = False
+
+
+def rel_rms(a, b):
+    a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
+    return float((a - b).pow(2).mean().sqrt() / b.pow(2).mean().sqrt())
+
+
+def roundoff_bound(plan):
+    """Distance allowed between the float64 chain and the float32 oracle.  One float32 contraction of n terms is off by
+    at most n u relative to S (u = 2^-24), the other operations by a few u; the stages are in series and none amplifies
+    a relative perturbation by more than O(1) (norms and LayerScale / ConvNeXt gammas of 0.1-0.2 keep the stack at unit
+    scale), so the relative RMS distance is bounded by (number of launches) x (largest term count) x u - the worst case,
+    linear in both; the measured distance (printed) is three orders of magnitude below it."""
+    n_max = max(len(st.p["offs"]) * st.p["K"] for st in plan if st.kind == "gemm")
+    return len(plan) * n_max * R.U
+
+
+def test_free_chain_reproduces_the_oracle_decode_and_the_reference_golden():
+    shape = tiny_codec_shape()
+    w = C.random_weights(shape, seed=0)
+    orc = C.CodecOracle(shape, w)
+    gold = np.load(os.path.join(G, "codec_tiny.npz"))
+    cases = [("b1", torch.from_numpy(gold["b1.codes"])[0], gold["b1.audio"][0, 0]),
+             ("b2[1]", torch.from_numpy(gold["b2.codes"])[1], gold["b2.audio"][1, 0]),
+             ("T=40", rand_codes(shape, 40, 9), None), ("T=1", rand_codes(shape, 1, 3), None)]
+    for name, codes, golden in cases:
+        plan = R.plan_decode(shape, codes)
+        env = R.chain_free(plan, w)
+        want, _ = orc.decode(codes[None], torch.tensor([codes.shape[1]]))
+        bound = roundoff_bound(plan)
+        d = rel_rms(env["audio"][:, 0], want[0, 0])
+        print(f"decode {name}: float64 chain vs f32 oracle, relative RMS {d:.2e} (bound {bound:.2e})")
+        assert env["audio"].shape == (codes.shape[1] * shape.frame_len, 1)
+        assert d <= bound, (name, d, bound)
+        if golden is not None:     # the oracle equals the golden file bit for bit (test_codec_oracle_golden.py)
+            assert rel_rms(env["audio"][:, 0], golden) <= bound, name
+
+
+def test_free_chain_reproduces_the_oracle_encode_taps():
+    shape = encode_shape()
+    w = C.random_weights(shape, seed=0)
+    w.update(C.random_encoder_weights(shape, seed=1))
+    orc = C.CodecOracle(shape, w)
+    for frames, cut, seed in ((37, 11, 5), (61, 5, 12)):
+        audio = test_audio(frames * shape.enc_frame_len - cut, seed)
+        plan = R.plan_encode(shape, audio)
+        env = R.chain_free(plan, w, keep=("enc.out",))
+        orc.encode(torch.from_numpy(audio)[None, None])
+        bound = roundoff_bound(plan)
+        d_enc = rel_rms(env["enc.out"]["bf"], orc.taps["enc_out"][0].t())
+        d_pre = rel_rms(env["zq"], orc.taps["pre"][0].t())
+        print(f"encode {frames} frames: enc_out {d_enc:.2e}, pre {d_pre:.2e} (bound {bound:.2e})")
+        assert env["zq"].shape == (frames, shape.latent_dim)
+        assert d_enc <= bound and d_pre <= bound, (d_enc, d_pre, bound)
+
+
+def test_select_rows_meets_the_stated_condition():
+    for M, halo, bm in ((4095, 54, 128), (4096, 54, 128), (440320, 54, 256), (30001, 6, 128), (100000, 0, 64)):
+        rows = R.select_rows(M, halo, bm, seed=1)
+        s = set(rows.tolist())
+        assert rows.tolist() == sorted(s) and min(s) >= 0 and max(s) < M
+        if M < 4096:
+            assert len(s) == M
+            continue
+        assert set(range(halo + 8)) <= s                                        # start-up padding
+        assert set(range(((M - 1) // bm - 1) * bm, M)) <= s                     # the last two row tiles
+        nb = (M - 1) // bm
+        full = [b for b in range(1, nb + 1) if set(range(b * bm - 4, min(M, b * bm + 4))) <= s]
+        assert len(full) >= 8, len(full)                                        # four rows either side of >= 8 boundaries
+        assert len(s) >= 1024 + halo + 8
+        assert R.select_rows(M, halo, bm, seed=1).tolist() == rows.tolist()     # fixed seed
+
+
+def test_half_ulp():
+    m = torch.tensor([1.0, 1.5, 1.999, 2.0, 0.75, 3e-3, 100.0], dtype=torch.float64)
+    want = [2.0 ** -8, 2.0 ** -8, 2.0 ** -8, 2.0 ** -7, 2.0 ** -9, 2.0 ** -17, 2.0 ** -2]
+    assert R.half_ulp(m, f32=False).tolist() == want
+    assert R.half_ulp(m, f32=True).tolist() == [x * 2.0 ** -16 for x in want]
+    # the store the checker models rounds to nearest even
+    x = torch.tensor([1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, 1.0 + 2.0 ** -8 + 2.0 ** -20])
+    assert R.from_raw(R.bf16_bits(x)).tolist() == [1.0, 1.0 + 2.0 ** -6, 1.0 + 2.0 ** -7]
+
+
+# ------------------------------------------------------------------------------------------------ sensitivity
+def flagged(verdicts):
+    return {v.name: v for v in verdicts if v.flagged}
+
+
+@pytest.fixture(scope="module")
+def tiny():
+    shape = tiny_codec_shape()
+    w = C.random_weights(shape, seed=0)
+    codes = rand_codes(shape, 40, 9)
+    return shape, w, R.plan_decode(shape, codes)
+
+
+def test_checker_passes_an_honest_emulation_with_zero_flagged_elements(tiny):
+    shape, w, plan = tiny
+    vs = R.check_trace(plan, R.chain_emulate(plan, w), w)
+    assert len(vs) == len(plan) and all(v.checked == st.rows * st.cols * len(st.dst) for v, st in zip(vs, plan))
+    assert not flagged(vs), [(v.name, v.flagged, v.worst) for v in flagged(vs).values()]
+    print("emulated decode: largest |got - ref| / bound per kind:",
+          {k: round(max(v.worst for v in vs if v.kind == k), 3) for k in sorted({v.kind for v in vs})})
+    es = encode_shape()
+    we = C.random_weights(es, seed=0)
+    we.update(C.random_encoder_weights(es, seed=1))
+    for frames, cut in ((37, 11), (6, 3)):
+        eplan = R.plan_encode(es, test_audio(frames * es.enc_frame_len - cut))
+        vs = R.check_trace(eplan, R.chain_emulate(eplan, we), we)
+        assert not flagged(vs), [(v.name, v.flagged, v.worst) for v in flagged(vs).values()]
+
+
+def scale_act(rows, cols, factor=1.25):
+    """Emulated MFMA sub-tile bug: the stored values of `cols` in `rows` at `factor` (re-rounded to bf16)."""
+    def f(outs):
+        outs = {k: v.copy() for k, v in outs.items()}
+        for k, a in outs.items():
+            v = R.from_raw(a).clone()
+            ri, ci = torch.tensor(rows)[:, None], torch.tensor(cols)[None, :]
+            v[ri, ci] = v[ri, ci] * factor
+            outs[k] = R.raw_store(k, v)
+        return outs
+    return f
+
+
+def stage(plan, name):
+    return next(st for st in plan if st.name == name)
+
+
+def with_p(st, **kw):
+    return dataclasses.replace(st, p={**st.p, **kw})
+
+
+def test_checker_flags_stale_rows_in_place_of_the_causal_padding(tiny):
+    """The final k = 7 convolution reads 6 stale rows (O(1) values left by an earlier decode) instead of zeros: a click
+    in the first 6 samples, invisible to a whole-waveform relative RMS."""
+    shape, w, plan = tiny
+    g = torch.Generator().manual_seed(4)
+    st = stage(plan, "final")
+    stale = R.from_raw(R.bf16_bits(torch.randn(6, st.p["C"], generator=g) * 0.8))
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, override={"final": with_p(st, stale=stale)}), w))
+    assert set(bad) == {"final"}, sorted(bad)
+    assert bad["final"].rows and set(bad["final"].rows) <= set(range(6)) and 0 in bad["final"].rows, bad["final"].rows
+    # the same in a dilated convolution's tap GEMM and in the depthwise convolution
+    for name, halo in (("dec.0.u2.c7", 54), ("up.1.dwln", 6)):
+        st = stage(plan, name)
+        C_in = st.p["K"] if st.kind == "gemm" else st.cols
+        stale = R.from_raw(R.bf16_bits(torch.randn(halo, C_in, generator=g) * 0.8))
+        bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, override={name: with_p(st, stale=stale)}), w))
+        assert set(bad) == {name}, sorted(bad)
+        assert bad[name].rows and set(bad[name].rows) <= set(range(halo)) and 0 in bad[name].rows, bad[name].rows
+
+
+def test_checker_flags_one_bad_sub_tile_per_row_tile(tiny):
+    """16 output channels of one row in every 128 at 1.25x in one dilated convolution of block 0; then the same, one row
+    in 64, in every k = 7 convolution: each is flagged at exactly those rows, and nothing else is."""
+    shape, w, plan = tiny
+    st = stage(plan, "dec.0.u1.c7")
+    rows = list(range(5, st.rows, 128))
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, mutate={st.name: scale_act(rows, list(range(16, 32)))}), w))
+    assert set(bad) == {st.name} and bad[st.name].rows == rows, {k: v.rows for k, v in bad.items()}
+    c7 = [s for s in plan if s.name.endswith(".c7") or s.name == "dec.in"]
+    mut = {s.name: scale_act(list(range(9, s.rows, 64)), list(range(0, 16))) for s in c7}
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, mutate=mut), w))
+    assert set(bad) == {s.name for s in c7}, sorted(bad)
+    for s in c7:
+        assert bad[s.name].rows == list(range(9, s.rows, 64)), s.name
+
+
+def test_checker_flags_an_attention_window_off_by_one(tiny):
+    shape, w, plan = tiny
+    st = stage(plan, "post.1.attn")
+    bugged = with_p(st, window=st.p["window"] - 1)
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, override={st.name: bugged}), w))
+    assert set(bad) == {st.name}, sorted(bad)
+    first = st.p["window"] - 1                                  # rows below it see the same keys either way
+    assert bad[st.name].rows and min(bad[st.name].rows) >= first, bad[st.name].rows
+    assert len(bad[st.name].rows) >= (st.rows - first) * 3 // 4, len(bad[st.name].rows)
+
+
+def test_checker_flags_a_dropped_tap_a_dropped_bias_and_two_ulp(tiny):
+    shape, w, plan = tiny
+    st = stage(plan, "dec.1.u2.c7")                             # dilation 9
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, override={st.name: with_p(st, drop_tap=2)}), w))
+    assert set(bad) == {st.name} and len(bad[st.name].rows) > st.rows // 2
+    st = stage(plan, "dec.1.u0.c1")                             # a 1x1 convolution
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, override={st.name: with_p(st, drop_bias=True)}), w))
+    assert set(bad) == {st.name} and len(bad[st.name].rows) > st.rows // 2
+    # one stored element two bf16 ulp off (same binade)
+    for name, kind in (("dec.0.u0.c1", "bf"), ("up.0.pw1", "bf"), ("dec.1.u1.c7", "act")):
+        st = stage(plan, name)
+
+        def two_ulp(outs, kind=kind, st=st):
+            outs = {k: v.copy() for k, v in outs.items()}
+            a = outs[kind]
+            r, c = st.rows // 3, st.cols // 2
+            assert (int(a[r, c]) & 0x7F) < 0x7D                 # stays in its binade
+            a[r, c] += 2
+            return outs
+        bad = flagged(R.check_trace(plan, R.chain_emulate(plan, w, mutate={name: two_ulp}), w))
+        assert set(bad) == {name} and bad[name].flagged == 1 and bad[name].rows == [st.rows // 3], (name, sorted(bad))
+
+
+def test_checker_flags_a_wrong_f32_residual_stream_and_encode_side_bugs():
+    """f32 stores are held to half an f32 ulp + the accumulation bound: a relative error of 1e-5 in one element of the
+    transformer's residual stream is flagged; on the encode side a strided convolution that drops its bias is."""
+    es = encode_shape()
+    we = C.random_weights(es, seed=0)
+    we.update(C.random_encoder_weights(es, seed=1))
+    plan = R.plan_encode(es, test_audio(20 * es.enc_frame_len - 3))
+
+    def nudge(outs):
+        outs = {k: v.copy() for k, v in outs.items()}
+        outs["f32"][3, 7] *= np.float32(1.00001)
+        return outs
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, we, mutate={"pre.0.wo": nudge}), we))
+    assert set(bad) == {"pre.0.wo"} and bad["pre.0.wo"].rows == [3] and bad["pre.0.wo"].flagged == 1
+    st = stage(plan, "enc.1.sc")
+    bad = flagged(R.check_trace(plan, R.chain_emulate(plan, we, override={st.name: with_p(st, drop_bias=True)}), we))
+    assert set(bad) == {st.name}
