@@ -226,6 +226,22 @@ class CodecHipEngine:
 
     MAX_STREAMS_PER_CALL = 64     # ft_codec_stream_decode_many
 
+    def _stream_groups(self, streams, chunks):
+        """The streams of one native call after the other: (i, j, streams[i:j], lens, codes, handles), at most 64 streams
+        and max_frames frames together in each (a single chunk goes alone whatever its length: the call judges it)."""
+        i = 0
+        while i < len(streams):
+            j, total = i, 0
+            while j < len(streams) and j - i < self.MAX_STREAMS_PER_CALL and (j == i or total + chunks[j].shape[1] <= self.max_frames):
+                total += chunks[j].shape[1]
+                j += 1
+            group = streams[i:j]
+            lens = np.array([c.shape[1] for c in chunks[i:j]], dtype=np.int32)
+            codes = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in chunks[i:j]]))
+            handles = (C.c_void_p * len(group))(*[s._h.value for s in group])
+            yield i, j, group, lens, codes, handles
+            i = j
+
     def decode_streams(self, streams: Sequence["CodecStream"], chunks: Sequence[np.ndarray],
                        final: Optional[Sequence[bool]] = None) -> List[np.ndarray]:
         """The next chunk of each of several distinct streams of this engine, in one pass through the codec per native
@@ -244,16 +260,7 @@ class CodecHipEngine:
         if final is not None or any(s.rate is not None for s in streams):
             return self._decode_streams_at(streams, chunks, [False] * len(streams) if final is None else list(final))
         out: List[np.ndarray] = []
-        i = 0
-        while i < len(streams):
-            j, total = i, 0
-            while j < len(streams) and j - i < self.MAX_STREAMS_PER_CALL and (j == i or total + chunks[j].shape[1] <= self.max_frames):
-                total += chunks[j].shape[1]
-                j += 1
-            group = streams[i:j]
-            lens = np.array([c.shape[1] for c in chunks[i:j]], dtype=np.int32)
-            codes = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in chunks[i:j]]))
-            handles = (C.c_void_p * len(group))(*[s._h.value for s in group])
+        for _, _, group, lens, codes, handles in self._stream_groups(streams, chunks):
             audio = np.empty(int(lens.sum()) * self.frame_len, dtype=np.float32)
             self._check(self.lib.ft_codec_stream_decode_many(self._h, len(group), handles, codes.ctypes.data_as(C.c_void_p),
                                                              lens.ctypes.data_as(C.c_void_p), audio.ctypes.data_as(C.c_void_p)),
@@ -263,24 +270,14 @@ class CodecHipEngine:
                 s.frames += int(T)
                 out.append(audio[off:off + int(T) * self.frame_len])
                 off += int(T) * self.frame_len
-            i = j
         return out
 
     def _decode_streams_at(self, streams, chunks, final) -> List[np.ndarray]:
         if len(final) != len(streams):
             raise ValueError("decode_streams: one final flag per stream")
         out: List[np.ndarray] = []
-        i = 0
-        while i < len(streams):
-            j, total = i, 0
-            while j < len(streams) and j - i < self.MAX_STREAMS_PER_CALL and (j == i or total + chunks[j].shape[1] <= self.max_frames):
-                total += chunks[j].shape[1]
-                j += 1
-            group = streams[i:j]
-            lens = np.array([c.shape[1] for c in chunks[i:j]], dtype=np.int32)
+        for i, j, group, lens, codes, handles in self._stream_groups(streams, chunks):
             fin = np.array([1 if f else 0 for f in final[i:j]], dtype=np.int32)
-            codes = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in chunks[i:j]]))
-            handles = (C.c_void_p * len(group))(*[s._h.value for s in group])
             # room for everything each stream can emit: its outputs up to the end of the chunk, less those it gave
             cap = sum(s._cap(int(T) * self.frame_len) for s, T in zip(group, lens))
             audio = np.empty(max(cap, 1), dtype=np.float32)
@@ -294,7 +291,6 @@ class CodecHipEngine:
                 s._advance(int(T), int(n), bool(f))
                 out.append(audio[off:off + int(n)])
                 off += int(n)
-            i = j
         return out
 
     def test_resample(self, x: np.ndarray, sample_rate: int) -> np.ndarray:

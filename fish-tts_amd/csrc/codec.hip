@@ -115,29 +115,18 @@ void codec_expected(ft_ctx* ctx) {
     const ft_codec_config& c = ctx->cc;
     const int D = c.latent_dim, H = c.tf_n_head * c.tf_head_dim;
     auto E = [&](const std::string& n, std::vector<int64_t> s) { ft_expect(ctx, n, std::move(s), FT_F32); };
-    E("quantizer.semantic_quantizer.quantizers.0.codebook.weight", {c.semantic_codebook_size, c.codebook_dim});
-    E("quantizer.semantic_quantizer.quantizers.0.out_proj.weight", {D, c.codebook_dim, 1});
-    E("quantizer.semantic_quantizer.quantizers.0.out_proj.bias", {D});
-    for (int i = 0; i < c.n_codebooks; ++i) {
-        E(cname("quantizer.quantizer.quantizers.%d.codebook.weight", i), {c.codebook_size, c.codebook_dim});
-        E(cname("quantizer.quantizer.quantizers.%d.out_proj.weight", i), {D, c.codebook_dim, 1});
-        E(cname("quantizer.quantizer.quantizers.%d.out_proj.bias", i), {D});
-    }
-    for (int l = 0; l < c.n_tf_layer; ++l) {
-        const std::string p = cname("quantizer.post_module.layers.%d", l);
-        E(p + ".attention.wqkv.weight", {3 * H, D});
-        E(p + ".attention.wo.weight", {D, H});
-        E(p + ".feed_forward.w1.weight", {c.tf_ffn, D});
-        E(p + ".feed_forward.w3.weight", {c.tf_ffn, D});
-        E(p + ".feed_forward.w2.weight", {D, c.tf_ffn});
-        E(p + ".ffn_norm.weight", {D});
-        E(p + ".attention_norm.weight", {D});
-        E(p + ".attention_layer_scale.gamma", {D});
-        E(p + ".ffn_layer_scale.gamma", {D});
-    }
-    E("quantizer.post_module.norm.weight", {D});
-    for (int j = 0; j < c.n_upsample; ++j) {
-        const std::string p = cname("quantizer.upsample.%d", j);
+    auto tf_layer = [&](const std::string& p, int d, int h, int ffn) {   // one window-transformer layer of width d
+        E(p + ".attention.wqkv.weight", {3 * h, d});
+        E(p + ".attention.wo.weight", {d, h});
+        E(p + ".feed_forward.w1.weight", {ffn, d});
+        E(p + ".feed_forward.w3.weight", {ffn, d});
+        E(p + ".feed_forward.w2.weight", {d, ffn});
+        E(p + ".ffn_norm.weight", {d});
+        E(p + ".attention_norm.weight", {d});
+        E(p + ".attention_layer_scale.gamma", {d});
+        E(p + ".ffn_layer_scale.gamma", {d});
+    };
+    auto resample_stage = [&](const std::string& p) {   // quantizer.upsample / downsample: (transposed) conv k = s = 2, ConvNeXt
         E(p + ".0.conv.weight", {D, D, 2});
         E(p + ".0.conv.bias", {D});
         E(p + ".1.dwconv.conv.weight", {D, 1, 7});
@@ -149,7 +138,18 @@ void codec_expected(ft_ctx* ctx) {
         E(p + ".1.pwconv2.weight", {D, 4 * D});
         E(p + ".1.pwconv2.bias", {D});
         E(p + ".1.gamma", {D});
+    };
+    E("quantizer.semantic_quantizer.quantizers.0.codebook.weight", {c.semantic_codebook_size, c.codebook_dim});
+    E("quantizer.semantic_quantizer.quantizers.0.out_proj.weight", {D, c.codebook_dim, 1});
+    E("quantizer.semantic_quantizer.quantizers.0.out_proj.bias", {D});
+    for (int i = 0; i < c.n_codebooks; ++i) {
+        E(cname("quantizer.quantizer.quantizers.%d.codebook.weight", i), {c.codebook_size, c.codebook_dim});
+        E(cname("quantizer.quantizer.quantizers.%d.out_proj.weight", i), {D, c.codebook_dim, 1});
+        E(cname("quantizer.quantizer.quantizers.%d.out_proj.bias", i), {D});
     }
+    for (int l = 0; l < c.n_tf_layer; ++l) tf_layer(cname("quantizer.post_module.layers.%d", l), D, H, c.tf_ffn);
+    E("quantizer.post_module.norm.weight", {D});
+    for (int j = 0; j < c.n_upsample; ++j) resample_stage(cname("quantizer.upsample.%d", j));
     E("decoder.model.0.conv.weight", {c.decoder_dim, D, 7});
     E("decoder.model.0.conv.bias", {c.decoder_dim});
     for (int i = 0; i < c.n_rates; ++i) {
@@ -193,49 +193,14 @@ void codec_expected(ft_ctx* ctx) {
         E(p + ".3.alpha", {1, d / 2, 1});
         E(p + ".4.conv.weight", {d, d / 2, 2 * c.enc_rates[i]});
         E(p + ".4.conv.bias", {d});
-        for (int l = 0; l < c.enc_tf_layers[i]; ++l) {
-            const std::string t = p + cname(".5.layers.%d", l);
-            E(t + ".attention.wqkv.weight", {3 * d, d});
-            E(t + ".attention.wo.weight", {d, d});
-            E(t + ".feed_forward.w1.weight", {3 * d, d});
-            E(t + ".feed_forward.w3.weight", {3 * d, d});
-            E(t + ".feed_forward.w2.weight", {d, 3 * d});
-            E(t + ".ffn_norm.weight", {d});
-            E(t + ".attention_norm.weight", {d});
-            E(t + ".attention_layer_scale.gamma", {d});
-            E(t + ".ffn_layer_scale.gamma", {d});
-        }
+        for (int l = 0; l < c.enc_tf_layers[i]; ++l) tf_layer(p + cname(".5.layers.%d", l), d, d, 3 * d);
         if (c.enc_tf_layers[i]) E(p + ".5.norm.weight", {d});
     }
     E(cname("encoder.block.%d.alpha", c.n_enc_rates + 1), {1, d, 1});
     E(cname("encoder.block.%d.conv.weight", c.n_enc_rates + 2), {D, d, 3});
     E(cname("encoder.block.%d.conv.bias", c.n_enc_rates + 2), {D});
-    for (int j = 0; j < c.n_upsample; ++j) {
-        const std::string p = cname("quantizer.downsample.%d", j);
-        E(p + ".0.conv.weight", {D, D, 2});
-        E(p + ".0.conv.bias", {D});
-        E(p + ".1.dwconv.conv.weight", {D, 1, 7});
-        E(p + ".1.dwconv.conv.bias", {D});
-        E(p + ".1.norm.weight", {D});
-        E(p + ".1.norm.bias", {D});
-        E(p + ".1.pwconv1.weight", {4 * D, D});
-        E(p + ".1.pwconv1.bias", {4 * D});
-        E(p + ".1.pwconv2.weight", {D, 4 * D});
-        E(p + ".1.pwconv2.bias", {D});
-        E(p + ".1.gamma", {D});
-    }
-    for (int l = 0; l < c.n_tf_layer; ++l) {
-        const std::string p = cname("quantizer.pre_module.layers.%d", l);
-        E(p + ".attention.wqkv.weight", {3 * H, D});
-        E(p + ".attention.wo.weight", {D, H});
-        E(p + ".feed_forward.w1.weight", {c.tf_ffn, D});
-        E(p + ".feed_forward.w3.weight", {c.tf_ffn, D});
-        E(p + ".feed_forward.w2.weight", {D, c.tf_ffn});
-        E(p + ".ffn_norm.weight", {D});
-        E(p + ".attention_norm.weight", {D});
-        E(p + ".attention_layer_scale.gamma", {D});
-        E(p + ".ffn_layer_scale.gamma", {D});
-    }
+    for (int j = 0; j < c.n_upsample; ++j) resample_stage(cname("quantizer.downsample.%d", j));
+    for (int l = 0; l < c.n_tf_layer; ++l) tf_layer(cname("quantizer.pre_module.layers.%d", l), D, H, c.tf_ffn);
     E("quantizer.pre_module.norm.weight", {D});
     E("quantizer.semantic_quantizer.quantizers.0.in_proj.weight", {c.codebook_dim, D, 1});
     E("quantizer.semantic_quantizer.quantizers.0.in_proj.bias", {c.codebook_dim});
@@ -307,13 +272,28 @@ static ft_status cmalloc(ft_ctx* ctx, T** p, size_t n) {
 static float* W32(ft_ctx* ctx, const std::string& n) { return (float*)ctx->expected[n].p; }
 static int gridfor(long n) { long b = (n + 255) / 256; return (int)(b < 4096 ? b : 4096); }
 
+// rows before the current one a convolution reads (a causal convolution's carried rows in a streamed decode)
+static int halo_of(const ConvW& w) {
+    int h = 0;
+    for (int i = 0; i < w.ntap; ++i) h = std::max(h, -w.offs[i]);
+    return h;
+}
+// What the pipelined kernels of gemm() need of a weight: 32-wide K steps, an A stripe of BM + 56 rows.  codec_create's
+// channel checks and the convolutions of the model (largest halo 54: k = 7, dilation 9) keep every packed weight to it,
+// so gemm()'s fall-back for other weights is never taken ("One decode chain", on why it is still there).
+constexpr int GEMM_MAX_HALO = 56;
+static ft_status pack_check(ft_ctx* ctx, const ConvW& cw) {
+    if (cw.K % 32 == 0 && halo_of(cw) <= GEMM_MAX_HALO) return FT_OK;
+    return ft_fail(ctx, FT_ERR_UNSUPPORTED, "codec: a convolution needs input channels in multiples of 32 and a halo of at most 56 rows");
+}
+
 static ft_status pack_linear(ft_ctx* ctx, ConvW& cw, const std::string& wname, const std::string& bname, int N, int K) {
     CodecState* s = ctx->codec;
     FT_TRY(cmalloc(ctx, &cw.w, (size_t)N * K));
     pack_rows_kernel<<<gridfor((long)N * K), 256, 0, s->stream>>>(W32(ctx, wname), cw.w, (long)N * K);
     cw.bias = bname.empty() ? nullptr : W32(ctx, bname);
     cw.ntap = 1; cw.N = N; cw.K = K; cw.n_mod = N; cw.offs[0] = 0;
-    return FT_OK;
+    return pack_check(ctx, cw);
 }
 static ft_status pack_conv(ft_ctx* ctx, ConvW& cw, const std::string& pfx, int Cout, int Cin, int k, int dil) {
     CodecState* s = ctx->codec;
@@ -322,7 +302,7 @@ static ft_status pack_conv(ft_ctx* ctx, ConvW& cw, const std::string& pfx, int C
     cw.bias = W32(ctx, pfx + ".bias");
     cw.ntap = k; cw.N = Cout; cw.K = Cin; cw.n_mod = Cout;
     for (int kk = 0; kk < k; ++kk) cw.offs[kk] = (kk - (k - 1)) * dil;
-    return FT_OK;
+    return pack_check(ctx, cw);
 }
 static ft_status pack_convT(ft_ctx* ctx, ConvW& cw, const std::string& pfx, int Cin, int Cout, int k, int stride) {
     CodecState* s = ctx->codec;
@@ -331,7 +311,7 @@ static ft_status pack_convT(ft_ctx* ctx, ConvW& cw, const std::string& pfx, int 
     cw.bias = W32(ctx, pfx + ".bias");
     cw.ntap = k / stride; cw.N = stride * Cout; cw.K = Cin; cw.n_mod = Cout;
     for (int j = 0; j < cw.ntap; ++j) cw.offs[j] = -j;
-    return FT_OK;
+    return pack_check(ctx, cw);
 }
 
 static ft_status pack_strided(ft_ctx* ctx, ConvW& cw, const std::string& pfx, int Cout, int Cin, int k, int stride) {
@@ -341,7 +321,7 @@ static ft_status pack_strided(ft_ctx* ctx, ConvW& cw, const std::string& pfx, in
     cw.bias = W32(ctx, pfx + ".bias");
     cw.ntap = k / stride; cw.N = Cout; cw.K = stride * Cin; cw.n_mod = Cout;
     for (int a = 0; a < cw.ntap; ++a) cw.offs[a] = a - (cw.ntap - 1);
-    return FT_OK;
+    return pack_check(ctx, cw);
 }
 static ft_status pack_tf_layer(ft_ctx* ctx, TfLayer& t, const std::string& p, int D, int H, int ffn) {
     CodecState* s = ctx->codec;
@@ -354,7 +334,17 @@ static ft_status pack_tf_layer(ft_ctx* ctx, TfLayer& t, const std::string& p, in
     t.w13.ntap = 1; t.w13.N = 2 * ffn; t.w13.K = D; t.w13.n_mod = 2 * ffn; t.w13.bias = nullptr;
     t.n1 = W32(ctx, p + ".attention_norm.weight"); t.n2 = W32(ctx, p + ".ffn_norm.weight");
     t.g1 = W32(ctx, p + ".attention_layer_scale.gamma"); t.g2 = W32(ctx, p + ".ffn_layer_scale.gamma");
-    return FT_OK;
+    return pack_check(ctx, t.w13);
+}
+
+// The ConvNeXt block behind the (transposed) convolution of a quantizer.upsample / downsample stage `p`.
+static ft_status pack_convnext(ft_ctx* ctx, UpStage& u, const std::string& p, int D) {
+    u.f = 2;
+    u.dw_w = W32(ctx, p + ".1.dwconv.conv.weight"); u.dw_b = W32(ctx, p + ".1.dwconv.conv.bias");
+    u.ln_w = W32(ctx, p + ".1.norm.weight"); u.ln_b = W32(ctx, p + ".1.norm.bias");
+    u.gamma = W32(ctx, p + ".1.gamma");
+    FT_TRY(pack_linear(ctx, u.pw1, p + ".1.pwconv1.weight", p + ".1.pwconv1.bias", 4 * D, D));
+    return pack_linear(ctx, u.pw2, p + ".1.pwconv2.weight", p + ".1.pwconv2.bias", D, 4 * D);
 }
 
 static ft_status codec_finalize_encoder(ft_ctx* ctx) {
@@ -396,14 +386,8 @@ static ft_status codec_finalize_encoder(ft_ctx* ctx) {
     s->down.resize(c.n_upsample);
     for (int j = 0; j < c.n_upsample; ++j) {
         const std::string p = cname("quantizer.downsample.%d", j);
-        UpStage& u = s->down[j];
-        u.f = 2;
-        FT_TRY(pack_strided(ctx, u.ct, p + ".0.conv", D, D, 2, 2));
-        u.dw_w = W32(ctx, p + ".1.dwconv.conv.weight"); u.dw_b = W32(ctx, p + ".1.dwconv.conv.bias");
-        u.ln_w = W32(ctx, p + ".1.norm.weight"); u.ln_b = W32(ctx, p + ".1.norm.bias");
-        u.gamma = W32(ctx, p + ".1.gamma");
-        FT_TRY(pack_linear(ctx, u.pw1, p + ".1.pwconv1.weight", p + ".1.pwconv1.bias", 4 * D, D));
-        FT_TRY(pack_linear(ctx, u.pw2, p + ".1.pwconv2.weight", p + ".1.pwconv2.bias", D, 4 * D));
+        FT_TRY(pack_strided(ctx, s->down[j].ct, p + ".0.conv", D, D, 2, 2));
+        FT_TRY(pack_convnext(ctx, s->down[j], p, D));
     }
     s->pre.resize(c.n_tf_layer);
     for (int l = 0; l < c.n_tf_layer; ++l)
@@ -462,31 +446,14 @@ ft_status codec_finalize(ft_ctx* ctx) {
     }
     s->rope = W32(ctx, "rope.codec");
     s->tf.resize(c.n_tf_layer);
-    for (int l = 0; l < c.n_tf_layer; ++l) {
-        const std::string p = cname("quantizer.post_module.layers.%d", l);
-        TfLayer& t = s->tf[l];
-        FT_TRY(pack_linear(ctx, t.qkv, p + ".attention.wqkv.weight", "", 3 * H, D));
-        FT_TRY(pack_linear(ctx, t.wo, p + ".attention.wo.weight", "", D, H));
-        FT_TRY(pack_linear(ctx, t.w2, p + ".feed_forward.w2.weight", "", D, c.tf_ffn));
-        FT_TRY(cmalloc(ctx, &t.w13.w, (size_t)2 * c.tf_ffn * D));
-        pack_interleave_kernel<<<gridfor((long)c.tf_ffn * D), 256, 0, s->stream>>>(
-            W32(ctx, p + ".feed_forward.w1.weight"), W32(ctx, p + ".feed_forward.w3.weight"), t.w13.w, c.tf_ffn, D);
-        t.w13.ntap = 1; t.w13.N = 2 * c.tf_ffn; t.w13.K = D; t.w13.n_mod = 2 * c.tf_ffn; t.w13.bias = nullptr;
-        t.n1 = W32(ctx, p + ".attention_norm.weight"); t.n2 = W32(ctx, p + ".ffn_norm.weight");
-        t.g1 = W32(ctx, p + ".attention_layer_scale.gamma"); t.g2 = W32(ctx, p + ".ffn_layer_scale.gamma");
-    }
+    for (int l = 0; l < c.n_tf_layer; ++l)
+        FT_TRY(pack_tf_layer(ctx, s->tf[l], cname("quantizer.post_module.layers.%d", l), D, H, c.tf_ffn));
     s->tf_norm = W32(ctx, "quantizer.post_module.norm.weight");
     s->up.resize(c.n_upsample);
     for (int j = 0; j < c.n_upsample; ++j) {
         const std::string p = cname("quantizer.upsample.%d", j);
-        UpStage& u = s->up[j];
-        u.f = 2;
-        FT_TRY(pack_convT(ctx, u.ct, p + ".0.conv", D, D, 2, 2));
-        u.dw_w = W32(ctx, p + ".1.dwconv.conv.weight"); u.dw_b = W32(ctx, p + ".1.dwconv.conv.bias");
-        u.ln_w = W32(ctx, p + ".1.norm.weight"); u.ln_b = W32(ctx, p + ".1.norm.bias");
-        u.gamma = W32(ctx, p + ".1.gamma");
-        FT_TRY(pack_linear(ctx, u.pw1, p + ".1.pwconv1.weight", p + ".1.pwconv1.bias", 4 * D, D));
-        FT_TRY(pack_linear(ctx, u.pw2, p + ".1.pwconv2.weight", p + ".1.pwconv2.bias", D, 4 * D));
+        FT_TRY(pack_convT(ctx, s->up[j].ct, p + ".0.conv", D, D, 2, 2));
+        FT_TRY(pack_convnext(ctx, s->up[j], p, D));
     }
     FT_TRY(pack_conv(ctx, s->conv_in, "decoder.model.0.conv", c.decoder_dim, D, 7, 1));
     s->blocks.resize(c.n_rates);
@@ -576,8 +543,6 @@ static int gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
     p.out_act = io.out_act; p.alpha = io.alpha; p.ldo = io.ldo; p.t_min = io.t_min;
     p.seg = io.seg; p.seg_m = io.seg_m; p.seg_xg = io.seg_xg; p.seg_og = io.seg_og;
     const long Msel = io.msel > 0 ? io.msel : io.M;
-    int halo = 0;
-    for (int i = 0; i < w.ntap; ++i) halo = std::max(halo, -w.offs[i]);
     // few rows (the 215-frame transformers, the first up-sampling stage): a 64x64 tile grid leaves most CUs idle and every
     // block walks all of K alone (20-75 us per GEMM); the skinny kernel cuts N into 16-row blocks and splits K over the
     // waves of a block (weights streamed once per 64 rows)
@@ -590,7 +555,7 @@ static int gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
         skinny_gemm_launch<4>(p, (io.M + 63) / 64, st, io.nz);
         return 0;
     }
-    if (w.K % 32 == 0 && halo <= 56) {  // pipelined kernel: A stripe shared by the taps, B double-buffered
+    if (w.K % 32 == 0 && halo_of(w) <= GEMM_MAX_HALO) {  // pipelined kernel: A stripe shared by the taps, B double-buffered
 #define FT_TG(BM_, BN_, BK_)                                                                                   \
     tapgemm64_kernel<BM_, BN_, BK_><<<dim3((io.M + BM_ - 1) / BM_, (w.N + BN_ - 1) / BN_, io.nz), 256,          \
                                       std::max((size_t)((BM_ + 56) + 2 * BN_) * (BK_ + 8) * 2,                  \
@@ -633,7 +598,7 @@ static int gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
             return k64 ? 5 : 6;
         }
 #undef FT_TG
-    } else if (w.N >= 128) {
+    } else if (w.N >= 128) {   // never taken (pack_check); see there for why the two instantiations stay
         const dim3 grid((io.M + 127) / 128, (w.N + 127) / 128, io.nz);
         tapgemm_kernel<128, 128, 2, 2><<<grid, 256, 0, st>>>(p);
         return 13;
@@ -681,9 +646,7 @@ static void gemm_t(CodecState* s, hipStream_t st, const ConvW& w, const GemmIO& 
     if (s->trace) {
         const long cols = io.act == ACT_SWIGLU ? w.N / 2 : w.N;
         if (io.ldo != cols) s->trace->failed = true;
-        int halo = 0;
-        for (int i = 0; i < w.ntap; ++i) halo = std::max(halo, -w.offs[i]);
-        trace_rec(s, st, tname(fmt, pfx, a, b), io.M, cols, id, halo, w.ntap, w.K,
+        trace_rec(s, st, tname(fmt, pfx, a, b), io.M, cols, id, halo_of(w), w.ntap, w.K,
                   {{0, io.out_bf, 0}, {1, io.out_act, 0}, {2, io.out_f32, 1}});
     }
 }
@@ -700,6 +663,14 @@ struct TraceScope {   // a traced call: armed -> active for this call only
     ~TraceScope() { s->trace = nullptr; }
 };
 
+// The state checks every codec entry point opens with: a codec in the context and, unless the call works on state that
+// only a finalized context hands out (`finalized` false), its weights finalized.
+static ft_status codec_ready(ft_ctx* ctx, bool finalized = true) {
+    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    if (finalized && !ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    return FT_OK;
+}
+
 // ---- streamed decode state (ft_codec_stream_*): what the causal codec needs from earlier chunks, two copies of each
 // (a chunk reads one and leaves the other).  The codec is strictly causal: the window-128 attention reads the K / V of
 // the 127 frames before a chunk (vocoder.py:325-332), every causal convolution the last `halo` rows of its input
@@ -711,7 +682,7 @@ struct ft_codec_stream {
     int par = 0;          // which copy is current
     std::vector<bf16_t*> kv[2];                    // per transformer layer: [window - 1][2 * H * hd], newest rows last
     struct Tail { bf16_t* buf[2]; int H, C; };
-    std::vector<Tail> tails;                       // in the order decode_one consumes them
+    std::vector<Tail> tails;                       // in the order decode_chain consumes them
     // resampled output (ft_codec_stream_begin_at; rate 0: the codec's own rate, no resampler): the last K input samples,
     // two copies (a call reads one and writes the other), and the input / output sample counters
     int rate = 0;
@@ -727,12 +698,6 @@ static void stream_orphan(ft_codec_stream* sc) {
     for (void* v : sc->owned) hipFree(v);
     sc->owned.clear();
     sc->owner = nullptr;
-}
-
-static int halo_of(const ConvW& w) {
-    int h = 0;
-    for (int i = 0; i < w.ntap; ++i) h = std::max(h, -w.offs[i]);
-    return h;
 }
 
 // ---- resampler (RsSeg, resample_kernel): filter design on the host in float64, a Kaiser-windowed sinc at the up-sampled
@@ -836,109 +801,224 @@ static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host) 
     return FT_OK;
 }
 
-// `rs`: resample the waveform (segment 0, its input set here) and copy the resampled samples instead.
-static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, int T, float* audio_host, ft_codec_stream* sc = nullptr,
-                            std::vector<RsSeg>* rs = nullptr) {
+// ---- the decode chain (DAC.decode), written once.  A Layout says where the rows of a call live; its helpers hand every
+// launch site the values that differ between the forms, and the kernels do the rest: they already take one item or the
+// chunk of blockIdx.z (SegZ::seg, TapGemmP::seg).
+//   one-shot (ft_codec_decode, the encoder's transformers): one item, nothing carried, GEMM variants by the real row count
+//   one stream (ft_codec_stream_decode): one chunk; its carries, rope position and carried K/V rows stated by the host
+//   many streams (ft_codec_stream_decode_many): n chunks on blockIdx.z; the transformer's per-row stages run on compact
+//     rows, everything else leaves gap rows in front of every chunk; what differs per chunk comes from the device table
+struct Layout {
+    int n = 1;                    // items on blockIdx.z
+    const int4* seg = nullptr;    // device table {P, L, t0, nh} per chunk; null: one item
+    int T = 0;                    // frames per launch: the item's, or the longest chunk's
+    int total = 0;                // frames of all items (the compact rows)
+    int own = 0;                  // the item's frames where the host states them; 0: the kernels read them from seg
+    int cgap = 0, qgap = 0;       // gap rows in front of every chunk: the convolution buffers, the q k v buffer
+    long nominal = 0;             // frames the GEMM variants are chosen for (GemmIO::msel, per frame); 0: the real rows
+    const int* codes = nullptr;   // [R][total]
+    bf16_t* big[4] = {nullptr, nullptr, nullptr, nullptr};   // convolution work buffers
+    bf16_t* qkv = nullptr;        // q k v work buffer, at item 0's first query row
+    // carried state.  Carry ci: the convolution tails in the order the chain consumes them, then one K/V per layer
+    const std::vector<ft_codec_stream::Tail>* tails = nullptr;   // the list the stream(s) hold; null: nothing carried
+    bf16_t* const* hcarry = nullptr;   // one stream: [ncarry][read, write], host pointers handed to the kernels
+    bf16_t* const* dcarry = nullptr;   // many: [n][ncarry][read, write] on the device (SegZ::carry)
+    int ncarry = 0;
+    int t0 = 0, nh = 0;           // one stream: rope position, carried K/V rows in front of the chunk (many: from seg)
+    int kv_in = 0, kv_out = 0;    // most K/V rows a chunk takes over / leaves behind; 0: no such launch
+
+    static Layout plain(int T, bf16_t* qkv) {
+        Layout L;
+        L.T = L.total = L.own = T;
+        L.qkv = qkv;
+        return L;
+    }
+    int ntail() const { return tails ? (int)tails->size() : 0; }
+    dim3 grid(int x) const { return dim3(x, 1, n); }
+    // the chunk of blockIdx.z at a stage of m rows per frame and g gap rows (the default SegZ: the one item)
+    SegZ Z(int m, int g, int ci = 0) const {
+        SegZ z;
+        if (seg) { z.seg = seg; z.carry = dcarry; z.ncarry = ncarry; z.ci = ci; z.m = m; z.g = g; }
+        return z;
+    }
+    bf16_t* carry_rd(int ci) const { return hcarry ? hcarry[2 * ci] : nullptr; }
+    bf16_t* carry_wr(int ci) const { return hcarry ? hcarry[2 * ci + 1] : nullptr; }
+    // a GEMM over every item's rows at m rows per frame; xg / og gap rows in front of every chunk of X / of the output
+    GemmIO io(const bf16_t* X, long ldx, int m, int xg, int og) const {
+        GemmIO io{X, ldx, T * m, T * m};
+        io.msel = nominal * m;
+        if (seg) { io.seg = seg; io.nz = n; io.seg_m = m; io.seg_xg = xg; io.seg_og = og; }
+        return io;
+    }
+    // a GEMM over the compact rows of all items (the transformer's linears behind the attention)
+    GemmIO io_rows(const bf16_t* X, long ldx) const {
+        GemmIO io{X, ldx, total, total};
+        io.msel = nominal;
+        return io;
+    }
+};
+
+// One window-limited transformer (vocoder.py:338-354) over the f32 residual stream x [L.total][D]: residual stream f32,
+// GEMM operands bf16; the output of the final RMSNorm goes to out_bf and / or out_f32.  A streamed form carries the K / V
+// of the window - 1 rows before a chunk (carries L.ntail() + layer).
+static void run_transformer(ft_ctx* ctx, const Layout& L, const std::vector<TfLayer>& layers, const float* final_norm,
+                            float* x, int D, int H, int hd, int ffn, int window, const float* rope,
+                            bf16_t* xn, bf16_t* y, bf16_t* g, bf16_t* out_bf, float* out_f32, const char* pfx) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     hipStream_t st = s->stream;
-    const int D = c.latent_dim, H = c.tf_n_head, hd = c.tf_head_dim, HD = H * hd, R = c.n_codebooks + 1;
-    const long Tn = sc ? STREAM_NOMINAL_FRAMES : 0;           // msel = Tn x rows per frame of the stage (0: by the real row count)
-    const int W1 = c.tf_window - 1;
-    const int nh = sc ? std::min(sc->t0, W1) : 0;             // carried K/V rows in front of the chunk's
-    size_t ti = 0;                                            // next tail of sc->tails
-    // the carried rows of x's earlier chunks in front of x (rows [-H, 0)), and the carry for the next chunk
-    auto roll = [&](bf16_t* x, int rows, int Hh, int C) {
-        if (!sc || Hh == 0) return 0;
-        ft_codec_stream::Tail& tl = sc->tails[ti++];
-        tail_roll_kernel<<<gridfor((long)Hh * C / 8), 256, 0, st>>>(x, tl.buf[sc->par], tl.buf[sc->par ^ 1], rows, Hh, C);
+    const int HD = H * hd, W1 = window - 1, T = L.total;
+    bf16_t* q0 = L.qkv - (size_t)L.nh * 3 * HD;               // one stream: the carried K/V rows in front of the chunk's
+    for (const TfLayer& t : layers) {
+        const int l = (int)(&t - layers.data()), ci = L.ntail() + l;
+        rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, t.n1, c.tf_norm_eps, D, xn, nullptr});
+        if (s->trace) trace_rec(s, st, tname("%s%d.norm1", pfx, l), T, D, -1, 0, 0, 0, {{0, xn, 0}});
+        { GemmIO io = L.io(xn, D, 1, 0, L.qgap); io.out_bf = L.qkv; io.ldo = 3 * HD; gemm_t(s, st, t.qkv, io, "%s%d.qkv", l, 0, pfx); }
+        rope_qk_kernel<<<L.grid(gridfor((long)L.T * 2 * H * (hd / 2))), 256, 0, st>>>(L.qkv, rope, L.T, H, hd, L.t0, L.Z(1, L.qgap));
+        if (s->trace) trace_rec(s, st, tname("%s%d.rope", pfx, l), T, 3 * HD, -1, 0, 0, 0, {{0, L.qkv, 0}});
+        if (L.kv_in > 0)
+            kv_carry_in_kernel<<<L.grid(gridfor((long)L.kv_in * 2 * HD / 8)), 256, 0, st>>>(q0, L.carry_rd(ci), L.nh, W1, HD, L.Z(1, L.qgap, ci));
+        if (L.kv_out > 0)
+            kv_carry_out_kernel<<<L.grid(gridfor((long)L.kv_out * 2 * HD / 8)), 256, 0, st>>>(
+                q0, L.carry_wr(ci), L.nh + L.own, std::min(W1, L.nh + L.own), W1, HD, L.Z(1, L.qgap, ci));
+        window_attn_kernel<<<L.grid((L.T * H + 3) / 4), 256, 0, st>>>(
+            WinAttnP{q0, y, L.nh + L.own, H, hd, window, 1.0f / sqrtf((float)hd), L.nh, L.Z(1, L.qgap)});
+        if (s->trace) trace_rec(s, st, tname("%s%d.attn", pfx, l), T, HD, -1, 0, 0, 0, {{0, y, 0}});
+        { GemmIO io = L.io_rows(y, HD); io.gamma = t.g1; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm_t(s, st, t.wo, io, "%s%d.wo", l, 0, pfx); }
+        rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, t.n2, c.tf_norm_eps, D, xn, nullptr});
+        if (s->trace) trace_rec(s, st, tname("%s%d.norm2", pfx, l), T, D, -1, 0, 0, 0, {{0, xn, 0}});
+        { GemmIO io = L.io_rows(xn, D); io.act = ACT_SWIGLU; io.out_bf = g; io.ldo = ffn; gemm_t(s, st, t.w13, io, "%s%d.w13", l, 0, pfx); }
+        { GemmIO io = L.io_rows(g, ffn); io.gamma = t.g2; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm_t(s, st, t.w2, io, "%s%d.w2", l, 0, pfx); }
+    }
+    rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, final_norm, c.tf_norm_eps, D, out_bf, out_f32});
+    if (s->trace) trace_rec(s, st, tname("%snorm", pfx), T, D, -1, 0, 0, 0, {{0, out_bf, 0}, {2, out_f32, 1}});
+}
+
+// Enqueues the decode of L's rows, RVQ gather to final conv + tanh (the samples land in s->audio, the items back to back).
+// false: the carried tails the chain consumes are not the list the stream holds (ft_codec_stream_begin): the call fails.
+static bool decode_chain(ft_ctx* ctx, const Layout& L) {
+    const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    const int D = c.latent_dim, G = L.cgap;
+    int ti = 0;                                               // next carried tail of *L.tails
+    bool in_step = true;
+    // the carried rows of x's earlier chunks in front of x (rows [-H, 0)), and the carry for the next chunk; the stream's
+    // entry must be this stage's: a stage added here and not there would otherwise read another stage's rows
+    auto roll = [&](bf16_t* x, int m, int Hh, int C) {
+        if (!L.tails || Hh == 0) return 0;
+        if (ti >= L.ntail() || (*L.tails)[ti].H != Hh || (*L.tails)[ti].C != C) { in_step = false; return 0; }
+        tail_roll_kernel<<<L.grid(gridfor((long)Hh * C / 8)), 256, 0, st>>>(x, L.carry_rd(ti), L.carry_wr(ti), L.own * m, Hh, C, L.Z(m, G, ti));
+        ++ti;
         return -Hh;
     };
-    // codes of this item, compacted to [R][T]
-    std::vector<int> hc((size_t)R * T);
-    for (int r = 0; r < R; ++r) memcpy(&hc[(size_t)r * T], codes_host + (size_t)r * Tfull, T * sizeof(int));
-    FT_HIP(ctx, hipMemcpyAsync(s->codes, hc.data(), hc.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    RvqP rq{s->codes, s->tables, c.n_codebooks, c.semantic_codebook_size, c.codebook_size, D, T, s->x};
-    rvq_gather_kernel<<<dim3(T, 1), 256, 0, st>>>(rq);
-    if (s->trace) trace_rec(s, st, "rvq", T, D, -1, 0, 0, 0, {{2, s->x, 1}});
-    // post transformer (vocoder.py:338-354): residual stream f32, GEMM operands bf16
-    bf16_t* qkv_c = s->qkv + (size_t)nh * 3 * HD;             // this chunk's rows of the q k v work buffer
-    for (int l = 0; l < c.n_tf_layer; ++l) {
-        const TfLayer& t = s->tf[l];
-        rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{s->x, t.n1, c.tf_norm_eps, D, s->xn, nullptr});
-        if (s->trace) trace_rec(s, st, tname("post.%d.norm1", l), T, D, -1, 0, 0, 0, {{0, s->xn, 0}});
-        { GemmIO io{s->xn, D, T, T}; io.out_bf = qkv_c; io.ldo = 3 * HD; io.msel = Tn; gemm_t(s, st, t.qkv, io, "%s%d.qkv", l, 0, "post."); }
-        rope_qk_kernel<<<gridfor((long)T * 2 * H * (hd / 2)), 256, 0, st>>>(qkv_c, s->rope, T, H, hd, sc ? sc->t0 : 0);
-        if (s->trace) trace_rec(s, st, tname("post.%d.rope", l), T, 3 * HD, -1, 0, 0, 0, {{0, qkv_c, 0}});
-        if (sc) {
-            if (nh > 0) kv_carry_in_kernel<<<gridfor((long)nh * 2 * HD / 8), 256, 0, st>>>(s->qkv, sc->kv[sc->par][l], nh, W1, HD);
-            const int nh2 = std::min(W1, nh + T);
-            if (nh2 > 0) kv_carry_out_kernel<<<gridfor((long)nh2 * 2 * HD / 8), 256, 0, st>>>(s->qkv, sc->kv[sc->par ^ 1][l], nh + T, nh2, W1, HD);
-        }
-        window_attn_kernel<<<(T * H + 3) / 4, 256, 0, st>>>(WinAttnP{s->qkv, s->y, nh + T, H, hd, c.tf_window, 1.0f / sqrtf((float)hd), nh});
-        if (s->trace) trace_rec(s, st, tname("post.%d.attn", l), T, HD, -1, 0, 0, 0, {{0, s->y, 0}});
-        { GemmIO io{s->y, HD, T, T}; io.gamma = t.g1; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm_t(s, st, t.wo, io, "%s%d.wo", l, 0, "post."); }
-        rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{s->x, t.n2, c.tf_norm_eps, D, s->xn, nullptr});
-        if (s->trace) trace_rec(s, st, tname("post.%d.norm2", l), T, D, -1, 0, 0, 0, {{0, s->xn, 0}});
-        { GemmIO io{s->xn, D, T, T}; io.act = ACT_SWIGLU; io.out_bf = s->g; io.ldo = c.tf_ffn; io.msel = Tn; gemm_t(s, st, t.w13, io, "%s%d.w13", l, 0, "post."); }
-        { GemmIO io{s->g, c.tf_ffn, T, T}; io.gamma = t.g2; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm_t(s, st, t.w2, io, "%s%d.w2", l, 0, "post."); }
-    }
-    bf16_t *z = s->big[0], *u = s->big[1], *n = s->big[2], *h = s->big[3];
-    rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{s->x, s->tf_norm, c.tf_norm_eps, D, z, nullptr});
-    if (s->trace) trace_rec(s, st, "post.norm", T, D, -1, 0, 0, 0, {{0, z, 0}});
-    int Tc = T;
-    long Tnc = Tn;                                            // nominal rows at the current rate
+    RvqP rq{L.codes, s->tables, c.n_codebooks, c.semantic_codebook_size, c.codebook_size, D, L.total, s->x};
+    rvq_gather_kernel<<<dim3(L.total, 1), 256, 0, st>>>(rq);
+    if (s->trace) trace_rec(s, st, "rvq", L.total, D, -1, 0, 0, 0, {{2, s->x, 1}});
+    bf16_t *z = L.big[0], *u = L.big[1], *n = L.big[2], *h = L.big[3];
+    run_transformer(ctx, L, s->tf, s->tf_norm, s->x, D, c.tf_n_head, c.tf_head_dim, c.tf_ffn, c.tf_window, s->rope,
+                    s->xn, s->y, s->g, z, nullptr, "post.");
+    int m = 1, xg = 0;                                        // rows per frame; gap rows of the input (compact after the transformer)
     for (const UpStage& us : s->up) {  // vocoder.py:737-748: convT k=s=2, then ConvNeXt
         const int uj = (int)(&us - s->up.data());
-        { GemmIO io{z, D, Tc, Tc}; io.out_bf = u; io.ldo = us.ct.N; io.msel = Tnc; gemm_t(s, st, us.ct, io, "%sup.%d.ct", uj); }
-        Tc *= us.f;
-        Tnc *= us.f;
-        const int tm = roll(u, Tc, 6, D);                     // depthwise causal k = 7
-        dwconv_ln_kernel<<<Tc, 256, D * sizeof(float), st>>>(DwLnP{u, us.dw_w, us.dw_b, us.ln_w, us.ln_b, Tc, D, n, tm});
-        if (s->trace) trace_rec(s, st, tname("up.%d.dwln", uj), Tc, D, -1, 6, 7, 0, {{0, n, 0}});
-        { GemmIO io{n, D, Tc, Tc}; io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; io.msel = Tnc; gemm_t(s, st, us.pw1, io, "%sup.%d.pw1", uj); }
-        { GemmIO io{h, 4 * D, Tc, Tc}; io.gamma = us.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D; io.msel = Tnc; gemm_t(s, st, us.pw2, io, "%sup.%d.pw2", uj); }
+        { GemmIO io = L.io(z, D, m, xg, G / us.f); io.out_bf = u; io.ldo = us.ct.N; gemm_t(s, st, us.ct, io, "%sup.%d.ct", uj); }
+        m *= us.f;
+        xg = G;
+        const int tm = roll(u, m, 6, D);                      // depthwise causal k = 7
+        dwconv_ln_kernel<<<L.grid(L.T * m), 256, D * sizeof(float), st>>>(DwLnP{u, us.dw_w, us.dw_b, us.ln_w, us.ln_b, L.T * m, D, n, tm, L.Z(m, G)});
+        if (s->trace) trace_rec(s, st, tname("up.%d.dwln", uj), L.T * m, D, -1, 6, 7, 0, {{0, n, 0}});
+        { GemmIO io = L.io(n, D, m, G, G); io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; gemm_t(s, st, us.pw1, io, "%sup.%d.pw1", uj); }
+        { GemmIO io = L.io(h, 4 * D, m, G, G); io.gamma = us.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D; gemm_t(s, st, us.pw2, io, "%sup.%d.pw2", uj); }
     }
     // decoder (vocoder.py:605-640).  Buffers: a = snake'd input of the next conv, r = raw residual
     bf16_t *a = u, *r = n, *hs = h, *a2 = z;
-    { GemmIO io{z, D, Tc, Tc}; io.out_act = a; io.alpha = s->blocks[0].a0; io.ldo = c.decoder_dim; io.msel = Tnc;
-      io.t_min = roll(z, Tc, halo_of(s->conv_in), D); gemm_t(s, st, s->conv_in, io, "%sdec.in"); }
+    { GemmIO io = L.io(z, D, m, xg, G); io.out_act = a; io.alpha = s->blocks[0].a0; io.ldo = c.decoder_dim;
+      io.t_min = roll(z, m, halo_of(s->conv_in), D); gemm_t(s, st, s->conv_in, io, "%sdec.in"); }
     // note: conv_in reads z and writes a (= big[1]); z (= big[0]) is free afterwards
     for (size_t bi = 0; bi < s->blocks.size(); ++bi) {
         const DecBlock& b = s->blocks[bi];
         // transposed conv: raw -> r, snake'd by unit 0 -> a2
-        { GemmIO io{a, b.cin, Tc, Tc}; io.out_bf = r; io.out_act = a2; io.alpha = b.u[0].a0; io.ldo = b.ct.N; io.msel = Tnc;
-          io.t_min = roll(a, Tc, halo_of(b.ct), b.cin); gemm_t(s, st, b.ct, io, "%sdec.%d.ct", (int)bi); }
-        Tc *= b.s;
-        Tnc *= b.s;
+        { GemmIO io = L.io(a, b.cin, m, G, G / b.s); io.out_bf = r; io.out_act = a2; io.alpha = b.u[0].a0; io.ldo = b.ct.N;
+          io.t_min = roll(a, m, halo_of(b.ct), b.cin); gemm_t(s, st, b.ct, io, "%sdec.%d.ct", (int)bi); }
+        m *= b.s;
         for (int ui = 0; ui < 3; ++ui) {
             const ResUnitW& ru = b.u[ui];
-            { GemmIO io{a2, b.cout, Tc, Tc}; io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cout; io.msel = Tnc;
-              io.t_min = roll(a2, Tc, halo_of(ru.c7), b.cout); gemm_t(s, st, ru.c7, io, "%sdec.%d.u%d.c7", (int)bi, ui); }
+            { GemmIO io = L.io(a2, b.cout, m, G, G); io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cout;
+              io.t_min = roll(a2, m, halo_of(ru.c7), b.cout); gemm_t(s, st, ru.c7, io, "%sdec.%d.u%d.c7", (int)bi, ui); }
             const float* next_alpha = ui < 2 ? b.u[ui + 1].a0 : (bi + 1 < s->blocks.size() ? s->blocks[bi + 1].a0 : s->a_last);
             bf16_t* act_dst = ui < 2 ? a2 : a;  // the last unit feeds the next block's transposed conv / the output conv
-            { GemmIO io{hs, b.cout, Tc, Tc}; io.resid_bf = r; io.ldr = b.cout; io.out_bf = ui < 2 ? r : nullptr;
-              io.out_act = act_dst; io.alpha = next_alpha; io.ldo = b.cout; io.msel = Tnc; gemm_t(s, st, ru.c1, io, "%sdec.%d.u%d.c1", (int)bi, ui); }
+            { GemmIO io = L.io(hs, b.cout, m, G, G); io.resid_bf = r; io.ldr = b.cout; io.out_bf = ui < 2 ? r : nullptr;
+              io.out_act = act_dst; io.alpha = next_alpha; io.ldo = b.cout; gemm_t(s, st, ru.c1, io, "%sdec.%d.u%d.c1", (int)bi, ui); }
         }
     }
-    FinalConvP fp{a, s->w_last, s->b_last, Tc, s->c_last, s->audio, roll(a, Tc, 6, s->c_last)};
-    final_conv_tanh_kernel<<<2048, 256, 0, st>>>(fp);
-    if (s->trace) trace_rec(s, st, "final", Tc, 1, -1, 6, 7, s->c_last, {{2, s->audio, 1}});
-    if (rs) {
-        (*rs)[0].x = s->audio;
-        FT_TRY(rs_enqueue(ctx, *rs, audio_host));
-    } else {
-        FT_HIP(ctx, hipMemcpyAsync(audio_host, s->audio, (size_t)Tc * sizeof(float), hipMemcpyDeviceToHost, st));
-    }
-    FT_HIP(ctx, hipStreamSynchronize(st));
+    // m = frame_len here: item z's samples land at P_z * frame_len, back to back as the caller wants them
+    FinalConvP fp{a, s->w_last, s->b_last, L.T * m, s->c_last, s->audio, roll(a, m, 6, s->c_last), L.Z(m, G)};
+    final_conv_tanh_kernel<<<L.grid(std::max(16, 2048 / L.n)), 256, 0, st>>>(fp);
+    if (s->trace) trace_rec(s, st, "final", L.T * m, 1, -1, 6, 7, s->c_last, {{2, s->audio, 1}});
+    return in_step && ti == L.ntail();
+}
+
+// The end of a call that leaves samples: the resampler over `rs` (its segments' inputs written earlier on the stream) or the
+// plain copy of `plain` floats of s->audio, the call's one synchronize and the launch check; then every stream named moves
+// on by its chunk.
+static ft_status call_tail(ft_ctx* ctx, std::vector<RsSeg>* rs, float* host, size_t plain, const char* what, int n = 0,
+                           ft_codec_stream* const* scs = nullptr, const int32_t* lens = nullptr) {
+    CodecState* s = ctx->codec;
+    if (rs) FT_TRY(rs_enqueue(ctx, *rs, host));
+    else FT_HIP(ctx, hipMemcpyAsync(host, s->audio, plain * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    FT_HIP(ctx, hipStreamSynchronize(s->stream));
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("codec launch: ") + hipGetErrorString(e));
-    if (sc) {
-        if (ti != sc->tails.size()) return ft_fail(ctx, FT_ERR_STATE, "codec stream: carry bookkeeping out of step");
-        sc->t0 += T;
-        sc->par ^= 1;
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string(what) + hipGetErrorString(e));
+    for (int j = 0; j < n; ++j) {
+        scs[j]->t0 += lens[j];
+        scs[j]->par ^= 1;
     }
     return FT_OK;
+}
+
+// The chain over L and the end of the call; `who` names the caller in the message of a carry list out of step.
+static ft_status decode_run(ft_ctx* ctx, const Layout& L, std::vector<RsSeg>* rs, float* audio_host, int n,
+                            ft_codec_stream* const* scs, const int32_t* lens, const char* who) {
+    const bool in_step = decode_chain(ctx, L);
+    FT_TRY(call_tail(ctx, rs, audio_host, (size_t)L.total * ctx->codec->frame_len, "codec launch: ", in_step ? n : 0, scs, lens));
+    if (!in_step) return ft_fail(ctx, FT_ERR_STATE, std::string(who) + ": carry bookkeeping out of step");
+    return FT_OK;
+}
+
+// The carries of one stream as the chain numbers them: [read, write] per convolution tail, then per transformer layer.
+static void stream_carries(const ft_codec_stream* sc, bf16_t** out) {
+    for (const ft_codec_stream::Tail& t : sc->tails) { *out++ = t.buf[sc->par]; *out++ = t.buf[sc->par ^ 1]; }
+    for (size_t l = 0; l < sc->kv[0].size(); ++l) { *out++ = sc->kv[sc->par][l]; *out++ = sc->kv[sc->par ^ 1][l]; }
+}
+
+// One item: T of the Tfull frames per codebook row of codes_host, decoded from zero state, or (sc) as the next chunk of a
+// stream.  `rs`: resample the waveform (segment 0 reads s->audio) and copy the resampled samples instead.
+static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, int T, float* audio_host, ft_codec_stream* sc = nullptr,
+                            std::vector<RsSeg>* rs = nullptr) {
+    const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
+    const int HD = c.tf_n_head * c.tf_head_dim, R = c.n_codebooks + 1, W1 = c.tf_window - 1;
+    Layout L = Layout::plain(T, s->qkv);
+    L.codes = s->codes;
+    std::copy(s->big, s->big + 4, L.big);
+    std::vector<bf16_t*> car;
+    if (sc) {
+        L.nominal = STREAM_NOMINAL_FRAMES;
+        L.tails = &sc->tails;
+        L.ncarry = L.ntail() + c.n_tf_layer;
+        car.resize((size_t)L.ncarry * 2);
+        stream_carries(sc, car.data());
+        L.hcarry = car.data();
+        L.t0 = sc->t0;
+        L.nh = L.kv_in = std::min(sc->t0, W1);
+        L.kv_out = std::min(W1, L.nh + T);
+        L.qkv += (size_t)L.nh * 3 * HD;                       // the carried K/V rows go in front
+    }
+    // codes of this item, compacted to [R][T]
+    std::vector<int> hc((size_t)R * T);
+    for (int r = 0; r < R; ++r) memcpy(&hc[(size_t)r * T], codes_host + (size_t)r * Tfull, T * sizeof(int));
+    FT_HIP(ctx, hipMemcpyAsync(s->codes, hc.data(), hc.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    return decode_run(ctx, L, rs, audio_host, sc ? 1 : 0, &sc, &T, "codec stream");
 }
 
 // Streamed decode (second half): successive chunks of one utterance's codes, each decoded with
@@ -946,8 +1026,7 @@ static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, i
 // 591-595: audible restarts at chunk borders); carrying the state is exact because the codec is causal.
 extern "C" ft_status ft_codec_stream_begin(ft_ctx* ctx, ft_codec_stream** out) {
     if (!ctx || !out) return FT_ERR_ARG;
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     FT_HIP(ctx, hipSetDevice(ctx->device));
@@ -973,7 +1052,7 @@ extern "C" ft_status ft_codec_stream_begin(ft_ctx* ctx, ft_codec_stream** out) {
         ok = zalloc(&t.buf[0], (size_t)Hh * C) && zalloc(&t.buf[1], (size_t)Hh * C);
         sc->tails.push_back(t);
     };
-    // the order decode_one consumes them in
+    // the order decode_chain consumes them in (its roll() checks every entry against the stage that asks for it)
     for (size_t j = 0; j < s->up.size(); ++j) tail(6, c.latent_dim);
     tail(halo_of(s->conv_in), c.latent_dim);
     for (const DecBlock& b : s->blocks) {
@@ -1000,7 +1079,7 @@ extern "C" ft_status ft_codec_stream_begin(ft_ctx* ctx, ft_codec_stream** out) {
 
 extern "C" ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* sc, const int32_t* codes, int32_t T, float* audio) {
     if (!ctx || !sc) return FT_ERR_ARG;
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    FT_TRY(codec_ready(ctx, false));
     if (!codes || !audio || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode: bad argument");
     if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: the stream belongs to another (or a destroyed) context");
     if (sc->rate) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
@@ -1072,11 +1151,8 @@ static ft_status decode_many(ft_ctx* ctx, int n, ft_codec_stream* const* scs, co
                              float* audio_host, std::vector<RsSeg>* rs = nullptr) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
-    hipStream_t st = s->stream;
-    const int D = c.latent_dim, H = c.tf_n_head, hd = c.tf_head_dim, HD = H * hd, R = c.n_codebooks + 1;
-    const long Tn = STREAM_NOMINAL_FRAMES;
-    const int W1 = c.tf_window - 1;
-    const int ntail = (int)scs[0]->tails.size(), ncarry = ntail + c.n_tf_layer;
+    const int HD = c.tf_n_head * c.tf_head_dim, R = c.n_codebooks + 1, W1 = c.tf_window - 1;
+    const int ncarry = (int)scs[0]->tails.size() + c.n_tf_layer;
     FT_TRY(many_alloc(ctx, ncarry));
     if (s->mcarry != ncarry) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: carry count out of step");
     // host side of the device table: chunks {P, L, t0, nh}, carries [n][ncarry][read, write], codes [R][sum L]
@@ -1095,161 +1171,101 @@ static ft_status decode_many(ft_ctx* ctx, int n, ft_codec_stream* const* scs, co
     for (int j = 0; j < n; ++j) {
         const ft_codec_stream* sc = scs[j];
         seg[j] = make_int4(P[j], lens[j], sc->t0, std::min(sc->t0, W1));
-        bf16_t** cj = car + (size_t)j * ncarry * 2;
-        for (int i = 0; i < ntail; ++i) { cj[2 * i] = sc->tails[i].buf[sc->par]; cj[2 * i + 1] = sc->tails[i].buf[sc->par ^ 1]; }
-        for (int l = 0; l < c.n_tf_layer; ++l) {
-            cj[2 * (ntail + l)] = sc->kv[sc->par][l];
-            cj[2 * (ntail + l) + 1] = sc->kv[sc->par ^ 1][l];
-        }
+        stream_carries(sc, car + (size_t)j * ncarry * 2);
         const int32_t* src = codes_host + (size_t)R * P[j];
         for (int r = 0; r < R; ++r) memcpy(hc + (size_t)r * Ts + P[j], src + (size_t)r * lens[j], lens[j] * sizeof(int));
     }
-    FT_HIP(ctx, hipMemcpyAsync(s->mtab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
-    const int4* segd = reinterpret_cast<const int4*>(s->mtab);
-    bf16_t* const* card = reinterpret_cast<bf16_t* const*>(s->mtab + seg_b);
-    const int* codes_d = reinterpret_cast<const int*>(s->mtab + seg_b + car_b);
-    auto Z = [&](int m, int g, int ci = 0) {
-        SegZ z;
-        z.seg = segd; z.carry = card; z.ncarry = ncarry; z.ci = ci; z.m = m; z.g = g;
-        return z;
-    };
-    // a GEMM over the chunks: m rows per frame, xg / og gap rows in front of every chunk of X / of the output
-    auto seg_io = [&](GemmIO& io, int m, int xg, int og) {
-        io.T_in = io.M = Lmax * m;
-        io.seg = segd; io.nz = n; io.seg_m = m; io.seg_xg = xg; io.seg_og = og;
-    };
-    int ti = 0;                                               // next carried convolution tail (the order of decode_one)
-    auto roll = [&](bf16_t* x, int m, int Hh, int C) {
-        if (Hh == 0) return 0;
-        tail_roll_kernel<<<dim3(gridfor((long)Hh * C / 8), 1, n), 256, 0, st>>>(x, nullptr, nullptr, 0, Hh, C, Z(m, MANY_GAP, ti++));
-        return -Hh;
-    };
-    RvqP rq{codes_d, s->tables, c.n_codebooks, c.semantic_codebook_size, c.codebook_size, D, Ts, s->x};
-    rvq_gather_kernel<<<dim3(Ts, 1), 256, 0, st>>>(rq);
-    // post transformer on compact rows; chunk z's q k v rows start at P_z + z * W1 of qkv_c (its carried K/V in front)
-    bf16_t* qkv_c = s->mqkv + (size_t)W1 * 3 * HD;
-    for (int l = 0; l < c.n_tf_layer; ++l) {
-        const TfLayer& t = s->tf[l];
-        rmsnorm_rows_kernel<<<Ts, 256, 0, st>>>(RowNormP{s->x, t.n1, c.tf_norm_eps, D, s->xn, nullptr});
-        { GemmIO io{s->xn, D, 0, 0}; io.out_bf = qkv_c; io.ldo = 3 * HD; io.msel = Tn; seg_io(io, 1, 0, W1); gemm(st, t.qkv, io); }
-        rope_qk_kernel<<<dim3(gridfor((long)Lmax * 2 * H * (hd / 2)), 1, n), 256, 0, st>>>(qkv_c, s->rope, Lmax, H, hd, 0, Z(1, W1));
-        if (W1 > 0) {
-            kv_carry_in_kernel<<<dim3(gridfor((long)W1 * 2 * HD / 8), 1, n), 256, 0, st>>>(qkv_c, nullptr, 0, W1, HD, Z(1, W1, ntail + l));
-            kv_carry_out_kernel<<<dim3(gridfor((long)W1 * 2 * HD / 8), 1, n), 256, 0, st>>>(qkv_c, nullptr, 0, 0, W1, HD, Z(1, W1, ntail + l));
-        }
-        window_attn_kernel<<<dim3((Lmax * H + 3) / 4, 1, n), 256, 0, st>>>(
-            WinAttnP{qkv_c, s->y, 0, H, hd, c.tf_window, 1.0f / sqrtf((float)hd), 0, Z(1, W1)});
-        { GemmIO io{s->y, HD, Ts, Ts}; io.gamma = t.g1; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm(st, t.wo, io); }
-        rmsnorm_rows_kernel<<<Ts, 256, 0, st>>>(RowNormP{s->x, t.n2, c.tf_norm_eps, D, s->xn, nullptr});
-        { GemmIO io{s->xn, D, Ts, Ts}; io.act = ACT_SWIGLU; io.out_bf = s->g; io.ldo = c.tf_ffn; io.msel = Tn; gemm(st, t.w13, io); }
-        { GemmIO io{s->g, c.tf_ffn, Ts, Ts}; io.gamma = t.g2; io.resid_f32 = s->x; io.ldr = D; io.out_f32 = s->x; io.ldo = D; io.msel = Tn; gemm(st, t.w2, io); }
-    }
-    bf16_t *z = s->mbig[0], *u = s->mbig[1], *nb = s->mbig[2], *h = s->mbig[3];
-    rmsnorm_rows_kernel<<<Ts, 256, 0, st>>>(RowNormP{s->x, s->tf_norm, c.tf_norm_eps, D, z, nullptr});
-    int m = 1, xg = 0;                                        // rows per frame; gap rows of the input (compact after the transformer)
-    long Tnc = Tn;
-    for (const UpStage& us : s->up) {
-        { GemmIO io{z, D, 0, 0}; io.out_bf = u; io.ldo = us.ct.N; io.msel = Tnc; seg_io(io, m, xg, MANY_GAP / us.f); gemm(st, us.ct, io); }
-        m *= us.f;
-        Tnc *= us.f;
-        xg = MANY_GAP;
-        DwLnP dp{u, us.dw_w, us.dw_b, us.ln_w, us.ln_b, Lmax * m, D, nb, roll(u, m, 6, D)};
-        dp.z = Z(m, MANY_GAP);
-        dwconv_ln_kernel<<<dim3(Lmax * m, 1, n), 256, D * sizeof(float), st>>>(dp);
-        { GemmIO io{nb, D, 0, 0}; io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; io.msel = Tnc; seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, us.pw1, io); }
-        { GemmIO io{h, 4 * D, 0, 0}; io.gamma = us.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D; io.msel = Tnc;
-          seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, us.pw2, io); }
-    }
-    bf16_t *a = u, *r = nb, *hs = h, *a2 = z;
-    { GemmIO io{z, D, 0, 0}; io.out_act = a; io.alpha = s->blocks[0].a0; io.ldo = c.decoder_dim; io.msel = Tnc;
-      io.t_min = roll(z, m, halo_of(s->conv_in), D); seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, s->conv_in, io); }
-    for (size_t bi = 0; bi < s->blocks.size(); ++bi) {
-        const DecBlock& b = s->blocks[bi];
-        { GemmIO io{a, b.cin, 0, 0}; io.out_bf = r; io.out_act = a2; io.alpha = b.u[0].a0; io.ldo = b.ct.N; io.msel = Tnc;
-          io.t_min = roll(a, m, halo_of(b.ct), b.cin); seg_io(io, m, MANY_GAP, MANY_GAP / b.s); gemm(st, b.ct, io); }
-        m *= b.s;
-        Tnc *= b.s;
-        for (int ui = 0; ui < 3; ++ui) {
-            const ResUnitW& ru = b.u[ui];
-            { GemmIO io{a2, b.cout, 0, 0}; io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cout; io.msel = Tnc;
-              io.t_min = roll(a2, m, halo_of(ru.c7), b.cout); seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, ru.c7, io); }
-            const float* next_alpha = ui < 2 ? b.u[ui + 1].a0 : (bi + 1 < s->blocks.size() ? s->blocks[bi + 1].a0 : s->a_last);
-            bf16_t* act_dst = ui < 2 ? a2 : a;
-            { GemmIO io{hs, b.cout, 0, 0}; io.resid_bf = r; io.ldr = b.cout; io.out_bf = ui < 2 ? r : nullptr;
-              io.out_act = act_dst; io.alpha = next_alpha; io.ldo = b.cout; io.msel = Tnc; seg_io(io, m, MANY_GAP, MANY_GAP); gemm(st, ru.c1, io); }
-        }
-    }
-    // m = frame_len here: chunk z's samples land at P_z * frame_len, the chunks back to back as the caller wants them
-    FinalConvP fp{a, s->w_last, s->b_last, Lmax * m, s->c_last, s->audio, roll(a, m, 6, s->c_last)};
-    fp.z = Z(m, MANY_GAP);
-    final_conv_tanh_kernel<<<dim3(std::max(16, 2048 / n), 1, n), 256, 0, st>>>(fp);
-    if (rs) FT_TRY(rs_enqueue(ctx, *rs, audio_host));
-    else FT_HIP(ctx, hipMemcpyAsync(audio_host, s->audio, (size_t)Ts * s->frame_len * sizeof(float), hipMemcpyDeviceToHost, st));
-    FT_HIP(ctx, hipStreamSynchronize(st));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("codec launch: ") + hipGetErrorString(e));
-    if (ti != ntail) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: carry bookkeeping out of step");
+    FT_HIP(ctx, hipMemcpyAsync(s->mtab, tab.data(), tab.size(), hipMemcpyHostToDevice, s->stream));
+    Layout L;
+    L.n = n; L.T = Lmax; L.total = Ts; L.cgap = MANY_GAP; L.qgap = W1; L.nominal = STREAM_NOMINAL_FRAMES;
+    L.seg = reinterpret_cast<const int4*>(s->mtab);
+    L.dcarry = reinterpret_cast<bf16_t* const*>(s->mtab + seg_b);
+    L.ncarry = ncarry;
+    L.codes = reinterpret_cast<const int*>(s->mtab + seg_b + car_b);
+    std::copy(s->mbig, s->mbig + 4, L.big);
+    // chunk z's q k v rows start at row P_z + z * W1 of L.qkv (its carried K/V in front)
+    L.qkv = s->mqkv + (size_t)W1 * 3 * HD;
+    L.tails = &scs[0]->tails;                                 // all streams of a context hold the same list
+    L.kv_in = L.kv_out = std::max(W1, 0);
+    return decode_run(ctx, L, rs, audio_host, n, scs, lens, "ft_codec_stream_decode_many");
+}
+
+// What ft_codec_stream_decode_many and .._many_at refuse, in one order: `fn` names the function in the message; `at`
+// (the second) takes streams of any rate that are not finished and, with `final`, a chunk of no frames.
+static ft_status many_check(ft_ctx* ctx, const std::string& fn, int n, ft_codec_stream* const* streams, const int32_t* lens,
+                            const int32_t* final, bool at) {
+    const ft_codec_config& c = ctx->cc;
+    CodecState* s = ctx->codec;
+    if (n > MANY_MAX_STREAMS) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": more than 64 streams in one call");
+    if (s->up.empty()) return ft_fail(ctx, FT_ERR_UNSUPPORTED, fn + ": needs an up-sampling stage");
+    for (const DecBlock& b : s->blocks)
+        if (MANY_GAP % b.s) return ft_fail(ctx, FT_ERR_UNSUPPORTED, fn + ": decoder rates must divide 64");
+    long total = 0;
     for (int j = 0; j < n; ++j) {
-        scs[j]->t0 += lens[j];
-        scs[j]->par ^= 1;
+        const ft_codec_stream* sc = streams[j];
+        if (!sc) return ft_fail(ctx, FT_ERR_ARG, fn + ": null stream");
+        if (lens[j] < 0 || (lens[j] == 0 && !(at && final && final[j])))
+            return ft_fail(ctx, FT_ERR_ARG, fn + ": a chunk of less than one frame" + (at ? " (zero only with final)" : ""));
+        if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream belongs to another (or a destroyed) context");
+        if (!at && sc->rate) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
+        if (at && sc->finished) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream whose final chunk went out");
+        for (int i = 0; i < j; ++i)
+            if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, fn + ": a stream named twice");
+        if (lens[j] > c.max_frames || sc->t0 + lens[j] > c.max_frames)
+            return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": stream longer than max_frames (rope table)");
+        total += lens[j];
     }
+    if (total > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": chunks longer than max_frames together");
     return FT_OK;
 }
 
 extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
                                                  const int32_t* lens, float* audio) {
     if (!ctx) return FT_ERR_ARG;
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     if (n < 1 || !streams || !codes || !lens || !audio) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: bad argument");
-    if (n > MANY_MAX_STREAMS) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many: more than 64 streams in one call");
-    const ft_codec_config& c = ctx->cc;
-    CodecState* s = ctx->codec;
-    if (s->up.empty()) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many: needs an up-sampling stage");
-    for (const DecBlock& b : s->blocks)
-        if (MANY_GAP % b.s) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many: decoder rates must divide 64");
-    long total = 0;
-    for (int j = 0; j < n; ++j) {
-        const ft_codec_stream* sc = streams[j];
-        if (!sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: null stream");
-        if (lens[j] < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: a chunk of less than one frame");
-        if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: a stream belongs to another (or a destroyed) context");
-        if (sc->rate) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
-        for (int i = 0; i < j; ++i)
-            if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many: a stream named twice");
-        if (lens[j] > c.max_frames || sc->t0 + lens[j] > c.max_frames)
-            return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many: stream longer than max_frames (rope table)");
-        total += lens[j];
-    }
-    if (total > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many: chunks longer than max_frames together");
-    std::lock_guard<std::mutex> lock(s->mu);
+    FT_TRY(many_check(ctx, "ft_codec_stream_decode_many", n, streams, lens, nullptr, false));
+    std::lock_guard<std::mutex> lock(ctx->codec->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
     return decode_many(ctx, n, streams, codes, lens, audio);
+}
+
+// The items of ft_codec_decode / ft_codec_decode_at, one after the other: item b's samples go to audio + b * stride, zeros
+// behind them.  `t`: the resampler's table (null, or K = 0: the codec's own rate).
+static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int B, int T, const int32_t* lens, float* audio,
+                              size_t stride, const CodecState::RsTab* t, int64_t* out_lens) {
+    CodecState* s = ctx->codec;
+    const int R = ctx->cc.n_codebooks + 1;
+    for (int b = 0; b < B; ++b) {
+        const int Tb = lens ? lens[b] : T;
+        if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
+        const size_t n_in = (size_t)Tb * s->frame_len, n_out = t ? (n_in * t->L + t->M - 1) / t->M : n_in;   // ft_resampled_len
+        float* out = audio + (size_t)b * stride;
+        if (out_lens) out_lens[b] = (int64_t)n_out;
+        if (n_out < stride) memset(out + n_out, 0, (stride - n_out) * sizeof(float));
+        if (Tb == 0) continue;
+        if (!t || t->K == 0) {
+            FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
+            continue;
+        }
+        // a fresh input to the resampler: zeros before it, zeros after it (the whole tail)
+        std::vector<RsSeg> g(1, RsSeg{s->audio, t->w, nullptr, nullptr, nullptr, 0, 0, (int)n_in, (int)n_out, t->L, t->M, t->K, 0});
+        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, &g));
+    }
+    return FT_OK;
 }
 
 extern "C" ft_status ft_codec_decode(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
                                      float* audio) {
     if (!ctx) return FT_ERR_ARG;
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     if (!codes || !audio || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode: bad argument");
-    const ft_codec_config& c = ctx->cc;
-    if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_decode: T exceeds max_frames");
+    if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_decode: T exceeds max_frames");
     CodecState* s = ctx->codec;
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    const int R = c.n_codebooks + 1;
-    const size_t alen = (size_t)T * s->frame_len;
     TraceScope traced(s, B == 1);
-    for (int b = 0; b < B; ++b) {
-        int Tb = lens ? lens[b] : T;
-        if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode: bad length");
-        float* out = audio + (size_t)b * alen;
-        if ((size_t)Tb * s->frame_len < alen) memset(out + (size_t)Tb * s->frame_len, 0, (alen - (size_t)Tb * s->frame_len) * sizeof(float));
-        if (Tb == 0) continue;
-        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
-    }
-    return FT_OK;
+    return decode_items(ctx, "ft_codec_decode", codes, B, T, lens, audio, (size_t)T * s->frame_len, nullptr, nullptr);
 }
 
 // ---- resampled output (fishtts_hip.h: ft_resample_filter .. ft_codec_stream_decode_many_at, ft_test_resample)
@@ -1280,48 +1296,28 @@ extern "C" ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32
                                         int32_t sample_rate, float* audio, int64_t* out_lens) {
     if (!ctx) return FT_ERR_ARG;
     FT_TRY(rs_refuse(ctx, "ft_codec_decode_at", sample_rate));
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     if (!codes || !audio || !out_lens || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode_at: bad argument");
-    const ft_codec_config& c = ctx->cc;
-    if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_decode_at: T exceeds max_frames");
+    if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_decode_at: T exceeds max_frames");
     CodecState* s = ctx->codec;
-    const int R = c.n_codebooks + 1;
-    std::vector<int64_t> ol(B);
-    int64_t stride = 0;
+    int64_t stride = 0;   // the longest item's resampled length (a bad length is refused before the table is built)
     for (int b = 0; b < B; ++b) {
         const int Tb = lens ? lens[b] : T;
         if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode_at: bad length");
-        ol[b] = ft_resampled_len(sample_rate, (int64_t)Tb * s->frame_len);
-        stride = std::max(stride, ol[b]);
+        stride = std::max(stride, ft_resampled_len(sample_rate, (int64_t)Tb * s->frame_len));
     }
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
     const CodecState::RsTab* t = nullptr;
     FT_TRY(rs_table(ctx, sample_rate, &t));
     if (t->K > 0) FT_TRY(rs_alloc(ctx));
-    for (int b = 0; b < B; ++b) {
-        const int Tb = lens ? lens[b] : T;
-        float* out = audio + (size_t)b * stride;
-        out_lens[b] = ol[b];
-        if (ol[b] < stride) memset(out + ol[b], 0, (size_t)(stride - ol[b]) * sizeof(float));
-        if (Tb == 0) continue;
-        if (t->K == 0) {
-            FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
-            continue;
-        }
-        // a fresh input: zeros before it, zeros after it (the whole tail)
-        std::vector<RsSeg> g(1, RsSeg{nullptr, t->w, nullptr, nullptr, nullptr, 0, 0, Tb * s->frame_len, (int)ol[b], t->L, t->M, t->K, 0});
-        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, &g));
-    }
-    return FT_OK;
+    return decode_items(ctx, "ft_codec_decode_at", codes, B, T, lens, audio, (size_t)stride, t, out_lens);
 }
 
 extern "C" ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, ft_codec_stream** out) {
     if (!ctx || !out) return FT_ERR_ARG;
     FT_TRY(rs_refuse(ctx, "ft_codec_stream_begin_at", sample_rate));
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     CodecState* s = ctx->codec;
     const CodecState::RsTab* t = nullptr;
     {
@@ -1360,40 +1356,22 @@ extern "C" ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, 
 extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
                                                     const int32_t* lens, const int32_t* final, float* audio, int64_t* out_lens) {
     if (!ctx) return FT_ERR_ARG;
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     if (n < 1 || !streams || !codes || !lens || !audio || !out_lens)
         return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: bad argument");
-    if (n > MANY_MAX_STREAMS) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: more than 64 streams in one call");
-    const ft_codec_config& c = ctx->cc;
+    FT_TRY(many_check(ctx, "ft_codec_stream_decode_many_at", n, streams, lens, final, true));
     CodecState* s = ctx->codec;
-    if (s->up.empty()) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many_at: needs an up-sampling stage");
-    for (const DecBlock& b : s->blocks)
-        if (MANY_GAP % b.s) return ft_fail(ctx, FT_ERR_UNSUPPORTED, "ft_codec_stream_decode_many_at: decoder rates must divide 64");
     const int fl = s->frame_len;
-    long total = 0;
     long long total_out = 0;
     bool any_rate = false;
-    std::vector<long long> no(n);
+    std::vector<long long> no(n);   // samples each stream gives out in this call
     for (int j = 0; j < n; ++j) {
         const ft_codec_stream* sc = streams[j];
-        const bool fin = final && final[j];
-        if (!sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: null stream");
-        if (lens[j] < 0 || (lens[j] == 0 && !fin))
-            return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: a chunk of less than one frame (zero only with final)");
-        if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: a stream belongs to another (or a destroyed) context");
-        if (sc->finished) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: a stream whose final chunk went out");
-        for (int i = 0; i < j; ++i)
-            if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode_many_at: a stream named twice");
-        if (lens[j] > c.max_frames || sc->t0 + lens[j] > c.max_frames)
-            return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: stream longer than max_frames (rope table)");
-        total += lens[j];
         const long long nin = (long long)lens[j] * fl;
-        no[j] = sc->rs ? rs_ready(*sc->rs, sc->nin + nin, fin) - sc->nout : nin;
+        no[j] = sc->rs ? rs_ready(*sc->rs, sc->nin + nin, final && final[j]) - sc->nout : nin;
         total_out += no[j];
         any_rate = any_rate || sc->rs;
     }
-    if (total > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: chunks longer than max_frames together");
     if (any_rate && (size_t)total_out > s->rs_cap) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: output buffer");
     // the codec runs over the streams with frames (their code blocks are back to back, as the call's)
     std::vector<ft_codec_stream*> cs;
@@ -1423,10 +1401,7 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     if (!cs.empty()) {
         FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio, &segs));
     } else {   // tails only
-        FT_TRY(rs_enqueue(ctx, segs, audio));
-        FT_HIP(ctx, hipStreamSynchronize(s->stream));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("resample launch: ") + hipGetErrorString(e));
+        FT_TRY(call_tail(ctx, &segs, audio, 0, "resample launch: "));
     }
     for (int j = 0; j < n; ++j) {
         ft_codec_stream* sc = streams[j];
@@ -1443,8 +1418,7 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
 extern "C" ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out) {
     if (!ctx) return FT_ERR_ARG;
     FT_TRY(rs_refuse(ctx, "ft_test_resample", sample_rate));
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     if (!x || !y || !n_out || n < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_resample: bad argument");
     CodecState* s = ctx->codec;
     if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_resample: longer than max_frames of audio");
@@ -1461,38 +1435,7 @@ extern "C" ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, in
     FT_TRY(rs_alloc(ctx));
     FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     std::vector<RsSeg> g(1, RsSeg{s->audio, t->w, nullptr, nullptr, nullptr, 0, 0, (int)n, (int)no, t->L, t->M, t->K, 0});
-    FT_TRY(rs_enqueue(ctx, g, y));
-    FT_HIP(ctx, hipStreamSynchronize(s->stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("resample launch: ") + hipGetErrorString(e));
-    return FT_OK;
-}
-
-// One window-limited transformer (vocoder.py:338-354) over the f32 residual stream x [T][D]; output of the final
-// RMSNorm goes to out_bf and/or out_f32.
-static void run_transformer(ft_ctx* ctx, hipStream_t st, const std::vector<TfLayer>& layers, const float* final_norm,
-                            float* x, int T, int D, int H, int hd, int ffn, int window, const float* rope,
-                            bf16_t* xn, bf16_t* qkv, bf16_t* y, bf16_t* g, bf16_t* out_bf, float* out_f32, const char* pfx) {
-    const ft_codec_config& c = ctx->cc;
-    CodecState* s = ctx->codec;
-    const int HD = H * hd;
-    for (const TfLayer& t : layers) {
-        const int l = (int)(&t - layers.data());
-        rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, t.n1, c.tf_norm_eps, D, xn, nullptr});
-        if (s->trace) trace_rec(s, st, tname("%s%d.norm1", pfx, l), T, D, -1, 0, 0, 0, {{0, xn, 0}});
-        { GemmIO io{xn, D, T, T}; io.out_bf = qkv; io.ldo = 3 * HD; gemm_t(s, st, t.qkv, io, "%s%d.qkv", l, 0, pfx); }
-        rope_qk_kernel<<<gridfor((long)T * 2 * H * (hd / 2)), 256, 0, st>>>(qkv, rope, T, H, hd);
-        if (s->trace) trace_rec(s, st, tname("%s%d.rope", pfx, l), T, 3 * HD, -1, 0, 0, 0, {{0, qkv, 0}});
-        window_attn_kernel<<<(T * H + 3) / 4, 256, 0, st>>>(WinAttnP{qkv, y, T, H, hd, window, 1.0f / sqrtf((float)hd)});
-        if (s->trace) trace_rec(s, st, tname("%s%d.attn", pfx, l), T, HD, -1, 0, 0, 0, {{0, y, 0}});
-        { GemmIO io{y, HD, T, T}; io.gamma = t.g1; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm_t(s, st, t.wo, io, "%s%d.wo", l, 0, pfx); }
-        rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, t.n2, c.tf_norm_eps, D, xn, nullptr});
-        if (s->trace) trace_rec(s, st, tname("%s%d.norm2", pfx, l), T, D, -1, 0, 0, 0, {{0, xn, 0}});
-        { GemmIO io{xn, D, T, T}; io.act = ACT_SWIGLU; io.out_bf = g; io.ldo = ffn; gemm_t(s, st, t.w13, io, "%s%d.w13", l, 0, pfx); }
-        { GemmIO io{g, ffn, T, T}; io.gamma = t.g2; io.resid_f32 = x; io.ldr = D; io.out_f32 = x; io.ldo = D; gemm_t(s, st, t.w2, io, "%s%d.w2", l, 0, pfx); }
-    }
-    rmsnorm_rows_kernel<<<T, 256, 0, st>>>(RowNormP{x, final_norm, c.tf_norm_eps, D, out_bf, out_f32});
-    if (s->trace) trace_rec(s, st, tname("%snorm", pfx), T, D, -1, 0, 0, 0, {{0, out_bf, 0}, {2, out_f32, 1}});
+    return call_tail(ctx, &g, y, 0, "resample launch: ");
 }
 
 static ft_status rvq_search(ft_ctx* ctx, hipStream_t st, const float* z, int T, int* codes_dev) {
@@ -1507,7 +1450,7 @@ static ft_status rvq_search(ft_ctx* ctx, hipStream_t st, const float* z, int T, 
 extern "C" ft_status ft_codec_rvq_encode(ft_ctx* ctx, const float* z, int32_t T, int32_t* codes) {
     if (!ctx) return FT_ERR_ARG;
     if (!ctx->has_codec || !ctx->codec || !ctx->codec->has_enc) return ft_fail(ctx, FT_ERR_STATE, "codec encoder not configured");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     const ft_codec_config& c = ctx->cc;
     if (!z || !codes || T < 1 || T > c.max_enc_frames) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_rvq_encode: bad argument");
     CodecState* s = ctx->codec;
@@ -1523,10 +1466,10 @@ extern "C" ft_status ft_codec_rvq_encode(ft_ctx* ctx, const float* z, int32_t T,
 
 extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_samples, int32_t* codes, int32_t* out_frames) {
     if (!ctx) return FT_ERR_ARG;
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    FT_TRY(codec_ready(ctx, false));
     CodecState* s = ctx->codec;
     if (!s->has_enc) return ft_fail(ctx, FT_ERR_STATE, "codec encoder not configured (encoder_dim = 0)");
-    if (!ctx->finalized) return ft_fail(ctx, FT_ERR_STATE, "weights not finalized (ft_finalize_weights)");
+    FT_TRY(codec_ready(ctx));
     if (!audio || !codes || !out_frames || n_samples < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_encode: bad argument");
     const ft_codec_config& c = ctx->cc;
     const long fl = s->enc_frame_len;
@@ -1563,8 +1506,8 @@ extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_
         { GemmIO io{a, (long)b.s * b.cin, (int)Tn, (int)Tn}; if (has_tf) io.out_f32 = s->enc_x; else io.out_bf = o; io.ldo = b.cout; gemm_t(s, st, b.sc, io, "%senc.%d.sc", (int)bi); }
         T = Tn;
         if (has_tf)
-            run_transformer(ctx, st, b.tf, b.tf_norm, s->enc_x, (int)T, b.cout, b.cout / 64, 64, 3 * b.cout, c.enc_tf_window,
-                            s->rope_enc, s->e_xn, s->e_qkv, s->e_y, s->e_g, o, nullptr, tname("enc.%d.tf.", (int)bi).c_str());
+            run_transformer(ctx, Layout::plain((int)T, s->e_qkv), b.tf, b.tf_norm, s->enc_x, b.cout, b.cout / 64, 64, 3 * b.cout,
+                            c.enc_tf_window, s->rope_enc, s->e_xn, s->e_y, s->e_g, o, nullptr, tname("enc.%d.tf.", (int)bi).c_str());
         const float* alpha_next = bi + 1 < s->enc.size() ? s->enc[bi + 1].u[0].a0 : s->enc_a_last;
         snake_bf_rows_kernel<<<gridfor(T * b.cout), 256, 0, st>>>(o, alpha_next, a, T * b.cout, b.cout);
         if (s->trace) trace_rec(s, st, tname("enc.%d.snake", (int)bi), T, b.cout, -1, 0, 0, 0, {{1, a, 0}});
@@ -1592,8 +1535,8 @@ extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_
     }
     if (T != Tf) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_encode: stage rates do not multiply to the frame length");
     // pre_module (window-limited transformer), then the residual quantiser search
-    run_transformer(ctx, st, s->pre, s->pre_norm, s->enc_x, (int)T, D, H, hd, c.tf_ffn, c.tf_window, s->rope,
-                    s->e_xn, s->e_qkv, s->e_y, s->e_g, nullptr, s->enc_zq, "pre.");
+    run_transformer(ctx, Layout::plain((int)T, s->e_qkv), s->pre, s->pre_norm, s->enc_x, D, H, hd, c.tf_ffn, c.tf_window, s->rope,
+                    s->e_xn, s->e_y, s->e_g, nullptr, s->enc_zq, "pre.");
     FT_TRY(rvq_search(ctx, st, s->enc_zq, (int)T, s->enc_codes));
     FT_HIP(ctx, hipMemcpyAsync(codes, s->enc_codes, (size_t)R * T * sizeof(int), hipMemcpyDeviceToHost, st));
     FT_HIP(ctx, hipStreamSynchronize(st));
@@ -1610,7 +1553,7 @@ extern "C" int32_t ft_codec_frame_len(const ft_ctx* ctx) { return ctx && ctx->co
 // ---- launch trace hooks (fishtts_hip_test.h)
 extern "C" ft_status ft_test_codec_trace_arm(ft_ctx* ctx, int32_t first, int32_t count) {
     if (!ctx) return FT_ERR_ARG;
-    if (!ctx->has_codec || !ctx->codec) return ft_fail(ctx, FT_ERR_STATE, "Vocoder not loaded");
+    FT_TRY(codec_ready(ctx, false));
     if (first < 0 || count < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_codec_trace_arm: bad range");
     CodecState* s = ctx->codec;
     std::lock_guard<std::mutex> lock(s->mu);
