@@ -15,7 +15,8 @@ would pass `max_frames` starts afresh (as synthesize_stream does).
 
 With `sample_rate` the streams are `stream(sample_rate)` (their output resampled on the device) and decode_streams takes
 one final flag per chunk: an utterance's last chunk is decoded with final=True, or, when its end is known only after its
-last chunk went out, the stream's `finish()` gives the held-back tail; either way the tail is out before (i, b"")."""
+last chunk went out, the stream's `finish()` gives the held-back tail; either way the tail is out before (i, b"").
+`speed` (a speaking rate) is passed through to the streams in the same way: `stream(sample_rate, speed=speed)`."""
 from __future__ import annotations
 
 import queue
@@ -69,13 +70,16 @@ class ChunkCutter:
 
 
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
-                      min_first_chunk: int = 10, sample_rate: Optional[int] = None) -> Iterator[Tuple[int, bytes]]:
+                      min_first_chunk: int = 10, sample_rate: Optional[int] = None,
+                      speed: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
     """Yields (i, pcm) chunks of the n utterances `run` generates, in the order they become ready, and (i, b"") once
     after utterance i's last chunk.  `run` is called on a producer thread, the codec on a worker thread; abandoning the
     generator stops the producer at its next block of frames and joins both threads.  An exception of either thread is
     raised from the generator."""
     if chunk_tokens < 1 or min_first_chunk < 1:
         raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
+    fx = sample_rate is not None or speed is not None       # an output stage holds back a tail
+    skw = {} if speed is None else {"speed": speed}
     cv = threading.Condition()
     cuts = [ChunkCutter(chunk_tokens, min_first_chunk) for _ in range(n)]
     ended = [False] * n                                 # end mark handed out (worker only)
@@ -133,8 +137,10 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                     chunks = [cuts[i].ready.popleft() for i in batch]
                     final = [cuts[i].done and not cuts[i].ready for i in batch]
                 for i in ends:                          # after the utterance's last chunk went out
-                    if sample_rate is not None and streams[i] is not None and not streams[i].finished:
-                        out.put((i, pcm16(streams[i].finish())))       # the resampler's tail
+                    if fx and streams[i] is not None and not streams[i].finished:
+                        tail = streams[i].finish()                     # the output stages' tail
+                        if len(tail) or not skw:
+                            out.put((i, pcm16(tail)))
                     if streams[i] is not None:
                         streams[i].close()
                         streams[i] = None
@@ -146,16 +152,17 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                     s = streams[i]
                     if s is None or s.frames + c.shape[1] > codec.max_frames:   # the rotation table ends there
                         if s is not None:
-                            if sample_rate is not None:
+                            if fx:
                                 out.put((i, pcm16(s.finish())))
                             s.close()
-                        streams[i] = codec.stream() if sample_rate is None else codec.stream(sample_rate)
-                if sample_rate is None:
+                        streams[i] = codec.stream() if not fx else codec.stream(sample_rate, **skw)
+                if not fx:
                     audio = codec.decode_streams([streams[i] for i in batch], chunks)
                 else:
                     audio = codec.decode_streams([streams[i] for i in batch], chunks, final)
                 for i, a in zip(batch, audio):
-                    out.put((i, pcm16(a)))
+                    if len(a) or not skw:               # (a chunk that completes no frame of the time-scale stage gives
+                        out.put((i, pcm16(a)))          # no samples yet: (i, b"") is the end mark alone)
         except BaseException as e:  # noqa: BLE001
             errors.append(e)
             with cv:

@@ -39,6 +39,34 @@ def resampled_len(sample_rate: Optional[int], n: int) -> int:
     return int(n) if rate is None else int(L.load().ft_resampled_len(rate, int(n)))
 
 
+def output_speed(speed) -> Optional[int]:
+    """A caller's `speed=`: None for the model's own pace (None, or a value that rounds to 100 percent: no time-scale
+    stage), else the speed as an integer percentage, round(speed * 100), for a speed in [0.5, 2.0]
+    (ft_timescaled_len).  Anything else raises ValueError (before any device work)."""
+    if speed is None:
+        return None
+    if isinstance(speed, bool) or not isinstance(speed, (int, float, np.integer, np.floating)):
+        raise ValueError(f"speed must be a number, got {speed!r}")
+    v = float(speed)
+    if not 0.5 <= v <= 2.0:      # (a nan fails both comparisons)
+        raise ValueError(f"unsupported speed {speed!r}: a factor in [0.5, 2.0]")
+    pct = int(round(v * 100))
+    return None if pct == 100 else pct
+
+
+def timescaled_len(speed, n: int) -> int:
+    """Samples that n codec samples give at `speed`: ceil(100 n / pct)."""
+    pct = output_speed(speed)
+    return int(n) if pct is None else int(L.load().ft_timescaled_len(pct, int(n)))
+
+
+def _out_len(rate: Optional[int], pct: Optional[int], n: int) -> int:
+    """n codec samples after the time-scale stage (pct) and the resampler (rate), either of them None: absent."""
+    lib = L.load()
+    n = int(n) if pct is None else int(lib.ft_timescaled_len(pct, int(n)))
+    return n if rate is None else int(lib.ft_resampled_len(rate, n))
+
+
 def fold_weight_norm(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """codec.pth stores weight-normed convs as parametrizations.weight.original0 (g) / original1 (v)
     (vocoder.py:423-429,457-463: torch weight_norm, dim=0).  Fold them to plain `.weight` tensors and
@@ -218,11 +246,13 @@ class CodecHipEngine:
             launches.append(rec)
         return res, launches
 
-    def stream(self, sample_rate: Optional[int] = None) -> "CodecStream":
+    def stream(self, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> "CodecStream":
         """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode.
         `sample_rate` (output_rate): the stream's output is resampled on the device; it holds back the samples whose
-        filter taps reach past the input so far, until a later chunk, decode(final=True) or finish()."""
-        return CodecStream(self, sample_rate)
+        filter taps reach past the input so far, until a later chunk, decode(final=True) or finish().
+        `speed` (output_speed): the waveform is time-scaled on the device first; the stream holds back the samples that
+        a later frame of the stage still adds to, in the same way."""
+        return CodecStream(self, sample_rate, speed)
 
     MAX_STREAMS_PER_CALL = 64     # ft_codec_stream_decode_many
 
@@ -248,8 +278,9 @@ class CodecHipEngine:
         call (ft_codec_stream_decode_many): chunks[j] (n_codebooks+1, T_j) integer -> float32 (T_j * frame_len,), bit
         for bit what streams[j].decode(chunks[j]) gives.  More than 64 streams, or more than max_frames frames together,
         take several calls (the streams of calls that went through stay advanced if a later one fails).
-        Streams at other rates (stream(sample_rate=...)) may be mixed in (ft_codec_stream_decode_many_at): theirs are
-        the resampled samples the chunk completes, bit for bit what streams[j].decode(chunks[j], final[j]) gives;
+        Streams at other rates or speeds (stream(sample_rate=..., speed=...)) may be mixed in
+        (ft_codec_stream_decode_many_at): theirs are the time-scaled / resampled samples the chunk completes, bit for
+        bit what streams[j].decode(chunks[j], final[j]) gives;
         final[j] also emits the stream's tail and closes it for decoding (a chunk of 0 frames is allowed then)."""
         streams = list(streams)
         chunks = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in chunks]
@@ -257,7 +288,7 @@ class CodecHipEngine:
             raise ValueError("decode_streams: one chunk per stream")
         for c in chunks:
             assert c.ndim == 2 and c.shape[0] == self.R, c.shape
-        if final is not None or any(s.rate is not None for s in streams):
+        if final is not None or any(s.rate is not None or s.pct is not None for s in streams):
             return self._decode_streams_at(streams, chunks, [False] * len(streams) if final is None else list(final))
         out: List[np.ndarray] = []
         for _, _, group, lens, codes, handles in self._stream_groups(streams, chunks):
@@ -303,11 +334,27 @@ class CodecHipEngine:
                                               y.ctypes.data_as(C.c_void_p), C.byref(n)), "ft_test_resample")
         return y[:n.value]
 
-    def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, sample_rate: Optional[int] = None) -> np.ndarray:
+    def test_timescale(self, x: np.ndarray, speed_pct: int):
+        """Test hook (ft_test_timescale): the time-scale stage alone on a waveform at the codec rate (zeros around it).
+        Returns (y, d): the timescaled_len samples and the alignment d_k the stage chose for every frame."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        pct = int(speed_pct)
+        n_out = max(1, int(self.lib.ft_timescaled_len(pct, len(x))))
+        y = np.empty(n_out, dtype=np.float32)
+        d = np.zeros((n_out + 511) // 512 + 1, dtype=np.int32)
+        n, k = C.c_int64(0), C.c_int32(0)
+        self._check(self.lib.ft_test_timescale(self._h, x.ctypes.data_as(C.c_void_p), len(x), pct, y.ctypes.data_as(C.c_void_p),
+                                               C.byref(n), d.ctypes.data_as(C.c_void_p), C.byref(k)), "ft_test_timescale")
+        return y[:n.value], d[:k.value]
+
+    def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, sample_rate: Optional[int] = None,
+               speed: Optional[float] = None) -> np.ndarray:
         """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len).
         `sample_rate` (output_rate): resampled on the device, (B, max_b resampled_len(lens[b] * frame_len)); row b holds
-        resampled_len(sample_rate, lens[b] * frame_len) samples, zeros after them."""
-        rate = output_rate(sample_rate)
+        resampled_len(sample_rate, lens[b] * frame_len) samples, zeros after them.
+        `speed` (output_speed): time-scaled on the device (before the resampler); row b holds the timescaled_len - then
+        resampled_len - of its samples, zeros after them."""
+        rate, pct = output_rate(sample_rate), output_speed(speed)
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
@@ -315,6 +362,15 @@ class CodecHipEngine:
         B, R, T = codes.shape
         assert R == self.R, codes.shape
         lens_a = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+        if pct is not None:
+            width = max(_out_len(rate, pct, int(n) * self.frame_len) for n in lens_a)
+            audio = np.empty((B, max(width, 1)), dtype=np.float32)
+            out_lens = np.zeros(B, dtype=np.int64)
+            self._check(self.lib.ft_codec_decode_fx(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
+                                                    lens_a.ctypes.data_as(C.c_void_p), CODEC_RATE if rate is None else rate, pct,
+                                                    audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
+                        "ft_codec_decode_fx")
+            return audio[:, :width]
         if rate is not None:
             width = max(resampled_len(rate, int(n) * self.frame_len) for n in lens_a)
             audio = np.empty((B, max(width, 1)), dtype=np.float32)
@@ -336,34 +392,38 @@ class CodecStream:
     here the causal codec's context - the last 127 frames' K/V of every transformer layer, the last rows of every
     convolution input - is carried)."""
 
-    def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None):
+    def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None, speed: Optional[float] = None):
         self.engine = engine
         self.rate = output_rate(sample_rate)      # None: the codec's own rate
+        self.pct = output_speed(speed)            # None: the model's own pace
         self._h = C.c_void_p()
-        if self.rate is None:
+        if self.pct is not None:
+            engine._check(engine.lib.ft_codec_stream_begin_fx(engine._h, CODEC_RATE if self.rate is None else self.rate, self.pct,
+                                                              C.byref(self._h)), "ft_codec_stream_begin_fx")
+        elif self.rate is None:
             engine._check(engine.lib.ft_codec_stream_begin(engine._h, C.byref(self._h)), "ft_codec_stream_begin")
         else:
             engine._check(engine.lib.ft_codec_stream_begin_at(engine._h, self.rate, C.byref(self._h)), "ft_codec_stream_begin_at")
         self.frames = 0
-        self.samples_out = 0       # resampled samples handed out so far (a stream at another rate)
+        self.samples_out = 0       # samples handed out so far (a stream at another rate or speed)
         self.finished = False      # its tail went out: no further chunk
         engine._streams.add(self)      # the engine ends its open streams before it destroys the native context
 
     def _cap(self, n_in: int) -> int:
         """Most samples the next call can give for n_in more codec samples."""
-        if self.rate is None:
+        if self.rate is None and self.pct is None:
             return n_in
-        return resampled_len(self.rate, self.frames * self.engine.frame_len + n_in) - self.samples_out
+        return _out_len(self.rate, self.pct, self.frames * self.engine.frame_len + n_in) - self.samples_out
 
     def _advance(self, T: int, n_out: int, final: bool) -> None:
         self.frames += T
         self.samples_out += n_out
-        self.finished = self.finished or (final and self.rate is not None)
+        self.finished = self.finished or (final and (self.rate is not None or self.pct is not None))
 
     def finish(self) -> np.ndarray:
-        """The held-back tail of a stream at another rate (the input taken as zero past its end); the stream takes no
-        further chunk.  Empty at the codec's own rate, and once the tail went out."""
-        if self.rate is None or self.finished:
+        """The held-back tail of a stream at another rate or speed (the input taken as zero past its end); the stream
+        takes no further chunk.  Empty at the codec's own rate and pace, and once the tail went out."""
+        if (self.rate is None and self.pct is None) or self.finished:
             return np.zeros(0, dtype=np.float32)
         return self.engine.decode_streams([self], [np.zeros((self.engine.R, 0), dtype=np.int32)], [True])[0]
 
@@ -373,7 +433,7 @@ class CodecStream:
         e = self.engine
         codes = np.ascontiguousarray(np.asarray(codes), dtype=np.int32)
         assert codes.ndim == 2 and codes.shape[0] == e.R, codes.shape
-        if self.rate is not None:
+        if self.rate is not None or self.pct is not None:
             return e.decode_streams([self], [codes], [final])[0]
         T = codes.shape[1]
         audio = np.empty(T * e.frame_len, dtype=np.float32)

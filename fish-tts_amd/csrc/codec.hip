@@ -64,6 +64,12 @@ struct CodecState {
     float* rs_out = nullptr;
     size_t rs_cap = 0;
     RsSeg* rs_seg = nullptr;
+    // time-scale stage (ft_codec_decode_fx, ft_codec_stream_begin_fx): the window, an output buffer (the resampler's input
+    // then), a segment table and the test hook's d_k, allocated on the first time-scaled call
+    float *ts_win = nullptr, *ts_out = nullptr;
+    size_t ts_cap = 0;
+    TsSeg* ts_seg = nullptr;
+    int* ts_delta = nullptr;
     // ---- encode side
     struct EncUnit { float *a0, *a2; ConvW c7, c1; };
     struct EncBlock { EncUnit u[3]; float* a3; ConvW sc; int s, cin, cout; std::vector<TfLayer> tf; float* tf_norm = nullptr; };
@@ -691,6 +697,13 @@ struct ft_codec_stream {
     int rpar = 0;
     long long nin = 0, nout = 0;
     bool finished = false;                         // its tail went out (final): no further chunk
+    // time-scaled output (ft_codec_stream_begin_fx; pct 0: none): the input samples a later frame can still read and
+    // the state after the last frame run (two copies each), the counters on the host.  The resampler's input is then the
+    // time-scaled waveform: nin counts those samples.
+    int pct = 0;
+    float *tcarry[2] = {nullptr, nullptr}, *tstate[2] = {nullptr, nullptr};
+    int tpar = 0, tk = 0;                          // tk: frames run so far
+    long long tin = 0, tbase = 0, tout = 0;        // codec samples seen, first one carried, time-scaled samples emitted
     std::vector<void*> owned;
 };
 
@@ -770,16 +783,90 @@ static ft_status rs_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) 
 
 // The output buffer and segment table, allocated once: max_frames of input at the highest rate, plus what streams hold
 // back (K/2 L/M + 1 < RS_LDS outputs each).
-static ft_status rs_alloc(ft_ctx* ctx) {
+// `wide`: for time-scaled input (ts_cap samples: twice the codec's, speed 0.5).  A context that resampled before its first
+// time-scaled call holds a narrow buffer already: that one is replaced and stays allocated, unused, until the context
+// is destroyed (max_frames frame_len 48 / 44.1 floats; the price of allocating nothing wide for callers who never set a speed).
+static ft_status rs_alloc(ft_ctx* ctx, bool wide = false) {
     CodecState* s = ctx->codec;
-    if (s->rs_seg) return FT_OK;
-    const size_t in = (size_t)ctx->cc.max_frames * s->frame_len;
+    const size_t in = wide ? s->ts_cap : (size_t)ctx->cc.max_frames * s->frame_len;
     const size_t cap = (in * RS_MAX_RATE + RS_FI - 1) / RS_FI + (size_t)RS_MAX_SEGS * RS_LDS;
-    FT_TRY(cmalloc(ctx, &s->rs_out, cap));
-    RsSeg* t = nullptr;
-    FT_TRY(cmalloc(ctx, &t, (size_t)RS_MAX_SEGS));
+    if (s->rs_seg && s->rs_cap >= cap) return FT_OK;
+    float* o = nullptr;
+    FT_TRY(cmalloc(ctx, &o, cap));
+    RsSeg* t = s->rs_seg;
+    if (!t) FT_TRY(cmalloc(ctx, &t, (size_t)RS_MAX_SEGS));
+    s->rs_out = o;
     s->rs_cap = cap;
     s->rs_seg = t;
+    return FT_OK;
+}
+
+// ---- time-scale stage (TsSeg, timescale_kernel; fishtts_hip.h states the algorithm)
+constexpr int TS_MIN_PCT = 50, TS_MAX_PCT = 200;
+static bool ts_ok(int pct) { return pct >= TS_MIN_PCT && pct <= TS_MAX_PCT; }
+static long long ts_len(int pct, long long n) { return (100 * n + pct - 1) / pct; }
+static long long ts_a(int pct, long long k) { return k * TS_HS * pct / 100; }
+// Input samples frame k needs to have been seen: its search region ends at a_k + HS + D, its template (the continuation
+// of frame k - 1) at most at a_{k-1} + D + N, which lies further on below speed 1.
+static long long ts_need(int pct, long long k) {
+    return std::max(ts_a(pct, k), k > 0 ? ts_a(pct, k - 1) + TS_HS : 0) + TS_HS + TS_D;
+}
+struct TsPlan { int k1 = 0; long long out = 0, base = 0; };
+// What a stream that has run k0 frames does once it has seen `nin` samples: frames [k0, k1), outputs below `out` final,
+// input from `base` on kept for later frames.
+static TsPlan ts_plan(int pct, int k0, long long nin, bool final) {
+    TsPlan p;
+    if (final) {
+        p.out = ts_len(pct, nin);
+        p.k1 = (int)((p.out + TS_HS - 1) / TS_HS) + 1;
+        p.base = nin;
+        return p;
+    }
+    p.k1 = k0;
+    while (ts_need(pct, p.k1) <= nin) ++p.k1;
+    p.out = p.k1 > 0 ? (long long)(p.k1 - 1) * TS_HS : 0;
+    p.base = ts_a(pct, p.k1) - TS_HS - TS_D;
+    if (p.k1 > 0) p.base = std::min(p.base, ts_a(pct, p.k1 - 1) - TS_D);
+    p.base = std::max(p.base, 0LL);
+    return p;
+}
+
+// The stage's buffers, allocated once: twice max_frames of audio (speed 0.5) plus what 64 streams can hold back.
+static ft_status ts_alloc(ft_ctx* ctx) {
+    CodecState* s = ctx->codec;
+    if (s->ts_seg) return FT_OK;
+    const size_t in = (size_t)ctx->cc.max_frames * s->frame_len;
+    const size_t cap = 2 * in + (size_t)RS_MAX_SEGS * (2 * TS_CARRY + 2 * TS_HS);
+    std::vector<float> w(TS_N);
+    for (int i = 0; i < TS_N; ++i) w[i] = (float)(0.5 * (1.0 - std::cos(2.0 * M_PI * i / TS_N)));
+    float *win = nullptr, *o = nullptr;
+    int* d = nullptr;
+    TsSeg* t = nullptr;
+    FT_TRY(cmalloc(ctx, &win, (size_t)TS_N));
+    FT_HIP(ctx, hipMemcpy(win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+    FT_TRY(cmalloc(ctx, &o, cap));
+    FT_TRY(cmalloc(ctx, &d, cap / TS_HS + 2));
+    FT_TRY(cmalloc(ctx, &t, (size_t)RS_MAX_SEGS));
+    s->ts_win = win;
+    s->ts_out = o;
+    s->ts_delta = d;
+    s->ts_cap = cap;
+    s->ts_seg = t;
+    return rs_alloc(ctx, true);
+}
+
+// Time-scales `segs` (their inputs written earlier on the codec's stream) into ts_out, back to back; segment g's output is
+// the input of resampler segment g.rsi.
+static ft_status ts_enqueue(ft_ctx* ctx, std::vector<TsSeg>& segs, std::vector<RsSeg>& rs) {
+    CodecState* s = ctx->codec;
+    long long off = 0;
+    for (TsSeg& g : segs) {
+        g.y = s->ts_out + off;
+        rs[g.rsi].x = g.y;
+        off += g.n_out;
+    }
+    FT_HIP(ctx, hipMemcpyAsync(s->ts_seg, segs.data(), segs.size() * sizeof(TsSeg), hipMemcpyHostToDevice, s->stream));
+    timescale_kernel<<<dim3((unsigned)segs.size()), TS_THREADS, 0, s->stream>>>(s->ts_seg, s->ts_win);
     return FT_OK;
 }
 
@@ -958,13 +1045,18 @@ static bool decode_chain(ft_ctx* ctx, const Layout& L) {
     return in_step && ti == L.ntail();
 }
 
-// The end of a call that leaves samples: the resampler over `rs` (its segments' inputs written earlier on the stream) or the
+// The end of a call that leaves samples: the time-scale stage and the resampler over `fx` (inputs written earlier on the stream) or the
 // plain copy of `plain` floats of s->audio, the call's one synchronize and the launch check; then every stream named moves
 // on by its chunk.
-static ft_status call_tail(ft_ctx* ctx, std::vector<RsSeg>* rs, float* host, size_t plain, const char* what, int n = 0,
+struct Fx {   // the output stages of a call: resampler segments, and the time-scale segments in front of some of them
+    std::vector<RsSeg> rs;
+    std::vector<TsSeg> ts;
+};
+static ft_status call_tail(ft_ctx* ctx, Fx* fx, float* host, size_t plain, const char* what, int n = 0,
                            ft_codec_stream* const* scs = nullptr, const int32_t* lens = nullptr) {
     CodecState* s = ctx->codec;
-    if (rs) FT_TRY(rs_enqueue(ctx, *rs, host));
+    if (fx && !fx->ts.empty()) FT_TRY(ts_enqueue(ctx, fx->ts, fx->rs));
+    if (fx) FT_TRY(rs_enqueue(ctx, fx->rs, host));
     else FT_HIP(ctx, hipMemcpyAsync(host, s->audio, plain * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     FT_HIP(ctx, hipStreamSynchronize(s->stream));
     hipError_t e = hipGetLastError();
@@ -977,7 +1069,7 @@ static ft_status call_tail(ft_ctx* ctx, std::vector<RsSeg>* rs, float* host, siz
 }
 
 // The chain over L and the end of the call; `who` names the caller in the message of a carry list out of step.
-static ft_status decode_run(ft_ctx* ctx, const Layout& L, std::vector<RsSeg>* rs, float* audio_host, int n,
+static ft_status decode_run(ft_ctx* ctx, const Layout& L, Fx* rs, float* audio_host, int n,
                             ft_codec_stream* const* scs, const int32_t* lens, const char* who) {
     const bool in_step = decode_chain(ctx, L);
     FT_TRY(call_tail(ctx, rs, audio_host, (size_t)L.total * ctx->codec->frame_len, "codec launch: ", in_step ? n : 0, scs, lens));
@@ -994,7 +1086,7 @@ static void stream_carries(const ft_codec_stream* sc, bf16_t** out) {
 // One item: T of the Tfull frames per codebook row of codes_host, decoded from zero state, or (sc) as the next chunk of a
 // stream.  `rs`: resample the waveform (segment 0 reads s->audio) and copy the resampled samples instead.
 static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, int T, float* audio_host, ft_codec_stream* sc = nullptr,
-                            std::vector<RsSeg>* rs = nullptr) {
+                            Fx* rs = nullptr) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     const int HD = c.tf_n_head * c.tf_head_dim, R = c.n_codebooks + 1, W1 = c.tf_window - 1;
@@ -1083,6 +1175,7 @@ extern "C" ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* sc, co
     if (!codes || !audio || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode: bad argument");
     if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: the stream belongs to another (or a destroyed) context");
     if (sc->rate) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
+    if (sc->pct) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another speed (ft_codec_stream_decode_many_at)");
     const ft_codec_config& c = ctx->cc;
     if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: chunk longer than max_frames");
     if (sc->t0 + T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: stream longer than max_frames (rope table)");
@@ -1148,7 +1241,7 @@ static ft_status many_alloc(ft_ctx* ctx, int ncarry) {
 
 // `rs`: resample the chunks (ft_codec_stream_decode_many_at: the segments' inputs set by the caller) and copy those samples.
 static ft_status decode_many(ft_ctx* ctx, int n, ft_codec_stream* const* scs, const int32_t* codes_host, const int32_t* lens,
-                             float* audio_host, std::vector<RsSeg>* rs = nullptr) {
+                             float* audio_host, Fx* rs = nullptr) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     const int HD = c.tf_n_head * c.tf_head_dim, R = c.n_codebooks + 1, W1 = c.tf_window - 1;
@@ -1208,6 +1301,7 @@ static ft_status many_check(ft_ctx* ctx, const std::string& fn, int n, ft_codec_
             return ft_fail(ctx, FT_ERR_ARG, fn + ": a chunk of less than one frame" + (at ? " (zero only with final)" : ""));
         if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream belongs to another (or a destroyed) context");
         if (!at && sc->rate) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
+        if (!at && sc->pct) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another speed (ft_codec_stream_decode_many_at)");
         if (at && sc->finished) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream whose final chunk went out");
         for (int i = 0; i < j; ++i)
             if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, fn + ": a stream named twice");
@@ -1231,25 +1325,32 @@ extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_code
 }
 
 // The items of ft_codec_decode / ft_codec_decode_at, one after the other: item b's samples go to audio + b * stride, zeros
-// behind them.  `t`: the resampler's table (null, or K = 0: the codec's own rate).
+// behind them.  `t`: the resampler's table (null, or K = 0: the codec's own rate); `pct`: the speed (100: no time-scale stage).
 static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int B, int T, const int32_t* lens, float* audio,
-                              size_t stride, const CodecState::RsTab* t, int64_t* out_lens) {
+                              size_t stride, const CodecState::RsTab* t, int64_t* out_lens, int pct = 100) {
     CodecState* s = ctx->codec;
     const int R = ctx->cc.n_codebooks + 1;
     for (int b = 0; b < B; ++b) {
         const int Tb = lens ? lens[b] : T;
         if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
-        const size_t n_in = (size_t)Tb * s->frame_len, n_out = t ? (n_in * t->L + t->M - 1) / t->M : n_in;   // ft_resampled_len
+        const size_t n_in = (size_t)Tb * s->frame_len, n_ts = pct == 100 ? n_in : (size_t)ts_len(pct, (long long)n_in);
+        const size_t n_out = t ? (n_ts * t->L + t->M - 1) / t->M : n_ts;   // ft_resampled_len
         float* out = audio + (size_t)b * stride;
         if (out_lens) out_lens[b] = (int64_t)n_out;
         if (n_out < stride) memset(out + n_out, 0, (stride - n_out) * sizeof(float));
         if (Tb == 0) continue;
-        if (!t || t->K == 0) {
+        if ((!t || t->K == 0) && pct == 100) {
             FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
             continue;
         }
-        // a fresh input to the resampler: zeros before it, zeros after it (the whole tail)
-        std::vector<RsSeg> g(1, RsSeg{s->audio, t->w, nullptr, nullptr, nullptr, 0, 0, (int)n_in, (int)n_out, t->L, t->M, t->K, 0});
+        // a fresh input to each stage: zeros before it, zeros after it (the whole tail)
+        Fx g;
+        g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)n_ts, (int)n_out, 1, 1, 0, 0});
+        if (t && t->K > 0) { g.rs[0].w = t->w; g.rs[0].L = t->L; g.rs[0].M = t->M; g.rs[0].K = t->K; }
+        if (pct != 100) {
+            const TsPlan p = ts_plan(pct, 0, (long long)n_in, true);
+            g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, (int)n_in, (int)n_ts, 0, p.k1, pct, 0});
+        }
         FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, &g));
     }
     return FT_OK;
@@ -1292,31 +1393,52 @@ static ft_status rs_refuse(ft_ctx* ctx, const char* fn, int rate) {
     return e ? ft_fail(ctx, FT_ERR_ARG, std::string(fn) + ": " + e + " (" + std::to_string(rate) + ")") : FT_OK;
 }
 
-extern "C" ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
-                                        int32_t sample_rate, float* audio, int64_t* out_lens) {
+static ft_status ts_refuse(ft_ctx* ctx, const std::string& fn, int pct) {
+    return ts_ok(pct) ? FT_OK : ft_fail(ctx, FT_ERR_ARG, fn + ": speed outside [50, 200] percent (" + std::to_string(pct) + ")");
+}
+
+extern "C" int64_t ft_timescaled_len(int32_t speed_pct, int64_t n_in) {
+    return n_in < 0 || !ts_ok(speed_pct) ? -1 : ts_len(speed_pct, n_in);
+}
+
+static ft_status decode_fx(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                           int32_t sample_rate, int32_t pct, float* audio, int64_t* out_lens) {
     if (!ctx) return FT_ERR_ARG;
-    FT_TRY(rs_refuse(ctx, "ft_codec_decode_at", sample_rate));
+    FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
+    FT_TRY(ts_refuse(ctx, fn, pct));
     FT_TRY(codec_ready(ctx));
-    if (!codes || !audio || !out_lens || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode_at: bad argument");
-    if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_decode_at: T exceeds max_frames");
+    if (!codes || !audio || !out_lens || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
     CodecState* s = ctx->codec;
-    int64_t stride = 0;   // the longest item's resampled length (a bad length is refused before the table is built)
+    int64_t stride = 0;   // the longest item's output length (a bad length is refused before the table is built)
     for (int b = 0; b < B; ++b) {
         const int Tb = lens ? lens[b] : T;
-        if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_decode_at: bad length");
-        stride = std::max(stride, ft_resampled_len(sample_rate, (int64_t)Tb * s->frame_len));
+        if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
+        stride = std::max(stride, ft_resampled_len(sample_rate, ts_len(pct, (int64_t)Tb * s->frame_len)));
     }
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
     const CodecState::RsTab* t = nullptr;
     FT_TRY(rs_table(ctx, sample_rate, &t));
-    if (t->K > 0) FT_TRY(rs_alloc(ctx));
-    return decode_items(ctx, "ft_codec_decode_at", codes, B, T, lens, audio, (size_t)stride, t, out_lens);
+    if (pct != 100) FT_TRY(ts_alloc(ctx));
+    else if (t->K > 0) FT_TRY(rs_alloc(ctx));
+    return decode_items(ctx, fn, codes, B, T, lens, audio, (size_t)stride, t, out_lens, pct);
 }
 
-extern "C" ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, ft_codec_stream** out) {
+extern "C" ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                        int32_t sample_rate, float* audio, int64_t* out_lens) {
+    return decode_fx(ctx, "ft_codec_decode_at", codes, B, T, lens, sample_rate, 100, audio, out_lens);
+}
+
+extern "C" ft_status ft_codec_decode_fx(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                        int32_t sample_rate, int32_t speed_pct, float* audio, int64_t* out_lens) {
+    return decode_fx(ctx, "ft_codec_decode_fx", codes, B, T, lens, sample_rate, speed_pct, audio, out_lens);
+}
+
+static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sample_rate, int32_t pct, ft_codec_stream** out) {
     if (!ctx || !out) return FT_ERR_ARG;
-    FT_TRY(rs_refuse(ctx, "ft_codec_stream_begin_at", sample_rate));
+    FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
+    FT_TRY(ts_refuse(ctx, fn, pct));
     FT_TRY(codec_ready(ctx));
     CodecState* s = ctx->codec;
     const CodecState::RsTab* t = nullptr;
@@ -1324,33 +1446,50 @@ extern "C" ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, 
         std::lock_guard<std::mutex> lock(s->mu);
         FT_HIP(ctx, hipSetDevice(ctx->device));
         FT_TRY(rs_table(ctx, sample_rate, &t));
-        if (t->K > 0) FT_TRY(rs_alloc(ctx));
+        if (pct != 100) FT_TRY(ts_alloc(ctx));
+        else if (t->K > 0) FT_TRY(rs_alloc(ctx));
     }
     ft_codec_stream* sc = nullptr;
     FT_TRY(ft_codec_stream_begin(ctx, &sc));
-    if (t->K == 0) {
+    if (t->K == 0 && pct == 100) {
         *out = sc;
         return FT_OK;
     }
     bool ok = true;   // (as ft_codec_stream_begin: the stream is not visible to other calls yet)
-    for (int k = 0; k < 2 && ok; ++k) {
+    auto zalloc = [&](float** q, size_t n) {
         void* v = nullptr;
-        ok = hipMalloc(&v, (size_t)t->K * sizeof(float)) == hipSuccess;
-        if (!ok) break;
+        ok = ok && hipMalloc(&v, n * sizeof(float)) == hipSuccess;
+        if (!ok) return;
         sc->owned.push_back(v);
-        sc->rcarry[k] = (float*)v;
-        ok = hipMemsetAsync(v, 0, (size_t)t->K * sizeof(float), s->stream) == hipSuccess;   // the input before the first sample
+        *q = (float*)v;
+        ok = hipMemsetAsync(v, 0, n * sizeof(float), s->stream) == hipSuccess;   // the input before the first sample
+    };
+    for (int k = 0; k < 2 && t->K > 0; ++k) zalloc(&sc->rcarry[k], (size_t)t->K);
+    for (int k = 0; k < 2 && pct != 100; ++k) {
+        zalloc(&sc->tcarry[k], (size_t)TS_CARRY);
+        zalloc(&sc->tstate[k], (size_t)TS_STATE);
     }
     ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         ft_codec_stream_end(ctx, sc);
-        return ft_fail(ctx, FT_ERR_NOMEM, "ft_codec_stream_begin_at: could not set up the resampler carry");
+        return ft_fail(ctx, FT_ERR_NOMEM, fn + ": could not set up the output stages' carry");
     }
-    sc->rate = sample_rate;
-    sc->rs = t;
+    if (t->K > 0) {
+        sc->rate = sample_rate;
+        sc->rs = t;
+    }
+    if (pct != 100) sc->pct = pct;
     *out = sc;
     return FT_OK;
+}
+
+extern "C" ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, ft_codec_stream** out) {
+    return stream_begin_fx(ctx, "ft_codec_stream_begin_at", sample_rate, 100, out);
+}
+
+extern "C" ft_status ft_codec_stream_begin_fx(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, ft_codec_stream** out) {
+    return stream_begin_fx(ctx, "ft_codec_stream_begin_fx", sample_rate, speed_pct, out);
 }
 
 extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
@@ -1362,17 +1501,26 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     FT_TRY(many_check(ctx, "ft_codec_stream_decode_many_at", n, streams, lens, final, true));
     CodecState* s = ctx->codec;
     const int fl = s->frame_len;
-    long long total_out = 0;
-    bool any_rate = false;
+    long long total_out = 0, total_ts = 0;
+    bool any_fx = false;
     std::vector<long long> no(n);   // samples each stream gives out in this call
+    std::vector<TsPlan> tp(n);
     for (int j = 0; j < n; ++j) {
         const ft_codec_stream* sc = streams[j];
-        const long long nin = (long long)lens[j] * fl;
-        no[j] = sc->rs ? rs_ready(*sc->rs, sc->nin + nin, final && final[j]) - sc->nout : nin;
+        const bool fin = final && final[j];
+        long long nin = (long long)lens[j] * fl;   // samples into the resampler
+        if (sc->pct) {
+            tp[j] = ts_plan(sc->pct, sc->tk, sc->tin + nin, fin);
+            if (sc->tin + nin - tp[j].base > TS_CARRY) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: time-scale carry out of step");
+            nin = tp[j].out - sc->tout;
+            total_ts += nin;
+        }
+        no[j] = sc->rs ? rs_ready(*sc->rs, sc->nin + nin, fin) - sc->nout : nin;
         total_out += no[j];
-        any_rate = any_rate || sc->rs;
+        any_fx = any_fx || sc->rs || sc->pct;
     }
-    if (any_rate && (size_t)total_out > s->rs_cap) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: output buffer");
+    if (any_fx && ((size_t)total_out > s->rs_cap || (size_t)total_ts > s->ts_cap))
+        return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: output buffer");
     // the codec runs over the streams with frames (their code blocks are back to back, as the call's)
     std::vector<ft_codec_stream*> cs;
     std::vector<int32_t> cl;
@@ -1380,17 +1528,24 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
         if (lens[j] > 0) { cs.push_back(streams[j]); cl.push_back(lens[j]); }
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!any_rate) {   // the codec's rate only: ft_codec_stream_decode_many
+    if (!any_fx) {   // the codec's rate and pace only: ft_codec_stream_decode_many
         if (!cs.empty()) FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio));
         for (int j = 0; j < n; ++j) out_lens[j] = no[j];
         return FT_OK;
     }
-    std::vector<RsSeg> segs(n);
+    Fx fx;
+    fx.rs.resize(n);
     long long P = 0;
     for (int j = 0; j < n; ++j) {
         const ft_codec_stream* sc = streams[j];
-        RsSeg& g = segs[j];
+        RsSeg& g = fx.rs[j];
         g = RsSeg{s->audio + P * fl, nullptr, nullptr, nullptr, nullptr, sc->nin, sc->nout, lens[j] * fl, (int)no[j], 1, 1, 0, 0};
+        if (sc->pct) {   // the resampler (or the copy) reads what the time-scale stage emits
+            g.n_in = (int)(tp[j].out - sc->tout);
+            fx.ts.push_back(TsSeg{s->audio + P * fl, sc->tcarry[sc->tpar], sc->tcarry[sc->tpar ^ 1], sc->tstate[sc->tpar],
+                                  sc->tstate[sc->tpar ^ 1], nullptr, nullptr, sc->tin, sc->tbase, tp[j].base, sc->tout,
+                                  lens[j] * fl, g.n_in, sc->tk, tp[j].k1, sc->pct, j});
+        }
         if (sc->rs) {
             g.w = sc->rs->w; g.L = sc->rs->L; g.M = sc->rs->M; g.K = sc->rs->K;
             g.carry_rd = sc->rcarry[sc->rpar];
@@ -1399,15 +1554,24 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
         P += lens[j];
     }
     if (!cs.empty()) {
-        FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio, &segs));
+        FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio, &fx));
     } else {   // tails only
-        FT_TRY(call_tail(ctx, &segs, audio, 0, "resample launch: "));
+        FT_TRY(call_tail(ctx, &fx, audio, 0, "output stage launch: "));
     }
     for (int j = 0; j < n; ++j) {
         ft_codec_stream* sc = streams[j];
         out_lens[j] = no[j];
-        if (!sc->rs) continue;
-        sc->nin += (long long)lens[j] * fl;
+        if (!sc->rs && !sc->pct) continue;
+        if (sc->pct) {
+            sc->nin += tp[j].out - sc->tout;
+            sc->tin += (long long)lens[j] * fl;
+            sc->tout = tp[j].out;
+            sc->tbase = tp[j].base;
+            sc->tk = tp[j].k1;
+            sc->tpar ^= 1;
+        } else {
+            sc->nin += (long long)lens[j] * fl;
+        }
         sc->nout += no[j];
         sc->rpar ^= 1;
         sc->finished = final && final[j];
@@ -1434,8 +1598,32 @@ extern "C" ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, in
     }
     FT_TRY(rs_alloc(ctx));
     FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    std::vector<RsSeg> g(1, RsSeg{s->audio, t->w, nullptr, nullptr, nullptr, 0, 0, (int)n, (int)no, t->L, t->M, t->K, 0});
+    Fx g;
+    g.rs.assign(1, RsSeg{s->audio, t->w, nullptr, nullptr, nullptr, 0, 0, (int)n, (int)no, t->L, t->M, t->K, 0});
     return call_tail(ctx, &g, y, 0, "resample launch: ");
+}
+
+extern "C" ft_status ft_test_timescale(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, float* y, int64_t* n_out,
+                                       int32_t* deltas, int32_t* n_frames) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(ts_refuse(ctx, "ft_test_timescale", speed_pct));
+    FT_TRY(codec_ready(ctx));
+    if (!x || !y || !n_out || n < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_timescale: bad argument");
+    CodecState* s = ctx->codec;
+    if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_timescale: longer than max_frames of audio");
+    const TsPlan p = ts_plan(speed_pct, 0, n, true);
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    FT_TRY(ts_alloc(ctx));
+    *n_out = p.out;
+    if (n_frames) *n_frames = p.k1;
+    FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    Fx g;
+    g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)p.out, (int)p.out, 1, 1, 0, 0});
+    g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, s->ts_delta, 0, 0, 0, 0, (int)n, (int)p.out, 0, p.k1, speed_pct, 0});
+    FT_TRY(call_tail(ctx, &g, y, 0, "time-scale launch: "));
+    if (deltas) FT_HIP(ctx, hipMemcpy(deltas, s->ts_delta, (size_t)p.k1 * sizeof(int), hipMemcpyDeviceToHost));
+    return FT_OK;
 }
 
 static ft_status rvq_search(ft_ctx* ctx, hipStream_t st, const float* z, int T, int* codes_dev) {

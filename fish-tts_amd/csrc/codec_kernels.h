@@ -1543,4 +1543,117 @@ static __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const RsSeg
     }
 }
 
+// ---- WSOLA time-scale stage (ft_codec_decode_fx, ft_codec_stream_begin_fx; the algorithm is stated in fishtts_hip.h): at the
+// codec rate, speed pct / 100.  Frame k lies at a_k = floor(k HS pct / 100); it reads x[s_k + i], i < N, with
+// s_k = a_k - HS + d_k, and adds w[i] x[s_k + i] to output (k - 1) HS + i.  d_k in [-D, D] maximises the plain
+// cross-correlation of the frame with the continuation of frame k - 1, x[s_{k-1} + HS + i]; the lowest d wins a tie.
+// The frames of a segment depend on each other through d_{k-1}: one workgroup walks one segment's frames in order, the
+// segments of a call sit on blockIdx.x.  Per frame the template (N floats) and the search region (N + 2 D floats) are staged
+// in LDS; a thread holds four adjacent candidates in registers, so one 16-byte read of the region and one of the template
+// (a broadcast) feed sixteen fused multiply-adds, each sum over i ascending.  The argmax is a wave, then a workgroup reduction
+// over (value, index), the lower index winning on equal values.
+// A stream's part of a call: input indices in [cbase_rd, nin) come from its carry, [nin, nin + n_in) from x, the rest is
+// zero (before the first sample; past the last one in the final call - the host runs no frame earlier whose reads reach
+// past the input seen).  It reads one copy of its carry and state (s_{k-1}, the HS half-overlapped outputs) and writes
+// the other.
+constexpr int TS_N = 1024, TS_HS = 512, TS_D = 384, TS_THREADS = 256;
+constexpr int TS_REG = TS_N + 2 * TS_D, TS_CAND = 2 * TS_D + 1;
+constexpr int TS_CARRY = TS_N + 2 * TS_D + 2 * TS_HS;   // most input samples a stream carries
+constexpr int TS_STATE = TS_HS + 4;                     // floats of a state copy: the overlap, then s_{k-1} (an int)
+struct TsSeg {
+    const float* x;          // input samples [nin, nin + n_in) (device; unused when n_in = 0)
+    const float* carry_rd;   // input samples [cbase_rd, nin); null: none
+    float* carry_wr;         // receives input samples [cbase_wr, nin + n_in); null: not kept
+    const float* st_rd;      // state after frame k0 - 1; null: a fresh input (k0 = 0)
+    float* st_wr;            // state after frame k1 - 1; null: not kept
+    float* y;                // outputs [emit0, emit0 + n_out)
+    int* deltas;             // d_k of frames [k0, k1) (the test hook); null: not kept
+    long long nin, cbase_rd, cbase_wr, emit0;
+    int n_in, n_out, k0, k1, pct, rsi;   // rsi: host side only, the resampler segment that reads y
+};
+
+__device__ inline float ts_in(const TsSeg& s, long long i) {
+    if (i < s.nin) return s.carry_rd && i >= s.cbase_rd ? s.carry_rd[i - s.cbase_rd] : 0.f;   // (i < 0: cbase_rd >= 0)
+    if (i < s.nin + s.n_in) return s.x[i - s.nin];
+    return 0.f;
+}
+
+static __global__ __launch_bounds__(TS_THREADS) void timescale_kernel(const TsSeg* segs, const float* win) {
+    __shared__ __attribute__((aligned(16))) float tpl[TS_N];
+    __shared__ __attribute__((aligned(16))) float reg[TS_REG + 8];   // 8 zeros behind it: the last thread's 16-byte reads
+    __shared__ float ola[TS_HS];
+    __shared__ float rv[TS_THREADS / 64];
+    __shared__ int ri[TS_THREADS / 64];
+    const TsSeg s = segs[blockIdx.x];
+    const int t = threadIdx.x;
+    for (int i = t; i < TS_HS; i += TS_THREADS) ola[i] = s.st_rd ? s.st_rd[i] : 0.f;   // thread t owns ola[t], ola[t + 256]
+    if (t < 8) reg[TS_REG + t] = 0.f;
+    int sprev = s.st_rd ? *reinterpret_cast<const int*>(s.st_rd + TS_HS) : 0;
+    for (int k = s.k0; k < s.k1; ++k) {
+        const long long a = (long long)k * TS_HS * s.pct / 100;
+        __syncthreads();   // the frame before has read reg, rv, ri
+        for (int i = t; i < TS_REG; i += TS_THREADS) reg[i] = ts_in(s, a - TS_HS - TS_D + i);
+        int c = TS_D;      // d_0 = 0
+        if (k > 0) {
+            for (int i = t; i < TS_N; i += TS_THREADS) tpl[i] = ts_in(s, (long long)sprev + TS_HS + i);
+            __syncthreads();
+            float bv = -INFINITY;
+            int bi = TS_CAND;
+            const int cb = 4 * t;   // candidates cb .. cb + 3
+            if (cb < TS_CAND) {
+                const float4* R4 = reinterpret_cast<const float4*>(reg + cb);
+                const float4* T4 = reinterpret_cast<const float4*>(tpl);
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+                float4 lo = R4[0];
+#pragma unroll 2
+                for (int j = 0; j < TS_N / 4; ++j) {
+                    const float4 hi = R4[j + 1], v = T4[j];
+                    a0 = __builtin_fmaf(v.x, lo.x, a0); a1 = __builtin_fmaf(v.x, lo.y, a1); a2 = __builtin_fmaf(v.x, lo.z, a2); a3 = __builtin_fmaf(v.x, lo.w, a3);
+                    a0 = __builtin_fmaf(v.y, lo.y, a0); a1 = __builtin_fmaf(v.y, lo.z, a1); a2 = __builtin_fmaf(v.y, lo.w, a2); a3 = __builtin_fmaf(v.y, hi.x, a3);
+                    a0 = __builtin_fmaf(v.z, lo.z, a0); a1 = __builtin_fmaf(v.z, lo.w, a1); a2 = __builtin_fmaf(v.z, hi.x, a2); a3 = __builtin_fmaf(v.z, hi.y, a3);
+                    a0 = __builtin_fmaf(v.w, lo.w, a0); a1 = __builtin_fmaf(v.w, hi.x, a1); a2 = __builtin_fmaf(v.w, hi.y, a2); a3 = __builtin_fmaf(v.w, hi.z, a3);
+                    lo = hi;
+                }
+                const float av[4] = {a0, a1, a2, a3};
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (cb + q < TS_CAND && av[q] > bv) { bv = av[q]; bi = cb + q; }
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ov = __shfl_down(bv, off);
+                const int oi = __shfl_down(bi, off);
+                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            }
+            if ((t & 63) == 0) { rv[t >> 6] = bv; ri[t >> 6] = bi; }
+            __syncthreads();
+            bv = rv[0];
+            bi = ri[0];
+#pragma unroll
+            for (int w = 1; w < TS_THREADS / 64; ++w)
+                if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
+            c = bi < TS_CAND ? bi : TS_D;   // (no finite sum: keep d = 0)
+        } else {
+            __syncthreads();
+        }
+        // overlap-add: outputs [(k - 1) HS, k HS) are final now; the second half waits for frame k + 1
+        const long long p0 = (long long)(k - 1) * TS_HS - s.emit0;
+        for (int i = t; i < TS_HS; i += TS_THREADS) {
+            const float v = ola[i] + win[i] * reg[c + i];
+            const long long p = p0 + i;
+            if (k > 0 && p >= 0 && p < s.n_out) s.y[p] = v;
+            ola[i] = win[i + TS_HS] * reg[c + i + TS_HS];
+        }
+        sprev = (int)(a - TS_HS) + c - TS_D;
+        if (t == 0 && s.deltas) s.deltas[k - s.k0] = c - TS_D;
+    }
+    if (s.carry_wr) {
+        const int n = (int)(s.nin + s.n_in - s.cbase_wr);
+        for (int i = t; i < n && i < TS_CARRY; i += TS_THREADS) s.carry_wr[i] = ts_in(s, s.cbase_wr + i);
+    }
+    if (s.st_wr) {
+        for (int i = t; i < TS_HS; i += TS_THREADS) s.st_wr[i] = ola[i];
+        if (t == 0) *reinterpret_cast<int*>(s.st_wr + TS_HS) = sprev;
+    }
+}
+
 }  // namespace ft

@@ -27,6 +27,8 @@ for bit on an engine of up to 4 slots, within the evaluation-order margin of the
 Requests may ask for another output rate (sample_rate=): their WAVs and zero-state chunks are resampled on the device one
 by one; their seamless streams resample through their CodecStream, in the same decode_streams call as every other ready
 chunk whatever its rate, the last chunk (or a finish() after it) giving the resampler's tail before the end mark.
+A speaking rate (speed=) travels the same way: WAVs and zero-state chunks are time-scaled on the device one by one, a
+seamless request runs one carried time-scale stage in its CodecStream, its tail out before the end mark.
 
 A native error in either thread fails every in-flight and queued request with that exception and closes the server."""
 from __future__ import annotations
@@ -84,13 +86,25 @@ def lockstep_width(n: int, max_batch: int, wide_from: int) -> int:
     return wide_from if 2 <= n < wide_from <= max_batch else n
 
 
+def _output_speed(speed: Optional[float]) -> Optional[float]:
+    """codec_engine.output_speed as a factor: None for the model's own pace, ValueError for an unsupported one."""
+    if speed is None:
+        return None
+    from .codec_engine import output_speed
+    pct = output_speed(speed)
+    return None if pct is None else pct / 100.0
+
+
 class _Request:
     """One synthesize / synthesize_stream call: its utterance, chunking and output queue."""
 
     def __init__(self, utt: Utterance, n_prefix: int, mode: str, chunk_tokens: int, min_first_chunk: int,
-                 rate: Optional[int] = None):
+                 rate: Optional[int] = None, speed: Optional[float] = None):
         self.utt, self.n_prefix, self.mode = utt, n_prefix, mode          # mode: "wav" | "seamless" | "chunks"
         self.rate = rate              # output sample rate (None: the codec's own)
+        self.speed = speed            # speaking rate (None: the model's own pace)
+        self.fx = rate is not None or speed is not None       # an output stage holds back a tail
+        self.skw = {} if speed is None else {"speed": speed}
         self.cut = None if mode == "wav" else ChunkCutter(chunk_tokens, min_first_chunk, hold_back=mode == "seamless")
         self.out: "queue.Queue" = queue.Queue()
         self.cancelled = False        # the caller went away (or close(cancel=True))
@@ -150,46 +164,48 @@ class BatchServer:
 
     def synthesize(self, text: str, references=None, temperature: float = 0.7, top_p: float = 0.8,
                    repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
-                   sample_rate: Optional[int] = None) -> bytes:
+                   sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
         """Text -> WAV bytes: FishTTS.synthesize's result for seed 0 (draws with `seed`).  Safe from any number of threads;
-        `references=None` means the instance's set_references voices; `sample_rate` as FishTTS.synthesize (an
-        unsupported one raises ValueError here, before anything is queued)."""
-        rate = _output_rate(sample_rate)
+        `references=None` means the instance's set_references voices; `sample_rate` and `speed` as FishTTS.synthesize_at
+        (an unsupported one raises ValueError here, before anything is queued)."""
+        rate, spd = _output_rate(sample_rate), _output_speed(speed)
         utt, n_prefix = self._prepare(text, references, temperature, top_p, repetition_penalty, max_tokens, seed)
-        item = self.submit(utt, n_prefix, sample_rate=rate).out.get()
+        item = self.submit(utt, n_prefix, sample_rate=rate, speed=spd).out.get()
         if isinstance(item, _Failed):
             raise item.error
         return item
 
     def synthesize_stream(self, text: str, references=None, chunk_tokens: int = 20, min_first_chunk: int = 10,
-                          seamless: bool = False, sample_rate: Optional[int] = None, **sampling) -> Iterator[bytes]:
+                          seamless: bool = False, sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                          **sampling) -> Iterator[bytes]:
         """Yields int16 PCM chunks as FishTTS.synthesize_stream does: seamless=False (the reference's default) every chunk
         decoded from zero state; seamless=True one stateful CodecStream per request, the chunks cut as
         synthesize_batch_stream cuts them.  `sampling`: temperature, top_p, repetition_penalty, max_tokens, seed.  The
         prompt is built and checked here (a too-long one raises ValueError now); the request is queued at the first
         next(), so a generator dropped before it never runs, and abandoning it later cancels the request (its slot is
-        freed at the next burst boundary).  `sample_rate` as FishTTS.synthesize_stream (checked here)."""
+        freed at the next burst boundary).  `sample_rate` and `speed` as FishTTS.synthesize_stream (checked here)."""
         if chunk_tokens < 1 or min_first_chunk < 1:
             raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-        rate = _output_rate(sample_rate)
+        rate, spd = _output_rate(sample_rate), _output_speed(speed)
         utt, n_prefix = self._prepare(text, references, sampling.get("temperature", 0.7), sampling.get("top_p", 0.8),
                                       sampling.get("repetition_penalty", 1.1), sampling.get("max_tokens", 2048),
                                       sampling.get("seed", 0))
-        return self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, rate)
+        return self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, rate, spd)
 
     def _stream(self, utt: Utterance, n_prefix: int, seamless: bool, chunk_tokens: int,
-                min_first_chunk: int, rate: Optional[int] = None) -> Iterator[bytes]:
+                min_first_chunk: int, rate: Optional[int] = None, speed: Optional[float] = None) -> Iterator[bytes]:
         yield from self._chunks(self.submit(utt, n_prefix, stream=True, seamless=seamless, chunk_tokens=chunk_tokens,
-                                            min_first_chunk=min_first_chunk, sample_rate=rate))
+                                            min_first_chunk=min_first_chunk, sample_rate=rate, speed=speed))
 
     def submit(self, utt: Utterance, n_prefix: int = 0, stream: bool = False, seamless: bool = False,
-               chunk_tokens: int = 20, min_first_chunk: int = 10, sample_rate: Optional[int] = None) -> _Request:
+               chunk_tokens: int = 20, min_first_chunk: int = 10, sample_rate: Optional[int] = None,
+               speed: Optional[float] = None) -> _Request:
         """Queues one prepared utterance (the layer under synthesize / synthesize_stream); its output arrives on
         `.out`.  Raises ServerClosed once the server is closing or has failed."""
         if self._codec is None:
             raise RuntimeError("Vocoder not loaded")
         req = _Request(utt, n_prefix, ("seamless" if seamless else "chunks") if stream else "wav", chunk_tokens,
-                       min_first_chunk, _output_rate(sample_rate))
+                       min_first_chunk, _output_rate(sample_rate), _output_speed(speed))
         with self._lock:
             if self._error is not None:
                 raise ServerClosed(f"BatchServer failed: {self._error!r}") from self._error
@@ -444,8 +460,8 @@ class BatchServer:
                     for r in gone + wavs + ends:
                         r.taken = True                   # its last hand-out is under way: not picked again
                 for r in gone + ends:
-                    if r in ends and r.rate is not None and r.stream is not None and not r.stream.finished:
-                        with self.codec_lock:           # the resampler's tail, before the end mark
+                    if r in ends and r.fx and r.stream is not None and not r.stream.finished:
+                        with self.codec_lock:           # the output stages' tail, before the end mark
                             r.out.put(pcm16(r.stream.finish()))
                     if r.stream is not None:
                         r.stream.close()
@@ -456,26 +472,27 @@ class BatchServer:
                         for r, c in zip(seam, seam_chunks):
                             if r.stream is None or r.stream.frames + c.shape[1] > self._codec.max_frames:
                                 if r.stream is not None:   # the rotation table ends there (as in synthesize_stream)
-                                    if r.rate is not None:
+                                    if r.fx:
                                         r.out.put(pcm16(r.stream.finish()))
                                     r.stream.close()
-                                r.stream = self._codec.stream() if r.rate is None else self._codec.stream(r.rate)
+                                r.stream = self._codec.stream() if not r.fx else self._codec.stream(r.rate, **r.skw)
                         streams = [r.stream for r in seam]
-                        if all(r.rate is None for r in seam):
+                        if not any(r.fx for r in seam):
                             audio = self._codec.decode_streams(streams, seam_chunks)
                         else:
                             audio = self._codec.decode_streams(streams, seam_chunks,
-                                                               [f and r.rate is not None for r, f in zip(seam, seam_final)])
+                                                               [f and r.fx for r, f in zip(seam, seam_final)])
                         for r, a in zip(seam, audio):
-                            r.out.put(pcm16(a))
+                            if len(a) or not r.skw:     # (no frame of the time-scale stage completed: nothing to hand out)
+                                r.out.put(pcm16(a))
                     for r, c in zip(plain, plain_chunks):
-                        r.out.put(self._decode_pcm(c) if r.rate is None else self._decode_pcm(c, r.rate))
+                        r.out.put(self._decode_pcm(c) if not r.fx else self._decode_pcm(c, r.rate, **r.skw))
                     for r in wavs:
                         codes = r.utt.codes()
                         if not codes.shape[1]:
                             self._last_out(r, _Failed(RuntimeError("No audio generated")))
                         else:
-                            self._last_out(r, self._decode_wav(codes) if r.rate is None else self._decode_wav(codes, r.rate))
+                            self._last_out(r, self._decode_wav(codes) if not r.fx else self._decode_wav(codes, r.rate, **r.skw))
         except BaseException as e:  # noqa: BLE001
             self._fail(e)
         finally:

@@ -242,24 +242,24 @@ class FishTTS:
     def synthesize(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                    top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048) -> bytes:
         """Text -> WAV bytes (synthesizer.py:431-481).  While a BatchServer is open (serve()) the call joins its batch.
-        The reference's signature; synthesize_at also takes an output sample rate."""
+        The reference's signature; synthesize_at also takes an output sample rate and a speaking rate."""
         return self.synthesize_at(text, references, temperature, top_p, repetition_penalty, max_tokens)
 
     def synthesize_at(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                       top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
-                      sample_rate: Optional[int] = None) -> bytes:
+                      sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
         """Extension: synthesize() with the WAV at `sample_rate` (resampled on the GPU; None or 44100: the codec's own
         rate, byte for byte synthesize()'s result; an unsupported rate raises ValueError before any work -
-        codec_engine.output_rate)."""
+        codec_engine.output_rate) and at speaking rate `speed` (a factor in [0.5, 2.0], the waveform time-scaled on the
+        GPU at unchanged pitch before the resampler; None or 1.0: the model's own pace, byte for byte synthesize()'s
+        result; anything else raises ValueError before any work - codec_engine.output_speed)."""
         from .generation import generate_long
         from .serve import ServerClosed
-        rate = output_rate(sample_rate)
+        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed)
         srv = getattr(self, "_server", None)
         if srv is not None:
             try:
-                if rate is None:
-                    return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens)
-                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens, sample_rate=rate)
+                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens, **fx)
             except ServerClosed:
                 pass                          # closed meanwhile: served here, once the server has let go of _gen_lock
         prompt_text, prompt_tokens = self._get_prompt_data(references)
@@ -275,9 +275,9 @@ class FishTTS:
                     break
         if not codes_list:
             raise RuntimeError("No audio generated")
-        if rate is None:
+        if not fx:
             return self._decode_to_wav(np.concatenate(codes_list, axis=1))
-        return self._decode_to_wav(np.concatenate(codes_list, axis=1), rate)
+        return self._decode_to_wav(np.concatenate(codes_list, axis=1), rate, fx.get("speed"))
 
     def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
                           repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]]):
@@ -315,13 +315,13 @@ class FishTTS:
     def synthesize_batch(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
                          temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
                          max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None,
-                         sample_rate: Optional[int] = None) -> List[bytes]:
+                         sample_rate: Optional[int] = None, speed: Optional[float] = None) -> List[bytes]:
         """Extension (BASELINE configs[2]): many texts -> WAV bytes each, decoded `max_batch` at a time in lock step
         with refill (fish_tts_amd.batch); utterance i uses seed + i, or seeds[i] when `seeds` is given (a sharded run
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
-        semantics as synthesize(), `sample_rate` included."""
+        semantics as synthesize(), `sample_rate` and `speed` (as synthesize_at) included."""
         from .batch import run_batch, run_batch_streams
-        rate = output_rate(sample_rate)
+        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed)
         self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
@@ -335,14 +335,15 @@ class FishTTS:
             codes = u.codes()
             if codes.shape[1] == 0:
                 raise RuntimeError("No audio generated")
-            out.append(self._decode_to_wav(codes) if rate is None else self._decode_to_wav(codes, rate))
+            out.append(self._decode_to_wav(codes) if not fx else self._decode_to_wav(codes, rate, fx.get("speed")))
         return out
 
     def synthesize_batch_stream(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
                                 chunk_tokens: int = 20, min_first_chunk: int = 10, temperature: float = 0.7,
                                 top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
                                 seed: int = 0, seeds: Optional[List[int]] = None,
-                                sample_rate: Optional[int] = None) -> Iterator[Tuple[int, bytes]]:
+                                sample_rate: Optional[int] = None,
+                                speed: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
         """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
         PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
         `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
@@ -352,10 +353,12 @@ class FishTTS:
         (CodecHipEngine.decode_streams, one chunk per utterance).  Generation holds _gen_lock on its own thread;
         abandoning the generator stops it within one burst and releases the lock (fish_tts_amd.batch_stream).
         `sample_rate` (as synthesize_at): each utterance's stream resamples on the GPU; the chunk before its (i, b"") holds
-        the resampler's tail, so its PCM concatenates to the resampled waveform of one streamed decode."""
+        the resampler's tail, so its PCM concatenates to the resampled waveform of one streamed decode.
+        `speed` (as synthesize_at): each utterance's stream is time-scaled on the GPU through one carried stage (before
+        the resampler, if any); the chunk before its (i, b"") holds the tail in the same way."""
         from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
-        rate = output_rate(sample_rate)
+        fx = _fx(sample_rate, speed)
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
@@ -370,11 +373,8 @@ class FishTTS:
                 else:
                     run_batch(self._engine, utts, on_frames=on_frames, on_done=on_done)
 
-        if rate is None:
-            return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
-                                     min_first_chunk=min_first_chunk)
         return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
-                                 min_first_chunk=min_first_chunk, sample_rate=rate)
+                                 min_first_chunk=min_first_chunk, **fx)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
@@ -395,10 +395,16 @@ class FishTTS:
 
         Extension `sample_rate=` (keyword, as synthesize_at; checked at the first next()): seamless=False chunks are
         resampled each on its own, as independent waveforms; a seamless stream resamples through one carried resampler
-        (a last PCM chunk holds its tail), so its chunks concatenate to the resampled waveform of one streamed decode."""
+        (a last PCM chunk holds its tail), so its chunks concatenate to the resampled waveform of one streamed decode.
+
+        Extension `speed=` (keyword, as synthesize_at; checked at the first next()): seamless=False chunks are time-scaled
+        each on its own, as independent waveforms; a seamless stream runs one carried time-scale stage (in front of the
+        resampler, if any; a last PCM chunk holds the tail), so its chunks concatenate to the time-scaled waveform of one
+        streamed decode."""
         from .generation import generate_long
         from .serve import ServerClosed
-        rate = output_rate(kwargs.get("sample_rate"))
+        rate, fx = output_rate(kwargs.get("sample_rate")), _fx(kwargs.get("sample_rate"), kwargs.get("speed"))
+        spd = fx.get("speed")
         srv = getattr(self, "_server", None)
         if srv is not None:
             chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, **kwargs)
@@ -428,23 +434,25 @@ class FishTTS:
                 if seamless:
                     if self._vocoder is None:
                         raise RuntimeError("Vocoder not loaded")
-                    stream = self._vocoder.stream(rate)  # carried state: K/V of the last 127 frames, conv tails
+                    stream = self._vocoder.stream(rate, spd)  # carried state: K/V of the last 127 frames, conv tails
                 while True:
                     codes = codes_queue.get()
                     if codes is None:
                         break
                     if stream is None:
-                        audio_queue.put(self._decode_to_pcm(codes) if rate is None else self._decode_to_pcm(codes, rate))
+                        audio_queue.put(self._decode_to_pcm(codes) if not fx else self._decode_to_pcm(codes, rate, spd))
                     else:
                         codes = np.asarray(codes)
                         if stream.frames + codes.shape[1] > self._vocoder.max_frames:   # the rotation table ends here
-                            if rate is not None:                # the old stream's resampler tail first
+                            if fx:                              # the old stream's output-stage tail first
                                 audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())
                             stream.close()
-                            stream = self._vocoder.stream(rate)
-                        audio_queue.put((stream.decode(codes) * 32767).astype(np.int16).tobytes())
-                if stream is not None and rate is not None:
-                    audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())   # the resampler's tail
+                            stream = self._vocoder.stream(rate, spd)
+                        audio = stream.decode(codes)
+                        if len(audio) or spd is None:   # (no frame of the time-scale stage completed: nothing to hand out)
+                            audio_queue.put((audio * 32767).astype(np.int16).tobytes())
+                if stream is not None and fx:
+                    audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())   # the output stages' tail
             except Exception as e:  # noqa: BLE001
                 error_holder.append(e)
             finally:
@@ -595,21 +603,28 @@ class FishTTS:
         return Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seed), n_prefix
 
     # ------------------------------------------------------------------ codes -> audio (synthesizer.py:586-648)
-    def _decode_to_wav(self, codes: np.ndarray, sample_rate: Optional[int] = None) -> bytes:
-        if sample_rate is None:
+    def _decode_to_wav(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
+        if sample_rate is None and speed is None:
             return self._to_wav_bytes(self._decode_codes(codes))
-        return self._to_wav_bytes(self._decode_codes(codes, sample_rate), sample_rate)
+        if speed is None:
+            return self._to_wav_bytes(self._decode_codes(codes, sample_rate), sample_rate)
+        return self._to_wav_bytes(self._decode_codes(codes, sample_rate, speed), self.sample_rate if sample_rate is None else sample_rate)
 
-    def _decode_to_pcm(self, codes: np.ndarray, sample_rate: Optional[int] = None) -> bytes:
-        audio = self._decode_codes(codes) if sample_rate is None else self._decode_codes(codes, sample_rate)
+    def _decode_to_pcm(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
+        if speed is not None:
+            audio = self._decode_codes(codes, sample_rate, speed)
+        else:
+            audio = self._decode_codes(codes) if sample_rate is None else self._decode_codes(codes, sample_rate)
         return (audio * 32767).astype(np.int16).tobytes()  # no clip on the PCM path (synthesizer.py:594)
 
-    def _decode_codes(self, codes: np.ndarray, sample_rate: Optional[int] = None) -> np.ndarray:
+    def _decode_codes(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> np.ndarray:
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
+        if speed is not None:
+            return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate, speed=speed), axis=0)
         if sample_rate is None:
             return np.squeeze(self._vocoder.decode(codes))
         return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate), axis=0)
@@ -639,6 +654,24 @@ def output_rate(sample_rate: Optional[int]) -> Optional[int]:
     """codec_engine.output_rate (imported when first needed, as the engines are)."""
     from .codec_engine import output_rate as check
     return check(sample_rate)
+
+
+def output_speed(speed: Optional[float]) -> Optional[float]:
+    """codec_engine.output_speed as a factor: None for the model's own pace, else the accepted percentage / 100."""
+    from .codec_engine import output_speed as check
+    pct = check(speed)
+    return None if pct is None else pct / 100.0
+
+
+def _fx(sample_rate, speed) -> dict:
+    """The checked output keywords of a call, absent ones left out: {} is the path without output stages."""
+    rate, spd = output_rate(sample_rate), output_speed(speed)
+    fx = {}
+    if rate is not None:
+        fx["sample_rate"] = rate
+    if spd is not None:
+        fx["speed"] = spd
+    return fx
 
 
 def get_instance(model_dir=None, device: Literal["cpu", "cuda"] = "cuda",

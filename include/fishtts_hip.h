@@ -210,6 +210,37 @@ ft_status ft_codec_stream_begin_at(ft_ctx* ctx, int32_t sample_rate, ft_codec_st
  * ft_codec_stream_decode_many, before any device work, every stream unchanged. */
 ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
                                          const int32_t* lens, const int32_t* final, float* audio, int64_t* out_lens);
+/* Speaking rate.  The model draws its own durations, so these calls change the pace of the codec's waveform instead: a
+ * pitch-preserving time-scale stage (WSOLA, waveform-similarity overlap-add) on the device, at the codec's 44100 Hz,
+ * between the codec and the resampler.  speed_pct is an integer percentage in [50, 200] (anything else: FT_ERR_ARG before
+ * any device work); 100 means the stage is absent, and the call is then ft_codec_decode_at / ft_codec_stream_begin_at.
+ * The algorithm, with N = 1024 (window), HS = 512 (synthesis hop), D = 384 (alignment tolerance, +-8.7 ms) and
+ * w[i] = 0.5 (1 - cos(2 pi i / N)), so that w[i] + w[i + HS] = 1:
+ *   the input is x[0 .. n_in), zero outside; n_out = ceil(100 n_in / pct); frames k = 0 .. K-1, K = ceil(n_out / HS) + 1;
+ *   a_k = floor(k HS pct / 100); frame k reads x[s_k + i], i in [0, N), s_k = a_k - HS + d_k, and adds w[i] x[s_k + i]
+ *   to output (k - 1) HS + i (positions below 0 or from n_out on are dropped);
+ *   d_0 = 0; for k >= 1, d_k is the d in [-D, D] that maximises c(d) = sum_{i<N} x[a_k - HS + d + i] x[s_{k-1} + HS + i],
+ *   the plain cross-correlation with the natural continuation of frame k - 1; the lowest d wins a tie.  The sums are
+ *   float32 (fused multiply-adds), over i ascending.
+ * Emission (what makes the chunking irrelevant): a stream runs frame k once the input seen so far reaches
+ * max(a_k, a_{k-1} + HS) + HS + D - the end of the frame's search region and of its template, the latter lying further on
+ * below speed 1; after frame k the outputs below k HS are final and are emitted.  final runs the remaining frames with
+ * zeros past the end; the stream's outputs then number n_out exactly.  A stream carries on the device the input samples a
+ * later frame can still read (at most N + 2 D + 2 HS), s_{k-1} and the HS half-overlapped outputs, two copies each (a call
+ * reads one and writes the other); k and the sample counters live on the host.  With a sample rate as well, the
+ * resampler runs over the time-scaled samples (its input count is theirs).  The first time-scaled call allocates the
+ * stage's buffers for speed 0.5: 2 max_frames frame_len float32 (plus 64 streams' hold-back), and a resampler output
+ * buffer for that many input samples. */
+/* Host only: ceil(100 n_in / speed_pct); -1 for a refused speed_pct. */
+int64_t ft_timescaled_len(int32_t speed_pct, int64_t n_in);
+/* ft_codec_decode_at at speed_pct: out_lens[b] = ft_resampled_len(sample_rate, ft_timescaled_len(speed_pct, lens[b] *
+ * frame_len)); audio: B x max(out_lens) float32 (host).  ft_codec_decode_at is this call with speed_pct = 100. */
+ft_status ft_codec_decode_fx(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                             int32_t sample_rate, int32_t speed_pct, float* audio, int64_t* out_lens);
+/* ft_codec_stream_begin_at at speed_pct.  ft_codec_stream_decode_many_at serves such streams, mixed with any others in one
+ * call (one workgroup of the stage per time-scaled stream); final and tail-only chunks behave as for the resampler, also at
+ * 44100.  ft_codec_stream_decode and ft_codec_stream_decode_many refuse them (FT_ERR_STATE). */
+ft_status ft_codec_stream_begin_fx(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, ft_codec_stream** out);
 /* Codec encode = vocoder.encode(audio, lengths) of encode_reference (synthesizer.py:325-357, vocoder.py:885-904):
  * mono f32 audio at the codec sample rate (host), right-padded to whole frames -> codes (num_codebooks+1) x T'
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */

@@ -49,6 +49,12 @@ ft_status ft_test_sample(ft_ctx* ctx, const float* logits, int32_t cb, const ft_
  * (zeros before and after it) -> y: *n_out = ft_resampled_len(sample_rate, n) samples. */
 ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out);
 
+/* Test hook: the time-scale stage of ft_codec_decode_fx alone on a host waveform x of n <= max_frames * frame_len samples
+ * at 44100 -> y: *n_out = ft_timescaled_len(speed_pct, n) samples; deltas (may be NULL) receives the chosen d_k of the
+ * *n_frames = ceil(*n_out / 512) + 1 frames. */
+ft_status ft_test_timescale(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, float* y, int64_t* n_out,
+                            int32_t* deltas, int32_t* n_frames);
+
 /* Test hook: a launch trace of the codec.  ft_test_codec_trace_arm makes the NEXT ft_codec_decode (B = 1; any other
  * B disarms it untraced) or ft_codec_encode on this context record one entry per kernel launch of the one-shot path, in
  * launch order: a stable stage name ("post.2.wo", "up.1.pw1", "dec.3.u2.c7", "enc.2.sc", ...), the rows and columns

@@ -56,6 +56,7 @@ def main():
     ap.add_argument("--burst", type=int, default=8)
     ap.add_argument("--no-serial", action="store_true")
     ap.add_argument("--sample-rate", type=int, default=None)
+    ap.add_argument("--speed", type=float, default=None)
     a = ap.parse_args()
     import fish_tts_amd as ft
     from fish_tts_amd.config import s1_mini_args
@@ -66,8 +67,11 @@ def main():
     kw = {} if a.sample_rate is None else {"sample_rate": a.sample_rate}
     if a.sample_rate is not None:
         fl = fl * a.sample_rate / 44100
+    if a.speed is not None:
+        kw["speed"] = a.speed
+        fl = fl / a.speed
     print(f"s1-mini shapes, synthetic weights, max_batch 32; {a.n} streaming requests x {a.frames} frames, Poisson arrivals; "
-          f"output rate {a.sample_rate or 44100} Hz; frames: {synth._engine.frame_path()}", flush=True)
+          f"output rate {a.sample_rate or 44100} Hz, speed {a.speed or 1.0}; frames: {synth._engine.frame_path()}", flush=True)
     rng = np.random.default_rng(0)
     texts = [" ".join(f"word{j}" for j in range(int(k))) for k in rng.integers(4, 24, a.n)]
     list(synth.synthesize_stream(texts[0], max_tokens=16))           # warm-up: graphs, codec
