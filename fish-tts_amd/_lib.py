@@ -84,6 +84,11 @@ SYMBOLS = {
     "ft_codec_decode_fx": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "ft_codec_stream_begin_fx": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "ft_test_timescale": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
+    "ft_pitch_filter": (C.c_int32, [C.c_int32, _P, _P, _P]),
+    "ft_pitch_ok": (C.c_int32, [C.c_int32, C.c_int32]),
+    "ft_codec_decode_fxp": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "ft_codec_stream_begin_fxp": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ft_test_pitch": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ft_codec_encode": (C.c_int32, [_P, _P, C.c_int64, _P, _P]),
     "ft_codec_enc_frame_len": (C.c_int32, [_P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),

@@ -16,7 +16,8 @@ would pass `max_frames` starts afresh (as synthesize_stream does).
 With `sample_rate` the streams are `stream(sample_rate)` (their output resampled on the device) and decode_streams takes
 one final flag per chunk: an utterance's last chunk is decoded with final=True, or, when its end is known only after its
 last chunk went out, the stream's `finish()` gives the held-back tail; either way the tail is out before (i, b"").
-`speed` (a speaking rate) is passed through to the streams in the same way: `stream(sample_rate, speed=speed)`."""
+`speed` (a speaking rate) and `pitch` (a shift in semitones) are passed through to the streams in the same way:
+`stream(sample_rate, speed=speed, pitch=pitch)`, each keyword only when set."""
 from __future__ import annotations
 
 import queue
@@ -71,15 +72,15 @@ class ChunkCutter:
 
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                       min_first_chunk: int = 10, sample_rate: Optional[int] = None,
-                      speed: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
+                      speed: Optional[float] = None, pitch: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
     """Yields (i, pcm) chunks of the n utterances `run` generates, in the order they become ready, and (i, b"") once
     after utterance i's last chunk.  `run` is called on a producer thread, the codec on a worker thread; abandoning the
     generator stops the producer at its next block of frames and joins both threads.  An exception of either thread is
     raised from the generator."""
     if chunk_tokens < 1 or min_first_chunk < 1:
         raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-    fx = sample_rate is not None or speed is not None       # an output stage holds back a tail
-    skw = {} if speed is None else {"speed": speed}
+    fx = sample_rate is not None or speed is not None or pitch is not None      # an output stage holds back a tail
+    skw = {k: v for k, v in (("speed", speed), ("pitch", pitch)) if v is not None}
     cv = threading.Condition()
     cuts = [ChunkCutter(chunk_tokens, min_first_chunk) for _ in range(n)]
     ended = [False] * n                                 # end mark handed out (worker only)
@@ -161,7 +162,7 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                 else:
                     audio = codec.decode_streams([streams[i] for i in batch], chunks, final)
                 for i, a in zip(batch, audio):
-                    if len(a) or not skw:               # (a chunk that completes no frame of the time-scale stage gives
+                    if len(a) or not skw:               # (a chunk that completes nothing in the time-scale or pitch stage gives
                         out.put((i, pcm16(a)))          # no samples yet: (i, b"") is the end mark alone)
         except BaseException as e:  # noqa: BLE001
             errors.append(e)

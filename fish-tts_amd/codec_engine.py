@@ -60,6 +60,32 @@ def timescaled_len(speed, n: int) -> int:
     return int(n) if pct is None else int(L.load().ft_timescaled_len(pct, int(n)))
 
 
+def output_pitch(pitch) -> Optional[int]:
+    """A caller's `pitch=`: None for the model's own pitch (None, or a value that rounds to 0 cents: no pitch stage), else
+    the shift in cents, round(100 * pitch), for a pitch in semitones in [-12, 12] (ft_pitch_filter).  The shift is a plain
+    one: formants move with the pitch.  Anything else raises ValueError (before any device work)."""
+    if pitch is None:
+        return None
+    if isinstance(pitch, bool) or not isinstance(pitch, (int, float, np.integer, np.floating)):
+        raise ValueError(f"pitch must be a number of semitones, got {pitch!r}")
+    v = float(pitch)
+    if not -12.0 <= v <= 12.0:      # (a nan fails both comparisons)
+        raise ValueError(f"unsupported pitch {pitch!r}: semitones in [-12, 12]")
+    cents = int(round(v * 100))
+    return None if cents == 0 else cents
+
+
+def output_fx(speed, pitch):
+    """(pct, cents) of a caller's `speed=` and `pitch=` (output_speed, output_pitch), checked together (ft_pitch_ok): the
+    time-scale stage under a pitch shift runs at speed / 2^(pitch / 12), which has to lie in [0.5, 2].  ValueError
+    otherwise (before any device work)."""
+    pct, cents = output_speed(speed), output_pitch(pitch)
+    if cents is not None and L.load().ft_pitch_ok(100 if pct is None else pct, cents) != L.FT_OK:
+        raise ValueError(f"unsupported combination speed={speed!r}, pitch={pitch!r}: speed / 2^(pitch / 12) must lie in "
+                         "[0.5, 2.0]")
+    return pct, cents
+
+
 def _out_len(rate: Optional[int], pct: Optional[int], n: int) -> int:
     """n codec samples after the time-scale stage (pct) and the resampler (rate), either of them None: absent."""
     lib = L.load()
@@ -246,13 +272,16 @@ class CodecHipEngine:
             launches.append(rec)
         return res, launches
 
-    def stream(self, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> "CodecStream":
+    def stream(self, sample_rate: Optional[int] = None, speed: Optional[float] = None,
+               pitch: Optional[float] = None) -> "CodecStream":
         """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode.
         `sample_rate` (output_rate): the stream's output is resampled on the device; it holds back the samples whose
         filter taps reach past the input so far, until a later chunk, decode(final=True) or finish().
         `speed` (output_speed): the waveform is time-scaled on the device first; the stream holds back the samples that
-        a later frame of the stage still adds to, in the same way."""
-        return CodecStream(self, sample_rate, speed)
+        a later frame of the stage still adds to, in the same way.
+        `pitch` (output_pitch, semitones): the waveform is pitch-shifted on the device (a plain shift: formants move with
+        the pitch) between the two; the stream's length does not change."""
+        return CodecStream(self, sample_rate, speed, pitch)
 
     MAX_STREAMS_PER_CALL = 64     # ft_codec_stream_decode_many
 
@@ -278,7 +307,7 @@ class CodecHipEngine:
         call (ft_codec_stream_decode_many): chunks[j] (n_codebooks+1, T_j) integer -> float32 (T_j * frame_len,), bit
         for bit what streams[j].decode(chunks[j]) gives.  More than 64 streams, or more than max_frames frames together,
         take several calls (the streams of calls that went through stay advanced if a later one fails).
-        Streams at other rates or speeds (stream(sample_rate=..., speed=...)) may be mixed in
+        Streams at other rates, speeds or pitches (stream(sample_rate=..., speed=..., pitch=...)) may be mixed in
         (ft_codec_stream_decode_many_at): theirs are the time-scaled / resampled samples the chunk completes, bit for
         bit what streams[j].decode(chunks[j], final[j]) gives;
         final[j] also emits the stream's tail and closes it for decoding (a chunk of 0 frames is allowed then)."""
@@ -288,7 +317,7 @@ class CodecHipEngine:
             raise ValueError("decode_streams: one chunk per stream")
         for c in chunks:
             assert c.ndim == 2 and c.shape[0] == self.R, c.shape
-        if final is not None or any(s.rate is not None or s.pct is not None for s in streams):
+        if final is not None or any(s.rate is not None or s.pct is not None or s.cents is not None for s in streams):
             return self._decode_streams_at(streams, chunks, [False] * len(streams) if final is None else list(final))
         out: List[np.ndarray] = []
         for _, _, group, lens, codes, handles in self._stream_groups(streams, chunks):
@@ -347,14 +376,32 @@ class CodecHipEngine:
                                                C.byref(n), d.ctypes.data_as(C.c_void_p), C.byref(k)), "ft_test_timescale")
         return y[:n.value], d[:k.value]
 
+    def test_pitch(self, x: np.ndarray, speed_pct: int, cents: int):
+        """Test hook (ft_test_pitch): the time-scale stage at its rational rate and the pitch stage on a waveform at the
+        codec rate (zeros around it).  Returns (y, mid, d): the timescaled_len samples, the time-scaled intermediate the
+        pitch stage read (x itself where that stage is absent) and the alignments d_k of its frames (none then)."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        pct, cents = int(speed_pct), int(cents)
+        y = np.empty(max(1, -(-100 * len(x) // max(pct, 1))), dtype=np.float32)
+        mid = np.empty(2 * len(x) + 1, dtype=np.float32)
+        d = np.zeros((len(mid) + 511) // 512 + 1, dtype=np.int32)
+        n, m, k = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._check(self.lib.ft_test_pitch(self._h, x.ctypes.data_as(C.c_void_p), len(x), pct, cents, y.ctypes.data_as(C.c_void_p),
+                                           C.byref(n), mid.ctypes.data_as(C.c_void_p), C.byref(m), d.ctypes.data_as(C.c_void_p),
+                                           C.byref(k)), "ft_test_pitch")
+        return y[:n.value], mid[:m.value], d[:k.value]
+
     def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, sample_rate: Optional[int] = None,
-               speed: Optional[float] = None) -> np.ndarray:
+               speed: Optional[float] = None, pitch: Optional[float] = None) -> np.ndarray:
         """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len).
         `sample_rate` (output_rate): resampled on the device, (B, max_b resampled_len(lens[b] * frame_len)); row b holds
         resampled_len(sample_rate, lens[b] * frame_len) samples, zeros after them.
         `speed` (output_speed): time-scaled on the device (before the resampler); row b holds the timescaled_len - then
-        resampled_len - of its samples, zeros after them."""
-        rate, pct = output_rate(sample_rate), output_speed(speed)
+        resampled_len - of its samples, zeros after them.
+        `pitch` (output_pitch, semitones): pitch-shifted on the device, between the two; a plain shift (formants move with
+        the pitch) that leaves every length as it is."""
+        rate = output_rate(sample_rate)
+        pct, cents = output_fx(speed, pitch)
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
@@ -362,6 +409,16 @@ class CodecHipEngine:
         B, R, T = codes.shape
         assert R == self.R, codes.shape
         lens_a = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
+        if cents is not None:
+            width = max(_out_len(rate, pct, int(n) * self.frame_len) for n in lens_a)
+            audio = np.empty((B, max(width, 1)), dtype=np.float32)
+            out_lens = np.zeros(B, dtype=np.int64)
+            self._check(self.lib.ft_codec_decode_fxp(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
+                                                     lens_a.ctypes.data_as(C.c_void_p), CODEC_RATE if rate is None else rate,
+                                                     100 if pct is None else pct, cents,
+                                                     audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
+                        "ft_codec_decode_fxp")
+            return audio[:, :width]
         if pct is not None:
             width = max(_out_len(rate, pct, int(n) * self.frame_len) for n in lens_a)
             audio = np.empty((B, max(width, 1)), dtype=np.float32)
@@ -392,12 +449,17 @@ class CodecStream:
     here the causal codec's context - the last 127 frames' K/V of every transformer layer, the last rows of every
     convolution input - is carried)."""
 
-    def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None, speed: Optional[float] = None):
+    def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                 pitch: Optional[float] = None):
         self.engine = engine
         self.rate = output_rate(sample_rate)      # None: the codec's own rate
-        self.pct = output_speed(speed)            # None: the model's own pace
+        self.pct, self.cents = output_fx(speed, pitch)   # None: the model's own pace / pitch
         self._h = C.c_void_p()
-        if self.pct is not None:
+        if self.cents is not None:
+            engine._check(engine.lib.ft_codec_stream_begin_fxp(engine._h, CODEC_RATE if self.rate is None else self.rate,
+                                                               100 if self.pct is None else self.pct, self.cents,
+                                                               C.byref(self._h)), "ft_codec_stream_begin_fxp")
+        elif self.pct is not None:
             engine._check(engine.lib.ft_codec_stream_begin_fx(engine._h, CODEC_RATE if self.rate is None else self.rate, self.pct,
                                                               C.byref(self._h)), "ft_codec_stream_begin_fx")
         elif self.rate is None:
@@ -405,25 +467,30 @@ class CodecStream:
         else:
             engine._check(engine.lib.ft_codec_stream_begin_at(engine._h, self.rate, C.byref(self._h)), "ft_codec_stream_begin_at")
         self.frames = 0
-        self.samples_out = 0       # samples handed out so far (a stream at another rate or speed)
+        self.samples_out = 0       # samples handed out so far (a stream at another rate, speed or pitch)
         self.finished = False      # its tail went out: no further chunk
         engine._streams.add(self)      # the engine ends its open streams before it destroys the native context
 
+    @property
+    def _plain(self) -> bool:
+        """The codec's own rate, pace and pitch: no output stage, nothing held back."""
+        return self.rate is None and self.pct is None and self.cents is None
+
     def _cap(self, n_in: int) -> int:
         """Most samples the next call can give for n_in more codec samples."""
-        if self.rate is None and self.pct is None:
+        if self._plain:
             return n_in
         return _out_len(self.rate, self.pct, self.frames * self.engine.frame_len + n_in) - self.samples_out
 
     def _advance(self, T: int, n_out: int, final: bool) -> None:
         self.frames += T
         self.samples_out += n_out
-        self.finished = self.finished or (final and (self.rate is not None or self.pct is not None))
+        self.finished = self.finished or (final and not self._plain)
 
     def finish(self) -> np.ndarray:
-        """The held-back tail of a stream at another rate or speed (the input taken as zero past its end); the stream
-        takes no further chunk.  Empty at the codec's own rate and pace, and once the tail went out."""
-        if (self.rate is None and self.pct is None) or self.finished:
+        """The held-back tail of a stream at another rate, speed or pitch (the input taken as zero past its end); the
+        stream takes no further chunk.  Empty at the codec's own rate, pace and pitch, and once the tail went out."""
+        if self._plain or self.finished:
             return np.zeros(0, dtype=np.float32)
         return self.engine.decode_streams([self], [np.zeros((self.engine.R, 0), dtype=np.int32)], [True])[0]
 
@@ -433,7 +500,7 @@ class CodecStream:
         e = self.engine
         codes = np.ascontiguousarray(np.asarray(codes), dtype=np.int32)
         assert codes.ndim == 2 and codes.shape[0] == e.R, codes.shape
-        if self.rate is not None or self.pct is not None:
+        if not self._plain:
             return e.decode_streams([self], [codes], [final])[0]
         T = codes.shape[1]
         audio = np.empty(T * e.frame_len, dtype=np.float32)

@@ -70,6 +70,12 @@ struct CodecState {
     size_t ts_cap = 0;
     TsSeg* ts_seg = nullptr;
     int* ts_delta = nullptr;
+    // pitch stage (ft_codec_decode_fxp, ft_codec_stream_begin_fxp): one [513][K] table per cents value, uploaded on its first
+    // use; an output buffer (the resampler's input then) and a segment table, allocated on the first pitched call
+    struct PsTab { long long S = 0; int K = 0; float* w = nullptr; };
+    std::map<int, PsTab> ps_tabs;
+    float* ps_out = nullptr;
+    PsSeg* ps_seg = nullptr;
     // ---- encode side
     struct EncUnit { float *a0, *a2; ConvW c7, c1; };
     struct EncBlock { EncUnit u[3]; float* a3; ConvW sc; int s, cin, cout; std::vector<TfLayer> tf; float* tf_norm = nullptr; };
@@ -701,9 +707,18 @@ struct ft_codec_stream {
     // the state after the last frame run (two copies each), the counters on the host.  The resampler's input is then the
     // time-scaled waveform: nin counts those samples.
     int pct = 0;
+    long long tnum = 0, tden = 0;                  // the stage's rate num / den (pct / 100 without a pitch shift)
     float *tcarry[2] = {nullptr, nullptr}, *tstate[2] = {nullptr, nullptr};
     int tpar = 0, tk = 0;                          // tk: frames run so far
     long long tin = 0, tbase = 0, tout = 0;        // codec samples seen, first one carried, time-scaled samples emitted
+    // pitched output (ft_codec_stream_begin_fxp; cents 0: none): the stage's last K input samples (two copies) and its
+    // input / output counters.  Its input is the time-scaled waveform (rate speed_pct 2^20 / (100 S): `pct` above is then
+    // set only if that stage runs), or the codec's where that rate is 1; the resampler's input is its output.
+    int cents = 0, speed = 100;                    // speed: speed_pct, which fixes the stage's output length
+    const CodecState::PsTab* ps = nullptr;
+    float* pcarry[2] = {nullptr, nullptr};
+    int ppar = 0;
+    long long pin = 0, pout = 0;
     std::vector<void*> owned;
 };
 
@@ -804,29 +819,33 @@ static ft_status rs_alloc(ft_ctx* ctx, bool wide = false) {
 // ---- time-scale stage (TsSeg, timescale_kernel; fishtts_hip.h states the algorithm)
 constexpr int TS_MIN_PCT = 50, TS_MAX_PCT = 200;
 static bool ts_ok(int pct) { return pct >= TS_MIN_PCT && pct <= TS_MAX_PCT; }
-static long long ts_len(int pct, long long n) { return (100 * n + pct - 1) / pct; }
-static long long ts_a(int pct, long long k) { return k * TS_HS * pct / 100; }
+// The stage runs at the rational rate num / den: pct / 100 for a speed alone, pct 2^20 / (100 S) under a pitch shift
+// (k HS num stays below 2^52 for any stream within max_frames).
+struct TsRate { long long num = 100, den = 100; };
+static long long ts_len(TsRate r, long long n) { return (n * r.den + r.num - 1) / r.num; }
+static long long ts_len(int pct, long long n) { return ts_len(TsRate{pct, 100}, n); }
+static long long ts_a(TsRate r, long long k) { return k * TS_HS * r.num / r.den; }
 // Input samples frame k needs to have been seen: its search region ends at a_k + HS + D, its template (the continuation
 // of frame k - 1) at most at a_{k-1} + D + N, which lies further on below speed 1.
-static long long ts_need(int pct, long long k) {
-    return std::max(ts_a(pct, k), k > 0 ? ts_a(pct, k - 1) + TS_HS : 0) + TS_HS + TS_D;
+static long long ts_need(TsRate r, long long k) {
+    return std::max(ts_a(r, k), k > 0 ? ts_a(r, k - 1) + TS_HS : 0) + TS_HS + TS_D;
 }
 struct TsPlan { int k1 = 0; long long out = 0, base = 0; };
 // What a stream that has run k0 frames does once it has seen `nin` samples: frames [k0, k1), outputs below `out` final,
 // input from `base` on kept for later frames.
-static TsPlan ts_plan(int pct, int k0, long long nin, bool final) {
+static TsPlan ts_plan(TsRate r, int k0, long long nin, bool final) {
     TsPlan p;
     if (final) {
-        p.out = ts_len(pct, nin);
+        p.out = ts_len(r, nin);
         p.k1 = (int)((p.out + TS_HS - 1) / TS_HS) + 1;
         p.base = nin;
         return p;
     }
     p.k1 = k0;
-    while (ts_need(pct, p.k1) <= nin) ++p.k1;
+    while (ts_need(r, p.k1) <= nin) ++p.k1;
     p.out = p.k1 > 0 ? (long long)(p.k1 - 1) * TS_HS : 0;
-    p.base = ts_a(pct, p.k1) - TS_HS - TS_D;
-    if (p.k1 > 0) p.base = std::min(p.base, ts_a(pct, p.k1 - 1) - TS_D);
+    p.base = ts_a(r, p.k1) - TS_HS - TS_D;
+    if (p.k1 > 0) p.base = std::min(p.base, ts_a(r, p.k1 - 1) - TS_D);
     p.base = std::max(p.base, 0LL);
     return p;
 }
@@ -855,18 +874,124 @@ static ft_status ts_alloc(ft_ctx* ctx) {
     return rs_alloc(ctx, true);
 }
 
-// Time-scales `segs` (their inputs written earlier on the codec's stream) into ts_out, back to back; segment g's output is
-// the input of resampler segment g.rsi.
-static ft_status ts_enqueue(ft_ctx* ctx, std::vector<TsSeg>& segs, std::vector<RsSeg>& rs) {
+// ---- pitch stage (PsSeg, pitch_kernel; fishtts_hip.h states it): the step S = llround(2^20 2^(cents / 1200)) and the
+// [513][K] table, a Kaiser-windowed sinc designed in float64 with the resampler's constants (75 dB, transition 0.07), cut off
+// at 0.465 min(1, 1 / r) cycles per input sample, r = S / 2^20; tap t of row p is the prototype at p / 512 + (K/2 - 1 - t).
+constexpr int PS_MAX_CENTS = 1200;
+static bool ps_design(int cents, long long* S, int* K, std::vector<float>* w) {
+    if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS) return false;
+    *S = std::llround(std::ldexp(std::exp2((double)cents / 1200.0), PS_SHIFT));
+    *K = 0;
+    if (cents == 0) return true;
+    const double A = 75.0, beta = 0.1102 * (A - 8.7), r = std::ldexp((double)*S, -PS_SHIFT);
+    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * std::max(1.0, r));
+    k += k & 1;
+    *K = k;
+    if (!w) return true;
+    const double fc = 0.465 * std::min(1.0, 1.0 / r), half = 0.5 * k, ib = bessel_i0(beta);
+    w->assign((size_t)(PS_PHASES + 1) * k, 0.f);
+    for (int p = 0; p <= PS_PHASES; ++p)
+        for (int t = 0; t < k; ++t) {
+            const double tau = (double)p / PS_PHASES + (double)(k / 2 - 1 - t), q = tau / half, x = M_PI * 2.0 * fc * tau;
+            const double sinc = tau == 0 ? 1.0 : std::sin(x) / x;
+            (*w)[(size_t)p * k + t] = (float)(2.0 * fc * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - q * q))) / ib);
+        }
+    return true;
+}
+
+// The stages in front of the resampler for (speed_pct, cents): the time-scale stage's rate, absent at rate 1.  Accepted:
+// cents in [-1200, 1200] and an effective rate speed_pct 2^20 / (100 S) in [0.5, 2].
+struct FxPlan { TsRate ts; bool has_ts = false; long long S = 0; };
+static bool fx_plan(int pct, int cents, FxPlan* out) {
+    FxPlan f;
+    int k;
+    if (!ts_ok(pct) || !ps_design(cents, &f.S, &k, nullptr)) return false;
+    f.ts = TsRate{(long long)pct << PS_SHIFT, 100 * f.S};
+    if (50 * f.S > f.ts.num || f.ts.num > 200 * f.S) return false;
+    f.has_ts = f.ts.num != f.ts.den;
+    if (cents == 0) f.ts = TsRate{pct, 100};   // the speed alone, as it always ran
+    if (out) *out = f;
+    return true;
+}
+
+// Outputs available after `nin` input samples: those whose taps all lie within them ((n S >> 20) + K/2 < nin); at the end of
+// the input (final) all `total` of them.
+static long long ps_ready(const CodecState::PsTab& t, long long nin, bool final, long long total) {
+    if (final) return total;
+    const long long a = nin - t.K / 2;
+    return a > 0 ? ((a << PS_SHIFT) + t.S - 1) / t.S : 0;
+}
+
+// The device table of `cents` (uploaded on its first use); the caller holds s->mu.
+static ft_status ps_table(ft_ctx* ctx, int cents, const CodecState::PsTab** out) {
     CodecState* s = ctx->codec;
+    auto it = s->ps_tabs.find(cents);
+    if (it == s->ps_tabs.end()) {
+        CodecState::PsTab t;
+        std::vector<float> w;
+        if (!ps_design(cents, &t.S, &t.K, &w) || t.K == 0) return ft_fail(ctx, FT_ERR_ARG, "pitch outside [-1200, 1200] cents");
+        FT_TRY(cmalloc(ctx, &t.w, w.size()));
+        FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        it = s->ps_tabs.emplace(cents, t).first;
+    }
+    *out = &it->second;
+    return FT_OK;
+}
+
+// The stage's output buffer (as wide as the time-scale stage's: speed 0.5) and segment table, allocated once, with the
+// time-scale stage's buffers (sized for rate 0.5 whatever the call's) and the wide resampler buffer behind them.
+static ft_status ps_alloc(ft_ctx* ctx) {
+    CodecState* s = ctx->codec;
+    FT_TRY(ts_alloc(ctx));
+    if (s->ps_seg) return FT_OK;
+    float* o = nullptr;
+    PsSeg* t = nullptr;
+    FT_TRY(cmalloc(ctx, &o, s->ts_cap));
+    FT_TRY(cmalloc(ctx, &t, (size_t)RS_MAX_SEGS));
+    s->ps_out = o;
+    s->ps_seg = t;
+    return FT_OK;
+}
+
+struct Fx {   // the output stages of a call: resampler segments, and the time-scale and pitch segments in front of some of them
+    std::vector<RsSeg> rs;
+    std::vector<TsSeg> ts;
+    std::vector<PsSeg> ps;
+};
+
+// Time-scales fx.ts (their inputs written earlier on the codec's stream) into ts_out, back to back; segment g's output is
+// the input of stream g.rsi's next stage: its pitch segment if it has one, else its resampler segment.
+static ft_status ts_enqueue(ft_ctx* ctx, Fx& fx) {
+    CodecState* s = ctx->codec;
+    std::vector<TsSeg>& segs = fx.ts;
     long long off = 0;
     for (TsSeg& g : segs) {
         g.y = s->ts_out + off;
-        rs[g.rsi].x = g.y;
+        const float** in = &fx.rs[g.rsi].x;
+        for (PsSeg& q : fx.ps)
+            if (q.rsi == g.rsi) in = &q.x;
+        *in = g.y;
         off += g.n_out;
     }
     FT_HIP(ctx, hipMemcpyAsync(s->ts_seg, segs.data(), segs.size() * sizeof(TsSeg), hipMemcpyHostToDevice, s->stream));
     timescale_kernel<<<dim3((unsigned)segs.size()), TS_THREADS, 0, s->stream>>>(s->ts_seg, s->ts_win);
+    return FT_OK;
+}
+
+// Pitch-shifts `segs` (their inputs written earlier on the codec's stream) into ps_out, back to back; segment g's output is
+// the input of resampler segment g.rsi.
+static ft_status ps_enqueue(ft_ctx* ctx, std::vector<PsSeg>& segs, std::vector<RsSeg>& rs) {
+    CodecState* s = ctx->codec;
+    long long off = 0, mx = 0;
+    for (PsSeg& g : segs) {
+        g.y = s->ps_out + off;
+        rs[g.rsi].x = g.y;
+        off += g.n_out;
+        mx = std::max(mx, (long long)g.n_out);
+    }
+    FT_HIP(ctx, hipMemcpyAsync(s->ps_seg, segs.data(), segs.size() * sizeof(PsSeg), hipMemcpyHostToDevice, s->stream));
+    const int gx = (int)std::max(1LL, std::min(2048LL, (mx + RS_THREADS - 1) / RS_THREADS));
+    pitch_kernel<<<dim3(gx, 1, (unsigned)segs.size()), RS_THREADS, 0, s->stream>>>(s->ps_seg);
     return FT_OK;
 }
 
@@ -1048,14 +1173,11 @@ static bool decode_chain(ft_ctx* ctx, const Layout& L) {
 // The end of a call that leaves samples: the time-scale stage and the resampler over `fx` (inputs written earlier on the stream) or the
 // plain copy of `plain` floats of s->audio, the call's one synchronize and the launch check; then every stream named moves
 // on by its chunk.
-struct Fx {   // the output stages of a call: resampler segments, and the time-scale segments in front of some of them
-    std::vector<RsSeg> rs;
-    std::vector<TsSeg> ts;
-};
 static ft_status call_tail(ft_ctx* ctx, Fx* fx, float* host, size_t plain, const char* what, int n = 0,
                            ft_codec_stream* const* scs = nullptr, const int32_t* lens = nullptr) {
     CodecState* s = ctx->codec;
-    if (fx && !fx->ts.empty()) FT_TRY(ts_enqueue(ctx, fx->ts, fx->rs));
+    if (fx && !fx->ts.empty()) FT_TRY(ts_enqueue(ctx, *fx));
+    if (fx && !fx->ps.empty()) FT_TRY(ps_enqueue(ctx, fx->ps, fx->rs));
     if (fx) FT_TRY(rs_enqueue(ctx, fx->rs, host));
     else FT_HIP(ctx, hipMemcpyAsync(host, s->audio, plain * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     FT_HIP(ctx, hipStreamSynchronize(s->stream));
@@ -1176,6 +1298,7 @@ extern "C" ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* sc, co
     if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: the stream belongs to another (or a destroyed) context");
     if (sc->rate) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
     if (sc->pct) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another speed (ft_codec_stream_decode_many_at)");
+    if (sc->ps) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another pitch (ft_codec_stream_decode_many_at)");
     const ft_codec_config& c = ctx->cc;
     if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: chunk longer than max_frames");
     if (sc->t0 + T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: stream longer than max_frames (rope table)");
@@ -1302,6 +1425,7 @@ static ft_status many_check(ft_ctx* ctx, const std::string& fn, int n, ft_codec_
         if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream belongs to another (or a destroyed) context");
         if (!at && sc->rate) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
         if (!at && sc->pct) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another speed (ft_codec_stream_decode_many_at)");
+        if (!at && sc->ps) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another pitch (ft_codec_stream_decode_many_at)");
         if (at && sc->finished) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream whose final chunk went out");
         for (int i = 0; i < j; ++i)
             if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, fn + ": a stream named twice");
@@ -1325,9 +1449,11 @@ extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_code
 }
 
 // The items of ft_codec_decode / ft_codec_decode_at, one after the other: item b's samples go to audio + b * stride, zeros
-// behind them.  `t`: the resampler's table (null, or K = 0: the codec's own rate); `pct`: the speed (100: no time-scale stage).
+// behind them.  `t`: the resampler's table (null, or K = 0: the codec's own rate); `pct`: the speed (100 and no pitch: no
+// time-scale stage); `pt`: the pitch stage's table (null: none), the time-scale stage then at the rate of `f`.
 static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int B, int T, const int32_t* lens, float* audio,
-                              size_t stride, const CodecState::RsTab* t, int64_t* out_lens, int pct = 100) {
+                              size_t stride, const CodecState::RsTab* t, int64_t* out_lens, int pct = 100,
+                              const CodecState::PsTab* pt = nullptr, const FxPlan* f = nullptr) {
     CodecState* s = ctx->codec;
     const int R = ctx->cc.n_codebooks + 1;
     for (int b = 0; b < B; ++b) {
@@ -1339,7 +1465,7 @@ static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t*
         if (out_lens) out_lens[b] = (int64_t)n_out;
         if (n_out < stride) memset(out + n_out, 0, (stride - n_out) * sizeof(float));
         if (Tb == 0) continue;
-        if ((!t || t->K == 0) && pct == 100) {
+        if ((!t || t->K == 0) && pct == 100 && !pt) {
             FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
             continue;
         }
@@ -1347,9 +1473,18 @@ static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t*
         Fx g;
         g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)n_ts, (int)n_out, 1, 1, 0, 0});
         if (t && t->K > 0) { g.rs[0].w = t->w; g.rs[0].L = t->L; g.rs[0].M = t->M; g.rs[0].K = t->K; }
-        if (pct != 100) {
-            const TsPlan p = ts_plan(pct, 0, (long long)n_in, true);
-            g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, (int)n_in, (int)n_ts, 0, p.k1, pct, 0});
+        if (pt) {   // the time-scale stage at the rate of f (or none), then the pitch stage back to n_ts samples
+            long long n_mid = (long long)n_in;
+            if (f->has_ts) {
+                const TsPlan p = ts_plan(f->ts, 0, (long long)n_in, true);
+                n_mid = p.out;
+                g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, f->ts.num, f->ts.den,
+                                     (int)n_in, (int)n_mid, 0, p.k1, 0, 0});
+            }
+            g.ps.assign(1, PsSeg{s->audio, pt->w, nullptr, nullptr, nullptr, 0, 0, pt->S, (int)n_mid, (int)n_ts, pt->K, 0});
+        } else if (pct != 100) {
+            const TsPlan p = ts_plan(TsRate{pct, 100}, 0, (long long)n_in, true);
+            g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, pct, 100, (int)n_in, (int)n_ts, 0, p.k1, 0, 0});
         }
         FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, &g));
     }
@@ -1401,11 +1536,36 @@ extern "C" int64_t ft_timescaled_len(int32_t speed_pct, int64_t n_in) {
     return n_in < 0 || !ts_ok(speed_pct) ? -1 : ts_len(speed_pct, n_in);
 }
 
+// cents and its combination with the speed (which ts_refuse judged on its own)
+static ft_status ps_refuse(ft_ctx* ctx, const std::string& fn, int pct, int cents, FxPlan* f) {
+    if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS)
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": pitch outside [-1200, 1200] cents (" + std::to_string(cents) + ")");
+    if (!fx_plan(pct, cents, f))
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": speed / pitch ratio outside [0.5, 2] (speed " + std::to_string(pct) + " percent, " +
+                                            std::to_string(cents) + " cents)");
+    return FT_OK;
+}
+
+extern "C" ft_status ft_pitch_filter(int32_t cents, int64_t* step, int32_t* K, float* table) {
+    long long S = 0;
+    int k = 0;
+    std::vector<float> w;
+    if (!ps_design(cents, &S, &k, table ? &w : nullptr)) return FT_ERR_ARG;
+    if (step) *step = S;
+    if (K) *K = k;
+    if (table && !w.empty()) memcpy(table, w.data(), w.size() * sizeof(float));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_pitch_ok(int32_t speed_pct, int32_t cents) { return fx_plan(speed_pct, cents, nullptr) ? FT_OK : FT_ERR_ARG; }
+
 static ft_status decode_fx(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
-                           int32_t sample_rate, int32_t pct, float* audio, int64_t* out_lens) {
+                           int32_t sample_rate, int32_t pct, float* audio, int64_t* out_lens, int32_t cents = 0) {
     if (!ctx) return FT_ERR_ARG;
     FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
     FT_TRY(ts_refuse(ctx, fn, pct));
+    FxPlan f;
+    FT_TRY(ps_refuse(ctx, fn, pct, cents, &f));
     FT_TRY(codec_ready(ctx));
     if (!codes || !audio || !out_lens || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
     if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
@@ -1420,9 +1580,13 @@ static ft_status decode_fx(ft_ctx* ctx, const std::string& fn, const int32_t* co
     FT_HIP(ctx, hipSetDevice(ctx->device));
     const CodecState::RsTab* t = nullptr;
     FT_TRY(rs_table(ctx, sample_rate, &t));
-    if (pct != 100) FT_TRY(ts_alloc(ctx));
+    const CodecState::PsTab* pt = nullptr;
+    if (cents != 0) {
+        FT_TRY(ps_table(ctx, cents, &pt));
+        FT_TRY(ps_alloc(ctx));
+    } else if (pct != 100) FT_TRY(ts_alloc(ctx));
     else if (t->K > 0) FT_TRY(rs_alloc(ctx));
-    return decode_items(ctx, fn, codes, B, T, lens, audio, (size_t)stride, t, out_lens, pct);
+    return decode_items(ctx, fn, codes, B, T, lens, audio, (size_t)stride, t, out_lens, pct, pt, &f);
 }
 
 extern "C" ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
@@ -1435,10 +1599,20 @@ extern "C" ft_status ft_codec_decode_fx(ft_ctx* ctx, const int32_t* codes, int32
     return decode_fx(ctx, "ft_codec_decode_fx", codes, B, T, lens, sample_rate, speed_pct, audio, out_lens);
 }
 
-static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sample_rate, int32_t pct, ft_codec_stream** out) {
+extern "C" ft_status ft_codec_decode_fxp(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                         int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, float* audio, int64_t* out_lens) {
+    return decode_fx(ctx, "ft_codec_decode_fxp", codes, B, T, lens, sample_rate, speed_pct, audio, out_lens, pitch_cents);
+}
+
+static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sample_rate, int32_t pct, ft_codec_stream** out,
+                                 int32_t cents = 0) {
     if (!ctx || !out) return FT_ERR_ARG;
     FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
     FT_TRY(ts_refuse(ctx, fn, pct));
+    FxPlan f;
+    FT_TRY(ps_refuse(ctx, fn, pct, cents, &f));
+    const bool has_ts = cents != 0 ? f.has_ts : pct != 100;
+    const CodecState::PsTab* pt = nullptr;
     FT_TRY(codec_ready(ctx));
     CodecState* s = ctx->codec;
     const CodecState::RsTab* t = nullptr;
@@ -1446,12 +1620,15 @@ static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sam
         std::lock_guard<std::mutex> lock(s->mu);
         FT_HIP(ctx, hipSetDevice(ctx->device));
         FT_TRY(rs_table(ctx, sample_rate, &t));
-        if (pct != 100) FT_TRY(ts_alloc(ctx));
+        if (cents != 0) {
+            FT_TRY(ps_table(ctx, cents, &pt));
+            FT_TRY(ps_alloc(ctx));
+        } else if (pct != 100) FT_TRY(ts_alloc(ctx));
         else if (t->K > 0) FT_TRY(rs_alloc(ctx));
     }
     ft_codec_stream* sc = nullptr;
     FT_TRY(ft_codec_stream_begin(ctx, &sc));
-    if (t->K == 0 && pct == 100) {
+    if (t->K == 0 && pct == 100 && !pt) {
         *out = sc;
         return FT_OK;
     }
@@ -1465,10 +1642,11 @@ static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sam
         ok = hipMemsetAsync(v, 0, n * sizeof(float), s->stream) == hipSuccess;   // the input before the first sample
     };
     for (int k = 0; k < 2 && t->K > 0; ++k) zalloc(&sc->rcarry[k], (size_t)t->K);
-    for (int k = 0; k < 2 && pct != 100; ++k) {
+    for (int k = 0; k < 2 && has_ts; ++k) {
         zalloc(&sc->tcarry[k], (size_t)TS_CARRY);
         zalloc(&sc->tstate[k], (size_t)TS_STATE);
     }
+    for (int k = 0; k < 2 && pt; ++k) zalloc(&sc->pcarry[k], (size_t)pt->K);
     ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
@@ -1479,7 +1657,16 @@ static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sam
         sc->rate = sample_rate;
         sc->rs = t;
     }
-    if (pct != 100) sc->pct = pct;
+    if (has_ts) {
+        sc->pct = pct;
+        sc->tnum = f.ts.num;
+        sc->tden = f.ts.den;
+    }
+    if (pt) {
+        sc->cents = cents;
+        sc->speed = pct;
+        sc->ps = pt;
+    }
     *out = sc;
     return FT_OK;
 }
@@ -1492,6 +1679,11 @@ extern "C" ft_status ft_codec_stream_begin_fx(ft_ctx* ctx, int32_t sample_rate, 
     return stream_begin_fx(ctx, "ft_codec_stream_begin_fx", sample_rate, speed_pct, out);
 }
 
+extern "C" ft_status ft_codec_stream_begin_fxp(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents,
+                                               ft_codec_stream** out) {
+    return stream_begin_fx(ctx, "ft_codec_stream_begin_fxp", sample_rate, speed_pct, out, pitch_cents);
+}
+
 extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
                                                     const int32_t* lens, const int32_t* final, float* audio, int64_t* out_lens) {
     if (!ctx) return FT_ERR_ARG;
@@ -1501,25 +1693,30 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     FT_TRY(many_check(ctx, "ft_codec_stream_decode_many_at", n, streams, lens, final, true));
     CodecState* s = ctx->codec;
     const int fl = s->frame_len;
-    long long total_out = 0, total_ts = 0;
+    long long total_out = 0, total_ts = 0, total_ps = 0;
     bool any_fx = false;
-    std::vector<long long> no(n);   // samples each stream gives out in this call
+    std::vector<long long> no(n), pn(n);   // samples each stream gives out in this call; those its pitch stage gives
     std::vector<TsPlan> tp(n);
     for (int j = 0; j < n; ++j) {
         const ft_codec_stream* sc = streams[j];
         const bool fin = final && final[j];
         long long nin = (long long)lens[j] * fl;   // samples into the resampler
         if (sc->pct) {
-            tp[j] = ts_plan(sc->pct, sc->tk, sc->tin + nin, fin);
+            tp[j] = ts_plan(TsRate{sc->tnum, sc->tden}, sc->tk, sc->tin + nin, fin);
             if (sc->tin + nin - tp[j].base > TS_CARRY) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: time-scale carry out of step");
             nin = tp[j].out - sc->tout;
             total_ts += nin;
         }
+        if (sc->ps) {   // its outputs number ft_timescaled_len(speed, codec samples) in the end, whatever its input's length
+            pn[j] = ps_ready(*sc->ps, sc->pin + nin, fin, ts_len(sc->speed, (long long)(sc->t0 + lens[j]) * fl)) - sc->pout;
+            nin = pn[j];
+            total_ps += nin;
+        }
         no[j] = sc->rs ? rs_ready(*sc->rs, sc->nin + nin, fin) - sc->nout : nin;
         total_out += no[j];
-        any_fx = any_fx || sc->rs || sc->pct;
+        any_fx = any_fx || sc->rs || sc->pct || sc->ps;
     }
-    if (any_fx && ((size_t)total_out > s->rs_cap || (size_t)total_ts > s->ts_cap))
+    if (any_fx && ((size_t)total_out > s->rs_cap || (size_t)total_ts > s->ts_cap || (size_t)total_ps > s->ts_cap))
         return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: output buffer");
     // the codec runs over the streams with frames (their code blocks are back to back, as the call's)
     std::vector<ft_codec_stream*> cs;
@@ -1544,7 +1741,12 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
             g.n_in = (int)(tp[j].out - sc->tout);
             fx.ts.push_back(TsSeg{s->audio + P * fl, sc->tcarry[sc->tpar], sc->tcarry[sc->tpar ^ 1], sc->tstate[sc->tpar],
                                   sc->tstate[sc->tpar ^ 1], nullptr, nullptr, sc->tin, sc->tbase, tp[j].base, sc->tout,
-                                  lens[j] * fl, g.n_in, sc->tk, tp[j].k1, sc->pct, j});
+                                  sc->tnum, sc->tden, lens[j] * fl, g.n_in, sc->tk, tp[j].k1, j, 0});
+        }
+        if (sc->ps) {   // between the two: it reads the time-scale stage's (or the codec's) samples, the resampler reads its
+            fx.ps.push_back(PsSeg{g.x, sc->ps->w, sc->pcarry[sc->ppar], sc->pcarry[sc->ppar ^ 1], nullptr, sc->pin, sc->pout,
+                                  sc->ps->S, g.n_in, (int)pn[j], sc->ps->K, j});
+            g.n_in = (int)pn[j];
         }
         if (sc->rs) {
             g.w = sc->rs->w; g.L = sc->rs->L; g.M = sc->rs->M; g.K = sc->rs->K;
@@ -1561,16 +1763,24 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     for (int j = 0; j < n; ++j) {
         ft_codec_stream* sc = streams[j];
         out_lens[j] = no[j];
-        if (!sc->rs && !sc->pct) continue;
+        if (!sc->rs && !sc->pct && !sc->ps) continue;
+        long long fed = (long long)lens[j] * fl;   // samples into the stage after the time-scale stage
+        if (sc->pct) fed = tp[j].out - sc->tout;
+        if (sc->ps) {
+            sc->pin += fed;
+            sc->pout += pn[j];
+            sc->ppar ^= 1;
+            fed = pn[j];
+        }
         if (sc->pct) {
-            sc->nin += tp[j].out - sc->tout;
+            sc->nin += fed;
             sc->tin += (long long)lens[j] * fl;
             sc->tout = tp[j].out;
             sc->tbase = tp[j].base;
             sc->tk = tp[j].k1;
             sc->tpar ^= 1;
         } else {
-            sc->nin += (long long)lens[j] * fl;
+            sc->nin += fed;
         }
         sc->nout += no[j];
         sc->rpar ^= 1;
@@ -1611,7 +1821,7 @@ extern "C" ft_status ft_test_timescale(ft_ctx* ctx, const float* x, int64_t n, i
     if (!x || !y || !n_out || n < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_timescale: bad argument");
     CodecState* s = ctx->codec;
     if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_timescale: longer than max_frames of audio");
-    const TsPlan p = ts_plan(speed_pct, 0, n, true);
+    const TsPlan p = ts_plan(TsRate{speed_pct, 100}, 0, n, true);
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
     FT_TRY(ts_alloc(ctx));
@@ -1620,9 +1830,44 @@ extern "C" ft_status ft_test_timescale(ft_ctx* ctx, const float* x, int64_t n, i
     FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     Fx g;
     g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)p.out, (int)p.out, 1, 1, 0, 0});
-    g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, s->ts_delta, 0, 0, 0, 0, (int)n, (int)p.out, 0, p.k1, speed_pct, 0});
+    g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, s->ts_delta, 0, 0, 0, 0, speed_pct, 100, (int)n, (int)p.out, 0, p.k1, 0, 0});
     FT_TRY(call_tail(ctx, &g, y, 0, "time-scale launch: "));
     if (deltas) FT_HIP(ctx, hipMemcpy(deltas, s->ts_delta, (size_t)p.k1 * sizeof(int), hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_pitch(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, int32_t cents, float* y, int64_t* n_out,
+                                   float* mid, int64_t* n_mid, int32_t* deltas, int32_t* n_frames) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(ts_refuse(ctx, "ft_test_pitch", speed_pct));
+    FxPlan f;
+    FT_TRY(ps_refuse(ctx, "ft_test_pitch", speed_pct, cents, &f));
+    FT_TRY(codec_ready(ctx));
+    if (!x || !y || !n_out || n < 1 || cents == 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pitch: bad argument");
+    CodecState* s = ctx->codec;
+    if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_pitch: longer than max_frames of audio");
+    const long long no = ts_len(speed_pct, n);
+    TsPlan p;
+    p.out = n;
+    if (f.has_ts) p = ts_plan(f.ts, 0, n, true);
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    const CodecState::PsTab* pt = nullptr;
+    FT_TRY(ps_table(ctx, cents, &pt));
+    FT_TRY(ps_alloc(ctx));
+    *n_out = no;
+    if (n_mid) *n_mid = p.out;
+    if (n_frames) *n_frames = p.k1;
+    FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    Fx g;
+    g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)no, (int)no, 1, 1, 0, 0});
+    if (f.has_ts)
+        g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, s->ts_delta, 0, 0, 0, 0, f.ts.num, f.ts.den,
+                             (int)n, (int)p.out, 0, p.k1, 0, 0});
+    g.ps.assign(1, PsSeg{s->audio, pt->w, nullptr, nullptr, nullptr, 0, 0, pt->S, (int)p.out, (int)no, pt->K, 0});
+    FT_TRY(call_tail(ctx, &g, y, 0, "pitch launch: "));
+    if (mid) FT_HIP(ctx, hipMemcpy(mid, f.has_ts ? s->ts_out : s->audio, (size_t)p.out * sizeof(float), hipMemcpyDeviceToHost));
+    if (deltas && p.k1 > 0) FT_HIP(ctx, hipMemcpy(deltas, s->ts_delta, (size_t)p.k1 * sizeof(int), hipMemcpyDeviceToHost));
     return FT_OK;
 }
 

@@ -1544,7 +1544,8 @@ static __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const RsSeg
 }
 
 // ---- WSOLA time-scale stage (ft_codec_decode_fx, ft_codec_stream_begin_fx; the algorithm is stated in fishtts_hip.h): at the
-// codec rate, speed pct / 100.  Frame k lies at a_k = floor(k HS pct / 100); it reads x[s_k + i], i < N, with
+// codec rate, at the rational rate num / den (a speed alone: pct / 100; under a pitch shift pct 2^20 / (100 S), see PsSeg).
+// Frame k lies at a_k = floor(k HS num / den); it reads x[s_k + i], i < N, with
 // s_k = a_k - HS + d_k, and adds w[i] x[s_k + i] to output (k - 1) HS + i.  d_k in [-D, D] maximises the plain
 // cross-correlation of the frame with the continuation of frame k - 1, x[s_{k-1} + HS + i]; the lowest d wins a tie.
 // The frames of a segment depend on each other through d_{k-1}: one workgroup walks one segment's frames in order, the
@@ -1569,7 +1570,8 @@ struct TsSeg {
     float* y;                // outputs [emit0, emit0 + n_out)
     int* deltas;             // d_k of frames [k0, k1) (the test hook); null: not kept
     long long nin, cbase_rd, cbase_wr, emit0;
-    int n_in, n_out, k0, k1, pct, rsi;   // rsi: host side only, the resampler segment that reads y
+    long long num, den;      // the rate num / den: a_k = floor(k HS num / den) (a speed alone: pct / 100)
+    int n_in, n_out, k0, k1, rsi, pad;   // rsi: host side only, the stream of the call whose next stage reads y
 };
 
 __device__ inline float ts_in(const TsSeg& s, long long i) {
@@ -1590,7 +1592,7 @@ static __global__ __launch_bounds__(TS_THREADS) void timescale_kernel(const TsSe
     if (t < 8) reg[TS_REG + t] = 0.f;
     int sprev = s.st_rd ? *reinterpret_cast<const int*>(s.st_rd + TS_HS) : 0;
     for (int k = s.k0; k < s.k1; ++k) {
-        const long long a = (long long)k * TS_HS * s.pct / 100;
+        const long long a = (long long)k * TS_HS * s.num / s.den;
         __syncthreads();   // the frame before has read reg, rv, ri
         for (int i = t; i < TS_REG; i += TS_THREADS) reg[i] = ts_in(s, a - TS_HS - TS_D + i);
         int c = TS_D;      // d_0 = 0
@@ -1653,6 +1655,65 @@ static __global__ __launch_bounds__(TS_THREADS) void timescale_kernel(const TsSe
     if (s.st_wr) {
         for (int i = t; i < TS_HS; i += TS_THREADS) s.st_wr[i] = ola[i];
         if (t == 0) *reinterpret_cast<int*>(s.st_wr + TS_HS) = sprev;
+    }
+}
+
+// ---- pitch stage (ft_codec_decode_fxp, ft_codec_stream_begin_fxp; stated in fishtts_hip.h): an arbitrary-ratio resampler
+// that reads its input faster by r = S / 2^20 and calls the result the same rate, behind a time-scale stage that stretched
+// the waveform by r.  Output n is the input at time n S / 2^20: with u = n S, i0 = u >> 20, p = (u >> 11) & 511,
+// f = (u & 2047) / 2048,
+//   y[n] = sum_{t < K} ((1 - f) w[p][t] + f w[p + 1][t]) * x[i0 - K/2 + 1 + t],
+// w [513][K] a Kaiser-windowed sinc at 512 phases per input sample (row 512: row 0 one tap on), linearly interpolated
+// between adjacent rows; summed in f32 over t ascending whatever the chunking and however many segments share the launch.
+// Segments, carry and the LDS stage as the resampler's: a block's 256 outputs span at most 255 * 2 + 2 inputs (r <= 2) plus
+// K <= 134 taps, well inside RS_LDS.
+struct PsSeg {
+    const float* x;          // input samples [nin, nin + n_in) (device; unused when n_in = 0)
+    const float* w;          // [513][K]
+    const float* carry_rd;   // input samples [nin - K, nin); null: zeros
+    float* carry_wr;         // receives input samples [nin + n_in - K, nin + n_in); null: not kept
+    float* y;                // outputs [nout, nout + n_out)
+    long long nin, nout, step;   // step: S
+    int n_in, n_out, K, rsi;     // rsi: host side only, the stream of the call whose resampler segment reads y
+};
+constexpr int PS_SHIFT = 20, PS_PHASES = 512, PS_FRAC = 2048;
+
+__device__ inline float ps_in(const PsSeg& s, long long i) {
+    if (i < s.nin) {
+        const long long c = i - (s.nin - s.K);
+        return s.carry_rd && c >= 0 ? s.carry_rd[c] : 0.f;
+    }
+    if (i < s.nin + s.n_in) return s.x[i - s.nin];
+    return 0.f;
+}
+
+static __global__ __launch_bounds__(RS_THREADS) void pitch_kernel(const PsSeg* segs) {
+    __shared__ float xs[RS_LDS];
+    const PsSeg s = segs[blockIdx.z];
+    if (blockIdx.x == 0 && s.carry_wr) {
+        const long long e = s.nin + s.n_in - s.K;
+        for (int k = threadIdx.x; k < s.K; k += RS_THREADS) s.carry_wr[k] = ps_in(s, e + k);
+    }
+    const int h = s.K / 2;
+    for (long b0 = (long)blockIdx.x * RS_THREADS; b0 < s.n_out; b0 += (long)gridDim.x * RS_THREADS) {
+        const long long na = s.nout + b0, nb = s.nout + min((long)s.n_out, b0 + RS_THREADS) - 1;
+        const long long ia = ((na * s.step) >> PS_SHIFT) - h + 1;
+        const int span = (int)(((nb * s.step) >> PS_SHIFT) + h - ia + 1);
+        __syncthreads();
+        for (int k = threadIdx.x; k < span && k < RS_LDS; k += RS_THREADS) xs[k] = ps_in(s, ia + k);
+        __syncthreads();
+        const long n = b0 + threadIdx.x;
+        if (n < s.n_out) {
+            const long long u = (s.nout + n) * s.step, i0 = u >> PS_SHIFT;
+            const int p = (int)(u >> 11) & (PS_PHASES - 1);
+            const float f = (float)(int)(u & (PS_FRAC - 1)) / (float)PS_FRAC, g = 1.f - f;
+            const float* w0 = s.w + (size_t)p * s.K;
+            const float* w1 = w0 + s.K;
+            const float* xp = xs + (i0 - h + 1 - ia);
+            float acc = 0.f;
+            for (int t = 0; t < s.K; ++t) acc += (g * w0[t] + f * w1[t]) * xp[t];
+            s.y[n] = acc;
+        }
     }
 }
 

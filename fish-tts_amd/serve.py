@@ -28,7 +28,8 @@ Requests may ask for another output rate (sample_rate=): their WAVs and zero-sta
 by one; their seamless streams resample through their CodecStream, in the same decode_streams call as every other ready
 chunk whatever its rate, the last chunk (or a finish() after it) giving the resampler's tail before the end mark.
 A speaking rate (speed=) travels the same way: WAVs and zero-state chunks are time-scaled on the device one by one, a
-seamless request runs one carried time-scale stage in its CodecStream, its tail out before the end mark.
+seamless request runs one carried time-scale stage in its CodecStream, its tail out before the end mark.  A pitch shift
+(pitch=, semitones) does too, through the carried pitch stage of the request's CodecStream.
 
 A native error in either thread fails every in-flight and queued request with that exception and closes the server."""
 from __future__ import annotations
@@ -95,16 +96,27 @@ def _output_speed(speed: Optional[float]) -> Optional[float]:
     return None if pct is None else pct / 100.0
 
 
+def _output_pitch(pitch: Optional[float], speed: Optional[float] = None) -> Optional[float]:
+    """codec_engine.output_fx's pitch in semitones: None for the model's own pitch, ValueError for an unsupported one or an
+    unsupported combination with `speed`."""
+    if pitch is None:
+        return None
+    from .codec_engine import output_fx
+    cents = output_fx(speed, pitch)[1]
+    return None if cents is None else cents / 100.0
+
+
 class _Request:
     """One synthesize / synthesize_stream call: its utterance, chunking and output queue."""
 
     def __init__(self, utt: Utterance, n_prefix: int, mode: str, chunk_tokens: int, min_first_chunk: int,
-                 rate: Optional[int] = None, speed: Optional[float] = None):
+                 rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None):
         self.utt, self.n_prefix, self.mode = utt, n_prefix, mode          # mode: "wav" | "seamless" | "chunks"
         self.rate = rate              # output sample rate (None: the codec's own)
         self.speed = speed            # speaking rate (None: the model's own pace)
-        self.fx = rate is not None or speed is not None       # an output stage holds back a tail
-        self.skw = {} if speed is None else {"speed": speed}
+        self.pitch = pitch            # pitch shift in semitones (None: the model's own pitch)
+        self.fx = rate is not None or speed is not None or pitch is not None      # an output stage holds back a tail
+        self.skw = {k: v for k, v in (("speed", speed), ("pitch", pitch)) if v is not None}
         self.cut = None if mode == "wav" else ChunkCutter(chunk_tokens, min_first_chunk, hold_back=mode == "seamless")
         self.out: "queue.Queue" = queue.Queue()
         self.cancelled = False        # the caller went away (or close(cancel=True))
@@ -164,48 +176,50 @@ class BatchServer:
 
     def synthesize(self, text: str, references=None, temperature: float = 0.7, top_p: float = 0.8,
                    repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
-                   sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
+                   sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                   pitch: Optional[float] = None) -> bytes:
         """Text -> WAV bytes: FishTTS.synthesize's result for seed 0 (draws with `seed`).  Safe from any number of threads;
-        `references=None` means the instance's set_references voices; `sample_rate` and `speed` as FishTTS.synthesize_at
-        (an unsupported one raises ValueError here, before anything is queued)."""
-        rate, spd = _output_rate(sample_rate), _output_speed(speed)
+        `references=None` means the instance's set_references voices; `sample_rate`, `speed` and `pitch` as
+        FishTTS.synthesize_at (an unsupported one raises ValueError here, before anything is queued)."""
+        rate, spd, pit = _output_rate(sample_rate), _output_speed(speed), _output_pitch(pitch, speed)
         utt, n_prefix = self._prepare(text, references, temperature, top_p, repetition_penalty, max_tokens, seed)
-        item = self.submit(utt, n_prefix, sample_rate=rate, speed=spd).out.get()
+        item = self.submit(utt, n_prefix, sample_rate=rate, speed=spd, pitch=pit).out.get()
         if isinstance(item, _Failed):
             raise item.error
         return item
 
     def synthesize_stream(self, text: str, references=None, chunk_tokens: int = 20, min_first_chunk: int = 10,
                           seamless: bool = False, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                          **sampling) -> Iterator[bytes]:
+                          pitch: Optional[float] = None, **sampling) -> Iterator[bytes]:
         """Yields int16 PCM chunks as FishTTS.synthesize_stream does: seamless=False (the reference's default) every chunk
         decoded from zero state; seamless=True one stateful CodecStream per request, the chunks cut as
         synthesize_batch_stream cuts them.  `sampling`: temperature, top_p, repetition_penalty, max_tokens, seed.  The
         prompt is built and checked here (a too-long one raises ValueError now); the request is queued at the first
         next(), so a generator dropped before it never runs, and abandoning it later cancels the request (its slot is
-        freed at the next burst boundary).  `sample_rate` and `speed` as FishTTS.synthesize_stream (checked here)."""
+        freed at the next burst boundary).  `sample_rate`, `speed` and `pitch` as FishTTS.synthesize_stream (checked here)."""
         if chunk_tokens < 1 or min_first_chunk < 1:
             raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-        rate, spd = _output_rate(sample_rate), _output_speed(speed)
+        rate, spd, pit = _output_rate(sample_rate), _output_speed(speed), _output_pitch(pitch, speed)
         utt, n_prefix = self._prepare(text, references, sampling.get("temperature", 0.7), sampling.get("top_p", 0.8),
                                       sampling.get("repetition_penalty", 1.1), sampling.get("max_tokens", 2048),
                                       sampling.get("seed", 0))
-        return self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, rate, spd)
+        return self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, rate, spd, pit)
 
     def _stream(self, utt: Utterance, n_prefix: int, seamless: bool, chunk_tokens: int,
-                min_first_chunk: int, rate: Optional[int] = None, speed: Optional[float] = None) -> Iterator[bytes]:
+                min_first_chunk: int, rate: Optional[int] = None, speed: Optional[float] = None,
+                pitch: Optional[float] = None) -> Iterator[bytes]:
         yield from self._chunks(self.submit(utt, n_prefix, stream=True, seamless=seamless, chunk_tokens=chunk_tokens,
-                                            min_first_chunk=min_first_chunk, sample_rate=rate, speed=speed))
+                                            min_first_chunk=min_first_chunk, sample_rate=rate, speed=speed, pitch=pitch))
 
     def submit(self, utt: Utterance, n_prefix: int = 0, stream: bool = False, seamless: bool = False,
                chunk_tokens: int = 20, min_first_chunk: int = 10, sample_rate: Optional[int] = None,
-               speed: Optional[float] = None) -> _Request:
+               speed: Optional[float] = None, pitch: Optional[float] = None) -> _Request:
         """Queues one prepared utterance (the layer under synthesize / synthesize_stream); its output arrives on
         `.out`.  Raises ServerClosed once the server is closing or has failed."""
         if self._codec is None:
             raise RuntimeError("Vocoder not loaded")
         req = _Request(utt, n_prefix, ("seamless" if seamless else "chunks") if stream else "wav", chunk_tokens,
-                       min_first_chunk, _output_rate(sample_rate), _output_speed(speed))
+                       min_first_chunk, _output_rate(sample_rate), _output_speed(speed), _output_pitch(pitch, speed))
         with self._lock:
             if self._error is not None:
                 raise ServerClosed(f"BatchServer failed: {self._error!r}") from self._error
@@ -483,7 +497,7 @@ class BatchServer:
                             audio = self._codec.decode_streams(streams, seam_chunks,
                                                                [f and r.fx for r, f in zip(seam, seam_final)])
                         for r, a in zip(seam, audio):
-                            if len(a) or not r.skw:     # (no frame of the time-scale stage completed: nothing to hand out)
+                            if len(a) or not r.skw:     # (nothing completed in the time-scale or pitch stage: nothing to hand out)
                                 r.out.put(pcm16(a))
                     for r, c in zip(plain, plain_chunks):
                         r.out.put(self._decode_pcm(c) if not r.fx else self._decode_pcm(c, r.rate, **r.skw))

@@ -242,20 +242,25 @@ class FishTTS:
     def synthesize(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                    top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048) -> bytes:
         """Text -> WAV bytes (synthesizer.py:431-481).  While a BatchServer is open (serve()) the call joins its batch.
-        The reference's signature; synthesize_at also takes an output sample rate and a speaking rate."""
+        The reference's signature; synthesize_at also takes an output sample rate, a speaking rate and a pitch shift."""
         return self.synthesize_at(text, references, temperature, top_p, repetition_penalty, max_tokens)
 
     def synthesize_at(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                       top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
-                      sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
+                      sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                      pitch: Optional[float] = None) -> bytes:
         """Extension: synthesize() with the WAV at `sample_rate` (resampled on the GPU; None or 44100: the codec's own
         rate, byte for byte synthesize()'s result; an unsupported rate raises ValueError before any work -
         codec_engine.output_rate) and at speaking rate `speed` (a factor in [0.5, 2.0], the waveform time-scaled on the
         GPU at unchanged pitch before the resampler; None or 1.0: the model's own pace, byte for byte synthesize()'s
-        result; anything else raises ValueError before any work - codec_engine.output_speed)."""
+        result; anything else raises ValueError before any work - codec_engine.output_speed), shifted by `pitch`
+        semitones (in [-12, 12], in steps of a cent; a plain shift on the GPU between the two stages - formants move with
+        the pitch - that leaves the length as it is; None or 0: the model's own pitch, byte for byte the result without
+        it; a value outside the range, or one whose speed / 2^(pitch / 12) leaves [0.5, 2], raises ValueError before any
+        work - codec_engine.output_pitch, output_fx)."""
         from .generation import generate_long
         from .serve import ServerClosed
-        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed)
+        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed, pitch)
         srv = getattr(self, "_server", None)
         if srv is not None:
             try:
@@ -277,7 +282,7 @@ class FishTTS:
             raise RuntimeError("No audio generated")
         if not fx:
             return self._decode_to_wav(np.concatenate(codes_list, axis=1))
-        return self._decode_to_wav(np.concatenate(codes_list, axis=1), rate, fx.get("speed"))
+        return self._decode_to_wav(np.concatenate(codes_list, axis=1), rate, fx.get("speed"), **_pkw(fx))
 
     def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
                           repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]]):
@@ -315,13 +320,14 @@ class FishTTS:
     def synthesize_batch(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
                          temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
                          max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None,
-                         sample_rate: Optional[int] = None, speed: Optional[float] = None) -> List[bytes]:
+                         sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                         pitch: Optional[float] = None) -> List[bytes]:
         """Extension (BASELINE configs[2]): many texts -> WAV bytes each, decoded `max_batch` at a time in lock step
         with refill (fish_tts_amd.batch); utterance i uses seed + i, or seeds[i] when `seeds` is given (a sharded run
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
-        semantics as synthesize(), `sample_rate` and `speed` (as synthesize_at) included."""
+        semantics as synthesize(), `sample_rate`, `speed` and `pitch` (as synthesize_at) included."""
         from .batch import run_batch, run_batch_streams
-        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed)
+        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed, pitch)
         self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
@@ -335,7 +341,7 @@ class FishTTS:
             codes = u.codes()
             if codes.shape[1] == 0:
                 raise RuntimeError("No audio generated")
-            out.append(self._decode_to_wav(codes) if not fx else self._decode_to_wav(codes, rate, fx.get("speed")))
+            out.append(self._decode_to_wav(codes) if not fx else self._decode_to_wav(codes, rate, fx.get("speed"), **_pkw(fx)))
         return out
 
     def synthesize_batch_stream(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
@@ -343,7 +349,8 @@ class FishTTS:
                                 top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
                                 seed: int = 0, seeds: Optional[List[int]] = None,
                                 sample_rate: Optional[int] = None,
-                                speed: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
+                                speed: Optional[float] = None,
+                                pitch: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
         """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
         PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
         `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
@@ -355,10 +362,12 @@ class FishTTS:
         `sample_rate` (as synthesize_at): each utterance's stream resamples on the GPU; the chunk before its (i, b"") holds
         the resampler's tail, so its PCM concatenates to the resampled waveform of one streamed decode.
         `speed` (as synthesize_at): each utterance's stream is time-scaled on the GPU through one carried stage (before
-        the resampler, if any); the chunk before its (i, b"") holds the tail in the same way."""
+        the resampler, if any); the chunk before its (i, b"") holds the tail in the same way.
+        `pitch` (as synthesize_at): each utterance's stream is pitch-shifted on the GPU through one carried stage (between
+        the two); the tail travels in the same way."""
         from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
-        fx = _fx(sample_rate, speed)
+        fx = _fx(sample_rate, speed, pitch)
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
@@ -400,11 +409,16 @@ class FishTTS:
         Extension `speed=` (keyword, as synthesize_at; checked at the first next()): seamless=False chunks are time-scaled
         each on its own, as independent waveforms; a seamless stream runs one carried time-scale stage (in front of the
         resampler, if any; a last PCM chunk holds the tail), so its chunks concatenate to the time-scaled waveform of one
-        streamed decode."""
+        streamed decode.
+
+        Extension `pitch=` (keyword, as synthesize_at; checked at the first next()): seamless=False chunks are shifted each
+        on its own, as independent waveforms; a seamless stream runs one carried pitch stage (between the time-scale stage
+        and the resampler), so its chunks concatenate to the shifted waveform of one streamed decode."""
         from .generation import generate_long
         from .serve import ServerClosed
-        rate, fx = output_rate(kwargs.get("sample_rate")), _fx(kwargs.get("sample_rate"), kwargs.get("speed"))
-        spd = fx.get("speed")
+        rate = output_rate(kwargs.get("sample_rate"))
+        fx = _fx(kwargs.get("sample_rate"), kwargs.get("speed"), kwargs.get("pitch"))
+        spd, pkw = fx.get("speed"), _pkw(fx)
         srv = getattr(self, "_server", None)
         if srv is not None:
             chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, **kwargs)
@@ -434,22 +448,22 @@ class FishTTS:
                 if seamless:
                     if self._vocoder is None:
                         raise RuntimeError("Vocoder not loaded")
-                    stream = self._vocoder.stream(rate, spd)  # carried state: K/V of the last 127 frames, conv tails
+                    stream = self._vocoder.stream(rate, spd, **pkw)  # carried state: K/V of the last 127 frames, conv tails
                 while True:
                     codes = codes_queue.get()
                     if codes is None:
                         break
                     if stream is None:
-                        audio_queue.put(self._decode_to_pcm(codes) if not fx else self._decode_to_pcm(codes, rate, spd))
+                        audio_queue.put(self._decode_to_pcm(codes) if not fx else self._decode_to_pcm(codes, rate, spd, **pkw))
                     else:
                         codes = np.asarray(codes)
                         if stream.frames + codes.shape[1] > self._vocoder.max_frames:   # the rotation table ends here
                             if fx:                              # the old stream's output-stage tail first
                                 audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())
                             stream.close()
-                            stream = self._vocoder.stream(rate, spd)
+                            stream = self._vocoder.stream(rate, spd, **pkw)
                         audio = stream.decode(codes)
-                        if len(audio) or spd is None:   # (no frame of the time-scale stage completed: nothing to hand out)
+                        if len(audio) or (spd is None and not pkw):   # (an output stage completed nothing: nothing to hand out)
                             audio_queue.put((audio * 32767).astype(np.int16).tobytes())
                 if stream is not None and fx:
                     audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())   # the output stages' tail
@@ -603,26 +617,35 @@ class FishTTS:
         return Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seed), n_prefix
 
     # ------------------------------------------------------------------ codes -> audio (synthesizer.py:586-648)
-    def _decode_to_wav(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
+    def _decode_to_wav(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                       pitch: Optional[float] = None) -> bytes:
+        if pitch is not None:
+            return self._to_wav_bytes(self._decode_codes(codes, sample_rate, speed, pitch), self.sample_rate if sample_rate is None else sample_rate)
         if sample_rate is None and speed is None:
             return self._to_wav_bytes(self._decode_codes(codes))
         if speed is None:
             return self._to_wav_bytes(self._decode_codes(codes, sample_rate), sample_rate)
         return self._to_wav_bytes(self._decode_codes(codes, sample_rate, speed), self.sample_rate if sample_rate is None else sample_rate)
 
-    def _decode_to_pcm(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> bytes:
-        if speed is not None:
+    def _decode_to_pcm(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                       pitch: Optional[float] = None) -> bytes:
+        if pitch is not None:
+            audio = self._decode_codes(codes, sample_rate, speed, pitch)
+        elif speed is not None:
             audio = self._decode_codes(codes, sample_rate, speed)
         else:
             audio = self._decode_codes(codes) if sample_rate is None else self._decode_codes(codes, sample_rate)
         return (audio * 32767).astype(np.int16).tobytes()  # no clip on the PCM path (synthesizer.py:594)
 
-    def _decode_codes(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None) -> np.ndarray:
+    def _decode_codes(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                      pitch: Optional[float] = None) -> np.ndarray:
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
+        if pitch is not None:
+            return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate, speed=speed, pitch=pitch), axis=0)
         if speed is not None:
             return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate, speed=speed), axis=0)
         if sample_rate is None:
@@ -663,15 +686,32 @@ def output_speed(speed: Optional[float]) -> Optional[float]:
     return None if pct is None else pct / 100.0
 
 
-def _fx(sample_rate, speed) -> dict:
+def output_pitch(pitch: Optional[float], speed: Optional[float] = None) -> Optional[float]:
+    """codec_engine.output_fx's pitch in semitones: None for the model's own pitch, else the accepted cents / 100; the
+    combination with `speed` is checked as well (speed / 2^(pitch / 12) in [0.5, 2])."""
+    from .codec_engine import output_fx as check
+    cents = check(speed, pitch)[1]
+    return None if cents is None else cents / 100.0
+
+
+def _fx(sample_rate, speed, pitch=None) -> dict:
     """The checked output keywords of a call, absent ones left out: {} is the path without output stages."""
     rate, spd = output_rate(sample_rate), output_speed(speed)
+    pit = output_pitch(pitch, speed)
     fx = {}
     if rate is not None:
         fx["sample_rate"] = rate
     if spd is not None:
         fx["speed"] = spd
+    if pit is not None:
+        fx["pitch"] = pit
     return fx
+
+
+def _pkw(fx: dict) -> dict:
+    """The pitch keyword of a checked call for the decode helpers and streams: absent without a pitch shift, so those
+    calls stay what they were."""
+    return {"pitch": fx["pitch"]} if "pitch" in fx else {}
 
 
 def get_instance(model_dir=None, device: Literal["cpu", "cuda"] = "cuda",

@@ -241,6 +241,53 @@ ft_status ft_codec_decode_fx(ft_ctx* ctx, const int32_t* codes, int32_t B, int32
  * call (one workgroup of the stage per time-scaled stream); final and tail-only chunks behave as for the resampler, also at
  * 44100.  ft_codec_stream_decode and ft_codec_stream_decode_many refuse them (FT_ERR_STATE). */
 ft_status ft_codec_stream_begin_fx(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, ft_codec_stream** out);
+/* Pitch.  A plain pitch shift of the codec's waveform by pitch_cents, an integer in [-1200, 1200] (anything else:
+ * FT_ERR_ARG before any device work); 0 means the stage is absent, and the call is then ft_codec_decode_fx /
+ * ft_codec_stream_begin_fx.  Formants move with the pitch (no formant preservation).  The shift is the two stages above put
+ * together: stretch the waveform by the pitch ratio at unchanged pitch, then read it back faster by the same ratio.
+ *   Step: S = llround(2^20 2^(cents / 1200)), computed in double; r = S / 2^20 is the realised pitch ratio (within half a
+ *   step, 2^-21, of the nominal one: at most 2^-20 = 9.6e-7 relative, at r = 0.5; below 5e-7 from r = 1 on).
+ *   Chain: codec -> time-scale stage -> pitch stage -> rate resampler, all on the codec's stream.
+ *   Time-scale stage under pitch: the WSOLA algorithm above at the rational rate num / den, num = speed_pct 2^20,
+ *   den = 100 S (speed_pct = 100 when no speed is given): a_k = floor(k HS num / den), and the stage's output count is
+ *   ceil(n_in den / num).  A speed alone is num = pct, den = 100.  (64-bit arithmetic: k 512 200 2^20 < 2^52 within
+ *   max_frames.)
+ *   Accepted combinations: 50 S <= speed_pct 2^20 <= 200 S, which keeps the effective time-scale rate in [0.5, 2]; anything
+ *   else is FT_ERR_ARG before any device work.  When speed_pct 2^20 == 100 S - (200, +1200) and (50, -1200) - the time-scale
+ *   stage is absent and the pitch stage reads the codec's samples directly: a plain "play faster, higher".
+ *   Pitch stage: output n is its input at time n S / 2^20.  With u = n S, i0 = u >> 20, p = (u >> 11) & 511,
+ *   f = (u & 2047) / 2048:
+ *     y[n] = sum_{t < K} ((1 - f) w[p][t] + f w[p + 1][t]) x[i0 - K/2 + 1 + t],
+ *   in float32 over t ascending, in the same order whatever the chunking and however many segments share the launch.  The
+ *   table w[513][K] is float32: a Kaiser-windowed sinc designed on the host in float64 with the resampler's constants
+ *   (A = 75 dB, beta = 0.1102 (A - 8.7), transition 0.07), cut-off fc = 0.465 min(1, 1 / r) cycles per input sample,
+ *   K = the even ceiling of (A - 7.95) / (2.285 2 pi 0.07) max(1, r) (68 taps for r <= 1, 134 at r = 2); tap w[p][t] is the
+ *   prototype h(tau) = 2 fc sinc(2 fc tau) I0(beta sqrt(1 - (tau / (K/2))^2)) / I0(beta) (sinc(v) = sin(pi v) / (pi v)) at
+ *   tau = p / 512 + (K/2 - 1 - t) input samples; row 512 is row 0 shifted by one tap.  One table per cents value, uploaded
+ *   on first use and kept.  Through the interpolated coefficients the pass band to 0.43 min(1, 1 / r) is within 0.01 dB
+ *   and the stop band from 0.5 / r is at least 70 dB down (measured in float64 on the float32 table: <= 0.0015 dB, >= 80 dB).
+ *   Output length: the pitch stage emits exactly ft_timescaled_len(speed_pct, n_codec) samples, its input taken as zero
+ *   past its end (the last output's centre tap lies at most two samples past it).  Pitch never changes an utterance's
+ *   length: ft_resampled_len(rate, ft_timescaled_len(pct, n)) stays the length formula of every path.
+ *   Streams: a pitched stream carries, besides the above, the stage's last K input samples (two copies: a call reads one
+ *   and writes the other), its input and output counters on the host, and the time-scale state at the rational rate.  A
+ *   chunk emits the outputs whose taps all lie within the stage's input seen so far ((n S >> 20) + K/2 < samples in);
+ *   final emits the rest up to the exact length above and closes the stream; tail-only chunks work as for the resampler.
+ *   A stream's samples depend neither on the chunking nor on the other streams of the call.
+ *   The first pitched call allocates the time-scale stage's buffers (sized for rate 0.5, as its own first call does) and a
+ *   pitch output buffer of the same size. */
+/* Host only (no context, no device): S, K (K = 0 at 0 cents) and, if `table` is non-null, the 513 x K weights.  Any pointer
+ * may be NULL.  FT_ERR_ARG outside [-1200, 1200], the outputs left untouched. */
+ft_status ft_pitch_filter(int32_t cents, int64_t* step, int32_t* K, float* table);
+/* Host only: FT_OK when (speed_pct, cents) is an accepted combination (speed_pct = 100: no speed), else FT_ERR_ARG. */
+ft_status ft_pitch_ok(int32_t speed_pct, int32_t cents);
+/* ft_codec_decode_fx at pitch_cents (same lengths, same layout); ft_codec_decode_fx is this call at 0 cents. */
+ft_status ft_codec_decode_fxp(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                              int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, float* audio, int64_t* out_lens);
+/* ft_codec_stream_begin_fx at pitch_cents.  ft_codec_stream_decode_many_at serves such streams, mixed with any others in
+ * one call; ft_codec_stream_decode and ft_codec_stream_decode_many refuse them (FT_ERR_STATE). */
+ft_status ft_codec_stream_begin_fxp(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents,
+                                    ft_codec_stream** out);
 /* Codec encode = vocoder.encode(audio, lengths) of encode_reference (synthesizer.py:325-357, vocoder.py:885-904):
  * mono f32 audio at the codec sample rate (host), right-padded to whole frames -> codes (num_codebooks+1) x T'
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */

@@ -55,6 +55,13 @@ ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sampl
 ft_status ft_test_timescale(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, float* y, int64_t* n_out,
                             int32_t* deltas, int32_t* n_frames);
 
+/* Test hook: the time-scale and pitch stages of ft_codec_decode_fxp on a host waveform x of n <= max_frames * frame_len
+ * samples at 44100 (cents != 0) -> y: *n_out = ft_timescaled_len(speed_pct, n) samples.  mid (may be NULL; room for 2 n + 1
+ * samples) receives the *n_mid time-scaled samples the pitch stage read, deltas (may be NULL) the d_k of the *n_frames
+ * frames of the time-scale stage at its rational rate.  With no time-scale stage *n_mid = n, mid = x and *n_frames = 0. */
+ft_status ft_test_pitch(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, int32_t cents, float* y, int64_t* n_out,
+                        float* mid, int64_t* n_mid, int32_t* deltas, int32_t* n_frames);
+
 /* Test hook: a launch trace of the codec.  ft_test_codec_trace_arm makes the NEXT ft_codec_decode (B = 1; any other
  * B disarms it untraced) or ft_codec_encode on this context record one entry per kernel launch of the one-shot path, in
  * launch order: a stable stage name ("post.2.wo", "up.1.pw1", "dec.3.u2.c7", "enc.2.sc", ...), the rows and columns
