@@ -292,6 +292,45 @@ class ARHipEngine:
             None if qq is None else qq.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "ft_test_sample")
         return int(out[0])
 
+    def test_wide_linear(self, epi: int, M: int, X: np.ndarray, W: np.ndarray, gain=None, bias=None, resid=None,
+                         alias: bool = False, vocab_head: bool = False):
+        """Test hook (ft_test_wide_linear): one Linear of a lock-step batch through the product's dispatcher.  X (M, K),
+        W (N, K), gain (K,), resid (M, N): uint16 patterns of the model's type; bias (N,) f32.  Returns (out, tail,
+        variant): the M written rows (f32 for epi 0, else uint16), the rows up to the tile edge, the class that ran."""
+        u16 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint16)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        X, W, gain, resid = u16(X), u16(W), u16(gain), u16(resid)
+        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        N, K = W.shape
+        assert X.shape == (M, K), (X.shape, M, K)
+        oc, dt = (N // 2 if epi == 1 else N), (np.float32 if epi == 0 else np.uint16)
+        out, tail = np.zeros((M, oc), dtype=dt), np.zeros((31, oc), dtype=dt)
+        tr, var = C.c_int32(0), C.c_int32(-1)
+        self._check(self.lib.ft_test_wide_linear(self._h, epi, 1 if vocab_head else 0, M, N, K, ptr(X), ptr(W), ptr(gain),
+                                                 ptr(bias), ptr(resid), 1 if alias else 0, ptr(out), ptr(tail),
+                                                 C.byref(tr), C.byref(var)), "ft_test_wide_linear")
+        return out, tail[: tr.value], var.value
+
+    def test_wide_attn(self, qkv: np.ndarray, pos: np.ndarray, qn: np.ndarray, kn: np.ndarray, kc: np.ndarray, vc: np.ndarray):
+        """Test hook (ft_test_wide_attn): the slow-stack attention launch of a lock-step batch.  qkv (M, qkvN) f32, pos (M,),
+        qn / kn (hd,) and kc / vc (M, Hkv, n_slots, hd) uint16 patterns.  Returns (y (M, H hd) uint16, kc, vc after the
+        launch, splits: 0 = attn_wide_kernel, n = the fall-back with n KV splits)."""
+        qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        qn, kn = np.ascontiguousarray(qn, dtype=np.uint16), np.ascontiguousarray(kn, dtype=np.uint16)
+        kc, vc = np.array(kc, dtype=np.uint16, order="C"), np.array(vc, dtype=np.uint16, order="C")     # copies: written in place
+        a = self.args
+        M = qkv.shape[0]
+        n_slots = a.max_seq_len + (-a.max_seq_len) % 8
+        assert qkv.shape == (M, (a.n_head + 2 * a.n_local_heads) * a.head_dim), qkv.shape
+        assert kc.shape == vc.shape == (M, a.n_local_heads, n_slots, a.head_dim), kc.shape
+        y = np.zeros((M, a.n_head * a.head_dim), dtype=np.uint16)
+        sp = C.c_int32(-1)
+        ptr = lambda t: t.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.ft_test_wide_attn(self._h, M, ptr(qkv), ptr(pos), ptr(qn), ptr(kn), ptr(kc), ptr(vc), ptr(y),
+                                               C.byref(sp)), "ft_test_wide_attn")
+        return y, kc, vc, sp.value
+
     def engine_state(self):
         """(flags, time-outs recovered so far, phase of the last one) of the persistent frame engine: flags bit 0 = slow
         stack, bit 1 = fast loop."""

@@ -610,8 +610,11 @@ __global__ __launch_bounds__(256) void prefill_rope_append_kernel(AttnP p) {
 // f32 scores and probabilities, one rounding of y), but the softmax is taken in two passes - all scores to LDS, the
 // exact maximum, then the weighted sum - instead of an online softmax per lane group: no exponentials or rescaling on
 // the per-position chain, every K row of up to 128 positions (and the first V rows) in flight from the first
-// instruction.  Sums run in another order than the single-utterance kernel; wide batches are judged against the oracle
-// with the precision's margin (tests/test_ar_gpu.py: test_wide_batch_vs_oracle, tests/test_wide_fp16_gpu.py), not bit for bit.
+// instruction.  Sums run in another order than the single-utterance kernel, so nothing pins it bit for bit: the launch
+// alone is checked element by element against a float64 restatement (ft_test_wide_attn, tests/test_wide_kernels_gpu.py:
+// y, the appended K / V rows, every other cache row unchanged; Gq = 1, 2, 4 and the split fall-back), and whole wide
+// batches follow the oracle with the precision's margin (tests/test_ar_gpu.py: test_wide_batch_vs_oracle,
+// tests/test_wide_fp16_gpu.py).
 // LDS: (G + 2) HD + 16 G + NSLOT G HD + G n_sc floats, n_sc >= the longest context + 1.
 // ------------------------------------------------------------------------------------------
 template <int G, int HD, typename WT = bf16_t, int ROUND = RND_BF16>

@@ -748,8 +748,10 @@ static bool wide_pair(const Launch& L) {
 // matrix (W13 always, Wqkv from 17 batch rows), both 16-row batch tiles in one workgroup only where the weights
 // dominate (W13, the vocabulary head); everything else splits the batch rows over workgroups.
 // WT: the model's 16-bit element type; the octet-major buffers of the context are raw 16-bit storage (declared bf16_t)
+// Returns which instantiation class ran (WIDE_ID_*, include/fishtts_hip_test.h: ft_test_wide_linear reports it).
+enum { WIDE_ID_S11 = 0, WIDE_ID_S12 = 1, WIDE_ID_S22 = 2, WIDE_ID_G12 = 3, WIDE_ID_G22 = 4, WIDE_ID_R11 = 5, WIDE_ID_HEAD = 6 };
 template <typename WT>
-static void wide_gemm(Launch& L, const bf16_t* X, const void* W, const float* bias, int N, int K, const void* gain, int epi,
+static int wide_gemm(Launch& L, const bf16_t* X, const void* W, const float* bias, int N, int K, const void* gain, int epi,
                       float* out_f32, long ldo, bf16_t* out_xo, const bf16_t* resid_xo, int rows = 0, bool vocab_head = false) {
     const int M = rows > 0 ? rows : L.M;
     WidePT<WT> p{};
@@ -757,20 +759,29 @@ static void wide_gemm(Launch& L, const bf16_t* X, const void* W, const float* bi
     p.bias = bias; p.M = M; p.N = N; p.K = K; p.out_f32 = out_f32; p.ldo = ldo; p.out_xo = (WT*)out_xo; p.ldm_o = L.ctx->xo_ldm;
     p.resid_xo = (const WT*)resid_xo;
     bool ok;
-    if (epi == WEPI_RESID) ok = wide_gemm_launch<1, 1, false, WEPI_RESID>(p, L.s);
-    else if (epi == WEPI_SWIGLU) ok = M > 16 ? wide_gemm_launch<2, 2, true, WEPI_SWIGLU>(p, L.s) : wide_gemm_launch<1, 2, true, WEPI_SWIGLU>(p, L.s);
+    int id;
+    if (epi == WEPI_RESID) { id = WIDE_ID_R11; ok = wide_gemm_launch<1, 1, false, WEPI_RESID>(p, L.s); }
+    else if (epi == WEPI_SWIGLU) {
+        id = M > 16 ? WIDE_ID_G22 : WIDE_ID_G12;
+        ok = M > 16 ? wide_gemm_launch<2, 2, true, WEPI_SWIGLU>(p, L.s) : wide_gemm_launch<1, 2, true, WEPI_SWIGLU>(p, L.s);
+    }
     else if (vocab_head && M <= 32 && K == 1024 && N % 16 == 0 && N >= 4096 && !L.ctx->no_head_stream) {
         // the vocabulary head: activations normalised once per workgroup, weights streamed per wave (wide_head_kernel)
         static DevOnce once;
         once.run([] { hipFuncSetAttribute((const void*)wide_head_kernel<1024, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_head_lds<1024>()); });
         wide_head_kernel<1024, WT><<<256, 512, wide_head_lds<1024>(), L.s>>>(p);
+        id = WIDE_ID_HEAD;
         ok = true;
     }
-    else if (N >= 32768) ok = M > 16 ? wide_gemm_launch<2, 2, true, WEPI_STORE>(p, L.s) : wide_gemm_launch<1, 2, true, WEPI_STORE>(p, L.s);
-    else if (N >= 4096 && M > 16) ok = wide_gemm_launch<1, 2, true, WEPI_STORE>(p, L.s);
-    else ok = wide_gemm_launch<1, 1, true, WEPI_STORE>(p, L.s);
+    else if (N >= 32768) {
+        id = M > 16 ? WIDE_ID_S22 : WIDE_ID_S12;
+        ok = M > 16 ? wide_gemm_launch<2, 2, true, WEPI_STORE>(p, L.s) : wide_gemm_launch<1, 2, true, WEPI_STORE>(p, L.s);
+    }
+    else if (N >= 4096 && M > 16) { id = WIDE_ID_S12; ok = wide_gemm_launch<1, 2, true, WEPI_STORE>(p, L.s); }
+    else { id = WIDE_ID_S11; ok = wide_gemm_launch<1, 1, true, WEPI_STORE>(p, L.s); }
     if (!ok && L.err == hipSuccess) L.err = hipErrorInvalidValue;
     L.chk();
+    return id;
 }
 
 // f32 rows -> octet-major 16-bit elements (the values are exact in the model's type): the residual stream a prompt pass left in ctx->x
@@ -1005,6 +1016,36 @@ static void gemv_combine_nt(Launch& L, const GemvP& p, const AttnP& a, int nt) {
 #undef FT_NT
 }
 
+// The slow-stack attention launch of a wide batch, on an AttnP filled but for the split fields.  >= 128 (row, kv head)
+// blocks: each walks its row's whole context with the two-pass kernel; fewer rows split the cache walk until
+// M x Hkv x nsplit blocks cover the chip (long contexts of few rows: voice prompts), and the partials are merged by
+// attn_combine_rows_kernel.  Returns 0 where attn_wide_kernel ran, else the KV splits of the fall-back (the test hook
+// ft_test_wide_attn reports it; the frames ignore it).
+template <typename WT, int ROUND>
+static int wide_attn(Launch& L, AttnP& a) {
+    ft_ctx* ctx = L.ctx;
+    const ft_ar_config& c = ctx->c;
+    const int M = L.M, Gq = c.n_head / c.n_local_heads;
+    const size_t wlds = (size_t)attn_wide_lds_floats(Gq, c.head_dim, ctx->n_slots) * sizeof(float);
+    if (!ctx->no_attn_wide && (long)M * c.n_local_heads >= 128 && c.head_dim == 128 && (Gq == 1 || Gq == 2 || Gq == 4) && wlds <= 65536) {
+        a.nsplit = 1;
+        const dim3 grid(c.n_local_heads, 1, M);
+        if (Gq == 1) attn_wide_kernel<1, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
+        else if (Gq == 2) attn_wide_kernel<2, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
+        else attn_wide_kernel<4, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
+        L.chk();
+        return 0;
+    }
+    int ns = 1;
+    while (ns < ctx->nsplit && (long)M * c.n_local_heads * ns < 256) ns *= 2;
+    a.nsplit = ns;
+    a.part_o = ctx->part_o + (size_t)L.m0 * c.n_head * ctx->nsplit * c.head_dim;
+    a.part_ml = ctx->part_ml + (size_t)L.m0 * c.n_head * ctx->nsplit * 2;
+    attn_decode<WT, ROUND>(L, a);
+    if (ns > 1) { attn_combine_rows_kernel<ROUND><<<M, 256, 0, L.s>>>(a); L.chk(); }
+    return ns;
+}
+
 // fast_project_in on the pre-norm hidden state (llama.py:453,590); identity when fast_dim == dim
 template <typename WT, int ROUND>
 static void enqueue_fproj(Launch& L) {
@@ -1047,7 +1088,7 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
             if constexpr (ROUND != RND_NONE) {
                 // five launches per layer (wide_kernels.h): the residual stream xo, the attention output and the SwiGLU vector
                 // travel octet-major in the 16-bit type; q k v stay f32 rows for the attention kernel
-                const int D = c.dim, HD = c.n_head * c.head_dim, F = c.intermediate_size, M = L.M, ldm = ctx->xo_ldm;
+                const int D = c.dim, HD = c.n_head * c.head_dim, F = c.intermediate_size, ldm = ctx->xo_ldm;
                 bf16_t* xo = ctx->xo_x + (size_t)m0 * 8;
                 bf16_t* yo = ctx->xo_y + (size_t)m0 * 8;
                 bf16_t* go = ctx->xo_g + (size_t)m0 * 8;
@@ -1060,26 +1101,7 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
                 a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots;
                 a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim);
                 a.y = nullptr; a.ldy = HD; a.y_bf = yo; a.y_xo_ldm = ldm;
-                // >= 128 (row, kv head) blocks: each walks its row's whole context with the two-pass kernel; fewer rows split
-                // the cache walk until M x Hkv x nsplit blocks cover the chip (long contexts of few rows: voice prompts)
-                const int Gq = c.n_head / c.n_local_heads;
-                const size_t wlds = (size_t)attn_wide_lds_floats(Gq, c.head_dim, ctx->n_slots) * sizeof(float);
-                if (!ctx->no_attn_wide && (long)M * c.n_local_heads >= 128 && c.head_dim == 128 && (Gq == 1 || Gq == 2 || Gq == 4) && wlds <= 65536) {
-                    a.nsplit = 1;
-                    const dim3 grid(c.n_local_heads, 1, M);
-                    if (Gq == 1) attn_wide_kernel<1, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
-                    else if (Gq == 2) attn_wide_kernel<2, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
-                    else attn_wide_kernel<4, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
-                    L.chk();
-                } else {
-                    int ns = 1;
-                    while (ns < ctx->nsplit && (long)M * c.n_local_heads * ns < 256) ns *= 2;
-                    a.nsplit = ns;
-                    a.part_o = ctx->part_o + (size_t)m0 * c.n_head * ctx->nsplit * c.head_dim;
-                    a.part_ml = ctx->part_ml + (size_t)m0 * c.n_head * ctx->nsplit * 2;
-                    attn_decode<WT, ROUND>(L, a);
-                    if (ns > 1) { attn_combine_rows_kernel<ROUND><<<M, 256, 0, L.s>>>(a); L.chk(); }
-                }
+                wide_attn<WT, ROUND>(L, a);
                 wide_gemm<WT>(L, yo, l.wo, l.bo_f32, D, HD, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
                 wide_gemm<WT>(L, xo, l.w13, nullptr, 2 * F, D, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr);
                 wide_gemm<WT>(L, go, l.w2, nullptr, D, F, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
@@ -2349,4 +2371,155 @@ extern "C" ft_status ft_test_sample(ft_ctx* ctx, const float* logits, int32_t cb
     FT_HIP(ctx, hipMemcpy(tokn, ctx->d_tokn + (cb == 0 ? 0 : cb + 1), sizeof(int), hipMemcpyDeviceToHost));
     *out_index = tokn[0];
     return ft_ar_reset(ctx, 0);
+}
+
+// ------------------------------------------------------------------------------------------ lock-step kernel test hooks
+// (include/fishtts_hip_test.h: ft_test_wide_linear, ft_test_wide_attn).  Host code around the product's own dispatchers
+// wide_gemm and wide_attn on temporaries: nothing here is reached from a frame.
+namespace {
+constexpr uint16_t WT_POISON = 0xFFFE;          // a NaN in bf16 and in fp16: operand rows >= M, and the 16-bit output sentinel
+constexpr uint32_t WT_POISON_F32 = 0xFFFFFFFEu; // the f32 output sentinel (a NaN)
+struct DevTmp {                                  // device temporaries of one hook call
+    std::vector<void*> v;
+    ~DevTmp() { for (void* p : v) hipFree(p); }
+    void* put(const void* host, size_t bytes) {
+        void* d = nullptr;
+        if (hipMalloc(&d, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        v.push_back(d);
+        if (host && bytes && hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return d;
+    }
+};
+}  // namespace
+
+template <typename WT>
+static ft_status test_wide_linear_t(ft_ctx* ctx, int epi, bool vocab_head, int M, int N, int K, const uint16_t* X, const uint16_t* W,
+                                    const uint16_t* gain, const float* bias, const uint16_t* resid, bool alias, void* out,
+                                    void* out_tail, int32_t* tail_rows, int32_t* variant) {
+    const int ldm = ctx->xo_ldm;
+    const int Mt = (M + 31) / 32 * 32;           // the edge of the tallest batch tile (TS = 2); <= ldm, a multiple of 32
+    const int oc = epi == WEPI_SWIGLU ? N / 2 : N;
+    auto to_xo = [&](const uint16_t* rows, int width) {
+        std::vector<uint16_t> o((size_t)width * ldm, WT_POISON);
+        for (int m = 0; m < M; ++m)
+            for (int k = 0; k < width; ++k) o[xo_index(m, k, ldm)] = rows[(size_t)m * width + k];
+        return o;
+    };
+    DevTmp tmp;
+    const std::vector<uint16_t> xo = to_xo(X, K);
+    void* dX = tmp.put(xo.data(), xo.size() * 2);
+    void* dW = tmp.put(W, (size_t)N * K * 2);
+    void* dG = gain ? tmp.put(gain, (size_t)K * 2) : nullptr;
+    void* dB = bias ? tmp.put(bias, (size_t)N * sizeof(float)) : nullptr;
+    void *dO = nullptr, *dR = nullptr;
+    if (epi == WEPI_STORE) {
+        const std::vector<uint32_t> fill((size_t)Mt * N, WT_POISON_F32);
+        dO = tmp.put(fill.data(), fill.size() * 4);
+    } else {
+        const std::vector<uint16_t> fill((size_t)oc * ldm, WT_POISON);
+        if (epi == WEPI_RESID) {
+            const std::vector<uint16_t> ro = to_xo(resid, N);
+            dR = tmp.put(ro.data(), ro.size() * 2);
+            dO = alias ? dR : tmp.put(fill.data(), fill.size() * 2);
+        } else {
+            dO = tmp.put(fill.data(), fill.size() * 2);
+        }
+    }
+    if (!dX || !dW || (gain && !dG) || (bias && !dB) || !dO || (epi == WEPI_RESID && !dR)) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_wide_linear: device temporaries");
+    }
+    Launch L{ctx, ctx->stream, 0, M, 0};
+    const int id = wide_gemm<WT>(L, (const bf16_t*)dX, dW, (const float*)dB, N, K, dG, epi, epi == WEPI_STORE ? (float*)dO : nullptr, (long)N,
+                                 epi == WEPI_STORE ? nullptr : (bf16_t*)dO, (const bf16_t*)dR, M, vocab_head);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (L.err == hipErrorInvalidValue) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_linear: N is not a whole number of the launch's tiles");
+    if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_wide_linear launch failed");
+    if (epi == WEPI_STORE) {
+        std::vector<float> o((size_t)Mt * N);
+        FT_HIP(ctx, hipMemcpy(o.data(), dO, o.size() * 4, hipMemcpyDeviceToHost));
+        memcpy(out, o.data(), (size_t)M * N * 4);
+        memcpy(out_tail, o.data() + (size_t)M * N, (size_t)(Mt - M) * N * 4);
+    } else {
+        std::vector<uint16_t> o((size_t)oc * ldm);
+        FT_HIP(ctx, hipMemcpy(o.data(), dO, o.size() * 2, hipMemcpyDeviceToHost));
+        for (int m = 0; m < Mt; ++m) {
+            uint16_t* dst = m < M ? (uint16_t*)out + (size_t)m * oc : (uint16_t*)out_tail + (size_t)(m - M) * oc;
+            for (int k = 0; k < oc; ++k) dst[k] = o[xo_index(m, k, ldm)];
+        }
+    }
+    *tail_rows = Mt - M;
+    *variant = id;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_wide_linear(ft_ctx* ctx, int32_t epi, int32_t vocab_head, int32_t M, int32_t N, int32_t K,
+                                         const uint16_t* X, const uint16_t* W, const uint16_t* gain, const float* bias,
+                                         const uint16_t* resid, int32_t alias, void* out, void* out_tail, int32_t* tail_rows,
+                                         int32_t* variant) {
+    FT_TRY(ar_ready(ctx));
+    if (ctx->c.dtype != FT_BF16 && ctx->c.dtype != FT_F16) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_linear: the model's type is not 16-bit");
+    if (!ctx->wide_ok) return ft_fail(ctx, FT_ERR_STATE, "ft_test_wide_linear: this context has no lock-step MFMA path");
+    if (epi != WEPI_STORE && epi != WEPI_SWIGLU && epi != WEPI_RESID) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_linear: bad epilogue");
+    if (M < 1 || M > ctx->xo_ldm) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_linear: M outside 1..xo_ldm");
+    if (!wide_k_ok(K)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_linear: K must be 1024, 2048 or 3072");
+    if (N < 16 || N % 16 != 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_linear: N is not a whole number of 16-row tiles");
+    if (!X || !W || !out || !out_tail || !tail_rows || !variant || (epi != WEPI_RESID && !gain) || (epi == WEPI_RESID && !resid))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_linear: missing argument");
+    if (ctx->c.dtype == FT_BF16)
+        return test_wide_linear_t<bf16_t>(ctx, epi, vocab_head != 0, M, N, K, X, W, epi == WEPI_RESID ? nullptr : gain, bias, resid, alias != 0, out, out_tail, tail_rows, variant);
+    return test_wide_linear_t<f16_t>(ctx, epi, vocab_head != 0, M, N, K, X, W, epi == WEPI_RESID ? nullptr : gain, bias, resid, alias != 0, out, out_tail, tail_rows, variant);
+}
+
+template <typename WT, int ROUND>
+static ft_status test_wide_attn_t(ft_ctx* ctx, int M, const float* qkv, const int32_t* pos, const uint16_t* qn, const uint16_t* kn,
+                                  uint16_t* kc, uint16_t* vc, uint16_t* y, int32_t* splits) {
+    const ft_ar_config& c = ctx->c;
+    const int HD = c.n_head * c.head_dim, ldm = ctx->xo_ldm;
+    const size_t qkvN = (size_t)(c.n_head + 2 * c.n_local_heads) * c.head_dim;
+    const size_t cbytes = (size_t)M * ctx->cache_m_stride * 2;
+    DevTmp tmp;
+    const std::vector<uint16_t> fill((size_t)HD * ldm, WT_POISON);
+    void* dQ = tmp.put(qkv, (size_t)M * qkvN * sizeof(float));
+    void* dP = tmp.put(pos, (size_t)M * sizeof(int));
+    void* dQn = tmp.put(qn, (size_t)c.head_dim * 2);
+    void* dKn = tmp.put(kn, (size_t)c.head_dim * 2);
+    void* dK = tmp.put(kc, cbytes);
+    void* dV = tmp.put(vc, cbytes);
+    void* dY = tmp.put(fill.data(), fill.size() * 2);
+    if (!dQ || !dP || !dQn || !dKn || !dK || !dV || !dY) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_wide_attn: device temporaries");
+    }
+    Launch L{ctx, ctx->stream, 0, M, 0};
+    AttnP a{};
+    a.qkv = (const float*)dQ; a.ldq = (int)qkvN; a.qn = dQn; a.kn = dKn; a.rope = ctx->rope;
+    a.kc = dK; a.vc = dV; a.cache_m_stride = ctx->cache_m_stride; a.pos = (const int*)dP; a.pos_off = 0;
+    a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots;
+    a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim);
+    a.y = nullptr; a.ldy = HD; a.y_bf = (bf16_t*)dY; a.y_xo_ldm = ldm;
+    *splits = wide_attn<WT, ROUND>(L, a);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_wide_attn launch failed");
+    std::vector<uint16_t> o((size_t)HD * ldm);
+    FT_HIP(ctx, hipMemcpy(o.data(), dY, o.size() * 2, hipMemcpyDeviceToHost));
+    for (int m = 0; m < M; ++m)
+        for (int k = 0; k < HD; ++k) y[(size_t)m * HD + k] = o[xo_index(m, k, ldm)];
+    FT_HIP(ctx, hipMemcpy(kc, dK, cbytes, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(vc, dV, cbytes, hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_wide_attn(ft_ctx* ctx, int32_t M, const float* qkv, const int32_t* pos, const uint16_t* qn,
+                                       const uint16_t* kn, uint16_t* kc, uint16_t* vc, uint16_t* y, int32_t* splits) {
+    FT_TRY(ar_ready(ctx));
+    if (ctx->c.dtype != FT_BF16 && ctx->c.dtype != FT_F16) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_attn: the model's type is not 16-bit");
+    if (!ctx->wide_ok) return ft_fail(ctx, FT_ERR_STATE, "ft_test_wide_attn: this context has no lock-step MFMA path");
+    if (M < 1 || M > ctx->c.max_batch || M > 64) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_attn: M outside 1..min(max_batch, 64)");
+    if (!qkv || !pos || !qn || !kn || !kc || !vc || !y || !splits) return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_attn: missing argument");
+    for (int m = 0; m < M; ++m)
+        if (pos[m] < 0 || pos[m] >= ctx->n_slots || pos[m] >= ctx->c.max_seq_len)
+            return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_attn: a position outside the cache or the rope table");
+    if (ctx->c.dtype == FT_BF16) return test_wide_attn_t<bf16_t, RND_BF16>(ctx, M, qkv, pos, qn, kn, kc, vc, y, splits);
+    return test_wide_attn_t<f16_t, RND_F16>(ctx, M, qkv, pos, qn, kn, kc, vc, y, splits);
 }

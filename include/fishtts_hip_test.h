@@ -84,6 +84,38 @@ ft_status ft_test_codec_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t
 ft_status ft_test_codec_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t* kind, int32_t* is_f32, int64_t* elems,
                                      void* dst);
 
+/* Test hook: ONE Linear of a lock-step batch through the product's own dispatcher (engine.hip: wide_gemm), so the tile
+ * class, the K split and the choice of wide_head_kernel are the product's.  epi: 0 store (fused RMSNorm; f32 output
+ * holding values of the model's type), 1 SwiGLU (fused RMSNorm; interleaved (gate, up) weight rows; N / 2 output columns),
+ * 2 residual add (no norm).  X [M][K], W [N][K], gain [K] (epi 0 and 1), resid [M][N] (epi 2): bit patterns of the context's
+ * 16-bit type; bias [N] f32 or NULL.  alias != 0 (epi 2): the output buffer IS the residual buffer (the product's
+ * `xo, xo` form), otherwise they are two buffers (`xfo, xlo`).  The hook lays X and resid out octet-major at the context's
+ * row stride xo_ldm = 2 x (max_batch rounded up to 16) with NaN patterns (0xFFFE) in operand rows M .. xo_ldm - 1, and
+ * pre-fills the output with a sentinel (0xFFFE per 16-bit element, 0xFFFFFFFE per f32 element).  Everything lives in
+ * temporaries of the call: no state of the context changes.
+ * out: the M written rows, dense ([M][N] f32 for epi 0, else [M][N or N / 2] 16-bit patterns).  out_tail (room for 31
+ * rows): the *tail_rows rows M .. 32 ceil(M / 32) - 1 of the output buffer, which must still hold the sentinel (in the
+ * aliased form: the NaN fill of the residual rows).  *variant: the class that ran: 0 <1,1,norm,store>, 1 <1,2,norm,store>,
+ * 2 <2,2,norm,store>, 3 <1,2,norm,SwiGLU>, 4 <2,2,norm,SwiGLU>, 5 <1,1,residual> (<batch tiles, weight tiles> of 16 rows
+ * per workgroup; K picks the wave split), 6 wide_head_kernel.
+ * FT_ERR_ARG for what the dispatcher would refuse: a model type that is not 16-bit, M outside 1..xo_ldm, K not in
+ * {1024, 2048, 3072}, N not a whole number of the class's tiles. */
+ft_status ft_test_wide_linear(ft_ctx* ctx, int32_t epi, int32_t vocab_head, int32_t M, int32_t N, int32_t K,
+                              const uint16_t* X, const uint16_t* W, const uint16_t* gain, const float* bias,
+                              const uint16_t* resid, int32_t alias, void* out, void* out_tail, int32_t* tail_rows,
+                              int32_t* variant);
+
+/* Test hook: the slow-stack attention launch of a lock-step batch of M <= min(max_batch, 64) rows at the context's head
+ * geometry and rope table, through the product's own choice (engine.hip: wide_attn) between attn_wide_kernel<Gq> and
+ * attn_decode_kernel + attn_combine_rows_kernel.  qkv [M][(H + 2 Hkv) hd] f32, pos [M] (the new position of each row:
+ * its context is pos + 1 long), qn / kn [hd] and the caches kc / vc [M][Hkv][n_slots][hd] as 16-bit patterns.  The hook
+ * works on temporaries (only the context's split-partial scratch is written): kc / vc are uploaded, the launch appends
+ * row pos[m], and both come back whole in place, so a caller can see every other row unchanged.  y [M][H hd]: 16-bit
+ * patterns read back from the octet-major operand buffer.  *splits: 0 = attn_wide_kernel ran, n >= 1 = the fall-back
+ * with n KV splits (n > 1: merged by attn_combine_rows_kernel). */
+ft_status ft_test_wide_attn(ft_ctx* ctx, int32_t M, const float* qkv, const int32_t* pos, const uint16_t* qn,
+                            const uint16_t* kn, uint16_t* kc, uint16_t* vc, uint16_t* y, int32_t* splits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,20 +76,31 @@ def bf16_bits(x: torch.Tensor) -> np.ndarray:
     return x.to(F32).to(torch.bfloat16).contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
-def from_raw(a) -> torch.Tensor:
-    """A recorded buffer (uint16 bf16 bits or float32) or a tensor -> a tensor of its exact values."""
+def h16_bits(x: torch.Tensor, fmt: str = "bf16") -> np.ndarray:
+    """float -> bit patterns of a 16-bit format, "bf16" or "fp16" (round to nearest even, overflow to infinity, fp16
+    subnormals included: the conversions of common.h)."""
+    if fmt == "bf16":
+        return bf16_bits(x)
+    return x.to(F32).to(torch.float16).contiguous().view(torch.int16).numpy().view(np.uint16)
+
+
+def from_raw(a, fmt: str = "bf16") -> torch.Tensor:
+    """A recorded buffer (uint16 bit patterns of `fmt`, or float32) or a tensor -> a tensor of its exact values."""
     if isinstance(a, torch.Tensor):
         return a
     a = np.ascontiguousarray(a)
     if a.dtype == np.uint16:
-        return torch.from_numpy(a.view(np.int16)).view(torch.bfloat16).to(F32)
+        return torch.from_numpy(a.view(np.int16)).view(torch.bfloat16 if fmt == "bf16" else torch.float16).to(F32)
     return torch.from_numpy(a)
 
 
-def half_ulp(mag: torch.Tensor, f32: bool) -> torch.Tensor:
-    """Half a unit in the last place at |mag|: 2^(e-8) (bf16) / 2^(e-24) (f32) for a magnitude in [2^e, 2^(e+1))."""
-    _, ex = torch.frexp(mag.to(F64).abs().clamp_min(2.0 ** -126))       # mag = f * 2^ex, f in [0.5, 1): e = ex - 1
-    return torch.ldexp(torch.ones_like(mag, dtype=F64), ex - 1 - (24 if f32 else 8))
+def half_ulp(mag: torch.Tensor, f32: bool, fmt: str = "bf16") -> torch.Tensor:
+    """Half a unit in the last place at |mag|: 2^(e-8) (bf16) / 2^(e-24) (f32) / 2^(e-11) (fp16) for a magnitude in
+    [2^e, 2^(e+1)); below the smallest normal number (2^-126; 2^-14 in fp16) the step stays that of the lowest binade
+    (fp16: 2^-24, so half of it 2^-25)."""
+    fp16 = fmt == "fp16" and not f32
+    _, ex = torch.frexp(mag.to(F64).abs().clamp_min(2.0 ** (-14 if fp16 else -126)))       # mag = f * 2^ex, f in [0.5, 1): e = ex - 1
+    return torch.ldexp(torch.ones_like(mag, dtype=F64), ex - 1 - (24 if f32 else 11 if fp16 else 8))
 
 
 # ------------------------------------------------------------------------------------------------------- the plan
