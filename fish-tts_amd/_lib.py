@@ -40,6 +40,10 @@ class ft_codec_config(C.Structure):
                 ("enc_tf_layers", C.c_int32 * 8), ("enc_tf_window", C.c_int32), ("max_enc_frames", C.c_int32)]
 
 
+class ft_join_params(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("hop", C.c_int32), ("keep", C.c_int32), ("fade", C.c_int32)]
+
+
 class ft_sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
                 ("ban_eos", C.c_int32), ("seed", C.c_uint64)]
@@ -89,6 +93,11 @@ SYMBOLS = {
     "ft_codec_decode_fxp": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "ft_codec_stream_begin_fxp": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
     "ft_test_pitch": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "ft_codec_decode_join": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(ft_join_params), _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    "ft_join_groups": (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
+    "ft_test_join": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.POINTER(ft_join_params), _P, C.c_int32, _P, C.c_int64,
+                                 C.POINTER(C.c_int64), _P]),
     "ft_codec_encode": (C.c_int32, [_P, _P, C.c_int64, _P, _P]),
     "ft_codec_enc_frame_len": (C.c_int32, [_P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),

@@ -391,6 +391,92 @@ class CodecHipEngine:
                                            C.byref(k)), "ft_test_pitch")
         return y[:n.value], mid[:m.value], d[:k.value]
 
+    @staticmethod
+    def _join_params(params) -> "L.ft_join_params":
+        """(threshold, hop, keep, fade) -> the native struct, the threshold rounded to float32."""
+        threshold, hop, keep, fade = params
+        return L.ft_join_params(float(np.float32(threshold)), int(hop), int(keep), int(fade))
+
+    def test_join(self, items: Sequence[np.ndarray], params, gaps: Sequence[int], started: int = 0,
+                  capacity: Optional[int] = None, y: Optional[np.ndarray] = None, stride: Optional[int] = None):
+        """Test hook (ft_test_join): the join stage alone on host waveforms.  Returns (y, total, cuts): y holds `capacity`
+        samples (default: sum of the items and gaps plus 8), the sentinel pattern past `total`."""
+        items = [np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1)) for x in items]
+        B = len(items)
+        n = np.array([len(x) for x in items], dtype=np.int64)
+        stride = int(max(1, n.max() if B else 1)) if stride is None else int(stride)
+        x = np.zeros((max(B, 1), stride), dtype=np.float32)
+        for b, it in enumerate(items):
+            x[b, :min(len(it), stride)] = it[:stride]
+        g = np.ascontiguousarray(np.asarray(gaps, dtype=np.int64).reshape(-1))
+        cap = int(n.sum() + g.sum()) + 8 if capacity is None else int(capacity)
+        if y is None:
+            y = np.zeros(max(cap, 1), dtype=np.float32)
+        total = C.c_int64(0)
+        cuts = np.zeros((max(B, 1), 2), dtype=np.int64)
+        jp = self._join_params(params)
+        self._check(self.lib.ft_test_join(self._h, x.ctypes.data_as(C.c_void_p), B, stride, n.ctypes.data_as(C.c_void_p),
+                                          C.byref(jp), g.ctypes.data_as(C.c_void_p), int(started),
+                                          y.ctypes.data_as(C.c_void_p), cap, C.byref(total), cuts.ctypes.data_as(C.c_void_p)),
+                    "ft_test_join")
+        return y, total.value, cuts[:B]
+
+    MAX_ITEMS_PER_JOIN = 64       # ft_codec_decode_join
+
+    def decode_join(self, codes_list: Sequence[np.ndarray], sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                    pitch: Optional[float] = None, params=(0.0, 1, 0, 0), gaps: Optional[Sequence[int]] = None,
+                    started: bool = False):
+        """The utterances of one document - codes_list[i] (n_codebooks+1, T_i) integer - decoded at `sample_rate`, `speed`
+        and `pitch` (as decode) and joined on the device into one waveform (ft_codec_decode_join): each trimmed to its
+        loud part, faded at the cuts and laid out behind gaps[i] samples of silence.  `params`: (threshold, hop, keep,
+        fade), sample counts at the output rate; (0, 1, 0, 0) is plain concatenation with gaps.  `started`: audio of the
+        document went out before this call (the first piece then gets its gap too).  Consecutive items go into native
+        calls of at most 64 items and max_frames frames (ft_join_groups), `started` carried from call to call, the calls'
+        outputs concatenated here - a piece depends on its own item only, so the grouping does not show.  Returns (audio
+        float32, cuts (n, 2) int64: the samples [a, e) kept of every item)."""
+        rate = output_rate(sample_rate)
+        pct, cents = output_fx(speed, pitch)
+        items = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in codes_list]
+        for c in items:
+            if c.ndim != 2 or c.shape[0] != self.R:
+                raise ValueError(f"decode_join: codes of shape {c.shape}, expected ({self.R}, T)")
+        n = len(items)
+        g = np.zeros(n, dtype=np.int64) if gaps is None else np.ascontiguousarray(np.asarray(gaps, dtype=np.int64).reshape(-1))
+        if len(g) != n:
+            raise ValueError("decode_join: one gap per item")
+        if n and g.min() < 0:
+            raise ValueError("decode_join: a negative gap")
+        jp = self._join_params(params)
+        if not jp.threshold >= 0 or jp.hop < 1 or jp.keep < 0 or jp.fade < 0:
+            raise ValueError(f"decode_join: bad join parameters {tuple(params)!r}")
+        lens = np.array([c.shape[1] for c in items], dtype=np.int32)
+        ends = np.zeros(max(n, 1), dtype=np.int32)
+        ng = self.lib.ft_join_groups(lens.ctypes.data_as(C.c_void_p), n, int(self.max_frames), ends.ctypes.data_as(C.c_void_p))
+        if ng < 0:
+            raise ValueError(f"decode_join: an item longer than max_frames ({self.max_frames}) frames")
+        out, cuts, i, begun = [], np.zeros((n, 2), dtype=np.int64), 0, bool(started)
+        for j in (int(e) for e in ends[:ng]):
+            B, T = j - i, max(1, int(lens[i:j].max()))
+            block = np.zeros((B, self.R, T), dtype=np.int32)
+            for b, c in enumerate(items[i:j]):
+                block[b, :, :c.shape[1]] = c
+            glens = np.ascontiguousarray(lens[i:j])
+            cap = sum(_out_len(rate, pct, int(t) * self.frame_len) for t in glens) + int(g[i:j].sum())
+            audio = np.empty(max(cap, 1), dtype=np.float32)
+            total = C.c_int64(0)
+            gcuts = np.zeros((B, 2), dtype=np.int64)
+            ggaps = np.ascontiguousarray(g[i:j])
+            self._check(self.lib.ft_codec_decode_join(
+                self._h, block.ctypes.data_as(C.c_void_p), B, T, glens.ctypes.data_as(C.c_void_p),
+                CODEC_RATE if rate is None else rate, 100 if pct is None else pct, 0 if cents is None else cents,
+                C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0, audio.ctypes.data_as(C.c_void_p), cap,
+                C.byref(total), gcuts.ctypes.data_as(C.c_void_p)), "ft_codec_decode_join")
+            out.append(audio[:total.value])
+            cuts[i:j] = gcuts
+            begun = begun or total.value > 0
+            i = j
+        return (np.concatenate(out) if out else np.zeros(0, dtype=np.float32)), cuts
+
     def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, sample_rate: Optional[int] = None,
                speed: Optional[float] = None, pitch: Optional[float] = None) -> np.ndarray:
         """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len).

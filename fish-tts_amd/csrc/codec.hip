@@ -11,6 +11,7 @@
 
 #include "codec_kernels.h"
 #include "engine.h"
+#include "join_plan.h"
 
 using namespace ft;
 
@@ -76,6 +77,11 @@ struct CodecState {
     std::map<int, PsTab> ps_tabs;
     float* ps_out = nullptr;
     PsSeg* ps_seg = nullptr;
+    // join stage (ft_codec_decode_join): the items of a call side by side at the output rate, the joined waveform and the
+    // item table, allocated on the first joined call (the two buffers grow when a later call needs more)
+    float *join_in = nullptr, *join_out = nullptr;
+    size_t join_in_cap = 0, join_out_cap = 0;
+    JoinTab* join_tab = nullptr;
     // ---- encode side
     struct EncUnit { float *a0, *a2; ConvW c7, c1; };
     struct EncBlock { EncUnit u[3]; float* a3; ConvW sc; int s, cin, cout; std::vector<TfLayer> tf; float* tf_norm = nullptr; };
@@ -996,8 +1002,9 @@ static ft_status ps_enqueue(ft_ctx* ctx, std::vector<PsSeg>& segs, std::vector<R
 }
 
 // Resamples `segs` (their inputs written earlier on the codec's stream) into rs_out, back to back, and queues the copy of
-// all their outputs to `host`; the caller synchronizes (and keeps `segs` alive until then).
-static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host) {
+// all their outputs to `host` (`kind`: a joined call names a device buffer there); the caller synchronizes (and keeps `segs`
+// alive until then).
+static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host, hipMemcpyKind kind = hipMemcpyDeviceToHost) {
     CodecState* s = ctx->codec;
     hipStream_t st = s->stream;
     long long off = 0, mx = 0;
@@ -1009,7 +1016,7 @@ static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host) 
     FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, segs.data(), segs.size() * sizeof(RsSeg), hipMemcpyHostToDevice, st));
     const int gx = (int)std::max(1LL, std::min(2048LL, (mx + RS_THREADS - 1) / RS_THREADS));
     resample_kernel<<<dim3(gx, 1, (unsigned)segs.size()), RS_THREADS, 0, st>>>(s->rs_seg);
-    if (off > 0) FT_HIP(ctx, hipMemcpyAsync(host, s->rs_out, (size_t)off * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (off > 0) FT_HIP(ctx, hipMemcpyAsync(host, s->rs_out, (size_t)off * sizeof(float), kind, st));
     return FT_OK;
 }
 
@@ -1172,14 +1179,15 @@ static bool decode_chain(ft_ctx* ctx, const Layout& L) {
 
 // The end of a call that leaves samples: the time-scale stage and the resampler over `fx` (inputs written earlier on the stream) or the
 // plain copy of `plain` floats of s->audio, the call's one synchronize and the launch check; then every stream named moves
-// on by its chunk.
+// on by its chunk.  `kind`: where `host` lies (ft_codec_decode_join leaves its items on the device).
 static ft_status call_tail(ft_ctx* ctx, Fx* fx, float* host, size_t plain, const char* what, int n = 0,
-                           ft_codec_stream* const* scs = nullptr, const int32_t* lens = nullptr) {
+                           ft_codec_stream* const* scs = nullptr, const int32_t* lens = nullptr,
+                           hipMemcpyKind kind = hipMemcpyDeviceToHost) {
     CodecState* s = ctx->codec;
     if (fx && !fx->ts.empty()) FT_TRY(ts_enqueue(ctx, *fx));
     if (fx && !fx->ps.empty()) FT_TRY(ps_enqueue(ctx, fx->ps, fx->rs));
-    if (fx) FT_TRY(rs_enqueue(ctx, fx->rs, host));
-    else FT_HIP(ctx, hipMemcpyAsync(host, s->audio, plain * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if (fx) FT_TRY(rs_enqueue(ctx, fx->rs, host, kind));
+    else FT_HIP(ctx, hipMemcpyAsync(host, s->audio, plain * sizeof(float), kind, s->stream));
     FT_HIP(ctx, hipStreamSynchronize(s->stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string(what) + hipGetErrorString(e));
@@ -1192,9 +1200,10 @@ static ft_status call_tail(ft_ctx* ctx, Fx* fx, float* host, size_t plain, const
 
 // The chain over L and the end of the call; `who` names the caller in the message of a carry list out of step.
 static ft_status decode_run(ft_ctx* ctx, const Layout& L, Fx* rs, float* audio_host, int n,
-                            ft_codec_stream* const* scs, const int32_t* lens, const char* who) {
+                            ft_codec_stream* const* scs, const int32_t* lens, const char* who,
+                            hipMemcpyKind kind = hipMemcpyDeviceToHost) {
     const bool in_step = decode_chain(ctx, L);
-    FT_TRY(call_tail(ctx, rs, audio_host, (size_t)L.total * ctx->codec->frame_len, "codec launch: ", in_step ? n : 0, scs, lens));
+    FT_TRY(call_tail(ctx, rs, audio_host, (size_t)L.total * ctx->codec->frame_len, "codec launch: ", in_step ? n : 0, scs, lens, kind));
     if (!in_step) return ft_fail(ctx, FT_ERR_STATE, std::string(who) + ": carry bookkeeping out of step");
     return FT_OK;
 }
@@ -1206,9 +1215,10 @@ static void stream_carries(const ft_codec_stream* sc, bf16_t** out) {
 }
 
 // One item: T of the Tfull frames per codebook row of codes_host, decoded from zero state, or (sc) as the next chunk of a
-// stream.  `rs`: resample the waveform (segment 0 reads s->audio) and copy the resampled samples instead.
+// stream.  `rs`: resample the waveform (segment 0 reads s->audio) and copy the resampled samples instead.  `kind`: the copy
+// that delivers the samples (device to device when audio_host is the join stage's input buffer).
 static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, int T, float* audio_host, ft_codec_stream* sc = nullptr,
-                            Fx* rs = nullptr) {
+                            Fx* rs = nullptr, hipMemcpyKind kind = hipMemcpyDeviceToHost) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     const int HD = c.tf_n_head * c.tf_head_dim, R = c.n_codebooks + 1, W1 = c.tf_window - 1;
@@ -1232,7 +1242,7 @@ static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, i
     std::vector<int> hc((size_t)R * T);
     for (int r = 0; r < R; ++r) memcpy(&hc[(size_t)r * T], codes_host + (size_t)r * Tfull, T * sizeof(int));
     FT_HIP(ctx, hipMemcpyAsync(s->codes, hc.data(), hc.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    return decode_run(ctx, L, rs, audio_host, sc ? 1 : 0, &sc, &T, "codec stream");
+    return decode_run(ctx, L, rs, audio_host, sc ? 1 : 0, &sc, &T, "codec stream", kind);
 }
 
 // Streamed decode (second half): successive chunks of one utterance's codes, each decoded with
@@ -1448,6 +1458,30 @@ extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_code
     return decode_many(ctx, n, streams, codes, lens, audio);
 }
 
+// The output stages of one item decoded from zero state, n_in codec samples -> n_ts after the time-scale and pitch stages
+// -> n_out after the resampler: a fresh input to each stage, zeros before it, zeros after it (the whole tail).  False: no
+// stage at all (the codec's own rate, pace and pitch).  `t`, `pct`, `pt`, `f` as decode_items takes them.
+static bool item_stages(CodecState* s, const CodecState::RsTab* t, int pct, const CodecState::PsTab* pt, const FxPlan* f,
+                        size_t n_in, size_t n_ts, size_t n_out, Fx& g) {
+    if ((!t || t->K == 0) && pct == 100 && !pt) return false;
+    g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)n_ts, (int)n_out, 1, 1, 0, 0});
+    if (t && t->K > 0) { g.rs[0].w = t->w; g.rs[0].L = t->L; g.rs[0].M = t->M; g.rs[0].K = t->K; }
+    if (pt) {   // the time-scale stage at the rate of f (or none), then the pitch stage back to n_ts samples
+        long long n_mid = (long long)n_in;
+        if (f->has_ts) {
+            const TsPlan p = ts_plan(f->ts, 0, (long long)n_in, true);
+            n_mid = p.out;
+            g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, f->ts.num, f->ts.den,
+                                 (int)n_in, (int)n_mid, 0, p.k1, 0, 0});
+        }
+        g.ps.assign(1, PsSeg{s->audio, pt->w, nullptr, nullptr, nullptr, 0, 0, pt->S, (int)n_mid, (int)n_ts, pt->K, 0});
+    } else if (pct != 100) {
+        const TsPlan p = ts_plan(TsRate{pct, 100}, 0, (long long)n_in, true);
+        g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, pct, 100, (int)n_in, (int)n_ts, 0, p.k1, 0, 0});
+    }
+    return true;
+}
+
 // The items of ft_codec_decode / ft_codec_decode_at, one after the other: item b's samples go to audio + b * stride, zeros
 // behind them.  `t`: the resampler's table (null, or K = 0: the codec's own rate); `pct`: the speed (100 and no pitch: no
 // time-scale stage); `pt`: the pitch stage's table (null: none), the time-scale stage then at the rate of `f`.
@@ -1465,26 +1499,10 @@ static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t*
         if (out_lens) out_lens[b] = (int64_t)n_out;
         if (n_out < stride) memset(out + n_out, 0, (stride - n_out) * sizeof(float));
         if (Tb == 0) continue;
-        if ((!t || t->K == 0) && pct == 100 && !pt) {
+        Fx g;
+        if (!item_stages(s, t, pct, pt, f, n_in, n_ts, n_out, g)) {
             FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
             continue;
-        }
-        // a fresh input to each stage: zeros before it, zeros after it (the whole tail)
-        Fx g;
-        g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)n_ts, (int)n_out, 1, 1, 0, 0});
-        if (t && t->K > 0) { g.rs[0].w = t->w; g.rs[0].L = t->L; g.rs[0].M = t->M; g.rs[0].K = t->K; }
-        if (pt) {   // the time-scale stage at the rate of f (or none), then the pitch stage back to n_ts samples
-            long long n_mid = (long long)n_in;
-            if (f->has_ts) {
-                const TsPlan p = ts_plan(f->ts, 0, (long long)n_in, true);
-                n_mid = p.out;
-                g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, f->ts.num, f->ts.den,
-                                     (int)n_in, (int)n_mid, 0, p.k1, 0, 0});
-            }
-            g.ps.assign(1, PsSeg{s->audio, pt->w, nullptr, nullptr, nullptr, 0, 0, pt->S, (int)n_mid, (int)n_ts, pt->K, 0});
-        } else if (pct != 100) {
-            const TsPlan p = ts_plan(TsRate{pct, 100}, 0, (long long)n_in, true);
-            g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, pct, 100, (int)n_in, (int)n_ts, 0, p.k1, 0, 0});
         }
         FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, &g));
     }
@@ -1602,6 +1620,147 @@ extern "C" ft_status ft_codec_decode_fx(ft_ctx* ctx, const int32_t* codes, int32
 extern "C" ft_status ft_codec_decode_fxp(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
                                          int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, float* audio, int64_t* out_lens) {
     return decode_fx(ctx, "ft_codec_decode_fxp", codes, B, T, lens, sample_rate, speed_pct, audio, out_lens, pitch_cents);
+}
+
+// ---- join stage (fishtts_hip.h: ft_codec_decode_join; JoinTab and the three kernels in codec_kernels.h, the argument
+// checks and the layout of the input buffer in join_plan.h)
+// Room for `in` input and `out` output samples: allocated on the first call, replaced by larger buffers when a call needs more.
+static ft_status join_alloc(ft_ctx* ctx, size_t in, size_t out) {
+    CodecState* s = ctx->codec;
+    if (!s->join_tab) FT_TRY(cmalloc(ctx, &s->join_tab, (size_t)1));
+    auto grow = [&](float** p, size_t* cap, size_t need) -> ft_status {
+        if (*p && *cap >= need) return FT_OK;
+        float* q = nullptr;
+        FT_TRY(cmalloc(ctx, &q, need + 4));
+        if (*p) {
+            s->owned.erase(std::find(s->owned.begin(), s->owned.end(), (void*)*p));
+            hipFree(*p);
+        }
+        *p = q;
+        *cap = need;
+        return FT_OK;
+    };
+    FT_TRY(grow(&s->join_in, &s->join_in_cap, std::max(in, (size_t)4)));
+    return grow(&s->join_out, &s->join_out_cap, std::max(out, (size_t)4));
+}
+
+// The three launches over items that lie at join_in + off[b] (written earlier on the codec's stream), then the table's
+// head - total and the cuts - and `*total` samples to the host.  `fill`: the test hook's form - the output buffer pre-filled with the sentinel and all
+// `need` samples of it copied back.
+static ft_status join_run(ft_ctx* ctx, int B, const int64_t* n, const int64_t* off, const ft_join_params* jp, const int64_t* gaps,
+                          int started, float* audio, int64_t* total, int64_t* cuts, int64_t need, bool fill) {
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    std::vector<char> raw(sizeof(JoinTab));
+    JoinTab* h = (JoinTab*)raw.data();
+    memset(h, 0, sizeof(JoinTab));
+    h->started = started;
+    h->B = B;
+    long long widest = 0;
+    for (int b = 0; b < B; ++b) {
+        JoinItem& it = h->it[b];
+        it.x = s->join_in + off[b];
+        it.n = n[b];
+        it.gap = gaps[b];
+        it.first = INT_MAX;
+        it.last = -1;
+        widest = std::max(widest, (long long)(n[b] + gaps[b]));
+    }
+    const size_t used = offsetof(JoinTab, it) + (size_t)B * sizeof(JoinItem);
+    FT_HIP(ctx, hipMemcpyAsync(s->join_tab, h, used, hipMemcpyHostToDevice, st));
+    if (fill && need > 0) FT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)s->join_out, (int)0xFFFFFFFE, (size_t)need, st));
+    const int gx = (int)std::max(1LL, std::min(1024LL, (widest / 4 + JOIN_THREADS - 1) / JOIN_THREADS));
+    join_edges_kernel<<<dim3(std::min(gx, JOIN_EDGE_BLOCKS), 1, B), JOIN_THREADS, 0, st>>>(s->join_tab, jp->threshold, jp->hop);
+    join_layout_kernel<<<1, 64, 0, st>>>(s->join_tab, jp->hop, jp->keep, jp->fade);
+    join_assemble_kernel<<<dim3(gx, 1, B), JOIN_THREADS, 0, st>>>(s->join_tab, s->join_out);
+    FT_HIP(ctx, hipMemcpyAsync(h, s->join_tab, offsetof(JoinTab, started), hipMemcpyDeviceToHost, st));   // total and the cuts
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("join launch: ") + hipGetErrorString(e));
+    if (h->total < 0 || h->total > need) return ft_fail(ctx, FT_ERR_STATE, "join: layout out of range");
+    const int64_t ncopy = fill ? need : (int64_t)h->total;
+    if (ncopy > 0) {       // its length is known only now: the call's second and last wait
+        FT_HIP(ctx, hipMemcpyAsync(audio, s->join_out, (size_t)ncopy * sizeof(float), hipMemcpyDeviceToHost, st));
+        FT_HIP(ctx, hipStreamSynchronize(st));
+    }
+    *total = h->total;
+    memcpy(cuts, h->cuts, (size_t)B * 2 * sizeof(int64_t));
+    return FT_OK;
+}
+
+extern "C" int32_t ft_join_groups(const int32_t* lens, int32_t n, int32_t max_frames, int32_t* ends) {
+    return join_groups(lens, n, max_frames, ends);
+}
+
+extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                          int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, const ft_join_params* jp,
+                                          const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
+                                          int64_t* cuts) {
+    const std::string fn = "ft_codec_decode_join";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
+    FT_TRY(ts_refuse(ctx, fn, speed_pct));
+    FxPlan f;
+    FT_TRY(ps_refuse(ctx, fn, speed_pct, pitch_cents, &f));
+    FT_TRY(codec_ready(ctx));
+    if (!codes || !audio || !total || !cuts || B < 1 || B > JOIN_MAX_ITEMS || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
+    CodecState* s = ctx->codec;
+    const int R = ctx->cc.n_codebooks + 1;
+    int64_t n[JOIN_MAX_ITEMS], off[JOIN_MAX_ITEMS], frames = 0, need = 0;
+    for (int b = 0; b < B; ++b) {
+        const int Tb = lens ? lens[b] : T;
+        if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
+        frames += Tb;
+        n[b] = ft_resampled_len(sample_rate, ts_len(speed_pct, (int64_t)Tb * s->frame_len));
+    }
+    if (frames > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": sum(lens) exceeds max_frames");
+    if (const char* why = join_check(B, n, jp, gaps, started, capacity, &need)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
+    const int64_t in_floats = join_offsets(B, n, off);
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    const CodecState::RsTab* t = nullptr;
+    FT_TRY(rs_table(ctx, sample_rate, &t));
+    const CodecState::PsTab* pt = nullptr;
+    if (pitch_cents != 0) {
+        FT_TRY(ps_table(ctx, pitch_cents, &pt));
+        FT_TRY(ps_alloc(ctx));
+    } else if (speed_pct != 100) FT_TRY(ts_alloc(ctx));
+    else if (t->K > 0) FT_TRY(rs_alloc(ctx));
+    FT_TRY(join_alloc(ctx, (size_t)in_floats, (size_t)need));
+    // the items as decode_items runs them (one synchronize each, as there), their samples left side by side in join_in
+    for (int b = 0; b < B; ++b) {
+        const int Tb = lens ? lens[b] : T;
+        if (Tb == 0) continue;
+        const size_t n_in = (size_t)Tb * s->frame_len, n_ts = speed_pct == 100 ? n_in : (size_t)ts_len(speed_pct, (long long)n_in);
+        Fx g;
+        const bool staged = item_stages(s, t, speed_pct, pt, &f, n_in, n_ts, (size_t)n[b], g);
+        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, s->join_in + off[b], nullptr, staged ? &g : nullptr, hipMemcpyDeviceToDevice));
+    }
+    return join_run(ctx, B, n, off, jp, gaps, started, audio, total, cuts, need, false);
+}
+
+extern "C" ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, const int64_t* n, const ft_join_params* jp,
+                                  const int64_t* gaps, int32_t started, float* y, int64_t capacity, int64_t* total, int64_t* cuts) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!x || !y || !total || !cuts || stride < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_join: bad argument");
+    int64_t need = 0, off[JOIN_MAX_ITEMS];
+    if (const char* why = join_check(B, n, jp, gaps, started, capacity, &need)) return ft_fail(ctx, FT_ERR_ARG, std::string("ft_test_join: ") + why);
+    for (int b = 0; b < B; ++b)
+        if (n[b] > stride) return ft_fail(ctx, FT_ERR_ARG, "ft_test_join: an item longer than the stride");
+    const int64_t in_floats = join_offsets(B, n, off);
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    FT_TRY(join_alloc(ctx, (size_t)in_floats, (size_t)need));
+    for (int b = 0; b < B; ++b)
+        if (n[b] > 0)
+            FT_HIP(ctx, hipMemcpyAsync(s->join_in + off[b], x + (size_t)b * stride, (size_t)n[b] * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    FT_TRY(join_run(ctx, B, n, off, jp, gaps, started, y, total, cuts, need, true));
+    const uint32_t mark = 0xFFFFFFFEu;
+    for (int64_t i = need; i < capacity; ++i) memcpy(y + i, &mark, sizeof mark);
+    return FT_OK;
 }
 
 static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sample_rate, int32_t pct, ft_codec_stream** out,

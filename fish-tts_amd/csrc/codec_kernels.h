@@ -8,6 +8,8 @@
 //   * Linear / 1x1 conv: one tap
 // Snake (x + sin^2(ax)/a) is applied once per element in the producer's epilogue, never per tap.
 #pragma once
+#include <limits.h>
+
 #include <algorithm>
 
 #include "common.h"
@@ -1714,6 +1716,139 @@ static __global__ __launch_bounds__(RS_THREADS) void pitch_kernel(const PsSeg* s
             for (int t = 0; t < s.K; ++t) acc += (g * w0[t] + f * w1[t]) * xp[t];
             s.y[n] = acc;
         }
+    }
+}
+
+// ---- join stage (ft_codec_decode_join, ft_test_join; stated in fishtts_hip.h): the items of a call - whole utterances at
+// the output rate, left on the device by the stages above - trimmed to their loud part, faded and laid out behind their
+// gaps as one waveform.  Three launches whatever the number of items (the item is blockIdx.z of a device table):
+//   join_edges_kernel     first / last loud window of every item: per thread over its samples (16-byte loads: the items
+//                         lie on 16-byte boundaries of the input buffer), per wave by shuffles, per workgroup through
+//                         LDS, then one atomicMin / atomicMax per workgroup that saw a loud sample (at most
+//                         JOIN_EDGE_BLOCKS per item: at the default threshold nearly every wave sees one, and with
+//                         one pair of atomics per wave on the same two words the launch took 56 us for 12 items of
+//                         246 000 samples)
+//   join_layout_kernel    one workgroup: cuts and fade lengths per item, then the running offsets (at most 64 items)
+//   join_assemble_kernel  the output: 16-byte stores on the aligned groups of every item's destination range; the source
+//                         offset a_b is arbitrary, so each lane loads its four samples with four 4-byte loads (lanes 16
+//                         bytes apart: a wave's loads together cover one contiguous 1 KiB run); scalar stores on the up
+//                         to three samples at either end
+struct JoinItem {
+    const float* x;            // the item's samples (device, 16-byte aligned)
+    long long n, gap;          // samples; zeros in front of the piece (when something precedes it)
+    int first, last;           // loud windows: the host sets INT_MAX / -1, join_edges_kernel reduces into them
+    long long a, e, f, G, off; // join_layout_kernel: cut positions, fade length, the gap that counts, output offset of the gap
+};
+struct JoinTab {
+    long long total;           // out: samples of the whole output
+    long long cuts[2 * 64];    // out: (a_b, e_b) per item; `total` and `cuts` are what the host reads back
+    int started, B;
+    JoinItem it[64];
+};
+constexpr int JOIN_THREADS = 256, JOIN_EDGE_BLOCKS = 64;
+
+__device__ inline void join_loud(float v, float thr, long long i, int hop, int& lo, int& hi) {
+    if (fabsf(v) >= thr) {     // (false for a NaN)
+        const int w = (int)(i / hop);
+        lo = min(lo, w);
+        hi = max(hi, w);
+    }
+}
+
+static __global__ __launch_bounds__(JOIN_THREADS) void join_edges_kernel(JoinTab* tab, float thr, int hop) {
+    JoinItem& it = tab->it[blockIdx.z];
+    const long long n = it.n, n4 = n >> 2;
+    const float4* x4 = (const float4*)it.x;
+    int lo = INT_MAX, hi = -1;
+    for (long long q = (long long)blockIdx.x * JOIN_THREADS + threadIdx.x; q < n4; q += (long long)gridDim.x * JOIN_THREADS) {
+        const float4 v = x4[q];
+        join_loud(v.x, thr, 4 * q, hop, lo, hi);
+        join_loud(v.y, thr, 4 * q + 1, hop, lo, hi);
+        join_loud(v.z, thr, 4 * q + 2, hop, lo, hi);
+        join_loud(v.w, thr, 4 * q + 3, hop, lo, hi);
+    }
+    if (blockIdx.x == 0 && 4 * n4 + threadIdx.x < n) join_loud(it.x[4 * n4 + threadIdx.x], thr, 4 * n4 + threadIdx.x, hop, lo, hi);
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o));
+        hi = max(hi, __shfl_xor(hi, o));
+    }
+    __shared__ int wlo[JOIN_THREADS / 64], whi[JOIN_THREADS / 64];
+    if ((threadIdx.x & 63) == 0) {
+        wlo[threadIdx.x >> 6] = lo;
+        whi[threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < JOIN_THREADS / 64; ++w) {
+            lo = min(lo, wlo[w]);
+            hi = max(hi, whi[w]);
+        }
+        if (hi >= 0) {      // all of an item's workgroups meet on these two words: one pair of atomics per workgroup
+            atomicMin(&it.first, lo);
+            atomicMax(&it.last, hi);
+        }
+    }
+}
+
+static __global__ __launch_bounds__(64) void join_layout_kernel(JoinTab* tab, int hop, int keep, int fade) {
+    const int B = tab->B, b = threadIdx.x;
+    if (b < B) {
+        JoinItem& it = tab->it[b];
+        long long a = 0, e = 0;
+        if (it.last >= 0) {
+            a = max(0LL, (long long)it.first * hop - keep);
+            e = min(it.n, ((long long)it.last + 1) * hop + keep);
+        }
+        it.a = tab->cuts[2 * b] = a;
+        it.e = tab->cuts[2 * b + 1] = e;
+        it.f = min((long long)fade, (e - a) / 2);
+    }
+    __syncthreads();
+    if (b == 0) {
+        bool s = tab->started != 0;
+        long long off = 0;
+        for (int c = 0; c < B; ++c) {
+            JoinItem& it = tab->it[c];
+            const long long m = it.e - it.a, G = m > 0 && s ? it.gap : 0;
+            it.G = G;
+            it.off = off;
+            off += G + m;
+            s = s || m > 0;
+        }
+        tab->total = off;
+    }
+}
+
+// Output sample d of an item's range [off, off + G + m): a zero of the gap, or piece sample i with its ramp.
+__device__ inline float join_sample(const JoinItem& it, const float* x, long long m, double den, long long d) {
+    const long long i = d - it.off - it.G;
+    if (i < 0) return 0.f;
+    float v = x[i];
+    if (i < it.f) v = v * (float)((double)(2 * i + 1) / den);
+    else if (i >= m - it.f) v = v * (float)((double)(2 * (m - 1 - i) + 1) / den);
+    return v;
+}
+
+static __global__ __launch_bounds__(JOIN_THREADS) void join_assemble_kernel(const JoinTab* tab, float* y) {
+    const JoinItem it = tab->it[blockIdx.z];
+    const long long m = it.e - it.a, d0 = it.off, d1 = d0 + it.G + m;
+    if (d1 == d0) return;
+    const float* x = it.x + it.a;
+    const double den = (double)(2 * it.f);
+    // whole 16-byte groups [4 q0, 4 q1) of y inside [d0, d1); head [d0, hb) and tail [te, d1) hold at most 3 samples each
+    const long long q0 = (d0 + 3) >> 2, q1 = d1 >> 2, hb = min(d1, 4 * q0), te = max(hb, 4 * q1);
+    for (long long q = q0 + (long long)blockIdx.x * JOIN_THREADS + threadIdx.x; q < q1; q += (long long)gridDim.x * JOIN_THREADS) {
+        float4 v;
+        v.x = join_sample(it, x, m, den, 4 * q);
+        v.y = join_sample(it, x, m, den, 4 * q + 1);
+        v.z = join_sample(it, x, m, den, 4 * q + 2);
+        v.w = join_sample(it, x, m, den, 4 * q + 3);
+        ((float4*)y)[q] = v;
+    }
+    if (blockIdx.x == 0) {
+        const long long t = threadIdx.x;
+        if (d0 + t < hb) y[d0 + t] = join_sample(it, x, m, den, d0 + t);
+        if (te + t < d1) y[te + t] = join_sample(it, x, m, den, te + t);
     }
 }
 

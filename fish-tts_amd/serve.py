@@ -20,7 +20,8 @@ With no work the thread blocks on the request queue: no GPU work, no spinning.  
 audio; the AR loop never waits for it.  seamless=True streams are cut as batch_stream cuts them (exactly `min_first_chunk`
 frames, then `chunk_tokens`, the last generated column held back) and every ready chunk goes through one decode_streams
 call, one CodecStream per request; seamless=False chunks are FishTTS.synthesize_stream's (every generated column, each
-chunk decoded from zero state); a non-streaming request's WAV is decoded when it ends.  Per request the codes are those of
+chunk decoded from zero state); a non-streaming request's WAV is decoded when it ends; a "codes" request (the segments of FishTTS.synthesize_long) is handed its codes
+and no audio - its caller decodes and joins them under codec_lock.  Per request the codes are those of
 a single run with the same seed - the draws depend on (seed, frame, codebook, index), not on the slot or the schedule: bit
 for bit on an engine of up to 4 slots, within the evaluation-order margin of the MFMA launches beyond (bf16 and fp16, batch.py).
 
@@ -111,13 +112,14 @@ class _Request:
 
     def __init__(self, utt: Utterance, n_prefix: int, mode: str, chunk_tokens: int, min_first_chunk: int,
                  rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None):
-        self.utt, self.n_prefix, self.mode = utt, n_prefix, mode          # mode: "wav" | "seamless" | "chunks"
+        self.utt, self.n_prefix, self.mode = utt, n_prefix, mode          # mode: "wav" | "seamless" | "chunks" | "codes"
+        self.cache = None             # a PrefixCache of the caller's own for this request's voice (None: the server's)
         self.rate = rate              # output sample rate (None: the codec's own)
         self.speed = speed            # speaking rate (None: the model's own pace)
         self.pitch = pitch            # pitch shift in semitones (None: the model's own pitch)
         self.fx = rate is not None or speed is not None or pitch is not None      # an output stage holds back a tail
         self.skw = {k: v for k, v in (("speed", speed), ("pitch", pitch)) if v is not None}
-        self.cut = None if mode == "wav" else ChunkCutter(chunk_tokens, min_first_chunk, hold_back=mode == "seamless")
+        self.cut = None if mode in ("wav", "codes") else ChunkCutter(chunk_tokens, min_first_chunk, hold_back=mode == "seamless")
         self.out: "queue.Queue" = queue.Queue()
         self.cancelled = False        # the caller went away (or close(cancel=True))
         self.finished = False         # generation over: no more columns will come
@@ -147,6 +149,7 @@ class BatchServer:
         self._work = threading.Condition(self._lock)      # scheduler: arrivals, cancellations, close
         self._codec_cv = threading.Condition(self._lock)  # codec worker: ready chunks, finished requests
         self._queue: deque = deque()
+        self._retired: list = []                 # callers' own PrefixCaches (submit(voice_cache=)) to clear: scheduler thread
         self._live: List[_Request] = []          # submitted, not yet ended on the codec side
         self._closing = False
         self._sched_done = False
@@ -213,13 +216,17 @@ class BatchServer:
 
     def submit(self, utt: Utterance, n_prefix: int = 0, stream: bool = False, seamless: bool = False,
                chunk_tokens: int = 20, min_first_chunk: int = 10, sample_rate: Optional[int] = None,
-               speed: Optional[float] = None, pitch: Optional[float] = None) -> _Request:
+               speed: Optional[float] = None, pitch: Optional[float] = None, codes: bool = False,
+               voice_cache=None) -> _Request:
         """Queues one prepared utterance (the layer under synthesize / synthesize_stream); its output arrives on
-        `.out`.  Raises ServerClosed once the server is closing or has failed."""
+        `.out`.  `codes`: the output is the utterance's codes (Utterance.codes()), no audio; `voice_cache`: the PrefixCache
+        its voice prefix lives in instead of the server's.  Raises ServerClosed once the server is closing or has failed."""
         if self._codec is None:
             raise RuntimeError("Vocoder not loaded")
-        req = _Request(utt, n_prefix, ("seamless" if seamless else "chunks") if stream else "wav", chunk_tokens,
+        mode = "codes" if codes else ("seamless" if seamless else "chunks") if stream else "wav"
+        req = _Request(utt, n_prefix, mode, chunk_tokens,
                        min_first_chunk, _output_rate(sample_rate), _output_speed(speed), _output_pitch(pitch, speed))
+        req.cache = voice_cache
         with self._lock:
             if self._error is not None:
                 raise ServerClosed(f"BatchServer failed: {self._error!r}") from self._error
@@ -229,6 +236,47 @@ class BatchServer:
             self._live.append(req)
             self._work.notify_all()
         return req
+
+    def submit_codes(self, text: str, references=None, temperature: float = 0.7, top_p: float = 0.8,
+                     repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0, voice_cache=None) -> _Request:
+        """One segment of a long text (FishTTS.synthesize_long): a request whose output is its codes; take_codes waits
+        for them.  `voice_cache`: a PrefixCache of the caller's own for the request's voice, so that a voice made up for
+        one call stays out of the cache of the user's voices (the caller clears it when its requests have ended)."""
+        utt, n_prefix = self._prepare(text, references, temperature, top_p, repetition_penalty, max_tokens, seed)
+        return self.submit(utt, n_prefix, codes=True, voice_cache=voice_cache)
+
+    def take_codes(self, req: _Request) -> np.ndarray:
+        item = req.out.get()
+        if isinstance(item, _Failed):
+            raise item.error
+        return item
+
+    def cancel(self, req: _Request) -> None:
+        """Gives up a submitted request: its slot is freed at the next burst boundary, its caller gets a RuntimeError."""
+        with self._lock:
+            self._cancel_locked(req, RuntimeError("BatchServer: request cancelled"))
+            self._work.notify_all()
+            self._codec_cv.notify_all()
+
+    def retire_cache(self, cache) -> None:
+        """The caller is done with a PrefixCache it passed as `voice_cache`: the scheduler thread - the only user of the
+        engine, and the only one that looks a prefix up - clears it at its next boundary at which no queued request still
+        names it (cancel those first); after the scheduler has stopped it is cleared here."""
+        with self._lock:
+            if not self._sched_done:
+                self._retired.append(cache)
+                self._work.notify_all()
+                return
+        cache.clear()
+
+    def _clear_retired_locked(self) -> None:
+        """Scheduler thread, at a boundary: every admitted request is past its prompt pass, so a retired cache that no
+        queued request names is out of use."""
+        keep = [c for c in self._retired if any(r.cache is c for r in self._queue)]
+        for c in self._retired:
+            if not any(c is k for k in keep):
+                c.clear()
+        self._retired = keep
 
     def stats(self) -> dict:
         """Counters: requests admitted / completed / cancelled, slot moves, lock-step frame steps by width
@@ -322,8 +370,10 @@ class BatchServer:
             while True:
                 with self._lock:
                     freed = self._retire_locked()
+                    self._clear_retired_locked()
                     while not self._queue and not any(self._owner) and not self._closing:
                         self._work.wait()
+                        self._clear_retired_locked()
                     if self._error is not None or (self._closing and not self._queue and not any(self._owner)):
                         return
                     free = [s for s in range(B) if self._owner[s] is None]
@@ -349,6 +399,9 @@ class BatchServer:
         finally:
             with self._lock:
                 self._sched_done = True
+                for c in self._retired:          # (no request is prefilled any more)
+                    c.clear()
+                self._retired = []
                 self._codec_cv.notify_all()
 
     def _retire_locked(self) -> List[int]:
@@ -375,6 +428,9 @@ class BatchServer:
         voices: set = set()
         for r, s in zip(reqs, free):
             voice = None
+            if r.cache is not None:                   # a cache of the caller's own: nothing of the server's can be evicted
+                groups[-1].append((r, s, r.n_prefix >= r.cache.min_positions))
+                continue
             if cache is not None and r.n_prefix >= cache.min_positions:
                 voice = np.ascontiguousarray(r.utt.prompt[:, :r.n_prefix], dtype=np.int32).tobytes()
                 if voice not in voices and len(voices) >= max(1, cache.capacity):
@@ -390,7 +446,8 @@ class BatchServer:
         reqs, slots = [r for r, _, _ in group], [s for _, s, _ in group]
         for r, s, voiced in group:
             # built once per voice, in the slot the request is about to take: no active slot is touched
-            r.utt.prefix = self._prefix_cache.get(eng, r.utt.prompt[:, :r.n_prefix], slot=s) if voiced else None
+            cache = r.cache if r.cache is not None else self._prefix_cache
+            r.utt.prefix = cache.get(eng, r.utt.prompt[:, :r.n_prefix], slot=s) if voiced else None
         sps = [eng._sampling(r.utt.temperature, r.utt.top_p, r.utt.repetition_penalty, r.utt.seed, r.utt.ban_eos)
                for r in reqs]
         firsts = eng.prefill_many([np.ascontiguousarray(r.utt.prompt, dtype=np.int32) for r in reqs], sps, slots,
@@ -462,8 +519,9 @@ class BatchServer:
                         seam = [r for r in live if not r.cancelled and r.mode == "seamless" and r.cut.ready]
                         plain = [r for r in live if not r.cancelled and r.mode == "chunks" and r.cut.ready]
                         wavs = [r for r in live if not r.cancelled and r.mode == "wav" and r.finished]
+                        coded = [r for r in live if not r.cancelled and r.mode == "codes" and r.finished]
                         ends = [r for r in live if not r.cancelled and r.cut is not None and r.cut.done and not r.cut.ready]
-                        if gone or seam or plain or wavs or ends:
+                        if gone or seam or plain or wavs or coded or ends:
                             break
                         if self._sched_done and not self._live:
                             return
@@ -471,7 +529,7 @@ class BatchServer:
                     seam_chunks = [r.cut.ready.popleft() for r in seam]
                     seam_final = [r.cut.done and not r.cut.ready for r in seam]
                     plain_chunks = [r.cut.ready.popleft() for r in plain]
-                    for r in gone + wavs + ends:
+                    for r in gone + wavs + coded + ends:
                         r.taken = True                   # its last hand-out is under way: not picked again
                 for r in gone + ends:
                     if r in ends and r.fx and r.stream is not None and not r.stream.finished:
@@ -481,6 +539,8 @@ class BatchServer:
                         r.stream.close()
                         r.stream = None
                     self._last_out(r, _END if r in ends else None)
+                for r in coded:
+                    self._last_out(r, r.utt.codes())     # no audio here: the caller decodes and joins under codec_lock
                 with self.codec_lock:
                     if seam:
                         for r, c in zip(seam, seam_chunks):

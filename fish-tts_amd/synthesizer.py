@@ -285,11 +285,15 @@ class FishTTS:
         return self._decode_to_wav(np.concatenate(codes_list, axis=1), rate, fx.get("speed"), **_pkw(fx))
 
     def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
-                          repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]]):
+                          repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]],
+                          made: Optional[dict] = None):
         """The engines and Utterances of a batch run (synthesize_batch, synthesize_batch_stream); call with _gen_lock
         held.  More engines than the first one when batch_streams > 1 and the texts outnumber max_batch (created on first
         use, kept); a voice's K/V prefix from the cache, spread over the engines; utterance i draws with seed + i, or
-        seeds[i]."""
+        seeds[i].  `made` (a dict the caller owns): the voice is one made up for this call - its prefix is built directly with
+        engine.build_prefix, once per engine, kept in `made` and freed by the caller; the cache of the user's voices is
+        not touched."""
+        cache = self._prefix_cache
         from .batch import Utterance
         from .prompt import build_prompt_split
         assert 0 < top_p <= 1, "top_p must be in (0, 1]"
@@ -310,9 +314,15 @@ class FishTTS:
             if enc.shape[1] > self._engine.args.max_seq_len - 2048:
                 raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
             prefix = None
-            if self._prefix_cache is not None and n_prefix >= self._prefix_cache.min_positions:
+            if cache is not None and n_prefix >= cache.min_positions:
                 # a saved prefix lives in one engine's memory and pins its utterance there: spread them evenly
-                prefix = self._prefix_cache.get(engines[i % len(engines)], enc[:, :n_prefix])
+                eng = engines[i % len(engines)]
+                if made is None:
+                    prefix = cache.get(eng, enc[:, :n_prefix])
+                else:
+                    if id(eng) not in made:
+                        made[id(eng)] = eng.build_prefix(np.ascontiguousarray(enc[:, :n_prefix], dtype=np.int32))
+                    prefix = made[id(eng)]
             utts.append(Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seeds[i] if seeds is not None else seed + i,
                                   prefix=prefix))
         return engines, utts
@@ -384,6 +394,208 @@ class FishTTS:
 
         return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
                                  min_first_chunk=min_first_chunk, **fx)
+
+    # ------------------------------------------------------------------ long texts (extension)
+    def _long_plan(self, text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch):
+        """Every check of a long-text call, before any device work: (texts, output rate, output keywords, join parameters,
+        gaps).  ValueError for a bad value."""
+        from .longform import join_params, split_text
+        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed, pitch)
+        jp, gap, pgap = join_params(rate, pause, paragraph_pause, silence_db)
+        segs = split_text(text, max_chars, min_chars)
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        return [s.text for s in segs], rate, fx, tuple(jp), [pgap if s.paragraph else gap for s in segs]
+
+    def _long_generate(self, texts, references, sampling, seed: int, emit, stopped) -> None:
+        """The codes of every segment, emit(i, codes) as each is complete (from any thread).  Segment i draws with seed + i;
+        all go through one lock-step batch with refill (_batch_utterances, run_batch / run_batch_streams), the voice prefix
+        from the cache.  Without any reference voice segment 0 runs first, on its own, and its text and codes are the
+        voice of every later segment - its K/V prefix built directly (engine.build_prefix) and freed when the call ends, so
+        the cache of the user's voices is neither entered nor evicted from.  `stopped()`: the consumer went away."""
+        from .batch import run_batch, run_batch_streams
+
+        def guard(i, block):
+            if stopped():
+                raise _LongStopped()
+
+        def run(texts_, refs, seed_, first, made=None):
+            engines, utts = self._batch_utterances(texts_, refs, *sampling, seed_, None, made=made)
+            done = lambda j: emit(first + j, utts[j].codes())   # noqa: E731
+            if len(engines) > 1:
+                run_batch_streams(engines, utts, on_frames=guard, on_done=done)
+            else:
+                run_batch(self._engine, utts, on_frames=guard, on_done=done)
+            return utts
+
+        made = None
+        with self._gen_lock:
+            try:
+                start = 0
+                if not self._get_prompt_data(references)[1] and len(texts) > 1:
+                    codes0 = run(texts[:1], references, seed, 0)[0].codes()
+                    start = 1
+                    if codes0.shape[1]:
+                        references, made = [VoiceProfile(codes=codes0, text=texts[0])], {}
+                if start < len(texts):
+                    run(texts[start:], references, seed + start, start, made)
+            finally:
+                for pf in (made or {}).values():
+                    pf.free()
+
+    def _long_serve(self, srv, texts, references, sampling, seed: int):
+        """_long_generate through an open BatchServer: the segments as requests whose output is their codes
+        (BatchServer.submit_codes).  Returns the requests' results as a list of callables in text order, each blocking
+        until its codes are there, and a release() to call when all were taken.  ServerClosed (nothing was handed out
+        yet): the caller serves the text itself."""
+        from .generation import PrefixCache
+        from .serve import ServerClosed
+        own, reqs, first = None, [], []
+        try:
+            if not self._get_prompt_data(references)[1] and len(texts) > 1:
+                codes0 = srv.take_codes(srv.submit_codes(texts[0], references, *sampling, seed))
+                first = [lambda: codes0]
+                if codes0.shape[1]:
+                    references = [VoiceProfile(codes=codes0, text=texts[0])]
+                    if self._prefix_cache is not None:
+                        own = PrefixCache(capacity=1, min_positions=self._prefix_cache.min_positions)
+            for k in range(len(first), len(texts)):
+                reqs.append(srv.submit_codes(texts[k], references, *sampling, seed + k, voice_cache=own))
+        except ServerClosed:
+            if own is not None:
+                srv.retire_cache(own)       # the closing server still finishes what it took, then frees the prefix
+            raise
+
+        def release(cancel: bool = False):
+            if cancel:
+                for r in reqs:
+                    srv.cancel(r)                # (nothing happens to a request that has ended)
+            if own is not None:
+                srv.retire_cache(own)        # freed on the server's scheduler thread, once none of its requests can use it
+        return first + [lambda r=r: srv.take_codes(r) for r in reqs], release
+
+    def synthesize_long(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
+                        top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
+                        pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
+                        max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
+                        speed: Optional[float] = None, pitch: Optional[float] = None) -> bytes:
+        """Extension: a text of any length -> one WAV.  The text is split into segments of at most `max_chars` bytes at
+        sentence ends (longform.split_text; pieces below `min_chars` join a neighbour), every segment is an utterance of
+        its own - `max_tokens` frames at most each, segment i drawing with seed + i - and all of them run as ONE lock-step
+        batch with refill over the engine's `max_batch` slots, the voice prefix restored per slot from the cache (with
+        max_batch=1 the call degrades to a loop; the result is built the same way).  The codec then decodes the segments
+        and joins them on the GPU (CodecHipEngine.decode_join): each is trimmed to its loud part - 5 ms windows with a
+        sample at or above `silence_db` dB full scale, 30 ms kept around them - faded over 5 ms at both cuts, and laid out
+        behind `pause` seconds of silence, `paragraph_pause` after a paragraph break; silence_db=None trims and fades
+        nothing.  One voice throughout: with no reference voice (neither `references` nor set_references) segment 0 is
+        generated first and then serves, text and codes, as the reference of every other segment.  `sample_rate`,
+        `speed`, `pitch` as synthesize_at, applied per segment before the join.  While a BatchServer is open the segments
+        join its batch.  ValueError before any device work: pause / paragraph_pause outside [0, 5] s, silence_db outside
+        [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch."""
+        texts, rate, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
+                                                    sample_rate, speed, pitch)
+        sampling = (temperature, top_p, repetition_penalty, max_tokens)
+        codes = self._long_codes_served(texts, references, sampling, seed)
+        lock = None
+        if codes is None:
+            got = {}
+            self._long_generate(texts, references, sampling, seed, got.__setitem__, lambda: False)
+            codes = [got[i] for i in range(len(texts))]
+        else:
+            codes, lock = codes
+        if lock is not None:
+            with lock:
+                audio, _ = self._vocoder.decode_join(codes, rate, fx.get("speed"), fx.get("pitch"), jp, gaps)
+        else:
+            audio, _ = self._vocoder.decode_join(codes, rate, fx.get("speed"), fx.get("pitch"), jp, gaps)
+        if not len(audio):
+            raise RuntimeError("No audio generated")
+        return self._to_wav_bytes(audio, self.sample_rate if rate is None else rate)
+
+    def _long_codes_served(self, texts, references, sampling, seed):
+        """([codes of every segment], the server's codec lock) from an open BatchServer; None: no server (or it closed before
+        it took the text) - the caller generates."""
+        from .serve import ServerClosed
+        srv = getattr(self, "_server", None)
+        if srv is None:
+            return None
+        try:
+            takes, release = self._long_serve(srv, texts, references, sampling, seed)
+        except ServerClosed:
+            return None
+        try:
+            return [t() for t in takes], srv.codec_lock
+        finally:
+            release()
+
+    def synthesize_long_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
+                               top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
+                               pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
+                               max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
+                               speed: Optional[float] = None, pitch: Optional[float] = None) -> Iterator[bytes]:
+        """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
+        next segments not yet handed out are complete, the longest such run is decoded and joined as one group
+        (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
+        chunks concatenate to synthesize_long's PCM byte for byte.  No empty chunk is yielded.  The arguments are checked
+        here, at the call; generation holds _gen_lock on its own thread and stops within one burst when the generator is
+        abandoned."""
+        texts, rate, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
+                                                    sample_rate, speed, pitch)
+        sampling = (temperature, top_p, repetition_penalty, max_tokens)
+        return self._long_chunks(texts, references, sampling, seed, rate, fx, jp, gaps)
+
+    def _long_chunks(self, texts, references, sampling, seed, rate, fx, jp, gaps) -> Iterator[bytes]:
+        from .longform import ready_prefixes
+        from .serve import ServerClosed
+        n = len(texts)
+        q: "queue.Queue" = queue.Queue()
+        stop = threading.Event()
+        srv, lock, release, threads = getattr(self, "_server", None), None, None, []
+        if srv is not None:
+            try:
+                takes, release = self._long_serve(srv, texts, references, sampling, seed)
+                lock = srv.codec_lock
+            except ServerClosed:
+                srv = None                       # closed meanwhile: served here, once the server has let go of _gen_lock
+
+        def feed_served() -> None:
+            try:
+                for i, take in enumerate(takes):
+                    q.put((i, take()))
+            except BaseException as e:  # noqa: BLE001
+                q.put(e)
+
+        def feed_own() -> None:
+            try:
+                self._long_generate(texts, references, sampling, seed, lambda i, c: q.put((i, c)), stop.is_set)
+            except _LongStopped:
+                pass
+            except BaseException as e:  # noqa: BLE001
+                q.put(e)
+
+        threads.append(threading.Thread(target=feed_own if srv is None else feed_served, daemon=True))
+        threads[0].start()
+        started = False
+        try:
+            for first, group in ready_prefixes(q, n):
+                kw = dict(sample_rate=rate, speed=fx.get("speed"), pitch=fx.get("pitch"), params=jp,
+                          gaps=gaps[first:first + len(group)], started=started)
+                if lock is not None:
+                    with lock:
+                        audio, _ = self._vocoder.decode_join(group, **kw)
+                else:
+                    audio, _ = self._vocoder.decode_join(group, **kw)
+                if len(audio):
+                    started = True
+                    yield (np.clip(audio, -1.0, 1.0) * 32767).astype(np.int16).tobytes()   # synthesize_long's samples
+        finally:
+            stop.set()
+            if release is not None:
+                release(cancel=True)
+            for t in threads:
+                t.join()
+        if not started:
+            raise RuntimeError("No audio generated")
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
@@ -671,6 +883,10 @@ class FishTTS:
     @property
     def precision(self) -> str:
         return self._precision
+
+
+class _LongStopped(Exception):
+    """The consumer of synthesize_long_stream went away: generation stops at its next block of frames."""
 
 
 def output_rate(sample_rate: Optional[int]) -> Optional[int]:

@@ -288,6 +288,50 @@ ft_status ft_codec_decode_fxp(ft_ctx* ctx, const int32_t* codes, int32_t B, int3
  * one call; ft_codec_stream_decode and ft_codec_stream_decode_many refuse them (FT_ERR_STATE). */
 ft_status ft_codec_stream_begin_fxp(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents,
                                     ft_codec_stream** out);
+/* Join.  The utterances of one call - the sentences of a long text - trimmed to their loud part, faded at the cuts and laid
+ * out behind pauses as ONE waveform, on the device, at the end of the chain: codec -> time-scale stage -> pitch stage ->
+ * rate resampler -> join, all on the codec's stream.  The reference speaks a text as one utterance and has no such stage
+ * (generate_long, inference.py:741-846, does not split the text).  The stage, which fixes every bit of its result:
+ *   Inputs: item b has samples x_b[0 .. n_b), float32, at the output rate; ft_join_params {threshold >= 0, hop H >= 1,
+ *   keep >= 0, fade F >= 0} (sample counts at the output rate); gaps[b] >= 0 samples; started in {0, 1}: audio of the same
+ *   document went out before this call.
+ *   Edges: window j of item b covers [j H, min((j + 1) H, n_b)), j = 0 .. ceil(n_b / H) - 1.  A window is loud when a sample
+ *   of it has |x| >= threshold, compared in float32 (a NaN is never loud).  first / last = the lowest / highest loud window.
+ *   No loud window: a_b = e_b = 0, the item contributes nothing.  Else a_b = max(0, first H - keep),
+ *   e_b = min(n_b, (last + 1) H + keep); m_b = e_b - a_b.
+ *   Fades: f_b = min(F, m_b / 2) (integer division).  Piece sample i is x_b[a_b + i]; for i < f_b it is multiplied by
+ *   ramp(i), for i >= m_b - f_b by ramp(m_b - 1 - i), ramp(j) = (float)((double)(2 j + 1) / (double)(2 f_b)): one float32
+ *   multiply per faded sample and nothing else touches a sample (the two ramps never overlap).
+ *   Layout: s_b = started || any m_c > 0 for c < b; G_b = gaps[b] if m_b > 0 and s_b, else 0 (gap b comes before piece b; it is
+ *   dropped for an empty piece and before the first audio of the document); off_b = sum_{c < b} (G_c + m_c).  The output
+ *   holds G_b zeros (+0.0) at off_b, then the piece; total = sum (G_b + m_b).
+ *   Outputs: audio[0 .. total), total and cuts[b] = (a_b, e_b).
+ * With threshold = 0, keep = 0, fade = 0 the join is plain concatenation with gaps; a piece depends on its own item only, so
+ * the items of a document may be split over several calls, `started` carried (1 once a call returned total > 0).
+ * Three launches whatever B (edges, layout, assemble; the item is a grid dimension), then two copies to the host: total
+ * with the cuts (1 KB), and `total` samples - one audio copy per call, not one per item. */
+typedef struct ft_join_params {
+    float threshold;           /* linear amplitude */
+    int32_t hop, keep, fade;   /* samples at the output rate */
+} ft_join_params;
+/* ft_codec_decode_fxp with the items joined on the device: item b's samples before the join are, bit for bit, row b of
+ * ft_codec_decode_fxp for the same arguments (out_lens[b] of them).  Limits: 1 <= B <= 64, lens[b] >= 0 (lens NULL: T each),
+ * sum(lens) <= max_frames.  capacity = the room in `audio` (samples); it must be at least sum(out_lens) + sum(gaps).
+ * audio receives `total` samples (nothing past them is written), *total their number, cuts B x 2 the (a_b, e_b).  Every
+ * argument is checked before any device work: FT_ERR_ARG (a bad rate, speed, pitch or combination; B outside [1, 64]; a null
+ * pointer; a length outside [0, T]; bad join parameters; a negative gap; started not 0 or 1; capacity too small;
+ * more than 2^28 samples of items and gaps), FT_ERR_TOO_LONG (T or sum(lens) beyond max_frames).  The first call allocates the
+ * stage's table (64 items, < 8 KB) and, besides what ft_codec_decode_fxp allocates for the same arguments, an input buffer
+ * of sum(out_lens) (every item rounded up to 4 samples) and an output buffer of sum(out_lens) + sum(gaps) float32; a later
+ * call that needs more replaces them by larger ones. */
+ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                               int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, const ft_join_params* jp,
+                               const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
+                               int64_t* cuts);
+/* Host only (no context, no device): consecutive items of lens[i] code frames grouped into ft_codec_decode_join calls of at
+ * most 64 items and max_frames frames; ends[g] (room for n) = one past the last item of group g.  Returns the number of
+ * groups, -1 for a negative length, an item beyond max_frames or a null pointer. */
+int32_t ft_join_groups(const int32_t* lens, int32_t n, int32_t max_frames, int32_t* ends);
 /* Codec encode = vocoder.encode(audio, lengths) of encode_reference (synthesizer.py:325-357, vocoder.py:885-904):
  * mono f32 audio at the codec sample rate (host), right-padded to whole frames -> codes (num_codebooks+1) x T'
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */

@@ -62,6 +62,16 @@ ft_status ft_test_timescale(ft_ctx* ctx, const float* x, int64_t n, int32_t spee
 ft_status ft_test_pitch(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, int32_t cents, float* y, int64_t* n_out,
                         float* mid, int64_t* n_mid, int32_t* deltas, int32_t* n_frames);
 
+/* Test hook: the join stage of ft_codec_decode_join alone on B host waveforms, item b = x[b * stride .. b * stride + n[b])
+ * (n[b] <= stride), which the hook uploads to the stage's input buffer as the decode leaves its items there.  y (room for
+ * `capacity` >= sum(n) + sum(gaps) samples) receives the *total joined samples.  The hook fills the stage's output buffer
+ * with the bit pattern 0xFFFFFFFE (a NaN) before the launches and copies all sum(n) + sum(gaps) samples of it back (the rest
+ * of y, up to capacity, gets the same pattern on the host), so y[*total .. capacity) shows whether the stage wrote past its
+ * output.  cuts: B x 2.  Refused
+ * before any device work, y untouched: what ft_codec_decode_join refuses (FT_ERR_ARG), n[b] > stride (FT_ERR_ARG). */
+ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, const int64_t* n, const ft_join_params* jp,
+                       const int64_t* gaps, int32_t started, float* y, int64_t capacity, int64_t* total, int64_t* cuts);
+
 /* Test hook: a launch trace of the codec.  ft_test_codec_trace_arm makes the NEXT ft_codec_decode (B = 1; any other
  * B disarms it untraced) or ft_codec_encode on this context record one entry per kernel launch of the one-shot path, in
  * launch order: a stable stage name ("post.2.wo", "up.1.pw1", "dec.3.u2.c7", "enc.2.sc", ...), the rows and columns
