@@ -120,6 +120,11 @@ SYMBOLS = {
     "ft_test_wide_linear": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
                                         _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ft_test_wide_attn": (C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "ft_test_pf_linear": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ft_test_pf_norm": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "ft_test_pf_attn": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                    C.POINTER(C.c_int32)]),
 }
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",

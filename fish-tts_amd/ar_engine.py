@@ -331,6 +331,57 @@ class ARHipEngine:
                                                C.byref(sp)), "ft_test_wide_attn")
         return y, kc, vc, sp.value
 
+    def test_pf_linear(self, form: int, X: np.ndarray, W: np.ndarray, bias=None, resid=None, alias: bool = False):
+        """Test hook (ft_test_pf_linear): one Linear product of the bf16 prompt pass through the product's dispatcher.  form
+        0 wqkv, 1 wo / w2 (resid (S, N) f32; alias: in place), 2 w13 (SwiGLU).  X (S, K), W (N, K): bf16 patterns; bias (N,)
+        f32.  Returns (out, tail, variant): the S written rows (f32 for forms 0 and 1, else uint16), the rows up to the next
+        multiple of 128, the kernel class that ran."""
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        X, W = np.ascontiguousarray(X, dtype=np.uint16), np.ascontiguousarray(W, dtype=np.uint16)
+        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        resid = None if resid is None else np.ascontiguousarray(resid, dtype=np.float32)
+        (S, K), N = X.shape, W.shape[0]
+        assert W.shape == (N, K) and (resid is None or resid.shape == (S, N)), (X.shape, W.shape)
+        oc, dt = (N // 2 if form == 2 else N), (np.uint16 if form == 2 else np.float32)
+        out, tail = np.zeros((S, oc), dtype=dt), np.zeros((127, oc), dtype=dt)
+        tr, var = C.c_int32(0), C.c_int32(-1)
+        self._check(self.lib.ft_test_pf_linear(self._h, form, S, N, K, ptr(X), ptr(W), ptr(bias), ptr(resid), 1 if alias else 0,
+                                               ptr(out), ptr(tail), C.byref(tr), C.byref(var)), "ft_test_pf_linear")
+        return out, tail[: tr.value], var.value
+
+    def test_pf_norm(self, x: np.ndarray, gain: np.ndarray):
+        """Test hook (ft_test_pf_norm): the row RMSNorm of the prompt pass.  x (S, D) f32, gain (D,) bf16 patterns.  Returns
+        (out (S, D) uint16, the row behind it)."""
+        x, gain = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(gain, dtype=np.uint16)
+        S, D = x.shape
+        out, tail = np.zeros((S, D), dtype=np.uint16), np.zeros(D, dtype=np.uint16)
+        ptr = lambda t: t.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.ft_test_pf_norm(self._h, S, D, ptr(x), ptr(gain), ptr(out), ptr(tail)), "ft_test_pf_norm")
+        return out, tail
+
+    def test_pf_attn(self, qkv: np.ndarray, qn: np.ndarray, kn: np.ndarray, kc: np.ndarray, vc: np.ndarray, seqs=None,
+                     pos0: int = 0, slot: int = 0):
+        """Test hook (ft_test_pf_attn): the K/V append and the causal attention of one layer of a prompt pass.  qkv (S, qkvN)
+        f32; qn / kn (hd,), kc / vc (max_batch, Hkv, n_slots, hd): bf16 patterns; seqs: None = one prompt of S rows at pos0 of
+        `slot`, else (n, 4) int32 {first row, rows, first cache position, slot}.  Returns (y, q (S, H hd) uint16, kc, vc as
+        the hook filled them and the pass left them, tail (2, H hd), path: NG of the tiled kernel or 0)."""
+        qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+        qn, kn = np.ascontiguousarray(qn, dtype=np.uint16), np.ascontiguousarray(kn, dtype=np.uint16)
+        kc, vc = np.array(kc, dtype=np.uint16, order="C"), np.array(vc, dtype=np.uint16, order="C")     # copies: written in place
+        a = self.args
+        S = qkv.shape[0]
+        n_slots = a.max_seq_len + (-a.max_seq_len) % 8
+        assert qkv.shape == (S, (a.n_head + 2 * a.n_local_heads) * a.head_dim), qkv.shape
+        assert kc.shape == vc.shape == (self.max_batch, a.n_local_heads, n_slots, a.head_dim), kc.shape
+        sq = None if seqs is None else np.ascontiguousarray(seqs, dtype=np.int32).reshape(-1, 4)
+        y, q = (np.zeros((S, a.n_head * a.head_dim), dtype=np.uint16) for _ in range(2))
+        tail = np.zeros((2, a.n_head * a.head_dim), dtype=np.uint16)
+        path = C.c_int32(-1)
+        ptr = lambda t: None if t is None else t.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.ft_test_pf_attn(self._h, 0 if sq is None else sq.shape[0], ptr(sq), S, pos0, slot, ptr(qkv), ptr(qn),
+                                             ptr(kn), ptr(kc), ptr(vc), ptr(y), ptr(q), ptr(tail), C.byref(path)), "ft_test_pf_attn")
+        return y, q, kc, vc, tail, path.value
+
     def engine_state(self):
         """(flags, time-outs recovered so far, phase of the last one) of the persistent frame engine: flags bit 0 = slow
         stack, bit 1 = fast loop."""

@@ -545,6 +545,13 @@ constexpr size_t lingemm_lds_bytes() {
 // in LDS once per block and shared by the waves.  S = Q K^T and O += P V run on v_mfma_f32_16x16x32_bf16; the softmax is
 // the online form in f32; P enters the second product as two bf16 planes (hi = bf16(p), lo = bf16(p - hi)), i.e. with
 // f32-like precision, so the result follows the f32 SDPA of the reference up to summation order (one rounding at the end).
+// Sums run in another order than the decode kernel's, so nothing pins it bit for bit: the launch alone is checked element by
+// element against a float64 restatement (ft_test_pf_attn through engine.hip: pf_attn, tests/test_pf_kernels_gpu.py: y, the
+// finished queries, the appended K / V rows, every other cache row unchanged with NaN patterns behind every sequence and in
+// unused slots; NG = 4 and 2, HD = 128 and 64, prompt lengths on both sides of every query tile, of the 128- and 256-key pair
+// steps and of the NG threshold, behind restored prefixes, alone and as a ragged pass over several slots), and whole prompt
+// passes follow the oracle with the bf16 margin (tests/test_ar_gpu.py: test_prefill_gemm_paths_vs_oracle,
+// test_ragged_prompt_pass_vs_oracle).
 struct FlashP {
     const bf16_t* q;    // [S][H*hd] normalised + rotated queries
     const bf16_t* kc;   // [Hkv][n_slots][hd]

@@ -727,9 +727,12 @@ struct PfX {   // fused RMSNorm hooks of the skinny kernel (codec_kernels.h TapG
     int nblk = 0;
     float* ss_out = nullptr;      // leave this GEMM's own partials for the next consumer
 };
-static void pf_gemm(Launch& L, const bf16_t* X, long ldx, int S, const void* W, const float* bias, int N, int K,
-                    int act, const float* resid, float* out_f32, bf16_t* out_bf, long ldo, int round_out,
-                    const PfX& fx = PfX());
+// Returns which kernel class ran (PF_ID_*, include/fishtts_hip_test.h: ft_test_pf_linear reports it; prefill_gemm ignores it).
+enum { PF_ID_NONE = -1, PF_ID_SKINNY1 = 0, PF_ID_SKINNY2 = 1, PF_ID_SKINNY4 = 2, PF_ID_LIN128 = 3, PF_ID_LIN64 = 4, PF_ID_TAP64_128 = 5,
+       PF_ID_TAP64_64 = 6, PF_ID_TAP_128 = 7, PF_ID_TAP_64 = 8 };
+static int pf_gemm(Launch& L, const bf16_t* X, long ldx, int S, const void* W, const float* bias, int N, int K,
+                   int act, const float* resid, float* out_f32, bf16_t* out_bf, long ldo, int round_out,
+                   const PfX& fx = PfX());
 // A lock-step batch of >= wide_min rows (bf16 or fp16): every Linear is ONE M-row MFMA launch (weights read once for the whole
 // batch) with the RMSNorm / SwiGLU / residual add folded in (wide_kernels.h): five launches per layer.
 static bool wide_batch(const Launch& L) {
@@ -1432,8 +1435,13 @@ static void lingemm_launch(const TapGemmP& p, int S, int N, hipStream_t st) {
 // tap-GEMM kernel (v_mfma_f32_16x16x32_bf16), with the reference's rounding points in the epilogues
 // (Linear output rounded, residual add rounded, SwiGLU steps rounded; llama.py:172-190,229-283,322-331).
 // K/V of all positions are appended first, then every position attends over the cache.
-static void pf_gemm(Launch& L, const bf16_t* X, long ldx, int S, const void* W, const float* bias, int N, int K,
-                    int act, const float* resid, float* out_f32, bf16_t* out_bf, long ldo, int round_out, const PfX& fx) {
+// The choice between the kernel classes below is checked ONE LAUNCH AT A TIME through this very dispatcher: ft_test_pf_linear
+// runs one product of each of prefill_gemm's four forms on temporaries, and tests/test_pf_kernels_gpu.py compares every
+// element of every written row with the float64 restatement of tests/pf_ref.py (every class, both sides of every row-tile
+// and K-round edge, the in-place residual form included).
+static int pf_gemm(Launch& L, const bf16_t* X, long ldx, int S, const void* W, const float* bias, int N, int K,
+                   int act, const float* resid, float* out_f32, bf16_t* out_bf, long ldo, int round_out, const PfX& fx) {
+    int id = PF_ID_NONE;
     TapGemmP p{};
     p.gain = (const bf16_t*)fx.gain; p.ss_in = fx.ss_in; p.ss_out = fx.ss_out; p.ss_nblk = fx.nblk;
     p.ss_ld = std::max(L.ctx->c.dim, L.ctx->c.fast_dim) / 16 + 1; p.eps = L.ctx->c.norm_eps;
@@ -1444,9 +1452,9 @@ static void pf_gemm(Launch& L, const bf16_t* X, long ldx, int S, const void* W, 
     const bool fused = fx.gain || fx.ss_out;
     if ((mode >= 2 || fused) && S <= 128 && K % 128 == 0 && N % 2 == 0) {
         // short prompts are weight-bandwidth bound: 16 weight rows per block, K split over the waves
-        if (S <= 16) skinny_gemm_launch<1>(p, 1, L.s);
-        else if (S <= 32) skinny_gemm_launch<2>(p, 1, L.s);
-        else skinny_gemm_launch<4>(p, (S + 63) / 64, L.s);
+        if (S <= 16) { id = PF_ID_SKINNY1; skinny_gemm_launch<1>(p, 1, L.s); }
+        else if (S <= 32) { id = PF_ID_SKINNY2; skinny_gemm_launch<2>(p, 1, L.s); }
+        else { id = PF_ID_SKINNY4; skinny_gemm_launch<4>(p, (S + 63) / 64, L.s); }
     } else if (fused) {
         L.err = hipErrorInvalidValue;   // the fused norm exists on the skinny kernel only (callers check the shapes)
     } else if (mode >= 1 && K % 64 == 0 && N % 128 == 0) {
@@ -1459,21 +1467,24 @@ static void pf_gemm(Launch& L, const bf16_t* X, long ldx, int S, const void* W, 
             // both tiles are held to <= 128 registers so that workgroups share a CU (128 x 128: two K-steps in flight, two
             // workgroups per CU - 4.92 against 5.25 ms per 780-position prefill with four steps and one workgroup; 64 x 64: four
             // steps, four workgroups - another 0.07 ms)
-            if (S >= tile8_s && N > 1024) lingemm_launch<128, 128, 2, 4, 2, 4>(p, S, N, L.s);
-            else lingemm_launch<64, 64, 2, 2, 4, 4>(p, S, N, L.s);
+            if (S >= tile8_s && N > 1024) { id = PF_ID_LIN128; lingemm_launch<128, 128, 2, 4, 2, 4>(p, S, N, L.s); }
+            else { id = PF_ID_LIN64; lingemm_launch<64, 64, 2, 2, 4, 4>(p, S, N, L.s); }
         } else if (S >= tile8_s) {
+            id = PF_ID_TAP64_128;
             constexpr size_t lds8 = std::max((size_t)((128 + 56) + 2 * 128) * (64 + 8) * 2, (size_t)(128 / 2) * (128 + 4) * 4);
             static DevOnce once8;
             once8.run([] { hipFuncSetAttribute((const void*)tapgemm64_kernel<128, 128, 64, 2, 4>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8); });
             tapgemm64_kernel<128, 128, 64, 2, 4><<<dim3((S + 127) / 128, N / 128, 1), 512, lds8, L.s>>>(p);
         } else {
+            id = PF_ID_TAP64_64;
             const size_t lds = std::max((size_t)((64 + 56) + 2 * 64) * (64 + 8) * 2, (size_t)(64 / 2) * (64 + 4) * 4);
             tapgemm64_kernel<64, 64, 64><<<dim3((S + 63) / 64, N / 64, 1), 256, lds, L.s>>>(p);
         }
-    } else if (N >= 128) tapgemm_kernel<128, 128, 2, 2><<<dim3((S + 127) / 128, (N + 127) / 128, 1), 256, 0, L.s>>>(p);
-    else tapgemm_kernel<128, 64, 4, 1><<<dim3((S + 127) / 128, (N + 63) / 64, 1), 256, 0, L.s>>>(p);
+    } else if (N >= 128) { id = PF_ID_TAP_128; tapgemm_kernel<128, 128, 2, 2><<<dim3((S + 127) / 128, (N + 127) / 128, 1), 256, 0, L.s>>>(p); }
+    else { id = PF_ID_TAP_64; tapgemm_kernel<128, 64, 4, 1><<<dim3((S + 127) / 128, (N + 63) / 64, 1), 256, 0, L.s>>>(p); }
     L.chk();
+    return id;
 }
 
 // rg: the rows are the prompts of rg->n slots back to back (ctx->pf_seqs / pf_rows describe them; Lp = all rows, slot and
@@ -1482,6 +1493,79 @@ struct RaggedPf { int n, max_lp; };
 static __global__ __launch_bounds__(256) void gather_last_rows_kernel(const float* pf_x, int D, const int4* seqs, float* x) {
     const int4 sq = seqs[blockIdx.x];
     for (int d = threadIdx.x; d < D; d += 256) x[(size_t)sq.w * D + d] = pf_x[(size_t)(sq.x + sq.y - 1) * D + d];
+}
+// The attention of one layer of a prompt pass: the K/V append of every row, then the causal attention.  Three choices live
+// here: the tiled kernel or the decode kernel position by position, its NG key groups, its head width.  prefill_gemm calls it
+// on the context's workspace and ft_test_pf_attn on temporaries (tests/test_pf_kernels_gpu.py: y, the finished queries and
+// the appended rows of ONE such pass against the float64 restatement of tests/pf_ref.py, every other cache row bit-unchanged).
+// kc / vc: the layer's base pointers (slot 0).  Returns the path taken: NG of flash_prefill_kernel, 0 = position by position.
+struct PfAttnIO {
+    const float* qkv;          // [rows][(H + 2 Hkv) hd]
+    const void *qn, *kn;
+    void *kc, *vc;
+    float* y;                  // [rows][H hd] f32 (the per-position kernel writes it too)
+    bf16_t* y_bf;              // [rows][H hd]
+    bf16_t* q_bf;              // [rows][H hd]: the finished queries (tiled path only)
+    const int4* seqs;          // ragged pass: device copies of {first row, rows, first cache position, slot} per sequence ...
+    const int2* rows;          // ... and of (slot, cache position) per row
+};
+static int pf_attn(Launch& L, const PfAttnIO& io, int slot, int Lp, int pos0, const RaggedPf* rg) {
+    ft_ctx* ctx = L.ctx;
+    const ft_ar_config& c = ctx->c;
+    const int HD = c.n_head * c.head_dim, qkvN = (c.n_head + 2 * c.n_local_heads) * c.head_dim;
+    const int G = c.n_head / c.n_local_heads;
+    const int nslot = 2048 / c.head_dim;
+    const size_t lds = ((size_t)G * c.head_dim + 2 * c.head_dim + (size_t)nslot * G * 2 + (size_t)nslot * G * c.head_dim) * sizeof(float);
+    int path = 0;
+    AttnP a{};
+    a.qkv = io.qkv; a.ldq = qkvN; a.qn = io.qn; a.kn = io.kn; a.rope = ctx->rope;
+    a.kc = (char*)io.kc + (size_t)slot * ctx->cache_m_stride * ctx->esz;
+    a.vc = (char*)io.vc + (size_t)slot * ctx->cache_m_stride * ctx->esz;
+    a.cache_m_stride = 0; a.pos = nullptr; a.pos_off = pos0; a.row_is_pos = 1;
+    if (rg) { a.kc = io.kc; a.vc = io.vc; a.cache_m_stride = ctx->cache_m_stride; a.row_sp = io.rows; }
+    a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots; a.nsplit = 1;
+    a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim); a.y = io.y; a.ldy = HD; a.y_bf = io.y_bf;
+    // pass 0 appends K/V of every position (and leaves the finished queries); pass 1 attends: on the matrix cores
+    // for 64- and 128-wide heads, otherwise position by position with the decode kernel
+    // (a short tail behind a long restored prefix: with four key groups per block the tiled kernel wins from 16 new
+    // positions - 47.7 against 49.5 ms to the first 10 frames of 8 cloned-voice utterances with 49-token tails; round 2's
+    // one-group kernel lost below 64)
+    const bool flash = rg || (!getenv("FT_PREFILL_ATTN_V0") && (c.head_dim == 64 || c.head_dim == 128) && Lp >= 16);
+    a.q_out = flash ? io.q_bf : nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        a.kv_only = pass == 0; a.no_append = pass == 1;
+        if (pass == 0 && flash) {       // every position's q k v in one launch of Lp blocks
+            if (c.head_dim == 128) prefill_rope_append_kernel<128><<<Lp, 256, 0, L.s>>>(a);
+            else prefill_rope_append_kernel<64><<<Lp, 256, 0, L.s>>>(a);
+            L.chk();
+            continue;
+        }
+        if (pass == 1 && flash) {
+            FlashP fp{io.q_bf, (const bf16_t*)a.kc, (const bf16_t*)a.vc, io.y_bf, Lp, c.n_head, c.n_local_heads,
+                      c.head_dim, ctx->n_slots, pos0, a.scale};
+            int nz = 1, lp_grid = Lp;
+            if (rg) { fp.seqs = io.seqs; fp.cache_m_stride = ctx->cache_m_stride; nz = rg->n; lp_grid = rg->max_lp; }
+            // key groups per block: four (32 query rows per block: more blocks) up to 320 positions, two beyond (measured:
+            // 3.39 against 3.46 ms per 160-position prefill, 5.24 against 4.91 at 780 - the longer walks re-read K/V twice as often)
+            const bool ng4 = lp_grid <= 320;
+            path = ng4 ? 4 : 2;
+            if (c.head_dim == 128) { if (ng4) flash_launch<128, 4>(fp, lp_grid, L.s, nz); else flash_launch<128, 2>(fp, lp_grid, L.s, nz); }
+            else { if (ng4) flash_launch<64, 4>(fp, lp_grid, L.s, nz); else flash_launch<64, 2>(fp, lp_grid, L.s, nz); }
+            L.chk();
+            continue;
+        }
+        const dim3 grid(c.n_local_heads, 1, Lp);
+        switch (G) {
+            case 1: attn_decode_kernel<bf16_t, 1, true><<<grid, 256, lds, L.s>>>(a); break;
+            case 2: attn_decode_kernel<bf16_t, 2, true><<<grid, 256, lds, L.s>>>(a); break;
+            case 4: attn_decode_kernel<bf16_t, 4, true><<<grid, 256, lds, L.s>>>(a); break;
+            default:
+                hipFuncSetAttribute((const void*)attn_decode_kernel<bf16_t, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                attn_decode_kernel<bf16_t, 8, true><<<grid, 256, lds, L.s>>>(a);
+        }
+        L.chk();
+    }
+    return path;
 }
 static void prefill_gemm(Launch& L, int slot, int Lp, int pos0, bool with_tail = true, const RaggedPf* rg = nullptr) {
     ft_ctx* ctx = L.ctx;
@@ -1495,62 +1579,12 @@ static void prefill_gemm(Launch& L, int slot, int Lp, int pos0, bool with_tail =
     e.scale = c.scale_codebook_embeddings; e.inv_div = (float)sqrt((double)(c.num_codebooks + 1));
     embed_kernel<bf16_t, true><<<dim3((D + 255) / 256, Lp), 256, 0, L.s>>>(e);
     L.chk();
-    const int G = c.n_head / c.n_local_heads;
-    const int nslot = 2048 / c.head_dim;
-    const size_t lds = ((size_t)G * c.head_dim + 2 * c.head_dim + (size_t)nslot * G * 2 + (size_t)nslot * G * c.head_dim) * sizeof(float);
     for (int li = 0; li < c.n_layer; ++li) {
         const FtLayer& l = ctx->layers[li];
         rmsnorm_llama_rows_kernel<bf16_t, true><<<Lp, 256, 0, L.s>>>(ctx->pf_x, l.attn_norm, c.norm_eps, D, ctx->pf_xn);
         pf_gemm(L, ctx->pf_xn, D, Lp, l.wqkv, l.bqkv_f32, qkvN, D, ACT_NONE, nullptr, ctx->pf_qkv, nullptr, qkvN, 0);
-        AttnP a{};
-        a.qkv = ctx->pf_qkv; a.ldq = qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->rope;
-        a.kc = (char*)l.kc + (size_t)slot * ctx->cache_m_stride * ctx->esz;
-        a.vc = (char*)l.vc + (size_t)slot * ctx->cache_m_stride * ctx->esz;
-        a.cache_m_stride = 0; a.pos = nullptr; a.pos_off = pos0; a.row_is_pos = 1;
-        if (rg) { a.kc = l.kc; a.vc = l.vc; a.cache_m_stride = ctx->cache_m_stride; a.row_sp = ctx->pf_rows; }
-        a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots; a.nsplit = 1;
-        a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim); a.y = ctx->pf_y; a.ldy = HD; a.y_bf = ctx->pf_ybf;
-        Launch LA = L;
-        LA.M = Lp;
-        // pass 0 appends K/V of every position (and leaves the finished queries); pass 1 attends: on the matrix cores
-        // for 64- and 128-wide heads, otherwise position by position with the decode kernel
-        // (a short tail behind a long restored prefix: with four key groups per block the tiled kernel wins from 16 new
-        // positions - 47.7 against 49.5 ms to the first 10 frames of 8 cloned-voice utterances with 49-token tails; round 2's
-        // one-group kernel lost below 64)
-        const bool flash = rg || (!getenv("FT_PREFILL_ATTN_V0") && (c.head_dim == 64 || c.head_dim == 128) && Lp >= 16);
-        a.q_out = flash ? ctx->pf_qbf : nullptr;
-        for (int pass = 0; pass < 2; ++pass) {
-            a.kv_only = pass == 0; a.no_append = pass == 1;
-            if (pass == 0 && flash) {       // every position's q k v in one launch of Lp blocks
-                if (c.head_dim == 128) prefill_rope_append_kernel<128><<<Lp, 256, 0, L.s>>>(a);
-                else prefill_rope_append_kernel<64><<<Lp, 256, 0, L.s>>>(a);
-                L.chk();
-                continue;
-            }
-            if (pass == 1 && flash) {
-                FlashP fp{ctx->pf_qbf, (const bf16_t*)a.kc, (const bf16_t*)a.vc, ctx->pf_ybf, Lp, c.n_head, c.n_local_heads,
-                          c.head_dim, ctx->n_slots, pos0, a.scale};
-                int nz = 1, lp_grid = Lp;
-                if (rg) { fp.seqs = ctx->pf_seqs; fp.cache_m_stride = ctx->cache_m_stride; nz = rg->n; lp_grid = rg->max_lp; }
-                // key groups per block: four (32 query rows per block: more blocks) up to 320 positions, two beyond (measured:
-                // 3.39 against 3.46 ms per 160-position prefill, 5.24 against 4.91 at 780 - the longer walks re-read K/V twice as often)
-                const bool ng4 = lp_grid <= 320;
-                if (c.head_dim == 128) { if (ng4) flash_launch<128, 4>(fp, lp_grid, L.s, nz); else flash_launch<128, 2>(fp, lp_grid, L.s, nz); }
-                else { if (ng4) flash_launch<64, 4>(fp, lp_grid, L.s, nz); else flash_launch<64, 2>(fp, lp_grid, L.s, nz); }
-                L.chk();
-                continue;
-            }
-            const dim3 grid(c.n_local_heads, 1, Lp);
-            switch (G) {
-                case 1: attn_decode_kernel<bf16_t, 1, true><<<grid, 256, lds, L.s>>>(a); break;
-                case 2: attn_decode_kernel<bf16_t, 2, true><<<grid, 256, lds, L.s>>>(a); break;
-                case 4: attn_decode_kernel<bf16_t, 4, true><<<grid, 256, lds, L.s>>>(a); break;
-                default:
-                    hipFuncSetAttribute((const void*)attn_decode_kernel<bf16_t, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    attn_decode_kernel<bf16_t, 8, true><<<grid, 256, lds, L.s>>>(a);
-            }
-            L.chk();
-        }
+        PfAttnIO io{ctx->pf_qkv, l.qn, l.kn, l.kc, l.vc, ctx->pf_y, ctx->pf_ybf, ctx->pf_qbf, ctx->pf_seqs, ctx->pf_rows};
+        pf_attn(L, io, slot, Lp, pos0, rg);
         pf_gemm(L, ctx->pf_ybf, HD, Lp, l.wo, l.bo_f32, D, HD, ACT_NONE, ctx->pf_x, ctx->pf_x, nullptr, D, 1);
         rmsnorm_llama_rows_kernel<bf16_t, true><<<Lp, 256, 0, L.s>>>(ctx->pf_x, l.ffn_norm, c.norm_eps, D, ctx->pf_xn);
         pf_gemm(L, ctx->pf_xn, D, Lp, l.w13, nullptr, 2 * F, D, ACT_SWIGLU, nullptr, nullptr, ctx->pf_g, F, 0);
@@ -2522,4 +2556,167 @@ extern "C" ft_status ft_test_wide_attn(ft_ctx* ctx, int32_t M, const float* qkv,
             return ft_fail(ctx, FT_ERR_ARG, "ft_test_wide_attn: a position outside the cache or the rope table");
     if (ctx->c.dtype == FT_BF16) return test_wide_attn_t<bf16_t, RND_BF16>(ctx, M, qkv, pos, qn, kn, kc, vc, y, splits);
     return test_wide_attn_t<f16_t, RND_F16>(ctx, M, qkv, pos, qn, kn, kc, vc, y, splits);
+}
+
+// ------------------------------------------------------------------------------------------ prompt-pass kernel test hooks
+// (include/fishtts_hip_test.h: ft_test_pf_linear, ft_test_pf_norm, ft_test_pf_attn).  Host code around pf_gemm, the row norm
+// and pf_attn on temporaries: nothing here is reached from a prompt pass.
+static ft_status pf_hook_ready(ft_ctx* ctx, const char* who) {
+    FT_TRY(ar_ready(ctx));
+    if (ctx->c.dtype != FT_BF16) return ft_fail(ctx, FT_ERR_ARG, std::string(who) + ": the MFMA prompt pass is bf16 only");
+    if (ctx->prefill_v0) return ft_fail(ctx, FT_ERR_STATE, std::string(who) + ": this context runs its prompts position by position");
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_pf_linear(ft_ctx* ctx, int32_t form, int32_t S, int32_t N, int32_t K, const uint16_t* X,
+                                       const uint16_t* W, const float* bias, const float* resid, int32_t alias, void* out,
+                                       void* out_tail, int32_t* tail_rows, int32_t* variant) {
+    FT_TRY(pf_hook_ready(ctx, "ft_test_pf_linear"));
+    if (form < 0 || form > 2) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_linear: bad form");
+    if (S < 1 || S > ctx->c.max_seq_len) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_linear: S outside 1..max_seq_len");
+    if (K < 32 || K % 32 != 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_linear: K is not a whole number of 32-wide MFMA steps");
+    if (N < 16 || N % 16 != 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_linear: N is not a whole number of 16-row tiles");
+    if (!X || !W || !out || !out_tail || !tail_rows || !variant || (form == 1 && !resid))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_linear: missing argument");
+    const int St = (S + 127) / 128 * 128;          // the edge of the tallest row tile of any class
+    const int oc = form == 2 ? N / 2 : N;
+    DevTmp tmp;
+    std::vector<uint16_t> xh((size_t)St * K, WT_POISON);
+    memcpy(xh.data(), X, (size_t)S * K * 2);
+    void* dX = tmp.put(xh.data(), xh.size() * 2);
+    void* dW = tmp.put(W, (size_t)N * K * 2);
+    void* dB = bias ? tmp.put(bias, (size_t)N * sizeof(float)) : nullptr;
+    void *dO = nullptr, *dR = nullptr;
+    if (form == 2) {
+        const std::vector<uint16_t> fill((size_t)St * oc, WT_POISON);
+        dO = tmp.put(fill.data(), fill.size() * 2);
+    } else {
+        std::vector<uint32_t> fill((size_t)St * N, WT_POISON_F32);
+        if (form == 1) {
+            std::vector<uint32_t> rh = fill;       // residual rows S .. St - 1 hold the sentinel too (the in-place form returns them)
+            memcpy(rh.data(), resid, (size_t)S * N * 4);
+            dR = tmp.put(rh.data(), rh.size() * 4);
+        }
+        dO = form == 1 && alias ? dR : tmp.put(fill.data(), fill.size() * 4);
+    }
+    if (!dX || !dW || (bias && !dB) || !dO || (form == 1 && !dR)) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_pf_linear: device temporaries");
+    }
+    Launch L{ctx, ctx->stream, 0, 1, 0};
+    int id;
+    if (form == 0) id = pf_gemm(L, (const bf16_t*)dX, K, S, dW, (const float*)dB, N, K, ACT_NONE, nullptr, (float*)dO, nullptr, N, 0);
+    else if (form == 1) id = pf_gemm(L, (const bf16_t*)dX, K, S, dW, (const float*)dB, N, K, ACT_NONE, (const float*)dR, (float*)dO, nullptr, N, 1);
+    else id = pf_gemm(L, (const bf16_t*)dX, K, S, dW, (const float*)dB, N, K, ACT_SWIGLU, nullptr, nullptr, (bf16_t*)dO, oc, 0);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_pf_linear launch failed");
+    const size_t esz = form == 2 ? 2 : 4;
+    std::vector<char> o((size_t)St * oc * esz);
+    FT_HIP(ctx, hipMemcpy(o.data(), dO, o.size(), hipMemcpyDeviceToHost));
+    memcpy(out, o.data(), (size_t)S * oc * esz);
+    memcpy(out_tail, o.data() + (size_t)S * oc * esz, (size_t)(St - S) * oc * esz);
+    *tail_rows = St - S;
+    *variant = id;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_pf_norm(ft_ctx* ctx, int32_t S, int32_t D, const float* x, const uint16_t* gain, uint16_t* out,
+                                     uint16_t* out_tail) {
+    FT_TRY(pf_hook_ready(ctx, "ft_test_pf_norm"));
+    if (S < 1 || S > ctx->c.max_seq_len || D < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_norm: S outside 1..max_seq_len or D < 1");
+    if (!x || !gain || !out || !out_tail) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_norm: missing argument");
+    DevTmp tmp;
+    const std::vector<uint16_t> fill((size_t)(S + 1) * D, WT_POISON);
+    void* dX = tmp.put(x, (size_t)S * D * sizeof(float));
+    void* dG = tmp.put(gain, (size_t)D * 2);
+    void* dO = tmp.put(fill.data(), fill.size() * 2);
+    if (!dX || !dG || !dO) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_pf_norm: device temporaries");
+    }
+    rmsnorm_llama_rows_kernel<bf16_t, true><<<S, 256, 0, ctx->stream>>>((const float*)dX, dG, ctx->c.norm_eps, D, (bf16_t*)dO);
+    const hipError_t le = hipGetLastError(), e = hipStreamSynchronize(ctx->stream);
+    if (le != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_pf_norm launch failed");
+    FT_HIP(ctx, hipMemcpy(out, dO, (size_t)S * D * 2, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(out_tail, (const uint16_t*)dO + (size_t)S * D, (size_t)D * 2, hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_pf_attn(ft_ctx* ctx, int32_t n_seq, const int32_t* seqs, int32_t Lp, int32_t pos0, int32_t slot,
+                                     const float* qkv, const uint16_t* qn, const uint16_t* kn, uint16_t* kc, uint16_t* vc,
+                                     uint16_t* y, uint16_t* q, uint16_t* tail, int32_t* path) {
+    FT_TRY(pf_hook_ready(ctx, "ft_test_pf_attn"));
+    const ft_ar_config& c = ctx->c;
+    if (!qkv || !qn || !kn || !kc || !vc || !y || !q || !tail || !path || (n_seq > 0 && !seqs))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_attn: missing argument");
+    if (n_seq < 0 || n_seq > c.max_batch) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_attn: bad sequence count");
+    std::vector<int4> sq;
+    std::vector<int2> rows;
+    int S = 0, max_lp = 0;
+    if (n_seq == 0) {
+        if (slot < 0 || slot >= c.max_batch || Lp < 1 || pos0 < 0 || pos0 + Lp >= c.max_seq_len)
+            return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_attn: bad slot, empty prompt or a prompt past max_seq_len");
+        sq.push_back(int4{0, Lp, pos0, slot});
+        S = max_lp = Lp;
+    } else {
+        if ((c.head_dim != 64 && c.head_dim != 128) || getenv("FT_PREFILL_ATTN_V0"))
+            return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_attn: a ragged pass runs on the tiled kernel only");
+        std::vector<char> seen(c.max_batch, 0);
+        for (int i = 0; i < n_seq; ++i) {
+            const int4 s4{seqs[4 * i], seqs[4 * i + 1], seqs[4 * i + 2], seqs[4 * i + 3]};
+            if (s4.w < 0 || s4.w >= c.max_batch || seen[s4.w]) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_attn: bad or repeated slot");
+            seen[s4.w] = 1;
+            if (s4.x != S || s4.y < 1 || s4.z < 0 || s4.z + s4.y >= c.max_seq_len)
+                return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_attn: rows not back to back, an empty prompt or one past max_seq_len");
+            sq.push_back(s4);
+            for (int t = 0; t < s4.y; ++t) rows.push_back(int2{s4.w, s4.z + t});
+            S += s4.y;
+            max_lp = std::max(max_lp, s4.y);
+        }
+        if (S > c.max_seq_len) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pf_attn: more rows than a pass holds (max_seq_len)");
+    }
+    const int HD = c.n_head * c.head_dim;
+    const size_t qkvN = (size_t)(c.n_head + 2 * c.n_local_heads) * c.head_dim;
+    const size_t cel = (size_t)c.max_batch * ctx->cache_m_stride;
+    // NaN patterns in every cache row at or behind a sequence's end and in every slot no sequence names: the kernels must
+    // mask or clamp them away by construction
+    std::vector<int> end(c.max_batch, 0);
+    for (const int4& s4 : sq) end[s4.w] = s4.z + s4.y;
+    for (int m = 0; m < c.max_batch; ++m)
+        for (int h = 0; h < c.n_local_heads; ++h) {
+            const size_t r0 = (size_t)m * ctx->cache_m_stride + ((size_t)h * ctx->n_slots + end[m]) * c.head_dim;
+            const size_t n = (size_t)(ctx->n_slots - end[m]) * c.head_dim;
+            std::fill(kc + r0, kc + r0 + n, WT_POISON);
+            std::fill(vc + r0, vc + r0 + n, WT_POISON);
+        }
+    DevTmp tmp;
+    const std::vector<uint16_t> fill((size_t)(S + 1) * HD, WT_POISON);
+    const std::vector<uint32_t> fill32((size_t)(S + 1) * HD, WT_POISON_F32);
+    void* dQkv = tmp.put(qkv, (size_t)S * qkvN * sizeof(float));
+    void* dQn = tmp.put(qn, (size_t)c.head_dim * 2);
+    void* dKn = tmp.put(kn, (size_t)c.head_dim * 2);
+    void* dK = tmp.put(kc, cel * 2);
+    void* dV = tmp.put(vc, cel * 2);
+    void* dY = tmp.put(fill.data(), fill.size() * 2);
+    void* dYf = tmp.put(fill32.data(), fill32.size() * 4);
+    void* dQ = tmp.put(fill.data(), fill.size() * 2);
+    void* dSeq = tmp.put(sq.data(), sq.size() * sizeof(int4));
+    void* dRows = n_seq ? tmp.put(rows.data(), rows.size() * sizeof(int2)) : nullptr;
+    if (!dQkv || !dQn || !dKn || !dK || !dV || !dY || !dYf || !dQ || !dSeq || (n_seq && !dRows)) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_pf_attn: device temporaries");
+    }
+    Launch L{ctx, ctx->stream, 0, 1, 0};
+    const PfAttnIO io{(const float*)dQkv, dQn, dKn, dK, dV, (float*)dYf, (bf16_t*)dY, (bf16_t*)dQ, (const int4*)dSeq, (const int2*)dRows};
+    const RaggedPf rg{n_seq, max_lp};
+    *path = n_seq ? pf_attn(L, io, 0, S, 0, &rg) : pf_attn(L, io, slot, Lp, pos0, nullptr);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_pf_attn launch failed");
+    FT_HIP(ctx, hipMemcpy(y, dY, (size_t)S * HD * 2, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(q, dQ, (size_t)S * HD * 2, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(tail, (const uint16_t*)dY + (size_t)S * HD, (size_t)HD * 2, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(tail + HD, (const uint16_t*)dQ + (size_t)S * HD, (size_t)HD * 2, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(kc, dK, cel * 2, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(vc, dV, cel * 2, hipMemcpyDeviceToHost));
+    return FT_OK;
 }

@@ -126,6 +126,50 @@ ft_status ft_test_wide_linear(ft_ctx* ctx, int32_t epi, int32_t vocab_head, int3
 ft_status ft_test_wide_attn(ft_ctx* ctx, int32_t M, const float* qkv, const int32_t* pos, const uint16_t* qn,
                             const uint16_t* kn, uint16_t* kc, uint16_t* vc, uint16_t* y, int32_t* splits);
 
+/* Test hook: ONE Linear product of the bf16 prompt pass through the product's own dispatcher (engine.hip: pf_gemm), unchanged,
+ * so the choice between skinny_gemm_kernel<TS>, lingemm_kernel<128,128>, lingemm_kernel<64,64>, the two tapgemm64_kernel tiles
+ * and the tapgemm_kernel fall-backs is the product's (FT_PREFILL_GEMM, read when the context is created, is honoured).  form
+ * picks one of the four calls prefill_gemm makes: 0 wqkv (f32 store of bf16-rounded values), 1 wo / w2 (f32 residual added to
+ * the rounded product, the sum rounded; alias != 0: the output buffer IS the residual buffer, as the product runs it, otherwise
+ * two buffers), 2 w13 (SwiGLU on interleaved (gate, up) weight rows, N / 2 bf16 output columns).  X [S][K], W [N][K]: bf16
+ * patterns; bias [N] f32 or NULL; resid [S][N] f32 (form 1).  The hook allocates X and the output with 128 ceil(S / 128) rows:
+ * X rows from S on hold NaN patterns (0xFFFE), output (and residual) rows from S on the sentinel (0xFFFE per 16-bit element,
+ * 0xFFFFFFFE per f32 element).  Everything lives in temporaries of the call: no state of the context changes.
+ * out: the S written rows, dense ([S][N] f32 for forms 0 and 1, [S][N / 2] bf16 patterns for form 2).  out_tail (room for 127
+ * rows): the *tail_rows rows S .. 128 ceil(S / 128) - 1 of the output buffer - past the row-tile edge of every class - which
+ * must still hold the sentinel.  *variant: the kernel class that ran: 0 / 1 / 2 skinny_gemm_kernel<1 / 2 / 4>, 3
+ * lingemm_kernel<128,128>, 4 lingemm_kernel<64,64>, 5 tapgemm64_kernel<128,128>, 6 tapgemm64_kernel<64,64>, 7
+ * tapgemm_kernel<128,128>, 8 tapgemm_kernel<128,64>.
+ * The fused-norm arguments of pf_gemm (PfX: gain, ss_in, ss_out) have no caller in the prompt pass and none here.
+ * FT_ERR_ARG: a context that is not bf16, S outside 1..max_seq_len, K not a multiple of 32, N not a multiple of 16, a missing
+ * argument; FT_ERR_STATE: a context whose prompts run position by position (FT_PREFILL_V0, widths off the MFMA tiles). */
+ft_status ft_test_pf_linear(ft_ctx* ctx, int32_t form, int32_t S, int32_t N, int32_t K, const uint16_t* X, const uint16_t* W,
+                            const float* bias, const float* resid, int32_t alias, void* out, void* out_tail,
+                            int32_t* tail_rows, int32_t* variant);
+
+/* Test hook: rmsnorm_llama_rows_kernel<bf16, round> of the prompt pass on S f32 rows x [S][D] with gain [D] (bf16 patterns)
+ * at the context's norm_eps -> out [S][D] bf16 patterns; out_tail [D]: the row behind them, which must still hold 0xFFFE.
+ * Refusals as ft_test_pf_linear. */
+ft_status ft_test_pf_norm(ft_ctx* ctx, int32_t S, int32_t D, const float* x, const uint16_t* gain, uint16_t* out,
+                          uint16_t* out_tail);
+
+/* Test hook: the attention of ONE layer of a prompt pass at the context's head geometry and rope table - the K/V append of
+ * every row, then the causal attention - through the host routine prefill_gemm itself calls (engine.hip: pf_attn), so the
+ * choice between flash_prefill_kernel<HD, NG> (NG = 4 up to 320 grid rows, else 2) and attn_decode_kernel position by position
+ * (fewer than 16 rows, FT_PREFILL_ATTN_V0) is the product's.  n_seq = 0: one prompt of Lp rows at cache positions
+ * pos0 .. pos0 + Lp - 1 of `slot`.  n_seq >= 1: the ragged pass, seqs [n_seq][4] = {first row, rows, first cache position,
+ * slot}, rows back to back, slots distinct (Lp, pos0, slot ignored).  qkv [S][(H + 2 Hkv) hd] f32 (S = all rows), qn / kn [hd]
+ * and the caches kc / vc [max_batch][Hkv][n_slots][hd] as bf16 patterns.  The hook writes NaN patterns (0xFFFE) into every
+ * cache row at or behind a sequence's pos0 + rows and into every slot no sequence names, uploads both caches, runs the pass on
+ * temporaries and returns them whole in place.  y, q [S][H hd]: the attention output and the finished (normalised, rotated)
+ * queries as bf16 patterns - q stays 0xFFFE on the per-position path, which keeps its queries in LDS.  tail [2][H hd]: the row
+ * behind y and behind q (0xFFFE).  *path: NG of the tiled kernel, 0 = position by position.
+ * FT_ERR_ARG for what the product would refuse (a bad or repeated slot, an empty prompt, pos0 + rows >= max_seq_len, more rows
+ * than max_seq_len, a ragged pass where the tiled kernel does not run) and a context that is not bf16; FT_ERR_STATE as above. */
+ft_status ft_test_pf_attn(ft_ctx* ctx, int32_t n_seq, const int32_t* seqs, int32_t Lp, int32_t pos0, int32_t slot,
+                          const float* qkv, const uint16_t* qn, const uint16_t* kn, uint16_t* kc, uint16_t* vc, uint16_t* y,
+                          uint16_t* q, uint16_t* tail, int32_t* path);
+
 #ifdef __cplusplus
 }
 #endif
