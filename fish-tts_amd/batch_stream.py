@@ -70,17 +70,25 @@ class ChunkCutter:
         self.done = True
 
 
+def checked_fx(fx=None, sample_rate=None, speed=None, pitch=None):
+    """The checked output stages of a call (codec_engine.OutputFx, imported when first needed, as the engines are): `fx`
+    itself where the caller checked already, else the three keywords checked now (ValueError for a bad one)."""
+    if fx is not None:
+        return fx
+    from .codec_engine import OutputFx
+    return OutputFx.of(sample_rate, speed, pitch)
+
+
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                       min_first_chunk: int = 10, sample_rate: Optional[int] = None,
-                      speed: Optional[float] = None, pitch: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
+                      speed: Optional[float] = None, pitch: Optional[float] = None, fx=None) -> Iterator[Tuple[int, bytes]]:
     """Yields (i, pcm) chunks of the n utterances `run` generates, in the order they become ready, and (i, b"") once
     after utterance i's last chunk.  `run` is called on a producer thread, the codec on a worker thread; abandoning the
     generator stops the producer at its next block of frames and joins both threads.  An exception of either thread is
     raised from the generator."""
     if chunk_tokens < 1 or min_first_chunk < 1:
         raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-    fx = sample_rate is not None or speed is not None or pitch is not None      # an output stage holds back a tail
-    skw = {k: v for k, v in (("speed", speed), ("pitch", pitch)) if v is not None}
+    fx = checked_fx(fx, sample_rate, speed, pitch)       # truthy: an output stage holds back a tail
     cv = threading.Condition()
     cuts = [ChunkCutter(chunk_tokens, min_first_chunk) for _ in range(n)]
     ended = [False] * n                                 # end mark handed out (worker only)
@@ -140,7 +148,7 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                 for i in ends:                          # after the utterance's last chunk went out
                     if fx and streams[i] is not None and not streams[i].finished:
                         tail = streams[i].finish()                     # the output stages' tail
-                        if len(tail) or not skw:
+                        if len(tail) or fx.emits_empty:
                             out.put((i, pcm16(tail)))
                     if streams[i] is not None:
                         streams[i].close()
@@ -156,13 +164,11 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                             if fx:
                                 out.put((i, pcm16(s.finish())))
                             s.close()
-                        streams[i] = codec.stream() if not fx else codec.stream(sample_rate, **skw)
-                if not fx:
-                    audio = codec.decode_streams([streams[i] for i in batch], chunks)
-                else:
-                    audio = codec.decode_streams([streams[i] for i in batch], chunks, final)
+                        streams[i] = codec.stream(**fx.kw)
+                # (final flags only where the streams have a stage: without one there is no tail, and the plain call stays)
+                audio = codec.decode_streams([streams[i] for i in batch], chunks, *([final] if fx else []))
                 for i, a in zip(batch, audio):
-                    if len(a) or not skw:               # (a chunk that completes nothing in the time-scale or pitch stage gives
+                    if len(a) or fx.emits_empty:             # (a chunk that completes nothing in the time-scale or pitch stage gives
                         out.put((i, pcm16(a)))          # no samples yet: (i, b"") is the end mark alone)
         except BaseException as e:  # noqa: BLE001
             errors.append(e)

@@ -3,6 +3,7 @@ feature_lengths)` (fish_tts/models/vocoder.py:906-912), on top of the C ABI."""
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -16,81 +17,113 @@ from .config import CodecArgs
 CODEC_RATE = 44100     # the codec's own sample rate (Fi of the resampler)
 
 
+def _number(v, what: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what}, got {v!r}")
+    return float(v)
+
+
+@dataclass(frozen=True)
+class OutputFx:
+    """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent) and `cents` (pitch), each None where the
+    stage is absent - the codec's own rate (None or 44100), the model's own pace (a speed that rounds to 100 percent) and
+    pitch (one that rounds to 0 cents).  Built once per call by of() and handed down to the native call as it is."""
+    rate: Optional[int] = None
+    pct: Optional[int] = None
+    cents: Optional[int] = None
+
+    @classmethod
+    def of(cls, sample_rate=None, speed=None, pitch=None) -> "OutputFx":
+        """A caller's `sample_rate=` (an integer in [8000, 48000] whose reduced L = rate / gcd(rate, 44100) is at most 640:
+        ft_resample_filter), `speed=` (a factor in [0.5, 2.0], kept as round(speed * 100): ft_timescaled_len) and `pitch=`
+        (semitones in [-12, 12], kept as round(100 * pitch) cents: ft_pitch_filter; a plain shift, formants move with the
+        pitch), then the two together (ft_pitch_ok: the time-scale stage under a pitch shift runs at speed / 2^(pitch / 12),
+        which has to lie in [0.5, 2]).  Anything else raises ValueError, before any device work."""
+        rate = pct = cents = None
+        if sample_rate is not None:
+            if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)):
+                raise ValueError(f"sample_rate must be an integer, got {sample_rate!r}")
+            rate = int(sample_rate)
+            if rate == CODEC_RATE:
+                rate = None
+            elif not -(1 << 31) <= rate < (1 << 31) or L.load().ft_resample_filter(rate, None, None, None, None) != L.FT_OK:
+                raise ValueError(f"unsupported sample_rate {rate}: integers in [8000, 48000] whose ratio to 44100 reduces to "
+                                 "L / M with L <= 640 (8000, 11025, 12000, 16000, 22050, 24000, 32000, 48000, ...)")
+        if speed is not None:
+            if not 0.5 <= _number(speed, "speed must be a number") <= 2.0:      # (a nan fails both comparisons)
+                raise ValueError(f"unsupported speed {speed!r}: a factor in [0.5, 2.0]")
+            pct = int(round(float(speed) * 100))
+            pct = None if pct == 100 else pct
+        if pitch is not None:
+            if not -12.0 <= _number(pitch, "pitch must be a number of semitones") <= 12.0:
+                raise ValueError(f"unsupported pitch {pitch!r}: semitones in [-12, 12]")
+            cents = int(round(float(pitch) * 100)) or None
+        if cents is not None and L.load().ft_pitch_ok(100 if pct is None else pct, cents) != L.FT_OK:
+            raise ValueError(f"unsupported combination speed={speed!r}, pitch={pitch!r}: speed / 2^(pitch / 12) must lie in "
+                             "[0.5, 2.0]")
+        return cls(rate, pct, cents)
+
+    def __bool__(self) -> bool:
+        """Any stage at all: the call goes through the chain's native entry points, a stream holds back a tail."""
+        return self.rate is not None or self.pct is not None or self.cents is not None
+
+    @property
+    def emits_empty(self) -> bool:
+        """A stream's empty chunk is handed out: no stage, or a resampler only.  Behind a time-scale or pitch stage a chunk
+        that completes nothing gives no samples yet, and nothing is handed out for it."""
+        return self.pct is None and self.cents is None
+
+    @property
+    def kw(self) -> dict:
+        """The value as the keyword of a call that takes it defaulted: {"fx": self}, and nothing without a stage - a decoder
+        or codec handed in by a caller, which may know of no stage, is then called as it always was."""
+        return {"fx": self} if self else {}
+
+    @property
+    def native(self):
+        """(sample_rate, speed_pct, pitch_cents) as the native entry points take them."""
+        return self.rate or CODEC_RATE, self.pct or 100, self.cents or 0
+
+    @property
+    def wav_rate(self) -> int:
+        return self.rate or CODEC_RATE
+
+    def out_len(self, n: int) -> int:
+        """Samples that n codec samples give: ceil(100 n / pct) after the time-scale stage (the pitch stage keeps that
+        length), then ceil(n L / M) after the resampler."""
+        n = int(n) if self.pct is None else int(L.load().ft_timescaled_len(self.pct, int(n)))
+        return n if self.rate is None else int(L.load().ft_resampled_len(self.rate, n))
+
+
 def output_rate(sample_rate: Optional[int]) -> Optional[int]:
-    """A caller's `sample_rate=`: None for the codec's own rate (None or 44100: no resampler), else the rate - an integer
-    in [8000, 48000] whose reduced L = rate / gcd(rate, 44100) is at most 640 (ft_resample_filter).  Anything else raises
-    ValueError (before any device work)."""
-    if sample_rate is None:
-        return None
-    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)):
-        raise ValueError(f"sample_rate must be an integer, got {sample_rate!r}")
-    rate = int(sample_rate)
-    if rate == CODEC_RATE:
-        return None
-    if not -(1 << 31) <= rate < (1 << 31) or L.load().ft_resample_filter(rate, None, None, None, None) != L.FT_OK:
-        raise ValueError(f"unsupported sample_rate {rate}: integers in [8000, 48000] whose ratio to 44100 reduces to "
-                         "L / M with L <= 640 (8000, 11025, 12000, 16000, 22050, 24000, 32000, 48000, ...)")
-    return rate
+    """OutputFx.of's rate: None for the codec's own rate."""
+    return OutputFx.of(sample_rate=sample_rate).rate
 
 
 def resampled_len(sample_rate: Optional[int], n: int) -> int:
     """Samples that n codec samples give at sample_rate: ceil(n L / M)."""
-    rate = output_rate(sample_rate)
-    return int(n) if rate is None else int(L.load().ft_resampled_len(rate, int(n)))
+    return OutputFx.of(sample_rate=sample_rate).out_len(n)
 
 
 def output_speed(speed) -> Optional[int]:
-    """A caller's `speed=`: None for the model's own pace (None, or a value that rounds to 100 percent: no time-scale
-    stage), else the speed as an integer percentage, round(speed * 100), for a speed in [0.5, 2.0]
-    (ft_timescaled_len).  Anything else raises ValueError (before any device work)."""
-    if speed is None:
-        return None
-    if isinstance(speed, bool) or not isinstance(speed, (int, float, np.integer, np.floating)):
-        raise ValueError(f"speed must be a number, got {speed!r}")
-    v = float(speed)
-    if not 0.5 <= v <= 2.0:      # (a nan fails both comparisons)
-        raise ValueError(f"unsupported speed {speed!r}: a factor in [0.5, 2.0]")
-    pct = int(round(v * 100))
-    return None if pct == 100 else pct
+    """OutputFx.of's speed in percent: None for the model's own pace."""
+    return OutputFx.of(speed=speed).pct
 
 
 def timescaled_len(speed, n: int) -> int:
     """Samples that n codec samples give at `speed`: ceil(100 n / pct)."""
-    pct = output_speed(speed)
-    return int(n) if pct is None else int(L.load().ft_timescaled_len(pct, int(n)))
+    return OutputFx.of(speed=speed).out_len(n)
 
 
 def output_pitch(pitch) -> Optional[int]:
-    """A caller's `pitch=`: None for the model's own pitch (None, or a value that rounds to 0 cents: no pitch stage), else
-    the shift in cents, round(100 * pitch), for a pitch in semitones in [-12, 12] (ft_pitch_filter).  The shift is a plain
-    one: formants move with the pitch.  Anything else raises ValueError (before any device work)."""
-    if pitch is None:
-        return None
-    if isinstance(pitch, bool) or not isinstance(pitch, (int, float, np.integer, np.floating)):
-        raise ValueError(f"pitch must be a number of semitones, got {pitch!r}")
-    v = float(pitch)
-    if not -12.0 <= v <= 12.0:      # (a nan fails both comparisons)
-        raise ValueError(f"unsupported pitch {pitch!r}: semitones in [-12, 12]")
-    cents = int(round(v * 100))
-    return None if cents == 0 else cents
+    """OutputFx.of's pitch in cents: None for the model's own pitch."""
+    return OutputFx.of(pitch=pitch).cents
 
 
 def output_fx(speed, pitch):
-    """(pct, cents) of a caller's `speed=` and `pitch=` (output_speed, output_pitch), checked together (ft_pitch_ok): the
-    time-scale stage under a pitch shift runs at speed / 2^(pitch / 12), which has to lie in [0.5, 2].  ValueError
-    otherwise (before any device work)."""
-    pct, cents = output_speed(speed), output_pitch(pitch)
-    if cents is not None and L.load().ft_pitch_ok(100 if pct is None else pct, cents) != L.FT_OK:
-        raise ValueError(f"unsupported combination speed={speed!r}, pitch={pitch!r}: speed / 2^(pitch / 12) must lie in "
-                         "[0.5, 2.0]")
-    return pct, cents
-
-
-def _out_len(rate: Optional[int], pct: Optional[int], n: int) -> int:
-    """n codec samples after the time-scale stage (pct) and the resampler (rate), either of them None: absent."""
-    lib = L.load()
-    n = int(n) if pct is None else int(lib.ft_timescaled_len(pct, int(n)))
-    return n if rate is None else int(lib.ft_resampled_len(rate, n))
+    """(pct, cents) of a caller's `speed=` and `pitch=`, checked together."""
+    fx = OutputFx.of(speed=speed, pitch=pitch)
+    return fx.pct, fx.cents
 
 
 def fold_weight_norm(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -273,15 +306,16 @@ class CodecHipEngine:
         return res, launches
 
     def stream(self, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-               pitch: Optional[float] = None) -> "CodecStream":
+               pitch: Optional[float] = None, fx: Optional[OutputFx] = None) -> "CodecStream":
         """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode.
-        `sample_rate` (output_rate): the stream's output is resampled on the device; it holds back the samples whose
+        `sample_rate`, `speed`, `pitch` (OutputFx.of), or `fx`, the checked value itself.
+        `sample_rate`: the stream's output is resampled on the device; it holds back the samples whose
         filter taps reach past the input so far, until a later chunk, decode(final=True) or finish().
-        `speed` (output_speed): the waveform is time-scaled on the device first; the stream holds back the samples that
+        `speed`: the waveform is time-scaled on the device first; the stream holds back the samples that
         a later frame of the stage still adds to, in the same way.
-        `pitch` (output_pitch, semitones): the waveform is pitch-shifted on the device (a plain shift: formants move with
+        `pitch` (semitones): the waveform is pitch-shifted on the device (a plain shift: formants move with
         the pitch) between the two; the stream's length does not change."""
-        return CodecStream(self, sample_rate, speed, pitch)
+        return CodecStream(self, sample_rate, speed, pitch, fx)
 
     MAX_STREAMS_PER_CALL = 64     # ft_codec_stream_decode_many
 
@@ -317,7 +351,7 @@ class CodecHipEngine:
             raise ValueError("decode_streams: one chunk per stream")
         for c in chunks:
             assert c.ndim == 2 and c.shape[0] == self.R, c.shape
-        if final is not None or any(s.rate is not None or s.pct is not None or s.cents is not None for s in streams):
+        if final is not None or any(s.fx for s in streams):
             return self._decode_streams_at(streams, chunks, [False] * len(streams) if final is None else list(final))
         out: List[np.ndarray] = []
         for _, _, group, lens, codes, handles in self._stream_groups(streams, chunks):
@@ -425,7 +459,7 @@ class CodecHipEngine:
 
     def decode_join(self, codes_list: Sequence[np.ndarray], sample_rate: Optional[int] = None, speed: Optional[float] = None,
                     pitch: Optional[float] = None, params=(0.0, 1, 0, 0), gaps: Optional[Sequence[int]] = None,
-                    started: bool = False):
+                    started: bool = False, fx: Optional[OutputFx] = None):
         """The utterances of one document - codes_list[i] (n_codebooks+1, T_i) integer - decoded at `sample_rate`, `speed`
         and `pitch` (as decode) and joined on the device into one waveform (ft_codec_decode_join): each trimmed to its
         loud part, faded at the cuts and laid out behind gaps[i] samples of silence.  `params`: (threshold, hop, keep,
@@ -434,8 +468,7 @@ class CodecHipEngine:
         calls of at most 64 items and max_frames frames (ft_join_groups), `started` carried from call to call, the calls'
         outputs concatenated here - a piece depends on its own item only, so the grouping does not show.  Returns (audio
         float32, cuts (n, 2) int64: the samples [a, e) kept of every item)."""
-        rate = output_rate(sample_rate)
-        pct, cents = output_fx(speed, pitch)
+        fx = OutputFx.of(sample_rate, speed, pitch) if fx is None else fx
         items = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in codes_list]
         for c in items:
             if c.ndim != 2 or c.shape[0] != self.R:
@@ -461,15 +494,14 @@ class CodecHipEngine:
             for b, c in enumerate(items[i:j]):
                 block[b, :, :c.shape[1]] = c
             glens = np.ascontiguousarray(lens[i:j])
-            cap = sum(_out_len(rate, pct, int(t) * self.frame_len) for t in glens) + int(g[i:j].sum())
+            cap = sum(fx.out_len(int(t) * self.frame_len) for t in glens) + int(g[i:j].sum())
             audio = np.empty(max(cap, 1), dtype=np.float32)
             total = C.c_int64(0)
             gcuts = np.zeros((B, 2), dtype=np.int64)
             ggaps = np.ascontiguousarray(g[i:j])
             self._check(self.lib.ft_codec_decode_join(
                 self._h, block.ctypes.data_as(C.c_void_p), B, T, glens.ctypes.data_as(C.c_void_p),
-                CODEC_RATE if rate is None else rate, 100 if pct is None else pct, 0 if cents is None else cents,
-                C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0, audio.ctypes.data_as(C.c_void_p), cap,
+                *fx.native, C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0, audio.ctypes.data_as(C.c_void_p), cap,
                 C.byref(total), gcuts.ctypes.data_as(C.c_void_p)), "ft_codec_decode_join")
             out.append(audio[:total.value])
             cuts[i:j] = gcuts
@@ -478,16 +510,14 @@ class CodecHipEngine:
         return (np.concatenate(out) if out else np.zeros(0, dtype=np.float32)), cuts
 
     def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, sample_rate: Optional[int] = None,
-               speed: Optional[float] = None, pitch: Optional[float] = None) -> np.ndarray:
+               speed: Optional[float] = None, pitch: Optional[float] = None, fx: Optional[OutputFx] = None) -> np.ndarray:
         """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len).
-        `sample_rate` (output_rate): resampled on the device, (B, max_b resampled_len(lens[b] * frame_len)); row b holds
-        resampled_len(sample_rate, lens[b] * frame_len) samples, zeros after them.
-        `speed` (output_speed): time-scaled on the device (before the resampler); row b holds the timescaled_len - then
-        resampled_len - of its samples, zeros after them.
-        `pitch` (output_pitch, semitones): pitch-shifted on the device, between the two; a plain shift (formants move with
-        the pitch) that leaves every length as it is."""
-        rate = output_rate(sample_rate)
-        pct, cents = output_fx(speed, pitch)
+        `sample_rate`, `speed`, `pitch` (OutputFx.of), or `fx`, the checked value itself: (B, max_b fx.out_len(lens[b] *
+        frame_len)); row b holds its fx.out_len samples, zeros after them.
+        `sample_rate`: resampled on the device.  `speed`: time-scaled on the device (before the resampler).
+        `pitch` (semitones): pitch-shifted on the device, between the two; a plain shift (formants move with the pitch)
+        that leaves every length as it is."""
+        fx = OutputFx.of(sample_rate, speed, pitch) if fx is None else fx
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
@@ -495,35 +525,16 @@ class CodecHipEngine:
         B, R, T = codes.shape
         assert R == self.R, codes.shape
         lens_a = np.full(B, T, dtype=np.int32) if lens is None else np.ascontiguousarray(lens, dtype=np.int32)
-        if cents is not None:
-            width = max(_out_len(rate, pct, int(n) * self.frame_len) for n in lens_a)
+        if fx:
+            width = max(fx.out_len(int(n) * self.frame_len) for n in lens_a)
             audio = np.empty((B, max(width, 1)), dtype=np.float32)
             out_lens = np.zeros(B, dtype=np.int64)
             self._check(self.lib.ft_codec_decode_fxp(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
-                                                     lens_a.ctypes.data_as(C.c_void_p), CODEC_RATE if rate is None else rate,
-                                                     100 if pct is None else pct, cents,
+                                                     lens_a.ctypes.data_as(C.c_void_p), *fx.native,
                                                      audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
                         "ft_codec_decode_fxp")
             return audio[:, :width]
-        if pct is not None:
-            width = max(_out_len(rate, pct, int(n) * self.frame_len) for n in lens_a)
-            audio = np.empty((B, max(width, 1)), dtype=np.float32)
-            out_lens = np.zeros(B, dtype=np.int64)
-            self._check(self.lib.ft_codec_decode_fx(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
-                                                    lens_a.ctypes.data_as(C.c_void_p), CODEC_RATE if rate is None else rate, pct,
-                                                    audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
-                        "ft_codec_decode_fx")
-            return audio[:, :width]
-        if rate is not None:
-            width = max(resampled_len(rate, int(n) * self.frame_len) for n in lens_a)
-            audio = np.empty((B, max(width, 1)), dtype=np.float32)
-            out_lens = np.zeros(B, dtype=np.int64)
-            self._check(self.lib.ft_codec_decode_at(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
-                                                    lens_a.ctypes.data_as(C.c_void_p), rate,
-                                                    audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
-                        "ft_codec_decode_at")
-            return audio[:, :width]
-        audio = np.empty((B, T * self.frame_len), dtype=np.float32)
+        audio = np.empty((B, T * self.frame_len), dtype=np.float32)     # no stage (the launch trace arms through this entry point)
         self._check(self.lib.ft_codec_decode(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
                                              lens_a.ctypes.data_as(C.c_void_p), audio.ctypes.data_as(C.c_void_p)),
                     "ft_codec_decode")
@@ -536,47 +547,43 @@ class CodecStream:
     convolution input - is carried)."""
 
     def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                 pitch: Optional[float] = None):
+                 pitch: Optional[float] = None, fx: Optional[OutputFx] = None):
         self.engine = engine
-        self.rate = output_rate(sample_rate)      # None: the codec's own rate
-        self.pct, self.cents = output_fx(speed, pitch)   # None: the model's own pace / pitch
+        self.fx = OutputFx.of(sample_rate, speed, pitch) if fx is None else fx    # falsy: no output stage, nothing held back
         self._h = C.c_void_p()
-        if self.cents is not None:
-            engine._check(engine.lib.ft_codec_stream_begin_fxp(engine._h, CODEC_RATE if self.rate is None else self.rate,
-                                                               100 if self.pct is None else self.pct, self.cents,
-                                                               C.byref(self._h)), "ft_codec_stream_begin_fxp")
-        elif self.pct is not None:
-            engine._check(engine.lib.ft_codec_stream_begin_fx(engine._h, CODEC_RATE if self.rate is None else self.rate, self.pct,
-                                                              C.byref(self._h)), "ft_codec_stream_begin_fx")
-        elif self.rate is None:
+        if not self.fx:
             engine._check(engine.lib.ft_codec_stream_begin(engine._h, C.byref(self._h)), "ft_codec_stream_begin")
         else:
-            engine._check(engine.lib.ft_codec_stream_begin_at(engine._h, self.rate, C.byref(self._h)), "ft_codec_stream_begin_at")
+            engine._check(engine.lib.ft_codec_stream_begin_fxp(engine._h, *self.fx.native, C.byref(self._h)),
+                          "ft_codec_stream_begin_fxp")
         self.frames = 0
         self.samples_out = 0       # samples handed out so far (a stream at another rate, speed or pitch)
         self.finished = False      # its tail went out: no further chunk
         engine._streams.add(self)      # the engine ends its open streams before it destroys the native context
 
+    rate = property(lambda self: self.fx.rate)      # None: the codec's own rate
+    pct = property(lambda self: self.fx.pct)        # None: the model's own pace
+    cents = property(lambda self: self.fx.cents)    # None: the model's own pitch
+
     @property
-    def _plain(self) -> bool:
-        """The codec's own rate, pace and pitch: no output stage, nothing held back."""
-        return self.rate is None and self.pct is None and self.cents is None
+    def closes_on_final(self) -> bool:
+        """A final chunk closes the stream for decoding only where it has a stage: the tail that went out cannot be taken
+        back.  Without one there is no tail, and the stream goes on."""
+        return bool(self.fx)
 
     def _cap(self, n_in: int) -> int:
         """Most samples the next call can give for n_in more codec samples."""
-        if self._plain:
-            return n_in
-        return _out_len(self.rate, self.pct, self.frames * self.engine.frame_len + n_in) - self.samples_out
+        return self.fx.out_len(self.frames * self.engine.frame_len + n_in) - self.samples_out if self.fx else n_in
 
     def _advance(self, T: int, n_out: int, final: bool) -> None:
         self.frames += T
         self.samples_out += n_out
-        self.finished = self.finished or (final and not self._plain)
+        self.finished = self.finished or (final and self.closes_on_final)
 
     def finish(self) -> np.ndarray:
         """The held-back tail of a stream at another rate, speed or pitch (the input taken as zero past its end); the
         stream takes no further chunk.  Empty at the codec's own rate, pace and pitch, and once the tail went out."""
-        if self._plain or self.finished:
+        if not self.fx or self.finished:
             return np.zeros(0, dtype=np.float32)
         return self.engine.decode_streams([self], [np.zeros((self.engine.R, 0), dtype=np.int32)], [True])[0]
 
@@ -586,7 +593,7 @@ class CodecStream:
         e = self.engine
         codes = np.ascontiguousarray(np.asarray(codes), dtype=np.int32)
         assert codes.ndim == 2 and codes.shape[0] == e.R, codes.shape
-        if not self._plain:
+        if self.fx:
             return e.decode_streams([self], [codes], [final])[0]
         T = codes.shape[1]
         audio = np.empty(T * e.frame_len, dtype=np.float32)

@@ -11,9 +11,16 @@
 
 #include "codec_kernels.h"
 #include "engine.h"
+#include "fx_chain.h"
 #include "join_plan.h"
 
 using namespace ft;
+// the output chain's host arithmetic (fx_chain.h), on the kernels' constants
+using chain::ChainPlan; using chain::FxDesc; using chain::StageChain; using chain::StagePlan;
+using chain::RS_FI; using chain::RS_MAX_RATE;
+static_assert(chain::RS_LDS == RS_LDS && chain::TS_N == TS_N && chain::TS_HS == TS_HS && chain::TS_D == TS_D &&
+              chain::TS_CARRY == TS_CARRY && chain::PS_SHIFT == PS_SHIFT && chain::PS_PHASES == PS_PHASES,
+              "fx_chain.h and codec_kernels.h disagree");
 
 #define FT_TRY(x) do { ft_status s_ = (x); if (s_ != FT_OK) return s_; } while (0)
 
@@ -60,7 +67,7 @@ struct CodecState {
     int mcarry = 0;           // carries per stream (convolution tails + one K/V per transformer layer)
     // resampler (ft_codec_decode_at, ft_codec_stream_*_at): one [L][K] table per output rate, uploaded on its first use;
     // an output buffer and a segment table, allocated on the first resampled call
-    struct RsTab { int L = 1, M = 1, K = 0; float* w = nullptr; };
+    using RsTab = chain::RsTab;
     std::map<int, RsTab> rs_tabs;
     float* rs_out = nullptr;
     size_t rs_cap = 0;
@@ -73,7 +80,7 @@ struct CodecState {
     int* ts_delta = nullptr;
     // pitch stage (ft_codec_decode_fxp, ft_codec_stream_begin_fxp): one [513][K] table per cents value, uploaded on its first
     // use; an output buffer (the resampler's input then) and a segment table, allocated on the first pitched call
-    struct PsTab { long long S = 0; int K = 0; float* w = nullptr; };
+    using PsTab = chain::PsTab;
     std::map<int, PsTab> ps_tabs;
     float* ps_out = nullptr;
     PsSeg* ps_seg = nullptr;
@@ -701,30 +708,10 @@ struct ft_codec_stream {
     std::vector<bf16_t*> kv[2];                    // per transformer layer: [window - 1][2 * H * hd], newest rows last
     struct Tail { bf16_t* buf[2]; int H, C; };
     std::vector<Tail> tails;                       // in the order decode_chain consumes them
-    // resampled output (ft_codec_stream_begin_at; rate 0: the codec's own rate, no resampler): the last K input samples,
-    // two copies (a call reads one and writes the other), and the input / output sample counters
-    int rate = 0;
-    const CodecState::RsTab* rs = nullptr;
-    float* rcarry[2] = {nullptr, nullptr};
-    int rpar = 0;
-    long long nin = 0, nout = 0;
+    // the output stages (ft_codec_stream_begin_at / _fx / _fxp; none: the codec's own rate, pace and pitch), each with its
+    // carry pair - a call reads one copy and writes the other - and its counters on the host (fx_chain.h)
+    StageChain fx;
     bool finished = false;                         // its tail went out (final): no further chunk
-    // time-scaled output (ft_codec_stream_begin_fx; pct 0: none): the input samples a later frame can still read and
-    // the state after the last frame run (two copies each), the counters on the host.  The resampler's input is then the
-    // time-scaled waveform: nin counts those samples.
-    int pct = 0;
-    long long tnum = 0, tden = 0;                  // the stage's rate num / den (pct / 100 without a pitch shift)
-    float *tcarry[2] = {nullptr, nullptr}, *tstate[2] = {nullptr, nullptr};
-    int tpar = 0, tk = 0;                          // tk: frames run so far
-    long long tin = 0, tbase = 0, tout = 0;        // codec samples seen, first one carried, time-scaled samples emitted
-    // pitched output (ft_codec_stream_begin_fxp; cents 0: none): the stage's last K input samples (two copies) and its
-    // input / output counters.  Its input is the time-scaled waveform (rate speed_pct 2^20 / (100 S): `pct` above is then
-    // set only if that stage runs), or the codec's where that rate is 1; the resampler's input is its output.
-    int cents = 0, speed = 100;                    // speed: speed_pct, which fixes the stage's output length
-    const CodecState::PsTab* ps = nullptr;
-    float* pcarry[2] = {nullptr, nullptr};
-    int ppar = 0;
-    long long pin = 0, pout = 0;
     std::vector<void*> owned;
 };
 
@@ -734,55 +721,8 @@ static void stream_orphan(ft_codec_stream* sc) {
     sc->owner = nullptr;
 }
 
-// ---- resampler (RsSeg, resample_kernel): filter design on the host in float64, a Kaiser-windowed sinc at the up-sampled
-// rate L Fi cut off at 0.465 Fmin (pass band to 0.43 Fmin, stop band from 0.5 Fmin, Fmin = min(Fi, Fo)), designed for 75 dB.
-// Tap t of phase p is the prototype at j = p + (K/2 - 1 - t) L up-sampled samples from the output instant, gain L (the
-// zero-stuffed input).  Rates: integers in [8000, 48000] whose reduced L is at most 640; the codec's own rate has K = 0.
-constexpr int RS_FI = 44100, RS_MIN_RATE = 8000, RS_MAX_RATE = 48000, RS_MAX_L = 640, RS_MAX_SEGS = 64;
-
-static double bessel_i0(double x) {
-    double sum = 1.0, term = 1.0;
-    const double q = x * x / 4.0;
-    for (int k = 1; k < 500 && term > 1e-17 * sum; ++k) {
-        term *= q / ((double)k * k);
-        sum += term;
-    }
-    return sum;
-}
-
-// Validates `rate` (an error message, or null) and gives L, M, K; fills w ([L][K] float32) when non-null.
-static const char* rs_design(int rate, int* L, int* M, int* K, std::vector<float>* w) {
-    if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return "sample rate outside [8000, 48000]";
-    const int g = std::gcd(rate, RS_FI), l = rate / g, m = RS_FI / g;
-    if (l > RS_MAX_L) return "sample rate: rate / gcd(rate, 44100) exceeds 640";
-    *L = l;
-    *M = m;
-    *K = 0;
-    if (rate == RS_FI) return nullptr;
-    const double A = 75.0, beta = 0.1102 * (A - 8.7), fmin = std::min(rate, RS_FI);
-    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * RS_FI / fmin);
-    k += k & 1;
-    if ((255L * m + l - 1) / l + k + 1 > RS_LDS) return "sample rate: filter window exceeds the resampler's LDS stage";
-    *K = k;
-    if (!w) return nullptr;
-    const double fc = 0.465 * fmin / ((double)l * RS_FI), half = 0.5 * k * l, ib = bessel_i0(beta);
-    w->assign((size_t)l * k, 0.f);
-    for (int p = 0; p < l; ++p)
-        for (int t = 0; t < k; ++t) {
-            const double j = p + (double)(k / 2 - 1 - t) * l, r = j / half, x = M_PI * 2.0 * fc * j;
-            const double sinc = j == 0 ? 1.0 : std::sin(x) / x;
-            (*w)[(size_t)p * k + t] = (float)(2.0 * fc * l * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / ib);
-        }
-    return nullptr;
-}
-
-// Outputs available after `nin` input samples: all of them at the end of the input (final), else those whose taps all
-// lie within it (floor(n M / L) + K/2 < nin).
-static long long rs_ready(const CodecState::RsTab& t, long long nin, bool final) {
-    if (t.K == 0) return nin;
-    const long long a = final ? nin : nin - t.K / 2;
-    return a > 0 ? (a * t.L + t.M - 1) / t.M : 0;
-}
+// ---- resampler (RsSeg, resample_kernel; the filter design and rs_ready in fx_chain.h)
+constexpr int RS_MAX_SEGS = 64;
 
 // The device table of `rate` (uploaded on its first use); the caller holds s->mu.
 static ft_status rs_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) {
@@ -791,7 +731,7 @@ static ft_status rs_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) 
     if (it == s->rs_tabs.end()) {
         CodecState::RsTab t;
         std::vector<float> w;
-        if (const char* e = rs_design(rate, &t.L, &t.M, &t.K, &w)) return ft_fail(ctx, FT_ERR_ARG, e);
+        if (const char* e = chain::rs_design(rate, &t.L, &t.M, &t.K, &w)) return ft_fail(ctx, FT_ERR_ARG, e);
         if (t.K > 0) {
             FT_TRY(cmalloc(ctx, &t.w, w.size()));
             FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -822,40 +762,7 @@ static ft_status rs_alloc(ft_ctx* ctx, bool wide = false) {
     return FT_OK;
 }
 
-// ---- time-scale stage (TsSeg, timescale_kernel; fishtts_hip.h states the algorithm)
-constexpr int TS_MIN_PCT = 50, TS_MAX_PCT = 200;
-static bool ts_ok(int pct) { return pct >= TS_MIN_PCT && pct <= TS_MAX_PCT; }
-// The stage runs at the rational rate num / den: pct / 100 for a speed alone, pct 2^20 / (100 S) under a pitch shift
-// (k HS num stays below 2^52 for any stream within max_frames).
-struct TsRate { long long num = 100, den = 100; };
-static long long ts_len(TsRate r, long long n) { return (n * r.den + r.num - 1) / r.num; }
-static long long ts_len(int pct, long long n) { return ts_len(TsRate{pct, 100}, n); }
-static long long ts_a(TsRate r, long long k) { return k * TS_HS * r.num / r.den; }
-// Input samples frame k needs to have been seen: its search region ends at a_k + HS + D, its template (the continuation
-// of frame k - 1) at most at a_{k-1} + D + N, which lies further on below speed 1.
-static long long ts_need(TsRate r, long long k) {
-    return std::max(ts_a(r, k), k > 0 ? ts_a(r, k - 1) + TS_HS : 0) + TS_HS + TS_D;
-}
-struct TsPlan { int k1 = 0; long long out = 0, base = 0; };
-// What a stream that has run k0 frames does once it has seen `nin` samples: frames [k0, k1), outputs below `out` final,
-// input from `base` on kept for later frames.
-static TsPlan ts_plan(TsRate r, int k0, long long nin, bool final) {
-    TsPlan p;
-    if (final) {
-        p.out = ts_len(r, nin);
-        p.k1 = (int)((p.out + TS_HS - 1) / TS_HS) + 1;
-        p.base = nin;
-        return p;
-    }
-    p.k1 = k0;
-    while (ts_need(r, p.k1) <= nin) ++p.k1;
-    p.out = p.k1 > 0 ? (long long)(p.k1 - 1) * TS_HS : 0;
-    p.base = ts_a(r, p.k1) - TS_HS - TS_D;
-    if (p.k1 > 0) p.base = std::min(p.base, ts_a(r, p.k1 - 1) - TS_D);
-    p.base = std::max(p.base, 0LL);
-    return p;
-}
-
+// ---- time-scale stage (TsSeg, timescale_kernel; fishtts_hip.h states the algorithm, fx_chain.h plans its frames)
 // The stage's buffers, allocated once: twice max_frames of audio (speed 0.5) plus what 64 streams can hold back.
 static ft_status ts_alloc(ft_ctx* ctx) {
     CodecState* s = ctx->codec;
@@ -880,54 +787,7 @@ static ft_status ts_alloc(ft_ctx* ctx) {
     return rs_alloc(ctx, true);
 }
 
-// ---- pitch stage (PsSeg, pitch_kernel; fishtts_hip.h states it): the step S = llround(2^20 2^(cents / 1200)) and the
-// [513][K] table, a Kaiser-windowed sinc designed in float64 with the resampler's constants (75 dB, transition 0.07), cut off
-// at 0.465 min(1, 1 / r) cycles per input sample, r = S / 2^20; tap t of row p is the prototype at p / 512 + (K/2 - 1 - t).
-constexpr int PS_MAX_CENTS = 1200;
-static bool ps_design(int cents, long long* S, int* K, std::vector<float>* w) {
-    if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS) return false;
-    *S = std::llround(std::ldexp(std::exp2((double)cents / 1200.0), PS_SHIFT));
-    *K = 0;
-    if (cents == 0) return true;
-    const double A = 75.0, beta = 0.1102 * (A - 8.7), r = std::ldexp((double)*S, -PS_SHIFT);
-    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * std::max(1.0, r));
-    k += k & 1;
-    *K = k;
-    if (!w) return true;
-    const double fc = 0.465 * std::min(1.0, 1.0 / r), half = 0.5 * k, ib = bessel_i0(beta);
-    w->assign((size_t)(PS_PHASES + 1) * k, 0.f);
-    for (int p = 0; p <= PS_PHASES; ++p)
-        for (int t = 0; t < k; ++t) {
-            const double tau = (double)p / PS_PHASES + (double)(k / 2 - 1 - t), q = tau / half, x = M_PI * 2.0 * fc * tau;
-            const double sinc = tau == 0 ? 1.0 : std::sin(x) / x;
-            (*w)[(size_t)p * k + t] = (float)(2.0 * fc * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - q * q))) / ib);
-        }
-    return true;
-}
-
-// The stages in front of the resampler for (speed_pct, cents): the time-scale stage's rate, absent at rate 1.  Accepted:
-// cents in [-1200, 1200] and an effective rate speed_pct 2^20 / (100 S) in [0.5, 2].
-struct FxPlan { TsRate ts; bool has_ts = false; long long S = 0; };
-static bool fx_plan(int pct, int cents, FxPlan* out) {
-    FxPlan f;
-    int k;
-    if (!ts_ok(pct) || !ps_design(cents, &f.S, &k, nullptr)) return false;
-    f.ts = TsRate{(long long)pct << PS_SHIFT, 100 * f.S};
-    if (50 * f.S > f.ts.num || f.ts.num > 200 * f.S) return false;
-    f.has_ts = f.ts.num != f.ts.den;
-    if (cents == 0) f.ts = TsRate{pct, 100};   // the speed alone, as it always ran
-    if (out) *out = f;
-    return true;
-}
-
-// Outputs available after `nin` input samples: those whose taps all lie within them ((n S >> 20) + K/2 < nin); at the end of
-// the input (final) all `total` of them.
-static long long ps_ready(const CodecState::PsTab& t, long long nin, bool final, long long total) {
-    if (final) return total;
-    const long long a = nin - t.K / 2;
-    return a > 0 ? ((a << PS_SHIFT) + t.S - 1) / t.S : 0;
-}
-
+// ---- pitch stage (PsSeg, pitch_kernel; fishtts_hip.h states it, fx_chain.h designs its table)
 // The device table of `cents` (uploaded on its first use); the caller holds s->mu.
 static ft_status ps_table(ft_ctx* ctx, int cents, const CodecState::PsTab** out) {
     CodecState* s = ctx->codec;
@@ -935,7 +795,7 @@ static ft_status ps_table(ft_ctx* ctx, int cents, const CodecState::PsTab** out)
     if (it == s->ps_tabs.end()) {
         CodecState::PsTab t;
         std::vector<float> w;
-        if (!ps_design(cents, &t.S, &t.K, &w) || t.K == 0) return ft_fail(ctx, FT_ERR_ARG, "pitch outside [-1200, 1200] cents");
+        if (!chain::ps_design(cents, &t.S, &t.K, &w) || t.K == 0) return ft_fail(ctx, FT_ERR_ARG, "pitch outside [-1200, 1200] cents");
         FT_TRY(cmalloc(ctx, &t.w, w.size()));
         FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
         it = s->ps_tabs.emplace(cents, t).first;
@@ -1306,9 +1166,9 @@ extern "C" ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* sc, co
     FT_TRY(codec_ready(ctx, false));
     if (!codes || !audio || T < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_stream_decode: bad argument");
     if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: the stream belongs to another (or a destroyed) context");
-    if (sc->rate) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
-    if (sc->pct) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another speed (ft_codec_stream_decode_many_at)");
-    if (sc->ps) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another pitch (ft_codec_stream_decode_many_at)");
+    if (sc->fx.rs.tab) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
+    if (sc->fx.ts.on) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another speed (ft_codec_stream_decode_many_at)");
+    if (sc->fx.ps.tab) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another pitch (ft_codec_stream_decode_many_at)");
     const ft_codec_config& c = ctx->cc;
     if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: chunk longer than max_frames");
     if (sc->t0 + T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: stream longer than max_frames (rope table)");
@@ -1433,9 +1293,9 @@ static ft_status many_check(ft_ctx* ctx, const std::string& fn, int n, ft_codec_
         if (lens[j] < 0 || (lens[j] == 0 && !(at && final && final[j])))
             return ft_fail(ctx, FT_ERR_ARG, fn + ": a chunk of less than one frame" + (at ? " (zero only with final)" : ""));
         if (sc->owner != ctx) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream belongs to another (or a destroyed) context");
-        if (!at && sc->rate) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
-        if (!at && sc->pct) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another speed (ft_codec_stream_decode_many_at)");
-        if (!at && sc->ps) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another pitch (ft_codec_stream_decode_many_at)");
+        if (!at && sc->fx.rs.tab) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
+        if (!at && sc->fx.ts.on) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another speed (ft_codec_stream_decode_many_at)");
+        if (!at && sc->fx.ps.tab) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another pitch (ft_codec_stream_decode_many_at)");
         if (at && sc->finished) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream whose final chunk went out");
         for (int i = 0; i < j; ++i)
             if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, fn + ": a stream named twice");
@@ -1458,53 +1318,50 @@ extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_code
     return decode_many(ctx, n, streams, codes, lens, audio);
 }
 
-// The output stages of one item decoded from zero state, n_in codec samples -> n_ts after the time-scale and pitch stages
-// -> n_out after the resampler: a fresh input to each stage, zeros before it, zeros after it (the whole tail).  False: no
-// stage at all (the codec's own rate, pace and pitch).  `t`, `pct`, `pt`, `f` as decode_items takes them.
-static bool item_stages(CodecState* s, const CodecState::RsTab* t, int pct, const CodecState::PsTab* pt, const FxPlan* f,
-                        size_t n_in, size_t n_ts, size_t n_out, Fx& g) {
-    if ((!t || t->K == 0) && pct == 100 && !pt) return false;
-    g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)n_ts, (int)n_out, 1, 1, 0, 0});
-    if (t && t->K > 0) { g.rs[0].w = t->w; g.rs[0].L = t->L; g.rs[0].M = t->M; g.rs[0].K = t->K; }
-    if (pt) {   // the time-scale stage at the rate of f (or none), then the pitch stage back to n_ts samples
-        long long n_mid = (long long)n_in;
-        if (f->has_ts) {
-            const TsPlan p = ts_plan(f->ts, 0, (long long)n_in, true);
-            n_mid = p.out;
-            g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, f->ts.num, f->ts.den,
-                                 (int)n_in, (int)n_mid, 0, p.k1, 0, 0});
-        }
-        g.ps.assign(1, PsSeg{s->audio, pt->w, nullptr, nullptr, nullptr, 0, 0, pt->S, (int)n_mid, (int)n_ts, pt->K, 0});
-    } else if (pct != 100) {
-        const TsPlan p = ts_plan(TsRate{pct, 100}, 0, (long long)n_in, true);
-        g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, pct, 100, (int)n_in, (int)n_ts, 0, p.k1, 0, 0});
-    }
+// The segments of one waveform's stages for a call: `x` holds the call's codec samples, `j` is the waveform's place in the
+// call (its resampler segment, which every waveform has: the copy out), `deltas` the test hooks' d_k.  A stage reads the
+// current copy of its carry and writes the other; ts_enqueue and ps_enqueue point the later stages at the earlier ones' output.
+static void chain_segs(const StageChain& c, const ChainPlan& p, const float* x, int j, int* deltas, Fx& fx) {
+    const chain::TsStage& t = c.ts;
+    if (t.on)
+        fx.ts.push_back(TsSeg{x, t.carry[t.par], t.carry[t.par ^ 1], t.state[t.par], t.state[t.par ^ 1], nullptr, deltas, t.nin, t.base,
+                              p.ts.base, t.nout, t.rate.num, t.rate.den, (int)p.ts.in, (int)p.ts.out, t.k, p.ts.k1, j, 0});
+    const chain::PsStage& q = c.ps;
+    if (q.tab)
+        fx.ps.push_back(PsSeg{x, q.tab->w, q.carry[q.par], q.carry[q.par ^ 1], nullptr, q.nin, q.nout, q.tab->S, (int)p.ps.in,
+                              (int)p.ps.out, q.tab->K, j});
+    const chain::RsStage& r = c.rs;
+    fx.rs.push_back(RsSeg{x, nullptr, r.carry[r.par], r.carry[r.par ^ 1], nullptr, r.nin, r.nout, (int)p.rs.in, (int)p.rs.out, 1, 1, 0, 0});
+    if (r.tab) { RsSeg& g = fx.rs.back(); g.w = r.tab->w; g.L = r.tab->L; g.M = r.tab->M; g.K = r.tab->K; }
+}
+
+// The output stages of one item of n_in codec samples decoded from zero state: a fresh input to each stage, zeros before
+// it, zeros after it (the whole tail).  False: no stage at all (the codec's own rate, pace and pitch).
+static bool item_stages(CodecState* s, const FxDesc& d, long long n_in, Fx& g) {
+    if (!d.any()) return false;
+    const StageChain c = d.fresh();
+    chain_segs(c, c.plan(n_in, true), s->audio, 0, nullptr, g);
     return true;
 }
 
-// The items of ft_codec_decode / ft_codec_decode_at, one after the other: item b's samples go to audio + b * stride, zeros
-// behind them.  `t`: the resampler's table (null, or K = 0: the codec's own rate); `pct`: the speed (100 and no pitch: no
-// time-scale stage); `pt`: the pitch stage's table (null: none), the time-scale stage then at the rate of `f`.
+// The items of ft_codec_decode / ft_codec_decode_fxp, one after the other through the chain `d`: item b's samples go to
+// audio + b * stride, zeros behind them.
 static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int B, int T, const int32_t* lens, float* audio,
-                              size_t stride, const CodecState::RsTab* t, int64_t* out_lens, int pct = 100,
-                              const CodecState::PsTab* pt = nullptr, const FxPlan* f = nullptr) {
+                              size_t stride, const FxDesc& d, int64_t* out_lens) {
     CodecState* s = ctx->codec;
     const int R = ctx->cc.n_codebooks + 1;
     for (int b = 0; b < B; ++b) {
         const int Tb = lens ? lens[b] : T;
         if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
-        const size_t n_in = (size_t)Tb * s->frame_len, n_ts = pct == 100 ? n_in : (size_t)ts_len(pct, (long long)n_in);
-        const size_t n_out = t ? (n_ts * t->L + t->M - 1) / t->M : n_ts;   // ft_resampled_len
+        const long long n_in = (long long)Tb * s->frame_len;
+        const size_t n_out = (size_t)d.out_len(n_in);
         float* out = audio + (size_t)b * stride;
         if (out_lens) out_lens[b] = (int64_t)n_out;
         if (n_out < stride) memset(out + n_out, 0, (stride - n_out) * sizeof(float));
         if (Tb == 0) continue;
         Fx g;
-        if (!item_stages(s, t, pct, pt, f, n_in, n_ts, n_out, g)) {
-            FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out));
-            continue;
-        }
-        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, &g));
+        const bool staged = item_stages(s, d, n_in, g);
+        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, staged ? &g : nullptr));
     }
     return FT_OK;
 }
@@ -1519,14 +1376,14 @@ extern "C" ft_status ft_codec_decode(ft_ctx* ctx, const int32_t* codes, int32_t 
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
     TraceScope traced(s, B == 1);
-    return decode_items(ctx, "ft_codec_decode", codes, B, T, lens, audio, (size_t)T * s->frame_len, nullptr, nullptr);
+    return decode_items(ctx, "ft_codec_decode", codes, B, T, lens, audio, (size_t)T * s->frame_len, FxDesc(), nullptr);
 }
 
 // ---- resampled output (fishtts_hip.h: ft_resample_filter .. ft_codec_stream_decode_many_at, ft_test_resample)
 extern "C" ft_status ft_resample_filter(int32_t sample_rate, int32_t* L, int32_t* M, int32_t* K, float* table) {
     int l = 1, m = 1, k = 0;
     std::vector<float> w;
-    if (rs_design(sample_rate, &l, &m, &k, table ? &w : nullptr)) return FT_ERR_ARG;
+    if (chain::rs_design(sample_rate, &l, &m, &k, table ? &w : nullptr)) return FT_ERR_ARG;
     if (L) *L = l;
     if (M) *M = m;
     if (K) *K = k;
@@ -1536,54 +1393,60 @@ extern "C" ft_status ft_resample_filter(int32_t sample_rate, int32_t* L, int32_t
 
 extern "C" int64_t ft_resampled_len(int32_t sample_rate, int64_t n_in) {
     int l = 1, m = 1, k = 0;
-    if (n_in < 0 || rs_design(sample_rate, &l, &m, &k, nullptr)) return -1;
+    if (n_in < 0 || chain::rs_design(sample_rate, &l, &m, &k, nullptr)) return -1;
     return (n_in * l + m - 1) / m;
 }
 
-static ft_status rs_refuse(ft_ctx* ctx, const char* fn, int rate) {
-    int l, m, k;
-    const char* e = rs_design(rate, &l, &m, &k, nullptr);
-    return e ? ft_fail(ctx, FT_ERR_ARG, std::string(fn) + ": " + e + " (" + std::to_string(rate) + ")") : FT_OK;
+// A call's chain from its three values, judged without a lock and before anything else: the rate, then the speed, then
+// the cents, then the pair.  `fn` names the entry point in the message.
+static ft_status fx_refuse(ft_ctx* ctx, const std::string& fn, int rate, int pct, int cents, FxDesc* d) {
+    const char* why = nullptr;
+    switch (d->make(rate, pct, cents, &why)) {
+    case FxDesc::RATE: return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why + " (" + std::to_string(rate) + ")");
+    case FxDesc::SPEED: return ft_fail(ctx, FT_ERR_ARG, fn + ": speed outside [50, 200] percent (" + std::to_string(pct) + ")");
+    case FxDesc::CENTS: return ft_fail(ctx, FT_ERR_ARG, fn + ": pitch outside [-1200, 1200] cents (" + std::to_string(cents) + ")");
+    case FxDesc::PAIR:
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": speed / pitch ratio outside [0.5, 2] (speed " + std::to_string(pct) + " percent, " +
+                                            std::to_string(cents) + " cents)");
+    case FxDesc::OK: break;
+    }
+    return FT_OK;
 }
 
-static ft_status ts_refuse(ft_ctx* ctx, const std::string& fn, int pct) {
-    return ts_ok(pct) ? FT_OK : ft_fail(ctx, FT_ERR_ARG, fn + ": speed outside [50, 200] percent (" + std::to_string(pct) + ")");
+// The chain's device side; the caller holds s->mu.  The tables of its rate and cents, and the buffers of the first stage it
+// has (each stage's allocation brings those of the stages behind it).
+static ft_status fx_prepare(ft_ctx* ctx, FxDesc* d) {
+    FT_TRY(rs_table(ctx, d->rate, &d->rs));
+    if (d->cents != 0) {
+        FT_TRY(ps_table(ctx, d->cents, &d->ps));
+        return ps_alloc(ctx);
+    }
+    if (d->pct != 100) return ts_alloc(ctx);
+    return d->K > 0 ? rs_alloc(ctx) : FT_OK;
 }
 
 extern "C" int64_t ft_timescaled_len(int32_t speed_pct, int64_t n_in) {
-    return n_in < 0 || !ts_ok(speed_pct) ? -1 : ts_len(speed_pct, n_in);
-}
-
-// cents and its combination with the speed (which ts_refuse judged on its own)
-static ft_status ps_refuse(ft_ctx* ctx, const std::string& fn, int pct, int cents, FxPlan* f) {
-    if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS)
-        return ft_fail(ctx, FT_ERR_ARG, fn + ": pitch outside [-1200, 1200] cents (" + std::to_string(cents) + ")");
-    if (!fx_plan(pct, cents, f))
-        return ft_fail(ctx, FT_ERR_ARG, fn + ": speed / pitch ratio outside [0.5, 2] (speed " + std::to_string(pct) + " percent, " +
-                                            std::to_string(cents) + " cents)");
-    return FT_OK;
+    return n_in < 0 || !chain::ts_ok(speed_pct) ? -1 : chain::ts_len(speed_pct, n_in);
 }
 
 extern "C" ft_status ft_pitch_filter(int32_t cents, int64_t* step, int32_t* K, float* table) {
     long long S = 0;
     int k = 0;
     std::vector<float> w;
-    if (!ps_design(cents, &S, &k, table ? &w : nullptr)) return FT_ERR_ARG;
+    if (!chain::ps_design(cents, &S, &k, table ? &w : nullptr)) return FT_ERR_ARG;
     if (step) *step = S;
     if (K) *K = k;
     if (table && !w.empty()) memcpy(table, w.data(), w.size() * sizeof(float));
     return FT_OK;
 }
 
-extern "C" ft_status ft_pitch_ok(int32_t speed_pct, int32_t cents) { return fx_plan(speed_pct, cents, nullptr) ? FT_OK : FT_ERR_ARG; }
+extern "C" ft_status ft_pitch_ok(int32_t speed_pct, int32_t cents) { return chain::fx_plan(speed_pct, cents, nullptr) ? FT_OK : FT_ERR_ARG; }
 
 static ft_status decode_fx(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
                            int32_t sample_rate, int32_t pct, float* audio, int64_t* out_lens, int32_t cents = 0) {
     if (!ctx) return FT_ERR_ARG;
-    FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
-    FT_TRY(ts_refuse(ctx, fn, pct));
-    FxPlan f;
-    FT_TRY(ps_refuse(ctx, fn, pct, cents, &f));
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, pct, cents, &d));
     FT_TRY(codec_ready(ctx));
     if (!codes || !audio || !out_lens || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
     if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
@@ -1592,19 +1455,12 @@ static ft_status decode_fx(ft_ctx* ctx, const std::string& fn, const int32_t* co
     for (int b = 0; b < B; ++b) {
         const int Tb = lens ? lens[b] : T;
         if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
-        stride = std::max(stride, ft_resampled_len(sample_rate, ts_len(pct, (int64_t)Tb * s->frame_len)));
+        stride = std::max(stride, (int64_t)d.out_len((long long)Tb * s->frame_len));
     }
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    const CodecState::RsTab* t = nullptr;
-    FT_TRY(rs_table(ctx, sample_rate, &t));
-    const CodecState::PsTab* pt = nullptr;
-    if (cents != 0) {
-        FT_TRY(ps_table(ctx, cents, &pt));
-        FT_TRY(ps_alloc(ctx));
-    } else if (pct != 100) FT_TRY(ts_alloc(ctx));
-    else if (t->K > 0) FT_TRY(rs_alloc(ctx));
-    return decode_items(ctx, fn, codes, B, T, lens, audio, (size_t)stride, t, out_lens, pct, pt, &f);
+    FT_TRY(fx_prepare(ctx, &d));
+    return decode_items(ctx, fn, codes, B, T, lens, audio, (size_t)stride, d, out_lens);
 }
 
 extern "C" ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
@@ -1698,10 +1554,8 @@ extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int
                                           int64_t* cuts) {
     const std::string fn = "ft_codec_decode_join";
     if (!ctx) return FT_ERR_ARG;
-    FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
-    FT_TRY(ts_refuse(ctx, fn, speed_pct));
-    FxPlan f;
-    FT_TRY(ps_refuse(ctx, fn, speed_pct, pitch_cents, &f));
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, speed_pct, pitch_cents, &d));
     FT_TRY(codec_ready(ctx));
     if (!codes || !audio || !total || !cuts || B < 1 || B > JOIN_MAX_ITEMS || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
     if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
@@ -1712,29 +1566,21 @@ extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int
         const int Tb = lens ? lens[b] : T;
         if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
         frames += Tb;
-        n[b] = ft_resampled_len(sample_rate, ts_len(speed_pct, (int64_t)Tb * s->frame_len));
+        n[b] = d.out_len((long long)Tb * s->frame_len);
     }
     if (frames > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": sum(lens) exceeds max_frames");
     if (const char* why = join_check(B, n, jp, gaps, started, capacity, &need)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
     const int64_t in_floats = join_offsets(B, n, off);
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    const CodecState::RsTab* t = nullptr;
-    FT_TRY(rs_table(ctx, sample_rate, &t));
-    const CodecState::PsTab* pt = nullptr;
-    if (pitch_cents != 0) {
-        FT_TRY(ps_table(ctx, pitch_cents, &pt));
-        FT_TRY(ps_alloc(ctx));
-    } else if (speed_pct != 100) FT_TRY(ts_alloc(ctx));
-    else if (t->K > 0) FT_TRY(rs_alloc(ctx));
+    FT_TRY(fx_prepare(ctx, &d));
     FT_TRY(join_alloc(ctx, (size_t)in_floats, (size_t)need));
     // the items as decode_items runs them (one synchronize each, as there), their samples left side by side in join_in
     for (int b = 0; b < B; ++b) {
         const int Tb = lens ? lens[b] : T;
         if (Tb == 0) continue;
-        const size_t n_in = (size_t)Tb * s->frame_len, n_ts = speed_pct == 100 ? n_in : (size_t)ts_len(speed_pct, (long long)n_in);
         Fx g;
-        const bool staged = item_stages(s, t, speed_pct, pt, &f, n_in, n_ts, (size_t)n[b], g);
+        const bool staged = item_stages(s, d, (long long)Tb * s->frame_len, g);
         FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, s->join_in + off[b], nullptr, staged ? &g : nullptr, hipMemcpyDeviceToDevice));
     }
     return join_run(ctx, B, n, off, jp, gaps, started, audio, total, cuts, need, false);
@@ -1766,31 +1612,22 @@ extern "C" ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_
 static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sample_rate, int32_t pct, ft_codec_stream** out,
                                  int32_t cents = 0) {
     if (!ctx || !out) return FT_ERR_ARG;
-    FT_TRY(rs_refuse(ctx, fn.c_str(), sample_rate));
-    FT_TRY(ts_refuse(ctx, fn, pct));
-    FxPlan f;
-    FT_TRY(ps_refuse(ctx, fn, pct, cents, &f));
-    const bool has_ts = cents != 0 ? f.has_ts : pct != 100;
-    const CodecState::PsTab* pt = nullptr;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, pct, cents, &d));
     FT_TRY(codec_ready(ctx));
     CodecState* s = ctx->codec;
-    const CodecState::RsTab* t = nullptr;
     {
         std::lock_guard<std::mutex> lock(s->mu);
         FT_HIP(ctx, hipSetDevice(ctx->device));
-        FT_TRY(rs_table(ctx, sample_rate, &t));
-        if (cents != 0) {
-            FT_TRY(ps_table(ctx, cents, &pt));
-            FT_TRY(ps_alloc(ctx));
-        } else if (pct != 100) FT_TRY(ts_alloc(ctx));
-        else if (t->K > 0) FT_TRY(rs_alloc(ctx));
+        FT_TRY(fx_prepare(ctx, &d));
     }
     ft_codec_stream* sc = nullptr;
     FT_TRY(ft_codec_stream_begin(ctx, &sc));
-    if (t->K == 0 && pct == 100 && !pt) {
+    if (!d.any()) {
         *out = sc;
         return FT_OK;
     }
+    StageChain c = d.fresh();
     bool ok = true;   // (as ft_codec_stream_begin: the stream is not visible to other calls yet)
     auto zalloc = [&](float** q, size_t n) {
         void* v = nullptr;
@@ -1800,32 +1637,19 @@ static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sam
         *q = (float*)v;
         ok = hipMemsetAsync(v, 0, n * sizeof(float), s->stream) == hipSuccess;   // the input before the first sample
     };
-    for (int k = 0; k < 2 && t->K > 0; ++k) zalloc(&sc->rcarry[k], (size_t)t->K);
-    for (int k = 0; k < 2 && has_ts; ++k) {
-        zalloc(&sc->tcarry[k], (size_t)TS_CARRY);
-        zalloc(&sc->tstate[k], (size_t)TS_STATE);
+    for (int k = 0; k < 2 && c.rs.tab; ++k) zalloc(&c.rs.carry[k], (size_t)c.rs.tab->K);
+    for (int k = 0; k < 2 && c.ts.on; ++k) {
+        zalloc(&c.ts.carry[k], (size_t)TS_CARRY);
+        zalloc(&c.ts.state[k], (size_t)TS_STATE);
     }
-    for (int k = 0; k < 2 && pt; ++k) zalloc(&sc->pcarry[k], (size_t)pt->K);
+    for (int k = 0; k < 2 && c.ps.tab; ++k) zalloc(&c.ps.carry[k], (size_t)c.ps.tab->K);
     ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         ft_codec_stream_end(ctx, sc);
         return ft_fail(ctx, FT_ERR_NOMEM, fn + ": could not set up the output stages' carry");
     }
-    if (t->K > 0) {
-        sc->rate = sample_rate;
-        sc->rs = t;
-    }
-    if (has_ts) {
-        sc->pct = pct;
-        sc->tnum = f.ts.num;
-        sc->tden = f.ts.den;
-    }
-    if (pt) {
-        sc->cents = cents;
-        sc->speed = pct;
-        sc->ps = pt;
-    }
+    sc->fx = c;
     *out = sc;
     return FT_OK;
 }
@@ -1852,28 +1676,18 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     FT_TRY(many_check(ctx, "ft_codec_stream_decode_many_at", n, streams, lens, final, true));
     CodecState* s = ctx->codec;
     const int fl = s->frame_len;
+    // what every stream's stages take and emit in this call, walked in chain order (fx_chain.h)
     long long total_out = 0, total_ts = 0, total_ps = 0;
     bool any_fx = false;
-    std::vector<long long> no(n), pn(n);   // samples each stream gives out in this call; those its pitch stage gives
-    std::vector<TsPlan> tp(n);
+    std::vector<ChainPlan> plan(n);
     for (int j = 0; j < n; ++j) {
-        const ft_codec_stream* sc = streams[j];
-        const bool fin = final && final[j];
-        long long nin = (long long)lens[j] * fl;   // samples into the resampler
-        if (sc->pct) {
-            tp[j] = ts_plan(TsRate{sc->tnum, sc->tden}, sc->tk, sc->tin + nin, fin);
-            if (sc->tin + nin - tp[j].base > TS_CARRY) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: time-scale carry out of step");
-            nin = tp[j].out - sc->tout;
-            total_ts += nin;
-        }
-        if (sc->ps) {   // its outputs number ft_timescaled_len(speed, codec samples) in the end, whatever its input's length
-            pn[j] = ps_ready(*sc->ps, sc->pin + nin, fin, ts_len(sc->speed, (long long)(sc->t0 + lens[j]) * fl)) - sc->pout;
-            nin = pn[j];
-            total_ps += nin;
-        }
-        no[j] = sc->rs ? rs_ready(*sc->rs, sc->nin + nin, fin) - sc->nout : nin;
-        total_out += no[j];
-        any_fx = any_fx || sc->rs || sc->pct || sc->ps;
+        const StageChain& c = streams[j]->fx;
+        plan[j] = c.plan((long long)lens[j] * fl, final && final[j]);
+        if (c.ts.held(plan[j].ts) > TS_CARRY) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: time-scale carry out of step");
+        if (c.ts.on) total_ts += plan[j].ts.out;
+        if (c.ps.tab) total_ps += plan[j].ps.out;
+        total_out += plan[j].rs.out;
+        any_fx = any_fx || c.any();
     }
     if (any_fx && ((size_t)total_out > s->rs_cap || (size_t)total_ts > s->ts_cap || (size_t)total_ps > s->ts_cap))
         return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: output buffer");
@@ -1886,32 +1700,13 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     FT_HIP(ctx, hipSetDevice(ctx->device));
     if (!any_fx) {   // the codec's rate and pace only: ft_codec_stream_decode_many
         if (!cs.empty()) FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio));
-        for (int j = 0; j < n; ++j) out_lens[j] = no[j];
+        for (int j = 0; j < n; ++j) out_lens[j] = plan[j].rs.out;
         return FT_OK;
     }
     Fx fx;
-    fx.rs.resize(n);
     long long P = 0;
     for (int j = 0; j < n; ++j) {
-        const ft_codec_stream* sc = streams[j];
-        RsSeg& g = fx.rs[j];
-        g = RsSeg{s->audio + P * fl, nullptr, nullptr, nullptr, nullptr, sc->nin, sc->nout, lens[j] * fl, (int)no[j], 1, 1, 0, 0};
-        if (sc->pct) {   // the resampler (or the copy) reads what the time-scale stage emits
-            g.n_in = (int)(tp[j].out - sc->tout);
-            fx.ts.push_back(TsSeg{s->audio + P * fl, sc->tcarry[sc->tpar], sc->tcarry[sc->tpar ^ 1], sc->tstate[sc->tpar],
-                                  sc->tstate[sc->tpar ^ 1], nullptr, nullptr, sc->tin, sc->tbase, tp[j].base, sc->tout,
-                                  sc->tnum, sc->tden, lens[j] * fl, g.n_in, sc->tk, tp[j].k1, j, 0});
-        }
-        if (sc->ps) {   // between the two: it reads the time-scale stage's (or the codec's) samples, the resampler reads its
-            fx.ps.push_back(PsSeg{g.x, sc->ps->w, sc->pcarry[sc->ppar], sc->pcarry[sc->ppar ^ 1], nullptr, sc->pin, sc->pout,
-                                  sc->ps->S, g.n_in, (int)pn[j], sc->ps->K, j});
-            g.n_in = (int)pn[j];
-        }
-        if (sc->rs) {
-            g.w = sc->rs->w; g.L = sc->rs->L; g.M = sc->rs->M; g.K = sc->rs->K;
-            g.carry_rd = sc->rcarry[sc->rpar];
-            g.carry_wr = sc->rcarry[sc->rpar ^ 1];
-        }
+        chain_segs(streams[j]->fx, plan[j], s->audio + P * fl, j, nullptr, fx);
         P += lens[j];
     }
     if (!cs.empty()) {
@@ -1921,28 +1716,9 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     }
     for (int j = 0; j < n; ++j) {
         ft_codec_stream* sc = streams[j];
-        out_lens[j] = no[j];
-        if (!sc->rs && !sc->pct && !sc->ps) continue;
-        long long fed = (long long)lens[j] * fl;   // samples into the stage after the time-scale stage
-        if (sc->pct) fed = tp[j].out - sc->tout;
-        if (sc->ps) {
-            sc->pin += fed;
-            sc->pout += pn[j];
-            sc->ppar ^= 1;
-            fed = pn[j];
-        }
-        if (sc->pct) {
-            sc->nin += fed;
-            sc->tin += (long long)lens[j] * fl;
-            sc->tout = tp[j].out;
-            sc->tbase = tp[j].base;
-            sc->tk = tp[j].k1;
-            sc->tpar ^= 1;
-        } else {
-            sc->nin += fed;
-        }
-        sc->nout += no[j];
-        sc->rpar ^= 1;
+        out_lens[j] = plan[j].rs.out;
+        if (!sc->fx.any()) continue;
+        sc->fx.commit(plan[j]);
         sc->finished = final && final[j];
     }
     return FT_OK;
@@ -1950,83 +1726,73 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
 
 extern "C" ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out) {
     if (!ctx) return FT_ERR_ARG;
-    FT_TRY(rs_refuse(ctx, "ft_test_resample", sample_rate));
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, "ft_test_resample", sample_rate, 100, 0, &d));
     FT_TRY(codec_ready(ctx));
     if (!x || !y || !n_out || n < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_resample: bad argument");
     CodecState* s = ctx->codec;
     if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_resample: longer than max_frames of audio");
-    const int64_t no = ft_resampled_len(sample_rate, n);
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    const CodecState::RsTab* t = nullptr;
-    FT_TRY(rs_table(ctx, sample_rate, &t));
-    *n_out = no;
-    if (t->K == 0) {
+    FT_TRY(fx_prepare(ctx, &d));
+    *n_out = d.out_len(n);
+    Fx g;
+    if (!item_stages(s, d, n, g)) {
         memcpy(y, x, (size_t)n * sizeof(float));
         return FT_OK;
     }
-    FT_TRY(rs_alloc(ctx));
     FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    Fx g;
-    g.rs.assign(1, RsSeg{s->audio, t->w, nullptr, nullptr, nullptr, 0, 0, (int)n, (int)no, t->L, t->M, t->K, 0});
     return call_tail(ctx, &g, y, 0, "resample launch: ");
 }
 
 extern "C" ft_status ft_test_timescale(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, float* y, int64_t* n_out,
                                        int32_t* deltas, int32_t* n_frames) {
     if (!ctx) return FT_ERR_ARG;
-    FT_TRY(ts_refuse(ctx, "ft_test_timescale", speed_pct));
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, "ft_test_timescale", RS_FI, speed_pct, 0, &d));
     FT_TRY(codec_ready(ctx));
     if (!x || !y || !n_out || n < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_timescale: bad argument");
     CodecState* s = ctx->codec;
     if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_timescale: longer than max_frames of audio");
-    const TsPlan p = ts_plan(TsRate{speed_pct, 100}, 0, n, true);
+    StageChain c = d.fresh();
+    c.ts.on = true;   // the hook runs the stage at 100 percent too
+    const ChainPlan p = c.plan(n, true);
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
     FT_TRY(ts_alloc(ctx));
-    *n_out = p.out;
-    if (n_frames) *n_frames = p.k1;
+    *n_out = p.ts.out;
+    if (n_frames) *n_frames = p.ts.k1;
     FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     Fx g;
-    g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)p.out, (int)p.out, 1, 1, 0, 0});
-    g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, s->ts_delta, 0, 0, 0, 0, speed_pct, 100, (int)n, (int)p.out, 0, p.k1, 0, 0});
+    chain_segs(c, p, s->audio, 0, s->ts_delta, g);
     FT_TRY(call_tail(ctx, &g, y, 0, "time-scale launch: "));
-    if (deltas) FT_HIP(ctx, hipMemcpy(deltas, s->ts_delta, (size_t)p.k1 * sizeof(int), hipMemcpyDeviceToHost));
+    if (deltas) FT_HIP(ctx, hipMemcpy(deltas, s->ts_delta, (size_t)p.ts.k1 * sizeof(int), hipMemcpyDeviceToHost));
     return FT_OK;
 }
 
 extern "C" ft_status ft_test_pitch(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pct, int32_t cents, float* y, int64_t* n_out,
                                    float* mid, int64_t* n_mid, int32_t* deltas, int32_t* n_frames) {
     if (!ctx) return FT_ERR_ARG;
-    FT_TRY(ts_refuse(ctx, "ft_test_pitch", speed_pct));
-    FxPlan f;
-    FT_TRY(ps_refuse(ctx, "ft_test_pitch", speed_pct, cents, &f));
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, "ft_test_pitch", RS_FI, speed_pct, cents, &d));
     FT_TRY(codec_ready(ctx));
     if (!x || !y || !n_out || n < 1 || cents == 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_pitch: bad argument");
     CodecState* s = ctx->codec;
     if (n > (int64_t)ctx->cc.max_frames * s->frame_len) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_test_pitch: longer than max_frames of audio");
-    const long long no = ts_len(speed_pct, n);
-    TsPlan p;
-    p.out = n;
-    if (f.has_ts) p = ts_plan(f.ts, 0, n, true);
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    const CodecState::PsTab* pt = nullptr;
-    FT_TRY(ps_table(ctx, cents, &pt));
-    FT_TRY(ps_alloc(ctx));
-    *n_out = no;
-    if (n_mid) *n_mid = p.out;
-    if (n_frames) *n_frames = p.k1;
+    FT_TRY(fx_prepare(ctx, &d));
+    const StageChain c = d.fresh();
+    const ChainPlan p = c.plan(n, true);
+    *n_out = p.ps.out;
+    if (n_mid) *n_mid = p.ts.out;
+    if (n_frames) *n_frames = p.ts.k1;
     FT_HIP(ctx, hipMemcpyAsync(s->audio, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
     Fx g;
-    g.rs.assign(1, RsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)no, (int)no, 1, 1, 0, 0});
-    if (f.has_ts)
-        g.ts.assign(1, TsSeg{s->audio, nullptr, nullptr, nullptr, nullptr, nullptr, s->ts_delta, 0, 0, 0, 0, f.ts.num, f.ts.den,
-                             (int)n, (int)p.out, 0, p.k1, 0, 0});
-    g.ps.assign(1, PsSeg{s->audio, pt->w, nullptr, nullptr, nullptr, 0, 0, pt->S, (int)p.out, (int)no, pt->K, 0});
+    chain_segs(c, p, s->audio, 0, s->ts_delta, g);
     FT_TRY(call_tail(ctx, &g, y, 0, "pitch launch: "));
-    if (mid) FT_HIP(ctx, hipMemcpy(mid, f.has_ts ? s->ts_out : s->audio, (size_t)p.out * sizeof(float), hipMemcpyDeviceToHost));
-    if (deltas && p.k1 > 0) FT_HIP(ctx, hipMemcpy(deltas, s->ts_delta, (size_t)p.k1 * sizeof(int), hipMemcpyDeviceToHost));
+    if (mid) FT_HIP(ctx, hipMemcpy(mid, c.ts.on ? s->ts_out : s->audio, (size_t)p.ts.out * sizeof(float), hipMemcpyDeviceToHost));
+    if (deltas && p.ts.k1 > 0) FT_HIP(ctx, hipMemcpy(deltas, s->ts_delta, (size_t)p.ts.k1 * sizeof(int), hipMemcpyDeviceToHost));
     return FT_OK;
 }
 

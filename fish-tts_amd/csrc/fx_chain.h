@@ -1,0 +1,256 @@
+// Host arithmetic of the output chain behind the codec (fishtts_hip.h: sample_rate, speed_pct, pitch_cents): the time-scale
+// stage, then the pitch stage, then the resampler.  The filter designs, the rule that accepts a (speed, cents) pair, what
+// each stage can emit after so many input samples, and the bookkeeping of a stream's three stages from call to call.
+// Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
+// are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <vector>
+
+namespace ft {
+namespace chain {
+
+constexpr int RS_FI = 44100, RS_MIN_RATE = 8000, RS_MAX_RATE = 48000, RS_MAX_L = 640, RS_LDS = 2048;
+constexpr int TS_N = 1024, TS_HS = 512, TS_D = 384, TS_CARRY = TS_N + 2 * TS_D + 2 * TS_HS;
+constexpr int TS_MIN_PCT = 50, TS_MAX_PCT = 200;
+constexpr int PS_SHIFT = 20, PS_PHASES = 512, PS_MAX_CENTS = 1200;
+
+struct RsTab { int L = 1, M = 1, K = 0; float* w = nullptr; };        // one output rate: [L][K] on the device
+struct PsTab { long long S = 0; int K = 0; float* w = nullptr; };     // one cents value: [513][K] on the device
+
+// ---- resampler (RsSeg, resample_kernel): filter design on the host in float64, a Kaiser-windowed sinc at the up-sampled
+// rate L Fi cut off at 0.465 Fmin (pass band to 0.43 Fmin, stop band from 0.5 Fmin, Fmin = min(Fi, Fo)), designed for 75 dB.
+// Tap t of phase p is the prototype at j = p + (K/2 - 1 - t) L up-sampled samples from the output instant, gain L (the
+// zero-stuffed input).  Rates: integers in [8000, 48000] whose reduced L is at most 640; the codec's own rate has K = 0.
+inline double bessel_i0(double x) {
+    double sum = 1.0, term = 1.0;
+    const double q = x * x / 4.0;
+    for (int k = 1; k < 500 && term > 1e-17 * sum; ++k) {
+        term *= q / ((double)k * k);
+        sum += term;
+    }
+    return sum;
+}
+
+// Validates `rate` (an error message, or null) and gives L, M, K; fills w ([L][K] float32) when non-null.
+inline const char* rs_design(int rate, int* L, int* M, int* K, std::vector<float>* w) {
+    if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return "sample rate outside [8000, 48000]";
+    const int g = std::gcd(rate, RS_FI), l = rate / g, m = RS_FI / g;
+    if (l > RS_MAX_L) return "sample rate: rate / gcd(rate, 44100) exceeds 640";
+    *L = l;
+    *M = m;
+    *K = 0;
+    if (rate == RS_FI) return nullptr;
+    const double A = 75.0, beta = 0.1102 * (A - 8.7), fmin = std::min(rate, RS_FI);
+    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * RS_FI / fmin);
+    k += k & 1;
+    if ((255L * m + l - 1) / l + k + 1 > RS_LDS) return "sample rate: filter window exceeds the resampler's LDS stage";
+    *K = k;
+    if (!w) return nullptr;
+    const double fc = 0.465 * fmin / ((double)l * RS_FI), half = 0.5 * k * l, ib = bessel_i0(beta);
+    w->assign((size_t)l * k, 0.f);
+    for (int p = 0; p < l; ++p)
+        for (int t = 0; t < k; ++t) {
+            const double j = p + (double)(k / 2 - 1 - t) * l, r = j / half, x = M_PI * 2.0 * fc * j;
+            const double sinc = j == 0 ? 1.0 : std::sin(x) / x;
+            (*w)[(size_t)p * k + t] = (float)(2.0 * fc * l * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / ib);
+        }
+    return nullptr;
+}
+
+// Outputs available after `nin` input samples: all of them at the end of the input (final), else those whose taps all
+// lie within it (floor(n M / L) + K/2 < nin).
+inline long long rs_ready(const RsTab& t, long long nin, bool final) {
+    if (t.K == 0) return nin;
+    const long long a = final ? nin : nin - t.K / 2;
+    return a > 0 ? (a * t.L + t.M - 1) / t.M : 0;
+}
+
+// ---- time-scale stage (TsSeg, timescale_kernel; fishtts_hip.h states the algorithm)
+inline bool ts_ok(int pct) { return pct >= TS_MIN_PCT && pct <= TS_MAX_PCT; }
+// The stage runs at the rational rate num / den: pct / 100 for a speed alone, pct 2^20 / (100 S) under a pitch shift
+// (k HS num stays below 2^52 for any stream within max_frames).
+struct TsRate { long long num = 100, den = 100; };
+inline long long ts_len(TsRate r, long long n) { return (n * r.den + r.num - 1) / r.num; }
+inline long long ts_len(int pct, long long n) { return ts_len(TsRate{pct, 100}, n); }
+inline long long ts_a(TsRate r, long long k) { return k * TS_HS * r.num / r.den; }
+// Input samples frame k needs to have been seen: its search region ends at a_k + HS + D, its template (the continuation
+// of frame k - 1) at most at a_{k-1} + D + N, which lies further on below speed 1.
+inline long long ts_need(TsRate r, long long k) {
+    return std::max(ts_a(r, k), k > 0 ? ts_a(r, k - 1) + TS_HS : 0) + TS_HS + TS_D;
+}
+struct TsPlan { int k1 = 0; long long out = 0, base = 0; };
+// What a stream that has run k0 frames does once it has seen `nin` samples: frames [k0, k1), outputs below `out` final,
+// input from `base` on kept for later frames.
+inline TsPlan ts_plan(TsRate r, int k0, long long nin, bool final) {
+    TsPlan p;
+    if (final) {
+        p.out = ts_len(r, nin);
+        p.k1 = (int)((p.out + TS_HS - 1) / TS_HS) + 1;
+        p.base = nin;
+        return p;
+    }
+    p.k1 = k0;
+    while (ts_need(r, p.k1) <= nin) ++p.k1;
+    p.out = p.k1 > 0 ? (long long)(p.k1 - 1) * TS_HS : 0;
+    p.base = ts_a(r, p.k1) - TS_HS - TS_D;
+    if (p.k1 > 0) p.base = std::min(p.base, ts_a(r, p.k1 - 1) - TS_D);
+    p.base = std::max(p.base, 0LL);
+    return p;
+}
+
+// ---- pitch stage (PsSeg, pitch_kernel; fishtts_hip.h states it): the step S = llround(2^20 2^(cents / 1200)) and the
+// [513][K] table, a Kaiser-windowed sinc designed in float64 with the resampler's constants (75 dB, transition 0.07), cut off
+// at 0.465 min(1, 1 / r) cycles per input sample, r = S / 2^20; tap t of row p is the prototype at p / 512 + (K/2 - 1 - t).
+inline bool ps_design(int cents, long long* S, int* K, std::vector<float>* w) {
+    if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS) return false;
+    *S = std::llround(std::ldexp(std::exp2((double)cents / 1200.0), PS_SHIFT));
+    *K = 0;
+    if (cents == 0) return true;
+    const double A = 75.0, beta = 0.1102 * (A - 8.7), r = std::ldexp((double)*S, -PS_SHIFT);
+    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * std::max(1.0, r));
+    k += k & 1;
+    *K = k;
+    if (!w) return true;
+    const double fc = 0.465 * std::min(1.0, 1.0 / r), half = 0.5 * k, ib = bessel_i0(beta);
+    w->assign((size_t)(PS_PHASES + 1) * k, 0.f);
+    for (int p = 0; p <= PS_PHASES; ++p)
+        for (int t = 0; t < k; ++t) {
+            const double tau = (double)p / PS_PHASES + (double)(k / 2 - 1 - t), q = tau / half, x = M_PI * 2.0 * fc * tau;
+            const double sinc = tau == 0 ? 1.0 : std::sin(x) / x;
+            (*w)[(size_t)p * k + t] = (float)(2.0 * fc * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - q * q))) / ib);
+        }
+    return true;
+}
+
+// The stages in front of the resampler for (speed_pct, cents): the time-scale stage's rate, absent at rate 1.  Accepted:
+// cents in [-1200, 1200] and an effective rate speed_pct 2^20 / (100 S) in [0.5, 2].
+struct FxPlan { TsRate ts; bool has_ts = false; long long S = 0; };
+inline bool fx_plan(int pct, int cents, FxPlan* out) {
+    FxPlan f;
+    int k;
+    if (!ts_ok(pct) || !ps_design(cents, &f.S, &k, nullptr)) return false;
+    f.ts = TsRate{(long long)pct << PS_SHIFT, 100 * f.S};
+    if (50 * f.S > f.ts.num || f.ts.num > 200 * f.S) return false;
+    f.has_ts = f.ts.num != f.ts.den;
+    if (cents == 0) f.ts = TsRate{pct, 100};   // the speed alone, as it always ran
+    if (out) *out = f;
+    return true;
+}
+
+// Outputs available after `nin` input samples: those whose taps all lie within them ((n S >> 20) + K/2 < nin); at the end of
+// the input (final) all `total` of them.
+inline long long ps_ready(const PsTab& t, long long nin, bool final, long long total) {
+    if (final) return total;
+    const long long a = nin - t.K / 2;
+    return a > 0 ? ((a << PS_SHIFT) + t.S - 1) / t.S : 0;
+}
+
+// ---- the three stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;
+// plan() says how many (nothing changes), the caller builds the stage's segment from the record and the plan, and commit()
+// advances the record once the call went through.  An absent stage passes its input on (out = in); its counters still run,
+// the parity of its carry pair too.  A record with null carries and zero counters is a waveform decoded from zero state.
+struct StagePlan { long long in = 0, out = 0, base = 0; int k1 = 0; };   // base, k1: the time-scale stage's (TsPlan)
+
+struct TsStage {
+    bool on = false;
+    TsRate rate;
+    float *carry[2] = {nullptr, nullptr}, *state[2] = {nullptr, nullptr};   // input a later frame still reads; state after the last frame
+    int par = 0, k = 0;                        // which copy is current; frames run so far
+    long long nin = 0, base = 0, nout = 0;     // input samples seen, first one carried, samples emitted
+    StagePlan plan(long long n, bool final) const {
+        if (!on) return StagePlan{n, n, 0, 0};
+        const TsPlan p = ts_plan(rate, k, nin + n, final);
+        return StagePlan{n, p.out - nout, p.base, p.k1};
+    }
+    long long held(const StagePlan& p) const { return on ? nin + p.in - p.base : 0; }   // carried after the call: at most TS_CARRY
+    void commit(const StagePlan& p) {
+        if (!on) return;
+        nin += p.in; nout += p.out; base = p.base; k = p.k1; par ^= 1;
+    }
+};
+
+struct PsStage {
+    const PsTab* tab = nullptr;                // null: absent
+    float* carry[2] = {nullptr, nullptr};      // its last K input samples
+    int par = 0;
+    long long nin = 0, nout = 0;
+    // `total`: the outputs the stage gives in the end for the codec samples seen so far (it restores the caller's length)
+    StagePlan plan(long long n, bool final, long long total) const {
+        return StagePlan{n, tab ? ps_ready(*tab, nin + n, final, total) - nout : n, 0, 0};
+    }
+    void commit(const StagePlan& p) {
+        if (!tab) return;
+        nin += p.in; nout += p.out; par ^= 1;
+    }
+};
+
+struct RsStage {
+    const RsTab* tab = nullptr;                // null: absent (the codec's own rate)
+    float* carry[2] = {nullptr, nullptr};      // its last K input samples
+    int par = 0;
+    long long nin = 0, nout = 0;
+    StagePlan plan(long long n, bool final) const { return StagePlan{n, tab ? rs_ready(*tab, nin + n, final) - nout : n, 0, 0}; }
+    void commit(const StagePlan& p) { nin += p.in; nout += p.out; par ^= 1; }
+};
+
+struct ChainPlan { StagePlan ts, ps, rs; };
+struct StageChain {
+    TsStage ts;
+    PsStage ps;
+    RsStage rs;
+    int speed = 100;          // the caller's speed_pct: with the codec samples seen it fixes the pitch stage's output length
+    long long seen = 0;       // codec samples taken so far
+    bool any() const { return ts.on || ps.tab || rs.tab; }
+    ChainPlan plan(long long n, bool final) const {
+        ChainPlan p;
+        p.ts = ts.plan(n, final);
+        p.ps = ps.plan(p.ts.out, final, ts_len(speed, seen + n));
+        p.rs = rs.plan(p.ps.out, final);
+        return p;
+    }
+    void commit(const ChainPlan& p) {
+        seen += p.ts.in;
+        ts.commit(p.ts);
+        ps.commit(p.ps);
+        rs.commit(p.rs);
+    }
+};
+
+// A call's chain, resolved: which stages exist and at what rate.  make() judges the three values as every entry point does
+// (an error message, or null): the rate, then the speed, then the cents, then the pair.  The device tables are filled in by
+// the caller that holds the context (codec.hip: fx_prepare).
+struct FxDesc {
+    int rate = RS_FI, pct = 100, cents = 0;
+    int L = 1, M = 1, K = 0;          // the resampler's (K = 0: the codec's own rate, no stage)
+    FxPlan f;                         // f.has_ts: the time-scale stage exists (under a pitch shift it may not)
+    const RsTab* rs = nullptr;        // set by the caller when K > 0
+    const PsTab* ps = nullptr;        // set by the caller when cents != 0
+    enum Bad { OK = 0, RATE, SPEED, CENTS, PAIR };
+    Bad make(int rate_, int pct_, int cents_, const char** why) {
+        rate = rate_; pct = pct_; cents = cents_;
+        if ((*why = rs_design(rate, &L, &M, &K, nullptr))) return RATE;
+        if (!ts_ok(pct)) return SPEED;
+        if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS) return CENTS;
+        return fx_plan(pct, cents, &f) ? OK : PAIR;
+    }
+    bool any() const { return K > 0 || f.has_ts || cents != 0; }
+    // a waveform from zero state through this chain
+    StageChain fresh() const {
+        StageChain c;
+        c.ts.on = f.has_ts;
+        c.ts.rate = f.ts;
+        c.ps.tab = ps;
+        c.rs.tab = K > 0 ? rs : nullptr;
+        c.speed = pct;
+        return c;
+    }
+    // n_in codec samples -> after the time-scale and pitch stages -> after the resampler (ft_resampled_len of ft_timescaled_len)
+    long long ts_out(long long n_in) const { return ts_len(pct, n_in); }
+    long long out_len(long long n_in) const { return (ts_out(n_in) * L + M - 1) / M; }
+};
+
+}  // namespace chain
+}  // namespace ft

@@ -43,7 +43,7 @@ from typing import TYPE_CHECKING, Callable, Iterator, List, Optional, Sequence, 
 
 import numpy as np
 
-from .batch_stream import ChunkCutter, pcm16
+from .batch_stream import ChunkCutter, checked_fx, pcm16
 
 if TYPE_CHECKING:
     from .batch import Utterance
@@ -59,14 +59,6 @@ class _Failed:
 
 
 _END = object()
-
-
-def _output_rate(sample_rate: Optional[int]) -> Optional[int]:
-    """codec_engine.output_rate: None for the codec's own rate, ValueError for an unsupported one."""
-    if sample_rate is None:
-        return None
-    from .codec_engine import output_rate
-    return output_rate(sample_rate)
 
 
 def compaction_moves(active: Sequence[int]) -> List[Tuple[int, int]]:
@@ -88,37 +80,14 @@ def lockstep_width(n: int, max_batch: int, wide_from: int) -> int:
     return wide_from if 2 <= n < wide_from <= max_batch else n
 
 
-def _output_speed(speed: Optional[float]) -> Optional[float]:
-    """codec_engine.output_speed as a factor: None for the model's own pace, ValueError for an unsupported one."""
-    if speed is None:
-        return None
-    from .codec_engine import output_speed
-    pct = output_speed(speed)
-    return None if pct is None else pct / 100.0
-
-
-def _output_pitch(pitch: Optional[float], speed: Optional[float] = None) -> Optional[float]:
-    """codec_engine.output_fx's pitch in semitones: None for the model's own pitch, ValueError for an unsupported one or an
-    unsupported combination with `speed`."""
-    if pitch is None:
-        return None
-    from .codec_engine import output_fx
-    cents = output_fx(speed, pitch)[1]
-    return None if cents is None else cents / 100.0
-
-
 class _Request:
     """One synthesize / synthesize_stream call: its utterance, chunking and output queue."""
 
     def __init__(self, utt: Utterance, n_prefix: int, mode: str, chunk_tokens: int, min_first_chunk: int,
-                 rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None):
+                 fx=None):
         self.utt, self.n_prefix, self.mode = utt, n_prefix, mode          # mode: "wav" | "seamless" | "chunks" | "codes"
         self.cache = None             # a PrefixCache of the caller's own for this request's voice (None: the server's)
-        self.rate = rate              # output sample rate (None: the codec's own)
-        self.speed = speed            # speaking rate (None: the model's own pace)
-        self.pitch = pitch            # pitch shift in semitones (None: the model's own pitch)
-        self.fx = rate is not None or speed is not None or pitch is not None      # an output stage holds back a tail
-        self.skw = {k: v for k, v in (("speed", speed), ("pitch", pitch)) if v is not None}
+        self.fx = checked_fx(fx)      # the checked output stages (codec_engine.OutputFx; falsy: none, no tail held back)
         self.cut = None if mode in ("wav", "codes") else ChunkCutter(chunk_tokens, min_first_chunk, hold_back=mode == "seamless")
         self.out: "queue.Queue" = queue.Queue()
         self.cancelled = False        # the caller went away (or close(cancel=True))
@@ -133,7 +102,7 @@ class BatchServer:
     """Continuous batching of concurrent synthesize / synthesize_stream calls on one AR engine (module docstring); a
     context manager, obtained from FishTTS.serve().  `prepare(text, references, temperature, top_p, repetition_penalty,
     max_tokens, seed) -> (Utterance, n_prefix)` builds and checks a request on the caller's thread; `decode_wav(codes)` /
-    `decode_pcm(codes)` give WAV bytes / zero-state PCM of codes; `prefix_cache` holds the voices' K/V prefixes;
+    `decode_pcm(codes)` give WAV bytes / zero-state PCM of codes (with output stages: `fx=` as well); `prefix_cache` holds the voices' K/V prefixes;
     `on_close(server)` runs once, after both threads have stopped."""
 
     def __init__(self, engine, codec, burst: int = 8, *, prepare: Optional[Callable] = None,
@@ -180,52 +149,52 @@ class BatchServer:
     def synthesize(self, text: str, references=None, temperature: float = 0.7, top_p: float = 0.8,
                    repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
                    sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                   pitch: Optional[float] = None) -> bytes:
+                   pitch: Optional[float] = None, fx=None) -> bytes:
         """Text -> WAV bytes: FishTTS.synthesize's result for seed 0 (draws with `seed`).  Safe from any number of threads;
         `references=None` means the instance's set_references voices; `sample_rate`, `speed` and `pitch` as
-        FishTTS.synthesize_at (an unsupported one raises ValueError here, before anything is queued)."""
-        rate, spd, pit = _output_rate(sample_rate), _output_speed(speed), _output_pitch(pitch, speed)
+        FishTTS.synthesize_at (an unsupported one raises ValueError here, before anything is queued), or `fx`: the three
+        already checked (codec_engine.OutputFx)."""
+        fx = checked_fx(fx, sample_rate, speed, pitch)
         utt, n_prefix = self._prepare(text, references, temperature, top_p, repetition_penalty, max_tokens, seed)
-        item = self.submit(utt, n_prefix, sample_rate=rate, speed=spd, pitch=pit).out.get()
+        item = self.submit(utt, n_prefix, fx=fx).out.get()
         if isinstance(item, _Failed):
             raise item.error
         return item
 
     def synthesize_stream(self, text: str, references=None, chunk_tokens: int = 20, min_first_chunk: int = 10,
                           seamless: bool = False, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                          pitch: Optional[float] = None, **sampling) -> Iterator[bytes]:
+                          pitch: Optional[float] = None, fx=None, **sampling) -> Iterator[bytes]:
         """Yields int16 PCM chunks as FishTTS.synthesize_stream does: seamless=False (the reference's default) every chunk
         decoded from zero state; seamless=True one stateful CodecStream per request, the chunks cut as
         synthesize_batch_stream cuts them.  `sampling`: temperature, top_p, repetition_penalty, max_tokens, seed.  The
         prompt is built and checked here (a too-long one raises ValueError now); the request is queued at the first
         next(), so a generator dropped before it never runs, and abandoning it later cancels the request (its slot is
-        freed at the next burst boundary).  `sample_rate`, `speed` and `pitch` as FishTTS.synthesize_stream (checked here)."""
+        freed at the next burst boundary).  `sample_rate`, `speed` and `pitch` as FishTTS.synthesize_stream (checked here), or
+        `fx`: the three already checked."""
         if chunk_tokens < 1 or min_first_chunk < 1:
             raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-        rate, spd, pit = _output_rate(sample_rate), _output_speed(speed), _output_pitch(pitch, speed)
+        fx = checked_fx(fx, sample_rate, speed, pitch)
         utt, n_prefix = self._prepare(text, references, sampling.get("temperature", 0.7), sampling.get("top_p", 0.8),
                                       sampling.get("repetition_penalty", 1.1), sampling.get("max_tokens", 2048),
                                       sampling.get("seed", 0))
-        return self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, rate, spd, pit)
+        return self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, fx)
 
     def _stream(self, utt: Utterance, n_prefix: int, seamless: bool, chunk_tokens: int,
-                min_first_chunk: int, rate: Optional[int] = None, speed: Optional[float] = None,
-                pitch: Optional[float] = None) -> Iterator[bytes]:
+                min_first_chunk: int, fx=None) -> Iterator[bytes]:
         yield from self._chunks(self.submit(utt, n_prefix, stream=True, seamless=seamless, chunk_tokens=chunk_tokens,
-                                            min_first_chunk=min_first_chunk, sample_rate=rate, speed=speed, pitch=pitch))
+                                            min_first_chunk=min_first_chunk, fx=fx))
 
     def submit(self, utt: Utterance, n_prefix: int = 0, stream: bool = False, seamless: bool = False,
                chunk_tokens: int = 20, min_first_chunk: int = 10, sample_rate: Optional[int] = None,
                speed: Optional[float] = None, pitch: Optional[float] = None, codes: bool = False,
-               voice_cache=None) -> _Request:
+               voice_cache=None, fx=None) -> _Request:
         """Queues one prepared utterance (the layer under synthesize / synthesize_stream); its output arrives on
         `.out`.  `codes`: the output is the utterance's codes (Utterance.codes()), no audio; `voice_cache`: the PrefixCache
         its voice prefix lives in instead of the server's.  Raises ServerClosed once the server is closing or has failed."""
         if self._codec is None:
             raise RuntimeError("Vocoder not loaded")
         mode = "codes" if codes else ("seamless" if seamless else "chunks") if stream else "wav"
-        req = _Request(utt, n_prefix, mode, chunk_tokens,
-                       min_first_chunk, _output_rate(sample_rate), _output_speed(speed), _output_pitch(pitch, speed))
+        req = _Request(utt, n_prefix, mode, chunk_tokens, min_first_chunk, checked_fx(fx, sample_rate, speed, pitch))
         req.cache = voice_cache
         with self._lock:
             if self._error is not None:
@@ -549,24 +518,22 @@ class BatchServer:
                                     if r.fx:
                                         r.out.put(pcm16(r.stream.finish()))
                                     r.stream.close()
-                                r.stream = self._codec.stream() if not r.fx else self._codec.stream(r.rate, **r.skw)
+                                r.stream = self._codec.stream(**r.fx.kw)
                         streams = [r.stream for r in seam]
-                        if not any(r.fx for r in seam):
-                            audio = self._codec.decode_streams(streams, seam_chunks)
-                        else:
-                            audio = self._codec.decode_streams(streams, seam_chunks,
-                                                               [f and r.fx for r, f in zip(seam, seam_final)])
+                        # (final flags only where a stream has a stage: the others have no tail and stay on the plain call)
+                        final = [[bool(f and r.fx) for r, f in zip(seam, seam_final)]] if any(r.fx for r in seam) else []
+                        audio = self._codec.decode_streams(streams, seam_chunks, *final)
                         for r, a in zip(seam, audio):
-                            if len(a) or not r.skw:     # (nothing completed in the time-scale or pitch stage: nothing to hand out)
+                            if len(a) or r.fx.emits_empty:     # (nothing completed in the time-scale or pitch stage: nothing to hand out)
                                 r.out.put(pcm16(a))
                     for r, c in zip(plain, plain_chunks):
-                        r.out.put(self._decode_pcm(c) if not r.fx else self._decode_pcm(c, r.rate, **r.skw))
+                        r.out.put(self._decode_pcm(c, **r.fx.kw))
                     for r in wavs:
                         codes = r.utt.codes()
                         if not codes.shape[1]:
                             self._last_out(r, _Failed(RuntimeError("No audio generated")))
                         else:
-                            self._last_out(r, self._decode_wav(codes) if not r.fx else self._decode_wav(codes, r.rate, **r.skw))
+                            self._last_out(r, self._decode_wav(codes, **r.fx.kw))
         except BaseException as e:  # noqa: BLE001
             self._fail(e)
         finally:

@@ -260,11 +260,11 @@ class FishTTS:
         work - codec_engine.output_pitch, output_fx)."""
         from .generation import generate_long
         from .serve import ServerClosed
-        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed, pitch)
+        fx = _output_fx(sample_rate, speed, pitch)
         srv = getattr(self, "_server", None)
         if srv is not None:
             try:
-                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens, **fx)
+                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens, fx=fx)
             except ServerClosed:
                 pass                          # closed meanwhile: served here, once the server has let go of _gen_lock
         prompt_text, prompt_tokens = self._get_prompt_data(references)
@@ -280,9 +280,7 @@ class FishTTS:
                     break
         if not codes_list:
             raise RuntimeError("No audio generated")
-        if not fx:
-            return self._decode_to_wav(np.concatenate(codes_list, axis=1))
-        return self._decode_to_wav(np.concatenate(codes_list, axis=1), rate, fx.get("speed"), **_pkw(fx))
+        return self._decode_to_wav(np.concatenate(codes_list, axis=1), fx)
 
     def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
                           repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]],
@@ -337,7 +335,7 @@ class FishTTS:
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
         semantics as synthesize(), `sample_rate`, `speed` and `pitch` (as synthesize_at) included."""
         from .batch import run_batch, run_batch_streams
-        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed, pitch)
+        fx = _output_fx(sample_rate, speed, pitch)
         self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
@@ -351,7 +349,7 @@ class FishTTS:
             codes = u.codes()
             if codes.shape[1] == 0:
                 raise RuntimeError("No audio generated")
-            out.append(self._decode_to_wav(codes) if not fx else self._decode_to_wav(codes, rate, fx.get("speed"), **_pkw(fx)))
+            out.append(self._decode_to_wav(codes, fx))
         return out
 
     def synthesize_batch_stream(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
@@ -377,7 +375,7 @@ class FishTTS:
         the two); the tail travels in the same way."""
         from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
-        fx = _fx(sample_rate, speed, pitch)
+        fx = _output_fx(sample_rate, speed, pitch)
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
@@ -393,19 +391,19 @@ class FishTTS:
                     run_batch(self._engine, utts, on_frames=on_frames, on_done=on_done)
 
         return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
-                                 min_first_chunk=min_first_chunk, **fx)
+                                 min_first_chunk=min_first_chunk, fx=fx)
 
     # ------------------------------------------------------------------ long texts (extension)
     def _long_plan(self, text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch):
-        """Every check of a long-text call, before any device work: (texts, output rate, output keywords, join parameters,
-        gaps).  ValueError for a bad value."""
+        """Every check of a long-text call, before any device work: (texts, output stages, join parameters, gaps).
+        ValueError for a bad value."""
         from .longform import join_params, split_text
-        rate, fx = output_rate(sample_rate), _fx(sample_rate, speed, pitch)
-        jp, gap, pgap = join_params(rate, pause, paragraph_pause, silence_db)
+        fx = _output_fx(sample_rate, speed, pitch)
+        jp, gap, pgap = join_params(fx.rate, pause, paragraph_pause, silence_db)
         segs = split_text(text, max_chars, min_chars)
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
-        return [s.text for s in segs], rate, fx, tuple(jp), [pgap if s.paragraph else gap for s in segs]
+        return [s.text for s in segs], fx, tuple(jp), [pgap if s.paragraph else gap for s in segs]
 
     def _long_generate(self, texts, references, sampling, seed: int, emit, stopped) -> None:
         """The codes of every segment, emit(i, codes) as each is complete (from any thread).  Segment i draws with seed + i;
@@ -492,8 +490,8 @@ class FishTTS:
         `speed`, `pitch` as synthesize_at, applied per segment before the join.  While a BatchServer is open the segments
         join its batch.  ValueError before any device work: pause / paragraph_pause outside [0, 5] s, silence_db outside
         [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch."""
-        texts, rate, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
-                                                    sample_rate, speed, pitch)
+        texts, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
+                                              sample_rate, speed, pitch)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         codes = self._long_codes_served(texts, references, sampling, seed)
         lock = None
@@ -505,12 +503,12 @@ class FishTTS:
             codes, lock = codes
         if lock is not None:
             with lock:
-                audio, _ = self._vocoder.decode_join(codes, rate, fx.get("speed"), fx.get("pitch"), jp, gaps)
+                audio, _ = self._vocoder.decode_join(codes, params=jp, gaps=gaps, fx=fx)
         else:
-            audio, _ = self._vocoder.decode_join(codes, rate, fx.get("speed"), fx.get("pitch"), jp, gaps)
+            audio, _ = self._vocoder.decode_join(codes, params=jp, gaps=gaps, fx=fx)
         if not len(audio):
             raise RuntimeError("No audio generated")
-        return self._to_wav_bytes(audio, self.sample_rate if rate is None else rate)
+        return self._to_wav_bytes(audio, fx.wav_rate)
 
     def _long_codes_served(self, texts, references, sampling, seed):
         """([codes of every segment], the server's codec lock) from an open BatchServer; None: no server (or it closed before
@@ -539,12 +537,12 @@ class FishTTS:
         chunks concatenate to synthesize_long's PCM byte for byte.  No empty chunk is yielded.  The arguments are checked
         here, at the call; generation holds _gen_lock on its own thread and stops within one burst when the generator is
         abandoned."""
-        texts, rate, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
-                                                    sample_rate, speed, pitch)
+        texts, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
+                                              sample_rate, speed, pitch)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        return self._long_chunks(texts, references, sampling, seed, rate, fx, jp, gaps)
+        return self._long_chunks(texts, references, sampling, seed, fx, jp, gaps)
 
-    def _long_chunks(self, texts, references, sampling, seed, rate, fx, jp, gaps) -> Iterator[bytes]:
+    def _long_chunks(self, texts, references, sampling, seed, fx, jp, gaps) -> Iterator[bytes]:
         from .longform import ready_prefixes
         from .serve import ServerClosed
         n = len(texts)
@@ -578,8 +576,7 @@ class FishTTS:
         started = False
         try:
             for first, group in ready_prefixes(q, n):
-                kw = dict(sample_rate=rate, speed=fx.get("speed"), pitch=fx.get("pitch"), params=jp,
-                          gaps=gaps[first:first + len(group)], started=started)
+                kw = dict(params=jp, gaps=gaps[first:first + len(group)], started=started, fx=fx)
                 if lock is not None:
                     with lock:
                         audio, _ = self._vocoder.decode_join(group, **kw)
@@ -628,12 +625,10 @@ class FishTTS:
         and the resampler), so its chunks concatenate to the shifted waveform of one streamed decode."""
         from .generation import generate_long
         from .serve import ServerClosed
-        rate = output_rate(kwargs.get("sample_rate"))
-        fx = _fx(kwargs.get("sample_rate"), kwargs.get("speed"), kwargs.get("pitch"))
-        spd, pkw = fx.get("speed"), _pkw(fx)
+        fx = _output_fx(kwargs.pop("sample_rate", None), kwargs.pop("speed", None), kwargs.pop("pitch", None))
         srv = getattr(self, "_server", None)
         if srv is not None:
-            chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, **kwargs)
+            chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, fx=fx, **kwargs)
             try:
                 try:
                     first = next(chunks)      # the request is queued here
@@ -660,22 +655,22 @@ class FishTTS:
                 if seamless:
                     if self._vocoder is None:
                         raise RuntimeError("Vocoder not loaded")
-                    stream = self._vocoder.stream(rate, spd, **pkw)  # carried state: K/V of the last 127 frames, conv tails
+                    stream = self._vocoder.stream(fx=fx)  # carried state: K/V of the last 127 frames, conv tails
                 while True:
                     codes = codes_queue.get()
                     if codes is None:
                         break
                     if stream is None:
-                        audio_queue.put(self._decode_to_pcm(codes) if not fx else self._decode_to_pcm(codes, rate, spd, **pkw))
+                        audio_queue.put(self._decode_to_pcm(codes, **fx.kw))
                     else:
                         codes = np.asarray(codes)
                         if stream.frames + codes.shape[1] > self._vocoder.max_frames:   # the rotation table ends here
                             if fx:                              # the old stream's output-stage tail first
                                 audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())
                             stream.close()
-                            stream = self._vocoder.stream(rate, spd, **pkw)
+                            stream = self._vocoder.stream(fx=fx)
                         audio = stream.decode(codes)
-                        if len(audio) or (spd is None and not pkw):   # (an output stage completed nothing: nothing to hand out)
+                        if len(audio) or fx.emits_empty:   # (a time-scale or pitch stage completed nothing: nothing to hand out)
                             audio_queue.put((audio * 32767).astype(np.int16).tobytes())
                 if stream is not None and fx:
                     audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())   # the output stages' tail
@@ -829,40 +824,21 @@ class FishTTS:
         return Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seed), n_prefix
 
     # ------------------------------------------------------------------ codes -> audio (synthesizer.py:586-648)
-    def _decode_to_wav(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                       pitch: Optional[float] = None) -> bytes:
-        if pitch is not None:
-            return self._to_wav_bytes(self._decode_codes(codes, sample_rate, speed, pitch), self.sample_rate if sample_rate is None else sample_rate)
-        if sample_rate is None and speed is None:
-            return self._to_wav_bytes(self._decode_codes(codes))
-        if speed is None:
-            return self._to_wav_bytes(self._decode_codes(codes, sample_rate), sample_rate)
-        return self._to_wav_bytes(self._decode_codes(codes, sample_rate, speed), self.sample_rate if sample_rate is None else sample_rate)
+    def _decode_to_wav(self, codes: np.ndarray, fx=None) -> bytes:
+        return self._to_wav_bytes(self._decode_codes(codes, fx), self.sample_rate if fx is None else fx.wav_rate)
 
-    def _decode_to_pcm(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                       pitch: Optional[float] = None) -> bytes:
-        if pitch is not None:
-            audio = self._decode_codes(codes, sample_rate, speed, pitch)
-        elif speed is not None:
-            audio = self._decode_codes(codes, sample_rate, speed)
-        else:
-            audio = self._decode_codes(codes) if sample_rate is None else self._decode_codes(codes, sample_rate)
-        return (audio * 32767).astype(np.int16).tobytes()  # no clip on the PCM path (synthesizer.py:594)
+    def _decode_to_pcm(self, codes: np.ndarray, fx=None) -> bytes:
+        return (self._decode_codes(codes, fx) * 32767).astype(np.int16).tobytes()  # no clip on the PCM path (synthesizer.py:594)
 
-    def _decode_codes(self, codes: np.ndarray, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                      pitch: Optional[float] = None) -> np.ndarray:
+    def _decode_codes(self, codes: np.ndarray, fx=None) -> np.ndarray:
+        """codes (n_codebooks+1, T) -> the waveform through the output stages `fx` (a checked codec_engine.OutputFx; None:
+        none)."""
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
-        if pitch is not None:
-            return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate, speed=speed, pitch=pitch), axis=0)
-        if speed is not None:
-            return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate, speed=speed), axis=0)
-        if sample_rate is None:
-            return np.squeeze(self._vocoder.decode(codes))
-        return np.squeeze(self._vocoder.decode(codes, sample_rate=sample_rate), axis=0)
+        return np.squeeze(self._vocoder.decode(codes, fx=fx), axis=0)
 
     @staticmethod
     def _to_wav_bytes(audio: np.ndarray, sample_rate: int = 44100) -> bytes:
@@ -889,45 +865,10 @@ class _LongStopped(Exception):
     """The consumer of synthesize_long_stream went away: generation stops at its next block of frames."""
 
 
-def output_rate(sample_rate: Optional[int]) -> Optional[int]:
-    """codec_engine.output_rate (imported when first needed, as the engines are)."""
-    from .codec_engine import output_rate as check
-    return check(sample_rate)
-
-
-def output_speed(speed: Optional[float]) -> Optional[float]:
-    """codec_engine.output_speed as a factor: None for the model's own pace, else the accepted percentage / 100."""
-    from .codec_engine import output_speed as check
-    pct = check(speed)
-    return None if pct is None else pct / 100.0
-
-
-def output_pitch(pitch: Optional[float], speed: Optional[float] = None) -> Optional[float]:
-    """codec_engine.output_fx's pitch in semitones: None for the model's own pitch, else the accepted cents / 100; the
-    combination with `speed` is checked as well (speed / 2^(pitch / 12) in [0.5, 2])."""
-    from .codec_engine import output_fx as check
-    cents = check(speed, pitch)[1]
-    return None if cents is None else cents / 100.0
-
-
-def _fx(sample_rate, speed, pitch=None) -> dict:
-    """The checked output keywords of a call, absent ones left out: {} is the path without output stages."""
-    rate, spd = output_rate(sample_rate), output_speed(speed)
-    pit = output_pitch(pitch, speed)
-    fx = {}
-    if rate is not None:
-        fx["sample_rate"] = rate
-    if spd is not None:
-        fx["speed"] = spd
-    if pit is not None:
-        fx["pitch"] = pit
-    return fx
-
-
-def _pkw(fx: dict) -> dict:
-    """The pitch keyword of a checked call for the decode helpers and streams: absent without a pitch shift, so those
-    calls stay what they were."""
-    return {"pitch": fx["pitch"]} if "pitch" in fx else {}
+def _output_fx(sample_rate, speed, pitch):
+    """codec_engine.OutputFx.of: the checked output stages of a call (imported when first needed, as the engines are)."""
+    from .codec_engine import OutputFx
+    return OutputFx.of(sample_rate, speed, pitch)
 
 
 def get_instance(model_dir=None, device: Literal["cpu", "cuda"] = "cuda",

@@ -227,7 +227,8 @@ ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream
  * below speed 1; after frame k the outputs below k HS are final and are emitted.  final runs the remaining frames with
  * zeros past the end; the stream's outputs then number n_out exactly.  A stream carries on the device the input samples a
  * later frame can still read (at most N + 2 D + 2 HS), s_{k-1} and the HS half-overlapped outputs, two copies each (a call
- * reads one and writes the other); k and the sample counters live on the host.  With a sample rate as well, the
+ * reads one and writes the other); k and the sample counters live on the host (csrc/fx_chain.h holds the host arithmetic
+ * of all three output stages).  With a sample rate as well, the
  * resampler runs over the time-scaled samples (its input count is theirs).  The first time-scaled call allocates the
  * stage's buffers for speed 0.5: 2 max_frames frame_len float32 (plus 64 streams' hold-back), and a resampler output
  * buffer for that many input samples. */

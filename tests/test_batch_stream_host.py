@@ -25,10 +25,10 @@ class FakeCodec:
     def __init__(self, delay=0.0, fail_at=None):
         self.calls, self.opened, self.delay, self.fail_at = [], [], delay, fail_at
 
-    def stream(self):
+    def stream(self, fx=None):
         return FakeStream(self)
 
-    def decode_streams(self, streams, chunks):
+    def decode_streams(self, streams, chunks, final=None):
         assert len(set(map(id, streams))) == len(streams)
         if self.fail_at is not None and len(self.calls) == self.fail_at:
             raise RuntimeError("codec failed")

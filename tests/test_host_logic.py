@@ -289,7 +289,7 @@ def test_stream_does_not_deadlock_when_ar_outruns_codec(monkeypatch):
     synth._prefix_cache = None
     synth._prefill_cache, synth._prefill_lock, synth._gen_lock = _PrefillCache(), threading.Lock(), threading.Lock()
 
-    def slow_decode(codes):
+    def slow_decode(codes, fx=None):
         time.sleep(0.02)
         return np.asarray(codes)[0].astype(np.int16).tobytes()   # 2 bytes per frame: the frame indices of the chunk
     synth._decode_to_pcm = slow_decode
@@ -326,7 +326,7 @@ def test_stream_raises_and_frees_the_lock_when_the_decoder_worker_dies(monkeypat
     synth._prefill_cache, synth._prefill_lock, synth._gen_lock = _PrefillCache(), threading.Lock(), threading.Lock()
     calls = []
 
-    def failing_decode(codes):
+    def failing_decode(codes, fx=None):
         calls.append(1)
         if len(calls) == 2:
             raise RuntimeError("codec exploded")

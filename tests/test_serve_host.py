@@ -44,11 +44,11 @@ def _prepare(text, references, temperature, top_p, repetition_penalty, max_token
     return _fake_utt(uid, max_tokens, eos_at=EOS.get(uid, 0)), 0
 
 
-def _wav(codes):
+def _wav(codes, fx=None):
     return np.ascontiguousarray(codes[0], dtype=np.int32).tobytes()
 
 
-def _plain(codes):
+def _plain(codes, fx=None):
     return b"P" + np.ascontiguousarray(codes[0], dtype=np.int32).tobytes()
 
 
@@ -272,7 +272,7 @@ def test_a_codec_error_reaches_every_waiter(where):
     """The codec worker fails (a WAV decode, or the batched stream decode): every caller gets the error, none hangs."""
     from fish_tts_amd.serve import BatchServer
 
-    def bad_wav(codes):
+    def bad_wav(codes, fx=None):
         raise RuntimeError("codec failed")
     gate = threading.Event()
     eng = MovingEngine(gate=gate)
