@@ -125,6 +125,13 @@ SYMBOLS = {
     "ft_test_pf_norm": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "ft_test_pf_attn": (C.c_int32, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
                                     C.POINTER(C.c_int32)]),
+    "ft_test_gemv": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.c_int32,
+                                 C.c_int32, C.c_int32, _P, _P]),
+    "ft_test_decode_attn": (C.c_int32, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P, _P, _P,
+                                        _P]),
+    "ft_test_fast_attn": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "ft_test_embed": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int64,
+                                  C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
 }
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",

@@ -382,6 +382,106 @@ class ARHipEngine:
                                              ptr(kn), ptr(kc), ptr(vc), ptr(y), ptr(q), ptr(tail), C.byref(path)), "ft_test_pf_attn")
         return y, q, kc, vc, tail, path.value
 
+    def _wt(self):
+        """numpy dtype of the patterns the context's weights travel as: uint16 (bf16 / fp16) or float32."""
+        return np.float32 if self.precision in ("fp32", "f32") else np.uint16
+
+    def test_gemv(self, pro: int, epi: int, x: np.ndarray, W: np.ndarray, gain=None, bias=None, resid=None, alias: bool = False,
+                  nt: bool = True, ldx=None, ldo=None):
+        """Test hook (ft_test_gemv): one product of a 1..4 row decode launch through the product's dispatcher.  x (M, K) f32;
+        W (N, K), gain (K,), bias (N,): patterns of the model's type (float32 in fp32); resid (M, N) f32.  Returns (out (M, oc)
+        f32, pad (M, ldo - oc) uint32, tail (ldo,) uint32: the row behind, (MB, R, NT))."""
+        wt = self._wt()
+        c = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        x, W, gain, bias, resid = c(x, np.float32), c(W, wt), c(gain, wt), c(bias, wt), c(resid, np.float32)
+        (M, K), N = x.shape, W.shape[0]
+        oc = N // 2 if epi == 2 else N
+        ldx = K if ldx is None else ldx
+        ldo = oc + (-oc) % 4 if ldo is None else ldo
+        out = np.zeros((M + 1, max(ldo, 1)), dtype=np.float32)
+        ids = np.zeros(3, dtype=np.int32)
+        self._check(self.lib.ft_test_gemv(self._h, pro, epi, M, N, K, ptr(x), ldx, ptr(W), ptr(gain), ptr(bias), ptr(resid),
+                                          1 if alias else 0, 1 if nt else 0, ldo, ptr(out), ptr(ids)), "ft_test_gemv")
+        return out[:M, :oc].copy(), out[:M, oc:].view(np.uint32).copy(), out[M].view(np.uint32).copy(), tuple(int(i) for i in ids)
+
+    def test_decode_attn(self, qkv: np.ndarray, pos: np.ndarray, qn, kn, kc: np.ndarray, vc: np.ndarray, wo: np.ndarray, bo,
+                         resid: np.ndarray, pos_off: int = 0):
+        """Test hook (ft_test_decode_attn): decode attention and the Wo product of 1..4 rows.  Patterns of the model's type
+        (float32 in fp32) for qn, kn, kc, vc (M, Hkv, n_slots, hd), wo (dim, H hd), bo.  Returns (nsplit, y (M, y_ld) f32,
+        part_o (M, H, nsplit, hd), part_ml (M, H, nsplit, 2) or None with one split, x_out (M, dim), kc, vc after the launch)."""
+        wt = self._wt()
+        c = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        a = self.args
+        qkv, pos, resid = c(qkv, np.float32), c(pos, np.int32), c(resid, np.float32)
+        qn, kn, wo, bo = c(qn, wt), c(kn, wt), c(wo, wt), c(bo, wt)
+        kc, vc = np.array(kc, dtype=wt, order="C"), np.array(vc, dtype=wt, order="C")                   # copies: written in place
+        M, H, hd = qkv.shape[0], a.n_head, a.head_dim
+        n_slots = a.max_seq_len + (-a.max_seq_len) % 8
+        y_ld = max(H * hd, a.fast_n_head * a.fast_head_dim)
+        assert qkv.shape == (M, (H + 2 * a.n_local_heads) * hd), qkv.shape
+        assert kc.shape == vc.shape == (M, a.n_local_heads, n_slots, hd), kc.shape
+        assert wo.shape == (a.dim, H * hd) and resid.shape == (M, a.dim), (wo.shape, resid.shape)
+        y = np.zeros((M, y_ld), dtype=np.float32)
+        po, pm = np.zeros((M * H * 32 * hd,), dtype=np.float32), np.zeros((M * H * 32 * 2,), dtype=np.float32)
+        xo = np.zeros((M, a.dim), dtype=np.float32)
+        ns = C.c_int32(0)
+        self._check(self.lib.ft_test_decode_attn(self._h, M, ptr(qkv), ptr(pos), pos_off, ptr(qn), ptr(kn), ptr(kc), ptr(vc), ptr(wo),
+                                                 ptr(bo), ptr(resid), C.byref(ns), ptr(y), ptr(po), ptr(pm), ptr(xo)),
+                    "ft_test_decode_attn")
+        n = ns.value
+        if n > 1:
+            po, pm = po[:M * H * n * hd].reshape(M, H, n, hd), pm[:M * H * n * 2].reshape(M, H, n, 2)
+        else:
+            po = pm = None
+        return n, y, po, pm, xo, kc, vc
+
+    def test_embed(self, emb: np.ndarray, cb_emb: np.ndarray, toks: np.ndarray, M: int, ncb: int, cbsize: int, sem_begin: int,
+                   sem_end: int, scale: bool, tok_row_stride: int, tok_m_stride: int, ldx=None, xo_ldm: int = 0):
+        """Test hook (ft_test_embed): one embed_kernel launch on caller tables.  emb (vocab, D), cb_emb (ncb cbsize, D):
+        patterns of the model's type; toks: flat int32.  Returns (x (M, D) f32, pad (M, ldx - D) uint32, tail (ldx,) uint32,
+        xo (D / 8, xo_ldm, 8) uint16 or None)."""
+        wt = self._wt()
+        emb, cb_emb = np.ascontiguousarray(emb, dtype=wt), np.ascontiguousarray(cb_emb, dtype=wt)
+        toks = np.ascontiguousarray(toks, dtype=np.int32).reshape(-1)
+        vocab, D = emb.shape
+        assert cb_emb.shape == (ncb * cbsize, D), cb_emb.shape
+        ldx = D if ldx is None else ldx
+        x = np.zeros((M + 1, ldx), dtype=np.float32)
+        xo = np.zeros(((D + 7) // 8, xo_ldm, 8), dtype=np.uint16) if xo_ldm > 0 else None
+        ptr = lambda t: None if t is None else t.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.ft_test_embed(self._h, M, D, ncb, cbsize, vocab, ptr(emb), ptr(cb_emb), ptr(toks), toks.size,
+                                           tok_row_stride, tok_m_stride, sem_begin, sem_end, 1 if scale else 0, ldx, xo_ldm, ptr(x),
+                                           ptr(xo)), "ft_test_embed")
+        return x[:M, :D].copy(), x[:M, D:].view(np.uint32).copy(), x[M].view(np.uint32).copy(), xo
+
+    def test_fast_attn(self, form: int, qkv: np.ndarray, c: int, qn, kn, kc: np.ndarray, vc: np.ndarray):
+        """Test hook (ft_test_fast_attn): one fast_attn_kernel launch.  form 0 single (M <= 4), 1 wide single, 2 paired (qkv
+        rows [0, M) at position 0, [M, 2 M) at position 1).  kc / vc (M, Hkv, ncb, hd).  Returns (y, pad, tail, kc, vc) for
+        form 0 (y (M, H hd) f32) or (y_bf (H hd / 8, xo_ldm, 8) uint16, kc, vc) for the wide forms; the caches as the hook
+        filled them (NaN from row c / 0 on) and the launch left them."""
+        wt = self._wt()
+        a = self.args
+        qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+        cc = lambda t: None if t is None else np.ascontiguousarray(t, dtype=wt)
+        ptr = lambda t: None if t is None else t.ctypes.data_as(C.c_void_p)
+        qn, kn = cc(qn), cc(kn)
+        kc, vc = np.array(kc, dtype=wt, order="C"), np.array(vc, dtype=wt, order="C")
+        M = qkv.shape[0] // 2 if form == 2 else qkv.shape[0]
+        H, hd = a.fast_n_head, a.fast_head_dim
+        assert qkv.shape[1] == (H + 2 * a.fast_n_local_heads) * hd, qkv.shape
+        assert kc.shape == vc.shape == (M, a.fast_n_local_heads, a.num_codebooks, hd), kc.shape
+        y_ld = max(a.n_head * a.head_dim, H * hd)
+        y = np.zeros((M + 1, y_ld), dtype=np.float32) if form == 0 else None
+        xo_ldm = 2 * ((self.max_batch + 15) // 16 * 16)
+        yb = None if form == 0 else np.zeros((H * hd // 8, xo_ldm, 8), dtype=np.uint16)
+        self._check(self.lib.ft_test_fast_attn(self._h, form, M, c, ptr(qkv), ptr(qn), ptr(kn), ptr(kc), ptr(vc), ptr(y), ptr(yb)),
+                    "ft_test_fast_attn")
+        if form == 0:
+            return y[:M, :H * hd].copy(), y[:M, H * hd:].view(np.uint32).copy(), y[M].view(np.uint32).copy(), kc, vc
+        return yb, kc, vc
+
     def engine_state(self):
         """(flags, time-outs recovered so far, phase of the last one) of the persistent frame engine: flags bit 0 = slow
         stack, bit 1 = fast loop."""

@@ -943,10 +943,14 @@ static void gemv_mb_nt(Launch& L, const GemvP& p, int nt) {
 #undef FT_NT
 }
 
+// Returns what it launched (the test hook ft_test_gemv reports it; the frames ignore it): MB rows per pass over the weights
+// (0: gemv_kernel, one grid row per batch row), R weight rows per wave, NT 16-byte pieces of K per lane.
+struct GemvId { int MB, R, NT; };
 template <typename WT, int ROUND>
-static void gemv(Launch& L, GemvP p, int R) {
+static GemvId gemv(Launch& L, GemvP p, int R) {
     const int nt = pick_nt(p.K, Vec<WT>::N);
-    if (nt < 0) { L.err = hipErrorInvalidValue; return; }
+    if (nt < 0) { L.err = hipErrorInvalidValue; return GemvId{-1, -1, -1}; }
+    GemvId id{0, 0, nt};
     ft_ctx* ctx = L.ctx;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ctx->prof && !ctx->prof_count_only) {
@@ -959,14 +963,14 @@ static void gemv(Launch& L, GemvP p, int R) {
     if (mb_ok) {
         if constexpr (sizeof(WT) == 2) {
             const bool four = L.M >= 3 && nt <= 2 && R <= 2;  // register budget: 4 x NT x 8 activations
-            if (R >= 4) { if (nt <= 2) gemv_mb_nt<WT, ROUND, 4, 2>(L, p, nt); else gemv_nt<WT, ROUND, 4>(L, p, nt); }
-            else if (R == 2) { if (four) gemv_mb_nt<WT, ROUND, 2, 4>(L, p, nt); else gemv_mb_nt<WT, ROUND, 2, 2>(L, p, nt); }
-            else { if (four) gemv_mb_nt<WT, ROUND, 1, 4>(L, p, nt); else gemv_mb_nt<WT, ROUND, 1, 2>(L, p, nt); }
+            if (R >= 4) { id.R = 4; if (nt <= 2) { id.MB = 2; gemv_mb_nt<WT, ROUND, 4, 2>(L, p, nt); } else gemv_nt<WT, ROUND, 4>(L, p, nt); }
+            else if (R == 2) { id.R = 2; id.MB = four ? 4 : 2; if (four) gemv_mb_nt<WT, ROUND, 2, 4>(L, p, nt); else gemv_mb_nt<WT, ROUND, 2, 2>(L, p, nt); }
+            else { id.R = 1; id.MB = four ? 4 : 2; if (four) gemv_mb_nt<WT, ROUND, 1, 4>(L, p, nt); else gemv_mb_nt<WT, ROUND, 1, 2>(L, p, nt); }
         }
-    } else if (R == 1) gemv_nt<WT, ROUND, 1>(L, p, nt);
-    else if (R == 2) gemv_nt<WT, ROUND, 2>(L, p, nt);
-    else if (R >= 8 && nt <= 2 && p.epi != EPI_SWIGLU) gemv_nt<WT, ROUND, 8>(L, p, nt);
-    else gemv_nt<WT, ROUND, 4>(L, p, nt);
+    } else if (R == 1) { id.R = 1; gemv_nt<WT, ROUND, 1>(L, p, nt); }
+    else if (R == 2) { id.R = 2; gemv_nt<WT, ROUND, 2>(L, p, nt); }
+    else if (R >= 8 && nt <= 2 && p.epi != EPI_SWIGLU) { id.R = 8; gemv_nt<WT, ROUND, 8>(L, p, nt); }
+    else { id.R = 4; gemv_nt<WT, ROUND, 4>(L, p, nt); }
     if (ctx->prof) {
         if (!ctx->prof_count_only) {
             hipEventRecord(e1, L.s);
@@ -976,6 +980,7 @@ static void gemv(Launch& L, GemvP p, int R) {
         ctx->prof_launches += 1;
     }
     L.chk();
+    return id;
 }
 
 static int rows_per_wave(int N, int M) {
@@ -1017,6 +1022,33 @@ static void gemv_combine_nt(Launch& L, const GemvP& p, const AttnP& a, int nt) {
 #define FT_NT(n) case n: gemv_attn_combine_kernel<WT, n, R, ROUND><<<grid, block, (size_t)a.H * a.hd * sizeof(float), L.s>>>(p, a); break;
     switch (nt) { FT_NT(1) FT_NT(2) FT_NT(3) FT_NT(4) FT_NT(6) FT_NT(8) FT_NT(12) default: L.err = hipErrorInvalidValue; }
 #undef FT_NT
+}
+
+// The "decode attention, then Wo" part of a slow layer for 1..4 rows: attn_decode_kernel over ctx->nsplit KV splits, then the
+// Wo product with the residual add - with more than one split the partials are merged inside it (gemv_attn_combine_kernel),
+// with one it reads the attention's y.  enqueue_slow and the test hook ft_test_decode_attn both call it.
+template <typename WT, int ROUND>
+static void decode_attn_wo(Launch& L, const AttnP& a, const GemvP& o) {
+    ft_ctx* ctx = L.ctx;
+    if (!L.gemv_only) attn_decode<WT, ROUND>(L, a);
+    if (ctx->nsplit > 1) {  // split-KV partials are merged inside the Wo kernel
+        const int nt = pick_nt(o.K, Vec<WT>::N);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (ctx->prof && !ctx->prof_count_only) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, L.s); }
+        if (rows_per_wave(o.N, L.M) >= 2) gemv_combine_nt<WT, ROUND, 2>(L, o, a, nt);
+        else gemv_combine_nt<WT, ROUND, 1>(L, o, a, nt);
+        if (ctx->prof) {
+            if (!ctx->prof_count_only) {
+                hipEventRecord(e1, L.s);
+                ctx->prof_ev.push_back(e0); ctx->prof_ev.push_back(e1);
+            }
+            ctx->prof_bytes += (int64_t)o.N * o.K * sizeof(WT);
+            ctx->prof_launches += 1;
+        }
+        L.chk();
+    } else {
+        gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
+    }
 }
 
 // The slow-stack attention launch of a wide batch, on an AttnP filled but for the split fields.  >= 128 (row, kv head)
@@ -1126,29 +1158,10 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
         a.y = y; a.ldy = ctx->y_ld;
         a.part_o = ctx->part_o + (size_t)m0 * c.n_head * ctx->nsplit * c.head_dim;
         a.part_ml = ctx->part_ml + (size_t)m0 * c.n_head * ctx->nsplit * 2;
-        if (!L.gemv_only) attn_decode<WT, ROUND>(L, a);
-
         GemvP o{};
         o.W = l.wo; o.bias = l.bo; o.x = y; o.ldx = ctx->y_ld; o.out = x; o.ldo = c.dim;
         o.resid = x; o.ldr = c.dim; o.N = c.dim; o.K = c.n_head * c.head_dim; o.pro = PRO_NONE; o.epi = EPI_RESID; o.nt = 1;
-        if (ctx->nsplit > 1) {  // split-KV partials are merged inside the Wo kernel
-            const int nt = pick_nt(o.K, Vec<WT>::N);
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (ctx->prof && !ctx->prof_count_only) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, L.s); }
-            if (rows_per_wave(o.N, L.M) >= 2) gemv_combine_nt<WT, ROUND, 2>(L, o, a, nt);
-            else gemv_combine_nt<WT, ROUND, 1>(L, o, a, nt);
-            if (ctx->prof) {
-                if (!ctx->prof_count_only) {
-                    hipEventRecord(e1, L.s);
-                    ctx->prof_ev.push_back(e0); ctx->prof_ev.push_back(e1);
-                }
-                ctx->prof_bytes += (int64_t)o.N * o.K * sizeof(WT);
-                ctx->prof_launches += 1;
-            }
-            L.chk();
-        } else {
-            gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
-        }
+        decode_attn_wo<WT, ROUND>(L, a, o);
 
         GemvP f{};
         f.W = l.w13; f.x = x; f.ldx = c.dim; f.gain = l.ffn_norm; f.eps = c.norm_eps; f.out = g;
@@ -2719,4 +2732,269 @@ extern "C" ft_status ft_test_pf_attn(ft_ctx* ctx, int32_t n_seq, const int32_t* 
     FT_HIP(ctx, hipMemcpy(kc, dK, cel * 2, hipMemcpyDeviceToHost));
     FT_HIP(ctx, hipMemcpy(vc, dV, cel * 2, hipMemcpyDeviceToHost));
     return FT_OK;
+}
+
+// ------------------------------------------------------------------------------------------ decode-launch test hooks (1..4 rows)
+// (include/fishtts_hip_test.h: ft_test_gemv, ft_test_decode_attn, ft_test_embed).  Host code around gemv, decode_attn_wo and
+// the embedding launch on temporaries: nothing here is reached from a frame.
+template <typename WT, int ROUND>
+static ft_status test_gemv_t(ft_ctx* ctx, int pro, int epi, int M, int N, int K, const float* x, int ldx, const void* W,
+                             const void* gain, const void* bias, const float* resid, bool alias, int nt, int ldo, float* out,
+                             int32_t* id3) {
+    const size_t esz = sizeof(WT);
+    std::vector<uint32_t> xh((size_t)4 * ldx, WT_POISON_F32);         // rows M .. 3 and the ldx padding: NaN patterns
+    for (int m = 0; m < M; ++m) memcpy(xh.data() + (size_t)m * ldx, x + (size_t)m * K, (size_t)K * 4);
+    std::vector<uint32_t> oh((size_t)(M + 1) * ldo, WT_POISON_F32);   // padding columns and the row behind row M - 1: the sentinel
+    std::vector<uint32_t> rh = oh;
+    if (epi == EPI_RESID)
+        for (int m = 0; m < M; ++m) memcpy(rh.data() + (size_t)m * ldo, resid + (size_t)m * N, (size_t)N * 4);
+    DevTmp tmp;
+    void* dX = tmp.put(xh.data(), xh.size() * 4);
+    void* dW = tmp.put(W, (size_t)N * K * esz);
+    void* dG = pro == PRO_RMSNORM ? tmp.put(gain, (size_t)K * esz) : nullptr;
+    void* dB = bias ? tmp.put(bias, (size_t)N * esz) : nullptr;
+    void* dR = epi == EPI_RESID ? tmp.put(rh.data(), rh.size() * 4) : nullptr;
+    void* dO = epi == EPI_RESID && alias ? dR : tmp.put(oh.data(), oh.size() * 4);
+    if (!dX || !dW || (pro == PRO_RMSNORM && !dG) || (bias && !dB) || (epi == EPI_RESID && !dR) || !dO) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_gemv: device temporaries");
+    }
+    Launch L{ctx, ctx->stream, 0, M, 0};
+    GemvP p{};
+    p.W = dW; p.bias = dB; p.x = (const float*)dX; p.ldx = ldx; p.gain = dG; p.eps = ctx->c.norm_eps;
+    p.out = (float*)dO; p.ldo = ldo; p.resid = (const float*)dR; p.ldr = ldo; p.N = N; p.K = K; p.pro = pro; p.epi = epi; p.nt = nt;
+    const GemvId id = gemv<WT, ROUND>(L, p, rows_per_wave(N, M));
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_gemv launch failed");
+    FT_HIP(ctx, hipMemcpy(out, dO, oh.size() * 4, hipMemcpyDeviceToHost));
+    id3[0] = id.MB; id3[1] = id.R; id3[2] = id.NT;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_gemv(ft_ctx* ctx, int32_t pro, int32_t epi, int32_t M, int32_t N, int32_t K, const float* x,
+                                  int32_t ldx, const void* W, const void* gain, const void* bias, const float* resid,
+                                  int32_t alias, int32_t nt, int32_t ldo, float* out, int32_t* id) {
+    FT_TRY(ar_ready(ctx));
+    const int vec = ctx->c.dtype == FT_F32 ? 4 : 8;
+    if (pro != PRO_NONE && pro != PRO_RMSNORM) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad prologue");
+    if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad epilogue");
+    if (M < 1 || M > 4) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: M outside 1..4");
+    if (K < 8 || K % 8 != 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: K is not a whole number of 16-byte pieces");
+    if (pick_nt(K, vec) < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: K above 12 x 64 pieces per row");
+    if (N < 1 || (epi == EPI_SWIGLU && N % 2 != 0)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad N");
+    const int oc = epi == EPI_SWIGLU ? N / 2 : N;
+    if (ldx < K || ldx % 4 != 0 || ldo < oc || ldo % 4 != 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad ldx or ldo");
+    if (!x || !W || !out || !id || (pro == PRO_RMSNORM && !gain) || (epi == EPI_RESID && !resid))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: missing argument");
+    if (ctx->c.dtype == FT_BF16) return test_gemv_t<bf16_t, RND_BF16>(ctx, pro, epi, M, N, K, x, ldx, W, gain, bias, resid, alias != 0, nt != 0, ldo, out, id);
+    if (ctx->c.dtype == FT_F16) return test_gemv_t<f16_t, RND_F16>(ctx, pro, epi, M, N, K, x, ldx, W, gain, bias, resid, alias != 0, nt != 0, ldo, out, id);
+    return test_gemv_t<float, RND_NONE>(ctx, pro, epi, M, N, K, x, ldx, W, gain, bias, resid, alias != 0, nt != 0, ldo, out, id);
+}
+
+template <typename WT, int ROUND>
+static ft_status test_decode_attn_t(ft_ctx* ctx, int M, const float* qkv, const int32_t* pos, int pos_off, const void* qn,
+                                    const void* kn, void* kc, void* vc, const void* wo, const void* bo, const float* resid,
+                                    float* y, float* part_o, float* part_ml, float* x_out) {
+    const ft_ar_config& c = ctx->c;
+    const size_t esz = sizeof(WT);
+    const int HD = c.n_head * c.head_dim, D = c.dim, ns = ctx->nsplit;
+    const size_t qkvN = (size_t)(c.n_head + 2 * c.n_local_heads) * c.head_dim;
+    const size_t cbytes = (size_t)M * ctx->cache_m_stride * esz;
+    const size_t n_po = (size_t)M * c.n_head * ns * c.head_dim, n_pm = (size_t)M * c.n_head * ns * 2;
+    const std::vector<uint32_t> yfill((size_t)M * ctx->y_ld, WT_POISON_F32);
+    DevTmp tmp;
+    void* dQ = tmp.put(qkv, (size_t)M * qkvN * sizeof(float));
+    void* dP = tmp.put(pos, (size_t)M * sizeof(int));
+    void* dQn = qn ? tmp.put(qn, (size_t)c.head_dim * esz) : nullptr;
+    void* dKn = kn ? tmp.put(kn, (size_t)c.head_dim * esz) : nullptr;
+    void* dK = tmp.put(kc, cbytes);
+    void* dV = tmp.put(vc, cbytes);
+    void* dW = tmp.put(wo, (size_t)D * HD * esz);
+    void* dB = bo ? tmp.put(bo, (size_t)D * esz) : nullptr;
+    void* dX = tmp.put(resid, (size_t)M * D * sizeof(float));
+    void* dY = tmp.put(yfill.data(), yfill.size() * 4);
+    if (!dQ || !dP || (qn && !dQn) || (kn && !dKn) || !dK || !dV || !dW || (bo && !dB) || !dX || !dY) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_decode_attn: device temporaries");
+    }
+    if (ns > 1) {   // the context's split-partial scratch: every (O, m, l) of this call must be written by the launch
+        const std::vector<uint32_t> pf(n_po, WT_POISON_F32);
+        FT_HIP(ctx, hipMemcpy(ctx->part_o, pf.data(), n_po * 4, hipMemcpyHostToDevice));
+        FT_HIP(ctx, hipMemcpy(ctx->part_ml, pf.data(), n_pm * 4, hipMemcpyHostToDevice));
+    }
+    Launch L{ctx, ctx->stream, 0, M, pos_off};
+    AttnP a{};
+    a.qkv = (const float*)dQ; a.ldq = (int)qkvN; a.qn = dQn; a.kn = dKn; a.rope = ctx->rope;
+    a.kc = dK; a.vc = dV; a.cache_m_stride = ctx->cache_m_stride; a.pos = (const int*)dP; a.pos_off = pos_off;
+    a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots;
+    a.nsplit = ns; a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim);
+    a.y = (float*)dY; a.ldy = ctx->y_ld;
+    a.part_o = ctx->part_o; a.part_ml = ctx->part_ml;
+    GemvP o{};
+    o.W = dW; o.bias = dB; o.x = (const float*)dY; o.ldx = ctx->y_ld; o.out = (float*)dX; o.ldo = D;
+    o.resid = (const float*)dX; o.ldr = D; o.N = D; o.K = HD; o.pro = PRO_NONE; o.epi = EPI_RESID; o.nt = 1;
+    decode_attn_wo<WT, ROUND>(L, a, o);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_decode_attn launch failed");
+    FT_HIP(ctx, hipMemcpy(y, dY, yfill.size() * 4, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(x_out, dX, (size_t)M * D * 4, hipMemcpyDeviceToHost));
+    if (ns > 1) {
+        FT_HIP(ctx, hipMemcpy(part_o, ctx->part_o, n_po * 4, hipMemcpyDeviceToHost));
+        FT_HIP(ctx, hipMemcpy(part_ml, ctx->part_ml, n_pm * 4, hipMemcpyDeviceToHost));
+    }
+    FT_HIP(ctx, hipMemcpy(kc, dK, cbytes, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(vc, dV, cbytes, hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_decode_attn(ft_ctx* ctx, int32_t M, const float* qkv, const int32_t* pos, int32_t pos_off,
+                                         const void* qn, const void* kn, void* kc, void* vc, const void* wo, const void* bo,
+                                         const float* resid, int32_t* nsplit, float* y, float* part_o, float* part_ml,
+                                         float* x_out) {
+    FT_TRY(ar_ready(ctx));
+    if (M < 1 || M > ctx->c.max_batch || M > 4) return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: M outside 1..min(max_batch, 4)");
+    if (!qkv || !pos || !kc || !vc || !wo || !resid || !nsplit || !y || !part_o || !part_ml || !x_out)
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: missing argument");
+    if (pos_off < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: negative pos_off");
+    int pos_end = 0;
+    for (int m = 0; m < M; ++m) {
+        if (pos[m] < 0 || pos[m] + pos_off >= ctx->n_slots || pos[m] + pos_off >= ctx->c.max_seq_len)
+            return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: a position outside the cache or the rope table");
+        pos_end = std::max(pos_end, pos[m] + pos_off + 1);
+    }
+    const int saved = ctx->nsplit;
+    pick_nsplit(ctx, pos_end);       // as ft_ar_decode does for the longest context of its call
+    *nsplit = ctx->nsplit;
+    ft_status st;
+    if (ctx->c.dtype == FT_BF16) st = test_decode_attn_t<bf16_t, RND_BF16>(ctx, M, qkv, pos, pos_off, qn, kn, kc, vc, wo, bo, resid, y, part_o, part_ml, x_out);
+    else if (ctx->c.dtype == FT_F16) st = test_decode_attn_t<f16_t, RND_F16>(ctx, M, qkv, pos, pos_off, qn, kn, kc, vc, wo, bo, resid, y, part_o, part_ml, x_out);
+    else st = test_decode_attn_t<float, RND_NONE>(ctx, M, qkv, pos, pos_off, qn, kn, kc, vc, wo, bo, resid, y, part_o, part_ml, x_out);
+    ctx->nsplit = saved;
+    return st;
+}
+
+template <typename WT, int ROUND>
+static ft_status test_embed_t(ft_ctx* ctx, int M, int D, int ncb, int cbsize, int vocab, const void* emb, const void* cb_emb,
+                              const int32_t* toks, int64_t n_toks, int64_t trs, int64_t tms, int sem_begin, int sem_end, int scale,
+                              int ldx, int xo_ldm, float* x, uint16_t* xo) {
+    const size_t esz = sizeof(WT);
+    const std::vector<uint32_t> xfill((size_t)(M + 1) * ldx, WT_POISON_F32);
+    const size_t n_xo = (size_t)((D + 7) / 8) * xo_ldm * 8;
+    const std::vector<uint16_t> ofill(n_xo, WT_POISON);
+    DevTmp tmp;
+    void* dE = tmp.put(emb, (size_t)vocab * D * esz);
+    void* dC = tmp.put(cb_emb, (size_t)ncb * cbsize * D * esz);
+    void* dT = tmp.put(toks, (size_t)n_toks * sizeof(int));
+    void* dX = tmp.put(xfill.data(), xfill.size() * 4);
+    void* dO = xo_ldm > 0 ? tmp.put(ofill.data(), n_xo * 2) : nullptr;
+    if (!dE || !dC || !dT || !dX || (xo_ldm > 0 && !dO)) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_embed: device temporaries");
+    }
+    EmbedP e{};
+    e.emb = dE; e.cb_emb = dC; e.toks = (const int*)dT; e.tok_row_stride = (long)trs; e.tok_m_stride = (long)tms; e.col = 0;
+    e.x = (float*)dX; e.ldx = ldx; e.D = D; e.ncb = ncb; e.cbsize = cbsize; e.vocab = vocab; e.sem_begin = sem_begin;
+    e.sem_end = sem_end; e.scale = scale; e.inv_div = (float)sqrt((double)(ncb + 1));
+    e.xo = (bf16_t*)dO; e.xo_ldm = xo_ldm;
+    embed_kernel<WT, ROUND><<<dim3((D + 255) / 256, M), 256, 0, ctx->stream>>>(e);
+    const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(ctx->stream);
+    if (le != hipSuccess || se != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_embed launch failed");
+    FT_HIP(ctx, hipMemcpy(x, dX, xfill.size() * 4, hipMemcpyDeviceToHost));
+    if (xo_ldm > 0) FT_HIP(ctx, hipMemcpy(xo, dO, n_xo * 2, hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_embed(ft_ctx* ctx, int32_t M, int32_t D, int32_t ncb, int32_t cbsize, int32_t vocab, const void* emb,
+                                   const void* cb_emb, const int32_t* toks, int64_t n_toks, int64_t tok_row_stride,
+                                   int64_t tok_m_stride, int32_t sem_begin, int32_t sem_end, int32_t scale, int32_t ldx,
+                                   int32_t xo_ldm, float* x, uint16_t* xo) {
+    FT_TRY(ar_ready(ctx));
+    if (M < 1 || M > 65535 || D < 1 || ncb < 1 || cbsize < 1 || vocab < 1 || ldx < D)
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_embed: bad size");
+    if (!emb || !cb_emb || !toks || !x || (xo_ldm > 0 && !xo)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_embed: missing argument");
+    if (xo_ldm < 0 || (xo_ldm > 0 && (ctx->c.dtype == FT_F32 || M > xo_ldm)))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_embed: the octet-major copy is 16-bit, of at most xo_ldm rows");
+    if (tok_row_stride < 0 || tok_m_stride < 0 || (int64_t)(M - 1) * tok_m_stride + (int64_t)ncb * tok_row_stride >= n_toks)
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_embed: the token strides reach past toks");
+    if (ctx->c.dtype == FT_BF16) return test_embed_t<bf16_t, RND_BF16>(ctx, M, D, ncb, cbsize, vocab, emb, cb_emb, toks, n_toks, tok_row_stride, tok_m_stride, sem_begin, sem_end, scale, ldx, xo_ldm, x, xo);
+    if (ctx->c.dtype == FT_F16) return test_embed_t<f16_t, RND_F16>(ctx, M, D, ncb, cbsize, vocab, emb, cb_emb, toks, n_toks, tok_row_stride, tok_m_stride, sem_begin, sem_end, scale, ldx, xo_ldm, x, xo);
+    return test_embed_t<float, RND_NONE>(ctx, M, D, ncb, cbsize, vocab, emb, cb_emb, toks, n_toks, tok_row_stride, tok_m_stride, sem_begin, sem_end, scale, ldx, xo_ldm, x, xo);
+}
+
+template <typename WT, int ROUND>
+static ft_status test_fast_attn_t(ft_ctx* ctx, int form, int M, int cpos, const float* qkv, const void* qn, const void* kn, void* kc,
+                                  void* vc, float* y, uint16_t* y_bf) {
+    const ft_ar_config& c = ctx->c;
+    const size_t esz = sizeof(WT);
+    const int Hf = c.fast_n_head, Hkvf = c.fast_n_local_heads, hdf = c.fast_head_dim, HDf = Hf * hdf, ncb = c.num_codebooks;
+    const size_t qkvN = (size_t)(Hf + 2 * Hkvf) * hdf;
+    const int rows = form == 2 ? ctx->xo_pair + M : M;
+    const size_t cel = (size_t)M * ctx->fcache_m_stride;
+    // NaN patterns in every cache row the launch appends or must not read: from c on (the paired pass: from row 0 on)
+    const int first = form == 2 ? 0 : cpos;
+    for (int m = 0; m < M; ++m)
+        for (int h = 0; h < Hkvf; ++h) {
+            char* k0 = (char*)kc + ((size_t)m * ctx->fcache_m_stride + ((size_t)h * ncb + first) * hdf) * esz;
+            char* v0 = (char*)vc + ((size_t)m * ctx->fcache_m_stride + ((size_t)h * ncb + first) * hdf) * esz;
+            memset(k0, 0xFF, (size_t)(ncb - first) * hdf * esz);          // all-ones: a NaN in bf16, fp16 and f32
+            memset(v0, 0xFF, (size_t)(ncb - first) * hdf * esz);
+        }
+    std::vector<uint32_t> qh((size_t)rows * qkvN, WT_POISON_F32);        // paired: rows M .. xo_pair - 1 belong to nobody
+    memcpy(qh.data(), qkv, (size_t)M * qkvN * 4);
+    if (form == 2) memcpy(qh.data() + (size_t)ctx->xo_pair * qkvN, qkv + (size_t)M * qkvN, (size_t)M * qkvN * 4);
+    const int ldm = ctx->xo_ldm;
+    const std::vector<uint32_t> yfill((size_t)(M + 1) * ctx->y_ld, WT_POISON_F32);
+    const std::vector<uint16_t> bfill(form ? (size_t)HDf * ldm : 0, WT_POISON);
+    DevTmp tmp;
+    void* dQ = tmp.put(qh.data(), qh.size() * 4);
+    void* dQn = qn ? tmp.put(qn, (size_t)hdf * esz) : nullptr;
+    void* dKn = kn ? tmp.put(kn, (size_t)hdf * esz) : nullptr;
+    void* dK = tmp.put(kc, cel * esz);
+    void* dV = tmp.put(vc, cel * esz);
+    void* dY = form == 0 ? tmp.put(yfill.data(), yfill.size() * 4) : tmp.put(bfill.data(), bfill.size() * 2);
+    if (!dQ || (qn && !dQn) || (kn && !dKn) || !dK || !dV || !dY) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_fast_attn: device temporaries");
+    }
+    FastAttnP a{};
+    a.qkv = (const float*)dQ; a.ldq = (int)qkvN; a.qn = dQn; a.kn = dKn; a.rope = ctx->frope;
+    a.kc = dK; a.vc = dV; a.cache_m_stride = ctx->fcache_m_stride; a.c = form == 2 ? 0 : cpos; a.H = Hf; a.Hkv = Hkvf; a.hd = hdf;
+    a.ncb = ncb; a.eps = c.norm_eps; a.scale = (float)(1.0 / sqrt((double)hdf));
+    if (form == 0) {
+        fast_attn_kernel<WT, ROUND><<<dim3(Hf, M), 64, 0, ctx->stream>>>(a, (float*)dY, ctx->y_ld);
+    } else {
+        a.y_bf = (bf16_t*)dY; a.y_xo_ldm = ldm;
+        a.pair_M = form == 2 ? M : 0; a.pair_off = ctx->xo_pair;
+        fast_attn_kernel<WT, ROUND><<<dim3(Hf, form == 2 ? 2 * M : M), 64, 0, ctx->stream>>>(a, nullptr, HDf);
+    }
+    const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(ctx->stream);
+    if (le != hipSuccess || se != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_fast_attn launch failed");
+    if (form == 0) FT_HIP(ctx, hipMemcpy(y, dY, yfill.size() * 4, hipMemcpyDeviceToHost));
+    else FT_HIP(ctx, hipMemcpy(y_bf, dY, bfill.size() * 2, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(kc, dK, cel * esz, hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(vc, dV, cel * esz, hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_fast_attn(ft_ctx* ctx, int32_t form, int32_t M, int32_t cpos, const float* qkv, const void* qn,
+                                       const void* kn, void* kc, void* vc, float* y, uint16_t* y_bf) {
+    FT_TRY(ar_ready(ctx));
+    const ft_ar_config& c = ctx->c;
+    if (form < 0 || form > 2) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: bad form");
+    if (!qkv || !kc || !vc || (form == 0 ? !y : !y_bf)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: missing argument");
+    if (c.n_fast_layer < 1 || c.num_codebooks > FAST_MAXCB || c.fast_head_dim > 128)
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: this context has no fast stack the kernel takes");
+    if (form == 0) {
+        if (M < 1 || M > 4) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: M outside 1..4");
+    } else {
+        if (c.dtype == FT_F32) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: the wide forms are 16-bit");
+        if (!ctx->wide_ok) return ft_fail(ctx, FT_ERR_STATE, "ft_test_fast_attn: this context has no lock-step MFMA path");
+        if (M < 5 || M > 64 || M > ctx->xo_ldm) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: M outside 5..min(64, xo_ldm)");
+        if (form == 2 && (c.num_codebooks < 2 || ctx->xo_pair + M > ctx->xo_ldm))
+            return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: the paired pass does not fit");
+    }
+    if (form != 2 && (cpos < 0 || cpos >= c.num_codebooks)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: c outside 0..ncb-1");
+    if (c.dtype == FT_BF16) return test_fast_attn_t<bf16_t, RND_BF16>(ctx, form, M, cpos, qkv, qn, kn, kc, vc, y, y_bf);
+    if (c.dtype == FT_F16) return test_fast_attn_t<f16_t, RND_F16>(ctx, form, M, cpos, qkv, qn, kn, kc, vc, y, y_bf);
+    return test_fast_attn_t<float, RND_NONE>(ctx, form, M, cpos, qkv, qn, kn, kc, vc, y, y_bf);
 }
