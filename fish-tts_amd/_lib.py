@@ -49,6 +49,14 @@ class ft_sampling(C.Structure):
                 ("ban_eos", C.c_int32), ("seed", C.c_uint64)]
 
 
+class ft_test_draw_io(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("M", "cb", "last", "what")] +
+                [("logits", C.c_void_p), ("sp", C.POINTER(ft_sampling)), ("noise", C.c_void_p),
+                 ("noise_rows", C.c_int64), ("noise_row_len", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("tokn", "tok", "seq", "pos", "nf", "done", "logits_out", "femb", "qkvf",
+                                           "xo_femb", "xo_x", "cut", "chunk_cnt", "part_idx")])
+
+
 # every symbol include/fishtts_hip.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -110,6 +118,8 @@ SYMBOLS = {
     "ft_ar_frame_path": (C.c_char_p, [_P]),
     "ft_test_engine_fault": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "ft_test_sample": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(ft_sampling), _P, _P, _P]),
+    "ft_test_draw": (C.c_int32, [_P, C.POINTER(ft_test_draw_io)]),
+    "ft_test_qkv0_tab": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     "ft_test_codec_trace_arm": (C.c_int32, [_P, C.c_int32, C.c_int32]),
     "ft_test_codec_trace_count": (C.c_int32, [_P]),
     "ft_test_codec_trace_variants": (C.c_int32, []),

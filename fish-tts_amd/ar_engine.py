@@ -292,6 +292,66 @@ class ARHipEngine:
             None if qq is None else qq.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "ft_test_sample")
         return int(out[0])
 
+    DRAW_SENTINEL = 0x7E5A5A5A                                              # integer state a draw must not touch
+
+    def test_draw(self, logits: np.ndarray, cb: int, samplings: Sequence[L.ft_sampling], nf, hist: np.ndarray, last: bool = False,
+                  pos=None, done=None, noise=None, omit=None):
+        """Test hook (ft_test_draw): ONE draw launch of M = len(logits) rows through the product's own host routine.  logits
+        (M, V) f32; nf, pos, done (M,); hist (M, R, cap): each row's history block, whole; noise (rows, row_len) in
+        set_noise's layout or None (the counter-based generator).  tokn, tok and rows M .. of every per-row array are
+        pre-set to DRAW_SENTINEL (pos, nf, done of rows M ..: too).  Returns a dict of everything the launch could write, max_batch
+        rows each: tokn, tok (MB, R), seq (MB, R, cap), pos, nf, done (MB,), femb (MB, fast_dim) f32, qkvf (rows, width) f32,
+        xo_femb / xo_x (dim / 8, xo_ldm, 8) uint16 or None, logits (MB, V) (rows M ..: the hook's fill), cut (MB, 8) uint32, chunk_cnt / part_idx
+        (MB-row scratch, flat int32), what (see include/fishtts_hip_test.h), path = what & 3.  Nothing is checked here: M, cb and
+        last (an int passes as it is) reach the hook, which refuses what is out of range; omit names a pointer left null."""
+        a, MB, R, cap = self.args, self.max_batch, self.R, self.max_new_tokens + 24
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        M = logits.shape[0]
+        S = self.DRAW_SENTINEL
+        ptr = lambda t: None if t is None else t.ctypes.data_as(C.c_void_p)
+
+        def rows(v, shape, fill=S):
+            o = np.full((MB,) + shape, fill, dtype=np.int32)
+            if v is not None:
+                o[:M] = np.asarray(v, dtype=np.int32).reshape((M,) + shape)[:MB]
+            return o
+        tokn, tok = rows(None, (R,)), rows(None, (R,))
+        seq = rows(hist, (R, cap))
+        nf_a, pos_a, done_a = rows(nf, ()), rows(np.zeros(M) if pos is None else pos, ()), rows(np.zeros(M) if done is None else done, ())
+        fqkv = (a.fast_n_head + 2 * a.fast_n_local_heads) * a.fast_head_dim
+        P = 2 * ((MB + 15) // 16 * 16)
+        nchunk = (a.vocab_size + 1023) // 1024
+        wide = "MFMA launches" in self.frame_path()
+        out = dict(logits=np.zeros((MB, logits.shape[1]), dtype=np.float32), femb=np.zeros((MB, a.fast_dim), dtype=np.float32),
+                   qkvf=np.zeros((P, fqkv), dtype=np.float32),
+                   xo_femb=np.zeros((a.dim // 8, P, 8), dtype=np.uint16) if wide else None,
+                   xo_x=np.zeros((a.dim // 8, P, 8), dtype=np.uint16) if wide else None,
+                   cut=np.zeros((MB, 8), dtype=np.uint32), chunk_cnt=np.zeros(MB * nchunk, dtype=np.int32),
+                   part_idx=np.zeros(MB * nchunk, dtype=np.int32))
+        sp = (L.ft_sampling * M)(*samplings)
+        q = None if noise is None else np.ascontiguousarray(noise, dtype=np.float32)
+        io = L.ft_test_draw_io()
+        io.M, io.cb, io.last, io.what = M, cb, int(last), -1
+        io.logits, io.sp, io.noise = ptr(logits), sp, ptr(q)
+        io.noise_rows, io.noise_row_len = (0, 0) if q is None else q.shape
+        io.tokn, io.tok, io.seq, io.pos, io.nf, io.done = ptr(tokn), ptr(tok), ptr(seq), ptr(pos_a), ptr(nf_a), ptr(done_a)
+        io.logits_out, io.femb, io.qkvf = ptr(out["logits"]), ptr(out["femb"]), ptr(out["qkvf"])
+        io.xo_femb, io.xo_x = ptr(out["xo_femb"]), ptr(out["xo_x"])
+        io.cut, io.chunk_cnt, io.part_idx = ptr(out["cut"]), ptr(out["chunk_cnt"]), ptr(out["part_idx"])
+        if omit:
+            setattr(io, omit, None)
+        self._check(self.lib.ft_test_draw(self._h, C.byref(io)), "ft_test_draw")
+        out.update(tokn=tokn, tok=tok, seq=seq, pos=pos_a, nf=nf_a, done=done_a, what=int(io.what), path=int(io.what) & 3)
+        return out
+
+    def test_qkv0_tab(self, row0: int, rows: int):
+        """Test hook (ft_test_qkv0_tab): rows of the lock-step batches' layer-0 q k v table, (rows, width) uint16, or None."""
+        a = self.args
+        out = np.zeros((rows, (a.fast_n_head + 2 * a.fast_n_local_heads) * a.fast_head_dim), dtype=np.uint16)
+        present = C.c_int32(0)
+        self._check(self.lib.ft_test_qkv0_tab(self._h, row0, rows, out.ctypes.data_as(C.c_void_p), C.byref(present)), "ft_test_qkv0_tab")
+        return out if present.value else None
+
     def test_wide_linear(self, epi: int, M: int, X: np.ndarray, W: np.ndarray, gain=None, bias=None, resid=None,
                          alias: bool = False, vocab_head: bool = False):
         """Test hook (ft_test_wide_linear): one Linear of a lock-step batch through the product's dispatcher.  X (M, K),

@@ -1199,9 +1199,12 @@ static void enqueue_head(Launch& L) {
     gemv<WT, ROUND>(L, h, rows_per_wave(h.N, L.M));
 }
 
+// Returns what it launched (the test hook ft_test_draw reports it; the frames ignore it): DRAW_* below
+enum { DRAW_SMALL = 0, DRAW_BLOCK = 1, DRAW_FOUR = 2, DRAW_PATH_MASK = 3, DRAW_XO_FEMB = 4, DRAW_XO_PAIR = 8, DRAW_QKV0_TAB = 16 };
 template <typename WT, int ROUND>
-static void enqueue_sample(Launch& L, int cb, bool last) {
-    if (L.gemv_only) return;
+static int enqueue_sample(Launch& L, int cb, bool last) {
+    if (L.gemv_only) return -1;
+    int what = 0;
     ft_ctx* ctx = L.ctx;
     const ft_ar_config& c = ctx->c;
     const int m0 = L.m0, R = c.num_codebooks + 1;
@@ -1219,13 +1222,16 @@ static void enqueue_sample(Launch& L, int cb, bool last) {
         // the semantic code's embedding is position 1 of the paired pass: it joins the slow stack's residual stream
         s.femb_xo = (cb == 0 && wide_pair(L) ? ctx->xo_x + (size_t)ctx->xo_pair * 8 : ctx->xo_femb) + (size_t)m0 * 8;
         s.femb_ldm = ctx->xo_ldm;
+        what |= cb == 0 && wide_pair(L) ? DRAW_XO_PAIR : DRAW_XO_FEMB;
         if (cb >= 1 && cb + 1 < c.num_codebooks && ctx->wide_qkv0_tab) {     // the next codebook step's layer-0 q k v (its launch is skipped)
+            what |= DRAW_QKV0_TAB;
             s.qkv0_tab = ctx->wide_qkv0_tab; s.qkv0_n = (c.fast_n_head + 2 * c.fast_n_local_heads) * c.fast_head_dim;
             s.qkv0_out = ctx->qkvf + (size_t)m0 * s.qkv0_n;
         }
     }
     if (s.V <= 1024) {
         sample_small_kernel<WT, ROUND><<<L.M, 256, 0, L.s>>>(s);
+        what |= DRAW_SMALL;
     } else if (ROUND == RND_BF16) {
         // large vocabulary, bf16: the histogram of the 65 536 bf16 classes and the search of the top-p cut on it in ONE block
         // per row (LDS counters), then index-ordered tie handling and the chip-wide race
@@ -1246,10 +1252,13 @@ static void enqueue_sample(Launch& L, int cb, bool last) {
         samp_count_kernel<<<gridc, 256, 0, L.s>>>(b);
         samp_race_kernel<<<gridc, 256, 0, L.s>>>(b);
         samp_finish_kernel<WT><<<L.M, 256, 0, L.s>>>(b);
+        what |= DRAW_FOUR;
     } else {
         sample_block_kernel<WT, ROUND><<<L.M, 1024, 0, L.s>>>(s);
+        what |= DRAW_BLOCK;
     }
     L.chk();
+    return what;
 }
 
 // The fast transformer over codebook positions 0..ncb-1 with its sampling (inference.py:115-149).
@@ -2420,9 +2429,7 @@ extern "C" ft_status ft_test_sample(ft_ctx* ctx, const float* logits, int32_t cb
     return ft_ar_reset(ctx, 0);
 }
 
-// ------------------------------------------------------------------------------------------ lock-step kernel test hooks
-// (include/fishtts_hip_test.h: ft_test_wide_linear, ft_test_wide_attn).  Host code around the product's own dispatchers
-// wide_gemm and wide_attn on temporaries: nothing here is reached from a frame.
+// device temporaries and sentinels of the test hooks below
 namespace {
 constexpr uint16_t WT_POISON = 0xFFFE;          // a NaN in bf16 and in fp16: operand rows >= M, and the 16-bit output sentinel
 constexpr uint32_t WT_POISON_F32 = 0xFFFFFFFEu; // the f32 output sentinel (a NaN)
@@ -2438,6 +2445,126 @@ struct DevTmp {                                  // device temporaries of one ho
     }
 };
 }  // namespace
+
+// Test hook (include/fishtts_hip_test.h: ft_test_draw): ONE enqueue_sample on the context's own buffers, M rows, every
+// buffer the draw may write pre-filled and returned whole.  Host code only: nothing here is reached from a frame.
+static ft_status test_draw_run(ft_ctx* ctx, ft_test_draw_io* io);
+extern "C" ft_status ft_test_draw(ft_ctx* ctx, ft_test_draw_io* io) {
+    FT_TRY(ar_ready(ctx));
+    const ft_ar_config& c = ctx->c;
+    if (!io) return ft_fail(ctx, FT_ERR_ARG, "ft_test_draw: no argument block");
+    const int MB = c.max_batch, M = io->M, cb = io->cb, R = c.num_codebooks + 1;
+    if (M < 1 || M > MB) return ft_fail(ctx, FT_ERR_ARG, "ft_test_draw: M outside 1..max_batch");
+    if (cb < 0 || cb >= c.num_codebooks) return ft_fail(ctx, FT_ERR_ARG, "ft_test_draw: bad codebook");
+    if (io->last != 0 && io->last != 1) return ft_fail(ctx, FT_ERR_ARG, "ft_test_draw: last is 0 or 1");
+    if (!io->logits || !io->sp || !io->tokn || !io->tok || !io->seq || !io->pos || !io->nf || !io->done || !io->logits_out ||
+        !io->femb || !io->qkvf || !io->cut || !io->chunk_cnt || !io->part_idx || (ctx->wide_ok && (!io->xo_femb || !io->xo_x)))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_draw: missing argument");
+    const long need = (long)c.vocab_size + (long)(c.num_codebooks - 1) * ctx->fastV;
+    if (io->noise && (io->noise_rows < 1 || io->noise_row_len < need))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_draw: noise block smaller than one frame's draws");
+    for (int m = 0; m < M; ++m)      // the kernels index the history and the noise by nf: keep both inside their blocks
+        if (io->nf[m] < 0 || io->nf[m] > ctx->cap || (io->noise && io->nf[m] >= io->noise_rows))
+            return ft_fail(ctx, FT_ERR_ARG, "ft_test_draw: nf outside 0..cap or past the noise block");
+    // the device work, then - whatever it returned - the context's own noise back and every slot as a reset leaves it
+    float* saved = ctx->noise;
+    const long srows = ctx->noise_rows, slen = ctx->noise_row_len;
+    const ft_status st = test_draw_run(ctx, io);
+    ctx->noise = saved; ctx->noise_rows = srows; ctx->noise_row_len = slen;
+    (void)hipStreamSynchronize(ctx->stream);
+    if (st != FT_OK) (void)hipGetLastError();
+    bool ok = hipMemsetAsync(ctx->d_tokn, 0, (size_t)MB * R * sizeof(int), ctx->stream) == hipSuccess &&
+              hipMemsetAsync(ctx->d_tok, 0, (size_t)MB * R * sizeof(int), ctx->stream) == hipSuccess;
+    for (int m = 0; m < MB; ++m) ok = ft_ar_reset(ctx, m) == FT_OK && ok;
+    ok = hipStreamSynchronize(ctx->stream) == hipSuccess && ok;
+    if (st != FT_OK) return st;
+    return ok ? FT_OK : ft_fail(ctx, FT_ERR_HIP, "ft_test_draw: reset failed");
+}
+
+static ft_status test_draw_run(ft_ctx* ctx, ft_test_draw_io* io) {
+    const ft_ar_config& c = ctx->c;
+    const int MB = c.max_batch, M = io->M, cb = io->cb, R = c.num_codebooks + 1;
+    const int V = cb == 0 ? c.vocab_size : ctx->fastV;
+    const size_t fqkvN = (size_t)(c.fast_n_head + 2 * c.fast_n_local_heads) * c.fast_head_dim;
+    const size_t qkvf_n = 2 * (((size_t)MB + 15) / 16 * 16) * fqkvN;
+    const size_t nchunk = ((size_t)c.vocab_size + 1023) / 1024;
+    const size_t xo_n = ctx->wide_ok ? (size_t)ctx->xo_ldm * c.dim : 0;     // wide_ok: fast_dim == dim
+    float* dl = cb == 0 ? ctx->logits : ctx->flog;
+    hipStream_t st = ctx->stream;
+    // 0xFF bytes: a NaN in f32, bf16 and fp16, -1 in the integer scratch
+    FT_HIP(ctx, hipMemsetAsync(dl, 0xFF, (size_t)MB * V * sizeof(float), st));
+    FT_HIP(ctx, hipMemsetAsync(ctx->femb, 0xFF, (size_t)MB * c.fast_dim * sizeof(float), st));
+    FT_HIP(ctx, hipMemsetAsync(ctx->qkvf, 0xFF, qkvf_n * sizeof(float), st));
+    FT_HIP(ctx, hipMemsetAsync(ctx->d_ctl, 0xFF, (size_t)MB * sizeof(RowCtl), st));
+    FT_HIP(ctx, hipMemsetAsync(ctx->samp_cut, 0xFF, (size_t)MB * sizeof(SampCut), st));
+    FT_HIP(ctx, hipMemsetAsync(ctx->samp_chunk_cnt, 0xFF, MB * nchunk * sizeof(int), st));
+    FT_HIP(ctx, hipMemsetAsync(ctx->samp_part_score, 0xFF, MB * nchunk * sizeof(float), st));
+    FT_HIP(ctx, hipMemsetAsync(ctx->samp_part_idx, 0xFF, MB * nchunk * sizeof(int), st));
+    if (xo_n) {
+        FT_HIP(ctx, hipMemsetAsync(ctx->xo_femb, 0xFF, xo_n * sizeof(bf16_t), st));
+        FT_HIP(ctx, hipMemsetAsync(ctx->xo_x, 0xFF, xo_n * sizeof(bf16_t), st));
+    }
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    FT_TRY(upload_ctl(ctx, 0, M, io->sp));
+    FT_HIP(ctx, hipMemcpy(dl, io->logits, (size_t)M * V * sizeof(float), hipMemcpyHostToDevice));
+    FT_HIP(ctx, hipMemcpy(ctx->d_tokn, io->tokn, (size_t)MB * R * sizeof(int), hipMemcpyHostToDevice));
+    FT_HIP(ctx, hipMemcpy(ctx->d_tok, io->tok, (size_t)MB * R * sizeof(int), hipMemcpyHostToDevice));
+    FT_HIP(ctx, hipMemcpy(ctx->d_seq, io->seq, (size_t)MB * R * ctx->cap * sizeof(int), hipMemcpyHostToDevice));
+    FT_HIP(ctx, hipMemcpy(ctx->d_pos, io->pos, (size_t)MB * sizeof(int), hipMemcpyHostToDevice));
+    FT_HIP(ctx, hipMemcpy(ctx->d_nf, io->nf, (size_t)MB * sizeof(int), hipMemcpyHostToDevice));
+    FT_HIP(ctx, hipMemcpy(ctx->d_done, io->done, (size_t)MB * sizeof(int), hipMemcpyHostToDevice));
+    DevTmp tmp;
+    if (io->noise) {
+        float* dq = (float*)tmp.put(io->noise, (size_t)io->noise_rows * io->noise_row_len * sizeof(float));
+        if (!dq) { (void)hipGetLastError(); return ft_fail(ctx, FT_ERR_NOMEM, "ft_test_draw: noise block"); }
+        ctx->noise = dq; ctx->noise_rows = io->noise_rows; ctx->noise_row_len = io->noise_row_len;
+    } else {
+        ctx->noise = nullptr; ctx->noise_rows = 0;
+    }
+    Launch L{ctx, st, 0, M, 0};
+    int what;
+    if (c.dtype == FT_BF16) what = enqueue_sample<bf16_t, RND_BF16>(L, cb, io->last != 0);
+    else if (c.dtype == FT_F16) what = enqueue_sample<f16_t, RND_F16>(L, cb, io->last != 0);
+    else what = enqueue_sample<float, RND_NONE>(L, cb, io->last != 0);
+    hipError_t e = hipStreamSynchronize(st);
+    if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_draw launch failed");
+    io->what = what;
+    FT_HIP(ctx, hipMemcpy(io->logits_out, dl, (size_t)MB * V * sizeof(float), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->tokn, ctx->d_tokn, (size_t)MB * R * sizeof(int), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->tok, ctx->d_tok, (size_t)MB * R * sizeof(int), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->seq, ctx->d_seq, (size_t)MB * R * ctx->cap * sizeof(int), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->pos, ctx->d_pos, (size_t)MB * sizeof(int), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->nf, ctx->d_nf, (size_t)MB * sizeof(int), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->done, ctx->d_done, (size_t)MB * sizeof(int), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->femb, ctx->femb, (size_t)MB * c.fast_dim * sizeof(float), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->qkvf, ctx->qkvf, qkvf_n * sizeof(float), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->cut, ctx->samp_cut, (size_t)MB * sizeof(SampCut), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->chunk_cnt, ctx->samp_chunk_cnt, MB * nchunk * sizeof(int), hipMemcpyDeviceToHost));
+    FT_HIP(ctx, hipMemcpy(io->part_idx, ctx->samp_part_idx, MB * nchunk * sizeof(int), hipMemcpyDeviceToHost));
+    if (xo_n) {
+        FT_HIP(ctx, hipMemcpy(io->xo_femb, ctx->xo_femb, xo_n * sizeof(bf16_t), hipMemcpyDeviceToHost));
+        FT_HIP(ctx, hipMemcpy(io->xo_x, ctx->xo_x, xo_n * sizeof(bf16_t), hipMemcpyDeviceToHost));
+    }
+    return FT_OK;
+}
+
+// Test hook: rows [row0, row0 + rows) of the lock-step batches' layer-0 q k v table as raw 16-bit patterns; *present = 0 (out
+// untouched) on a context that built none.
+extern "C" ft_status ft_test_qkv0_tab(ft_ctx* ctx, int32_t row0, int32_t rows, uint16_t* out, int32_t* present) {
+    FT_TRY(ar_ready(ctx));
+    if (!present) return ft_fail(ctx, FT_ERR_ARG, "ft_test_qkv0_tab: missing argument");
+    *present = ctx->wide_qkv0_tab ? 1 : 0;
+    if (!ctx->wide_qkv0_tab) return FT_OK;
+    const ft_ar_config& c = ctx->c;
+    const size_t n = (size_t)(c.fast_n_head + 2 * c.fast_n_local_heads) * c.fast_head_dim;
+    if (!out || row0 < 0 || rows < 1 || (long)row0 + rows > ctx->fastV) return ft_fail(ctx, FT_ERR_ARG, "ft_test_qkv0_tab: bad row range");
+    FT_HIP(ctx, hipMemcpy(out, ctx->wide_qkv0_tab + (size_t)row0 * n, (size_t)rows * n * sizeof(bf16_t), hipMemcpyDeviceToHost));
+    return FT_OK;
+}
+
+// ------------------------------------------------------------------------------------------ lock-step kernel test hooks
+// (include/fishtts_hip_test.h: ft_test_wide_linear, ft_test_wide_attn).  Host code around the product's own dispatchers
+// wide_gemm and wide_attn on temporaries: nothing here is reached from a frame.
 
 template <typename WT>
 static ft_status test_wide_linear_t(ft_ctx* ctx, int epi, bool vocab_head, int M, int N, int K, const uint16_t* X, const uint16_t* W,

@@ -45,6 +45,40 @@ ft_status ft_test_engine_fault(ft_ctx* ctx, int32_t which, int32_t wg, int32_t s
 ft_status ft_test_sample(ft_ctx* ctx, const float* logits, int32_t cb, const ft_sampling* sp,
                          const int32_t* window, const float* q, int32_t* out_index);
 
+/* Test hook: ONE draw launch of M rows (1 <= M <= max_batch, rows 0 .. M - 1) through the product's own host routine
+ * (engine.hip: enqueue_sample(L, cb, last)) on the context's own buffers, so the choice between sample_small_kernel, sample_block_kernel
+ * and the four-launch draw, the lock-step form (wide_batch / wide_pair of an M-row launch) and the layer-0 q k v table are the
+ * product's.  R = num_codebooks + 1, cap = max_new_tokens + 24, V = vocab_size (cb = 0) or min(1024, codebook_size).
+ * In: logits [M][V]; sp [M]; noise [noise_rows][noise_row_len] in the layout ft_ar_set_noise takes (row = the drawing row's
+ * nf, codebook cb at vocab_size + (cb - 1) fastV) or NULL (the counter-based generator).
+ * In and out, whole, max_batch rows each (the caller puts sentinels wherever a draw must not write, rows M .. included):
+ * tokn, tok [max_batch][R]; seq [max_batch][R][cap]; pos, nf, done [max_batch].
+ * Out: logits_out [max_batch][V]: the M rows as the launch left them, then the 0xFF fill of rows M ..; femb [max_batch][fast_dim]; qkvf [2 ceil16(max_batch)][fast q k v width];
+ * on a context with the lock-step path xo_femb and xo_x [dim / 8][xo_ldm][8] raw 16-bit (xo_ldm = 2 ceil16(max_batch)); cut
+ * [max_batch][8] (the words of SampCut: kstar, nk, all_kept, argmax, Lmax, Mt, Z2, Tc), chunk_cnt, part_idx [max_batch x
+ * ceil(vocab_size / 1024)], row m at m ceil(V / 1024).  All of these are filled with 0xFF bytes before the launch (a NaN in
+ * every float type, -1 as an int), as are the logits rows M .., and the unused rows of the controls.
+ * what: path (0 sample_small_kernel, 1 sample_block_kernel, 2 the four launches) | 4 the octet-major copy went to xo_femb | 8 to
+ * rows xo_pair .. of xo_x (the paired pass) | 16 the q k v row came from the table.
+ * Ends with every slot reset and the context's own noise back, also when a step of the hook fails.  FT_ERR_ARG: M, cb or last out of range, nf outside 0..cap or past the noise block, a noise row
+ * shorter than vocab_size + (num_codebooks - 1) fastV, a missing argument. */
+typedef struct ft_test_draw_io {
+    int32_t M, cb, last, what;
+    const float* logits;
+    const ft_sampling* sp;
+    const float* noise;
+    int64_t noise_rows, noise_row_len;
+    int32_t *tokn, *tok, *seq, *pos, *nf, *done;
+    float *logits_out, *femb, *qkvf;
+    uint16_t *xo_femb, *xo_x;
+    int32_t *cut, *chunk_cnt, *part_idx;
+} ft_test_draw_io;
+ft_status ft_test_draw(ft_ctx* ctx, ft_test_draw_io* io);
+
+/* Test hook: rows [row0, row0 + rows) of the table of fast layer 0's q k v by drawn code (lock-step batches) as raw 16-bit
+ * patterns, [rows][fast q k v width]; *present = 0 and out untouched on a context that built none. */
+ft_status ft_test_qkv0_tab(ft_ctx* ctx, int32_t row0, int32_t rows, uint16_t* out, int32_t* present);
+
 /* Test hook: the resampler of ft_codec_decode_at on a host waveform x of n <= max_frames * frame_len samples at 44100
  * (zeros before and after it) -> y: *n_out = ft_resampled_len(sample_rate, n) samples. */
 ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out);
