@@ -44,6 +44,11 @@ class ft_join_params(C.Structure):
     _fields_ = [("threshold", C.c_float), ("hop", C.c_int32), ("keep", C.c_int32), ("fade", C.c_int32)]
 
 
+class ft_level_info(C.Structure):
+    _fields_ = [("lufs", C.c_double), ("peak", C.c_float), ("gain", C.c_float), ("blocks", C.c_int32), ("gated", C.c_int32),
+                ("capped", C.c_int32)]
+
+
 class ft_sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
                 ("ban_eos", C.c_int32), ("seed", C.c_uint64)]
@@ -106,6 +111,13 @@ SYMBOLS = {
     "ft_join_groups": (C.c_int32, [_P, C.c_int32, C.c_int32, _P]),
     "ft_test_join": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.POINTER(ft_join_params), _P, C.c_int32, _P, C.c_int64,
                                  C.POINTER(C.c_int64), _P]),
+    "ft_level_filter": (C.c_int32, [C.c_int32, _P, _P]),
+    "ft_codec_loudness": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ft_level_info), _P]),
+    "ft_codec_decode_level": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "ft_codec_decode_join_level": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(ft_join_params), _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), _P,
+                                               _P]),
+    "ft_test_level_hops": (C.c_int32, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ft_codec_encode": (C.c_int32, [_P, _P, C.c_int64, _P, _P]),
     "ft_codec_enc_frame_len": (C.c_int32, [_P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),

@@ -17,7 +17,8 @@ With `sample_rate` the streams are `stream(sample_rate)` (their output resampled
 one final flag per chunk: an utterance's last chunk is decoded with final=True, or, when its end is known only after its
 last chunk went out, the stream's `finish()` gives the held-back tail; either way the tail is out before (i, b"").
 `speed` (a speaking rate) and `pitch` (a shift in semitones) are passed through to the streams in the same way:
-`stream(sample_rate, speed=speed, pitch=pitch)`, each keyword only when set."""
+`stream(sample_rate, speed=speed, pitch=pitch)`, each keyword only when set.  A loudness target is refused (ValueError):
+the level stage needs the whole utterance."""
 from __future__ import annotations
 
 import queue
@@ -70,13 +71,13 @@ class ChunkCutter:
         self.done = True
 
 
-def checked_fx(fx=None, sample_rate=None, speed=None, pitch=None):
+def checked_fx(fx=None, sample_rate=None, speed=None, pitch=None, loudness=None):
     """The checked output stages of a call (codec_engine.OutputFx, imported when first needed, as the engines are): `fx`
-    itself where the caller checked already, else the three keywords checked now (ValueError for a bad one)."""
+    itself where the caller checked already, else the keywords checked now (ValueError for a bad one)."""
     if fx is not None:
         return fx
     from .codec_engine import OutputFx
-    return OutputFx.of(sample_rate, speed, pitch)
+    return OutputFx.of(sample_rate, speed, pitch, loudness)
 
 
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
@@ -88,7 +89,7 @@ def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
     raised from the generator."""
     if chunk_tokens < 1 or min_first_chunk < 1:
         raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-    fx = checked_fx(fx, sample_rate, speed, pitch)       # truthy: an output stage holds back a tail
+    fx = checked_fx(fx, sample_rate, speed, pitch).no_level("stream_utterances")   # truthy: an output stage holds back a tail
     cv = threading.Condition()
     cuts = [ChunkCutter(chunk_tokens, min_first_chunk) for _ in range(n)]
     ended = [False] * n                                 # end mark handed out (worker only)

@@ -24,22 +24,43 @@ def _number(v, what: str) -> float:
 
 
 @dataclass(frozen=True)
+class LevelInfo:
+    """What the level stage found in one item (ft_level_info): `lufs` the integrated loudness before the gain (-inf when
+    nothing was measured), `peak` the sample peak before the gain, `gain` the factor applied, `blocks` / `gated` the
+    400 ms blocks and those that passed both gates, `capped` whether the -1 dBFS ceiling bound the gain."""
+    lufs: float
+    peak: float
+    gain: float
+    blocks: int
+    gated: int
+    capped: bool
+
+    @classmethod
+    def of(cls, i: "L.ft_level_info") -> "LevelInfo":
+        return cls(float(i.lufs), float(np.float32(i.peak)), float(np.float32(i.gain)), int(i.blocks), int(i.gated), bool(i.capped))
+
+
+@dataclass(frozen=True)
 class OutputFx:
-    """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent) and `cents` (pitch), each None where the
-    stage is absent - the codec's own rate (None or 44100), the model's own pace (a speed that rounds to 100 percent) and
-    pitch (one that rounds to 0 cents).  Built once per call by of() and handed down to the native call as it is."""
+    """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent), `cents` (pitch) and `level` (loudness
+    target, hundredths of a LUFS), each None where the stage is absent - the codec's own rate (None or 44100), the model's
+    own pace (a speed that rounds to 100 percent), pitch (one that rounds to 0 cents) and level (no loudness given).  Built
+    once per call by of() and handed down to the native call as it is."""
     rate: Optional[int] = None
     pct: Optional[int] = None
     cents: Optional[int] = None
+    level: Optional[int] = None
 
     @classmethod
-    def of(cls, sample_rate=None, speed=None, pitch=None) -> "OutputFx":
+    def of(cls, sample_rate=None, speed=None, pitch=None, loudness=None) -> "OutputFx":
         """A caller's `sample_rate=` (an integer in [8000, 48000] whose reduced L = rate / gcd(rate, 44100) is at most 640:
         ft_resample_filter), `speed=` (a factor in [0.5, 2.0], kept as round(speed * 100): ft_timescaled_len) and `pitch=`
         (semitones in [-12, 12], kept as round(100 * pitch) cents: ft_pitch_filter; a plain shift, formants move with the
         pitch), then the two together (ft_pitch_ok: the time-scale stage under a pitch shift runs at speed / 2^(pitch / 12),
-        which has to lie in [0.5, 2]).  Anything else raises ValueError, before any device work."""
-        rate = pct = cents = None
+        which has to lie in [0.5, 2]), then `loudness=` (a target in LUFS in [-50, -5], kept as round(100 * loudness):
+        ft_codec_loudness; every item is brought to that integrated loudness, its sample peak held at -1 dBFS).  Anything
+        else raises ValueError, before any device work."""
+        rate = pct = cents = level = None
         if sample_rate is not None:
             if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)):
                 raise ValueError(f"sample_rate must be an integer, got {sample_rate!r}")
@@ -61,11 +82,22 @@ class OutputFx:
         if cents is not None and L.load().ft_pitch_ok(100 if pct is None else pct, cents) != L.FT_OK:
             raise ValueError(f"unsupported combination speed={speed!r}, pitch={pitch!r}: speed / 2^(pitch / 12) must lie in "
                              "[0.5, 2.0]")
-        return cls(rate, pct, cents)
+        if loudness is not None:
+            if not -50.0 <= _number(loudness, "loudness must be a number of LUFS") <= -5.0:
+                raise ValueError(f"unsupported loudness {loudness!r}: a target in LUFS in [-50, -5]")
+            level = int(round(float(loudness) * 100))
+        return cls(rate, pct, cents, level)
 
     def __bool__(self) -> bool:
         """Any stage at all: the call goes through the chain's native entry points, a stream holds back a tail."""
-        return self.rate is not None or self.pct is not None or self.cents is not None
+        return self.rate is not None or self.pct is not None or self.cents is not None or self.level is not None
+
+    def no_level(self, what: str) -> "OutputFx":
+        """self, for a call that hands out audio before the utterance has ended: ValueError with a level."""
+        if self.level is not None:
+            raise ValueError(f"loudness needs the whole utterance: {what} hands out audio before its end, and the integrated "
+                             "loudness is known only there")
+        return self
 
     @property
     def emits_empty(self) -> bool:
@@ -83,6 +115,11 @@ class OutputFx:
     def native(self):
         """(sample_rate, speed_pct, pitch_cents) as the native entry points take them."""
         return self.rate or CODEC_RATE, self.pct or 100, self.cents or 0
+
+    @property
+    def native_level(self) -> int:
+        """The level as the native entry points take it: hundredths of a LUFS, 0 without the stage."""
+        return self.level or 0
 
     @property
     def wav_rate(self) -> int:
@@ -351,6 +388,8 @@ class CodecHipEngine:
             raise ValueError("decode_streams: one chunk per stream")
         for c in chunks:
             assert c.ndim == 2 and c.shape[0] == self.R, c.shape
+        for st in streams:
+            st.fx.no_level("decode_streams")
         if final is not None or any(s.fx for s in streams):
             return self._decode_streams_at(streams, chunks, [False] * len(streams) if final is None else list(final))
         out: List[np.ndarray] = []
@@ -386,6 +425,31 @@ class CodecHipEngine:
                 out.append(audio[off:off + int(n)])
                 off += int(n)
         return out
+
+    @property
+    def max_level_samples(self) -> int:
+        """The longest waveform loudness() takes: the longest item a decode gives, max_frames frames at speed 0.5 and 48 kHz."""
+        return -(-2 * int(self.max_frames) * self.frame_len * 48000 // CODEC_RATE)
+
+    def loudness(self, x: np.ndarray, sample_rate: Optional[int] = None, target: Optional[float] = None):
+        """The level stage alone on a host waveform at `sample_rate` (None: the codec's rate), on the device
+        (ft_codec_loudness): measured - integrated loudness per BS.1770, sample peak - and, with `target` (LUFS, as
+        decode's `loudness`), levelled.  Returns (LevelInfo, y): y is x times the one gain, x's own samples without a target."""
+        fx = OutputFx.of(sample_rate=sample_rate, loudness=target)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        y = np.empty(len(x), dtype=np.float32)
+        info = L.ft_level_info()
+        self._check(self.lib.ft_codec_loudness(self._h, x.ctypes.data_as(C.c_void_p), len(x), fx.wav_rate, fx.native_level,
+                                               C.byref(info), y.ctypes.data_as(C.c_void_p)), "ft_codec_loudness")
+        return LevelInfo.of(info), y
+
+    def test_level_hops(self) -> np.ndarray:
+        """Test hook (ft_test_level_hops): the hop sums of the last levelled call."""
+        n = C.c_int64(0)
+        self._check(self.lib.ft_test_level_hops(self._h, None, 0, C.byref(n)), "ft_test_level_hops")
+        e = np.zeros(max(n.value, 1), dtype=np.float64)
+        self._check(self.lib.ft_test_level_hops(self._h, e.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "ft_test_level_hops")
+        return e[:n.value]
 
     def test_resample(self, x: np.ndarray, sample_rate: int) -> np.ndarray:
         """Test hook (ft_test_resample): the resampler alone on a waveform at the codec rate (zeros around it)."""
@@ -459,16 +523,20 @@ class CodecHipEngine:
 
     def decode_join(self, codes_list: Sequence[np.ndarray], sample_rate: Optional[int] = None, speed: Optional[float] = None,
                     pitch: Optional[float] = None, params=(0.0, 1, 0, 0), gaps: Optional[Sequence[int]] = None,
-                    started: bool = False, fx: Optional[OutputFx] = None):
+                    started: bool = False, fx: Optional[OutputFx] = None, loudness: Optional[float] = None,
+                    levels: Optional[list] = None):
         """The utterances of one document - codes_list[i] (n_codebooks+1, T_i) integer - decoded at `sample_rate`, `speed`
         and `pitch` (as decode) and joined on the device into one waveform (ft_codec_decode_join): each trimmed to its
         loud part, faded at the cuts and laid out behind gaps[i] samples of silence.  `params`: (threshold, hop, keep,
         fade), sample counts at the output rate; (0, 1, 0, 0) is plain concatenation with gaps.  `started`: audio of the
         document went out before this call (the first piece then gets its gap too).  Consecutive items go into native
         calls of at most 64 items and max_frames frames (ft_join_groups), `started` carried from call to call, the calls'
-        outputs concatenated here - a piece depends on its own item only, so the grouping does not show.  Returns (audio
-        float32, cuts (n, 2) int64: the samples [a, e) kept of every item)."""
-        fx = OutputFx.of(sample_rate, speed, pitch) if fx is None else fx
+        outputs concatenated here - a piece depends on its own item only, so the grouping does not show.  `loudness` (LUFS,
+        as decode): every item is levelled on its own before the join finds its edges (ft_codec_decode_join_level), so the
+        threshold acts on the levelled samples - an absolute threshold such as synthesize_long's silence_db then means the
+        same for every item; `levels`: a list that receives one LevelInfo per item.  Returns (audio float32, cuts (n, 2)
+        int64: the samples [a, e) kept of every item)."""
+        fx = OutputFx.of(sample_rate, speed, pitch, loudness) if fx is None else fx
         items = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in codes_list]
         for c in items:
             if c.ndim != 2 or c.shape[0] != self.R:
@@ -499,10 +567,20 @@ class CodecHipEngine:
             total = C.c_int64(0)
             gcuts = np.zeros((B, 2), dtype=np.int64)
             ggaps = np.ascontiguousarray(g[i:j])
-            self._check(self.lib.ft_codec_decode_join(
-                self._h, block.ctypes.data_as(C.c_void_p), B, T, glens.ctypes.data_as(C.c_void_p),
-                *fx.native, C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0, audio.ctypes.data_as(C.c_void_p), cap,
-                C.byref(total), gcuts.ctypes.data_as(C.c_void_p)), "ft_codec_decode_join")
+            if fx.level is None:
+                self._check(self.lib.ft_codec_decode_join(
+                    self._h, block.ctypes.data_as(C.c_void_p), B, T, glens.ctypes.data_as(C.c_void_p),
+                    *fx.native, C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0, audio.ctypes.data_as(C.c_void_p), cap,
+                    C.byref(total), gcuts.ctypes.data_as(C.c_void_p)), "ft_codec_decode_join")
+            else:
+                infos = (L.ft_level_info * B)()
+                self._check(self.lib.ft_codec_decode_join_level(
+                    self._h, block.ctypes.data_as(C.c_void_p), B, T, glens.ctypes.data_as(C.c_void_p),
+                    *fx.native, fx.native_level, C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0,
+                    audio.ctypes.data_as(C.c_void_p), cap, C.byref(total), gcuts.ctypes.data_as(C.c_void_p), infos),
+                    "ft_codec_decode_join_level")
+                if levels is not None:
+                    levels.extend(LevelInfo.of(i) for i in infos)
             out.append(audio[:total.value])
             cuts[i:j] = gcuts
             begun = begun or total.value > 0
@@ -510,14 +588,16 @@ class CodecHipEngine:
         return (np.concatenate(out) if out else np.zeros(0, dtype=np.float32)), cuts
 
     def decode(self, codes: np.ndarray, lens: Optional[np.ndarray] = None, sample_rate: Optional[int] = None,
-               speed: Optional[float] = None, pitch: Optional[float] = None, fx: Optional[OutputFx] = None) -> np.ndarray:
+               speed: Optional[float] = None, pitch: Optional[float] = None, fx: Optional[OutputFx] = None,
+               loudness: Optional[float] = None, levels: Optional[list] = None) -> np.ndarray:
         """codes (B, n_codebooks+1, T) or (n_codebooks+1, T) integer -> float32 (B, T*frame_len).
         `sample_rate`, `speed`, `pitch` (OutputFx.of), or `fx`, the checked value itself: (B, max_b fx.out_len(lens[b] *
         frame_len)); row b holds its fx.out_len samples, zeros after them.
         `sample_rate`: resampled on the device.  `speed`: time-scaled on the device (before the resampler).
         `pitch` (semitones): pitch-shifted on the device, between the two; a plain shift (formants move with the pitch)
-        that leaves every length as it is."""
-        fx = OutputFx.of(sample_rate, speed, pitch) if fx is None else fx
+        that leaves every length as it is.  `loudness` (LUFS): every row is brought to that integrated loudness on the
+        device, behind the other stages (ft_codec_decode_level); `levels`: a list that receives one LevelInfo per row."""
+        fx = OutputFx.of(sample_rate, speed, pitch, loudness) if fx is None else fx
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
@@ -529,6 +609,15 @@ class CodecHipEngine:
             width = max(fx.out_len(int(n) * self.frame_len) for n in lens_a)
             audio = np.empty((B, max(width, 1)), dtype=np.float32)
             out_lens = np.zeros(B, dtype=np.int64)
+            if fx.level is not None:
+                infos = (L.ft_level_info * B)()
+                self._check(self.lib.ft_codec_decode_level(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
+                                                           lens_a.ctypes.data_as(C.c_void_p), *fx.native, fx.native_level,
+                                                           audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p),
+                                                           infos), "ft_codec_decode_level")
+                if levels is not None:
+                    levels.extend(LevelInfo.of(i) for i in infos)
+                return audio[:, :width]
             self._check(self.lib.ft_codec_decode_fxp(self._h, codes.ctypes.data_as(C.c_void_p), B, T,
                                                      lens_a.ctypes.data_as(C.c_void_p), *fx.native,
                                                      audio.ctypes.data_as(C.c_void_p), out_lens.ctypes.data_as(C.c_void_p)),
@@ -549,7 +638,7 @@ class CodecStream:
     def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                  pitch: Optional[float] = None, fx: Optional[OutputFx] = None):
         self.engine = engine
-        self.fx = OutputFx.of(sample_rate, speed, pitch) if fx is None else fx    # falsy: no output stage, nothing held back
+        self.fx = (OutputFx.of(sample_rate, speed, pitch) if fx is None else fx).no_level("a codec stream")   # falsy: no output stage, nothing held back
         self._h = C.c_void_p()
         if not self.fx:
             engine._check(engine.lib.ft_codec_stream_begin(engine._h, C.byref(self._h)), "ft_codec_stream_begin")

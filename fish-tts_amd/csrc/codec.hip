@@ -19,8 +19,12 @@ using namespace ft;
 using chain::ChainPlan; using chain::FxDesc; using chain::StageChain; using chain::StagePlan;
 using chain::RS_FI; using chain::RS_MAX_RATE;
 static_assert(chain::RS_LDS == RS_LDS && chain::TS_N == TS_N && chain::TS_HS == TS_HS && chain::TS_D == TS_D &&
-              chain::TS_CARRY == TS_CARRY && chain::PS_SHIFT == PS_SHIFT && chain::PS_PHASES == PS_PHASES,
+              chain::TS_CARRY == TS_CARRY && chain::PS_SHIFT == PS_SHIFT && chain::PS_PHASES == PS_PHASES &&
+              chain::LV_WARM_HOPS == LV_WARM,
               "fx_chain.h and codec_kernels.h disagree");
+static_assert(sizeof(ft_level_info) == 32 && offsetof(LevelItem, L) + sizeof(ft_level_info) == sizeof(LevelItem) &&
+              offsetof(ft_level_info, peak) == 8 && offsetof(ft_level_info, capped) == 24,
+              "ft_level_info is the tail of a LevelItem");
 
 #define FT_TRY(x) do { ft_status s_ = (x); if (s_ != FT_OK) return s_; } while (0)
 
@@ -89,6 +93,14 @@ struct CodecState {
     float *join_in = nullptr, *join_out = nullptr;
     size_t join_in_cap = 0, join_out_cap = 0;
     JoinTab* join_tab = nullptr;
+    // level stage (ft_codec_loudness, ft_codec_decode_level, ft_codec_decode_join_level): the item table, one hop sum and
+    // one hop peak per 100 ms of a call's items, the host copies of the table on its way there and back, and the waveform
+    // of ft_codec_loudness; allocated on the first levelled call (the buffers grow when a later call needs more)
+    LevelTab* lv_tab = nullptr;
+    double* lv_hops = nullptr;
+    float *lv_peaks = nullptr, *lv_x = nullptr;
+    size_t lv_cap = 0, lv_xcap = 0, lv_nhops = 0;
+    std::vector<char> lv_up, lv_down;
     // ---- encode side
     struct EncUnit { float *a0, *a2; ConvW c7, c1; };
     struct EncBlock { EncUnit u[3]; float* a3; ConvW sc; int s, cin, cout; std::vector<TfLayer> tf; float* tf_norm = nullptr; };
@@ -819,6 +831,85 @@ static ft_status ps_alloc(ft_ctx* ctx) {
     return FT_OK;
 }
 
+// ---- level stage (LevelTab and the three kernels in codec_kernels.h; fishtts_hip.h states it, fx_chain.h designs it)
+struct LevelJob { int rate = 0, target = 0; ft_level_info* info = nullptr; };   // the level of a one-item call (call_tail)
+
+// A device buffer of at least `need` elements: allocated on first use, replaced by a larger one when a call needs more.
+template <typename T>
+static ft_status cgrow(ft_ctx* ctx, T** p, size_t* cap, size_t need) {
+    CodecState* s = ctx->codec;
+    if (*p && *cap >= need) return FT_OK;
+    T* q = nullptr;
+    FT_TRY(cmalloc(ctx, &q, need + 4));
+    if (*p) {
+        s->owned.erase(std::find(s->owned.begin(), s->owned.end(), (void*)*p));
+        hipFree(*p);
+    }
+    *p = q;
+    *cap = need;
+    return FT_OK;
+}
+
+static size_t level_hops(long long n, int rate) { return (size_t)((n + chain::lv_hop(rate) - 1) / chain::lv_hop(rate)); }
+
+// The table, and room for `hops` hop sums and peaks.
+static ft_status level_alloc(ft_ctx* ctx, size_t hops) {
+    CodecState* s = ctx->codec;
+    if (!s->lv_tab) FT_TRY(cmalloc(ctx, &s->lv_tab, (size_t)1));
+    size_t cap = s->lv_cap;
+    FT_TRY(cgrow(ctx, &s->lv_hops, &cap, std::max(hops, (size_t)4)));
+    cap = s->lv_cap;
+    FT_TRY(cgrow(ctx, &s->lv_peaks, &cap, std::max(hops, (size_t)4)));
+    s->lv_cap = cap;
+    return FT_OK;
+}
+
+// Levels B items in place (x[b], n[b] samples at `rate`, written earlier on the codec's stream): the three launches (two
+// when the call only measures: target 0, or `scale` false) and the copy of the table back to the host.  The caller has
+// called level_alloc for the items' hops, synchronizes, and then reads the results with level_fetch.
+static ft_status level_enqueue(ft_ctx* ctx, int B, float* const* x, const int64_t* n, int rate, int target, bool scale = true) {
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    s->lv_up.assign(sizeof(LevelTab), 0);
+    LevelTab* h = (LevelTab*)s->lv_up.data();
+    chain::lv_design(rate, h->c);
+    h->ceiling = chain::lv_ceiling();
+    h->H = chain::lv_hop(rate);
+    h->target = target;
+    h->B = B;
+    long long hop0 = 0, most = 0, widest = 0;
+    for (int b = 0; b < B; ++b) {
+        LevelItem& it = h->it[b];
+        it.x = x[b];
+        it.n = n[b];
+        it.hop0 = hop0;
+        const long long nh = (long long)level_hops(n[b], rate);
+        hop0 += nh;
+        most = std::max(most, nh);
+        widest = std::max(widest, (long long)n[b]);
+    }
+    if ((size_t)hop0 > s->lv_cap) return ft_fail(ctx, FT_ERR_STATE, "level: hop buffers too small");
+    s->lv_nhops = (size_t)hop0;
+    const size_t used = offsetof(LevelTab, it) + (size_t)B * sizeof(LevelItem);
+    FT_HIP(ctx, hipMemcpyAsync(s->lv_tab, h, used, hipMemcpyHostToDevice, st));
+    const int gf = (int)std::max(1LL, (most + LV_FILTER_THREADS - 1) / LV_FILTER_THREADS);
+    level_filter_kernel<<<dim3(gf, 1, B), LV_FILTER_THREADS, 0, st>>>(s->lv_tab, s->lv_hops, s->lv_peaks);
+    level_gain_kernel<<<B, LV_GAIN_THREADS, 0, st>>>(s->lv_tab, s->lv_hops, s->lv_peaks);
+    if (scale && target != 0) {
+        const int gx = (int)std::max(1LL, std::min(1024LL, (widest + LV_SCALE_THREADS - 1) / LV_SCALE_THREADS));
+        level_scale_kernel<<<dim3(gx, 1, B), LV_SCALE_THREADS, 0, st>>>(s->lv_tab);
+    }
+    s->lv_down.resize(sizeof(LevelTab));
+    FT_HIP(ctx, hipMemcpyAsync(s->lv_down.data(), s->lv_tab, used, hipMemcpyDeviceToHost, st));
+    return FT_OK;
+}
+
+// The results of the last level_enqueue, once the stream was synchronized.
+static void level_fetch(CodecState* s, int B, ft_level_info* infos) {
+    const LevelTab* h = (const LevelTab*)s->lv_down.data();
+    for (int b = 0; infos && b < B; ++b) memcpy(&infos[b], &h->it[b].L, sizeof(ft_level_info));
+}
+
 struct Fx {   // the output stages of a call: resampler segments, and the time-scale and pitch segments in front of some of them
     std::vector<RsSeg> rs;
     std::vector<TsSeg> ts;
@@ -863,8 +954,9 @@ static ft_status ps_enqueue(ft_ctx* ctx, std::vector<PsSeg>& segs, std::vector<R
 
 // Resamples `segs` (their inputs written earlier on the codec's stream) into rs_out, back to back, and queues the copy of
 // all their outputs to `host` (`kind`: a joined call names a device buffer there); the caller synchronizes (and keeps `segs`
-// alive until then).
-static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host, hipMemcpyKind kind = hipMemcpyDeviceToHost) {
+// alive until then).  `lv`: the call's one item is levelled in rs_out before the copy.
+static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host, hipMemcpyKind kind = hipMemcpyDeviceToHost,
+                            const LevelJob* lv = nullptr) {
     CodecState* s = ctx->codec;
     hipStream_t st = s->stream;
     long long off = 0, mx = 0;
@@ -876,6 +968,10 @@ static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host, 
     FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, segs.data(), segs.size() * sizeof(RsSeg), hipMemcpyHostToDevice, st));
     const int gx = (int)std::max(1LL, std::min(2048LL, (mx + RS_THREADS - 1) / RS_THREADS));
     resample_kernel<<<dim3(gx, 1, (unsigned)segs.size()), RS_THREADS, 0, st>>>(s->rs_seg);
+    if (lv) {
+        const int64_t n = off;
+        FT_TRY(level_enqueue(ctx, 1, &s->rs_out, &n, lv->rate, lv->target));
+    }
     if (off > 0) FT_HIP(ctx, hipMemcpyAsync(host, s->rs_out, (size_t)off * sizeof(float), kind, st));
     return FT_OK;
 }
@@ -1039,18 +1135,26 @@ static bool decode_chain(ft_ctx* ctx, const Layout& L) {
 
 // The end of a call that leaves samples: the time-scale stage and the resampler over `fx` (inputs written earlier on the stream) or the
 // plain copy of `plain` floats of s->audio, the call's one synchronize and the launch check; then every stream named moves
-// on by its chunk.  `kind`: where `host` lies (ft_codec_decode_join leaves its items on the device).
+// on by its chunk.  `kind`: where `host` lies (ft_codec_decode_join leaves its items on the device).  `lv`: the level stage
+// over the call's one item, behind the last stage and in front of the copy; its result is in lv->info afterwards.
 static ft_status call_tail(ft_ctx* ctx, Fx* fx, float* host, size_t plain, const char* what, int n = 0,
                            ft_codec_stream* const* scs = nullptr, const int32_t* lens = nullptr,
-                           hipMemcpyKind kind = hipMemcpyDeviceToHost) {
+                           hipMemcpyKind kind = hipMemcpyDeviceToHost, const LevelJob* lv = nullptr) {
     CodecState* s = ctx->codec;
     if (fx && !fx->ts.empty()) FT_TRY(ts_enqueue(ctx, *fx));
     if (fx && !fx->ps.empty()) FT_TRY(ps_enqueue(ctx, fx->ps, fx->rs));
-    if (fx) FT_TRY(rs_enqueue(ctx, fx->rs, host, kind));
-    else FT_HIP(ctx, hipMemcpyAsync(host, s->audio, plain * sizeof(float), kind, s->stream));
+    if (fx) FT_TRY(rs_enqueue(ctx, fx->rs, host, kind, lv));
+    else {
+        if (lv) {
+            const int64_t np = (int64_t)plain;
+            FT_TRY(level_enqueue(ctx, 1, &s->audio, &np, lv->rate, lv->target));
+        }
+        FT_HIP(ctx, hipMemcpyAsync(host, s->audio, plain * sizeof(float), kind, s->stream));
+    }
     FT_HIP(ctx, hipStreamSynchronize(s->stream));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string(what) + hipGetErrorString(e));
+    if (lv) level_fetch(s, 1, lv->info);
     for (int j = 0; j < n; ++j) {
         scs[j]->t0 += lens[j];
         scs[j]->par ^= 1;
@@ -1061,9 +1165,9 @@ static ft_status call_tail(ft_ctx* ctx, Fx* fx, float* host, size_t plain, const
 // The chain over L and the end of the call; `who` names the caller in the message of a carry list out of step.
 static ft_status decode_run(ft_ctx* ctx, const Layout& L, Fx* rs, float* audio_host, int n,
                             ft_codec_stream* const* scs, const int32_t* lens, const char* who,
-                            hipMemcpyKind kind = hipMemcpyDeviceToHost) {
+                            hipMemcpyKind kind = hipMemcpyDeviceToHost, const LevelJob* lv = nullptr) {
     const bool in_step = decode_chain(ctx, L);
-    FT_TRY(call_tail(ctx, rs, audio_host, (size_t)L.total * ctx->codec->frame_len, "codec launch: ", in_step ? n : 0, scs, lens, kind));
+    FT_TRY(call_tail(ctx, rs, audio_host, (size_t)L.total * ctx->codec->frame_len, "codec launch: ", in_step ? n : 0, scs, lens, kind, lv));
     if (!in_step) return ft_fail(ctx, FT_ERR_STATE, std::string(who) + ": carry bookkeeping out of step");
     return FT_OK;
 }
@@ -1078,7 +1182,7 @@ static void stream_carries(const ft_codec_stream* sc, bf16_t** out) {
 // stream.  `rs`: resample the waveform (segment 0 reads s->audio) and copy the resampled samples instead.  `kind`: the copy
 // that delivers the samples (device to device when audio_host is the join stage's input buffer).
 static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, int T, float* audio_host, ft_codec_stream* sc = nullptr,
-                            Fx* rs = nullptr, hipMemcpyKind kind = hipMemcpyDeviceToHost) {
+                            Fx* rs = nullptr, hipMemcpyKind kind = hipMemcpyDeviceToHost, const LevelJob* lv = nullptr) {
     const ft_codec_config& c = ctx->cc;
     CodecState* s = ctx->codec;
     const int HD = c.tf_n_head * c.tf_head_dim, R = c.n_codebooks + 1, W1 = c.tf_window - 1;
@@ -1102,7 +1206,7 @@ static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, i
     std::vector<int> hc((size_t)R * T);
     for (int r = 0; r < R; ++r) memcpy(&hc[(size_t)r * T], codes_host + (size_t)r * Tfull, T * sizeof(int));
     FT_HIP(ctx, hipMemcpyAsync(s->codes, hc.data(), hc.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    return decode_run(ctx, L, rs, audio_host, sc ? 1 : 0, &sc, &T, "codec stream", kind);
+    return decode_run(ctx, L, rs, audio_host, sc ? 1 : 0, &sc, &T, "codec stream", kind, lv);
 }
 
 // Streamed decode (second half): successive chunks of one utterance's codes, each decoded with
@@ -1345,9 +1449,10 @@ static bool item_stages(CodecState* s, const FxDesc& d, long long n_in, Fx& g) {
 }
 
 // The items of ft_codec_decode / ft_codec_decode_fxp, one after the other through the chain `d`: item b's samples go to
-// audio + b * stride, zeros behind them.
+// audio + b * stride, zeros behind them.  With a level (d.level), every item is levelled before its copy; infos[b] (infos
+// may be null) receives what the stage found, an item without samples the result of an empty one.
 static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int B, int T, const int32_t* lens, float* audio,
-                              size_t stride, const FxDesc& d, int64_t* out_lens) {
+                              size_t stride, const FxDesc& d, int64_t* out_lens, ft_level_info* infos = nullptr) {
     CodecState* s = ctx->codec;
     const int R = ctx->cc.n_codebooks + 1;
     for (int b = 0; b < B; ++b) {
@@ -1358,10 +1463,15 @@ static ft_status decode_items(ft_ctx* ctx, const std::string& fn, const int32_t*
         float* out = audio + (size_t)b * stride;
         if (out_lens) out_lens[b] = (int64_t)n_out;
         if (n_out < stride) memset(out + n_out, 0, (stride - n_out) * sizeof(float));
+        ft_level_info info = {-INFINITY, 0.f, 1.f, 0, 0, 0};
+        if (infos) infos[b] = info;
         if (Tb == 0) continue;
         Fx g;
         const bool staged = item_stages(s, d, n_in, g);
-        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, staged ? &g : nullptr));
+        const LevelJob lv{d.rate, d.level, &info};
+        FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, out, nullptr, staged ? &g : nullptr, hipMemcpyDeviceToHost,
+                          d.level != 0 ? &lv : nullptr));
+        if (infos) infos[b] = info;
     }
     return FT_OK;
 }
@@ -1398,24 +1508,27 @@ extern "C" int64_t ft_resampled_len(int32_t sample_rate, int64_t n_in) {
 }
 
 // A call's chain from its three values, judged without a lock and before anything else: the rate, then the speed, then
-// the cents, then the pair.  `fn` names the entry point in the message.
-static ft_status fx_refuse(ft_ctx* ctx, const std::string& fn, int rate, int pct, int cents, FxDesc* d) {
+// the cents, then the pair, then the level.  `fn` names the entry point in the message.
+static ft_status fx_refuse(ft_ctx* ctx, const std::string& fn, int rate, int pct, int cents, FxDesc* d, int level = 0) {
     const char* why = nullptr;
-    switch (d->make(rate, pct, cents, &why)) {
+    switch (d->make(rate, pct, cents, level, &why)) {
     case FxDesc::RATE: return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why + " (" + std::to_string(rate) + ")");
     case FxDesc::SPEED: return ft_fail(ctx, FT_ERR_ARG, fn + ": speed outside [50, 200] percent (" + std::to_string(pct) + ")");
     case FxDesc::CENTS: return ft_fail(ctx, FT_ERR_ARG, fn + ": pitch outside [-1200, 1200] cents (" + std::to_string(cents) + ")");
     case FxDesc::PAIR:
         return ft_fail(ctx, FT_ERR_ARG, fn + ": speed / pitch ratio outside [0.5, 2] (speed " + std::to_string(pct) + " percent, " +
                                             std::to_string(cents) + " cents)");
+    case FxDesc::LEVEL:
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": loudness outside [-5000, -500] hundredths of a LUFS (" + std::to_string(level) + ")");
     case FxDesc::OK: break;
     }
     return FT_OK;
 }
 
 // The chain's device side; the caller holds s->mu.  The tables of its rate and cents, and the buffers of the first stage it
-// has (each stage's allocation brings those of the stages behind it).
-static ft_status fx_prepare(ft_ctx* ctx, FxDesc* d) {
+// has (each stage's allocation brings those of the stages behind it); with a level, the level stage's table and `hops` hop sums.
+static ft_status fx_prepare(ft_ctx* ctx, FxDesc* d, size_t hops = 0) {
+    if (d->level != 0) FT_TRY(level_alloc(ctx, hops));
     FT_TRY(rs_table(ctx, d->rate, &d->rs));
     if (d->cents != 0) {
         FT_TRY(ps_table(ctx, d->cents, &d->ps));
@@ -1443,10 +1556,11 @@ extern "C" ft_status ft_pitch_filter(int32_t cents, int64_t* step, int32_t* K, f
 extern "C" ft_status ft_pitch_ok(int32_t speed_pct, int32_t cents) { return chain::fx_plan(speed_pct, cents, nullptr) ? FT_OK : FT_ERR_ARG; }
 
 static ft_status decode_fx(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
-                           int32_t sample_rate, int32_t pct, float* audio, int64_t* out_lens, int32_t cents = 0) {
+                           int32_t sample_rate, int32_t pct, float* audio, int64_t* out_lens, int32_t cents = 0, int32_t level = 0,
+                           ft_level_info* infos = nullptr) {
     if (!ctx) return FT_ERR_ARG;
     FxDesc d;
-    FT_TRY(fx_refuse(ctx, fn, sample_rate, pct, cents, &d));
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, pct, cents, &d, level));
     FT_TRY(codec_ready(ctx));
     if (!codes || !audio || !out_lens || B < 1 || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
     if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
@@ -1459,8 +1573,8 @@ static ft_status decode_fx(ft_ctx* ctx, const std::string& fn, const int32_t* co
     }
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    FT_TRY(fx_prepare(ctx, &d));
-    return decode_items(ctx, fn, codes, B, T, lens, audio, (size_t)stride, d, out_lens);
+    FT_TRY(fx_prepare(ctx, &d, level_hops(stride, d.rate)));     // (one item at a time: the longest one's hops)
+    return decode_items(ctx, fn, codes, B, T, lens, audio, (size_t)stride, d, out_lens, infos);
 }
 
 extern "C" ft_status ft_codec_decode_at(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
@@ -1476,6 +1590,60 @@ extern "C" ft_status ft_codec_decode_fx(ft_ctx* ctx, const int32_t* codes, int32
 extern "C" ft_status ft_codec_decode_fxp(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
                                          int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, float* audio, int64_t* out_lens) {
     return decode_fx(ctx, "ft_codec_decode_fxp", codes, B, T, lens, sample_rate, speed_pct, audio, out_lens, pitch_cents);
+}
+
+extern "C" ft_status ft_codec_decode_level(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                           int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t loudness, float* audio,
+                                           int64_t* out_lens, ft_level_info* infos) {
+    return decode_fx(ctx, "ft_codec_decode_level", codes, B, T, lens, sample_rate, speed_pct, audio, out_lens, pitch_cents, loudness, infos);
+}
+
+// ---- level stage alone (fishtts_hip.h: ft_level_filter, ft_codec_loudness; fishtts_hip_test.h: ft_test_level_hops)
+extern "C" ft_status ft_level_filter(int32_t sample_rate, double* coeffs, int32_t* hop) {
+    int l = 1, m = 1, k = 0;
+    if (chain::rs_design(sample_rate, &l, &m, &k, nullptr)) return FT_ERR_ARG;
+    if (coeffs) chain::lv_design(sample_rate, coeffs);
+    if (hop) *hop = chain::lv_hop(sample_rate);
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_loudness(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, int32_t target,
+                                       ft_level_info* info, float* y) {
+    const std::string fn = "ft_codec_loudness";
+    if (!ctx) return FT_ERR_ARG;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d, target));
+    FT_TRY(codec_ready(ctx));
+    if ((!x && n > 0) || !info || n < 0) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    CodecState* s = ctx->codec;
+    // the longest item a decode can give: max_frames of audio at speed 0.5 and the highest rate
+    const int64_t most = (2 * (int64_t)ctx->cc.max_frames * s->frame_len * RS_MAX_RATE + RS_FI - 1) / RS_FI;
+    if (n > most) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": longer than the longest item a decode gives");
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    FT_TRY(level_alloc(ctx, level_hops(n, sample_rate)));
+    FT_TRY(cgrow(ctx, &s->lv_x, &s->lv_xcap, (size_t)std::max(n, (int64_t)4)));
+    if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->lv_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    FT_TRY(level_enqueue(ctx, 1, &s->lv_x, &n, sample_rate, target, y != nullptr));
+    if (y && n > 0) FT_HIP(ctx, hipMemcpyAsync(y, s->lv_x, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    FT_HIP(ctx, hipStreamSynchronize(s->stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("level launch: ") + hipGetErrorString(e));
+    level_fetch(s, 1, info);
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_level_hops(ft_ctx* ctx, double* hops, int64_t capacity, int64_t* count) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!count || (capacity > 0 && !hops)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_level_hops: bad argument");
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    *count = (int64_t)s->lv_nhops;
+    const size_t k = std::min((size_t)std::max(capacity, (int64_t)0), s->lv_nhops);
+    if (k > 0) FT_HIP(ctx, hipMemcpy(hops, s->lv_hops, k * sizeof(double), hipMemcpyDeviceToHost));
+    return FT_OK;
 }
 
 // ---- join stage (fishtts_hip.h: ft_codec_decode_join; JoinTab and the three kernels in codec_kernels.h, the argument
@@ -1548,14 +1716,15 @@ extern "C" int32_t ft_join_groups(const int32_t* lens, int32_t n, int32_t max_fr
     return join_groups(lens, n, max_frames, ends);
 }
 
-extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
-                                          int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, const ft_join_params* jp,
-                                          const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
-                                          int64_t* cuts) {
-    const std::string fn = "ft_codec_decode_join";
+// ft_codec_decode_join and ft_codec_decode_join_level: the items decoded one after the other into join_in, levelled there in one
+// go (the item is a grid dimension) when the call has a level, then joined.
+static ft_status decode_join(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                             int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t level, const ft_join_params* jp,
+                             const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
+                             int64_t* cuts, ft_level_info* infos) {
     if (!ctx) return FT_ERR_ARG;
     FxDesc d;
-    FT_TRY(fx_refuse(ctx, fn, sample_rate, speed_pct, pitch_cents, &d));
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, speed_pct, pitch_cents, &d, level));
     FT_TRY(codec_ready(ctx));
     if (!codes || !audio || !total || !cuts || B < 1 || B > JOIN_MAX_ITEMS || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
     if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
@@ -1573,7 +1742,9 @@ extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int
     const int64_t in_floats = join_offsets(B, n, off);
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    FT_TRY(fx_prepare(ctx, &d));
+    size_t hops = 0;
+    for (int b = 0; b < B; ++b) hops += level_hops(n[b], d.rate);
+    FT_TRY(fx_prepare(ctx, &d, hops));
     FT_TRY(join_alloc(ctx, (size_t)in_floats, (size_t)need));
     // the items as decode_items runs them (one synchronize each, as there), their samples left side by side in join_in
     for (int b = 0; b < B; ++b) {
@@ -1583,7 +1754,30 @@ extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int
         const bool staged = item_stages(s, d, (long long)Tb * s->frame_len, g);
         FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, s->join_in + off[b], nullptr, staged ? &g : nullptr, hipMemcpyDeviceToDevice));
     }
-    return join_run(ctx, B, n, off, jp, gaps, started, audio, total, cuts, need, false);
+    if (d.level != 0) {
+        float* x[JOIN_MAX_ITEMS];
+        for (int b = 0; b < B; ++b) x[b] = s->join_in + off[b];
+        FT_TRY(level_enqueue(ctx, B, x, n, d.rate, d.level));
+    }
+    FT_TRY(join_run(ctx, B, n, off, jp, gaps, started, audio, total, cuts, need, false));
+    if (d.level != 0) level_fetch(s, B, infos);
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                          int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, const ft_join_params* jp,
+                                          const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
+                                          int64_t* cuts) {
+    return decode_join(ctx, "ft_codec_decode_join", codes, B, T, lens, sample_rate, speed_pct, pitch_cents, 0, jp, gaps, started,
+                       audio, capacity, total, cuts, nullptr);
+}
+
+extern "C" ft_status ft_codec_decode_join_level(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                                int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t loudness,
+                                                const ft_join_params* jp, const int64_t* gaps, int32_t started, float* audio,
+                                                int64_t capacity, int64_t* total, int64_t* cuts, ft_level_info* infos) {
+    return decode_join(ctx, "ft_codec_decode_join_level", codes, B, T, lens, sample_rate, speed_pct, pitch_cents, loudness, jp, gaps,
+                       started, audio, capacity, total, cuts, infos);
 }
 
 extern "C" ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, const int64_t* n, const ft_join_params* jp,

@@ -1859,4 +1859,156 @@ static __global__ __launch_bounds__(JOIN_THREADS) void join_assemble_kernel(cons
     }
 }
 
+// ---- level stage (ft_codec_loudness, ft_codec_decode_level, ft_codec_decode_join_level; stated in fishtts_hip.h): the items
+// of a call - whole utterances at the output rate, left on the device by the stages above - each measured (BS.1770
+// integrated loudness, sample peak) and multiplied by one gain, in place.  Three launches whatever the number of items (the
+// item is blockIdx.z of a device table):
+//   level_filter_kernel   one lane per hop of H samples: it runs the two K-weighting biquads in float64 from zero state
+//                         LV_WARM hops before its own (or from sample 0) and leaves the sum of z^2 and the peak of |x| over
+//                         its hop.  No scan and no hand-over of state: the high-pass's double pole has decayed by e^-48
+//                         over the 0.2 s of warm-up at every rate.  A lane's sum runs over its samples ascending, so the
+//                         hop sums do not depend on the grid.  Lanes of a wave read streams H samples apart (each lane
+//                         its own cache lines), 16 samples at a time, the next 16 loaded while these are filtered; the
+//                         launch is bound by the serial recursion, 3 H steps per lane, not by memory.  One wave per
+//                         workgroup, so that the waves of an item spread over the CUs.
+//   level_gain_kernel     one workgroup per item: the peak, the 400 ms blocks from four hop sums each, the absolute and the
+//                         relative gate, L and the gain.  Per-thread partial sums over blocks j = t, t + 256, ..., then
+//                         added by thread 0 in thread order: the same bits on every call.
+//   level_scale_kernel    x[i] = g x[i], one float32 multiply (not launched when the call only measures)
+struct LevelItem {
+    float* x;                  // the item's samples (device), levelled in place
+    long long n;
+    long long hop0;            // its first hop sum / hop peak in the two hop buffers
+    double L;                  // out, in the layout of ft_level_info from here on: integrated loudness (-inf: nothing measured)
+    float p, g;                // out: sample peak, gain
+    int blocks, gated, capped; // out: 400 ms blocks, those that passed both gates, whether the ceiling bound the gain
+    int pad;
+};
+struct LevelTab {
+    double c[10];              // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2
+    double ceiling;            // 10^(-1/20)
+    int H, target, B, pad;     // hop; target in hundredths of a LUFS (0: measure only)
+    LevelItem it[64];
+};
+constexpr int LV_WARM = 2, LV_CHUNK = 16, LV_FILTER_THREADS = 64, LV_GAIN_THREADS = 256, LV_SCALE_THREADS = 256;
+
+__device__ inline void level_load(const float* x, long long i, long long end, float* v) {
+#pragma unroll
+    for (int k = 0; k < LV_CHUNK; ++k) v[k] = i + k < end ? x[i + k] : 0.f;
+}
+
+static __global__ __launch_bounds__(LV_FILTER_THREADS) void level_filter_kernel(const LevelTab* tab, double* hops, float* peaks) {
+    const LevelItem& it = tab->it[blockIdx.z];
+    const long long n = it.n, H = tab->H, nh = (n + H - 1) / H;
+    const double b0 = tab->c[0], b1 = tab->c[1], b2 = tab->c[2], a1 = tab->c[3], a2 = tab->c[4];
+    const double d0 = tab->c[5], d1 = tab->c[6], d2 = tab->c[7], e1 = tab->c[8], e2 = tab->c[9];
+    const float* x = it.x;
+    for (long long h = (long long)blockIdx.x * LV_FILTER_THREADS + threadIdx.x; h < nh; h += (long long)gridDim.x * LV_FILTER_THREADS) {
+        const long long s0 = h * H, s1 = min(n, s0 + H), w0 = max(0LL, s0 - LV_WARM * H);
+        double u1 = 0.0, u2 = 0.0, v1 = 0.0, v2 = 0.0, acc = 0.0;   // the two filters' states (transposed direct form II)
+        float pk = 0.f;
+        float cur[LV_CHUNK], nxt[LV_CHUNK];
+        level_load(x, w0, s1, cur);
+        for (long long i = w0; i < s1; i += LV_CHUNK) {
+            level_load(x, i + LV_CHUNK, s1, nxt);
+#pragma unroll
+            for (int k = 0; k < LV_CHUNK; ++k) {
+                const long long q = i + k;
+                const float xf = cur[k];
+                const double xv = (double)xf;
+                const double y = fma(b0, xv, u1);
+                u1 = fma(b1, xv, fma(-a1, y, u2));
+                u2 = fma(b2, xv, -a2 * y);
+                const double z = fma(d0, y, v1);
+                v1 = fma(d1, y, fma(-e1, z, v2));
+                v2 = fma(d2, y, -e2 * z);
+                if (q >= s0 && q < s1) {
+                    acc = fma(z, z, acc);
+                    pk = fmaxf(pk, fabsf(xf));
+                }
+                cur[k] = nxt[k];
+            }
+        }
+        hops[it.hop0 + h] = acc;
+        peaks[it.hop0 + h] = pk;
+    }
+}
+
+// Block j of an item with `whole` whole hops: four hop sums, or (fewer than four whole hops) everything the item has.
+__device__ inline double level_block(const double* e, long long j, long long whole, long long nh, long long n, int H) {
+    if (whole >= 4) return (e[j] + e[j + 1] + e[j + 2] + e[j + 3]) / (4.0 * (double)H);
+    double s = 0.0;
+    for (long long h = 0; h < nh; ++h) s += e[h];
+    return s / (double)n;
+}
+__device__ inline double level_lufs(double E) { return -0.691 + 10.0 * log10(E); }
+
+static __global__ __launch_bounds__(LV_GAIN_THREADS) void level_gain_kernel(LevelTab* tab, const double* hops, const float* peaks) {
+    LevelItem& it = tab->it[blockIdx.x];
+    const int H = tab->H, t = threadIdx.x;
+    const long long n = it.n, nh = (n + H - 1) / H, whole = n / H, nb = whole >= 4 ? whole - 3 : (n >= 1 ? 1 : 0);
+    const double* e = hops + it.hop0;
+    __shared__ double ssum[LV_GAIN_THREADS], sall[LV_GAIN_THREADS];
+    __shared__ long long scnt[LV_GAIN_THREADS];
+    __shared__ float spk[LV_GAIN_THREADS];
+    __shared__ double gamma;
+    __shared__ int live;
+    float pk = 0.f;
+    for (long long h = t; h < nh; h += LV_GAIN_THREADS) pk = fmaxf(pk, peaks[it.hop0 + h]);
+    double s = 0.0, all = 0.0;
+    long long k = 0;
+    for (long long j = t; j < nb; j += LV_GAIN_THREADS) {
+        const double E = level_block(e, j, whole, nh, n, H);
+        all += E;
+        if (level_lufs(E) > -70.0) { s += E; ++k; }
+    }
+    ssum[t] = s; sall[t] = all; scnt[t] = k; spk[t] = pk;
+    __syncthreads();
+    if (t == 0) {
+        s = 0.0; all = 0.0; k = 0; pk = 0.f;
+        for (int i = 0; i < LV_GAIN_THREADS; ++i) { s += ssum[i]; all += sall[i]; k += scnt[i]; pk = fmaxf(pk, spk[i]); }
+        live = isfinite(all) && k > 0;
+        gamma = live ? level_lufs(s / (double)k) - 10.0 : 0.0;
+        it.L = -INFINITY; it.p = pk; it.g = 1.f; it.blocks = (int)nb; it.gated = 0; it.capped = 0;
+    }
+    __syncthreads();
+    if (!live) return;
+    const double gm = gamma;
+    s = 0.0;
+    k = 0;
+    for (long long j = t; j < nb; j += LV_GAIN_THREADS) {
+        const double E = level_block(e, j, whole, nh, n, H), l = level_lufs(E);
+        if (l > -70.0 && l > gm) { s += E; ++k; }
+    }
+    __syncthreads();
+    ssum[t] = s; scnt[t] = k;
+    __syncthreads();
+    if (t == 0) {
+        s = 0.0; k = 0;
+        for (int i = 0; i < LV_GAIN_THREADS; ++i) { s += ssum[i]; k += scnt[i]; }
+        if (k > 0) {
+            const double L = level_lufs(s / (double)k);
+            it.L = L;
+            it.gated = (int)k;
+            if (tab->target != 0) {
+                double g = pow(10.0, ((double)tab->target / 100.0 - L) / 20.0);
+                const double p = (double)it.p;
+                if (p > 0.0 && tab->ceiling / p < g) {
+                    g = tab->ceiling / p;
+                    it.capped = 1;
+                }
+                it.g = (float)g;
+            }
+        }
+    }
+}
+
+static __global__ __launch_bounds__(LV_SCALE_THREADS) void level_scale_kernel(const LevelTab* tab) {
+    const LevelItem& it = tab->it[blockIdx.z];
+    const float g = it.g;
+    float* x = it.x;
+    for (long long i = (long long)blockIdx.x * LV_SCALE_THREADS + threadIdx.x; i < it.n; i += (long long)gridDim.x * LV_SCALE_THREADS)
+        x[i] = g * x[i];
+}
+
 }  // namespace ft

@@ -1,6 +1,7 @@
-// Host arithmetic of the output chain behind the codec (fishtts_hip.h: sample_rate, speed_pct, pitch_cents): the time-scale
-// stage, then the pitch stage, then the resampler.  The filter designs, the rule that accepts a (speed, cents) pair, what
-// each stage can emit after so many input samples, and the bookkeeping of a stream's three stages from call to call.
+// Host arithmetic of the output chain behind the codec (fishtts_hip.h: sample_rate, speed_pct, pitch_cents, loudness): the
+// time-scale stage, then the pitch stage, then the resampler, then the level.  The filter designs, the rule that accepts a
+// (speed, cents) pair, what each stage can emit after so many input samples, the bookkeeping of a stream's three stages from
+// call to call, and the level stage's K-weighting design, gates and gain.
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
 // are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
@@ -148,6 +149,81 @@ inline long long ps_ready(const PsTab& t, long long nin, bool final, long long t
     return a > 0 ? ((a << PS_SHIFT) + t.S - 1) / t.S : 0;
 }
 
+// ---- level stage (level_filter_kernel, level_gain_kernel, level_scale_kernel; fishtts_hip.h states it): the K-weighting
+// design at any rate, the hop, and the gates and the gain over given hop sums.  The target is in hundredths of a LUFS.
+constexpr int LV_MIN = -5000, LV_MAX = -500, LV_WARM_HOPS = 2;
+inline bool lv_ok(int target) { return target == 0 || (target >= LV_MIN && target <= LV_MAX); }
+inline int lv_hop(int rate) { return rate / 10; }
+inline double lv_ceiling() { return std::pow(10.0, -1.0 / 20.0); }      // -1 dBFS on the sample peak
+
+// c = the shelf's b0 b1 b2 a1 a2, then the high-pass's: two biquads from the analogue prototypes of BS.1770, in float64.
+inline void lv_design(int rate, double c[10]) {
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = std::tan(M_PI * f0 / rate), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double a0 = 1.0 + K / Q + K * K;
+        c[0] = (Vh + Vb * K / Q + K * K) / a0;
+        c[1] = 2.0 * (K * K - Vh) / a0;
+        c[2] = (Vh - Vb * K / Q + K * K) / a0;
+        c[3] = 2.0 * (K * K - 1.0) / a0;
+        c[4] = (1.0 - K / Q + K * K) / a0;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = std::tan(M_PI * f0 / rate), d = 1.0 + K / Q + K * K;
+        c[5] = 1.0;
+        c[6] = -2.0;
+        c[7] = 1.0;
+        c[8] = 2.0 * (K * K - 1.0) / d;
+        c[9] = (1.0 - K / Q + K * K) / d;
+    }
+}
+
+inline double lv_lufs(double E) { return -0.691 + 10.0 * std::log10(E); }
+
+struct LvInfo { double L = -INFINITY; float p = 0.f, g = 1.f; int blocks = 0, gated = 0, capped = 0; };
+
+// The stage's result for an item of n samples with hop H from its hop sums e[0 .. ceil(n / H)) (the last one over what is
+// left of the item), its sample peak p and the target (0: measure only, the gain stays 1).
+inline LvInfo lv_gain(const double* e, long long n, int H, float p, int target) {
+    LvInfo r;
+    r.p = p;
+    if (n < 1 || H < 1) return r;
+    const long long hops = n / H;
+    std::vector<double> E;
+    if (hops < 4) {
+        double s = 0.0;
+        for (long long h = 0; h < (n + H - 1) / H; ++h) s += e[h];
+        E.push_back(s / (double)n);
+    } else {
+        for (long long j = 0; j + 3 < hops; ++j) E.push_back((e[j] + e[j + 1] + e[j + 2] + e[j + 3]) / (4.0 * H));
+    }
+    r.blocks = (int)E.size();
+    double s = 0.0, all = 0.0;
+    long long k = 0;
+    for (double v : E) {
+        all += v;
+        if (lv_lufs(v) > -70.0) { s += v; ++k; }
+    }
+    if (!std::isfinite(all) || k == 0) return r;
+    const double gamma = lv_lufs(s / (double)k) - 10.0;
+    s = 0.0;
+    k = 0;
+    for (double v : E)
+        if (lv_lufs(v) > -70.0 && lv_lufs(v) > gamma) { s += v; ++k; }
+    if (k == 0) return r;
+    r.gated = (int)k;
+    r.L = lv_lufs(s / (double)k);
+    if (target == 0) return r;
+    double g = std::pow(10.0, ((double)target / 100.0 - r.L) / 20.0);
+    if (p > 0.f && lv_ceiling() / (double)p < g) {
+        g = lv_ceiling() / (double)p;
+        r.capped = 1;
+    }
+    r.g = (float)g;
+    return r;
+}
+
 // ---- the three stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;
 // plan() says how many (nothing changes), the caller builds the stage's segment from the record and the plan, and commit()
 // advances the record once the call went through.  An absent stage passes its input on (out = in); its counters still run,
@@ -219,22 +295,24 @@ struct StageChain {
     }
 };
 
-// A call's chain, resolved: which stages exist and at what rate.  make() judges the three values as every entry point does
-// (an error message, or null): the rate, then the speed, then the cents, then the pair.  The device tables are filled in by
+// A call's chain, resolved: which stages exist and at what rate.  make() judges the values as every entry point does
+// (an error message, or null): the rate, then the speed, then the cents, then the pair, then the level.  The device tables are filled in by
 // the caller that holds the context (codec.hip: fx_prepare).
 struct FxDesc {
-    int rate = RS_FI, pct = 100, cents = 0;
+    int rate = RS_FI, pct = 100, cents = 0, level = 0;   // level: the target in hundredths of a LUFS, 0: no level stage
     int L = 1, M = 1, K = 0;          // the resampler's (K = 0: the codec's own rate, no stage)
     FxPlan f;                         // f.has_ts: the time-scale stage exists (under a pitch shift it may not)
     const RsTab* rs = nullptr;        // set by the caller when K > 0
     const PsTab* ps = nullptr;        // set by the caller when cents != 0
-    enum Bad { OK = 0, RATE, SPEED, CENTS, PAIR };
-    Bad make(int rate_, int pct_, int cents_, const char** why) {
-        rate = rate_; pct = pct_; cents = cents_;
+    enum Bad { OK = 0, RATE, SPEED, CENTS, PAIR, LEVEL };
+    Bad make(int rate_, int pct_, int cents_, const char** why) { return make(rate_, pct_, cents_, 0, why); }
+    Bad make(int rate_, int pct_, int cents_, int level_, const char** why) {
+        rate = rate_; pct = pct_; cents = cents_; level = level_;
         if ((*why = rs_design(rate, &L, &M, &K, nullptr))) return RATE;
         if (!ts_ok(pct)) return SPEED;
         if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS) return CENTS;
-        return fx_plan(pct, cents, &f) ? OK : PAIR;
+        if (!fx_plan(pct, cents, &f)) return PAIR;
+        return lv_ok(level) ? OK : LEVEL;
     }
     bool any() const { return K > 0 || f.has_ts || cents != 0; }
     // a waveform from zero state through this chain

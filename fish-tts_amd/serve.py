@@ -149,12 +149,12 @@ class BatchServer:
     def synthesize(self, text: str, references=None, temperature: float = 0.7, top_p: float = 0.8,
                    repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
                    sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                   pitch: Optional[float] = None, fx=None) -> bytes:
+                   pitch: Optional[float] = None, fx=None, loudness: Optional[float] = None) -> bytes:
         """Text -> WAV bytes: FishTTS.synthesize's result for seed 0 (draws with `seed`).  Safe from any number of threads;
-        `references=None` means the instance's set_references voices; `sample_rate`, `speed` and `pitch` as
-        FishTTS.synthesize_at (an unsupported one raises ValueError here, before anything is queued), or `fx`: the three
-        already checked (codec_engine.OutputFx)."""
-        fx = checked_fx(fx, sample_rate, speed, pitch)
+        `references=None` means the instance's set_references voices; `sample_rate`, `speed`, `pitch` and `loudness` as
+        FishTTS.synthesize_at (an unsupported one raises ValueError here, before anything is queued; requests of different
+        voices then come out at one level), or `fx`: these already checked (codec_engine.OutputFx)."""
+        fx = checked_fx(fx, sample_rate, speed, pitch, loudness)
         utt, n_prefix = self._prepare(text, references, temperature, top_p, repetition_penalty, max_tokens, seed)
         item = self.submit(utt, n_prefix, fx=fx).out.get()
         if isinstance(item, _Failed):
@@ -163,17 +163,19 @@ class BatchServer:
 
     def synthesize_stream(self, text: str, references=None, chunk_tokens: int = 20, min_first_chunk: int = 10,
                           seamless: bool = False, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                          pitch: Optional[float] = None, fx=None, **sampling) -> Iterator[bytes]:
+                          pitch: Optional[float] = None, fx=None, loudness: Optional[float] = None,
+                          **sampling) -> Iterator[bytes]:
         """Yields int16 PCM chunks as FishTTS.synthesize_stream does: seamless=False (the reference's default) every chunk
         decoded from zero state; seamless=True one stateful CodecStream per request, the chunks cut as
         synthesize_batch_stream cuts them.  `sampling`: temperature, top_p, repetition_penalty, max_tokens, seed.  The
         prompt is built and checked here (a too-long one raises ValueError now); the request is queued at the first
         next(), so a generator dropped before it never runs, and abandoning it later cancels the request (its slot is
         freed at the next burst boundary).  `sample_rate`, `speed` and `pitch` as FishTTS.synthesize_stream (checked here), or
-        `fx`: the three already checked."""
+        `fx`: the three already checked.  `loudness` (or an `fx` with a level) raises ValueError here: the level needs the whole
+        utterance."""
         if chunk_tokens < 1 or min_first_chunk < 1:
             raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-        fx = checked_fx(fx, sample_rate, speed, pitch)
+        fx = checked_fx(fx, sample_rate, speed, pitch, loudness).no_level("BatchServer.synthesize_stream")
         utt, n_prefix = self._prepare(text, references, sampling.get("temperature", 0.7), sampling.get("top_p", 0.8),
                                       sampling.get("repetition_penalty", 1.1), sampling.get("max_tokens", 2048),
                                       sampling.get("seed", 0))

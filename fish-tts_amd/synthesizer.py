@@ -195,6 +195,30 @@ class FishTTS:
             codes = self._vocoder.encode(audio)
         return VoiceProfile(codes=codes.astype(np.int64), text=text)
 
+    def measure_loudness(self, wav_bytes: bytes) -> float:
+        """Extension: the integrated loudness (LUFS, ITU-R BS.1770-4) of a 16-bit mono WAV, measured on the GPU at the WAV's
+        own rate by the stage that `loudness=` runs (CodecHipEngine.loudness) - the figure to pass as `loudness=` to match
+        a reference clip.  -inf for a clip with nothing above the absolute gate.  ValueError: not 16-bit mono, a rate that is
+        no accepted `sample_rate`, or a clip longer than the longest utterance the codec decodes
+        (CodecHipEngine.max_level_samples: over three minutes at 48 kHz with the codec's 2056 frames)."""
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        with wave.open(io.BytesIO(wav_bytes), "rb") as wf:
+            if wf.getnchannels() != 1 or wf.getsampwidth() != 2:
+                raise ValueError("measure_loudness: a 16-bit mono WAV is needed")
+            rate = wf.getframerate()
+            audio = np.frombuffer(wf.readframes(wf.getnframes()), dtype=np.int16).astype(np.float32) / 32768.0
+        _output_fx(rate, None, None)                  # (ValueError for a rate the output stages do not take)
+        if len(audio) > self._vocoder.max_level_samples:
+            raise ValueError(f"measure_loudness: {len(audio)} samples, the stage takes {self._vocoder.max_level_samples}")
+        srv = getattr(self, "_server", None)
+        if srv is not None:
+            with srv.codec_lock:              # the server's codec worker shares the codec context
+                info, _ = self._vocoder.loudness(audio, rate)
+        else:
+            info, _ = self._vocoder.loudness(audio, rate)
+        return info.lufs
+
     @staticmethod
     def _read_wav(audio_bytes: bytes) -> np.ndarray:
         """synthesizer.py:613-631: 16-bit PCM -> float32 / 32768, Fourier resampling to 44.1 kHz if needed."""
@@ -248,7 +272,7 @@ class FishTTS:
     def synthesize_at(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                       top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
                       sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                      pitch: Optional[float] = None) -> bytes:
+                      pitch: Optional[float] = None, loudness: Optional[float] = None) -> bytes:
         """Extension: synthesize() with the WAV at `sample_rate` (resampled on the GPU; None or 44100: the codec's own
         rate, byte for byte synthesize()'s result; an unsupported rate raises ValueError before any work -
         codec_engine.output_rate) and at speaking rate `speed` (a factor in [0.5, 2.0], the waveform time-scaled on the
@@ -257,10 +281,13 @@ class FishTTS:
         semitones (in [-12, 12], in steps of a cent; a plain shift on the GPU between the two stages - formants move with
         the pitch - that leaves the length as it is; None or 0: the model's own pitch, byte for byte the result without
         it; a value outside the range, or one whose speed / 2^(pitch / 12) leaves [0.5, 2], raises ValueError before any
-        work - codec_engine.output_pitch, output_fx)."""
+        work - codec_engine.output_pitch, output_fx), and levelled to `loudness` LUFS (a target in [-50, -5]: the
+        utterance's integrated loudness per ITU-R BS.1770-4 is measured on the GPU behind the other stages and one gain
+        brings it to the target, the sample peak held at -1 dBFS; None: the model's own level, byte for byte the result
+        without it; anything else raises ValueError before any work - codec_engine.OutputFx.of)."""
         from .generation import generate_long
         from .serve import ServerClosed
-        fx = _output_fx(sample_rate, speed, pitch)
+        fx = _output_fx(sample_rate, speed, pitch, loudness)
         srv = getattr(self, "_server", None)
         if srv is not None:
             try:
@@ -329,13 +356,14 @@ class FishTTS:
                          temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
                          max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None,
                          sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                         pitch: Optional[float] = None) -> List[bytes]:
+                         pitch: Optional[float] = None, loudness: Optional[float] = None) -> List[bytes]:
         """Extension (BASELINE configs[2]): many texts -> WAV bytes each, decoded `max_batch` at a time in lock step
         with refill (fish_tts_amd.batch); utterance i uses seed + i, or seeds[i] when `seeds` is given (a sharded run
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
-        semantics as synthesize(), `sample_rate`, `speed` and `pitch` (as synthesize_at) included."""
+        semantics as synthesize(), `sample_rate`, `speed`, `pitch` and `loudness` (as synthesize_at; every utterance is
+        levelled on its own) included."""
         from .batch import run_batch, run_batch_streams
-        fx = _output_fx(sample_rate, speed, pitch)
+        fx = _output_fx(sample_rate, speed, pitch, loudness)
         self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
@@ -358,7 +386,7 @@ class FishTTS:
                                 seed: int = 0, seeds: Optional[List[int]] = None,
                                 sample_rate: Optional[int] = None,
                                 speed: Optional[float] = None,
-                                pitch: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
+                                pitch: Optional[float] = None, loudness: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
         """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
         PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
         `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
@@ -372,10 +400,11 @@ class FishTTS:
         `speed` (as synthesize_at): each utterance's stream is time-scaled on the GPU through one carried stage (before
         the resampler, if any); the chunk before its (i, b"") holds the tail in the same way.
         `pitch` (as synthesize_at): each utterance's stream is pitch-shifted on the GPU through one carried stage (between
-        the two); the tail travels in the same way."""
+        the two); the tail travels in the same way.
+        `loudness`: ValueError here, before any work - the level needs the whole utterance (synthesize_batch has it)."""
         from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
-        fx = _output_fx(sample_rate, speed, pitch)
+        fx = _output_fx(sample_rate, speed, pitch, loudness).no_level("synthesize_batch_stream")
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
@@ -394,11 +423,12 @@ class FishTTS:
                                  min_first_chunk=min_first_chunk, fx=fx)
 
     # ------------------------------------------------------------------ long texts (extension)
-    def _long_plan(self, text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch):
+    def _long_plan(self, text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
+                   loudness=None):
         """Every check of a long-text call, before any device work: (texts, output stages, join parameters, gaps).
         ValueError for a bad value."""
         from .longform import join_params, split_text
-        fx = _output_fx(sample_rate, speed, pitch)
+        fx = _output_fx(sample_rate, speed, pitch, loudness)
         jp, gap, pgap = join_params(fx.rate, pause, paragraph_pause, silence_db)
         segs = split_text(text, max_chars, min_chars)
         if self._vocoder is None:
@@ -476,7 +506,8 @@ class FishTTS:
                         top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
                         pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                         max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
-                        speed: Optional[float] = None, pitch: Optional[float] = None) -> bytes:
+                        speed: Optional[float] = None, pitch: Optional[float] = None,
+                        loudness: Optional[float] = None) -> bytes:
         """Extension: a text of any length -> one WAV.  The text is split into segments of at most `max_chars` bytes at
         sentence ends (longform.split_text; pieces below `min_chars` join a neighbour), every segment is an utterance of
         its own - `max_tokens` frames at most each, segment i drawing with seed + i - and all of them run as ONE lock-step
@@ -487,11 +518,14 @@ class FishTTS:
         behind `pause` seconds of silence, `paragraph_pause` after a paragraph break; silence_db=None trims and fades
         nothing.  One voice throughout: with no reference voice (neither `references` nor set_references) segment 0 is
         generated first and then serves, text and codes, as the reference of every other segment.  `sample_rate`,
-        `speed`, `pitch` as synthesize_at, applied per segment before the join.  While a BatchServer is open the segments
+        `speed`, `pitch` as synthesize_at, applied per segment before the join.  `loudness` (as synthesize_at): every
+        segment is levelled to the target on its own, before the join - the sentences of the document then stand at one
+        level, and `silence_db` is judged on the levelled samples.  While a BatchServer is open the segments
         join its batch.  ValueError before any device work: pause / paragraph_pause outside [0, 5] s, silence_db outside
-        [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch."""
+        [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch /
+        loudness."""
         texts, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
-                                              sample_rate, speed, pitch)
+                                              sample_rate, speed, pitch, loudness)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         codes = self._long_codes_served(texts, references, sampling, seed)
         lock = None
@@ -530,15 +564,17 @@ class FishTTS:
                                top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
                                pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                                max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
-                               speed: Optional[float] = None, pitch: Optional[float] = None) -> Iterator[bytes]:
+                               speed: Optional[float] = None, pitch: Optional[float] = None,
+                               loudness: Optional[float] = None) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
-        chunks concatenate to synthesize_long's PCM byte for byte.  No empty chunk is yielded.  The arguments are checked
+        chunks concatenate to synthesize_long's PCM byte for byte - with `loudness` too: a group holds whole segments, and
+        each is levelled on its own.  No empty chunk is yielded.  The arguments are checked
         here, at the call; generation holds _gen_lock on its own thread and stops within one burst when the generator is
         abandoned."""
         texts, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
-                                              sample_rate, speed, pitch)
+                                              sample_rate, speed, pitch, loudness)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         return self._long_chunks(texts, references, sampling, seed, fx, jp, gaps)
 
@@ -622,10 +658,14 @@ class FishTTS:
 
         Extension `pitch=` (keyword, as synthesize_at; checked at the first next()): seamless=False chunks are shifted each
         on its own, as independent waveforms; a seamless stream runs one carried pitch stage (between the time-scale stage
-        and the resampler), so its chunks concatenate to the shifted waveform of one streamed decode."""
+        and the resampler), so its chunks concatenate to the shifted waveform of one streamed decode.
+
+        `loudness=` raises ValueError (at the first next(), before any work): the level needs the whole utterance, and a
+        stream hands out audio before its end (synthesize_at, synthesize_long_stream take it)."""
         from .generation import generate_long
         from .serve import ServerClosed
-        fx = _output_fx(kwargs.pop("sample_rate", None), kwargs.pop("speed", None), kwargs.pop("pitch", None))
+        fx = _output_fx(kwargs.pop("sample_rate", None), kwargs.pop("speed", None), kwargs.pop("pitch", None),
+                        kwargs.pop("loudness", None)).no_level("synthesize_stream")
         srv = getattr(self, "_server", None)
         if srv is not None:
             chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, fx=fx, **kwargs)
@@ -865,10 +905,10 @@ class _LongStopped(Exception):
     """The consumer of synthesize_long_stream went away: generation stops at its next block of frames."""
 
 
-def _output_fx(sample_rate, speed, pitch):
+def _output_fx(sample_rate, speed, pitch, loudness=None):
     """codec_engine.OutputFx.of: the checked output stages of a call (imported when first needed, as the engines are)."""
     from .codec_engine import OutputFx
-    return OutputFx.of(sample_rate, speed, pitch)
+    return OutputFx.of(sample_rate, speed, pitch, loudness)
 
 
 def get_instance(model_dir=None, device: Literal["cpu", "cuda"] = "cuda",

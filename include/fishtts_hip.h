@@ -333,6 +333,70 @@ ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int32_t B, int
  * most 64 items and max_frames frames; ends[g] (room for n) = one past the last item of group g.  Returns the number of
  * groups, -1 for a negative length, an item beyond max_frames or a null pointer. */
 int32_t ft_join_groups(const int32_t* lens, int32_t n, int32_t max_frames, int32_t* ends);
+/* Level.  The model sets its own level per utterance; these calls bring every item to a caller-chosen integrated loudness
+ * (ITU-R BS.1770-4 / EBU R128) on the device, as the last stage of the chain and in front of the join:
+ * codec -> time-scale stage -> pitch stage -> rate resampler -> level -> (join), all on the codec's stream.  The reference
+ * has no such stage.  The stage runs at the output rate Fo; per item it measures the integrated loudness and the sample
+ * peak, derives ONE gain and multiplies every sample of the item by it.  Stated, which fixes its result:
+ *   Inputs: item b has samples x[0 .. n), float32, at rate Fo.  The target T is in LUFS, given as an integer number of
+ *   hundredths (`loudness`): accepted values are [-5000, -500]; 0 means the stage is absent (the call is then the one without
+ *   it, bit for bit); anything else is FT_ERR_ARG before any device work.  The ceiling c = 10^(-1/20), -1 dBFS on the sample
+ *   peak, is fixed.
+ *   K-weighting at any rate: two biquads in series, designed in float64 on the host from the analogue prototypes (at 48 kHz
+ *   they are the table of BS.1770 to 1e-12).
+ *     Shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / Fo), Vh = 10^(G/20),
+ *     Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2; b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0],
+ *     a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0].
+ *     High-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan(pi f0 / Fo), d = 1 + K/Q + K^2; b = [1, -2, 1],
+ *     a = [1, 2 (K^2 - 1)/d, (1 - K/Q + K^2)/d].
+ *   z = hp(shelf(x)), both filters from zero state at sample 0.  The recursion and every sum below run in float64.
+ *   Blocks: the hop is H = floor(Fo / 10).  Hop sums e_h = sum z^2 over [h H, (h + 1) H), h < floor(n / H).  Block j is
+ *   E_j = (e_j + e_{j+1} + e_{j+2} + e_{j+3}) / (4 H), j = 0 .. floor(n / H) - 4: whole 400 ms blocks only, overlapped by
+ *   75 %.  An item shorter than 4 H with n >= 1 has the single block E_0 = sum z^2 / n.  l_j = -0.691 + 10 log10 E_j.
+ *   Gates: the absolute gate keeps blocks with l_j > -70.  If none is kept, or n = 0, or a sum is not finite, L = -inf and
+ *   the gain is exactly 1.  The relative gate is Gamma = -0.691 + 10 log10(mean E_j over the absolute-gated) - 10, and
+ *   L = -0.691 + 10 log10(mean E_j over the blocks with l_j > -70 and l_j > Gamma).
+ *   Gain: p = max |x|; g = min(10^((T/100 - L)/20), c / p) in float64 (no ceiling term when p = 0), rounded once to float32.
+ *   Output sample i is the float32 product g x[i]: one multiply and nothing else.
+ *   Reported per item (ft_level_info): L, p, g, the number of blocks, the number that passed both gates, and whether the
+ *   ceiling bound the gain.
+ *   Determinism: no floating-point atomics; every sum runs in a fixed order, so a call repeated gives the same bits.
+ * On the device the recursion runs one lane per hop, each lane starting both filters from zero state 2 H samples (0.2 s)
+ * before its hop, or at sample 0: the high-pass's double pole has decayed by e^-48 over that stretch at every rate, which
+ * leaves z within 1e-13 of the recursion from sample 0 (measured in float64 on noise with a DC offset); the hop sums do not
+ * depend on how the lanes are spread over the grid.  Three launches whatever the number of items (filter, gates and gain,
+ * multiply; the item is a grid dimension).  The first levelled call allocates the stage's table (64 items, < 4 KB) and one
+ * float64 and one float32 per hop of the call's items; a later call that needs more replaces them by larger ones.
+ * No stream entry point takes a level: the integrated loudness of an utterance is not known before its end. */
+typedef struct ft_level_info {
+    double lufs;               /* L: integrated loudness; -inf when nothing was measured (the gain is then 1) */
+    float peak, gain;          /* p = max |x| of the item before the stage; g */
+    int32_t blocks, gated;     /* 400 ms blocks of the item; those that passed both gates */
+    int32_t capped;            /* 1: the ceiling bound the gain (g = c / p) */
+} ft_level_info;
+/* Host only (no context, no device): validates the rate as ft_resample_filter does (FT_ERR_ARG otherwise, the outputs left
+ * untouched); coeffs[10] = the shelf's b0 b1 b2 a1 a2, then the high-pass's; *hop = H.  Either pointer may be NULL. */
+ft_status ft_level_filter(int32_t sample_rate, double* coeffs, int32_t* hop);
+/* The stage alone on a host waveform x of n >= 0 samples at sample_rate - this is also how a caller measures a reference
+ * clip.  target = 0 measures only (gain 1); y (may be NULL: nothing is multiplied or copied) receives the n levelled samples.
+ * n may be as long as the longest item a decode gives (max_frames frames at speed 0.5 and 48000 Hz), FT_ERR_TOO_LONG beyond.
+ * FT_ERR_ARG before any device work: a refused rate, a target that is neither 0 nor in [-5000, -500], a null x or info. */
+ft_status ft_codec_loudness(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, int32_t target,
+                            ft_level_info* info, float* y);
+/* ft_codec_decode_fxp with the level stage behind the resampler: row b is, bit for bit, ft_codec_loudness at `loudness` over
+ * row b of ft_codec_decode_fxp (its out_lens[b] samples; zeros past them as there).  infos (B entries; may be NULL) receives
+ * every item's result.  ft_codec_decode_fxp is this call at loudness = 0. */
+ft_status ft_codec_decode_level(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t loudness, float* audio,
+                                int64_t* out_lens, ft_level_info* infos);
+/* ft_codec_decode_join with the level stage in front of the join: every item is levelled on its own, all of them in one go,
+ * before the edges are found - the join's threshold therefore acts on the levelled samples, which gives its absolute figure
+ * a meaning.  The result is ft_test_join over the rows of ft_codec_decode_level.  infos (B entries; may be NULL) as there.
+ * ft_codec_decode_join is this call at loudness = 0. */
+ft_status ft_codec_decode_join_level(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                     int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t loudness,
+                                     const ft_join_params* jp, const int64_t* gaps, int32_t started, float* audio,
+                                     int64_t capacity, int64_t* total, int64_t* cuts, ft_level_info* infos);
 /* Codec encode = vocoder.encode(audio, lengths) of encode_reference (synthesizer.py:325-357, vocoder.py:885-904):
  * mono f32 audio at the codec sample rate (host), right-padded to whole frames -> codes (num_codebooks+1) x T'
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */

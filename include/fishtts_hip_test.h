@@ -106,6 +106,11 @@ ft_status ft_test_pitch(ft_ctx* ctx, const float* x, int64_t n, int32_t speed_pc
 ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, const int64_t* n, const ft_join_params* jp,
                        const int64_t* gaps, int32_t started, float* y, int64_t capacity, int64_t* total, int64_t* cuts);
 
+/* Test hook: the hop sums the level stage left in its last call on this context (ft_codec_loudness: one item; a joined call:
+ * the items back to back), ceil(n / H) per item, the last one over what is left of the item.  *count = their number; the
+ * first min(capacity, *count) go to hops. */
+ft_status ft_test_level_hops(ft_ctx* ctx, double* hops, int64_t capacity, int64_t* count);
+
 /* Test hook: a launch trace of the codec.  ft_test_codec_trace_arm makes the NEXT ft_codec_decode (B = 1; any other
  * B disarms it untraced) or ft_codec_encode on this context record one entry per kernel launch of the one-shot path, in
  * launch order: a stable stage name ("post.2.wo", "up.1.pw1", "dec.3.u2.c7", "enc.2.sc", ...), the rows and columns
