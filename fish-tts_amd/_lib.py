@@ -134,6 +134,7 @@ SYMBOLS = {
     "ft_test_qkv0_tab": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     "ft_test_codec_trace_arm": (C.c_int32, [_P, C.c_int32, C.c_int32]),
     "ft_test_codec_trace_count": (C.c_int32, [_P]),
+    "ft_test_codec_trace_chunks": (C.c_int32, [_P, C.POINTER(C.c_int32), _P]),
     "ft_test_codec_trace_variants": (C.c_int32, []),
     "ft_test_codec_trace_variant": (C.c_char_p, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ft_test_codec_trace_launch": (C.c_int32, [_P, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),

@@ -300,7 +300,9 @@ class CodecHipEngine:
                                                  codes.ctypes.data_as(C.c_void_p)), "ft_codec_rvq_encode")
         return codes
 
-    TRACE_KINDS = ("bf", "act", "f32")    # ft_test_codec_trace_buffer kinds: main bf16 output, Snake'd copy, f32 output
+    # ft_test_codec_trace_buffer kinds: main bf16 output, Snake'd copy, f32 output; a carrying launch of a streamed decode:
+    # the carried rows as placed in front of the chunk, the whole carry left for the next chunk
+    TRACE_KINDS = ("bf", "act", "f32", "front", "carry")
 
     def trace_variants(self) -> List[dict]:
         """Test hook: the GEMM instantiations gemm() can pick, by id: name and row / column tile."""
@@ -312,9 +314,12 @@ class CodecHipEngine:
         return out
 
     def trace(self, call, first: int = 0, count: int = 0):
-        """Test hook (ft_test_codec_trace_*): run call() - ONE decode of one item or ONE encode - traced.  Returns
+        """Test hook (ft_test_codec_trace_*): run call() - ONE decode of one item, ONE encode, ONE chunk of a stream
+        (CodecStream.decode) or ONE batched call (decode_streams of at most 64 plain streams) - traced.  Returns
         (call's result, launches): per launch in launch order a dict name / rows / cols / variant / halo / ntap / K and,
-        for launches [first, first + count), "out": {"bf" | "act" | "f32": (rows, cols) array}, bf16 as uint16 bits."""
+        for launches [first, first + count), "out": {"bf" | "act" | "f32": (rows, cols) array}, bf16 as uint16 bits.
+        A carrying launch of a streamed call ("*.roll", "*.kvin", "*.kvout") has "chunk" (its chunk's index in the
+        call, where the others have ntap) and "out": {"front" | "carry": ...}.  trace_chunks() gives the chunk table."""
         self._check(self.lib.ft_test_codec_trace_arm(self._h, int(first), int(count)), "ft_test_codec_trace_arm")
         res = call()
         n = self.lib.ft_test_codec_trace_count(self._h)
@@ -327,6 +332,8 @@ class CodecHipEngine:
             self._check(self.lib.ft_test_codec_trace_launch(self._h, i, name, 96, info), "ft_test_codec_trace_launch")
             rec = {"name": name.value.decode(), "rows": info[0], "cols": info[1], "variant": info[2], "halo": info[4],
                    "ntap": info[5], "K": info[6], "kinds": [], "out": {}}
+            if rec["name"].endswith((".roll", ".kvin", ".kvout")):
+                rec["chunk"] = rec.pop("ntap")
             for j in range(info[3]):
                 kind, f32, elems = C.c_int32(0), C.c_int32(0), C.c_int64(0)
                 self._check(self.lib.ft_test_codec_trace_buffer(self._h, i, j, C.byref(kind), C.byref(f32), C.byref(elems), None),
@@ -341,6 +348,15 @@ class CodecHipEngine:
                     rec["out"][k] = a
             launches.append(rec)
         return res, launches
+
+    def trace_chunks(self) -> List[dict]:
+        """Test hook (ft_test_codec_trace_chunks): the chunks of the last traced call, in call order: P (first frame in
+        the call), L (frames), t0 (rope position), nh (carried K/V rows).  Empty after a one-shot call."""
+        n = C.c_int32(0)
+        tab = np.zeros((64, 4), dtype=np.int32)
+        self._check(self.lib.ft_test_codec_trace_chunks(self._h, C.byref(n), tab.ctypes.data_as(C.c_void_p)),
+                    "ft_test_codec_trace_chunks")
+        return [dict(zip(("P", "L", "t0", "nh"), (int(v) for v in row))) for row in tab[:n.value]]
 
     def stream(self, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                pitch: Optional[float] = None, fx: Optional[OutputFx] = None) -> "CodecStream":

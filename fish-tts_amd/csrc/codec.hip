@@ -119,10 +119,18 @@ struct CodecState {
     int hop = 1, enc_frame_len = 0;
     long max_samples = 0;
     // ---- test hook (fishtts_hip_test.h, ft_test_codec_trace_*): `trace` is non-null only inside a traced one-shot
-    // decode / encode; every launch site tests it once
+    // decode / encode or a traced streamed decode; every launch site tests it once
     struct TraceBuf { int kind = 0, f32 = 0; long elems = 0; std::vector<char> data; };   // kind: 0 out_bf, 1 out_act, 2 out_f32
     struct TraceRec { std::string name; int rows = 0, cols = 0, variant = -1, halo = 0, ntap = 0, K = 0; bool held = false; std::vector<TraceBuf> bufs; };
-    struct Trace { int first = 0, count = 0; bool armed = false, failed = false; std::vector<TraceRec> recs; };
+    struct TraceChunk { int P, L, t0, nh; };
+    struct Trace {
+        int first = 0, count = 0;
+        bool armed = false, failed = false;
+        std::vector<TraceRec> recs;
+        std::vector<TraceChunk> chunks;   // a streamed call: its chunks {P, L, t0, nh} in call order; empty: a one-shot call
+        bool batched = false;             // ft_codec_stream_decode_many: gap rows in front of every chunk
+        long frames = 0;                  // frames of all chunks
+    };
     Trace tstore;
     Trace* trace = nullptr;
 };
@@ -657,8 +665,10 @@ static std::string tname(const char* fmt, ...) {
     va_end(ap);
     return buf;
 }
+// m > 0 in a batched streamed call: the rows are those of the chunks back to back, chunk z's at row P_z m + z g of the buffer
+// (the gap rows are left out).
 static void trace_rec(CodecState* s, hipStream_t st, const std::string& name, long rows, long cols, int variant, int halo, int ntap,
-                      int K, std::initializer_list<TraceOut> outs) {
+                      int K, std::initializer_list<TraceOut> outs, int m = 0, int g = 0) {
     CodecState::Trace& t = *s->trace;
     const int idx = (int)t.recs.size();
     t.recs.emplace_back();
@@ -671,8 +681,39 @@ static void trace_rec(CodecState* s, hipStream_t st, const std::string& name, lo
         CodecState::TraceBuf& b = r.bufs.back();
         b.kind = o.kind; b.f32 = o.f32; b.elems = rows * cols;
         if (!r.held) continue;
-        b.data.resize((size_t)b.elems * (o.f32 ? 4 : 2));
-        if (hipMemcpyAsync(b.data.data(), o.p, b.data.size(), hipMemcpyDeviceToHost, st) != hipSuccess) t.failed = true;
+        const size_t esz = o.f32 ? 4 : 2;
+        b.data.resize((size_t)b.elems * esz);
+        if (m > 0 && t.batched) {
+            char* dst = b.data.data();
+            for (size_t z = 0; z < t.chunks.size(); ++z) {
+                const size_t nb = (size_t)t.chunks[z].L * m * cols * esz;
+                const char* src = (const char*)o.p + ((size_t)t.chunks[z].P * m + z * (size_t)g) * cols * esz;
+                if (dst + nb > b.data.data() + b.data.size() || hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToHost, st) != hipSuccess) { t.failed = true; break; }
+                dst += nb;
+            }
+        } else if (hipMemcpyAsync(b.data.data(), o.p, b.data.size(), hipMemcpyDeviceToHost, st) != hipSuccess) t.failed = true;
+    }
+    if (r.held && hipStreamSynchronize(st) != hipSuccess) t.failed = true;
+}
+// The record of a carrying launch of a streamed decode, for chunk z: rows x cols bf16 per buffer, buffer i read at row
+// stride ld[i] (kinds 3: the carried rows as placed in front of the chunk, 4: the whole carry left for the next chunk).
+struct TraceCarry { int kind; const bf16_t* p; long ld; };
+static void trace_carry(CodecState* s, hipStream_t st, const std::string& name, int z, int rows, int cols,
+                        std::initializer_list<TraceCarry> outs) {
+    CodecState::Trace& t = *s->trace;
+    const int idx = (int)t.recs.size();
+    t.recs.emplace_back();
+    CodecState::TraceRec& r = t.recs.back();
+    r.name = name; r.rows = rows; r.cols = cols; r.variant = -1; r.halo = rows; r.ntap = z; r.K = 0;
+    r.held = idx >= t.first && idx < t.first + t.count;
+    for (const TraceCarry& o : outs) {
+        r.bufs.emplace_back();
+        CodecState::TraceBuf& b = r.bufs.back();
+        b.kind = o.kind; b.f32 = 0; b.elems = (long)rows * cols;
+        if (!r.held) continue;
+        b.data.resize((size_t)b.elems * 2);
+        if (hipMemcpy2DAsync(b.data.data(), (size_t)cols * 2, o.p, (size_t)o.ld * 2, (size_t)cols * 2, (size_t)rows,
+                             hipMemcpyDeviceToHost, st) != hipSuccess) t.failed = true;
     }
     if (r.held && hipStreamSynchronize(st) != hipSuccess) t.failed = true;
 }
@@ -683,8 +724,8 @@ static void gemm_t(CodecState* s, hipStream_t st, const ConvW& w, const GemmIO& 
     if (s->trace) {
         const long cols = io.act == ACT_SWIGLU ? w.N / 2 : w.N;
         if (io.ldo != cols) s->trace->failed = true;
-        trace_rec(s, st, tname(fmt, pfx, a, b), io.M, cols, id, halo_of(w), w.ntap, w.K,
-                  {{0, io.out_bf, 0}, {1, io.out_act, 0}, {2, io.out_f32, 1}});
+        trace_rec(s, st, tname(fmt, pfx, a, b), io.seg ? s->trace->frames * io.seg_m : io.M, cols, id, halo_of(w), w.ntap, w.K,
+                  {{0, io.out_bf, 0}, {1, io.out_act, 0}, {2, io.out_f32, 1}}, io.seg ? io.seg_m : 0, io.seg_og);
     }
 }
 struct TraceScope {   // a traced call: armed -> active for this call only
@@ -694,6 +735,9 @@ struct TraceScope {   // a traced call: armed -> active for this call only
         s->tstore.armed = false;
         if (!eligible) return;
         s->tstore.recs.clear();
+        s->tstore.chunks.clear();
+        s->tstore.batched = false;
+        s->tstore.frames = 0;
         s->tstore.failed = false;
         s->trace = &s->tstore;
     }
@@ -998,6 +1042,7 @@ struct Layout {
     const std::vector<ft_codec_stream::Tail>* tails = nullptr;   // the list the stream(s) hold; null: nothing carried
     bf16_t* const* hcarry = nullptr;   // one stream: [ncarry][read, write], host pointers handed to the kernels
     bf16_t* const* dcarry = nullptr;   // many: [n][ncarry][read, write] on the device (SegZ::carry)
+    bf16_t* const* tcarry = nullptr;   // the launch trace: [n][ncarry][read, write] on the host (one stream: hcarry)
     int ncarry = 0;
     int t0 = 0, nh = 0;           // one stream: rope position, carried K/V rows in front of the chunk (many: from seg)
     int kv_in = 0, kv_out = 0;    // most K/V rows a chunk takes over / leaves behind; 0: no such launch
@@ -1050,12 +1095,21 @@ static void run_transformer(ft_ctx* ctx, const Layout& L, const std::vector<TfLa
         if (s->trace) trace_rec(s, st, tname("%s%d.norm1", pfx, l), T, D, -1, 0, 0, 0, {{0, xn, 0}});
         { GemmIO io = L.io(xn, D, 1, 0, L.qgap); io.out_bf = L.qkv; io.ldo = 3 * HD; gemm_t(s, st, t.qkv, io, "%s%d.qkv", l, 0, pfx); }
         rope_qk_kernel<<<L.grid(gridfor((long)L.T * 2 * H * (hd / 2))), 256, 0, st>>>(L.qkv, rope, L.T, H, hd, L.t0, L.Z(1, L.qgap));
-        if (s->trace) trace_rec(s, st, tname("%s%d.rope", pfx, l), T, 3 * HD, -1, 0, 0, 0, {{0, L.qkv, 0}});
+        if (s->trace) trace_rec(s, st, tname("%s%d.rope", pfx, l), T, 3 * HD, -1, 0, 0, 0, {{0, L.qkv, 0}}, 1, L.qgap);
         if (L.kv_in > 0)
             kv_carry_in_kernel<<<L.grid(gridfor((long)L.kv_in * 2 * HD / 8)), 256, 0, st>>>(q0, L.carry_rd(ci), L.nh, W1, HD, L.Z(1, L.qgap, ci));
+        if (s->trace && L.kv_in > 0)        // per chunk with carried rows: the k and v thirds of the nh rows in front of it
+            for (size_t z = 0; z < s->trace->chunks.size(); ++z) {
+                const CodecState::TraceChunk& ch = s->trace->chunks[z];
+                const long row0 = s->trace->batched ? (long)ch.P + (long)z * L.qgap : 0;
+                if (ch.nh > 0) trace_carry(s, st, tname("%s%d.kvin", pfx, l), (int)z, ch.nh, 2 * HD, {{3, L.qkv + (row0 - ch.nh) * 3 * HD + HD, 3L * HD}});
+            }
         if (L.kv_out > 0)
             kv_carry_out_kernel<<<L.grid(gridfor((long)L.kv_out * 2 * HD / 8)), 256, 0, st>>>(
                 q0, L.carry_wr(ci), L.nh + L.own, std::min(W1, L.nh + L.own), W1, HD, L.Z(1, L.qgap, ci));
+        if (s->trace && L.kv_out > 0)       // per chunk: the whole carry it leaves
+            for (size_t z = 0; z < s->trace->chunks.size(); ++z)
+                trace_carry(s, st, tname("%s%d.kvout", pfx, l), (int)z, W1, 2 * HD, {{4, L.tcarry[(z * L.ncarry + ci) * 2 + 1], 2L * HD}});
         window_attn_kernel<<<L.grid((L.T * H + 3) / 4), 256, 0, st>>>(
             WinAttnP{q0, y, L.nh + L.own, H, hd, window, 1.0f / sqrtf((float)hd), L.nh, L.Z(1, L.qgap)});
         if (s->trace) trace_rec(s, st, tname("%s%d.attn", pfx, l), T, HD, -1, 0, 0, 0, {{0, y, 0}});
@@ -1080,10 +1134,17 @@ static bool decode_chain(ft_ctx* ctx, const Layout& L) {
     bool in_step = true;
     // the carried rows of x's earlier chunks in front of x (rows [-H, 0)), and the carry for the next chunk; the stream's
     // entry must be this stage's: a stage added here and not there would otherwise read another stage's rows
-    auto roll = [&](bf16_t* x, int m, int Hh, int C) {
+    // (fmt, a, b: the name of the stage that reads the rows, for the launch trace)
+    auto roll = [&](bf16_t* x, int m, int Hh, int C, const char* fmt, int a = 0, int b = 0) {
         if (!L.tails || Hh == 0) return 0;
         if (ti >= L.ntail() || (*L.tails)[ti].H != Hh || (*L.tails)[ti].C != C) { in_step = false; return 0; }
         tail_roll_kernel<<<L.grid(gridfor((long)Hh * C / 8)), 256, 0, st>>>(x, L.carry_rd(ti), L.carry_wr(ti), L.own * m, Hh, C, L.Z(m, G, ti));
+        if (s->trace)                       // per chunk: the rows in front of it after the copy, the whole carry it leaves
+            for (size_t z = 0; z < s->trace->chunks.size(); ++z) {
+                const long row0 = s->trace->batched ? (long)s->trace->chunks[z].P * m + (long)z * G : 0;
+                trace_carry(s, st, tname(fmt, a, b), (int)z, Hh, C,
+                            {{3, x + (row0 - Hh) * C, (long)C}, {4, L.tcarry[(z * L.ncarry + ti) * 2 + 1], (long)C}});
+            }
         ++ti;
         return -Hh;
     };
@@ -1099,27 +1160,27 @@ static bool decode_chain(ft_ctx* ctx, const Layout& L) {
         { GemmIO io = L.io(z, D, m, xg, G / us.f); io.out_bf = u; io.ldo = us.ct.N; gemm_t(s, st, us.ct, io, "%sup.%d.ct", uj); }
         m *= us.f;
         xg = G;
-        const int tm = roll(u, m, 6, D);                      // depthwise causal k = 7
+        const int tm = roll(u, m, 6, D, "up.%d.dwln.roll", uj);   // depthwise causal k = 7
         dwconv_ln_kernel<<<L.grid(L.T * m), 256, D * sizeof(float), st>>>(DwLnP{u, us.dw_w, us.dw_b, us.ln_w, us.ln_b, L.T * m, D, n, tm, L.Z(m, G)});
-        if (s->trace) trace_rec(s, st, tname("up.%d.dwln", uj), L.T * m, D, -1, 6, 7, 0, {{0, n, 0}});
+        if (s->trace) trace_rec(s, st, tname("up.%d.dwln", uj), (long)L.total * m, D, -1, 6, 7, 0, {{0, n, 0}}, m, G);
         { GemmIO io = L.io(n, D, m, G, G); io.act = ACT_GELU; io.out_bf = h; io.ldo = 4 * D; gemm_t(s, st, us.pw1, io, "%sup.%d.pw1", uj); }
         { GemmIO io = L.io(h, 4 * D, m, G, G); io.gamma = us.gamma; io.resid_bf = u; io.ldr = D; io.out_bf = z; io.ldo = D; gemm_t(s, st, us.pw2, io, "%sup.%d.pw2", uj); }
     }
     // decoder (vocoder.py:605-640).  Buffers: a = snake'd input of the next conv, r = raw residual
     bf16_t *a = u, *r = n, *hs = h, *a2 = z;
     { GemmIO io = L.io(z, D, m, xg, G); io.out_act = a; io.alpha = s->blocks[0].a0; io.ldo = c.decoder_dim;
-      io.t_min = roll(z, m, halo_of(s->conv_in), D); gemm_t(s, st, s->conv_in, io, "%sdec.in"); }
+      io.t_min = roll(z, m, halo_of(s->conv_in), D, "dec.in.roll"); gemm_t(s, st, s->conv_in, io, "%sdec.in"); }
     // note: conv_in reads z and writes a (= big[1]); z (= big[0]) is free afterwards
     for (size_t bi = 0; bi < s->blocks.size(); ++bi) {
         const DecBlock& b = s->blocks[bi];
         // transposed conv: raw -> r, snake'd by unit 0 -> a2
         { GemmIO io = L.io(a, b.cin, m, G, G / b.s); io.out_bf = r; io.out_act = a2; io.alpha = b.u[0].a0; io.ldo = b.ct.N;
-          io.t_min = roll(a, m, halo_of(b.ct), b.cin); gemm_t(s, st, b.ct, io, "%sdec.%d.ct", (int)bi); }
+          io.t_min = roll(a, m, halo_of(b.ct), b.cin, "dec.%d.ct.roll", (int)bi); gemm_t(s, st, b.ct, io, "%sdec.%d.ct", (int)bi); }
         m *= b.s;
         for (int ui = 0; ui < 3; ++ui) {
             const ResUnitW& ru = b.u[ui];
             { GemmIO io = L.io(a2, b.cout, m, G, G); io.out_act = hs; io.alpha = ru.a2; io.ldo = b.cout;
-              io.t_min = roll(a2, m, halo_of(ru.c7), b.cout); gemm_t(s, st, ru.c7, io, "%sdec.%d.u%d.c7", (int)bi, ui); }
+              io.t_min = roll(a2, m, halo_of(ru.c7), b.cout, "dec.%d.u%d.c7.roll", (int)bi, ui); gemm_t(s, st, ru.c7, io, "%sdec.%d.u%d.c7", (int)bi, ui); }
             const float* next_alpha = ui < 2 ? b.u[ui + 1].a0 : (bi + 1 < s->blocks.size() ? s->blocks[bi + 1].a0 : s->a_last);
             bf16_t* act_dst = ui < 2 ? a2 : a;  // the last unit feeds the next block's transposed conv / the output conv
             { GemmIO io = L.io(hs, b.cout, m, G, G); io.resid_bf = r; io.ldr = b.cout; io.out_bf = ui < 2 ? r : nullptr;
@@ -1127,9 +1188,9 @@ static bool decode_chain(ft_ctx* ctx, const Layout& L) {
         }
     }
     // m = frame_len here: item z's samples land at P_z * frame_len, back to back as the caller wants them
-    FinalConvP fp{a, s->w_last, s->b_last, L.T * m, s->c_last, s->audio, roll(a, m, 6, s->c_last), L.Z(m, G)};
+    FinalConvP fp{a, s->w_last, s->b_last, L.T * m, s->c_last, s->audio, roll(a, m, 6, s->c_last, "final.roll"), L.Z(m, G)};
     final_conv_tanh_kernel<<<L.grid(std::max(16, 2048 / L.n)), 256, 0, st>>>(fp);
-    if (s->trace) trace_rec(s, st, "final", L.T * m, 1, -1, 6, 7, s->c_last, {{2, s->audio, 1}});
+    if (s->trace) trace_rec(s, st, "final", (long)L.total * m, 1, -1, 6, 7, s->c_last, {{2, s->audio, 1}});
     return in_step && ti == L.ntail();
 }
 
@@ -1196,11 +1257,12 @@ static ft_status decode_one(ft_ctx* ctx, const int32_t* codes_host, int Tfull, i
         L.ncarry = L.ntail() + c.n_tf_layer;
         car.resize((size_t)L.ncarry * 2);
         stream_carries(sc, car.data());
-        L.hcarry = car.data();
+        L.hcarry = L.tcarry = car.data();
         L.t0 = sc->t0;
         L.nh = L.kv_in = std::min(sc->t0, W1);
         L.kv_out = std::min(W1, L.nh + T);
         L.qkv += (size_t)L.nh * 3 * HD;                       // the carried K/V rows go in front
+        if (s->trace) { s->trace->chunks.push_back({0, T, L.t0, L.nh}); s->trace->frames = T; }
     }
     // codes of this item, compacted to [R][T]
     std::vector<int> hc((size_t)R * T);
@@ -1279,6 +1341,7 @@ extern "C" ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* sc, co
     CodecState* s = ctx->codec;
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
+    TraceScope traced(s, true);
     return decode_one(ctx, codes, T, T, audio, sc);
 }
 
@@ -1371,6 +1434,12 @@ static ft_status decode_many(ft_ctx* ctx, int n, ft_codec_stream* const* scs, co
     L.seg = reinterpret_cast<const int4*>(s->mtab);
     L.dcarry = reinterpret_cast<bf16_t* const*>(s->mtab + seg_b);
     L.ncarry = ncarry;
+    L.tcarry = car;
+    if (s->trace) {
+        for (int j = 0; j < n; ++j) s->trace->chunks.push_back({seg[j].x, seg[j].y, seg[j].z, seg[j].w});
+        s->trace->batched = true;
+        s->trace->frames = Ts;
+    }
     L.codes = reinterpret_cast<const int*>(s->mtab + seg_b + car_b);
     std::copy(s->mbig, s->mbig + 4, L.big);
     // chunk z's q k v rows start at row P_z + z * W1 of L.qkv (its carried K/V in front)
@@ -1419,6 +1488,7 @@ extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_code
     FT_TRY(many_check(ctx, "ft_codec_stream_decode_many", n, streams, lens, nullptr, false));
     std::lock_guard<std::mutex> lock(ctx->codec->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
+    TraceScope traced(ctx->codec, true);
     return decode_many(ctx, n, streams, codes, lens, audio);
 }
 
@@ -1892,6 +1962,7 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
         if (lens[j] > 0) { cs.push_back(streams[j]); cl.push_back(lens[j]); }
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
+    TraceScope untraced(s, false);   // the launch trace covers ft_codec_stream_decode_many only: an armed trace is dropped here
     if (!any_fx) {   // the codec's rate and pace only: ft_codec_stream_decode_many
         if (!cs.empty()) FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio));
         for (int j = 0; j < n; ++j) out_lens[j] = plan[j].rs.out;
@@ -2117,6 +2188,17 @@ extern "C" int32_t ft_test_codec_trace_count(ft_ctx* ctx) {
     if (!ctx || !ctx->codec) return -1;
     std::lock_guard<std::mutex> lock(ctx->codec->mu);
     return ctx->codec->tstore.failed ? -1 : (int32_t)ctx->codec->tstore.recs.size();
+}
+extern "C" ft_status ft_test_codec_trace_chunks(ft_ctx* ctx, int32_t* n, int32_t* table) {
+    if (!ctx || !ctx->codec || !n) return FT_ERR_ARG;
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    *n = (int32_t)s->tstore.chunks.size();
+    for (size_t z = 0; table && z < s->tstore.chunks.size(); ++z) {
+        const CodecState::TraceChunk& c = s->tstore.chunks[z];
+        table[4 * z] = c.P; table[4 * z + 1] = c.L; table[4 * z + 2] = c.t0; table[4 * z + 3] = c.nh;
+    }
+    return FT_OK;
 }
 extern "C" int32_t ft_test_codec_trace_variants(void) { return N_GEMM_VARIANTS; }
 extern "C" const char* ft_test_codec_trace_variant(int32_t id, int32_t* bm, int32_t* bn) {

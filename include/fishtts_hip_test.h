@@ -112,7 +112,8 @@ ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, c
 ft_status ft_test_level_hops(ft_ctx* ctx, double* hops, int64_t capacity, int64_t* count);
 
 /* Test hook: a launch trace of the codec.  ft_test_codec_trace_arm makes the NEXT ft_codec_decode (B = 1; any other
- * B disarms it untraced) or ft_codec_encode on this context record one entry per kernel launch of the one-shot path, in
+ * B disarms it untraced), ft_codec_encode, ft_codec_stream_decode or ft_codec_stream_decode_many on this context
+ * (ft_codec_stream_decode_many_at disarms it untraced) record one entry per kernel launch, in
  * launch order: a stable stage name ("post.2.wo", "up.1.pw1", "dec.3.u2.c7", "enc.2.sc", ...), the rows and columns
  * it wrote and, for a GEMM launch, the id of the instantiation picked (0 .. ft_test_codec_trace_variants() - 1, -1 for
  * the other kernels).  Launches [first, first + count) also keep a host copy of every buffer they wrote (bf16 as bf16,
@@ -124,9 +125,24 @@ ft_status ft_test_level_hops(ft_ctx* ctx, double* hops, int64_t capacity, int64_
  * ft_test_codec_trace_variant: name and row / column tile of an instantiation id (NULL: no such id).
  * ft_test_codec_trace_launch: info[8] = {rows, cols, variant, buffers, halo rows, taps, K per tap, 1 if held}.
  * ft_test_codec_trace_buffer: buffer j of launch i: kind (0 out_bf / main output, 1 out_act (Snake'd copy), 2 out_f32),
- * is_f32, element count; dst != NULL receives the values (once: the copy is released). */
+ * is_f32, element count; dst != NULL receives the values (once: the copy is released).
+ * A streamed call: the rows of a launch are the rows it wrote - one stream: the chunk's T x (rows per frame); the batched
+ * call: the chunks' rows back to back in call order, the gap rows between them left out, so every buffer is dense
+ * [sum L x rows per frame][cols].  A GEMM still reports the instantiation it ran (picked for the nominal utterance).
+ * The carrying launches are recorded too, one entry per launch and chunk (chunks in call order), bf16, copied at that
+ * point of the stream; info = {rows, cols, -1, buffers, rows, chunk index, 0, held}:
+ *   "<stage>.roll" (tail_roll_kernel in front of <stage>: "up.0.dwln", "dec.in", "dec.1.ct", "dec.1.u2.c7", "final"):
+ *       H x C; kind 3: the H rows in front of the chunk after the copy, kind 4: the whole carry left for the next chunk;
+ *   "post.<l>.kvin" (kv_carry_in_kernel; only for a chunk with nh > 0): nh x 2 HD, kind 3: the K / V thirds of the nh
+ *       rows placed in front of the chunk's q k v rows;
+ *   "post.<l>.kvout" (kv_carry_out_kernel): (window - 1) x 2 HD, kind 4: the WHOLE carry left, rows the launch must not
+ *       have written included.
+ * ft_test_codec_trace_chunks: the chunk table of the last traced call: *n chunks (0: a one-shot call; 1: one stream),
+ * table (may be NULL; room for 64 x 4) receives {P, L, t0, nh} per chunk: first frame in the call, frames, rope position,
+ * carried K/V rows. */
 ft_status ft_test_codec_trace_arm(ft_ctx* ctx, int32_t first, int32_t count);
 int32_t ft_test_codec_trace_count(ft_ctx* ctx);
+ft_status ft_test_codec_trace_chunks(ft_ctx* ctx, int32_t* n, int32_t* table);
 int32_t ft_test_codec_trace_variants(void);
 const char* ft_test_codec_trace_variant(int32_t id, int32_t* bm, int32_t* bn);
 ft_status ft_test_codec_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t cap, int32_t* info);

@@ -50,6 +50,23 @@ Error model (u = 2^-24, the float32 unit round-off; every float32 operation retu
   first encoder convolution (1 channel, k = 7, f32): err = 8 u (|b| + sum |w| |x|), then the stores / Snake as above.
   RVQ gather: each table entry is codebook_dim products and the bias in f32 at load time, then 1 + n_codebooks entries
       are summed: err = sum_i (cd + 1) u (sum |w| |cb| + |b|)_i + (n_codebooks + 1) u sum_i |table_i|.
+
+Carried context (the streamed decode: ft_codec_stream_decode, one chunk of ft_codec_stream_decode_many).  `plan_stream`
+lists the launches of ONE chunk of T frames at rope position t0 with nh = min(t0, window - 1) carried K/V rows: the
+launches of plan_decode on the chunk's codes, plus the carrying launches, which are stages of their own:
+  "<stage>.roll" (kind roll) in front of every stage with a halo H: "front" = the carry the previous chunk left for that
+      stage (H x C; zeros before the first chunk), "carry" = the last H rows of (front ++ the chunk's T m input rows);
+  "post.<l>.kvin" (kind kvin; only when nh > 0): "front" = the last nh rows of the layer's K/V carry ((window-1) x 2 HD);
+  "post.<l>.kvout" (kind kvout): "carry" = the last min(window - 1, nh + T) rows of (front ++ the chunk's rotated K / V),
+      placed at the END of the (window-1)-row carry.  The rows in front of them are not written: they hold zeros, because
+      the number of rows kept never shrinks from chunk to chunk, so no earlier chunk wrote there in either copy.
+The arithmetic stages then read "rows before 0" from the recorded front instead of the causal zero padding (gather's
+`stale=` path: tap GEMMs, dwln, final); RoPE takes rows t0 + i of the table; attention puts the nh front rows before the
+chunk's keys, query i seeing keys [max(0, nh + i - window + 1), nh + i] of the nh + T.  Their error bounds are the ones
+above, unchanged: the carried rows are operands like any other.  The carrying stages are pure copies: they are
+restated on the recorded bit patterns and accepted bit for bit only (bound 0).  Carries live in env under "carry:..."
+keys from chunk to chunk (`carries`); a chunk traced after untraced chunks is judged on the front rows it recorded
+(`seed_unlinked`).  A batched call is the same plan per chunk on the chunk's rows of the dense records.
 """
 from __future__ import annotations
 
@@ -107,7 +124,7 @@ def half_ulp(mag: torch.Tensor, f32: bool, fmt: str = "bf16") -> torch.Tensor:
 @dataclass
 class Stage:
     name: str
-    kind: str                     # gemm | rvq | rmsnorm | rope | attn | dwln | final | enc_in | snake | tof32
+    kind: str                     # gemm | rvq | rmsnorm | rope | attn | dwln | final | enc_in | snake | tof32 | roll | kvin | kvout
     rows: int
     cols: int
     src: Dict[str, str] = field(default_factory=dict)     # role ("x", "resid") -> logical buffer
@@ -120,6 +137,8 @@ class Stage:
 
     @property
     def halo(self) -> int:
+        if self.kind in CARRY_KINDS:
+            return self.rows
         if self.kind == "gemm":
             return max(0, -min(self.p["offs"]))
         return 6 if self.kind in ("dwln", "final", "enc_in") else 0
@@ -249,12 +268,64 @@ def plan_encode(c: OC.CodecShape, audio) -> List[Stage]:
     return out
 
 
+CARRY_KINDS = ("roll", "kvin", "kvout")
+
+
+def plan_stream(c: OC.CodecShape, codes_chunk, t0: int, nh: int) -> List[Stage]:
+    """The launches of one chunk of a streamed decode, carrying launches included (see the module docstring): codes_chunk
+    (1 + n_codebooks, T) are the chunk's codes, t0 the frames decoded before it, nh the carried K/V rows."""
+    codes_chunk = torch.as_tensor(np.asarray(codes_chunk)).long()
+    T, W1, HD = codes_chunk.shape[1], c.tf_window - 1, c.tf_n_head * c.tf_head_dim
+    assert 0 <= nh == min(t0, W1), (t0, nh, W1)
+    tab = OC.rope_table(t0 + T, c.tf_head_dim, c.tf_rope_base).to(F32)
+    out: List[Stage] = []
+    for st in plan_decode(c, codes_chunk):
+        if st.kind == "rope":
+            out.append(Stage(st.name, st.kind, st.rows, st.cols, dict(st.src), dict(st.dst), {**st.p, "tab": tab, "t0": t0}))
+            pfx = st.name[:-len("rope")]
+            if nh > 0:
+                out.append(Stage(pfx + "kvin", "kvin", nh, 2 * HD, {"prev": f"carry:{pfx}kv"}, {"front": pfx + "kv.front"}, dict(W1=W1)))
+            if W1 > 0:
+                src = {"x": "qkv", **({"front": pfx + "kv.front"} if nh > 0 else {})}
+                out.append(Stage(pfx + "kvout", "kvout", W1, 2 * HD, src, {"carry": f"carry:{pfx}kv"}, dict(HD=HD)))
+        elif st.kind == "attn":
+            src = {**st.src, **({"kv": st.name[:-len("attn")] + "kv.front"} if nh > 0 else {})}
+            out.append(Stage(st.name, st.kind, st.rows, st.cols, src, dict(st.dst), {**st.p, "nh": nh}))
+        elif st.halo > 0:
+            C_in = st.p["K"] if st.kind == "gemm" else st.p["C"] if st.kind == "final" else st.cols
+            out.append(Stage(st.name + ".roll", "roll", st.halo, C_in, {"x": st.src["x"], "prev": f"carry:{st.name}"},
+                             {"front": st.name + ".front", "carry": f"carry:{st.name}"}))
+            out.append(Stage(st.name, st.kind, st.rows, st.cols, {**st.src, "halo": st.name + ".front"}, dict(st.dst), dict(st.p)))
+        else:
+            out.append(st)
+    return out
+
+
+def carries(env: dict) -> dict:
+    """What a chunk hands to the next one: the "carry:..." entries of its environment."""
+    return {k: v for k, v in env.items() if k.startswith("carry:")}
+
+
+def seed_unlinked(plan: List[Stage], outs: List[Dict[str, np.ndarray]]) -> dict:
+    """The carries a chunk whose predecessor was not traced is judged on: those that make its own recorded front rows."""
+    env = {}
+    for st, o in zip(plan, outs):
+        if st.kind == "roll":
+            env[st.src["prev"]] = o["front"]
+        elif st.kind == "kvin":
+            full = np.zeros((st.p["W1"], st.cols), dtype=np.uint16)
+            full[st.p["W1"] - st.rows:] = np.asarray(o["front"]).reshape(st.rows, st.cols)
+            env[st.src["prev"]] = full
+    return env
+
+
 def producers(plan: List[Stage]) -> List[List[int]]:
-    """For every stage, the indices of the launches whose recorded outputs it reads (the last writer of each source)."""
+    """For every stage, the indices of the launches whose recorded outputs it reads (the last writer of each source;
+    a carry of an earlier chunk has none)."""
     last: Dict[str, int] = {}
     out = []
     for i, st in enumerate(plan):
-        out.append(sorted({last[b] for b in st.src.values()}))
+        out.append(sorted({last[b] for b in st.src.values() if b in last}))
         for b in st.dst.values():
             last[b] = i
     return out
@@ -343,9 +414,12 @@ def f32_orders(X: torch.Tensor, Wm: torch.Tensor) -> List[torch.Tensor]:
     R, n = X.shape
     Cc = Wm.shape[1]
     Xt = X.t().contiguous()
-    chain = torch.zeros(R, Cc, dtype=F32)
-    for t in range(n):                                                   # one chain, k ascending, taps outermost
-        chain.addcmul_(Xt[t][:, None], Wm[t][None, :])
+    if R * n * Cc <= 1 << 21:     # few rows (a short streamed chunk): the same chain as one sequential float32 scan over k
+        chain = torch.from_numpy(np.add.accumulate((X[:, :, None] * Wm[None]).numpy(), axis=1, dtype=np.float32)[:, -1].copy())
+    else:
+        chain = torch.zeros(R, Cc, dtype=F32)
+        for t in range(n):                                               # one chain, k ascending, taps outermost
+            chain.addcmul_(Xt[t][:, None], Wm[t][None, :])
     blocked = blocked32(X, Wm)
     P = 1 << max(0, (n - 1).bit_length())
     pair = torch.empty(R, Cc, dtype=F32)
@@ -417,6 +491,11 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
     p = st.p
     fw = (lambda n: W.f(n).to(dt))
 
+    def carried(C):
+        """The rows a stage with a halo reads before row 0: the recorded front rows of a streamed chunk, else an emulated
+        bug's stale rows, else None (zeros)."""
+        return whole(env[st.src["halo"]], C) if "halo" in st.src else p.get("stale")
+
     def stores(v, err, alpha_name=None):
         ref, er = {}, {}
         for k in st.dst:
@@ -434,7 +513,7 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
         if p.get("drop_tap") is not None:                                   # an emulated bug: one tap never accumulated
             Wm = Wm.clone()
             Wm[p["drop_tap"] * K:(p["drop_tap"] + 1) * K] = 0
-        Xg = gather(env[st.src["x"]], K, rows, p["offs"], p.get("stale"))
+        Xg = gather(env[st.src["x"]], K, rows, p["offs"], carried(K))
         S = r = E = None
         if mode == "emulate":
             acc = blocked32(Xg.to(F64), Wm)
@@ -490,7 +569,7 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
             cb, w, b = fw(f"{q}.codebook.weight"), fw(f"{q}.out_proj.weight")[:, :, 0], fw(f"{q}.out_proj.bias")
             idx = codes[i, rows].clamp(0, (c_sem if i == 0 else cb.shape[0]) - 1)
             e = cb[idx]
-            tab = e @ w.t() + b
+            tab = (cb @ w.t() + b)[idx]           # the whole table, then the rows: as at load time, and the same sums for any row count
             if i == 0:
                 zs = tab
             else:
@@ -513,7 +592,7 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
     if st.kind == "rope":
         H, hd = p["H"], p["hd"]
         x = whole(env[st.src["x"]], st.cols)[rows].to(dt)
-        tab = p["tab"][rows].to(dt)                                         # [R, hd/2, 2]
+        tab = p["tab"][rows + p.get("t0", 0)].to(dt)                        # [R, hd/2, 2]: rows t0 .. of the table
         qk = x[:, :2 * H * hd].reshape(len(rows), 2 * H, hd // 2, 2)
         c, s = tab[:, None, :, 0], tab[:, None, :, 1]
         x0, x1 = qk[..., 0], qk[..., 1]
@@ -529,13 +608,19 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
     if st.kind == "attn":
         H, hd, win = p["H"], p["hd"], p["window"]
         x = whole(env[st.src["x"]], 3 * H * hd).to(dt)
-        T = x.shape[0]
-        q, k, vv = (x[:, i * H * hd:(i + 1) * H * hd].reshape(T, H, hd).transpose(0, 1) for i in range(3))   # [H, T, hd]
-        q = q[:, rows]
+        nh = p.get("nh", 0) if "kv" in st.src else 0                        # carried key / value rows in front of the chunk's
+        kv = torch.cat([whole(env[st.src["kv"]], 2 * H * hd).to(dt), x[:, H * hd:]], dim=0) if nh else x[:, H * hd:]
+        T = kv.shape[0]
+        q = x[:, :H * hd].reshape(-1, H, hd).transpose(0, 1)[:, rows]       # [H, R, hd]
+        k, vv = (kv[:, i * H * hd:(i + 1) * H * hd].reshape(T, H, hd).transpose(0, 1) for i in range(2))     # [H, T, hd]
         scale = 1.0 / math.sqrt(hd)
-        t = rows[:, None]
+        t = rows[:, None] + nh
         j = torch.arange(T)[None, :]
-        mask = (j <= t) & (j >= (t - win + 1).clamp_min(0))                 # the band of vocoder.py:325-332
+        bug = p.get("bug")                                                  # emulated faults of the carried form
+        lo = (rows[:, None] - win + 1).clamp_min(0) if bug == "window_ignores_nh" else (t - win + 1).clamp_min(0)
+        if bug == "drops_oldest" and nh == win - 1:
+            lo = lo.clamp_min(1)
+        mask = (j <= t) & (j >= lo)                                         # the band of vocoder.py:325-332
         sc = (q @ k.transpose(1, 2)) * scale
         sc = sc.masked_fill(~mask[None], float("-inf"))
         mx = sc.max(dim=-1, keepdim=True).values
@@ -554,7 +639,7 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
     if st.kind == "dwln":
         C = st.cols
         w, b, lw, lb = fw(p["w"])[:, 0, :], fw(p["b"]), fw(p["lw"]), fw(p["lb"])
-        xg = gather(env[st.src["x"]], C, rows, [k - 6 for k in range(7)], p.get("stale")).to(dt).reshape(len(rows), 7, C)
+        xg = gather(env[st.src["x"]], C, rows, [k - 6 for k in range(7)], carried(C)).to(dt).reshape(len(rows), 7, C)
         a = b + (xg * w.t()[None]).sum(dim=1) if dt == F64 else b + sum(xg[:, k] * w[:, k] for k in range(7))
         mean = a.mean(dim=-1, keepdim=True)
         d = a - mean
@@ -576,7 +661,7 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
         C = p["C"]
         w, b = fw(p["w"])[0], fw(p["b"])                                    # [C][7]
         wm = w.t().reshape(-1, 1)                                           # tap-major [7 C, 1]
-        xg = gather(env[st.src["x"]], C, rows, [k - 6 for k in range(7)], p.get("stale")).to(dt)
+        xg = gather(env[st.src["x"]], C, rows, [k - 6 for k in range(7)], carried(C)).to(dt)
         acc = xg @ wm + b
         v = torch.tanh(acc)
         err = None
@@ -597,6 +682,40 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
         x = whole(env[st.src["x"]], st.cols)[rows].to(dt)
         return Out(*stores(x, torch.zeros_like(x) if chk else None, p["alpha"]))
 
+    if st.kind in CARRY_KINDS:
+        # pure copies, restated on exact values (bf16 patterns survive from_raw / bf16_bits unchanged); bound 0
+        bug = p.get("bug")
+        if st.kind == "roll":
+            H, C = st.rows, st.cols
+            x = whole(env[st.src["x"]], C).to(F64)
+            prev = whole(env[st.src["prev"]], C).to(F64) if st.src["prev"] in env else torch.zeros(H, C, dtype=F64)
+            Tm = x.shape[0]
+            cat = torch.cat([prev, x], dim=0)
+            carry = cat[-H:].clone()
+            if bug == "tail_src_r" and Tm < H:                              # tail_in[r] in place of tail_in[r + T]
+                carry[:H - Tm] = prev[:H - Tm]
+            if bug == "chunk_only" and Tm < H:                              # rows that should come from the old carry
+                carry[:H - Tm] = 0
+            ref = {"front": prev, "carry": carry}
+        elif st.kind == "kvin":
+            prev = whole(env[st.src["prev"]], st.cols).to(F64)
+            W1 = p["W1"]
+            sh = 1 if bug == "off_by_one" else 0
+            ref = {"front": prev[torch.arange(W1 - st.rows, W1) - sh]}
+        else:
+            HD, W1 = p["HD"], st.rows
+            cat = whole(env[st.src["x"]], 3 * HD).to(F64)[:, HD:]
+            if "front" in st.src:
+                cat = torch.cat([whole(env[st.src["front"]], 2 * HD).to(F64), cat], dim=0)
+            n2 = min(W1, cat.shape[0])
+            carry = torch.zeros(W1, 2 * HD, dtype=F64)
+            carry[W1 - n2:] = cat[-n2:]
+            if bug == "writes_all_rows" and n2 < W1:                        # rows that do not exist yet: whatever lies before
+                carry[:W1 - n2] = cat[0]
+            ref = {"carry": carry}
+        ref = {k: v[rows].to(dt) for k, v in ref.items()}
+        return Out(ref, {k: (torch.zeros_like(v, dtype=F64) if chk else None) for k, v in ref.items()})
+
     if st.kind == "tof32":
         x = whole(env[st.src["x"]], st.cols)[rows].to(dt)
         return Out(*stores(x, torch.zeros_like(x) if chk else None))
@@ -604,10 +723,11 @@ def eval_stage(st: Stage, env: dict, W: Weights, rows: Optional[torch.Tensor] = 
 
 
 # ------------------------------------------------------------------------------------------------------ chains
-def chain_free(plan: List[Stage], weights: Dict[str, torch.Tensor], keep=()) -> dict:
+def chain_free(plan: List[Stage], weights: Dict[str, torch.Tensor], keep=(), env: Optional[dict] = None) -> dict:
     """The plan in float64 on its own outputs with the unrounded weights; returns the final buffers by logical name and,
-    for the stage names in `keep`, what that stage wrote (under the stage's name)."""
-    W, env, kept = Weights(weights, dev=False), {}, {}
+    for the stage names in `keep`, what that stage wrote (under the stage's name).  env: the buffers before the first
+    launch (a streamed chunk: the carries of the chunk before it)."""
+    W, env, kept = Weights(weights, dev=False), dict(env or {}), {}
     for st in plan:
         o = eval_stage(st, env, W, None, "free")
         for k, b in st.dst.items():
@@ -619,9 +739,10 @@ def chain_free(plan: List[Stage], weights: Dict[str, torch.Tensor], keep=()) -> 
 
 
 def check_trace(plan: List[Stage], trace: List[Dict[str, np.ndarray]], weights: Dict[str, torch.Tensor], seed: int = 0,
-                bm: int = 128) -> List["Verdict"]:
-    """The checker over a whole trace held in memory (the GPU test does the same in windows of launches)."""
-    W, env, out = Weights(weights, dev=True), {}, []
+                bm: int = 128, env: Optional[dict] = None) -> List["Verdict"]:
+    """The checker over a whole trace held in memory (the GPU test does the same in windows of launches).  env: the
+    buffers before the first launch (a streamed chunk: the carries recorded for the chunk before it); updated in place."""
+    W, env, out = Weights(weights, dev=True), ({} if env is None else env), []
     for st, outs in zip(plan, trace):
         out.append(check_stage(st, env, W, outs, select_rows(st.rows, st.halo, bm, seed)))
         for k, b in st.dst.items():
@@ -634,11 +755,12 @@ def raw_store(kind: str, v: torch.Tensor) -> np.ndarray:
 
 
 def chain_emulate(plan: List[Stage], weights: Dict[str, torch.Tensor], override: Optional[Dict[str, Stage]] = None,
-                  mutate: Optional[Dict[str, Callable]] = None) -> List[Dict[str, np.ndarray]]:
+                  mutate: Optional[Dict[str, Callable]] = None, env: Optional[dict] = None) -> List[Dict[str, np.ndarray]]:
     """A synthetic trace: every launch in float32 with the device's storage formats, on the outputs before it.
     override[name]: evaluate that launch as another Stage (an emulated bug in its parameters); mutate[name](outs):
-    alter what it stored.  Later launches run on the altered values, as they would on the device."""
-    W, env, trace = Weights(weights, dev=True), {}, []
+    alter what it stored.  Later launches run on the altered values, as they would on the device.  env: the buffers
+    before the first launch (a streamed chunk: the carries of the chunk before it); it is updated in place."""
+    W, env, trace = Weights(weights, dev=True), ({} if env is None else env), []
     for st in plan:
         o = eval_stage((override or {}).get(st.name, st), env, W, None, "emulate")
         outs = {k: raw_store(k, o.ref[k]) for k in st.dst}
@@ -674,6 +796,14 @@ def check_stage(st: Stage, env: dict, W: Weights, got: Dict[str, np.ndarray], ro
         g = from_raw(np.asarray(got[k]).reshape(st.rows, st.cols)[rows.numpy()]).to(F64)
         ref, err = o.ref[k].to(F64), o.err[k]
         assert g.shape == ref.shape == err.shape, (st.name, k, g.shape, ref.shape, err.shape)
+        if st.kind in CARRY_KINDS:                          # a copy: the bit patterns themselves
+            gb = np.asarray(got[k]).reshape(st.rows, st.cols)[rows.numpy()]
+            bad = torch.from_numpy(gb != bf16_bits(o.ref[k]))
+            v.checked += bad.numel()
+            v.flagged += int(bad.sum())
+            bad_rows |= bad.any(dim=1)
+            v.worst = max(v.worst, float("inf") if bool(bad.any()) else 0.0)
+            continue
         bound = half_ulp(torch.maximum(g.abs(), ref.abs()), k == "f32") + err
         diff = (g - ref).abs()
         bad = ~(diff <= bound)                              # NaN flags

@@ -259,3 +259,166 @@ def test_checker_flags_a_wrong_f32_residual_stream_and_encode_side_bugs():
     st = stage(plan, "enc.1.sc")
     bad = flagged(R.check_trace(plan, R.chain_emulate(plan, we, override={st.name: with_p(st, drop_bias=True)}), we))
     assert set(bad) == {st.name}
+
+
+# ------------------------------------------------------------------------------------------------ carried context
+STREAM_CHUNKS = (3, 1, 7, 1, 5)      # t0 = 0, 3, 4, 11, 12 at window 8: a fresh chunk, chunks below the halos, nh = 3, 4, 7, 7
+
+
+def run_stream(shape, w, codes, chunks, mode="emulate"):
+    """The stream chunk by chunk on its own carries: per chunk (plan, carries before it, trace or final env)."""
+    t0, car, out = 0, {}, []
+    for T in chunks:
+        plan = R.plan_stream(shape, codes[:, t0:t0 + T], t0, min(t0, shape.tf_window - 1))
+        if mode == "emulate":
+            env = dict(car)
+            res = R.chain_emulate(plan, w, env=env)
+        else:
+            res = env = R.chain_free(plan, w, env=car)
+        out.append((plan, car, res))
+        car = R.carries(env)
+        t0 += T
+    return out
+
+
+def test_chunked_emulation_equals_the_whole_emulation_bit_for_bit():
+    """Emulate mode: every arithmetic launch of every chunk stores what the whole decode stores in those rows, whatever
+    the chunking (chunks of one frame are below every halo; window 8 is passed within the stream; [1] * 12 covers the
+    first 12 frames: the codec is causal)."""
+    shape = tiny_codec_shape()
+    w = C.random_weights(shape, seed=0)
+    codes = rand_codes(shape, 40, 9)
+    wplan = R.plan_decode(shape, codes)
+    whole = {st.name: (st, outs) for st, outs in zip(wplan, R.chain_emulate(wplan, w))}
+    for chunks in ([40], [3, 7, 1, 20, 9], [1] * 12):
+        t0 = 0
+        for (plan, _, trace), T in zip(run_stream(shape, w, codes, chunks), chunks):
+            for st, outs in zip(plan, trace):
+                if st.kind in R.CARRY_KINDS:
+                    continue
+                wst, wouts = whole[st.name]
+                m = wst.rows // 40
+                for k, a in outs.items():
+                    assert np.array_equal(a, wouts[k][t0 * m:(t0 + T) * m]), (chunks, t0, st.name, k)
+            t0 += T
+
+
+def test_chunked_free_chain_reproduces_the_oracle_decode():
+    """Free mode: the streamed plan chained in float64 over its own carries is the codec: the oracle's decode of the
+    whole code matrix, within the bound of the one-shot plan."""
+    shape = tiny_codec_shape()
+    w = C.random_weights(shape, seed=0)
+    codes = rand_codes(shape, 40, 9)
+    orc = C.CodecOracle(shape, w)
+    for chunks in ([40], [3, 7, 1, 20, 9], [1] * 12):
+        n = sum(chunks)                                          # ([1] * 12: the first 12 frames of the code matrix)
+        want, _ = orc.decode(codes[None, :, :n], torch.tensor([n]))
+        bound = roundoff_bound(R.plan_decode(shape, codes[:, :n]))
+        audio = torch.cat([env["audio"][:, 0] for _, _, env in run_stream(shape, w, codes, chunks, "free")])
+        d = rel_rms(audio, want[0, 0])
+        print(f"stream {chunks}: float64 chain vs f32 oracle, relative RMS {d:.2e} (bound {bound:.2e})")
+        assert audio.shape == want[0, 0].shape and d <= bound, (chunks, d, bound)
+
+
+@pytest.fixture(scope="module")
+def tiny_stream():
+    shape = tiny_codec_shape()
+    w = C.random_weights(shape, seed=0)
+    codes = rand_codes(shape, sum(STREAM_CHUNKS), 11)
+    return shape, w, run_stream(shape, w, codes, STREAM_CHUNKS)
+
+
+def check_chunk(w, plan, before, trace):
+    """The verdicts of one chunk judged on the carries recorded before it (those the honest stream left)."""
+    return R.check_trace(plan, trace, w, env=dict(before))
+
+
+def faulty(tiny_stream, c, override=None, mutate=None, before=None):
+    """Chunk c emulated again with a fault (on the honest carries unless `before` says otherwise), judged on the honest
+    carries: {stage name: verdict} of the flagged launches."""
+    shape, w, runs = tiny_stream
+    plan, car, _ = runs[c]
+    env = dict(car if before is None else before)
+    trace = R.chain_emulate(plan, w, override=override, mutate=mutate, env=env)
+    return flagged(check_chunk(w, plan, car, trace)), plan
+
+
+def test_checker_passes_an_honest_emulated_stream_with_zero_flagged_elements(tiny_stream):
+    shape, w, runs = tiny_stream
+    kinds = set()
+    for c, (plan, car, trace) in enumerate(runs):
+        vs = check_chunk(w, plan, car, trace)
+        assert len(vs) == len(plan) and all(v.checked == st.rows * st.cols * len(st.dst) for v, st in zip(vs, plan))
+        assert not flagged(vs), (c, [(v.name, v.flagged, v.worst) for v in flagged(vs).values()])
+        kinds |= {v.kind for v in vs}
+        # the same chunk judged as one whose predecessor was not traced: on its own recorded front rows
+        assert not flagged(R.check_trace(plan, trace, w, env=R.seed_unlinked(plan, trace)))
+    assert {"roll", "kvin", "kvout"} <= kinds
+
+
+def test_checker_flags_the_carrying_faults(tiny_stream):
+    """Each fault of the carrying launches, at the launch, chunk and rows it touches, and nowhere else."""
+    shape, w, runs = tiny_stream
+    W1 = shape.tf_window - 1
+    # chunk 1 (one frame, t0 = 3): 2 rows at up.0 against halo 6
+    for bug in ("tail_src_r", "chunk_only"):
+        plan = runs[1][0]
+        st = stage(plan, "up.0.dwln.roll")
+        bad, _ = faulty(tiny_stream, 1, override={st.name: with_p(st, bug=bug)})
+        assert set(bad) == {st.name}, (bug, sorted(bad))
+        assert bad[st.name].rows and set(bad[st.name].rows) <= set(range(6 - 2)), (bug, bad[st.name].rows)
+    # the carried K/V one row off (chunk 2: nh = 4)
+    st = stage(runs[2][0], "post.1.kvin")
+    bad, _ = faulty(tiny_stream, 2, override={st.name: with_p(st, bug="off_by_one")})
+    assert set(bad) == {st.name} and bad[st.name].rows == list(range(4)), {k: v.rows for k, v in bad.items()}
+    # kv_out writes all W1 rows when only nh + T = 3 exist (chunk 0)
+    st = stage(runs[0][0], "post.0.kvout")
+    bad, _ = faulty(tiny_stream, 0, override={st.name: with_p(st, bug="writes_all_rows")})
+    assert set(bad) == {st.name} and bad[st.name].rows == list(range(W1 - 3)), {k: v.rows for k, v in bad.items()}
+    # chunk z of a batched call reads chunk z - 1's carry: another stream's carry in place of its own
+    other = run_stream(shape, w, rand_codes(shape, 9, 12), (4, 5))
+    st = stage(runs[4][0], "dec.0.u1.c7.roll")
+    key = st.src["prev"]
+    bad, _ = faulty(tiny_stream, 4, before={**runs[4][1], key: other[1][1][key]})
+    assert set(bad) == {st.name} and bad[st.name].rows == list(range(st.rows)), {k: v.rows[:8] for k, v in bad.items()}
+
+
+def test_checker_flags_the_carried_context_faults(tiny_stream):
+    """Each fault of an arithmetic launch in its carried-context form, at the launch, chunk and rows it touches."""
+    shape, w, runs = tiny_stream
+    # rope at position 0 instead of t0 (chunk 2, t0 = 4)
+    st = stage(runs[2][0], "post.0.rope")
+    bad, _ = faulty(tiny_stream, 2, override={st.name: with_p(st, t0=0)})
+    assert set(bad) == {st.name} and bad[st.name].rows == list(range(7)), {k: v.rows for k, v in bad.items()}
+    # the window counted from the chunk's first row (chunk 4: nh = 7 = window - 1, 5 frames): query 0 sees the same keys
+    st = stage(runs[4][0], "post.1.attn")
+    bad, _ = faulty(tiny_stream, 4, override={st.name: with_p(st, bug="window_ignores_nh")})
+    assert set(bad) == {st.name} and bad[st.name].rows and set(bad[st.name].rows) <= {1, 2, 3, 4}, {k: v.rows for k, v in bad.items()}
+    assert len(bad[st.name].rows) >= 3
+    # the oldest carried key dropped at nh = window - 1: only query 0 reaches it
+    bad, _ = faulty(tiny_stream, 4, override={st.name: with_p(st, bug="drops_oldest")})
+    assert set(bad) == {st.name} and bad[st.name].rows == [0], {k: v.rows for k, v in bad.items()}
+    # the final convolution reads zeros instead of its carry (chunk 3)
+    st = stage(runs[3][0], "final")
+    blind = dataclasses.replace(st, src={"x": st.src["x"]})
+    bad, _ = faulty(tiny_stream, 3, override={"final": blind})
+    assert set(bad) == {"final"} and bad["final"].rows and set(bad["final"].rows) <= set(range(6)) and 0 in bad["final"].rows
+    # z * gap left out of one stage's row base: the stage reads the neighbour chunk's last rows where its carry belongs
+    other = run_stream(shape, w, rand_codes(shape, 9, 12), (4, 5))
+    oplan, _, otrace = other[1]
+    st = stage(runs[4][0], "dec.1.u2.c7")                      # dilation 9: halo 54
+    src = next(o for s_, o in zip(oplan, otrace) if s_.name == "dec.1.u1.c1")["act"]   # what the neighbour's dec.1.u2.c7 read
+    tail = R.from_raw(src[-54:])
+    bad, _ = faulty(tiny_stream, 4, override={st.name: dataclasses.replace(st, src={"x": st.src["x"]}, p={**st.p, "stale": tail})})
+    assert set(bad) == {st.name} and bad[st.name].rows and set(bad[st.name].rows) <= set(range(54)) and 0 in bad[st.name].rows
+    # one element two ulp off in the last, partial row tile of a chunk (chunk 2: 7 frames, 224 rows at dec.0.u0.c1)
+    st = stage(runs[2][0], "dec.0.u0.c1")
+
+    def two_ulp(outs, st=st):
+        outs = {k: v.copy() for k, v in outs.items()}
+        a = outs["bf"]
+        assert (int(a[st.rows - 1, 5]) & 0x7F) < 0x7D
+        a[st.rows - 1, 5] += 2
+        return outs
+    bad, _ = faulty(tiny_stream, 2, mutate={st.name: two_ulp})
+    assert set(bad) == {st.name} and bad[st.name].flagged == 1 and bad[st.name].rows == [st.rows - 1]
