@@ -170,6 +170,13 @@ class ARHipEngine:
         `skip` launches of that kind pass first."""
         self._check(self.lib.ft_test_engine_fault(self._h, which, workgroup, skip), "ft_test_engine_fault")
 
+    def attn_plan(self):
+        """Test hook: (nsplit, xl, n_slots): the KV split count the last prefill / decode call picked, whether the
+        slow-stack frame engine is the XCD-local kernel, the rows of the KV cache."""
+        n, x, s = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.ft_test_ar_attn_plan(self._h, C.byref(n), C.byref(x), C.byref(s)), "ft_test_ar_attn_plan")
+        return n.value, x.value, s.value
+
     # ------------------------------------------------------------------ primitives
     @staticmethod
     def _sampling(temperature, top_p, repetition_penalty, seed=0, ban_eos=False) -> L.ft_sampling:

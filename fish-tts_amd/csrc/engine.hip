@@ -2109,6 +2109,16 @@ extern "C" ft_status ft_test_engine_fault(ft_ctx* ctx, int32_t which, int32_t wg
     return FT_OK;
 }
 
+// Test hook: what the attention of the last prefill / decode call ran on: its KV split count (pick_nsplit), whether the
+// slow-stack engine of this context is the XCD-local kernel, and the rows of the cache.  Host fields only.
+extern "C" ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t* xl, int32_t* n_slots) {
+    FT_TRY(ar_ready(ctx));
+    if (nsplit) *nsplit = ctx->nsplit;
+    if (xl) *xl = ctx->eng_on && ctx->eng_xl ? 1 : 0;
+    if (n_slots) *n_slots = ctx->n_slots;
+    return FT_OK;
+}
+
 extern "C" ft_status ft_ar_park(ft_ctx* ctx, int32_t slot) {
     FT_TRY(ar_ready(ctx));
     const ft_ar_config& c = ctx->c;

@@ -38,6 +38,12 @@ ft_status ft_ar_profile_frame(ft_ctx* ctx, int32_t frames, const ft_sampling* sp
  * launch inside a multi-frame graph).  Exercises the recovery described above. */
 ft_status ft_test_engine_fault(ft_ctx* ctx, int32_t which, int32_t wg, int32_t skip);
 
+/* Test hook (reads host fields only; no device work, nothing on the frame path): what the slow-stack attention of the LAST
+ * ft_ar_prefill / ft_ar_decode call on this context ran on.  *nsplit: the KV split count that call picked (launches and
+ * frame engine alike); *xl: 1 if the slow-stack frame engine is on and is the XCD-local kernel (one kv head per XCD), else 0;
+ * *n_slots: the rows of the KV cache (max_seq_len rounded up to 8).  Any pointer may be NULL. */
+ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t* xl, int32_t* n_slots);
+
 /* Test hook: one draw of the sampling kernel (inference.py:30-80) on caller-supplied logits.
  * cb = 0 draws from `vocab_size` logits, cb >= 1 from min(1024, codebook_size); window is the
  * (num_codebooks+1) x 16 penalty window of inference.py:187-191 or NULL (no penalty); q the Exp(1)

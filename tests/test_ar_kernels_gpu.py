@@ -315,6 +315,21 @@ def test_decode_attention_split_counts(fmt):
     assert {8, 16, 32} <= NSPLITS
 
 
+def test_decode_attention_long_contexts():
+    """bf16 at the 16/8 x 128 geometry, at the lengths where tests/test_engine_long_context_gpu.py holds the frame engine to
+    these launches bit for bit: a context of 8192 slots with pos 6143, 6144 and 8191 (32 splits of up to 256 positions, the
+    last row of the cache), and pos 1535, 1536 of a 4096-slot context at 16 splits (96 | 97 positions per split).  Bounds as
+    everywhere in this file."""
+    noxl = (("FT_NO_XL", "1"),)
+    e4 = engine("bf16", "16/8x128", 4096, env=noxl)
+    line16 = run_attn("bf16", "16/8x128", e4, 4096, [1535, 1536], want_nsplit=16)
+    run_attn("bf16", "16/8x128", e4, 4096, [1535], want_nsplit=16)
+    e8 = engine("bf16", "16/8x128", 8192, env=noxl)
+    line32 = run_attn("bf16", "16/8x128", e8, 8192, [6143, 6144, 8191], want_nsplit=32)
+    run_attn("bf16", "16/8x128", e8, 8192, [8186], pos_off=5, want_nsplit=32, qk_norm=False, with_bo=True)
+    print(f"\n16 splits: {line16}\n32 splits: {line32}")
+
+
 # ------------------------------------------------------------------------------------------------------ fast attention
 def fast_inputs(fmt, key, rows):
     k = ("fast", fmt, key)
