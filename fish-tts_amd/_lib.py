@@ -118,6 +118,10 @@ SYMBOLS = {
                                                C.POINTER(ft_join_params), _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), _P,
                                                _P]),
     "ft_test_level_hops": (C.c_int32, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ft_ride_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int32, _P, _P]),
+    "ft_codec_ride": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    "ft_codec_stream_begin_live": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ft_test_ride_streams": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "ft_codec_encode": (C.c_int32, [_P, _P, C.c_int64, _P, _P]),
     "ft_codec_enc_frame_len": (C.c_int32, [_P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),

@@ -18,7 +18,9 @@ one final flag per chunk: an utterance's last chunk is decoded with final=True, 
 last chunk went out, the stream's `finish()` gives the held-back tail; either way the tail is out before (i, b"").
 `speed` (a speaking rate) and `pitch` (a shift in semitones) are passed through to the streams in the same way:
 `stream(sample_rate, speed=speed, pitch=pitch)`, each keyword only when set.  A loudness target is refused (ValueError):
-the level stage needs the whole utterance."""
+the level stage needs the whole utterance.  `live_loudness` is what a stream takes instead: its streams are
+`stream(fx=...)` with the ride stage last, which holds back up to 1.1 s of output like any other tail; a stream that starts
+afresh at `max_frames` starts a fresh ride state with it."""
 from __future__ import annotations
 
 import queue
@@ -71,25 +73,26 @@ class ChunkCutter:
         self.done = True
 
 
-def checked_fx(fx=None, sample_rate=None, speed=None, pitch=None, loudness=None):
+def checked_fx(fx=None, sample_rate=None, speed=None, pitch=None, loudness=None, live_loudness=None):
     """The checked output stages of a call (codec_engine.OutputFx, imported when first needed, as the engines are): `fx`
     itself where the caller checked already, else the keywords checked now (ValueError for a bad one)."""
     if fx is not None:
         return fx
     from .codec_engine import OutputFx
-    return OutputFx.of(sample_rate, speed, pitch, loudness)
+    return OutputFx.of(sample_rate, speed, pitch, loudness, live_loudness)
 
 
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                       min_first_chunk: int = 10, sample_rate: Optional[int] = None,
-                      speed: Optional[float] = None, pitch: Optional[float] = None, fx=None) -> Iterator[Tuple[int, bytes]]:
+                      speed: Optional[float] = None, pitch: Optional[float] = None, fx=None,
+                      live_loudness: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
     """Yields (i, pcm) chunks of the n utterances `run` generates, in the order they become ready, and (i, b"") once
     after utterance i's last chunk.  `run` is called on a producer thread, the codec on a worker thread; abandoning the
     generator stops the producer at its next block of frames and joins both threads.  An exception of either thread is
     raised from the generator."""
     if chunk_tokens < 1 or min_first_chunk < 1:
         raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-    fx = checked_fx(fx, sample_rate, speed, pitch).no_level("stream_utterances")   # truthy: an output stage holds back a tail
+    fx = checked_fx(fx, sample_rate, speed, pitch, live_loudness=live_loudness).no_level("stream_utterances")   # truthy: an output stage holds back a tail
     cv = threading.Condition()
     cuts = [ChunkCutter(chunk_tokens, min_first_chunk) for _ in range(n)]
     ended = [False] * n                                 # end mark handed out (worker only)

@@ -42,25 +42,28 @@ class LevelInfo:
 
 @dataclass(frozen=True)
 class OutputFx:
-    """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent), `cents` (pitch) and `level` (loudness
-    target, hundredths of a LUFS), each None where the stage is absent - the codec's own rate (None or 44100), the model's
-    own pace (a speed that rounds to 100 percent), pitch (one that rounds to 0 cents) and level (no loudness given).  Built
-    once per call by of() and handed down to the native call as it is."""
+    """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent), `cents` (pitch), `level` (loudness
+    target, hundredths of a LUFS) and `live` (a stream's live loudness target, the same unit), each None where the stage is
+    absent - the codec's own rate (None or 44100), the model's own pace (a speed that rounds to 100 percent), pitch (one
+    that rounds to 0 cents), level (no loudness given) and ride stage (no live loudness given).  Built once per call by
+    of() and handed down to the native call as it is."""
     rate: Optional[int] = None
     pct: Optional[int] = None
     cents: Optional[int] = None
     level: Optional[int] = None
+    live: Optional[int] = None
 
     @classmethod
-    def of(cls, sample_rate=None, speed=None, pitch=None, loudness=None) -> "OutputFx":
+    def of(cls, sample_rate=None, speed=None, pitch=None, loudness=None, live_loudness=None) -> "OutputFx":
         """A caller's `sample_rate=` (an integer in [8000, 48000] whose reduced L = rate / gcd(rate, 44100) is at most 640:
         ft_resample_filter), `speed=` (a factor in [0.5, 2.0], kept as round(speed * 100): ft_timescaled_len) and `pitch=`
         (semitones in [-12, 12], kept as round(100 * pitch) cents: ft_pitch_filter; a plain shift, formants move with the
         pitch), then the two together (ft_pitch_ok: the time-scale stage under a pitch shift runs at speed / 2^(pitch / 12),
         which has to lie in [0.5, 2]), then `loudness=` (a target in LUFS in [-50, -5], kept as round(100 * loudness):
-        ft_codec_loudness; every item is brought to that integrated loudness, its sample peak held at -1 dBFS).  Anything
-        else raises ValueError, before any device work."""
-        rate = pct = cents = level = None
+        ft_codec_loudness; every item is brought to that integrated loudness, its sample peak held at -1 dBFS), or
+        `live_loudness=` (the same range and unit: a stream is ridden toward that loudness by a look-ahead gain rider,
+        ft_codec_stream_begin_live; not both).  Anything else raises ValueError, before any device work."""
+        rate = pct = cents = level = live = None
         if sample_rate is not None:
             if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)):
                 raise ValueError(f"sample_rate must be an integer, got {sample_rate!r}")
@@ -86,11 +89,19 @@ class OutputFx:
             if not -50.0 <= _number(loudness, "loudness must be a number of LUFS") <= -5.0:
                 raise ValueError(f"unsupported loudness {loudness!r}: a target in LUFS in [-50, -5]")
             level = int(round(float(loudness) * 100))
-        return cls(rate, pct, cents, level)
+        if live_loudness is not None:
+            if not -50.0 <= _number(live_loudness, "live_loudness must be a number of LUFS") <= -5.0:
+                raise ValueError(f"unsupported live_loudness {live_loudness!r}: a target in LUFS in [-50, -5]")
+            if loudness is not None:
+                raise ValueError("loudness and live_loudness together: one gain over the whole utterance, or a gain ridden "
+                                 "over a stream, not both")
+            live = int(round(float(live_loudness) * 100))
+        return cls(rate, pct, cents, level, live)
 
     def __bool__(self) -> bool:
         """Any stage at all: the call goes through the chain's native entry points, a stream holds back a tail."""
-        return self.rate is not None or self.pct is not None or self.cents is not None or self.level is not None
+        return (self.rate is not None or self.pct is not None or self.cents is not None or self.level is not None
+                or self.live is not None)
 
     def no_level(self, what: str) -> "OutputFx":
         """self, for a call that hands out audio before the utterance has ended: ValueError with a level."""
@@ -99,11 +110,17 @@ class OutputFx:
                              "loudness is known only there")
         return self
 
+    def no_live(self) -> "OutputFx":
+        """self, for a call that decodes whole items: ValueError with a ride stage (such a call has `loudness`)."""
+        if self.live is not None:
+            raise ValueError("live_loudness rides a stream: a call that decodes whole utterances takes loudness instead")
+        return self
+
     @property
     def emits_empty(self) -> bool:
-        """A stream's empty chunk is handed out: no stage, or a resampler only.  Behind a time-scale or pitch stage a chunk
-        that completes nothing gives no samples yet, and nothing is handed out for it."""
-        return self.pct is None and self.cents is None
+        """A stream's empty chunk is handed out: no stage, or a resampler only.  Behind a time-scale, pitch or ride stage a
+        chunk that completes nothing gives no samples yet, and nothing is handed out for it."""
+        return self.pct is None and self.cents is None and self.live is None
 
     @property
     def kw(self) -> dict:
@@ -120,6 +137,11 @@ class OutputFx:
     def native_level(self) -> int:
         """The level as the native entry points take it: hundredths of a LUFS, 0 without the stage."""
         return self.level or 0
+
+    @property
+    def native_live(self) -> int:
+        """The ride stage's target as the native entry points take it: hundredths of a LUFS, 0 without the stage."""
+        return self.live or 0
 
     @property
     def wav_rate(self) -> int:
@@ -359,7 +381,7 @@ class CodecHipEngine:
         return [dict(zip(("P", "L", "t0", "nh"), (int(v) for v in row))) for row in tab[:n.value]]
 
     def stream(self, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-               pitch: Optional[float] = None, fx: Optional[OutputFx] = None) -> "CodecStream":
+               pitch: Optional[float] = None, fx: Optional[OutputFx] = None, live_loudness: Optional[float] = None) -> "CodecStream":
         """A streamed decode with carried state: the chunks' waveforms concatenate to the waveform of one decode.
         `sample_rate`, `speed`, `pitch` (OutputFx.of), or `fx`, the checked value itself.
         `sample_rate`: the stream's output is resampled on the device; it holds back the samples whose
@@ -367,8 +389,11 @@ class CodecHipEngine:
         `speed`: the waveform is time-scaled on the device first; the stream holds back the samples that
         a later frame of the stage still adds to, in the same way.
         `pitch` (semitones): the waveform is pitch-shifted on the device (a plain shift: formants move with
-        the pitch) between the two; the stream's length does not change."""
-        return CodecStream(self, sample_rate, speed, pitch, fx)
+        the pitch) between the two; the stream's length does not change.
+        `live_loudness` (LUFS): the stream is ridden toward that loudness on the device, behind the other stages, by a gain
+        that looks one second ahead (ft_codec_stream_begin_live); the stream holds back up to 1.1 s of output until a
+        later chunk or the final one, and its length does not change."""
+        return CodecStream(self, sample_rate, speed, pitch, fx, live_loudness)
 
     MAX_STREAMS_PER_CALL = 64     # ft_codec_stream_decode_many
 
@@ -458,6 +483,48 @@ class CodecHipEngine:
         self._check(self.lib.ft_codec_loudness(self._h, x.ctypes.data_as(C.c_void_p), len(x), fx.wav_rate, fx.native_level,
                                                C.byref(info), y.ctypes.data_as(C.c_void_p)), "ft_codec_loudness")
         return LevelInfo.of(info), y
+
+    def ride(self, x: np.ndarray, sample_rate: Optional[int] = None, target: Optional[float] = None, nodes: bool = False):
+        """The ride stage alone on a host waveform at `sample_rate` (None: the codec's rate), on the device (ft_codec_ride):
+        x as one stream ridden toward `target` (LUFS, as stream's `live_loudness`; None: x's own samples).  Returns y, or
+        (y, g) with `nodes`: the ceil(n / H) + 1 gains at the hop borders."""
+        fx = OutputFx.of(sample_rate=sample_rate, live_loudness=target)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        y = np.empty(len(x), dtype=np.float32)
+        H = fx.wav_rate // 10
+        g = np.empty(-(-len(x) // H) + 1, dtype=np.float32)
+        self._check(self.lib.ft_codec_ride(self._h, x.ctypes.data_as(C.c_void_p), len(x), fx.wav_rate, fx.native_live,
+                                           y.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p)), "ft_codec_ride")
+        return (y, g) if nodes else y
+
+    def ride_plan(self, sample_rate: Optional[int], n_in: int, final: bool = False):
+        """(final nodes, samples emitted) of a live stream after n_in samples at sample_rate (ft_ride_plan; host only)."""
+        k, n = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.ft_ride_plan(OutputFx.of(sample_rate=sample_rate).wav_rate, int(n_in), 1 if final else 0,
+                                          C.byref(k), C.byref(n)), "ft_ride_plan")
+        return k.value, n.value
+
+    def test_ride_streams(self, xs: Sequence[np.ndarray], sample_rate: int, target: int, cuts: Sequence[int]):
+        """Test hook (ft_test_ride_streams): the waveforms xs as carried streams of the ride stage alone, fed in
+        len(cuts) + 1 calls cut at the sample positions `cuts`; target in hundredths of a LUFS.  Returns (ys, nodes,
+        emitted): per stream its samples and nodes, and emitted (len(cuts) + 1, B)."""
+        xs = [np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1)) for x in xs]
+        B = len(xs)
+        n = np.array([len(x) for x in xs], dtype=np.int64)
+        stride = int(max(1, n.max()))
+        H = int(sample_rate) // 10
+        x = np.zeros((B, stride), dtype=np.float32)
+        for b, it in enumerate(xs):
+            x[b, :len(it)] = it
+        cuts = np.ascontiguousarray(np.asarray(list(cuts), dtype=np.int64).reshape(-1))
+        y = np.zeros((B, stride), dtype=np.float32)
+        g = np.zeros((B, stride // H + 2), dtype=np.float32)
+        emitted = np.zeros((len(cuts) + 1, B), dtype=np.int64)
+        self._check(self.lib.ft_test_ride_streams(self._h, x.ctypes.data_as(C.c_void_p), B, stride, n.ctypes.data_as(C.c_void_p),
+                                                  int(sample_rate), int(target), cuts.ctypes.data_as(C.c_void_p), len(cuts),
+                                                  y.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+                                                  emitted.ctypes.data_as(C.c_void_p)), "ft_test_ride_streams")
+        return ([y[b, :n[b]] for b in range(B)], [g[b, :-(-int(n[b]) // H) + 1] for b in range(B)], emitted)
 
     def test_level_hops(self) -> np.ndarray:
         """Test hook (ft_test_level_hops): the hop sums of the last levelled call."""
@@ -553,6 +620,7 @@ class CodecHipEngine:
         same for every item; `levels`: a list that receives one LevelInfo per item.  Returns (audio float32, cuts (n, 2)
         int64: the samples [a, e) kept of every item)."""
         fx = OutputFx.of(sample_rate, speed, pitch, loudness) if fx is None else fx
+        fx.no_live()
         items = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in codes_list]
         for c in items:
             if c.ndim != 2 or c.shape[0] != self.R:
@@ -614,6 +682,7 @@ class CodecHipEngine:
         that leaves every length as it is.  `loudness` (LUFS): every row is brought to that integrated loudness on the
         device, behind the other stages (ft_codec_decode_level); `levels`: a list that receives one LevelInfo per row."""
         fx = OutputFx.of(sample_rate, speed, pitch, loudness) if fx is None else fx
+        fx.no_live()
         codes = np.asarray(codes)
         if codes.ndim == 2:
             codes = codes[None]
@@ -652,12 +721,15 @@ class CodecStream:
     convolution input - is carried)."""
 
     def __init__(self, engine: CodecHipEngine, sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                 pitch: Optional[float] = None, fx: Optional[OutputFx] = None):
+                 pitch: Optional[float] = None, fx: Optional[OutputFx] = None, live_loudness: Optional[float] = None):
         self.engine = engine
-        self.fx = (OutputFx.of(sample_rate, speed, pitch) if fx is None else fx).no_level("a codec stream")   # falsy: no output stage, nothing held back
+        self.fx = (OutputFx.of(sample_rate, speed, pitch, live_loudness=live_loudness) if fx is None else fx).no_level("a codec stream")   # falsy: no output stage, nothing held back
         self._h = C.c_void_p()
         if not self.fx:
             engine._check(engine.lib.ft_codec_stream_begin(engine._h, C.byref(self._h)), "ft_codec_stream_begin")
+        elif self.fx.live is not None:
+            engine._check(engine.lib.ft_codec_stream_begin_live(engine._h, *self.fx.native, self.fx.native_live, C.byref(self._h)),
+                          "ft_codec_stream_begin_live")
         else:
             engine._check(engine.lib.ft_codec_stream_begin_fxp(engine._h, *self.fx.native, C.byref(self._h)),
                           "ft_codec_stream_begin_fxp")
@@ -669,6 +741,7 @@ class CodecStream:
     rate = property(lambda self: self.fx.rate)      # None: the codec's own rate
     pct = property(lambda self: self.fx.pct)        # None: the model's own pace
     cents = property(lambda self: self.fx.cents)    # None: the model's own pitch
+    live = property(lambda self: self.fx.live)      # None: no ride stage
 
     @property
     def closes_on_final(self) -> bool:

@@ -20,7 +20,7 @@ using chain::ChainPlan; using chain::FxDesc; using chain::StageChain; using chai
 using chain::RS_FI; using chain::RS_MAX_RATE;
 static_assert(chain::RS_LDS == RS_LDS && chain::TS_N == TS_N && chain::TS_HS == TS_HS && chain::TS_D == TS_D &&
               chain::TS_CARRY == TS_CARRY && chain::PS_SHIFT == PS_SHIFT && chain::PS_PHASES == PS_PHASES &&
-              chain::LV_WARM_HOPS == LV_WARM,
+              chain::LV_WARM_HOPS == LV_WARM && chain::RD_A == RD_LOOK && chain::RD_R == RD_SLEW,
               "fx_chain.h and codec_kernels.h disagree");
 static_assert(sizeof(ft_level_info) == 32 && offsetof(LevelItem, L) + sizeof(ft_level_info) == sizeof(LevelItem) &&
               offsetof(ft_level_info, peak) == 8 && offsetof(ft_level_info, capped) == 24,
@@ -101,6 +101,15 @@ struct CodecState {
     float *lv_peaks = nullptr, *lv_x = nullptr;
     size_t lv_cap = 0, lv_xcap = 0, lv_nhops = 0;
     std::vector<char> lv_up, lv_down;
+    // ride stage (ft_codec_stream_begin_live, ft_codec_ride): the segment table and the buffer the emitted samples of a call
+    // lie in back to back, allocated with the first live stream; the state of ft_codec_ride's one waveform (hop sums, v,
+    // peaks, nodes), which grows like the level stage's buffers
+    RdSeg* rd_seg = nullptr;
+    float* rd_out = nullptr;
+    size_t rd_cap = 0;
+    double *rd_e = nullptr, *rd_v = nullptr;
+    float *rd_p = nullptr, *rd_g = nullptr;
+    size_t rd_ecap = 0, rd_vcap = 0, rd_pcap = 0, rd_gcap = 0;
     // ---- encode side
     struct EncUnit { float *a0, *a2; ConvW c7, c1; };
     struct EncBlock { EncUnit u[3]; float* a3; ConvW sc; int s, cin, cout; std::vector<TfLayer> tf; float* tf_norm = nullptr; };
@@ -958,6 +967,7 @@ struct Fx {   // the output stages of a call: resampler segments, and the time-s
     std::vector<RsSeg> rs;
     std::vector<TsSeg> ts;
     std::vector<PsSeg> ps;
+    std::vector<RdSeg> rd;     // the ride stage behind the resampler: none, or one per resampler segment (a call with a live stream)
 };
 
 // Time-scales fx.ts (their inputs written earlier on the codec's stream) into ts_out, back to back; segment g's output is
@@ -1016,7 +1026,67 @@ static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host, 
         const int64_t n = off;
         FT_TRY(level_enqueue(ctx, 1, &s->rs_out, &n, lv->rate, lv->target));
     }
-    if (off > 0) FT_HIP(ctx, hipMemcpyAsync(host, s->rs_out, (size_t)off * sizeof(float), kind, st));
+    if (off > 0 && host) FT_HIP(ctx, hipMemcpyAsync(host, s->rs_out, (size_t)off * sizeof(float), kind, st));
+    return FT_OK;
+}
+
+// ---- ride stage (RdSeg and the three kernels in codec_kernels.h; fishtts_hip.h states it, fx_chain.h plans it)
+constexpr size_t RD_MAX_HELD = (size_t)(chain::RD_A + 1) * (RS_MAX_RATE / 10);   // a stream holds back less than this
+
+// The segment table and room for `need` emitted samples.
+static ft_status rd_alloc(ft_ctx* ctx, size_t need) {
+    CodecState* s = ctx->codec;
+    if (!s->rd_seg) FT_TRY(cmalloc(ctx, &s->rd_seg, (size_t)RS_MAX_SEGS));
+    return cgrow(ctx, &s->rd_out, &s->rd_cap, need);
+}
+
+// One stream's ride segment for a call (x: its new samples), from its record and the call's plan; without the stage a copy.
+static RdSeg rd_seg_of(const chain::RdStage& r, const chain::RdPlan& q, const float* x) {
+    RdSeg g;
+    memset(&g, 0, sizeof g);
+    g.x = x;
+    g.n = (int)q.in;
+    g.target = r.target;
+    g.H = 1;
+    if (r.target == 0) return g;
+    g.cin = r.carry[r.par];
+    g.cout = r.carry[r.par ^ 1];
+    g.e = r.e; g.v = r.v; g.p = r.p; g.g = r.g;
+    chain::lv_design(r.rate, g.c);
+    g.ceiling = chain::lv_ceiling();
+    g.nin = r.nin; g.base = r.base; g.base1 = q.base; g.out0 = r.nout; g.out1 = r.nout + q.out;
+    g.H = r.H;
+    g.h0 = r.peaks; g.h1 = q.peaks; g.W = q.hops; g.k0 = r.nodes; g.k1 = q.nodes;
+    return g;
+}
+
+// The ride stage over fx.rd (segment j reads resampler segment j's output) into rd_out, back to back, and the copy of all
+// emitted samples to `host`; the caller synchronizes.
+static ft_status rd_enqueue(ft_ctx* ctx, Fx& fx, float* host) {
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    long long off = 0, hops = 0, mx = 0;
+    bool nodes = false;
+    for (size_t j = 0; j < fx.rd.size(); ++j) {
+        RdSeg& g = fx.rd[j];
+        if (!g.x) g.x = fx.rs[j].y;
+        g.y = s->rd_out + off;
+        const long long out = g.target != 0 ? g.out1 - g.out0 : g.n;
+        off += out;
+        hops = std::max(hops, (long long)g.h1 - g.h0);
+        nodes = nodes || g.k1 > g.k0;
+        mx = std::max({mx, out, g.target != 0 ? g.nin + g.n - g.base1 : 0LL});
+    }
+    if ((size_t)off > s->rd_cap) return ft_fail(ctx, FT_ERR_STATE, "ride: output buffer too small");
+    const unsigned n = (unsigned)fx.rd.size();
+    FT_HIP(ctx, hipMemcpyAsync(s->rd_seg, fx.rd.data(), n * sizeof(RdSeg), hipMemcpyHostToDevice, st));
+    if (hops > 0) ride_hop_kernel<<<dim3((unsigned)((hops + RD_HOP_THREADS - 1) / RD_HOP_THREADS), 1, n), RD_HOP_THREADS, 0, st>>>(s->rd_seg);
+    if (nodes) ride_node_kernel<<<n, RD_NODE_THREADS, 0, st>>>(s->rd_seg);
+    if (mx > 0) {
+        const int gx = (int)std::min(1024LL, (mx + RD_APPLY_THREADS - 1) / RD_APPLY_THREADS);
+        ride_apply_kernel<<<dim3(gx, 1, n), RD_APPLY_THREADS, 0, st>>>(s->rd_seg);
+    }
+    if (off > 0) FT_HIP(ctx, hipMemcpyAsync(host, s->rd_out, (size_t)off * sizeof(float), hipMemcpyDeviceToHost, st));
     return FT_OK;
 }
 
@@ -1204,8 +1274,10 @@ static ft_status call_tail(ft_ctx* ctx, Fx* fx, float* host, size_t plain, const
     CodecState* s = ctx->codec;
     if (fx && !fx->ts.empty()) FT_TRY(ts_enqueue(ctx, *fx));
     if (fx && !fx->ps.empty()) FT_TRY(ps_enqueue(ctx, fx->ps, fx->rs));
-    if (fx) FT_TRY(rs_enqueue(ctx, fx->rs, host, kind, lv));
-    else {
+    if (fx) {
+        FT_TRY(rs_enqueue(ctx, fx->rs, fx->rd.empty() ? host : nullptr, kind, lv));
+        if (!fx->rd.empty()) FT_TRY(rd_enqueue(ctx, *fx, host));    // the ride stage hands out the call's samples
+    } else {
         if (lv) {
             const int64_t np = (int64_t)plain;
             FT_TRY(level_enqueue(ctx, 1, &s->audio, &np, lv->rate, lv->target));
@@ -1335,6 +1407,7 @@ extern "C" ft_status ft_codec_stream_decode(ft_ctx* ctx, ft_codec_stream* sc, co
     if (sc->fx.rs.tab) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
     if (sc->fx.ts.on) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another speed (ft_codec_stream_decode_many_at)");
     if (sc->fx.ps.tab) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened at another pitch (ft_codec_stream_decode_many_at)");
+    if (sc->fx.rd.target != 0) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode: a stream opened with a live loudness (ft_codec_stream_decode_many_at)");
     const ft_codec_config& c = ctx->cc;
     if (T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: chunk longer than max_frames");
     if (sc->t0 + T > c.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode: stream longer than max_frames (rope table)");
@@ -1469,6 +1542,7 @@ static ft_status many_check(ft_ctx* ctx, const std::string& fn, int n, ft_codec_
         if (!at && sc->fx.rs.tab) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another sample rate (ft_codec_stream_decode_many_at)");
         if (!at && sc->fx.ts.on) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another speed (ft_codec_stream_decode_many_at)");
         if (!at && sc->fx.ps.tab) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened at another pitch (ft_codec_stream_decode_many_at)");
+        if (!at && sc->fx.rd.target != 0) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream opened with a live loudness (ft_codec_stream_decode_many_at)");
         if (at && sc->finished) return ft_fail(ctx, FT_ERR_STATE, fn + ": a stream whose final chunk went out");
         for (int i = 0; i < j; ++i)
             if (streams[i] == sc) return ft_fail(ctx, FT_ERR_ARG, fn + ": a stream named twice");
@@ -1495,7 +1569,8 @@ extern "C" ft_status ft_codec_stream_decode_many(ft_ctx* ctx, int32_t n, ft_code
 // The segments of one waveform's stages for a call: `x` holds the call's codec samples, `j` is the waveform's place in the
 // call (its resampler segment, which every waveform has: the copy out), `deltas` the test hooks' d_k.  A stage reads the
 // current copy of its carry and writes the other; ts_enqueue and ps_enqueue point the later stages at the earlier ones' output.
-static void chain_segs(const StageChain& c, const ChainPlan& p, const float* x, int j, int* deltas, Fx& fx) {
+// `ride`: the call has a live stream, and every waveform gets a ride segment behind its resampler segment (a copy without the stage).
+static void chain_segs(const StageChain& c, const ChainPlan& p, const float* x, int j, int* deltas, Fx& fx, bool ride = false) {
     const chain::TsStage& t = c.ts;
     if (t.on)
         fx.ts.push_back(TsSeg{x, t.carry[t.par], t.carry[t.par ^ 1], t.state[t.par], t.state[t.par ^ 1], nullptr, deltas, t.nin, t.base,
@@ -1507,6 +1582,7 @@ static void chain_segs(const StageChain& c, const ChainPlan& p, const float* x, 
     const chain::RsStage& r = c.rs;
     fx.rs.push_back(RsSeg{x, nullptr, r.carry[r.par], r.carry[r.par ^ 1], nullptr, r.nin, r.nout, (int)p.rs.in, (int)p.rs.out, 1, 1, 0, 0});
     if (r.tab) { RsSeg& g = fx.rs.back(); g.w = r.tab->w; g.L = r.tab->L; g.M = r.tab->M; g.K = r.tab->K; }
+    if (ride) fx.rd.push_back(rd_seg_of(c.rd, p.rd, nullptr));   // (rd_enqueue points it at the resampler segment's output)
 }
 
 // The output stages of one item of n_in codec samples decoded from zero state: a fresh input to each stage, zeros before
@@ -1578,10 +1654,10 @@ extern "C" int64_t ft_resampled_len(int32_t sample_rate, int64_t n_in) {
 }
 
 // A call's chain from its three values, judged without a lock and before anything else: the rate, then the speed, then
-// the cents, then the pair, then the level.  `fn` names the entry point in the message.
-static ft_status fx_refuse(ft_ctx* ctx, const std::string& fn, int rate, int pct, int cents, FxDesc* d, int level = 0) {
+// the cents, then the pair, then the level, then the ride stage's target.  `fn` names the entry point in the message.
+static ft_status fx_refuse(ft_ctx* ctx, const std::string& fn, int rate, int pct, int cents, FxDesc* d, int level = 0, int live = 0) {
     const char* why = nullptr;
-    switch (d->make(rate, pct, cents, level, &why)) {
+    switch (d->make(rate, pct, cents, level, live, &why)) {
     case FxDesc::RATE: return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why + " (" + std::to_string(rate) + ")");
     case FxDesc::SPEED: return ft_fail(ctx, FT_ERR_ARG, fn + ": speed outside [50, 200] percent (" + std::to_string(pct) + ")");
     case FxDesc::CENTS: return ft_fail(ctx, FT_ERR_ARG, fn + ": pitch outside [-1200, 1200] cents (" + std::to_string(cents) + ")");
@@ -1590,6 +1666,8 @@ static ft_status fx_refuse(ft_ctx* ctx, const std::string& fn, int rate, int pct
                                             std::to_string(cents) + " cents)");
     case FxDesc::LEVEL:
         return ft_fail(ctx, FT_ERR_ARG, fn + ": loudness outside [-5000, -500] hundredths of a LUFS (" + std::to_string(level) + ")");
+    case FxDesc::LIVE:
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": live loudness outside [-5000, -500] hundredths of a LUFS (" + std::to_string(live) + ")");
     case FxDesc::OK: break;
     }
     return FT_OK;
@@ -1602,10 +1680,15 @@ static ft_status fx_prepare(ft_ctx* ctx, FxDesc* d, size_t hops = 0) {
     FT_TRY(rs_table(ctx, d->rate, &d->rs));
     if (d->cents != 0) {
         FT_TRY(ps_table(ctx, d->cents, &d->ps));
-        return ps_alloc(ctx);
+        FT_TRY(ps_alloc(ctx));
+    } else if (d->pct != 100) {
+        FT_TRY(ts_alloc(ctx));
+    } else if (d->K > 0 || d->live != 0) {
+        FT_TRY(rs_alloc(ctx));       // (a live stream's samples pass through the resampler's buffer at any rate)
     }
-    if (d->pct != 100) return ts_alloc(ctx);
-    return d->K > 0 ? rs_alloc(ctx) : FT_OK;
+    // a live stream: everything a call's resampler can give, and what 64 streams can hold back
+    // (kept in step with the resampler's buffer once the context has had a live stream: a later chain may widen that one)
+    return d->live != 0 || ctx->codec->rd_seg ? rd_alloc(ctx, ctx->codec->rs_cap + (size_t)RS_MAX_SEGS * RD_MAX_HELD) : FT_OK;
 }
 
 extern "C" int64_t ft_timescaled_len(int32_t speed_pct, int64_t n_in) {
@@ -1873,11 +1956,17 @@ extern "C" ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_
     return FT_OK;
 }
 
+// Hops (and nodes) of the longest waveform a stream or ft_codec_ride can see at `rate`: max_frames frames at speed 0.5.
+static size_t rd_max_hops(ft_ctx* ctx, int rate) {
+    const long long most = (2LL * ctx->cc.max_frames * ctx->codec->frame_len * rate + RS_FI - 1) / RS_FI;
+    return (size_t)(most / chain::lv_hop(rate)) + 4;
+}
+
 static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sample_rate, int32_t pct, ft_codec_stream** out,
-                                 int32_t cents = 0) {
+                                 int32_t cents = 0, int32_t live = 0) {
     if (!ctx || !out) return FT_ERR_ARG;
     FxDesc d;
-    FT_TRY(fx_refuse(ctx, fn, sample_rate, pct, cents, &d));
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, pct, cents, &d, 0, live));
     FT_TRY(codec_ready(ctx));
     CodecState* s = ctx->codec;
     {
@@ -1907,6 +1996,17 @@ static ft_status stream_begin_fx(ft_ctx* ctx, const std::string& fn, int32_t sam
         zalloc(&c.ts.state[k], (size_t)TS_STATE);
     }
     for (int k = 0; k < 2 && c.ps.tab; ++k) zalloc(&c.ps.carry[k], (size_t)c.ps.tab->K);
+    if (c.rd.target != 0) {   // the ride stage: two carries, and a hop sum, a peak, a v and a node per hop of the longest stream
+        const size_t hops = rd_max_hops(ctx, d.rate);
+        float *e = nullptr, *v = nullptr;
+        for (int k = 0; k < 2; ++k) zalloc(&c.rd.carry[k], (size_t)(chain::RD_A + 1) * c.rd.H);
+        zalloc(&e, 2 * hops);
+        zalloc(&v, 2 * hops);
+        zalloc(&c.rd.p, hops);
+        zalloc(&c.rd.g, hops);
+        c.rd.e = (double*)e;
+        c.rd.v = (double*)v;
+    }
     ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
@@ -1931,6 +2031,12 @@ extern "C" ft_status ft_codec_stream_begin_fxp(ft_ctx* ctx, int32_t sample_rate,
     return stream_begin_fx(ctx, "ft_codec_stream_begin_fxp", sample_rate, speed_pct, out, pitch_cents);
 }
 
+extern "C" ft_status ft_codec_stream_begin_live(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents,
+                                                int32_t live, ft_codec_stream** out) {
+    return stream_begin_fx(ctx, live != 0 ? "ft_codec_stream_begin_live" : "ft_codec_stream_begin_fxp", sample_rate, speed_pct, out,
+                           pitch_cents, live);
+}
+
 extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_codec_stream* const* streams, const int32_t* codes,
                                                     const int32_t* lens, const int32_t* final, float* audio, int64_t* out_lens) {
     if (!ctx) return FT_ERR_ARG;
@@ -1941,8 +2047,8 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     CodecState* s = ctx->codec;
     const int fl = s->frame_len;
     // what every stream's stages take and emit in this call, walked in chain order (fx_chain.h)
-    long long total_out = 0, total_ts = 0, total_ps = 0;
-    bool any_fx = false;
+    long long total_out = 0, total_ts = 0, total_ps = 0, total_rd = 0;
+    bool any_fx = false, ride = false;
     std::vector<ChainPlan> plan(n);
     for (int j = 0; j < n; ++j) {
         const StageChain& c = streams[j]->fx;
@@ -1950,10 +2056,15 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
         if (c.ts.held(plan[j].ts) > TS_CARRY) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: time-scale carry out of step");
         if (c.ts.on) total_ts += plan[j].ts.out;
         if (c.ps.tab) total_ps += plan[j].ps.out;
+        if (c.rd.held(plan[j].rd) >= (long long)(chain::RD_A + 1) * c.rd.H || (size_t)plan[j].rd.nodes > (c.rd.target != 0 ? rd_max_hops(ctx, c.rd.rate) : 1))
+            return ft_fail(ctx, FT_ERR_STATE, "ft_codec_stream_decode_many_at: ride carry out of step");
         total_out += plan[j].rs.out;
+        total_rd += plan[j].rd.out;
         any_fx = any_fx || c.any();
+        ride = ride || c.rd.target != 0;
     }
-    if (any_fx && ((size_t)total_out > s->rs_cap || (size_t)total_ts > s->ts_cap || (size_t)total_ps > s->ts_cap))
+    if (any_fx && ((size_t)total_out > s->rs_cap || (size_t)total_ts > s->ts_cap || (size_t)total_ps > s->ts_cap ||
+                   (ride && (size_t)total_rd > s->rd_cap)))
         return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_stream_decode_many_at: output buffer");
     // the codec runs over the streams with frames (their code blocks are back to back, as the call's)
     std::vector<ft_codec_stream*> cs;
@@ -1965,13 +2076,13 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     TraceScope untraced(s, false);   // the launch trace covers ft_codec_stream_decode_many only: an armed trace is dropped here
     if (!any_fx) {   // the codec's rate and pace only: ft_codec_stream_decode_many
         if (!cs.empty()) FT_TRY(decode_many(ctx, (int)cs.size(), cs.data(), codes, cl.data(), audio));
-        for (int j = 0; j < n; ++j) out_lens[j] = plan[j].rs.out;
+        for (int j = 0; j < n; ++j) out_lens[j] = plan[j].rd.out;
         return FT_OK;
     }
     Fx fx;
     long long P = 0;
     for (int j = 0; j < n; ++j) {
-        chain_segs(streams[j]->fx, plan[j], s->audio + P * fl, j, nullptr, fx);
+        chain_segs(streams[j]->fx, plan[j], s->audio + P * fl, j, nullptr, fx, ride);
         P += lens[j];
     }
     if (!cs.empty()) {
@@ -1981,11 +2092,136 @@ extern "C" ft_status ft_codec_stream_decode_many_at(ft_ctx* ctx, int32_t n, ft_c
     }
     for (int j = 0; j < n; ++j) {
         ft_codec_stream* sc = streams[j];
-        out_lens[j] = plan[j].rs.out;
+        out_lens[j] = plan[j].rd.out;
         if (!sc->fx.any()) continue;
         sc->fx.commit(plan[j]);
         sc->finished = final && final[j];
     }
+    return FT_OK;
+}
+
+// ---- ride stage alone (fishtts_hip.h: ft_ride_plan, ft_codec_ride; fishtts_hip_test.h: ft_test_ride_streams)
+extern "C" ft_status ft_ride_plan(int32_t sample_rate, int64_t n_in, int32_t final, int64_t* nodes, int64_t* n_out) {
+    int l = 1, m = 1, k = 0;
+    if (n_in < 0 || chain::rs_design(sample_rate, &l, &m, &k, nullptr)) return FT_ERR_ARG;
+    const chain::RdPlan p = chain::rd_plan(chain::lv_hop(sample_rate), n_in, final != 0);
+    if (nodes) *nodes = p.nodes;
+    if (n_out) *n_out = p.out;
+    return FT_OK;
+}
+
+// What the launches of a ride call left behind, after the call's one synchronize.
+static ft_status rd_finish(ft_ctx* ctx) {
+    FT_HIP(ctx, hipStreamSynchronize(ctx->codec->stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("ride launch: ") + hipGetErrorString(e));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_ride(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, int32_t target, float* y,
+                                   float* nodes) {
+    const std::string fn = "ft_codec_ride";
+    if (!ctx) return FT_ERR_ARG;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d, 0, target));
+    FT_TRY(codec_ready(ctx));
+    if ((!x && n > 0) || !y || n < 0) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    CodecState* s = ctx->codec;
+    const int64_t most = (2 * (int64_t)ctx->cc.max_frames * s->frame_len * RS_MAX_RATE + RS_FI - 1) / RS_FI;
+    if (n > most) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": longer than the longest item a decode gives");
+    chain::RdStage r = d.fresh().rd;
+    const size_t nn = (size_t)((n + r.H - 1) / r.H) + 1;
+    if (target == 0) {   // no stage
+        if (n > 0) memcpy(y, x, (size_t)n * sizeof(float));
+        for (size_t k = 0; nodes && k < nn; ++k) nodes[k] = 1.f;
+        return FT_OK;
+    }
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    FT_TRY(rd_alloc(ctx, (size_t)std::max(n, (int64_t)4)));
+    FT_TRY(cgrow(ctx, &s->lv_x, &s->lv_xcap, (size_t)std::max(n, (int64_t)4)));
+    FT_TRY(cgrow(ctx, &s->rd_e, &s->rd_ecap, nn));
+    FT_TRY(cgrow(ctx, &s->rd_v, &s->rd_vcap, nn));
+    FT_TRY(cgrow(ctx, &s->rd_p, &s->rd_pcap, nn));
+    FT_TRY(cgrow(ctx, &s->rd_g, &s->rd_gcap, nn));
+    r.e = s->rd_e; r.v = s->rd_v; r.p = s->rd_p; r.g = s->rd_g;
+    if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->lv_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    Fx fx;
+    fx.rd.push_back(rd_seg_of(r, r.plan(n, true), s->lv_x));     // a stream whose one call is its last: nothing carried in or out
+    FT_TRY(rd_enqueue(ctx, fx, y));
+    if (nodes) FT_HIP(ctx, hipMemcpyAsync(nodes, s->rd_g, nn * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    return rd_finish(ctx);
+}
+
+extern "C" ft_status ft_test_ride_streams(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, const int64_t* n, int32_t sample_rate,
+                                          int32_t target, const int64_t* cuts, int32_t ncuts, float* y, float* nodes, int64_t* emitted) {
+    const std::string fn = "ft_test_ride_streams";
+    if (!ctx) return FT_ERR_ARG;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d, 0, target));
+    FT_TRY(codec_ready(ctx));
+    if (!x || !n || !y || !nodes || !emitted || B < 1 || B > RS_MAX_SEGS || stride < 1 || ncuts < 0 || (ncuts > 0 && !cuts) || target == 0)
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n[b] < 0 || n[b] > stride) return ft_fail(ctx, FT_ERR_ARG, fn + ": a waveform longer than the stride");
+        total += n[b];
+    }
+    for (int j = 0; j < ncuts; ++j)
+        if (cuts[j] < (j ? cuts[j - 1] : 0)) return ft_fail(ctx, FT_ERR_ARG, fn + ": cuts must not descend");
+    CodecState* s = ctx->codec;
+    const int H = chain::lv_hop(sample_rate);
+    const size_t nn = (size_t)(stride / H) + 2;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    FT_TRY(rd_alloc(ctx, (size_t)std::max(total, (int64_t)4)));
+    FT_TRY(cgrow(ctx, &s->lv_x, &s->lv_xcap, (size_t)std::max(total, (int64_t)4)));
+    // the streams' state in one allocation, freed when the call ends: per stream two carries, e, v, p, g
+    const size_t held = (size_t)(chain::RD_A + 1) * H, per = 2 * held + 6 * nn;
+    float* blk = nullptr;
+    if (hipMalloc((void**)&blk, (size_t)B * per * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return ft_fail(ctx, FT_ERR_NOMEM, fn + ": the streams' state");
+    }
+    struct Free { float* p; ~Free() { hipFree(p); } } guard{blk};
+    FT_HIP(ctx, hipMemsetAsync(blk, 0, (size_t)B * per * sizeof(float), s->stream));
+    std::vector<chain::RdStage> st((size_t)B, d.fresh().rd);
+    for (int b = 0; b < B; ++b) {
+        float* q = blk + (size_t)b * per;
+        st[b].e = (double*)q;
+        st[b].v = (double*)(q + 2 * nn);
+        st[b].p = q + 4 * nn;
+        st[b].g = q + 5 * nn;
+        st[b].carry[0] = q + 6 * nn;
+        st[b].carry[1] = q + 6 * nn + held;
+    }
+    std::vector<float> got((size_t)std::max(total, (int64_t)1));
+    for (int j = 0; j <= ncuts; ++j) {
+        const bool fin = j == ncuts;
+        Fx fx;
+        std::vector<chain::RdPlan> plan((size_t)B);
+        int64_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t lo = std::min(n[b], j ? cuts[j - 1] : 0), hi = fin ? n[b] : std::min(n[b], cuts[j]);
+            if (hi > lo)
+                FT_HIP(ctx, hipMemcpyAsync(s->lv_x + off, x + (size_t)b * stride + lo, (size_t)(hi - lo) * sizeof(float), hipMemcpyHostToDevice, s->stream));
+            plan[b] = st[b].plan(hi - lo, fin);
+            if (st[b].held(plan[b]) >= (long long)held) return ft_fail(ctx, FT_ERR_STATE, fn + ": ride carry out of step");
+            fx.rd.push_back(rd_seg_of(st[b], plan[b], s->lv_x + off));
+            off += hi - lo;
+        }
+        FT_TRY(rd_enqueue(ctx, fx, got.data()));
+        FT_TRY(rd_finish(ctx));
+        off = 0;
+        for (int b = 0; b < B; ++b) {
+            memcpy(y + (size_t)b * stride + st[b].nout, got.data() + off, (size_t)plan[b].out * sizeof(float));
+            off += plan[b].out;
+            emitted[(size_t)j * B + b] = plan[b].out;
+            st[b].commit(plan[b]);
+        }
+    }
+    for (int b = 0; b < B; ++b)
+        FT_HIP(ctx, hipMemcpy(nodes + (size_t)b * nn, st[b].g, (size_t)st[b].nodes * sizeof(float), hipMemcpyDeviceToHost));
     return FT_OK;
 }
 

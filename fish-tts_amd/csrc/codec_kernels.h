@@ -2011,4 +2011,155 @@ static __global__ __launch_bounds__(LV_SCALE_THREADS) void level_scale_kernel(co
         x[i] = g * x[i];
 }
 
+// ---- ride stage (ft_codec_stream_begin_live, ft_codec_ride; stated in fishtts_hip.h): a look-ahead gain rider behind the
+// resampler of a stream, with carried state.  A call names one segment per stream (blockIdx.z of a device table; streams at
+// different rates mix, so the filter and the hop travel with the segment).  Sample q of a stream lives in the carry copy
+// the call reads (q < nin: cin[q - base]) or in the call's new samples (x[q - nin]).  Three launches whatever the number of
+// streams:
+//   ride_hop_kernel     the hops the new samples complete (at the end of a stream also the one cut short): one lane per hop
+//                       with level_filter_kernel's arithmetic - both biquads in float64 from zero state LV_WARM hops earlier
+//                       or at sample 0, the sum over the hop ascending - so a hop sum has the bits of the whole-waveform
+//                       call.  A call completes few hops per stream; the streams lie on blockIdx.z, one wave per workgroup,
+//                       so that they spread over the CUs.  The launch is bound by the recursion, 3 H steps per lane.
+//   ride_node_kernel    one workgroup (one wave) per stream, the new nodes serially in k: the measure over the first m_k
+//                       hops (blocks, both gates: per-thread partial sums over blocks j = t, t + 64, ..., added by thread 0
+//                       in thread order - an order that depends on m_k alone), then slew, peak guard and the float32 node
+//                       by thread 0.  A call brings a few nodes per stream and a measure has at most some 2000 blocks.
+//   ride_apply_kernel   the emitted range times the interpolated gain, and the samples from the new base on rolled into the
+//                       carry copy the call writes.  A segment without a target copies its samples (a stream without the
+//                       stage in a call that has one).
+struct RdSeg {
+    const float* x;            // the call's new samples (device): what the stage in front gave
+    const float* cin;          // carry read: samples [base, nin)
+    float* cout;               // carry written: samples [base1, nin + n)
+    float* y;                  // out: samples [out0, out1)
+    double *e, *v;             // the stream's hop sums and v_k
+    float *p, *g;              // its hop peaks and nodes
+    double c[10];              // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 at the stream's rate
+    double ceiling;            // 10^(-1/20)
+    long long nin, base, base1, out0, out1;
+    int n, H;                  // new samples; hop
+    int h0, h1;                // hops to filter (h1: the peaks known after the call)
+    int W;                     // whole hops after the call
+    int k0, k1;                // nodes to compute
+    int target;                // hundredths of a LUFS; 0: no stage, y = x
+};
+constexpr int RD_LOOK = 10, RD_HOP_THREADS = 64, RD_NODE_THREADS = 64, RD_APPLY_THREADS = 256;
+constexpr double RD_SLEW = 0.5;
+
+__device__ inline float ride_at(const RdSeg& g, long long q) { return q < g.nin ? g.cin[q - g.base] : g.x[q - g.nin]; }
+
+__device__ inline void ride_load(const RdSeg& g, long long i, long long end, float* v) {
+#pragma unroll
+    for (int k = 0; k < LV_CHUNK; ++k) v[k] = i + k < end ? ride_at(g, i + k) : 0.f;
+}
+
+static __global__ __launch_bounds__(RD_HOP_THREADS) void ride_hop_kernel(const RdSeg* segs) {
+    const RdSeg& g = segs[blockIdx.z];
+    const long long h = (long long)g.h0 + (long long)blockIdx.x * RD_HOP_THREADS + threadIdx.x;
+    if (h >= g.h1) return;
+    const long long n = g.nin + g.n, H = g.H;
+    const double b0 = g.c[0], b1 = g.c[1], b2 = g.c[2], a1 = g.c[3], a2 = g.c[4];
+    const double d0 = g.c[5], d1 = g.c[6], d2 = g.c[7], e1 = g.c[8], e2 = g.c[9];
+    const long long s0 = h * H, s1 = min(n, s0 + H), w0 = max(0LL, s0 - LV_WARM * H);
+    double u1 = 0.0, u2 = 0.0, v1 = 0.0, v2 = 0.0, acc = 0.0;   // as level_filter_kernel
+    float pk = 0.f;
+    float cur[LV_CHUNK], nxt[LV_CHUNK];
+    ride_load(g, w0, s1, cur);
+    for (long long i = w0; i < s1; i += LV_CHUNK) {
+        ride_load(g, i + LV_CHUNK, s1, nxt);
+#pragma unroll
+        for (int k = 0; k < LV_CHUNK; ++k) {
+            const long long q = i + k;
+            const float xf = cur[k];
+            const double xv = (double)xf;
+            const double y = fma(b0, xv, u1);
+            u1 = fma(b1, xv, fma(-a1, y, u2));
+            u2 = fma(b2, xv, -a2 * y);
+            const double z = fma(d0, y, v1);
+            v1 = fma(d1, y, fma(-e1, z, v2));
+            v2 = fma(d2, y, -e2 * z);
+            if (q >= s0 && q < s1) {
+                acc = fma(z, z, acc);
+                pk = fmaxf(pk, fabsf(xf));
+            }
+            cur[k] = nxt[k];
+        }
+    }
+    g.e[h] = acc;
+    g.p[h] = pk;
+}
+
+static __global__ __launch_bounds__(RD_NODE_THREADS) void ride_node_kernel(const RdSeg* segs) {
+    const RdSeg& g = segs[blockIdx.x];
+    const int H = g.H, t = threadIdx.x;
+    const double* e = g.e;
+    __shared__ double ssum[RD_NODE_THREADS], sall[RD_NODE_THREADS];
+    __shared__ long long scnt[RD_NODE_THREADS];
+    __shared__ double gamma;
+    __shared__ int live;
+    double vprev = g.k0 > 0 ? g.v[g.k0 - 1] : 0.0;      // thread 0's; v_{-1} = 0
+    for (int k = g.k0; k < g.k1; ++k) {
+        const long long m = min(k + RD_LOOK, g.W), nb = m >= 4 ? m - 3 : (m >= 1 ? 1 : 0), n = m * H;
+        const int used = (int)min((long long)RD_NODE_THREADS, nb);
+        double s = 0.0, all = 0.0;
+        long long cnt = 0;
+        for (long long j = t; j < nb; j += RD_NODE_THREADS) {
+            const double E = level_block(e, j, m, m, n, H);
+            all += E;
+            if (level_lufs(E) > -70.0) { s += E; ++cnt; }
+        }
+        ssum[t] = s; sall[t] = all; scnt[t] = cnt;
+        __syncthreads();
+        if (t == 0) {
+            s = 0.0; all = 0.0; cnt = 0;
+            for (int i = 0; i < used; ++i) { s += ssum[i]; all += sall[i]; cnt += scnt[i]; }
+            live = isfinite(all) && cnt > 0;
+            gamma = live ? level_lufs(s / (double)cnt) - 10.0 : 0.0;
+        }
+        __syncthreads();
+        const bool on = live != 0;
+        const double gm = gamma;
+        s = 0.0;
+        cnt = 0;
+        if (on)
+            for (long long j = t; j < nb; j += RD_NODE_THREADS) {
+                const double E = level_block(e, j, m, m, n, H), l = level_lufs(E);
+                if (l > -70.0 && l > gm) { s += E; ++cnt; }
+            }
+        __syncthreads();
+        ssum[t] = s; scnt[t] = cnt;
+        __syncthreads();
+        if (t == 0) {
+            s = 0.0; cnt = 0;
+            for (int i = 0; i < used; ++i) { s += ssum[i]; cnt += scnt[i]; }
+            const double L = on && cnt > 0 ? level_lufs(s / (double)cnt) : -INFINITY;
+            const double u = isfinite(L) ? (double)g.target / 100.0 - L : vprev;
+            const double v = k == 0 ? u : fmin(fmax(u, vprev - RD_SLEW), vprev + RD_SLEW);
+            const float q = fmaxf(k >= 1 && k - 1 < g.h1 ? g.p[k - 1] : 0.f, k < g.h1 ? g.p[k] : 0.f);
+            const double cap = q > 0.f ? 20.0 * log10(g.ceiling / (double)q) : INFINITY;
+            g.v[k] = v;
+            g.g[k] = (float)pow(10.0, fmin(v, cap) / 20.0);
+            vprev = v;
+        }
+        __syncthreads();
+    }
+}
+
+static __global__ __launch_bounds__(RD_APPLY_THREADS) void ride_apply_kernel(const RdSeg* segs) {
+    const RdSeg& g = segs[blockIdx.z];
+    const long long step = (long long)gridDim.x * RD_APPLY_THREADS, t = (long long)blockIdx.x * RD_APPLY_THREADS + threadIdx.x;
+    if (g.target == 0) {
+        for (long long i = t; i < g.n; i += step) g.y[i] = g.x[i];
+        return;
+    }
+    const float Hf = (float)g.H;
+    for (long long i = g.out0 + t; i < g.out1; i += step) {
+        const long long k = i / g.H;
+        const float gk = g.g[k], w = (float)(i - k * g.H) / Hf;
+        g.y[i - g.out0] = ride_at(g, i) * fmaf(w, g.g[k + 1] - gk, gk);
+    }
+    for (long long q = g.base1 + t; q < g.nin + g.n; q += step) g.cout[q - g.base1] = ride_at(g, q);
+}
+
 }  // namespace ft

@@ -1,5 +1,5 @@
-// Host arithmetic of the output chain behind the codec (fishtts_hip.h: sample_rate, speed_pct, pitch_cents, loudness): the
-// time-scale stage, then the pitch stage, then the resampler, then the level.  The filter designs, the rule that accepts a
+// Host arithmetic of the output chain behind the codec (fishtts_hip.h: sample_rate, speed_pct, pitch_cents, loudness, live): the
+// time-scale stage, then the pitch stage, then the resampler, then the level (whole items) or the ride stage (streams).  The filter designs, the rule that accepts a
 // (speed, cents) pair, what each stage can emit after so many input samples, the bookkeeping of a stream's three stages from
 // call to call, and the level stage's K-weighting design, gates and gain.
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
@@ -224,7 +224,30 @@ inline LvInfo lv_gain(const double* e, long long n, int H, float p, int target) 
     return r;
 }
 
-// ---- the three stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;
+// ---- ride stage (ride_hop_kernel, ride_node_kernel, ride_apply_kernel; fishtts_hip.h states it): a look-ahead gain rider
+// behind the resampler of a stream.  Node k sits at sample k H; it is final once RD_A more whole hops have been seen (or at
+// the end of the stream), and the samples below the last final node go out.  The target is the level stage's.
+constexpr int RD_A = 10;              // look-ahead, hops
+constexpr double RD_R = 0.5;          // slew, dB per hop
+inline bool rd_ok(int target) { return lv_ok(target); }
+// After `nin` samples at hop H: whole hops, hop peaks known, final nodes, final outputs (= the first sample still carried).
+struct RdPlan { long long in = 0, out = 0, base = 0; int hops = 0, peaks = 0, nodes = 0; };
+inline RdPlan rd_plan(int H, long long nin, bool final) {
+    RdPlan p;
+    p.hops = (int)(nin / H);
+    if (final) {
+        p.peaks = (int)((nin + H - 1) / H);
+        p.nodes = p.peaks + 1;
+        p.out = p.base = nin;
+        return p;
+    }
+    p.peaks = p.hops;
+    p.nodes = p.hops >= RD_A ? p.hops - RD_A + 1 : 0;
+    p.out = p.base = (long long)std::max(0, p.hops - RD_A) * H;
+    return p;
+}
+
+// ---- the stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;
 // plan() says how many (nothing changes), the caller builds the stage's segment from the record and the plan, and commit()
 // advances the record once the call went through.  An absent stage passes its input on (out = in); its counters still run,
 // the parity of its carry pair too.  A record with null carries and zero counters is a waveform decoded from zero state.
@@ -272,19 +295,44 @@ struct RsStage {
     void commit(const StagePlan& p) { nin += p.in; nout += p.out; par ^= 1; }
 };
 
-struct ChainPlan { StagePlan ts, ps, rs; };
+// The ride stage of a stream: `in` more samples, `out` emitted; hops, peaks and nodes are the totals after the call.
+struct RdStage {
+    int target = 0, rate = RS_FI, H = 1;       // target 0: absent; the output rate and its hop
+    float* carry[2] = {nullptr, nullptr};      // the samples from `base` on (fewer than (RD_A + 1) H)
+    double *e = nullptr, *v = nullptr;         // on the device, per stream: hop sums, v_k
+    float *p = nullptr, *g = nullptr;          // hop peaks, nodes g_k
+    int par = 0, hops = 0, peaks = 0, nodes = 0;
+    long long nin = 0, nout = 0, base = 0;
+    RdPlan plan(long long n, bool final) const {
+        RdPlan q;
+        if (target == 0) { q.in = q.out = n; return q; }
+        q = rd_plan(H, nin + n, final);
+        q.in = n;
+        q.out -= nout;
+        return q;
+    }
+    long long held(const RdPlan& q) const { return target != 0 ? nin + q.in - q.base : 0; }   // carried after the call: below (RD_A + 1) H
+    void commit(const RdPlan& q) {
+        if (target == 0) return;
+        nin += q.in; nout += q.out; base = q.base; hops = q.hops; peaks = q.peaks; nodes = q.nodes; par ^= 1;
+    }
+};
+
+struct ChainPlan { StagePlan ts, ps, rs; RdPlan rd; };
 struct StageChain {
     TsStage ts;
     PsStage ps;
     RsStage rs;
+    RdStage rd;
     int speed = 100;          // the caller's speed_pct: with the codec samples seen it fixes the pitch stage's output length
     long long seen = 0;       // codec samples taken so far
-    bool any() const { return ts.on || ps.tab || rs.tab; }
+    bool any() const { return ts.on || ps.tab || rs.tab || rd.target != 0; }
     ChainPlan plan(long long n, bool final) const {
         ChainPlan p;
         p.ts = ts.plan(n, final);
         p.ps = ps.plan(p.ts.out, final, ts_len(speed, seen + n));
         p.rs = rs.plan(p.ps.out, final);
+        p.rd = rd.plan(p.rs.out, final);
         return p;
     }
     void commit(const ChainPlan& p) {
@@ -292,29 +340,37 @@ struct StageChain {
         ts.commit(p.ts);
         ps.commit(p.ps);
         rs.commit(p.rs);
+        rd.commit(p.rd);
     }
 };
 
 // A call's chain, resolved: which stages exist and at what rate.  make() judges the values as every entry point does
-// (an error message, or null): the rate, then the speed, then the cents, then the pair, then the level.  The device tables are filled in by
+// (an error message, or null): the rate, then the speed, then the cents, then the pair, then the level, then the ride stage's
+// target.  The device tables are filled in by
 // the caller that holds the context (codec.hip: fx_prepare).
 struct FxDesc {
     int rate = RS_FI, pct = 100, cents = 0, level = 0;   // level: the target in hundredths of a LUFS, 0: no level stage
+    int live = 0;                     // the ride stage's target (a stream's), 0: no ride stage
     int L = 1, M = 1, K = 0;          // the resampler's (K = 0: the codec's own rate, no stage)
     FxPlan f;                         // f.has_ts: the time-scale stage exists (under a pitch shift it may not)
     const RsTab* rs = nullptr;        // set by the caller when K > 0
     const PsTab* ps = nullptr;        // set by the caller when cents != 0
-    enum Bad { OK = 0, RATE, SPEED, CENTS, PAIR, LEVEL };
+    enum Bad { OK = 0, RATE, SPEED, CENTS, PAIR, LEVEL, LIVE };
     Bad make(int rate_, int pct_, int cents_, const char** why) { return make(rate_, pct_, cents_, 0, why); }
+    Bad make(int rate_, int pct_, int cents_, int level_, int live_, const char** why) {
+        const Bad b = make(rate_, pct_, cents_, level_, why);
+        live = live_;
+        return b != OK ? b : rd_ok(live) ? OK : LIVE;
+    }
     Bad make(int rate_, int pct_, int cents_, int level_, const char** why) {
-        rate = rate_; pct = pct_; cents = cents_; level = level_;
+        rate = rate_; pct = pct_; cents = cents_; level = level_; live = 0;
         if ((*why = rs_design(rate, &L, &M, &K, nullptr))) return RATE;
         if (!ts_ok(pct)) return SPEED;
         if (cents < -PS_MAX_CENTS || cents > PS_MAX_CENTS) return CENTS;
         if (!fx_plan(pct, cents, &f)) return PAIR;
         return lv_ok(level) ? OK : LEVEL;
     }
-    bool any() const { return K > 0 || f.has_ts || cents != 0; }
+    bool any() const { return K > 0 || f.has_ts || cents != 0 || live != 0; }
     // a waveform from zero state through this chain
     StageChain fresh() const {
         StageChain c;
@@ -323,6 +379,9 @@ struct FxDesc {
         c.ps.tab = ps;
         c.rs.tab = K > 0 ? rs : nullptr;
         c.speed = pct;
+        c.rd.target = live;
+        c.rd.rate = rate;
+        c.rd.H = lv_hop(rate);
         return c;
     }
     // n_in codec samples -> after the time-scale and pitch stages -> after the resampler (ft_resampled_len of ft_timescaled_len)

@@ -164,7 +164,7 @@ class BatchServer:
     def synthesize_stream(self, text: str, references=None, chunk_tokens: int = 20, min_first_chunk: int = 10,
                           seamless: bool = False, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                           pitch: Optional[float] = None, fx=None, loudness: Optional[float] = None,
-                          **sampling) -> Iterator[bytes]:
+                          live_loudness: Optional[float] = None, **sampling) -> Iterator[bytes]:
         """Yields int16 PCM chunks as FishTTS.synthesize_stream does: seamless=False (the reference's default) every chunk
         decoded from zero state; seamless=True one stateful CodecStream per request, the chunks cut as
         synthesize_batch_stream cuts them.  `sampling`: temperature, top_p, repetition_penalty, max_tokens, seed.  The
@@ -172,10 +172,15 @@ class BatchServer:
         next(), so a generator dropped before it never runs, and abandoning it later cancels the request (its slot is
         freed at the next burst boundary).  `sample_rate`, `speed` and `pitch` as FishTTS.synthesize_stream (checked here), or
         `fx`: the three already checked.  `loudness` (or an `fx` with a level) raises ValueError here: the level needs the whole
-        utterance."""
+        utterance.  `live_loudness` (or an `fx` with a ride stage; as FishTTS.synthesize_stream) is what a stream takes
+        instead, with seamless=True only (ValueError here otherwise): the request's CodecStream carries the ride stage, in the
+        same decode_streams call as every other ready chunk."""
         if chunk_tokens < 1 or min_first_chunk < 1:
             raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
-        fx = checked_fx(fx, sample_rate, speed, pitch, loudness).no_level("BatchServer.synthesize_stream")
+        fx = checked_fx(fx, sample_rate, speed, pitch, loudness, live_loudness).no_level("BatchServer.synthesize_stream")
+        if fx.live is not None and not seamless:
+            raise ValueError("live_loudness needs seamless=True: seamless=False chunks are independent waveforms, and "
+                             "levelling each on its own would jump")
         utt, n_prefix = self._prepare(text, references, sampling.get("temperature", 0.7), sampling.get("top_p", 0.8),
                                       sampling.get("repetition_penalty", 1.1), sampling.get("max_tokens", 2048),
                                       sampling.get("seed", 0))
@@ -526,7 +531,7 @@ class BatchServer:
                         final = [[bool(f and r.fx) for r, f in zip(seam, seam_final)]] if any(r.fx for r in seam) else []
                         audio = self._codec.decode_streams(streams, seam_chunks, *final)
                         for r, a in zip(seam, audio):
-                            if len(a) or r.fx.emits_empty:     # (nothing completed in the time-scale or pitch stage: nothing to hand out)
+                            if len(a) or r.fx.emits_empty:     # (nothing completed in the time-scale, pitch or ride stage: nothing to hand out)
                                 r.out.put(pcm16(a))
                     for r, c in zip(plain, plain_chunks):
                         r.out.put(self._decode_pcm(c, **r.fx.kw))

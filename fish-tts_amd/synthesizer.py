@@ -386,7 +386,8 @@ class FishTTS:
                                 seed: int = 0, seeds: Optional[List[int]] = None,
                                 sample_rate: Optional[int] = None,
                                 speed: Optional[float] = None,
-                                pitch: Optional[float] = None, loudness: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
+                                pitch: Optional[float] = None, loudness: Optional[float] = None,
+                                live_loudness: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
         """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
         PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
         `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
@@ -401,10 +402,12 @@ class FishTTS:
         the resampler, if any); the chunk before its (i, b"") holds the tail in the same way.
         `pitch` (as synthesize_at): each utterance's stream is pitch-shifted on the GPU through one carried stage (between
         the two); the tail travels in the same way.
-        `loudness`: ValueError here, before any work - the level needs the whole utterance (synthesize_batch has it)."""
+        `loudness`: ValueError here, before any work - the level needs the whole utterance (synthesize_batch has it).
+        `live_loudness` (LUFS in [-50, -5]) is what a stream takes instead: each utterance's stream is ridden toward that
+        loudness on the GPU by a gain that looks one second ahead, last in its chain (as synthesize_stream)."""
         from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
-        fx = _output_fx(sample_rate, speed, pitch, loudness).no_level("synthesize_batch_stream")
+        fx = _output_fx(sample_rate, speed, pitch, loudness, live_loudness).no_level("synthesize_batch_stream")
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
@@ -661,11 +664,24 @@ class FishTTS:
         and the resampler), so its chunks concatenate to the shifted waveform of one streamed decode.
 
         `loudness=` raises ValueError (at the first next(), before any work): the level needs the whole utterance, and a
-        stream hands out audio before its end (synthesize_at, synthesize_long_stream take it)."""
+        stream hands out audio before its end (synthesize_at, synthesize_long_stream take it).
+
+        Extension `live_loudness=` (keyword; LUFS in [-50, -5]; checked at the first next()): with seamless=True the stream
+        is ridden toward that loudness on the GPU by a carried look-ahead gain rider, last in the chain (CodecStream /
+        ft_codec_stream_begin_live): a gain that follows the loudness of the programme so far, moves at most 0.5 dB per
+        100 ms, looks one second ahead and holds the sample peak at -1 dBFS.  First audio comes one second of output
+        (about 22 frames) later, and the result does not depend on the chunking, bit for bit.  A fresh stream at
+        `max_frames`, or the cut at `max_tokens`, starts a fresh ride state: the level is not carried over that one
+        boundary.  seamless=False chunks are independent waveforms - levelling each on its own would jump - so that
+        combination raises ValueError (at the first next(), before any work).  The one-shot and long-form calls do not
+        take it: they have `loudness=`."""
         from .generation import generate_long
         from .serve import ServerClosed
         fx = _output_fx(kwargs.pop("sample_rate", None), kwargs.pop("speed", None), kwargs.pop("pitch", None),
-                        kwargs.pop("loudness", None)).no_level("synthesize_stream")
+                        kwargs.pop("loudness", None), kwargs.pop("live_loudness", None)).no_level("synthesize_stream")
+        if fx.live is not None and not kwargs.get("seamless", False):
+            raise ValueError("live_loudness needs seamless=True: seamless=False chunks are independent waveforms, and "
+                             "levelling each on its own would jump")
         srv = getattr(self, "_server", None)
         if srv is not None:
             chunks = srv.synthesize_stream(text, references, chunk_tokens, min_first_chunk, fx=fx, **kwargs)
@@ -710,7 +726,7 @@ class FishTTS:
                             stream.close()
                             stream = self._vocoder.stream(fx=fx)
                         audio = stream.decode(codes)
-                        if len(audio) or fx.emits_empty:   # (a time-scale or pitch stage completed nothing: nothing to hand out)
+                        if len(audio) or fx.emits_empty:   # (a time-scale, pitch or ride stage completed nothing: nothing to hand out)
                             audio_queue.put((audio * 32767).astype(np.int16).tobytes())
                 if stream is not None and fx:
                     audio_queue.put((stream.finish() * 32767).astype(np.int16).tobytes())   # the output stages' tail
@@ -905,10 +921,10 @@ class _LongStopped(Exception):
     """The consumer of synthesize_long_stream went away: generation stops at its next block of frames."""
 
 
-def _output_fx(sample_rate, speed, pitch, loudness=None):
+def _output_fx(sample_rate, speed, pitch, loudness=None, live_loudness=None):
     """codec_engine.OutputFx.of: the checked output stages of a call (imported when first needed, as the engines are)."""
     from .codec_engine import OutputFx
-    return OutputFx.of(sample_rate, speed, pitch, loudness)
+    return OutputFx.of(sample_rate, speed, pitch, loudness, live_loudness)
 
 
 def get_instance(model_dir=None, device: Literal["cpu", "cuda"] = "cuda",

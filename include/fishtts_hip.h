@@ -367,7 +367,8 @@ int32_t ft_join_groups(const int32_t* lens, int32_t n, int32_t max_frames, int32
  * depend on how the lanes are spread over the grid.  Three launches whatever the number of items (filter, gates and gain,
  * multiply; the item is a grid dimension).  The first levelled call allocates the stage's table (64 items, < 4 KB) and one
  * float64 and one float32 per hop of the call's items; a later call that needs more replaces them by larger ones.
- * No stream entry point takes a level: the integrated loudness of an utterance is not known before its end. */
+ * No stream entry point takes a level: the integrated loudness of an utterance is not known before its end.  A stream is
+ * levelled by the ride stage instead (ft_codec_stream_begin_live, below). */
 typedef struct ft_level_info {
     double lufs;               /* L: integrated loudness; -inf when nothing was measured (the gain is then 1) */
     float peak, gain;          /* p = max |x| of the item before the stage; g */
@@ -397,6 +398,57 @@ ft_status ft_codec_decode_join_level(ft_ctx* ctx, const int32_t* codes, int32_t 
                                      int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t loudness,
                                      const ft_join_params* jp, const int64_t* gaps, int32_t started, float* audio,
                                      int64_t capacity, int64_t* total, int64_t* cuts, ft_level_info* infos);
+/* Ride.  A stream cannot wait for its integrated loudness, so it gets a second, streaming level stage: a look-ahead gain
+ * rider with carried state, last in the stream's chain: codec -> time-scale stage -> pitch stage -> rate resampler -> ride.
+ * It is a different operation from the level above - a gain that varies in time, steered by the loudness of the programme
+ * so far - and its output does not depend on how the stream was cut into chunks, bit for bit, like the other three stream
+ * stages.  The measure is cumulative: after a change of level the output settles toward the loudness of the programme so
+ * far and does not pump (a 6.4 s signal with a +12 dB step came out at -21.3 LUFS overall for a -23 target); that is
+ * intended.  Stated, which fixes its result:
+ *   Inputs: a stream's samples x[0 .. n) at the output rate Fo, float32, arriving in chunks; n is known only at `final`.
+ *   The target T (`live`) is in hundredths of a LUFS in [-5000, -500]; 0 means the stage is absent (the call is then the one
+ *   without it, bit for bit); anything else is FT_ERR_ARG before any device work.
+ *   Constants: the level stage's hop H = floor(Fo / 10) and ceiling c = 10^(-1/20); look-ahead A = 10 hops; slew R = 0.5 dB
+ *   per hop.
+ *   Hop sums and peaks: z is the K-weighted x exactly as the level stage computes it (the same design, float64, one lane
+ *   per hop from zero state 2 hops earlier or at sample 0).  e_h = sum z^2 over [h H, (h + 1) H) for the W = floor(n / H)
+ *   whole hops; p_h = max |x| over hop h for h < Nh = ceil(n / H), the last one over what is left; p_-1 = p_Nh = 0.
+ *   Running measure: L(m) is the level stage's integrated loudness of the first m whole hops (its blocks and gates over
+ *   e_0 .. e_m-1 as an item of m H samples: 400 ms blocks, both gates, a single mean block below four hops, -inf when
+ *   nothing passes).
+ *   Nodes: node k sits at sample k H, k = 0 .. Nh.  m_k = min(k + A, W).  u_k = T / 100 - L(m_k) when L(m_k) is finite,
+ *   else u_k = v_k-1 (v_-1 = 0).  v_0 = u_0; for k >= 1, v_k = min(max(u_k, v_k-1 - R), v_k-1 + R).  Peak guard:
+ *   q_k = max(p_k-1, p_k), cap_k = 20 log10(c / q_k), +inf when q_k = 0; the guard does not feed back into v.
+ *   g_k = (float) 10^(min(v_k, cap_k) / 20): float64 throughout, rounded to float32 once.
+ *   Output: for i = k H + j, 0 <= j < H: y[i] = x[i] * fmaf((float)j / (float)H, g_k+1 - g_k, g_k), float32 with an IEEE
+ *   division, and nothing else touches a sample.  Both nodes of hop k are at most c / p_k, so |y| <= c up to rounding.
+ *   Silence, or nothing above the gates, gives g = 1 exactly and y = x bit for bit.
+ *   Emission: after n_in samples with W' = floor(n_in / H) whole hops, node k is final once k + A <= W', and the outputs
+ *   below max(0, W' - A) H are final and are emitted.  `final` computes the remaining nodes with m_k = min(k + A, W) and
+ *   emits all n samples.  The stage changes no length; a stream holds back less than (A + 1) H samples.
+ *   Determinism: no floating-point atomics; every reduction runs in an order that depends only on m_k, never on the call.
+ * On the device a stream carries the held-back samples (two copies: a call reads one and writes the other), its hop sums,
+ * peaks, nodes and v; the counters live on the host.  Three launches per call whatever the number of streams (the hops the
+ * call completes; the new nodes, one workgroup per stream; the multiply and the roll of the carry).  A live stream's first
+ * audio comes A hops (one second) of output later than a plain stream's.  A stream that rolls over at max_frames, or is cut
+ * by the caller's max_tokens, starts a fresh ride state with its fresh codec stream: the level is not carried over that one
+ * boundary. */
+/* Host only (no context, no device): validates the rate as ft_resample_filter does (FT_ERR_ARG otherwise, or for n_in < 0).
+ * After n_in samples of a stream (final: its end), *nodes = the nodes that are final and *n_out = the samples emitted so
+ * far.  Either pointer may be NULL. */
+ft_status ft_ride_plan(int32_t sample_rate, int64_t n_in, int32_t final, int64_t* nodes, int64_t* n_out);
+/* The stage alone on a host waveform x of n >= 0 samples at sample_rate, as one stream whose only call is its last.  y
+ * receives the n samples; nodes (may be NULL) receives the ceil(n / H) + 1 nodes g_k.  target = 0: y = x, every node 1.
+ * Limits and refusals as ft_codec_loudness: n up to the longest item a decode gives, FT_ERR_TOO_LONG beyond; FT_ERR_ARG
+ * before any device work for a refused rate, a target that is neither 0 nor in [-5000, -500], a null x or y. */
+ft_status ft_codec_ride(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, int32_t target, float* y, float* nodes);
+/* ft_codec_stream_begin_fxp with the ride stage behind the resampler at target `live`; with live = 0 it is that call.
+ * ft_codec_stream_decode_many_at serves such streams, mixed with any others in one call: the concatenation of a stream's
+ * chunks is, bit for bit, ft_codec_ride over the concatenation of the same stream opened without the target.
+ * ft_codec_stream_decode and ft_codec_stream_decode_many refuse them (FT_ERR_STATE); ft_codec_stream_end frees the state:
+ * two carries of (A + 1) H floats and 24 bytes per 100 ms of the longest stream (max_frames frames at speed 0.5). */
+ft_status ft_codec_stream_begin_live(ft_ctx* ctx, int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t live,
+                                     ft_codec_stream** out);
 /* Codec encode = vocoder.encode(audio, lengths) of encode_reference (synthesizer.py:325-357, vocoder.py:885-904):
  * mono f32 audio at the codec sample rate (host), right-padded to whole frames -> codes (num_codebooks+1) x T'
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */

@@ -289,6 +289,14 @@ ft_status ft_test_embed(ft_ctx* ctx, int32_t M, int32_t D, int32_t ncb, int32_t 
 ft_status ft_test_fast_attn(ft_ctx* ctx, int32_t form, int32_t M, int32_t c, const float* qkv, const void* qn, const void* kn,
                             void* kc, void* vc, float* y, uint16_t* y_bf);
 
+/* Test hook: the ride stage alone (fishtts_hip.h: "Ride") on B host waveforms run as B carried streams in the same calls.
+ * x [B][stride], waveform b has n[b] <= stride samples at sample_rate; target as ft_codec_ride's, not 0.  There are
+ * ncuts + 1 calls: call j gives every stream its samples in [cuts[j-1], cuts[j]) (cuts[-1] = 0, cuts non-descending), clipped
+ * to n[b]; the last call takes what is left and is `final`.  y [B][stride] receives each stream's emitted samples one call
+ * after the other, nodes [B][stride / H + 2] its ceil(n[b] / H) + 1 nodes, emitted[j B + b] what call j gave stream b. */
+ft_status ft_test_ride_streams(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, const int64_t* n, int32_t sample_rate,
+                               int32_t target, const int64_t* cuts, int32_t ncuts, float* y, float* nodes, int64_t* emitted);
+
 #ifdef __cplusplus
 }
 #endif
