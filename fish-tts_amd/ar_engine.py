@@ -455,7 +455,7 @@ class ARHipEngine:
 
     def test_gemv(self, pro: int, epi: int, x: np.ndarray, W: np.ndarray, gain=None, bias=None, resid=None, alias: bool = False,
                   nt: bool = True, ldx=None, ldo=None):
-        """Test hook (ft_test_gemv): one product of a 1..4 row decode launch through the product's dispatcher.  x (M, K) f32;
+        """Test hook (ft_test_gemv): one product of a decode launch of 1..max_batch rows through the product's dispatcher.  x (M, K) f32;
         W (N, K), gain (K,), bias (N,): patterns of the model's type (float32 in fp32); resid (M, N) f32.  Returns (out (M, oc)
         f32, pad (M, ldo - oc) uint32, tail (ldo,) uint32: the row behind, (MB, R, NT))."""
         wt = self._wt()
@@ -474,7 +474,7 @@ class ARHipEngine:
 
     def test_decode_attn(self, qkv: np.ndarray, pos: np.ndarray, qn, kn, kc: np.ndarray, vc: np.ndarray, wo: np.ndarray, bo,
                          resid: np.ndarray, pos_off: int = 0):
-        """Test hook (ft_test_decode_attn): decode attention and the Wo product of 1..4 rows.  Patterns of the model's type
+        """Test hook (ft_test_decode_attn): decode attention and the Wo product of 1..max_batch rows.  Patterns of the model's type
         (float32 in fp32) for qn, kn, kc, vc (M, Hkv, n_slots, hd), wo (dim, H hd), bo.  Returns (nsplit, y (M, y_ld) f32,
         part_o (M, H, nsplit, hd), part_ml (M, H, nsplit, 2) or None with one split, x_out (M, dim), kc, vc after the launch)."""
         wt = self._wt()
@@ -524,7 +524,7 @@ class ARHipEngine:
         return x[:M, :D].copy(), x[:M, D:].view(np.uint32).copy(), x[M].view(np.uint32).copy(), xo
 
     def test_fast_attn(self, form: int, qkv: np.ndarray, c: int, qn, kn, kc: np.ndarray, vc: np.ndarray):
-        """Test hook (ft_test_fast_attn): one fast_attn_kernel launch.  form 0 single (M <= 4), 1 wide single, 2 paired (qkv
+        """Test hook (ft_test_fast_attn): one fast_attn_kernel launch.  form 0 single (M <= max_batch), 1 wide single, 2 paired (qkv
         rows [0, M) at position 0, [M, 2 M) at position 1).  kc / vc (M, Hkv, ncb, hd).  Returns (y, pad, tail, kc, vc) for
         form 0 (y (M, H hd) f32) or (y_bf (H hd / 8, xo_ldm, 8) uint16, kc, vc) for the wide forms; the caches as the hook
         filled them (NaN from row c / 0 on) and the launch left them."""

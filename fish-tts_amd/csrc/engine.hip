@@ -1024,7 +1024,7 @@ static void gemv_combine_nt(Launch& L, const GemvP& p, const AttnP& a, int nt) {
 #undef FT_NT
 }
 
-// The "decode attention, then Wo" part of a slow layer for 1..4 rows: attn_decode_kernel over ctx->nsplit KV splits, then the
+// The "decode attention, then Wo" part of a slow layer for 1..max_batch rows: attn_decode_kernel over ctx->nsplit KV splits, then the
 // Wo product with the residual add - with more than one split the partials are merged inside it (gemv_attn_combine_kernel),
 // with one it reads the attention's y.  enqueue_slow and the test hook ft_test_decode_attn both call it.
 template <typename WT, int ROUND>
@@ -2871,7 +2871,7 @@ extern "C" ft_status ft_test_pf_attn(ft_ctx* ctx, int32_t n_seq, const int32_t* 
     return FT_OK;
 }
 
-// ------------------------------------------------------------------------------------------ decode-launch test hooks (1..4 rows)
+// ------------------------------------------------------------------------------------------ decode-launch test hooks (1..max_batch rows)
 // (include/fishtts_hip_test.h: ft_test_gemv, ft_test_decode_attn, ft_test_embed).  Host code around gemv, decode_attn_wo and
 // the embedding launch on temporaries: nothing here is reached from a frame.
 template <typename WT, int ROUND>
@@ -2879,7 +2879,7 @@ static ft_status test_gemv_t(ft_ctx* ctx, int pro, int epi, int M, int N, int K,
                              const void* gain, const void* bias, const float* resid, bool alias, int nt, int ldo, float* out,
                              int32_t* id3) {
     const size_t esz = sizeof(WT);
-    std::vector<uint32_t> xh((size_t)4 * ldx, WT_POISON_F32);         // rows M .. 3 and the ldx padding: NaN patterns
+    std::vector<uint32_t> xh((size_t)((M + 3) / 4 * 4) * ldx, WT_POISON_F32);   // rows M .. 4 ceil(M / 4) - 1 and the ldx padding: NaN patterns
     for (int m = 0; m < M; ++m) memcpy(xh.data() + (size_t)m * ldx, x + (size_t)m * K, (size_t)K * 4);
     std::vector<uint32_t> oh((size_t)(M + 1) * ldo, WT_POISON_F32);   // padding columns and the row behind row M - 1: the sentinel
     std::vector<uint32_t> rh = oh;
@@ -2915,7 +2915,7 @@ extern "C" ft_status ft_test_gemv(ft_ctx* ctx, int32_t pro, int32_t epi, int32_t
     const int vec = ctx->c.dtype == FT_F32 ? 4 : 8;
     if (pro != PRO_NONE && pro != PRO_RMSNORM) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad prologue");
     if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad epilogue");
-    if (M < 1 || M > 4) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: M outside 1..4");
+    if (M < 1 || M > ctx->c.max_batch) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: M outside 1..max_batch");
     if (K < 8 || K % 8 != 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: K is not a whole number of 16-byte pieces");
     if (pick_nt(K, vec) < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: K above 12 x 64 pieces per row");
     if (N < 1 || (epi == EPI_SWIGLU && N % 2 != 0)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad N");
@@ -2989,7 +2989,7 @@ extern "C" ft_status ft_test_decode_attn(ft_ctx* ctx, int32_t M, const float* qk
                                          const float* resid, int32_t* nsplit, float* y, float* part_o, float* part_ml,
                                          float* x_out) {
     FT_TRY(ar_ready(ctx));
-    if (M < 1 || M > ctx->c.max_batch || M > 4) return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: M outside 1..min(max_batch, 4)");
+    if (M < 1 || M > ctx->c.max_batch) return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: M outside 1..max_batch");
     if (!qkv || !pos || !kc || !vc || !wo || !resid || !nsplit || !y || !part_o || !part_ml || !x_out)
         return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: missing argument");
     if (pos_off < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_decode_attn: negative pos_off");
@@ -3122,12 +3122,17 @@ extern "C" ft_status ft_test_fast_attn(ft_ctx* ctx, int32_t form, int32_t M, int
     if (c.n_fast_layer < 1 || c.num_codebooks > FAST_MAXCB || c.fast_head_dim > 128)
         return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: this context has no fast stack the kernel takes");
     if (form == 0) {
-        if (M < 1 || M > 4) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: M outside 1..4");
+        if (M < 1 || M > c.max_batch) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: M outside 1..max_batch");
     } else {
         if (c.dtype == FT_F32) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: the wide forms are 16-bit");
         if (!ctx->wide_ok) return ft_fail(ctx, FT_ERR_STATE, "ft_test_fast_attn: this context has no lock-step MFMA path");
         if (M < 5 || M > 64 || M > ctx->xo_ldm) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: M outside 5..min(64, xo_ldm)");
-        if (form == 2 && (c.num_codebooks < 2 || ctx->xo_pair + M > ctx->xo_ldm))
+        // The hook is wider than the product's rule on purpose.  wide_pair pairs where xo_pair + M <= 64; the hook also takes
+        // every M that fits the buffers of a context of up to 64 rows (xo_pair <= 64, M <= xo_ldm - xo_pair), so that the kernel's
+        // paired form is checked at every tile edge up to 64 rows on the one 64-row context the kernel tests share, not only
+        // at the M a context's own xo_pair admits.  Above 64 rows (xo_pair >= 80) no M pairs in the product and none is added
+        // by a larger context: refused.
+        if (form == 2 && (c.num_codebooks < 2 || ctx->xo_pair > 64 || ctx->xo_pair + M > ctx->xo_ldm))
             return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: the paired pass does not fit");
     }
     if (form != 2 && (cpos < 0 || cpos >= c.num_codebooks)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: c outside 0..ncb-1");

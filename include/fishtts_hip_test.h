@@ -231,35 +231,36 @@ ft_status ft_test_pf_attn(ft_ctx* ctx, int32_t n_seq, const int32_t* seqs, int32
                           const float* qkv, const uint16_t* qn, const uint16_t* kn, uint16_t* kc, uint16_t* vc, uint16_t* y,
                           uint16_t* q, uint16_t* tail, int32_t* path);
 
-/* Test hook: ONE product of a 1..4 row decode launch through the product's own dispatcher (engine.hip: gemv), with
+/* Test hook: ONE product of a decode launch of M in 1..max_batch rows through the product's own dispatcher (engine.hip: gemv), with
  * R = rows_per_wave(N, M) as every caller passes it, so the choice between gemv_kernel<NT, R> and gemv_mb_kernel<NT, R, MB> is
  * the product's.  pro: 0 none, 1 fused RMSNorm (gain [K]); epi: 0 store, 1 residual add, 2 SwiGLU on interleaved (gate, up)
  * weight rows (N / 2 output columns).  x [M][K] f32 (dense: the hook lays it out at row stride ldx >= K); W [N][K], gain [K]
  * and bias [N] (or NULL) in the context's type - bit patterns of the 16-bit type, f32 in an f32 context; resid [M][N] f32 (epi
  * 1).  alias != 0 (epi 1): the output buffer IS the residual buffer, as the slow layers run it (`x, x`), otherwise two
  * buffers, as fast layer 0 runs it.  nt: non-temporal weight loads.  ldx, ldo: multiples of 4, ldo >= the output columns.
- * The hook fills x rows M .. 3 and the ldx padding with NaN patterns, and the output - [M + 1][ldo], the residual buffer in
+ * x is allocated with 4 ceil(M / 4) rows: the hook fills rows M .. and the ldx padding with NaN patterns, and the output - [M + 1][ldo], the residual buffer in
  * the aliased form - with 0xFFFFFFFE before the launch.  Everything lives in temporaries of the call.
  * out [M + 1][ldo]: the whole output buffer: the written rows, their padding columns and the row behind row M - 1, which
  * must still hold the sentinel.  id[3] = {MB (0: gemv_kernel), R, NT} of the launch.
- * FT_ERR_ARG: what gemv refuses (K above 12 x 64 16-byte pieces), K not a multiple of 8, M outside 1..4, an odd N for SwiGLU,
+ * FT_ERR_ARG: what gemv refuses (K above 12 x 64 16-byte pieces), K not a multiple of 8, M outside 1..max_batch, an odd N for SwiGLU,
  * a bad stride, a missing argument. */
 ft_status ft_test_gemv(ft_ctx* ctx, int32_t pro, int32_t epi, int32_t M, int32_t N, int32_t K, const float* x, int32_t ldx,
                        const void* W, const void* gain, const void* bias, const float* resid, int32_t alias, int32_t nt,
                        int32_t ldo, float* out, int32_t* id);
 
-/* Test hook: the "decode attention, then Wo" part of a slow layer for M in 1..4 rows at the context's head geometry and rope
+/* Test hook: the "decode attention, then Wo" part of a slow layer for M in 1..max_batch rows at the context's head geometry and rope
  * table, through the host routine enqueue_slow itself calls (engine.hip: decode_attn_wo): attn_decode_kernel over the
  * context's KV splits, then gemv_attn_combine_kernel (more than one split: the merge of the partials rides inside the Wo
  * product) or the plain product.  The split count is picked first, as ft_ar_decode picks it, for a call whose longest context
  * ends at max(pos) + pos_off + 1, and the context's own value is put back afterwards.  qkv [M][(H + 2 Hkv) hd] f32, pos [M]
  * (the device position; pos + pos_off is the appended row), qn / kn [hd] or NULL, the caches kc / vc [M][Hkv][n_slots][hd],
  * wo [dim][H hd] and bo [dim] or NULL in the context's type (patterns; f32 in an f32 context), resid [M][dim] f32.
- * Temporaries of the call but for the context's split-partial scratch.  Outputs: *nsplit; y [M][y_ld] (y_ld = max(H hd,
+ * Temporaries of the call but for the context's split-partial scratch (row m's partials at m H nsplit hd, as decode_attn_wo
+ * places them; its room is max_batch rows).  Outputs: *nsplit; y [M][y_ld] (y_ld = max(H hd,
  * fast H x hd)): with one split the attention output, otherwise still the 0xFFFFFFFE fill; with more than one split
  * part_o [M][H][nsplit][hd] and part_ml [M][H][nsplit][2] as the kernel left them (pre-filled with the sentinel); x_out
  * [M][dim]: the residual stream after the Wo product (in place, as the product runs it); kc / vc back whole in place.
- * part_o / part_ml need room for 32 splits.  FT_ERR_ARG: M outside 1..min(max_batch, 4), a position outside the cache or the
+ * part_o / part_ml need room for 32 splits.  FT_ERR_ARG: M outside 1..max_batch, a position outside the cache or the
  * rope table, a missing argument. */
 ft_status ft_test_decode_attn(ft_ctx* ctx, int32_t M, const float* qkv, const int32_t* pos, int32_t pos_off, const void* qn,
                               const void* kn, void* kc, void* vc, const void* wo, const void* bo, const float* resid,
@@ -276,7 +277,7 @@ ft_status ft_test_embed(ft_ctx* ctx, int32_t M, int32_t D, int32_t ncb, int32_t 
                         int32_t sem_begin, int32_t sem_end, int32_t scale, int32_t ldx, int32_t xo_ldm, float* x, uint16_t* xo);
 
 /* Test hook: ONE fast_attn_kernel launch at the context's fast-stack geometry and its `frope` table, in one of three forms.
- * form 0, single: M in 1..4 rows at codebook position c in 0..ncb-1, y [M + 1][y_ld] f32 (the whole buffer, pre-filled with
+ * form 0, single: M in 1..max_batch rows at codebook position c in 0..ncb-1, y [M + 1][y_ld] f32 (the whole buffer, pre-filled with
  * 0xFFFFFFFE: padding columns and the row behind row M - 1 keep it).  form 1, wide single: M in 5..64, y_bf [H hd / 8][xo_ldm][8]
  * 16-bit patterns, octet-major at the context's xo_ldm, pre-filled with 0xFFFE.  form 2, paired: pair_M = M; qkv rows [0, M)
  * are the utterances at position 0, qkv rows [M, 2 M) the same utterances at position 1 (the hook places them at rows
@@ -284,7 +285,11 @@ ft_status ft_test_embed(ft_ctx* ctx, int32_t M, int32_t D, int32_t ncb, int32_t 
  * qkv [rows][(H + 2 Hkv) hd] f32; qn / kn [hd] or NULL and the caches kc / vc [M][Hkv][ncb][hd] in the context's type.  The hook
  * writes NaN patterns into cache rows c .. ncb - 1 (paired: 0 .. ncb - 1) in place, uploads, launches on temporaries and
  * returns both caches whole in place.
- * FT_ERR_ARG: a bad form, M or c, a missing argument, a wide form in an f32 context, a paired pass past xo_ldm;
+ * The paired form is wider than the product's rule (wide_pair: xo_pair + M <= 64) on purpose: on a context of up to 64 rows it
+ * takes every M up to xo_ldm - xo_pair, so that one 64-row context serves every tile edge; on a context above 64 rows, where
+ * the product pairs at no M, it is refused.
+ * FT_ERR_ARG: a bad form, M or c, a missing argument, a wide form in an f32 context, a paired pass past xo_ldm or on a context
+ * above 64 rows (xo_pair > 64);
  * FT_ERR_STATE: a wide form on a context without the lock-step MFMA path. */
 ft_status ft_test_fast_attn(ft_ctx* ctx, int32_t form, int32_t M, int32_t c, const float* qkv, const void* qn, const void* kn,
                             void* kc, void* vc, float* y, uint16_t* y_bf);

@@ -1,4 +1,4 @@
-"""Float64 reference of the 1..4 row decode launches of csrc/ar_kernels.h, ONE LAUNCH AT A TIME (host only; test
+"""Float64 reference of the decode launches of csrc/ar_kernels.h (1..max_batch rows), ONE LAUNCH AT A TIME (host only; test
 infrastructure, the sibling of tests/codec_stage_ref.py, tests/wide_ref.py and tests/pf_ref.py, whose number-format helpers,
 `reach`, `rms_inv`, `_norm_rope`, `attn_ref`, three-order `r_stage` measurement and MARGIN it reuses):
 
@@ -25,9 +25,9 @@ Error model (u = 2^-24; every f32 operation returns its exact result times (1 + 
       lanes are summed in 6 steps (row16_sum: 4, then 3 more additions counted as 2 levels): every term passes at most
       n_c + 6 roundings, so the worst case is (n_c + 7) u S, S = sum |w| |x|.  The bound used is the issue's
       E = min(MARGIN r_stage, (n_c + 7) u) S  (MARGIN = 4) with r_stage = the largest |f32 - f64| / S of the reference's own
-      sums in three f32 orders (codec_stage_ref.measure_r).  A decode launch has 1..4 rows and may have one weight row: too
+      sums in three f32 orders (codec_stage_ref.measure_r).  A decode launch may have one row and one weight row: too
       few sums to measure on.  The sample is therefore the reference's own activation rows AND their rotations along k (the
-      same operands paired with other weights: 64 rows in all), never device output.
+      same operands paired with other weights: 64 rows in all; the first 64 rows of a larger launch), never device output.
   fused RMSNorm.  ss = sum x^2 goes through the same lane chain and wave sum: non-negative terms, relative error
       (n_c + 6) u; / K and + eps add one u each, the square root halves the sum and adds one, the reciprocal one, x inv one:
       t' = x inv is within d = (n_c / 2 + 8) u |t| of the float64 t (7 from the count, 1 for the second order).  16-bit
@@ -58,8 +58,9 @@ Error model (u = 2^-24; every f32 operation returns its exact result times (1 + 
       (float)sqrt(ncb + 1) - the float32 divisor is restated exactly - u; the stored value.  A text token is a copy: err 0.
 
 `emulate_*` restate the launches in float32 with the device's work split (lanes of NT x VEC fma, a butterfly wave sum, MB
-rows per tile, nsplit ranges with the in-block slot merge, the 8-split chunks of merge_splits4): an honest stand-in from
-which tests/test_ar_ref_host.py builds outputs with and without injected faults.
+rows per tile over ceil(M / MB) groups - a tail group's dead rows load row M - 1 and store nothing -, nsplit ranges with the
+in-block slot merge, the 8-split chunks of merge_splits4 on row m's own partials): an honest stand-in from which
+tests/test_ar_ref_host.py builds outputs with and without injected faults.
 """
 from __future__ import annotations
 
@@ -276,9 +277,33 @@ def _chain_dot(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     return _wave_sum(acc)
 
 
+def tile_rows(M: int, MB: int, bug: Optional[str] = None):
+    """gemv_mb_kernel's work split: grid.y = ceil(M / MB) groups of MB rows.  -> (src, dst): slot i of the padded launch loads
+    activation row src[i] (m = min(m0 + mb, M - 1)) and stores output row dst[i], or nothing (-1: m0 + mb >= M).  MB = 0
+    (gemv_kernel, grid.y = M): row m is its own block.  bug: the emulated faults of the split."""
+    if MB == 0:
+        return list(range(M)), list(range(M))
+    src, dst = [], []
+    for g in range((M + MB - 1) // MB):
+        m0 = g * MB
+        tail = m0 + MB > M
+        for mb in range(MB):
+            m = m0 + mb
+            live = m < M
+            s = min(m, M - 1)
+            if bug == "tail_from_last" and tail:                          # a tail group's live rows computed from row M - 1's activation
+                s = M - 1
+            if bug == "group_prev" and g > 0:                             # group g reads group g - 1's rows
+                s = min(m, M - 1) - MB
+            src.append(s)
+            dst.append(m if live or bug == "tail_store" else -1)          # the dead rows of a tail group stored
+    return src, dst
+
+
 def emulate_gemv(fmt: str, pro: int, epi: int, x, W, gain=None, bias=None, resid=None, eps: float = 1e-6, bug: Optional[str] = None,
-                 bug_row: int = 2) -> torch.Tensor:
-    """The launch in float32 with the device's work split.  Returns the stored values (float64).  bug: an emulated fault of
+                 bug_row: int = 2, tail: bool = False) -> torch.Tensor:
+    """The launch in float32 with the device's work split.  Returns the stored values (float64) [M, columns]; tail: [M + 1,
+    columns], the row behind row M - 1 included (NaN unless a fault stores it).  bug: an emulated fault of
     tests/test_ar_ref_host.py."""
     x32, W32 = x.to(F32).clone(), W.to(F32).clone()
     M, K = x32.shape
@@ -288,6 +313,13 @@ def emulate_gemv(fmt: str, pro: int, epi: int, x, W, gain=None, bias=None, resid
     if bug == "mb_row":                                                   # row bug_row of an MB = 4 tile reads row M - 1's activation
         assert MB == 4 and M == 4
         x32[bug_row] = x32[M - 1]
+    if bug in ("tail_store", "tail_from_last", "group_prev"):
+        assert MB > 0, "a fault of gemv_mb_kernel's work split"
+    src, dst = tile_rows(M, MB, bug if bug in ("tail_store", "tail_from_last", "group_prev") else None)
+    x32 = x32[src]                                                        # the padded launch: one slot per (group, mb)
+    if resid is not None:                                                 # the residual is read at the OUTPUT row (0 behind row M - 1: the hook's fill is a NaN pattern)
+        r_all = torch.cat([resid.to(F32), torch.zeros(max(dst) + 1 - M if max(dst) >= M else 0, resid.shape[1])])
+        resid = r_all[[d if d >= 0 else 0 for d in dst]]
     xl = _lanes(x32, NT, VEC)                                             # [M, 64, n]
     if pro == PRO_RMSNORM:
         ss = _chain_dot(xl, xl)[:, None]
@@ -321,7 +353,11 @@ def emulate_gemv(fmt: str, pro: int, epi: int, x, W, gain=None, bias=None, resid
         v = out
     else:
         v = _r32(v, fmt)
-    return v.to(F64)
+    out = torch.full((M + 1, v.shape[1]), float("nan"), dtype=F64)
+    for i, d in enumerate(dst):                                           # the stores, in launch order
+        if 0 <= d <= M:
+            out[d] = v[i].to(F64)
+    return out if tail else out[:M]
 
 
 # ------------------------------------------------------------------------------------------------------ decode attention
@@ -547,6 +583,9 @@ def emulate_decode_attn(fmt: str, qkv, pos, qn, kn, kc, vc, tab, H: int, Hkv: in
 def emulate_merge(fmt: str, part_o, part_ml, bug: Optional[str] = None, bug_split: int = 1) -> torch.Tensor:
     """merge_splits4 in float32: chunks of 8 splits, the running sums rescaled per later chunk; returns rb(y) [M, H hd]."""
     O, ml = torch.from_numpy(np.ascontiguousarray(part_o)), torch.from_numpy(np.ascontiguousarray(part_ml))
+    if bug == "row_mod4":                                                 # row m's partials read at row m mod 4's offset
+        rows = torch.arange(O.shape[0]) % 4
+        O, ml = O[rows], ml[rows]
     m, l = ml[..., 0], ml[..., 1]
     ns = m.shape[-1]
     Mr = torch.full(m.shape[:-1], float("-inf"), dtype=F32)

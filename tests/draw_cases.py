@@ -14,6 +14,12 @@ from tests.shapes import tiny_shape
 FMTS = ("bf16", "fp16", "f32")
 NEW = 8                                                                    # max_new_tokens: cap = 32
 EDGES = {0, 1, 2, 16, 17, 18, NEW + 23, NEW + 24}                          # nf = 0, both sides of ws = 0 | it - 16, cap - 1, cap
+NEW_ROWS66 = 42                                                            # cap = 66: the rows of one launch differ in nf, 0 .. cap - 1 and cap
+
+
+def new_for(kind):
+    """max_new_tokens of a plan's context."""
+    return NEW_ROWS66 if kind == "rows66" else NEW
 
 
 def shape_for(V=2319, cbsize=2048, ncb=10, wide=False, n_slots=128):
@@ -179,6 +185,10 @@ def plan(kind, fmt, size=None):
     t0 = fmt != "fp16"
     if kind == "small":
         return dict(cbsize=size), 33, [(cb, 5, size + cb, {}) for cb in (1, 2, 9)], (33, 1, 4, 5)
+    if kind == "rows66":
+        # the small path beyond the 33 rows of "small": max_batch = 66, launches of 66, 65 and 5 rows (grid rows 33 .. 65 of
+        # sample_small_kernel and finish_draw); ten configurations per codebook give the rows of one launch of each size
+        return dict(cbsize=257), 66, [(cb, 10, 70 + cb, {}) for cb in (1, 9)], (66, 65, 5)
     if kind == "semantic":
         return dict(V=1024, cbsize=512), 33, [(0, 6, 3, dict(t0=t0))], (5, 33, 4)
     if kind == "block":
@@ -195,7 +205,7 @@ def plan(kind, fmt, size=None):
 
 
 def plans():
-    return ([("small", f, v) for f in FMTS for v in SMALL_V] + [("semantic", f, None) for f in FMTS] +
+    return ([("small", f, v) for f in FMTS for v in SMALL_V] + [("rows66", f, None) for f in FMTS] + [("semantic", f, None) for f in FMTS] +
             [("block", f, v) for f in ("fp16", "f32") for v in BLOCK_V] + [("block_real", f, None) for f in ("fp16", "f32")] +
             [("four", "bf16", v) for v in FOUR_V] + [("wide", f, None) for f in ("bf16", "fp16")] + [("wide6144", "bf16", None)])
 
@@ -204,7 +214,7 @@ def family_cases():
     """(name, DrawModel, [(cb, configurations, seed)]) of every probe test below, on models without a context."""
     for kind, fmt, size in plans():
         kw, MB, parts, _ = plan(kind, fmt, size)
-        m = model_of(fmt, shape_for(**kw), MB)
+        m = model_of(fmt, shape_for(**kw), MB, new_for(kind))
         yield f"{kind} {fmt} {size}", m, [(cb, configs_for(m, cb, n, seed, **ckw), seed) for cb, n, seed, ckw in parts]
 
 

@@ -1,4 +1,4 @@
-"""GPU: the decode launches of 1..4 rows (csrc/ar_kernels.h: gemv_kernel, gemv_mb_kernel, attn_decode_kernel with its f32
+"""GPU: the decode launches of 1..4 rows (5..256 rows: tests/test_ar_rows_gpu.py) (csrc/ar_kernels.h: gemv_kernel, gemv_mb_kernel, attn_decode_kernel with its f32
 output and its split partials, gemv_attn_combine_kernel, fast_attn_kernel, embed_kernel) called ONE LAUNCH AT A TIME through
 the product's own host dispatchers (ft_test_gemv, ft_test_decode_attn, ft_test_fast_attn, ft_test_embed) on seeded inputs,
 every element of every written row against the float64 restatement of tests/ar_ref.py:
@@ -484,7 +484,9 @@ def test_what_the_hooks_refuse():
     refused(L.FT_ERR_ARG, bf.test_gemv, 0, 0, zf(1, 6152), zu(4, 6152))                       # pick_nt < 0
     refused(L.FT_ERR_ARG, f32.test_gemv, 0, 0, zf(1, 3080), zf(4, 3080))
     refused(L.FT_ERR_ARG, bf.test_gemv, 0, 0, zf(1, 12), zu(4, 12))                           # K no multiple of 8
-    refused(L.FT_ERR_ARG, bf.test_gemv, 0, 0, zf(5, 8), zu(4, 8))                             # M outside 1..4
+    refused(L.FT_ERR_ARG, bf.test_gemv, 0, 0, zf(5, 8), zu(4, 8))                             # M outside 1..max_batch (4 here)
+    assert bf.max_batch == 4 and engine("bf16", max_batch=64).test_gemv(0, 0, zf(64, 8), zu(4, 8))[3] == A.want_id("bf16", 0, 64, 4, 8)
+    refused(L.FT_ERR_ARG, engine("bf16", max_batch=64).test_gemv, 0, 0, zf(65, 8), zu(4, 8))
     refused(L.FT_ERR_ARG, bf.test_gemv, 1, 0, zf(1, 8), zu(4, 8))                             # the norm without a gain
     refused(L.FT_ERR_ARG, bf.test_gemv, 0, 1, zf(1, 8), zu(4, 8))                             # the residual epilogue without one
     refused(L.FT_ERR_ARG, bf.test_gemv, 0, 2, zf(1, 8), zu(5, 8))                             # SwiGLU on an odd N
@@ -500,7 +502,7 @@ def test_what_the_hooks_refuse():
     refused(L.FT_ERR_ARG, bf.test_decode_attn, zf(5, qkvN), [0] * 5, None, None, c5, c5, wo, None, zf(5, a.dim))
     fq = (a.fast_n_head + 2 * a.fast_n_local_heads) * a.fast_head_dim
     fc = lambda M: zu(M, a.fast_n_local_heads, a.num_codebooks, a.fast_head_dim)
-    refused(L.FT_ERR_ARG, bf.test_fast_attn, 0, zf(5, fq), 0, None, None, fc(5), fc(5))       # the f32 y form takes 1..4 rows
+    refused(L.FT_ERR_ARG, bf.test_fast_attn, 0, zf(5, fq), 0, None, None, fc(5), fc(5))       # the f32 y form takes 1..max_batch rows
     refused(L.FT_ERR_ARG, bf.test_fast_attn, 0, zf(1, fq), a.num_codebooks, None, None, fc(1), fc(1))
     refused(L.FT_ERR_STATE, bf.test_fast_attn, 1, zf(5, fq), 0, None, None, fc(5), fc(5))     # a tiny context has no lock-step MFMA path
     refused(L.FT_ERR_STATE, bf.test_fast_attn, 2, zf(10, fq), 0, None, None, fc(5), fc(5))

@@ -1,8 +1,9 @@
 """Pins tests/ar_ref.py on the CPU: (1) launch by launch on oracle/ar.py's own intermediates of one decode step (one slow
 layer, the head, two fast steps) it passes with NO element flagged, bit for bit where float32 is exact, the boundary flips
 counted; (2) its checkers pass an honest float32 emulation of the device's work split and flag every one of a list of
-emulated kernel faults at the right rows and columns - the proof that tests/test_ar_kernels_gpu.py would fail if a 1..4
-row decode kernel were subtly wrong.
+emulated kernel faults at the right rows and columns - the proof that tests/test_ar_kernels_gpu.py (1..4 rows) and
+tests/test_ar_rows_gpu.py (5..256 rows: MB-row tiles over several groups, a tail group, partials of rows >= 4) would fail if
+a decode kernel were subtly wrong.
 
 Two of the listed faults are roundings left out ("residual added before the rounding", "one norm rounding for two").  An f32
 model has no rounding (RND_NONE), so there they are no faults; they are asserted in bf16 and fp16.  "One element two ulp
@@ -204,6 +205,46 @@ def test_checker_passes_the_honest_product_and_flags_each_product_fault(fmt):
                 assert len(b.rows) >= M - 1 and len(b.cols) >= (cols * 8) // 10, (bug, len(b.rows), len(b.cols))
 
 
+# (M, N, K): MB = 4 in groups of 4 + 3 (NT 2, R 1); MB = 2 in groups of 2 + 2 + 1 (NT 4 takes no four-row tile)
+TILE_CASES = [(7, 23, 520, 4), (5, 21, 1544, 2)]
+
+
+@pytest.mark.parametrize("fmt", A.FMTS)
+def test_checker_passes_the_honest_tiles_and_flags_each_tile_fault(fmt):
+    """More rows than one tile: the emulation of ceil(M / MB) groups passes with no flag, the row behind row M - 1 unwritten;
+    each fault of the split is flagged at the rows it moves and nowhere else.  gemv_mb_kernel exists in bf16 and fp16; an
+    f32 launch is gemv_kernel with grid.y = M (MB = 0), which has no tile to get wrong: there the honest launch alone."""
+    for M, N, K, MB in TILE_CASES:
+        for pro, epi in ((1, A.EPI_STORE), (0, A.EPI_RESID)):
+            x, W, gain, bias, resid = A.seeded_gemv_inputs(fmt, M, N, K, seed=17)
+            kw = dict(x=x, W=W, gain=gain if pro else None, bias=bias, resid=resid if epi == A.EPI_RESID else None)
+            ref = A.gemv_ref(fmt, pro, epi, **kw)
+            assert A.want_id(fmt, epi, M, N, K)[0] == (0 if fmt == "f32" else MB)
+            clean = A.emulate_gemv(fmt, pro, epi, tail=True, **kw)
+            v = A.check(clean[:M].to(F32).numpy(), ref.ref, ref.err, fmt)
+            assert v.checked == M * N and v.flagged == 0, (fmt, M, epi, v.rows, v.cols[:8])
+            assert bool(torch.isnan(clean[M]).all()), "the honest launch stores nothing behind row M - 1"
+            if fmt == "f32":
+                continue
+            src, dst = A.tile_rows(M, MB)
+            assert len(src) == MB * -(-M // MB) and [d for d in dst if d >= 0] == list(range(M)) and dst.count(-1) == len(dst) - M
+            assert all(s == min(i, M - 1) for i, s in enumerate(src))
+            g_last = (M - 1) // MB * MB                                    # first row of the tail group
+            want = {"tail_store": [], "tail_from_last": list(range(g_last, M - 1)), "group_prev": list(range(MB, M))}
+            for bug, rows in want.items():
+                got = A.emulate_gemv(fmt, pro, epi, bug=bug, tail=True, **kw)
+                b = A.check(got[:M].to(F32).numpy(), ref.ref, ref.err, fmt)
+                assert b.rows == rows, (fmt, M, MB, epi, bug, b.rows)
+                assert not bool((b.bad & (got[:M] == clean[:M])).any()), (fmt, bug)
+                if rows:
+                    assert len(b.cols) >= (N * 9) // 10, (bug, len(b.cols))
+                # the sentinel row: written by the fault that stores dead rows, by no other
+                assert bool(torch.isnan(got[M]).all()) == (bug != "tail_store"), (fmt, M, bug)
+            # (MB = 2, M = 5: the tail group's one live row IS row M - 1, so "tail_from_last" moves nothing there - by
+            # construction, as the empty row list above says; at MB = 4, M = 7 it is rows 4 and 5)
+    assert A.tile_rows(3, 0) == ([0, 1, 2], [0, 1, 2])
+
+
 def test_dispatch_restated():
     """want_id over the issue's axes reaches exactly the set the dispatcher can pick."""
     seen = set()
@@ -216,6 +257,17 @@ def test_dispatch_restated():
     plain = {(0, R, nt) for R in (1, 2, 4) for nt in A.NT_OPTS}
     mb = {(MB, R, nt) for (R, MB) in ((1, 2), (1, 4), (2, 2), (2, 4)) for nt in ((1, 2, 4, 6) if MB == 2 else (1, 2))} | {(2, 4, 1), (2, 4, 2)}
     assert seen == plain | mb, (sorted(seen - plain - mb), sorted((plain | mb) - seen))
+    # five rows and more (tests/test_ar_rows_gpu.py): gemv_mb_kernel<R, MB> for (1, 4), (1, 2), (2, 4), (2, 2), (4, 2) at the NT the
+    # register rule allows, gemv_kernel<R> with grid.y = M for every other NT and for f32; R = 4 with NT > 2 is (0, 4, NT)
+    for nt, K in ((4, 2048), (6, 3072)):
+        assert A.want_id("bf16", A.EPI_STORE, 64, 1024, K) == (0, 4, nt) and A.want_id("bf16", A.EPI_STORE, 63, 1024, K) == (2, 2, nt)
+    assert A.want_id("bf16", A.EPI_STORE, 64, 1024, 1024) == (2, 4, 2) and A.want_id("bf16", A.EPI_STORE, 63, 1024, 1024) == (4, 2, 2)
+    assert A.want_id("bf16", A.EPI_STORE, 256, 256, 4096) == (0, 4, 8) and A.want_id("f32", A.EPI_STORE, 256, 256, 256) == (0, 4, 1)
+    assert A.want_id("fp16", A.EPI_SWIGLU, 5, 6, 512) == (4, 2, 1) and A.want_id("bf16", A.EPI_SWIGLU, 5, 6, 2048) == (2, 2, 4)
+    big = {A.want_id(f, A.EPI_STORE, M, N, K) for f, Ks in (("bf16", (512, 1024, 2048, 3072, 4096)), ("f32", (256, 1024, 3072)))
+           for K in Ks for M in (5, 7, 63, 64, 256) for N in (1, 5, -(-2048 // M), -(-65536 // M), 1024)}
+    assert big == ({(MB, R, nt) for MB, R in ((4, 1), (4, 2)) for nt in (1, 2)} | {(2, R, nt) for R in (1, 2) for nt in (4, 6)} |
+                   {(2, 4, 1), (2, 4, 2), (0, 4, 4), (0, 4, 6)} | {(0, R, nt) for R in (1, 2, 4) for nt in (8, 1, 4, 12)}), sorted(big)
     assert A.pick_nt(6152, "bf16") < 0 and A.pick_nt(3080, "f32") < 0 and A.pick_nt(6144, "bf16") == 12
 
 
@@ -287,6 +339,30 @@ def test_checker_passes_the_honest_decode_attention_and_flags_each_fault(fmt):
     if fmt != "f32":
         b = A.check(_two_ulp(clean, 2, 7, fmt).to(F32).numpy(), xr.ref, xr.err, fmt)
         assert b.flagged == 1 and b.rows == [2] and b.cols == [7]
+
+
+@pytest.mark.parametrize("fmt", ("bf16", "f32"))
+def test_merge_reading_another_rows_partials_is_flagged(fmt):
+    """Seven rows, 16 splits: the merge of row m must read the partials at m H nsplit (hd).  Read at row m mod 4's offset, rows
+    0..3 are right and rows 4, 5, 6 take the partials of rows 0, 1, 2: flagged there, in most columns, and nowhere else."""
+    M, H, Hkv, hd, n_slots, ns, D = 7, 4, 2, 64, 264, 16, 24
+    qkv, qn, kn, kc, vc, tab = _attn_inputs(fmt, M, H, Hkv, hd, n_slots, seed=8)
+    pos = [0, 9, 128, 262, 40, 3, 200]
+    ref = A.decode_attn_ref(fmt, qkv, pos, qn, kn, kc, vc, tab, H, Hkv, hd, ns)
+    po, pml, _, kc1, vc1 = A.emulate_decode_attn(fmt, qkv, pos, qn, kn, kc, vc, tab, H, Hkv, hd, ns)
+    assert A.check_parts(po, pml, ref).flagged == 0
+    vk, v_ok, same = A.check_cache(fmt, kc, vc, kc1, vc1, pos, ref.k, ref.v)
+    assert vk.flagged == 0 and vk.checked == M * Hkv * hd and v_ok and same
+    g = torch.Generator().manual_seed(6)
+    r = lambda t: A.store(t.to(F64), fmt).to(F32)
+    wo, bo, resid = r(0.05 * torch.randn(D, H * hd, generator=g)), r(0.1 * torch.randn(D, generator=g)), r(torch.randn(M, D, generator=g))
+    _, _, yr, er = A.merge_ref(po, pml, fmt)
+    xr = A.gemv_ref(fmt, 0, A.EPI_RESID, yr, wo, bias=bo, resid=resid, dx_in=er)
+    x_out = lambda y: A.emulate_gemv(fmt, 0, A.EPI_RESID, y.to(F32), wo, bias=bo, resid=resid)
+    v = A.check(x_out(A.emulate_merge(fmt, po, pml)).to(F32).numpy(), xr.ref, xr.err, fmt)
+    assert v.flagged == 0 and v.checked == M * D, (v.rows, v.cols)
+    b = A.check(x_out(A.emulate_merge(fmt, po, pml, bug="row_mod4")).to(F32).numpy(), xr.ref, xr.err, fmt)
+    assert b.rows == [4, 5, 6] and len(b.cols) >= D // 2, (b.rows, b.cols)
 
 
 # ------------------------------------------------------------------------------------------------- fast attention

@@ -16,7 +16,7 @@ import torch
 
 from tests import draw_ref as D
 from tests.draw_cases import (BLOCK_V, EDGES, FMTS, FOUR_V, NEW, SMALL_V, configs_for, counter_rows, discriminating, frames_used,
-                              launches, model_of, plan, rows_for, shape_for, strict_q_row)
+                              launches, model_of, new_for, plan, rows_for, shape_for, strict_q_row)
 
 pytestmark = pytest.mark.gpu
 
@@ -102,7 +102,7 @@ def run(eng, model, cb, parts, last=False):
 # ------------------------------------------------------------------------------------------------------------ the cases
 def run_plan(kind, fmt, size=None, env=()):
     kw, MB, parts, sizes = plan(kind, fmt, size)
-    eng, model = context(fmt, MB, env=env, **kw)
+    eng, model = context(fmt, MB, new=new_for(kind), env=env, **kw)
     total = left = 0
     fl = []
     for cb, n, seed, ckw in parts:
@@ -125,6 +125,15 @@ def test_small_kernel(fmt, fv):
     """sample_small_kernel at a full last thread (1024), a partial one (V % 4 != 0), idle waves (V <= 192) and one lane (5);
     cb in {1, 2, ncb - 1}; launches of 1, 4, 5 and 33 rows with mixed controls and frames."""
     assert run_plan("small", fmt, fv)[2] > 30
+    drop_contexts()
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_small_kernel_66_rows(fmt):
+    """max_batch = 66 (cap = 66, so that 66 rows of one launch differ in nf): launches of 66, 65 and 5 rows at cb = 1 and
+    ncb - 1 - grid rows 33 .. 65 of sample_small_kernel and finish_draw, which a batch beyond the MFMA launches' 64 rows runs."""
+    eng, model, n = run_plan("rows66", fmt)
+    assert model.MB == 66 and model.cap == 66 and n > 250
     drop_contexts()
 
 

@@ -509,7 +509,8 @@ def test_bookkeeping_faults(fault, field):
 # Pinned, so that a spread dropping out of a kind of test is seen.  bf16 and f32 use all four wherever a test has five or more
 # configurations; in fp16 the wide spreads lose to probe validity (probabilities below 3e-8 are 0 in fp16), not to the band.
 ALL4 = [0.3, 1.0, 3.0, 8.0]
-SPREADS_IN_USE = {("small", "bf16"): ALL4, ("small", "fp16"): ALL4, ("small", "f32"): ALL4, ("semantic", "bf16"): ALL4,
+SPREADS_IN_USE = {("small", "bf16"): ALL4, ("small", "fp16"): ALL4, ("small", "f32"): ALL4, ("rows66", "bf16"): ALL4,
+                  ("rows66", "fp16"): ALL4, ("rows66", "f32"): ALL4, ("semantic", "bf16"): ALL4,
                   ("semantic", "fp16"): [0.3, 3.0], ("semantic", "f32"): ALL4, ("block", "fp16"): [0.3, 1.0, 3.0], ("block", "f32"): ALL4,
                   ("block_real", "fp16"): [3.0, 8.0], ("block_real", "f32"): [3.0, 8.0], ("four", "bf16"): ALL4, ("wide", "bf16"): ALL4,
                   ("wide", "fp16"): [0.3, 1.0], ("wide6144", "bf16"): [1.0, 3.0, 8.0]}
@@ -537,8 +538,12 @@ def test_input_families_hold_their_caps():
                 used.setdefault((kind, fmt), set()).add(refs["spread"])
                 for sp, why in refs["skipped"]:
                     passed_over[(kind, fmt, size, c.top_p, sp, why)] = passed_over.get((kind, fmt, size, c.top_p, sp, why), 0) + 1
-            seen = frames_used(launches(model, cb, rows, plan(kind, fmt, None if size == "None" else int(size))[3], filler, seed))
+            parts_ = launches(model, cb, rows, plan(kind, fmt, None if size == "None" else int(size))[3], filler, seed)
+            seen = frames_used(parts_)
             assert EDGES <= seen, (name, cb, sorted(EDGES - seen))
+            if kind == "rows66":                                           # the plan is about its row counts: one launch of each size, every nf of a 66-row launch distinct
+                assert model.MB == 66 and model.cap == 66 and [len(p) for p in parts_[:3]] == [66, 65, 5], (name, [len(p) for p in parts_])
+                assert {model.cap - 1, model.cap} <= seen and all(len({r.nf for r in p}) == len(p) for p in parts_)
         assert left <= 0.1 * total, (name, left, total)
         assert {"last must-keep", "first must-drop"} <= kinds, (name, kinds)   # (the argmax probe is the last must-keep one where lo = 1)
     for key, n in sorted(passed_over.items()):

@@ -7,7 +7,10 @@ written row against the float64 restatement of tests/wide_ref.py:
 
 with err derived there.  Rows past M must still hold the sentinel, cache rows other than the appended one must be
 bit-unchanged.  tests/test_wide_ref_host.py proves the checker flags the subtle faults this is for.  No frame is traced:
-the wiring between the launches stays the job of the oracle-following tests (test_ar_gpu.py, test_wide_fp16_gpu.py)."""
+the wiring between the launches stays the job of the oracle-following tests (test_ar_gpu.py, test_wide_fp16_gpu.py).
+
+A subset runs once more on a max_batch = 256 context, whose octet-major operands lie at xo_ldm = 512 (the contexts above have
+32 and 128): the launches a 5..64-row batch runs on an engine sized for 256 rows, where the paired codebook pass never holds."""
 import os
 
 import numpy as np
@@ -232,9 +235,12 @@ def attn_inputs(fmt, H, Hkv):
 def test_attention(fmt, H, Hkv, M):
     """attn_wide_kernel<2>, <1> and <4> from 128 (row, kv head) blocks on, the split fall-back below: one launch mixing the
     context lengths of CTX_LENS; y, the appended K and V rows, and every other cache row bit-unchanged."""
+    check_attention(engine(fmt, H, Hkv), fmt, H, Hkv, M)
+
+
+def check_attention(eng, fmt, H, Hkv, M):
     hd = 128
     qkv, qn, kn, pos, kc, vc, tab = attn_inputs(fmt, H, Hkv)
-    eng = engine(fmt, H, Hkv)
     b = lambda t: h16_bits(t, fmt)
     y, kc2, vc2, splits = eng.test_wide_attn(qkv[:M].numpy(), pos[:M], b(qn), b(kn), kc[:M], vc[:M])
     if M * Hkv >= 128:
@@ -261,6 +267,71 @@ def test_attention(fmt, H, Hkv, M):
         was = was.copy()
         was[rows, :, pos[:M]] = new
         assert np.array_equal(got, was), "a cache row other than pos[m] changed"
+
+
+# ------------------------------------------------------------------------------------------------------ a 256-row context
+BIG = 256                                                       # xo_pair = 256, xo_ldm = 512
+
+
+@pytest.mark.parametrize("epi,N,head", [(R.STORE, 64, False), (R.STORE, 4096, False), (R.STORE, 32768, False), (R.STORE, 4096, True),
+                                        (R.SWIGLU, 64, False), (R.RESID, 1024, False)])
+@pytest.mark.parametrize("fmt", FMTS)
+def test_linear_at_xo_ldm_512(fmt, epi, N, head):
+    """Every epilogue and tile class (<1,1>, <1,2>, <2,2> store, the vocabulary head, <1,2> / <2,2> SwiGLU, the residual
+    epilogue aliased and not) at K = 1024 and M = 5, 17, 33, 64 with the operands at row stride 512: same verdicts, same
+    sentinel rows."""
+    eng = engine(fmt, max_batch=BIG)
+    line = ""
+    for M in (5, 17, 33, 64):
+        for alias in ((False, True) if epi == R.RESID else (False,)):
+            line = run_linear(eng, fmt, epi, M, N, 1024, with_bias=bool(M & 1) and not head, alias=alias, head=head,
+                              kind="vocabulary head (wide_head_kernel)" if head and M <= 32 else None)
+    print(f"\n{fmt} epi {epi} N {N} head {head} on a {BIG}-row context: {line}")
+
+
+@pytest.mark.parametrize("M", (16, 64))
+@pytest.mark.parametrize("fmt", FMTS)
+def test_attention_at_xo_ldm_512(fmt, M):
+    check_attention(engine(fmt, max_batch=BIG), fmt, 16, 8, M)
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fast_attention_and_draw_at_xo_ldm_512(fmt):
+    """fast_attn_kernel's octet-major output (form 1) at M = 5 and 64 on the 256-row context, judged as
+    tests/test_ar_kernels_gpu.py judges it; the paired form is refused (xo_pair = 256: xo_pair + M <= 64 holds for no M, the
+    product never pairs there), and a lock-step draw at cb = 0 sends its octet-major copy to xo_femb, never to the paired rows."""
+    from fish_tts_amd import _lib as L
+    from fish_tts_amd.ar_engine import HipError
+    from tests import ar_ref as A
+    from tests import test_ar_kernels_gpu as AK
+    eng = engine(fmt, max_batch=BIG)
+    qkv, qn, kn, kc, vc, tab, (H, Hkv, hd, ncb) = AK.fast_inputs(fmt, "16/8x128", 128)
+    b = lambda t: A.wbits(t, fmt)
+    HD, line = H * hd, ""
+    for M in (5, 64):
+        for c in (0, 1, ncb - 1):
+            norm = bool((M + c) & 1)
+            q_, k_ = (qn, kn) if norm else (None, None)
+            what = f"{fmt} wide M {M} c {c} qk-norm {norm} xo_ldm 512"
+            yb, kc1, vc1 = eng.test_fast_attn(1, qkv[:M].numpy(), c, None if q_ is None else b(q_), None if k_ is None else b(k_), kc[:M], vc[:M])
+            assert yb.shape[1] == 2 * BIG and bool((yb[:, M:, :] == A.SENT16).all()), "rows past M written: " + what
+            kin, vin = AK.nan_from(kc[:M], vc[:M], c, fmt)
+            ref = A.fast_attn_ref(fmt, qkv[:M], c, q_, k_, kin, vin, tab, H, Hkv, hd)
+            line = AK.check_fast(fmt, what, f"fast_attn_kernel (wide, hd {hd}, xo_ldm 512)", A.xo_rows(yb, M, HD), ref, kin, vin, kc1, vc1, c, M)
+    for M in (5, 64):
+        with pytest.raises(HipError) as e:
+            eng.test_fast_attn(2, torch.cat([qkv[:M], qkv[64:64 + M]]).numpy(), 0, None, None, kc[:M], vc[:M])
+        assert f"({L.FT_ERR_ARG})" in str(e.value), str(e.value)
+    a = eng.args
+    g = np.random.default_rng(9)
+    for M in (5, 64):
+        for cb in (0, 1):
+            V = a.vocab_size if cb == 0 else min(1024, a.codebook_size)
+            got = eng.test_draw(g.standard_normal((M, V)).astype(np.float32), cb, [eng._sampling(0.7, 0.8, 1.1, seed=3 + m) for m in range(M)],
+                                [1 + m % 20 for m in range(M)], np.zeros((M, a.num_codebooks + 1, 8 + 24), dtype=np.int32))
+            assert got["what"] >= 0 and not got["what"] & 8, (M, cb, got["what"])
+            assert got["what"] & 4, (M, cb, got["what"])                   # the lock-step form: the copy goes to xo_femb
+    print(f"\n{line}")
 
 
 def test_every_class_is_reachable():
