@@ -49,6 +49,10 @@ class ft_level_info(C.Structure):
                 ("capped", C.c_int32)]
 
 
+class ft_item_fx(C.Structure):
+    _fields_ = [("speed_pct", C.c_int32), ("pitch_cents", C.c_int32), ("loudness", C.c_int32)]
+
+
 class ft_sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
                 ("ban_eos", C.c_int32), ("seed", C.c_uint64)]
@@ -117,6 +121,8 @@ SYMBOLS = {
     "ft_codec_decode_join_level": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.POINTER(ft_join_params), _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), _P,
                                                _P]),
+    "ft_codec_decode_join_items": (C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.POINTER(ft_join_params), _P,
+                                               C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64), _P, _P]),
     "ft_test_level_hops": (C.c_int32, [_P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ft_ride_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int32, _P, _P]),
     "ft_codec_ride": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),

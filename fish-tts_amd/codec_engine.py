@@ -607,7 +607,7 @@ class CodecHipEngine:
     def decode_join(self, codes_list: Sequence[np.ndarray], sample_rate: Optional[int] = None, speed: Optional[float] = None,
                     pitch: Optional[float] = None, params=(0.0, 1, 0, 0), gaps: Optional[Sequence[int]] = None,
                     started: bool = False, fx: Optional[OutputFx] = None, loudness: Optional[float] = None,
-                    levels: Optional[list] = None):
+                    levels: Optional[list] = None, item_fx: Optional[Sequence[OutputFx]] = None):
         """The utterances of one document - codes_list[i] (n_codebooks+1, T_i) integer - decoded at `sample_rate`, `speed`
         and `pitch` (as decode) and joined on the device into one waveform (ft_codec_decode_join): each trimmed to its
         loud part, faded at the cuts and laid out behind gaps[i] samples of silence.  `params`: (threshold, hop, keep,
@@ -617,8 +617,25 @@ class CodecHipEngine:
         outputs concatenated here - a piece depends on its own item only, so the grouping does not show.  `loudness` (LUFS,
         as decode): every item is levelled on its own before the join finds its edges (ft_codec_decode_join_level), so the
         threshold acts on the levelled samples - an absolute threshold such as synthesize_long's silence_db then means the
-        same for every item; `levels`: a list that receives one LevelInfo per item.  Returns (audio float32, cuts (n, 2)
-        int64: the samples [a, e) kept of every item)."""
+        same for every item; `levels`: a list that receives one LevelInfo per item.  `item_fx`: one checked OutputFx per item
+        instead of the call's one chain - the lines of a script, each at its own pace, pitch and level
+        (ft_codec_decode_join_items): item i's samples before the join are those of decode(codes_list[i], fx=item_fx[i]), bit
+        for bit; the chains travel with their items through the grouping; all share one rate (the result is one waveform)
+        and none is live, ValueError otherwise; `levels` then receives every item's LevelInfo, the empty result for an item
+        without a level.  Returns (audio float32, cuts (n, 2) int64: the samples [a, e) kept of every item)."""
+        if item_fx is not None:
+            item_fx = list(item_fx)
+            if len(item_fx) != len(codes_list):
+                raise ValueError("decode_join: one item_fx entry per item")
+            for f in item_fx:
+                if not isinstance(f, OutputFx):
+                    raise ValueError(f"decode_join: item_fx holds {f!r}, expected a checked OutputFx")
+                f.no_live()
+            if len({f.wav_rate for f in item_fx}) > 1:
+                raise ValueError("decode_join: the items of a call share one sample rate (the result is one waveform), got "
+                                 f"{sorted({f.wav_rate for f in item_fx})}")
+            if item_fx:
+                fx = OutputFx(rate=item_fx[0].rate)
         fx = OutputFx.of(sample_rate, speed, pitch, loudness) if fx is None else fx
         fx.no_live()
         items = [np.ascontiguousarray(np.asarray(c), dtype=np.int32) for c in codes_list]
@@ -646,12 +663,22 @@ class CodecHipEngine:
             for b, c in enumerate(items[i:j]):
                 block[b, :, :c.shape[1]] = c
             glens = np.ascontiguousarray(lens[i:j])
-            cap = sum(fx.out_len(int(t) * self.frame_len) for t in glens) + int(g[i:j].sum())
+            chains = [fx] * B if item_fx is None else item_fx[i:j]
+            cap = sum(f.out_len(int(t) * self.frame_len) for f, t in zip(chains, glens)) + int(g[i:j].sum())
             audio = np.empty(max(cap, 1), dtype=np.float32)
             total = C.c_int64(0)
             gcuts = np.zeros((B, 2), dtype=np.int64)
             ggaps = np.ascontiguousarray(g[i:j])
-            if fx.level is None:
+            if item_fx is not None:
+                infos = (L.ft_level_info * B)()
+                native = (L.ft_item_fx * B)(*[L.ft_item_fx(f.pct or 100, f.cents or 0, f.native_level) for f in chains])
+                self._check(self.lib.ft_codec_decode_join_items(
+                    self._h, block.ctypes.data_as(C.c_void_p), B, T, glens.ctypes.data_as(C.c_void_p), fx.wav_rate, native,
+                    C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0, audio.ctypes.data_as(C.c_void_p), cap,
+                    C.byref(total), gcuts.ctypes.data_as(C.c_void_p), infos), "ft_codec_decode_join_items")
+                if levels is not None:
+                    levels.extend(LevelInfo.of(i) for i in infos)
+            elif fx.level is None:
                 self._check(self.lib.ft_codec_decode_join(
                     self._h, block.ctypes.data_as(C.c_void_p), B, T, glens.ctypes.data_as(C.c_void_p),
                     *fx.native, C.byref(jp), ggaps.ctypes.data_as(C.c_void_p), 1 if begun else 0, audio.ctypes.data_as(C.c_void_p), cap,

@@ -13,6 +13,7 @@
 #include "engine.h"
 #include "fx_chain.h"
 #include "join_plan.h"
+#include "item_fx.h"
 
 using namespace ft;
 // the output chain's host arithmetic (fx_chain.h), on the kernels' constants
@@ -23,8 +24,9 @@ static_assert(chain::RS_LDS == RS_LDS && chain::TS_N == TS_N && chain::TS_HS == 
               chain::LV_WARM_HOPS == LV_WARM && chain::RD_A == RD_LOOK && chain::RD_R == RD_SLEW,
               "fx_chain.h and codec_kernels.h disagree");
 static_assert(sizeof(ft_level_info) == 32 && offsetof(LevelItem, L) + sizeof(ft_level_info) == sizeof(LevelItem) &&
-              offsetof(ft_level_info, peak) == 8 && offsetof(ft_level_info, capped) == 24,
-              "ft_level_info is the tail of a LevelItem");
+              offsetof(ft_level_info, peak) == 8 && offsetof(ft_level_info, capped) == 24 &&
+              offsetof(LevelItem, target) == offsetof(LevelItem, L) + 28,
+              "ft_level_info is the tail of a LevelItem, the item's target in the bytes that pad it");
 
 #define FT_TRY(x) do { ft_status s_ = (x); if (s_ != FT_OK) return s_; } while (0)
 
@@ -917,10 +919,11 @@ static ft_status level_alloc(ft_ctx* ctx, size_t hops) {
     return FT_OK;
 }
 
-// Levels B items in place (x[b], n[b] samples at `rate`, written earlier on the codec's stream): the three launches (two
-// when the call only measures: target 0, or `scale` false) and the copy of the table back to the host.  The caller has
-// called level_alloc for the items' hops, synchronizes, and then reads the results with level_fetch.
-static ft_status level_enqueue(ft_ctx* ctx, int B, float* const* x, const int64_t* n, int rate, int target, bool scale = true) {
+// Levels B items in place (x[b], n[b] samples at `rate`, written earlier on the codec's stream), item b toward targets[b]:
+// the three launches (two when the call only measures: no target at all, or `scale` false) and the copy of the table back
+// to the host.  The caller has called level_alloc for the items' hops, synchronizes, and then reads the results with
+// level_fetch.
+static ft_status level_enqueue(ft_ctx* ctx, int B, float* const* x, const int64_t* n, int rate, const int* targets, bool scale = true) {
     CodecState* s = ctx->codec;
     hipStream_t st = s->stream;
     s->lv_up.assign(sizeof(LevelTab), 0);
@@ -928,14 +931,16 @@ static ft_status level_enqueue(ft_ctx* ctx, int B, float* const* x, const int64_
     chain::lv_design(rate, h->c);
     h->ceiling = chain::lv_ceiling();
     h->H = chain::lv_hop(rate);
-    h->target = target;
     h->B = B;
     long long hop0 = 0, most = 0, widest = 0;
+    bool any = false;
     for (int b = 0; b < B; ++b) {
         LevelItem& it = h->it[b];
         it.x = x[b];
         it.n = n[b];
         it.hop0 = hop0;
+        it.target = targets[b];
+        any = any || targets[b] != 0;
         const long long nh = (long long)level_hops(n[b], rate);
         hop0 += nh;
         most = std::max(most, nh);
@@ -948,7 +953,7 @@ static ft_status level_enqueue(ft_ctx* ctx, int B, float* const* x, const int64_
     const int gf = (int)std::max(1LL, (most + LV_FILTER_THREADS - 1) / LV_FILTER_THREADS);
     level_filter_kernel<<<dim3(gf, 1, B), LV_FILTER_THREADS, 0, st>>>(s->lv_tab, s->lv_hops, s->lv_peaks);
     level_gain_kernel<<<B, LV_GAIN_THREADS, 0, st>>>(s->lv_tab, s->lv_hops, s->lv_peaks);
-    if (scale && target != 0) {
+    if (scale && any) {
         const int gx = (int)std::max(1LL, std::min(1024LL, (widest + LV_SCALE_THREADS - 1) / LV_SCALE_THREADS));
         level_scale_kernel<<<dim3(gx, 1, B), LV_SCALE_THREADS, 0, st>>>(s->lv_tab);
     }
@@ -957,10 +962,24 @@ static ft_status level_enqueue(ft_ctx* ctx, int B, float* const* x, const int64_
     return FT_OK;
 }
 
-// The results of the last level_enqueue, once the stream was synchronized.
-static void level_fetch(CodecState* s, int B, ft_level_info* infos) {
+// Every item toward the call's one target.
+static ft_status level_enqueue(ft_ctx* ctx, int B, float* const* x, const int64_t* n, int rate, int target, bool scale = true) {
+    int targets[64];
+    if (B < 0 || B > 64) return ft_fail(ctx, FT_ERR_STATE, "level: more than 64 items");
+    std::fill(targets, targets + B, target);
+    return level_enqueue(ctx, B, x, n, rate, targets, scale);
+}
+
+// The results of the last level_enqueue, once the stream was synchronized: its item b goes to infos[to ? to[b] : b].  The
+// item's target lies in the bytes that pad an ft_level_info: those stay zero, as they always were.
+static void level_fetch(CodecState* s, int B, ft_level_info* infos, const int* to = nullptr) {
     const LevelTab* h = (const LevelTab*)s->lv_down.data();
-    for (int b = 0; infos && b < B; ++b) memcpy(&infos[b], &h->it[b].L, sizeof(ft_level_info));
+    constexpr size_t told = offsetof(ft_level_info, capped) + sizeof(int32_t);
+    for (int b = 0; infos && b < B; ++b) {
+        ft_level_info* out = &infos[to ? to[b] : b];
+        memcpy(out, &h->it[b].L, told);
+        memset((char*)out + told, 0, sizeof(ft_level_info) - told);
+    }
 }
 
 struct Fx {   // the output stages of a call: resampler segments, and the time-scale and pitch segments in front of some of them
@@ -1675,20 +1694,31 @@ static ft_status fx_refuse(ft_ctx* ctx, const std::string& fn, int rate, int pct
 
 // The chain's device side; the caller holds s->mu.  The tables of its rate and cents, and the buffers of the first stage it
 // has (each stage's allocation brings those of the stages behind it); with a level, the level stage's table and `hops` hop sums.
-static ft_status fx_prepare(ft_ctx* ctx, FxDesc* d, size_t hops = 0) {
-    if (d->level != 0) FT_TRY(level_alloc(ctx, hops));
-    FT_TRY(rs_table(ctx, d->rate, &d->rs));
-    if (d->cents != 0) {
-        FT_TRY(ps_table(ctx, d->cents, &d->ps));
+// `count` chains of one call (at most 64, all at one rate): the union of theirs (item_fx.h) - every distinct cents value's
+// table, the buffers of the longest chain, `hops` hop sums for those with a level.
+static ft_status fx_prepare(ft_ctx* ctx, FxDesc* d, size_t hops = 0, int count = 1) {
+    if (count < 1 || count > JOIN_MAX_ITEMS) return ft_fail(ctx, FT_ERR_STATE, "fx_prepare: 1 to 64 chains");
+    const ItemFxUnion u = item_fx_union(d, count, nullptr);
+    bool live = false;       // (a stream's; such a call has one chain)
+    for (int i = 0; i < count; ++i) live = live || d[i].live != 0;
+    if (u.levelled > 0) FT_TRY(level_alloc(ctx, hops));
+    FT_TRY(rs_table(ctx, d[0].rate, &d[0].rs));
+    const CodecState::PsTab* ps[JOIN_MAX_ITEMS];
+    for (int k = 0; k < u.ncents; ++k) FT_TRY(ps_table(ctx, u.cents[k], &ps[k]));
+    for (int i = 0; i < count; ++i) {
+        d[i].rs = d[0].rs;
+        if (d[i].cents != 0) d[i].ps = ps[std::find(u.cents, u.cents + u.ncents, d[i].cents) - u.cents];
+    }
+    if (u.ps) {
         FT_TRY(ps_alloc(ctx));
-    } else if (d->pct != 100) {
+    } else if (u.ts) {
         FT_TRY(ts_alloc(ctx));
-    } else if (d->K > 0 || d->live != 0) {
+    } else if (u.rs || live) {
         FT_TRY(rs_alloc(ctx));       // (a live stream's samples pass through the resampler's buffer at any rate)
     }
     // a live stream: everything a call's resampler can give, and what 64 streams can hold back
     // (kept in step with the resampler's buffer once the context has had a live stream: a later chain may widen that one)
-    return d->live != 0 || ctx->codec->rd_seg ? rd_alloc(ctx, ctx->codec->rs_cap + (size_t)RS_MAX_SEGS * RD_MAX_HELD) : FT_OK;
+    return live || ctx->codec->rd_seg ? rd_alloc(ctx, ctx->codec->rs_cap + (size_t)RS_MAX_SEGS * RD_MAX_HELD) : FT_OK;
 }
 
 extern "C" int64_t ft_timescaled_len(int32_t speed_pct, int64_t n_in) {
@@ -1869,51 +1899,71 @@ extern "C" int32_t ft_join_groups(const int32_t* lens, int32_t n, int32_t max_fr
     return join_groups(lens, n, max_frames, ends);
 }
 
-// ft_codec_decode_join and ft_codec_decode_join_level: the items decoded one after the other into join_in, levelled there in one
-// go (the item is a grid dimension) when the call has a level, then joined.
+// ft_codec_decode_join, ft_codec_decode_join_level and ft_codec_decode_join_items: the items decoded one after the other into
+// join_in, each through its own chain, those with a level levelled there in one go (the item is a grid dimension), then
+// joined.  `per_item`: fx has B entries and the refusals name the item (item_fx.h); else fx is the one chain of all items.
 static ft_status decode_join(ft_ctx* ctx, const std::string& fn, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
-                             int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t level, const ft_join_params* jp,
+                             int32_t sample_rate, const ft_item_fx* fx, bool per_item, const ft_join_params* jp,
                              const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
                              int64_t* cuts, ft_level_info* infos) {
     if (!ctx) return FT_ERR_ARG;
-    FxDesc d;
-    FT_TRY(fx_refuse(ctx, fn, sample_rate, speed_pct, pitch_cents, &d, level));
+    FxDesc d[JOIN_MAX_ITEMS];
+    if (per_item) {
+        FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d[0]));       // the rate, which the items share, first
+        if (!fx || B < 1 || B > JOIN_MAX_ITEMS) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+        const ItemFxBad bad = item_fx_make(sample_rate, fx, B, d);
+        if (bad.bad != FxDesc::OK) {       // (fx_refuse words the message; it judges the item again, to the same end)
+            const ft_item_fx& f = fx[bad.item];
+            const ft_status st = fx_refuse(ctx, fn + ": item " + std::to_string(bad.item), sample_rate, f.speed_pct, f.pitch_cents, &d[0], f.loudness);
+            return st != FT_OK ? st : ft_fail(ctx, FT_ERR_ARG, fn + ": item " + std::to_string(bad.item) + ": a bad chain");
+        }
+    } else {
+        FT_TRY(fx_refuse(ctx, fn, sample_rate, fx->speed_pct, fx->pitch_cents, &d[0], fx->loudness));
+    }
     FT_TRY(codec_ready(ctx));
     if (!codes || !audio || !total || !cuts || B < 1 || B > JOIN_MAX_ITEMS || T < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
     if (T > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": T exceeds max_frames");
+    if (!per_item) std::fill(d + 1, d + B, d[0]);
     CodecState* s = ctx->codec;
     const int R = ctx->cc.n_codebooks + 1;
     int64_t n[JOIN_MAX_ITEMS], off[JOIN_MAX_ITEMS], frames = 0, need = 0;
-    for (int b = 0; b < B; ++b) {
-        const int Tb = lens ? lens[b] : T;
-        if (Tb < 0 || Tb > T) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad length");
-        frames += Tb;
-        n[b] = d.out_len((long long)Tb * s->frame_len);
-    }
+    if (const char* why = item_fx_lens(d, B, T, lens, s->frame_len, n, &frames)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
     if (frames > ctx->cc.max_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": sum(lens) exceeds max_frames");
     if (const char* why = join_check(B, n, jp, gaps, started, capacity, &need)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
     const int64_t in_floats = join_offsets(B, n, off);
+    const ItemFxUnion u = item_fx_union(d, B, n);
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
-    size_t hops = 0;
-    for (int b = 0; b < B; ++b) hops += level_hops(n[b], d.rate);
-    FT_TRY(fx_prepare(ctx, &d, hops));
+    FT_TRY(fx_prepare(ctx, d, u.hops, B));
     FT_TRY(join_alloc(ctx, (size_t)in_floats, (size_t)need));
     // the items as decode_items runs them (one synchronize each, as there), their samples left side by side in join_in
     for (int b = 0; b < B; ++b) {
         const int Tb = lens ? lens[b] : T;
         if (Tb == 0) continue;
         Fx g;
-        const bool staged = item_stages(s, d, (long long)Tb * s->frame_len, g);
+        const bool staged = item_stages(s, d[b], (long long)Tb * s->frame_len, g);
         FT_TRY(decode_one(ctx, codes + (size_t)b * R * T, T, Tb, s->join_in + off[b], nullptr, staged ? &g : nullptr, hipMemcpyDeviceToDevice));
     }
-    if (d.level != 0) {
+    if (u.levelled > 0) {       // the levelled items alone, each toward its own target
         float* x[JOIN_MAX_ITEMS];
-        for (int b = 0; b < B; ++b) x[b] = s->join_in + off[b];
-        FT_TRY(level_enqueue(ctx, B, x, n, d.rate, d.level));
+        int64_t nl[JOIN_MAX_ITEMS];
+        int targets[JOIN_MAX_ITEMS];
+        for (int k = 0; k < u.levelled; ++k) {
+            x[k] = s->join_in + off[u.lv[k]];
+            nl[k] = n[u.lv[k]];
+            targets[k] = d[u.lv[k]].level;
+        }
+        FT_TRY(level_enqueue(ctx, u.levelled, x, nl, d[0].rate, targets));
     }
     FT_TRY(join_run(ctx, B, n, off, jp, gaps, started, audio, total, cuts, need, false));
-    if (d.level != 0) level_fetch(s, B, infos);
+    if (per_item && infos) {
+        const ft_level_info none = {-INFINITY, 0.f, 1.f, 0, 0, 0};
+        for (int b = 0; b < B; ++b) {
+            memset(&infos[b], 0, sizeof(ft_level_info));
+            infos[b] = none;
+        }
+    }
+    if (u.levelled > 0) level_fetch(s, u.levelled, infos, u.lv);
     return FT_OK;
 }
 
@@ -1921,16 +1971,26 @@ extern "C" ft_status ft_codec_decode_join(ft_ctx* ctx, const int32_t* codes, int
                                           int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, const ft_join_params* jp,
                                           const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
                                           int64_t* cuts) {
-    return decode_join(ctx, "ft_codec_decode_join", codes, B, T, lens, sample_rate, speed_pct, pitch_cents, 0, jp, gaps, started,
-                       audio, capacity, total, cuts, nullptr);
+    const ft_item_fx fx = {speed_pct, pitch_cents, 0};
+    return decode_join(ctx, "ft_codec_decode_join", codes, B, T, lens, sample_rate, &fx, false, jp, gaps, started, audio, capacity,
+                       total, cuts, nullptr);
 }
 
 extern "C" ft_status ft_codec_decode_join_level(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
                                                 int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t loudness,
                                                 const ft_join_params* jp, const int64_t* gaps, int32_t started, float* audio,
                                                 int64_t capacity, int64_t* total, int64_t* cuts, ft_level_info* infos) {
-    return decode_join(ctx, "ft_codec_decode_join_level", codes, B, T, lens, sample_rate, speed_pct, pitch_cents, loudness, jp, gaps,
-                       started, audio, capacity, total, cuts, infos);
+    const ft_item_fx fx = {speed_pct, pitch_cents, loudness};
+    return decode_join(ctx, "ft_codec_decode_join_level", codes, B, T, lens, sample_rate, &fx, false, jp, gaps, started, audio,
+                       capacity, total, cuts, infos);
+}
+
+extern "C" ft_status ft_codec_decode_join_items(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                                int32_t sample_rate, const ft_item_fx* fx, const ft_join_params* jp,
+                                                const int64_t* gaps, int32_t started, float* audio, int64_t capacity,
+                                                int64_t* total, int64_t* cuts, ft_level_info* infos) {
+    return decode_join(ctx, "ft_codec_decode_join_items", codes, B, T, lens, sample_rate, fx, true, jp, gaps, started, audio,
+                       capacity, total, cuts, infos);
 }
 
 extern "C" ft_status ft_test_join(ft_ctx* ctx, const float* x, int32_t B, int64_t stride, const int64_t* n, const ft_join_params* jp,

@@ -1859,7 +1859,8 @@ static __global__ __launch_bounds__(JOIN_THREADS) void join_assemble_kernel(cons
     }
 }
 
-// ---- level stage (ft_codec_loudness, ft_codec_decode_level, ft_codec_decode_join_level; stated in fishtts_hip.h): the items
+// ---- level stage (ft_codec_loudness, ft_codec_decode_level, ft_codec_decode_join_level, ft_codec_decode_join_items; stated in
+// fishtts_hip.h): the items
 // of a call - whole utterances at the output rate, left on the device by the stages above - each measured (BS.1770
 // integrated loudness, sample peak) and multiplied by one gain, in place.  Three launches whatever the number of items (the
 // item is blockIdx.z of a device table):
@@ -1874,7 +1875,8 @@ static __global__ __launch_bounds__(JOIN_THREADS) void join_assemble_kernel(cons
 //   level_gain_kernel     one workgroup per item: the peak, the 400 ms blocks from four hop sums each, the absolute and the
 //                         relative gate, L and the gain.  Per-thread partial sums over blocks j = t, t + 256, ..., then
 //                         added by thread 0 in thread order: the same bits on every call.
-//   level_scale_kernel    x[i] = g x[i], one float32 multiply (not launched when the call only measures)
+//   level_scale_kernel    x[i] = g x[i], one float32 multiply (not launched when the call only measures; an item without
+//                         a target is left alone)
 struct LevelItem {
     float* x;                  // the item's samples (device), levelled in place
     long long n;
@@ -1882,12 +1884,12 @@ struct LevelItem {
     double L;                  // out, in the layout of ft_level_info from here on: integrated loudness (-inf: nothing measured)
     float p, g;                // out: sample peak, gain
     int blocks, gated, capped; // out: 400 ms blocks, those that passed both gates, whether the ceiling bound the gain
-    int pad;
+    int target;                // in: the item's target in hundredths of a LUFS (0: measure only, the item is left as it is)
 };
 struct LevelTab {
     double c[10];              // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2
     double ceiling;            // 10^(-1/20)
-    int H, target, B, pad;     // hop; target in hundredths of a LUFS (0: measure only)
+    int H, B, pad[2];          // hop; items (the target travels with the item: a call may level each toward its own)
     LevelItem it[64];
 };
 constexpr int LV_WARM = 2, LV_CHUNK = 16, LV_FILTER_THREADS = 64, LV_GAIN_THREADS = 256, LV_SCALE_THREADS = 256;
@@ -1990,8 +1992,8 @@ static __global__ __launch_bounds__(LV_GAIN_THREADS) void level_gain_kernel(Leve
             const double L = level_lufs(s / (double)k);
             it.L = L;
             it.gated = (int)k;
-            if (tab->target != 0) {
-                double g = pow(10.0, ((double)tab->target / 100.0 - L) / 20.0);
+            if (it.target != 0) {
+                double g = pow(10.0, ((double)it.target / 100.0 - L) / 20.0);
                 const double p = (double)it.p;
                 if (p > 0.0 && tab->ceiling / p < g) {
                     g = tab->ceiling / p;
@@ -2005,6 +2007,7 @@ static __global__ __launch_bounds__(LV_GAIN_THREADS) void level_gain_kernel(Leve
 
 static __global__ __launch_bounds__(LV_SCALE_THREADS) void level_scale_kernel(const LevelTab* tab) {
     const LevelItem& it = tab->it[blockIdx.z];
+    if (it.target == 0) return;       // measured only
     const float g = it.g;
     float* x = it.x;
     for (long long i = (long long)blockIdx.x * LV_SCALE_THREADS + threadIdx.x; i < it.n; i += (long long)gridDim.x * LV_SCALE_THREADS)

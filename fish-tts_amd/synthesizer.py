@@ -311,13 +311,15 @@ class FishTTS:
 
     def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
                           repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]],
-                          made: Optional[dict] = None):
+                          made: Optional[dict] = None, text_references: Optional[list] = None):
         """The engines and Utterances of a batch run (synthesize_batch, synthesize_batch_stream); call with _gen_lock
         held.  More engines than the first one when batch_streams > 1 and the texts outnumber max_batch (created on first
         use, kept); a voice's K/V prefix from the cache, spread over the engines; utterance i draws with seed + i, or
         seeds[i].  `made` (a dict the caller owns): the voice is one made up for this call - its prefix is built directly with
         engine.build_prefix, once per engine, kept in `made` and freed by the caller; the cache of the user's voices is
-        not touched."""
+        not touched.  `text_references` (one entry per text): text i speaks in the voice text_references[i], a list of
+        VoiceProfile, its prefix from the cache; an entry of None means `references` (and `made`), as without the
+        argument."""
         cache = self._prefix_cache
         from .batch import Utterance
         from .prompt import build_prompt_split
@@ -326,7 +328,9 @@ class FishTTS:
         assert 0 < temperature < 2, "temperature must be in (0, 2)"
         if seeds is not None and len(seeds) != len(texts):
             raise ValueError("seeds must have one entry per text")
-        prompt_text, prompt_tokens = self._get_prompt_data(references)
+        if text_references is not None and len(text_references) != len(texts):
+            raise ValueError("text_references must have one entry per text")
+        call_prompt = self._get_prompt_data(references)
         ncb = self._engine.args.num_codebooks
         utts = []
         engines = [self._engine]
@@ -335,6 +339,8 @@ class FishTTS:
                 self._more_engines.append(self._engine_factory())
             engines += self._more_engines
         for i, text in enumerate(texts):
+            own_voice = text_references is not None and text_references[i] is not None
+            prompt_text, prompt_tokens = self._get_prompt_data(text_references[i]) if own_voice else call_prompt
             enc, n_prefix = build_prompt_split(self._tokenizer, text, prompt_text, prompt_tokens, ncb)
             if enc.shape[1] > self._engine.args.max_seq_len - 2048:
                 raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
@@ -342,7 +348,7 @@ class FishTTS:
             if cache is not None and n_prefix >= cache.min_positions:
                 # a saved prefix lives in one engine's memory and pins its utterance there: spread them evenly
                 eng = engines[i % len(engines)]
-                if made is None:
+                if made is None or own_voice:
                     prefix = cache.get(eng, enc[:, :n_prefix])
                 else:
                     if id(eng) not in made:
@@ -550,12 +556,16 @@ class FishTTS:
     def _long_codes_served(self, texts, references, sampling, seed):
         """([codes of every segment], the server's codec lock) from an open BatchServer; None: no server (or it closed before
         it took the text) - the caller generates."""
+        return self._codes_served(lambda srv: self._long_serve(srv, texts, references, sampling, seed))
+
+    def _codes_served(self, serve):
+        """_long_codes_served over serve(srv) -> (takes, release), as _long_serve gives them."""
         from .serve import ServerClosed
         srv = getattr(self, "_server", None)
         if srv is None:
             return None
         try:
-            takes, release = self._long_serve(srv, texts, references, sampling, seed)
+            takes, release = serve(srv)
         except ServerClosed:
             return None
         try:
@@ -582,15 +592,23 @@ class FishTTS:
         return self._long_chunks(texts, references, sampling, seed, fx, jp, gaps)
 
     def _long_chunks(self, texts, references, sampling, seed, fx, jp, gaps) -> Iterator[bytes]:
+        return self._join_chunks(len(texts), lambda srv: self._long_serve(srv, texts, references, sampling, seed),
+                                 lambda emit, stopped: self._long_generate(texts, references, sampling, seed, emit, stopped),
+                                 fx, jp, gaps)
+
+    def _join_chunks(self, n, serve, generate, fx, jp, gaps, item_fx=None, on_cuts=None) -> Iterator[bytes]:
+        """The PCM chunks of n segments as they become ready in order: serve(srv) -> (takes, release) through an open
+        BatchServer (_long_serve), else generate(emit, stopped) on a thread of its own (_long_generate); every ready run
+        decoded and joined as one group.  `item_fx`: the segments' own chains in place of `fx`; on_cuts(first, cuts): what
+        the join kept of the group that starts at segment `first`, before its chunk goes out."""
         from .longform import ready_prefixes
         from .serve import ServerClosed
-        n = len(texts)
         q: "queue.Queue" = queue.Queue()
         stop = threading.Event()
         srv, lock, release, threads = getattr(self, "_server", None), None, None, []
         if srv is not None:
             try:
-                takes, release = self._long_serve(srv, texts, references, sampling, seed)
+                takes, release = serve(srv)
                 lock = srv.codec_lock
             except ServerClosed:
                 srv = None                       # closed meanwhile: served here, once the server has let go of _gen_lock
@@ -604,7 +622,7 @@ class FishTTS:
 
         def feed_own() -> None:
             try:
-                self._long_generate(texts, references, sampling, seed, lambda i, c: q.put((i, c)), stop.is_set)
+                generate(lambda i, c: q.put((i, c)), stop.is_set)
             except _LongStopped:
                 pass
             except BaseException as e:  # noqa: BLE001
@@ -616,11 +634,15 @@ class FishTTS:
         try:
             for first, group in ready_prefixes(q, n):
                 kw = dict(params=jp, gaps=gaps[first:first + len(group)], started=started, fx=fx)
+                if item_fx is not None:
+                    kw["item_fx"] = item_fx[first:first + len(group)]
                 if lock is not None:
                     with lock:
-                        audio, _ = self._vocoder.decode_join(group, **kw)
+                        audio, cuts = self._vocoder.decode_join(group, **kw)
                 else:
-                    audio, _ = self._vocoder.decode_join(group, **kw)
+                    audio, cuts = self._vocoder.decode_join(group, **kw)
+                if on_cuts is not None:
+                    on_cuts(first, cuts)
                 if len(audio):
                     started = True
                     yield (np.clip(audio, -1.0, 1.0) * 32767).astype(np.int16).tobytes()   # synthesize_long's samples
@@ -632,6 +654,195 @@ class FishTTS:
                 t.join()
         if not started:
             raise RuntimeError("No audio generated")
+
+    # ------------------------------------------------------------------ scripts (extension)
+    def _script_plan(self, lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
+                     sample_rate, speed, pitch, loudness, marks):
+        """Every check of a script call, before any device work: (the plan - script.plan_script - and every segment's
+        references, None where it speaks in the call's voice).  ValueError for a bad value, an unknown voice, or more
+        voices than the prefix cache holds: the cache frees its least recently used entry on insert, and an Utterance of
+        the batch still holds the prefix it was given."""
+        from .script import plan_script
+        if marks is not None and not isinstance(marks, list):
+            raise ValueError(f"marks must be None or a list, got {type(marks).__name__}")
+        plan = plan_script(lines, voices, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
+                           sample_rate, speed, pitch, loudness)
+        used = []
+        for v in plan.voices:
+            if v is not None and v not in used:
+                used.append(v)
+        for v in used:
+            if not isinstance(voices[v], (list, tuple)) or not all(isinstance(p, VoiceProfile) for p in voices[v]):
+                raise ValueError(f"voices[{v!r}] must be a list of VoiceProfile")
+        cache = self._prefix_cache
+        if cache is not None:
+            # the call's own voice goes through the cache too, unless it is made up for this call
+            count = len(used) + (1 if None in plan.voices and self._get_prompt_data(references)[1] else 0)
+            engines = self._batch_streams if self._batch_streams > 1 and len(plan.texts) > self._max_batch else 1
+            if count * engines > cache.capacity:
+                raise ValueError(f"a script of {count} voices" + (f" on {engines} engines" if engines > 1 else "") +
+                                 f": the reference cache holds {cache.capacity} prefixes, and every voice of the batch needs "
+                                 "its own to stay (split the script, or build the instance with cache_reference_kv=False)")
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        return plan, [None if v is None else list(voices[v]) for v in plan.voices]
+
+    def _script_generate(self, texts, seg_refs, references, sampling, seed, emit, stopped) -> None:
+        """_long_generate for a script: segment i speaks in seg_refs[i], or (None) in the call's voice; segment i draws with
+        seed + i, and all run as one lock-step batch with refill.  Without any reference voice synthesize_long's rule holds
+        for the segments in the call's voice alone: the first of them runs first, on its own, and is the voice of the
+        others through a prefix that this call builds and frees."""
+        from .batch import run_batch, run_batch_streams
+
+        def guard(i, block):
+            if stopped():
+                raise _LongStopped()
+
+        def run(idx, refs, made=None):
+            engines, utts = self._batch_utterances([texts[i] for i in idx], refs, *sampling, 0, [seed + i for i in idx],
+                                                   made=made, text_references=[seg_refs[i] for i in idx])
+            done = lambda j: emit(idx[j], utts[j].codes())   # noqa: E731
+            if len(engines) > 1:
+                run_batch_streams(engines, utts, on_frames=guard, on_done=done)
+            else:
+                run_batch(self._engine, utts, on_frames=guard, on_done=done)
+            return utts
+
+        made = None
+        own = [i for i, r in enumerate(seg_refs) if r is None]
+        with self._gen_lock:
+            try:
+                rest = list(range(len(texts)))
+                if len(own) > 1 and not self._get_prompt_data(references)[1]:
+                    codes0 = run(own[:1], references)[0].codes()
+                    rest.remove(own[0])
+                    if codes0.shape[1]:
+                        references, made = [VoiceProfile(codes=codes0, text=texts[own[0]])], {}
+                if rest:
+                    run(rest, references, made)
+            finally:
+                for pf in (made or {}).values():
+                    pf.free()
+
+    def _script_serve(self, srv, texts, seg_refs, references, sampling, seed):
+        """_long_serve for a script: (takes in segment order, release).  The segments with a voice of their own are queued
+        first; then, without any reference voice, the first segment in the call's voice is awaited and made the voice of
+        the others."""
+        from .generation import PrefixCache
+        from .serve import ServerClosed
+        own, reqs, taken = None, {}, {}
+        mine = [i for i, r in enumerate(seg_refs) if r is None]
+        try:
+            for k, r in enumerate(seg_refs):
+                if r is not None:
+                    reqs[k] = srv.submit_codes(texts[k], r, *sampling, seed + k)
+            if len(mine) > 1 and not self._get_prompt_data(references)[1]:
+                k = mine[0]
+                taken[k] = srv.take_codes(srv.submit_codes(texts[k], references, *sampling, seed + k))
+                if taken[k].shape[1]:
+                    references = [VoiceProfile(codes=taken[k], text=texts[k])]
+                    if self._prefix_cache is not None:
+                        own = PrefixCache(capacity=1, min_positions=self._prefix_cache.min_positions)
+            for k in mine:
+                if k not in taken:
+                    reqs[k] = srv.submit_codes(texts[k], references, *sampling, seed + k, voice_cache=own)
+        except ServerClosed:
+            for r in reqs.values():
+                srv.cancel(r)
+            if own is not None:
+                srv.retire_cache(own)       # the closing server still finishes what it took, then frees the prefix
+            raise
+
+        def release(cancel: bool = False):
+            if cancel:
+                for r in reqs.values():
+                    srv.cancel(r)                # (nothing happens to a request that has ended)
+            if own is not None:
+                srv.retire_cache(own)
+        return [(lambda c=taken[k]: c) if k in taken else (lambda r=reqs[k]: srv.take_codes(r)) for k in range(len(texts))], release
+
+    def synthesize_script(self, lines, voices=None, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
+                          top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
+                          pause: float = 0.2, paragraph_pause: float = 0.5, line_pause: float = 0.4,
+                          silence_db: Optional[float] = -45.0, max_chars: int = 200, min_chars: int = 24,
+                          sample_rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None,
+                          loudness: Optional[float] = None, marks: Optional[list] = None) -> bytes:
+        """Extension: a script - a dialogue, a narrated piece with quoted speakers - as one WAV.  `lines`: a list of
+        script.Line (text, voice, speed, pitch, loudness, volume, pause), or an SSML string (script.parse_ssml: speak, p, s,
+        voice, break, prosody); `voices`: name -> list of VoiceProfile.  Every line is split as synthesize_long splits a text
+        and ALL segments of all lines run as one lock-step batch with refill, segment i (counted over the whole script)
+        drawing with seed + i, each with its own voice's prompt and K/V prefix.  A line without a voice speaks in
+        `references` / set_references; with neither, synthesize_long's rule holds for those lines alone (their first segment
+        becomes their voice).  The codec decodes every segment through its line's own chain - `speed`, `pitch`, `loudness`
+        are the line's, or the call's where the line has None; `volume` dB is added to the loudness target - and joins them
+        on the GPU (CodecHipEngine.decode_join with item_fx), behind `pause` / `paragraph_pause` inside a line and the
+        line's `pause` or `line_pause` in front of it.  One `sample_rate` per call.  `marks` (a list) receives one
+        (start_sample, end_sample) per line at the output rate, from the join's cuts and gaps.  A script of one plain Line
+        is synthesize_long of its text, byte for byte.  While a BatchServer is open the segments join its batch.
+        ValueError before any device work: no line, an unknown voice, a bad value in a line or in the call, a bad
+        line_pause, more distinct voices than the reference cache holds (8; not with cache_reference_kv=False)."""
+        from .script import line_marks
+        plan, seg_refs = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db,
+                                           max_chars, min_chars, sample_rate, speed, pitch, loudness, marks)
+        sampling = (temperature, top_p, repetition_penalty, max_tokens)
+        codes = self._codes_served(lambda srv: self._script_serve(srv, plan.texts, seg_refs, references, sampling, seed))
+        lock = None
+        if codes is None:
+            got = {}
+            self._script_generate(plan.texts, seg_refs, references, sampling, seed, got.__setitem__, lambda: False)
+            codes = [got[i] for i in range(len(plan.texts))]
+        else:
+            codes, lock = codes
+        kw = dict(params=tuple(plan.jp), gaps=plan.gaps, item_fx=plan.fx)
+        if lock is not None:
+            with lock:
+                audio, cuts = self._vocoder.decode_join(codes, **kw)
+        else:
+            audio, cuts = self._vocoder.decode_join(codes, **kw)
+        if not len(audio):
+            raise RuntimeError("No audio generated")
+        if marks is not None:
+            found = [None] * plan.n_lines
+            line_marks(plan.line_of, plan.gaps, cuts, found)
+            marks.extend(found)
+        return self._to_wav_bytes(audio, plan.rate)
+
+    def synthesize_script_stream(self, lines, voices=None, references: Optional[List[VoiceProfile]] = None,
+                                 temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
+                                 max_tokens: int = 2048, seed: int = 0, pause: float = 0.2, paragraph_pause: float = 0.5,
+                                 line_pause: float = 0.4, silence_db: Optional[float] = -45.0, max_chars: int = 200,
+                                 min_chars: int = 24, sample_rate: Optional[int] = None, speed: Optional[float] = None,
+                                 pitch: Optional[float] = None, loudness: Optional[float] = None,
+                                 marks: Optional[list] = None) -> Iterator[bytes]:
+        """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
+        (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
+        out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
+        byte for byte; no empty chunk is yielded.  `marks` fills as groups go out: a line's entry is added once its last
+        segment went out, and in the end the list is synthesize_script's.  The arguments are checked here, at the call."""
+        plan, seg_refs = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db,
+                                           max_chars, min_chars, sample_rate, speed, pitch, loudness, marks)
+        sampling = (temperature, top_p, repetition_penalty, max_tokens)
+        return self._script_chunks(plan, seg_refs, references, sampling, seed, marks)
+
+    def _script_chunks(self, plan, seg_refs, references, sampling, seed, marks) -> Iterator[bytes]:
+        from .script import line_marks
+        found = [None] * plan.n_lines
+        state = {"at": 0, "started": False, "told": 0}
+
+        def on_cuts(first, cuts) -> None:
+            if marks is None:
+                return
+            end = first + len(cuts)
+            state["at"], state["started"] = line_marks(plan.line_of[first:end], plan.gaps[first:end], cuts, found,
+                                                       state["at"], state["started"])
+            done = plan.n_lines if end == len(plan.texts) else plan.line_of[end]     # the lines whose last segment went out
+            marks.extend(found[state["told"]:done])
+            state["told"] = max(state["told"], done)
+
+        yield from self._join_chunks(
+            len(plan.texts), lambda srv: self._script_serve(srv, plan.texts, seg_refs, references, sampling, seed),
+            lambda emit, stopped: self._script_generate(plan.texts, seg_refs, references, sampling, seed, emit, stopped),
+            None, tuple(plan.jp), plan.gaps, item_fx=plan.fx, on_cuts=on_cuts)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:

@@ -398,6 +398,26 @@ ft_status ft_codec_decode_join_level(ft_ctx* ctx, const int32_t* codes, int32_t 
                                      int32_t sample_rate, int32_t speed_pct, int32_t pitch_cents, int32_t loudness,
                                      const ft_join_params* jp, const int64_t* gaps, int32_t started, float* audio,
                                      int64_t capacity, int64_t* total, int64_t* cuts, ft_level_info* infos);
+/* ft_codec_decode_join_level with a chain per item - the lines of a script, each at its own pace, pitch and level, in one
+ * waveform: item b goes through fx[b] (B entries; the values as ft_codec_decode_level takes them).  One output rate per
+ * call, because the result is one waveform.  What fixes the result: before the join, item b's samples are, bit for bit, row b
+ * of ft_codec_decode_level(sample_rate, fx[b].speed_pct, fx[b].pitch_cents, fx[b].loudness) for the same codes, and the
+ * output is ft_test_join over those rows with jp, gaps and started.  With all fx[b] equal the call is
+ * ft_codec_decode_join_level, bit for bit.  An item with loudness = 0 is not levelled and its infos[b] (infos may be NULL)
+ * is the empty result {-inf, 0, 1, 0, 0, 0}; the levelled items are levelled in one go, each toward its own target: three
+ * launches whatever B.  No kernel is new here: the stages are those above, driven per item, and the level stage reads its
+ * target from the item.  Before the first decode the call builds the pitch table of every distinct cents value, allocates
+ * the buffers of its longest chain and the hop sums of its levelled items.  Every argument is checked before any device
+ * work, in this order, and a refused call changes nothing: the rate; then for each item in order its speed, cents, pair and
+ * level as ft_codec_decode_level judges them (FT_ERR_ARG, the message names the item); then the checks of
+ * ft_codec_decode_join, out_lens[b] being that of item b's own chain. */
+typedef struct ft_item_fx {
+    int32_t speed_pct, pitch_cents, loudness;
+} ft_item_fx;
+ft_status ft_codec_decode_join_items(ft_ctx* ctx, const int32_t* codes, int32_t B, int32_t T, const int32_t* lens,
+                                     int32_t sample_rate, const ft_item_fx* fx, const ft_join_params* jp,
+                                     const int64_t* gaps, int32_t started, float* audio, int64_t capacity, int64_t* total,
+                                     int64_t* cuts, ft_level_info* infos);
 /* Ride.  A stream cannot wait for its integrated loudness, so it gets a second, streaming level stage: a look-ahead gain
  * rider with carried state, last in the stream's chain: codec -> time-scale stage -> pitch stage -> rate resampler -> ride.
  * It is a different operation from the level above - a gain that varies in time, steered by the loudness of the programme
