@@ -215,9 +215,11 @@ class BatchServer:
 
     def submit_codes(self, text: str, references=None, temperature: float = 0.7, top_p: float = 0.8,
                      repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0, voice_cache=None) -> _Request:
-        """One segment of a long text (FishTTS.synthesize_long) or of a script (FishTTS.synthesize_script: every segment
-        with its own line's `references`): a request whose output is its codes; take_codes waits for them.  `voice_cache`: a PrefixCache of the caller's own for the request's voice, so that a voice made up for
-        one call stays out of the cache of the user's voices (the caller clears it when its requests have ended)."""
+        """One segment of a long text or of a script (segments.serve, under FishTTS.synthesize_long / synthesize_script and
+        their streams; `references`: the segment's own, or the call's): a request whose output is its codes; take_codes
+        waits for them.  `voice_cache`: a PrefixCache of the caller's own for the request's voice, so that a voice made up
+        for one call stays out of the cache of the user's voices (the caller cancels what is still open and hands the
+        cache to retire_cache when it is done, or when the server closes under its submissions)."""
         utt, n_prefix = self._prepare(text, references, temperature, top_p, repetition_penalty, max_tokens, seed)
         return self.submit(utt, n_prefix, codes=True, voice_cache=voice_cache)
 

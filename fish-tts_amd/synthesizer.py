@@ -321,17 +321,12 @@ class FishTTS:
         VoiceProfile, its prefix from the cache; an entry of None means `references` (and `made`), as without the
         argument."""
         cache = self._prefix_cache
-        from .batch import Utterance
-        from .prompt import build_prompt_split
-        assert 0 < top_p <= 1, "top_p must be in (0, 1]"
-        assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
-        assert 0 < temperature < 2, "temperature must be in (0, 2)"
+        _check_sampling(temperature, top_p, repetition_penalty)
         if seeds is not None and len(seeds) != len(texts):
             raise ValueError("seeds must have one entry per text")
         if text_references is not None and len(text_references) != len(texts):
             raise ValueError("text_references must have one entry per text")
         call_prompt = self._get_prompt_data(references)
-        ncb = self._engine.args.num_codebooks
         utts = []
         engines = [self._engine]
         if self._batch_streams > 1 and len(texts) > self._max_batch:
@@ -340,23 +335,40 @@ class FishTTS:
             engines += self._more_engines
         for i, text in enumerate(texts):
             own_voice = text_references is not None and text_references[i] is not None
-            prompt_text, prompt_tokens = self._get_prompt_data(text_references[i]) if own_voice else call_prompt
-            enc, n_prefix = build_prompt_split(self._tokenizer, text, prompt_text, prompt_tokens, ncb)
-            if enc.shape[1] > self._engine.args.max_seq_len - 2048:
-                raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
-            prefix = None
+            utt, n_prefix = self._utterance(text, self._get_prompt_data(text_references[i]) if own_voice else call_prompt,
+                                            (temperature, top_p, repetition_penalty, max_tokens),
+                                            seeds[i] if seeds is not None else seed + i)
             if cache is not None and n_prefix >= cache.min_positions:
                 # a saved prefix lives in one engine's memory and pins its utterance there: spread them evenly
                 eng = engines[i % len(engines)]
                 if made is None or own_voice:
-                    prefix = cache.get(eng, enc[:, :n_prefix])
+                    utt.prefix = cache.get(eng, utt.prompt[:, :n_prefix])
                 else:
                     if id(eng) not in made:
-                        made[id(eng)] = eng.build_prefix(np.ascontiguousarray(enc[:, :n_prefix], dtype=np.int32))
-                    prefix = made[id(eng)]
-            utts.append(Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seeds[i] if seeds is not None else seed + i,
-                                  prefix=prefix))
+                        made[id(eng)] = eng.build_prefix(np.ascontiguousarray(utt.prompt[:, :n_prefix], dtype=np.int32))
+                    utt.prefix = made[id(eng)]
+            utts.append(utt)
         return engines, utts
+
+    def _utterance(self, text: str, prompt, sampling, seed: int):
+        """(Utterance, n_prefix) of one text behind `prompt` = (reference texts, reference codes), as generate_long builds
+        and checks it; `sampling` = (temperature, top_p, repetition_penalty, max_tokens)."""
+        from .batch import Utterance
+        from .prompt import build_prompt_split
+        temperature, top_p, repetition_penalty, max_tokens = sampling
+        _check_sampling(temperature, top_p, repetition_penalty)
+        enc, n_prefix = build_prompt_split(self._tokenizer, text, *prompt, self._engine.args.num_codebooks)
+        if enc.shape[1] > self._engine.args.max_seq_len - 2048:
+            raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
+        return Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seed), n_prefix
+
+    def _run_utterances(self, engines, utts, on_frames=None, on_done=None) -> None:
+        """Runs the utterances of _batch_utterances: one lock-step batch with refill, or several side by side."""
+        from .batch import run_batch, run_batch_streams
+        if len(engines) > 1:
+            run_batch_streams(engines, utts, on_frames=on_frames, on_done=on_done)
+        else:
+            run_batch(self._engine, utts, on_frames=on_frames, on_done=on_done)
 
     def synthesize_batch(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
                          temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
@@ -368,16 +380,12 @@ class FishTTS:
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
         semantics as synthesize(), `sample_rate`, `speed`, `pitch` and `loudness` (as synthesize_at; every utterance is
         levelled on its own) included."""
-        from .batch import run_batch, run_batch_streams
         fx = _output_fx(sample_rate, speed, pitch, loudness)
         self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
                                                    seed, seeds)
-            if len(engines) > 1:
-                run_batch_streams(engines, utts)
-            else:
-                run_batch(self._engine, utts)
+            self._run_utterances(engines, utts)
         out = []
         for u in utts:
             codes = u.codes()
@@ -411,7 +419,6 @@ class FishTTS:
         `loudness`: ValueError here, before any work - the level needs the whole utterance (synthesize_batch has it).
         `live_loudness` (LUFS in [-50, -5]) is what a stream takes instead: each utterance's stream is ridden toward that
         loudness on the GPU by a gain that looks one second ahead, last in its chain (as synthesize_stream)."""
-        from .batch import run_batch, run_batch_streams
         from .batch_stream import stream_utterances
         fx = _output_fx(sample_rate, speed, pitch, loudness, live_loudness).no_level("synthesize_batch_stream")
         self._no_server("synthesize_batch_stream")
@@ -423,10 +430,7 @@ class FishTTS:
             with self._gen_lock:
                 engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty,
                                                        max_tokens, seed, seeds)
-                if len(engines) > 1:
-                    run_batch_streams(engines, utts, on_frames=on_frames, on_done=on_done)
-                else:
-                    run_batch(self._engine, utts, on_frames=on_frames, on_done=on_done)
+                self._run_utterances(engines, utts, on_frames, on_done)
 
         return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
                                  min_first_chunk=min_first_chunk, fx=fx)
@@ -434,82 +438,38 @@ class FishTTS:
     # ------------------------------------------------------------------ long texts (extension)
     def _long_plan(self, text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
                    loudness=None):
-        """Every check of a long-text call, before any device work: (texts, output stages, join parameters, gaps).
-        ValueError for a bad value."""
+        """Every check of a long-text call, before any device work: its segments.SegmentPlan - every segment in the call's
+        voice, one chain of output stages for all.  ValueError for a bad value."""
         from .longform import join_params, split_text
+        from .segments import SegmentPlan
         fx = _output_fx(sample_rate, speed, pitch, loudness)
         jp, gap, pgap = join_params(fx.rate, pause, paragraph_pause, silence_db)
         segs = split_text(text, max_chars, min_chars)
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
-        return [s.text for s in segs], fx, tuple(jp), [pgap if s.paragraph else gap for s in segs]
+        return SegmentPlan([s.text for s in segs], [None] * len(segs), [pgap if s.paragraph else gap for s in segs], tuple(jp),
+                           fx.wav_rate, fx)
 
-    def _long_generate(self, texts, references, sampling, seed: int, emit, stopped) -> None:
-        """The codes of every segment, emit(i, codes) as each is complete (from any thread).  Segment i draws with seed + i;
-        all go through one lock-step batch with refill (_batch_utterances, run_batch / run_batch_streams), the voice prefix
-        from the cache.  Without any reference voice segment 0 runs first, on its own, and its text and codes are the
-        voice of every later segment - its K/V prefix built directly (engine.build_prefix) and freed when the call ends, so
-        the cache of the user's voices is neither entered nor evicted from.  `stopped()`: the consumer went away."""
-        from .batch import run_batch, run_batch_streams
+    def _segment_calls(self, plan, references, sampling, seed: int):
+        """The keyword arguments of segments.join_wav / join_chunks for a checked call: the vocoder, the open BatchServer
+        (asked when the work begins: a stream's first next()), and the segments through that server or as lock-step batches
+        on this instance's engines (_batch_utterances with _gen_lock held: the voices' prefixes from the cache, one made up
+        for this call in `made`)."""
+        from . import segments
 
-        def guard(i, block):
-            if stopped():
-                raise _LongStopped()
+        def has_voice() -> bool:
+            return bool(self._get_prompt_data(references)[1])
 
-        def run(texts_, refs, seed_, first, made=None):
-            engines, utts = self._batch_utterances(texts_, refs, *sampling, seed_, None, made=made)
-            done = lambda j: emit(first + j, utts[j].codes())   # noqa: E731
-            if len(engines) > 1:
-                run_batch_streams(engines, utts, on_frames=guard, on_done=done)
-            else:
-                run_batch(self._engine, utts, on_frames=guard, on_done=done)
-            return utts
+        def run(idx, seg_refs, refs, seeds, made, on_frames, on_done) -> None:
+            engines, utts = self._batch_utterances([plan.texts[i] for i in idx], refs, *sampling, 0, seeds, made=made,
+                                                   text_references=seg_refs)
+            self._run_utterances(engines, utts, on_frames, lambda j: on_done(j, utts[j].codes()))
 
-        made = None
-        with self._gen_lock:
-            try:
-                start = 0
-                if not self._get_prompt_data(references)[1] and len(texts) > 1:
-                    codes0 = run(texts[:1], references, seed, 0)[0].codes()
-                    start = 1
-                    if codes0.shape[1]:
-                        references, made = [VoiceProfile(codes=codes0, text=texts[0])], {}
-                if start < len(texts):
-                    run(texts[start:], references, seed + start, start, made)
-            finally:
-                for pf in (made or {}).values():
-                    pf.free()
-
-    def _long_serve(self, srv, texts, references, sampling, seed: int):
-        """_long_generate through an open BatchServer: the segments as requests whose output is their codes
-        (BatchServer.submit_codes).  Returns the requests' results as a list of callables in text order, each blocking
-        until its codes are there, and a release() to call when all were taken.  ServerClosed (nothing was handed out
-        yet): the caller serves the text itself."""
-        from .generation import PrefixCache
-        from .serve import ServerClosed
-        own, reqs, first = None, [], []
-        try:
-            if not self._get_prompt_data(references)[1] and len(texts) > 1:
-                codes0 = srv.take_codes(srv.submit_codes(texts[0], references, *sampling, seed))
-                first = [lambda: codes0]
-                if codes0.shape[1]:
-                    references = [VoiceProfile(codes=codes0, text=texts[0])]
-                    if self._prefix_cache is not None:
-                        own = PrefixCache(capacity=1, min_positions=self._prefix_cache.min_positions)
-            for k in range(len(first), len(texts)):
-                reqs.append(srv.submit_codes(texts[k], references, *sampling, seed + k, voice_cache=own))
-        except ServerClosed:
-            if own is not None:
-                srv.retire_cache(own)       # the closing server still finishes what it took, then frees the prefix
-            raise
-
-        def release(cancel: bool = False):
-            if cancel:
-                for r in reqs:
-                    srv.cancel(r)                # (nothing happens to a request that has ended)
-            if own is not None:
-                srv.retire_cache(own)        # freed on the server's scheduler thread, once none of its requests can use it
-        return first + [lambda r=r: srv.take_codes(r) for r in reqs], release
+        return dict(
+            vocoder=self._vocoder, server=lambda: getattr(self, "_server", None),
+            serve_=lambda srv: segments.serve(srv, plan, references, has_voice, sampling, seed, self._prefix_cache),
+            generate_=lambda emit, stopped: segments.generate(plan, references, has_voice, seed, run, self._gen_lock, emit,
+                                                              stopped))
 
     def synthesize_long(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                         top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
@@ -533,45 +493,12 @@ class FishTTS:
         join its batch.  ValueError before any device work: pause / paragraph_pause outside [0, 5] s, silence_db outside
         [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch /
         loudness."""
-        texts, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
-                                              sample_rate, speed, pitch, loudness)
+        from . import segments
+        plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
+                               loudness)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        codes = self._long_codes_served(texts, references, sampling, seed)
-        lock = None
-        if codes is None:
-            got = {}
-            self._long_generate(texts, references, sampling, seed, got.__setitem__, lambda: False)
-            codes = [got[i] for i in range(len(texts))]
-        else:
-            codes, lock = codes
-        if lock is not None:
-            with lock:
-                audio, _ = self._vocoder.decode_join(codes, params=jp, gaps=gaps, fx=fx)
-        else:
-            audio, _ = self._vocoder.decode_join(codes, params=jp, gaps=gaps, fx=fx)
-        if not len(audio):
-            raise RuntimeError("No audio generated")
-        return self._to_wav_bytes(audio, fx.wav_rate)
-
-    def _long_codes_served(self, texts, references, sampling, seed):
-        """([codes of every segment], the server's codec lock) from an open BatchServer; None: no server (or it closed before
-        it took the text) - the caller generates."""
-        return self._codes_served(lambda srv: self._long_serve(srv, texts, references, sampling, seed))
-
-    def _codes_served(self, serve):
-        """_long_codes_served over serve(srv) -> (takes, release), as _long_serve gives them."""
-        from .serve import ServerClosed
-        srv = getattr(self, "_server", None)
-        if srv is None:
-            return None
-        try:
-            takes, release = serve(srv)
-        except ServerClosed:
-            return None
-        try:
-            return [t() for t in takes], srv.codec_lock
-        finally:
-            release()
+        audio, _ = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed))
+        return self._to_wav_bytes(audio, plan.rate)
 
     def synthesize_long_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                                top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
@@ -586,83 +513,21 @@ class FishTTS:
         each is levelled on its own.  No empty chunk is yielded.  The arguments are checked
         here, at the call; generation holds _gen_lock on its own thread and stops within one burst when the generator is
         abandoned."""
-        texts, fx, jp, gaps = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars,
-                                              sample_rate, speed, pitch, loudness)
+        from . import segments
+        plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
+                               loudness)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        return self._long_chunks(texts, references, sampling, seed, fx, jp, gaps)
-
-    def _long_chunks(self, texts, references, sampling, seed, fx, jp, gaps) -> Iterator[bytes]:
-        return self._join_chunks(len(texts), lambda srv: self._long_serve(srv, texts, references, sampling, seed),
-                                 lambda emit, stopped: self._long_generate(texts, references, sampling, seed, emit, stopped),
-                                 fx, jp, gaps)
-
-    def _join_chunks(self, n, serve, generate, fx, jp, gaps, item_fx=None, on_cuts=None) -> Iterator[bytes]:
-        """The PCM chunks of n segments as they become ready in order: serve(srv) -> (takes, release) through an open
-        BatchServer (_long_serve), else generate(emit, stopped) on a thread of its own (_long_generate); every ready run
-        decoded and joined as one group.  `item_fx`: the segments' own chains in place of `fx`; on_cuts(first, cuts): what
-        the join kept of the group that starts at segment `first`, before its chunk goes out."""
-        from .longform import ready_prefixes
-        from .serve import ServerClosed
-        q: "queue.Queue" = queue.Queue()
-        stop = threading.Event()
-        srv, lock, release, threads = getattr(self, "_server", None), None, None, []
-        if srv is not None:
-            try:
-                takes, release = serve(srv)
-                lock = srv.codec_lock
-            except ServerClosed:
-                srv = None                       # closed meanwhile: served here, once the server has let go of _gen_lock
-
-        def feed_served() -> None:
-            try:
-                for i, take in enumerate(takes):
-                    q.put((i, take()))
-            except BaseException as e:  # noqa: BLE001
-                q.put(e)
-
-        def feed_own() -> None:
-            try:
-                generate(lambda i, c: q.put((i, c)), stop.is_set)
-            except _LongStopped:
-                pass
-            except BaseException as e:  # noqa: BLE001
-                q.put(e)
-
-        threads.append(threading.Thread(target=feed_own if srv is None else feed_served, daemon=True))
-        threads[0].start()
-        started = False
-        try:
-            for first, group in ready_prefixes(q, n):
-                kw = dict(params=jp, gaps=gaps[first:first + len(group)], started=started, fx=fx)
-                if item_fx is not None:
-                    kw["item_fx"] = item_fx[first:first + len(group)]
-                if lock is not None:
-                    with lock:
-                        audio, cuts = self._vocoder.decode_join(group, **kw)
-                else:
-                    audio, cuts = self._vocoder.decode_join(group, **kw)
-                if on_cuts is not None:
-                    on_cuts(first, cuts)
-                if len(audio):
-                    started = True
-                    yield (np.clip(audio, -1.0, 1.0) * 32767).astype(np.int16).tobytes()   # synthesize_long's samples
-        finally:
-            stop.set()
-            if release is not None:
-                release(cancel=True)
-            for t in threads:
-                t.join()
-        if not started:
-            raise RuntimeError("No audio generated")
+        return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed))
 
     # ------------------------------------------------------------------ scripts (extension)
     def _script_plan(self, lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
                      sample_rate, speed, pitch, loudness, marks):
-        """Every check of a script call, before any device work: (the plan - script.plan_script - and every segment's
-        references, None where it speaks in the call's voice).  ValueError for a bad value, an unknown voice, or more
-        voices than the prefix cache holds: the cache frees its least recently used entry on insert, and an Utterance of
-        the batch still holds the prefix it was given."""
+        """Every check of a script call, before any device work: its segments.SegmentPlan, from script.plan_script - every
+        segment with its line's references (None where it speaks in the call's voice) and its line's own chain of output
+        stages.  ValueError for a bad value, an unknown voice, or more voices than the prefix cache holds: the cache frees
+        its least recently used entry on insert, and an Utterance of the batch still holds the prefix it was given."""
         from .script import plan_script
+        from .segments import SegmentPlan
         if marks is not None and not isinstance(marks, list):
             raise ValueError(f"marks must be None or a list, got {type(marks).__name__}")
         plan = plan_script(lines, voices, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
@@ -685,81 +550,8 @@ class FishTTS:
                                  "its own to stay (split the script, or build the instance with cache_reference_kv=False)")
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
-        return plan, [None if v is None else list(voices[v]) for v in plan.voices]
-
-    def _script_generate(self, texts, seg_refs, references, sampling, seed, emit, stopped) -> None:
-        """_long_generate for a script: segment i speaks in seg_refs[i], or (None) in the call's voice; segment i draws with
-        seed + i, and all run as one lock-step batch with refill.  Without any reference voice synthesize_long's rule holds
-        for the segments in the call's voice alone: the first of them runs first, on its own, and is the voice of the
-        others through a prefix that this call builds and frees."""
-        from .batch import run_batch, run_batch_streams
-
-        def guard(i, block):
-            if stopped():
-                raise _LongStopped()
-
-        def run(idx, refs, made=None):
-            engines, utts = self._batch_utterances([texts[i] for i in idx], refs, *sampling, 0, [seed + i for i in idx],
-                                                   made=made, text_references=[seg_refs[i] for i in idx])
-            done = lambda j: emit(idx[j], utts[j].codes())   # noqa: E731
-            if len(engines) > 1:
-                run_batch_streams(engines, utts, on_frames=guard, on_done=done)
-            else:
-                run_batch(self._engine, utts, on_frames=guard, on_done=done)
-            return utts
-
-        made = None
-        own = [i for i, r in enumerate(seg_refs) if r is None]
-        with self._gen_lock:
-            try:
-                rest = list(range(len(texts)))
-                if len(own) > 1 and not self._get_prompt_data(references)[1]:
-                    codes0 = run(own[:1], references)[0].codes()
-                    rest.remove(own[0])
-                    if codes0.shape[1]:
-                        references, made = [VoiceProfile(codes=codes0, text=texts[own[0]])], {}
-                if rest:
-                    run(rest, references, made)
-            finally:
-                for pf in (made or {}).values():
-                    pf.free()
-
-    def _script_serve(self, srv, texts, seg_refs, references, sampling, seed):
-        """_long_serve for a script: (takes in segment order, release).  The segments with a voice of their own are queued
-        first; then, without any reference voice, the first segment in the call's voice is awaited and made the voice of
-        the others."""
-        from .generation import PrefixCache
-        from .serve import ServerClosed
-        own, reqs, taken = None, {}, {}
-        mine = [i for i, r in enumerate(seg_refs) if r is None]
-        try:
-            for k, r in enumerate(seg_refs):
-                if r is not None:
-                    reqs[k] = srv.submit_codes(texts[k], r, *sampling, seed + k)
-            if len(mine) > 1 and not self._get_prompt_data(references)[1]:
-                k = mine[0]
-                taken[k] = srv.take_codes(srv.submit_codes(texts[k], references, *sampling, seed + k))
-                if taken[k].shape[1]:
-                    references = [VoiceProfile(codes=taken[k], text=texts[k])]
-                    if self._prefix_cache is not None:
-                        own = PrefixCache(capacity=1, min_positions=self._prefix_cache.min_positions)
-            for k in mine:
-                if k not in taken:
-                    reqs[k] = srv.submit_codes(texts[k], references, *sampling, seed + k, voice_cache=own)
-        except ServerClosed:
-            for r in reqs.values():
-                srv.cancel(r)
-            if own is not None:
-                srv.retire_cache(own)       # the closing server still finishes what it took, then frees the prefix
-            raise
-
-        def release(cancel: bool = False):
-            if cancel:
-                for r in reqs.values():
-                    srv.cancel(r)                # (nothing happens to a request that has ended)
-            if own is not None:
-                srv.retire_cache(own)
-        return [(lambda c=taken[k]: c) if k in taken else (lambda r=reqs[k]: srv.take_codes(r)) for k in range(len(texts))], release
+        return SegmentPlan(plan.texts, [None if v is None else list(voices[v]) for v in plan.voices], plan.gaps,
+                           tuple(plan.jp), plan.rate, plan.fx, plan.line_of, plan.n_lines)
 
     def synthesize_script(self, lines, voices=None, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                           top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
@@ -781,26 +573,12 @@ class FishTTS:
         is synthesize_long of its text, byte for byte.  While a BatchServer is open the segments join its batch.
         ValueError before any device work: no line, an unknown voice, a bad value in a line or in the call, a bad
         line_pause, more distinct voices than the reference cache holds (8; not with cache_reference_kv=False)."""
+        from . import segments
         from .script import line_marks
-        plan, seg_refs = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db,
-                                           max_chars, min_chars, sample_rate, speed, pitch, loudness, marks)
+        plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
+                                 min_chars, sample_rate, speed, pitch, loudness, marks)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        codes = self._codes_served(lambda srv: self._script_serve(srv, plan.texts, seg_refs, references, sampling, seed))
-        lock = None
-        if codes is None:
-            got = {}
-            self._script_generate(plan.texts, seg_refs, references, sampling, seed, got.__setitem__, lambda: False)
-            codes = [got[i] for i in range(len(plan.texts))]
-        else:
-            codes, lock = codes
-        kw = dict(params=tuple(plan.jp), gaps=plan.gaps, item_fx=plan.fx)
-        if lock is not None:
-            with lock:
-                audio, cuts = self._vocoder.decode_join(codes, **kw)
-        else:
-            audio, cuts = self._vocoder.decode_join(codes, **kw)
-        if not len(audio):
-            raise RuntimeError("No audio generated")
+        audio, cuts = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed))
         if marks is not None:
             found = [None] * plan.n_lines
             line_marks(plan.line_of, plan.gaps, cuts, found)
@@ -819,19 +597,15 @@ class FishTTS:
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
         byte for byte; no empty chunk is yielded.  `marks` fills as groups go out: a line's entry is added once its last
         segment went out, and in the end the list is synthesize_script's.  The arguments are checked here, at the call."""
-        plan, seg_refs = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db,
-                                           max_chars, min_chars, sample_rate, speed, pitch, loudness, marks)
-        sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        return self._script_chunks(plan, seg_refs, references, sampling, seed, marks)
-
-    def _script_chunks(self, plan, seg_refs, references, sampling, seed, marks) -> Iterator[bytes]:
+        from . import segments
         from .script import line_marks
+        plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
+                                 min_chars, sample_rate, speed, pitch, loudness, marks)
+        sampling = (temperature, top_p, repetition_penalty, max_tokens)
         found = [None] * plan.n_lines
         state = {"at": 0, "started": False, "told": 0}
 
         def on_cuts(first, cuts) -> None:
-            if marks is None:
-                return
             end = first + len(cuts)
             state["at"], state["started"] = line_marks(plan.line_of[first:end], plan.gaps[first:end], cuts, found,
                                                        state["at"], state["started"])
@@ -839,10 +613,8 @@ class FishTTS:
             marks.extend(found[state["told"]:done])
             state["told"] = max(state["told"], done)
 
-        yield from self._join_chunks(
-            len(plan.texts), lambda srv: self._script_serve(srv, plan.texts, seg_refs, references, sampling, seed),
-            lambda emit, stopped: self._script_generate(plan.texts, seg_refs, references, sampling, seed, emit, stopped),
-            None, tuple(plan.jp), plan.gaps, item_fx=plan.fx, on_cuts=on_cuts)
+        return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed),
+                                    on_cuts=None if marks is None else on_cuts)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
@@ -1079,16 +851,8 @@ class FishTTS:
     def _serve_prepare(self, text: str, references, temperature: float, top_p: float, repetition_penalty: float,
                        max_tokens: int, seed: int):
         """A BatchServer request on the caller's thread: the prompt as generate_long builds and checks it."""
-        from .batch import Utterance
-        from .prompt import build_prompt_split
-        assert 0 < top_p <= 1, "top_p must be in (0, 1]"
-        assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
-        assert 0 < temperature < 2, "temperature must be in (0, 2)"
-        prompt_text, prompt_tokens = self._get_prompt_data(references)
-        enc, n_prefix = build_prompt_split(self._tokenizer, text, prompt_text, prompt_tokens, self._engine.args.num_codebooks)
-        if enc.shape[1] > self._engine.args.max_seq_len - 2048:
-            raise ValueError(f"Prompt is too long: {enc.shape[1]} > {self._engine.args.max_seq_len - 2048}")
-        return Utterance(enc, max_tokens, temperature, top_p, repetition_penalty, seed), n_prefix
+        return self._utterance(text, self._get_prompt_data(references), (temperature, top_p, repetition_penalty, max_tokens),
+                               seed)
 
     # ------------------------------------------------------------------ codes -> audio (synthesizer.py:586-648)
     def _decode_to_wav(self, codes: np.ndarray, fx=None) -> bytes:
@@ -1128,8 +892,10 @@ class FishTTS:
         return self._precision
 
 
-class _LongStopped(Exception):
-    """The consumer of synthesize_long_stream went away: generation stops at its next block of frames."""
+def _check_sampling(temperature: float, top_p: float, repetition_penalty: float) -> None:
+    assert 0 < top_p <= 1, "top_p must be in (0, 1]"
+    assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
+    assert 0 < temperature < 2, "temperature must be in (0, 2)"
 
 
 def _output_fx(sample_rate, speed, pitch, loudness=None, live_loudness=None):
