@@ -53,6 +53,16 @@ class ft_item_fx(C.Structure):
     _fields_ = [("speed_pct", C.c_int32), ("pitch_cents", C.c_int32), ("loudness", C.c_int32)]
 
 
+class ft_intake_item(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("n_frames", C.c_int64), ("rate", C.c_int32), ("channels", C.c_int32), ("fmt", C.c_int32),
+                ("channel", C.c_int32)]
+
+
+class ft_intake_info(C.Structure):
+    _fields_ = [("n44", C.c_int64), ("a", C.c_int64), ("e", C.c_int64), ("frames", C.c_int32), ("status", C.c_int32),
+                ("clipped", C.c_int64), ("nonfinite", C.c_int64), ("level", ft_level_info)]
+
+
 class ft_sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
                 ("ban_eos", C.c_int32), ("seed", C.c_uint64)]
@@ -130,6 +140,10 @@ SYMBOLS = {
     "ft_test_ride_streams": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "ft_codec_encode": (C.c_int32, [_P, _P, C.c_int64, _P, _P]),
     "ft_codec_enc_frame_len": (C.c_int32, [_P]),
+    "ft_intake_filter": (C.c_int32, [C.c_int32, _P, _P, _P, _P]),
+    "ft_intake_len": (C.c_int64, [C.c_int32, C.c_int64]),
+    "ft_codec_intake": (C.c_int32, [_P, C.c_int32, _P, C.POINTER(ft_join_params), C.c_int32, _P, C.c_int64, _P, _P]),
+    "ft_codec_encode_items": (C.c_int32, [_P, C.c_int32, _P, C.POINTER(ft_join_params), C.c_int32, _P, C.c_int64, _P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),
     "ft_ar_profile_gemv": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_sampling), C.POINTER(C.c_double),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

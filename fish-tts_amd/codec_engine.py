@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -38,6 +38,31 @@ class LevelInfo:
     @classmethod
     def of(cls, i: "L.ft_level_info") -> "LevelInfo":
         return cls(float(i.lufs), float(np.float32(i.peak)), float(np.float32(i.gain)), int(i.blocks), int(i.gated), bool(i.capped))
+
+
+@dataclass(frozen=True)
+class IntakeReport:
+    """What the reference intake did with one clip (ft_intake_info): `n44` its samples at 44.1 kHz, `cut` the samples [a, e)
+    of those that were kept, `frames` the code frames of the kept piece (0 unless status is 0), `status` 0 ok, 1 no loud
+    window (nothing kept), 2 the kept piece is longer than the encoder takes (not encoded), `clipped` / `nonfinite` the
+    channel samples at an extreme code of their format (float: |v| >= 1) and the float samples that were not finite (they
+    count as 0), `level` the level stage's result (the loudness and peak before the gain)."""
+    n44: int
+    cut: Tuple[int, int]
+    frames: int
+    status: int
+    clipped: int
+    nonfinite: int
+    level: LevelInfo
+
+    @property
+    def kept(self) -> int:
+        return self.cut[1] - self.cut[0]
+
+    @classmethod
+    def of(cls, i: "L.ft_intake_info") -> "IntakeReport":
+        return cls(int(i.n44), (int(i.a), int(i.e)), int(i.frames), int(i.status), int(i.clipped), int(i.nonfinite),
+                   LevelInfo.of(i.level))
 
 
 @dataclass(frozen=True)
@@ -601,6 +626,85 @@ class CodecHipEngine:
                                           y.ctypes.data_as(C.c_void_p), cap, C.byref(total), cuts.ctypes.data_as(C.c_void_p)),
                     "ft_test_join")
         return y, total.value, cuts[:B]
+
+    MAX_CLIPS_PER_INTAKE = 64     # ft_codec_intake, ft_codec_encode_items
+    MAX_INTAKE_BYTES = 1 << 30
+
+    def _intake_args(self, what, clips, params, loudness, channel):
+        """The checked arguments of an intake call: (items, keep-alive, join params, level).  clips: (WAV bytes, WavInfo of
+        wavfile.parse_wav) each; the frames are handed to the device as they lie in the bytes."""
+        from .wavfile import FORMATS, WIDTH
+        clips = list(clips)
+        if not 1 <= len(clips) <= self.MAX_CLIPS_PER_INTAKE:
+            raise ValueError(f"{what}: {len(clips)} clips, a call takes 1 to {self.MAX_CLIPS_PER_INTAKE}")
+        if channel is not None and (isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or channel < 0):
+            raise ValueError(f"{what}: channel must be None or a channel index, got {channel!r}")
+        level = OutputFx.of(loudness=loudness).native_level
+        jp = self._join_params(params)
+        if not jp.threshold >= 0 or jp.hop < 1 or jp.keep < 0 or jp.fade < 0:
+            raise ValueError(f"{what}: bad join parameters {tuple(params)!r}")
+        items = (L.ft_intake_item * len(clips))()
+        keep, raw = [], 0
+        for b, (data, info) in enumerate(clips):
+            if info.fmt not in FORMATS:
+                raise ValueError(f"{what}: clip {b}: unknown sample format {info.fmt!r}")
+            if channel is not None and channel >= info.channels:
+                raise ValueError(f"{what}: clip {b}: channel {channel} of a file with {info.channels} channels")
+            if self.lib.ft_intake_len(int(info.rate), 0) < 0:
+                raise ValueError(f"{what}: clip {b}: unsupported input sample rate {info.rate}: integers in [8000, 192000] whose "
+                                 "ratio to 44100 reduces to L / M with L <= 640 and a filter window within the kernel's stage")
+            buf = np.frombuffer(data, dtype=np.uint8)
+            size = info.n_frames * info.channels * WIDTH[info.fmt]
+            if info.n_frames < 1 or info.data_offset < 0 or info.data_offset + size > len(buf):
+                raise ValueError(f"{what}: clip {b}: its frames lie outside its bytes")
+            raw += -(-size // 16) * 16
+            keep.append(buf)
+            items[b] = L.ft_intake_item(buf.ctypes.data + info.data_offset, info.n_frames, info.rate, info.channels,
+                                        FORMATS.index(info.fmt), -1 if channel is None else int(channel))
+        if raw > self.MAX_INTAKE_BYTES:
+            raise ValueError(f"{what}: {raw} raw bytes, a call takes {self.MAX_INTAKE_BYTES}")
+        return items, keep, jp, level
+
+    def intake(self, clips, params=(0.0, 1, 0, 0), loudness: Optional[float] = None, channel: Optional[int] = None):
+        """The reference intake without the encoder (ft_codec_intake): clips - (WAV bytes, WavInfo) each, at most 64 and
+        2^30 raw bytes - decoded, mixed down (`channel`: that channel alone), resampled to 44.1 kHz, levelled toward
+        `loudness` (LUFS, as decode's; None: measured only) and trimmed and faded by the join stage with `params`
+        ((threshold, hop, keep, fade); (0, 1, 0, 0): nothing), all on the device.  Returns (pieces, reports): the float32
+        samples the encoder would be given, per clip, and one IntakeReport each."""
+        items, keep, jp, level = self._intake_args("intake", clips, params, loudness, channel)
+        B = len(items)
+        cap = sum(int(self.lib.ft_intake_len(it.rate, it.n_frames)) for it in items)
+        audio = np.empty(max(cap, 1), dtype=np.float32)
+        lens = np.zeros(B, dtype=np.int64)
+        infos = (L.ft_intake_info * B)()
+        self._check(self.lib.ft_codec_intake(self._h, B, items, C.byref(jp), level, audio.ctypes.data_as(C.c_void_p), cap,
+                                             lens.ctypes.data_as(C.c_void_p), infos), "ft_codec_intake")
+        del keep
+        ends = np.cumsum(lens)
+        return [audio[int(e - n):int(e)] for e, n in zip(ends, lens)], [IntakeReport.of(i) for i in infos]
+
+    def encode_items(self, clips, params=(0.0, 1, 0, 0), loudness: Optional[float] = None, channel: Optional[int] = None):
+        """intake() with the encoder behind it, the prepared pieces never leaving the device (ft_codec_encode_items).
+        Returns (codes, reports): per clip the (n_codebooks + 1, frames) int64 codes - what encode() gives for the piece
+        intake() returns, bit for bit - or None where the report's status is not 0."""
+        if not self.with_encoder:
+            raise RuntimeError("codec encoder not built (CodecHipEngine(..., with_encoder=True))")
+        items, keep, jp, level = self._intake_args("encode_items", clips, params, loudness, channel)
+        B = len(items)
+        cap = sum(-(-int(self.lib.ft_intake_len(it.rate, it.n_frames)) // self.enc_frame_len) for it in items)
+        codes = np.zeros(self.R * max(cap, 1), dtype=np.int32)
+        infos = (L.ft_intake_info * B)()
+        self._check(self.lib.ft_codec_encode_items(self._h, B, items, C.byref(jp), level, codes.ctypes.data_as(C.c_void_p), cap,
+                                                   infos), "ft_codec_encode_items")
+        del keep
+        out, at = [], 0
+        for i in infos:
+            if i.status != 0:
+                out.append(None)
+                continue
+            out.append(codes[at:at + self.R * i.frames].reshape(self.R, i.frames).astype(np.int64))
+            at += self.R * i.frames
+        return out, [IntakeReport.of(i) for i in infos]
 
     MAX_ITEMS_PER_JOIN = 64       # ft_codec_decode_join
 

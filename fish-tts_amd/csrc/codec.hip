@@ -98,6 +98,16 @@ struct CodecState {
     // level stage (ft_codec_loudness, ft_codec_decode_level, ft_codec_decode_join_level): the item table, one hop sum and
     // one hop peak per 100 ms of a call's items, the host copies of the table on its way there and back, and the waveform
     // of ft_codec_loudness; allocated on the first levelled call (the buffers grow when a later call needs more)
+    // reference intake (ft_codec_intake, ft_codec_encode_items): one [L][K] table per input rate, uploaded on its first use; the
+    // raw bytes of a call's clips (every clip on a 16-byte boundary), the segment table with the counters behind it, and the
+    // codes of a call's clips gathered for one copy; allocated on the first intake call (the buffers grow on need)
+    std::map<int, RsTab> in_tabs;
+    unsigned char* in_raw = nullptr;
+    size_t in_raw_cap = 0;
+    IntakeSeg* in_seg = nullptr;
+    unsigned long long* in_count = nullptr;
+    int* in_codes = nullptr;
+    size_t in_codes_cap = 0;
     LevelTab* lv_tab = nullptr;
     double* lv_hops = nullptr;
     float *lv_peaks = nullptr, *lv_x = nullptr;
@@ -1853,9 +1863,10 @@ static ft_status join_alloc(ft_ctx* ctx, size_t in, size_t out) {
 
 // The three launches over items that lie at join_in + off[b] (written earlier on the codec's stream), then the table's
 // head - total and the cuts - and `*total` samples to the host.  `fill`: the test hook's form - the output buffer pre-filled with the sentinel and all
-// `need` samples of it copied back.
+// `need` samples of it copied back.  `fetch` false: the call stops after the one read-back of total and the cuts, the pieces
+// stay in join_out for a stage behind the join (the intake's encoder).
 static ft_status join_run(ft_ctx* ctx, int B, const int64_t* n, const int64_t* off, const ft_join_params* jp, const int64_t* gaps,
-                          int started, float* audio, int64_t* total, int64_t* cuts, int64_t need, bool fill) {
+                          int started, float* audio, int64_t* total, int64_t* cuts, int64_t need, bool fill, bool fetch = true) {
     CodecState* s = ctx->codec;
     hipStream_t st = s->stream;
     std::vector<char> raw(sizeof(JoinTab));
@@ -1886,7 +1897,7 @@ static ft_status join_run(ft_ctx* ctx, int B, const int64_t* n, const int64_t* o
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("join launch: ") + hipGetErrorString(e));
     if (h->total < 0 || h->total > need) return ft_fail(ctx, FT_ERR_STATE, "join: layout out of range");
     const int64_t ncopy = fill ? need : (int64_t)h->total;
-    if (ncopy > 0) {       // its length is known only now: the call's second and last wait
+    if (ncopy > 0 && fetch) {       // its length is known only now: the call's second and last wait
         FT_HIP(ctx, hipMemcpyAsync(audio, s->join_out, (size_t)ncopy * sizeof(float), hipMemcpyDeviceToHost, st));
         FT_HIP(ctx, hipStreamSynchronize(st));
     }
@@ -2383,25 +2394,21 @@ extern "C" ft_status ft_codec_rvq_encode(ft_ctx* ctx, const float* z, int32_t T,
     return FT_OK;
 }
 
-extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_samples, int32_t* codes, int32_t* out_frames) {
-    if (!ctx) return FT_ERR_ARG;
-    FT_TRY(codec_ready(ctx, false));
+// The encoder over n_samples samples at `audio` (host or device: `src_kind`), enqueued on the codec's stream: the zero fill to
+// whole frames, the copy into enc_audio, the chain, the quantiser search, and the copy of the (n_codebooks+1) x T' codes to
+// `codes` (host or device: `dst_kind`).  The caller holds s->mu, has checked 1 <= n_samples <= max_enc_frames frames, and
+// synchronizes.
+static ft_status encode_enqueue(ft_ctx* ctx, const float* audio, hipMemcpyKind src_kind, int64_t n_samples, int* codes,
+                                hipMemcpyKind dst_kind) {
     CodecState* s = ctx->codec;
-    if (!s->has_enc) return ft_fail(ctx, FT_ERR_STATE, "codec encoder not configured (encoder_dim = 0)");
-    FT_TRY(codec_ready(ctx));
-    if (!audio || !codes || !out_frames || n_samples < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_encode: bad argument");
     const ft_codec_config& c = ctx->cc;
     const long fl = s->enc_frame_len;
-    const long Tf = (n_samples + fl - 1) / fl;            // code frames (vocoder.py:891-892, 903)
-    if (Tf > c.max_enc_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_encode: audio longer than max_enc_frames");
-    const long T0 = Tf * fl;                              // padded samples
-    std::lock_guard<std::mutex> lock(s->mu);
-    FT_HIP(ctx, hipSetDevice(ctx->device));
+    const long Tf = (n_samples + fl - 1) / fl;
+    const long T0 = Tf * fl;
     hipStream_t st = s->stream;
     const int D = c.latent_dim, H = c.tf_n_head, hd = c.tf_head_dim, R = c.n_codebooks + 1;
-    TraceScope traced(s, true);
     FT_HIP(ctx, hipMemsetAsync(s->enc_audio, 0, (size_t)T0 * sizeof(float), st));
-    FT_HIP(ctx, hipMemcpyAsync(s->enc_audio, audio, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipMemcpyAsync(s->enc_audio, audio, (size_t)n_samples * sizeof(float), src_kind, st));
     // Encoder (vocoder.py:539-575).  r = raw residual stream, a = Snake'd operand of the next conv, hs = inner buffer
     bf16_t *r = s->ebuf[0], *a = s->ebuf[1], *hs = s->ebuf[2], *o = s->ebuf[3];
     long T = T0;
@@ -2457,17 +2464,206 @@ extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_
     run_transformer(ctx, Layout::plain((int)T, s->e_qkv), s->pre, s->pre_norm, s->enc_x, D, H, hd, c.tf_ffn, c.tf_window, s->rope,
                     s->e_xn, s->e_y, s->e_g, nullptr, s->enc_zq, "pre.");
     FT_TRY(rvq_search(ctx, st, s->enc_zq, (int)T, s->enc_codes));
-    FT_HIP(ctx, hipMemcpyAsync(codes, s->enc_codes, (size_t)R * T * sizeof(int), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipMemcpyAsync(codes, s->enc_codes, (size_t)R * T * sizeof(int), dst_kind, st));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_samples, int32_t* codes, int32_t* out_frames) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx, false));
+    CodecState* s = ctx->codec;
+    if (!s->has_enc) return ft_fail(ctx, FT_ERR_STATE, "codec encoder not configured (encoder_dim = 0)");
+    FT_TRY(codec_ready(ctx));
+    if (!audio || !codes || !out_frames || n_samples < 1) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_encode: bad argument");
+    const ft_codec_config& c = ctx->cc;
+    const long fl = s->enc_frame_len;
+    const long Tf = (n_samples + fl - 1) / fl;            // code frames (vocoder.py:891-892, 903)
+    if (Tf > c.max_enc_frames) return ft_fail(ctx, FT_ERR_TOO_LONG, "ft_codec_encode: audio longer than max_enc_frames");
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    TraceScope traced(s, true);
+    hipStream_t st = s->stream;
+    FT_TRY(encode_enqueue(ctx, audio, hipMemcpyHostToDevice, n_samples, codes, hipMemcpyDeviceToHost));
     FT_HIP(ctx, hipStreamSynchronize(st));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("codec encode launch: ") + hipGetErrorString(e));
-    *out_frames = (int32_t)T;
+    *out_frames = (int32_t)Tf;
     return FT_OK;
 }
 
 extern "C" int32_t ft_codec_enc_frame_len(const ft_ctx* ctx) { return ctx && ctx->codec ? ctx->codec->enc_frame_len : 0; }
 
 extern "C" int32_t ft_codec_frame_len(const ft_ctx* ctx) { return ctx && ctx->codec ? ctx->codec->frame_len : 0; }
+
+// ---- reference intake (fishtts_hip.h: ft_intake_filter .. ft_codec_encode_items; IntakeSeg and intake_kernel in
+// codec_kernels.h, the filter design in fx_chain.h)
+static_assert(sizeof(ft_intake_info) == 80 && offsetof(ft_intake_info, level) == 48, "ft_intake_info layout");
+constexpr int64_t IN_MAX_RAW = (int64_t)1 << 30;
+
+extern "C" ft_status ft_intake_filter(int32_t rate_in, int32_t* L, int32_t* M, int32_t* K, float* table) {
+    int l = 1, m = 1, k = 0;
+    std::vector<float> w;
+    if (chain::rs_design_in(rate_in, &l, &m, &k, table ? &w : nullptr)) return FT_ERR_ARG;
+    if (L) *L = l;
+    if (M) *M = m;
+    if (K) *K = k;
+    if (table && !w.empty()) memcpy(table, w.data(), w.size() * sizeof(float));
+    return FT_OK;
+}
+
+extern "C" int64_t ft_intake_len(int32_t rate_in, int64_t n) {
+    int l = 1, m = 1, k = 0;
+    if (n < 0 || chain::rs_design_in(rate_in, &l, &m, &k, nullptr)) return -1;
+    return (n * l + m - 1) / m;
+}
+
+// The device table of input rate `rate` (uploaded on its first use); the caller holds s->mu.
+static ft_status in_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) {
+    CodecState* s = ctx->codec;
+    auto it = s->in_tabs.find(rate);
+    if (it == s->in_tabs.end()) {
+        CodecState::RsTab t;
+        std::vector<float> w;
+        if (const char* e = chain::rs_design_in(rate, &t.L, &t.M, &t.K, &w)) return ft_fail(ctx, FT_ERR_ARG, e);
+        if (t.K > 0) {
+            FT_TRY(cmalloc(ctx, &t.w, w.size()));
+            FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        it = s->in_tabs.emplace(rate, t).first;
+    }
+    *out = &it->second;
+    return FT_OK;
+}
+
+// Both entry points: every check, then raw bytes -> intake -> level -> join on the codec's stream; `enc`: the encoder over
+// the kept pieces and their codes to `codes`, else the pieces themselves to `audio`.
+static ft_status intake_run(ft_ctx* ctx, const std::string& fn, int32_t B, const ft_intake_item* items, const ft_join_params* jp,
+                            int32_t loudness, bool enc, float* audio, int32_t* codes, int64_t capacity, int64_t* lens, ft_intake_info* infos) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx, false));
+    CodecState* s = ctx->codec;
+    if (enc && !s->has_enc) return ft_fail(ctx, FT_ERR_STATE, fn + ": codec encoder not configured (encoder_dim = 0)");
+    FT_TRY(codec_ready(ctx));
+    if (!items || !jp || !infos || (enc ? !codes : (!audio || !lens)) || B < 1 || B > JOIN_MAX_ITEMS)
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument (null pointer, or B outside [1, 64])");
+    if (!chain::lv_ok(loudness))
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": loudness outside [-5000, -500] hundredths of a LUFS (" + std::to_string(loudness) + ")");
+    const int64_t fl = s->has_enc ? s->enc_frame_len : 0;
+    const int64_t most = (2 * (int64_t)ctx->cc.max_frames * s->frame_len * RS_MAX_RATE + RS_FI - 1) / RS_FI;   // ft_codec_loudness
+    int64_t n44[JOIN_MAX_ITEMS], off[JOIN_MAX_ITEMS], raw_off[JOIN_MAX_ITEMS], gaps[JOIN_MAX_ITEMS], raw = 0, need = 0, room = 0;
+    int Ls[JOIN_MAX_ITEMS], Ms[JOIN_MAX_ITEMS], Ks[JOIN_MAX_ITEMS];
+    size_t hops = 0;
+    for (int b = 0; b < B; ++b) {
+        const ft_intake_item& it = items[b];
+        const std::string who = fn + ": item " + std::to_string(b);
+        if (!it.data || it.n_frames < 1) return ft_fail(ctx, FT_ERR_ARG, who + ": no frames");
+        if (it.fmt < IN_U8 || it.fmt > IN_F32) return ft_fail(ctx, FT_ERR_ARG, who + ": fmt outside [0, 4]");
+        if (it.channels < 1 || it.channels > 8) return ft_fail(ctx, FT_ERR_ARG, who + ": channels outside [1, 8]");
+        if (it.channel < -1 || it.channel >= it.channels) return ft_fail(ctx, FT_ERR_ARG, who + ": channel outside [-1, channels)");
+        if (const char* e = chain::rs_design_in(it.rate, &Ls[b], &Ms[b], &Ks[b], nullptr))
+            return ft_fail(ctx, FT_ERR_ARG, who + ": " + e + " (" + std::to_string(it.rate) + ")");
+        if (it.n_frames > IN_MAX_RAW) return ft_fail(ctx, FT_ERR_TOO_LONG, who + ": more than 2^30 raw bytes in one call");
+        const int64_t bytes = it.n_frames * it.channels * IN_WIDTH[it.fmt];
+        raw_off[b] = raw;
+        raw += (bytes + 15) & ~(int64_t)15;
+        if (raw > IN_MAX_RAW) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": more than 2^30 raw bytes in one call");
+        n44[b] = (it.n_frames * Ls[b] + Ms[b] - 1) / Ms[b];
+        if (n44[b] > most) return ft_fail(ctx, FT_ERR_TOO_LONG, who + ": longer at 44100 Hz than the longest item the level stage takes");
+        hops += level_hops(n44[b], RS_FI);
+        room += enc ? (n44[b] + fl - 1) / fl : n44[b];
+        gaps[b] = 0;
+    }
+    if (const char* why = join_check(B, n44, jp, gaps, 0, INT64_MAX, &need)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
+    if (capacity < room) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity too small");
+    const int64_t in_floats = join_offsets(B, n44, off);
+    const int R = ctx->cc.n_codebooks + 1;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = s->stream;
+    std::vector<IntakeSeg> segs((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const CodecState::RsTab* t = nullptr;
+        FT_TRY(in_table(ctx, items[b].rate, &t));
+        IntakeSeg& g = segs[b];
+        memset(&g, 0, sizeof g);
+        g.w = t->K > 0 ? t->w : nullptr;
+        g.L = t->L; g.M = t->M; g.K = t->K;
+    }
+    if (!s->in_seg) {
+        FT_TRY(cmalloc(ctx, &s->in_seg, (size_t)JOIN_MAX_ITEMS));
+        FT_TRY(cmalloc(ctx, &s->in_count, (size_t)2 * JOIN_MAX_ITEMS));
+    }
+    FT_TRY(cgrow(ctx, &s->in_raw, &s->in_raw_cap, (size_t)raw));
+    if (enc) FT_TRY(cgrow(ctx, &s->in_codes, &s->in_codes_cap, (size_t)room * R));
+    FT_TRY(join_alloc(ctx, (size_t)in_floats, (size_t)need));
+    FT_TRY(level_alloc(ctx, hops));
+    long long mx = 0;
+    float* x[JOIN_MAX_ITEMS];
+    for (int b = 0; b < B; ++b) {
+        const ft_intake_item& it = items[b];
+        IntakeSeg& g = segs[b];
+        g.raw = s->in_raw + raw_off[b];
+        g.y = x[b] = s->join_in + off[b];
+        g.count = s->in_count + 2 * b;
+        g.n_frames = it.n_frames;
+        g.n_out = n44[b];
+        g.fmt = it.fmt; g.channels = it.channels; g.channel = it.channel;
+        mx = std::max(mx, (long long)n44[b]);
+        FT_HIP(ctx, hipMemcpyAsync(s->in_raw + raw_off[b], it.data, (size_t)(it.n_frames * it.channels * IN_WIDTH[it.fmt]),
+                                   hipMemcpyHostToDevice, st));
+    }
+    FT_HIP(ctx, hipMemsetAsync(s->in_count, 0, (size_t)2 * B * sizeof(unsigned long long), st));
+    FT_HIP(ctx, hipMemcpyAsync(s->in_seg, segs.data(), segs.size() * sizeof(IntakeSeg), hipMemcpyHostToDevice, st));
+    const int gx = (int)std::max(1LL, std::min(2048LL, (mx + RS_THREADS - 1) / RS_THREADS));
+    intake_kernel<<<dim3(gx, 1, (unsigned)B), RS_THREADS, 0, st>>>(s->in_seg);
+    unsigned long long count[2 * JOIN_MAX_ITEMS];
+    FT_HIP(ctx, hipMemcpyAsync(count, s->in_count, (size_t)2 * B * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    FT_TRY(level_enqueue(ctx, B, x, n44, RS_FI, loudness, loudness != 0));
+    int64_t total = 0, cuts[2 * JOIN_MAX_ITEMS];
+    FT_TRY(join_run(ctx, B, n44, off, jp, gaps, 0, audio, &total, cuts, need, false, !enc));   // waits for the cuts
+    for (int b = 0; b < B; ++b) {
+        ft_intake_info& o = infos[b];
+        memset(&o, 0, sizeof o);
+        o.n44 = n44[b];
+        o.a = cuts[2 * b];
+        o.e = cuts[2 * b + 1];
+        o.clipped = (int64_t)count[2 * b];
+        o.nonfinite = (int64_t)count[2 * b + 1];
+        const int64_t m = o.e - o.a;
+        o.status = m < 1 ? 1 : (fl > 0 && m > (int64_t)s->max_samples) ? 2 : 0;
+        o.frames = o.status == 0 && fl > 0 ? (int32_t)((m + fl - 1) / fl) : 0;
+        if (lens) lens[b] = m;
+    }
+    ft_level_info lv[JOIN_MAX_ITEMS];
+    level_fetch(s, B, lv);
+    for (int b = 0; b < B; ++b) infos[b].level = lv[b];
+    if (!enc) return FT_OK;
+    // the encoder, clip by clip on the stream; piece b lies at the sum of the pieces before it (no gaps)
+    int64_t at = 0, done = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t m = infos[b].e - infos[b].a;
+        if (infos[b].status == 0) {
+            FT_TRY(encode_enqueue(ctx, s->join_out + at, hipMemcpyDeviceToDevice, m, s->in_codes + done * R, hipMemcpyDeviceToDevice));
+            done += infos[b].frames;
+        }
+        at += m;
+    }
+    if (done > 0) FT_HIP(ctx, hipMemcpyAsync(codes, s->in_codes, (size_t)done * R * sizeof(int), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("intake encode launch: ") + hipGetErrorString(e));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_intake(ft_ctx* ctx, int32_t B, const ft_intake_item* items, const ft_join_params* jp, int32_t loudness,
+                                     float* audio, int64_t capacity, int64_t* lens, ft_intake_info* infos) {
+    return intake_run(ctx, "ft_codec_intake", B, items, jp, loudness, false, audio, nullptr, capacity, lens, infos);
+}
+
+extern "C" ft_status ft_codec_encode_items(ft_ctx* ctx, int32_t B, const ft_intake_item* items, const ft_join_params* jp,
+                                           int32_t loudness, int32_t* codes, int64_t capacity_frames, ft_intake_info* infos) {
+    return intake_run(ctx, "ft_codec_encode_items", B, items, jp, loudness, true, nullptr, codes, capacity_frames, nullptr, infos);
+}
 
 // ---- launch trace hooks (fishtts_hip_test.h)
 extern "C" ft_status ft_test_codec_trace_arm(ft_ctx* ctx, int32_t first, int32_t count) {

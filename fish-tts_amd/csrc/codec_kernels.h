@@ -8,6 +8,7 @@
 //   * Linear / 1x1 conv: one tap
 // Snake (x + sin^2(ax)/a) is applied once per element in the producer's epilogue, never per tap.
 #pragma once
+#include <float.h>
 #include <limits.h>
 
 #include <algorithm>
@@ -1549,6 +1550,136 @@ static __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const RsSeg
             for (int t = 0; t < s.K; ++t) acc += wp[t] * xp[t];
             s.y[n] = acc;
         }
+    }
+}
+
+// ---- reference intake (ft_codec_intake, ft_codec_encode_items; stated in fishtts_hip.h): the raw frames of a WAV - any of
+// five sample formats, one to eight interleaved channels, any accepted rate - decoded, mixed down to mono and brought to
+// the codec's rate in ONE launch for all clips of a call (the clip sits on blockIdx.z).  The launch has the shape of
+// resample_kernel: a workgroup computes 256 consecutive outputs from an input window staged in LDS, the polyphase sum in
+// float32 over t ascending; the difference is where the window comes from - each staged element is one frame, decoded and
+// mixed from the clip's bytes, so no mono copy at the input rate ever exists.  (255 M + L - 1) / L + K + 1 <= RS_LDS is
+// checked with the table (rs_design_in).
+// Loads: a clip starts on a 16-byte boundary of the raw buffer, so every 2- and 4-byte sample is naturally aligned and is
+// read with one load of its size; a 24-bit sample has no alignment at all and is read as three bytes.  Lane k of a wave
+// stages frame ia + k: the lanes' addresses are C width bytes apart, so a wave's loads of one channel cover one contiguous
+// run of 64 C width bytes, and the C loads of a lane hit the lines its neighbours just fetched.  A 30 s stereo 48 kHz clip
+// is 5.8 MB, read K / 256 M/L + 1 times over (the windows of adjacent workgroups overlap by K frames) out of L2.
+// The two counters are integer atomics, one pair per workgroup that saw something: every frame is counted by exactly one
+// workgroup - the one whose outputs' centre taps start at it, frames [floor(na M / L), floor((nb + 1) M / L)) for outputs
+// [na, nb], the last workgroup to the end of the clip - and those frames lie inside its window (M / L < 5 <= K / 2).
+enum { IN_U8 = 0, IN_S16 = 1, IN_S24 = 2, IN_S32 = 3, IN_F32 = 4 };
+struct IntakeSeg {
+    const unsigned char* raw;     // n_frames frames of `channels` samples, interleaved, little-endian (device, 16-byte aligned)
+    const float* w;               // [L][K]; null: the codec's own rate, y = m
+    float* y;                     // n_out outputs
+    unsigned long long* count;    // [2]: clipped, nonfinite (zeroed by the host before the launch)
+    long long n_frames, n_out;
+    int L, M, K, fmt, channels, channel;   // channel < 0: the mean of all channels
+};
+constexpr int IN_WIDTH[5] = {1, 2, 3, 4, 4};
+
+// Sample `c` of frame `i` as a real number (exact in float64); `clip`, `bad`: the sample sits at an extreme code (f32:
+// |v| >= 1), is not finite (and counts as 0).
+__device__ inline double intake_sample(const IntakeSeg& s, long long i, int c, int& clip, int& bad) {
+    const long long at = i * s.channels + c;
+    switch (s.fmt) {
+    case IN_U8: {
+        const int v = s.raw[at];
+        clip += v == 0 || v == 255;
+        return (double)(v - 128) / 128.0;
+    }
+    case IN_S16: {
+        const int v = ((const short*)s.raw)[at];
+        clip += v == -32768 || v == 32767;
+        return (double)v / 32768.0;
+    }
+    case IN_S24: {
+        const unsigned char* q = s.raw + 3 * at;
+        const int v = ((int)((unsigned)q[0] << 8 | (unsigned)q[1] << 16 | (unsigned)q[2] << 24)) >> 8;
+        clip += v == -8388608 || v == 8388607;
+        return (double)v / 8388608.0;
+    }
+    case IN_S32: {
+        const int v = ((const int*)s.raw)[at];
+        clip += v == INT_MIN || v == INT_MAX;
+        return (double)v / 2147483648.0;
+    }
+    default: {
+        const float v = ((const float*)s.raw)[at];
+        if (!(fabsf(v) <= FLT_MAX)) {      // inf or NaN
+            bad += 1;
+            return 0.0;
+        }
+        clip += fabsf(v) >= 1.f;
+        return (double)v;
+    }
+    }
+}
+
+// m[i]: the mono sample of frame i, zero outside the clip; `own`: this workgroup counts the frame.
+__device__ inline float intake_mono(const IntakeSeg& s, long long i, bool own, int& clip, int& bad) {
+    if (i < 0 || i >= s.n_frames) return 0.f;
+    int cl = 0, bd = 0;
+    float m;
+    if (s.channel >= 0) {
+        m = (float)intake_sample(s, i, s.channel, cl, bd);
+    } else {
+        double sum = 0.0;
+        for (int c = 0; c < s.channels; ++c) sum += intake_sample(s, i, c, cl, bd);
+        m = (float)(sum / (double)s.channels);
+    }
+    if (own) {
+        clip += cl;
+        bad += bd;
+    }
+    return m;
+}
+
+static __global__ __launch_bounds__(RS_THREADS) void intake_kernel(const IntakeSeg* segs) {
+    __shared__ float xs[RS_LDS];
+    __shared__ int tot[2];
+    const IntakeSeg s = segs[blockIdx.z];
+    int clip = 0, bad = 0;
+    if (threadIdx.x < 2) tot[threadIdx.x] = 0;
+    if (!s.w) {
+        for (long long i = (long long)blockIdx.x * RS_THREADS + threadIdx.x; i < s.n_out; i += (long long)gridDim.x * RS_THREADS)
+            s.y[i] = intake_mono(s, i, true, clip, bad);
+    } else {
+        const int h = s.K / 2;
+        for (long long b0 = (long long)blockIdx.x * RS_THREADS; b0 < s.n_out; b0 += (long long)gridDim.x * RS_THREADS) {
+            const long long na = b0, nb = min(s.n_out, b0 + RS_THREADS) - 1;
+            const long long ia = na * s.M / s.L - h + 1;
+            const int span = (int)(nb * s.M / s.L + h - ia + 1);
+            const long long own_a = na * s.M / s.L, own_b = nb + 1 == s.n_out ? s.n_frames : (nb + 1) * s.M / s.L;
+            __syncthreads();
+            for (int k = threadIdx.x; k < span && k < RS_LDS; k += RS_THREADS)
+                xs[k] = intake_mono(s, ia + k, ia + k >= own_a && ia + k < own_b, clip, bad);
+            __syncthreads();
+            const long long n = b0 + threadIdx.x;
+            if (n < s.n_out) {
+                const long long u = n * s.M, i0 = u / s.L;
+                const float* wp = s.w + (size_t)(u - i0 * s.L) * s.K;
+                const float* xp = xs + (i0 - h + 1 - ia);
+                float acc = 0.f;
+                for (int t = 0; t < s.K; ++t) acc += wp[t] * xp[t];
+                s.y[n] = acc;
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        clip += __shfl_xor(clip, o);
+        bad += __shfl_xor(bad, o);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        if (clip) atomicAdd(&tot[0], clip);
+        if (bad) atomicAdd(&tot[1], bad);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (tot[0]) atomicAdd(&s.count[0], (unsigned long long)tot[0]);
+        if (tot[1]) atomicAdd(&s.count[1], (unsigned long long)tot[1]);
     }
 }
 

@@ -35,22 +35,22 @@ inline double bessel_i0(double x) {
     return sum;
 }
 
-// Validates `rate` (an error message, or null) and gives L, M, K; fills w ([L][K] float32) when non-null.
-inline const char* rs_design(int rate, int* L, int* M, int* K, std::vector<float>* w) {
-    if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return "sample rate outside [8000, 48000]";
-    const int g = std::gcd(rate, RS_FI), l = rate / g, m = RS_FI / g;
+// The design for any pair of rates: from Fi to Fo = Fi L / M, L = Fo / g, M = Fi / g, g = gcd(Fi, Fo); K = 0 when Fi == Fo.
+// An error message (the caller says which rate is meant), or null; fills w ([L][K] float32) when non-null.
+inline const char* rs_design_pair(int fi, int fo, int* L, int* M, int* K, std::vector<float>* w) {
+    const int g = std::gcd(fi, fo), l = fo / g, m = fi / g;
     if (l > RS_MAX_L) return "sample rate: rate / gcd(rate, 44100) exceeds 640";
     *L = l;
     *M = m;
     *K = 0;
-    if (rate == RS_FI) return nullptr;
-    const double A = 75.0, beta = 0.1102 * (A - 8.7), fmin = std::min(rate, RS_FI);
-    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * RS_FI / fmin);
+    if (fi == fo) return nullptr;
+    const double A = 75.0, beta = 0.1102 * (A - 8.7), fmin = std::min(fi, fo);
+    int k = (int)std::ceil((A - 7.95) / (2.285 * 2.0 * M_PI * 0.07) * fi / fmin);
     k += k & 1;
     if ((255L * m + l - 1) / l + k + 1 > RS_LDS) return "sample rate: filter window exceeds the resampler's LDS stage";
     *K = k;
     if (!w) return nullptr;
-    const double fc = 0.465 * fmin / ((double)l * RS_FI), half = 0.5 * k * l, ib = bessel_i0(beta);
+    const double fc = 0.465 * fmin / ((double)l * fi), half = 0.5 * k * l, ib = bessel_i0(beta);
     w->assign((size_t)l * k, 0.f);
     for (int p = 0; p < l; ++p)
         for (int t = 0; t < k; ++t) {
@@ -59,6 +59,22 @@ inline const char* rs_design(int rate, int* L, int* M, int* K, std::vector<float
             (*w)[(size_t)p * k + t] = (float)(2.0 * fc * l * sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / ib);
         }
     return nullptr;
+}
+
+// The output direction, Fi = 44100 and Fo = `rate`: validates `rate` (an error message, or null) and gives L, M, K; fills w
+// ([L][K] float32) when non-null.
+inline const char* rs_design(int rate, int* L, int* M, int* K, std::vector<float>* w) {
+    if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return "sample rate outside [8000, 48000]";
+    return rs_design_pair(RS_FI, rate, L, M, K, w);
+}
+
+// The intake direction (intake_kernel), Fi = `rate_in` and Fo = 44100: a reference clip brought to the codec's rate.  Rates:
+// integers in [8000, 192000] whose reduced L = 44100 / gcd is at most 640 and whose window fits the LDS stage.
+constexpr int RS_MAX_RATE_IN = 192000;
+inline const char* rs_design_in(int rate_in, int* L, int* M, int* K, std::vector<float>* w) {
+    if (rate_in < RS_MIN_RATE || rate_in > RS_MAX_RATE_IN) return "input sample rate outside [8000, 192000]";
+    if (RS_FI / std::gcd(rate_in, RS_FI) > RS_MAX_L) return "input sample rate: 44100 / gcd(rate, 44100) exceeds 640";
+    return rs_design_pair(rate_in, RS_FI, L, M, K, w);
 }
 
 // Outputs available after `nin` input samples: all of them at the end of the input (final), else those whose taps all

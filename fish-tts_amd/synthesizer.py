@@ -195,6 +195,99 @@ class FishTTS:
             codes = self._vocoder.encode(audio)
         return VoiceProfile(codes=codes.astype(np.int64), text=text)
 
+    # ------------------------------------------------------------------ reference intake (extension)
+    def _intake(self, clips, silence_db, loudness, channel, encode: bool):
+        """(results, reports) of engine.encode_items / engine.intake over clips (WAV bytes each), in calls of at most 64
+        clips and 2^30 raw bytes; every argument is checked before any device work."""
+        from .codec_engine import CodecHipEngine, OutputFx
+        from .longform import join_params
+        from .wavfile import WIDTH, parse_wav
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        OutputFx.of(loudness=loudness)
+        params = tuple(join_params(44100, 0, 0, silence_db)[0])
+        if channel is not None and (isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or channel < 0):
+            raise ValueError(f"channel must be None or a channel index, got {channel!r}")
+        parsed = []
+        for i, data in enumerate(clips):
+            try:
+                info = parse_wav(data)
+            except ValueError as e:
+                raise ValueError(f"clip {i}: {e}") from None
+            if channel is not None and channel >= info.channels:
+                raise ValueError(f"clip {i}: channel {channel} of a file with {info.channels} channels")
+            if self._vocoder.lib.ft_intake_len(info.rate, 0) < 0:
+                raise ValueError(f"clip {i}: unsupported input sample rate {info.rate}")
+            parsed.append((data, info))
+        groups, cur, raw = [], [], 0
+        for c in parsed:
+            size = -(-c[1].n_frames * c[1].channels * WIDTH[c[1].fmt] // 16) * 16
+            if cur and (len(cur) == CodecHipEngine.MAX_CLIPS_PER_INTAKE or raw + size > CodecHipEngine.MAX_INTAKE_BYTES):
+                groups.append(cur)
+                cur, raw = [], 0
+            cur.append(c)
+            raw += size
+        if cur:
+            groups.append(cur)
+        call = self._vocoder.encode_items if encode else self._vocoder.intake
+        out, reports = [], []
+        srv = getattr(self, "_server", None)
+        for g in groups:
+            if srv is not None:
+                with srv.codec_lock:              # the server's codec worker shares the codec context
+                    o, r = call(g, params, loudness, channel)
+            else:
+                o, r = call(g, params, loudness, channel)
+            out += o
+            reports += r
+        return out, reports
+
+    def _intake_refusals(self, reports) -> None:
+        a = self._vocoder.args
+        for i, r in enumerate(reports):
+            if r.status == 1:
+                raise ValueError(f"clip {i}: nothing in it is louder than silence_db: there is nothing to encode")
+            if r.status == 2:
+                takes = self._vocoder.max_enc_frames * self._vocoder.enc_frame_len / 44100.0
+                raise ValueError(f"clip {i}: {r.kept / 44100.0:.2f} s are kept, the encoder takes {takes:.2f} s "
+                                 f"(max_reference_seconds = {a.max_reference_seconds:g}); the clip is not cut: its transcript "
+                                 "would no longer match")
+
+    def encode_references(self, clips: List[Tuple[bytes, str]], silence_db: Optional[float] = -45.0,
+                          loudness: Optional[float] = None, channel: Optional[int] = None,
+                          reports: Optional[list] = None) -> List[VoiceProfile]:
+        """Extension: a voice library onboarded in one go - (WAV bytes, transcript) each -> one VoiceProfile each, every
+        clip prepared on the GPU (ft_codec_encode_items): any WAV of 8-, 16-, 24-, 32-bit PCM or 32-bit float, 1 to 8
+        channels (mixed down; `channel`: that channel alone), plain or WAVE_FORMAT_EXTENSIBLE header, at an input rate in
+        [8000, 192000] (resampled by a polyphase FIR, not a whole-clip FFT on the host); leading and trailing silence below
+        `silence_db` dBFS trimmed with 5 ms fades (None: nothing is trimmed or faded); with `loudness` (LUFS in [-50, -5], as
+        synthesize_at's) the clip is levelled to it before the trim, the peak held at -1 dBFS - the model follows its
+        prompt's level.  The clips go in calls of at most 64 clips and 2^30 raw bytes, each call one launch chain.  `reports`:
+        a list that receives one IntakeReport per clip.  ValueError before any device work for a bad WAV, rate or argument;
+        after it, naming the clip, for one with nothing above silence_db and for one whose kept part is longer than
+        max_reference_seconds."""
+        clips = list(clips)
+        codes, reps = self._intake([c[0] for c in clips], silence_db, loudness, channel, True) if clips else ([], [])
+        if reports is not None:
+            reports.extend(reps)
+        self._intake_refusals(reps)
+        return [VoiceProfile(codes=c, text=t) for c, (_, t) in zip(codes, clips)]
+
+    def encode_reference_at(self, audio_bytes: bytes, text: str, silence_db: Optional[float] = -45.0,
+                            loudness: Optional[float] = None, channel: Optional[int] = None,
+                            report: Optional[list] = None) -> VoiceProfile:
+        """Extension: encode_reference for any WAV, prepared on the GPU - encode_references of one clip.  With
+        silence_db=None and loudness=None a 16-bit mono 44.1 kHz file gives encode_reference's codes, bit for bit.
+        `report`: a list that receives the clip's IntakeReport."""
+        return self.encode_references([(audio_bytes, text)], silence_db, loudness, channel, report)[0]
+
+    def prepare_reference(self, audio_bytes: bytes, silence_db: Optional[float] = -45.0, loudness: Optional[float] = None,
+                          channel: Optional[int] = None):
+        """Extension: (float32 audio at 44.1 kHz, IntakeReport) - what encode_reference_at would hand to the encoder, for a
+        caller who wants to hear what was kept (ft_codec_intake).  Nothing is refused after the call: the report tells."""
+        audio, reps = self._intake([audio_bytes], silence_db, loudness, channel, False)
+        return audio[0], reps[0]
+
     def measure_loudness(self, wav_bytes: bytes) -> float:
         """Extension: the integrated loudness (LUFS, ITU-R BS.1770-4) of a 16-bit mono WAV, measured on the GPU at the WAV's
         own rate by the stage that `loudness=` runs (CodecHipEngine.loudness) - the figure to pass as `loudness=` to match

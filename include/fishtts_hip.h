@@ -474,6 +474,75 @@ ft_status ft_codec_stream_begin_live(ft_ctx* ctx, int32_t sample_rate, int32_t s
  * int32 row-major (host, row stride = T' = ceil(n_samples / ft_codec_enc_frame_len)); *out_frames = T'. */
 ft_status ft_codec_encode(ft_ctx* ctx, const float* audio, int64_t n_samples, int32_t* codes, int32_t* out_frames);
 int32_t ft_codec_enc_frame_len(const ft_ctx* ctx);
+/* Reference intake.  A cloned voice is as good as what the encoder is given; these calls take the frames of a WAV as they lie
+ * in the file and prepare them on the device, on the codec's stream: raw bytes -> intake (decode, mix down, resample to
+ * 44100 Hz; one launch for all clips of a call) -> level -> trim and fades (the join stage) -> encoder.  The reference reads
+ * 16-bit mono only, resamples with a whole-clip FFT on the host and keeps silence and level as they come
+ * (synthesizer.py:613-631); ft_codec_encode is that path and is unchanged.  Stated, which fixes every bit of the result:
+ *   Inputs: item b = {data, n_frames >= 1, rate, channels in [1, 8], fmt, channel}: n_frames frames of `channels` interleaved
+ *   little-endian samples (host memory, no alignment asked); fmt 0 u8, 1 s16, 2 s24 (three bytes), 3 s32, 4 f32; channel = -1
+ *   takes the mean of all channels, channel = k in [0, channels) takes channel k alone.
+ *   Samples: channel sample v becomes the real number d = (v - 128) / 128 (u8), v / 32768 (s16), v / 8388608 (s24),
+ *   v / 2147483648 (s32), v itself (f32; a v that is not finite counts as 0).  The mono sample of frame i is
+ *   m[i] = (float)(sum_c d_c / C): the sum in float64 over c ascending (exact), one float64 division, rounded once to float32;
+ *   with channel = k it is (float) d_k.  m is zero outside [0, n_frames).  A 16-bit mono file gives v / 32768 exactly.
+ *   Rate: Fi = rate, Fo = 44100; g = gcd(Fi, 44100), L = 44100 / g, M = Fi / g, Fmin = min(Fi, 44100).  The filter is the
+ *   resampler's (ft_resample_filter) designed for this pair: A = 75 dB, beta = 0.1102 (A - 8.7), K = the even ceiling of
+ *   (A - 7.95) / (2.285 2 pi 0.07) Fi / Fmin, cut-off 0.465 Fmin / (L Fi) cycles per sample at the up-sampled rate L Fi, gain L,
+ *   tap t of phase p the prototype at p + (K/2 - 1 - t) L; pass band to 0.43 Fmin (<= 0.01 dB), stop band from 0.5 Fmin
+ *   (>= 70 dB).  Accepted rates: integers in [8000, 192000] with L <= 640 and (255 M + L - 1) / L + K + 1 <= 2048 (8000, 11025,
+ *   12000, 16000, 22050, 24000, 32000, 48000, 64000, 88200, 96000, 176400, 192000 among them: K from 68 to 292).  At 44100,
+ *   K = 0 and y[n] = m[n].  Else n44 = ceil(n_frames L / M) outputs, y[n] = sum_{t < K} w[p][t] m[i0 - K/2 + 1 + t] with
+ *   u = n M, i0 = u / L, p = u % L, in float32 over t ascending.  An output does not depend on the other clips of the call.
+ *   Counters (exact integers, over the channels that are used): clipped = samples at an extreme code of their format (0 or
+ *   255; -32768 or 32767; ...), for f32 finite samples with |v| >= 1; nonfinite = f32 samples that are not finite (they are
+ *   not counted as clipped).
+ *   Level: the level stage (ft_codec_loudness) over every clip's n44 samples at 44100 Hz.  It always measures - infos[b].level
+ *   holds L and the peak of the clip before the gain - and multiplies by the gain only with a target (`loudness` in
+ *   [-5000, -500]; 0: the clip keeps its level, the reported gain is 1).
+ *   Trim: the join stage (ft_codec_decode_join) over the levelled clips with jp, every gap 0 and started = 0: piece b is
+ *   x_b[a_b .. e_b) with its fades, m_b = e_b - a_b samples; the pieces lie back to back.  With threshold = 0, keep = 0,
+ *   fade = 0 nothing is trimmed or faded and m_b = n44_b.
+ *   Encoder: piece b is encoded as ft_codec_encode encodes the same samples from the host, bit for bit, wherever
+ *   1 <= m_b <= max_enc_frames * ft_codec_enc_frame_len; frames_b = ceil(m_b / ft_codec_enc_frame_len).
+ *   Reported per item (ft_intake_info): n44, (a, e), frames, the two counters, the level, and status: 0 ok; 1 no loud window
+ *   (m_b = 0: nothing kept, nothing encoded); 2 the kept piece is longer than the encoder takes (not encoded: cutting it
+ *   would leave its transcript behind).  frames = 0 unless status = 0.  Items with status 1 or 2 do not fail the call.
+ * Limits: 1 <= B <= 64; n44 <= the level stage's longest item (ft_codec_loudness); raw bytes of a call (every item rounded
+ * up to 16) <= 2^30; sum(n44) <= 2^28.  Every argument is checked before any device work, and a refused call changes
+ * nothing: FT_ERR_ARG (a null pointer; B; n_frames < 1; fmt; channels; channel >= channels or < -1; a refused rate; a loudness
+ * that is neither 0 nor in [-5000, -500]; bad join parameters; capacity too small), FT_ERR_TOO_LONG (n44 or the raw bytes
+ * beyond the limits), FT_ERR_STATE (ft_codec_encode_items on a context without the encoder).
+ * On the device: the raw bytes lie in one buffer, every clip on a 16-byte boundary (a 24-bit clip with an odd number of
+ * frames would leave its successor unaligned otherwise); the clips at 44100 Hz lie in the join stage's input buffer, the
+ * pieces in its output buffer; one [L][K] table per input rate, uploaded on first use and kept (168 KB at most).  The buffers
+ * grow when a later call needs more.  Launches per call: 1 (intake) + 2 or 3 (level) + 3 (join), whatever B; then one
+ * read-back of the cuts, the encoder clip by clip on the stream, all codes gathered on the device and copied once. */
+typedef struct ft_intake_item {
+    const void* data;
+    int64_t n_frames;
+    int32_t rate, channels, fmt, channel;
+} ft_intake_item;
+typedef struct ft_intake_info {
+    int64_t n44, a, e;
+    int32_t frames, status;
+    int64_t clipped, nonfinite;
+    ft_level_info level;
+} ft_intake_info;
+/* Host only (no context, no device): the intake filter of rate_in; L, M, K (K = 0 at 44100) and, if `table` is non-null, the
+ * L x K weights.  Any output pointer may be NULL.  FT_ERR_ARG for a refused rate, the outputs left untouched. */
+ft_status ft_intake_filter(int32_t rate_in, int32_t* L, int32_t* M, int32_t* K, float* table);
+/* ceil(n L / M) - the samples n frames at rate_in give at 44100 Hz; -1 for a refused rate or n < 0. */
+int64_t ft_intake_len(int32_t rate_in, int64_t n);
+/* The prepared pieces themselves - what the encoder would be given - back to back in `audio` (host), lens[b] = m_b samples
+ * each; capacity (samples) must be at least sum(n44).  Needs no encoder: without one frames = 0 and status 2 does not
+ * arise; with one, infos are those of ft_codec_encode_items for the same arguments. */
+ft_status ft_codec_intake(ft_ctx* ctx, int32_t B, const ft_intake_item* items, const ft_join_params* jp, int32_t loudness,
+                          float* audio, int64_t capacity, int64_t* lens, ft_intake_info* infos);
+/* The codes of every item with status 0, back to back in `codes` (host): item b's block is (n_codebooks+1) x frames_b int32
+ * row-major.  capacity_frames must be at least sum_b ceil(n44_b / ft_codec_enc_frame_len), the most the call can give. */
+ft_status ft_codec_encode_items(ft_ctx* ctx, int32_t B, const ft_intake_item* items, const ft_join_params* jp,
+                                int32_t loudness, int32_t* codes, int64_t capacity_frames, ft_intake_info* infos);
 
 ft_status ft_sync(ft_ctx* ctx);
 /* State of the persistent frame engine (csrc/frame_engine.h), the batch-1 form of the decode step

@@ -30,6 +30,7 @@ static char where[160] = "";
 
 constexpr int FRAME = 2048;
 static const int RATES[] = {8000, 16000, 22050, 24000, 44100, 48000};
+static const int RATES_IN[] = {8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 64000, 88200, 96000, 176400, 192000};
 static const int SPEEDS[] = {50, 80, 100, 125, 200};
 static const int CENTS[] = {-1200, -300, 0, 400, 1200};
 static const int FRAMES[] = {1, 2, 5, 17, 40};
@@ -75,6 +76,17 @@ static void tables() {
     }
     int L, M, K;
     EXPECT(rs_design(7999, &L, &M, &K, nullptr) && rs_design(48001, &L, &M, &K, nullptr) && rs_design(44101, &L, &M, &K, nullptr));
+    // the intake direction (rs_design_in: a reference clip's rate to the codec's)
+    for (int rate : RATES_IN) {
+        int l = 0, m = 0, k = -1;
+        std::vector<float> w;
+        EXPECT(rs_design_in(rate, &l, &m, &k, &w) == nullptr);
+        EXPECT(l >= 1 && l <= RS_MAX_L && (long long)l * rate == (long long)m * RS_FI);
+        EXPECT((rate == RS_FI) == (k == 0) && k % 2 == 0 && k <= 292 && w.size() == (size_t)(k ? l * k : 0));
+        EXPECT((255L * m + l - 1) / l + k + 1 <= 1404);
+    }
+    EXPECT(rs_design_in(7999, &L, &M, &K, nullptr) && rs_design_in(192001, &L, &M, &K, nullptr) &&
+           rs_design_in(44099, &L, &M, &K, nullptr) && rs_design_in(47999, &L, &M, &K, nullptr));
     for (int cents : CENTS) {
         long long S = 0;
         std::vector<float> w;
