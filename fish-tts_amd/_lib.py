@@ -63,6 +63,17 @@ class ft_intake_info(C.Structure):
                 ("clipped", C.c_int64), ("nonfinite", C.c_int64), ("level", ft_level_info)]
 
 
+class ft_mix_params(C.Structure):
+    _fields_ = [("bed_loudness", C.c_int32), ("channel", C.c_int32), ("depth", C.c_int32), ("threshold", C.c_float),
+                ("attack", C.c_int32), ("release", C.c_int32), ("lead", C.c_int64), ("tail", C.c_int64), ("fade_in", C.c_int64),
+                ("fade_out", C.c_int64), ("offset", C.c_int64), ("loop", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ft_mix_info(C.Structure):
+    _fields_ = [("N", C.c_int64), ("nb", C.c_int64), ("Nh", C.c_int64), ("active", C.c_int64), ("dmax", C.c_int32),
+                ("capped", C.c_int32), ("pk", C.c_float), ("sg", C.c_float), ("bed", ft_intake_info)]
+
+
 class ft_sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
                 ("ban_eos", C.c_int32), ("seed", C.c_uint64)]
@@ -144,6 +155,10 @@ SYMBOLS = {
     "ft_intake_len": (C.c_int64, [C.c_int32, C.c_int64]),
     "ft_codec_intake": (C.c_int32, [_P, C.c_int32, _P, C.POINTER(ft_join_params), C.c_int32, _P, C.c_int64, _P, _P]),
     "ft_codec_encode_items": (C.c_int32, [_P, C.c_int32, _P, C.POINTER(ft_join_params), C.c_int32, _P, C.c_int64, _P]),
+    "ft_codec_mix": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), _P, C.c_int64,
+                                 _P, _P, C.POINTER(ft_mix_info)]),
+    "ft_mix_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "ft_mix_gains": (C.c_int32, [_P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),
     "ft_ar_profile_gemv": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_sampling), C.POINTER(C.c_double),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -66,6 +66,28 @@ class IntakeReport:
 
 
 @dataclass(frozen=True)
+class MixReport:
+    """What the mix stage did (ft_mix_info): `n` the samples of the mixed piece (lead + programme + tail), `bed_len` the bed's
+    samples at the output rate, `hops` the 20 ms hops of the timeline and `active` those in which the programme reached the
+    threshold, `duck_max` the deepest duck (dB), `peak` the sample peak before the ceiling, `gain` the one gain the ceiling
+    applied (1 when `capped` is False), `bed` the intake's report of the bed."""
+    n: int
+    bed_len: int
+    hops: int
+    active: int
+    duck_max: float
+    peak: float
+    gain: float
+    capped: bool
+    bed: IntakeReport
+
+    @classmethod
+    def of(cls, i: "L.ft_mix_info") -> "MixReport":
+        return cls(int(i.N), int(i.nb), int(i.Nh), int(i.active), i.dmax / 100.0, float(np.float32(i.pk)), float(np.float32(i.sg)),
+                   bool(i.capped), IntakeReport.of(i.bed))
+
+
+@dataclass(frozen=True)
 class OutputFx:
     """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent), `cents` (pitch), `level` (loudness
     target, hundredths of a LUFS) and `live` (a stream's live loudness target, the same unit), each None where the stage is
@@ -705,6 +727,38 @@ class CodecHipEngine:
             out.append(codes[at:at + self.R * i.frames].reshape(self.R, i.frames).astype(np.int64))
             at += self.R * i.frames
         return out, [IntakeReport.of(i) for i in infos]
+
+    def mix(self, x: np.ndarray, bed, sample_rate: Optional[int] = None, params=None, nodes: bool = False):
+        """The mix stage on a host waveform at `sample_rate` (None: the codec's rate), on the device (ft_codec_mix): `bed` -
+        (WAV bytes, WavInfo of wavfile.parse_wav) - prepared by the intake launches, brought to the output rate, looped or
+        cut to the programme's length, ducked where x is loud, added to x and held under -1 dBFS.  `params`: a
+        mix.MixParams (mix.bed_params makes one from a Bed), or None for a default Bed's.  Returns (y, MixReport), or
+        (y, MixReport, D) with `nodes`: the duck D_k in hundredths of a dB at the hops + 1 hop borders."""
+        from .mix import Bed, MixParams, bed_params
+        fx = OutputFx.of(sample_rate=sample_rate)
+        rate = fx.wav_rate
+        if params is None:
+            params = bed_params(Bed(b""), rate)
+        if not isinstance(params, MixParams):
+            raise ValueError(f"mix: params must be a MixParams, got {type(params).__name__}")
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        if len(x) < 1:
+            raise ValueError("mix: an empty programme")
+        items, keep, _, _ = self._intake_args("mix", [bed], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
+        mp = L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
+                             params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
+        N, hop, nn = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._check(self.lib.ft_mix_plan(rate, len(x), params.lead, params.tail, C.byref(N), C.byref(hop), C.byref(nn)), "ft_mix_plan")
+        y = np.empty(N.value, dtype=np.float32)
+        D = np.empty(nn.value, dtype=np.int32)
+        total = C.c_int64(0)
+        info = L.ft_mix_info()
+        self._check(self.lib.ft_codec_mix(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, items, C.byref(mp),
+                                          y.ctypes.data_as(C.c_void_p), N.value, C.byref(total),
+                                          D.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)), "ft_codec_mix")
+        del keep
+        rep = MixReport.of(info)
+        return (y[:total.value], rep, D) if nodes else (y[:total.value], rep)
 
     MAX_ITEMS_PER_JOIN = 64       # ft_codec_decode_join
 

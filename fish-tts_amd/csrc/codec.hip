@@ -21,7 +21,8 @@ using chain::ChainPlan; using chain::FxDesc; using chain::StageChain; using chai
 using chain::RS_FI; using chain::RS_MAX_RATE;
 static_assert(chain::RS_LDS == RS_LDS && chain::TS_N == TS_N && chain::TS_HS == TS_HS && chain::TS_D == TS_D &&
               chain::TS_CARRY == TS_CARRY && chain::PS_SHIFT == PS_SHIFT && chain::PS_PHASES == PS_PHASES &&
-              chain::LV_WARM_HOPS == LV_WARM && chain::RD_A == RD_LOOK && chain::RD_R == RD_SLEW,
+              chain::LV_WARM_HOPS == LV_WARM && chain::RD_A == RD_LOOK && chain::RD_R == RD_SLEW &&
+              chain::MX_MAX_W == MX_MAX_WIN && chain::MX_MAX_N <= (1LL << 28),
               "fx_chain.h and codec_kernels.h disagree");
 static_assert(sizeof(ft_level_info) == 32 && offsetof(LevelItem, L) + sizeof(ft_level_info) == sizeof(LevelItem) &&
               offsetof(ft_level_info, peak) == 8 && offsetof(ft_level_info, capped) == 24 &&
@@ -108,6 +109,14 @@ struct CodecState {
     unsigned long long* in_count = nullptr;
     int* in_codes = nullptr;
     size_t in_codes_cap = 0;
+    // mix stage (ft_codec_mix): the gain table, uploaded once; the programme, the bed at the output rate, the output, the
+    // activity flags, D_k and g_k, and the three words the launches reduce into; allocated on the first mixed call (the
+    // buffers grow on need)
+    float *mx_T = nullptr, *mx_x = nullptr, *mx_bed = nullptr, *mx_y = nullptr, *mx_g = nullptr;
+    unsigned char* mx_act = nullptr;
+    int* mx_D = nullptr;
+    MixOut* mx_out = nullptr;
+    size_t mx_xcap = 0, mx_bedcap = 0, mx_ycap = 0, mx_gcap = 0, mx_actcap = 0, mx_Dcap = 0;
     LevelTab* lv_tab = nullptr;
     double* lv_hops = nullptr;
     float *lv_peaks = nullptr, *lv_x = nullptr;
@@ -2536,15 +2545,17 @@ static ft_status in_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) 
 }
 
 // Both entry points: every check, then raw bytes -> intake -> level -> join on the codec's stream; `enc`: the encoder over
-// the kept pieces and their codes to `codes`, else the pieces themselves to `audio`.
+// the kept pieces and their codes to `codes`, else the pieces themselves to `audio`.  `held`: the caller holds s->mu and
+// wants the pieces left in join_out for a stage of its own (the mix stage's bed); `audio` is not written.
 static ft_status intake_run(ft_ctx* ctx, const std::string& fn, int32_t B, const ft_intake_item* items, const ft_join_params* jp,
-                            int32_t loudness, bool enc, float* audio, int32_t* codes, int64_t capacity, int64_t* lens, ft_intake_info* infos) {
+                            int32_t loudness, bool enc, float* audio, int32_t* codes, int64_t capacity, int64_t* lens, ft_intake_info* infos,
+                            bool held = false) {
     if (!ctx) return FT_ERR_ARG;
     FT_TRY(codec_ready(ctx, false));
     CodecState* s = ctx->codec;
     if (enc && !s->has_enc) return ft_fail(ctx, FT_ERR_STATE, fn + ": codec encoder not configured (encoder_dim = 0)");
     FT_TRY(codec_ready(ctx));
-    if (!items || !jp || !infos || (enc ? !codes : (!audio || !lens)) || B < 1 || B > JOIN_MAX_ITEMS)
+    if (!items || !jp || !infos || (enc ? !codes : ((!audio && !held) || !lens)) || B < 1 || B > JOIN_MAX_ITEMS)
         return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument (null pointer, or B outside [1, 64])");
     if (!chain::lv_ok(loudness))
         return ft_fail(ctx, FT_ERR_ARG, fn + ": loudness outside [-5000, -500] hundredths of a LUFS (" + std::to_string(loudness) + ")");
@@ -2577,7 +2588,8 @@ static ft_status intake_run(ft_ctx* ctx, const std::string& fn, int32_t B, const
     if (capacity < room) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity too small");
     const int64_t in_floats = join_offsets(B, n44, off);
     const int R = ctx->cc.n_codebooks + 1;
-    std::lock_guard<std::mutex> lock(s->mu);
+    std::unique_lock<std::mutex> lock(s->mu, std::defer_lock);
+    if (!held) lock.lock();
     FT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = s->stream;
     std::vector<IntakeSeg> segs((size_t)B);
@@ -2620,7 +2632,7 @@ static ft_status intake_run(ft_ctx* ctx, const std::string& fn, int32_t B, const
     FT_HIP(ctx, hipMemcpyAsync(count, s->in_count, (size_t)2 * B * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     FT_TRY(level_enqueue(ctx, B, x, n44, RS_FI, loudness, loudness != 0));
     int64_t total = 0, cuts[2 * JOIN_MAX_ITEMS];
-    FT_TRY(join_run(ctx, B, n44, off, jp, gaps, 0, audio, &total, cuts, need, false, !enc));   // waits for the cuts
+    FT_TRY(join_run(ctx, B, n44, off, jp, gaps, 0, audio, &total, cuts, need, false, !enc && !held));   // waits for the cuts
     for (int b = 0; b < B; ++b) {
         ft_intake_info& o = infos[b];
         memset(&o, 0, sizeof o);
@@ -2663,6 +2675,122 @@ extern "C" ft_status ft_codec_intake(ft_ctx* ctx, int32_t B, const ft_intake_ite
 extern "C" ft_status ft_codec_encode_items(ft_ctx* ctx, int32_t B, const ft_intake_item* items, const ft_join_params* jp,
                                            int32_t loudness, int32_t* codes, int64_t capacity_frames, ft_intake_info* infos) {
     return intake_run(ctx, "ft_codec_encode_items", B, items, jp, loudness, true, nullptr, codes, capacity_frames, nullptr, infos);
+}
+
+// ---- mix stage (fishtts_hip.h: ft_codec_mix, ft_mix_plan, ft_mix_gains; the kernels in codec_kernels.h, the checks, the hop
+// and the table in fx_chain.h)
+static_assert(sizeof(ft_mix_params) == 72 && offsetof(ft_mix_params, lead) == 24 && offsetof(ft_mix_params, loop) == 64, "ft_mix_params layout");
+static_assert(sizeof(ft_mix_info) == 128 && offsetof(ft_mix_info, bed) == 48, "ft_mix_info layout");
+
+extern "C" ft_status ft_mix_gains(float* table) {
+    if (!table) return FT_ERR_ARG;
+    chain::mx_gains(table);
+    return FT_OK;
+}
+
+extern "C" ft_status ft_mix_plan(int32_t sample_rate, int64_t n, int64_t lead, int64_t tail, int64_t* N, int32_t* hop, int64_t* nodes) {
+    chain::MxArgs a;
+    a.rate = sample_rate; a.n = n; a.lead = lead; a.tail = tail;
+    bool too_long = false;
+    if (chain::mx_check(a, &too_long)) return too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG;
+    const chain::MxPlan p = chain::mx_plan(sample_rate, n, lead, tail);
+    if (N) *N = p.N;
+    if (hop) *hop = p.H;
+    if (nodes) *nodes = p.Nh + 1;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
+                                  const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck, ft_mix_info* info) {
+    const std::string fn = "ft_codec_mix";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!x || !bed || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    chain::MxArgs a;
+    a.rate = sample_rate; a.n = n; a.bed_loudness = mp->bed_loudness; a.depth = mp->depth; a.threshold = mp->threshold;
+    a.attack = mp->attack; a.release = mp->release; a.lead = mp->lead; a.tail = mp->tail; a.fade_in = mp->fade_in;
+    a.fade_out = mp->fade_out; a.offset = mp->offset; a.loop = mp->loop;
+    bool too_long = false;
+    if (const char* why = chain::mx_check(a, &too_long)) return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    const chain::MxPlan pl = chain::mx_plan(sample_rate, n, mp->lead, mp->tail);
+    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
+    CodecState* s = ctx->codec;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d));
+    ft_intake_item item = *bed;
+    item.channel = mp->channel;
+    const ft_join_params whole = {0.f, 1, 0, 0};
+    std::lock_guard<std::mutex> lock(s->mu);
+    // the bed: raw frames -> 44100 Hz, levelled, nothing trimmed (its own checks come before its first device work)
+    int64_t nb44 = 0;
+    ft_intake_info binfo;
+    FT_TRY(intake_run(ctx, fn, 1, &item, &whole, mp->bed_loudness, false, nullptr, nullptr, INT64_MAX, &nb44, &binfo, true));
+    if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
+    hipStream_t st = s->stream;
+    // to the output rate: the whole clip from zero state in one final call
+    FT_TRY(rs_table(ctx, sample_rate, &d.rs));
+    const int64_t nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
+    const float* bedp = s->join_out;
+    RsSeg g;                                          // (read by an asynchronous copy: alive until the call's waits)
+    if (d.K > 0) {
+        if (!s->rs_seg) FT_TRY(cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS));
+        FT_TRY(cgrow(ctx, &s->mx_bed, &s->mx_bedcap, (size_t)nb));
+        g = RsSeg{s->join_out, d.rs->w, nullptr, nullptr, s->mx_bed, 0, 0, (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
+        FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, &g, sizeof g, hipMemcpyHostToDevice, st));
+        const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
+        resample_kernel<<<dim3(gx, 1, 1), RS_THREADS, 0, st>>>(s->rs_seg);
+        bedp = s->mx_bed;
+    }
+    if (!s->mx_T) {
+        std::vector<float> T(chain::MX_MAX_DEPTH + 1);
+        chain::mx_gains(T.data());
+        float* t = nullptr;
+        FT_TRY(cmalloc(ctx, &t, T.size()));
+        FT_HIP(ctx, hipMemcpy(t, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
+        FT_TRY(cmalloc(ctx, &s->mx_out, (size_t)1));
+        s->mx_T = t;
+    }
+    FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, (size_t)n));
+    FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)pl.N));
+    FT_TRY(cgrow(ctx, &s->mx_act, &s->mx_actcap, (size_t)pl.Nh));
+    FT_TRY(cgrow(ctx, &s->mx_D, &s->mx_Dcap, (size_t)pl.Nh + 1));
+    FT_TRY(cgrow(ctx, &s->mx_g, &s->mx_gcap, (size_t)pl.Nh + 1));
+    MixP p;
+    memset(&p, 0, sizeof p);
+    p.x = s->mx_x; p.bed = bedp; p.T = s->mx_T; p.act = s->mx_act; p.D = s->mx_D; p.g = s->mx_g; p.y = s->mx_y; p.out = s->mx_out;
+    p.nb = nb;
+    p.off = mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
+    p.N = (int)pl.N; p.n = (int)n; p.lead = (int)mp->lead; p.Nh = (int)pl.Nh; p.H = pl.H;
+    p.depth = mp->depth; p.Wa = mp->attack; p.Wr = mp->release;
+    p.f_in = (int)std::min(mp->fade_in, (int64_t)(pl.N / 2)); p.f_out = (int)std::min(mp->fade_out, (int64_t)(pl.N / 2));
+    p.loop = mp->loop; p.thr = mp->threshold;
+    FT_HIP(ctx, hipMemcpyAsync(s->mx_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipMemsetAsync(s->mx_out, 0, sizeof(MixOut), st));
+    mix_hop_kernel<<<(unsigned)((pl.Nh + MX_THREADS / 64 - 1) / (MX_THREADS / 64)), MX_THREADS, 0, st>>>(p);
+    mix_node_kernel<<<(unsigned)((pl.Nh + 1 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
+    mix_kernel<<<(unsigned)((pl.N + MX_SPAN - 1) / MX_SPAN), MX_THREADS, 0, st>>>(p);
+    MixOut out;
+    FT_HIP(ctx, hipMemcpyAsync(&out, s->mx_out, sizeof out, hipMemcpyDeviceToHost, st));
+    if (duck) FT_HIP(ctx, hipMemcpyAsync(duck, s->mx_D, ((size_t)pl.Nh + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));            // the peak decides whether the fourth launch runs
+    float pk, sg = 1.f;
+    memcpy(&pk, &out.pk, sizeof pk);
+    const bool capped = (double)pk > chain::lv_ceiling();
+    if (capped) {
+        sg = (float)(chain::lv_ceiling() / (double)pk);
+        const int gx = (int)std::max(1LL, std::min(4096LL, (pl.N / 4 + MX_THREADS - 1) / MX_THREADS));
+        mix_scale_kernel<<<gx, MX_THREADS, 0, st>>>(s->mx_y, (int)pl.N, sg);
+    }
+    FT_HIP(ctx, hipMemcpyAsync(y, s->mx_y, (size_t)pl.N * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("mix launch: ") + hipGetErrorString(e));
+    *total = pl.N;
+    memset(info, 0, sizeof *info);
+    info->N = pl.N; info->nb = nb; info->Nh = pl.Nh; info->active = out.active;
+    info->dmax = out.dmax; info->capped = capped ? 1 : 0; info->pk = pk; info->sg = sg;
+    info->bed = binfo;
+    return FT_OK;
 }
 
 // ---- launch trace hooks (fishtts_hip_test.h)

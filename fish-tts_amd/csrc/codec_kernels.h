@@ -2296,4 +2296,158 @@ static __global__ __launch_bounds__(RD_APPLY_THREADS) void ride_apply_kernel(con
     for (long long q = g.base1 + t; q < g.nin + g.n; q += step) g.cout[q - g.base1] = ride_at(g, q);
 }
 
+// ---- mix stage (ft_codec_mix; stated in fishtts_hip.h): a bed at the output rate under a finished programme.  The timeline
+// has N = lead + n + tail samples (N <= 2^28: sample and hop indices fit 32 bits), s[i] = x[i - lead] inside the programme
+// and 0 outside it.  Three launches, four when the ceiling binds:
+//   mix_hop_kernel    one wave per hop of H samples: act[h] = some |s| of the hop is >= the threshold (never a NaN); the
+//                     active hops are counted with one integer atomic per workgroup
+//   mix_node_kernel   one lane per node k = 0 .. Nh: the nearest active hop in [k, k + Wa) and in [k - Wr, k) from the
+//                     workgroup's window of flags staged in LDS (256 + Wa + Wr bytes), D_k and g_k = T[D_k]
+//   mix_kernel        a workgroup per MX_SPAN samples, four per lane and step: 16-byte stores on the aligned groups of y,
+//                     16-byte loads of the programme where `lead` is a multiple of 4 and the group lies inside it, of the
+//                     bed where the group starts on a multiple of 4 of the bed and does not wrap; scalar loads elsewhere and
+//                     on the last up to three samples.  Per workgroup the peak of |m|, one integer atomicMax on its bits
+//                     (the values are not negative, so their bit patterns order as they do)
+//   mix_scale_kernel  y times sg in place
+struct MixOut { unsigned int pk; int active, dmax, pad; };
+struct MixP {
+    const float* x;            // programme, n samples (device, 16-byte aligned)
+    const float* bed;          // bed at the output rate, nb samples (device, 16-byte aligned)
+    const float* T;            // [6001]
+    unsigned char* act;        // [Nh]
+    int* D;                    // [Nh + 1]
+    float* g;                  // [Nh + 1]
+    float* y;                  // [N]
+    MixOut* out;
+    long long nb, off;         // off: `offset` (mod nb with loop, at most nb without)
+    int N, n, lead, Nh, H, depth, Wa, Wr, f_in, f_out, loop;
+    float thr;
+};
+constexpr int MX_THREADS = 256, MX_STEPS = 4, MX_SPAN = MX_THREADS * 4 * MX_STEPS, MX_MAX_WIN = 500;
+
+static __global__ __launch_bounds__(MX_THREADS) void mix_hop_kernel(MixP p) {
+    const int lane = threadIdx.x & 63, h = blockIdx.x * (MX_THREADS / 64) + (threadIdx.x >> 6);
+    __shared__ int cnt[MX_THREADS / 64];
+    int on = 0;
+    if (h < p.Nh) {
+        const int i0 = h * p.H, i1 = min(p.N, i0 + p.H);
+        float pk = -1.f;                                   // (fmaxf passes a NaN by: a hop of NaNs stays below any threshold)
+        for (int i = i0 + lane; i < i1; i += 64) {
+            const int q = i - p.lead;
+            if (q >= 0 && q < p.n) pk = fmaxf(pk, fabsf(p.x[q]));
+            else pk = fmaxf(pk, 0.f);
+        }
+        for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o));
+        on = pk >= p.thr;
+        if (lane == 0) p.act[h] = (unsigned char)on;
+    }
+    if (lane == 0) cnt[threadIdx.x >> 6] = on;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int w = 0; w < MX_THREADS / 64; ++w) c += cnt[w];
+        if (c > 0) atomicAdd(&p.out->active, c);
+    }
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mix_node_kernel(MixP p) {
+    __shared__ unsigned char win[MX_THREADS + 2 * MX_MAX_WIN];
+    __shared__ int wmax[MX_THREADS / 64];
+    const int k0 = blockIdx.x * MX_THREADS, lo = k0 - p.Wr, span = MX_THREADS + p.Wa + p.Wr;   // win[j] = act[lo + j]
+    for (int j = threadIdx.x; j < span; j += MX_THREADS) {
+        const int h = lo + j;
+        win[j] = h >= 0 && h < p.Nh ? p.act[h] : 0;
+    }
+    __syncthreads();
+    const int k = k0 + threadIdx.x;
+    int d = 0;
+    if (k <= p.Nh) {
+        const unsigned char* w = win + (k - lo);           // w[j] = act[k + j]
+        for (int j = 0; j < p.Wa; ++j)
+            if (w[j]) { d = (int)((long long)p.depth * (p.Wa - j) / p.Wa); break; }
+        for (int j = 0; j < p.Wr; ++j)
+            if (w[-1 - j]) { d = max(d, (int)((long long)p.depth * (p.Wr - j) / p.Wr)); break; }
+        p.D[k] = d;
+        p.g[k] = p.T[d];
+    }
+    for (int o = 32; o > 0; o >>= 1) d = max(d, __shfl_xor(d, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < MX_THREADS / 64; ++w) d = max(d, wmax[w]);
+        if (d > 0) atomicMax(&p.out->dmax, d);
+    }
+}
+
+__device__ inline float mix_prog(const MixP& p, int i) {
+    const int q = i - p.lead;
+    return q >= 0 && q < p.n ? p.x[q] : 0.f;
+}
+
+// Bed sample at position j = i + off of the bed (j >= 0).
+__device__ inline float mix_bed(const MixP& p, long long j) {
+    if (p.loop) return p.bed[j % p.nb];
+    return j < p.nb ? p.bed[j] : 0.f;
+}
+
+// m[i] from s = s[i] and t = b(i): the fades, the duck, the sum, every operation rounded on its own.
+__device__ inline float mix_sample(const MixP& p, int i, float s, float t) {
+    const unsigned int k = (unsigned int)i / (unsigned int)p.H;
+    const float gk = p.g[k], r = __fdiv_rn((float)(i - (int)k * p.H), (float)p.H);
+    const float gd = fmaf(r, p.g[k + 1] - gk, gk);
+    if (i < p.f_in) t = __fmul_rn(t, (float)((double)(2 * (long long)i + 1) / (double)(2 * (long long)p.f_in)));
+    if (i >= p.N - p.f_out) t = __fmul_rn(t, (float)((double)(2 * (long long)(p.N - 1 - i) + 1) / (double)(2 * (long long)p.f_out)));
+    return __fadd_rn(s, __fmul_rn(t, gd));
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mix_kernel(MixP p) {
+    __shared__ float wpk[MX_THREADS / 64];
+    const int N4 = p.N >> 2;
+    const bool xal = (p.lead & 3) == 0;
+    float pk = 0.f;
+    for (int st = 0; st < MX_STEPS; ++st) {
+        const int q = (blockIdx.x * MX_STEPS + st) * MX_THREADS + threadIdx.x, i = 4 * q;
+        if (q >= N4) break;
+        float4 s, t;
+        const int a = i - p.lead;
+        if (xal && a >= 0 && a + 3 < p.n) s = *(const float4*)(p.x + a);
+        else s = make_float4(mix_prog(p, i), mix_prog(p, i + 1), mix_prog(p, i + 2), mix_prog(p, i + 3));
+        long long j = (long long)i + p.off;
+        if (p.loop) j %= p.nb;
+        if ((j & 3) == 0 && j + 3 < p.nb) t = *(const float4*)(p.bed + j);
+        else t = make_float4(mix_bed(p, j), mix_bed(p, j + 1), mix_bed(p, j + 2), mix_bed(p, j + 3));
+        float4 m;
+        m.x = mix_sample(p, i, s.x, t.x);
+        m.y = mix_sample(p, i + 1, s.y, t.y);
+        m.z = mix_sample(p, i + 2, s.z, t.z);
+        m.w = mix_sample(p, i + 3, s.w, t.w);
+        ((float4*)p.y)[q] = m;
+        pk = fmaxf(pk, fmaxf(fmaxf(fabsf(m.x), fabsf(m.y)), fmaxf(fabsf(m.z), fabsf(m.w))));
+    }
+    // the up to three samples behind the last whole group: the workgroup that owns position N4
+    if (4 * N4 < p.N && N4 / (MX_THREADS * MX_STEPS) == (int)blockIdx.x && threadIdx.x < p.N - 4 * N4) {
+        const int i = 4 * N4 + threadIdx.x;
+        const float m = mix_sample(p, i, mix_prog(p, i), mix_bed(p, (long long)i + p.off));
+        p.y[i] = m;
+        pk = fmaxf(pk, fabsf(m));
+    }
+    for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o));
+    if ((threadIdx.x & 63) == 0) wpk[threadIdx.x >> 6] = pk;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < MX_THREADS / 64; ++w) pk = fmaxf(pk, wpk[w]);
+        if (pk > 0.f) atomicMax(&p.out->pk, __float_as_uint(pk));
+    }
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mix_scale_kernel(float* y, int N, float sg) {
+    const int N4 = N >> 2;
+    for (int q = blockIdx.x * MX_THREADS + threadIdx.x; q < N4; q += gridDim.x * MX_THREADS) {
+        float4 v = ((float4*)y)[q];
+        v.x = __fmul_rn(v.x, sg); v.y = __fmul_rn(v.y, sg); v.z = __fmul_rn(v.z, sg); v.w = __fmul_rn(v.w, sg);
+        ((float4*)y)[q] = v;
+    }
+    if (blockIdx.x == 0 && 4 * N4 + (int)threadIdx.x < N) y[4 * N4 + threadIdx.x] = __fmul_rn(y[4 * N4 + threadIdx.x], sg);
+}
+
 }  // namespace ft

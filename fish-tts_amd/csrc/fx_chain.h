@@ -1,7 +1,8 @@
 // Host arithmetic of the output chain behind the codec (fishtts_hip.h: sample_rate, speed_pct, pitch_cents, loudness, live): the
 // time-scale stage, then the pitch stage, then the resampler, then the level (whole items) or the ride stage (streams).  The filter designs, the rule that accepts a
 // (speed, cents) pair, what each stage can emit after so many input samples, the bookkeeping of a stream's three stages from
-// call to call, and the level stage's K-weighting design, gates and gain.
+// call to call, and the level stage's K-weighting design, gates and gain; behind the join, the mix stage's timeline, checks,
+// duck and gain table (mx_*; tools/mix_check.cpp drives that block).
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
 // are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
@@ -261,6 +262,73 @@ inline RdPlan rd_plan(int H, long long nin, bool final) {
     p.nodes = p.hops >= RD_A ? p.hops - RD_A + 1 : 0;
     p.out = p.base = (long long)std::max(0, p.hops - RD_A) * H;
     return p;
+}
+
+// ---- mix stage (mix_hop_kernel, mix_node_kernel, mix_kernel, mix_scale_kernel; fishtts_hip.h states it): a bed under a
+// finished programme, lowered by a look-ahead sidechain gain that follows the programme's activity.  The hop (20 ms), the
+// timeline, the argument checks in their stated order, the duck D_k (hundredths of a dB) from an activity array, the table.
+constexpr int MX_MAX_DEPTH = 6000, MX_MAX_W = 500;
+constexpr long long MX_MAX_N = 1LL << 28;
+inline int mx_hop(int rate) { return rate / 50; }
+struct MxPlan { long long N = 0, Nh = 0; int H = 1; };
+// The timeline of n programme samples at `rate` with `lead` and `tail` (all judged by mx_check first).
+inline MxPlan mx_plan(int rate, long long n, long long lead, long long tail) {
+    MxPlan p;
+    p.H = mx_hop(rate);
+    p.N = lead + n + tail;
+    p.Nh = (p.N + p.H - 1) / p.H;
+    return p;
+}
+// The values of a call in the order every entry point judges them: null, or why not (*too_long: the refusal is a length).
+struct MxArgs {
+    int rate = RS_FI;
+    long long n = 0;
+    int bed_loudness = 0, depth = 0;
+    float threshold = 0.f;
+    int attack = 1, release = 1;
+    long long lead = 0, tail = 0, fade_in = 0, fade_out = 0, offset = 0;
+    int loop = 0;
+};
+inline const char* mx_check(const MxArgs& a, bool* too_long) {
+    int L, M, K;
+    *too_long = false;
+    if (const char* e = rs_design(a.rate, &L, &M, &K, nullptr)) return e;
+    if (a.n < 1) return "n must be at least 1";
+    if (!lv_ok(a.bed_loudness)) return "bed_loudness neither 0 nor in [-5000, -500] hundredths of a LUFS";
+    if (a.depth < 0 || a.depth > MX_MAX_DEPTH) return "depth outside [0, 6000] hundredths of a dB";
+    if (!(a.threshold >= 0.f)) return "threshold must be >= 0";   // (refuses a NaN too)
+    if (a.attack < 1 || a.attack > MX_MAX_W) return "attack outside [1, 500] hops";
+    if (a.release < 1 || a.release > MX_MAX_W) return "release outside [1, 500] hops";
+    if (a.lead < 0) return "lead must be >= 0";
+    if (a.tail < 0) return "tail must be >= 0";
+    if (a.fade_in < 0) return "fade_in must be >= 0";
+    if (a.fade_out < 0) return "fade_out must be >= 0";
+    if (a.offset < 0) return "offset must be >= 0";
+    if (a.loop != 0 && a.loop != 1) return "loop must be 0 or 1";
+    if (a.n > MX_MAX_N || a.lead > MX_MAX_N || a.tail > MX_MAX_N || a.lead + a.n + a.tail > MX_MAX_N) {
+        *too_long = true;
+        return "lead + n + tail exceeds 2^28 samples";
+    }
+    return nullptr;
+}
+// D_k for k = 0 .. Nh from act[0 .. Nh): the largest of 0, depth (Wa - (h - k)) / Wa over active h in [k, k + Wa - 1] and
+// depth (Wr - (k - 1 - h)) / Wr over active h in [k - Wr, k - 1] (int64 divisions).  Both terms fall with the distance, so
+// the nearest active hop on either side decides: one pass each way.
+inline void mx_duck(const unsigned char* act, long long Nh, int depth, int Wa, int Wr, int* D) {
+    long long near = -1;                      // the nearest active hop at or after k
+    for (long long k = Nh; k >= 0; --k) {
+        if (k < Nh && act[k]) near = k;
+        D[k] = near >= 0 && near - k < Wa ? (int)((long long)depth * (Wa - (near - k)) / Wa) : 0;
+    }
+    near = -1;                                // the nearest active hop before k
+    for (long long k = 0; k <= Nh; ++k) {
+        if (k >= 1 && act[k - 1]) near = k - 1;
+        if (near >= 0 && k - 1 - near < Wr) D[k] = std::max(D[k], (int)((long long)depth * (Wr - (k - 1 - near)) / Wr));
+    }
+}
+// T[d] = (float) 10^(-d / 2000), d = 0 .. 6000: float64 rounded once; T[0] = 1.
+inline void mx_gains(float* T) {
+    for (int d = 0; d <= MX_MAX_DEPTH; ++d) T[d] = (float)std::pow(10.0, -(double)d / 2000.0);
 }
 
 // ---- the stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;

@@ -147,9 +147,11 @@ def codes_served(srv, serve_) -> Optional[list]:
         release()
 
 
-def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_):
+def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None):
     """(audio, cuts) of the whole call: the codes from serve_(srv) while a BatchServer srv = server() is open (None: there
-    is none), else from generate_(emit, stopped); one decode_join, under the server's codec lock when it served them."""
+    is none), else from generate_(emit, stopped); one decode_join, under the server's codec lock when it served them.
+    `bed`: (clip, mix.MixParams) - the joined piece then goes through the mix stage (vocoder.mix) under the same lock, and
+    `audio` is the mixed piece: `lead` samples longer in front, `tail` behind (the cuts are the join's own)."""
     srv = server()
     codes = codes_served(srv, serve_)
     lock = contextlib.nullcontext() if codes is None else srv.codec_lock
@@ -159,6 +161,8 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_):
         codes = [got[i] for i in range(len(plan.texts))]
     with lock:
         audio, cuts = vocoder.decode_join(codes, params=plan.jp, gaps=plan.gaps, **plan.fx_of())
+        if bed is not None and len(audio):
+            audio, _ = vocoder.mix(audio, bed[0], sample_rate=plan.rate, params=bed[1])
     if not len(audio):
         raise RuntimeError("No audio generated")
     return audio, cuts

@@ -3,6 +3,7 @@ signatures, defaults and exceptions of fish_tts/synthesizer.py:47-719.  The dual
 run in libfishtts_hip.so; this file is host logic only (threads, queues, WAV packing)."""
 from __future__ import annotations
 
+import contextlib
 import io
 import logging
 import queue
@@ -569,7 +570,7 @@ class FishTTS:
                         pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                         max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                         speed: Optional[float] = None, pitch: Optional[float] = None,
-                        loudness: Optional[float] = None) -> bytes:
+                        loudness: Optional[float] = None, bed=None) -> bytes:
         """Extension: a text of any length -> one WAV.  The text is split into segments of at most `max_chars` bytes at
         sentence ends (longform.split_text; pieces below `min_chars` join a neighbour), every segment is an utterance of
         its own - `max_tokens` frames at most each, segment i drawing with seed + i - and all of them run as ONE lock-step
@@ -583,14 +584,17 @@ class FishTTS:
         `speed`, `pitch` as synthesize_at, applied per segment before the join.  `loudness` (as synthesize_at): every
         segment is levelled to the target on its own, before the join - the sentences of the document then stand at one
         level, and `silence_db` is judged on the levelled samples.  While a BatchServer is open the segments
-        join its batch.  ValueError before any device work: pause / paragraph_pause outside [0, 5] s, silence_db outside
+        join its batch.  `bed` (a mix.Bed): music or room tone under the joined piece, ducked where it speaks (the mix
+        stage, CodecHipEngine.mix; bed=None: the call as it always was).  ValueError before any device work: pause /
+        paragraph_pause outside [0, 5] s, silence_db outside
         [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch /
-        loudness."""
+        loudness, a bad value in `bed` or a bed file the intake does not read."""
         from . import segments
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
                                loudness)
+        mixed = self._bed_args(bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        audio, _ = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed))
+        audio, _ = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed)
         return self._to_wav_bytes(audio, plan.rate)
 
     def synthesize_long_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
@@ -598,19 +602,62 @@ class FishTTS:
                                pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                                max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                                speed: Optional[float] = None, pitch: Optional[float] = None,
-                               loudness: Optional[float] = None) -> Iterator[bytes]:
+                               loudness: Optional[float] = None, bed=None) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
         chunks concatenate to synthesize_long's PCM byte for byte - with `loudness` too: a group holds whole segments, and
         each is levelled on its own.  No empty chunk is yielded.  The arguments are checked
         here, at the call; generation holds _gen_lock on its own thread and stops within one burst when the generator is
-        abandoned."""
+        abandoned.  `bed` is refused (ValueError): see _no_streamed_bed."""
         from . import segments
+        _no_streamed_bed(bed, "synthesize_long_stream")
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
                                loudness)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed))
+
+    # ------------------------------------------------------------------ music bed (extension)
+    def _bed_args(self, bed, rate: int, silence_db=None):
+        """Every check of a call's `bed=`, before any device work: None without one, else (clip, mix.MixParams) as
+        CodecHipEngine.mix takes them - the Bed's values in their native form at output rate `rate` (mix.bed_params), its
+        WAV read (wavfile.parse_wav) and judged as the intake judges a clip.  ValueError for a bad value."""
+        if bed is None:
+            return None
+        from .mix import bed_bytes, bed_params
+        from .wavfile import parse_wav
+        mp = bed_params(bed, rate, silence_db)
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        data = bed_bytes(bed)
+        clip = (data, parse_wav(data))
+        self._vocoder._intake_args("bed", [clip], (0.0, 1, 0, 0), None, bed.channel)
+        return clip, mp
+
+    def mix(self, wav_bytes: bytes, bed, silence_db: Optional[float] = None, report: Optional[list] = None) -> bytes:
+        """Extension: a finished 16-bit mono WAV - at 44.1 kHz or any rate `sample_rate=` takes - with `bed` (a mix.Bed)
+        under it -> one WAV at the same rate, `lead` + `tail` longer (the mix stage, CodecHipEngine.mix).  `silence_db`:
+        what counts as speech where the Bed has no threshold_db (None: -45).  `report`: a list that receives the
+        MixReport.  ValueError before any device work: not 16-bit mono, no sample, an unsupported rate, a bad Bed."""
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        with wave.open(io.BytesIO(wav_bytes), "rb") as wf:
+            if wf.getnchannels() != 1 or wf.getsampwidth() != 2:
+                raise ValueError("mix: a 16-bit mono WAV is needed")
+            rate = wf.getframerate()
+            audio = np.frombuffer(wf.readframes(wf.getnframes()), dtype=np.int16).astype(np.float32) / 32768.0
+        if not len(audio):
+            raise ValueError("mix: the WAV holds no sample")
+        rate = _output_fx(rate, None, None).wav_rate            # (ValueError for a rate the output stages do not take)
+        if bed is None:
+            raise ValueError("mix: a Bed is needed")
+        clip, mp = self._bed_args(bed, rate, silence_db)
+        srv = getattr(self, "_server", None)
+        with (srv.codec_lock if srv is not None else contextlib.nullcontext()):   # the server's codec worker shares the codec context
+            y, rep = self._vocoder.mix(audio, clip, sample_rate=rate, params=mp)
+        if report is not None:
+            report.append(rep)
+        return self._to_wav_bytes(y, rate)
 
     # ------------------------------------------------------------------ scripts (extension)
     def _script_plan(self, lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
@@ -651,7 +698,7 @@ class FishTTS:
                           pause: float = 0.2, paragraph_pause: float = 0.5, line_pause: float = 0.4,
                           silence_db: Optional[float] = -45.0, max_chars: int = 200, min_chars: int = 24,
                           sample_rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None,
-                          loudness: Optional[float] = None, marks: Optional[list] = None) -> bytes:
+                          loudness: Optional[float] = None, marks: Optional[list] = None, bed=None) -> bytes:
         """Extension: a script - a dialogue, a narrated piece with quoted speakers - as one WAV.  `lines`: a list of
         script.Line (text, voice, speed, pitch, loudness, volume, pause), or an SSML string (script.parse_ssml: speak, p, s,
         voice, break, prosody); `voices`: name -> list of VoiceProfile.  Every line is split as synthesize_long splits a text
@@ -664,17 +711,20 @@ class FishTTS:
         line's `pause` or `line_pause` in front of it.  One `sample_rate` per call.  `marks` (a list) receives one
         (start_sample, end_sample) per line at the output rate, from the join's cuts and gaps.  A script of one plain Line
         is synthesize_long of its text, byte for byte.  While a BatchServer is open the segments join its batch.
+        `bed` (a mix.Bed): as synthesize_long's; `marks` then count from the start of the mixed piece (the join's marks plus
+        the bed's `lead` in samples).
         ValueError before any device work: no line, an unknown voice, a bad value in a line or in the call, a bad
         line_pause, more distinct voices than the reference cache holds (8; not with cache_reference_kv=False)."""
         from . import segments
         from .script import line_marks
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
                                  min_chars, sample_rate, speed, pitch, loudness, marks)
+        mixed = self._bed_args(bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        audio, cuts = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed))
+        audio, cuts = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed)
         if marks is not None:
             found = [None] * plan.n_lines
-            line_marks(plan.line_of, plan.gaps, cuts, found)
+            line_marks(plan.line_of, plan.gaps, cuts, found, at=0 if mixed is None else mixed[1].lead)
             marks.extend(found)
         return self._to_wav_bytes(audio, plan.rate)
 
@@ -684,14 +734,16 @@ class FishTTS:
                                  line_pause: float = 0.4, silence_db: Optional[float] = -45.0, max_chars: int = 200,
                                  min_chars: int = 24, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                                  pitch: Optional[float] = None, loudness: Optional[float] = None,
-                                 marks: Optional[list] = None) -> Iterator[bytes]:
+                                 marks: Optional[list] = None, bed=None) -> Iterator[bytes]:
         """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
         (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
         byte for byte; no empty chunk is yielded.  `marks` fills as groups go out: a line's entry is added once its last
-        segment went out, and in the end the list is synthesize_script's.  The arguments are checked here, at the call."""
+        segment went out, and in the end the list is synthesize_script's.  The arguments are checked here, at the call.
+        `bed` is refused (ValueError): see _no_streamed_bed."""
         from . import segments
         from .script import line_marks
+        _no_streamed_bed(bed, "synthesize_script_stream")
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
                                  min_chars, sample_rate, speed, pitch, loudness, marks)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
@@ -989,6 +1041,14 @@ def _check_sampling(temperature: float, top_p: float, repetition_penalty: float)
     assert 0 < top_p <= 1, "top_p must be in (0, 1]"
     assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
     assert 0 < temperature < 2, "temperature must be in (0, 2)"
+
+
+def _no_streamed_bed(bed, what: str) -> None:
+    """A stream takes no bed: the mix stage holds the whole piece under the -1 dBFS ceiling with ONE gain, known only when
+    the last sample is (as `loudness=` was before `live_loudness=`); a streamed form is not built yet."""
+    if bed is not None:
+        raise ValueError(f"bed needs the whole piece: {what} hands out audio before its end, and the mix stage's ceiling - one "
+                         "gain over the whole mixed piece - is known only there (synthesize the piece, or mix() a finished WAV)")
 
 
 def _output_fx(sample_rate, speed, pitch, loudness=None, live_loudness=None):

@@ -543,6 +543,70 @@ ft_status ft_codec_intake(ft_ctx* ctx, int32_t B, const ft_intake_item* items, c
  * row-major.  capacity_frames must be at least sum_b ceil(n44_b / ft_codec_enc_frame_len), the most the call can give. */
 ft_status ft_codec_encode_items(ft_ctx* ctx, int32_t B, const ft_intake_item* items, const ft_join_params* jp,
                                 int32_t loudness, int32_t* codes, int64_t capacity_frames, ft_intake_info* infos);
+/* Mix.  A music bed under a finished programme: codec -> time-scale stage -> pitch stage -> rate resampler -> level -> join ->
+ * mix.  The bed is a second WAV, prepared by the intake launches, brought to the output rate, looped or cut to the
+ * programme's length, lowered by a look-ahead sidechain gain that follows where the programme is loud, added to the programme
+ * and held under the -1 dBFS ceiling, all on the codec's stream.  The reference has no such stage.  Stated, which fixes every
+ * bit of the result:
+ *   Inputs: the programme x[0 .. n), float32 at the output rate Fo (any rate ft_resample_filter accepts), n >= 1; the bed, one
+ *   ft_intake_item (its `channel` field is not read: mp->channel stands for it); ft_mix_params, sample counts at Fo:
+ *   bed_loudness 0 or in [-5000, -500] hundredths of a LUFS (the intake's `loudness`), channel (the intake's), depth in
+ *   [0, 6000] hundredths of a dB, threshold >= 0 (linear), attack Wa and release Wr in hops, each in [1, 500], lead and tail
+ *   >= 0 (bed alone before and after the programme), fade_in and fade_out >= 0, offset >= 0 (the first bed sample used),
+ *   loop 0 or 1.
+ *   Bed: bed44 is, bit for bit, the piece ft_codec_intake gives for the item with jp = (0, 1, 0, 0) and loudness =
+ *   bed_loudness (nothing trimmed); bed is, bit for bit, what resample_kernel gives for the whole of bed44 from zero state in one
+ *   final call (ft_test_resample), at Fo = 44100 bed44 itself.  Its length is nb; nb = 0 is refused with FT_ERR_ARG.
+ *   Timeline: N = lead + n + tail; s[i] = x[i - lead] inside [lead, lead + n), else +0.0.  With j = i + offset, b(i) =
+ *   bed[j mod nb] with loop; without it bed[j] for j < nb and +0.0 past it.
+ *   Activity: H = floor(Fo / 50) (20 ms), Nh = ceil(N / H); act_h = some sample of [h H, min((h + 1) H, N)) has
+ *   |s| >= threshold, compared in float32 (the join's rule: a NaN is never loud).  That is P_h >= threshold with P_h the
+ *   largest |s| of the hop that is not a NaN.
+ *   Duck: nodes k = 0 .. Nh at sample k H; D_k, an integer in hundredths of a dB, is the largest of 0,
+ *   depth (Wa - (h - k)) / Wa over active h in [k, k + Wa - 1] and depth (Wr - (k - 1 - h)) / Wr over active h in
+ *   [k - Wr, k - 1]; only hops in [0, Nh) count; integer divisions in int64.  So both nodes of an active hop sit at full
+ *   depth, the gain falls over Wa hops before speech and rises over Wr hops after it; it is a function of the activity alone.
+ *   Gains: g_k = T[D_k], T[d] = (float) 10^(-d / 2000) for d = 0 .. 6000, float64 rounded once (ft_mix_gains); T[0] = 1.
+ *   Sample i = k H + j: r = (float) j / (float) H (an IEEE division), gd = fmaf(r, g_k+1 - g_k, g_k); t = b(i); if
+ *   i < f_in = min(fade_in, N / 2), t = t ramp_in(i); if i >= N - f_out, f_out = min(fade_out, N / 2), t = t ramp_out(N - 1 - i);
+ *   ramp(j) = (float)((double)(2 j + 1) / (double)(2 f)) with f the fade's length (the join's ramp); u = t gd; m[i] = s[i] + u.
+ *   Every product and the sum are rounded to float32 on their own, none contracted.
+ *   Ceiling: pk = max |m| (a NaN is never the peak), c = 10^(-1/20); if pk > c every sample is multiplied once by
+ *   sg = (float)(c / pk) (float64, rounded once), else nothing more touches a sample.
+ *   It follows: a bed of zeros gives `lead` zeros, x, `tail` zeros (a -0.0 of x becomes +0.0); depth = 0 gives every node
+ *   exactly 1; a call repeated gives the same bits (no floating-point atomics; the peak is a max).
+ *   Reported (ft_mix_info): N, nb, Nh, the active hops, the largest D_k, pk, sg (1 when not capped), capped, the bed's
+ *   ft_intake_info.  duck (may be NULL) receives D_0 .. D_Nh.
+ * Limits: N <= 2^28; the bed as an intake item; capacity >= N.  Every argument is checked before any device work and a
+ * refused call changes nothing.  The checks, in this order: a null pointer (FT_ERR_ARG); sample_rate; n < 1; bed_loudness;
+ * depth; threshold (a NaN too); attack; release; lead; tail; fade_in; fade_out; offset; loop (FT_ERR_ARG each);
+ * n, lead, tail or N beyond 2^28 (FT_ERR_TOO_LONG); capacity < N (FT_ERR_ARG); then the bed as ft_codec_intake judges an
+ * item: no frames, fmt, channels, channel, rate (FT_ERR_ARG), its length (FT_ERR_TOO_LONG).  A bed that comes out of the
+ * intake with no sample (nb = 0) is refused after the intake launches (FT_ERR_ARG).
+ * On the device: the programme, the bed at Fo, the output, one activity byte per hop, D_k and g_k per node; the buffers grow
+ * when a later call needs more.  Launches beyond the bed's preparation (intake, level, join, resampler): mix_hop_kernel (hop
+ * activity), mix_node_kernel (D_k, the flags of a workgroup's window staged in LDS), mix_kernel (the sample rule and the
+ * peak), and mix_scale_kernel only when the ceiling binds. */
+typedef struct ft_mix_params {
+    int32_t bed_loudness, channel, depth;
+    float threshold;
+    int32_t attack, release;
+    int64_t lead, tail, fade_in, fade_out, offset;
+    int32_t loop, reserved;
+} ft_mix_params;
+typedef struct ft_mix_info {
+    int64_t N, nb, Nh, active;
+    int32_t dmax, capped;
+    float pk, sg;
+    ft_intake_info bed;
+} ft_mix_info;
+ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
+                       const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck, ft_mix_info* info);
+/* Host only: the timeline of a call - N = lead + n + tail, the hop H and the Nh + 1 nodes.  Any output pointer may be NULL.
+ * FT_ERR_ARG / FT_ERR_TOO_LONG as ft_codec_mix judges the four values. */
+ft_status ft_mix_plan(int32_t sample_rate, int64_t n, int64_t lead, int64_t tail, int64_t* N, int32_t* hop, int64_t* nodes);
+/* Host only: T[0 .. 6000]. */
+ft_status ft_mix_gains(float* table);
 
 ft_status ft_sync(ft_ctx* ctx);
 /* State of the persistent frame engine (csrc/frame_engine.h), the batch-1 form of the decode step
