@@ -74,6 +74,11 @@ class ft_mix_info(C.Structure):
                 ("capped", C.c_int32), ("pk", C.c_float), ("sg", C.c_float), ("bed", ft_intake_info)]
 
 
+class ft_mix_live_info(C.Structure):
+    _fields_ = [("N", C.c_int64), ("nb", C.c_int64), ("Nh", C.c_int64), ("active", C.c_int64), ("dmax", C.c_int32),
+                ("lmax", C.c_int32), ("qmax", C.c_float), ("reserved", C.c_int32), ("bed", ft_intake_info)]
+
+
 class ft_sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("repetition_penalty", C.c_float),
                 ("ban_eos", C.c_int32), ("seed", C.c_uint64)]
@@ -159,6 +164,12 @@ SYMBOLS = {
                                  _P, _P, C.POINTER(ft_mix_info)]),
     "ft_mix_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "ft_mix_gains": (C.c_int32, [_P]),
+    "ft_mix_live_plan": (C.c_int32, [C.c_int32, C.POINTER(ft_mix_params), C.c_int64, C.c_int32, _P, _P]),
+    "ft_codec_mix_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), _P,
+                                      C.c_int64, _P, _P, _P, C.POINTER(ft_mix_live_info)]),
+    "ft_codec_mix_stream_begin": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), C.POINTER(_P)]),
+    "ft_codec_mix_stream_push": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
+    "ft_codec_mix_stream_end": (None, [_P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),
     "ft_ar_profile_gemv": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_sampling), C.POINTER(C.c_double),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -88,6 +88,63 @@ class MixReport:
 
 
 @dataclass(frozen=True)
+class MixLiveReport:
+    """What the live mix stage did (ft_mix_live_info): `n`, `bed_len`, `hops`, `active`, `duck_max` and `bed` as MixReport's;
+    `limit_max` the deepest the limiter went (dB), `peak` the largest hop peak before the limiter."""
+    n: int
+    bed_len: int
+    hops: int
+    active: int
+    duck_max: float
+    limit_max: float
+    peak: float
+    bed: IntakeReport
+
+    @classmethod
+    def of(cls, i: "L.ft_mix_live_info") -> "MixLiveReport":
+        return cls(int(i.N), int(i.nb), int(i.Nh), int(i.active), i.dmax / 100.0, i.lmax / 100.0, float(np.float32(i.qmax)),
+                   IntakeReport.of(i.bed))
+
+
+class MixStream:
+    """An open stream of the live mix stage (ft_codec_mix_stream_*; CodecHipEngine.mix_stream makes one): push(x) takes the
+    next programme samples and returns the mixed samples that became final, push(x, final=True) ends the programme and returns
+    all that is left; close() frees the stream's device state (a closed stream refuses pushes)."""
+
+    def __init__(self, engine, handle, mp, rate: int):
+        self._eng, self._h, self._mp, self._rate = engine, handle, mp, rate
+        self._nin, self._out = 0, 0
+
+    def push(self, x=None, final: bool = False) -> np.ndarray:
+        if self._h is None:
+            raise RuntimeError("mix stream: closed")
+        x = np.zeros(0, dtype=np.float32) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        eng = self._eng
+        done = C.c_int64(0)
+        eng._check(eng.lib.ft_mix_live_plan(self._rate, C.byref(self._mp), self._nin + len(x), 1 if final else 0, C.byref(done),
+                                            None), "ft_mix_live_plan")
+        cap = max(done.value - self._out, 0)
+        y = np.empty(max(cap, 1), dtype=np.float32)
+        n = C.c_int64(0)
+        eng._check(eng.lib.ft_codec_mix_stream_push(self._h, x.ctypes.data_as(C.c_void_p), len(x), 1 if final else 0,
+                                                    y.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "ft_codec_mix_stream_push")
+        self._nin += len(x)
+        self._out += n.value
+        return y[:n.value]
+
+    def close(self) -> None:
+        if self._h is not None:
+            self._eng.lib.ft_codec_mix_stream_end(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+@dataclass(frozen=True)
 class OutputFx:
     """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent), `cents` (pitch), `level` (loudness
     target, hundredths of a LUFS) and `live` (a stream's live loudness target, the same unit), each None where the stage is
@@ -759,6 +816,58 @@ class CodecHipEngine:
         del keep
         rep = MixReport.of(info)
         return (y[:total.value], rep, D) if nodes else (y[:total.value], rep)
+
+    def _mix_args(self, what: str, bed, sample_rate, params):
+        """(rate, bed item array, what keeps its bytes alive, ft_mix_params) of a mix call, checked as mix() checks them."""
+        from .mix import Bed, MixParams, bed_params
+        rate = OutputFx.of(sample_rate=sample_rate).wav_rate
+        if params is None:
+            params = bed_params(Bed(b""), rate)
+        if not isinstance(params, MixParams):
+            raise ValueError(f"{what}: params must be a MixParams, got {type(params).__name__}")
+        items, keep, _, _ = self._intake_args(what, [bed], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
+        mp = L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
+                             params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
+        return rate, items, keep, mp
+
+    def mix_live_plan(self, sample_rate: Optional[int], params, n_in: int, final: bool = False):
+        """(samples emitted, final limiter nodes) of a mix stream after n_in programme samples (ft_mix_live_plan; host only)."""
+        mp = L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
+                             params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
+        n, k = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.ft_mix_live_plan(OutputFx.of(sample_rate=sample_rate).wav_rate, C.byref(mp), int(n_in),
+                                              1 if final else 0, C.byref(n), C.byref(k)), "ft_mix_live_plan")
+        return n.value, k.value
+
+    def mix_live(self, x: np.ndarray, bed, sample_rate: Optional[int] = None, params=None, nodes: bool = False):
+        """The live mix stage on a whole host waveform (ft_codec_mix_live): what a mix stream gives for x in one final push -
+        mix()'s bed, duck and sum, held under -1 dBFS by a look-ahead limiter instead of one gain.  x may be empty.  Returns
+        (y, MixLiveReport), or (y, MixLiveReport, D, L) with `nodes`: the duck and the limiter's depth in hundredths of a dB at
+        the hops + 1 hop borders."""
+        rate, items, keep, mp = self._mix_args("mix_live", bed, sample_rate, params)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        N = mp.lead + len(x) + mp.tail
+        nn = -(-N // (rate // 50)) + 1
+        y = np.empty(max(N, 1), dtype=np.float32)
+        D, Lk = np.empty(nn, dtype=np.int32), np.empty(nn, dtype=np.int32)
+        total = C.c_int64(0)
+        info = L.ft_mix_live_info()
+        self._check(self.lib.ft_codec_mix_live(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, items, C.byref(mp),
+                                               y.ctypes.data_as(C.c_void_p), N, C.byref(total),
+                                               D.ctypes.data_as(C.c_void_p) if nodes else None,
+                                               Lk.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)), "ft_codec_mix_live")
+        del keep
+        rep = MixLiveReport.of(info)
+        return (y[:total.value], rep, D, Lk) if nodes else (y[:total.value], rep)
+
+    def mix_stream(self, bed, sample_rate: Optional[int] = None, params=None) -> MixStream:
+        """A stream of the live mix stage (ft_codec_mix_stream_begin): the bed is prepared here and stays on the device; the
+        MixStream's pushes concatenate to mix_live() of the whole programme, bit for bit, however they are cut."""
+        rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params)
+        h = C.c_void_p()
+        self._check(self.lib.ft_codec_mix_stream_begin(self._h, rate, items, C.byref(mp), C.byref(h)), "ft_codec_mix_stream_begin")
+        del keep                                           # (begin has prepared the bed: its bytes are no longer read)
+        return MixStream(self, h, mp, rate)
 
     MAX_ITEMS_PER_JOIN = 64       # ft_codec_decode_join
 

@@ -43,6 +43,7 @@ struct ResUnitW { float *a0, *a2; ConvW c7, c1; };
 struct DecBlock { float* a0; ConvW ct; ResUnitW u[3]; int s, cin, cout; };
 
 struct ft_codec_stream;
+struct ft_mix_stream;
 struct CodecState {
     hipStream_t stream = nullptr;
     std::mutex mu;
@@ -117,6 +118,11 @@ struct CodecState {
     int* mx_D = nullptr;
     MixOut* mx_out = nullptr;
     size_t mx_xcap = 0, mx_bedcap = 0, mx_ycap = 0, mx_gcap = 0, mx_actcap = 0, mx_Dcap = 0;
+    // live mix stage (ft_codec_mix_stream_*): the open streams (their device state is freed with the context), and what a
+    // push stages - its samples, the m of the hops it completes, the samples it emits; the buffers grow on need
+    std::vector<ft_mix_stream*> mix_streams;
+    float *ml_x = nullptr, *ml_m = nullptr, *ml_y = nullptr;
+    size_t ml_xcap = 0, ml_mcap = 0, ml_ycap = 0;
     LevelTab* lv_tab = nullptr;
     double* lv_hops = nullptr;
     float *lv_peaks = nullptr, *lv_x = nullptr;
@@ -322,6 +328,7 @@ ft_status codec_create(ft_ctx* ctx) {
 }
 
 static void stream_orphan(ft_codec_stream* sc);
+static void mix_stream_orphan(ft_mix_stream* ms);
 void codec_destroy(ft_ctx* ctx) {
     CodecState* s = ctx->codec;
     if (!s) return;
@@ -330,6 +337,8 @@ void codec_destroy(ft_ctx* ctx) {
     // ft_codec_stream_end (which then only deletes it) and is refused by ft_codec_stream_decode
     for (ft_codec_stream* sc : s->streams) stream_orphan(sc);
     s->streams.clear();
+    for (ft_mix_stream* ms : s->mix_streams) mix_stream_orphan(ms);
+    s->mix_streams.clear();
     for (void* p : s->owned) hipFree(p);
     delete s;
     ctx->codec = nullptr;
@@ -342,6 +351,14 @@ static ft_status cmalloc(ft_ctx* ctx, T** p, size_t n) {
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_NOMEM, std::string("codec hipMalloc: ") + hipGetErrorString(e));
     ctx->codec->owned.push_back(q);
     *p = (T*)q;
+    return FT_OK;
+}
+// A table built on the host, to the device on the codec's own stream and waited for: a copy on the legacy stream is refused
+// while another thread of the process - a stream's generation - captures a graph on a blocking stream.
+static ft_status cupload(ft_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    hipStream_t st = ctx->codec->stream;
+    FT_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
     return FT_OK;
 }
 static float* W32(ft_ctx* ctx, const std::string& n) { return (float*)ctx->expected[n].p; }
@@ -820,7 +837,7 @@ static ft_status rs_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) 
         if (const char* e = chain::rs_design(rate, &t.L, &t.M, &t.K, &w)) return ft_fail(ctx, FT_ERR_ARG, e);
         if (t.K > 0) {
             FT_TRY(cmalloc(ctx, &t.w, w.size()));
-            FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+            FT_TRY(cupload(ctx, t.w, w.data(), w.size() * sizeof(float)));
         }
         it = s->rs_tabs.emplace(rate, t).first;
     }
@@ -861,7 +878,7 @@ static ft_status ts_alloc(ft_ctx* ctx) {
     int* d = nullptr;
     TsSeg* t = nullptr;
     FT_TRY(cmalloc(ctx, &win, (size_t)TS_N));
-    FT_HIP(ctx, hipMemcpy(win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+    FT_TRY(cupload(ctx, win, w.data(), w.size() * sizeof(float)));
     FT_TRY(cmalloc(ctx, &o, cap));
     FT_TRY(cmalloc(ctx, &d, cap / TS_HS + 2));
     FT_TRY(cmalloc(ctx, &t, (size_t)RS_MAX_SEGS));
@@ -883,7 +900,7 @@ static ft_status ps_table(ft_ctx* ctx, int cents, const CodecState::PsTab** out)
         std::vector<float> w;
         if (!chain::ps_design(cents, &t.S, &t.K, &w) || t.K == 0) return ft_fail(ctx, FT_ERR_ARG, "pitch outside [-1200, 1200] cents");
         FT_TRY(cmalloc(ctx, &t.w, w.size()));
-        FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        FT_TRY(cupload(ctx, t.w, w.data(), w.size() * sizeof(float)));
         it = s->ps_tabs.emplace(cents, t).first;
     }
     *out = &it->second;
@@ -2536,7 +2553,7 @@ static ft_status in_table(ft_ctx* ctx, int rate, const CodecState::RsTab** out) 
         if (const char* e = chain::rs_design_in(rate, &t.L, &t.M, &t.K, &w)) return ft_fail(ctx, FT_ERR_ARG, e);
         if (t.K > 0) {
             FT_TRY(cmalloc(ctx, &t.w, w.size()));
-            FT_HIP(ctx, hipMemcpy(t.w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+            FT_TRY(cupload(ctx, t.w, w.data(), w.size() * sizeof(float)));
         }
         it = s->in_tabs.emplace(rate, t).first;
     }
@@ -2700,6 +2717,20 @@ extern "C" ft_status ft_mix_plan(int32_t sample_rate, int64_t n, int64_t lead, i
     return FT_OK;
 }
 
+// T on the device, and the words ft_codec_mix reduces into: uploaded with the first mixed call.
+static ft_status mix_table(ft_ctx* ctx) {
+    CodecState* s = ctx->codec;
+    if (s->mx_T) return FT_OK;
+    std::vector<float> T(chain::MX_MAX_DEPTH + 1);
+    chain::mx_gains(T.data());
+    float* t = nullptr;
+    FT_TRY(cmalloc(ctx, &t, T.size()));
+    FT_TRY(cupload(ctx, t, T.data(), T.size() * sizeof(float)));
+    FT_TRY(cmalloc(ctx, &s->mx_out, (size_t)1));
+    s->mx_T = t;
+    return FT_OK;
+}
+
 extern "C" ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
                                   const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck, ft_mix_info* info) {
     const std::string fn = "ft_codec_mix";
@@ -2741,15 +2772,7 @@ extern "C" ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_
         resample_kernel<<<dim3(gx, 1, 1), RS_THREADS, 0, st>>>(s->rs_seg);
         bedp = s->mx_bed;
     }
-    if (!s->mx_T) {
-        std::vector<float> T(chain::MX_MAX_DEPTH + 1);
-        chain::mx_gains(T.data());
-        float* t = nullptr;
-        FT_TRY(cmalloc(ctx, &t, T.size()));
-        FT_HIP(ctx, hipMemcpy(t, T.data(), T.size() * sizeof(float), hipMemcpyHostToDevice));
-        FT_TRY(cmalloc(ctx, &s->mx_out, (size_t)1));
-        s->mx_T = t;
-    }
+    FT_TRY(mix_table(ctx));
     FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, (size_t)n));
     FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)pl.N));
     FT_TRY(cgrow(ctx, &s->mx_act, &s->mx_actcap, (size_t)pl.Nh));
@@ -2789,6 +2812,318 @@ extern "C" ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_
     memset(info, 0, sizeof *info);
     info->N = pl.N; info->nb = nb; info->Nh = pl.Nh; info->active = out.active;
     info->dmax = out.dmax; info->capped = capped ? 1 : 0; info->pk = pk; info->sg = sg;
+    info->bed = binfo;
+    return FT_OK;
+}
+
+// ---- live mix stage (fishtts_hip.h: "Live mix"; the kernels in codec_kernels.h, the emission and the stream's counters in
+// fx_chain.h).  A stream owns its prepared bed, its two pairs of carries, its per-hop arrays and the four words it reports;
+// a push stages its samples in the context's buffers and ends with one wait, so nothing of a push outlives it.
+static_assert(chain::ML_LA == ML_ATTACK && chain::ML_LR == ML_RELEASE && RS_MAX_RATE / 50 / 4 + 1 <= MX_THREADS &&
+              chain::ML_MAX_FADE == (1LL << 30), "fx_chain.h and codec_kernels.h disagree on the live mix stage");
+static_assert(sizeof(ft_mix_live_info) == 128 && offsetof(ft_mix_live_info, bed) == 48, "ft_mix_live_info layout");
+
+struct ft_mix_stream {
+    ft_ctx* owner = nullptr;          // null once its context is gone (the device state went with it)
+    chain::MlStage st;
+    ft_mix_params mp;
+    int rate = RS_FI;
+    float* bed = nullptr;             // the prepared bed at the output rate, nb samples
+    long long nb = 0, off = 0;
+    ft_intake_info binfo;
+    float *prog[2] = {nullptr, nullptr}, *mc[2] = {nullptr, nullptr};   // the carries: programme, m
+    size_t pcap[2] = {0, 0}, mcap[2] = {0, 0};
+    unsigned char* act = nullptr;     // per hop, whole: they grow on need
+    int *D = nullptr, *need = nullptr, *L = nullptr;
+    float* g = nullptr;
+    size_t hcap = 0;
+    MixLiveOut* out = nullptr;
+    std::vector<void*> owned;
+};
+
+static void mix_stream_orphan(ft_mix_stream* ms) {
+    for (void* v : ms->owned) hipFree(v);
+    ms->owned.clear();
+    ms->owner = nullptr;
+}
+
+template <typename T>
+static ft_status ml_malloc(ft_ctx* ctx, ft_mix_stream* ms, T** p, size_t n) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, (n + 8) * sizeof(T));
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_NOMEM, std::string("mix stream hipMalloc: ") + hipGetErrorString(e));
+    ms->owned.push_back(q);
+    *p = (T*)q;
+    return FT_OK;
+}
+static void ml_free(ft_mix_stream* ms, void* p) {
+    if (!p) return;
+    ms->owned.erase(std::find(ms->owned.begin(), ms->owned.end(), p));
+    hipFree(p);
+}
+// A carry copy the next push writes from its first sample on: nothing of it is kept when it has to be larger.
+static ft_status ml_carry(ft_ctx* ctx, ft_mix_stream* ms, float** p, size_t* cap, size_t need) {
+    if (*p && *cap >= need) return FT_OK;
+    float* q = nullptr;
+    FT_TRY(ml_malloc(ctx, ms, &q, need));
+    ml_free(ms, *p);
+    *p = q;
+    *cap = need;
+    return FT_OK;
+}
+// The per-hop arrays with room for `hops` hops and hops + 1 nodes; what they hold moves along.
+static ft_status ml_hops(ft_ctx* ctx, ft_mix_stream* ms, size_t hops) {
+    if (ms->act && ms->hcap >= hops) return FT_OK;
+    const size_t cap = std::max(hops, std::max((size_t)4096, 2 * ms->hcap)), n = cap + 1;
+    hipStream_t st = ctx->codec->stream;
+    unsigned char* act = nullptr;
+    int *D = nullptr, *need = nullptr, *L = nullptr;
+    float* g = nullptr;
+    FT_TRY(ml_malloc(ctx, ms, &act, n));
+    FT_TRY(ml_malloc(ctx, ms, &D, n));
+    FT_TRY(ml_malloc(ctx, ms, &g, n));
+    FT_TRY(ml_malloc(ctx, ms, &need, n));
+    FT_TRY(ml_malloc(ctx, ms, &L, n));
+    if (ms->act) {
+        const size_t o = ms->hcap + 1;
+        FT_HIP(ctx, hipMemcpyAsync(act, ms->act, o, hipMemcpyDeviceToDevice, st));
+        FT_HIP(ctx, hipMemcpyAsync(D, ms->D, o * sizeof(int), hipMemcpyDeviceToDevice, st));
+        FT_HIP(ctx, hipMemcpyAsync(g, ms->g, o * sizeof(float), hipMemcpyDeviceToDevice, st));
+        FT_HIP(ctx, hipMemcpyAsync(need, ms->need, o * sizeof(int), hipMemcpyDeviceToDevice, st));
+        FT_HIP(ctx, hipMemcpyAsync(L, ms->L, o * sizeof(int), hipMemcpyDeviceToDevice, st));
+        FT_HIP(ctx, hipStreamSynchronize(st));
+        ml_free(ms, ms->act); ml_free(ms, ms->D); ml_free(ms, ms->g); ml_free(ms, ms->need); ml_free(ms, ms->L);
+    }
+    ms->act = act; ms->D = D; ms->g = g; ms->need = need; ms->L = L;
+    ms->hcap = cap;
+    return FT_OK;
+}
+
+static chain::MxArgs ml_args(int rate, int64_t n, const ft_mix_params* mp) {
+    chain::MxArgs a;
+    a.rate = rate; a.n = n; a.bed_loudness = mp->bed_loudness; a.depth = mp->depth; a.threshold = mp->threshold;
+    a.attack = mp->attack; a.release = mp->release; a.lead = mp->lead; a.tail = mp->tail; a.fade_in = mp->fade_in;
+    a.fade_out = mp->fade_out; a.offset = mp->offset; a.loop = mp->loop;
+    return a;
+}
+static chain::MlShape ml_shape(int rate, const ft_mix_params* mp) {
+    chain::MlShape sh;
+    sh.H = chain::mx_hop(rate); sh.Wa = mp->attack; sh.lead = mp->lead; sh.tail = mp->tail; sh.fade_out = mp->fade_out;
+    return sh;
+}
+
+extern "C" ft_status ft_mix_live_plan(int32_t sample_rate, const ft_mix_params* mp, int64_t n_in, int32_t final, int64_t* n_out,
+                                      int64_t* nodes) {
+    if (!mp) return FT_ERR_ARG;
+    bool too_long = false;
+    if (chain::mx_check(ml_args(sample_rate, n_in, mp), &too_long, 0)) return too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG;
+    const chain::MlPlan p = chain::ml_plan(ml_shape(sample_rate, mp), n_in, final != 0);
+    if (n_out) *n_out = p.done;
+    if (nodes) *nodes = p.limits;
+    return FT_OK;
+}
+
+static void ml_end(ft_ctx* ctx, ft_mix_stream* ms) {   // (s->mu held)
+    CodecState* s = ctx->codec;
+    hipStreamSynchronize(s->stream);
+    for (void* v : ms->owned) hipFree(v);
+    ms->owned.clear();
+    for (size_t i = 0; i < s->mix_streams.size(); ++i)
+        if (s->mix_streams[i] == ms) { s->mix_streams.erase(s->mix_streams.begin() + (long)i); break; }
+    delete ms;
+}
+
+// The stream of a call whose values mx_check has passed (s->mu held): the bed prepared - its own checks come before its
+// first device work - and kept, the state allocated.
+static ft_status ml_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* bed, const ft_mix_params* mp,
+                          ft_mix_stream** out) {
+    CodecState* s = ctx->codec;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, rate, 100, 0, &d));
+    ft_intake_item item = *bed;
+    item.channel = mp->channel;
+    const ft_join_params whole = {0.f, 1, 0, 0};
+    int64_t nb44 = 0;
+    ft_intake_info binfo;
+    FT_TRY(intake_run(ctx, fn, 1, &item, &whole, mp->bed_loudness, false, nullptr, nullptr, INT64_MAX, &nb44, &binfo, true));
+    if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
+    hipStream_t st = s->stream;
+    FT_TRY(rs_table(ctx, rate, &d.rs));
+    FT_TRY(mix_table(ctx));
+    const int64_t nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
+    ft_mix_stream* ms = new ft_mix_stream();
+    ms->owner = ctx;
+    ms->mp = *mp;
+    ms->rate = rate;
+    ms->nb = nb;
+    ms->off = mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
+    ms->binfo = binfo;
+    ms->st = chain::MlStage::fresh(ml_shape(rate, mp));
+    s->mix_streams.push_back(ms);
+    RsSeg g;                                          // (read by an asynchronous copy: alive until the wait below)
+    ft_status r = ml_malloc(ctx, ms, &ms->bed, (size_t)nb);
+    if (r == FT_OK) r = ml_malloc(ctx, ms, &ms->out, (size_t)1);
+    if (r == FT_OK) r = ml_hops(ctx, ms, 1);
+    for (int c = 0; c < 2 && r == FT_OK; ++c) {
+        r = ml_carry(ctx, ms, &ms->prog[c], &ms->pcap[c], 4);
+        if (r == FT_OK) r = ml_carry(ctx, ms, &ms->mc[c], &ms->mcap[c], 4);
+    }
+    if (r == FT_OK && d.K > 0 && !s->rs_seg) r = cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS);
+    hipError_t e = hipSuccess;
+    if (r == FT_OK) {
+        if (d.K > 0) {                                // to the output rate: the whole clip from zero state in one final call
+            g = RsSeg{s->join_out, d.rs->w, nullptr, nullptr, ms->bed, 0, 0, (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
+            e = hipMemcpyAsync(s->rs_seg, &g, sizeof g, hipMemcpyHostToDevice, st);
+            const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
+            if (e == hipSuccess) resample_kernel<<<dim3(gx, 1, 1), RS_THREADS, 0, st>>>(s->rs_seg);
+        } else {
+            e = hipMemcpyAsync(ms->bed, s->join_out, (size_t)nb * sizeof(float), hipMemcpyDeviceToDevice, st);
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(ms->out, 0, sizeof(MixLiveOut), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
+    }
+    if (r != FT_OK) {
+        ml_end(ctx, ms);
+        return r;
+    }
+    *out = ms;
+    return FT_OK;
+}
+
+// One push (s->mu held).  Everything is judged first; the stream's counters move only when the launches went through.
+static ft_status ml_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, const float* x, int64_t n, bool final, float* y,
+                         int64_t capacity, int64_t* n_out) {
+    CodecState* s = ctx->codec;
+    chain::MlStage& stg = ms->st;
+    if (stg.ended) return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream has had its final push");
+    if (n < 0 || (!x && n > 0) || !n_out) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    if (n > chain::MX_MAX_N || stg.s.lead + stg.nin + n + stg.s.tail > chain::MX_MAX_N)
+        return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": lead + n + tail exceeds 2^28 samples");
+    const chain::MlPlan pl = stg.plan(n, final);
+    if (capacity < pl.out || (!y && pl.out > 0)) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below what the push emits");
+    const int H = stg.s.H, w = stg.par ^ 1;
+    const long long F0 = stg.s.lead + stg.nin, mend0 = stg.mixed * H, mend1 = final ? pl.N : pl.mixed * H;
+    hipStream_t st = s->stream;
+    FT_TRY(ml_hops(ctx, ms, (size_t)pl.hops + 1));
+    FT_TRY(ml_carry(ctx, ms, &ms->prog[w], &ms->pcap[w], (size_t)(pl.F - pl.base) + 4));
+    FT_TRY(ml_carry(ctx, ms, &ms->mc[w], &ms->mcap[w], (size_t)(mend1 - pl.done) + 4));
+    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, (size_t)n + 8));
+    FT_TRY(cgrow(ctx, &s->ml_m, &s->ml_mcap, (size_t)(mend1 - mend0) + 8));
+    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, (size_t)pl.out + 8));
+    MixLiveP p;
+    memset(&p, 0, sizeof p);
+    p.m.x = s->ml_x; p.m.bed = ms->bed; p.m.T = s->mx_T; p.m.act = ms->act; p.m.D = ms->D; p.m.g = ms->g; p.m.y = s->ml_m;
+    p.m.nb = ms->nb; p.m.off = ms->off;
+    p.m.N = final ? (int)pl.N : 1 << 30;
+    p.m.lead = (int)stg.s.lead; p.m.H = H; p.m.depth = ms->mp.depth; p.m.Wa = ms->mp.attack; p.m.Wr = ms->mp.release;
+    p.m.f_in = (int)std::min(ms->mp.fade_in, (int64_t)chain::ML_MAX_FADE);
+    p.m.f_out = final ? (int)std::min(ms->mp.fade_out, (int64_t)chain::ML_MAX_FADE) : 0;
+    p.m.loop = ms->mp.loop; p.m.thr = ms->mp.threshold;
+    p.pin = ms->prog[stg.par]; p.pout = ms->prog[w]; p.cin = ms->mc[stg.par]; p.cout = ms->mc[w];
+    p.y = s->ml_y; p.need = ms->need; p.L = ms->L; p.out = ms->out;
+    p.F0 = (int)F0; p.F1 = (int)pl.F; p.cb0 = (int)stg.base; p.cb1 = (int)pl.base;
+    p.h0 = (int)stg.hops; p.h1 = (int)pl.hops; p.kd0 = (int)stg.ducks; p.kd1 = (int)pl.ducks;
+    p.q0 = (int)stg.mixed; p.q1 = (int)pl.mixed; p.kl0 = (int)stg.limits; p.kl1 = (int)pl.limits;
+    p.out0 = (int)stg.done; p.out1 = (int)pl.done;
+    p.mend1 = (int)mend1;
+    p.Nend = final ? (int)pl.N : 1 << 30;
+    p.xb = p.F0 & ~3; p.pib = p.cb0 & ~3; p.pob = p.cb1 & ~3; p.mb = (int)mend0 & ~3; p.cib = p.out0 & ~3; p.cob = p.out1 & ~3;
+    p.cf = (float)chain::lv_ceiling();
+    if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->ml_x + (p.F0 - p.xb), x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    const int W = MX_THREADS / 64;
+    if (p.h1 > p.h0) mixl_hop_kernel<<<(unsigned)((p.h1 - p.h0 + W - 1) / W), MX_THREADS, 0, st>>>(p);
+    if (p.kd1 > p.kd0) mixl_node_kernel<<<(unsigned)((p.kd1 - p.kd0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
+    if (p.q1 > p.q0) mixl_sample_kernel<<<(unsigned)(p.q1 - p.q0), MX_THREADS, 0, st>>>(p);
+    if (p.kl1 > p.kl0) mixl_limit_kernel<<<(unsigned)((p.kl1 - p.kl0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
+    const long long work = std::max((long long)pl.out, std::max(mend1 - pl.done, pl.F - pl.base));
+    if (work > 0) mixl_apply_kernel<<<(unsigned)std::min(4096LL, (work + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
+    if (pl.out > 0) FT_HIP(ctx, hipMemcpyAsync(y, s->ml_y, (size_t)pl.out * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("live mix launch: ") + hipGetErrorString(e));
+    stg.commit(pl);
+    *n_out = pl.out;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_mix_stream_begin(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed, const ft_mix_params* mp,
+                                               ft_mix_stream** out) {
+    const std::string fn = "ft_codec_mix_stream_begin";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!bed || !mp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    bool too_long = false;
+    if (const char* why = chain::mx_check(ml_args(sample_rate, 0, mp), &too_long, 0))
+        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    return ml_begin(ctx, fn, sample_rate, bed, mp, out);
+}
+
+extern "C" ft_status ft_codec_mix_stream_push(ft_mix_stream* ms, const float* x, int64_t n, int32_t final, float* y, int64_t capacity,
+                                              int64_t* n_out) {
+    if (!ms) return FT_ERR_ARG;
+    ft_ctx* ctx = ms->owner;
+    if (!ctx || !ctx->codec) return FT_ERR_STATE;      // its context was destroyed
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    return ml_push(ctx, "ft_codec_mix_stream_push", ms, x, n, final != 0, y, capacity, n_out);
+}
+
+extern "C" void ft_codec_mix_stream_end(ft_mix_stream* ms) {
+    if (!ms) return;
+    ft_ctx* own = ms->owner;
+    if (own && own->codec) {
+        std::lock_guard<std::mutex> lock(own->codec->mu);
+        hipSetDevice(own->device);
+        ml_end(own, ms);
+        return;
+    }
+    delete ms;
+}
+
+extern "C" ft_status ft_codec_mix_live(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
+                                       const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck,
+                                       int32_t* limit, ft_mix_live_info* info) {
+    const std::string fn = "ft_codec_mix_live";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if ((!x && n != 0) || !bed || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    bool too_long = false;
+    if (const char* why = chain::mx_check(ml_args(sample_rate, n, mp), &too_long, 0))
+        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    const chain::MlPlan pl = chain::ml_plan(ml_shape(sample_rate, mp), n, true);
+    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    ft_mix_stream* ms = nullptr;
+    FT_TRY(ml_begin(ctx, fn, sample_rate, bed, mp, &ms));
+    int64_t got = 0;
+    ft_status r = ml_push(ctx, fn, ms, x, n, true, y, capacity, &got);
+    MixLiveOut out;
+    memset(&out, 0, sizeof out);
+    hipError_t e = hipSuccess;
+    if (r == FT_OK) {
+        const size_t nn = (size_t)pl.hops + 1;
+        hipStream_t st = s->stream;
+        e = hipMemcpyAsync(&out, ms->out, sizeof out, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && duck) e = hipMemcpyAsync(duck, ms->D, nn * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && limit) e = hipMemcpyAsync(limit, ms->L, nn * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
+    }
+    const long long nb = ms->nb;
+    const ft_intake_info binfo = ms->binfo;
+    ml_end(ctx, ms);
+    FT_TRY(r);
+    *total = got;
+    memset(info, 0, sizeof *info);
+    info->N = pl.N; info->nb = nb; info->Nh = pl.hops; info->active = out.active;
+    info->dmax = out.dmax; info->lmax = out.lmax;
+    memcpy(&info->qmax, &out.qmax, sizeof(float));
     info->bed = binfo;
     return FT_OK;
 }

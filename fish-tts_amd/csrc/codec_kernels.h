@@ -2450,4 +2450,204 @@ static __global__ __launch_bounds__(MX_THREADS) void mix_scale_kernel(float* y, 
     if (blockIdx.x == 0 && 4 * N4 + (int)threadIdx.x < N) y[4 * N4 + threadIdx.x] = __fmul_rn(y[4 * N4 + threadIdx.x], sg);
 }
 
+// ---- live mix stage (ft_codec_mix_stream_*, ft_codec_mix_live; stated in fishtts_hip.h under "Live mix"): the mix stage on a
+// stream.  A push brings the programme samples of timeline [F0, F1); the stream carries the programme from cb0 on (pin) and the
+// m of [out0, q0 H) that did not go out yet (cin), and the push writes both carries anew for its successor (pout from cb1,
+// cout from out1).  Every sample buffer is laid out by the sample's timeline index minus a multiple of four (xb, pib, pob,
+// mb, cib, cob: the first index rounded down), so a group of four samples that starts at a multiple of four lies on a
+// 16-byte boundary in every one of them.  The per-hop arrays (act, D, g, need, L) are whole and indexed absolutely.  Five
+// launches per push, whatever its size; a launch whose range is empty is left out:
+//   mixl_hop_kernel     one wave per hop of [h0, h1): the activity flag, as mix_hop_kernel.  A sample comes from the carry
+//                       or from the push: the lane picks the buffer and clamps the index, loads once and then selects
+//                       between the value and zero - no branch per sample
+//   mixl_node_kernel    one lane per duck node of [kd0, kd1): D_k and g_k from the flags of the workgroup's window in LDS,
+//                       as mix_node_kernel (only hops below h1 exist so far)
+//   mixl_sample_kernel  one workgroup per hop of [q0, q1), one group of four samples per lane (a hop has at most 960
+//                       samples): mix_sample over the hop with 16-byte loads where a whole group lies in one buffer and
+//                       16-byte stores of the whole groups; the hop's peak Q_h reduced in the workgroup; lane 0 then finds
+//                       need_h by binary search over T
+//   mixl_limit_kernel   one lane per limiter node of [kl0, kl1): L_k from the 30 hops around it
+//   mixl_apply_kernel   y over [out0, out1), then the two carries rolled
+// The integers a stream reports are kept in MixLiveOut by integer atomics, so no sum or max depends on an order.
+struct MixLiveOut { unsigned int qmax; int active, dmax, lmax; };
+struct MixLiveP {
+    MixP m;                    // bed, T, act, D, g, nb, off, lead, H, depth, Wa, Wr, f_in, loop, thr as ft_codec_mix fills them;
+                               // x: the push's samples; y: the m of hops [q0, q1); N, f_out: the timeline's once it has ended,
+                               // else 2^30 and 0 (no sample that is final before the end lies in the fade-out)
+    const float* pin;          // programme carry read: timeline [cb0, F0)
+    float* pout;               // programme carry written: [cb1, F1)
+    const float* cin;          // m carry read: [out0, q0 H)
+    float* cout;               // m carry written: [out1, mend1)
+    float* y;                  // out: [out0, out1)
+    int* need;                 // [hops]
+    int* L;                    // [hops + 1]
+    MixLiveOut* out;
+    int F0, F1, cb0, cb1;      // the push's samples; the first programme sample carried in, out
+    int h0, h1, kd0, kd1, q0, q1, kl0, kl1, out0, out1;
+    int mend1;                 // the end of the m known after the push: q1 H (at the end of the stream out1 = N: nothing rolls)
+    int Nend;                  // samples that exist: N once the stream has ended, else 2^30
+    int xb, pib, pob, mb, cib, cob;
+    float cf;                  // (float) 10^(-1/20)
+};
+constexpr int ML_ATTACK = 5, ML_RELEASE = 25;
+
+// s[i] for any i: the carry below F0, the push from there, zero outside [cb0, F1) - the lead, and the tail once it exists.
+__device__ inline float mixl_prog(const MixLiveP& p, int i) {
+    const bool old = i < p.F0;
+    const float* src = old ? p.pin : p.m.x;
+    const int lo = old ? p.cb0 : p.F0, hi = old ? p.F0 : p.F1, ab = old ? p.pib : p.xb;
+    const int ic = min(max(i, lo), max(hi - 1, lo));       // (an empty range: lo, inside the buffer's margin)
+    const float v = src[ic - ab];
+    return i >= lo && i < hi ? v : 0.f;
+}
+
+// m[i] for i in [out0, mend1): the carry below q0 H, the push's hops from there.
+__device__ inline float mixl_m(const MixLiveP& p, int i, int mend0) {
+    const bool old = i < mend0;
+    const float* src = old ? p.cin : p.m.y;
+    const int lo = old ? p.out0 : mend0, hi = old ? mend0 : p.mend1, ab = old ? p.cib : p.mb;
+    const int ic = min(max(i, lo), max(hi - 1, lo));
+    return src[ic - ab];
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mixl_hop_kernel(MixLiveP p) {
+    const int lane = threadIdx.x & 63, h = p.h0 + blockIdx.x * (MX_THREADS / 64) + (threadIdx.x >> 6);
+    __shared__ int cnt[MX_THREADS / 64];
+    int on = 0;
+    if (h < p.h1) {
+        const int i0 = h * p.m.H, i1 = min(p.Nend, i0 + p.m.H);
+        float pk = -1.f;                                   // (as mix_hop_kernel: a hop of NaNs stays below any threshold)
+        for (int i = i0 + lane; i < i1; i += 64) pk = fmaxf(pk, fabsf(mixl_prog(p, i)));
+        for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o));
+        on = pk >= p.m.thr;
+        if (lane == 0) p.m.act[h] = (unsigned char)on;
+    }
+    if (lane == 0) cnt[threadIdx.x >> 6] = on;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int w = 0; w < MX_THREADS / 64; ++w) c += cnt[w];
+        if (c > 0) atomicAdd(&p.out->active, c);
+    }
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mixl_node_kernel(MixLiveP p) {
+    __shared__ unsigned char win[MX_THREADS + 2 * MX_MAX_WIN];
+    __shared__ int wmax[MX_THREADS / 64];
+    const int Wa = p.m.Wa, Wr = p.m.Wr;
+    const int k0 = p.kd0 + blockIdx.x * MX_THREADS, lo = k0 - Wr, span = MX_THREADS + Wa + Wr;   // win[j] = act[lo + j]
+    for (int j = threadIdx.x; j < span; j += MX_THREADS) {
+        const int h = lo + j;
+        win[j] = h >= 0 && h < p.h1 ? p.m.act[h] : 0;
+    }
+    __syncthreads();
+    const int k = k0 + threadIdx.x;
+    int d = 0;
+    if (k < p.kd1) {
+        const unsigned char* w = win + (k - lo);           // w[j] = act[k + j]
+        for (int j = 0; j < Wa; ++j)
+            if (w[j]) { d = (int)((long long)p.m.depth * (Wa - j) / Wa); break; }
+        for (int j = 0; j < Wr; ++j)
+            if (w[-1 - j]) { d = max(d, (int)((long long)p.m.depth * (Wr - j) / Wr)); break; }
+        p.m.D[k] = d;
+        p.m.g[k] = p.m.T[d];
+    }
+    for (int o = 32; o > 0; o >>= 1) d = max(d, __shfl_xor(d, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < MX_THREADS / 64; ++w) d = max(d, wmax[w]);
+        if (d > 0) atomicMax(&p.out->dmax, d);
+    }
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mixl_sample_kernel(MixLiveP p) {
+    __shared__ float wpk[MX_THREADS / 64];
+    const int h = p.q0 + blockIdx.x, i0 = h * p.m.H, i1 = min(i0 + p.m.H, p.Nend);
+    const int i = (i0 & ~3) + 4 * (int)threadIdx.x;       // this lane's group: [i, i + 4), cut to the hop
+    float pk = 0.f;
+    if (i < i1) {
+        const bool whole = i >= i0 && i + 3 < i1;
+        float4 s, t;
+        if (whole && i >= p.F0 && i + 3 < p.F1) s = *(const float4*)(p.m.x + (i - p.xb));
+        else if (whole && i >= p.cb0 && i + 3 < p.F0) s = *(const float4*)(p.pin + (i - p.pib));
+        else s = make_float4(mixl_prog(p, i), mixl_prog(p, i + 1), mixl_prog(p, i + 2), mixl_prog(p, i + 3));
+        long long j = (long long)i + p.m.off;
+        if (p.m.loop) j %= p.m.nb;
+        if ((j & 3) == 0 && j + 3 < p.m.nb) t = *(const float4*)(p.m.bed + j);
+        else t = make_float4(mix_bed(p.m, j), mix_bed(p.m, j + 1), mix_bed(p.m, j + 2), mix_bed(p.m, j + 3));
+        if (whole) {
+            float4 m;
+            m.x = mix_sample(p.m, i, s.x, t.x);
+            m.y = mix_sample(p.m, i + 1, s.y, t.y);
+            m.z = mix_sample(p.m, i + 2, s.z, t.z);
+            m.w = mix_sample(p.m, i + 3, s.w, t.w);
+            *(float4*)(p.m.y + (i - p.mb)) = m;
+            pk = fmaxf(fmaxf(fabsf(m.x), fabsf(m.y)), fmaxf(fabsf(m.z), fabsf(m.w)));   // (fmaxf passes a NaN by)
+            pk = fmaxf(pk, 0.f);
+        } else {                                           // the hop's first and last group: the samples inside it
+            const float sv[4] = {s.x, s.y, s.z, s.w}, tv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (i + c >= i0 && i + c < i1) {
+                    const float m = mix_sample(p.m, i + c, sv[c], tv[c]);
+                    p.m.y[i + c - p.mb] = m;
+                    pk = fmaxf(pk, fabsf(m));
+                }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o));
+    if ((threadIdx.x & 63) == 0) wpk[threadIdx.x >> 6] = pk;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < MX_THREADS / 64; ++w) pk = fmaxf(pk, wpk[w]);
+        // need_h: the smallest d with T[d] Q <= cf (T falls with d, so the test is monotone), 6000 when there is none
+        int lo = 0, hi = 6000;
+        if (__fmul_rn(p.m.T[hi], pk) <= p.cf)
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (__fmul_rn(p.m.T[mid], pk) <= p.cf) hi = mid;
+                else lo = mid + 1;
+            }
+        p.need[h] = hi;
+        if (pk > 0.f) atomicMax(&p.out->qmax, __float_as_uint(pk));
+    }
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mixl_limit_kernel(MixLiveP p) {
+    __shared__ int wmax[MX_THREADS / 64];
+    const int k = p.kl0 + blockIdx.x * MX_THREADS + threadIdx.x;
+    int l = 0;
+    if (k < p.kl1) {
+        for (int j = 0; j < ML_ATTACK; ++j) {              // hops k .. k + La - 1
+            const int h = k + j;
+            if (h < p.q1) l = max(l, (int)((long long)p.need[h] * (ML_ATTACK - j) / ML_ATTACK));
+        }
+        for (int j = 0; j < ML_RELEASE; ++j) {             // hops k - 1 .. k - Lr
+            const int h = k - 1 - j;
+            if (h >= 0 && h < p.q1) l = max(l, (int)((long long)p.need[h] * (ML_RELEASE - j) / ML_RELEASE));
+        }
+        p.L[k] = l;
+    }
+    for (int o = 32; o > 0; o >>= 1) l = max(l, __shfl_xor(l, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = l;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < MX_THREADS / 64; ++w) l = max(l, wmax[w]);
+        if (l > 0) atomicMax(&p.out->lmax, l);
+    }
+}
+
+static __global__ __launch_bounds__(MX_THREADS) void mixl_apply_kernel(MixLiveP p) {
+    const int step = gridDim.x * MX_THREADS, t = blockIdx.x * MX_THREADS + threadIdx.x, H = p.m.H, mend0 = p.q0 * H;
+    const float Hf = (float)H;
+    for (int i = p.out0 + t; i < p.out1; i += step) {
+        const int k = (int)((unsigned int)i / (unsigned int)H);
+        const float lk = p.m.T[p.L[k]], r = __fdiv_rn((float)(i - k * H), Hf);
+        p.y[i - p.out0] = __fmul_rn(mixl_m(p, i, mend0), fmaf(r, p.m.T[p.L[k + 1]] - lk, lk));
+    }
+    for (int i = p.out1 + t; i < p.mend1; i += step) p.cout[i - p.cob] = mixl_m(p, i, mend0);
+    for (int i = p.cb1 + t; i < p.F1; i += step) p.pout[i - p.pob] = mixl_prog(p, i);
+}
+
 }  // namespace ft

@@ -2,7 +2,8 @@
 // time-scale stage, then the pitch stage, then the resampler, then the level (whole items) or the ride stage (streams).  The filter designs, the rule that accepts a
 // (speed, cents) pair, what each stage can emit after so many input samples, the bookkeeping of a stream's three stages from
 // call to call, and the level stage's K-weighting design, gates and gain; behind the join, the mix stage's timeline, checks,
-// duck and gain table (mx_*; tools/mix_check.cpp drives that block).
+// duck and gain table (mx_*; tools/mix_check.cpp drives that block) and the live mix stage's emission (ml_*, MlStage;
+// tools/mix_live_check.cpp).
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
 // are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
@@ -289,11 +290,12 @@ struct MxArgs {
     long long lead = 0, tail = 0, fade_in = 0, fade_out = 0, offset = 0;
     int loop = 0;
 };
-inline const char* mx_check(const MxArgs& a, bool* too_long) {
+// (min_n: 1 for the mix stage; 0 for the live mix stage, whose programme may be empty)
+inline const char* mx_check(const MxArgs& a, bool* too_long, long long min_n = 1) {
     int L, M, K;
     *too_long = false;
     if (const char* e = rs_design(a.rate, &L, &M, &K, nullptr)) return e;
-    if (a.n < 1) return "n must be at least 1";
+    if (a.n < min_n) return min_n >= 1 ? "n must be at least 1" : "n must be >= 0";
     if (!lv_ok(a.bed_loudness)) return "bed_loudness neither 0 nor in [-5000, -500] hundredths of a LUFS";
     if (a.depth < 0 || a.depth > MX_MAX_DEPTH) return "depth outside [0, 6000] hundredths of a dB";
     if (!(a.threshold >= 0.f)) return "threshold must be >= 0";   // (refuses a NaN too)
@@ -330,6 +332,68 @@ inline void mx_duck(const unsigned char* act, long long Nh, int depth, int Wa, i
 inline void mx_gains(float* T) {
     for (int d = 0; d <= MX_MAX_DEPTH; ++d) T[d] = (float)std::pow(10.0, -(double)d / 2000.0);
 }
+
+// ---- live mix stage (mixl_*_kernel; fishtts_hip.h states it under "Live mix"): the mix stage on a stream, the one gain of
+// its ceiling replaced by a look-ahead limiter over the hops' own peaks.  What is final after n_in programme samples - hops
+// with their activity, duck nodes, hops with their m and Q, limiter nodes, outputs - in closed form (ml_plan), and the stage
+// that walks a stream from push to push (MlStage; tools/mix_live_check.cpp drives both).
+constexpr int ML_LA = 5, ML_LR = 25;                 // the limiter's attack and release, hops
+constexpr long long ML_MAX_FADE = 1LL << 30;         // a fade counts as this at most: longer than any timeline (MX_MAX_N)
+struct MlShape { int H = 1, Wa = 1; long long lead = 0, tail = 0, fade_out = 0; };
+// Totals after n_in programme samples: F = lead + n_in; hops [0, hops) have their activity, nodes [0, ducks) their D_k, hops
+// [0, mixed) their m and Q, nodes [0, limits) their L_k, samples [0, done) went out; the programme is carried from timeline
+// sample `base` on.  in / out: what the call that led here took and emitted (MlStage::plan).
+struct MlPlan { long long in = 0, out = 0, F = 0, N = 0, hops = 0, ducks = 0, mixed = 0, limits = 0, done = 0, base = 0; bool final = false; };
+inline MlPlan ml_plan(const MlShape& s, long long n_in, bool final) {
+    MlPlan p;
+    p.final = final;
+    p.F = s.lead + n_in;
+    p.N = p.F + s.tail;
+    if (final) {
+        p.hops = p.mixed = (p.N + s.H - 1) / s.H;
+        p.ducks = p.limits = p.hops + 1;
+        p.done = p.N;
+        p.base = p.F;
+        return p;
+    }
+    const long long W = p.F / s.H, E = p.N - std::min(s.fade_out, ML_MAX_FADE);
+    p.hops = W;
+    p.ducks = std::max(0LL, W - s.Wa + 1);
+    p.mixed = std::min(std::max(0LL, W - s.Wa), std::max(0LL, E) / s.H);
+    p.limits = std::max(0LL, p.mixed - ML_LA + 1);
+    p.done = std::max(0LL, p.mixed - ML_LA) * s.H;
+    p.base = std::min(std::max(p.mixed * s.H, s.lead), p.F);
+    return p;
+}
+// A stream of the stage.  The counters live here, on the host; on the device the stream carries the programme from `base` on
+// and the m of [done, mixed H), two copies each (a push reads carry[par] and writes carry[par ^ 1]).
+struct MlStage {
+    MlShape s;
+    int par = 0;
+    bool ended = false;                        // the final push went through
+    long long nin = 0, hops = 0, ducks = 0, mixed = 0, limits = 0, done = 0, base = 0;
+    static MlStage fresh(const MlShape& shape) {
+        MlStage m;
+        m.s = shape;
+        m.base = shape.lead;                   // nothing carried: the programme begins at `lead`
+        return m;
+    }
+    MlPlan plan(long long n, bool final) const {
+        MlPlan p = ml_plan(s, nin + n, final);
+        p.in = n;
+        p.out = p.done - done;
+        return p;
+    }
+    // carried after the call: programme samples, below (Wa + 2) H + max(0, fade_out - tail), and samples of m, at most ML_LA H
+    long long held_prog(const MlPlan& p) const { return p.F - p.base; }
+    long long held_mix(const MlPlan& p) const { return p.final ? 0 : p.mixed * s.H - p.done; }
+    long long held(const MlPlan& p) const { return held_prog(p) + held_mix(p); }
+    void commit(const MlPlan& p) {
+        nin += p.in; hops = p.hops; ducks = p.ducks; mixed = p.mixed; limits = p.limits; done = p.done; base = p.base;
+        ended = p.final;
+        par ^= 1;
+    }
+};
 
 // ---- the stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;
 // plan() says how many (nothing changes), the caller builds the stage's segment from the record and the plan, and commit()

@@ -168,13 +168,16 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None)
     return audio, cuts
 
 
-def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cuts=None) -> Iterator[bytes]:
+def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cuts=None, live_bed=None) -> Iterator[bytes]:
     """The int16 PCM chunks of the segments as they become ready in order: serve_(srv) -> (takes, release) through an open
     BatchServer srv = server() - asked at the first next(), so a stream made before a server opens and read while it is
     open joins its batch - else generate_(emit, stopped) on a thread of its own; every ready run decoded and joined as one
     group (longform.ready_prefixes, decode_join with `started`).  on_cuts(first, cuts): what the join kept of the group that
     starts at segment `first`, before its chunk goes out.  Abandoning the generator sets stopped() and cancels the open
-    requests."""
+    requests.  `live_bed`: (clip, mix.MixParams) - every joined group then goes through a stream of the live mix stage
+    (vocoder.mix_stream, opened at the first next()) under the same lock as its decode_join: what an empty push emits - the
+    bed alone, where `lead` is longer than the stage holds back - goes out before any group, then what each group's push
+    emits, then what the final push leaves; the stream is closed when the generator ends or is abandoned."""
     import numpy as np
 
     from .longform import ready_prefixes
@@ -204,24 +207,44 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
         except BaseException as e:  # noqa: BLE001
             q.put(e)
 
+    def pcm(audio) -> bytes:
+        return (np.clip(audio, -1.0, 1.0) * 32767).astype(np.int16).tobytes()   # the WAV's samples
+
     feeder = threading.Thread(target=feed_own if srv is None else feed_served, daemon=True)
     feeder.start()
     started = False
+    mixer = None
     try:
+        if live_bed is not None:
+            with lock:
+                mixer = vocoder.mix_stream(live_bed[0], sample_rate=plan.rate, params=live_bed[1])
+                head = mixer.push(None)
+            if len(head):
+                yield pcm(head)
         for first, group in ready_prefixes(q, len(plan.texts)):
             end = first + len(group)
             with lock:
                 audio, cuts = vocoder.decode_join(group, params=plan.jp, gaps=plan.gaps[first:end], started=started,
                                                   **plan.fx_of(first, end))
+                out = audio if mixer is None or not len(audio) else mixer.push(audio)
             if on_cuts is not None:
                 on_cuts(first, cuts)
             if len(audio):
                 started = True
-                yield (np.clip(audio, -1.0, 1.0) * 32767).astype(np.int16).tobytes()   # the WAV's samples
+            if len(out):
+                yield pcm(out)
+        if mixer is not None and started:
+            with lock:
+                rest = mixer.push(None, final=True)
+            if len(rest):
+                yield pcm(rest)
     finally:
         stop.set()
         if release is not None:
             release(cancel=True)
         feeder.join()
+        if mixer is not None:
+            with lock:
+                mixer.close()
     if not started:
         raise RuntimeError("No audio generated")

@@ -602,20 +602,25 @@ class FishTTS:
                                pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                                max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                                speed: Optional[float] = None, pitch: Optional[float] = None,
-                               loudness: Optional[float] = None, bed=None) -> Iterator[bytes]:
+                               loudness: Optional[float] = None, bed=None, live_bed=None) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
         chunks concatenate to synthesize_long's PCM byte for byte - with `loudness` too: a group holds whole segments, and
         each is levelled on its own.  No empty chunk is yielded.  The arguments are checked
         here, at the call; generation holds _gen_lock on its own thread and stops within one burst when the generator is
-        abandoned.  `bed` is refused (ValueError): see _no_streamed_bed."""
+        abandoned.  `bed` is refused (ValueError): see _no_streamed_bed.  `live_bed` (a mix.Bed): the bed under the stream -
+        every joined group goes through a stream of the live mix stage (CodecHipEngine.mix_stream), which holds the piece
+        under -1 dBFS with a look-ahead limiter instead of bed='s one gain and holds back under half a second; with a `lead`
+        longer than that the music starts while the first sentence is still generating.  The chunks then concatenate to
+        CodecHipEngine.mix_live over the plain stream's audio.  Its values are checked here, as bed='s are."""
         from . import segments
-        _no_streamed_bed(bed, "synthesize_long_stream")
+        _no_streamed_bed(bed, "synthesize_long_stream", live_bed)
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
                                loudness)
+        mixed = self._bed_args(live_bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed))
+        return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed), live_bed=mixed)
 
     # ------------------------------------------------------------------ music bed (extension)
     def _bed_args(self, bed, rate: int, silence_db=None):
@@ -734,21 +739,23 @@ class FishTTS:
                                  line_pause: float = 0.4, silence_db: Optional[float] = -45.0, max_chars: int = 200,
                                  min_chars: int = 24, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                                  pitch: Optional[float] = None, loudness: Optional[float] = None,
-                                 marks: Optional[list] = None, bed=None) -> Iterator[bytes]:
+                                 marks: Optional[list] = None, bed=None, live_bed=None) -> Iterator[bytes]:
         """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
         (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
         byte for byte; no empty chunk is yielded.  `marks` fills as groups go out: a line's entry is added once its last
         segment went out, and in the end the list is synthesize_script's.  The arguments are checked here, at the call.
-        `bed` is refused (ValueError): see _no_streamed_bed."""
+        `bed` is refused (ValueError): see _no_streamed_bed.  `live_bed` (a mix.Bed): as synthesize_long_stream's; `marks`
+        then count from the start of the mixed piece (the join's marks plus the bed's `lead` in samples)."""
         from . import segments
         from .script import line_marks
-        _no_streamed_bed(bed, "synthesize_script_stream")
+        _no_streamed_bed(bed, "synthesize_script_stream", live_bed)
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
                                  min_chars, sample_rate, speed, pitch, loudness, marks)
+        mixed = self._bed_args(live_bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         found = [None] * plan.n_lines
-        state = {"at": 0, "started": False, "told": 0}
+        state = {"at": 0 if mixed is None else mixed[1].lead, "started": False, "told": 0}
 
         def on_cuts(first, cuts) -> None:
             end = first + len(cuts)
@@ -759,7 +766,7 @@ class FishTTS:
             state["told"] = max(state["told"], done)
 
         return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed),
-                                    on_cuts=None if marks is None else on_cuts)
+                                    on_cuts=None if marks is None else on_cuts, live_bed=mixed)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
@@ -1043,12 +1050,16 @@ def _check_sampling(temperature: float, top_p: float, repetition_penalty: float)
     assert 0 < temperature < 2, "temperature must be in (0, 2)"
 
 
-def _no_streamed_bed(bed, what: str) -> None:
-    """A stream takes no bed: the mix stage holds the whole piece under the -1 dBFS ceiling with ONE gain, known only when
-    the last sample is (as `loudness=` was before `live_loudness=`); a streamed form is not built yet."""
+def _no_streamed_bed(bed, what: str, live_bed=None) -> None:
+    """A stream takes no `bed=`: the mix stage holds the whole piece under the -1 dBFS ceiling with ONE gain, known only when
+    the last sample is (as `loudness=` was before `live_loudness=`).  `live_bed=` is the streamed form: the same bed under a
+    look-ahead limiter (the live mix stage)."""
+    if bed is not None and live_bed is not None:
+        raise ValueError(f"{what}: bed= and live_bed= are two ways to hold one ceiling; give one (a stream takes live_bed=)")
     if bed is not None:
         raise ValueError(f"bed needs the whole piece: {what} hands out audio before its end, and the mix stage's ceiling - one "
-                         "gain over the whole mixed piece - is known only there (synthesize the piece, or mix() a finished WAV)")
+                         "gain over the whole mixed piece - is known only there (synthesize the piece, or mix() a finished WAV); "
+                         "use live_bed= for a bed under the stream")
 
 
 def _output_fx(sample_rate, speed, pitch, loudness=None, live_loudness=None):

@@ -607,6 +607,79 @@ ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_ra
 ft_status ft_mix_plan(int32_t sample_rate, int64_t n, int64_t lead, int64_t tail, int64_t* N, int32_t* hop, int64_t* nodes);
 /* Host only: T[0 .. 6000]. */
 ft_status ft_mix_gains(float* table);
+/* Live mix.  The mix stage on a stream: synthesize_long_stream and synthesize_script_stream hand out audio before the piece
+ * ends, and the one gain of Mix's ceiling is known only there.  Everything in Mix before the ceiling is local in time, so this
+ * second stage keeps it as it is and replaces the one gain by a look-ahead limiter with the duck's own cone shape, driven by
+ * the peaks of the mixed hops; it then holds back less than half a second.  It is a different operation from Mix - a gain that
+ * varies in time - and Mix, its ceiling and its refusals stay as they are.  Stated, which fixes every bit of the result:
+ *   Inputs: the programme x[0 .. n) at the output rate Fo, float32, arriving in pushes of any size; a push of 0 samples is
+ *   allowed; n is known at `final` and n = 0 is allowed.  One bed item and ft_mix_params, both as ft_codec_mix takes them:
+ *   the same fields, the same checks in the same order (n < 0 where Mix refuses n < 1).
+ *   Constants: H = floor(Fo / 50); T[d] the table of ft_mix_gains; cf = (float) 10^(-1/20); limiter attack La = 5 hops and
+ *   release Lr = 25 hops.
+ *   Bed, timeline, activity, duck, gains: exactly as Mix states them, with N = lead + n + tail and Nh = ceil(N / H).  The bed is
+ *   prepared once, at `begin` - intake, level, join with (0, 1, 0, 0), then the resampler from zero state - and stays on the
+ *   device for the life of the stream; nb = 0 is FT_ERR_ARG after those launches, as in ft_codec_mix.
+ *   Fades: N is not known while streaming, so Mix's N / 2 clamps go: f_in = fade_in and f_out = fade_out (a fade beyond 2^30
+ *   samples, four times the longest timeline, counts as 2^30).  A sample with i < f_in gets t = t ramp_in(i); one with
+ *   i >= N - f_out then gets t = t ramp_out(N - 1 - i); a sample in both ranges gets both products, in that order, each
+ *   rounded on its own.  The rest of the sample rule is Mix's, so for N >= 2 max(fade_in, fade_out) the sample before the
+ *   limiter, m[i], is Mix's m[i] bit for bit.
+ *   Limiter: Q_h = max |m| over hop h (a NaN is never the peak; 0 for a hop of NaNs).  need_h is the smallest d in [0, 6000]
+ *   with __fmul_rn(T[d], Q_h) <= cf, 6000 if there is none (T is monotone: a binary search finds it).  Nodes k = 0 .. Nh:
+ *   L_k is the largest of 0, need_h (La - (h - k)) / La over h in [k, k + La - 1] and need_h (Lr - (k - 1 - h)) / Lr over h in
+ *   [k - Lr, k - 1]; only hops in [0, Nh) count; integer divisions in int64.  Unlike the duck, every hop of a window counts, not
+ *   the nearest alone, because need varies from hop to hop.  l_k = T[L_k].  For i = k H + j:
+ *   y[i] = __fmul_rn(m[i], fmaf(__fdiv_rn((float) j, (float) H), l_k+1 - l_k, l_k)).  Both nodes of hop h sit at need_h or
+ *   deeper, so |y| <= cf up to rounding; where L_k = L_k+1 = 0 the factor is exactly 1 and y = m bit for bit.  So a call whose m
+ *   never exceeds cf, with N >= 2 max(fade_in, fade_out), equals ft_codec_mix bit for bit.
+ *   Emission: after n_in programme samples, not final, let F = lead + n_in and W' = floor(F / H).  The activity is final for
+ *   hops h < W', D_k for k <= W' - Wa; m[i] where both of its nodes are and i < E = lead + n_in + tail - fade_out (a later
+ *   sample might still lie in the fade-out); Q_h for h < Wm = min(max(0, W' - Wa), floor(max(0, E) / H)); L_k for
+ *   k <= Wm - La; and the outputs below max(0, Wm - La) H, which go out.  `final` fixes N, computes the rest and emits all N
+ *   samples.  The stage holds back less than (Wa + La + 2) H + max(0, fade_out - tail) samples, 0.44 s at the default attack;
+ *   an empty first push emits what `lead` alone makes final.
+ *   Determinism: no floating-point atomics; Q_h is reduced inside the one workgroup that owns hop h; nothing depends on how the
+ *   pushes were cut.
+ *   Reported (ft_mix_live_info, by ft_codec_mix_live): N, nb, Nh, the active hops, the largest D_k (dmax), the largest L_k
+ *   (lmax), the largest Q_h (qmax), the bed's ft_intake_info.
+ * Limits and refusals: every argument is checked before any device work, in ft_codec_mix's order, and a refused call changes
+ * nothing - a refused push leaves its stream as it was.  A push after `final` is FT_ERR_STATE; a capacity below what the push
+ * emits (ft_mix_live_plan says how much) is FT_ERR_ARG; N beyond 2^28 is FT_ERR_TOO_LONG at the push that would cross it.
+ * Several mix streams may be open on one context, each with its own state; all device work runs on the codec's stream.
+ * On the device a stream holds its bed, two carries in two copies each (a push reads one and writes the other) - the programme
+ * not yet mixed, below (Wa + 2) H + max(0, fade_out - tail) samples, and the m not yet emitted, at most La H - and whole arrays
+ * of act, D_k, g_k, need_h and L_k, 17 bytes per 20 ms, which grow on need; the counters live on the host.  Five launches per
+ * push whatever its size, a launch with nothing to do left out: mixl_hop_kernel, mixl_node_kernel, mixl_sample_kernel (m, Q_h,
+ * need_h), mixl_limit_kernel, mixl_apply_kernel (y, then the roll of the carries). */
+typedef struct ft_mix_live_info {
+    int64_t N, nb, Nh, active;
+    int32_t dmax, lmax;
+    float qmax;
+    int32_t reserved;
+    ft_intake_info bed;
+} ft_mix_live_info;
+typedef struct ft_mix_stream ft_mix_stream;
+/* Host only: after n_in programme samples of a stream with these values (final: its end), *n_out = the samples emitted so far
+ * and *nodes = the limiter nodes that are final.  Either pointer may be NULL.  FT_ERR_ARG / FT_ERR_TOO_LONG as
+ * ft_codec_mix_live judges the rate, n_in and mp. */
+ft_status ft_mix_live_plan(int32_t sample_rate, const ft_mix_params* mp, int64_t n_in, int32_t final, int64_t* n_out,
+                           int64_t* nodes);
+/* The stage on a host waveform, as a stream whose only push is its last.  y receives the N = lead + n + tail samples
+ * (capacity >= N), *total = N; duck and limit (each may be NULL) receive D_0 .. D_Nh and L_0 .. L_Nh.  x may be NULL when
+ * n = 0. */
+ft_status ft_codec_mix_live(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
+                            const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck, int32_t* limit,
+                            ft_mix_live_info* info);
+/* A stream of the stage: prepares the bed and allocates the stream's state. */
+ft_status ft_codec_mix_stream_begin(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed, const ft_mix_params* mp,
+                                    ft_mix_stream** out);
+/* One push of n >= 0 programme samples (host; x may be NULL when n = 0); final: the programme ends with it.  The samples that
+ * became final are written into y (host, `capacity` samples) and their count into *n_out. */
+ft_status ft_codec_mix_stream_push(ft_mix_stream* ms, const float* x, int64_t n, int32_t final, float* y, int64_t capacity,
+                                   int64_t* n_out);
+/* Frees the stream (after its context was destroyed: the host handle alone). */
+void ft_codec_mix_stream_end(ft_mix_stream* ms);
 
 ft_status ft_sync(ft_ctx* ctx);
 /* State of the persistent frame engine (csrc/frame_engine.h), the batch-1 form of the decode step
