@@ -51,6 +51,42 @@ Error model (u = 2^-24, the float32 unit round-off; every float32 operation retu
   RVQ gather: each table entry is codebook_dim products and the bias in f32 at load time, then 1 + n_codebooks entries
       are summed: err = sum_i (cd + 1) u (sum |w| |cb| + |b|)_i + (n_codebooks + 1) u sum_i |table_i|.
 
+The quantiser search (rvq_encode_kernel; `rvq_search_check`) returns integers, so it is judged per DECISION, not per
+element: one decision per (frame, codebook).  The reference restates CodecOracle._vq / quantizer_encode in float64,
+teacher-forced on the device's picks: at codebook q the residual is the recorded zq minus the float64 table rows of the
+device's picks 0 .. q-1, its score of row i is s_i = -(|en|^2 - 2 en . c_i + |c_i|^2) with en = e / |e|, e = in_proj
+(residual), c_i the L2-normalised codebook row, and the device's pick must have s_pick >= max_i s_i - b.  Codebook rows
+that are bit-identical in float32 have identical device scores (cbn, cn2 and the dot chain are functions of the row
+alone), and the kernel keeps the lowest index on equal scores within a thread, across lanes and across waves: a pick
+that is not the lowest index of its group of bit-identical rows is a fault, with no tolerance.
+    The device takes the argmax of s~_i = s_i + c + eta_i, c common to all rows of the decision (its |en|^2 is not
+exactly 1), |eta_i| <= eps; then s_pick >= s_best - 2 eps, so b = 2 eps, and eps collects, with cd = codebook_dim and
+|en| = |c_i| = 1 (so sum_k |en_k| |c_ik| <= 1, |2 en . c_i| <= 2, |s_i| <= 4):
+  projection: products of f32 operands are exact in f64, D / 256 fused terms per thread, a 6-step tree, three sums and
+      the bias in f64, then ONE rounding to f32: de_k = u |e_k| + (D / 256 + 12) 2^-53 (sum |W| |res| + |b|)_k
+      + sum_d |W_kd| dres_d, dres the distance of the device's f32 residual from the reference's (below).  A
+      perturbation de of e moves en by at most 2 |de| / |e| and a score by twice that: 4 |de|_2 / |e|_2.
+  norm and reciprocal: nn a cd-term chain of non-negative terms (cd u relative), the square root halves it and adds u,
+      the reciprocal adds u (2 u if approximated), the product en_k = e_k inv u: a common relative error (cd / 2 + 4) u
+      of en that scales 2 en . c_i (row-dependent): 2 (cd / 2 + 4) u; the product's own rounding, per component: 2 u.
+  normalised codebook at load (normalize_codebook_kernel): the same chain per row, c~_i = c_i (1 + rho),
+      |rho| <= (cd / 2 + 4) u, and cn2 a cd-term chain on the stored c~: -2 en . c~_i + |c~_i|^2 is off by
+      2 |rho| + 2 |rho| + cd u = (3 cd + 16) u.
+  the cd-term fma chain of the dot: cd u sum |en_k| |c_ik| <= cd u, doubled (2.0f * dot is exact): 2 cd u.
+  three-term score: (l2 - 2 dot) rounds at |.| <= 3, the sum with cn2 at |.| <= 4: 7 u.
+      Together (cd + 8) u + 2 u + (3 cd + 16) u + 2 cd u + 7 u = (6 cd + 33) u: 4.8e-6 at cd = 8.
+  residual: the table built in f32 at load (the gather stage's term, (cd + 1) u (sum |w| |cb| + |b|) per entry) and one
+      f32 subtraction per codebook: dres_d += (cd + 1) u (sum |w| |cb| + |b|)_d + u |res_d| after every pick.
+  eps = (6 cd + 33) u + 4 |de|_2 / |e|_2.
+    At the first codebook dres = 0 and b is about 1e-5.  From the second on, sum_d |W_kd| dres_d is a sum of D absolute
+values whose signs a worst case may not let cancel: it reaches 2e-3 at D = 1024 (tests/test_codec_stage_ref_host.py
+prints it beside b; the honest float32 search there never leaves the float64 argmax), more than the 5e-5 the search
+was already held to on the oracle's latents (the accumulation error of a 1024-term f32 sum on scores of O(1):
+tests/test_codec_gpu.py).  b is therefore the SMALLER of the two,
+b = min(2 eps, 5e-5): nowhere wider than the bound the search already had, tighter where the derivation is.  A pick
+other than the float64 argmax must lie inside b, and at most 1 % of a case's decisions may be such picks
+(RVQ_NON_ARGMAX_CAP; the float32 emulation has none in 1290 decisions at the real widths).
+
 Carried context (the streamed decode: ft_codec_stream_decode, one chunk of ft_codec_stream_decode_many).  `plan_stream`
 lists the launches of ONE chunk of T frames at rope position t0 with nh = min(t0, window - 1) carried K/V rows: the
 launches of plan_decode on the chunk's codes, plus the carrying launches, which are stages of their own:
@@ -816,3 +852,157 @@ def check_stage(st: Stage, env: dict, W: Weights, got: Dict[str, np.ndarray], ro
             v.over_S = float((diff[ok] / o.S[ok]).max()) if bool(ok.any()) else 0.0
     v.rows = rows[bad_rows].tolist()
     return v
+
+
+# ------------------------------------------------------------------------------------------------ the quantiser search
+RVQ_B_CAP = 5e-5              # the bound the search was already held to at the real widths (tests/test_codec_gpu.py)
+RVQ_NON_ARGMAX_CAP = 0.01     # share of a case's decisions that may be picks other than the float64 argmax (each inside b)
+
+
+def vq_prefix(q: int) -> str:
+    return "quantizer.semantic_quantizer.quantizers.0" if q == 0 else f"quantizer.quantizer.quantizers.{q - 1}"
+
+
+def first_identical(cb: torch.Tensor) -> torch.Tensor:
+    """[N]: for every row of the f32 codebook the lowest index of a row with the same bit pattern."""
+    a = np.ascontiguousarray(cb.to(F32).numpy())
+    _, first, inv = np.unique(a.view(np.uint32), axis=0, return_index=True, return_inverse=True)
+    return torch.from_numpy(first[inv.reshape(-1)].astype(np.int64))
+
+
+@dataclass
+class SearchVerdict:
+    """Per decision [codebook, frame]: the bound b, best score - the pick's score, the float64 argmax and runner-up (lowest
+    index of their groups of bit-identical rows) and the gap between them; and the lists a test asserts on."""
+    b: np.ndarray
+    deficit: np.ndarray
+    argmax: np.ndarray
+    runner: np.ndarray
+    gap: np.ndarray
+    b_derived_max: float
+    outside: List[tuple] = field(default_factory=list)      # (frame, codebook, deficit, b): a pick farther than b from the best
+    ties: List[tuple] = field(default_factory=list)         # (frame, codebook, pick, lowest identical row)
+    invalid: List[tuple] = field(default_factory=list)      # (frame, codebook, pick): not an index of the codebook
+
+    @property
+    def decisions(self) -> int:
+        return int(self.b.size)
+
+    @property
+    def non_argmax(self) -> int:
+        return int((self.deficit > 0).sum())
+
+    @property
+    def flagged(self) -> List[tuple]:
+        """(frame, codebook) of every faulty decision, sorted."""
+        return sorted({(t, q) for t, q, *_ in self.outside + self.ties + self.invalid})
+
+    @property
+    def ok(self) -> bool:
+        return not self.flagged and self.non_argmax <= RVQ_NON_ARGMAX_CAP * self.decisions
+
+    def summary(self) -> str:
+        return (f"{self.decisions} decisions, {self.non_argmax} picks other than the float64 argmax, {len(self.outside)} outside b, "
+                f"{len(self.ties)} tie faults, b <= {float(self.b.max()):.2e} (derived up to {self.b_derived_max:.2e}), "
+                f"largest deficit / b {float((self.deficit / self.b).max()):.3f}")
+
+
+def rvq_search_check(shape: OC.CodecShape, weights: Dict[str, torch.Tensor], zq, codes) -> SearchVerdict:
+    """Every decision of a quantiser search judged in float64 (the module docstring derives the rule and b): zq (T, D) are
+    the pre-quantiser latents the search read (f32, as recorded), codes (1 + n_codebooks, T) the device's picks."""
+    W = Weights(weights, dev=False)
+    res = from_raw(np.ascontiguousarray(zq, dtype=np.float32)).to(F64)
+    codes = torch.as_tensor(np.asarray(codes)).long()
+    T, D = res.shape
+    R, cd = shape.n_codebooks + 1, shape.codebook_dim
+    assert codes.shape == (R, T), (tuple(codes.shape), R, T)
+    dres = torch.zeros(T, D, dtype=F64)
+    ar = torch.arange(T)
+    out = SearchVerdict(*(np.zeros((R, T), dtype=dt) for dt in (np.float64, np.float64, np.int64, np.int64, np.float64)), 0.0)
+    for q in range(R):
+        p = vq_prefix(q)
+        Win, bin_ = W.f(f"{p}.in_proj.weight")[:, :, 0], W.f(f"{p}.in_proj.bias")
+        cb, wout, bout = W.f(f"{p}.codebook.weight"), W.f(f"{p}.out_proj.weight")[:, :, 0], W.f(f"{p}.out_proj.bias")
+        N = cb.shape[0]
+        e = res @ Win.t() + bin_
+        de = U * e.abs() + (D / 256 + 12) * 2.0 ** -53 * (res.abs() @ Win.abs().t() + bin_.abs()) + dres @ Win.abs().t()
+        ne = e.norm(dim=1).clamp_min(1e-12)
+        en = e / ne[:, None]
+        cbn = cb / cb.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        rep = first_identical(weights[f"{p}.codebook.weight"])
+        score = -((en * en).sum(dim=1, keepdim=True) - 2.0 * (en @ cbn.t()) + (cbn * cbn).sum(dim=1)[None, :])
+        score = score[:, rep]                                  # bit-identical rows: one value, whatever the order of the sums
+        pick = codes[q]
+        valid = (pick >= 0) & (pick < N)
+        out.invalid += [(int(t), q, int(pick[t])) for t in ar[~valid]]
+        pick = pick.clamp(0, N - 1)
+        lowest = score.clone()
+        lowest[:, rep != torch.arange(N)] = float("-inf")      # one candidate per group of identical rows
+        top = lowest.topk(min(2, N), dim=1)
+        best = top.values[:, 0]
+        deficit = best - score[ar, pick]
+        b_derived = 2.0 * ((6 * cd + 33) * U + 4.0 * de.norm(dim=1) / ne)
+        b = b_derived.clamp_max(RVQ_B_CAP)
+        out.b[q], out.deficit[q], out.argmax[q] = b.numpy(), deficit.numpy(), top.indices[:, 0].numpy()
+        out.runner[q], out.gap[q] = top.indices[:, -1].numpy(), (best - top.values[:, -1]).numpy()
+        out.b_derived_max = max(out.b_derived_max, float(b_derived.max()))
+        far = ~(deficit <= b) & valid                          # NaN flags
+        out.outside += [(int(t), q, float(deficit[t]), float(b[t])) for t in ar[far]]
+        low = rep[pick]
+        out.ties += [(int(t), q, int(pick[t]), int(low[t])) for t in ar[(low != pick) & valid]]
+        # the residual the device went on with: minus the table row of ITS pick
+        dres = dres + (cd + 1) * U * (cb[pick].abs() @ wout.abs().t() + bout.abs())
+        res = res - (cb[pick] @ wout.t() + bout)
+        dres = dres + U * res.abs()
+    return out
+
+
+def rvq_search_emulate(shape: OC.CodecShape, weights: Dict[str, torch.Tensor], zq, bug: Optional[dict] = None) -> np.ndarray:
+    """An honest float32 stand-in for rvq_encode_kernel (the projection in f64 rounded once to f32, everything after it in
+    f32, first index on equal scores), (1 + n_codebooks, T) picks; with `bug`, one emulated fault:
+      {"no_update": q}     the residual is not updated after codebook q;
+      {"offset": q}        residual codebook q's rows (normalised rows, norms and table) read at the semantic codebook's
+                           offset rule, S0 + (q - 1) S0 for S0 + (q - 1) S;
+      {"no_bias": q}       the in-projection bias of codebook q dropped;
+      {"last_on_ties": 1}  the highest index kept on equal scores;
+      {"force": {(t, q): i}}  the pick of frame t at codebook q replaced by row i (the residual follows the replaced pick)."""
+    bug = bug or {}
+    W = Weights(weights, dev=False)
+    res = from_raw(np.ascontiguousarray(zq, dtype=np.float32)).to(F32).clone()
+    T = res.shape[0]
+    R, S0, S = shape.n_codebooks + 1, shape.semantic_codebook_size, shape.codebook_size
+    cbn_all, cn2_all, tab_all = [], [], []
+    for q in range(R):                                         # what the load leaves on the device, all codebooks in one array
+        p = vq_prefix(q)
+        cb = W.f(f"{p}.codebook.weight").to(F32)
+        inv = 1.0 / (cb * cb).sum(dim=1, keepdim=True).sqrt().clamp_min(1e-12)
+        cn = cb * inv
+        cbn_all.append(cn)
+        cn2_all.append((cn * cn).sum(dim=1))
+        tab_all.append(cb @ W.f(f"{p}.out_proj.weight")[:, :, 0].to(F32).t() + W.f(f"{p}.out_proj.bias").to(F32))
+    cbn_all, cn2_all, tab_all = torch.cat(cbn_all), torch.cat(cn2_all), torch.cat(tab_all)
+    codes = np.zeros((R, T), dtype=np.int64)
+    for q in range(R):
+        p = vq_prefix(q)
+        N = S0 if q == 0 else S
+        off = 0 if q == 0 else S0 + (q - 1) * (S0 if bug.get("offset") == q else S)
+        assert off + N <= cbn_all.shape[0], "the emulated offset fault must stay inside the arrays"
+        e = res.to(F64) @ W.f(f"{p}.in_proj.weight")[:, :, 0].t()
+        if bug.get("no_bias") != q:
+            e = e + W.f(f"{p}.in_proj.bias")
+        e = e.to(F32)
+        inv = 1.0 / (e * e).sum(dim=1, keepdim=True).sqrt().clamp_min(1e-12)
+        en = e * inv
+        l2 = (en * en).sum(dim=1, keepdim=True)
+        dot = torch.zeros(T, N, dtype=F32)
+        for k in range(shape.codebook_dim):
+            dot = dot + en[:, k:k + 1] * cbn_all[off:off + N, k][None, :]
+        score = (-((l2 - 2.0 * dot) + cn2_all[off:off + N][None, :])).numpy()
+        pick = N - 1 - np.argmax(score[:, ::-1], axis=1) if bug.get("last_on_ties") else np.argmax(score, axis=1)
+        for (t, qq), i in bug.get("force", {}).items():
+            if qq == q:
+                pick[t] = i
+        codes[q] = pick
+        if bug.get("no_update") != q:
+            res = res - tab_all[off + torch.from_numpy(pick)]
+    return codes

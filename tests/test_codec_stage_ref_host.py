@@ -422,3 +422,140 @@ def test_checker_flags_the_carried_context_faults(tiny_stream):
         return outs
     bad, _ = faulty(tiny_stream, 2, mutate={st.name: two_ulp})
     assert set(bad) == {st.name} and bad[st.name].flagged == 1 and bad[st.name].rows == [st.rows - 1]
+
+
+# ------------------------------------------------------------------- the encode's windows at the real head geometry
+ENC_TF_ATTN = dict(H=16, hd=64, window=512, rows=520)      # enc.3.tf.*.attn: the window IS window_attn_kernel's capacity
+PRE_ATTN = dict(H=C.CodecShape().tf_n_head, hd=C.CodecShape().tf_head_dim, window=C.CodecShape().tf_window, rows=132)
+
+
+@pytest.mark.parametrize("geo", (ENC_TF_ATTN, PRE_ATTN), ids=("enc_tf", "pre"))
+def test_checker_flags_a_window_one_off_at_the_real_head_geometry(geo):
+    """ONE attention stage on a seeded bf16 qkv of unit scale, a few rows past the window: the honest emulation passes;
+    a window one short is flagged from the first query that has `window` keys to drop one of (row window - 1), a window
+    one long from the first query that sees one key too many (row window), and neither at any earlier row."""
+    H, hd, win, T = geo["H"], geo["hd"], geo["window"], geo["rows"]
+    g = torch.Generator().manual_seed(win)
+    env = {"qkv": R.bf16_bits(torch.randn(T, 3 * H * hd, generator=g))}
+    st = R.Stage("attn", "attn", T, H * hd, {"x": "qkv"}, {"bf": "y"}, dict(H=H, hd=hd, window=win))
+    W = R.Weights({}, dev=True)
+
+    def stored(stage):
+        return {"bf": R.raw_store("bf", R.eval_stage(stage, env, W, None, "emulate").ref["bf"])}
+    v = R.check_stage(st, env, W, stored(st))
+    assert v.checked == T * H * hd and v.flagged == 0, (v.flagged, v.worst, v.rows[:8])
+    print(f"window {win}, {T} rows: honest emulation, largest |got - ref| / bound {v.worst:.3f}")
+    for w_bug, first in ((win - 1, win - 1), (win + 1, win)):
+        v = R.check_stage(st, env, W, stored(with_p(st, window=w_bug)))
+        assert v.rows == list(range(first, T)), (w_bug, v.rows)
+
+
+# ------------------------------------------------------------------------------------------- the quantiser search
+def quantiser_weights(shape, seed=3):
+    """The tensors the search reads, seeded, in the distributions of oracle.codec.random_weights (the real-width codec has
+    10^8 other parameters that a host test of the search has no use for)."""
+    g = torch.Generator().manual_seed(seed)
+    D, cd, w = shape.latent_dim, shape.codebook_dim, {}
+    for q in range(shape.n_codebooks + 1):
+        p = R.vq_prefix(q)
+        N = shape.semantic_codebook_size if q == 0 else shape.codebook_size
+        w[f"{p}.in_proj.weight"] = torch.randn(cd, D, 1, generator=g) / D ** 0.5
+        w[f"{p}.in_proj.bias"] = 0.05 * torch.randn(cd, generator=g)
+        w[f"{p}.codebook.weight"] = torch.randn(N, cd, generator=g)
+        w[f"{p}.out_proj.weight"] = torch.randn(D, cd, 1, generator=g) / cd ** 0.5
+        w[f"{p}.out_proj.bias"] = 0.05 * torch.randn(D, generator=g)
+    return w
+
+
+def latents(shape, T, seed=17):
+    return torch.randn(T, shape.latent_dim, generator=torch.Generator().manual_seed(seed)).numpy()
+
+
+@pytest.fixture(scope="module", params=("encode_shape", "real"))
+def search(request):
+    shape = encode_shape() if request.param == "encode_shape" else C.CodecShape()
+    w = quantiser_weights(shape)
+    zq = latents(shape, 40)
+    return shape, w, zq, R.rvq_search_emulate(shape, w, zq)
+
+
+def test_search_check_passes_an_honest_float32_search(search):
+    shape, w, zq, codes = search
+    v = R.rvq_search_check(shape, w, zq, codes)
+    print(f"honest float32 search, {shape.latent_dim}-wide, {shape.semantic_codebook_size} + {shape.n_codebooks} x "
+          f"{shape.codebook_size} rows: {v.summary()}")
+    assert v.decisions == 40 * (shape.n_codebooks + 1)
+    assert not v.outside and not v.ties and not v.invalid, v.flagged
+    assert v.ok and float(v.b.max()) <= R.RVQ_B_CAP
+    # the oracle's own search on the same latents (f32 throughout): the same picks wherever its two best rows are b apart
+    orc = C.CodecOracle.__new__(C.CodecOracle)
+    orc.c, orc.w, orc.taps = shape, w, {}
+    res = torch.from_numpy(zq).t()[None]
+    for q in range(shape.n_codebooks + 1):
+        zr, idx = orc._vq(R.vq_prefix(q), res)
+        differ = np.flatnonzero(idx[0].numpy() != codes[q])
+        assert all(v.gap[q, t] <= v.b[q, t] for t in differ), (q, differ)
+        if len(differ):
+            break                                              # past a flip the oracle's residual is another one
+        res = res - zr
+
+
+def test_search_check_flags_a_residual_left_as_it_was(search):
+    """Up to codebook q + 1 the faulty search has the honest one's picks, so at q + 1 it faces the residual the honest
+    one faced: flagged there are exactly the frames whose pick on the stale residual is another row, and nothing before."""
+    shape, w, zq, honest = search
+    q = 1
+    codes = R.rvq_search_emulate(shape, w, zq, {"no_update": q})
+    v = R.rvq_search_check(shape, w, zq, codes)
+    moved = [(int(t), q + 1) for t in np.flatnonzero(codes[q + 1] != honest[q + 1])]
+    assert len(moved) >= 10 and [f for f in v.flagged if f[1] <= q + 1] == moved, (moved, v.flagged[:8])
+
+
+def test_search_check_flags_rows_read_at_the_semantic_offset_rule(search):
+    shape, w, zq, honest = search
+    q = 2                                                     # S0 + S0 for S0 + S: the rows of a later codebook
+    codes = R.rvq_search_emulate(shape, w, zq, {"offset": q})
+    v = R.rvq_search_check(shape, w, zq, codes)
+    moved = [(int(t), q) for t in np.flatnonzero(codes[q] != honest[q])]
+    assert len(moved) >= 10 and [f for f in v.flagged if f[1] <= q] == moved, (moved, v.flagged[:8])
+    # a frame whose pick survived still subtracted the other codebook's table row: caught at the next codebook
+    kept = [t for t in range(40) if codes[q, t] == honest[q, t] and codes[q + 1, t] != honest[q + 1, t]]
+    assert all((t, q + 1) in v.flagged for t in kept)
+
+
+def test_search_check_flags_a_dropped_in_projection_bias(search):
+    """The bias is small against the projection (0.05 against O(1)), so most picks survive it: the ones that do not are
+    flagged at that codebook, and no other decision is (the residual follows the device's pick)."""
+    shape, w, zq, honest = search
+    q = 1
+    codes = R.rvq_search_emulate(shape, w, zq, {"no_bias": q})
+    v = R.rvq_search_check(shape, w, zq, codes)
+    moved = sorted((int(t), q) for t in np.flatnonzero(codes[q] != honest[q]))
+    assert moved and v.flagged == moved, (moved, v.flagged)
+
+
+def test_search_check_flags_the_highest_index_on_a_planted_tie(search):
+    shape, w, zq, _ = search
+    w = dict(w)
+    for q in range(shape.n_codebooks + 1):
+        cb = w[f"{R.vq_prefix(q)}.codebook.weight"].clone()
+        cb[cb.shape[0] // 2:] = cb[:cb.shape[0] // 2]
+        w[f"{R.vq_prefix(q)}.codebook.weight"] = cb
+    good = R.rvq_search_check(shape, w, zq, R.rvq_search_emulate(shape, w, zq))
+    assert not good.flagged and good.non_argmax == 0, good.flagged[:8]
+    codes = R.rvq_search_emulate(shape, w, zq, {"last_on_ties": 1})
+    v = R.rvq_search_check(shape, w, zq, codes)
+    assert not v.outside                                       # the score is the best one: only the tie rule is broken
+    assert sorted((t, q) for t, q, *_ in v.ties) == [(t, q) for t in range(40) for q in range(shape.n_codebooks + 1)]
+    assert all(pick == low + w[f"{R.vq_prefix(q)}.codebook.weight"].shape[0] // 2 for _, q, pick, low in v.ties)
+
+
+def test_search_check_flags_the_runner_up_at_ten_b(search):
+    shape, w, zq, honest = search
+    v0 = R.rvq_search_check(shape, w, zq, honest)
+    ok = v0.gap >= 10 * v0.b
+    q, t = (int(i) for i in np.unravel_index(np.argmin(np.where(ok, v0.gap, np.inf)), v0.gap.shape))    # the narrowest such gap
+    assert ok[q, t] and honest[q, t] == v0.argmax[q, t]
+    print(f"runner-up planted at frame {t}, codebook {q}: gap {v0.gap[q, t]:.2e}, b {v0.b[q, t]:.2e}")
+    v = R.rvq_search_check(shape, w, zq, R.rvq_search_emulate(shape, w, zq, {"force": {(t, q): int(v0.runner[q, t])}}))
+    assert v.flagged == [(t, q)] and v.non_argmax == 1, v.flagged
