@@ -492,7 +492,9 @@ typedef void (*eng_slow_fn_t)(SlowEngP);
 typedef void (*eng_fast_fn_t)(FastEngP);
 typedef void (*eng_qkv0_fn_t)(const bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, int, float);
 struct EngSlowEntry { int D, H, HKV, HDIM, F, SQ, SF, SO; eng_slow_fn_t xl, plain; };
-struct EngFastEntry { int D, H, HKV, HDIM, F, V, SQ, SF, SO; eng_fast_fn_t loop; eng_qkv0_fn_t qkv0; };
+// loop: the all-streaming form; resident: W13 pairs held in the gathering waves' registers (nullptr: nothing fits this class),
+// resf pairs per gathering wave of each of up to resl layers
+struct EngFastEntry { int D, H, HKV, HDIM, F, V, SQ, SF, SO; eng_fast_fn_t loop; eng_qkv0_fn_t qkv0; eng_fast_fn_t resident; int resf, resl; };
 template <typename S, bool WITH_XL>
 static EngSlowEntry eng_slow_entry() {
     eng_slow_fn_t xl = nullptr;
@@ -501,7 +503,10 @@ static EngSlowEntry eng_slow_entry() {
 }
 template <typename S>
 static EngFastEntry eng_fast_entry() {
-    return EngFastEntry{S::D, S::H, S::HKV, S::HDIM, S::F, S::V, S::SQ, S::SF, S::SO, fast_engine_kernel<S, 10>, eng_qkv0_table_kernel<S>};
+    eng_fast_fn_t res = nullptr;
+    if constexpr (S::RESF > 0) res = fast_engine_kernel<S, 10, true>;
+    return EngFastEntry{S::D, S::H, S::HKV, S::HDIM, S::F, S::V, S::SQ, S::SF, S::SO, fast_engine_kernel<S, 10, false>, eng_qkv0_table_kernel<S>,
+                        res, S::RESF, S::RESL};
 }
 static const EngSlowEntry* eng_slow_shapes(int* n) {
     static const EngSlowEntry tab[] = {eng_slow_entry<EngSlowS1, true>(), eng_slow_entry<EngSlowShape<1024, 16, 8, 128, 4096>, true>(),
@@ -628,7 +633,9 @@ static bool eng_setup_try(ft_ctx* ctx, std::string& why) {
                          per(ctx->fastV) <= fe->SO * ENG_CW && per(fqkvN) <= ENG_LINE && per(c.fast_intermediate_size) <= ENG_LINE && ctx->fastV <= 1024 &&
                          c.codebook_size <= 65536;
     if (!fast_ok) { why += "; fast loop on launches (FT_NO_FAST_ENGINE, or fast widths outside the instantiations: 1024 / 16 + 8 heads x 64 / ffn 3072 or 4096 / 1024 codes used, <= 10 codebooks)"; return true; }
-    ctx->eng_fast_fn = (const void*)fe->loop;
+    // the resident form needs every layer in its set; FT_NO_RESIDENT selects the all-streaming form (A/B runs, the equality test)
+    const bool fast_res = fe->resident != nullptr && c.n_fast_layer <= fe->resl && getenv("FT_NO_RESIDENT") == nullptr;
+    ctx->eng_fast_fn = (const void*)(fast_res ? fe->resident : fe->loop);
     // from here on a failure keeps the slow engine and leaves the fast loop on launches
     auto fast_off = [&](const std::string& w2) { why += "; fast loop on launches (" + w2 + ")"; return true; };
     std::vector<EngLayer> hf(c.n_fast_layer);
@@ -679,6 +686,16 @@ static bool eng_setup_try(ft_ctx* ctx, std::string& why) {
     }
     ctx->eng_fast_on = true;
     why = ctx->eng_xl ? "slow stack (one kv head per XCD) and codebook loop on the frame engine" : "slow stack and codebook loop on the frame engine";
+    {
+        char buf[160];
+        if (fast_res)
+            snprintf(buf, sizeof buf, "; codebook loop: %d of %d W13 pairs per CU of %d layers resident in the gathering waves' registers",
+                     fe->resf * ENG_GW, per(c.fast_intermediate_size), c.n_fast_layer);
+        else
+            snprintf(buf, sizeof buf, "; codebook loop: all weights streamed (%s)", fe->resident == nullptr ? "no resident set fits this shape class" :
+                     c.n_fast_layer > fe->resl ? "more layers than the resident set holds" : "FT_NO_RESIDENT is set");
+        why += buf;
+    }
     return true;
 }
 

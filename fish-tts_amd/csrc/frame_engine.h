@@ -57,6 +57,14 @@ struct EngFastShape {
     static constexpr int NTD = D / 512, NTA = HD / 512, NTF = F / 512;
     static constexpr int SQ = (QKVN / ENG_NB + ENG_CW - 1) / ENG_CW, SF = (F / ENG_NB + ENG_CW - 1) / ENG_CW, SO = (D / ENG_NB + ENG_CW - 1) / ENG_CW;
     static constexpr bool PK3 = F % 384 == 0 && (F / ENG_NB) % 3 == 0;
+    // Resident set of the codebook loop (fast_engine_kernel<.., true>): RESF (w1, w3) pairs of W13 per gathering wave, of
+    // each of up to RESL layers, are loaded ONCE per launch (in its first pass) and stay in that wave's registers (8 * NTD registers a
+    // pair).  Budget: 256 registers a wave; the gathering waves' own work (attention share, the draw) peaks near 100.  At
+    // 12 pairs per workgroup and NTD = 2 two pairs a wave and four layers are 128 registers: 8 of the 12 pairs of every
+    // layer = 32 of the 96 KB a CU streams per layer-step, the burst in front of the longest hop (g).  Wider feed-forward
+    // classes already fill the compute waves' registers with a spill: nothing fits, they keep the all-streaming form.
+    static constexpr int RESF = (NTD <= 2 && F / ENG_NB == 12) ? 2 : 0;
+    static constexpr int RESL = RESF ? 4 : 0;
     static_assert(D % 512 == 0 && HD % 512 == 0 && F % 512 == 0 && V == 1024 && HD == D, "fast widths");
     static_assert(QKVN % (4 * ENG_NB) == 0 && D % (4 * ENG_NB) == 0 && F % (4 * ENG_NB) == 0 && V % (4 * ENG_NB) == 0, "whole granule groups per workgroup");
 };
@@ -432,6 +440,22 @@ struct EngRowQkvX {
     __device__ __forceinline__ int operator()(int u) const { return u < nq ? q0 + u : (u < nq + nk ? k0 + (u - nq) : v0 + (u - nq - nk)); }
 };
 
+// Rows that stay in registers for a whole launch (the codebook loop's resident set): called right in front of every use.
+// To the compiler the registers change here, so the unpacking of the bf16 pairs stays at the use - hoisted out of the loops
+// as loop-invariant it would keep two registers per packed word alive (and spill them).
+template <int NT, int RPU, int MAXS>
+__device__ __forceinline__ void eng_res_pin(EngW<NT, RPU, MAXS>& r) {
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s)
+#pragma unroll
+        for (int rr = 0; rr < RPU; ++rr)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                U4& w = r.w[s][rr][t];
+                asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w));
+            }
+}
+
 template <bool NTL = true, int NT, int RPU, int MAXS, typename RM = EngRowIdent>
 __device__ __forceinline__ void eng_issue(EngW<NT, RPU, MAXS>& r, const bf16_t* W, const bf16_t* gain, int K, int u_lo, int u_hi,
                                           int cw, int lane, int nt, RM rm = RM()) {
@@ -461,7 +485,7 @@ __device__ __forceinline__ void eng_issue(EngW<NT, RPU, MAXS>& r, const bf16_t* 
 // the other (measured: acknowledgements of the 4-byte stores of a phase spread over 2.5 us).
 struct EngOut {
     float* vals;     // LDS [ENG_MAX_OUT]
-    int* count;      // LDS arrival counter (never reset: phase k is complete at (k + 1) * ENG_CW)
+    int* count;      // LDS arrival counter (never reset: phase k is complete at (k + 1) * the waves that count in here)
     int seq;         // phases done so far (per-wave copy, all compute waves agree)
 };
 constexpr int ENG_MAX_OUT = 64;
@@ -566,18 +590,21 @@ __device__ __forceinline__ void eng_gemv_qkv_local(const EngW<NT, 1, MAXS>& r, c
 // PK3: the vector is handed over as 8-byte granules of THREE values {v0 | v1 << 16, v2 | tag << 16} (the SwiGLU vector: 3072
 // values are 8 KB instead of 12, and its hand-off is the longest of a layer); gout then points at the vector's base and the
 // workgroup's units must be a multiple of three (12 at 256 workgroups).
-template <int NT, int RPU, int MAXS, int PRO, int EPI, bool PK3 = false>
-__device__ __forceinline__ void eng_gemv(const EngW<NT, RPU, MAXS>& r, const float* xs, int K, float eps, const bf16_t* bias,
-                                         const float* resid, unsigned* gout, unsigned tag, float* plain, int u_lo, int u_hi,
-                                         int cw, int lane, EngOut& eo) {
-    eng_gemv_rows<NT, RPU, MAXS, PRO, EPI>(r, xs, K, eps, bias, resid, eo.vals, u_lo, u_hi, cw, lane);
+// eng_gemv_part: the calling wave computes units [r_lo, r_hi) of the workgroup's [u_lo, u_hi) (unit r_lo + cw + s * ENG_CW, s < MAXS);
+// ARR waves of the workgroup count in at eo (the codebook loop's W13 phases: the compute waves with the streamed units and
+// the gathering waves with their resident ones, each collection point with its own counter).
+template <int NT, int RPU, int MAXS, int PRO, int EPI, bool PK3 = false, int ARR = ENG_CW>
+__device__ __forceinline__ void eng_gemv_part(const EngW<NT, RPU, MAXS>& r, const float* xs, int K, float eps, const bf16_t* bias,
+                                              const float* resid, unsigned* gout, unsigned tag, float* plain, int u_lo, int u_hi,
+                                              int r_lo, int r_hi, int cw, int lane, EngOut& eo) {
+    eng_gemv_rows<NT, RPU, MAXS, PRO, EPI>(r, xs, K, eps, bias, resid, eo.vals + (r_lo - u_lo), r_lo, r_hi, cw, lane);
     // count in; the last wave of the workgroup to arrive publishes
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     int old = 0;
     if (lane == 0) old = __hip_atomic_fetch_add((eng_lds_int)eo.count, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     old = __builtin_amdgcn_readfirstlane(old);
     eo.seq += 1;
-    if (old + 1 == eo.seq * ENG_CW) {
+    if (old + 1 == eo.seq * ARR) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
         const int n = u_hi - u_lo;
         if constexpr (PK3) {
@@ -593,6 +620,12 @@ __device__ __forceinline__ void eng_gemv(const EngW<NT, RPU, MAXS>& r, const flo
             if (plain) plain[u_lo + lane] = o;
         }
     }
+}
+template <int NT, int RPU, int MAXS, int PRO, int EPI, bool PK3 = false>
+__device__ __forceinline__ void eng_gemv(const EngW<NT, RPU, MAXS>& r, const float* xs, int K, float eps, const bf16_t* bias,
+                                         const float* resid, unsigned* gout, unsigned tag, float* plain, int u_lo, int u_hi,
+                                         int cw, int lane, EngOut& eo) {
+    eng_gemv_part<NT, RPU, MAXS, PRO, EPI, PK3, ENG_CW>(r, xs, K, eps, bias, resid, gout, tag, plain, u_lo, u_hi, u_lo, u_hi, cw, lane, eo);
 }
 
 // eng_gemv_rows for two input rows at once (each weight register unpacked once; per row the operations of eng_gemv_rows)
@@ -675,23 +708,24 @@ __device__ __forceinline__ void eng_gemv_rows2(const EngW<NT, RPU, MAXS>& r, con
 // Two input rows against the same rows of the matrix (the fast loop's first pass: codebook positions 0 and 1 are both
 // known when the launch starts).  Row r's outputs go to gout[r] with tag[r]; still ONE store instruction per workgroup
 // (lanes 0.. carry row 0, lanes 32.. row 1; a workgroup owns at most 32 units of a vector).
-template <int NT, int RPU, int MAXS, int PRO, int EPI>
-__device__ __forceinline__ void eng_gemv2(const EngW<NT, RPU, MAXS>& r, const float* xs0, const float* xs1, int K, float eps,
-                                          const bf16_t* bias, const float* resid0, const float* resid1, unsigned* gout0, unsigned* gout1,
-                                          unsigned tag0, unsigned tag1, int u_lo, int u_hi, int cw, int lane, EngOut& eo) {
+template <int NT, int RPU, int MAXS, int PRO, int EPI, int ARR = ENG_CW>
+__device__ __forceinline__ void eng_gemv2_part(const EngW<NT, RPU, MAXS>& r, const float* xs0, const float* xs1, int K, float eps,
+                                               const bf16_t* bias, const float* resid0, const float* resid1, unsigned* gout0, unsigned* gout1,
+                                               unsigned tag0, unsigned tag1, int u_lo, int u_hi, int r_lo, int r_hi, int cw, int lane, EngOut& eo) {
+    float* const v0 = eo.vals + (r_lo - u_lo);       // (units [r_lo, r_hi) of the workgroup's [u_lo, u_hi): see eng_gemv_part)
     if (NT <= 2) {
-        eng_gemv_rows2<NT, RPU, MAXS, PRO, EPI>(r, xs0, xs1, K, eps, bias, resid0, resid1, eo.vals, eo.vals + 32, u_lo, u_hi, cw, lane);
+        eng_gemv_rows2<NT, RPU, MAXS, PRO, EPI>(r, xs0, xs1, K, eps, bias, resid0, resid1, v0, v0 + 32, r_lo, r_hi, cw, lane);
     } else {
-        eng_gemv_rows<NT, RPU, MAXS, PRO, EPI>(r, xs0, K, eps, bias, resid0, eo.vals, u_lo, u_hi, cw, lane);
+        eng_gemv_rows<NT, RPU, MAXS, PRO, EPI>(r, xs0, K, eps, bias, resid0, v0, r_lo, r_hi, cw, lane);
         __builtin_amdgcn_sched_barrier(0);       // one row's inputs in registers at a time
-        eng_gemv_rows<NT, RPU, MAXS, PRO, EPI>(r, xs1, K, eps, bias, resid1, eo.vals + 32, u_lo, u_hi, cw, lane);
+        eng_gemv_rows<NT, RPU, MAXS, PRO, EPI>(r, xs1, K, eps, bias, resid1, v0 + 32, r_lo, r_hi, cw, lane);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     int old = 0;
     if (lane == 0) old = __hip_atomic_fetch_add((eng_lds_int)eo.count, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     old = __builtin_amdgcn_readfirstlane(old);
     eo.seq += 1;
-    if (old + 1 == eo.seq * ENG_CW) {
+    if (old + 1 == eo.seq * ARR) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
         const int n = u_hi - u_lo;
         const int i = lane & 31;
@@ -700,6 +734,13 @@ __device__ __forceinline__ void eng_gemv2(const EngW<NT, RPU, MAXS>& r, const fl
             eng_put(lane < 32 ? gout0 : gout1, i, o, lane < 32 ? tag0 : tag1);
         }
     }
+}
+template <int NT, int RPU, int MAXS, int PRO, int EPI>
+__device__ __forceinline__ void eng_gemv2(const EngW<NT, RPU, MAXS>& r, const float* xs0, const float* xs1, int K, float eps,
+                                          const bf16_t* bias, const float* resid0, const float* resid1, unsigned* gout0, unsigned* gout1,
+                                          unsigned tag0, unsigned tag1, int u_lo, int u_hi, int cw, int lane, EngOut& eo) {
+    eng_gemv2_part<NT, RPU, MAXS, PRO, EPI, ENG_CW>(r, xs0, xs1, K, eps, bias, resid0, resid1, gout0, gout1, tag0, tag1, u_lo, u_hi, u_lo, u_hi,
+                                                    cw, lane, eo);
 }
 
 __device__ __forceinline__ void eng_units(int U, int b, int nb, int& lo, int& hi) {
@@ -1418,6 +1459,7 @@ struct FastEngP {
     const bf16_t* qkv0_tab;       // [V][qkvN] bf16 or nullptr: layer 0's q k v of every codebook-embedding row (eng_qkv0_table_kernel):
                                   // from position 2 on the layer-0 input is one of V table rows, so its QKV phase and hand-off are a lookup
     unsigned long long* stamps;   // diagnostic builds only (tools/mb_engine.hip): [workgroup][step][layer][16] ticks, or nullptr
+    int nt;                       // bit 1 (timing experiments only): skip the weight loads
 };
 #define ENG_FSTAMP(k) do { if (p.stamps && tid == 0) p.stamps[(((size_t)b * p.ncb + cb) * nL + li) * 16 + (k)] = eng_rt(); } while (0)
 
@@ -1986,11 +2028,19 @@ inline size_t eng_fast_lds_bytes(int D, int qkvN, int HD, int F, int V, int nL, 
     return by;
 }
 
-template <typename FS, int MAXCB>
+// RES: the resident form (EngFastShape::RESF / RESL; needs n_layer <= RESL): the gathering waves hold FRES of the workgroup's
+// W13 pairs of every layer in registers from the launch's first pass on and compute them in the W13 phases beside the compute waves,
+// which stream only the other pairs.  !RES: the all-streaming form (every weight row through the compute waves).
+template <typename FS, int MAXCB, bool RES>
 __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
-    // units per compute wave (s1-mini: QKV 8 rows -> 2, W13 12 pairs -> 3, Wo / W2 / head 4 rows -> 1)
+    // units per compute wave (s1-mini: QKV 8 rows -> 2, W13 12 pairs -> 3 (resident form: 1 + 2 per gathering wave), Wo / W2 / head 4 rows -> 1)
     constexpr int NTD = FS::NTD, NTA = FS::NTA, NTF = FS::NTF, HDIM = FS::HDIM;
     constexpr int SQ = FS::SQ, SF = FS::SF, SO = FS::SO;
+    static_assert(!RES || (FS::RESF > 0 && FS::RESL > 0), "this shape class has no resident set");
+    constexpr int RF = RES ? FS::RESF : 0, RL = RES ? FS::RESL : 0, FRES = RF * ENG_GW;    // resident pairs per gathering wave / layers / pairs per workgroup
+    constexpr int SFC = RES ? (FS::F / ENG_NB - FRES + ENG_CW - 1) / ENG_CW : SF;          // streamed pairs per compute wave
+    constexpr int ARRF = RES ? ENG_WAVES : ENG_CW;                                         // waves that count in at a W13 phase
+    static_assert(FS::F / ENG_NB > FRES, "the compute waves keep at least one pair");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (scalar: uniform branches, row offsets in SGPRs)
     const int b = blockIdx.x;
@@ -2026,7 +2076,14 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
     float* gS1 = xB1 + D;
     float* qkvS1 = gS1;
     float* yS1 = gS1 + QKVN;
-    if (tid == 0) { *dead = eng_fault_here(p.ctl, ENG_FAULT_FAST, b) ? 1 : 0; *out_count = 0; *sub_count = 0; }
+    // W13 phases: [f_lo, f_c_hi) streamed by the compute waves, [f_c_hi, f_hi) resident in the gathering waves (unit f_c_hi + gw +
+    // s * ENG_GW, s < RF; requested in the launch's first pass, kept from then on); in the resident form the W13 phases have a collection point of their own (eight waves count in)
+    int f_lo, f_hi;
+    eng_units(F, b, nb, f_lo, f_hi);
+    const int f_c_hi = f_hi - FRES;
+    EngW<NTD, 2, (RF ? RF : 1)> res[RL ? RL : 1];
+    if (p.stamps && tid == 0) p.stamps[(size_t)b * p.ncb * p.n_layer * 16 + 15] = eng_rt();      // kernel entry (row of step 0, layer 0)
+    if (tid == 0) { *dead = eng_fault_here(p.ctl, ENG_FAULT_FAST, b) ? 1 : 0; *out_count = 0; *sub_count = 0; dead[3] = 0; }
     if (tid == ENG_CW * 64) {                  // one thread owns the registration words
         reg_s[0] = 0; reg_s[1] = 0; reg_s[2] = 1;
         if (p.rep_stride) eng_register(p.ctl, nb, reg_s, dead);
@@ -2047,27 +2104,29 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
 
     if (wave < ENG_CW) {
         // =============================== compute waves ===============================
-        int q_lo, q_hi, o_lo, o_hi, f_lo, f_hi, h_lo, h_hi;
+        int q_lo, q_hi, o_lo, o_hi, h_lo, h_hi;
         eng_units(QKVN, b, nb, q_lo, q_hi);
         eng_units(D, b, nb, o_lo, o_hi);
-        eng_units(F, b, nb, f_lo, f_hi);
         eng_units(V, b, nb, h_lo, h_hi);
         EngW<NTD, 1, SQ> wq;
         EngW<NTA, 1, SO> wo;
-        EngW<NTD, 2, SF> wf;
+        EngW<NTD, 2, SFC> wf;
         EngW<NTF, 1, SO> wd;
         EngW<NTD, 1, SO> wh;
         EngOut eo{outS, out_count, 0};
+        EngOut eo13{outS, dead + 3, 0};
+        EngOut& eoF = RES ? eo13 : eo;
         {
             const EngLayer l0 = eng_layer(p.layers, 0);
-            eng_issue<false>(wq, l0.wqkv, l0.attn_norm, D, q_lo, q_hi, cw, lane, 0);
-            eng_issue<false>(wo, l0.wo, (const bf16_t*)nullptr, HD, o_lo, o_hi, cw, lane, 0);
-            eng_issue<false>(wf, l0.w13, l0.ffn_norm, D, f_lo, f_hi, cw, lane, 0);
-            eng_issue<false>(wd, l0.w2, (const bf16_t*)nullptr, F, o_lo, o_hi, cw, lane, 0);
+            eng_issue<false>(wq, l0.wqkv, l0.attn_norm, D, q_lo, q_hi, cw, lane, p.nt);
+            eng_issue<false>(wo, l0.wo, (const bf16_t*)nullptr, HD, o_lo, o_hi, cw, lane, p.nt);
+            eng_issue<false>(wf, l0.w13, l0.ffn_norm, D, f_lo, f_c_hi, cw, lane, p.nt);
+            eng_issue<false>(wd, l0.w2, (const bf16_t*)nullptr, F, o_lo, o_hi, cw, lane, p.nt);
             __builtin_amdgcn_sched_barrier(0);
         }
         eng_barrier();                                                  // (registration results in LDS)
         eng_barrier();                                                  // B0
+        if (p.stamps && tid == 0) p.stamps[(size_t)b * p.ncb * p.n_layer * 16 + 14] = eng_rt();  // every workgroup registered, B0 passed
         if (pair) {
             // ---- codebook positions 0 and 1 as two rows of one pass: row 0 = (parity 0, tag of step 0), row 1 = (parity 1,
             // tag of step 1); per row the arithmetic of the single-row pass.  Row 0 only feeds the K/V history, so its
@@ -2104,7 +2163,7 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                                                               bq(1, li) + eng_pub(b, q_lo), tag0, tag1, q_lo, q_hi, cw, lane, eo);
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(1);
-                if (more && !(li == nL - 1 && p.qkv0_tab != nullptr)) eng_issue<false>(wq, ln.wqkv, ln.attn_norm, D, q_lo, q_hi, cw, lane, 0);
+                if (more && !(li == nL - 1 && p.qkv0_tab != nullptr)) eng_issue<false>(wq, ln.wqkv, ln.attn_norm, D, q_lo, q_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B1b: qkvS, qkvS1
                 ENG_FSTAMP(2);
@@ -2122,19 +2181,19 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                                                               o_lo, o_hi, cw, lane, eo);
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(4);
-                if (more) eng_issue<false>(wo, ln.wo, (const bf16_t*)nullptr, HD, o_lo, o_hi, cw, lane, 0);
+                if (more) eng_issue<false>(wo, ln.wo, (const bf16_t*)nullptr, HD, o_lo, o_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B3: xB, xB1
                 ENG_FSTAMP(5);
                 if (tail0)
-                    eng_gemv2<NTD, 2, SF, PRO_RMSNORM, EPI_SWIGLU>(wf, xB, xB1, D, p.eps, nullptr, nullptr, nullptr, bg(0, li) + eng_pub(b, f_lo),
-                                                                   bg(1, li) + eng_pub(b, f_lo), tag0, tag1, f_lo, f_hi, cw, lane, eo);
+                    eng_gemv2_part<NTD, 2, SFC, PRO_RMSNORM, EPI_SWIGLU, ARRF>(wf, xB, xB1, D, p.eps, nullptr, nullptr, nullptr, bg(0, li) + eng_pub(b, f_lo),
+                                                                               bg(1, li) + eng_pub(b, f_lo), tag0, tag1, f_lo, f_hi, f_lo, f_c_hi, cw, lane, eoF);
                 else
-                    eng_gemv<NTD, 2, SF, PRO_RMSNORM, EPI_SWIGLU, FS::PK3>(wf, xB1, D, p.eps, nullptr, nullptr, bg(1, li) + (FS::PK3 ? 0 : eng_pub(b, f_lo)), tag1, nullptr,
-                                                                    f_lo, f_hi, cw, lane, eo);
+                    eng_gemv_part<NTD, 2, SFC, PRO_RMSNORM, EPI_SWIGLU, FS::PK3, ARRF>(wf, xB1, D, p.eps, nullptr, nullptr, bg(1, li) + (FS::PK3 ? 0 : eng_pub(b, f_lo)), tag1, nullptr,
+                                                                                f_lo, f_hi, f_lo, f_c_hi, cw, lane, eoF);
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(6);
-                if (more) eng_issue<false>(wf, ln.w13, ln.ffn_norm, D, f_lo, f_hi, cw, lane, 0);
+                if (more) eng_issue<false>(wf, ln.w13, ln.ffn_norm, D, f_lo, f_c_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B4: gS, gS1
                 ENG_FSTAMP(7);
@@ -2146,8 +2205,8 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                                                               o_lo, o_hi, cw, lane, eo);
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(8);
-                if (more) eng_issue<false>(wd, ln.w2, (const bf16_t*)nullptr, F, o_lo, o_hi, cw, lane, 0);
-                if (li == nL - 1) eng_issue<false>(wh, p.fast_out, p.fast_norm, D, h_lo, h_hi, cw, lane, 0);
+                if (more) eng_issue<false>(wd, ln.w2, (const bf16_t*)nullptr, F, o_lo, o_hi, cw, lane, p.nt);
+                if (li == nL - 1) eng_issue<false>(wh, p.fast_out, p.fast_norm, D, h_lo, h_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (alive) {
@@ -2184,7 +2243,7 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(1);
                 if (more && !(li == nL - 1 && p.qkv0_tab != nullptr && cb + 1 >= 2))
-                    eng_issue<false>(wq, ln.wqkv, ln.attn_norm, D, q_lo, q_hi, cw, lane, 0);
+                    eng_issue<false>(wq, ln.wqkv, ln.attn_norm, D, q_lo, q_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B1b: qkvS
                 ENG_FSTAMP(2);
@@ -2197,15 +2256,15 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                                                           o_lo, o_hi, cw, lane, eo);
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(4);
-                if (more) eng_issue<false>(wo, ln.wo, (const bf16_t*)nullptr, HD, o_lo, o_hi, cw, lane, 0);
+                if (more) eng_issue<false>(wo, ln.wo, (const bf16_t*)nullptr, HD, o_lo, o_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B3: xB
                 ENG_FSTAMP(5);
-                eng_gemv<NTD, 2, SF, PRO_RMSNORM, EPI_SWIGLU, FS::PK3>(wf, xB, D, p.eps, nullptr, nullptr, bg(par, li) + (FS::PK3 ? 0 : eng_pub(b, f_lo)), tag, nullptr,
-                                                                f_lo, f_hi, cw, lane, eo);
+                eng_gemv_part<NTD, 2, SFC, PRO_RMSNORM, EPI_SWIGLU, FS::PK3, ARRF>(wf, xB, D, p.eps, nullptr, nullptr, bg(par, li) + (FS::PK3 ? 0 : eng_pub(b, f_lo)), tag, nullptr,
+                                                                            f_lo, f_hi, f_lo, f_c_hi, cw, lane, eoF);
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(6);
-                if (more) eng_issue<false>(wf, ln.w13, ln.ffn_norm, D, f_lo, f_hi, cw, lane, 0);
+                if (more) eng_issue<false>(wf, ln.w13, ln.ffn_norm, D, f_lo, f_c_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B4: gS
                 ENG_FSTAMP(7);
@@ -2213,9 +2272,9 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                                                           o_lo, o_hi, cw, lane, eo);
                 __builtin_amdgcn_sched_barrier(0);
                 ENG_FSTAMP(8);
-                if (more) eng_issue<false>(wd, ln.w2, (const bf16_t*)nullptr, F, o_lo, o_hi, cw, lane, 0);
+                if (more) eng_issue<false>(wd, ln.w2, (const bf16_t*)nullptr, F, o_lo, o_hi, cw, lane, p.nt);
                 // the head's rows are requested one hand-off before their use (held only across it)
-                if (li == nL - 1 && cb >= 1) eng_issue<false>(wh, p.fast_out, p.fast_norm, D, h_lo, h_hi, cw, lane, 0);
+                if (li == nL - 1 && cb >= 1) eng_issue<false>(wh, p.fast_out, p.fast_norm, D, h_lo, h_hi, cw, lane, p.nt);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (!alive) break;
@@ -2232,6 +2291,8 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
         EngSub sub{sub_count, 0};
         SampP sp = p.samp;
         int prev_code = 0;
+        EngOut eo13{outS, dead + 3, 0};
+        U4 fgain[NTD];             // resident form: the layer's ffn_norm gains, requested in front of the attention (landed long before the next poll)
         eng_barrier();                                                  // (registration results in LDS)
         const EngRelay rl{p.rep_stride != 0, reg_s[1], reg_s[2], p.rep_delta0 + (long)reg_s[0] * p.rep_stride};
         eng_barrier();                                                  // B0
@@ -2249,11 +2310,13 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
             for (int li = 0; li < nL; ++li) {
                 const EngLayer l = eng_layer(p.layers, li);
                 const bool tail0 = li + 1 < nL;
+                int gl = lane;       // (resident form: see the main loop below)
+                if constexpr (RES) asm volatile("" : "+v"(gl));
                 const int wh = 1000 + 64 + li * 8;
                 bf16_t* kL = kvS + (size_t)(li * 2) * p.ncb * KVW;
                 bf16_t* vL = kvS + (size_t)(li * 2 + 1) * p.ncb * KVW;
                 if (li > 0) {
-                    eng_gather_x2(rl, EngSrc2{{bx(0, li), bx(1, li)}, {xA, xA1}, {tag0, tag1}}, D, gw, ENG_GW, lane, p.ctl, dead, wh + 0);
+                    eng_gather_x2(rl, EngSrc2{{bx(0, li), bx(1, li)}, {xA, xA1}, {tag0, tag1}}, D, gw, ENG_GW, gl, p.ctl, dead, wh + 0);
                 } else {
                     for (int d = atid * 4; d < D; d += ENG_GW * 64 * 4) {
                         *reinterpret_cast<float4*>(xA + d) = *reinterpret_cast<const float4*>(p.hid + d);
@@ -2261,18 +2324,42 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                     }
                 }
                 eng_barrier(); if (*dead) { alive = false; break; }     // B1
-                eng_gather_x2(rl, EngSrc2{{bq(0, li), bq(1, li)}, {qkvS, qkvS1}, {tag0, tag1}}, QKVN, gw, ENG_GW, lane, p.ctl, dead, wh + 1);
+                eng_gather_x2(rl, EngSrc2{{bq(0, li), bq(1, li)}, {qkvS, qkvS1}, {tag0, tag1}}, QKVN, gw, ENG_GW, gl, p.ctl, dead, wh + 1);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B1b
+                if constexpr (RES) {
+#pragma unroll
+                    for (int r = 0; r < RL; ++r)
+                        if (li == r) eng_issue<false>(res[r], l.w13, (const bf16_t*)nullptr, D, f_c_hi, f_hi, gw, lane, p.nt);    // (first pass: see the main loop)
+#pragma unroll
+                    for (int t = 0; t < NTD; ++t) fgain[t] = eng_ldg16<false>(l.ffn_norm + t * 512 + lane * 8);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 eng_fast_attn_any<MAXCB, HDIM>(qkvS, kL, vL, yS, l.qn, l.kn, r0c, r0s, 0, p.ncb, H, Hkv, p.eps, p.scale, wave, ENG_WAVES, lane);
                 eng_barrier();
                 eng_fast_attn_any<MAXCB, HDIM>(qkvS1, kL, vL, yS1, l.qn, l.kn, r1c, r1s, 1, p.ncb, H, Hkv, p.eps, p.scale, wave, ENG_WAVES, lane);
                 eng_barrier();                                          // B2
-                if (tail0) eng_gather_x2(rl, EngSrc2{{bxb(0, li), bxb(1, li)}, {xB, xB1}, {tag0, tag1}}, D, gw, ENG_GW, lane, p.ctl, dead, wh + 2);
-                else eng_gather_x(rl, bxb(1, li), layD, 0, D, tag1, xB1, gw, ENG_GW, lane, p.ctl, dead, wh + 2);
+                if (tail0) eng_gather_x2(rl, EngSrc2{{bxb(0, li), bxb(1, li)}, {xB, xB1}, {tag0, tag1}}, D, gw, ENG_GW, gl, p.ctl, dead, wh + 2);
+                else eng_gather_x(rl, bxb(1, li), layD, 0, D, tag1, xB1, gw, ENG_GW, gl, p.ctl, dead, wh + 2);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B3
-                if (tail0) eng_gather_x2(rl, EngSrc2{{bg(0, li), bg(1, li)}, {gS, gS1}, {tag0, tag1}}, F, gw, ENG_GW, lane, p.ctl, dead, wh + 3);
-                else if constexpr (FS::PK3) eng_gather3_x(rl, bg(1, li), F, tag1, gS1, gw, ENG_GW, lane, p.ctl, dead, wh + 3);
-                else eng_gather_x(rl, bg(1, li), layF, 0, F, tag1, gS1, gw, ENG_GW, lane, p.ctl, dead, wh + 3);
+                if constexpr (RES) {       // this wave's resident pairs of the layer (static register indices: one copy per layer)
+#pragma unroll
+                    for (int r = 0; r < RL; ++r)
+                        if (li == r) {
+                            eng_res_pin(res[r]);
+#pragma unroll
+                            for (int t = 0; t < NTD; ++t) res[r].gain[t] = fgain[t];
+                            if (tail0)
+                                eng_gemv2_part<NTD, 2, RF, PRO_RMSNORM, EPI_SWIGLU, ARRF>(res[r], xB, xB1, D, p.eps, nullptr, nullptr, nullptr, bg(0, li) + eng_pub(b, f_lo),
+                                                                                          bg(1, li) + eng_pub(b, f_lo), tag0, tag1, f_lo, f_hi, f_c_hi, f_hi, gw, lane, eo13);
+                            else
+                                eng_gemv_part<NTD, 2, RF, PRO_RMSNORM, EPI_SWIGLU, FS::PK3, ARRF>(res[r], xB1, D, p.eps, nullptr, nullptr, bg(1, li) + (FS::PK3 ? 0 : eng_pub(b, f_lo)),
+                                                                                           tag1, nullptr, f_lo, f_hi, f_c_hi, f_hi, gw, lane, eo13);
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (tail0) eng_gather_x2(rl, EngSrc2{{bg(0, li), bg(1, li)}, {gS, gS1}, {tag0, tag1}}, F, gw, ENG_GW, gl, p.ctl, dead, wh + 3);
+                else if constexpr (FS::PK3) eng_gather3_x(rl, bg(1, li), F, tag1, gS1, gw, ENG_GW, gl, p.ctl, dead, wh + 3);
+                else eng_gather_x(rl, bg(1, li), layF, 0, F, tag1, gS1, gw, ENG_GW, gl, p.ctl, dead, wh + 3);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B4
             }
         }
@@ -2286,16 +2373,23 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                 rcs[e] = d < hd ? p.rope[((size_t)cb * (hd >> 1) + (d >> 1)) * 2] : 1.f;
                 rsn[e] = d < hd ? p.rope[((size_t)cb * (hd >> 1) + (d >> 1)) * 2 + 1] : 0.f;
             }
+            int at = atid, dl = lane;      // (resident form: opaque per step, as gl per layer below - the draw's per-thread addresses)
+            if constexpr (RES) asm volatile("" : "+v"(at), "+v"(dl));
             EngDrawPre pre{};
             if (cb >= 1) {
                 sp.cb = cb;
                 sp.noise_off = p.noise_off1 + (long)(cb - 1) * p.noise_cb_stride;
-                pre = eng_draw_pre(sp, atid);
+                pre = eng_draw_pre(sp, at);
             }
             for (int li = (pair && cb == 1) ? nL : 0; li < nL; ++li) {
                 const EngLayer l = eng_layer(p.layers, li);
+                // resident form: the lane index is opaque per layer, so the ~40 per-lane poll addresses of a layer-step are formed
+                // where they are used (two instructions each) instead of living in registers beside the resident rows for the
+                // whole launch (hoisted as loop invariants they spill)
+                int gl = lane;
+                if constexpr (RES) asm volatile("" : "+v"(gl));
                 if (li > 0) {
-                    eng_gather_x(rl, bx(par, li), layD, 0, D, tag, xA, gw, ENG_GW, lane, p.ctl, dead, 1000 + cb * 64 + li * 8 + 0);
+                    eng_gather_x(rl, bx(par, li), layD, 0, D, tag, xA, gw, ENG_GW, gl, p.ctl, dead, 1000 + cb * 64 + li * 8 + 0);
                 } else if (cb <= 1) {
                     const float* src = cb == 0 ? p.hid : p.femb;        // plain f32 left by the launches before this one
                     for (int d = atid * 4; d < D; d += ENG_GW * 64 * 4) *reinterpret_cast<float4*>(xA + d) = *reinterpret_cast<const float4*>(src + d);
@@ -2338,36 +2432,62 @@ __global__ __launch_bounds__(ENG_THREADS) void fast_engine_kernel(FastEngP p) {
                 }
                 eng_barrier(); if (*dead) { alive = false; break; }     // B1
                 if (!(li == 0 && cb >= 2 && p.qkv0_tab))
-                    eng_gather_x(rl, bq(par, li), layQ, 0, QKVN, tag, qkvS, gw, ENG_GW, lane, p.ctl, dead, 1000 + cb * 64 + li * 8 + 1);
+                    eng_gather_x(rl, bq(par, li), layQ, 0, QKVN, tag, qkvS, gw, ENG_GW, gl, p.ctl, dead, 1000 + cb * 64 + li * 8 + 1);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B1b
+                if constexpr (RES) {
+                    // The resident rows of a layer are requested ONCE per launch: in the first pass, here - the attention and the
+                    // x' hand-off (no poll for ~1.5 us, none that can succeed for ~3.5) cover their arrival, so no later poll waits
+                    // behind a load of this wave.  (Requested at kernel entry they add 25 MB to the cold burst every CU starts
+                    // with, and the registration's atomics queue behind it: +6 us per launch, measured.)
+                    if (!pair && cb == 0) {
+#pragma unroll
+                        for (int r = 0; r < RL; ++r)
+                            if (li == r) eng_issue<false>(res[r], l.w13, (const bf16_t*)nullptr, D, f_c_hi, f_hi, gw, lane, p.nt);
+                    }
+#pragma unroll
+                    for (int t = 0; t < NTD; ++t) fgain[t] = eng_ldg16<false>(l.ffn_norm + t * 512 + lane * 8);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 eng_fast_attn_any<MAXCB, HDIM>(qkvS, kvS + (size_t)(li * 2) * p.ncb * KVW, kvS + (size_t)(li * 2 + 1) * p.ncb * KVW, yS, l.qn, l.kn,
                                          rcs, rsn, cb, p.ncb, H, Hkv, p.eps, p.scale, wave, ENG_WAVES, lane);
                 eng_barrier();                                          // B2
-                eng_gather_x(rl, bxb(par, li), layD, 0, D, tag, xB, gw, ENG_GW, lane, p.ctl, dead, 1000 + cb * 64 + li * 8 + 2);
+                eng_gather_x(rl, bxb(par, li), layD, 0, D, tag, xB, gw, ENG_GW, gl, p.ctl, dead, 1000 + cb * 64 + li * 8 + 2);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B3
-                if constexpr (FS::PK3) eng_gather3_x(rl, bg(par, li), F, tag, gS, gw, ENG_GW, lane, p.ctl, dead, 1000 + cb * 64 + li * 8 + 3);
-                else eng_gather_x(rl, bg(par, li), layF, 0, F, tag, gS, gw, ENG_GW, lane, p.ctl, dead, 1000 + cb * 64 + li * 8 + 3);
+                if constexpr (RES) {       // this wave's resident pairs of the layer (static register indices: one copy per layer)
+#pragma unroll
+                    for (int r = 0; r < RL; ++r)
+                        if (li == r) {
+                            eng_res_pin(res[r]);
+#pragma unroll
+                            for (int t = 0; t < NTD; ++t) res[r].gain[t] = fgain[t];
+                            eng_gemv_part<NTD, 2, RF, PRO_RMSNORM, EPI_SWIGLU, FS::PK3, ARRF>(res[r], xB, D, p.eps, nullptr, nullptr, bg(par, li) + (FS::PK3 ? 0 : eng_pub(b, f_lo)),
+                                                                                       tag, nullptr, f_lo, f_hi, f_c_hi, f_hi, gw, lane, eo13);
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (FS::PK3) eng_gather3_x(rl, bg(par, li), F, tag, gS, gw, ENG_GW, gl, p.ctl, dead, 1000 + cb * 64 + li * 8 + 3);
+                else eng_gather_x(rl, bg(par, li), layF, 0, F, tag, gS, gw, ENG_GW, gl, p.ctl, dead, 1000 + cb * 64 + li * 8 + 3);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B4
             }
             if (!alive) break;
             if (cb >= 1) {
-                eng_gather_x(rl, bx(par, nL), layD, 0, D, tag, xA, gw, ENG_GW, lane, p.ctl, dead, 1000 + cb * 64 + 56);
+                eng_gather_x(rl, bx(par, nL), layD, 0, D, tag, xA, gw, ENG_GW, dl, p.ctl, dead, 1000 + cb * 64 + 56);
                 eng_barrier(); if (*dead) { alive = false; break; }     // B5
                 ENG_GSTAMP(10);
                 {
                     // ---- the draw of codebook cb (inference.py:134-149).  EVERY workgroup gathers the logits and draws (the
                     // draw is a deterministic function of logits, frame and seed): no hand-off of the code, the next step's
                     // embedding row can be fetched at once.  Workgroup drawer(cb) alone does the frame bookkeeping (finish_draw).
-                    eng_gather_x(rl, blog(par), layV, 0, V, tag, logS, gw, ENG_GW, lane, p.ctl, dead, 1000 + cb * 64 + 57);
+                    eng_gather_x(rl, blog(par), layV, 0, V, tag, logS, gw, ENG_GW, dl, p.ctl, dead, 1000 + cb * 64 + 57);
                     sub.n = 0;
-                    if (atid == 0) *sub_count = *dead ? 1 : 0;       // (a workgroup that gave up draws nothing: one barrier, then on)
-                    sub.sync(lane);
+                    if (at == 0) *sub_count = *dead ? 1 : 0;       // (a workgroup that gave up draws nothing: one barrier, then on)
+                    sub.sync(dl);
                     ENG_GSTAMP(11);
                     if (*reinterpret_cast<volatile int*>(sub_count) == 0) {
                         const int last = cb == p.ncb - 1;
                         const int nfv = pre.nfv;
                         EngSampLds S{redbuf, pen_id, pen_val, amv, ami, wcnt, prL, keyL, cut};
-                        const int code = eng_sample_small(sp, pre, logS, S, sub, atid, lane, gw,
+                        const int code = eng_sample_small(sp, pre, logS, S, sub, at, dl, gw,
                                                           p.stamps ? p.stamps + (((size_t)b * p.ncb + cb) * nL + nL - 1) * 16 : nullptr);
                         ENG_GSTAMP(14);
                         const int R = p.ncb + 1;

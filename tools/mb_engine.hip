@@ -1,6 +1,7 @@
 // Timing harness for the persistent slow-stack engine (csrc/frame_engine.h) on synthetic weights at the s1-mini widths:
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -Ifish-tts_amd/csrc tools/mb_engine.hip -o tools/bin/mb_engine
 //   tools/bin/mb_engine [n_layer=28] [pos=150] [nsplit=8]
+//   tools/bin/mb_engine 0        the codebook loop: plain / with stamps / with NO weight loads; NO_RESIDENT=1: its all-streaming form
 // Prints the kernel time per launch and, from the in-kernel s_memrealtime stamps of workgroup 0 and of one attention
 // workgroup, where a layer's time goes.  Correctness is NOT checked here (tests/test_engine_gpu.py does that).
 #include "frame_engine.h"
@@ -224,22 +225,26 @@ static int run_fast(int nb, hipStream_t s) {
     }
     size_t ldsb = eng_fast_lds_bytes(D, qkvN, HD, F, V, nL, ncb, Hkv * hd, p.pair != 0);
     printf("paired first pass: %d, LDS %zu bytes\n", p.pair, ldsb);
-    CK(hipFuncSetAttribute((const void*)fast_engine_kernel<EngFastS1, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
+    const bool resident = getenv("NO_RESIDENT") == nullptr;      // W13 pairs resident in the gathering waves' registers (the product's default)
+    void (*const loop)(FastEngP) = resident ? fast_engine_kernel<EngFastS1, 10, true> : fast_engine_kernel<EngFastS1, 10, false>;
+    printf("resident set: %d of %d W13 pairs per workgroup, %d layers\n", resident ? EngFastS1::RESF * ENG_GW : 0, F / ENG_NB, resident ? EngFastS1::RESL : 0);
+    CK(hipFuncSetAttribute((const void*)loop, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
     CK(hipStreamSynchronize(s));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    for (int mode = 0; mode < 2; ++mode) {
-        p.stamps = mode ? stamps : nullptr;
-        float sum = 0.f; const int reps = 10;
+    for (int mode = 0; mode < 3; ++mode) {      // plain, with stamps, NO weight loads (timing only: the rows are zeros)
+        p.stamps = mode == 1 ? stamps : nullptr;
+        p.nt = mode == 2 ? 2 : 0;
+        float sum = 0.f, best = 1e9f; const int reps = 10;
         for (int r = 0; r < reps + 3; ++r) {
             CK(hipMemcpyAsync(sp.nf, &one, 4, hipMemcpyHostToDevice, s));
             CK(hipEventRecord(e0, s));
-            fast_engine_kernel<EngFastS1, 10><<<nb, ENG_THREADS, ldsb, s>>>(p);
+            loop<<<nb, ENG_THREADS, ldsb, s>>>(p);
             CK(hipEventRecord(e1, s)); CK(hipStreamSynchronize(s));
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
-            if (r >= 3) sum += ms;
+            if (r >= 3) { sum += ms; best = std::min(best, ms); }
         }
         unsigned h[4]; CK(hipMemcpy(h, p.ctl, 16, hipMemcpyDeviceToHost));
-        printf("fast loop %-12s: %.1f us per launch = %.2f us per layer-step%s\n", mode ? "with stamps" : "plain", sum / reps * 1e3, sum / reps * 1e3 / (nL * ncb),
+        printf("fast loop %-15s: %.1f us per launch (best %.1f) = %.2f us per layer-step%s\n", mode == 0 ? "plain" : mode == 1 ? "with stamps" : "NO weight loads", sum / reps * 1e3, best * 1e3, sum / reps * 1e3 / (nL * ncb),
                h[ENG_CTL_ABORT] ? "  ABORTED" : "");
         if (h[ENG_CTL_ABORT]) { printf("abort at phase %u\n", h[ENG_CTL_WHERE]); return 1; }
     }
@@ -297,6 +302,17 @@ static int run_fast(int nb, hipStream_t s) {
         { unsigned long long e = 0; for (int b = 0; b < nb; ++b) e = std::max(e, st[(((size_t)b * ncb + cb0) * nL + nL - 1) * 16 + 8]); pass0 = (double)e - (double)first; }
         printf("first B1 of the launch -> last draw: %.1f us (kernel: see above); first pass (layers only): %.1f us\n",
                ((double)last - (double)first) / 100.0, pass0 / 100.0);
+        if (p.pair) {     // the launch's head: entry and B0 stamps live in the (otherwise unused) row of step 0, layer 0
+            unsigned long long e_lo = ~0ull, e_hi = 0, b0_lo = ~0ull, b0_hi = 0, b1_hi = 0;
+            for (int b = 0; b < nb; ++b) {
+                const unsigned long long* a = &st[((size_t)b * ncb) * nL * 16];
+                e_lo = std::min(e_lo, a[15]); e_hi = std::max(e_hi, a[15]); b0_lo = std::min(b0_lo, a[14]); b0_hi = std::max(b0_hi, a[14]);
+                b1_hi = std::max(b1_hi, st[(((size_t)b * ncb + 1) * nL + 0) * 16 + 0]);
+            }
+            printf("launch head, us after the first workgroup's entry: last entry %.2f, registered + B0 %.2f .. %.2f, first B1 %.2f .. %.2f\n",
+                   ((double)e_hi - (double)e_lo) / 100.0, ((double)b0_lo - (double)e_lo) / 100.0, ((double)b0_hi - (double)e_lo) / 100.0,
+                   ((double)first - (double)e_lo) / 100.0, ((double)b1_hi - (double)e_lo) / 100.0);
+        }
     }
     printf("head + draw + code hand-off between two steps: %.2f us\n", gap / gc / 100.0);
     {   // inside that gap (gathering wave 0): chip-wide medians relative to the last workgroup's W2 of the step
