@@ -92,6 +92,16 @@ class ft_test_draw_io(C.Structure):
                                            "xo_femb", "xo_x", "cut", "chunk_cnt", "part_idx")])
 
 
+class ft_test_engine_io(C.Structure):
+    _fields_ = ([("which", C.c_int32), ("copies", C.c_int32), ("epoch", C.c_uint32)] +
+                [(n, C.c_int32) for n in ("epoch_step", "n_layer", "D", "QKVN", "HD", "F", "V", "ncb", "H", "Hkv", "hd", "pk3", "pair",
+                                          "qkv0", "resident", "relay", "xl", "nsplit", "line")] +
+                [(n, C.c_void_p) for n in ("x", "x_tag", "qkv", "qkv_tag", "xb", "xb_tag", "g", "g_tag", "g3", "g3_tag", "log",
+                                           "log_tag", "y", "y_tag", "code", "part", "part_tag")] +
+                [(n, C.c_int32) for n in ("kv_layer", "kv_slot", "kv_rows", "tab_row")] +
+                [("kv_k", C.c_void_p), ("kv_v", C.c_void_p), ("tab", C.c_void_p)])
+
+
 # every symbol include/fishtts_hip.h declares: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -180,6 +190,7 @@ SYMBOLS = {
     "ft_ar_frame_path": (C.c_char_p, [_P]),
     "ft_test_engine_fault": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "ft_test_ar_attn_plan": (C.c_int32, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ft_test_engine_handoffs": (C.c_int32, [_P, C.POINTER(ft_test_engine_io)]),
     "ft_test_sample": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(ft_sampling), _P, _P, _P]),
     "ft_test_draw": (C.c_int32, [_P, C.POINTER(ft_test_draw_io)]),
     "ft_test_qkv0_tab": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),

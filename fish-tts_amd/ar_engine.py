@@ -177,6 +177,52 @@ class ARHipEngine:
         self._check(self.lib.ft_test_ar_attn_plan(self._h, C.byref(n), C.byref(x), C.byref(s)), "ft_test_ar_attn_plan")
         return n.value, x.value, s.value
 
+    def engine_handoffs(self, which: int, vectors: bool = True, kv=None, tab_row=None):
+        """Test hook (ft_test_engine_handoffs): what the frame engine's launches left in their hand-off buffers.  which: 0 the
+        slow stack, 1 the codebook loop.  Returns a dict: the geometry words of the hook's struct as ints (copies = 0: that
+        engine is off) and, with `vectors` on a context whose engine is on, uint16 (values, tags) pairs x, qkv, xb, g, g3, log
+        (loop) or y (slow stack) shaped (copies, 2, layers, n), code (copies, ncb, line) uint32, part / part_tag
+        (2, H, nsplit, hd + 2) f32 / uint32.  kv = (layer, slot, rows): also kv_k, kv_v (Hkv, rows, hd) uint16, the slow
+        cache (which = 0) or the launch path's codebook-loop cache (which = 1).  tab_row: also tab (QKVN,) uint16, that row
+        of the loop's own layer-0 q k v table."""
+        io = L.ft_test_engine_io()
+        io.which, io.copies = which, 0
+        self._check(self.lib.ft_test_engine_handoffs(self._h, C.byref(io)), "ft_test_engine_handoffs")
+        geo = ("copies", "epoch", "epoch_step", "n_layer", "D", "QKVN", "HD", "F", "V", "ncb", "H", "Hkv", "hd", "pk3", "pair",
+               "qkv0", "resident", "relay", "xl", "nsplit", "line")
+        out = {k: int(getattr(io, k)) for k in geo}
+        ptr = lambda t: t.ctypes.data_as(C.c_void_p)
+        if vectors and io.copies > 0:
+            cp, nl = io.copies, io.n_layer
+            shapes = dict(x=(nl + 1 if which else 1, io.D), qkv=(nl if which else 1, io.QKVN), xb=(nl if which else 1, io.D),
+                          g=(nl if which else 1, io.F))
+            if io.pk3:
+                shapes["g3"] = shapes["g"]
+            shapes["log" if which else "y"] = (1, io.V if which else io.HD)
+            for name, (layers, n) in shapes.items():
+                v, t = (np.zeros((cp, 2, layers, n), dtype=np.uint16) for _ in range(2))
+                out[name], out[name + "_tag"] = v, t
+                setattr(io, name, ptr(v)); setattr(io, name + "_tag", ptr(t))
+            if which:
+                out["code"] = np.zeros((cp, io.ncb, io.line), dtype=np.uint32)
+                io.code = ptr(out["code"])
+            else:
+                out["part"] = np.zeros((2, io.H, io.nsplit, io.hd + 2), dtype=np.float32)
+                out["part_tag"] = np.zeros((2, io.H, io.nsplit, io.hd + 2), dtype=np.uint32)
+                io.part, io.part_tag = ptr(out["part"]), ptr(out["part_tag"])
+        if kv is not None:
+            io.kv_layer, io.kv_slot, io.kv_rows = (int(v) for v in kv)
+            out["kv_k"], out["kv_v"] = (np.zeros((io.Hkv, io.kv_rows, io.hd), dtype=np.uint16) for _ in range(2))
+            io.kv_k, io.kv_v = ptr(out["kv_k"]), ptr(out["kv_v"])
+        if tab_row is not None:
+            io.tab_row = int(tab_row)
+            out["tab"] = np.zeros(io.QKVN, dtype=np.uint16)
+            io.tab = ptr(out["tab"])
+        if (vectors and io.copies > 0) or kv is not None or tab_row is not None:
+            self._check(self.lib.ft_test_engine_handoffs(self._h, C.byref(io)), "ft_test_engine_handoffs")
+            out["epoch"] = int(io.epoch)
+        return out
+
     # ------------------------------------------------------------------ primitives
     @staticmethod
     def _sampling(temperature, top_p, repetition_penalty, seed=0, ban_eos=False) -> L.ft_sampling:

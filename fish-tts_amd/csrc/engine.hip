@@ -2136,6 +2136,155 @@ extern "C" ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t*
     return FT_OK;
 }
 
+// Test hook: the hand-off vectors the engine's launches left behind, and K/V rows (include/fishtts_hip_test.h).  Host code:
+// one copy of each pool to the host, then the decoding below with the layout rules of frame_engine.h.
+namespace {
+struct EngDump {
+    const unsigned* w;      // one copy of a pool on the host
+    // n plain granules {tag16 | bf16} of a vector stored linearly (EngLayout::off is the identity) from word `at`
+    void plain(size_t at, int n, uint16_t* v, uint16_t* t) const {
+        for (int i = 0; i < n; ++i) { v[i] = (uint16_t)(w[at + i] & 0xffffu); t[i] = (uint16_t)(w[at + i] >> 16); }
+    }
+    // n values as PK3 granules {v0 | v1 << 16, v2 | tag << 16}: granule j holds values 3 j .. 3 j + 2 under one tag
+    void pk3(size_t at, int n, uint16_t* v, uint16_t* t) const {
+        for (int j = 0; j < n / 3; ++j) {
+            const unsigned w0 = w[at + 2 * j], w1 = w[at + 2 * j + 1];
+            v[3 * j] = (uint16_t)(w0 & 0xffffu); v[3 * j + 1] = (uint16_t)(w0 >> 16); v[3 * j + 2] = (uint16_t)(w1 & 0xffffu);
+            t[3 * j] = t[3 * j + 1] = t[3 * j + 2] = (uint16_t)(w1 >> 16);
+        }
+    }
+};
+}  // namespace
+
+extern "C" ft_status ft_test_engine_handoffs(ft_ctx* ctx, ft_test_engine_io* io) {
+    FT_TRY(ar_ready(ctx));
+    if (!io || (io->which != 0 && io->which != 1)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: bad argument");
+    const ft_ar_config& c = ctx->c;
+    const bool fast = io->which == 1;
+    const bool on = fast ? ctx->eng_fast_on : ctx->eng_on;
+    const int room = io->copies;
+    const int nL = fast ? c.n_fast_layer : c.n_layer;
+    const int H = fast ? c.fast_n_head : c.n_head, Hkv = fast ? c.fast_n_local_heads : c.n_local_heads;
+    const int hd = fast ? c.fast_head_dim : c.head_dim;
+    const int D = fast ? c.fast_dim : c.dim, F = fast ? c.fast_intermediate_size : c.intermediate_size;
+    const int HD = H * hd, QKVN = (H + 2 * Hkv) * hd, V = fast ? ctx->fastV : 0;
+    const int nb = ctx->eng_nb;
+    FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    io->copies = on ? (ctx->eng_relay ? 9 : 1) : 0;
+    io->epoch = 0; io->epoch_step = ENG_EPOCH_STEP; io->line = ENG_LINE;
+    io->n_layer = nL; io->D = D; io->QKVN = QKVN; io->HD = HD; io->F = F; io->V = V; io->ncb = c.num_codebooks;
+    io->H = H; io->Hkv = Hkv; io->hd = hd;
+    io->pk3 = on && F % 384 == 0 && nb > 0 && (F / nb) % 3 == 0 ? 1 : 0;      // EngSlowShape / EngFastShape::PK3
+    io->pair = fast && on && ctx->eng_pair && c.num_codebooks >= 2 ? 1 : 0;
+    io->qkv0 = fast && on && ctx->eng_qkv0_tab ? 1 : 0;
+    io->resident = 0;
+    if (fast && on) {
+        int n = 0;
+        const EngFastEntry* tab = eng_fast_shapes(&n);
+        for (int i = 0; i < n; ++i) if (tab[i].resident && (const void*)tab[i].resident == ctx->eng_fast_fn) io->resident = 1;
+    }
+    io->relay = on && ctx->eng_relay ? 1 : 0;
+    io->xl = !fast && on && ctx->eng_xl ? 1 : 0;
+    io->nsplit = fast ? 1 : ctx->nsplit;
+    if (on) FT_HIP(ctx, hipMemcpy(&io->epoch, ctx->eng_ctl + ENG_CTL_EPOCH, sizeof(unsigned), hipMemcpyDeviceToHost));
+    const bool want = io->x || io->qkv || io->xb || io->g || io->g3 || io->log || io->y || io->code || io->part;
+    if (want && !on) return ft_fail(ctx, FT_ERR_STATE, "ft_test_engine_handoffs: that engine is off on this context");
+    if (want && room < io->copies) return ft_fail(ctx, FT_ERR_STATE, "ft_test_engine_handoffs: room for fewer copies than exist");
+    if (want && ((io->x && !io->x_tag) || (io->qkv && !io->qkv_tag) || (io->xb && !io->xb_tag) || (io->g && !io->g_tag) ||
+                 (io->g3 && !io->g3_tag) || (io->log && !io->log_tag) || (io->y && !io->y_tag) || (io->part && !io->part_tag)))
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: a value array without its tag array");
+    if (want) {
+        const size_t VW = (size_t)nb * ENG_LINE;                      // words per vector buffer (the kernels' VSTR)
+        const size_t words = fast ? ctx->eng_fast_words : ctx->eng_pool_words;
+        const unsigned* dev = fast ? ctx->eng_fast_g : ctx->eng_gx;
+        std::vector<unsigned> host(words);
+        const size_t L = (size_t)nL;
+        // word offsets of the vectors inside one copy of the pool, as the launches lay them out
+        // (enqueue_fast_engine: gx gqkv gxb gg glog gcode; eng_setup_try: gx gxb gg gy gqkv)
+        const size_t f_gx = 0, f_gq = 2 * (L + 1) * VW, f_gxb = f_gq + 2 * L * VW, f_gg = f_gxb + 2 * L * VW, f_log = f_gg + 2 * L * VW,
+                     f_code = f_log + 2 * VW;
+        const size_t s_gx = 0, s_gxb = (L + 1) * VW, s_gg = s_gxb + L * VW, s_gy = s_gg + L * VW, s_gq = s_gy + L * (size_t)HD;
+        const int ns = io->nsplit > 0 ? io->nsplit : 1, G = H / Hkv, epb = hd / ns;
+        for (int cp = 0; cp < io->copies; ++cp) {
+            FT_HIP(ctx, hipMemcpy(host.data(), dev + (size_t)cp * words, words * sizeof(unsigned), hipMemcpyDeviceToHost));
+            const EngDump d{host.data()};
+            for (int par = 0; par < 2; ++par) {
+                if (fast) {
+                    for (int l = 0; l <= nL; ++l) {
+                        const size_t o = ((size_t)cp * 2 + par) * (L + 1) + l;
+                        if (io->x) d.plain(f_gx + ((size_t)par * (L + 1) + l) * VW, D, io->x + o * D, io->x_tag + o * D);
+                        if (l == nL) continue;
+                        const size_t q = ((size_t)cp * 2 + par) * L + l, b = ((size_t)par * L + l) * VW;
+                        if (io->qkv) d.plain(f_gq + b, QKVN, io->qkv + q * QKVN, io->qkv_tag + q * QKVN);
+                        if (io->xb) d.plain(f_gxb + b, D, io->xb + q * D, io->xb_tag + q * D);
+                        if (io->g) d.plain(f_gg + b, F, io->g + q * F, io->g_tag + q * F);
+                        if (io->g3 && io->pk3) d.pk3(f_gg + b, F, io->g3 + q * F, io->g3_tag + q * F);
+                    }
+                    const size_t o = (size_t)cp * 2 + par;
+                    if (io->log) d.plain(f_log + (size_t)par * VW, V, io->log + o * V, io->log_tag + o * V);
+                } else {
+                    const size_t o = (size_t)cp * 2 + par;
+                    const bool have = par < nL;                           // gqkv, gxb, gg, gy hold n_layer buffers, gx one more
+                    auto zero = [&](uint16_t* v, uint16_t* t, size_t n) { if (v) { memset(v + o * n, 0, n * 2); memset(t + o * n, 0, n * 2); } };
+                    if (io->x) d.plain(s_gx + (size_t)par * VW, D, io->x + o * D, io->x_tag + o * D);
+                    if (!have) {
+                        zero(io->qkv, io->qkv_tag, QKVN); zero(io->xb, io->xb_tag, D); zero(io->g, io->g_tag, F);
+                        zero(io->g3, io->g3_tag, F); zero(io->y, io->y_tag, HD);
+                        continue;
+                    }
+                    if (io->qkv) d.plain(s_gq + (size_t)par * VW, QKVN, io->qkv + o * QKVN, io->qkv_tag + o * QKVN);
+                    if (io->xb) d.plain(s_gxb + (size_t)par * VW, D, io->xb + o * D, io->xb_tag + o * D);
+                    if (io->g) d.plain(s_gg + (size_t)par * VW, F, io->g + o * F, io->g_tag + o * F);
+                    if (io->g3 && io->pk3) d.pk3(s_gg + (size_t)par * VW, F, io->g3 + o * F, io->g3_tag + o * F);
+                    if (io->y) {
+                        // y is stored per attention workgroup, [kvh][split][g][hd / nsplit] (slow_engine_kernel: ymap)
+                        for (int i = 0; i < HD; ++i) {
+                            const int a2 = i / (G * epb), r2 = i % (G * epb), g2 = r2 / epb, eo = r2 % epb;
+                            const int u = ((a2 / ns) * G + g2) * hd + (a2 % ns) * epb + eo;
+                            const unsigned wv = host[s_gy + (size_t)par * HD + i];
+                            io->y[o * HD + u] = (uint16_t)(wv & 0xffffu); io->y_tag[o * HD + u] = (uint16_t)(wv >> 16);
+                        }
+                    }
+                }
+            }
+            if (fast && io->code)
+                memcpy(io->code + (size_t)cp * c.num_codebooks * ENG_LINE, host.data() + f_code, (size_t)c.num_codebooks * ENG_LINE * sizeof(unsigned));
+        }
+        if (!fast && io->part) {
+            const size_t per = (size_t)H * ns * (hd + 2);
+            const int pars = nL < 2 ? nL : 2;
+            std::vector<unsigned long long> hp(per * pars);
+            FT_HIP(ctx, hipMemcpy(hp.data(), ctx->eng_gpart, hp.size() * 8, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < 2 * per; ++i) {
+                const unsigned long long g = i < hp.size() ? hp[i] : 0ull;
+                const unsigned lo = (unsigned)(g & 0xffffffffull);
+                memcpy(io->part + i, &lo, 4);
+                io->part_tag[i] = (unsigned)(g >> 32);
+            }
+        }
+    }
+    if (io->tab) {
+        if (!fast || !on || !ctx->eng_qkv0_tab) return ft_fail(ctx, FT_ERR_STATE, "ft_test_engine_handoffs: this context built no layer-0 q k v table for the loop");
+        if (io->tab_row < 0 || io->tab_row >= ctx->fastV) return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: bad table row");
+        FT_HIP(ctx, hipMemcpy(io->tab, (const bf16_t*)ctx->eng_qkv0_tab + (size_t)io->tab_row * QKVN, (size_t)QKVN * sizeof(bf16_t), hipMemcpyDeviceToHost));
+    }
+    if (io->kv_k || io->kv_v) {
+        if (!io->kv_k || !io->kv_v || ctx->esz != 2) return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: K/V needs both arrays and a 16-bit context");
+        const int rows_max = fast ? c.num_codebooks : ctx->n_slots;
+        if (io->kv_layer < 0 || io->kv_layer >= nL || io->kv_slot < 0 || io->kv_slot >= c.max_batch || io->kv_rows < 1 || io->kv_rows > rows_max)
+            return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: bad K/V layer, slot or row count");
+        const FtLayer& l = fast ? ctx->flayers[io->kv_layer] : ctx->layers[io->kv_layer];
+        const size_t mstr = fast ? ctx->fcache_m_stride : ctx->cache_m_stride;
+        for (int h = 0; h < Hkv; ++h) {
+            const size_t src = (size_t)io->kv_slot * mstr + (size_t)h * rows_max * hd, dst = (size_t)h * io->kv_rows * hd;
+            const size_t bytes = (size_t)io->kv_rows * hd * 2;
+            FT_HIP(ctx, hipMemcpy(io->kv_k + dst, (const char*)l.kc + src * 2, bytes, hipMemcpyDeviceToHost));
+            FT_HIP(ctx, hipMemcpy(io->kv_v + dst, (const char*)l.vc + src * 2, bytes, hipMemcpyDeviceToHost));
+        }
+    }
+    return FT_OK;
+}
+
 extern "C" ft_status ft_ar_park(ft_ctx* ctx, int32_t slot) {
     FT_TRY(ar_ready(ctx));
     const ft_ar_config& c = ctx->c;

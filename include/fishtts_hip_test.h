@@ -44,6 +44,46 @@ ft_status ft_test_engine_fault(ft_ctx* ctx, int32_t which, int32_t wg, int32_t s
  * *n_slots: the rows of the KV cache (max_seq_len rounded up to 8).  Any pointer may be NULL. */
 ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t* xl, int32_t* n_slots);
 
+/* Test hook (host code only: it synchronises the context's stream and copies device memory out; no kernel, no branch in a
+ * kernel, nothing on the frame path): the hand-off vectors the frame engine's launches LEFT in device memory, decoded through
+ * the kernels' own layout constants (frame_engine.h: ENG_LINE, EngLayout, the PK3 granules, VSTR, the y map of the slow
+ * attention) into one (bf16 pattern, 16-bit tag) pair per unit.  Every hand-off buffer is double-buffered - the codebook
+ * loop's by step parity with one buffer per layer, the slow stack's by layer parity - so after a launch the loop's last two
+ * steps at every layer and the slow stack's last two layers are there.  A unit written by step / layer i of a launch that read
+ * epoch word e carries the tag 0x8000 | ((e + i) & 0x7fff); every engine launch, slow or loop, advances the word by
+ * epoch_step, so the last launch of a context read `epoch - epoch_step` (the slow launch of a whole frame: one more back).
+ * which: 0 the slow stack, 1 the codebook loop.  copies (in): the copies of each vector the arrays have room for; (out) what
+ * exists: 0 that engine is off, else 1 (copy 0: the source buffers) + 8 with the relay on (copy 1 + x: XCD x's replica).
+ * Arrays (any may be NULL), uint16 values and tags, [copies][2 parities][layers][n]; parities the context did not allocate
+ * (a one-layer slow stack) read as zeros, a tag no launch writes:
+ *   which = 1: x [n_layer + 1][D] (entry n_layer: the stack's output), qkv [n_layer][QKVN], xb [n_layer][D], g [n_layer][F]
+ *      read as plain granules, g3 [n_layer][F] read as PK3 triples (pk3 = 1 only; a triple shares its tag; which of the two
+ *      forms a (step, layer) wrote is the kernel's: the paired first pass writes plain granules wherever position 0 goes on
+ *      after the attention), log [1][V]; code: [copies][ncb][ENG_LINE] raw words of the code lines.
+ *   which = 0: x, qkv, xb, g / g3 with layers = 1; y [1][HD]: unit i of the buffer at ymap(i) (the head-major order the
+ *      Wo phase reads, for the split count of the last call); part [2][H][nsplit][hd + 2] f32 with part_tag (32-bit tags
+ *      0x80000000 | (e + layer)): the split partials (O, then m, l), source only - they are not relayed.
+ * K/V (kv_k and kv_v both non-NULL; works on a context whose engine is off as well): which = 0: rows [0, kv_rows) of slow
+ * layer kv_layer of slot kv_slot, [Hkv][kv_rows][hd]; which = 1: the launch path's codebook-loop cache (fast_attn_kernel's
+ * kc / vc) of fast layer kv_layer, [fast Hkv][kv_rows <= ncb][fast hd].  Bit patterns of the context's 16-bit type.
+ * tab (which = 1, qkv0 = 1): row tab_row of the LOOP's own table of layer 0's q k v by drawn code (eng_qkv0_table_kernel;
+ * ft_test_qkv0_tab reads the lock-step batches' table, another buffer built by another kernel), [QKVN] bf16 patterns.
+ * FT_ERR_ARG: a bad which / layer / slot / row count, an f32 context asked for K/V; FT_ERR_STATE: a vector array on a context
+ * whose engine of that kind is off, fewer copies than exist, a table row where there is no table. */
+typedef struct ft_test_engine_io {
+    int32_t which, copies;
+    uint32_t epoch;
+    int32_t epoch_step, n_layer, D, QKVN, HD, F, V, ncb, H, Hkv, hd;
+    int32_t pk3, pair, qkv0, resident, relay, xl, nsplit, line;
+    uint16_t *x, *x_tag, *qkv, *qkv_tag, *xb, *xb_tag, *g, *g_tag, *g3, *g3_tag, *log, *log_tag, *y, *y_tag;
+    uint32_t* code;
+    float* part;
+    uint32_t* part_tag;
+    int32_t kv_layer, kv_slot, kv_rows, tab_row;
+    uint16_t *kv_k, *kv_v, *tab;
+} ft_test_engine_io;
+ft_status ft_test_engine_handoffs(ft_ctx* ctx, ft_test_engine_io* io);
+
 /* Test hook: one draw of the sampling kernel (inference.py:30-80) on caller-supplied logits.
  * cb = 0 draws from `vocab_size` logits, cb >= 1 from min(1024, codebook_size); window is the
  * (num_codebooks+1) x 16 penalty window of inference.py:187-191 or NULL (no penalty); q the Exp(1)

@@ -621,9 +621,11 @@ class FastRef:
     v: torch.Tensor
 
 
-def fast_attn_ref(fmt: str, qkv, c: int, qn, kn, kc, vc, tab, H: int, Hkv: int, hd: int, eps: float = 1e-6) -> FastRef:
+def fast_attn_ref(fmt: str, qkv, c: int, qn, kn, kc, vc, tab, H: int, Hkv: int, hd: int, eps: float = 1e-6,
+                  k_hist_err=None) -> FastRef:
     """One fast_attn_kernel launch at codebook position c: qkv [M, (H + 2 Hkv) hd], kc / vc [M, Hkv, ncb, hd] (rows < c read),
-    tab [ncb, hd / 2, 2]."""
+    tab [ncb, hd / 2, 2].  k_hist_err [M, Hkv, c, hd]: how far the K rows the device read may lie from kc's (rows that are
+    themselves restated, not read back: the reach of their last rounding); it joins the scores as the new row's ek does."""
     qkv, tab = qkv.to(F64), tab.to(F64)
     qn = None if qn is None else qn.to(F64)
     kn = None if kn is None else kn.to(F64)
@@ -642,6 +644,9 @@ def fast_attn_ref(fmt: str, qkv, c: int, qn, kn, kc, vc, tab, H: int, Hkv: int, 
         ed = torch.einsum("hd,hnd->hn", eq, K.abs()) + 8 * U * torch.einsum("hd,hnd->hn", qr.abs(), K.abs())
         ekh = ek.repeat_interleave(G, dim=0)
         ed[:, c] += (qr.abs() * ekh).sum(-1) + (eq * ekh).sum(-1)
+        if k_hist_err is not None and c > 0:
+            eh = k_hist_err[m].to(F64).repeat_interleave(G, dim=0)                                           # [H, c, hd]
+            ed[:, :c] += torch.einsum("hd,hnd->hn", qr.abs() + eq, eh)
         dr, e1 = rch(d, ed, fmt)
         s = dr * scale
         sr, e_s = rch(s, scale * e1 + U * s.abs(), fmt)
