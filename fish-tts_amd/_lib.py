@@ -202,6 +202,11 @@ SYMBOLS = {
     "ft_test_codec_trace_launch": (C.c_int32, [_P, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     "ft_test_codec_trace_buffer": (C.c_int32, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int64), _P]),
+    "ft_test_ar_trace_arm": (C.c_int32, [_P, C.c_int32, C.c_int32]),
+    "ft_test_ar_trace_count": (C.c_int32, [_P, _P]),
+    "ft_test_ar_trace_launch": (C.c_int32, [_P, C.c_int32, C.c_char_p, C.c_int32, _P]),
+    "ft_test_ar_trace_buffer": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P]),
+    "ft_test_ar_trace_state": (C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "ft_test_wide_linear": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
                                         _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ft_test_wide_attn": (C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),

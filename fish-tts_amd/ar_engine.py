@@ -212,7 +212,7 @@ class ARHipEngine:
                 io.part, io.part_tag = ptr(out["part"]), ptr(out["part_tag"])
         if kv is not None:
             io.kv_layer, io.kv_slot, io.kv_rows = (int(v) for v in kv)
-            out["kv_k"], out["kv_v"] = (np.zeros((io.Hkv, io.kv_rows, io.hd), dtype=np.uint16) for _ in range(2))
+            out["kv_k"], out["kv_v"] = (np.zeros((io.Hkv, io.kv_rows, io.hd), dtype=self._wt()) for _ in range(2))
             io.kv_k, io.kv_v = ptr(out["kv_k"]), ptr(out["kv_v"])
         if tab_row is not None:
             io.tab_row = int(tab_row)
@@ -594,6 +594,86 @@ class ARHipEngine:
         if form == 0:
             return y[:M, :H * hd].copy(), y[:M, H * hd:].view(np.uint32).copy(), y[M].view(np.uint32).copy(), kc, vc
         return yb, kc, vc
+
+    # ------------------------------------------------------------------ launch trace of a frame (test hook)
+    def trace_arm(self, first: int = 0, count: int = 1 << 30) -> None:
+        """Test hook (ft_test_ar_trace_arm): the next decode(1, ...) or first-frames call records one entry per launch; the
+        entries [first, first + count) keep host copies of every buffer they wrote."""
+        self._check(self.lib.ft_test_ar_trace_arm(self._h, first, count), "ft_test_ar_trace_arm")
+
+    def trace_read(self):
+        """Test hook: the last traced call as a dict: kind (1 a decode frame, 2 first frames), m0, M, launches - a list of dicts
+        name, m0, rows, cols, cls (4 ints), held, bufs {buffer id: array} (f32 / int32 (rows, cols); the octet-major 16-bit
+        buffers as uint16 (width / 8, xo_ldm, 8)) - and state: [before, after], each a dict tok (MB, R), pos, nf, done (MB,),
+        seq (MB, R, cap); begin: {buffer id: array}, every traceable buffer as the call found it.  The copies are handed over:
+        a second read finds none."""
+        info = np.zeros(5, dtype=np.int32)
+        n = self.lib.ft_test_ar_trace_count(self._h, info.ctypes.data_as(C.c_void_p))
+        if n < 0:
+            raise HipError("the launch trace failed to copy a buffer")
+        MB, R, cap = self.max_batch, self.R, self.max_new_tokens + 24
+        launches = []
+        name, li, bi = C.create_string_buffer(64), np.zeros(9, dtype=np.int32), np.zeros(4, dtype=np.int32)
+        for i in range(-1, n):
+            if i < 0:                                   # the record before the first launch: every buffer as the call found it
+                rec = dict(name="begin", m0=0, rows=0, cols=0, held=True, cls=(-1,) * 4, bufs={})
+                li[3] = info[4]
+            else:
+                self._check(self.lib.ft_test_ar_trace_launch(self._h, i, name, 64, li.ctypes.data_as(C.c_void_p)), "ft_test_ar_trace_launch")
+                rec = dict(name=name.value.decode(), m0=int(li[0]), rows=int(li[1]), cols=int(li[2]), held=bool(li[4]),
+                           cls=tuple(int(v) for v in li[5:9]), bufs={})
+            for j in range(int(li[3])):
+                self._check(self.lib.ft_test_ar_trace_buffer(self._h, i, j, bi.ctypes.data_as(C.c_void_p), None), "ft_test_ar_trace_buffer")
+                bid, esz, rows, cols = (int(v) for v in bi)
+                if not rec["held"]:
+                    rec["bufs"][bid] = None
+                    continue
+                a = np.zeros((rows, cols), dtype=np.uint16 if esz == 2 else np.int32 if bid >= 30 else np.float32)
+                self._check(self.lib.ft_test_ar_trace_buffer(self._h, i, j, bi.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p)),
+                            "ft_test_ar_trace_buffer")
+                rec["bufs"][bid] = a.reshape(rows, cols // 8, 8) if esz == 2 else a
+            if i < 0:
+                begin = rec["bufs"]
+                continue
+            launches.append(rec)
+        state = []
+        for which in (0, 1):
+            s = dict(tok=np.zeros((MB, R), dtype=np.int32), pos=np.zeros(MB, dtype=np.int32), nf=np.zeros(MB, dtype=np.int32),
+                     done=np.zeros(MB, dtype=np.int32), seq=np.zeros((MB, R, cap), dtype=np.int32))
+            self._check(self.lib.ft_test_ar_trace_state(self._h, which, *(s[k].ctypes.data_as(C.c_void_p) for k in ("tok", "pos", "nf", "done", "seq"))),
+                        "ft_test_ar_trace_state")
+            state.append(s)
+        return dict(kind=int(info[0]), m0=int(info[1]), M=int(info[2]), launches=launches, state=state, begin=begin)
+
+    def read_caches(self):
+        """Test hook: every K/V cache of the launch path, whole: {("slow" | "fast", layer): (k, v)}, each (max_batch, Hkv,
+        rows, hd) in the context's type (uint16 patterns or float32), rows = the cache's (n_slots / num_codebooks)."""
+        a = self.args
+        out = {}
+        for which, kind, nl, rows in ((0, "slow", a.n_layer, a.max_seq_len + (-a.max_seq_len) % 8), (1, "fast", a.n_fast_layer, a.num_codebooks)):
+            for li in range(nl):
+                d = [self.engine_handoffs(which, vectors=False, kv=(li, m, rows)) for m in range(self.max_batch)]
+                out[(kind, li)] = (np.stack([x["kv_k"] for x in d]), np.stack([x["kv_v"] for x in d]))
+        return out
+
+    def first_frames(self, slot0: int, samplings: Sequence[L.ft_sampling], next_pos) -> np.ndarray:
+        """ft_ar_first_frames alone: the first frames of slots [slot0, slot0 + n) whose prompts went through the slow stack."""
+        n = len(samplings)
+        arr = (L.ft_sampling * n)(*samplings)
+        npos = np.ascontiguousarray(next_pos, dtype=np.int32)
+        out = np.zeros((n, self.R), dtype=np.int32)
+        self._check(self.lib.ft_ar_first_frames(self._h, slot0, n, arr, npos.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)),
+                    "ft_ar_first_frames")
+        return out
+
+    def prefill_slow_many(self, prompts: Sequence[np.ndarray], slots: Sequence[int]) -> np.ndarray:
+        """ft_ar_prefill_slow_many alone: the prompt passes of `slots`, no first frames.  Returns each slot's next position."""
+        tails = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in prompts]
+        lps = np.asarray([np.asarray(p).shape[1] for p in prompts], dtype=np.int32)
+        packed, sl, z = np.ascontiguousarray(np.concatenate(tails)), np.asarray(slots, dtype=np.int32), np.zeros(len(prompts), dtype=np.int32)
+        self._check(self.lib.ft_ar_prefill_slow_many(self._h, len(prompts), sl.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p),
+                                                     lps.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p)), "ft_ar_prefill")
+        return lps.copy()
 
     def engine_state(self):
         """(flags, time-outs recovered so far, phase of the last one) of the persistent frame engine: flags bit 0 = slow

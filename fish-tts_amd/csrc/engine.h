@@ -36,6 +36,23 @@ struct FtLayer {
 
 struct CodecState;  // codec.hip
 
+// ---- launch trace of the AR frame (test hook, fishtts_hip_test.h: ft_test_ar_trace_*; engine.hip: tr_rec, ArTraceScope)
+struct ArTraceBuf { int id = 0, esz = 4, rows = 0, cols = 0; std::vector<char> data; };
+struct ArTraceRec {
+    std::string name;
+    int m0 = 0, rows = 0, cols = 0, cls[4] = {-1, -1, -1, -1};
+    bool held = false;
+    std::vector<ArTraceBuf> bufs;
+};
+struct ArTraceState { std::vector<int> tok, pos, nf, done, seq; };
+struct ArTrace {
+    bool armed = false, failed = false;
+    int first = 0, count = 0, kind = 0, m0 = 0, M = 0;   // kind: 1 a decode frame, 2 first frames
+    std::vector<ArTraceRec> recs;
+    ArTraceState st[2];                                  // before the first launch, after the call
+    std::vector<ArTraceBuf> begin;                       // every traceable buffer before the first launch
+};
+
 struct ft_ctx {
     ft_ar_config c{};
     bool has_ar = false;
@@ -136,6 +153,12 @@ struct ft_ctx {
     bool prof = false, prof_count_only = false;
     std::vector<hipEvent_t> prof_ev;
     int64_t prof_bytes = 0, prof_launches = 0;
+
+    // test hook: `trace` is non-null only inside a traced ft_ar_decode / ft_ar_first_frames; every launch site tests it once
+    ArTrace tstore;
+    ArTrace* trace = nullptr;
+    // ft_ar_get_debug: slots whose last frame ran on the MFMA launches keep their residual stream in xo_x, not in x
+    std::vector<char> hid_in_xo;
 
     CodecState* codec = nullptr;
 };

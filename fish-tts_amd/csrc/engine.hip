@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -150,6 +151,7 @@ static ft_status ar_alloc(ft_ctx* ctx) {
     if (ctx->nsplit > 32) ctx->nsplit = 32;
     ctx->nsplit_max = std::max(1, std::min(32, std::max(ctx->nsplit_max, ctx->nsplit)));
     ctx->cap = c.max_new_tokens + 24;
+    ctx->hid_in_xo.assign(M, 0);
     ctx->fastV = c.codebook_size < 1024 ? c.codebook_size : 1024;  // inference.py:134
     const size_t qkvN = (size_t)(c.n_head + 2 * c.n_local_heads) * c.head_dim;
     const size_t fqkvN = (size_t)(c.fast_n_head + 2 * c.fast_n_local_heads) * c.fast_head_dim;
@@ -738,6 +740,126 @@ struct Launch {
     void chk() { hipError_t e = hipGetLastError(); if (e != hipSuccess && err == hipSuccess) err = e; }
 };
 
+// ---- launch trace of the AR frame (test hook, fishtts_hip_test.h).  A traced call appends one record per launch, in launch
+// order; the launches of the armed range also copy every buffer they wrote to the host, WHOLE (every row of the allocation:
+// the rows outside [m0, m0 + M) are there for the reader to compare with the record before), at that point of the stream.
+// The copies read only: a traced call computes what an untraced one does.  Buffer ids (AR_TB_*): fishtts_hip_test.h.
+enum { TB_X = 0, TB_QKV, TB_Y, TB_G, TB_LOGITS, TB_HID, TB_FEMB, TB_XF, TB_QKVF, TB_GF, TB_FLOG, TB_PART_O, TB_PART_ML,
+       TB_XO_X = 20, TB_XO_XF, TB_XO_FEMB, TB_XO_Y, TB_XO_G,
+       TB_TOKN = 30, TB_TOK, TB_POS, TB_NF, TB_DONE, TB_SEQ, TB_CUT, TB_CHUNK_CNT, TB_PART_IDX };
+static const void* tr_buf(const ft_ctx* ctx, int id, int* esz, int* rows, int* cols) {
+    const ft_ar_config& c = ctx->c;
+    const int MB = c.max_batch, R = c.num_codebooks + 1, ldm = ctx->xo_ldm;
+    const int qkvN = (c.n_head + 2 * c.n_local_heads) * c.head_dim, fqkvN = (c.fast_n_head + 2 * c.fast_n_local_heads) * c.fast_head_dim;
+    const int HD = c.n_head * c.head_dim, HDf = c.fast_n_head * c.fast_head_dim, nchunk = (c.vocab_size + 1023) / 1024;
+    *esz = 4;
+    auto f = [&](const void* p, int r, int k) { *rows = r; *cols = k; return p; };
+    auto o = [&](const void* p, int width) { *esz = 2; *rows = width / 8; *cols = ldm * 8; return p; };   // [width / 8][ldm][8]
+    switch (id) {
+        case TB_X: return f(ctx->x, MB, c.dim);
+        case TB_QKV: return f(ctx->qkv, MB, qkvN);
+        case TB_Y: return f(ctx->y, MB, ctx->y_ld);
+        case TB_G: return f(ctx->g, MB, c.intermediate_size);
+        case TB_LOGITS: return f(ctx->logits, MB, c.vocab_size);
+        case TB_HID: return f(ctx->hid, MB, c.fast_dim);
+        case TB_FEMB: return f(ctx->femb, MB, c.fast_dim);
+        case TB_XF: return f(ctx->xf, MB, c.fast_dim);
+        case TB_QKVF: return f(ctx->qkvf, 2 * ((MB + 15) / 16 * 16), fqkvN);
+        case TB_GF: return f(ctx->gf, MB, c.fast_intermediate_size);
+        case TB_FLOG: return f(ctx->flog, MB, ctx->fastV);
+        case TB_PART_O: return f(ctx->part_o, 1, MB * c.n_head * ctx->nsplit_max * c.head_dim);
+        case TB_PART_ML: return f(ctx->part_ml, 1, MB * c.n_head * ctx->nsplit_max * 2);
+        case TB_XO_X: return o(ctx->xo_x, c.dim);
+        case TB_XO_XF: return o(ctx->xo_xf, c.fast_dim);
+        case TB_XO_FEMB: return o(ctx->xo_femb, c.fast_dim);
+        case TB_XO_Y: return o(ctx->xo_y, std::max(HD, HDf));
+        case TB_XO_G: return o(ctx->xo_g, std::max(c.intermediate_size, c.fast_intermediate_size));
+        case TB_TOKN: return f(ctx->d_tokn, MB, R);
+        case TB_TOK: return f(ctx->d_tok, MB, R);
+        case TB_POS: return f(ctx->d_pos, 1, MB);
+        case TB_NF: return f(ctx->d_nf, 1, MB);
+        case TB_DONE: return f(ctx->d_done, 1, MB);
+        case TB_SEQ: return f(ctx->d_seq, MB, R * ctx->cap);
+        case TB_CUT: return f(ctx->samp_cut, MB, (int)(sizeof(SampCut) / 4));
+        case TB_CHUNK_CNT: return f(ctx->samp_chunk_cnt, 1, MB * nchunk);
+        case TB_PART_IDX: return f(ctx->samp_part_idx, 1, MB * nchunk);
+    }
+    return nullptr;
+}
+struct TrCls { int a = -1, b = -1, c = -1, d = -1; };
+static void tr_rec(Launch& L, const std::string& name, int rows, int cols, TrCls cls, std::initializer_list<int> bufs) {
+    ft_ctx* ctx = L.ctx;
+    ArTrace& t = *ctx->trace;
+    const int idx = (int)t.recs.size();
+    t.recs.emplace_back();
+    ArTraceRec& r = t.recs.back();
+    r.name = name; r.m0 = L.m0; r.rows = rows; r.cols = cols;
+    r.cls[0] = cls.a; r.cls[1] = cls.b; r.cls[2] = cls.c; r.cls[3] = cls.d;
+    r.held = idx >= t.first && idx < t.first + t.count;
+    for (int id : bufs) {
+        ArTraceBuf b;
+        const void* p = tr_buf(ctx, id, &b.esz, &b.rows, &b.cols);
+        if (!p) continue;
+        b.id = id;
+        if (r.held) {
+            b.data.resize((size_t)b.rows * b.cols * b.esz);
+            if (hipMemcpyAsync(b.data.data(), p, b.data.size(), hipMemcpyDeviceToHost, L.s) != hipSuccess) t.failed = true;
+        }
+        r.bufs.push_back(std::move(b));
+    }
+    if (r.held && hipStreamSynchronize(L.s) != hipSuccess) t.failed = true;
+}
+static std::string tr_name(const char* fmt, ...) {
+    char buf[64];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
+// d_tok, d_pos, d_nf, d_done and the frame store d_seq of every slot (which: 0 before the first launch, 1 after the call)
+static void tr_state(ft_ctx* ctx, int which) {
+    ArTrace& t = *ctx->trace;
+    ArTraceState& s = t.st[which];
+    const size_t MB = ctx->c.max_batch, R = ctx->c.num_codebooks + 1;
+    s.tok.resize(MB * R); s.pos.resize(MB); s.nf.resize(MB); s.done.resize(MB); s.seq.resize(MB * R * ctx->cap);
+    bool ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
+    ok = ok && hipMemcpy(s.tok.data(), ctx->d_tok, s.tok.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(s.pos.data(), ctx->d_pos, MB * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(s.nf.data(), ctx->d_nf, MB * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(s.done.data(), ctx->d_done, MB * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(s.seq.data(), ctx->d_seq, s.seq.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    if (which == 0) {   // and every buffer a launch can write, as the call found it: the record before a buffer's first write
+        static const int ids[] = {TB_X, TB_QKV, TB_Y, TB_G, TB_LOGITS, TB_HID, TB_FEMB, TB_XF, TB_QKVF, TB_GF, TB_FLOG, TB_PART_O, TB_PART_ML,
+                                  TB_XO_X, TB_XO_XF, TB_XO_FEMB, TB_XO_Y, TB_XO_G, TB_TOKN, TB_TOK, TB_POS, TB_NF, TB_DONE, TB_SEQ, TB_CUT,
+                                  TB_CHUNK_CNT, TB_PART_IDX};
+        t.begin.clear();
+        for (int id : ids) {
+            ArTraceBuf b;
+            const void* p = tr_buf(ctx, id, &b.esz, &b.rows, &b.cols);
+            if (!p) continue;
+            b.id = id;
+            b.data.resize((size_t)b.rows * b.cols * b.esz);
+            ok = ok && hipMemcpy(b.data.data(), p, b.data.size(), hipMemcpyDeviceToHost) == hipSuccess;
+            t.begin.push_back(std::move(b));
+        }
+    }
+    if (!ok) t.failed = true;
+}
+struct ArTraceScope {   // a traced call: armed -> active for this call only (kind: 1 a decode frame, 2 first frames)
+    ft_ctx* ctx;
+    ArTraceScope(ft_ctx* c, bool eligible, int kind, int m0, int M) : ctx(c) {
+        ArTrace& t = ctx->tstore;
+        if (!t.armed) return;
+        t.armed = false;
+        if (!eligible) return;
+        t.recs.clear();
+        t.failed = false; t.kind = kind; t.m0 = m0; t.M = M;
+        ctx->trace = &t;
+    }
+    ~ArTraceScope() { ctx->trace = nullptr; }
+};
+
 struct PfX {   // fused RMSNorm hooks of the skinny kernel (codec_kernels.h TapGemmP)
     const void* gain = nullptr;   // normalise the X rows with this gain ...
     const float* ss_in = nullptr; // ... and the producer's partial sums of squares (nblk per row)
@@ -1045,15 +1167,20 @@ static void gemv_combine_nt(Launch& L, const GemvP& p, const AttnP& a, int nt) {
 // Wo product with the residual add - with more than one split the partials are merged inside it (gemv_attn_combine_kernel),
 // with one it reads the attention's y.  enqueue_slow and the test hook ft_test_decode_attn both call it.
 template <typename WT, int ROUND>
-static void decode_attn_wo(Launch& L, const AttnP& a, const GemvP& o) {
+static void decode_attn_wo(Launch& L, const AttnP& a, const GemvP& o, int li = -1) {
     ft_ctx* ctx = L.ctx;
     if (!L.gemv_only) attn_decode<WT, ROUND>(L, a);
+    if (ctx->trace) {
+        if (ctx->nsplit > 1) tr_rec(L, tr_name("slow.%d.attn", li), L.M, a.H * a.hd, TrCls{ctx->nsplit}, {TB_PART_O, TB_PART_ML});
+        else tr_rec(L, tr_name("slow.%d.attn", li), L.M, a.H * a.hd, TrCls{1}, {TB_Y});
+    }
     if (ctx->nsplit > 1) {  // split-KV partials are merged inside the Wo kernel
         const int nt = pick_nt(o.K, Vec<WT>::N);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (ctx->prof && !ctx->prof_count_only) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, L.s); }
         if (rows_per_wave(o.N, L.M) >= 2) gemv_combine_nt<WT, ROUND, 2>(L, o, a, nt);
         else gemv_combine_nt<WT, ROUND, 1>(L, o, a, nt);
+        if (ctx->trace) tr_rec(L, tr_name("slow.%d.wo", li), L.M, o.N, TrCls{-2, rows_per_wave(o.N, L.M) >= 2 ? 2 : 1, nt}, {TB_X});
         if (ctx->prof) {
             if (!ctx->prof_count_only) {
                 hipEventRecord(e1, L.s);
@@ -1064,7 +1191,8 @@ static void decode_attn_wo(Launch& L, const AttnP& a, const GemvP& o) {
         }
         L.chk();
     } else {
-        gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
+        const GemvId id = gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
+        if (ctx->trace) tr_rec(L, tr_name("slow.%d.wo", li), L.M, o.N, TrCls{id.MB, id.R, id.NT}, {TB_X});
     }
 }
 
@@ -1074,7 +1202,7 @@ static void decode_attn_wo(Launch& L, const AttnP& a, const GemvP& o) {
 // attn_combine_rows_kernel.  Returns 0 where attn_wide_kernel ran, else the KV splits of the fall-back (the test hook
 // ft_test_wide_attn reports it; the frames ignore it).
 template <typename WT, int ROUND>
-static int wide_attn(Launch& L, AttnP& a) {
+static int wide_attn(Launch& L, AttnP& a, int li = -1) {
     ft_ctx* ctx = L.ctx;
     const ft_ar_config& c = ctx->c;
     const int M = L.M, Gq = c.n_head / c.n_local_heads;
@@ -1086,6 +1214,7 @@ static int wide_attn(Launch& L, AttnP& a) {
         else if (Gq == 2) attn_wide_kernel<2, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
         else attn_wide_kernel<4, 128, WT, ROUND><<<grid, 256, wlds, L.s>>>(a, ctx->n_slots);
         L.chk();
+        if (ctx->trace) tr_rec(L, tr_name("slow.%d.attn", li), M, c.n_head * c.head_dim, TrCls{0}, {TB_XO_Y});
         return 0;
     }
     int ns = 1;
@@ -1094,7 +1223,14 @@ static int wide_attn(Launch& L, AttnP& a) {
     a.part_o = ctx->part_o + (size_t)L.m0 * c.n_head * ctx->nsplit * c.head_dim;
     a.part_ml = ctx->part_ml + (size_t)L.m0 * c.n_head * ctx->nsplit * 2;
     attn_decode<WT, ROUND>(L, a);
-    if (ns > 1) { attn_combine_rows_kernel<ROUND><<<M, 256, 0, L.s>>>(a); L.chk(); }
+    if (ctx->trace) {
+        if (ns > 1) tr_rec(L, tr_name("slow.%d.attn", li), M, c.n_head * c.head_dim, TrCls{ns}, {TB_PART_O, TB_PART_ML});
+        else tr_rec(L, tr_name("slow.%d.attn", li), M, c.n_head * c.head_dim, TrCls{1}, {TB_XO_Y});
+    }
+    if (ns > 1) {
+        attn_combine_rows_kernel<ROUND><<<M, 256, 0, L.s>>>(a); L.chk();
+        if (ctx->trace) tr_rec(L, tr_name("slow.%d.attn.merge", li), M, c.n_head * c.head_dim, TrCls{ns}, {TB_XO_Y});
+    }
     return ns;
 }
 
@@ -1108,7 +1244,8 @@ static void enqueue_fproj(Launch& L) {
     q.W = ctx->fproj_w; q.bias = ctx->fproj_b; q.x = ctx->x + (size_t)L.m0 * c.dim; q.ldx = c.dim;
     q.out = ctx->hid + (size_t)L.m0 * c.fast_dim; q.ldo = c.fast_dim; q.N = c.fast_dim; q.K = c.dim;
     q.pro = PRO_NONE; q.epi = EPI_STORE;
-    gemv<WT, ROUND>(L, q, rows_per_wave(q.N, L.M));
+    const GemvId id = gemv<WT, ROUND>(L, q, rows_per_wave(q.N, L.M));
+    if (ctx->trace) tr_rec(L, "fproj", L.M, q.N, TrCls{id.MB, id.R, id.NT}, {TB_HID});
 }
 
 // One slow-transformer pass over the current input column of rows [m0, m0+M) (llama.py:400-453).
@@ -1133,6 +1270,7 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
     if (wide) { e.xo = ctx->xo_x + (size_t)m0 * 8; e.xo_ldm = ctx->xo_ldm; }
     if (!L.gemv_only) embed_kernel<WT, ROUND><<<dim3((c.dim + 255) / 256, L.M), 256, 0, L.s>>>(e);
     L.chk();
+    if (ctx->trace) { if (wide) tr_rec(L, "embed", L.M, c.dim, TrCls{}, {TB_X, TB_XO_X}); else tr_rec(L, "embed", L.M, c.dim, TrCls{}, {TB_X}); }
 
     for (int li = 0; li < c.n_layer; ++li) {
         const FtLayer& l = ctx->layers[li];
@@ -1144,7 +1282,8 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
                 bf16_t* xo = ctx->xo_x + (size_t)m0 * 8;
                 bf16_t* yo = ctx->xo_y + (size_t)m0 * 8;
                 bf16_t* go = ctx->xo_g + (size_t)m0 * 8;
-                wide_gemm<WT>(L, xo, l.wqkv, l.bqkv_f32, (int)qkvN, D, l.attn_norm, WEPI_STORE, qkv, (long)qkvN, nullptr, nullptr);
+                int id = wide_gemm<WT>(L, xo, l.wqkv, l.bqkv_f32, (int)qkvN, D, l.attn_norm, WEPI_STORE, qkv, (long)qkvN, nullptr, nullptr);
+                if (ctx->trace) tr_rec(L, tr_name("slow.%d.wqkv", li), L.M, (int)qkvN, TrCls{id}, {TB_QKV});
                 AttnP a{};
                 a.qkv = qkv; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->rope;
                 a.kc = (char*)l.kc + (size_t)m0 * ctx->cache_m_stride * ctx->esz;
@@ -1153,17 +1292,21 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
                 a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots;
                 a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim);
                 a.y = nullptr; a.ldy = HD; a.y_bf = yo; a.y_xo_ldm = ldm;
-                wide_attn<WT, ROUND>(L, a);
-                wide_gemm<WT>(L, yo, l.wo, l.bo_f32, D, HD, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
-                wide_gemm<WT>(L, xo, l.w13, nullptr, 2 * F, D, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr);
-                wide_gemm<WT>(L, go, l.w2, nullptr, D, F, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
+                wide_attn<WT, ROUND>(L, a, li);
+                id = wide_gemm<WT>(L, yo, l.wo, l.bo_f32, D, HD, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
+                if (ctx->trace) tr_rec(L, tr_name("slow.%d.wo", li), L.M, D, TrCls{id}, {TB_XO_X});
+                id = wide_gemm<WT>(L, xo, l.w13, nullptr, 2 * F, D, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr);
+                if (ctx->trace) tr_rec(L, tr_name("slow.%d.w13", li), L.M, F, TrCls{id}, {TB_XO_G});
+                id = wide_gemm<WT>(L, go, l.w2, nullptr, D, F, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
+                if (ctx->trace) tr_rec(L, tr_name("slow.%d.w2", li), L.M, D, TrCls{id}, {TB_XO_X});
             }
             continue;
         }
         GemvP p{};
         p.W = l.wqkv; p.bias = l.bqkv; p.x = x; p.ldx = c.dim; p.gain = l.attn_norm; p.eps = c.norm_eps;
         p.out = qkv; p.ldo = (int)qkvN; p.N = (int)qkvN; p.K = c.dim; p.pro = PRO_RMSNORM; p.epi = EPI_STORE; p.nt = 1;
-        gemv<WT, ROUND>(L, p, rows_per_wave(p.N, L.M));
+        GemvId gid = gemv<WT, ROUND>(L, p, rows_per_wave(p.N, L.M));
+        if (ctx->trace) tr_rec(L, tr_name("slow.%d.wqkv", li), L.M, p.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_QKV});
 
         AttnP a{};
         a.qkv = qkv; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->rope;
@@ -1178,17 +1321,19 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
         GemvP o{};
         o.W = l.wo; o.bias = l.bo; o.x = y; o.ldx = ctx->y_ld; o.out = x; o.ldo = c.dim;
         o.resid = x; o.ldr = c.dim; o.N = c.dim; o.K = c.n_head * c.head_dim; o.pro = PRO_NONE; o.epi = EPI_RESID; o.nt = 1;
-        decode_attn_wo<WT, ROUND>(L, a, o);
+        decode_attn_wo<WT, ROUND>(L, a, o, li);
 
         GemvP f{};
         f.W = l.w13; f.x = x; f.ldx = c.dim; f.gain = l.ffn_norm; f.eps = c.norm_eps; f.out = g;
         f.ldo = c.intermediate_size; f.N = 2 * c.intermediate_size; f.K = c.dim; f.pro = PRO_RMSNORM; f.epi = EPI_SWIGLU; f.nt = 1;
-        gemv<WT, ROUND>(L, f, rows_per_wave(f.N, L.M));
+        gid = gemv<WT, ROUND>(L, f, rows_per_wave(f.N, L.M));
+        if (ctx->trace) tr_rec(L, tr_name("slow.%d.w13", li), L.M, c.intermediate_size, TrCls{gid.MB, gid.R, gid.NT}, {TB_G});
 
         GemvP d{};
         d.W = l.w2; d.x = g; d.ldx = c.intermediate_size; d.out = x; d.ldo = c.dim; d.resid = x; d.ldr = c.dim;
         d.N = c.dim; d.K = c.intermediate_size; d.pro = PRO_NONE; d.epi = EPI_RESID; d.nt = 1;
-        gemv<WT, ROUND>(L, d, rows_per_wave(d.N, L.M));
+        gid = gemv<WT, ROUND>(L, d, rows_per_wave(d.N, L.M));
+        if (ctx->trace) tr_rec(L, tr_name("slow.%d.w2", li), L.M, d.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_X});
     }
     if (with_head) enqueue_fproj<WT, ROUND>(L);
 }
@@ -1203,17 +1348,21 @@ static void enqueue_head(Launch& L) {
             xo_from_rows_kernel<WT><<<dim3((c.dim + 255) / 256, L.M), 256, 0, L.s>>>(ctx->x + (size_t)L.m0 * c.dim, c.dim, c.dim,
                                                                              ctx->xo_x + (size_t)L.m0 * 8, ctx->xo_ldm);
             L.chk();
+            if (ctx->trace) tr_rec(L, "xo_rows", L.M, c.dim, TrCls{}, {TB_XO_X});
         }
-        if constexpr (ROUND != RND_NONE)
-            wide_gemm<WT>(L, ctx->xo_x + (size_t)L.m0 * 8, ctx->head, nullptr, c.vocab_size, c.dim, ctx->norm, WEPI_STORE,
-                      ctx->logits + (size_t)L.m0 * c.vocab_size, c.vocab_size, nullptr, nullptr, 0, true);
+        if constexpr (ROUND != RND_NONE) {
+            const int id = wide_gemm<WT>(L, ctx->xo_x + (size_t)L.m0 * 8, ctx->head, nullptr, c.vocab_size, c.dim, ctx->norm, WEPI_STORE,
+                                         ctx->logits + (size_t)L.m0 * c.vocab_size, c.vocab_size, nullptr, nullptr, 0, true);
+            if (ctx->trace) tr_rec(L, "head", L.M, c.vocab_size, TrCls{id}, {TB_LOGITS});
+        }
         return;
     }
     GemvP h{};
     h.W = ctx->head; h.x = ctx->x + (size_t)L.m0 * c.dim; h.ldx = c.dim; h.gain = ctx->norm; h.eps = c.norm_eps;
     h.out = ctx->logits + (size_t)L.m0 * c.vocab_size; h.ldo = c.vocab_size; h.N = c.vocab_size; h.K = c.dim;
     h.pro = PRO_RMSNORM; h.epi = EPI_STORE; h.nt = 1;
-    gemv<WT, ROUND>(L, h, rows_per_wave(h.N, L.M));
+    const GemvId id = gemv<WT, ROUND>(L, h, rows_per_wave(h.N, L.M));
+    if (ctx->trace) tr_rec(L, "head", L.M, h.N, TrCls{id.MB, id.R, id.NT}, {TB_LOGITS});
 }
 
 // Returns what it launched (the test hook ft_test_draw reports it; the frames ignore it): DRAW_* below
@@ -1246,9 +1395,16 @@ static int enqueue_sample(Launch& L, int cb, bool last) {
             s.qkv0_out = ctx->qkvf + (size_t)m0 * s.qkv0_n;
         }
     }
+    // what a finishing draw launch may write (finish_draw): the frame under construction and, on the last codebook, the state
+    auto tr_draw = [&](const char* sfx, int w) {
+        const std::string nm = tr_name("draw.%d%s", cb, sfx);
+        if (!wide_batch(L)) tr_rec(L, nm, L.M, s.V, TrCls{w}, {cb == 0 ? TB_LOGITS : TB_FLOG, TB_TOKN, TB_TOK, TB_POS, TB_NF, TB_DONE, TB_SEQ, TB_FEMB});
+        else tr_rec(L, nm, L.M, s.V, TrCls{w}, {cb == 0 ? TB_LOGITS : TB_FLOG, TB_TOKN, TB_TOK, TB_POS, TB_NF, TB_DONE, TB_SEQ, TB_FEMB, TB_XO_FEMB, TB_XO_X, TB_QKVF});
+    };
     if (s.V <= 1024) {
         sample_small_kernel<WT, ROUND><<<L.M, 256, 0, L.s>>>(s);
         what |= DRAW_SMALL;
+        if (ctx->trace) tr_draw("", what);
     } else if (ROUND == RND_BF16) {
         // large vocabulary, bf16: the histogram of the 65 536 bf16 classes and the search of the top-p cut on it in ONE block
         // per row (LDS counters), then index-ordered tie handling and the chip-wide race
@@ -1265,14 +1421,19 @@ static int enqueue_sample(Launch& L, int cb, bool last) {
                 hipFuncSetAttribute((const void*)samp_cut_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SAMP_TH_LDS);
             });
         }
-        samp_cut_kernel<<<L.M, SAMP_TH_THREADS, SAMP_TH_LDS, L.s>>>(b);
-        samp_count_kernel<<<gridc, 256, 0, L.s>>>(b);
-        samp_race_kernel<<<gridc, 256, 0, L.s>>>(b);
-        samp_finish_kernel<WT><<<L.M, 256, 0, L.s>>>(b);
         what |= DRAW_FOUR;
+        samp_cut_kernel<<<L.M, SAMP_TH_THREADS, SAMP_TH_LDS, L.s>>>(b);
+        if (ctx->trace) tr_rec(L, tr_name("draw.%d.cut", cb), L.M, s.V, TrCls{what}, {TB_LOGITS, TB_CUT});
+        samp_count_kernel<<<gridc, 256, 0, L.s>>>(b);
+        if (ctx->trace) tr_rec(L, tr_name("draw.%d.count", cb), L.M, s.V, TrCls{what}, {TB_CUT, TB_CHUNK_CNT});
+        samp_race_kernel<<<gridc, 256, 0, L.s>>>(b);
+        if (ctx->trace) tr_rec(L, tr_name("draw.%d.race", cb), L.M, s.V, TrCls{what}, {TB_PART_IDX});
+        samp_finish_kernel<WT><<<L.M, 256, 0, L.s>>>(b);
+        if (ctx->trace) tr_draw(".finish", what);
     } else {
         sample_block_kernel<WT, ROUND><<<L.M, 1024, 0, L.s>>>(s);
         what |= DRAW_BLOCK;
+        if (ctx->trace) tr_draw("", what);
     }
     L.chk();
     return what;
@@ -1289,6 +1450,8 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
     float* xf = ctx->xf + (size_t)m0 * Df;
     float* qkvf = ctx->qkvf + (size_t)m0 * qkvN;
     float* gf = ctx->gf + (size_t)m0 * c.fast_intermediate_size;
+    char tp[16] = "";      // the launch trace's name of this step: fast.<cb>, or fast.pair
+    if (ctx->trace) { if (pair) snprintf(tp, sizeof tp, "fast.pair"); else snprintf(tp, sizeof tp, "fast.%d", cb); }
     {
         const float* xin = cb == 0 ? ctx->hid + (size_t)m0 * Df : ctx->femb + (size_t)m0 * Df;
         const bool wide = wide_batch(L);
@@ -1307,8 +1470,11 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
                     bf16_t* go = ctx->xo_g + (size_t)m0 * 8;
                     const bf16_t* xlo = li == 0 ? xin_o : xfo;
                     // layer 0 of steps >= 2: the draw of the previous step left this step's q k v (wide_qkv0_build)
-                    if (!(li == 0 && cb >= 2 && !pair && ctx->wide_qkv0_tab))
-                        wide_gemm<WT>(L, xlo, l.wqkv, nullptr, (int)qkvN, Df, l.attn_norm, WEPI_STORE, qkvf, (long)qkvN, nullptr, nullptr, rows);
+                    int id = -1;
+                    if (!(li == 0 && cb >= 2 && !pair && ctx->wide_qkv0_tab)) {
+                        id = wide_gemm<WT>(L, xlo, l.wqkv, nullptr, (int)qkvN, Df, l.attn_norm, WEPI_STORE, qkvf, (long)qkvN, nullptr, nullptr, rows);
+                        if (ctx->trace) tr_rec(L, tr_name("%s.%d.wqkv", tp, li), rows, (int)qkvN, TrCls{id}, {TB_QKVF});
+                    }
                     FastAttnP a{};
                     a.qkv = qkvf; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->frope;
                     a.kc = (char*)l.kc + (size_t)m0 * ctx->fcache_m_stride * ctx->esz;
@@ -1319,16 +1485,21 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
                     a.pair_M = pair ? M : 0; a.pair_off = ctx->xo_pair;
                     fast_attn_kernel<WT, ROUND><<<dim3(Hf, pair ? 2 * M : M), 64, 0, L.s>>>(a, nullptr, HDf);
                     L.chk();
-                    wide_gemm<WT>(L, yo, l.wo, nullptr, Df, HDf, nullptr, WEPI_RESID, nullptr, 0, xfo, xlo, rows);
-                    wide_gemm<WT>(L, xfo, l.w13, nullptr, 2 * Ff, Df, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr, rows);
-                    wide_gemm<WT>(L, go, l.w2, nullptr, Df, Ff, nullptr, WEPI_RESID, nullptr, 0, xfo, xfo, rows);
+                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.attn", tp, li), pair ? 2 * M : M, HDf, TrCls{}, {TB_XO_Y});
+                    id = wide_gemm<WT>(L, yo, l.wo, nullptr, Df, HDf, nullptr, WEPI_RESID, nullptr, 0, xfo, xlo, rows);
+                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.wo", tp, li), rows, Df, TrCls{id}, {TB_XO_XF});
+                    id = wide_gemm<WT>(L, xfo, l.w13, nullptr, 2 * Ff, Df, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr, rows);
+                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.w13", tp, li), rows, Ff, TrCls{id}, {TB_XO_G});
+                    id = wide_gemm<WT>(L, go, l.w2, nullptr, Df, Ff, nullptr, WEPI_RESID, nullptr, 0, xfo, xfo, rows);
+                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.w2", tp, li), rows, Df, TrCls{id}, {TB_XO_XF});
                 }
                 continue;
             }
             GemvP p{};
             p.W = l.wqkv; p.bias = l.bqkv; p.x = xl; p.ldx = Df; p.gain = l.attn_norm; p.eps = c.norm_eps;
             p.out = qkvf; p.ldo = (int)qkvN; p.N = (int)qkvN; p.K = Df; p.pro = PRO_RMSNORM; p.epi = EPI_STORE;
-            gemv<WT, ROUND>(L, p, rows_per_wave(p.N, L.M));
+            GemvId gid = gemv<WT, ROUND>(L, p, rows_per_wave(p.N, L.M));
+            if (ctx->trace) tr_rec(L, tr_name("%s.%d.wqkv", tp, li), L.M, p.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_QKVF});
 
             FastAttnP a{};
             a.qkv = qkvf; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->frope;
@@ -1339,27 +1510,33 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
             float* yf = ctx->y + (size_t)m0 * ctx->y_ld;  // the slow attention's y buffer is free here
             if (!L.gemv_only) fast_attn_kernel<WT, ROUND><<<dim3(Hf, L.M), 64, 0, L.s>>>(a, yf, ctx->y_ld);
             L.chk();
+            if (ctx->trace) tr_rec(L, tr_name("%s.%d.attn", tp, li), L.M, Hf * hdf, TrCls{}, {TB_Y});
             GemvP o{};
             o.W = l.wo; o.bias = l.bo; o.x = yf; o.ldx = ctx->y_ld; o.out = xf; o.ldo = Df; o.resid = xl;
             o.ldr = Df; o.N = Df; o.K = Hf * hdf; o.pro = PRO_NONE; o.epi = EPI_RESID;
-            gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
+            gid = gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
+            if (ctx->trace) tr_rec(L, tr_name("%s.%d.wo", tp, li), L.M, o.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_XF});
 
             GemvP f{};
             f.W = l.w13; f.x = xf; f.ldx = Df; f.gain = l.ffn_norm; f.eps = c.norm_eps; f.out = gf;
             f.ldo = c.fast_intermediate_size; f.N = 2 * c.fast_intermediate_size; f.K = Df; f.pro = PRO_RMSNORM;
             f.epi = EPI_SWIGLU;
-            gemv<WT, ROUND>(L, f, rows_per_wave(f.N, L.M));
+            gid = gemv<WT, ROUND>(L, f, rows_per_wave(f.N, L.M));
+            if (ctx->trace) tr_rec(L, tr_name("%s.%d.w13", tp, li), L.M, c.fast_intermediate_size, TrCls{gid.MB, gid.R, gid.NT}, {TB_GF});
 
             GemvP d{};
             d.W = l.w2; d.x = gf; d.ldx = c.fast_intermediate_size; d.out = xf; d.ldo = Df; d.resid = xf; d.ldr = Df;
             d.N = Df; d.K = c.fast_intermediate_size; d.pro = PRO_NONE; d.epi = EPI_RESID;
-            gemv<WT, ROUND>(L, d, rows_per_wave(d.N, L.M));
+            gid = gemv<WT, ROUND>(L, d, rows_per_wave(d.N, L.M));
+            if (ctx->trace) tr_rec(L, tr_name("%s.%d.w2", tp, li), L.M, d.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_XF});
         }
         if (cb == 0) return;  // logits of position 0 are discarded (inference.py:122)
         if (wide) {
-            if constexpr (ROUND != RND_NONE)
-                wide_gemm<WT>(L, (c.n_fast_layer > 0 ? ctx->xo_xf : ctx->xo_femb) + (size_t)(m0 + (pair ? ctx->xo_pair : 0)) * 8, ctx->fast_out, nullptr,
-                          ctx->fastV, Df, ctx->fast_norm, WEPI_STORE, ctx->flog + (size_t)m0 * ctx->fastV, ctx->fastV, nullptr, nullptr);
+            if constexpr (ROUND != RND_NONE) {
+                const int id = wide_gemm<WT>(L, (c.n_fast_layer > 0 ? ctx->xo_xf : ctx->xo_femb) + (size_t)(m0 + (pair ? ctx->xo_pair : 0)) * 8, ctx->fast_out, nullptr,
+                                             ctx->fastV, Df, ctx->fast_norm, WEPI_STORE, ctx->flog + (size_t)m0 * ctx->fastV, ctx->fastV, nullptr, nullptr);
+                if (ctx->trace) tr_rec(L, tr_name("fast.%d.head", cb), L.M, ctx->fastV, TrCls{id}, {TB_FLOG});
+            }
             enqueue_sample<WT, ROUND>(L, cb, cb == c.num_codebooks - 1);
             return;
         }
@@ -1367,7 +1544,8 @@ static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) 
         h.W = ctx->fast_out; h.x = xf; h.ldx = Df; h.gain = ctx->fast_norm; h.eps = c.norm_eps;
         h.out = ctx->flog + (size_t)m0 * ctx->fastV; h.ldo = ctx->fastV; h.N = ctx->fastV; h.K = Df;
         h.pro = PRO_RMSNORM; h.epi = EPI_STORE;
-        gemv<WT, ROUND>(L, h, rows_per_wave(h.N, L.M));
+        const GemvId hid_ = gemv<WT, ROUND>(L, h, rows_per_wave(h.N, L.M));
+        if (ctx->trace) tr_rec(L, tr_name("fast.%d.head", cb), L.M, h.N, TrCls{hid_.MB, hid_.R, hid_.NT}, {TB_FLOG});
         enqueue_sample<WT, ROUND>(L, cb, cb == c.num_codebooks - 1);
     }
 }
@@ -1651,6 +1829,8 @@ extern "C" ft_status ft_ar_prefill_at(ft_ctx* ctx, int32_t slot, const int32_t* 
         return ft_fail(ctx, FT_ERR_TOO_LONG, buf);
     }
     const int R = c.num_codebooks + 1;
+    ctx->tstore.armed = false;        // the launch trace arms the next decode frame / first frames only
+    ctx->hid_in_xo[slot] = 0;
     FT_TRY(ft_ar_reset(ctx, slot));
     FT_TRY(upload_ctl(ctx, slot, 1, sp));
     FT_HIP(ctx, hipMemcpyAsync(ctx->d_prompt, prompt, (size_t)R * Lp * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -1707,6 +1887,8 @@ extern "C" ft_status ft_ar_prefill_slow(ft_ctx* ctx, int32_t slot, const int32_t
         return ft_fail(ctx, FT_ERR_TOO_LONG, buf);
     }
     const int R = c.num_codebooks + 1;
+    ctx->tstore.armed = false;
+    ctx->hid_in_xo[slot] = 0;
     FT_TRY(ft_ar_reset(ctx, slot));
     FT_HIP(ctx, hipMemcpyAsync(ctx->d_prompt, prompt, (size_t)R * Lp * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     pick_nsplit(ctx, pos0 + Lp);
@@ -1739,6 +1921,7 @@ extern "C" ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32
     if (!slots || !prompts || !Lps || !pos0s) return ft_fail(ctx, FT_ERR_ARG, "ft_ar_prefill_slow_many: null argument");
     if (n < 1 || n > c.max_batch) return ft_fail(ctx, FT_ERR_ARG, "ft_ar_prefill_slow_many: bad count");
     const int R = c.num_codebooks + 1;
+    ctx->tstore.armed = false;
     std::vector<char> seen(c.max_batch, 0);
     std::vector<size_t> off(n + 1, 0);
     for (int i = 0; i < n; ++i) {
@@ -1798,10 +1981,16 @@ extern "C" ft_status ft_ar_first_frames(ft_ctx* ctx, int32_t slot0, int32_t n, c
     if (!sp || !next_pos || !out_frames) return ft_fail(ctx, FT_ERR_ARG, "ft_ar_first_frames: null argument");
     if (slot0 < 0 || n < 1 || slot0 + n > c.max_batch) return ft_fail(ctx, FT_ERR_ARG, "ft_ar_first_frames: bad slot range");
     const int R = c.num_codebooks + 1;
+    const bool on_engine = n == 1 && eng_in_use(ctx);
+    if (ctx->tstore.armed && on_engine) {
+        ctx->tstore.armed = false;
+        return ft_fail(ctx, FT_ERR_STATE, "ft_ar_first_frames: a traced call never runs on the frame engine");
+    }
+    ArTraceScope traced(ctx, true, 2, slot0, n);
     FT_TRY(upload_ctl(ctx, slot0, n, sp));
+    if (ctx->trace) tr_state(ctx, 0);
     Launch L{ctx, ctx->stream, slot0, n, 0};
     L.tail_only = true;
-    const bool on_engine = n == 1 && eng_in_use(ctx);
     auto tail = [&]() {
         if (c.dtype == FT_BF16) { enqueue_fproj<bf16_t, RND_BF16>(L); enqueue_frame_tail<bf16_t, RND_BF16>(L); }
         else if (c.dtype == FT_F16) { enqueue_fproj<f16_t, RND_F16>(L); enqueue_frame_tail<f16_t, RND_F16>(L); }
@@ -1825,6 +2014,8 @@ extern "C" ft_status ft_ar_first_frames(ft_ctx* ctx, int32_t slot0, int32_t n, c
     FT_HIP(ctx, hipMemcpyAsync(ctx->d_pos + slot0, next_pos, n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     FT_HIP(ctx, hipMemcpyAsync(out_frames, ctx->d_tok + (size_t)slot0 * R, (size_t)n * R * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int m = slot0; m < slot0 + n; ++m) ctx->hid_in_xo[m] = 0;    // a prompt pass leaves the rows' residual stream in ctx->x
+    if (ctx->trace) tr_state(ctx, 1);
     return FT_OK;
 }
 
@@ -1934,6 +2125,11 @@ extern "C" ft_status ft_ar_decode(ft_ctx* ctx, int32_t nslots, int32_t n_frames,
     if (n_frames < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_ar_decode: n_frames < 0");
     if (poll < 1) poll = 1;
     const int R = c.num_codebooks + 1;
+    if (ctx->tstore.armed && n_frames == 1 && nslots == 1 && eng_in_use(ctx)) {
+        ctx->tstore.armed = false;
+        return ft_fail(ctx, FT_ERR_STATE, "ft_ar_decode: a traced call never runs on the frame engine");
+    }
+    ArTraceScope traced(ctx, n_frames == 1, 1, 0, nslots);
     FT_TRY(upload_ctl(ctx, 0, nslots, sp));
     // state at entry
     int* h = ctx->h_pin;
@@ -1948,16 +2144,27 @@ extern "C" ft_status ft_ar_decode(ft_ctx* ctx, int32_t nslots, int32_t n_frames,
         if (nf0[m] < 1) return ft_fail(ctx, FT_ERR_STATE, "ft_ar_decode: slot has not been prefilled");
         if (h[2 * nslots + m]) continue;  // finished or parked: frozen on the device, limits nothing
         budget = std::min(budget, ctx->cap - nf0[m]);
-        budget = std::min(budget, ctx->n_slots - h[nslots + m]);  // cache positions left
+        // cache positions left: the rope table has max_seq_len rows (the cache's n_slots is that rounded up to 8)
+        budget = std::min(budget, c.max_seq_len - h[nslots + m]);
     }
     if (budget < 0) budget = 0;
+    // A row that drew <|im_end|> at its last cache row is frozen at position max_seq_len, and the attention launches take no
+    // done flag: while the caller keeps it in the lock-step batch they would append at that row (the next kv head's, the next
+    // slot's or nobody's) and read the rope table past its end.  Its position goes back inside its own cache: the row it
+    // rewrites there is one no frame reads again.
+    for (int m = 0; m < nslots; ++m)
+        if (h[2 * nslots + m] && h[nslots + m] >= c.max_seq_len) {
+            h[nslots + m] = c.max_seq_len - 1;
+            FT_HIP(ctx, hipMemcpyAsync(ctx->d_pos + m, h + nslots + m, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        }
+    if (ctx->trace) tr_state(ctx, 0);
     {   // KV splits follow the longest context this call will reach
         int pos_end = 0;
         for (int m = 0; m < nslots; ++m)
             if (!h[2 * nslots + m]) pos_end = std::max(pos_end, h[nslots + m] + budget);
         pick_nsplit(ctx, pos_end);
     }
-    const bool eager = getenv("FT_NO_GRAPH") != nullptr;
+    const bool eager = getenv("FT_NO_GRAPH") != nullptr || ctx->trace;   // a traced frame is launched, never captured or replayed
     // several frames per graph launch where a burst allows: the gap between two graph launches is ~7 us (measured: 687 ->
     // 692 tok/s at 16 frames per graph; the frames are the same launches in the same order)
     constexpr int gk = 16;
@@ -2050,6 +2257,11 @@ extern "C" ft_status ft_ar_decode(ft_ctx* ctx, int32_t nslots, int32_t n_frames,
         }
         out_n[m] = n;
     }
+    if (done_frames > 0) {   // ft_ar_get_debug: where these rows' residual stream is
+        Launch L{ctx, ctx->stream, 0, nslots, 0};
+        for (int m = 0; m < nslots; ++m) ctx->hid_in_xo[m] = wide_batch(L) ? 1 : 0;
+    }
+    if (ctx->trace) tr_state(ctx, 1);
     return FT_OK;
 }
 
@@ -2139,6 +2351,56 @@ extern "C" ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t*
 // Test hook: the hand-off vectors the engine's launches left behind, and K/V rows (include/fishtts_hip_test.h).  Host code:
 // one copy of each pool to the host, then the decoding below with the layout rules of frame_engine.h.
 namespace {
+// ---- launch trace hooks of the AR frame (fishtts_hip_test.h)
+extern "C" ft_status ft_test_ar_trace_arm(ft_ctx* ctx, int32_t first, int32_t count) {
+    FT_TRY(ar_ready(ctx));
+    if (first < 0 || count < 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_ar_trace_arm: bad range");
+    if (ctx->c.max_batch == 1 && eng_in_use(ctx))
+        return ft_fail(ctx, FT_ERR_STATE, "ft_test_ar_trace_arm: this context's frames run on the frame engine");
+    ArTrace& t = ctx->tstore;
+    t.recs.clear();
+    t.first = first; t.count = count; t.armed = true; t.failed = false; t.kind = 0;
+    return FT_OK;
+}
+extern "C" int32_t ft_test_ar_trace_count(ft_ctx* ctx, int32_t* info) {
+    if (!ctx || !ctx->has_ar) return -1;
+    const ArTrace& t = ctx->tstore;
+    if (info) { info[0] = t.kind; info[1] = t.m0; info[2] = t.M; info[3] = t.armed ? 1 : 0; info[4] = (int32_t)t.begin.size(); }
+    return t.failed ? -1 : (int32_t)t.recs.size();
+}
+extern "C" ft_status ft_test_ar_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t cap, int32_t* info) {
+    if (!ctx || !ctx->has_ar || !name || cap < 1 || !info) return FT_ERR_ARG;
+    const ArTrace& t = ctx->tstore;
+    if (i < 0 || i >= (int)t.recs.size()) return ft_fail(ctx, FT_ERR_ARG, "ft_test_ar_trace_launch: no such launch");
+    const ArTraceRec& r = t.recs[i];
+    snprintf(name, (size_t)cap, "%s", r.name.c_str());
+    info[0] = r.m0; info[1] = r.rows; info[2] = r.cols; info[3] = (int32_t)r.bufs.size(); info[4] = r.held ? 1 : 0;
+    for (int k = 0; k < 4; ++k) info[5 + k] = r.cls[k];
+    return FT_OK;
+}
+extern "C" ft_status ft_test_ar_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t* info, void* dst) {
+    if (!ctx || !ctx->has_ar || !info) return FT_ERR_ARG;
+    ArTrace& t = ctx->tstore;
+    std::vector<ArTraceBuf>* bufs = i == -1 ? &t.begin : i >= 0 && i < (int)t.recs.size() ? &t.recs[i].bufs : nullptr;
+    if (!bufs || j < 0 || j >= (int)bufs->size()) return ft_fail(ctx, FT_ERR_ARG, "ft_test_ar_trace_buffer: no such buffer");
+    ArTraceBuf& b = (*bufs)[j];
+    info[0] = b.id; info[1] = b.esz; info[2] = b.rows; info[3] = b.cols;
+    if (dst) {
+        if (b.data.empty()) return ft_fail(ctx, FT_ERR_STATE, "ft_test_ar_trace_buffer: launch outside the armed range, or read before");
+        memcpy(dst, b.data.data(), b.data.size());
+        std::vector<char>().swap(b.data);   // handed over
+    }
+    return FT_OK;
+}
+extern "C" ft_status ft_test_ar_trace_state(ft_ctx* ctx, int32_t which, int32_t* tok, int32_t* pos, int32_t* nf, int32_t* done, int32_t* seq) {
+    if (!ctx || !ctx->has_ar || (which != 0 && which != 1) || !tok || !pos || !nf || !done || !seq) return FT_ERR_ARG;
+    const ArTraceState& s = ctx->tstore.st[which];
+    if (ctx->tstore.kind == 0 || s.pos.empty()) return ft_fail(ctx, FT_ERR_STATE, "ft_test_ar_trace_state: no traced call");
+    memcpy(tok, s.tok.data(), s.tok.size() * 4); memcpy(pos, s.pos.data(), s.pos.size() * 4); memcpy(nf, s.nf.data(), s.nf.size() * 4);
+    memcpy(done, s.done.data(), s.done.size() * 4); memcpy(seq, s.seq.data(), s.seq.size() * 4);
+    return FT_OK;
+}
+
 struct EngDump {
     const unsigned* w;      // one copy of a pool on the host
     // n plain granules {tag16 | bf16} of a vector stored linearly (EngLayout::off is the identity) from word `at`
@@ -2269,7 +2531,8 @@ extern "C" ft_status ft_test_engine_handoffs(ft_ctx* ctx, ft_test_engine_io* io)
         FT_HIP(ctx, hipMemcpy(io->tab, (const bf16_t*)ctx->eng_qkv0_tab + (size_t)io->tab_row * QKVN, (size_t)QKVN * sizeof(bf16_t), hipMemcpyDeviceToHost));
     }
     if (io->kv_k || io->kv_v) {
-        if (!io->kv_k || !io->kv_v || ctx->esz != 2) return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: K/V needs both arrays and a 16-bit context");
+        if (!io->kv_k || !io->kv_v) return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: K/V needs both arrays");
+        const size_t esz = ctx->esz;      // an f32 context: the arrays hold f32 values (twice the room)
         const int rows_max = fast ? c.num_codebooks : ctx->n_slots;
         if (io->kv_layer < 0 || io->kv_layer >= nL || io->kv_slot < 0 || io->kv_slot >= c.max_batch || io->kv_rows < 1 || io->kv_rows > rows_max)
             return ft_fail(ctx, FT_ERR_ARG, "ft_test_engine_handoffs: bad K/V layer, slot or row count");
@@ -2277,9 +2540,9 @@ extern "C" ft_status ft_test_engine_handoffs(ft_ctx* ctx, ft_test_engine_io* io)
         const size_t mstr = fast ? ctx->fcache_m_stride : ctx->cache_m_stride;
         for (int h = 0; h < Hkv; ++h) {
             const size_t src = (size_t)io->kv_slot * mstr + (size_t)h * rows_max * hd, dst = (size_t)h * io->kv_rows * hd;
-            const size_t bytes = (size_t)io->kv_rows * hd * 2;
-            FT_HIP(ctx, hipMemcpy(io->kv_k + dst, (const char*)l.kc + src * 2, bytes, hipMemcpyDeviceToHost));
-            FT_HIP(ctx, hipMemcpy(io->kv_v + dst, (const char*)l.vc + src * 2, bytes, hipMemcpyDeviceToHost));
+            const size_t bytes = (size_t)io->kv_rows * hd * esz;
+            FT_HIP(ctx, hipMemcpy((char*)io->kv_k + dst * esz, (const char*)l.kc + src * esz, bytes, hipMemcpyDeviceToHost));
+            FT_HIP(ctx, hipMemcpy((char*)io->kv_v + dst * esz, (const char*)l.vc + src * esz, bytes, hipMemcpyDeviceToHost));
         }
     }
     return FT_OK;
@@ -2422,7 +2685,18 @@ extern "C" ft_status ft_ar_get_debug(ft_ctx* ctx, int32_t slot, float* logits, f
     FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (logits)
         FT_HIP(ctx, hipMemcpy(logits, ctx->logits + (size_t)slot * ctx->c.vocab_size, ctx->c.vocab_size * sizeof(float), hipMemcpyDeviceToHost));
-    if (hidden)
+    if (hidden && ctx->hid_in_xo[slot]) {
+        // the slot's last frame ran on the MFMA launches: its residual stream is row `slot` of the octet-major xo_x (fast_dim ==
+        // dim there), ctx->x holds what embed_kernel left
+        const int D = ctx->c.dim;
+        std::vector<uint16_t> hb((size_t)D);
+        FT_HIP(ctx, hipMemcpy2D(hb.data(), 8 * sizeof(uint16_t), ctx->xo_x + (size_t)slot * 8, (size_t)ctx->xo_ldm * 8 * sizeof(uint16_t),
+                                8 * sizeof(uint16_t), (size_t)D / 8, hipMemcpyDeviceToHost));
+        for (int d = 0; d < D; ++d) {
+            if (ctx->c.dtype == FT_BF16) { const uint32_t u = (uint32_t)hb[d] << 16; memcpy(hidden + d, &u, 4); }
+            else { _Float16 v; memcpy(&v, &hb[d], 2); hidden[d] = (float)v; }
+        }
+    } else if (hidden)
         FT_HIP(ctx, hipMemcpy(hidden, ctx->hid + (size_t)slot * ctx->c.fast_dim, ctx->c.fast_dim * sizeof(float), hipMemcpyDeviceToHost));
     return FT_OK;
 }

@@ -143,7 +143,10 @@ void ft_ar_kv_free(ft_ctx* ctx, ft_kv_snapshot* snap);
  * (inference.py:83-155), for slots [0, nslots) in lock step, up to n_frames more frames each.
  * out_frames: nslots x n_frames x (num_codebooks+1) int32 (host), frame-major; out_n[slot] =
  * frames produced (the <|im_end|> frame included, as the streaming loop yields it).
- * The step is hipGraph-captured; EOS is polled every `poll` frames (>=1). */
+ * The step is hipGraph-captured; EOS is polled every `poll` frames (>=1).
+ * A call runs no live slot past position max_seq_len - 1 (the last row of the rope table; the cache has max_seq_len rounded
+ * up to 8 rows) nor past its frame store.  A slot that finished on its last cache row may stay in the batch until the
+ * caller parks or refills it: frozen, it rewrites that row of its own cache and nothing else. */
 ft_status ft_ar_decode(ft_ctx* ctx, int32_t nslots, int32_t n_frames, const ft_sampling* sp,
                        int32_t poll, int32_t* out_frames, int32_t* out_n);
 

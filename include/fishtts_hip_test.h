@@ -10,7 +10,8 @@ extern "C" {
 
 /* Test hooks: inject the Exp(1) noise the sampler divides by (inference.py:26), one row of
  * `row_len` floats per generated frame (slow vocab draws first, then (num_codebooks-1) x 1024);
- * q == NULL restores the RNG.  Read back the last slow logits / pre-norm hidden of a slot. */
+ * q == NULL restores the RNG.  Read back the last slow logits / pre-norm hidden of a slot (after a frame on the lock-step
+ * MFMA launches the hidden state is gathered from the octet-major residual stream, where those launches keep it). */
 ft_status ft_ar_set_noise(ft_ctx* ctx, const float* q, int64_t n_rows, int64_t row_len);
 ft_status ft_ar_get_debug(ft_ctx* ctx, int32_t slot, float* logits /*vocab*/, float* hidden /*fast_dim*/);
 
@@ -68,7 +69,8 @@ ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t* xl, int32_
  * kc / vc) of fast layer kv_layer, [fast Hkv][kv_rows <= ncb][fast hd].  Bit patterns of the context's 16-bit type.
  * tab (which = 1, qkv0 = 1): row tab_row of the LOOP's own table of layer 0's q k v by drawn code (eng_qkv0_table_kernel;
  * ft_test_qkv0_tab reads the lock-step batches' table, another buffer built by another kernel), [QKVN] bf16 patterns.
- * FT_ERR_ARG: a bad which / layer / slot / row count, an f32 context asked for K/V; FT_ERR_STATE: a vector array on a context
+ * In an f32 context kv_k / kv_v receive f32 values (twice the room; the pointers are declared for the 16-bit case).
+ * FT_ERR_ARG: a bad which / layer / slot / row count; FT_ERR_STATE: a vector array on a context
  * whose engine of that kind is off, fewer copies than exist, a table row where there is no table. */
 typedef struct ft_test_engine_io {
     int32_t which, copies;
@@ -194,6 +196,43 @@ const char* ft_test_codec_trace_variant(int32_t id, int32_t* bm, int32_t* bn);
 ft_status ft_test_codec_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t cap, int32_t* info);
 ft_status ft_test_codec_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t* kind, int32_t* is_f32, int64_t* elems,
                                      void* dst);
+
+/* Test hook: a launch trace of the AR frame (host code only: no kernel, no branch in a kernel, nothing in a captured graph;
+ * off, it costs one null-pointer test per launch site).  ft_test_ar_trace_arm makes the NEXT ft_ar_decode with n_frames == 1,
+ * or the NEXT ft_ar_first_frames, on this context record one entry per kernel launch, in launch order; any other prompt or
+ * decode call disarms it untraced.  The traced decode call launches its frame eagerly (the FT_NO_GRAPH branch), never from
+ * a captured graph and never on the frame engine: arming a one-slot context whose frames run on the engine is FT_ERR_STATE,
+ * and so is the armed call itself where it would go to the engine (one slot on a context that owns one).
+ * Recording only reads: the traced call's frames and the state it leaves equal the untraced call's bit for bit.
+ * An entry: a stable name - "embed", "slow.<l>.wqkv|attn|wo|w13|w2" ("slow.<l>.attn.merge": attn_combine_rows_kernel behind a
+ * split lock-step attention), "fproj", "xo_rows", "head", "draw.<cb>" (the four-launch draw: "draw.0.cut|count|race|finish"),
+ * "fast.<cb>.<l>.wqkv|attn|wo|w13|w2" ("fast.pair.<l>...": codebook positions 0 and 1 in one pass), "fast.<cb>.head" -, the
+ * row offset m0, the rows and the columns of the launch, and the class its dispatcher picked, cls[4]: a lock-step Linear
+ * {WIDE_ID_*}; a gemv {MB, R, NT} ({-2, R, NT}: gemv_attn_combine_kernel); an attention {KV splits; 0: attn_wide_kernel}; a draw
+ * launch {what} (ft_test_draw's word).  Entries [first, first + count) also keep a host copy of every buffer the launch wrote,
+ * taken at that point of the stream and WHOLE: every row of the allocation, so the rows outside [m0, m0 + rows) can be held
+ * against the record before.  Buffer ids (AR_TB_*), f32 [rows][cols] unless said: 0 x [max_batch][dim], 1 qkv, 2 y
+ * [max_batch][y_ld], 3 g, 4 logits, 5 hid (x itself where fast_dim == dim), 6 femb, 7 xf, 8 qkvf [2 ceil16(max_batch)][fast q k v
+ * width], 9 gf, 10 flog [max_batch][fastV], 11 part_o, 12 part_ml (flat: row m's partials at m H nsplit hd / m H nsplit 2 for
+ * the call's split count); raw 16-bit octet-major [width / 8][xo_ldm][8], reported as rows = width / 8, cols = 8 xo_ldm: 20
+ * xo_x, 21 xo_xf, 22 xo_femb, 23 xo_y, 24 xo_g; int32: 30 tokn, 31 tok [max_batch][R], 32 pos, 33 nf, 34 done [1][max_batch], 35
+ * seq [max_batch][R cap], 36 cut [max_batch][8], 37 chunk_cnt, 38 part_idx [1][max_batch ceil(vocab / 1024)].  A draw entry
+ * lists every buffer finish_draw can write, written in this launch or not.  The K/V caches are not copied: read them before and
+ * after the call with ft_test_engine_handoffs (which takes an f32 context too: its arrays then hold f32 values).
+ * ft_test_ar_trace_count: launches the last traced call recorded (-1: a copy failed); info[5] (may be NULL) = {kind (0 none,
+ * 1 a decode frame, 2 first frames), m0, rows of the call, 1 if still armed, buffers of the record before the first launch}.
+ * That record (launch index -1 of ft_test_ar_trace_buffer) holds every buffer listed above as the call found it: what a
+ * buffer's first write in the call is held against.
+ * ft_test_ar_trace_launch: info[9] = {m0, rows, cols, buffers, 1 if held, cls[0..3]}.
+ * ft_test_ar_trace_buffer: info[4] = {id, bytes per element, rows, cols} of buffer j of launch i; dst != NULL receives it
+ * (once: the copy is released).
+ * ft_test_ar_trace_state: which = 0 before the first launch (after the call's controls went up and a frozen row's position was
+ * put back inside its cache), 1 at the end of the call: tok [max_batch][R], pos, nf, done [max_batch], seq [max_batch][R][cap]. */
+ft_status ft_test_ar_trace_arm(ft_ctx* ctx, int32_t first, int32_t count);
+int32_t ft_test_ar_trace_count(ft_ctx* ctx, int32_t* info);
+ft_status ft_test_ar_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t cap, int32_t* info);
+ft_status ft_test_ar_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t* info, void* dst);
+ft_status ft_test_ar_trace_state(ft_ctx* ctx, int32_t which, int32_t* tok, int32_t* pos, int32_t* nf, int32_t* done, int32_t* seq);
 
 /* Test hook: ONE Linear of a lock-step batch through the product's own dispatcher (engine.hip: wide_gemm), so the tile
  * class, the K split and the choice of wide_head_kernel are the product's.  epi: 0 store (fused RMSNorm; f32 output
