@@ -740,6 +740,15 @@ struct Launch {
     void chk() { hipError_t e = hipGetLastError(); if (e != hipSuccess && err == hipSuccess) err = e; }
 };
 
+// The model's type as template arguments: by_dtype(ctx, [&](auto t) { using T = decltype(t); f<typename T::WT, T::ROUND>(..); })
+template <typename W, int R> struct DType { typedef W WT; static constexpr int ROUND = R; };
+template <typename F>
+static auto by_dtype(const ft_ctx* ctx, F&& f) {
+    if (ctx->c.dtype == FT_BF16) return f(DType<bf16_t, RND_BF16>{});
+    if (ctx->c.dtype == FT_F16) return f(DType<f16_t, RND_F16>{});
+    return f(DType<float, RND_NONE>{});
+}
+
 // ---- launch trace of the AR frame (test hook, fishtts_hip_test.h).  A traced call appends one record per launch, in launch
 // order; the launches of the armed range also copy every buffer they wrote to the host, WHOLE (every row of the allocation:
 // the rows outside [m0, m0 + M) are there for the reader to compare with the record before), at that point of the stream.
@@ -817,6 +826,15 @@ static std::string tr_name(const char* fmt, ...) {
     va_end(ap);
     return buf;
 }
+// The trace's name of a layer's launch, <stack>.<n>.<op> (slow.3.wo, fast.2.0.wqkv, fast.pair.1.attn; the codebook heads are
+// fast.<cb>.head), or <op> alone (fproj, head).  Formatted only while a trace is active.
+struct TrName {
+    const char* stack; int n; const char* op;
+    std::string str() const { return stack ? tr_name("%s.%d.%s", stack, n, op) : std::string(op); }
+};
+// A working buffer from the launch's first row on, with its trace id: f32 rows, or octet-major 16-bit elements (wide_kernels.h)
+struct RowBuf { float* p; int id; };
+struct XoBuf { bf16_t* p; int id; };
 // d_tok, d_pos, d_nf, d_done and the frame store d_seq of every slot (which: 0 before the first launch, 1 after the call)
 static void tr_state(ft_ctx* ctx, int which) {
     ArTrace& t = *ctx->trace;
@@ -924,6 +942,13 @@ static int wide_gemm(Launch& L, const bf16_t* X, const void* W, const float* bia
     if (!ok && L.err == hipSuccess) L.err = hipErrorInvalidValue;
     L.chk();
     return id;
+}
+// A Linear of the frame on that launch, with its trace record: the output is f32 rows (WEPI_STORE) or octet-major
+template <typename WT>
+static void wide_linear(Launch& L, const TrName& nm, const bf16_t* X, const void* W, const float* bias, const void* gain, int N, int K,
+                        int epi, RowBuf out_f32, long ldo, XoBuf out_xo, const bf16_t* resid_xo, int rows = 0, bool vocab_head = false) {
+    const int id = wide_gemm<WT>(L, X, W, bias, N, K, gain, epi, out_f32.p, ldo, out_xo.p, resid_xo, rows, vocab_head);
+    if (L.ctx->trace) tr_rec(L, nm.str(), rows > 0 ? rows : L.M, epi == WEPI_SWIGLU ? N / 2 : N, TrCls{id}, {out_xo.p ? out_xo.id : out_f32.id});
 }
 
 // f32 rows -> octet-major 16-bit elements (the values are exact in the model's type): the residual stream a prompt pass left in ctx->x
@@ -1131,6 +1156,28 @@ static int rows_per_wave(int N, int M) {
     return 1;
 }
 
+// A Linear of the frame on the GEMV launches.  The frame's GemvP are filled here and nowhere else: a gain selects the RMSNorm
+// prologue, a residual (rows of the output's stride) belongs to EPI_RESID, ldo is the stride of the output rows (N / 2
+// columns under EPI_SWIGLU).  gemv_launch runs a filled one and owns its trace record.
+static GemvP gemv_params(const ft_ctx* ctx, const void* W, const void* bias, const void* gain, const float* x, int ldx, float* out, int ldo,
+                         const float* resid, int N, int K, int epi, int nt) {
+    GemvP p{};
+    p.W = W; p.bias = bias; p.x = x; p.ldx = ldx; p.gain = gain; p.eps = gain ? ctx->c.norm_eps : 0.f;
+    p.out = out; p.ldo = ldo; p.resid = resid; p.ldr = resid ? ldo : 0; p.N = N; p.K = K;
+    p.pro = gain ? PRO_RMSNORM : PRO_NONE; p.epi = epi; p.nt = nt;
+    return p;
+}
+template <typename WT, int ROUND>
+static void gemv_launch(Launch& L, const TrName& nm, int buf, const GemvP& p) {
+    const GemvId id = gemv<WT, ROUND>(L, p, rows_per_wave(p.N, L.M));
+    if (L.ctx->trace) tr_rec(L, nm.str(), L.M, p.epi == EPI_SWIGLU ? p.N / 2 : p.N, TrCls{id.MB, id.R, id.NT}, {buf});
+}
+template <typename WT, int ROUND>
+static void gemv_linear(Launch& L, const TrName& nm, const void* W, const void* bias, const void* gain, const float* x, int ldx, RowBuf out,
+                        int ldo, const float* resid, int N, int K, int epi, int nt) {
+    gemv_launch<WT, ROUND>(L, nm, out.id, gemv_params(L.ctx, W, bias, gain, x, ldx, out.p, ldo, resid, N, K, epi, nt));
+}
+
 template <typename WT, int ROUND>
 static void attn_decode(Launch& L, const AttnP& p) {
     ft_ctx* ctx = L.ctx;
@@ -1165,7 +1212,7 @@ static void gemv_combine_nt(Launch& L, const GemvP& p, const AttnP& a, int nt) {
 
 // The "decode attention, then Wo" part of a slow layer for 1..max_batch rows: attn_decode_kernel over ctx->nsplit KV splits, then the
 // Wo product with the residual add - with more than one split the partials are merged inside it (gemv_attn_combine_kernel),
-// with one it reads the attention's y.  enqueue_slow and the test hook ft_test_decode_attn both call it.
+// with one it reads the attention's y.  enqueue_slow's attention step and the test hook ft_test_decode_attn both call it.
 template <typename WT, int ROUND>
 static void decode_attn_wo(Launch& L, const AttnP& a, const GemvP& o, int li = -1) {
     ft_ctx* ctx = L.ctx;
@@ -1191,8 +1238,7 @@ static void decode_attn_wo(Launch& L, const AttnP& a, const GemvP& o, int li = -
         }
         L.chk();
     } else {
-        const GemvId id = gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
-        if (ctx->trace) tr_rec(L, tr_name("slow.%d.wo", li), L.M, o.N, TrCls{id.MB, id.R, id.NT}, {TB_X});
+        gemv_launch<WT, ROUND>(L, TrName{"slow", li, "wo"}, TB_X, o);
     }
 }
 
@@ -1234,18 +1280,84 @@ static int wide_attn(Launch& L, AttnP& a, int li = -1) {
     return ns;
 }
 
+// One transformer stack as a decode frame walks it: the slow stack, or the fast stack at one codebook step.  Everything in which
+// the two differ only by name is a field; the buffers start at the launch's first row m0.
+struct Stack {
+    const FtLayer* layers; int n_layer;
+    int D, H, Hkv, hd, F, qkvN;
+    const float* rope;
+    size_t cache_m_stride;      // elements of one slot in a layer's K or V cache
+    int nt;                     // GemvP::nt (non-temporal weight loads) of every product of the stack: 1 slow, 0 fast
+    int rows;                   // rows of a lock-step Linear: M, or xo_pair + M in the paired pass
+    char name[16];              // the launch trace's name of the stack: slow, fast.<cb> or fast.pair (filled while a trace is active)
+    RowBuf x, qkv, y, g;        // f32 rows: residual stream, q k v, attention output (stride ctx->y_ld), SwiGLU vector
+    XoBuf xo_x, xo_y, xo_g;     // octet-major, lock-step batches: residual stream, attention output, SwiGLU vector
+};
+static XoBuf xo_at(bf16_t* p, int m0, int id) { return XoBuf{p ? p + (size_t)m0 * 8 : nullptr, id}; }
+static Stack slow_stack(const Launch& L) {
+    const ft_ctx* ctx = L.ctx;
+    const ft_ar_config& c = ctx->c;
+    const size_t m0 = L.m0;
+    Stack S{ctx->layers.data(), c.n_layer, c.dim, c.n_head, c.n_local_heads, c.head_dim, c.intermediate_size};
+    S.qkvN = (S.H + 2 * S.Hkv) * S.hd; S.rope = ctx->rope; S.cache_m_stride = ctx->cache_m_stride; S.nt = 1; S.rows = L.M;
+    if (ctx->trace) snprintf(S.name, sizeof S.name, "slow");
+    S.x = {ctx->x + m0 * S.D, TB_X}; S.qkv = {ctx->qkv + m0 * S.qkvN, TB_QKV}; S.y = {ctx->y + m0 * ctx->y_ld, TB_Y}; S.g = {ctx->g + m0 * S.F, TB_G};
+    S.xo_x = xo_at(ctx->xo_x, L.m0, TB_XO_X); S.xo_y = xo_at(ctx->xo_y, L.m0, TB_XO_Y); S.xo_g = xo_at(ctx->xo_g, L.m0, TB_XO_G);
+    return S;
+}
+// pair: rows [0, M) at position 0 and rows [xo_pair, xo_pair + M) at position 1 (cb == 1) in one pass
+static Stack fast_stack(const Launch& L, int cb, bool pair) {
+    const ft_ctx* ctx = L.ctx;
+    const ft_ar_config& c = ctx->c;
+    const size_t m0 = L.m0;
+    Stack S{ctx->flayers.data(), c.n_fast_layer, c.fast_dim, c.fast_n_head, c.fast_n_local_heads, c.fast_head_dim, c.fast_intermediate_size};
+    S.qkvN = (S.H + 2 * S.Hkv) * S.hd; S.rope = ctx->frope; S.cache_m_stride = ctx->fcache_m_stride; S.nt = 0; S.rows = pair ? ctx->xo_pair + L.M : L.M;
+    if (ctx->trace) { if (pair) snprintf(S.name, sizeof S.name, "fast.pair"); else snprintf(S.name, sizeof S.name, "fast.%d", cb); }
+    S.x = {ctx->xf + m0 * S.D, TB_XF}; S.qkv = {ctx->qkvf + m0 * S.qkvN, TB_QKVF}; S.g = {ctx->gf + m0 * S.F, TB_GF};
+    S.y = {ctx->y + m0 * ctx->y_ld, TB_Y};  // the slow attention's y buffer is free here
+    S.xo_x = xo_at(ctx->xo_xf, L.m0, TB_XO_XF); S.xo_y = xo_at(ctx->xo_y, L.m0, TB_XO_Y); S.xo_g = xo_at(ctx->xo_g, L.m0, TB_XO_G);
+    return S;
+}
+
+// One transformer layer of a decode frame: wqkv, attention, wo, w13, w2, on the GEMV launches or, in a wide batch, on the MFMA
+// launches.
+//   in, in_xo   the layer's input, which is also the residual of Wo: the stack's own stream, except in layer 0 of the fast
+//               stack (the hidden state or a drawn code's embedding); the layer leaves its output in the stack's stream
+//   skip_wqkv   the previous draw left this layer's q k v (wide_qkv0_tab): no launch
+//   attention   the stack's attention step, (layer, li, Wo's GemvP or null in a wide batch) -> true where it ran Wo itself
+// L.gemv_only is the attention step's to honour (no Linear is skipped); S.nt and S.rows are the stack's.
+template <typename WT, int ROUND, typename Attn>
+static void enqueue_layer(Launch& L, const Stack& S, int li, const float* in, const bf16_t* in_xo, bool skip_wqkv, Attn&& attention) {
+    const FtLayer& l = S.layers[li];
+    const int HD = S.H * S.hd;
+    const auto nm = [&](const char* op) { return TrName{S.name, li, op}; };
+    if (wide_batch(L)) {
+        if constexpr (ROUND != RND_NONE) {
+            // five launches per layer (wide_kernels.h): the residual stream xo, the attention output and the SwiGLU vector
+            // travel octet-major in the 16-bit type; q k v stay f32 rows for the attention kernel
+            if (!skip_wqkv) wide_linear<WT>(L, nm("wqkv"), in_xo, l.wqkv, l.bqkv_f32, l.attn_norm, S.qkvN, S.D, WEPI_STORE, S.qkv, S.qkvN, XoBuf{}, nullptr, S.rows);
+            attention(l, li, nullptr);
+            wide_linear<WT>(L, nm("wo"), S.xo_y.p, l.wo, l.bo_f32, nullptr, S.D, HD, WEPI_RESID, RowBuf{}, 0, S.xo_x, in_xo, S.rows);
+            wide_linear<WT>(L, nm("w13"), S.xo_x.p, l.w13, nullptr, l.ffn_norm, 2 * S.F, S.D, WEPI_SWIGLU, RowBuf{}, 0, S.xo_g, nullptr, S.rows);
+            wide_linear<WT>(L, nm("w2"), S.xo_g.p, l.w2, nullptr, nullptr, S.D, S.F, WEPI_RESID, RowBuf{}, 0, S.xo_x, S.xo_x.p, S.rows);
+        }
+        return;
+    }
+    if (!skip_wqkv) gemv_linear<WT, ROUND>(L, nm("wqkv"), l.wqkv, l.bqkv, l.attn_norm, in, S.D, S.qkv, S.qkvN, nullptr, S.qkvN, S.D, EPI_STORE, S.nt);
+    const GemvP wo = gemv_params(L.ctx, l.wo, l.bo, nullptr, S.y.p, L.ctx->y_ld, S.x.p, S.D, in, S.D, HD, EPI_RESID, S.nt);
+    if (!attention(l, li, &wo)) gemv_launch<WT, ROUND>(L, nm("wo"), S.x.id, wo);
+    gemv_linear<WT, ROUND>(L, nm("w13"), l.w13, nullptr, l.ffn_norm, S.x.p, S.D, S.g, S.F, nullptr, 2 * S.F, S.D, EPI_SWIGLU, S.nt);
+    gemv_linear<WT, ROUND>(L, nm("w2"), l.w2, nullptr, nullptr, S.g.p, S.F, S.x, S.D, S.x.p, S.D, S.F, EPI_RESID, S.nt);
+}
+
 // fast_project_in on the pre-norm hidden state (llama.py:453,590); identity when fast_dim == dim
 template <typename WT, int ROUND>
 static void enqueue_fproj(Launch& L) {
     ft_ctx* ctx = L.ctx;
     const ft_ar_config& c = ctx->c;
     if (c.fast_dim == c.dim) return;
-    GemvP q{};
-    q.W = ctx->fproj_w; q.bias = ctx->fproj_b; q.x = ctx->x + (size_t)L.m0 * c.dim; q.ldx = c.dim;
-    q.out = ctx->hid + (size_t)L.m0 * c.fast_dim; q.ldo = c.fast_dim; q.N = c.fast_dim; q.K = c.dim;
-    q.pro = PRO_NONE; q.epi = EPI_STORE;
-    const GemvId id = gemv<WT, ROUND>(L, q, rows_per_wave(q.N, L.M));
-    if (ctx->trace) tr_rec(L, "fproj", L.M, q.N, TrCls{id.MB, id.R, id.NT}, {TB_HID});
+    gemv_linear<WT, ROUND>(L, TrName{nullptr, 0, "fproj"}, ctx->fproj_w, ctx->fproj_b, nullptr, ctx->x + (size_t)L.m0 * c.dim, c.dim,
+                           RowBuf{ctx->hid + (size_t)L.m0 * c.fast_dim, TB_HID}, c.fast_dim, nullptr, c.fast_dim, c.dim, EPI_STORE, 0);
 }
 
 // One slow-transformer pass over the current input column of rows [m0, m0+M) (llama.py:400-453).
@@ -1254,95 +1366,52 @@ static void enqueue_slow(Launch& L, const int* toks, long tok_row_stride, long t
     ft_ctx* ctx = L.ctx;
     const ft_ar_config& c = ctx->c;
     const int m0 = L.m0;
-    const size_t qkvN = (size_t)(c.n_head + 2 * c.n_local_heads) * c.head_dim;
-    float* x = ctx->x + (size_t)m0 * c.dim;
-    float* qkv = ctx->qkv + (size_t)m0 * qkvN;
-    float* y = ctx->y + (size_t)m0 * ctx->y_ld;
-    float* g = ctx->g + (size_t)m0 * c.intermediate_size;
+    const Stack S = slow_stack(L);
+    const bool wide = wide_batch(L);
 
     EmbedP e{};
     e.emb = ctx->emb; e.cb_emb = ctx->cb_emb; e.toks = toks; e.tok_row_stride = tok_row_stride;
-    e.tok_m_stride = tok_m_stride; e.col = col; e.x = x; e.ldx = c.dim; e.D = c.dim; e.ncb = c.num_codebooks;
+    e.tok_m_stride = tok_m_stride; e.col = col; e.x = S.x.p; e.ldx = c.dim; e.D = c.dim; e.ncb = c.num_codebooks;
     e.cbsize = c.codebook_size; e.vocab = c.vocab_size; e.sem_begin = c.semantic_begin_id;
     e.sem_end = c.semantic_end_id; e.scale = c.scale_codebook_embeddings;
     e.inv_div = (float)sqrt((double)(c.num_codebooks + 1));
-    const bool wide = wide_batch(L);
-    if (wide) { e.xo = ctx->xo_x + (size_t)m0 * 8; e.xo_ldm = ctx->xo_ldm; }
+    if (wide) { e.xo = S.xo_x.p; e.xo_ldm = ctx->xo_ldm; }
     if (!L.gemv_only) embed_kernel<WT, ROUND><<<dim3((c.dim + 255) / 256, L.M), 256, 0, L.s>>>(e);
     L.chk();
     if (ctx->trace) { if (wide) tr_rec(L, "embed", L.M, c.dim, TrCls{}, {TB_X, TB_XO_X}); else tr_rec(L, "embed", L.M, c.dim, TrCls{}, {TB_X}); }
 
-    for (int li = 0; li < c.n_layer; ++li) {
-        const FtLayer& l = ctx->layers[li];
+    // a wide batch: wide_attn into the octet-major y; 1..4 rows: decode_attn_wo, which also runs Wo (the split merge is inside it)
+    auto attention = [&](const FtLayer& l, int li, const GemvP* wo) {
+        AttnP a{};
+        a.qkv = S.qkv.p; a.ldq = S.qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = S.rope;
+        a.kc = (char*)l.kc + (size_t)m0 * S.cache_m_stride * ctx->esz;
+        a.vc = (char*)l.vc + (size_t)m0 * S.cache_m_stride * ctx->esz;
+        a.cache_m_stride = S.cache_m_stride; a.pos = ctx->d_pos + m0; a.pos_off = L.pos_off;
+        a.H = S.H; a.Hkv = S.Hkv; a.hd = S.hd; a.n_slots = ctx->n_slots;
+        a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)S.hd);
         if (wide) {
             if constexpr (ROUND != RND_NONE) {
-                // five launches per layer (wide_kernels.h): the residual stream xo, the attention output and the SwiGLU vector
-                // travel octet-major in the 16-bit type; q k v stay f32 rows for the attention kernel
-                const int D = c.dim, HD = c.n_head * c.head_dim, F = c.intermediate_size, ldm = ctx->xo_ldm;
-                bf16_t* xo = ctx->xo_x + (size_t)m0 * 8;
-                bf16_t* yo = ctx->xo_y + (size_t)m0 * 8;
-                bf16_t* go = ctx->xo_g + (size_t)m0 * 8;
-                int id = wide_gemm<WT>(L, xo, l.wqkv, l.bqkv_f32, (int)qkvN, D, l.attn_norm, WEPI_STORE, qkv, (long)qkvN, nullptr, nullptr);
-                if (ctx->trace) tr_rec(L, tr_name("slow.%d.wqkv", li), L.M, (int)qkvN, TrCls{id}, {TB_QKV});
-                AttnP a{};
-                a.qkv = qkv; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->rope;
-                a.kc = (char*)l.kc + (size_t)m0 * ctx->cache_m_stride * ctx->esz;
-                a.vc = (char*)l.vc + (size_t)m0 * ctx->cache_m_stride * ctx->esz;
-                a.cache_m_stride = ctx->cache_m_stride; a.pos = ctx->d_pos + m0; a.pos_off = L.pos_off;
-                a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots;
-                a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim);
-                a.y = nullptr; a.ldy = HD; a.y_bf = yo; a.y_xo_ldm = ldm;
+                a.y = nullptr; a.ldy = S.H * S.hd; a.y_bf = S.xo_y.p; a.y_xo_ldm = ctx->xo_ldm;
                 wide_attn<WT, ROUND>(L, a, li);
-                id = wide_gemm<WT>(L, yo, l.wo, l.bo_f32, D, HD, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
-                if (ctx->trace) tr_rec(L, tr_name("slow.%d.wo", li), L.M, D, TrCls{id}, {TB_XO_X});
-                id = wide_gemm<WT>(L, xo, l.w13, nullptr, 2 * F, D, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr);
-                if (ctx->trace) tr_rec(L, tr_name("slow.%d.w13", li), L.M, F, TrCls{id}, {TB_XO_G});
-                id = wide_gemm<WT>(L, go, l.w2, nullptr, D, F, nullptr, WEPI_RESID, nullptr, 0, xo, xo);
-                if (ctx->trace) tr_rec(L, tr_name("slow.%d.w2", li), L.M, D, TrCls{id}, {TB_XO_X});
             }
-            continue;
+            return false;
         }
-        GemvP p{};
-        p.W = l.wqkv; p.bias = l.bqkv; p.x = x; p.ldx = c.dim; p.gain = l.attn_norm; p.eps = c.norm_eps;
-        p.out = qkv; p.ldo = (int)qkvN; p.N = (int)qkvN; p.K = c.dim; p.pro = PRO_RMSNORM; p.epi = EPI_STORE; p.nt = 1;
-        GemvId gid = gemv<WT, ROUND>(L, p, rows_per_wave(p.N, L.M));
-        if (ctx->trace) tr_rec(L, tr_name("slow.%d.wqkv", li), L.M, p.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_QKV});
-
-        AttnP a{};
-        a.qkv = qkv; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->rope;
-        a.kc = (char*)l.kc + (size_t)m0 * ctx->cache_m_stride * ctx->esz;
-        a.vc = (char*)l.vc + (size_t)m0 * ctx->cache_m_stride * ctx->esz;
-        a.cache_m_stride = ctx->cache_m_stride; a.pos = ctx->d_pos + m0; a.pos_off = L.pos_off;
-        a.H = c.n_head; a.Hkv = c.n_local_heads; a.hd = c.head_dim; a.n_slots = ctx->n_slots;
-        a.nsplit = ctx->nsplit; a.eps = c.norm_eps; a.scale = 1.0f / sqrtf((float)c.head_dim);
-        a.y = y; a.ldy = ctx->y_ld;
-        a.part_o = ctx->part_o + (size_t)m0 * c.n_head * ctx->nsplit * c.head_dim;
-        a.part_ml = ctx->part_ml + (size_t)m0 * c.n_head * ctx->nsplit * 2;
-        GemvP o{};
-        o.W = l.wo; o.bias = l.bo; o.x = y; o.ldx = ctx->y_ld; o.out = x; o.ldo = c.dim;
-        o.resid = x; o.ldr = c.dim; o.N = c.dim; o.K = c.n_head * c.head_dim; o.pro = PRO_NONE; o.epi = EPI_RESID; o.nt = 1;
-        decode_attn_wo<WT, ROUND>(L, a, o, li);
-
-        GemvP f{};
-        f.W = l.w13; f.x = x; f.ldx = c.dim; f.gain = l.ffn_norm; f.eps = c.norm_eps; f.out = g;
-        f.ldo = c.intermediate_size; f.N = 2 * c.intermediate_size; f.K = c.dim; f.pro = PRO_RMSNORM; f.epi = EPI_SWIGLU; f.nt = 1;
-        gid = gemv<WT, ROUND>(L, f, rows_per_wave(f.N, L.M));
-        if (ctx->trace) tr_rec(L, tr_name("slow.%d.w13", li), L.M, c.intermediate_size, TrCls{gid.MB, gid.R, gid.NT}, {TB_G});
-
-        GemvP d{};
-        d.W = l.w2; d.x = g; d.ldx = c.intermediate_size; d.out = x; d.ldo = c.dim; d.resid = x; d.ldr = c.dim;
-        d.N = c.dim; d.K = c.intermediate_size; d.pro = PRO_NONE; d.epi = EPI_RESID; d.nt = 1;
-        gid = gemv<WT, ROUND>(L, d, rows_per_wave(d.N, L.M));
-        if (ctx->trace) tr_rec(L, tr_name("slow.%d.w2", li), L.M, d.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_X});
-    }
+        a.nsplit = ctx->nsplit; a.y = S.y.p; a.ldy = ctx->y_ld;
+        a.part_o = ctx->part_o + (size_t)m0 * S.H * ctx->nsplit * S.hd;
+        a.part_ml = ctx->part_ml + (size_t)m0 * S.H * ctx->nsplit * 2;
+        decode_attn_wo<WT, ROUND>(L, a, *wo, li);
+        return true;
+    };
+    for (int li = 0; li < S.n_layer; ++li) enqueue_layer<WT, ROUND>(L, S, li, S.x.p, S.xo_x.p, false, attention);
     if (with_head) enqueue_fproj<WT, ROUND>(L);
 }
 
-// final norm + vocabulary head (llama.py:446-451)
+// final norm + vocabulary head (llama.py:446-451); as the slow stack's products it streams its weights with nt = 1
 template <typename WT, int ROUND>
 static void enqueue_head(Launch& L) {
     ft_ctx* ctx = L.ctx;
     const ft_ar_config& c = ctx->c;
+    const RowBuf logits{ctx->logits + (size_t)L.m0 * c.vocab_size, TB_LOGITS};
     if (wide_batch(L)) {
         if (L.tail_only) {
             xo_from_rows_kernel<WT><<<dim3((c.dim + 255) / 256, L.M), 256, 0, L.s>>>(ctx->x + (size_t)L.m0 * c.dim, c.dim, c.dim,
@@ -1350,19 +1419,13 @@ static void enqueue_head(Launch& L) {
             L.chk();
             if (ctx->trace) tr_rec(L, "xo_rows", L.M, c.dim, TrCls{}, {TB_XO_X});
         }
-        if constexpr (ROUND != RND_NONE) {
-            const int id = wide_gemm<WT>(L, ctx->xo_x + (size_t)L.m0 * 8, ctx->head, nullptr, c.vocab_size, c.dim, ctx->norm, WEPI_STORE,
-                                         ctx->logits + (size_t)L.m0 * c.vocab_size, c.vocab_size, nullptr, nullptr, 0, true);
-            if (ctx->trace) tr_rec(L, "head", L.M, c.vocab_size, TrCls{id}, {TB_LOGITS});
-        }
+        if constexpr (ROUND != RND_NONE)
+            wide_linear<WT>(L, TrName{nullptr, 0, "head"}, ctx->xo_x + (size_t)L.m0 * 8, ctx->head, nullptr, ctx->norm, c.vocab_size, c.dim, WEPI_STORE,
+                            logits, c.vocab_size, XoBuf{}, nullptr, 0, true);
         return;
     }
-    GemvP h{};
-    h.W = ctx->head; h.x = ctx->x + (size_t)L.m0 * c.dim; h.ldx = c.dim; h.gain = ctx->norm; h.eps = c.norm_eps;
-    h.out = ctx->logits + (size_t)L.m0 * c.vocab_size; h.ldo = c.vocab_size; h.N = c.vocab_size; h.K = c.dim;
-    h.pro = PRO_RMSNORM; h.epi = EPI_STORE; h.nt = 1;
-    const GemvId id = gemv<WT, ROUND>(L, h, rows_per_wave(h.N, L.M));
-    if (ctx->trace) tr_rec(L, "head", L.M, h.N, TrCls{id.MB, id.R, id.NT}, {TB_LOGITS});
+    gemv_linear<WT, ROUND>(L, TrName{nullptr, 0, "head"}, ctx->head, nullptr, ctx->norm, ctx->x + (size_t)L.m0 * c.dim, c.dim, logits, c.vocab_size,
+                           nullptr, c.vocab_size, c.dim, EPI_STORE, 1);
 }
 
 // Returns what it launched (the test hook ft_test_draw reports it; the frames ignore it): DRAW_* below
@@ -1444,121 +1507,50 @@ template <typename WT, int ROUND>
 static void enqueue_fast_step(Launch& L, const int cb, const bool pair = false) {
     ft_ctx* ctx = L.ctx;
     const ft_ar_config& c = ctx->c;
-    const int m0 = L.m0;
-    const int Df = c.fast_dim, Hf = c.fast_n_head, Hkvf = c.fast_n_local_heads, hdf = c.fast_head_dim;
-    const size_t qkvN = (size_t)(Hf + 2 * Hkvf) * hdf;
-    float* xf = ctx->xf + (size_t)m0 * Df;
-    float* qkvf = ctx->qkvf + (size_t)m0 * qkvN;
-    float* gf = ctx->gf + (size_t)m0 * c.fast_intermediate_size;
-    char tp[16] = "";      // the launch trace's name of this step: fast.<cb>, or fast.pair
-    if (ctx->trace) { if (pair) snprintf(tp, sizeof tp, "fast.pair"); else snprintf(tp, sizeof tp, "fast.%d", cb); }
-    {
-        const float* xin = cb == 0 ? ctx->hid + (size_t)m0 * Df : ctx->femb + (size_t)m0 * Df;
-        const bool wide = wide_batch(L);
-        for (int li = 0; li < c.n_fast_layer; ++li) {
-            const FtLayer& l = ctx->flayers[li];
-            const float* xl = li == 0 ? xin : xf;
-            if (wide) {
-                if constexpr (ROUND != RND_NONE) {
-                    // as the slow layers; layer 0 reads the slow stack's residual stream (position 0) or the drawn code's embedding
-                    // pair: rows [0, M) at position 0 and rows [xo_pair, xo_pair + M) at position 1 (cb == 1) in one pass
-                    const int HDf = Hf * hdf, Ff = c.fast_intermediate_size, M = L.M, ldm = ctx->xo_ldm;
-                    const int rows = pair ? ctx->xo_pair + M : M;
-                    const bf16_t* xin_o = ((cb == 0 || pair) ? ctx->xo_x : ctx->xo_femb) + (size_t)m0 * 8;
-                    bf16_t* xfo = ctx->xo_xf + (size_t)m0 * 8;
-                    bf16_t* yo = ctx->xo_y + (size_t)m0 * 8;
-                    bf16_t* go = ctx->xo_g + (size_t)m0 * 8;
-                    const bf16_t* xlo = li == 0 ? xin_o : xfo;
-                    // layer 0 of steps >= 2: the draw of the previous step left this step's q k v (wide_qkv0_build)
-                    int id = -1;
-                    if (!(li == 0 && cb >= 2 && !pair && ctx->wide_qkv0_tab)) {
-                        id = wide_gemm<WT>(L, xlo, l.wqkv, nullptr, (int)qkvN, Df, l.attn_norm, WEPI_STORE, qkvf, (long)qkvN, nullptr, nullptr, rows);
-                        if (ctx->trace) tr_rec(L, tr_name("%s.%d.wqkv", tp, li), rows, (int)qkvN, TrCls{id}, {TB_QKVF});
-                    }
-                    FastAttnP a{};
-                    a.qkv = qkvf; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->frope;
-                    a.kc = (char*)l.kc + (size_t)m0 * ctx->fcache_m_stride * ctx->esz;
-                    a.vc = (char*)l.vc + (size_t)m0 * ctx->fcache_m_stride * ctx->esz;
-                    a.cache_m_stride = ctx->fcache_m_stride; a.c = pair ? 0 : cb; a.H = Hf; a.Hkv = Hkvf; a.hd = hdf;
-                    a.ncb = c.num_codebooks; a.eps = c.norm_eps; a.scale = (float)(1.0 / sqrt((double)hdf));
-                    a.y_bf = yo; a.y_xo_ldm = ldm;
-                    a.pair_M = pair ? M : 0; a.pair_off = ctx->xo_pair;
-                    fast_attn_kernel<WT, ROUND><<<dim3(Hf, pair ? 2 * M : M), 64, 0, L.s>>>(a, nullptr, HDf);
-                    L.chk();
-                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.attn", tp, li), pair ? 2 * M : M, HDf, TrCls{}, {TB_XO_Y});
-                    id = wide_gemm<WT>(L, yo, l.wo, nullptr, Df, HDf, nullptr, WEPI_RESID, nullptr, 0, xfo, xlo, rows);
-                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.wo", tp, li), rows, Df, TrCls{id}, {TB_XO_XF});
-                    id = wide_gemm<WT>(L, xfo, l.w13, nullptr, 2 * Ff, Df, l.ffn_norm, WEPI_SWIGLU, nullptr, 0, go, nullptr, rows);
-                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.w13", tp, li), rows, Ff, TrCls{id}, {TB_XO_G});
-                    id = wide_gemm<WT>(L, go, l.w2, nullptr, Df, Ff, nullptr, WEPI_RESID, nullptr, 0, xfo, xfo, rows);
-                    if (ctx->trace) tr_rec(L, tr_name("%s.%d.w2", tp, li), rows, Df, TrCls{id}, {TB_XO_XF});
-                }
-                continue;
-            }
-            GemvP p{};
-            p.W = l.wqkv; p.bias = l.bqkv; p.x = xl; p.ldx = Df; p.gain = l.attn_norm; p.eps = c.norm_eps;
-            p.out = qkvf; p.ldo = (int)qkvN; p.N = (int)qkvN; p.K = Df; p.pro = PRO_RMSNORM; p.epi = EPI_STORE;
-            GemvId gid = gemv<WT, ROUND>(L, p, rows_per_wave(p.N, L.M));
-            if (ctx->trace) tr_rec(L, tr_name("%s.%d.wqkv", tp, li), L.M, p.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_QKVF});
+    const int m0 = L.m0, M = L.M;
+    const Stack S = fast_stack(L, cb, pair);
+    const bool wide = wide_batch(L);
+    // layer 0 reads the slow stack's hidden state (position 0; in a wide batch its residual stream) or the drawn code's
+    // embedding; the paired pass reads both from the slow stack's stream, where the semantic draw left position 1's rows
+    const float* xin = cb == 0 ? ctx->hid + (size_t)m0 * S.D : ctx->femb + (size_t)m0 * S.D;
+    const bf16_t* xin_o = wide ? ((cb == 0 || pair) ? ctx->xo_x : ctx->xo_femb) + (size_t)m0 * 8 : nullptr;
 
-            FastAttnP a{};
-            a.qkv = qkvf; a.ldq = (int)qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = ctx->frope;
-            a.kc = (char*)l.kc + (size_t)m0 * ctx->fcache_m_stride * ctx->esz;
-            a.vc = (char*)l.vc + (size_t)m0 * ctx->fcache_m_stride * ctx->esz;
-            a.cache_m_stride = ctx->fcache_m_stride; a.c = cb; a.H = Hf; a.Hkv = Hkvf; a.hd = hdf;
-            a.ncb = c.num_codebooks; a.eps = c.norm_eps; a.scale = (float)(1.0 / sqrt((double)hdf));
-            float* yf = ctx->y + (size_t)m0 * ctx->y_ld;  // the slow attention's y buffer is free here
-            if (!L.gemv_only) fast_attn_kernel<WT, ROUND><<<dim3(Hf, L.M), 64, 0, L.s>>>(a, yf, ctx->y_ld);
-            L.chk();
-            if (ctx->trace) tr_rec(L, tr_name("%s.%d.attn", tp, li), L.M, Hf * hdf, TrCls{}, {TB_Y});
-            GemvP o{};
-            o.W = l.wo; o.bias = l.bo; o.x = yf; o.ldx = ctx->y_ld; o.out = xf; o.ldo = Df; o.resid = xl;
-            o.ldr = Df; o.N = Df; o.K = Hf * hdf; o.pro = PRO_NONE; o.epi = EPI_RESID;
-            gid = gemv<WT, ROUND>(L, o, rows_per_wave(o.N, L.M));
-            if (ctx->trace) tr_rec(L, tr_name("%s.%d.wo", tp, li), L.M, o.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_XF});
-
-            GemvP f{};
-            f.W = l.w13; f.x = xf; f.ldx = Df; f.gain = l.ffn_norm; f.eps = c.norm_eps; f.out = gf;
-            f.ldo = c.fast_intermediate_size; f.N = 2 * c.fast_intermediate_size; f.K = Df; f.pro = PRO_RMSNORM;
-            f.epi = EPI_SWIGLU;
-            gid = gemv<WT, ROUND>(L, f, rows_per_wave(f.N, L.M));
-            if (ctx->trace) tr_rec(L, tr_name("%s.%d.w13", tp, li), L.M, c.fast_intermediate_size, TrCls{gid.MB, gid.R, gid.NT}, {TB_GF});
-
-            GemvP d{};
-            d.W = l.w2; d.x = gf; d.ldx = c.fast_intermediate_size; d.out = xf; d.ldo = Df; d.resid = xf; d.ldr = Df;
-            d.N = Df; d.K = c.fast_intermediate_size; d.pro = PRO_NONE; d.epi = EPI_RESID;
-            gid = gemv<WT, ROUND>(L, d, rows_per_wave(d.N, L.M));
-            if (ctx->trace) tr_rec(L, tr_name("%s.%d.w2", tp, li), L.M, d.N, TrCls{gid.MB, gid.R, gid.NT}, {TB_XF});
-        }
-        if (cb == 0) return;  // logits of position 0 are discarded (inference.py:122)
+    auto attention = [&](const FtLayer& l, int li, const GemvP*) {
+        FastAttnP a{};
+        a.qkv = S.qkv.p; a.ldq = S.qkvN; a.qn = l.qn; a.kn = l.kn; a.rope = S.rope;
+        a.kc = (char*)l.kc + (size_t)m0 * S.cache_m_stride * ctx->esz;
+        a.vc = (char*)l.vc + (size_t)m0 * S.cache_m_stride * ctx->esz;
+        a.cache_m_stride = S.cache_m_stride; a.H = S.H; a.Hkv = S.Hkv; a.hd = S.hd;
+        a.ncb = c.num_codebooks; a.eps = c.norm_eps; a.scale = (float)(1.0 / sqrt((double)S.hd));
+        const int HD = S.H * S.hd, rows = pair ? 2 * M : M;      // (a paired pass is a wide batch)
         if (wide) {
-            if constexpr (ROUND != RND_NONE) {
-                const int id = wide_gemm<WT>(L, (c.n_fast_layer > 0 ? ctx->xo_xf : ctx->xo_femb) + (size_t)(m0 + (pair ? ctx->xo_pair : 0)) * 8, ctx->fast_out, nullptr,
-                                             ctx->fastV, Df, ctx->fast_norm, WEPI_STORE, ctx->flog + (size_t)m0 * ctx->fastV, ctx->fastV, nullptr, nullptr);
-                if (ctx->trace) tr_rec(L, tr_name("fast.%d.head", cb), L.M, ctx->fastV, TrCls{id}, {TB_FLOG});
-            }
-            enqueue_sample<WT, ROUND>(L, cb, cb == c.num_codebooks - 1);
-            return;
+            a.c = pair ? 0 : cb; a.y_bf = S.xo_y.p; a.y_xo_ldm = ctx->xo_ldm;
+            a.pair_M = pair ? M : 0; a.pair_off = ctx->xo_pair;
+            fast_attn_kernel<WT, ROUND><<<dim3(S.H, rows), 64, 0, L.s>>>(a, nullptr, HD);
+        } else {
+            a.c = cb;
+            if (!L.gemv_only) fast_attn_kernel<WT, ROUND><<<dim3(S.H, rows), 64, 0, L.s>>>(a, S.y.p, ctx->y_ld);
         }
-        GemvP h{};
-        h.W = ctx->fast_out; h.x = xf; h.ldx = Df; h.gain = ctx->fast_norm; h.eps = c.norm_eps;
-        h.out = ctx->flog + (size_t)m0 * ctx->fastV; h.ldo = ctx->fastV; h.N = ctx->fastV; h.K = Df;
-        h.pro = PRO_RMSNORM; h.epi = EPI_STORE;
-        const GemvId hid_ = gemv<WT, ROUND>(L, h, rows_per_wave(h.N, L.M));
-        if (ctx->trace) tr_rec(L, tr_name("fast.%d.head", cb), L.M, h.N, TrCls{hid_.MB, hid_.R, hid_.NT}, {TB_FLOG});
-        enqueue_sample<WT, ROUND>(L, cb, cb == c.num_codebooks - 1);
+        L.chk();
+        if (ctx->trace) tr_rec(L, TrName{S.name, li, "attn"}.str(), rows, HD, TrCls{}, {wide ? S.xo_y.id : S.y.id});
+        return false;
+    };
+    for (int li = 0; li < S.n_layer; ++li) {
+        // layer 0 of steps >= 2: the draw of the previous step left this step's q k v (wide_qkv0_build)
+        const bool tab = wide && li == 0 && cb >= 2 && !pair && ctx->wide_qkv0_tab;
+        enqueue_layer<WT, ROUND>(L, S, li, li == 0 ? xin : S.x.p, li == 0 ? xin_o : S.xo_x.p, tab, attention);
     }
-}
-
-// One full frame: slow pass on the current column, semantic sample, fast codebooks (inference.py:83-155).
-template <typename WT, int ROUND>
-static void enqueue_frame_tail(Launch& L);
-
-template <typename WT, int ROUND>
-static void enqueue_frame_t(Launch& L, const int* toks, long trs, long tms, int col) {
-    if (ROUND == RND_BF16 && eng_slow_ok(L)) enqueue_slow_engine(L, toks, trs, tms, col);
-    else enqueue_slow<WT, ROUND>(L, toks, trs, tms, col, true);
-    enqueue_frame_tail<WT, ROUND>(L);
+    if (cb == 0) return;  // logits of position 0 are discarded (inference.py:122)
+    const TrName head{"fast", cb, "head"};
+    const RowBuf flog{ctx->flog + (size_t)m0 * ctx->fastV, TB_FLOG};
+    if (wide) {
+        if constexpr (ROUND != RND_NONE)
+            wide_linear<WT>(L, head, (S.n_layer > 0 ? ctx->xo_xf : ctx->xo_femb) + (size_t)(m0 + (pair ? ctx->xo_pair : 0)) * 8, ctx->fast_out, nullptr,
+                            ctx->fast_norm, ctx->fastV, S.D, WEPI_STORE, flog, ctx->fastV, XoBuf{}, nullptr);
+    } else {
+        gemv_linear<WT, ROUND>(L, head, ctx->fast_out, nullptr, ctx->fast_norm, S.x.p, S.D, flog, ctx->fastV, nullptr, ctx->fastV, S.D, EPI_STORE, S.nt);
+    }
+    enqueue_sample<WT, ROUND>(L, cb, cb == c.num_codebooks - 1);
 }
 
 // everything after the slow layers: vocabulary head, semantic draw, the fast codebooks
@@ -1566,11 +1558,8 @@ template <typename WT, int ROUND>
 static void enqueue_frame_tail(Launch& L) {
     ft_ctx* ctx = L.ctx;
     const int ncb = ctx->c.num_codebooks;
-    if (L.gemv_only) {  // measurement graph: the HBM-streamed launches only (slow layers above + the head)
-        enqueue_head<WT, ROUND>(L);
-        return;
-    }
     enqueue_head<WT, ROUND>(L);
+    if (L.gemv_only) return;  // measurement graph: the HBM-streamed launches only (slow layers above + the head)
     enqueue_sample<WT, ROUND>(L, 0, ncb == 1);
     if (ROUND == RND_BF16 && eng_fast_ok(L)) { enqueue_fast_engine(L); return; }
     int cb0 = 0;
@@ -1578,20 +1567,43 @@ static void enqueue_frame_tail(Launch& L) {
     for (int cb = cb0; cb < ncb; ++cb) enqueue_fast_step<WT, ROUND>(L, cb);
 }
 
+// One full frame: slow pass on the current column, semantic sample, fast codebooks (inference.py:83-155).
+template <typename WT, int ROUND>
+static void enqueue_frame_t(Launch& L, const int* toks, long trs, long tms, int col) {
+    if (ROUND == RND_BF16 && eng_slow_ok(L)) enqueue_slow_engine(L, toks, trs, tms, col);
+    else enqueue_slow<WT, ROUND>(L, toks, trs, tms, col, true);
+    enqueue_frame_tail<WT, ROUND>(L);
+}
+
 static void enqueue_frame(Launch& L, const int* toks, long trs, long tms, int col) {
-    if (L.ctx->c.dtype == FT_BF16) enqueue_frame_t<bf16_t, RND_BF16>(L, toks, trs, tms, col);
-    else if (L.ctx->c.dtype == FT_F16) enqueue_frame_t<f16_t, RND_F16>(L, toks, trs, tms, col);
-    else enqueue_frame_t<float, RND_NONE>(L, toks, trs, tms, col);
+    by_dtype(L.ctx, [&](auto t) { using T = decltype(t); enqueue_frame_t<typename T::WT, T::ROUND>(L, toks, trs, tms, col); });
 }
 static void enqueue_slow_only(Launch& L, const int* toks, long trs, long tms, int col) {
-    if (L.ctx->c.dtype == FT_BF16) enqueue_slow<bf16_t, RND_BF16>(L, toks, trs, tms, col, false);
-    else if (L.ctx->c.dtype == FT_F16) enqueue_slow<f16_t, RND_F16>(L, toks, trs, tms, col, false);
-    else enqueue_slow<float, RND_NONE>(L, toks, trs, tms, col, false);
+    by_dtype(L.ctx, [&](auto t) { using T = decltype(t); enqueue_slow<typename T::WT, T::ROUND>(L, toks, trs, tms, col, false); });
+}
+// the frame tail after a prompt pass, whose last position left the rows' hidden state in ctx->x
+static void enqueue_tail(Launch& L) {
+    by_dtype(L.ctx, [&](auto t) { using T = decltype(t); enqueue_fproj<typename T::WT, T::ROUND>(L); enqueue_frame_tail<typename T::WT, T::ROUND>(L); });
 }
 
 // ------------------------------------------------------------------------------------------ AR API
 static ft_status eng_recover(ft_ctx* ctx, bool* aborted);
 static bool eng_in_use(const ft_ctx* ctx);
+// Frames that ran on the frame engine must not pass where one of its hand-offs timed out: once the stream has drained,
+// eng_recover tells; then `rewind` puts the slot back where those frames began and `rerun` enqueues them again on the launch
+// path (ctx->eng_suspended).
+template <typename Rewind, typename Rerun>
+static ft_status eng_fallback(ft_ctx* ctx, Rewind&& rewind, Rerun&& rerun) {
+    FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    bool aborted = false;
+    FT_TRY(eng_recover(ctx, &aborted));
+    if (!aborted) return FT_OK;
+    FT_TRY(rewind());
+    ctx->eng_suspended = true;
+    const ft_status st = rerun();
+    ctx->eng_suspended = false;
+    return st;
+}
 static ft_status ar_ready(ft_ctx* ctx) {
     if (!ctx) return FT_ERR_ARG;
     if (!ctx->has_ar) return ft_fail(ctx, FT_ERR_STATE, "context was created without an AR config");
@@ -1854,17 +1866,11 @@ extern "C" ft_status ft_ar_prefill_at(ft_ctx* ctx, int32_t slot, const int32_t* 
         // the first frame's codebook loop (and, position by position, its slow pass) ran on the frame engine: a hand-off
         // time-out there must not pass for a first frame - redo that frame on the launch path (the prompt's K/V and the
         // last position's hidden state are untouched by it)
-        FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        bool aborted = false;
-        FT_TRY(eng_recover(ctx, &aborted));
-        if (aborted) {
-            FT_TRY(ft_ar_reset(ctx, slot));
-            ctx->eng_suspended = true;
-            if (!ctx->prefill_v0) { enqueue_fproj<bf16_t, true>(L); enqueue_frame_tail<bf16_t, true>(L); }
+        FT_TRY(eng_fallback(ctx, [&] { return ft_ar_reset(ctx, slot); }, [&]() -> ft_status {
+            if (!ctx->prefill_v0) enqueue_tail(L);      // (the MFMA prompt pass is bf16 only)
             else enqueue_frame(L, ctx->d_prompt, Lp, 0, Lp - 1);
-            ctx->eng_suspended = false;
-            if (L.err != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("prefill launch: ") + hipGetErrorString(L.err));
-        }
+            return L.err == hipSuccess ? FT_OK : ft_fail(ctx, FT_ERR_HIP, std::string("prefill launch: ") + hipGetErrorString(L.err));
+        }));
     }
     // finalize() advanced pos 0 -> 1; the next input position is pos0 + Lp
     ctx->h_pin[0] = pos0 + Lp;
@@ -1991,25 +1997,13 @@ extern "C" ft_status ft_ar_first_frames(ft_ctx* ctx, int32_t slot0, int32_t n, c
     if (ctx->trace) tr_state(ctx, 0);
     Launch L{ctx, ctx->stream, slot0, n, 0};
     L.tail_only = true;
-    auto tail = [&]() {
-        if (c.dtype == FT_BF16) { enqueue_fproj<bf16_t, RND_BF16>(L); enqueue_frame_tail<bf16_t, RND_BF16>(L); }
-        else if (c.dtype == FT_F16) { enqueue_fproj<f16_t, RND_F16>(L); enqueue_frame_tail<f16_t, RND_F16>(L); }
-        else { enqueue_fproj<float, RND_NONE>(L); enqueue_frame_tail<float, RND_NONE>(L); }
+    auto tail = [&]() -> ft_status {
+        enqueue_tail(L);
+        return L.err == hipSuccess ? FT_OK : ft_fail(ctx, FT_ERR_HIP, std::string("first-frame launch: ") + hipGetErrorString(L.err));
     };
-    tail();
-    if (L.err != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("first-frame launch: ") + hipGetErrorString(L.err));
-    if (on_engine) {      // as in ft_ar_prefill_at: a timed-out codebook loop is redone on the launch path
-        FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        bool aborted = false;
-        FT_TRY(eng_recover(ctx, &aborted));
-        if (aborted) {
-            FT_TRY(ft_ar_reset(ctx, slot0));
-            ctx->eng_suspended = true;
-            tail();
-            ctx->eng_suspended = false;
-            if (L.err != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("first-frame launch: ") + hipGetErrorString(L.err));
-        }
-    }
+    FT_TRY(tail());
+    // as in ft_ar_prefill_at: a timed-out codebook loop is redone on the launch path
+    if (on_engine) FT_TRY(eng_fallback(ctx, [&] { return ft_ar_reset(ctx, slot0); }, tail));
     // finalize() advanced every position 0 -> 1; the next input position of a slot is the end of its prompt
     FT_HIP(ctx, hipMemcpyAsync(ctx->d_pos + slot0, next_pos, n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     FT_HIP(ctx, hipMemcpyAsync(out_frames, ctx->d_tok + (size_t)slot0 * R, (size_t)n * R * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -2200,9 +2194,7 @@ extern "C" ft_status ft_ar_decode(ft_ctx* ctx, int32_t nslots, int32_t n_frames,
         const bool on_engine = nslots == 1 && eng_in_use(ctx);
         FT_TRY(run_burst(burst));
         if (on_engine) {
-            bool aborted = false;
-            FT_TRY(eng_recover(ctx, &aborted));
-            if (aborted) {
+            FT_TRY(eng_fallback(ctx, [&]() -> ft_status {
                 // slot 0 back to where this burst began (its frames [nf0 + done_frames, ..) and cache rows are rewritten by
                 // the redo; the draws are counter-based, so the redo draws what the engine would have drawn), then the same
                 // frames on the launch path
@@ -2219,11 +2211,8 @@ extern "C" ft_status ft_ar_decode(ft_ctx* ctx, int32_t nslots, int32_t n_frames,
                 if (!done0 && hp[1] < ctx->cap)
                     FT_HIP(ctx, hipMemset2DAsync(ctx->d_seq + hp[1], (size_t)ctx->cap * sizeof(int), 0,
                                                  (size_t)std::min(burst, ctx->cap - hp[1]) * sizeof(int), R, ctx->stream));
-                ctx->eng_suspended = true;
-                const ft_status st = run_burst(burst);
-                ctx->eng_suspended = false;
-                FT_TRY(st);
-            }
+                return FT_OK;
+            }, [&] { return run_burst(burst); }));
         }
         done_frames += burst;
         bool all = true;
@@ -2813,13 +2802,13 @@ extern "C" ft_status ft_ar_profile_frame(ft_ctx* ctx, int32_t frames, const ft_s
             Launch L{ctx, ctx->stream, 0, 1, 0};
             FT_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
             if (eng_slow_ok(L)) enqueue_slow_engine(L, ctx->d_tok, 1, R, 0);
-            else enqueue_slow<bf16_t, true>(L, ctx->d_tok, 1, R, 0, true);
+            else enqueue_slow<bf16_t, RND_BF16>(L, ctx->d_tok, 1, R, 0, true);
             FT_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-            enqueue_head<bf16_t, true>(L);
-            enqueue_sample<bf16_t, true>(L, 0, c.num_codebooks == 1);
+            enqueue_head<bf16_t, RND_BF16>(L);
+            enqueue_sample<bf16_t, RND_BF16>(L, 0, c.num_codebooks == 1);
             FT_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
             if (eng_fast_ok(L)) enqueue_fast_engine(L);
-            else for (int cb = 0; cb < c.num_codebooks; ++cb) enqueue_fast_step<bf16_t, true>(L, cb);
+            else for (int cb = 0; cb < c.num_codebooks; ++cb) enqueue_fast_step<bf16_t, RND_BF16>(L, cb);
             FT_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
             FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
             if (L.err != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_ar_profile_frame: launch failed");
@@ -2866,9 +2855,7 @@ extern "C" ft_status ft_test_sample(ft_ctx* ctx, const float* logits, int32_t cb
         ctx->noise = nullptr; ctx->noise_rows = 0;
     }
     Launch L{ctx, ctx->stream, 0, 1, 0};
-    if (c.dtype == FT_BF16) enqueue_sample<bf16_t, RND_BF16>(L, cb, false);
-    else if (c.dtype == FT_F16) enqueue_sample<f16_t, RND_F16>(L, cb, false);
-    else enqueue_sample<float, RND_NONE>(L, cb, false);
+    by_dtype(ctx, [&](auto t) { using T = decltype(t); return enqueue_sample<typename T::WT, T::ROUND>(L, cb, false); });
     hipError_t e = hipStreamSynchronize(ctx->stream);
     ctx->noise = saved; ctx->noise_rows = srows; ctx->noise_row_len = slen;
     if (tmp) hipFree(tmp);
@@ -2972,10 +2959,7 @@ static ft_status test_draw_run(ft_ctx* ctx, ft_test_draw_io* io) {
         ctx->noise = nullptr; ctx->noise_rows = 0;
     }
     Launch L{ctx, st, 0, M, 0};
-    int what;
-    if (c.dtype == FT_BF16) what = enqueue_sample<bf16_t, RND_BF16>(L, cb, io->last != 0);
-    else if (c.dtype == FT_F16) what = enqueue_sample<f16_t, RND_F16>(L, cb, io->last != 0);
-    else what = enqueue_sample<float, RND_NONE>(L, cb, io->last != 0);
+    const int what = by_dtype(ctx, [&](auto t) { using T = decltype(t); return enqueue_sample<typename T::WT, T::ROUND>(L, cb, io->last != 0); });
     hipError_t e = hipStreamSynchronize(st);
     if (L.err != hipSuccess || e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, "ft_test_draw launch failed");
     io->what = what;
@@ -3363,9 +3347,7 @@ extern "C" ft_status ft_test_gemv(ft_ctx* ctx, int32_t pro, int32_t epi, int32_t
     if (ldx < K || ldx % 4 != 0 || ldo < oc || ldo % 4 != 0) return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: bad ldx or ldo");
     if (!x || !W || !out || !id || (pro == PRO_RMSNORM && !gain) || (epi == EPI_RESID && !resid))
         return ft_fail(ctx, FT_ERR_ARG, "ft_test_gemv: missing argument");
-    if (ctx->c.dtype == FT_BF16) return test_gemv_t<bf16_t, RND_BF16>(ctx, pro, epi, M, N, K, x, ldx, W, gain, bias, resid, alias != 0, nt != 0, ldo, out, id);
-    if (ctx->c.dtype == FT_F16) return test_gemv_t<f16_t, RND_F16>(ctx, pro, epi, M, N, K, x, ldx, W, gain, bias, resid, alias != 0, nt != 0, ldo, out, id);
-    return test_gemv_t<float, RND_NONE>(ctx, pro, epi, M, N, K, x, ldx, W, gain, bias, resid, alias != 0, nt != 0, ldo, out, id);
+    return by_dtype(ctx, [&](auto t) { using T = decltype(t); return test_gemv_t<typename T::WT, T::ROUND>(ctx, pro, epi, M, N, K, x, ldx, W, gain, bias, resid, alias != 0, nt != 0, ldo, out, id); });
 }
 
 template <typename WT, int ROUND>
@@ -3442,10 +3424,7 @@ extern "C" ft_status ft_test_decode_attn(ft_ctx* ctx, int32_t M, const float* qk
     const int saved = ctx->nsplit;
     pick_nsplit(ctx, pos_end);       // as ft_ar_decode does for the longest context of its call
     *nsplit = ctx->nsplit;
-    ft_status st;
-    if (ctx->c.dtype == FT_BF16) st = test_decode_attn_t<bf16_t, RND_BF16>(ctx, M, qkv, pos, pos_off, qn, kn, kc, vc, wo, bo, resid, y, part_o, part_ml, x_out);
-    else if (ctx->c.dtype == FT_F16) st = test_decode_attn_t<f16_t, RND_F16>(ctx, M, qkv, pos, pos_off, qn, kn, kc, vc, wo, bo, resid, y, part_o, part_ml, x_out);
-    else st = test_decode_attn_t<float, RND_NONE>(ctx, M, qkv, pos, pos_off, qn, kn, kc, vc, wo, bo, resid, y, part_o, part_ml, x_out);
+    const ft_status st = by_dtype(ctx, [&](auto t) { using T = decltype(t); return test_decode_attn_t<typename T::WT, T::ROUND>(ctx, M, qkv, pos, pos_off, qn, kn, kc, vc, wo, bo, resid, y, part_o, part_ml, x_out); });
     ctx->nsplit = saved;
     return st;
 }
@@ -3493,9 +3472,8 @@ extern "C" ft_status ft_test_embed(ft_ctx* ctx, int32_t M, int32_t D, int32_t nc
         return ft_fail(ctx, FT_ERR_ARG, "ft_test_embed: the octet-major copy is 16-bit, of at most xo_ldm rows");
     if (tok_row_stride < 0 || tok_m_stride < 0 || (int64_t)(M - 1) * tok_m_stride + (int64_t)ncb * tok_row_stride >= n_toks)
         return ft_fail(ctx, FT_ERR_ARG, "ft_test_embed: the token strides reach past toks");
-    if (ctx->c.dtype == FT_BF16) return test_embed_t<bf16_t, RND_BF16>(ctx, M, D, ncb, cbsize, vocab, emb, cb_emb, toks, n_toks, tok_row_stride, tok_m_stride, sem_begin, sem_end, scale, ldx, xo_ldm, x, xo);
-    if (ctx->c.dtype == FT_F16) return test_embed_t<f16_t, RND_F16>(ctx, M, D, ncb, cbsize, vocab, emb, cb_emb, toks, n_toks, tok_row_stride, tok_m_stride, sem_begin, sem_end, scale, ldx, xo_ldm, x, xo);
-    return test_embed_t<float, RND_NONE>(ctx, M, D, ncb, cbsize, vocab, emb, cb_emb, toks, n_toks, tok_row_stride, tok_m_stride, sem_begin, sem_end, scale, ldx, xo_ldm, x, xo);
+    return by_dtype(ctx, [&](auto t) { using T = decltype(t); return test_embed_t<typename T::WT, T::ROUND>(ctx, M, D, ncb, cbsize, vocab, emb, cb_emb, toks, n_toks,
+                                                                      tok_row_stride, tok_m_stride, sem_begin, sem_end, scale, ldx, xo_ldm, x, xo); });
 }
 
 template <typename WT, int ROUND>
@@ -3576,7 +3554,5 @@ extern "C" ft_status ft_test_fast_attn(ft_ctx* ctx, int32_t form, int32_t M, int
             return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: the paired pass does not fit");
     }
     if (form != 2 && (cpos < 0 || cpos >= c.num_codebooks)) return ft_fail(ctx, FT_ERR_ARG, "ft_test_fast_attn: c outside 0..ncb-1");
-    if (c.dtype == FT_BF16) return test_fast_attn_t<bf16_t, RND_BF16>(ctx, form, M, cpos, qkv, qn, kn, kc, vc, y, y_bf);
-    if (c.dtype == FT_F16) return test_fast_attn_t<f16_t, RND_F16>(ctx, form, M, cpos, qkv, qn, kn, kc, vc, y, y_bf);
-    return test_fast_attn_t<float, RND_NONE>(ctx, form, M, cpos, qkv, qn, kn, kc, vc, y, y_bf);
+    return by_dtype(ctx, [&](auto t) { using T = decltype(t); return test_fast_attn_t<typename T::WT, T::ROUND>(ctx, form, M, cpos, qkv, qn, kn, kc, vc, y, y_bf); });
 }

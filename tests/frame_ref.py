@@ -3,10 +3,11 @@ infrastructure, the sibling of tests/ar_ref.py, tests/wide_ref.py and tests/draw
 UNCHANGED - no tolerance is defined here).
 
 The kernels of a frame are each held to float64 through their own hooks, on temporaries, with the batch in rows 0 .. M - 1.
-What no hook sees is the host code of csrc/engine.hip that strings them into a frame (enqueue_slow, enqueue_head,
-enqueue_sample, enqueue_fast_step, enqueue_frame_tail, the tail() of ft_ar_first_frames): which weight, gain and bias a
-launch gets, which buffer it reads and writes, at which row offset m0, with how many rows in the paired codebook pass, and
-whether layer 0's Wqkv launch is skipped because the draw left the table row.
+What no hook sees is the host code of csrc/engine.hip that strings them into a frame (slow_stack and fast_stack, enqueue_layer
+under enqueue_slow and enqueue_fast_step, gemv_linear and wide_linear, enqueue_fproj, enqueue_head, enqueue_sample,
+enqueue_frame_tail, the enqueue_tail of ft_ar_first_frames): which weight, gain and bias a launch gets, which buffer it
+reads and writes, at which row offset m0, with how many rows in the paired codebook pass, and whether layer 0's Wqkv launch
+is skipped because the draw left the table row.
 
 `plan` restates that host code from DESIGN.md and the comments of engine.hip - from the shape, the type, max_batch, (m0, M), the
 switches and the kind of call - as the ordered list of launches, each with its name, its rows and columns, the class its

@@ -130,7 +130,7 @@ class Ctx:
         return trace, rep, out, c1
 
 
-N_SETTLED = 22                                                 # traced calls the module's cases judge
+N_SETTLED = 24                                                 # traced calls the module's cases judge
 
 
 def settle(what, rep):
@@ -282,6 +282,21 @@ def test_gemv_bf16_rows(which, max_batch, M, env):
     if which == "medium":
         assert trace["launches"][2]["name"] == "slow.0.attn" and trace["launches"][2]["cls"][0] == 32       # one kv head per XCD: 32 splits, merged in the Wo launch
         assert trace["launches"][3]["cls"][0] == FR.COMBINE
+
+
+def test_gemv_fp16_rows():
+    """fp16 at the medium shape, max_batch 4: a 3-row frame - the smallest batch of the 4-rows-per-pass GEMV class, the one
+    (16-bit type x width) cell the cases above leave out - then first frames at slot0 = 1, n = 3."""
+    cx, trace, rep = decode_case(mfma_shape(), "fp16", 4, 3)
+    try:
+        assert "xo_rows" not in [r["name"] for r in trace["launches"]] and all(FR.TB_XO_X not in r["bufs"] for r in trace["launches"])
+        assert any(r["cls"][0] == 4 for r in trace["launches"] if r["name"].endswith(("wqkv", "wo", "w2")))    # gemv_mb_kernel, four rows per pass
+        assert "draw.0" in [r["name"] for r in trace["launches"]]        # fp16: the large draw is one launch
+        trace, rep, _, _ = cx.traced_first(1, 3, seed=5)
+        assert all(r["m0"] == 1 and r["rows"] == 3 for r in trace["launches"])
+        settle("fp16 medium max_batch 4 first frames of slots 1..3", rep)
+    finally:
+        cx.close()
 
 
 def test_arming_rules():
