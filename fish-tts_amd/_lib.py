@@ -191,6 +191,7 @@ SYMBOLS = {
     "ft_test_engine_fault": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "ft_test_ar_attn_plan": (C.c_int32, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ft_test_engine_handoffs": (C.c_int32, [_P, C.POINTER(ft_test_engine_io)]),
+    "ft_test_ar_slots": (C.c_int32, [_P] * 11),
     "ft_test_sample": (C.c_int32, [_P, _P, C.c_int32, C.POINTER(ft_sampling), _P, _P, _P]),
     "ft_test_draw": (C.c_int32, [_P, C.POINTER(ft_test_draw_io)]),
     "ft_test_qkv0_tab": (C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),

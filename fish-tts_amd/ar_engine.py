@@ -656,6 +656,26 @@ class ARHipEngine:
                 out[(kind, li)] = (np.stack([x["kv_k"] for x in d]), np.stack([x["kv_v"] for x in d]))
         return out
 
+    def test_slots(self, kv: bool = True) -> dict:
+        """Test hook (ft_test_ar_slots): the per-slot state of every slot as a dict: geo (the hook's ten geometry words by
+        name), tok, tokn (MB, R), pos, nf, done (MB,), seq (MB, R, cap) int32, ctl (MB, ctl_words) uint32, hid_in_xo (MB,)
+        uint8 and, with `kv`, kv (n_layer, 2, MB, Hkv, n_slots, head_dim x esz) uint8: the slow caches' bytes."""
+        g = np.zeros(10, dtype=np.int32)
+        self._check(self.lib.ft_test_ar_slots(self._h, g.ctypes.data_as(C.c_void_p), *([None] * 9)), "ft_test_ar_slots")
+        names = ("max_batch", "R", "cap", "ctl_words", "n_layer", "Hkv", "n_slots", "head_dim", "esz", "im_end_id")
+        geo = {k: int(v) for k, v in zip(names, g)}
+        MB, R, cap = geo["max_batch"], geo["R"], geo["cap"]
+        out = dict(tok=np.zeros((MB, R), dtype=np.int32), tokn=np.zeros((MB, R), dtype=np.int32), pos=np.zeros(MB, dtype=np.int32),
+                   nf=np.zeros(MB, dtype=np.int32), done=np.zeros(MB, dtype=np.int32), seq=np.zeros((MB, R, cap), dtype=np.int32),
+                   ctl=np.zeros((MB, geo["ctl_words"]), dtype=np.uint32), hid_in_xo=np.zeros(MB, dtype=np.uint8))
+        if kv:
+            out["kv"] = np.zeros((geo["n_layer"], 2, MB, geo["Hkv"], geo["n_slots"], geo["head_dim"] * geo["esz"]), dtype=np.uint8)
+        ptr = lambda k: out[k].ctypes.data_as(C.c_void_p) if k in out else None
+        self._check(self.lib.ft_test_ar_slots(self._h, None, *(ptr(k) for k in ("tok", "tokn", "pos", "nf", "done", "seq", "ctl",
+                                                                               "hid_in_xo", "kv"))), "ft_test_ar_slots")
+        out["geo"] = geo
+        return out
+
     def first_frames(self, slot0: int, samplings: Sequence[L.ft_sampling], next_pos) -> np.ndarray:
         """ft_ar_first_frames alone: the first frames of slots [slot0, slot0 + n) whose prompts went through the slow stack."""
         n = len(samplings)

@@ -2337,6 +2337,39 @@ extern "C" ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t*
     return FT_OK;
 }
 
+// Test hook: the per-slot state of every slot, whole (include/fishtts_hip_test.h).  Host code: the stream is drained, then
+// one copy per array (and per layer's K and V cache) to the host.
+extern "C" ft_status ft_test_ar_slots(ft_ctx* ctx, int32_t* geo, int32_t* tok, int32_t* tokn, int32_t* pos, int32_t* nf, int32_t* done,
+                                      int32_t* seq, uint32_t* ctl, uint8_t* hid_in_xo, void* kv) {
+    FT_TRY(ar_ready(ctx));
+    const ft_ar_config& c = ctx->c;
+    const size_t MB = c.max_batch, R = c.num_codebooks + 1, W = sizeof(RowCtl) / sizeof(uint32_t);
+    static_assert(sizeof(RowCtl) % sizeof(uint32_t) == 0, "the sampling rows are read as whole words");
+    FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (geo) {
+        const int32_t g[10] = {c.max_batch, (int32_t)R, ctx->cap, (int32_t)W, c.n_layer, c.n_local_heads, ctx->n_slots, c.head_dim,
+                               (int32_t)ctx->esz, c.im_end_id};
+        memcpy(geo, g, sizeof g);
+    }
+    auto out = [&](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+    FT_HIP(ctx, out(tok, ctx->d_tok, MB * R * 4));
+    FT_HIP(ctx, out(tokn, ctx->d_tokn, MB * R * 4));
+    FT_HIP(ctx, out(pos, ctx->d_pos, MB * 4));
+    FT_HIP(ctx, out(nf, ctx->d_nf, MB * 4));
+    FT_HIP(ctx, out(done, ctx->d_done, MB * 4));
+    FT_HIP(ctx, out(seq, ctx->d_seq, MB * R * ctx->cap * 4));
+    FT_HIP(ctx, out(ctl, ctx->d_ctl, MB * sizeof(RowCtl)));
+    if (hid_in_xo) for (size_t m = 0; m < MB; ++m) hid_in_xo[m] = ctx->hid_in_xo[m] ? 1 : 0;
+    if (kv) {
+        const size_t bytes = MB * ctx->cache_m_stride * ctx->esz;            // one layer's K or V cache, every slot
+        for (int li = 0; li < c.n_layer; ++li) {
+            FT_HIP(ctx, hipMemcpy((char*)kv + ((size_t)li * 2) * bytes, ctx->layers[li].kc, bytes, hipMemcpyDeviceToHost));
+            FT_HIP(ctx, hipMemcpy((char*)kv + ((size_t)li * 2 + 1) * bytes, ctx->layers[li].vc, bytes, hipMemcpyDeviceToHost));
+        }
+    }
+    return FT_OK;
+}
+
 // Test hook: the hand-off vectors the engine's launches left behind, and K/V rows (include/fishtts_hip_test.h).  Host code:
 // one copy of each pool to the host, then the decoding below with the layout rules of frame_engine.h.
 namespace {
@@ -2611,7 +2644,9 @@ static __global__ __launch_bounds__(256) void slot_move_kernel(SlotMoveP p) {
 // Between ft_ar_decode calls (and after a fill) only: the recovery of a frame-engine time-out needs nothing more here - it
 // takes slot 0's position, frame count and done flag from the device at the start of every ft_ar_decode call (pos0, nf0,
 // done0) and ft_ar_prefill_at / ft_ar_first_frames reset the slot they serve, so a moved utterance is rewound from its new
-// slot like any other.  The host keeps no other per-slot state.
+// slot like any other.  The host keeps one more piece of per-slot state, hid_in_xo (which buffer ft_ar_get_debug(hidden) reads
+// the slot's residual stream from), and the move does not carry it - nor the hidden and logits rows themselves: those of `to`
+// are defined again after its next frame, which sets the flag (include/fishtts_hip.h; tests/test_slot_state_gpu.py).
 extern "C" ft_status ft_ar_slot_move(ft_ctx* ctx, int32_t from, int32_t to) {
     FT_TRY(ar_ready(ctx));
     const ft_ar_config& c = ctx->c;

@@ -122,7 +122,10 @@ ft_status ft_ar_park(ft_ctx* ctx, int32_t slot);
  * rows [0, pos) of every layer, the slot's row of the frame store (the repetition-penalty window reads it), position,
  * input column, frame count, done flag and sampling row; `from` is left parked (as ft_ar_park leaves it), `to`'s former
  * content is overwritten.  One launch, stream-ordered after every earlier call.  Refused before any device work, both
- * slots unchanged: FT_ERR_ARG (a slot out of range, from == to), FT_ERR_STATE (a context without the AR model). */
+ * slots unchanged: FT_ERR_ARG (a slot out of range, from == to), FT_ERR_STATE (a context without the AR model).
+ * Not carried: the residual stream of the slot's last frame.  ft_ar_get_debug(hidden) of `to` is defined only after its
+ * next frame (the logits row is not carried either); K/V rows >= pos of `to`, every other slot and the K/V, column under
+ * construction and sampling row of `from` stay as they are. */
 ft_status ft_ar_slot_move(ft_ctx* ctx, int32_t from, int32_t to);
 /* Reference-prefix KV reuse (the reference keeps the reference tensors in
  * `_prefill_cache` but re-prefills them on every call: synthesizer.py:363-429, inference.py:779-793,

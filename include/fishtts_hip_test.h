@@ -11,7 +11,9 @@ extern "C" {
 /* Test hooks: inject the Exp(1) noise the sampler divides by (inference.py:26), one row of
  * `row_len` floats per generated frame (slow vocab draws first, then (num_codebooks-1) x 1024);
  * q == NULL restores the RNG.  Read back the last slow logits / pre-norm hidden of a slot (after a frame on the lock-step
- * MFMA launches the hidden state is gathered from the octet-major residual stream, where those launches keep it). */
+ * MFMA launches the hidden state is gathered from the octet-major residual stream, where those launches keep it).  Both
+ * rows belong to the slot index, not to the utterance: ft_ar_slot_move carries neither them nor the host's note of where
+ * the hidden row lies, so after a move they are defined for `to` only once its next frame has run. */
 ft_status ft_ar_set_noise(ft_ctx* ctx, const float* q, int64_t n_rows, int64_t row_len);
 ft_status ft_ar_get_debug(ft_ctx* ctx, int32_t slot, float* logits /*vocab*/, float* hidden /*fast_dim*/);
 
@@ -44,6 +46,25 @@ ft_status ft_test_engine_fault(ft_ctx* ctx, int32_t which, int32_t wg, int32_t s
  * frame engine alike); *xl: 1 if the slow-stack frame engine is on and is the XCD-local kernel (one kv head per XCD), else 0;
  * *n_slots: the rows of the KV cache (max_seq_len rounded up to 8).  Any pointer may be NULL. */
 ft_status ft_test_ar_attn_plan(ft_ctx* ctx, int32_t* nsplit, int32_t* xl, int32_t* n_slots);
+
+/* Test hook (host code only: it synchronises the context's stream and copies device memory out; no kernel, no branch in a
+ * kernel, nothing on the frame path): everything an utterance owns between two launches, for ALL max_batch slots, so that
+ * the calls which carry that state - ft_ar_slot_move, ft_ar_park, ft_ar_reset, ft_ar_kv_save / ft_ar_kv_restore and the
+ * ft_ar_prefill_at behind a restore - can be held to "a defined set of bytes is equal, every other byte is untouched".
+ * Any pointer may be NULL.
+ *   geo [10]: max_batch, R = num_codebooks + 1, cap (columns of a frame-store row), ctl_words (32-bit words of one sampling
+ *             row), n_layer, Hkv, n_slots (rows of a kv head's cache), head_dim, esz (bytes of a cache element), im_end_id
+ *   tok, tokn [max_batch][R]: the input column and the column under construction
+ *   pos, nf, done [max_batch]
+ *   seq [max_batch][R][cap]: the frame store
+ *   ctl [max_batch][ctl_words]: the sampling rows (RowCtl) as raw words
+ *   hid_in_xo [max_batch] bytes: the host's note of where ft_ar_get_debug(hidden) finds a slot's residual stream (1: the
+ *             octet-major buffer of the MFMA launches).  This is the one piece of per-slot state that lives on the host.
+ *   kv: the slow stack's caches, whole, [n_layer][K | V][max_batch][Hkv][n_slots][head_dim] in the cache's element type
+ *             (ft_test_engine_handoffs reads one (layer, slot) per call; a byte check of every slot before and after every
+ *             call wants them all at once). */
+ft_status ft_test_ar_slots(ft_ctx* ctx, int32_t* geo, int32_t* tok, int32_t* tokn, int32_t* pos, int32_t* nf, int32_t* done,
+                           int32_t* seq, uint32_t* ctl, uint8_t* hid_in_xo, void* kv);
 
 /* Test hook (host code only: it synchronises the context's stream and copies device memory out; no kernel, no branch in a
  * kernel, nothing on the frame path): the hand-off vectors the frame engine's launches LEFT in device memory, decoded through

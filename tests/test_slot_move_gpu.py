@@ -21,10 +21,12 @@ def _engine(shape, precision, max_batch, max_new_tokens):
     return eng
 
 
-def _moved_equals_unmoved(eng, shape, n_before=3, n_after=9, width_after=None, lp=14):
+def _moved_equals_unmoved(eng, shape, n_before=3, n_after=9, width_after=None, lp=14, bytes_too=False):
     """Utterance A (an lp-column prompt; sampled, repetition_penalty 1.1, ban_eos: fixed length) runs n_before frames in
     slot 3 of a 4-wide batch while slot 0 holds what another utterance left there, moves to slot 0 and finishes: every
-    column equals A's unmoved single run with the same seed."""
+    column equals A's unmoved single run with the same seed.  bytes_too: the move itself is first held to tests/slot_ref.py
+    byte by byte - the lp + n_before moved K/V rows of every layer and head, the rows behind them, every other slot, the state
+    arrays."""
     pa, pb = make_prompt(shape, lp, seed=5, n_vq=2).numpy(), make_prompt(shape, 9, seed=6, n_vq=1).numpy()
     kw = dict(temperature=0.7, top_p=0.8, repetition_penalty=1.1)
     spa = eng._sampling(seed=11, ban_eos=True, **kw)
@@ -38,7 +40,15 @@ def _moved_equals_unmoved(eng, shape, n_before=3, n_after=9, width_after=None, l
     first = eng.prefill_many([pa], [spa], [3])[0]
     frames, n = eng.decode(n_before, [spb, idle, idle, spa], poll=n_before)
     assert n[3] == n_before and n[1] == n[2] == 0
+    if bytes_too:
+        from tests import slot_ref as S
+        before = S.State.from_hook(eng.test_slots())
+        assert S.moved_positions(before, 3) == lp + n_before
     eng.move_slot(3, 0)
+    if bytes_too:
+        after, model = S.State.from_hook(eng.test_slots()), S.move(before, 3, 0)
+        assert S.diff(after, model) is None, S.describe(S.diff(after, model), after, model)
+        assert np.array_equal(after.kv[:, :, 0, :, :lp + n_before], before.kv[:, :, 3, :, :lp + n_before])
     w = width_after or 4
     sps = [spa] + [idle] * (w - 1)
     after, m = eng.decode(n_after, sps, poll=4)
@@ -87,13 +97,14 @@ def test_refused_without_the_ar_model():
 
 def test_moved_slot_at_s1_widths_runs_on_the_frame_engine():
     """medium_shape (s1-mini widths): the frames after the move run at width 1 on the persistent frame engine.  The slot
-    holds 150 + 3 positions when it moves: the K/V copy spans three chunks of 64 positions (head_dim 128, bf16)."""
+    holds 150 + 3 positions when it moves: the K/V copy spans three chunks of 64 positions (head_dim 128, bf16); its 153 rows
+    and everything the move must leave alone are checked byte by byte in front of the decode."""
     from tests.test_ar_gpu import medium_shape
     shape = medium_shape()
     eng = _engine(shape, "bf16", max_batch=4, max_new_tokens=32)
     try:
         assert eng.engine_state()[0] == 3, eng.frame_path()
-        _moved_equals_unmoved(eng, shape, n_before=3, n_after=9, width_after=1, lp=150)
+        _moved_equals_unmoved(eng, shape, n_before=3, n_after=9, width_after=1, lp=150, bytes_too=True)
         flags, aborted, _ = eng.engine_state()
         assert flags == 3 and aborted == 0
     finally:
