@@ -597,14 +597,16 @@ class ARHipEngine:
 
     # ------------------------------------------------------------------ launch trace of a frame (test hook)
     def trace_arm(self, first: int = 0, count: int = 1 << 30) -> None:
-        """Test hook (ft_test_ar_trace_arm): the next decode(1, ...) or first-frames call records one entry per launch; the
-        entries [first, first + count) keep host copies of every buffer they wrote."""
+        """Test hook (ft_test_ar_trace_arm): the next decode(1, ...), first-frames or prompt call (prefill, prefill_slow,
+        prefill_slow_many) records one entry per launch; the entries [first, first + count) keep host copies of every buffer
+        they wrote."""
         self._check(self.lib.ft_test_ar_trace_arm(self._h, first, count), "ft_test_ar_trace_arm")
 
     def trace_read(self):
-        """Test hook: the last traced call as a dict: kind (1 a decode frame, 2 first frames), m0, M, launches - a list of dicts
-        name, m0, rows, cols, cls (4 ints), held, bufs {buffer id: array} (f32 / int32 (rows, cols); the octet-major 16-bit
-        buffers as uint16 (width / 8, xo_ldm, 8)) - and state: [before, after], each a dict tok (MB, R), pos, nf, done (MB,),
+        """Test hook: the last traced call as a dict: kind (1 a decode frame, 2 first frames, 3 prefill, 4 prefill_slow, 5
+        prefill_slow_many), m0, M, launches - a list of dicts name, m0, rows, cols, cls (4 ints), pos_off, held, bufs {buffer id:
+        array} (f32 / int32 (rows, cols); the octet-major 16-bit buffers as uint16 (width / 8, xo_ldm, 8); the prompt workspace's
+        16-bit rows, ids 25 .. 28, as uint16 (max_seq_len, width)) - and state: [before, after], each a dict tok (MB, R), pos, nf, done (MB,),
         seq (MB, R, cap); begin: {buffer id: array}, every traceable buffer as the call found it.  The copies are handed over:
         a second read finds none."""
         info = np.zeros(5, dtype=np.int32)
@@ -613,15 +615,15 @@ class ARHipEngine:
             raise HipError("the launch trace failed to copy a buffer")
         MB, R, cap = self.max_batch, self.R, self.max_new_tokens + 24
         launches = []
-        name, li, bi = C.create_string_buffer(64), np.zeros(9, dtype=np.int32), np.zeros(4, dtype=np.int32)
+        name, li, bi = C.create_string_buffer(64), np.zeros(10, dtype=np.int32), np.zeros(4, dtype=np.int32)
         for i in range(-1, n):
             if i < 0:                                   # the record before the first launch: every buffer as the call found it
-                rec = dict(name="begin", m0=0, rows=0, cols=0, held=True, cls=(-1,) * 4, bufs={})
+                rec = dict(name="begin", m0=0, rows=0, cols=0, held=True, cls=(-1,) * 4, pos_off=0, bufs={})
                 li[3] = info[4]
             else:
                 self._check(self.lib.ft_test_ar_trace_launch(self._h, i, name, 64, li.ctypes.data_as(C.c_void_p)), "ft_test_ar_trace_launch")
                 rec = dict(name=name.value.decode(), m0=int(li[0]), rows=int(li[1]), cols=int(li[2]), held=bool(li[4]),
-                           cls=tuple(int(v) for v in li[5:9]), bufs={})
+                           cls=tuple(int(v) for v in li[5:9]), pos_off=int(li[9]), bufs={})
             for j in range(int(li[3])):
                 self._check(self.lib.ft_test_ar_trace_buffer(self._h, i, j, bi.ctypes.data_as(C.c_void_p), None), "ft_test_ar_trace_buffer")
                 bid, esz, rows, cols = (int(v) for v in bi)
@@ -631,7 +633,7 @@ class ARHipEngine:
                 a = np.zeros((rows, cols), dtype=np.uint16 if esz == 2 else np.int32 if bid >= 30 else np.float32)
                 self._check(self.lib.ft_test_ar_trace_buffer(self._h, i, j, bi.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p)),
                             "ft_test_ar_trace_buffer")
-                rec["bufs"][bid] = a.reshape(rows, cols // 8, 8) if esz == 2 else a
+                rec["bufs"][bid] = a.reshape(rows, cols // 8, 8) if esz == 2 and not 25 <= bid <= 28 else a
             if i < 0:
                 begin = rec["bufs"]
                 continue
@@ -686,14 +688,22 @@ class ARHipEngine:
                     "ft_ar_first_frames")
         return out
 
-    def prefill_slow_many(self, prompts: Sequence[np.ndarray], slots: Sequence[int]) -> np.ndarray:
-        """ft_ar_prefill_slow_many alone: the prompt passes of `slots`, no first frames.  Returns each slot's next position."""
+    def prefill_slow_many(self, prompts: Sequence[np.ndarray], slots: Sequence[int], pos0s=None) -> np.ndarray:
+        """ft_ar_prefill_slow_many alone: the prompt passes of `slots` (pos0s: behind restored prefixes), no first frames.
+        Returns each slot's next position."""
         tails = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in prompts]
         lps = np.asarray([np.asarray(p).shape[1] for p in prompts], dtype=np.int32)
-        packed, sl, z = np.ascontiguousarray(np.concatenate(tails)), np.asarray(slots, dtype=np.int32), np.zeros(len(prompts), dtype=np.int32)
+        packed, sl = np.ascontiguousarray(np.concatenate(tails)), np.asarray(slots, dtype=np.int32)
+        z = np.zeros(len(prompts), dtype=np.int32) if pos0s is None else np.ascontiguousarray(pos0s, dtype=np.int32)
         self._check(self.lib.ft_ar_prefill_slow_many(self._h, len(prompts), sl.ctypes.data_as(C.c_void_p), packed.ctypes.data_as(C.c_void_p),
                                                      lps.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p)), "ft_ar_prefill")
-        return lps.copy()
+        return (lps + z).astype(np.int32)
+
+    def prefill_slow(self, prompt: np.ndarray, slot: int = 0, pos0: int = 0) -> None:
+        """ft_ar_prefill_slow alone: one prompt pass, no first frame."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32)
+        assert prompt.ndim == 2 and prompt.shape[0] == self.R, prompt.shape
+        self._check(self.lib.ft_ar_prefill_slow(self._h, slot, prompt.ctypes.data_as(C.c_void_p), prompt.shape[1], pos0), "ft_ar_prefill_slow")
 
     def engine_state(self):
         """(flags, time-outs recovered so far, phase of the last one) of the persistent frame engine: flags bit 0 = slow

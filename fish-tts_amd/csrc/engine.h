@@ -41,13 +41,16 @@ struct ArTraceBuf { int id = 0, esz = 4, rows = 0, cols = 0; std::vector<char> d
 struct ArTraceRec {
     std::string name;
     int m0 = 0, rows = 0, cols = 0, cls[4] = {-1, -1, -1, -1};
+    int pos_off = 0;                                     // Launch::pos_off of the launch (position-by-position prompts)
     bool held = false;
     std::vector<ArTraceBuf> bufs;
 };
 struct ArTraceState { std::vector<int> tok, pos, nf, done, seq; };
 struct ArTrace {
     bool armed = false, failed = false;
-    int first = 0, count = 0, kind = 0, m0 = 0, M = 0;   // kind: 1 a decode frame, 2 first frames
+    int first = 0, count = 0, kind = 0, m0 = 0, M = 0;   // kind: 1 a decode frame, 2 first frames, 3 / 4 / 5 the prompt calls
+    std::string pass_prefix, pos_prefix;                 // "pass<k>." of a call of several passes, "t<k>." of a position
+    std::vector<int> uploaded;                           // buffers the host uploaded since the last record
     std::vector<ArTraceRec> recs;
     ArTraceState st[2];                                  // before the first launch, after the call
     std::vector<ArTraceBuf> begin;                       // every traceable buffer before the first launch

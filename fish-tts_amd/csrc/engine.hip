@@ -754,8 +754,11 @@ static auto by_dtype(const ft_ctx* ctx, F&& f) {
 // the rows outside [m0, m0 + M) are there for the reader to compare with the record before), at that point of the stream.
 // The copies read only: a traced call computes what an untraced one does.  Buffer ids (AR_TB_*): fishtts_hip_test.h.
 enum { TB_X = 0, TB_QKV, TB_Y, TB_G, TB_LOGITS, TB_HID, TB_FEMB, TB_XF, TB_QKVF, TB_GF, TB_FLOG, TB_PART_O, TB_PART_ML,
+       TB_PF_X = 13, TB_PF_QKV, TB_PF_Y,                         // the prompt pass's workspace: f32 rows [max_seq_len][width] ...
        TB_XO_X = 20, TB_XO_XF, TB_XO_FEMB, TB_XO_Y, TB_XO_G,
-       TB_TOKN = 30, TB_TOK, TB_POS, TB_NF, TB_DONE, TB_SEQ, TB_CUT, TB_CHUNK_CNT, TB_PART_IDX };
+       TB_PF_XN = 25, TB_PF_YBF, TB_PF_QBF, TB_PF_G,             // ... and 16-bit rows [max_seq_len][width] (row-major, not octet-major)
+       TB_TOKN = 30, TB_TOK, TB_POS, TB_NF, TB_DONE, TB_SEQ, TB_CUT, TB_CHUNK_CNT, TB_PART_IDX,
+       TB_PROMPT = 39, TB_PF_SEQS, TB_PF_ROWS };                 // d_prompt [1][R max_seq_len], pf_seqs [max_batch][4], pf_rows [max_seq_len][2]
 static const void* tr_buf(const ft_ctx* ctx, int id, int* esz, int* rows, int* cols) {
     const ft_ar_config& c = ctx->c;
     const int MB = c.max_batch, R = c.num_codebooks + 1, ldm = ctx->xo_ldm;
@@ -792,6 +795,16 @@ static const void* tr_buf(const ft_ctx* ctx, int id, int* esz, int* rows, int* c
         case TB_CUT: return f(ctx->samp_cut, MB, (int)(sizeof(SampCut) / 4));
         case TB_CHUNK_CNT: return f(ctx->samp_chunk_cnt, 1, MB * nchunk);
         case TB_PART_IDX: return f(ctx->samp_part_idx, 1, MB * nchunk);
+        case TB_PF_X: return f(ctx->pf_x, c.max_seq_len, c.dim);
+        case TB_PF_QKV: return f(ctx->pf_qkv, c.max_seq_len, qkvN);
+        case TB_PF_Y: return f(ctx->pf_y, c.max_seq_len, HD);
+        case TB_PF_XN: *esz = 2; return f(ctx->pf_xn, c.max_seq_len, c.dim);
+        case TB_PF_YBF: *esz = 2; return f(ctx->pf_ybf, c.max_seq_len, HD);
+        case TB_PF_QBF: *esz = 2; return f(ctx->pf_qbf, c.max_seq_len, HD);
+        case TB_PF_G: *esz = 2; return f(ctx->pf_g, c.max_seq_len, c.intermediate_size);
+        case TB_PROMPT: return f(ctx->d_prompt, 1, R * c.max_seq_len);
+        case TB_PF_SEQS: return f(ctx->pf_seqs, MB, 4);
+        case TB_PF_ROWS: return f(ctx->pf_rows, c.max_seq_len, 2);
     }
     return nullptr;
 }
@@ -802,10 +815,15 @@ static void tr_rec(Launch& L, const std::string& name, int rows, int cols, TrCls
     const int idx = (int)t.recs.size();
     t.recs.emplace_back();
     ArTraceRec& r = t.recs.back();
-    r.name = name; r.m0 = L.m0; r.rows = rows; r.cols = cols;
+    // a prompt call: the pass in front of every name, the position in front of the position-by-position slow stack's
+    r.name = t.pass_prefix + (name == "embed" || name.compare(0, 5, "slow.") == 0 ? t.pos_prefix : std::string()) + name;
+    r.m0 = L.m0; r.rows = rows; r.cols = cols; r.pos_off = L.pos_off;
     r.cls[0] = cls.a; r.cls[1] = cls.b; r.cls[2] = cls.c; r.cls[3] = cls.d;
     r.held = idx >= t.first && idx < t.first + t.count;
-    for (int id : bufs) {
+    std::vector<int> ids(bufs);
+    ids.insert(ids.end(), t.uploaded.begin(), t.uploaded.end());   // what the host uploaded for this pass rides with its first launch
+    t.uploaded.clear();
+    for (int id : ids) {
         ArTraceBuf b;
         const void* p = tr_buf(ctx, id, &b.esz, &b.rows, &b.cols);
         if (!p) continue;
@@ -851,8 +869,11 @@ static void tr_state(ft_ctx* ctx, int which) {
         static const int ids[] = {TB_X, TB_QKV, TB_Y, TB_G, TB_LOGITS, TB_HID, TB_FEMB, TB_XF, TB_QKVF, TB_GF, TB_FLOG, TB_PART_O, TB_PART_ML,
                                   TB_XO_X, TB_XO_XF, TB_XO_FEMB, TB_XO_Y, TB_XO_G, TB_TOKN, TB_TOK, TB_POS, TB_NF, TB_DONE, TB_SEQ, TB_CUT,
                                   TB_CHUNK_CNT, TB_PART_IDX};
+        static const int pf_ids[] = {TB_PF_X, TB_PF_QKV, TB_PF_Y, TB_PF_XN, TB_PF_YBF, TB_PF_QBF, TB_PF_G, TB_PROMPT, TB_PF_SEQS, TB_PF_ROWS};
+        std::vector<int> all(std::begin(ids), std::end(ids));
+        if (t.kind >= 3) all.insert(all.end(), std::begin(pf_ids), std::end(pf_ids));     // a prompt call: its workspace too
         t.begin.clear();
-        for (int id : ids) {
+        for (int id : all) {
             ArTraceBuf b;
             const void* p = tr_buf(ctx, id, &b.esz, &b.rows, &b.cols);
             if (!p) continue;
@@ -864,19 +885,27 @@ static void tr_state(ft_ctx* ctx, int which) {
     }
     if (!ok) t.failed = true;
 }
-struct ArTraceScope {   // a traced call: armed -> active for this call only (kind: 1 a decode frame, 2 first frames)
+// A traced call: armed -> active for this call only (kind: 1 a decode frame, 2 first frames, 3 ft_ar_prefill_at, 4
+// ft_ar_prefill_slow, 5 ft_ar_prefill_slow_many).  A call made inside a traced one (the single passes ft_ar_prefill_slow_many falls
+// back to) finds the trace active and leaves it alone: `own` is false there, and so is it in an untraced call.
+struct ArTraceScope {
     ft_ctx* ctx;
+    bool own = false;
     ArTraceScope(ft_ctx* c, bool eligible, int kind, int m0, int M) : ctx(c) {
         ArTrace& t = ctx->tstore;
-        if (!t.armed) return;
+        if (ctx->trace || !t.armed) return;
         t.armed = false;
         if (!eligible) return;
-        t.recs.clear();
+        t.recs.clear(); t.uploaded.clear(); t.pass_prefix.clear(); t.pos_prefix.clear();
         t.failed = false; t.kind = kind; t.m0 = m0; t.M = M;
         ctx->trace = &t;
+        own = true;
     }
-    ~ArTraceScope() { ctx->trace = nullptr; }
+    ~ArTraceScope() { if (own) ctx->trace = nullptr; }
 };
+// the host uploaded these buffers for the pass about to start: the pass's first launch record carries them
+static void tr_uploaded(ft_ctx* ctx, std::initializer_list<int> ids) { if (ctx->trace) ctx->trace->uploaded.assign(ids); }
+static void tr_pos(ft_ctx* ctx, int t) { if (ctx->trace) ctx->trace->pos_prefix = tr_name("t%d.", t); }
 
 struct PfX {   // fused RMSNorm hooks of the skinny kernel (codec_kernels.h TapGemmP)
     const void* gain = nullptr;   // normalise the X rows with this gain ...
@@ -1738,7 +1767,8 @@ struct PfAttnIO {
     const int4* seqs;          // ragged pass: device copies of {first row, rows, first cache position, slot} per sequence ...
     const int2* rows;          // ... and of (slot, cache position) per row
 };
-static int pf_attn(Launch& L, const PfAttnIO& io, int slot, int Lp, int pos0, const RaggedPf* rg) {
+// li: the layer, for the launch trace's names (pf.<li>.append, pf.<li>.attn; class {1 tiled | 0} and {the path})
+static int pf_attn(Launch& L, const PfAttnIO& io, int slot, int Lp, int pos0, const RaggedPf* rg, int li = -1) {
     ft_ctx* ctx = L.ctx;
     const ft_ar_config& c = ctx->c;
     const int HD = c.n_head * c.head_dim, qkvN = (c.n_head + 2 * c.n_local_heads) * c.head_dim;
@@ -1767,6 +1797,7 @@ static int pf_attn(Launch& L, const PfAttnIO& io, int slot, int Lp, int pos0, co
             if (c.head_dim == 128) prefill_rope_append_kernel<128><<<Lp, 256, 0, L.s>>>(a);
             else prefill_rope_append_kernel<64><<<Lp, 256, 0, L.s>>>(a);
             L.chk();
+            if (ctx->trace) tr_rec(L, tr_name("pf.%d.append", li), Lp, HD, TrCls{1}, {TB_PF_QBF});
             continue;
         }
         if (pass == 1 && flash) {
@@ -1781,6 +1812,7 @@ static int pf_attn(Launch& L, const PfAttnIO& io, int slot, int Lp, int pos0, co
             if (c.head_dim == 128) { if (ng4) flash_launch<128, 4>(fp, lp_grid, L.s, nz); else flash_launch<128, 2>(fp, lp_grid, L.s, nz); }
             else { if (ng4) flash_launch<64, 4>(fp, lp_grid, L.s, nz); else flash_launch<64, 2>(fp, lp_grid, L.s, nz); }
             L.chk();
+            if (ctx->trace) tr_rec(L, tr_name("pf.%d.attn", li), Lp, HD, TrCls{path}, {TB_PF_YBF});
             continue;
         }
         const dim3 grid(c.n_local_heads, 1, Lp);
@@ -1793,6 +1825,10 @@ static int pf_attn(Launch& L, const PfAttnIO& io, int slot, int Lp, int pos0, co
                 attn_decode_kernel<bf16_t, 8, true><<<grid, 256, lds, L.s>>>(a);
         }
         L.chk();
+        if (ctx->trace) {
+            if (pass == 0) tr_rec(L, tr_name("pf.%d.append", li), Lp, HD, TrCls{0}, {TB_PF_QBF});
+            else tr_rec(L, tr_name("pf.%d.attn", li), Lp, HD, TrCls{0}, {TB_PF_Y, TB_PF_YBF});
+        }
     }
     return path;
 }
@@ -1808,20 +1844,32 @@ static void prefill_gemm(Launch& L, int slot, int Lp, int pos0, bool with_tail =
     e.scale = c.scale_codebook_embeddings; e.inv_div = (float)sqrt((double)(c.num_codebooks + 1));
     embed_kernel<bf16_t, true><<<dim3((D + 255) / 256, Lp), 256, 0, L.s>>>(e);
     L.chk();
+    // the launch trace's records (fishtts_hip_test.h): pf.embed, pf.<l>.<op>, pf.last; a product's class is pf_gemm's PF_ID_*
+    const auto rec = [&](const char* op, int li, int cols, int id, int buf) {
+        if (ctx->trace) tr_rec(L, li < 0 ? tr_name("pf.%s", op) : tr_name("pf.%d.%s", li, op), Lp, cols, TrCls{id}, {buf});
+    };
+    rec("embed", -1, D, -1, TB_PF_X);
     for (int li = 0; li < c.n_layer; ++li) {
         const FtLayer& l = ctx->layers[li];
         rmsnorm_llama_rows_kernel<bf16_t, true><<<Lp, 256, 0, L.s>>>(ctx->pf_x, l.attn_norm, c.norm_eps, D, ctx->pf_xn);
-        pf_gemm(L, ctx->pf_xn, D, Lp, l.wqkv, l.bqkv_f32, qkvN, D, ACT_NONE, nullptr, ctx->pf_qkv, nullptr, qkvN, 0);
+        rec("norm1", li, D, -1, TB_PF_XN);
+        rec("wqkv", li, qkvN, pf_gemm(L, ctx->pf_xn, D, Lp, l.wqkv, l.bqkv_f32, qkvN, D, ACT_NONE, nullptr, ctx->pf_qkv, nullptr, qkvN, 0), TB_PF_QKV);
         PfAttnIO io{ctx->pf_qkv, l.qn, l.kn, l.kc, l.vc, ctx->pf_y, ctx->pf_ybf, ctx->pf_qbf, ctx->pf_seqs, ctx->pf_rows};
-        pf_attn(L, io, slot, Lp, pos0, rg);
-        pf_gemm(L, ctx->pf_ybf, HD, Lp, l.wo, l.bo_f32, D, HD, ACT_NONE, ctx->pf_x, ctx->pf_x, nullptr, D, 1);
+        pf_attn(L, io, slot, Lp, pos0, rg, li);
+        rec("wo", li, D, pf_gemm(L, ctx->pf_ybf, HD, Lp, l.wo, l.bo_f32, D, HD, ACT_NONE, ctx->pf_x, ctx->pf_x, nullptr, D, 1), TB_PF_X);
         rmsnorm_llama_rows_kernel<bf16_t, true><<<Lp, 256, 0, L.s>>>(ctx->pf_x, l.ffn_norm, c.norm_eps, D, ctx->pf_xn);
-        pf_gemm(L, ctx->pf_xn, D, Lp, l.w13, nullptr, 2 * F, D, ACT_SWIGLU, nullptr, nullptr, ctx->pf_g, F, 0);
-        pf_gemm(L, ctx->pf_g, F, Lp, l.w2, nullptr, D, F, ACT_NONE, ctx->pf_x, ctx->pf_x, nullptr, D, 1);
+        rec("norm2", li, D, -1, TB_PF_XN);
+        rec("w13", li, F, pf_gemm(L, ctx->pf_xn, D, Lp, l.w13, nullptr, 2 * F, D, ACT_SWIGLU, nullptr, nullptr, ctx->pf_g, F, 0), TB_PF_G);
+        rec("w2", li, D, pf_gemm(L, ctx->pf_g, F, Lp, l.w2, nullptr, D, F, ACT_NONE, ctx->pf_x, ctx->pf_x, nullptr, D, 1), TB_PF_X);
     }
     // the last position feeds the head and the fast stack through the decode kernels
-    if (rg) { gather_last_rows_kernel<<<rg->n, 256, 0, L.s>>>(ctx->pf_x, D, ctx->pf_seqs, ctx->x); L.chk(); return; }
+    if (rg) {
+        gather_last_rows_kernel<<<rg->n, 256, 0, L.s>>>(ctx->pf_x, D, ctx->pf_seqs, ctx->x); L.chk();
+        if (ctx->trace) tr_rec(L, "pf.last", rg->n, D, TrCls{}, {TB_X});
+        return;
+    }
     hipMemcpyAsync(ctx->x + (size_t)slot * D, ctx->pf_x + (size_t)(Lp - 1) * D, D * sizeof(float), hipMemcpyDeviceToDevice, L.s);
+    if (ctx->trace) tr_rec(L, "pf.last", 1, D, TrCls{}, {TB_X});
     if (!with_tail) return;   // ft_ar_prefill_slow: the first frames of several slots are drawn together later
     enqueue_fproj<bf16_t, true>(L);
     enqueue_frame_tail<bf16_t, true>(L);
@@ -1841,14 +1889,20 @@ extern "C" ft_status ft_ar_prefill_at(ft_ctx* ctx, int32_t slot, const int32_t* 
         return ft_fail(ctx, FT_ERR_TOO_LONG, buf);
     }
     const int R = c.num_codebooks + 1;
-    ctx->tstore.armed = false;        // the launch trace arms the next decode frame / first frames only
+    const bool on_engine = eng_in_use(ctx);
+    if (ctx->tstore.armed && on_engine) {
+        ctx->tstore.armed = false;
+        return ft_fail(ctx, FT_ERR_STATE, "ft_ar_prefill: a traced call never runs on the frame engine");
+    }
+    ArTraceScope traced(ctx, true, 3, slot, 1);
+    if (traced.own) tr_state(ctx, 0);  // before the reset: what it does to the slot is part of the record
     ctx->hid_in_xo[slot] = 0;
     FT_TRY(ft_ar_reset(ctx, slot));
     FT_TRY(upload_ctl(ctx, slot, 1, sp));
     FT_HIP(ctx, hipMemcpyAsync(ctx->d_prompt, prompt, (size_t)R * Lp * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    tr_uploaded(ctx, {TB_PROMPT});
     pick_nsplit(ctx, pos0 + Lp);       // (position-by-position prompt passes: the split count of this prompt's length)
     Launch L{ctx, ctx->stream, slot, 1, 0};
-    const bool on_engine = eng_in_use(ctx);
     if (!ctx->prefill_v0) {
         prefill_gemm(L, slot, Lp, pos0);
     } else {
@@ -1856,9 +1910,11 @@ extern "C" ft_status ft_ar_prefill_at(ft_ctx* ctx, int32_t slot, const int32_t* 
         // kernels position by position (same causal arithmetic); only the last position runs the head
         for (int t = 0; t < Lp - 1; ++t) {
             L.pos_off = pos0 + t;
+            tr_pos(ctx, t);
             enqueue_slow_only(L, ctx->d_prompt, Lp, 0, t);
         }
         L.pos_off = pos0 + Lp - 1;
+        tr_pos(ctx, Lp - 1);
         enqueue_frame(L, ctx->d_prompt, Lp, 0, Lp - 1);
     }
     if (L.err != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("prefill launch: ") + hipGetErrorString(L.err));
@@ -1877,6 +1933,7 @@ extern "C" ft_status ft_ar_prefill_at(ft_ctx* ctx, int32_t slot, const int32_t* 
     FT_HIP(ctx, hipMemcpyAsync(ctx->d_pos + slot, ctx->h_pin, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     FT_HIP(ctx, hipMemcpyAsync(out_frame, ctx->d_tok + (size_t)slot * R, R * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     FT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (traced.own) tr_state(ctx, 1);
     return FT_OK;
 }
 
@@ -1893,10 +1950,12 @@ extern "C" ft_status ft_ar_prefill_slow(ft_ctx* ctx, int32_t slot, const int32_t
         return ft_fail(ctx, FT_ERR_TOO_LONG, buf);
     }
     const int R = c.num_codebooks + 1;
-    ctx->tstore.armed = false;
+    ArTraceScope traced(ctx, true, 4, slot, 1);        // (inside a traced ft_ar_prefill_slow_many: that call's trace goes on)
+    if (traced.own) tr_state(ctx, 0);
     ctx->hid_in_xo[slot] = 0;
     FT_TRY(ft_ar_reset(ctx, slot));
     FT_HIP(ctx, hipMemcpyAsync(ctx->d_prompt, prompt, (size_t)R * Lp * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    tr_uploaded(ctx, {TB_PROMPT});
     pick_nsplit(ctx, pos0 + Lp);
     Launch L{ctx, ctx->stream, slot, 1, 0};
     if (!ctx->prefill_v0) {
@@ -1904,11 +1963,13 @@ extern "C" ft_status ft_ar_prefill_slow(ft_ctx* ctx, int32_t slot, const int32_t
     } else {
         for (int t = 0; t < Lp; ++t) {
             L.pos_off = pos0 + t;
+            tr_pos(ctx, t);
             enqueue_slow_only(L, ctx->d_prompt, Lp, 0, t);
         }
     }
     if (L.err != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("prefill launch: ") + hipGetErrorString(L.err));
     FT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // d_prompt is reused by the next call
+    if (traced.own) tr_state(ctx, 1);
     return FT_OK;
 }
 
@@ -1927,7 +1988,6 @@ extern "C" ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32
     if (!slots || !prompts || !Lps || !pos0s) return ft_fail(ctx, FT_ERR_ARG, "ft_ar_prefill_slow_many: null argument");
     if (n < 1 || n > c.max_batch) return ft_fail(ctx, FT_ERR_ARG, "ft_ar_prefill_slow_many: bad count");
     const int R = c.num_codebooks + 1;
-    ctx->tstore.armed = false;
     std::vector<char> seen(c.max_batch, 0);
     std::vector<size_t> off(n + 1, 0);
     for (int i = 0; i < n; ++i) {
@@ -1944,19 +2004,27 @@ extern "C" ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32
     // bf16 only (the pf_* workspace and the prompt kernels): fp16 runs its lock-step frames on the MFMA launches, its prompts one by one
     const bool ragged = c.dtype == FT_BF16 && !ctx->prefill_v0 && ctx->wide_ok && n >= ctx->wide_min && (c.head_dim == 64 || c.head_dim == 128) &&
                         !getenv("FT_PREFILL_ATTN_V0") && !getenv("FT_NO_RAGGED_PREFILL");
+    ArTraceScope traced(ctx, true, 5, 0, n);           // one trace over every pass of the call, the single passes of the fall-back included
+    if (traced.own) tr_state(ctx, 0);
     if (!ragged) {
-        for (int i = 0; i < n; ++i) FT_TRY(ft_ar_prefill_slow(ctx, slots[i], prompts + off[i], Lps[i], pos0s[i]));
+        for (int i = 0; i < n; ++i) {
+            if (traced.own && n > 1) ctx->tstore.pass_prefix = tr_name("pass%d.", i);
+            FT_TRY(ft_ar_prefill_slow(ctx, slots[i], prompts + off[i], Lps[i], pos0s[i]));
+        }
+        if (traced.own) tr_state(ctx, 1);
         return FT_OK;
     }
     std::vector<int> tok;
     std::vector<int4> seqs;
     std::vector<int2> rows;
-    for (int i0 = 0; i0 < n;) {
+    for (int i0 = 0, pass = 0; i0 < n; ++pass) {
         int i1 = i0, S = 0, max_lp = 0, end = 0;
         while (i1 < n && S + Lps[i1] <= c.max_seq_len) { S += Lps[i1]; max_lp = std::max(max_lp, Lps[i1]); end = std::max(end, pos0s[i1] + Lps[i1]); ++i1; }
+        if (traced.own && (pass > 0 || i1 < n)) ctx->tstore.pass_prefix = tr_name("pass%d.", pass);
         tok.assign((size_t)R * S, 0); seqs.clear(); rows.clear();
         int row0 = 0;
         for (int i = i0; i < i1; ++i) {
+            ctx->hid_in_xo[slots[i]] = 0;       // as a single pass: the slot's hidden state is the row this pass leaves in ctx->x
             FT_TRY(ft_ar_reset(ctx, slots[i]));
             for (int r = 0; r < R; ++r)
                 memcpy(&tok[(size_t)r * S + row0], prompts + off[i] + (size_t)r * Lps[i], (size_t)Lps[i] * sizeof(int));
@@ -1967,6 +2035,7 @@ extern "C" ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32
         FT_HIP(ctx, hipMemcpyAsync(ctx->d_prompt, tok.data(), tok.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         FT_HIP(ctx, hipMemcpyAsync(ctx->pf_seqs, seqs.data(), seqs.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
         FT_HIP(ctx, hipMemcpyAsync(ctx->pf_rows, rows.data(), rows.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
+        tr_uploaded(ctx, {TB_PROMPT, TB_PF_SEQS, TB_PF_ROWS});
         pick_nsplit(ctx, end);
         Launch L{ctx, ctx->stream, 0, 1, 0};
         const RaggedPf rg{i1 - i0, max_lp};
@@ -1975,6 +2044,7 @@ extern "C" ft_status ft_ar_prefill_slow_many(ft_ctx* ctx, int32_t n, const int32
         FT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host vectors and d_prompt are reused by the next pass
         i0 = i1;
     }
+    if (traced.own) tr_state(ctx, 1);
     return FT_OK;
 }
 
@@ -2398,6 +2468,7 @@ extern "C" ft_status ft_test_ar_trace_launch(ft_ctx* ctx, int32_t i, char* name,
     snprintf(name, (size_t)cap, "%s", r.name.c_str());
     info[0] = r.m0; info[1] = r.rows; info[2] = r.cols; info[3] = (int32_t)r.bufs.size(); info[4] = r.held ? 1 : 0;
     for (int k = 0; k < 4; ++k) info[5 + k] = r.cls[k];
+    info[9] = r.pos_off;
     return FT_OK;
 }
 extern "C" ft_status ft_test_ar_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t* info, void* dst) {

@@ -220,10 +220,24 @@ ft_status ft_test_codec_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t*
 
 /* Test hook: a launch trace of the AR frame (host code only: no kernel, no branch in a kernel, nothing in a captured graph;
  * off, it costs one null-pointer test per launch site).  ft_test_ar_trace_arm makes the NEXT ft_ar_decode with n_frames == 1,
- * or the NEXT ft_ar_first_frames, on this context record one entry per kernel launch, in launch order; any other prompt or
- * decode call disarms it untraced.  The traced decode call launches its frame eagerly (the FT_NO_GRAPH branch), never from
+ * the NEXT ft_ar_first_frames or the NEXT prompt call (ft_ar_prefill_at / ft_ar_prefill, ft_ar_prefill_slow,
+ * ft_ar_prefill_slow_many) on this context record one entry per kernel launch, in launch order; any other decode call disarms
+ * it untraced.  The traced decode call launches its frame eagerly (the FT_NO_GRAPH branch), never from
  * a captured graph and never on the frame engine: arming a one-slot context whose frames run on the engine is FT_ERR_STATE,
- * and so is the armed call itself where it would go to the engine (one slot on a context that owns one).
+ * and so is the armed call itself where it would go to the engine (one slot on a context that owns one; ft_ar_prefill_at on
+ * any context that owns one, whose first frame's codebook loop runs there).
+ * A prompt call (kinds 3, 4, 5).  prefill_gemm records "pf.embed", per layer "pf.<l>.norm1|wqkv|append|attn|wo|norm2|w13|w2",
+ * "pf.last" (gather_last_rows_kernel, or the device-to-device copy of the last row into ctx->x) and, for kind 3, the tail under
+ * the names of first frames ("fproj", "head", "draw.*", "fast.*").  cls[0]: a product's PF_ID_* (ft_test_pf_linear's *variant), the
+ * append's 1 (prefill_rope_append_kernel) or 0, the attention's path (NG of the tiled kernel; 0: position by position).  m0 is the
+ * slot of a single pass, 0 in a ragged one; rows the pass's rows.  A position-by-position prompt records the "embed" and
+ * "slow.<l>.*" entries of each position k with "t<k>." in front, and the launch's pos_off (= pos0 + k; the device position is 0
+ * after the reset).  A call of several passes - a ragged fill of more rows than max_seq_len, or ft_ar_prefill_slow_many falling back
+ * to single passes, which is ONE trace over all of them - carries "pass<k>." in front of every name.  What the host uploaded for a
+ * pass (d_prompt; pf_seqs and pf_rows in a ragged one) rides with the pass's first record.  State 0 and the record before the
+ * first launch are taken BEFORE the call's ft_ar_reset, so the reset is part of what a reader judges; state 1 at the end of the call.
+ * hid_in_xo of every slot a prompt call fills is 0 when the call returns (the single passes and the ragged pass alike: the slot's
+ * hidden state is the row the pass left in ctx->x); read it with ft_test_ar_slots.
  * Recording only reads: the traced call's frames and the state it leaves equal the untraced call's bit for bit.
  * An entry: a stable name - "embed", "slow.<l>.wqkv|attn|wo|w13|w2" ("slow.<l>.attn.merge": attn_combine_rows_kernel behind a
  * split lock-step attention), "fproj", "xo_rows", "head", "draw.<cb>" (the four-launch draw: "draw.0.cut|count|race|finish"),
@@ -237,18 +251,23 @@ ft_status ft_test_codec_trace_buffer(ft_ctx* ctx, int32_t i, int32_t j, int32_t*
  * width], 9 gf, 10 flog [max_batch][fastV], 11 part_o, 12 part_ml (flat: row m's partials at m H nsplit hd / m H nsplit 2 for
  * the call's split count); raw 16-bit octet-major [width / 8][xo_ldm][8], reported as rows = width / 8, cols = 8 xo_ldm: 20
  * xo_x, 21 xo_xf, 22 xo_femb, 23 xo_y, 24 xo_g; int32: 30 tokn, 31 tok [max_batch][R], 32 pos, 33 nf, 34 done [1][max_batch], 35
- * seq [max_batch][R cap], 36 cut [max_batch][8], 37 chunk_cnt, 38 part_idx [1][max_batch ceil(vocab / 1024)].  A draw entry
+ * seq [max_batch][R cap], 36 cut [max_batch][8], 37 chunk_cnt, 38 part_idx [1][max_batch ceil(vocab / 1024)]; the prompt pass's
+ * workspace, every one of its max_seq_len rows (prompt calls only, where the context has one): f32 13 pf_x [max_seq_len][dim], 14
+ * pf_qkv, 15 pf_y [max_seq_len][H hd]; 16-bit ROW-major (rows, cols as said) 25 pf_xn [max_seq_len][dim], 26 pf_ybf, 27 pf_qbf
+ * [max_seq_len][H hd], 28 pf_g [max_seq_len][intermediate]; int32 39 d_prompt [1][R max_seq_len], 40 pf_seqs [max_batch][4], 41 pf_rows
+ * [max_seq_len][2].  A draw entry
  * lists every buffer finish_draw can write, written in this launch or not.  The K/V caches are not copied: read them before and
  * after the call with ft_test_engine_handoffs (which takes an f32 context too: its arrays then hold f32 values).
  * ft_test_ar_trace_count: launches the last traced call recorded (-1: a copy failed); info[5] (may be NULL) = {kind (0 none,
- * 1 a decode frame, 2 first frames), m0, rows of the call, 1 if still armed, buffers of the record before the first launch}.
+ * 1 a decode frame, 2 first frames, 3 ft_ar_prefill_at, 4 ft_ar_prefill_slow, 5 ft_ar_prefill_slow_many), m0 (kinds 3, 4: the slot; 5: 0),
+ * rows of the call (kinds 3, 4: 1; 5: n), 1 if still armed, buffers of the record before the first launch}.
  * That record (launch index -1 of ft_test_ar_trace_buffer) holds every buffer listed above as the call found it: what a
  * buffer's first write in the call is held against.
- * ft_test_ar_trace_launch: info[9] = {m0, rows, cols, buffers, 1 if held, cls[0..3]}.
+ * ft_test_ar_trace_launch: info[10] = {m0, rows, cols, buffers, 1 if held, cls[0..3], pos_off}.
  * ft_test_ar_trace_buffer: info[4] = {id, bytes per element, rows, cols} of buffer j of launch i; dst != NULL receives it
  * (once: the copy is released).
  * ft_test_ar_trace_state: which = 0 before the first launch (after the call's controls went up and a frozen row's position was
- * put back inside its cache), 1 at the end of the call: tok [max_batch][R], pos, nf, done [max_batch], seq [max_batch][R][cap]. */
+ * put back inside its cache; a prompt call: before its reset), 1 at the end of the call: tok [max_batch][R], pos, nf, done [max_batch], seq [max_batch][R][cap]. */
 ft_status ft_test_ar_trace_arm(ft_ctx* ctx, int32_t first, int32_t count);
 int32_t ft_test_ar_trace_count(ft_ctx* ctx, int32_t* info);
 ft_status ft_test_ar_trace_launch(ft_ctx* ctx, int32_t i, char* name, int32_t cap, int32_t* info);

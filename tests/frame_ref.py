@@ -380,6 +380,7 @@ class Report:
     draws: D.Tally = field(default_factory=D.Tally)
     draw_rows: int = 0                                           # rows of all draw launches judged ...
     unplaced: int = 0                                            # ... of which the reference could not place the top-p cut (see _draw_rows)
+    shares: Dict[str, float] = field(default_factory=dict)       # launch kind (the name's last part) -> the largest share of a bound
 
     def flagged(self) -> List[str]:
         return sorted({n for n, _ in self.flags})
@@ -387,6 +388,8 @@ class Report:
     def note(self, name, checked, worst):
         self.judged += 1
         self.elements += int(checked)
+        kind = name.split(" ")[0].split(".")[-1]
+        self.shares[kind] = max(self.shares.get(kind, 0.0), float(worst))
         if worst > self.worst:
             self.worst, self.worst_at = float(worst), name
 
@@ -395,6 +398,8 @@ class Report:
         if o.worst > self.worst:
             self.worst, self.worst_at = o.worst, o.worst_at
         self.classes |= o.classes; self.names |= o.names; self.left_out += o.left_out
+        for k, v in o.shares.items():
+            self.shares[k] = max(self.shares.get(k, 0.0), v)
         self.draw_rows += o.draw_rows; self.unplaced += o.unplaced
         for k in ("probes", "left_out", "draws", "allowed"):
             setattr(self.draws, k, getattr(self.draws, k) + getattr(o.draws, k))

@@ -312,8 +312,8 @@ def test_arming_rules():
         info = np.zeros(5, dtype=np.int32)
         assert cx.eng.lib.ft_test_ar_trace_count(cx.eng._h, info.ctypes.data_as(L.C.c_void_p)) == 0 and info[3] == 0 and info[0] == 0
         cx.eng.trace_arm()
-        cx.fill([3], seed=6)                                             # a prompt pass disarms it
-        assert cx.eng.lib.ft_test_ar_trace_count(cx.eng._h, info.ctypes.data_as(L.C.c_void_p)) == 0 and info[3] == 0
+        cx.fill([3], seed=6)                                             # the prompt pass takes it (kind 5); the first frames behind it run untraced
+        assert cx.eng.lib.ft_test_ar_trace_count(cx.eng._h, info.ctypes.data_as(L.C.c_void_p)) > 0 and info[3] == 0 and info[0] == 5
         cx.eng.trace_arm(first=2, count=3)                               # only launches 2, 3, 4 keep their copies
         cx.decode(2, traced=False)
         tr = cx.eng.trace_read()

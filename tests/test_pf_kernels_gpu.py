@@ -8,9 +8,9 @@ every element of every written row against the float64 restatement of tests/pf_r
 
 with err derived there.  Rows past S must still hold the sentinel, cache rows other than the appended ones must be
 bit-unchanged (the hook's NaN fill behind every sequence and in unused slots included), every y must be finite.
-tests/test_pf_ref_host.py proves the checker flags the subtle faults this is for.  No prompt pass is traced: the wiring between
-the launches stays the job of the oracle-following tests (test_ar_gpu.py: test_prefill_gemm_paths_vs_oracle,
-test_ragged_prompt_pass_vs_oracle)."""
+tests/test_pf_ref_host.py proves the checker flags the subtle faults this is for.  These hooks trace no prompt pass: the wiring between
+the launches is held to float64 launch by launch in tests/test_prompt_launches_gpu.py (the launch trace of a whole prompt call),
+beside the oracle-following tests (test_ar_gpu.py: test_prefill_gemm_paths_vs_oracle, test_ragged_prompt_pass_vs_oracle)."""
 import os
 
 import numpy as np
