@@ -74,6 +74,10 @@ class ft_mix_info(C.Structure):
                 ("capped", C.c_int32), ("pk", C.c_float), ("sg", C.c_float), ("bed", ft_intake_info)]
 
 
+class ft_pan_region(C.Structure):
+    _fields_ = [("a", C.c_int64), ("e", C.c_int64), ("pan", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ft_mix_live_info(C.Structure):
     _fields_ = [("N", C.c_int64), ("nb", C.c_int64), ("Nh", C.c_int64), ("active", C.c_int64), ("dmax", C.c_int32),
                 ("lmax", C.c_int32), ("qmax", C.c_float), ("reserved", C.c_int32), ("bed", ft_intake_info)]
@@ -174,6 +178,9 @@ SYMBOLS = {
                                  _P, _P, C.POINTER(ft_mix_info)]),
     "ft_mix_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "ft_mix_gains": (C.c_int32, [_P]),
+    "ft_codec_mix_stereo": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.POINTER(ft_intake_item),
+                                        C.POINTER(ft_mix_params), _P, C.c_int64, _P, _P, C.POINTER(ft_mix_info)]),
+    "ft_pan_gains": (C.c_int32, [_P]),
     "ft_mix_live_plan": (C.c_int32, [C.c_int32, C.POINTER(ft_mix_params), C.c_int64, C.c_int32, _P, _P]),
     "ft_codec_mix_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), _P,
                                       C.c_int64, _P, _P, _P, C.POINTER(ft_mix_live_info)]),

@@ -817,15 +817,56 @@ class CodecHipEngine:
         rep = MixReport.of(info)
         return (y[:total.value], rep, D) if nodes else (y[:total.value], rep)
 
-    def _mix_args(self, what: str, bed, sample_rate, params):
-        """(rate, bed item array, what keeps its bytes alive, ft_mix_params) of a mix call, checked as mix() checks them."""
+    MAX_PAN_REGIONS = 4096        # ft_codec_mix_stereo
+
+    def mix_stereo(self, x: np.ndarray, bed, regions=(), sample_rate: Optional[int] = None, params=None, nodes: bool = False):
+        """The stereo mix stage on a mono host waveform (ft_codec_mix_stereo): mix() with two channels out.  `regions`:
+        (a, e, pan) each - samples [a, e) of x sit at `pan`, an integer in [-100, 100] with -100 hard left; sorted and
+        disjoint, at most 4096; what no region holds sits in the centre.  `bed`: as mix()'s, its first two channels the two
+        sides (a mono file, or a `channel` in params: that channel on both), or None for a panned programme without a bed.
+        Returns (y, MixReport), or (y, MixReport, D) with `nodes`; y is (N, 2) float32, left then right."""
+        rate, items, keep, mp = self._mix_args("mix_stereo", bed, sample_rate, params, bedless=True)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        if len(x) < 1:
+            raise ValueError("mix_stereo: an empty programme")
+        regions = [tuple(r) for r in regions]
+        if len(regions) > self.MAX_PAN_REGIONS:
+            raise ValueError(f"mix_stereo: {len(regions)} pan regions, a call takes {self.MAX_PAN_REGIONS}")
+        at = 0
+        for r in regions:
+            if len(r) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
+                raise ValueError(f"mix_stereo: a region is three integers (a, e, pan), got {r!r}")
+            a, e, pan = r
+            if not at <= a < e <= len(x) or not -100 <= pan <= 100:
+                raise ValueError(f"mix_stereo: region {r!r} out of order, outside [0, {len(x)}) or its pan outside [-100, 100]")
+            at = e
+        reg = (L.ft_pan_region * max(len(regions), 1))(*[L.ft_pan_region(int(a), int(e), int(pan), 0) for a, e, pan in regions])
+        N, hop, nn = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._check(self.lib.ft_mix_plan(rate, len(x), mp.lead, mp.tail, C.byref(N), C.byref(hop), C.byref(nn)), "ft_mix_plan")
+        y = np.empty((N.value, 2), dtype=np.float32)
+        D = np.empty(nn.value, dtype=np.int32)
+        total = C.c_int64(0)
+        info = L.ft_mix_info()
+        self._check(self.lib.ft_codec_mix_stereo(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, reg, len(regions), items,
+                                                 C.byref(mp), y.ctypes.data_as(C.c_void_p), N.value, C.byref(total),
+                                                 D.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)),
+                    "ft_codec_mix_stereo")
+        del keep
+        rep = MixReport.of(info)
+        return (y[:total.value], rep, D) if nodes else (y[:total.value], rep)
+
+    def _mix_args(self, what: str, bed, sample_rate, params, bedless: bool = False):
+        """(rate, bed item array, what keeps its bytes alive, ft_mix_params) of a mix call, checked as mix() checks them.
+        `bedless`: the call takes None for the bed (the item array is then None)."""
         from .mix import Bed, MixParams, bed_params
         rate = OutputFx.of(sample_rate=sample_rate).wav_rate
         if params is None:
             params = bed_params(Bed(b""), rate)
         if not isinstance(params, MixParams):
             raise ValueError(f"{what}: params must be a MixParams, got {type(params).__name__}")
-        items, keep, _, _ = self._intake_args(what, [bed], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
+        items, keep = None, None
+        if bed is not None or not bedless:
+            items, keep, _, _ = self._intake_args(what, [bed], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
         mp = L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
                              params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
         return rate, items, keep, mp

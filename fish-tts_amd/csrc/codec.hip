@@ -10,6 +10,7 @@
 #include <numeric>
 
 #include "codec_kernels.h"
+#include "stereo_kernels.h"
 #include "engine.h"
 #include "fx_chain.h"
 #include "join_plan.h"
@@ -118,6 +119,11 @@ struct CodecState {
     int* mx_D = nullptr;
     MixOut* mx_out = nullptr;
     size_t mx_xcap = 0, mx_bedcap = 0, mx_ycap = 0, mx_gcap = 0, mx_actcap = 0, mx_Dcap = 0;
+    // stereo mix stage (ft_codec_mix_stereo): the pan table, uploaded once, and the call's regions; the rest is the mix
+    // stage's (mx_bed then holds both sides, mx_y the 2 N interleaved floats)
+    float* mx_U = nullptr;
+    MixPan* mx_reg = nullptr;
+    size_t mx_regcap = 0;
     // live mix stage (ft_codec_mix_stream_*): the open streams (their device state is freed with the context), and what a
     // push stages - its samples, the m of the hops it completes, the samples it emits; the buffers grow on need
     std::vector<ft_mix_stream*> mix_streams;
@@ -2580,6 +2586,7 @@ static ft_status intake_run(ft_ctx* ctx, const std::string& fn, int32_t B, const
     const int64_t most = (2 * (int64_t)ctx->cc.max_frames * s->frame_len * RS_MAX_RATE + RS_FI - 1) / RS_FI;   // ft_codec_loudness
     int64_t n44[JOIN_MAX_ITEMS], off[JOIN_MAX_ITEMS], raw_off[JOIN_MAX_ITEMS], gaps[JOIN_MAX_ITEMS], raw = 0, need = 0, room = 0;
     int Ls[JOIN_MAX_ITEMS], Ms[JOIN_MAX_ITEMS], Ks[JOIN_MAX_ITEMS];
+    bool twin[JOIN_MAX_ITEMS];
     size_t hops = 0;
     for (int b = 0; b < B; ++b) {
         const ft_intake_item& it = items[b];
@@ -2592,8 +2599,10 @@ static ft_status intake_run(ft_ctx* ctx, const std::string& fn, int32_t B, const
             return ft_fail(ctx, FT_ERR_ARG, who + ": " + e + " (" + std::to_string(it.rate) + ")");
         if (it.n_frames > IN_MAX_RAW) return ft_fail(ctx, FT_ERR_TOO_LONG, who + ": more than 2^30 raw bytes in one call");
         const int64_t bytes = it.n_frames * it.channels * IN_WIDTH[it.fmt];
-        raw_off[b] = raw;
-        raw += (bytes + 15) & ~(int64_t)15;
+        twin[b] = held && b > 0 && it.data == items[b - 1].data && it.n_frames == items[b - 1].n_frames &&
+                  it.channels == items[b - 1].channels && it.fmt == items[b - 1].fmt;     // the other side of a stereo bed:
+        raw_off[b] = twin[b] ? raw_off[b - 1] : raw;                                       // its frames are staged once
+        if (!twin[b]) raw += (bytes + 15) & ~(int64_t)15;
         if (raw > IN_MAX_RAW) return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": more than 2^30 raw bytes in one call");
         n44[b] = (it.n_frames * Ls[b] + Ms[b] - 1) / Ms[b];
         if (n44[b] > most) return ft_fail(ctx, FT_ERR_TOO_LONG, who + ": longer at 44100 Hz than the longest item the level stage takes");
@@ -2638,8 +2647,9 @@ static ft_status intake_run(ft_ctx* ctx, const std::string& fn, int32_t B, const
         g.n_out = n44[b];
         g.fmt = it.fmt; g.channels = it.channels; g.channel = it.channel;
         mx = std::max(mx, (long long)n44[b]);
-        FT_HIP(ctx, hipMemcpyAsync(s->in_raw + raw_off[b], it.data, (size_t)(it.n_frames * it.channels * IN_WIDTH[it.fmt]),
-                                   hipMemcpyHostToDevice, st));
+        if (!twin[b])
+            FT_HIP(ctx, hipMemcpyAsync(s->in_raw + raw_off[b], it.data, (size_t)(it.n_frames * it.channels * IN_WIDTH[it.fmt]),
+                                       hipMemcpyHostToDevice, st));
     }
     FT_HIP(ctx, hipMemsetAsync(s->in_count, 0, (size_t)2 * B * sizeof(unsigned long long), st));
     FT_HIP(ctx, hipMemcpyAsync(s->in_seg, segs.data(), segs.size() * sizeof(IntakeSeg), hipMemcpyHostToDevice, st));
@@ -2808,6 +2818,174 @@ extern "C" ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_
     FT_HIP(ctx, hipStreamSynchronize(st));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("mix launch: ") + hipGetErrorString(e));
+    *total = pl.N;
+    memset(info, 0, sizeof *info);
+    info->N = pl.N; info->nb = nb; info->Nh = pl.Nh; info->active = out.active;
+    info->dmax = out.dmax; info->capped = capped ? 1 : 0; info->pk = pk; info->sg = sg;
+    info->bed = binfo;
+    return FT_OK;
+}
+
+// ---- stereo mix stage (fishtts_hip.h: "Stereo mix"; mix_stereo_kernel and the pair level's two kernels in stereo_kernels.h,
+// the region checks, the pan table and the side selection in fx_chain.h)
+static_assert(sizeof(ft_pan_region) == sizeof(chain::MsRegion) && sizeof(ft_pan_region) == sizeof(MixPan) &&
+              offsetof(ft_pan_region, pan) == offsetof(chain::MsRegion, pan) && offsetof(ft_pan_region, pan) == offsetof(MixPan, pan) &&
+              offsetof(ft_pan_region, e) == 8 && sizeof(ft_pan_region) == 24, "ft_pan_region layout");
+static_assert(2 * chain::MS_MAX_PAN + 1 == MS_PANS && chain::MS_MAX_PAN == MS_CENTRE && MX_SPAN == 4096,
+              "fx_chain.h and codec_kernels.h disagree on the stereo mix stage");
+
+extern "C" ft_status ft_pan_gains(float* table) {
+    if (!table) return FT_ERR_ARG;
+    chain::ms_gains(table);
+    return FT_OK;
+}
+
+// The pair level over the two sides of n samples each that intake_run has just left back to back in join_out, their hop sums
+// and peaks back to back in the level stage's buffers (s->mu held): the sums added, one gain toward `target`, both sides
+// scaled by it.  Waits, and leaves the pair's ft_level_info in *out.
+static ft_status level_pair(ft_ctx* ctx, int64_t n, int target, ft_level_info* out) {
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    const long long nh = (long long)level_hops(n, RS_FI);
+    s->lv_up.assign(sizeof(LevelTab), 0);
+    LevelTab* h = (LevelTab*)s->lv_up.data();
+    chain::lv_design(RS_FI, h->c);
+    h->ceiling = chain::lv_ceiling();
+    h->H = chain::lv_hop(RS_FI);
+    h->B = 1;
+    h->it[0].x = s->join_out;
+    h->it[0].n = n;
+    h->it[0].hop0 = 0;
+    h->it[0].target = target;
+    const size_t used = offsetof(LevelTab, it) + sizeof(LevelItem);
+    FT_HIP(ctx, hipMemcpyAsync(s->lv_tab, h, used, hipMemcpyHostToDevice, st));
+    level_pair_kernel<<<(unsigned)std::max(1LL, std::min(1024LL, (nh + LV_SCALE_THREADS - 1) / LV_SCALE_THREADS)), LV_SCALE_THREADS, 0, st>>>(
+        s->lv_hops, s->lv_peaks, nh);
+    level_gain_kernel<<<1, LV_GAIN_THREADS, 0, st>>>(s->lv_tab, s->lv_hops, s->lv_peaks);
+    if (target != 0) {
+        const int gx = (int)std::max(1LL, std::min(1024LL, (2 * (long long)n + LV_SCALE_THREADS - 1) / LV_SCALE_THREADS));
+        level_pair_scale_kernel<<<gx, LV_SCALE_THREADS, 0, st>>>(s->lv_tab);
+    }
+    s->lv_down.resize(sizeof(LevelTab));
+    FT_HIP(ctx, hipMemcpyAsync(s->lv_down.data(), s->lv_tab, used, hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    level_fetch(s, 1, out);
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_pan_region* regions,
+                                         int32_t R, const ft_intake_item* bed, const ft_mix_params* mp, float* y, int64_t capacity,
+                                         int64_t* total, int32_t* duck, ft_mix_info* info) {
+    const std::string fn = "ft_codec_mix_stereo";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!x || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    chain::MxArgs a;
+    a.rate = sample_rate; a.n = n; a.bed_loudness = mp->bed_loudness; a.depth = mp->depth; a.threshold = mp->threshold;
+    a.attack = mp->attack; a.release = mp->release; a.lead = mp->lead; a.tail = mp->tail; a.fade_in = mp->fade_in;
+    a.fade_out = mp->fade_out; a.offset = mp->offset; a.loop = mp->loop;
+    const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
+    bool too_long = false;
+    if (const char* why = chain::mx_check(a, &too_long, 1, &pans))
+        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    const chain::MxPlan pl = chain::mx_plan(sample_rate, n, mp->lead, mp->tail);
+    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
+    CodecState* s = ctx->codec;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d));
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));           // (a call without a bed does not pass through intake_run)
+    hipStream_t st = s->stream;
+    // the bed: one side prepared as ft_codec_mix prepares its bed, or two sides measured as a pair, each to the output rate
+    int64_t nb = 0;
+    const float* side[2] = {nullptr, nullptr};
+    ft_intake_info binfo;
+    memset(&binfo, 0, sizeof binfo);
+    RsSeg g[2];                                       // (read by an asynchronous copy: alive until the call's waits)
+    if (bed) {
+        const chain::MsSides sd = chain::ms_sides(mp->channel, bed->channels);
+        const int sides = sd.same ? 1 : 2;
+        ft_intake_item item[2] = {*bed, *bed};
+        item[0].channel = sd.same ? mp->channel : sd.ch[0];
+        item[1].channel = sd.ch[1];
+        const ft_join_params whole = {0.f, 1, 0, 0};
+        int64_t lens[2] = {0, 0};
+        ft_intake_info bi[2];
+        FT_TRY(intake_run(ctx, fn, sides, item, &whole, sd.same ? mp->bed_loudness : 0, false, nullptr, nullptr, INT64_MAX, lens, bi, true));
+        const int64_t nb44 = lens[0];
+        if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
+        binfo = bi[0];
+        if (!sd.same) {
+            binfo.clipped += bi[1].clipped;
+            binfo.nonfinite += bi[1].nonfinite;
+            FT_TRY(level_pair(ctx, nb44, mp->bed_loudness, &binfo.level));
+        }
+        FT_TRY(rs_table(ctx, sample_rate, &d.rs));
+        nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
+        const int64_t pitch = (nb + 3) & ~(int64_t)3;  // side 1 begins on a 16-byte boundary
+        if (d.K > 0 || !sd.same) {
+            if (!s->rs_seg) FT_TRY(cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS));
+            FT_TRY(cgrow(ctx, &s->mx_bed, &s->mx_bedcap, (size_t)(pitch * sides)));
+            for (int c = 0; c < sides; ++c) {
+                g[c] = RsSeg{s->join_out + c * nb44, d.K > 0 ? d.rs->w : nullptr, nullptr, nullptr, s->mx_bed + c * pitch, 0, 0,
+                             (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
+                side[c] = s->mx_bed + c * pitch;
+            }
+            FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, g, (size_t)sides * sizeof(RsSeg), hipMemcpyHostToDevice, st));
+            const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
+            resample_kernel<<<dim3(gx, 1, sides), RS_THREADS, 0, st>>>(s->rs_seg);
+        } else {
+            side[0] = s->join_out;
+        }
+        if (sd.same) side[1] = side[0];
+    }
+    FT_TRY(mix_table(ctx));
+    if (!s->mx_U) {
+        float U[MS_PANS], *u = nullptr;
+        chain::ms_gains(U);
+        FT_TRY(cmalloc(ctx, &u, (size_t)MS_PANS));
+        FT_TRY(cupload(ctx, u, U, sizeof U));
+        s->mx_U = u;
+    }
+    FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
+    FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, (size_t)n));
+    FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)(2 * pl.N)));
+    FT_TRY(cgrow(ctx, &s->mx_act, &s->mx_actcap, (size_t)pl.Nh));
+    FT_TRY(cgrow(ctx, &s->mx_D, &s->mx_Dcap, (size_t)pl.Nh + 1));
+    FT_TRY(cgrow(ctx, &s->mx_g, &s->mx_gcap, (size_t)pl.Nh + 1));
+    MixSP sp;
+    memset(&sp, 0, sizeof sp);
+    MixP& p = sp.m;
+    p.x = s->mx_x; p.bed = side[0]; p.T = s->mx_T; p.act = s->mx_act; p.D = s->mx_D; p.g = s->mx_g; p.y = s->mx_y; p.out = s->mx_out;
+    p.nb = nb;
+    p.off = !bed ? 0 : mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
+    p.N = (int)pl.N; p.n = (int)n; p.lead = (int)mp->lead; p.Nh = (int)pl.Nh; p.H = pl.H;
+    p.depth = mp->depth; p.Wa = mp->attack; p.Wr = mp->release;
+    p.f_in = (int)std::min(mp->fade_in, (int64_t)(pl.N / 2)); p.f_out = (int)std::min(mp->fade_out, (int64_t)(pl.N / 2));
+    p.loop = bed ? mp->loop : 0; p.thr = mp->threshold;
+    sp.bed1 = side[1]; sp.reg = s->mx_reg; sp.U = s->mx_U; sp.R = R;
+    FT_HIP(ctx, hipMemcpyAsync(s->mx_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, regions, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipMemsetAsync(s->mx_out, 0, sizeof(MixOut), st));
+    mix_hop_kernel<<<(unsigned)((pl.Nh + MX_THREADS / 64 - 1) / (MX_THREADS / 64)), MX_THREADS, 0, st>>>(p);
+    mix_node_kernel<<<(unsigned)((pl.Nh + 1 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
+    mix_stereo_kernel<<<(unsigned)((pl.N + MX_SPAN - 1) / MX_SPAN), MX_THREADS, 0, st>>>(sp);
+    MixOut out;
+    FT_HIP(ctx, hipMemcpyAsync(&out, s->mx_out, sizeof out, hipMemcpyDeviceToHost, st));
+    if (duck) FT_HIP(ctx, hipMemcpyAsync(duck, s->mx_D, ((size_t)pl.Nh + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));            // the peak decides whether the fourth launch runs
+    float pk, sg = 1.f;
+    memcpy(&pk, &out.pk, sizeof pk);
+    const bool capped = (double)pk > chain::lv_ceiling();
+    if (capped) {
+        sg = (float)(chain::lv_ceiling() / (double)pk);
+        const int gx = (int)std::max(1LL, std::min(4096LL, (pl.N / 2 + MX_THREADS - 1) / MX_THREADS));
+        mix_scale_kernel<<<gx, MX_THREADS, 0, st>>>(s->mx_y, (int)(2 * pl.N), sg);
+    }
+    FT_HIP(ctx, hipMemcpyAsync(y, s->mx_y, (size_t)(2 * pl.N) * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("stereo mix launch: ") + hipGetErrorString(e));
     *total = pl.N;
     memset(info, 0, sizeof *info);
     info->N = pl.N; info->nb = nb; info->Nh = pl.Nh; info->active = out.active;

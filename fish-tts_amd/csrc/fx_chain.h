@@ -2,8 +2,8 @@
 // time-scale stage, then the pitch stage, then the resampler, then the level (whole items) or the ride stage (streams).  The filter designs, the rule that accepts a
 // (speed, cents) pair, what each stage can emit after so many input samples, the bookkeeping of a stream's three stages from
 // call to call, and the level stage's K-weighting design, gates and gain; behind the join, the mix stage's timeline, checks,
-// duck and gain table (mx_*; tools/mix_check.cpp drives that block) and the live mix stage's emission (ml_*, MlStage;
-// tools/mix_live_check.cpp).
+// duck and gain table (mx_*; tools/mix_check.cpp drives that block), the stereo mix stage's pan regions, pan table and bed
+// sides (ms_*; tools/stereo_check.cpp) and the live mix stage's emission (ml_*, MlStage; tools/mix_live_check.cpp).
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
 // are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
@@ -290,12 +290,57 @@ struct MxArgs {
     long long lead = 0, tail = 0, fade_in = 0, fade_out = 0, offset = 0;
     int loop = 0;
 };
-// (min_n: 1 for the mix stage; 0 for the live mix stage, whose programme may be empty)
-inline const char* mx_check(const MxArgs& a, bool* too_long, long long min_n = 1) {
+// The stereo mix stage's pan regions (ft_pan_region; fishtts_hip.h: "Stereo mix"): sorted, disjoint, inside [0, n), pans in
+// hundredths from -100 (hard left) to 100.  ms_check judges a table; ms_pan is q of programme sample j by binary search.
+constexpr int MS_MAX_REGIONS = 4096, MS_MAX_PAN = 100;
+struct MsRegion { long long a = 0, e = 0; int pan = 0, reserved = 0; };
+struct MsTable { const MsRegion* reg = nullptr; long long R = 0; };
+inline const char* ms_check(const MsTable& t, long long n) {
+    if (t.R > 0 && !t.reg) return "a null region table with R > 0";
+    if (t.R < 0 || t.R > MS_MAX_REGIONS) return "R outside [0, 4096] pan regions";
+    long long at = 0;                         // the end of the region before
+    for (long long r = 0; r < t.R; ++r) {
+        const MsRegion& g = t.reg[r];
+        if (g.a < at || g.a >= g.e || g.e > n) return "a pan region out of order or outside [0, n)";
+        if (g.pan < -MS_MAX_PAN || g.pan > MS_MAX_PAN) return "a pan outside [-100, 100]";
+        at = g.e;
+    }
+    return nullptr;
+}
+inline int ms_pan(const MsTable& t, long long j) {
+    long long lo = 0, hi = t.R;               // the first region that ends behind j
+    while (lo < hi) {
+        const long long mid = (lo + hi) / 2;
+        if (t.reg[mid].e > j) hi = mid; else lo = mid + 1;
+    }
+    return lo < t.R && t.reg[lo].a <= j ? t.reg[lo].pan : 0;
+}
+// U[j] = (float) min(1, sqrt(2) sin(j pi / 400)), j = 0 .. 200: float64 rounded once; U[0] = 0 and U[j] = 1 from the centre
+// (j = 100) on by definition.  The right gain of pan q is U[100 + q], the left one U[100 - q].
+inline void ms_gains(float* U) {
+    for (int j = 0; j <= 2 * MS_MAX_PAN; ++j)
+        U[j] = j == 0 ? 0.f : j >= MS_MAX_PAN ? 1.f : (float)std::min(1.0, std::sqrt(2.0) * std::sin((double)j * M_PI / 400.0));
+}
+// The channels of the bed's two sides: channel = -1 takes channels 0 and 1 (a mono file: 0 twice), channel = k takes k twice.
+// Where both sides name one channel the bed is the mono bed of the mix stage with `channel` as it was given.
+struct MsSides { int ch[2] = {0, 0}; bool same = true; };
+inline MsSides ms_sides(int channel, int channels) {
+    MsSides s;
+    if (channel == -1) s.ch[1] = channels >= 2 ? 1 : 0;
+    else s.ch[0] = s.ch[1] = channel;         // (a channel the intake refuses is refused there, as the mix stage's is)
+    s.same = s.ch[0] == s.ch[1];
+    return s;
+}
+
+// (min_n: 1 for the mix stage; 0 for the live mix stage, whose programme may be empty.  pans: the stereo mix stage's region
+// table, judged behind the rate and n)
+inline const char* mx_check(const MxArgs& a, bool* too_long, long long min_n = 1, const MsTable* pans = nullptr) {
     int L, M, K;
     *too_long = false;
     if (const char* e = rs_design(a.rate, &L, &M, &K, nullptr)) return e;
     if (a.n < min_n) return min_n >= 1 ? "n must be at least 1" : "n must be >= 0";
+    if (pans)
+        if (const char* e = ms_check(*pans, a.n)) return e;
     if (!lv_ok(a.bed_loudness)) return "bed_loudness neither 0 nor in [-5000, -500] hundredths of a LUFS";
     if (a.depth < 0 || a.depth > MX_MAX_DEPTH) return "depth outside [0, 6000] hundredths of a dB";
     if (!(a.threshold >= 0.f)) return "threshold must be >= 0";   // (refuses a NaN too)

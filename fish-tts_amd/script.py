@@ -23,6 +23,7 @@ class Line(NamedTuple):
     loudness: Optional[float] = None   # LUFS target of this line; None: the call's
     volume: float = 0.0                # dB, added to the effective target
     pause: Optional[float] = None      # s of silence before the line; None: line_pause
+    pan: Optional[float] = None        # [-1, 1], -1 hard left (stereo=True alone); None: the voice's in `pans`, else the centre
 
 
 class ScriptPlan(NamedTuple):
@@ -34,6 +35,35 @@ class ScriptPlan(NamedTuple):
     jp: JoinParams
     rate: int                          # the output rate (Hz)
     n_lines: int
+    pans: Optional[List[int]] = None   # stereo: every line's pan in hundredths, -100 hard left (the stereo mix stage's)
+
+
+MAX_PAN_REGIONS = 4096                 # ft_codec_mix_stereo
+
+
+def native_pan(name: str, v) -> int:
+    """round(100 pan) of a pan in [-1, 1]; ValueError for anything else (a bool, a NaN)."""
+    if isinstance(v, bool) or not isinstance(v, Real) or not -1.0 <= float(v) <= 1.0:       # (a nan fails)
+        raise ValueError(f"{name} must be a number in [-1, 1] (-1 hard left), got {v!r}")
+    return int(round(100.0 * float(v)))
+
+
+def pan_regions(pans: Sequence[int], marks: Sequence) -> List[Tuple[int, int, int]]:
+    """The stereo mix stage's regions (a, e, pan) from every line's pan and its mark (line_marks, before a bed's lead is
+    added): one per line that has audio and a pan other than 0; a line's region is merged into that of the line before it where
+    both have the same pan (the silence between them goes along, and a line without audio separates nothing)."""
+    out: List[Tuple[int, int, int]] = []
+    before = 0                          # the pan of the last line that had audio
+    for pan, m in zip(pans, marks):
+        if m is None or m[1] <= m[0]:
+            continue
+        if pan != 0:
+            if out and before == pan:
+                out[-1] = (out[-1][0], int(m[1]), pan)
+            else:
+                out.append((int(m[0]), int(m[1]), pan))
+        before = pan
+    return out
 
 
 def _samples(ms: int, rate: int) -> int:
@@ -42,15 +72,18 @@ def _samples(ms: int, rate: int) -> int:
 
 def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, paragraph_pause=0.5,
                 line_pause=0.4, silence_db: Optional[float] = -45.0, max_chars: int = 200, min_chars: int = 24,
-                sample_rate: Optional[int] = None, speed=None, pitch=None, loudness=None) -> ScriptPlan:
+                sample_rate: Optional[int] = None, speed=None, pitch=None, loudness=None, stereo: bool = False,
+                pans: Optional[Dict[str, float]] = None) -> ScriptPlan:
     """Every check of a script - `lines` a list of Line, or an SSML string (parse_ssml) - and its segments.  Each line is
     split on its own (split_text) and its segments inherit its voice and its output stages: `speed`, `pitch` and `loudness` are the line's, or the call's where the line has None; the
     line's `volume` (dB) is added to that loudness target, which must then exist and stay in [-50, -5].  Every value is
     judged by OutputFx.of, the code that judges it for every other call.  Gaps: inside a line `pause`, or `paragraph_pause`
     after a paragraph break, as join_params gives them; the first segment of a line takes the line's `pause`, or
     `line_pause` (the same range and rounding: [0, 5] s, whole milliseconds) - the join drops the gap before the script's
-    first audio, as ever.  ValueError: no line, a line that is no Line or has nothing to speak, a voice that `voices` does not
-    hold, a bad value anywhere."""
+    first audio, as ever.  `stereo`: every line gets a place - its `pan`, else its voice's in `pans` (voice name -> pan),
+    else the centre - as ScriptPlan.pans; without it a `pan` or `pans` is refused.  ValueError: no line, a line that is no Line
+    or has nothing to speak, a voice that `voices` does not hold, a bad value anywhere, a `pans` key that is no voice of the
+    call, more than 4096 runs of lines at one place other than the centre."""
     from .codec_engine import OutputFx
     if isinstance(lines, str):
         lines = parse_ssml(lines)
@@ -64,13 +97,28 @@ def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, para
         raise ValueError("an empty script: no line to speak")
     if voices is not None and not isinstance(voices, dict):
         raise ValueError("voices must be a dict of name -> list of VoiceProfile")
-    plan = ScriptPlan([], [], [], [], [], jp, rate, len(lines))
+    if not isinstance(stereo, bool):
+        raise ValueError(f"stereo must be True or False, got {stereo!r}")
+    if pans is not None:
+        if not stereo:
+            raise ValueError("pans needs stereo=True: a mono piece has no left and right")
+        if not isinstance(pans, dict):
+            raise ValueError("pans must be a dict of voice name -> pan")
+        for name in pans:
+            if voices is None or name not in voices:
+                raise ValueError(f"pans: {name!r} is no voice of this call")
+        pans = {name: native_pan(f"pans[{name!r}]", v) for name, v in pans.items()}
+    plan = ScriptPlan([], [], [], [], [], jp, rate, len(lines), [] if stereo else None)
     for j, ln in enumerate(lines):
         if not isinstance(ln, Line):
             raise ValueError(f"line {j}: expected a Line, got {type(ln).__name__}")
         if ln.voice is not None and (voices is None or ln.voice not in voices):
             raise ValueError(f"line {j}: unknown voice {ln.voice!r}" +
                              (f" (voices: {sorted(map(str, voices))})" if voices else " (no voices were given)"))
+        if ln.pan is not None and not stereo:
+            raise ValueError(f"line {j}: pan={ln.pan!r} needs stereo=True (the streams are mono)")
+        if stereo:
+            plan.pans.append(native_pan(f"line {j}: pan", ln.pan) if ln.pan is not None else (pans or {}).get(ln.voice, 0))
         target = loudness if ln.loudness is None else ln.loudness
         if isinstance(ln.volume, bool) or not isinstance(ln.volume, Real) or not math.isfinite(float(ln.volume)):
             raise ValueError(f"line {j}: volume must be a number of dB, got {ln.volume!r}")
@@ -92,6 +140,10 @@ def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, para
             plan.voices.append(ln.voice)
             plan.fx.append(fx)
             plan.gaps.append(first if k == 0 else pgap if seg.paragraph else gap)
+    if stereo:
+        runs = sum(1 for j, q in enumerate(plan.pans) if q != 0 and (j == 0 or plan.pans[j - 1] != q))
+        if runs > MAX_PAN_REGIONS:
+            raise ValueError(f"{runs} pan regions after merging: the stereo mix stage takes {MAX_PAN_REGIONS} (split the script)")
     return plan
 
 

@@ -25,6 +25,7 @@ class SegmentPlan(NamedTuple):
                                        # ft_codec_decode_join_items)
     line_of: Optional[List[int]] = None   # a script: the line every segment came from (its marks) ...
     n_lines: int = 0                   # ... and the number of its lines
+    pans: Optional[List[int]] = None   # a stereo call: every line's pan in hundredths (a long text is one line); None: mono
 
     def fx_of(self, first: int = 0, end: Optional[int] = None) -> dict:
         """decode_join's keywords for the output stages of segments first .. end - 1."""
@@ -151,7 +152,10 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None)
     """(audio, cuts) of the whole call: the codes from serve_(srv) while a BatchServer srv = server() is open (None: there
     is none), else from generate_(emit, stopped); one decode_join, under the server's codec lock when it served them.
     `bed`: (clip, mix.MixParams) - the joined piece then goes through the mix stage (vocoder.mix) under the same lock, and
-    `audio` is the mixed piece: `lead` samples longer in front, `tail` behind (the cuts are the join's own)."""
+    `audio` is the mixed piece: `lead` samples longer in front, `tail` behind (the cuts are the join's own).  A plan with
+    `pans` goes through the stereo mix stage instead (vocoder.mix_stereo), with or without a bed: the regions are the lines'
+    marks from the cuts (script.pan_regions), and `audio` is (N, 2)."""
+    from .script import line_marks, pan_regions
     srv = server()
     codes = codes_served(srv, serve_)
     lock = contextlib.nullcontext() if codes is None else srv.codec_lock
@@ -161,7 +165,12 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None)
         codes = [got[i] for i in range(len(plan.texts))]
     with lock:
         audio, cuts = vocoder.decode_join(codes, params=plan.jp, gaps=plan.gaps, **plan.fx_of())
-        if bed is not None and len(audio):
+        if plan.pans is not None and len(audio):
+            found = [None] * len(plan.pans)
+            line_marks(plan.line_of if plan.line_of is not None else [0] * len(plan.texts), plan.gaps, cuts, found)
+            audio, _ = vocoder.mix_stereo(audio, None if bed is None else bed[0], pan_regions(plan.pans, found),
+                                          sample_rate=plan.rate, params=None if bed is None else bed[1])
+        elif bed is not None and len(audio):
             audio, _ = vocoder.mix(audio, bed[0], sample_rate=plan.rate, params=bed[1])
     if not len(audio):
         raise RuntimeError("No audio generated")

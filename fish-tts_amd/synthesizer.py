@@ -531,18 +531,25 @@ class FishTTS:
 
     # ------------------------------------------------------------------ long texts (extension)
     def _long_plan(self, text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
-                   loudness=None):
+                   loudness=None, stereo: bool = False, pan=0.0):
         """Every check of a long-text call, before any device work: its segments.SegmentPlan - every segment in the call's
-        voice, one chain of output stages for all.  ValueError for a bad value."""
+        voice, one chain of output stages for all; with `stereo` the piece is one line at `pan`.  ValueError for a bad
+        value, a `stereo` that is no bool, a pan without stereo."""
         from .longform import join_params, split_text
+        from .script import native_pan
         from .segments import SegmentPlan
+        if not isinstance(stereo, bool):
+            raise ValueError(f"stereo must be True or False, got {stereo!r}")
+        place = native_pan("pan", pan)
+        if place != 0 and not stereo:
+            raise ValueError(f"pan={pan!r} needs stereo=True (the streams are mono)")
         fx = _output_fx(sample_rate, speed, pitch, loudness)
         jp, gap, pgap = join_params(fx.rate, pause, paragraph_pause, silence_db)
         segs = split_text(text, max_chars, min_chars)
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         return SegmentPlan([s.text for s in segs], [None] * len(segs), [pgap if s.paragraph else gap for s in segs], tuple(jp),
-                           fx.wav_rate, fx)
+                           fx.wav_rate, fx, pans=[place] if stereo else None)
 
     def _segment_calls(self, plan, references, sampling, seed: int):
         """The keyword arguments of segments.join_wav / join_chunks for a checked call: the vocoder, the open BatchServer
@@ -570,7 +577,7 @@ class FishTTS:
                         pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                         max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                         speed: Optional[float] = None, pitch: Optional[float] = None,
-                        loudness: Optional[float] = None, bed=None) -> bytes:
+                        loudness: Optional[float] = None, bed=None, stereo: bool = False, pan: float = 0.0) -> bytes:
         """Extension: a text of any length -> one WAV.  The text is split into segments of at most `max_chars` bytes at
         sentence ends (longform.split_text; pieces below `min_chars` join a neighbour), every segment is an utterance of
         its own - `max_tokens` frames at most each, segment i drawing with seed + i - and all of them run as ONE lock-step
@@ -585,13 +592,15 @@ class FishTTS:
         segment is levelled to the target on its own, before the join - the sentences of the document then stand at one
         level, and `silence_db` is judged on the levelled samples.  While a BatchServer is open the segments
         join its batch.  `bed` (a mix.Bed): music or room tone under the joined piece, ducked where it speaks (the mix
-        stage, CodecHipEngine.mix; bed=None: the call as it always was).  ValueError before any device work: pause /
+        stage, CodecHipEngine.mix; bed=None: the call as it always was).  `stereo`: a two-channel WAV - the voice at `pan`
+        in [-1, 1], -1 hard left, over the bed's own left and right (the stereo mix stage, CodecHipEngine.mix_stereo; with
+        or without a bed).  ValueError before any device work: a pan without stereo or outside [-1, 1], pause /
         paragraph_pause outside [0, 5] s, silence_db outside
         [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch /
         loudness, a bad value in `bed` or a bed file the intake does not read."""
         from . import segments
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
-                               loudness)
+                               loudness, stereo, pan)
         mixed = self._bed_args(bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         audio, _ = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed)
@@ -639,11 +648,14 @@ class FishTTS:
         self._vocoder._intake_args("bed", [clip], (0.0, 1, 0, 0), None, bed.channel)
         return clip, mp
 
-    def mix(self, wav_bytes: bytes, bed, silence_db: Optional[float] = None, report: Optional[list] = None) -> bytes:
+    def mix(self, wav_bytes: bytes, bed, silence_db: Optional[float] = None, report: Optional[list] = None,
+            stereo: bool = False) -> bytes:
         """Extension: a finished 16-bit mono WAV - at 44.1 kHz or any rate `sample_rate=` takes - with `bed` (a mix.Bed)
         under it -> one WAV at the same rate, `lead` + `tail` longer (the mix stage, CodecHipEngine.mix).  `silence_db`:
         what counts as speech where the Bed has no threshold_db (None: -45).  `report`: a list that receives the
-        MixReport.  ValueError before any device work: not 16-bit mono, no sample, an unsupported rate, a bad Bed."""
+        MixReport.  `stereo`: a two-channel WAV - the programme (still mono) in the centre over the bed's own left and
+        right (CodecHipEngine.mix_stereo).  ValueError before any device work: not 16-bit mono, no sample, an unsupported
+        rate, a bad Bed."""
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         with wave.open(io.BytesIO(wav_bytes), "rb") as wf:
@@ -653,20 +665,25 @@ class FishTTS:
             audio = np.frombuffer(wf.readframes(wf.getnframes()), dtype=np.int16).astype(np.float32) / 32768.0
         if not len(audio):
             raise ValueError("mix: the WAV holds no sample")
+        if not isinstance(stereo, bool):
+            raise ValueError(f"mix: stereo must be True or False, got {stereo!r}")
         rate = _output_fx(rate, None, None).wav_rate            # (ValueError for a rate the output stages do not take)
         if bed is None:
             raise ValueError("mix: a Bed is needed")
         clip, mp = self._bed_args(bed, rate, silence_db)
         srv = getattr(self, "_server", None)
         with (srv.codec_lock if srv is not None else contextlib.nullcontext()):   # the server's codec worker shares the codec context
-            y, rep = self._vocoder.mix(audio, clip, sample_rate=rate, params=mp)
+            if stereo:
+                y, rep = self._vocoder.mix_stereo(audio, clip, (), sample_rate=rate, params=mp)
+            else:
+                y, rep = self._vocoder.mix(audio, clip, sample_rate=rate, params=mp)
         if report is not None:
             report.append(rep)
         return self._to_wav_bytes(y, rate)
 
     # ------------------------------------------------------------------ scripts (extension)
     def _script_plan(self, lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
-                     sample_rate, speed, pitch, loudness, marks):
+                     sample_rate, speed, pitch, loudness, marks, stereo: bool = False, pans=None):
         """Every check of a script call, before any device work: its segments.SegmentPlan, from script.plan_script - every
         segment with its line's references (None where it speaks in the call's voice) and its line's own chain of output
         stages.  ValueError for a bad value, an unknown voice, or more voices than the prefix cache holds: the cache frees
@@ -676,7 +693,7 @@ class FishTTS:
         if marks is not None and not isinstance(marks, list):
             raise ValueError(f"marks must be None or a list, got {type(marks).__name__}")
         plan = plan_script(lines, voices, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
-                           sample_rate, speed, pitch, loudness)
+                           sample_rate, speed, pitch, loudness, stereo, pans)
         used = []
         for v in plan.voices:
             if v is not None and v not in used:
@@ -696,14 +713,15 @@ class FishTTS:
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         return SegmentPlan(plan.texts, [None if v is None else list(voices[v]) for v in plan.voices], plan.gaps,
-                           tuple(plan.jp), plan.rate, plan.fx, plan.line_of, plan.n_lines)
+                           tuple(plan.jp), plan.rate, plan.fx, plan.line_of, plan.n_lines, plan.pans)
 
     def synthesize_script(self, lines, voices=None, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                           top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
                           pause: float = 0.2, paragraph_pause: float = 0.5, line_pause: float = 0.4,
                           silence_db: Optional[float] = -45.0, max_chars: int = 200, min_chars: int = 24,
                           sample_rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None,
-                          loudness: Optional[float] = None, marks: Optional[list] = None, bed=None) -> bytes:
+                          loudness: Optional[float] = None, marks: Optional[list] = None, bed=None, stereo: bool = False,
+                          pans: Optional[dict] = None) -> bytes:
         """Extension: a script - a dialogue, a narrated piece with quoted speakers - as one WAV.  `lines`: a list of
         script.Line (text, voice, speed, pitch, loudness, volume, pause), or an SSML string (script.parse_ssml: speak, p, s,
         voice, break, prosody); `voices`: name -> list of VoiceProfile.  Every line is split as synthesize_long splits a text
@@ -717,13 +735,16 @@ class FishTTS:
         (start_sample, end_sample) per line at the output rate, from the join's cuts and gaps.  A script of one plain Line
         is synthesize_long of its text, byte for byte.  While a BatchServer is open the segments join its batch.
         `bed` (a mix.Bed): as synthesize_long's; `marks` then count from the start of the mixed piece (the join's marks plus
-        the bed's `lead` in samples).
-        ValueError before any device work: no line, an unknown voice, a bad value in a line or in the call, a bad
+        the bed's `lead` in samples).  `stereo`: a two-channel WAV - every line at its place, its `pan` or else its voice's
+        in `pans` (voice name -> pan in [-1, 1], -1 hard left) or else the centre, over the bed's own left and right (the
+        stereo mix stage, CodecHipEngine.mix_stereo, with or without a bed; the lines' marks are its regions); `marks` count
+        frames.  ValueError before any device work: a pan or `pans` without stereo, a pan outside [-1, 1], a `pans` key that
+        is no voice of the call, no line, an unknown voice, a bad value in a line or in the call, a bad
         line_pause, more distinct voices than the reference cache holds (8; not with cache_reference_kv=False)."""
         from . import segments
         from .script import line_marks
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
-                                 min_chars, sample_rate, speed, pitch, loudness, marks)
+                                 min_chars, sample_rate, speed, pitch, loudness, marks, stereo, pans)
         mixed = self._bed_args(bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         audio, cuts = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed)
@@ -1025,11 +1046,15 @@ class FishTTS:
 
     @staticmethod
     def _to_wav_bytes(audio: np.ndarray, sample_rate: int = 44100) -> bytes:
+        """A 16-bit WAV: mono, or - from an (N, 2) array, left then right - two interleaved channels."""
+        stereo = getattr(audio, "ndim", 1) == 2
+        if stereo and audio.shape[1] != 2:
+            raise ValueError(f"a two-channel waveform is (N, 2), got {audio.shape}")
         audio = np.clip(audio, -1.0, 1.0)
-        audio_int16 = (audio * 32767).astype(np.int16)
+        audio_int16 = np.ascontiguousarray((audio * 32767).astype(np.int16))
         buffer = io.BytesIO()
         with wave.open(buffer, "wb") as wf:
-            wf.setnchannels(1)
+            wf.setnchannels(2 if stereo else 1)
             wf.setsampwidth(2)
             wf.setframerate(sample_rate)
             wf.writeframes(audio_int16.tobytes())

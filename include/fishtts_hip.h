@@ -613,6 +613,55 @@ ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_ra
 ft_status ft_mix_plan(int32_t sample_rate, int64_t n, int64_t lead, int64_t tail, int64_t* N, int32_t* hop, int64_t* nodes);
 /* Host only: T[0 .. 6000]. */
 ft_status ft_mix_gains(float* table);
+/* Stereo mix.  The mix stage with two channels out: the mono programme panned region by region - the lines of a script, each
+ * at its speaker's place - and the two sides of the bed kept apart: codec -> ... -> join -> stereo mix.  Mix, its bits and its
+ * refusals stay as they are; what this paragraph does not state is Mix's.  Stated, which fixes every bit of the result:
+ *   Inputs: the programme x[0 .. n) as for ft_codec_mix; R pan regions, 0 <= R <= 4096, ft_pan_region {a, e, pan} each with
+ *   0 <= a < e <= n, e_r <= a_r+1 (sorted, disjoint; they may touch) and pan in [-100, 100], -100 hard left; one bed item, or
+ *   NULL; ft_mix_params with Mix's fields, checks and check order.  q(i) is the pan of the region that holds i - lead, 0 where
+ *   none does.
+ *   Pan table: U[j] = (float) min(1, sqrt(2) sin(j pi / 400)) for j = 0 .. 200, float64 rounded once; U[0] = 0 and U[j] = 1 for
+ *   j >= 100 by definition (ft_pan_gains).  The right gain of pan q is P_1(q) = U[100 + q], the left one P_0(q) = U[100 - q]:
+ *   constant power (P_0^2 + P_1^2 = 2 sin^2 + 2 cos^2 below the clamp) normalised to the centre, so that no gain exceeds 1 - a
+ *   levelled voice keeps its ceiling - and a centred voice is the mono programme itself.
+ *   Programme: s_c[i] = x[i - lead] P_c(q(i)), one float32 product, inside [lead, lead + n), +0.0 outside it.
+ *   Bed sides: with mp->channel = -1 side 0 is channel 0 and side 1 is channel 1 of a file with two or more channels, channel 0
+ *   of a mono file; with mp->channel = k both sides are channel k.  Where both sides name one channel the bed is Mix's mono bed
+ *   for the same item and mp, bit for bit, level included, prepared once.  Else side c at 44100 Hz is, bit for bit, the piece
+ *   ft_codec_intake gives for the item with channel = c, jp = (0, 1, 0, 0) and loudness 0.
+ *   Pair level (only with bed_loudness != 0 and two different sides): e_h = e_h(side 0) + e_h(side 1), one float64 addition
+ *   per hop of the level stage's own hop sums (the BS.1770 channel weights of left and right are 1), p = the larger of the
+ *   two peaks; then the blocks, both gates, L and g exactly as the level stage states them for one item of n44 samples with
+ *   those sums, and every sample of both sides is multiplied once by that one g in float32.  info->bed.level is the pair's.
+ *   Each side then goes through resample_kernel on its own, from zero state, as in Mix; nb is common to both.
+ *   Timeline, activity, D_k, g_k: Mix's, from the mono x - identical to ft_codec_mix for the same x and mp.
+ *   Sample: m_c[i] is Mix's sample rule over s_c and b_c (the bed rule over side c): the fades, gd, every product and the sum
+ *   rounded on its own.  Without a bed t = +0.0 and the rule runs as stated (nb = 0, info->bed zeroed; mp is still checked).
+ *   Ceiling: pk = max |m_c| over both channels (a NaN is never the peak); one sg for both.
+ *   Output: y[2 i + c], interleaved; capacity and *total count frames.
+ *   It follows: with every q = 0 and equal sides y[2 i] = y[2 i + 1] = ft_codec_mix's y[i], bit for bit; with bed_loudness = 0
+ *   channel c is, up to the ceiling, the mono call with channel = c over the programme s_c; a call repeated gives the same
+ *   bits (no floating-point atomics).
+ *   Reported: ft_mix_info as Mix reports it (N, nb, Nh in frames; pk, sg over both channels); with two different sides
+ *   info->bed is side 0's ft_intake_info with the counters of both sides added and the pair's level (measured without a
+ *   target too).
+ * Limits and refusals: Mix's, in Mix's order, with the regions judged behind the rate and n: a null table with R > 0, R
+ * outside [0, 4096], a region out of order or outside [0, n), a pan outside [-100, 100] (FT_ERR_ARG each).  Every argument is
+ * checked before any device work and a refused call changes nothing.
+ * On the device: Mix's buffers, the bed buffer holding both sides (each on a 16-byte boundary) and the output 2 N floats; the
+ * pan table and the call's regions.  Launches beyond the bed's preparation: mix_hop_kernel and mix_node_kernel as they are,
+ * mix_stereo_kernel (the sample rule for both channels and the peak; the regions that meet a workgroup's span found once per
+ * workgroup and kept in LDS), mix_scale_kernel over the 2 N floats when the ceiling binds; for the pair level
+ * level_pair_kernel, level_gain_kernel and level_pair_scale_kernel behind the intake's own launches. */
+typedef struct ft_pan_region {
+    int64_t a, e;
+    int32_t pan, reserved;
+} ft_pan_region;
+ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_pan_region* regions, int32_t R,
+                              const ft_intake_item* bed, const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total,
+                              int32_t* duck, ft_mix_info* info);
+/* Host only: U[0 .. 200]. */
+ft_status ft_pan_gains(float* table);
 /* Live mix.  The mix stage on a stream: synthesize_long_stream and synthesize_script_stream hand out audio before the piece
  * ends, and the one gain of Mix's ceiling is known only there.  Everything in Mix before the ceiling is local in time, so this
  * second stage keeps it as it is and replaces the one gain by a look-ahead limiter with the duck's own cone shape, driven by
