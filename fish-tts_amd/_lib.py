@@ -187,6 +187,11 @@ SYMBOLS = {
     "ft_codec_mix_stream_begin": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), C.POINTER(_P)]),
     "ft_codec_mix_stream_push": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P]),
     "ft_codec_mix_stream_end": (None, [_P]),
+    "ft_codec_mix_live_stereo": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.POINTER(ft_intake_item),
+                                             C.POINTER(ft_mix_params), _P, C.c_int64, _P, _P, _P, C.POINTER(ft_mix_live_info)]),
+    "ft_codec_mix_stream_begin_stereo": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params),
+                                                     C.POINTER(_P)]),
+    "ft_codec_mix_stream_push_stereo": (C.c_int32, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "ft_codec_rvq_encode": (C.c_int32, [_P, _P, C.c_int32, _P]),
     "ft_ar_profile_gemv": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_sampling), C.POINTER(C.c_double),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -144,6 +144,52 @@ class MixStream:
         self.close()
 
 
+MAX_PAN_REGIONS = 4096            # per call of ft_codec_mix_stereo, per push of a stereo mix stream
+
+
+def pan_region_table(what: str, regions, n: int):
+    """(ft_pan_region array, R) of `regions` - (a, e, pan) each, integers, sorted and disjoint inside [0, n), pan in
+    [-100, 100] - checked as the stage checks them, before any device work."""
+    regions = [tuple(r) for r in regions]
+    if len(regions) > MAX_PAN_REGIONS:
+        raise ValueError(f"{what}: {len(regions)} pan regions, a call takes {MAX_PAN_REGIONS}")
+    at = 0
+    for r in regions:
+        if len(r) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
+            raise ValueError(f"{what}: a region is three integers (a, e, pan), got {r!r}")
+        a, e, pan = r
+        if not at <= a < e <= n or not -100 <= pan <= 100:
+            raise ValueError(f"{what}: region {r!r} out of order, outside [0, {n}) or its pan outside [-100, 100]")
+        at = e
+    reg = (L.ft_pan_region * max(len(regions), 1))(*[L.ft_pan_region(int(a), int(e), int(pan), 0) for a, e, pan in regions])
+    return reg, len(regions)
+
+
+class StereoMixStream(MixStream):
+    """An open stream of the live stereo mix stage (ft_codec_mix_stream_*_stereo; CodecHipEngine.mix_stream(stereo=True) makes
+    one): push(x, regions) takes the next mono programme samples with the pan regions of that push - (a, e, pan) each,
+    relative to the push - and returns the frames that became final, (frames, 2) float32, left then right."""
+
+    def push(self, x=None, regions=(), final: bool = False) -> np.ndarray:
+        if self._h is None:
+            raise RuntimeError("mix stream: closed")
+        x = np.zeros(0, dtype=np.float32) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        reg, R = pan_region_table("mix stream push", regions, len(x))
+        eng = self._eng
+        done = C.c_int64(0)
+        eng._check(eng.lib.ft_mix_live_plan(self._rate, C.byref(self._mp), self._nin + len(x), 1 if final else 0, C.byref(done),
+                                            None), "ft_mix_live_plan")
+        cap = max(done.value - self._out, 0)
+        y = np.empty((max(cap, 1), 2), dtype=np.float32)
+        n = C.c_int64(0)
+        eng._check(eng.lib.ft_codec_mix_stream_push_stereo(self._h, x.ctypes.data_as(C.c_void_p), len(x), reg, R, 1 if final else 0,
+                                                           y.ctypes.data_as(C.c_void_p), cap, C.byref(n)),
+                   "ft_codec_mix_stream_push_stereo")
+        self._nin += len(x)
+        self._out += n.value
+        return y[:n.value]
+
+
 @dataclass(frozen=True)
 class OutputFx:
     """The output stages of a call, checked: `rate` (Hz), `pct` (speed, percent), `cents` (pitch), `level` (loudness
@@ -901,9 +947,42 @@ class CodecHipEngine:
         rep = MixLiveReport.of(info)
         return (y[:total.value], rep, D, Lk) if nodes else (y[:total.value], rep)
 
-    def mix_stream(self, bed, sample_rate: Optional[int] = None, params=None) -> MixStream:
+    def mix_live_stereo(self, x: np.ndarray, bed, regions=(), sample_rate: Optional[int] = None, params=None, nodes: bool = False):
+        """The live stereo mix stage on a whole mono host waveform (ft_codec_mix_live_stereo): what a stereo mix stream gives
+        for x in one final push - mix_live() with two channels out, x panned by `regions` and the bed's two sides kept apart
+        as in mix_stereo(), one limiter for both channels.  x may be empty; `bed` may be None.  Returns (y, MixLiveReport), or
+        (y, MixLiveReport, D, L) with `nodes`; y is (N, 2) float32, left then right."""
+        rate, items, keep, mp = self._mix_args("mix_live_stereo", bed, sample_rate, params, bedless=True)
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        reg, R = pan_region_table("mix_live_stereo", regions, len(x))
+        N = mp.lead + len(x) + mp.tail
+        nn = -(-N // (rate // 50)) + 1
+        y = np.empty((max(N, 1), 2), dtype=np.float32)
+        D, Lk = np.empty(nn, dtype=np.int32), np.empty(nn, dtype=np.int32)
+        total = C.c_int64(0)
+        info = L.ft_mix_live_info()
+        self._check(self.lib.ft_codec_mix_live_stereo(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, reg, R, items, C.byref(mp),
+                                                      y.ctypes.data_as(C.c_void_p), N, C.byref(total),
+                                                      D.ctypes.data_as(C.c_void_p) if nodes else None,
+                                                      Lk.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)),
+                    "ft_codec_mix_live_stereo")
+        del keep
+        rep = MixLiveReport.of(info)
+        return (y[:total.value], rep, D, Lk) if nodes else (y[:total.value], rep)
+
+    def mix_stream(self, bed, sample_rate: Optional[int] = None, params=None, stereo: bool = False) -> MixStream:
         """A stream of the live mix stage (ft_codec_mix_stream_begin): the bed is prepared here and stays on the device; the
-        MixStream's pushes concatenate to mix_live() of the whole programme, bit for bit, however they are cut."""
+        MixStream's pushes concatenate to mix_live() of the whole programme, bit for bit, however they are cut.  `stereo`: a
+        stream of the live stereo mix stage (ft_codec_mix_stream_begin_stereo) - a StereoMixStream, whose
+        push(x, regions=(), final=False) takes the pan regions of that push, relative to it, and returns (frames, 2) arrays
+        that concatenate to mix_live_stereo(); `bed` may then be None."""
+        if stereo:
+            rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params, bedless=True)
+            h = C.c_void_p()
+            self._check(self.lib.ft_codec_mix_stream_begin_stereo(self._h, rate, items, C.byref(mp), C.byref(h)),
+                        "ft_codec_mix_stream_begin_stereo")
+            del keep
+            return StereoMixStream(self, h, mp, rate)
         rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params)
         h = C.c_void_p()
         self._check(self.lib.ft_codec_mix_stream_begin(self._h, rate, items, C.byref(mp), C.byref(h)), "ft_codec_mix_stream_begin")

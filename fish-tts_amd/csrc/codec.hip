@@ -129,6 +129,8 @@ struct CodecState {
     std::vector<ft_mix_stream*> mix_streams;
     float *ml_x = nullptr, *ml_m = nullptr, *ml_y = nullptr;
     size_t ml_xcap = 0, ml_mcap = 0, ml_ycap = 0;
+    unsigned char* ml_q = nullptr;    // live stereo mix stage: the pan bytes of a push
+    size_t ml_qcap = 0;
     LevelTab* lv_tab = nullptr;
     double* lv_hops = nullptr;
     float *lv_peaks = nullptr, *lv_x = nullptr;
@@ -2840,6 +2842,18 @@ extern "C" ft_status ft_pan_gains(float* table) {
     return FT_OK;
 }
 
+// U on the device: uploaded with the first stereo call.
+static ft_status pan_table(ft_ctx* ctx) {
+    CodecState* s = ctx->codec;
+    if (s->mx_U) return FT_OK;
+    float U[MS_PANS], *u = nullptr;
+    chain::ms_gains(U);
+    FT_TRY(cmalloc(ctx, &u, (size_t)MS_PANS));
+    FT_TRY(cupload(ctx, u, U, sizeof U));
+    s->mx_U = u;
+    return FT_OK;
+}
+
 // The pair level over the two sides of n samples each that intake_run has just left back to back in join_out, their hop sums
 // and peaks back to back in the level stage's buffers (s->mu held): the sums added, one gain toward `target`, both sides
 // scaled by it.  Waits, and leaves the pair's ft_level_info in *out.
@@ -2940,13 +2954,7 @@ extern "C" ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n,
         if (sd.same) side[1] = side[0];
     }
     FT_TRY(mix_table(ctx));
-    if (!s->mx_U) {
-        float U[MS_PANS], *u = nullptr;
-        chain::ms_gains(U);
-        FT_TRY(cmalloc(ctx, &u, (size_t)MS_PANS));
-        FT_TRY(cupload(ctx, u, U, sizeof U));
-        s->mx_U = u;
-    }
+    FT_TRY(pan_table(ctx));
     FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
     FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, (size_t)n));
     FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)(2 * pl.N)));
@@ -3006,7 +3014,11 @@ struct ft_mix_stream {
     chain::MlStage st;
     ft_mix_params mp;
     int rate = RS_FI;
-    float* bed = nullptr;             // the prepared bed at the output rate, nb samples
+    bool stereo = false;              // a stream of the live stereo mix stage: two floats per frame in mc and in what it emits
+    float* bed = nullptr;             // the prepared bed at the output rate, nb samples (stereo: side 0, null without a bed)
+    const float* bed1 = nullptr;      // stereo: side 1, `bed` itself where both sides are one
+    unsigned char* pq[2] = {nullptr, nullptr};   // stereo: the pan bytes of the carried programme, laid out as prog
+    size_t qcap[2] = {0, 0};
     long long nb = 0, off = 0;
     ft_intake_info binfo;
     float *prog[2] = {nullptr, nullptr}, *mc[2] = {nullptr, nullptr};   // the carries: programme, m
@@ -3040,9 +3052,10 @@ static void ml_free(ft_mix_stream* ms, void* p) {
     hipFree(p);
 }
 // A carry copy the next push writes from its first sample on: nothing of it is kept when it has to be larger.
-static ft_status ml_carry(ft_ctx* ctx, ft_mix_stream* ms, float** p, size_t* cap, size_t need) {
+template <typename T>
+static ft_status ml_carry(ft_ctx* ctx, ft_mix_stream* ms, T** p, size_t* cap, size_t need) {
     if (*p && *cap >= need) return FT_OK;
-    float* q = nullptr;
+    T* q = nullptr;
     FT_TRY(ml_malloc(ctx, ms, &q, need));
     ml_free(ms, *p);
     *p = q;
@@ -3170,26 +3183,11 @@ static ft_status ml_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft
     return FT_OK;
 }
 
-// One push (s->mu held).  Everything is judged first; the stream's counters move only when the launches went through.
-static ft_status ml_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, const float* x, int64_t n, bool final, float* y,
-                         int64_t capacity, int64_t* n_out) {
-    CodecState* s = ctx->codec;
-    chain::MlStage& stg = ms->st;
-    if (stg.ended) return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream has had its final push");
-    if (n < 0 || (!x && n > 0) || !n_out) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
-    if (n > chain::MX_MAX_N || stg.s.lead + stg.nin + n + stg.s.tail > chain::MX_MAX_N)
-        return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": lead + n + tail exceeds 2^28 samples");
-    const chain::MlPlan pl = stg.plan(n, final);
-    if (capacity < pl.out || (!y && pl.out > 0)) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below what the push emits");
+// The launch parameters of a push with plan pl (the staged buffers are the context's).
+static MixLiveP ml_fill(CodecState* s, const ft_mix_stream* ms, const chain::MlPlan& pl, bool final) {
+    const chain::MlStage& stg = ms->st;
     const int H = stg.s.H, w = stg.par ^ 1;
     const long long F0 = stg.s.lead + stg.nin, mend0 = stg.mixed * H, mend1 = final ? pl.N : pl.mixed * H;
-    hipStream_t st = s->stream;
-    FT_TRY(ml_hops(ctx, ms, (size_t)pl.hops + 1));
-    FT_TRY(ml_carry(ctx, ms, &ms->prog[w], &ms->pcap[w], (size_t)(pl.F - pl.base) + 4));
-    FT_TRY(ml_carry(ctx, ms, &ms->mc[w], &ms->mcap[w], (size_t)(mend1 - pl.done) + 4));
-    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, (size_t)n + 8));
-    FT_TRY(cgrow(ctx, &s->ml_m, &s->ml_mcap, (size_t)(mend1 - mend0) + 8));
-    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, (size_t)pl.out + 8));
     MixLiveP p;
     memset(&p, 0, sizeof p);
     p.m.x = s->ml_x; p.m.bed = ms->bed; p.m.T = s->mx_T; p.m.act = ms->act; p.m.D = ms->D; p.m.g = ms->g; p.m.y = s->ml_m;
@@ -3209,6 +3207,30 @@ static ft_status ml_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, 
     p.Nend = final ? (int)pl.N : 1 << 30;
     p.xb = p.F0 & ~3; p.pib = p.cb0 & ~3; p.pob = p.cb1 & ~3; p.mb = (int)mend0 & ~3; p.cib = p.out0 & ~3; p.cob = p.out1 & ~3;
     p.cf = (float)chain::lv_ceiling();
+    return p;
+}
+
+// One push (s->mu held).  Everything is judged first; the stream's counters move only when the launches went through.
+static ft_status ml_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, const float* x, int64_t n, bool final, float* y,
+                         int64_t capacity, int64_t* n_out) {
+    CodecState* s = ctx->codec;
+    chain::MlStage& stg = ms->st;
+    if (stg.ended) return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream has had its final push");
+    if (n < 0 || (!x && n > 0) || !n_out) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    if (n > chain::MX_MAX_N || stg.s.lead + stg.nin + n + stg.s.tail > chain::MX_MAX_N)
+        return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": lead + n + tail exceeds 2^28 samples");
+    const chain::MlPlan pl = stg.plan(n, final);
+    if (capacity < pl.out || (!y && pl.out > 0)) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below what the push emits");
+    const int H = stg.s.H, w = stg.par ^ 1;
+    const long long mend0 = stg.mixed * H, mend1 = final ? pl.N : pl.mixed * H;
+    hipStream_t st = s->stream;
+    FT_TRY(ml_hops(ctx, ms, (size_t)pl.hops + 1));
+    FT_TRY(ml_carry(ctx, ms, &ms->prog[w], &ms->pcap[w], (size_t)(pl.F - pl.base) + 4));
+    FT_TRY(ml_carry(ctx, ms, &ms->mc[w], &ms->mcap[w], (size_t)(mend1 - pl.done) + 4));
+    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, (size_t)n + 8));
+    FT_TRY(cgrow(ctx, &s->ml_m, &s->ml_mcap, (size_t)(mend1 - mend0) + 8));
+    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, (size_t)pl.out + 8));
+    const MixLiveP p = ml_fill(s, ms, pl, final);
     if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->ml_x + (p.F0 - p.xb), x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
     const int W = MX_THREADS / 64;
     if (p.h1 > p.h0) mixl_hop_kernel<<<(unsigned)((p.h1 - p.h0 + W - 1) / W), MX_THREADS, 0, st>>>(p);
@@ -3248,6 +3270,7 @@ extern "C" ft_status ft_codec_mix_stream_push(ft_mix_stream* ms, const float* x,
     CodecState* s = ctx->codec;
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
+    if (ms->stereo) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_mix_stream_push: a stereo stream takes ft_codec_mix_stream_push_stereo");
     return ml_push(ctx, "ft_codec_mix_stream_push", ms, x, n, final != 0, y, capacity, n_out);
 }
 
@@ -3281,6 +3304,217 @@ extern "C" ft_status ft_codec_mix_live(ft_ctx* ctx, const float* x, int64_t n, i
     FT_TRY(ml_begin(ctx, fn, sample_rate, bed, mp, &ms));
     int64_t got = 0;
     ft_status r = ml_push(ctx, fn, ms, x, n, true, y, capacity, &got);
+    MixLiveOut out;
+    memset(&out, 0, sizeof out);
+    hipError_t e = hipSuccess;
+    if (r == FT_OK) {
+        const size_t nn = (size_t)pl.hops + 1;
+        hipStream_t st = s->stream;
+        e = hipMemcpyAsync(&out, ms->out, sizeof out, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && duck) e = hipMemcpyAsync(duck, ms->D, nn * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && limit) e = hipMemcpyAsync(limit, ms->L, nn * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
+    }
+    const long long nb = ms->nb;
+    const ft_intake_info binfo = ms->binfo;
+    ml_end(ctx, ms);
+    FT_TRY(r);
+    *total = got;
+    memset(info, 0, sizeof *info);
+    info->N = pl.N; info->nb = nb; info->Nh = pl.hops; info->active = out.active;
+    info->dmax = out.dmax; info->lmax = out.lmax;
+    memcpy(&info->qmax, &out.qmax, sizeof(float));
+    info->bed = binfo;
+    return FT_OK;
+}
+
+// ---- live stereo mix stage (fishtts_hip.h: "Live stereo mix"; mixls_*_kernel in stereo_kernels.h, the per-push region
+// check, the pan words and the buffer sizes in fx_chain.h).  A stereo stream is a mix stream with two sides of the bed, a pan
+// byte carry beside its programme carry and two floats per frame in its m carries and in what it emits.
+static_assert(chain::MLS_WORD == 16 && MS_CENTRE == chain::MS_MAX_PAN, "fx_chain.h and stereo_kernels.h disagree on the pan bytes");
+
+// ml_begin for a stereo stream (s->mu held, mx_check passed): the bed's sides prepared as ft_codec_mix_stereo prepares them,
+// into the stream's own buffer; `bed` may be null.
+static ft_status mls_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* bed, const ft_mix_params* mp,
+                           ft_mix_stream** out) {
+    CodecState* s = ctx->codec;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, rate, 100, 0, &d));
+    FT_HIP(ctx, hipSetDevice(ctx->device));           // (a stream without a bed does not pass through intake_run)
+    hipStream_t st = s->stream;
+    int64_t nb44 = 0, nb = 0, pitch = 0;
+    int sides = 0;
+    bool same = true;
+    ft_intake_info binfo;
+    memset(&binfo, 0, sizeof binfo);
+    if (bed) {
+        const chain::MsSides sd = chain::ms_sides(mp->channel, bed->channels);
+        same = sd.same;
+        sides = same ? 1 : 2;
+        ft_intake_item item[2] = {*bed, *bed};
+        item[0].channel = same ? mp->channel : sd.ch[0];
+        item[1].channel = sd.ch[1];
+        const ft_join_params whole = {0.f, 1, 0, 0};
+        int64_t lens[2] = {0, 0};
+        ft_intake_info bi[2];
+        FT_TRY(intake_run(ctx, fn, sides, item, &whole, same ? mp->bed_loudness : 0, false, nullptr, nullptr, INT64_MAX, lens, bi, true));
+        nb44 = lens[0];
+        if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
+        binfo = bi[0];
+        if (!same) {
+            binfo.clipped += bi[1].clipped;
+            binfo.nonfinite += bi[1].nonfinite;
+            FT_TRY(level_pair(ctx, nb44, mp->bed_loudness, &binfo.level));
+        }
+        FT_TRY(rs_table(ctx, rate, &d.rs));
+        nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
+        pitch = (nb + 3) & ~(int64_t)3;               // side 1 begins on a 16-byte boundary
+        if (!s->rs_seg) FT_TRY(cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS));
+    }
+    FT_TRY(mix_table(ctx));
+    FT_TRY(pan_table(ctx));
+    ft_mix_stream* ms = new ft_mix_stream();
+    ms->owner = ctx;
+    ms->stereo = true;
+    ms->mp = *mp;
+    ms->rate = rate;
+    ms->nb = nb;
+    ms->off = !bed ? 0 : mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
+    if (!bed) ms->mp.loop = 0;                        // (without a bed nothing loops: nb = 0)
+    ms->binfo = binfo;
+    ms->st = chain::MlStage::fresh(ml_shape(rate, mp));
+    s->mix_streams.push_back(ms);
+    RsSeg g[2];                                       // (read by an asynchronous copy: alive until the wait below)
+    ft_status r = FT_OK;
+    if (bed) r = ml_malloc(ctx, ms, &ms->bed, (size_t)(pitch * sides));
+    if (r == FT_OK) r = ml_malloc(ctx, ms, &ms->out, (size_t)1);
+    if (r == FT_OK) r = ml_hops(ctx, ms, 1);
+    for (int c = 0; c < 2 && r == FT_OK; ++c) {
+        r = ml_carry(ctx, ms, &ms->prog[c], &ms->pcap[c], 4);
+        if (r == FT_OK) r = ml_carry(ctx, ms, &ms->pq[c], &ms->qcap[c], 4);
+        if (r == FT_OK) r = ml_carry(ctx, ms, &ms->mc[c], &ms->mcap[c], 8);
+    }
+    hipError_t e = hipSuccess;
+    if (r == FT_OK) {
+        if (bed) {                                    // each side to the output rate, from zero state in one final call
+            for (int c = 0; c < sides; ++c)
+                g[c] = RsSeg{s->join_out + c * nb44, d.K > 0 ? d.rs->w : nullptr, nullptr, nullptr, ms->bed + c * pitch, 0, 0,
+                             (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
+            e = hipMemcpyAsync(s->rs_seg, g, (size_t)sides * sizeof(RsSeg), hipMemcpyHostToDevice, st);
+            const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
+            if (e == hipSuccess) resample_kernel<<<dim3(gx, 1, sides), RS_THREADS, 0, st>>>(s->rs_seg);
+            ms->bed1 = same ? ms->bed : ms->bed + pitch;
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(ms->out, 0, sizeof(MixLiveOut), st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
+    }
+    if (r != FT_OK) {
+        ml_end(ctx, ms);
+        return r;
+    }
+    *out = ms;
+    return FT_OK;
+}
+
+// ml_push for a stereo stream: the regions are the push's own, judged behind n.
+static ft_status mls_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, const float* x, int64_t n, const ft_pan_region* regions,
+                          int32_t R, bool final, float* y, int64_t capacity, int64_t* n_out) {
+    CodecState* s = ctx->codec;
+    chain::MlStage& stg = ms->st;
+    if (stg.ended) return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream has had its final push");
+    if (n < 0 || (!x && n > 0) || !n_out) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
+    if (const char* why = chain::mls_check(pans, n)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
+    if (n > chain::MX_MAX_N || stg.s.lead + stg.nin + n + stg.s.tail > chain::MX_MAX_N)
+        return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": lead + n + tail exceeds 2^28 samples");
+    const chain::MlPlan pl = stg.plan(n, final);
+    if (capacity < pl.out || (!y && pl.out > 0)) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below what the push emits");
+    const int w = stg.par ^ 1;
+    const chain::MlsSizes z = chain::mls_sizes(stg, pl);
+    const long long mend1 = final ? pl.N : pl.mixed * stg.s.H;
+    hipStream_t st = s->stream;
+    FT_TRY(ml_hops(ctx, ms, (size_t)pl.hops + 1));
+    FT_TRY(ml_carry(ctx, ms, &ms->prog[w], &ms->pcap[w], z.prog));
+    FT_TRY(ml_carry(ctx, ms, &ms->pq[w], &ms->qcap[w], z.pans));
+    FT_TRY(ml_carry(ctx, ms, &ms->mc[w], &ms->mcap[w], z.mc));
+    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, z.x));
+    FT_TRY(cgrow(ctx, &s->ml_q, &s->ml_qcap, z.q));
+    FT_TRY(cgrow(ctx, &s->ml_m, &s->ml_mcap, z.m));
+    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, z.y));
+    FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
+    MixLiveSP sp;
+    memset(&sp, 0, sizeof sp);
+    sp.l = ml_fill(s, ms, pl, final);
+    const MixLiveP& p = sp.l;
+    sp.bed1 = ms->bed1; sp.U = s->mx_U; sp.reg = s->mx_reg; sp.qx = s->ml_q; sp.qin = ms->pq[stg.par]; sp.qout = ms->pq[w];
+    sp.R = R; sp.words = (int)chain::mls_words(p.F0, n);
+    if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->ml_x + (p.F0 - p.xb), x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, regions, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
+    const int W = MX_THREADS / 64;
+    if (p.h1 > p.h0) mixl_hop_kernel<<<(unsigned)((p.h1 - p.h0 + W - 1) / W), MX_THREADS, 0, st>>>(p);
+    if (p.kd1 > p.kd0) mixl_node_kernel<<<(unsigned)((p.kd1 - p.kd0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
+    if (sp.words > 0) mixls_pan_kernel<<<(unsigned)((sp.words + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(sp);
+    if (p.q1 > p.q0) mixls_sample_kernel<<<(unsigned)(p.q1 - p.q0), MX_THREADS, 0, st>>>(sp);
+    if (p.kl1 > p.kl0) mixl_limit_kernel<<<(unsigned)((p.kl1 - p.kl0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
+    const long long work = std::max((long long)(pl.out + 1) / 2, std::max(mend1 - pl.done, pl.F - pl.base));
+    if (work > 0) mixls_apply_kernel<<<(unsigned)std::min(4096LL, (work + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(sp);
+    if (pl.out > 0) FT_HIP(ctx, hipMemcpyAsync(y, s->ml_y, (size_t)pl.out * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("live stereo mix launch: ") + hipGetErrorString(e));
+    stg.commit(pl);
+    *n_out = pl.out;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_mix_stream_begin_stereo(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed,
+                                                      const ft_mix_params* mp, ft_mix_stream** out) {
+    const std::string fn = "ft_codec_mix_stream_begin_stereo";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!mp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    bool too_long = false;
+    if (const char* why = chain::mx_check(ml_args(sample_rate, 0, mp), &too_long, 0))
+        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    return mls_begin(ctx, fn, sample_rate, bed, mp, out);
+}
+
+extern "C" ft_status ft_codec_mix_stream_push_stereo(ft_mix_stream* ms, const float* x, int64_t n, const ft_pan_region* regions,
+                                                     int32_t R, int32_t final, float* y, int64_t capacity, int64_t* n_out) {
+    if (!ms) return FT_ERR_ARG;
+    ft_ctx* ctx = ms->owner;
+    if (!ctx || !ctx->codec) return FT_ERR_STATE;      // its context was destroyed
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ms->stereo) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_mix_stream_push_stereo: a mono stream takes ft_codec_mix_stream_push");
+    return mls_push(ctx, "ft_codec_mix_stream_push_stereo", ms, x, n, regions, R, final != 0, y, capacity, n_out);
+}
+
+extern "C" ft_status ft_codec_mix_live_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_pan_region* regions,
+                                              int32_t R, const ft_intake_item* bed, const ft_mix_params* mp, float* y,
+                                              int64_t capacity, int64_t* total, int32_t* duck, int32_t* limit, ft_mix_live_info* info) {
+    const std::string fn = "ft_codec_mix_live_stereo";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if ((!x && n != 0) || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
+    bool too_long = false;
+    if (const char* why = chain::mx_check(ml_args(sample_rate, n, mp), &too_long, 0, &pans))
+        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    const chain::MlPlan pl = chain::ml_plan(ml_shape(sample_rate, mp), n, true);
+    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    ft_mix_stream* ms = nullptr;
+    FT_TRY(mls_begin(ctx, fn, sample_rate, bed, mp, &ms));
+    int64_t got = 0;
+    ft_status r = mls_push(ctx, fn, ms, x, n, regions, R, true, y, capacity, &got);
     MixLiveOut out;
     memset(&out, 0, sizeof out);
     hipError_t e = hipSuccess;

@@ -3,7 +3,8 @@
 // (speed, cents) pair, what each stage can emit after so many input samples, the bookkeeping of a stream's three stages from
 // call to call, and the level stage's K-weighting design, gates and gain; behind the join, the mix stage's timeline, checks,
 // duck and gain table (mx_*; tools/mix_check.cpp drives that block), the stereo mix stage's pan regions, pan table and bed
-// sides (ms_*; tools/stereo_check.cpp) and the live mix stage's emission (ml_*, MlStage; tools/mix_live_check.cpp).
+// sides (ms_*; tools/stereo_check.cpp), the live mix stage's emission (ml_*, MlStage; tools/mix_live_check.cpp) and the live
+// stereo mix stage's per-push regions, pan words and buffer sizes (mls_*; tools/stereo_live_check.cpp).
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
 // are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
@@ -439,6 +440,46 @@ struct MlStage {
         par ^= 1;
     }
 };
+
+// ---- live stereo mix stage (mixls_*_kernel in stereo_kernels.h; fishtts_hip.h states it under "Live stereo mix"): the live
+// mix stage with two channels out.  Its counters are MlStage's and its emission ml_plan's, in frames.  What it adds on the
+// host: the regions of a push, relative to that push, judged by ms_check over the push's n; their place on the timeline (a
+// push that begins at timeline sample F0 = lead + n_in puts its sample j at F0 + j); the pan bytes - pan + 100 per programme
+// sample, 100 outside every region - which a push expands on the device and which roll beside the programme carry in the same
+// layout (timeline index minus a multiple of four); and the sizes of the buffers a push touches, in elements, so that the
+// stream and tools/stereo_live_check.cpp, which walks random cuttings over host buffers of exactly these sizes, agree.
+constexpr int MLS_WORD = 16;                         // pan bytes one lane of the expansion writes, one 16-byte store
+inline const char* mls_check(const MsTable& t, long long n) { return ms_check(t, n); }
+inline MsRegion mls_shift(const MsRegion& g, long long F0) { return MsRegion{g.a + F0, g.e + F0, g.pan, 0}; }
+// The 16-byte words of pan bytes a push of n samples from timeline sample F0 writes: they begin at xb = F0 rounded down to
+// a multiple of four and cover [xb, F0 + n); bytes outside [F0, F0 + n) are written as the centre and never read.
+inline long long mls_words(long long F0, long long n) {
+    return n > 0 ? (F0 + n - (F0 & ~3LL) + MLS_WORD - 1) / MLS_WORD : 0;
+}
+// Word w of that expansion, as mixls_pan_kernel writes it: the regions are the push's own, relative to it.
+inline void mls_expand(const MsTable& t, long long F0, long long n, long long w, unsigned char* out) {
+    const long long xb = F0 & ~3LL;
+    for (int k = 0; k < MLS_WORD; ++k) {
+        const long long j = xb + w * MLS_WORD + k - F0;
+        out[k] = (unsigned char)(MS_MAX_PAN + (j >= 0 && j < n ? ms_pan(t, j) : 0));
+    }
+}
+// Elements a push needs in each buffer (the margins are the layout's: a buffer begins up to three elements before its first
+// sample, and a 16-byte access may end up to three behind its last): the staged push and its pan bytes, the staged m and the
+// output (floats, two per frame), and the three carries the push writes (programme, pan bytes, m - two floats per frame).
+struct MlsSizes { size_t x = 0, q = 0, m = 0, y = 0, prog = 0, pans = 0, mc = 0; };
+inline MlsSizes mls_sizes(const MlStage& st, const MlPlan& p) {
+    MlsSizes z;
+    const long long H = st.s.H, F0 = st.s.lead + st.nin, mend0 = st.mixed * H, mend1 = p.final ? p.N : p.mixed * H;
+    z.x = (size_t)p.in + 8;
+    z.q = (size_t)(mls_words(F0, p.in) * MLS_WORD) + 8;
+    z.m = 2 * ((size_t)(mend1 - mend0) + 8);
+    z.y = 2 * ((size_t)p.out + 4);
+    z.prog = (size_t)(p.F - p.base) + 4;
+    z.pans = (size_t)(p.F - p.base) + 4;
+    z.mc = 2 * ((size_t)(mend1 - p.done) + 4);
+    return z;
+}
 
 // ---- the stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;
 // plan() says how many (nothing changes), the caller builds the stage's segment from the record and the plan, and commit()

@@ -66,6 +66,26 @@ def pan_regions(pans: Sequence[int], marks: Sequence) -> List[Tuple[int, int, in
     return out
 
 
+def push_regions(pans: Sequence[int], line_of: Sequence[int], gaps: Sequence[int], cuts, at: int = 0, started: bool = False,
+                 before: int = 0):
+    """The live stereo mix stage's regions for ONE joined group of a stream - segments of lines `line_of` behind `gaps`, kept
+    as `cuts` says, beginning at sample `at` of the programme with `started` saying whether audio went out before it and
+    `before` the pan of the last line that had audio by then.  The group's marks (line_marks) go through pan_regions; they
+    are then relative to the push: shifted by `at` and clipped to the group.  Where the group's first line with audio sits
+    where `before` did - the line continues from the group before, or follows a line of equal pan - its region begins with
+    the group, so the silence in front of it goes along as pan_regions has it for the whole piece.  The regions of all groups,
+    shifted back and touching ones of equal pan joined, are pan_regions of the final marks.
+    Returns (regions, at, started, before) after the group."""
+    found: list = [None] * len(pans)
+    end, started_after = line_marks(line_of, gaps, cuts, found, at, started)
+    spoken = [j for j in sorted(set(line_of)) if found[j] is not None and found[j][1] > found[j][0]]
+    regions = pan_regions(pans, found)
+    if spoken and regions and pans[spoken[0]] == before != 0:
+        regions[0] = (at, regions[0][1], before)
+    out = [(max(a, at) - at, min(e, end) - at, q) for a, e, q in regions if max(a, at) < min(e, end)]
+    return out, end, started_after, (pans[spoken[-1]] if spoken else before)
+
+
 def _samples(ms: int, rate: int) -> int:
     return (ms * rate + 500) // 1000
 

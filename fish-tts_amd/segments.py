@@ -177,7 +177,8 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None)
     return audio, cuts
 
 
-def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cuts=None, live_bed=None) -> Iterator[bytes]:
+def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cuts=None, live_bed=None,
+                live_stereo: bool = False) -> Iterator[bytes]:
     """The int16 PCM chunks of the segments as they become ready in order: serve_(srv) -> (takes, release) through an open
     BatchServer srv = server() - asked at the first next(), so a stream made before a server opens and read while it is
     open joins its batch - else generate_(emit, stopped) on a thread of its own; every ready run decoded and joined as one
@@ -186,7 +187,11 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
     requests.  `live_bed`: (clip, mix.MixParams) - every joined group then goes through a stream of the live mix stage
     (vocoder.mix_stream, opened at the first next()) under the same lock as its decode_join: what an empty push emits - the
     bed alone, where `lead` is longer than the stage holds back - goes out before any group, then what each group's push
-    emits, then what the final push leaves; the stream is closed when the generator ends or is abandoned."""
+    emits, then what the final push leaves; the stream is closed when the generator ends or is abandoned.  `live_stereo`
+    (the plan then has `pans`): the mixer is a stream of the live stereo mix stage (vocoder.mix_stream(stereo=True)), opened
+    with or without a `live_bed`; every group is pushed with the regions of that group (script.push_regions: the lines'
+    marks from the group's cuts through pan_regions, clipped to the push and in its coordinates), and the chunks are
+    interleaved int16, left then right."""
     import numpy as np
 
     from .longform import ready_prefixes
@@ -223,10 +228,20 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
     feeder.start()
     started = False
     mixer = None
+    if live_stereo:
+        from .script import push_regions
+        if plan.pans is None:
+            raise ValueError("live_stereo needs a plan with pans")
+        line_of = plan.line_of if plan.line_of is not None else [0] * len(plan.texts)
+        place = (0, False, 0)                # where the next group begins, whether audio went out, the pan of the last line heard
     try:
-        if live_bed is not None:
+        if live_bed is not None or live_stereo:
             with lock:
-                mixer = vocoder.mix_stream(live_bed[0], sample_rate=plan.rate, params=live_bed[1])
+                if live_stereo:
+                    mixer = vocoder.mix_stream(None if live_bed is None else live_bed[0], sample_rate=plan.rate,
+                                               params=None if live_bed is None else live_bed[1], stereo=True)
+                else:
+                    mixer = vocoder.mix_stream(live_bed[0], sample_rate=plan.rate, params=live_bed[1])
                 head = mixer.push(None)
             if len(head):
                 yield pcm(head)
@@ -235,7 +250,11 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
             with lock:
                 audio, cuts = vocoder.decode_join(group, params=plan.jp, gaps=plan.gaps[first:end], started=started,
                                                   **plan.fx_of(first, end))
-                out = audio if mixer is None or not len(audio) else mixer.push(audio)
+                if live_stereo:
+                    regions, *place = push_regions(plan.pans, line_of[first:end], plan.gaps[first:end], cuts, *place)
+                    out = mixer.push(audio, regions) if len(audio) else audio
+                else:
+                    out = audio if mixer is None or not len(audio) else mixer.push(audio)
             if on_cuts is not None:
                 on_cuts(first, cuts)
             if len(audio):

@@ -611,7 +611,8 @@ class FishTTS:
                                pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                                max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                                speed: Optional[float] = None, pitch: Optional[float] = None,
-                               loudness: Optional[float] = None, bed=None, live_bed=None) -> Iterator[bytes]:
+                               loudness: Optional[float] = None, bed=None, live_bed=None, live_stereo: bool = False,
+                               live_pan: float = 0.0) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
@@ -622,14 +623,25 @@ class FishTTS:
         every joined group goes through a stream of the live mix stage (CodecHipEngine.mix_stream), which holds the piece
         under -1 dBFS with a look-ahead limiter instead of bed='s one gain and holds back under half a second; with a `lead`
         longer than that the music starts while the first sentence is still generating.  The chunks then concatenate to
-        CodecHipEngine.mix_live over the plain stream's audio.  Its values are checked here, as bed='s are."""
+        CodecHipEngine.mix_live over the plain stream's audio.  Its values are checked here, as bed='s are.
+        `live_stereo`: the stream in stereo - interleaved int16 chunks, the voice at `live_pan` in [-1, 1] (-1 hard left)
+        over the live_bed's own left and right, or without a bed (the live stereo mix stage,
+        CodecHipEngine.mix_stream(stereo=True): one limiter for both channels, so the image stays where it is); where neither
+        ceiling binds the chunks concatenate to synthesize_long(stereo=True, pan=live_pan)'s PCM.  ValueError: a live_pan
+        other than 0 without live_stereo, or outside [-1, 1]."""
         from . import segments
+        from .script import native_pan
         _no_streamed_bed(bed, "synthesize_long_stream", live_bed)
+        if not isinstance(live_stereo, bool):
+            raise ValueError(f"live_stereo must be True or False, got {live_stereo!r}")
+        if native_pan("live_pan", live_pan) != 0 and not live_stereo:
+            raise ValueError(f"live_pan={live_pan!r} needs live_stereo=True: a mono stream has no left and right")
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
-                               loudness)
+                               loudness, live_stereo, live_pan)
         mixed = self._bed_args(live_bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed), live_bed=mixed)
+        return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed), live_bed=mixed,
+                                    live_stereo=live_stereo)
 
     # ------------------------------------------------------------------ music bed (extension)
     def _bed_args(self, bed, rate: int, silence_db=None):
@@ -760,19 +772,30 @@ class FishTTS:
                                  line_pause: float = 0.4, silence_db: Optional[float] = -45.0, max_chars: int = 200,
                                  min_chars: int = 24, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                                  pitch: Optional[float] = None, loudness: Optional[float] = None,
-                                 marks: Optional[list] = None, bed=None, live_bed=None) -> Iterator[bytes]:
+                                 marks: Optional[list] = None, bed=None, live_bed=None, live_stereo: bool = False,
+                                 live_pans: Optional[dict] = None) -> Iterator[bytes]:
         """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
         (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
         byte for byte; no empty chunk is yielded.  `marks` fills as groups go out: a line's entry is added once its last
         segment went out, and in the end the list is synthesize_script's.  The arguments are checked here, at the call.
         `bed` is refused (ValueError): see _no_streamed_bed.  `live_bed` (a mix.Bed): as synthesize_long_stream's; `marks`
-        then count from the start of the mixed piece (the join's marks plus the bed's `lead` in samples)."""
+        then count from the start of the mixed piece (the join's marks plus the bed's `lead` in samples).  `live_stereo`: the
+        stream in stereo - interleaved int16 chunks, every line at its place, its `pan` or else its voice's in `live_pans`
+        (voice name -> pan in [-1, 1], -1 hard left) or else the centre, over the live_bed's own left and right or without a
+        bed (the live stereo mix stage, CodecHipEngine.mix_stream(stereo=True): every joined group is pushed with the regions
+        of its lines, one limiter for both channels); where neither ceiling binds the chunks concatenate to
+        synthesize_script(stereo=True, pans=live_pans)'s PCM; `marks` count frames.  ValueError: `live_pans` without
+        live_stereo; a Line.pan without it stays refused, as a stereo value on a mono stream."""
         from . import segments
         from .script import line_marks
         _no_streamed_bed(bed, "synthesize_script_stream", live_bed)
+        if not isinstance(live_stereo, bool):
+            raise ValueError(f"live_stereo must be True or False, got {live_stereo!r}")
+        if live_pans is not None and not live_stereo:
+            raise ValueError("live_pans needs live_stereo=True: a mono stream has no left and right")
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
-                                 min_chars, sample_rate, speed, pitch, loudness, marks)
+                                 min_chars, sample_rate, speed, pitch, loudness, marks, live_stereo, live_pans)
         mixed = self._bed_args(live_bed, plan.rate, silence_db)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         found = [None] * plan.n_lines
@@ -787,7 +810,7 @@ class FishTTS:
             state["told"] = max(state["told"], done)
 
         return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed),
-                                    on_cuts=None if marks is None else on_cuts, live_bed=mixed)
+                                    on_cuts=None if marks is None else on_cuts, live_bed=mixed, live_stereo=live_stereo)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:

@@ -735,6 +735,57 @@ ft_status ft_codec_mix_stream_push(ft_mix_stream* ms, const float* x, int64_t n,
                                    int64_t* n_out);
 /* Frees the stream (after its context was destroyed: the host handle alone). */
 void ft_codec_mix_stream_end(ft_mix_stream* ms);
+/* Live stereo mix.  The live mix stage with two channels out: a streamed dialogue with its speakers panned and its bed kept in
+ * stereo.  Live mix, Stereo mix, their bits and their refusals stay as they are; what this paragraph does not state is Live
+ * mix's, and what Live mix does not state is Stereo mix's.  Stated, which fixes every bit of the result:
+ *   Inputs: the mono programme x at the output rate, in pushes of any size (0 samples allowed).  Each push carries its own pan
+ *   regions, ft_pan_region {a, e, pan} relative to that push: 0 <= a < e <= n_push, sorted and disjoint (they may touch), pan
+ *   in [-100, 100], 0 <= R <= 4096 per push; a push of 0 samples takes R = 0.  A line that crosses a cut is given as two regions
+ *   of equal pan, one ending a push and one beginning the next.  q(i) is the pan of the region that holds programme sample
+ *   i - lead, 0 where none does.  One bed item, or NULL (a panned stream without music); ft_mix_params with Mix's fields,
+ *   checks and check order.
+ *   Bed: the two sides and the pair level exactly as Stereo mix states them (the sides by mp->channel, one side prepared as
+ *   Mix's bed where both name one channel, else each side from the intake and one gain for the pair), each side through the
+ *   resampler from zero state.  Prepared once, at `begin`, and kept on the device for the life of the stream; nb = 0 is
+ *   FT_ERR_ARG after those launches.  Without a bed t = +0.0, nb = 0 and info->bed is zeroed.
+ *   Timeline, activity, D_k, g_k: Live mix's, from the mono x.
+ *   Sample: s_c[i] = __fmul_rn(x[i - lead], P_c(q(i))) inside [lead, lead + n), +0.0 outside; m_c[i] is Live mix's sample rule
+ *   over s_c and side c of the bed - the fades without the N / 2 clamp, every product and the sum rounded on its own.
+ *   Limiter: linked across the channels, so the image does not move when one channel peaks.  Q_h = max |m_c| over both
+ *   channels of hop h (a NaN is never the peak); one need_h and one L_k as Live mix states them;
+ *   y[2 i + c] = __fmul_rn(m_c[i], f(i)) with Live mix's interpolated factor f, the same for both channels.
+ *   Emission: Live mix's (ft_mix_live_plan), counted in frames; capacity and *n_out count frames.
+ *   Determinism: no floating-point atomics; nothing - no bit and no refusal beyond the per-push limit on R - depends on how the
+ *   pushes were cut, wherever a cut falls in a region: every programme sample carried into a later push keeps its pan.
+ *   It follows: (a) with every pan 0 and both sides one channel y[2 i] = y[2 i + 1] = ft_codec_mix_live's y[i], with the same
+ *   D_k, L_k, need_h and counts; (b) where m never exceeds cf and N >= 2 max(fade_in, fade_out) the output is
+ *   ft_codec_mix_stereo's for the concatenated regions, bit for bit; (c) any cutting gives the one-shot call's bits, each push
+ *   emitting ft_mix_live_plan's count; (d) |y| <= cf up to one rounding on both channels.
+ *   Reported (ft_mix_live_info): as Live mix, N, nb and Nh in frames, qmax over both channels, the bed's info as Stereo mix.
+ * Limits and refusals: Live mix's, in its order, with the regions of a push judged behind the rate and n: a null table with
+ * R > 0, R outside [0, 4096], a region out of order or outside [0, n_push), a pan outside [-100, 100] (FT_ERR_ARG each); a
+ * refused push leaves its stream as it was.  ft_codec_mix_stream_push on a stereo stream and ft_codec_mix_stream_push_stereo
+ * on a mono one are FT_ERR_STATE.  ft_codec_mix_stream_end serves both kinds.
+ * On the device a stereo stream holds both sides of its bed (each on a 16-byte boundary), Live mix's per-hop arrays and three
+ * carries in two copies each: the mono programme not yet mixed, one pan byte (pan + 100) per carried programme sample in the
+ * same layout, and the m not yet emitted, at most 2 La H floats.  Every sample buffer is laid out by the timeline index minus a
+ * multiple of four, so a group of four frames that begins at a multiple of four lies on a 16-byte boundary in the push and in
+ * the programme carry and on a 32-byte boundary in the staged m and the m carry.  Six launches per push whatever its size and
+ * its R, a launch with nothing to do left out: mixl_hop_kernel, mixl_node_kernel, mixls_pan_kernel (the push's regions to one
+ * pan byte per sample), mixls_sample_kernel (m_0, m_1, Q_h, need_h), mixl_limit_kernel, mixls_apply_kernel (y, then the roll of
+ * the three carries). */
+/* The stage on a host waveform, as a stereo stream whose only push is its last: y receives N = lead + n + tail interleaved
+ * frames (capacity >= N frames), *total = N; duck, limit and info as ft_codec_mix_live; bed may be NULL. */
+ft_status ft_codec_mix_live_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_pan_region* regions,
+                                   int32_t R, const ft_intake_item* bed, const ft_mix_params* mp, float* y, int64_t capacity,
+                                   int64_t* total, int32_t* duck, int32_t* limit, ft_mix_live_info* info);
+/* A stereo stream of the stage: prepares the bed's sides (bed may be NULL) and allocates the stream's state. */
+ft_status ft_codec_mix_stream_begin_stereo(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed, const ft_mix_params* mp,
+                                           ft_mix_stream** out);
+/* One push of n >= 0 programme samples with its R regions (relative to the push; regions may be NULL when R = 0).  The frames
+ * that became final are written into y (host, 2 * capacity floats) and their count into *n_out. */
+ft_status ft_codec_mix_stream_push_stereo(ft_mix_stream* ms, const float* x, int64_t n, const ft_pan_region* regions, int32_t R,
+                                          int32_t final, float* y, int64_t capacity, int64_t* n_out);
 
 ft_status ft_sync(ft_ctx* ctx);
 /* State of the persistent frame engine (csrc/frame_engine.h), the batch-1 form of the decode step
