@@ -116,18 +116,25 @@ class MixStream:
         self._nin, self._out = 0, 0
 
     def push(self, x=None, final: bool = False) -> np.ndarray:
+        return self._push(x, None, final)
+
+    def _push(self, x, regions, final: bool) -> np.ndarray:
+        """One push; `regions`: a stereo stream's (None: a mono stream, which has no region table and emits one float per frame)."""
         if self._h is None:
             raise RuntimeError("mix stream: closed")
         x = np.zeros(0, dtype=np.float32) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        stereo = regions is not None
+        table = pan_region_table("mix stream push", regions, len(x)) if stereo else ()
         eng = self._eng
         done = C.c_int64(0)
         eng._check(eng.lib.ft_mix_live_plan(self._rate, C.byref(self._mp), self._nin + len(x), 1 if final else 0, C.byref(done),
                                             None), "ft_mix_live_plan")
         cap = max(done.value - self._out, 0)
-        y = np.empty(max(cap, 1), dtype=np.float32)
+        y = np.empty((max(cap, 1), 2) if stereo else max(cap, 1), dtype=np.float32)
         n = C.c_int64(0)
-        eng._check(eng.lib.ft_codec_mix_stream_push(self._h, x.ctypes.data_as(C.c_void_p), len(x), 1 if final else 0,
-                                                    y.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "ft_codec_mix_stream_push")
+        what = "ft_codec_mix_stream_push_stereo" if stereo else "ft_codec_mix_stream_push"
+        eng._check(getattr(eng.lib, what)(self._h, x.ctypes.data_as(C.c_void_p), len(x), *table, 1 if final else 0,
+                                          y.ctypes.data_as(C.c_void_p), cap, C.byref(n)), what)
         self._nin += len(x)
         self._out += n.value
         return y[:n.value]
@@ -171,23 +178,7 @@ class StereoMixStream(MixStream):
     relative to the push - and returns the frames that became final, (frames, 2) float32, left then right."""
 
     def push(self, x=None, regions=(), final: bool = False) -> np.ndarray:
-        if self._h is None:
-            raise RuntimeError("mix stream: closed")
-        x = np.zeros(0, dtype=np.float32) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-        reg, R = pan_region_table("mix stream push", regions, len(x))
-        eng = self._eng
-        done = C.c_int64(0)
-        eng._check(eng.lib.ft_mix_live_plan(self._rate, C.byref(self._mp), self._nin + len(x), 1 if final else 0, C.byref(done),
-                                            None), "ft_mix_live_plan")
-        cap = max(done.value - self._out, 0)
-        y = np.empty((max(cap, 1), 2), dtype=np.float32)
-        n = C.c_int64(0)
-        eng._check(eng.lib.ft_codec_mix_stream_push_stereo(self._h, x.ctypes.data_as(C.c_void_p), len(x), reg, R, 1 if final else 0,
-                                                           y.ctypes.data_as(C.c_void_p), cap, C.byref(n)),
-                   "ft_codec_mix_stream_push_stereo")
-        self._nin += len(x)
-        self._out += n.value
-        return y[:n.value]
+        return self._push(x, list(regions), final)
 
 
 @dataclass(frozen=True)
@@ -837,33 +828,7 @@ class CodecHipEngine:
         cut to the programme's length, ducked where x is loud, added to x and held under -1 dBFS.  `params`: a
         mix.MixParams (mix.bed_params makes one from a Bed), or None for a default Bed's.  Returns (y, MixReport), or
         (y, MixReport, D) with `nodes`: the duck D_k in hundredths of a dB at the hops + 1 hop borders."""
-        from .mix import Bed, MixParams, bed_params
-        fx = OutputFx.of(sample_rate=sample_rate)
-        rate = fx.wav_rate
-        if params is None:
-            params = bed_params(Bed(b""), rate)
-        if not isinstance(params, MixParams):
-            raise ValueError(f"mix: params must be a MixParams, got {type(params).__name__}")
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-        if len(x) < 1:
-            raise ValueError("mix: an empty programme")
-        items, keep, _, _ = self._intake_args("mix", [bed], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
-        mp = L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
-                             params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
-        N, hop, nn = C.c_int64(0), C.c_int32(0), C.c_int64(0)
-        self._check(self.lib.ft_mix_plan(rate, len(x), params.lead, params.tail, C.byref(N), C.byref(hop), C.byref(nn)), "ft_mix_plan")
-        y = np.empty(N.value, dtype=np.float32)
-        D = np.empty(nn.value, dtype=np.int32)
-        total = C.c_int64(0)
-        info = L.ft_mix_info()
-        self._check(self.lib.ft_codec_mix(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, items, C.byref(mp),
-                                          y.ctypes.data_as(C.c_void_p), N.value, C.byref(total),
-                                          D.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)), "ft_codec_mix")
-        del keep
-        rep = MixReport.of(info)
-        return (y[:total.value], rep, D) if nodes else (y[:total.value], rep)
-
-    MAX_PAN_REGIONS = 4096        # ft_codec_mix_stereo
+        return self._mix_whole("mix", x, bed, None, sample_rate, params, nodes)
 
     def mix_stereo(self, x: np.ndarray, bed, regions=(), sample_rate: Optional[int] = None, params=None, nodes: bool = False):
         """The stereo mix stage on a mono host waveform (ft_codec_mix_stereo): mix() with two channels out.  `regions`:
@@ -871,35 +836,34 @@ class CodecHipEngine:
         disjoint, at most 4096; what no region holds sits in the centre.  `bed`: as mix()'s, its first two channels the two
         sides (a mono file, or a `channel` in params: that channel on both), or None for a panned programme without a bed.
         Returns (y, MixReport), or (y, MixReport, D) with `nodes`; y is (N, 2) float32, left then right."""
-        rate, items, keep, mp = self._mix_args("mix_stereo", bed, sample_rate, params, bedless=True)
+        return self._mix_whole("mix_stereo", x, bed, list(regions), sample_rate, params, nodes)
+
+    def _mix_whole(self, what: str, x, bed, regions, sample_rate, params, nodes: bool):
+        """mix(), and with `regions` (None: mono) mix_stereo(): the plan, the buffers, the call and the report."""
+        stereo = regions is not None
+        rate, items, keep, mp = self._mix_args(what, bed, sample_rate, params, bedless=stereo)
         x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
         if len(x) < 1:
-            raise ValueError("mix_stereo: an empty programme")
-        regions = [tuple(r) for r in regions]
-        if len(regions) > self.MAX_PAN_REGIONS:
-            raise ValueError(f"mix_stereo: {len(regions)} pan regions, a call takes {self.MAX_PAN_REGIONS}")
-        at = 0
-        for r in regions:
-            if len(r) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
-                raise ValueError(f"mix_stereo: a region is three integers (a, e, pan), got {r!r}")
-            a, e, pan = r
-            if not at <= a < e <= len(x) or not -100 <= pan <= 100:
-                raise ValueError(f"mix_stereo: region {r!r} out of order, outside [0, {len(x)}) or its pan outside [-100, 100]")
-            at = e
-        reg = (L.ft_pan_region * max(len(regions), 1))(*[L.ft_pan_region(int(a), int(e), int(pan), 0) for a, e, pan in regions])
+            raise ValueError(f"{what}: an empty programme")
+        table = pan_region_table(what, regions, len(x)) if stereo else ()
         N, hop, nn = C.c_int64(0), C.c_int32(0), C.c_int64(0)
         self._check(self.lib.ft_mix_plan(rate, len(x), mp.lead, mp.tail, C.byref(N), C.byref(hop), C.byref(nn)), "ft_mix_plan")
-        y = np.empty((N.value, 2), dtype=np.float32)
+        y = np.empty((N.value, 2) if stereo else N.value, dtype=np.float32)
         D = np.empty(nn.value, dtype=np.int32)
         total = C.c_int64(0)
         info = L.ft_mix_info()
-        self._check(self.lib.ft_codec_mix_stereo(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, reg, len(regions), items,
-                                                 C.byref(mp), y.ctypes.data_as(C.c_void_p), N.value, C.byref(total),
-                                                 D.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)),
-                    "ft_codec_mix_stereo")
+        fn = "ft_codec_mix_stereo" if stereo else "ft_codec_mix"
+        self._check(getattr(self.lib, fn)(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, *table, items, C.byref(mp),
+                                          y.ctypes.data_as(C.c_void_p), N.value, C.byref(total),
+                                          D.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)), fn)
         del keep
         rep = MixReport.of(info)
         return (y[:total.value], rep, D) if nodes else (y[:total.value], rep)
+
+    @staticmethod
+    def _mix_params(params) -> "L.ft_mix_params":
+        return L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
+                               params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
 
     def _mix_args(self, what: str, bed, sample_rate, params, bedless: bool = False):
         """(rate, bed item array, what keeps its bytes alive, ft_mix_params) of a mix call, checked as mix() checks them.
@@ -913,14 +877,11 @@ class CodecHipEngine:
         items, keep = None, None
         if bed is not None or not bedless:
             items, keep, _, _ = self._intake_args(what, [bed], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
-        mp = L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
-                             params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
-        return rate, items, keep, mp
+        return rate, items, keep, self._mix_params(params)
 
     def mix_live_plan(self, sample_rate: Optional[int], params, n_in: int, final: bool = False):
         """(samples emitted, final limiter nodes) of a mix stream after n_in programme samples (ft_mix_live_plan; host only)."""
-        mp = L.ft_mix_params(params.bed_loudness, params.channel, params.depth, params.threshold, params.attack, params.release,
-                             params.lead, params.tail, params.fade_in, params.fade_out, params.offset, params.loop, 0)
+        mp = self._mix_params(params)
         n, k = C.c_int64(0), C.c_int64(0)
         self._check(self.lib.ft_mix_live_plan(OutputFx.of(sample_rate=sample_rate).wav_rate, C.byref(mp), int(n_in),
                                               1 if final else 0, C.byref(n), C.byref(k)), "ft_mix_live_plan")
@@ -931,41 +892,32 @@ class CodecHipEngine:
         mix()'s bed, duck and sum, held under -1 dBFS by a look-ahead limiter instead of one gain.  x may be empty.  Returns
         (y, MixLiveReport), or (y, MixLiveReport, D, L) with `nodes`: the duck and the limiter's depth in hundredths of a dB at
         the hops + 1 hop borders."""
-        rate, items, keep, mp = self._mix_args("mix_live", bed, sample_rate, params)
-        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-        N = mp.lead + len(x) + mp.tail
-        nn = -(-N // (rate // 50)) + 1
-        y = np.empty(max(N, 1), dtype=np.float32)
-        D, Lk = np.empty(nn, dtype=np.int32), np.empty(nn, dtype=np.int32)
-        total = C.c_int64(0)
-        info = L.ft_mix_live_info()
-        self._check(self.lib.ft_codec_mix_live(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, items, C.byref(mp),
-                                               y.ctypes.data_as(C.c_void_p), N, C.byref(total),
-                                               D.ctypes.data_as(C.c_void_p) if nodes else None,
-                                               Lk.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)), "ft_codec_mix_live")
-        del keep
-        rep = MixLiveReport.of(info)
-        return (y[:total.value], rep, D, Lk) if nodes else (y[:total.value], rep)
+        return self._mix_live("mix_live", x, bed, None, sample_rate, params, nodes)
 
     def mix_live_stereo(self, x: np.ndarray, bed, regions=(), sample_rate: Optional[int] = None, params=None, nodes: bool = False):
         """The live stereo mix stage on a whole mono host waveform (ft_codec_mix_live_stereo): what a stereo mix stream gives
         for x in one final push - mix_live() with two channels out, x panned by `regions` and the bed's two sides kept apart
         as in mix_stereo(), one limiter for both channels.  x may be empty; `bed` may be None.  Returns (y, MixLiveReport), or
         (y, MixLiveReport, D, L) with `nodes`; y is (N, 2) float32, left then right."""
-        rate, items, keep, mp = self._mix_args("mix_live_stereo", bed, sample_rate, params, bedless=True)
+        return self._mix_live("mix_live_stereo", x, bed, list(regions), sample_rate, params, nodes)
+
+    def _mix_live(self, what: str, x, bed, regions, sample_rate, params, nodes: bool):
+        """mix_live(), and with `regions` (None: mono) mix_live_stereo(): the plan, the buffers, the call and the report."""
+        stereo = regions is not None
+        rate, items, keep, mp = self._mix_args(what, bed, sample_rate, params, bedless=stereo)
         x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
-        reg, R = pan_region_table("mix_live_stereo", regions, len(x))
+        table = pan_region_table(what, regions, len(x)) if stereo else ()
         N = mp.lead + len(x) + mp.tail
         nn = -(-N // (rate // 50)) + 1
-        y = np.empty((max(N, 1), 2), dtype=np.float32)
+        y = np.empty((max(N, 1), 2) if stereo else max(N, 1), dtype=np.float32)
         D, Lk = np.empty(nn, dtype=np.int32), np.empty(nn, dtype=np.int32)
         total = C.c_int64(0)
         info = L.ft_mix_live_info()
-        self._check(self.lib.ft_codec_mix_live_stereo(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, reg, R, items, C.byref(mp),
-                                                      y.ctypes.data_as(C.c_void_p), N, C.byref(total),
-                                                      D.ctypes.data_as(C.c_void_p) if nodes else None,
-                                                      Lk.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)),
-                    "ft_codec_mix_live_stereo")
+        fn = "ft_codec_mix_live_stereo" if stereo else "ft_codec_mix_live"
+        self._check(getattr(self.lib, fn)(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, *table, items, C.byref(mp),
+                                          y.ctypes.data_as(C.c_void_p), N, C.byref(total),
+                                          D.ctypes.data_as(C.c_void_p) if nodes else None,
+                                          Lk.ctypes.data_as(C.c_void_p) if nodes else None, C.byref(info)), fn)
         del keep
         rep = MixLiveReport.of(info)
         return (y[:total.value], rep, D, Lk) if nodes else (y[:total.value], rep)
@@ -976,18 +928,12 @@ class CodecHipEngine:
         stream of the live stereo mix stage (ft_codec_mix_stream_begin_stereo) - a StereoMixStream, whose
         push(x, regions=(), final=False) takes the pan regions of that push, relative to it, and returns (frames, 2) arrays
         that concatenate to mix_live_stereo(); `bed` may then be None."""
-        if stereo:
-            rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params, bedless=True)
-            h = C.c_void_p()
-            self._check(self.lib.ft_codec_mix_stream_begin_stereo(self._h, rate, items, C.byref(mp), C.byref(h)),
-                        "ft_codec_mix_stream_begin_stereo")
-            del keep
-            return StereoMixStream(self, h, mp, rate)
-        rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params)
+        rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params, bedless=stereo)
+        fn = "ft_codec_mix_stream_begin_stereo" if stereo else "ft_codec_mix_stream_begin"
         h = C.c_void_p()
-        self._check(self.lib.ft_codec_mix_stream_begin(self._h, rate, items, C.byref(mp), C.byref(h)), "ft_codec_mix_stream_begin")
+        self._check(getattr(self.lib, fn)(self._h, rate, items, C.byref(mp), C.byref(h)), fn)
         del keep                                           # (begin has prepared the bed: its bytes are no longer read)
-        return MixStream(self, h, mp, rate)
+        return (StereoMixStream if stereo else MixStream)(self, h, mp, rate)
 
     MAX_ITEMS_PER_JOIN = 64       # ft_codec_decode_join
 

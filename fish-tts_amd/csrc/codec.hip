@@ -2707,7 +2707,9 @@ extern "C" ft_status ft_codec_encode_items(ft_ctx* ctx, int32_t B, const ft_inta
 }
 
 // ---- mix stage (fishtts_hip.h: ft_codec_mix, ft_mix_plan, ft_mix_gains; the kernels in codec_kernels.h, the checks, the hop
-// and the table in fx_chain.h)
+// and the table in fx_chain.h).  The four mix stages - mix, stereo mix, live mix, live stereo mix - share one host path:
+// mix_args / mix_refuse judge the values, mix_bed prepares the bed, mix_whole is the whole-call walk of the first two,
+// ml_begin / ml_push / ml_live the stream of the last two; `pans` (a region table) is what makes a call or a push stereo.
 static_assert(sizeof(ft_mix_params) == 72 && offsetof(ft_mix_params, lead) == 24 && offsetof(ft_mix_params, loop) == 64, "ft_mix_params layout");
 static_assert(sizeof(ft_mix_info) == 128 && offsetof(ft_mix_info, bed) == 48, "ft_mix_info layout");
 
@@ -2740,91 +2742,6 @@ static ft_status mix_table(ft_ctx* ctx) {
     FT_TRY(cupload(ctx, t, T.data(), T.size() * sizeof(float)));
     FT_TRY(cmalloc(ctx, &s->mx_out, (size_t)1));
     s->mx_T = t;
-    return FT_OK;
-}
-
-extern "C" ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
-                                  const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck, ft_mix_info* info) {
-    const std::string fn = "ft_codec_mix";
-    if (!ctx) return FT_ERR_ARG;
-    FT_TRY(codec_ready(ctx));
-    if (!x || !bed || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
-    chain::MxArgs a;
-    a.rate = sample_rate; a.n = n; a.bed_loudness = mp->bed_loudness; a.depth = mp->depth; a.threshold = mp->threshold;
-    a.attack = mp->attack; a.release = mp->release; a.lead = mp->lead; a.tail = mp->tail; a.fade_in = mp->fade_in;
-    a.fade_out = mp->fade_out; a.offset = mp->offset; a.loop = mp->loop;
-    bool too_long = false;
-    if (const char* why = chain::mx_check(a, &too_long)) return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
-    const chain::MxPlan pl = chain::mx_plan(sample_rate, n, mp->lead, mp->tail);
-    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
-    CodecState* s = ctx->codec;
-    FxDesc d;
-    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d));
-    ft_intake_item item = *bed;
-    item.channel = mp->channel;
-    const ft_join_params whole = {0.f, 1, 0, 0};
-    std::lock_guard<std::mutex> lock(s->mu);
-    // the bed: raw frames -> 44100 Hz, levelled, nothing trimmed (its own checks come before its first device work)
-    int64_t nb44 = 0;
-    ft_intake_info binfo;
-    FT_TRY(intake_run(ctx, fn, 1, &item, &whole, mp->bed_loudness, false, nullptr, nullptr, INT64_MAX, &nb44, &binfo, true));
-    if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
-    hipStream_t st = s->stream;
-    // to the output rate: the whole clip from zero state in one final call
-    FT_TRY(rs_table(ctx, sample_rate, &d.rs));
-    const int64_t nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
-    const float* bedp = s->join_out;
-    RsSeg g;                                          // (read by an asynchronous copy: alive until the call's waits)
-    if (d.K > 0) {
-        if (!s->rs_seg) FT_TRY(cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS));
-        FT_TRY(cgrow(ctx, &s->mx_bed, &s->mx_bedcap, (size_t)nb));
-        g = RsSeg{s->join_out, d.rs->w, nullptr, nullptr, s->mx_bed, 0, 0, (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
-        FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, &g, sizeof g, hipMemcpyHostToDevice, st));
-        const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
-        resample_kernel<<<dim3(gx, 1, 1), RS_THREADS, 0, st>>>(s->rs_seg);
-        bedp = s->mx_bed;
-    }
-    FT_TRY(mix_table(ctx));
-    FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, (size_t)n));
-    FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)pl.N));
-    FT_TRY(cgrow(ctx, &s->mx_act, &s->mx_actcap, (size_t)pl.Nh));
-    FT_TRY(cgrow(ctx, &s->mx_D, &s->mx_Dcap, (size_t)pl.Nh + 1));
-    FT_TRY(cgrow(ctx, &s->mx_g, &s->mx_gcap, (size_t)pl.Nh + 1));
-    MixP p;
-    memset(&p, 0, sizeof p);
-    p.x = s->mx_x; p.bed = bedp; p.T = s->mx_T; p.act = s->mx_act; p.D = s->mx_D; p.g = s->mx_g; p.y = s->mx_y; p.out = s->mx_out;
-    p.nb = nb;
-    p.off = mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
-    p.N = (int)pl.N; p.n = (int)n; p.lead = (int)mp->lead; p.Nh = (int)pl.Nh; p.H = pl.H;
-    p.depth = mp->depth; p.Wa = mp->attack; p.Wr = mp->release;
-    p.f_in = (int)std::min(mp->fade_in, (int64_t)(pl.N / 2)); p.f_out = (int)std::min(mp->fade_out, (int64_t)(pl.N / 2));
-    p.loop = mp->loop; p.thr = mp->threshold;
-    FT_HIP(ctx, hipMemcpyAsync(s->mx_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    FT_HIP(ctx, hipMemsetAsync(s->mx_out, 0, sizeof(MixOut), st));
-    mix_hop_kernel<<<(unsigned)((pl.Nh + MX_THREADS / 64 - 1) / (MX_THREADS / 64)), MX_THREADS, 0, st>>>(p);
-    mix_node_kernel<<<(unsigned)((pl.Nh + 1 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
-    mix_kernel<<<(unsigned)((pl.N + MX_SPAN - 1) / MX_SPAN), MX_THREADS, 0, st>>>(p);
-    MixOut out;
-    FT_HIP(ctx, hipMemcpyAsync(&out, s->mx_out, sizeof out, hipMemcpyDeviceToHost, st));
-    if (duck) FT_HIP(ctx, hipMemcpyAsync(duck, s->mx_D, ((size_t)pl.Nh + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
-    FT_HIP(ctx, hipStreamSynchronize(st));            // the peak decides whether the fourth launch runs
-    float pk, sg = 1.f;
-    memcpy(&pk, &out.pk, sizeof pk);
-    const bool capped = (double)pk > chain::lv_ceiling();
-    if (capped) {
-        sg = (float)(chain::lv_ceiling() / (double)pk);
-        const int gx = (int)std::max(1LL, std::min(4096LL, (pl.N / 4 + MX_THREADS - 1) / MX_THREADS));
-        mix_scale_kernel<<<gx, MX_THREADS, 0, st>>>(s->mx_y, (int)pl.N, sg);
-    }
-    FT_HIP(ctx, hipMemcpyAsync(y, s->mx_y, (size_t)pl.N * sizeof(float), hipMemcpyDeviceToHost, st));
-    FT_HIP(ctx, hipStreamSynchronize(st));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("mix launch: ") + hipGetErrorString(e));
-    *total = pl.N;
-    memset(info, 0, sizeof *info);
-    info->N = pl.N; info->nb = nb; info->Nh = pl.Nh; info->active = out.active;
-    info->dmax = out.dmax; info->capped = capped ? 1 : 0; info->pk = pk; info->sg = sg;
-    info->bed = binfo;
     return FT_OK;
 }
 
@@ -2887,97 +2804,139 @@ static ft_status level_pair(ft_ctx* ctx, int64_t n, int target, ft_level_info* o
     return FT_OK;
 }
 
-extern "C" ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_pan_region* regions,
-                                         int32_t R, const ft_intake_item* bed, const ft_mix_params* mp, float* y, int64_t capacity,
-                                         int64_t* total, int32_t* duck, ft_mix_info* info) {
-    const std::string fn = "ft_codec_mix_stereo";
-    if (!ctx) return FT_ERR_ARG;
-    FT_TRY(codec_ready(ctx));
-    if (!x || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+// ---- what the four mix stages share on the host: the judged values, the prepared bed, the whole-call walk
+static chain::MxArgs mix_args(int rate, int64_t n, const ft_mix_params* mp) {
     chain::MxArgs a;
-    a.rate = sample_rate; a.n = n; a.bed_loudness = mp->bed_loudness; a.depth = mp->depth; a.threshold = mp->threshold;
+    a.rate = rate; a.n = n; a.bed_loudness = mp->bed_loudness; a.depth = mp->depth; a.threshold = mp->threshold;
     a.attack = mp->attack; a.release = mp->release; a.lead = mp->lead; a.tail = mp->tail; a.fade_in = mp->fade_in;
     a.fade_out = mp->fade_out; a.offset = mp->offset; a.loop = mp->loop;
-    const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
+    return a;
+}
+// mx_check's refusal as the entry point `fn` reports it (min_n, pans: as mx_check takes them).
+static ft_status mix_refuse(ft_ctx* ctx, const std::string& fn, int rate, int64_t n, const ft_mix_params* mp, long long min_n,
+                            const chain::MsTable* pans) {
     bool too_long = false;
-    if (const char* why = chain::mx_check(a, &too_long, 1, &pans))
-        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
-    const chain::MxPlan pl = chain::mx_plan(sample_rate, n, mp->lead, mp->tail);
+    const char* why = chain::mx_check(mix_args(rate, n, mp), &too_long, min_n, pans);
+    return why ? ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why) : FT_OK;
+}
+
+template <typename T>
+static ft_status ml_malloc(ft_ctx* ctx, ft_mix_stream* ms, T** p, size_t n);   // (an allocation a mix stream owns: below)
+
+// The bed of a mix call or a mix stream (s->mu held; the bed's own checks come before its first device work): raw frames ->
+// 44100 Hz by the intake launches, nothing trimmed - one side levelled there; with `stereo`, where the file has two, both
+// sides measured as a pair - then each side to the output rate, the whole clip from zero state in one final call
+// (resample_kernel; at 44100 Hz its copy mode).  The sides land in an allocation of the stream `ms`, or for a whole call
+// (ms null) in the context's mx_bed, side 1 on a 16-byte pitch; a whole call reads one side at 44100 Hz where the intake
+// left it, nothing launched.  A null bed (the stereo forms take one): nb = 0, nothing loops, a zeroed report.
+// The launch is enqueued, not awaited: g is read by an asynchronous copy and lives until the caller's next wait.
+struct MixBed {
+    const float* side[2] = {nullptr, nullptr};        // side[1] is side[0] where both sides are one
+    int64_t nb = 0, off = 0;                          // samples at the output rate; the bed sample under timeline sample 0
+    int loop = 0;
+    ft_intake_info info;                              // two sides: clipped and nonfinite summed, the pair's level
+    RsSeg g[2];
+};
+static ft_status mix_bed(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* bed, const ft_mix_params* mp, bool stereo,
+                         ft_mix_stream* ms, MixBed* b) {
+    CodecState* s = ctx->codec;
+    memset(&b->info, 0, sizeof b->info);
+    if (!bed) return FT_OK;
+    const chain::MsSides sd = stereo ? chain::ms_sides(mp->channel, bed->channels) : chain::MsSides();
+    const int sides = sd.same ? 1 : 2;
+    ft_intake_item item[2] = {*bed, *bed};
+    item[0].channel = sd.same ? mp->channel : sd.ch[0];
+    item[1].channel = sd.ch[1];
+    const ft_join_params whole = {0.f, 1, 0, 0};
+    int64_t lens[2] = {0, 0};
+    ft_intake_info bi[2];
+    FT_TRY(intake_run(ctx, fn, sides, item, &whole, sd.same ? mp->bed_loudness : 0, false, nullptr, nullptr, INT64_MAX, lens, bi, true));
+    const int64_t nb44 = lens[0];
+    if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
+    b->info = bi[0];
+    if (!sd.same) {
+        b->info.clipped += bi[1].clipped;
+        b->info.nonfinite += bi[1].nonfinite;
+        FT_TRY(level_pair(ctx, nb44, mp->bed_loudness, &b->info.level));
+    }
+    const CodecState::RsTab* rs = nullptr;
+    FT_TRY(rs_table(ctx, rate, &rs));
+    const int64_t nb = rs->K > 0 ? (nb44 * rs->L + rs->M - 1) / rs->M : nb44;
+    const int64_t pitch = (nb + 3) & ~(int64_t)3;     // side 1 begins on a 16-byte boundary
+    b->nb = nb;
+    b->off = mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
+    b->loop = mp->loop;
+    if (!ms && sides == 1 && rs->K == 0) {
+        b->side[0] = b->side[1] = s->join_out;
+        return FT_OK;
+    }
+    float* to = nullptr;
+    if (ms) {
+        FT_TRY(ml_malloc(ctx, ms, &to, (size_t)(pitch * sides)));
+    } else {
+        FT_TRY(cgrow(ctx, &s->mx_bed, &s->mx_bedcap, (size_t)(pitch * sides)));
+        to = s->mx_bed;
+    }
+    if (!s->rs_seg) FT_TRY(cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS));
+    for (int c = 0; c < sides; ++c) {
+        b->g[c] = RsSeg{s->join_out + c * nb44, rs->K > 0 ? rs->w : nullptr, nullptr, nullptr, to + c * pitch, 0, 0,
+                        (int)nb44, (int)nb, rs->L, rs->M, rs->K, 0};
+        b->side[c] = to + c * pitch;
+    }
+    if (sides == 1) b->side[1] = b->side[0];
+    FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, b->g, (size_t)sides * sizeof(RsSeg), hipMemcpyHostToDevice, s->stream));
+    const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
+    resample_kernel<<<dim3(gx, 1, sides), RS_THREADS, 0, s->stream>>>(s->rs_seg);
+    return FT_OK;
+}
+
+// The mix stage on a whole programme (ft_codec_mix), and with `pans` the stereo mix stage (ft_codec_mix_stereo): two floats
+// per frame out, the programme panned by the regions, the bed's sides kept apart, and the bed may be null.  The entry point
+// has judged its pointers.  Two waits: the peak decides whether the fourth launch runs.
+static ft_status mix_whole(ft_ctx* ctx, const std::string& fn, const float* x, int64_t n, int rate, const chain::MsTable* pans,
+                           const ft_intake_item* bed, const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total,
+                           int32_t* duck, ft_mix_info* info) {
+    FT_TRY(mix_refuse(ctx, fn, rate, n, mp, 1, pans));
+    const chain::MxPlan pl = chain::mx_plan(rate, n, mp->lead, mp->tail);
     if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
     CodecState* s = ctx->codec;
     FxDesc d;
-    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d));
+    FT_TRY(fx_refuse(ctx, fn, rate, 100, 0, &d));
+    const int ch = pans ? 2 : 1, R = pans ? (int)pans->R : 0;
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));           // (a call without a bed does not pass through intake_run)
     hipStream_t st = s->stream;
-    // the bed: one side prepared as ft_codec_mix prepares its bed, or two sides measured as a pair, each to the output rate
-    int64_t nb = 0;
-    const float* side[2] = {nullptr, nullptr};
-    ft_intake_info binfo;
-    memset(&binfo, 0, sizeof binfo);
-    RsSeg g[2];                                       // (read by an asynchronous copy: alive until the call's waits)
-    if (bed) {
-        const chain::MsSides sd = chain::ms_sides(mp->channel, bed->channels);
-        const int sides = sd.same ? 1 : 2;
-        ft_intake_item item[2] = {*bed, *bed};
-        item[0].channel = sd.same ? mp->channel : sd.ch[0];
-        item[1].channel = sd.ch[1];
-        const ft_join_params whole = {0.f, 1, 0, 0};
-        int64_t lens[2] = {0, 0};
-        ft_intake_info bi[2];
-        FT_TRY(intake_run(ctx, fn, sides, item, &whole, sd.same ? mp->bed_loudness : 0, false, nullptr, nullptr, INT64_MAX, lens, bi, true));
-        const int64_t nb44 = lens[0];
-        if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
-        binfo = bi[0];
-        if (!sd.same) {
-            binfo.clipped += bi[1].clipped;
-            binfo.nonfinite += bi[1].nonfinite;
-            FT_TRY(level_pair(ctx, nb44, mp->bed_loudness, &binfo.level));
-        }
-        FT_TRY(rs_table(ctx, sample_rate, &d.rs));
-        nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
-        const int64_t pitch = (nb + 3) & ~(int64_t)3;  // side 1 begins on a 16-byte boundary
-        if (d.K > 0 || !sd.same) {
-            if (!s->rs_seg) FT_TRY(cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS));
-            FT_TRY(cgrow(ctx, &s->mx_bed, &s->mx_bedcap, (size_t)(pitch * sides)));
-            for (int c = 0; c < sides; ++c) {
-                g[c] = RsSeg{s->join_out + c * nb44, d.K > 0 ? d.rs->w : nullptr, nullptr, nullptr, s->mx_bed + c * pitch, 0, 0,
-                             (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
-                side[c] = s->mx_bed + c * pitch;
-            }
-            FT_HIP(ctx, hipMemcpyAsync(s->rs_seg, g, (size_t)sides * sizeof(RsSeg), hipMemcpyHostToDevice, st));
-            const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
-            resample_kernel<<<dim3(gx, 1, sides), RS_THREADS, 0, st>>>(s->rs_seg);
-        } else {
-            side[0] = s->join_out;
-        }
-        if (sd.same) side[1] = side[0];
-    }
+    MixBed b;
+    FT_TRY(mix_bed(ctx, fn, rate, bed, mp, pans != nullptr, nullptr, &b));
     FT_TRY(mix_table(ctx));
-    FT_TRY(pan_table(ctx));
-    FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
+    if (pans) {
+        FT_TRY(pan_table(ctx));
+        FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
+    }
     FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, (size_t)n));
-    FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)(2 * pl.N)));
+    FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)(ch * pl.N)));
     FT_TRY(cgrow(ctx, &s->mx_act, &s->mx_actcap, (size_t)pl.Nh));
     FT_TRY(cgrow(ctx, &s->mx_D, &s->mx_Dcap, (size_t)pl.Nh + 1));
     FT_TRY(cgrow(ctx, &s->mx_g, &s->mx_gcap, (size_t)pl.Nh + 1));
-    MixSP sp;
+    MixSP sp;                                         // (the mono kernels take its MixP alone)
     memset(&sp, 0, sizeof sp);
     MixP& p = sp.m;
-    p.x = s->mx_x; p.bed = side[0]; p.T = s->mx_T; p.act = s->mx_act; p.D = s->mx_D; p.g = s->mx_g; p.y = s->mx_y; p.out = s->mx_out;
-    p.nb = nb;
-    p.off = !bed ? 0 : mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
+    p.x = s->mx_x; p.bed = b.side[0]; p.T = s->mx_T; p.act = s->mx_act; p.D = s->mx_D; p.g = s->mx_g; p.y = s->mx_y; p.out = s->mx_out;
+    p.nb = b.nb; p.off = b.off;
     p.N = (int)pl.N; p.n = (int)n; p.lead = (int)mp->lead; p.Nh = (int)pl.Nh; p.H = pl.H;
     p.depth = mp->depth; p.Wa = mp->attack; p.Wr = mp->release;
     p.f_in = (int)std::min(mp->fade_in, (int64_t)(pl.N / 2)); p.f_out = (int)std::min(mp->fade_out, (int64_t)(pl.N / 2));
-    p.loop = bed ? mp->loop : 0; p.thr = mp->threshold;
-    sp.bed1 = side[1]; sp.reg = s->mx_reg; sp.U = s->mx_U; sp.R = R;
+    p.loop = b.loop; p.thr = mp->threshold;
     FT_HIP(ctx, hipMemcpyAsync(s->mx_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, regions, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
+    if (pans) {
+        sp.bed1 = b.side[1]; sp.reg = s->mx_reg; sp.U = s->mx_U; sp.R = R;
+        if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, pans->reg, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
+    }
     FT_HIP(ctx, hipMemsetAsync(s->mx_out, 0, sizeof(MixOut), st));
     mix_hop_kernel<<<(unsigned)((pl.Nh + MX_THREADS / 64 - 1) / (MX_THREADS / 64)), MX_THREADS, 0, st>>>(p);
     mix_node_kernel<<<(unsigned)((pl.Nh + 1 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
-    mix_stereo_kernel<<<(unsigned)((pl.N + MX_SPAN - 1) / MX_SPAN), MX_THREADS, 0, st>>>(sp);
+    if (pans) mix_stereo_kernel<<<(unsigned)((pl.N + MX_SPAN - 1) / MX_SPAN), MX_THREADS, 0, st>>>(sp);
+    else mix_kernel<<<(unsigned)((pl.N + MX_SPAN - 1) / MX_SPAN), MX_THREADS, 0, st>>>(p);
     MixOut out;
     FT_HIP(ctx, hipMemcpyAsync(&out, s->mx_out, sizeof out, hipMemcpyDeviceToHost, st));
     if (duck) FT_HIP(ctx, hipMemcpyAsync(duck, s->mx_D, ((size_t)pl.Nh + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2987,24 +2946,46 @@ extern "C" ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n,
     const bool capped = (double)pk > chain::lv_ceiling();
     if (capped) {
         sg = (float)(chain::lv_ceiling() / (double)pk);
-        const int gx = (int)std::max(1LL, std::min(4096LL, (pl.N / 2 + MX_THREADS - 1) / MX_THREADS));
-        mix_scale_kernel<<<gx, MX_THREADS, 0, st>>>(s->mx_y, (int)(2 * pl.N), sg);
+        const int gx = (int)std::max(1LL, std::min(4096LL, (ch * pl.N / 4 + MX_THREADS - 1) / MX_THREADS));
+        mix_scale_kernel<<<gx, MX_THREADS, 0, st>>>(s->mx_y, (int)(ch * pl.N), sg);
     }
-    FT_HIP(ctx, hipMemcpyAsync(y, s->mx_y, (size_t)(2 * pl.N) * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipMemcpyAsync(y, s->mx_y, (size_t)(ch * pl.N) * sizeof(float), hipMemcpyDeviceToHost, st));
     FT_HIP(ctx, hipStreamSynchronize(st));
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("stereo mix launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
     *total = pl.N;
     memset(info, 0, sizeof *info);
-    info->N = pl.N; info->nb = nb; info->Nh = pl.Nh; info->active = out.active;
+    info->N = pl.N; info->nb = b.nb; info->Nh = pl.Nh; info->active = out.active;
     info->dmax = out.dmax; info->capped = capped ? 1 : 0; info->pk = pk; info->sg = sg;
-    info->bed = binfo;
+    info->bed = b.info;
     return FT_OK;
 }
 
-// ---- live mix stage (fishtts_hip.h: "Live mix"; the kernels in codec_kernels.h, the emission and the stream's counters in
+extern "C" ft_status ft_codec_mix(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
+                                  const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck, ft_mix_info* info) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!x || !bed || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_mix: a null pointer");
+    return mix_whole(ctx, "ft_codec_mix", x, n, sample_rate, nullptr, bed, mp, y, capacity, total, duck, info);
+}
+
+extern "C" ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_pan_region* regions,
+                                         int32_t R, const ft_intake_item* bed, const ft_mix_params* mp, float* y, int64_t capacity,
+                                         int64_t* total, int32_t* duck, ft_mix_info* info) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!x || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_mix_stereo: a null pointer");
+    const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
+    return mix_whole(ctx, "ft_codec_mix_stereo", x, n, sample_rate, &pans, bed, mp, y, capacity, total, duck, info);
+}
+
+// ---- live mix stages (fishtts_hip.h: "Live mix", "Live stereo mix"; the kernels in codec_kernels.h and, mixls_*_kernel, in
+// stereo_kernels.h; the emission, the stream's counters, the per-push region check, the pan words and the buffer sizes in
 // fx_chain.h).  A stream owns its prepared bed, its two pairs of carries, its per-hop arrays and the four words it reports;
-// a push stages its samples in the context's buffers and ends with one wait, so nothing of a push outlives it.
+// a push stages its samples in the context's buffers and ends with one wait, so nothing of a push outlives it.  A stereo
+// stream is a mix stream with two sides of the bed, a pan byte carry beside its programme carry and two floats per frame in
+// its m carries and in what it emits.
+static_assert(chain::MLS_WORD == 16 && MS_CENTRE == chain::MS_MAX_PAN, "fx_chain.h and stereo_kernels.h disagree on the pan bytes");
 static_assert(chain::ML_LA == ML_ATTACK && chain::ML_LR == ML_RELEASE && RS_MAX_RATE / 50 / 4 + 1 <= MX_THREADS &&
               chain::ML_MAX_FADE == (1LL << 30), "fx_chain.h and codec_kernels.h disagree on the live mix stage");
 static_assert(sizeof(ft_mix_live_info) == 128 && offsetof(ft_mix_live_info, bed) == 48, "ft_mix_live_info layout");
@@ -3015,8 +2996,8 @@ struct ft_mix_stream {
     ft_mix_params mp;
     int rate = RS_FI;
     bool stereo = false;              // a stream of the live stereo mix stage: two floats per frame in mc and in what it emits
-    float* bed = nullptr;             // the prepared bed at the output rate, nb samples (stereo: side 0, null without a bed)
-    const float* bed1 = nullptr;      // stereo: side 1, `bed` itself where both sides are one
+    const float* bed = nullptr;       // the prepared bed at the output rate, nb samples (stereo: side 0, null without a bed)
+    const float* bed1 = nullptr;      // side 1, `bed` itself where both sides are one
     unsigned char* pq[2] = {nullptr, nullptr};   // stereo: the pan bytes of the carried programme, laid out as prog
     size_t qcap[2] = {0, 0};
     long long nb = 0, off = 0;
@@ -3090,13 +3071,6 @@ static ft_status ml_hops(ft_ctx* ctx, ft_mix_stream* ms, size_t hops) {
     return FT_OK;
 }
 
-static chain::MxArgs ml_args(int rate, int64_t n, const ft_mix_params* mp) {
-    chain::MxArgs a;
-    a.rate = rate; a.n = n; a.bed_loudness = mp->bed_loudness; a.depth = mp->depth; a.threshold = mp->threshold;
-    a.attack = mp->attack; a.release = mp->release; a.lead = mp->lead; a.tail = mp->tail; a.fade_in = mp->fade_in;
-    a.fade_out = mp->fade_out; a.offset = mp->offset; a.loop = mp->loop;
-    return a;
-}
 static chain::MlShape ml_shape(int rate, const ft_mix_params* mp) {
     chain::MlShape sh;
     sh.H = chain::mx_hop(rate); sh.Wa = mp->attack; sh.lead = mp->lead; sh.tail = mp->tail; sh.fade_out = mp->fade_out;
@@ -3107,7 +3081,7 @@ extern "C" ft_status ft_mix_live_plan(int32_t sample_rate, const ft_mix_params* 
                                       int64_t* nodes) {
     if (!mp) return FT_ERR_ARG;
     bool too_long = false;
-    if (chain::mx_check(ml_args(sample_rate, n_in, mp), &too_long, 0)) return too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG;
+    if (chain::mx_check(mix_args(sample_rate, n_in, mp), &too_long, 0)) return too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG;
     const chain::MlPlan p = chain::ml_plan(ml_shape(sample_rate, mp), n_in, final != 0);
     if (n_out) *n_out = p.done;
     if (nodes) *nodes = p.limits;
@@ -3124,53 +3098,36 @@ static void ml_end(ft_ctx* ctx, ft_mix_stream* ms) {   // (s->mu held)
     delete ms;
 }
 
-// The stream of a call whose values mx_check has passed (s->mu held): the bed prepared - its own checks come before its
-// first device work - and kept, the state allocated.
-static ft_status ml_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* bed, const ft_mix_params* mp,
+// The stream of a call whose values mx_check has passed (s->mu held): the bed prepared into an allocation of the stream's
+// own, the state allocated.  `stereo`: a stream of the live stereo mix stage, whose bed may be null.  A begin that fails
+// once the stream exists frees it.
+static ft_status ml_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* bed, const ft_mix_params* mp, bool stereo,
                           ft_mix_stream** out) {
     CodecState* s = ctx->codec;
     FxDesc d;
     FT_TRY(fx_refuse(ctx, fn, rate, 100, 0, &d));
-    ft_intake_item item = *bed;
-    item.channel = mp->channel;
-    const ft_join_params whole = {0.f, 1, 0, 0};
-    int64_t nb44 = 0;
-    ft_intake_info binfo;
-    FT_TRY(intake_run(ctx, fn, 1, &item, &whole, mp->bed_loudness, false, nullptr, nullptr, INT64_MAX, &nb44, &binfo, true));
-    if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
+    FT_HIP(ctx, hipSetDevice(ctx->device));           // (a stream without a bed does not pass through intake_run)
     hipStream_t st = s->stream;
-    FT_TRY(rs_table(ctx, rate, &d.rs));
-    FT_TRY(mix_table(ctx));
-    const int64_t nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
     ft_mix_stream* ms = new ft_mix_stream();
     ms->owner = ctx;
+    ms->stereo = stereo;
     ms->mp = *mp;
     ms->rate = rate;
-    ms->nb = nb;
-    ms->off = mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
-    ms->binfo = binfo;
     ms->st = chain::MlStage::fresh(ml_shape(rate, mp));
     s->mix_streams.push_back(ms);
-    RsSeg g;                                          // (read by an asynchronous copy: alive until the wait below)
-    ft_status r = ml_malloc(ctx, ms, &ms->bed, (size_t)nb);
+    MixBed b;                                         // (alive until the wait below)
+    ft_status r = mix_bed(ctx, fn, rate, bed, mp, stereo, ms, &b);
+    if (r == FT_OK) r = mix_table(ctx);
+    if (r == FT_OK && stereo) r = pan_table(ctx);
     if (r == FT_OK) r = ml_malloc(ctx, ms, &ms->out, (size_t)1);
     if (r == FT_OK) r = ml_hops(ctx, ms, 1);
     for (int c = 0; c < 2 && r == FT_OK; ++c) {
         r = ml_carry(ctx, ms, &ms->prog[c], &ms->pcap[c], 4);
-        if (r == FT_OK) r = ml_carry(ctx, ms, &ms->mc[c], &ms->mcap[c], 4);
+        if (r == FT_OK && stereo) r = ml_carry(ctx, ms, &ms->pq[c], &ms->qcap[c], 4);
+        if (r == FT_OK) r = ml_carry(ctx, ms, &ms->mc[c], &ms->mcap[c], stereo ? 8 : 4);
     }
-    if (r == FT_OK && d.K > 0 && !s->rs_seg) r = cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS);
-    hipError_t e = hipSuccess;
     if (r == FT_OK) {
-        if (d.K > 0) {                                // to the output rate: the whole clip from zero state in one final call
-            g = RsSeg{s->join_out, d.rs->w, nullptr, nullptr, ms->bed, 0, 0, (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
-            e = hipMemcpyAsync(s->rs_seg, &g, sizeof g, hipMemcpyHostToDevice, st);
-            const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
-            if (e == hipSuccess) resample_kernel<<<dim3(gx, 1, 1), RS_THREADS, 0, st>>>(s->rs_seg);
-        } else {
-            e = hipMemcpyAsync(ms->bed, s->join_out, (size_t)nb * sizeof(float), hipMemcpyDeviceToDevice, st);
-        }
-        if (e == hipSuccess) e = hipMemsetAsync(ms->out, 0, sizeof(MixLiveOut), st);
+        hipError_t e = hipMemsetAsync(ms->out, 0, sizeof(MixLiveOut), st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) e = hipGetLastError();
         if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
@@ -3179,6 +3136,12 @@ static ft_status ml_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft
         ml_end(ctx, ms);
         return r;
     }
+    ms->bed = b.side[0];
+    ms->bed1 = b.side[1];
+    ms->nb = b.nb;
+    ms->off = b.off;
+    ms->mp.loop = b.loop;                             // (without a bed nothing loops: nb = 0)
+    ms->binfo = b.info;
     *out = ms;
     return FT_OK;
 }
@@ -3210,41 +3173,106 @@ static MixLiveP ml_fill(CodecState* s, const ft_mix_stream* ms, const chain::MlP
     return p;
 }
 
-// One push (s->mu held).  Everything is judged first; the stream's counters move only when the launches went through.
-static ft_status ml_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, const float* x, int64_t n, bool final, float* y,
-                         int64_t capacity, int64_t* n_out) {
+// One push (s->mu held; `pans`: a stereo stream's, the push's own regions, judged behind n).  Everything is judged first;
+// the stream's counters move only when the launches went through.
+static ft_status ml_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, const float* x, int64_t n, const chain::MsTable* pans,
+                         bool final, float* y, int64_t capacity, int64_t* n_out) {
     CodecState* s = ctx->codec;
     chain::MlStage& stg = ms->st;
     if (stg.ended) return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream has had its final push");
     if (n < 0 || (!x && n > 0) || !n_out) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    if (pans)
+        if (const char* why = chain::mls_check(*pans, n)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
     if (n > chain::MX_MAX_N || stg.s.lead + stg.nin + n + stg.s.tail > chain::MX_MAX_N)
         return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": lead + n + tail exceeds 2^28 samples");
     const chain::MlPlan pl = stg.plan(n, final);
     if (capacity < pl.out || (!y && pl.out > 0)) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below what the push emits");
-    const int H = stg.s.H, w = stg.par ^ 1;
-    const long long mend0 = stg.mixed * H, mend1 = final ? pl.N : pl.mixed * H;
+    const int w = stg.par ^ 1, ch = pans ? 2 : 1, R = pans ? (int)pans->R : 0;
+    const chain::MlsSizes z = chain::mls_sizes(stg, pl, ch);
+    const long long mend1 = final ? pl.N : pl.mixed * stg.s.H;
     hipStream_t st = s->stream;
     FT_TRY(ml_hops(ctx, ms, (size_t)pl.hops + 1));
-    FT_TRY(ml_carry(ctx, ms, &ms->prog[w], &ms->pcap[w], (size_t)(pl.F - pl.base) + 4));
-    FT_TRY(ml_carry(ctx, ms, &ms->mc[w], &ms->mcap[w], (size_t)(mend1 - pl.done) + 4));
-    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, (size_t)n + 8));
-    FT_TRY(cgrow(ctx, &s->ml_m, &s->ml_mcap, (size_t)(mend1 - mend0) + 8));
-    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, (size_t)pl.out + 8));
-    const MixLiveP p = ml_fill(s, ms, pl, final);
+    FT_TRY(ml_carry(ctx, ms, &ms->prog[w], &ms->pcap[w], z.prog));
+    FT_TRY(ml_carry(ctx, ms, &ms->mc[w], &ms->mcap[w], z.mc));
+    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, z.x));
+    FT_TRY(cgrow(ctx, &s->ml_m, &s->ml_mcap, z.m));
+    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, z.y));
+    if (pans) {
+        FT_TRY(ml_carry(ctx, ms, &ms->pq[w], &ms->qcap[w], z.pans));
+        FT_TRY(cgrow(ctx, &s->ml_q, &s->ml_qcap, z.q));
+        FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
+    }
+    MixLiveSP sp;                                     // (the mono kernels take its MixLiveP alone)
+    memset(&sp, 0, sizeof sp);
+    sp.l = ml_fill(s, ms, pl, final);
+    const MixLiveP& p = sp.l;
     if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->ml_x + (p.F0 - p.xb), x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (pans) {
+        sp.bed1 = ms->bed1; sp.U = s->mx_U; sp.reg = s->mx_reg; sp.qx = s->ml_q; sp.qin = ms->pq[stg.par]; sp.qout = ms->pq[w];
+        sp.R = R; sp.words = (int)chain::mls_words(p.F0, n);
+        if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, pans->reg, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
+    }
     const int W = MX_THREADS / 64;
     if (p.h1 > p.h0) mixl_hop_kernel<<<(unsigned)((p.h1 - p.h0 + W - 1) / W), MX_THREADS, 0, st>>>(p);
     if (p.kd1 > p.kd0) mixl_node_kernel<<<(unsigned)((p.kd1 - p.kd0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
-    if (p.q1 > p.q0) mixl_sample_kernel<<<(unsigned)(p.q1 - p.q0), MX_THREADS, 0, st>>>(p);
+    if (sp.words > 0) mixls_pan_kernel<<<(unsigned)((sp.words + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(sp);
+    if (p.q1 > p.q0) {
+        if (pans) mixls_sample_kernel<<<(unsigned)(p.q1 - p.q0), MX_THREADS, 0, st>>>(sp);
+        else mixl_sample_kernel<<<(unsigned)(p.q1 - p.q0), MX_THREADS, 0, st>>>(p);
+    }
     if (p.kl1 > p.kl0) mixl_limit_kernel<<<(unsigned)((p.kl1 - p.kl0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
-    const long long work = std::max((long long)pl.out, std::max(mend1 - pl.done, pl.F - pl.base));
-    if (work > 0) mixl_apply_kernel<<<(unsigned)std::min(4096LL, (work + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
-    if (pl.out > 0) FT_HIP(ctx, hipMemcpyAsync(y, s->ml_y, (size_t)pl.out * sizeof(float), hipMemcpyDeviceToHost, st));
+    // (a lane of the stereo apply kernel writes two frames of the output)
+    const long long work = std::max((long long)(pans ? (pl.out + 1) / 2 : pl.out), std::max(mend1 - pl.done, pl.F - pl.base));
+    if (work > 0) {
+        const unsigned gx = (unsigned)std::min(4096LL, (work + MX_THREADS - 1) / MX_THREADS);
+        if (pans) mixls_apply_kernel<<<gx, MX_THREADS, 0, st>>>(sp);
+        else mixl_apply_kernel<<<gx, MX_THREADS, 0, st>>>(p);
+    }
+    if (pl.out > 0) FT_HIP(ctx, hipMemcpyAsync(y, s->ml_y, (size_t)pl.out * ch * sizeof(float), hipMemcpyDeviceToHost, st));
     FT_HIP(ctx, hipStreamSynchronize(st));
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("live mix launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
     stg.commit(pl);
     *n_out = pl.out;
+    return FT_OK;
+}
+
+// The live stage on a whole programme (ft_codec_mix_live; with `pans`, ft_codec_mix_live_stereo): a stream begun, one final
+// push, its report and its D and L nodes read back, the stream ended.  The entry point has judged its pointers.
+static ft_status ml_live(ft_ctx* ctx, const std::string& fn, const float* x, int64_t n, int rate, const chain::MsTable* pans,
+                         const ft_intake_item* bed, const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total,
+                         int32_t* duck, int32_t* limit, ft_mix_live_info* info) {
+    FT_TRY(mix_refuse(ctx, fn, rate, n, mp, 0, pans));
+    const chain::MlPlan pl = chain::ml_plan(ml_shape(rate, mp), n, true);
+    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    ft_mix_stream* ms = nullptr;
+    FT_TRY(ml_begin(ctx, fn, rate, bed, mp, pans != nullptr, &ms));
+    int64_t got = 0;
+    ft_status r = ml_push(ctx, fn, ms, x, n, pans, true, y, capacity, &got);
+    MixLiveOut out;
+    memset(&out, 0, sizeof out);
+    hipError_t e = hipSuccess;
+    if (r == FT_OK) {
+        const size_t nn = (size_t)pl.hops + 1;
+        hipStream_t st = s->stream;
+        e = hipMemcpyAsync(&out, ms->out, sizeof out, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && duck) e = hipMemcpyAsync(duck, ms->D, nn * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && limit) e = hipMemcpyAsync(limit, ms->L, nn * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
+    }
+    const long long nb = ms->nb;
+    const ft_intake_info binfo = ms->binfo;
+    ml_end(ctx, ms);
+    FT_TRY(r);
+    *total = got;
+    memset(info, 0, sizeof *info);
+    info->N = pl.N; info->nb = nb; info->Nh = pl.hops; info->active = out.active;
+    info->dmax = out.dmax; info->lmax = out.lmax;
+    memcpy(&info->qmax, &out.qmax, sizeof(float));
+    info->bed = binfo;
     return FT_OK;
 }
 
@@ -3254,12 +3282,20 @@ extern "C" ft_status ft_codec_mix_stream_begin(ft_ctx* ctx, int32_t sample_rate,
     if (!ctx) return FT_ERR_ARG;
     FT_TRY(codec_ready(ctx));
     if (!bed || !mp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
-    bool too_long = false;
-    if (const char* why = chain::mx_check(ml_args(sample_rate, 0, mp), &too_long, 0))
-        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
-    CodecState* s = ctx->codec;
-    std::lock_guard<std::mutex> lock(s->mu);
-    return ml_begin(ctx, fn, sample_rate, bed, mp, out);
+    FT_TRY(mix_refuse(ctx, fn, sample_rate, 0, mp, 0, nullptr));
+    std::lock_guard<std::mutex> lock(ctx->codec->mu);
+    return ml_begin(ctx, fn, sample_rate, bed, mp, false, out);
+}
+
+extern "C" ft_status ft_codec_mix_stream_begin_stereo(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed,
+                                                      const ft_mix_params* mp, ft_mix_stream** out) {
+    const std::string fn = "ft_codec_mix_stream_begin_stereo";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!mp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    FT_TRY(mix_refuse(ctx, fn, sample_rate, 0, mp, 0, nullptr));
+    std::lock_guard<std::mutex> lock(ctx->codec->mu);
+    return ml_begin(ctx, fn, sample_rate, bed, mp, true, out);
 }
 
 extern "C" ft_status ft_codec_mix_stream_push(ft_mix_stream* ms, const float* x, int64_t n, int32_t final, float* y, int64_t capacity,
@@ -3271,7 +3307,20 @@ extern "C" ft_status ft_codec_mix_stream_push(ft_mix_stream* ms, const float* x,
     std::lock_guard<std::mutex> lock(s->mu);
     FT_HIP(ctx, hipSetDevice(ctx->device));
     if (ms->stereo) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_mix_stream_push: a stereo stream takes ft_codec_mix_stream_push_stereo");
-    return ml_push(ctx, "ft_codec_mix_stream_push", ms, x, n, final != 0, y, capacity, n_out);
+    return ml_push(ctx, "ft_codec_mix_stream_push", ms, x, n, nullptr, final != 0, y, capacity, n_out);
+}
+
+extern "C" ft_status ft_codec_mix_stream_push_stereo(ft_mix_stream* ms, const float* x, int64_t n, const ft_pan_region* regions,
+                                                     int32_t R, int32_t final, float* y, int64_t capacity, int64_t* n_out) {
+    if (!ms) return FT_ERR_ARG;
+    ft_ctx* ctx = ms->owner;
+    if (!ctx || !ctx->codec) return FT_ERR_STATE;      // its context was destroyed
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ms->stereo) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_mix_stream_push_stereo: a mono stream takes ft_codec_mix_stream_push");
+    const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
+    return ml_push(ctx, "ft_codec_mix_stream_push_stereo", ms, x, n, &pans, final != 0, y, capacity, n_out);
 }
 
 extern "C" void ft_codec_mix_stream_end(ft_mix_stream* ms) {
@@ -3289,255 +3338,20 @@ extern "C" void ft_codec_mix_stream_end(ft_mix_stream* ms) {
 extern "C" ft_status ft_codec_mix_live(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_intake_item* bed,
                                        const ft_mix_params* mp, float* y, int64_t capacity, int64_t* total, int32_t* duck,
                                        int32_t* limit, ft_mix_live_info* info) {
-    const std::string fn = "ft_codec_mix_live";
     if (!ctx) return FT_ERR_ARG;
     FT_TRY(codec_ready(ctx));
-    if ((!x && n != 0) || !bed || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
-    bool too_long = false;
-    if (const char* why = chain::mx_check(ml_args(sample_rate, n, mp), &too_long, 0))
-        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
-    const chain::MlPlan pl = chain::ml_plan(ml_shape(sample_rate, mp), n, true);
-    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
-    CodecState* s = ctx->codec;
-    std::lock_guard<std::mutex> lock(s->mu);
-    ft_mix_stream* ms = nullptr;
-    FT_TRY(ml_begin(ctx, fn, sample_rate, bed, mp, &ms));
-    int64_t got = 0;
-    ft_status r = ml_push(ctx, fn, ms, x, n, true, y, capacity, &got);
-    MixLiveOut out;
-    memset(&out, 0, sizeof out);
-    hipError_t e = hipSuccess;
-    if (r == FT_OK) {
-        const size_t nn = (size_t)pl.hops + 1;
-        hipStream_t st = s->stream;
-        e = hipMemcpyAsync(&out, ms->out, sizeof out, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && duck) e = hipMemcpyAsync(duck, ms->D, nn * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && limit) e = hipMemcpyAsync(limit, ms->L, nn * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
-    }
-    const long long nb = ms->nb;
-    const ft_intake_info binfo = ms->binfo;
-    ml_end(ctx, ms);
-    FT_TRY(r);
-    *total = got;
-    memset(info, 0, sizeof *info);
-    info->N = pl.N; info->nb = nb; info->Nh = pl.hops; info->active = out.active;
-    info->dmax = out.dmax; info->lmax = out.lmax;
-    memcpy(&info->qmax, &out.qmax, sizeof(float));
-    info->bed = binfo;
-    return FT_OK;
-}
-
-// ---- live stereo mix stage (fishtts_hip.h: "Live stereo mix"; mixls_*_kernel in stereo_kernels.h, the per-push region
-// check, the pan words and the buffer sizes in fx_chain.h).  A stereo stream is a mix stream with two sides of the bed, a pan
-// byte carry beside its programme carry and two floats per frame in its m carries and in what it emits.
-static_assert(chain::MLS_WORD == 16 && MS_CENTRE == chain::MS_MAX_PAN, "fx_chain.h and stereo_kernels.h disagree on the pan bytes");
-
-// ml_begin for a stereo stream (s->mu held, mx_check passed): the bed's sides prepared as ft_codec_mix_stereo prepares them,
-// into the stream's own buffer; `bed` may be null.
-static ft_status mls_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* bed, const ft_mix_params* mp,
-                           ft_mix_stream** out) {
-    CodecState* s = ctx->codec;
-    FxDesc d;
-    FT_TRY(fx_refuse(ctx, fn, rate, 100, 0, &d));
-    FT_HIP(ctx, hipSetDevice(ctx->device));           // (a stream without a bed does not pass through intake_run)
-    hipStream_t st = s->stream;
-    int64_t nb44 = 0, nb = 0, pitch = 0;
-    int sides = 0;
-    bool same = true;
-    ft_intake_info binfo;
-    memset(&binfo, 0, sizeof binfo);
-    if (bed) {
-        const chain::MsSides sd = chain::ms_sides(mp->channel, bed->channels);
-        same = sd.same;
-        sides = same ? 1 : 2;
-        ft_intake_item item[2] = {*bed, *bed};
-        item[0].channel = same ? mp->channel : sd.ch[0];
-        item[1].channel = sd.ch[1];
-        const ft_join_params whole = {0.f, 1, 0, 0};
-        int64_t lens[2] = {0, 0};
-        ft_intake_info bi[2];
-        FT_TRY(intake_run(ctx, fn, sides, item, &whole, same ? mp->bed_loudness : 0, false, nullptr, nullptr, INT64_MAX, lens, bi, true));
-        nb44 = lens[0];
-        if (nb44 < 1) return ft_fail(ctx, FT_ERR_ARG, fn + ": the bed has no samples");
-        binfo = bi[0];
-        if (!same) {
-            binfo.clipped += bi[1].clipped;
-            binfo.nonfinite += bi[1].nonfinite;
-            FT_TRY(level_pair(ctx, nb44, mp->bed_loudness, &binfo.level));
-        }
-        FT_TRY(rs_table(ctx, rate, &d.rs));
-        nb = d.K > 0 ? (nb44 * d.L + d.M - 1) / d.M : nb44;
-        pitch = (nb + 3) & ~(int64_t)3;               // side 1 begins on a 16-byte boundary
-        if (!s->rs_seg) FT_TRY(cmalloc(ctx, &s->rs_seg, (size_t)RS_MAX_SEGS));
-    }
-    FT_TRY(mix_table(ctx));
-    FT_TRY(pan_table(ctx));
-    ft_mix_stream* ms = new ft_mix_stream();
-    ms->owner = ctx;
-    ms->stereo = true;
-    ms->mp = *mp;
-    ms->rate = rate;
-    ms->nb = nb;
-    ms->off = !bed ? 0 : mp->loop ? mp->offset % nb : std::min(mp->offset, nb);
-    if (!bed) ms->mp.loop = 0;                        // (without a bed nothing loops: nb = 0)
-    ms->binfo = binfo;
-    ms->st = chain::MlStage::fresh(ml_shape(rate, mp));
-    s->mix_streams.push_back(ms);
-    RsSeg g[2];                                       // (read by an asynchronous copy: alive until the wait below)
-    ft_status r = FT_OK;
-    if (bed) r = ml_malloc(ctx, ms, &ms->bed, (size_t)(pitch * sides));
-    if (r == FT_OK) r = ml_malloc(ctx, ms, &ms->out, (size_t)1);
-    if (r == FT_OK) r = ml_hops(ctx, ms, 1);
-    for (int c = 0; c < 2 && r == FT_OK; ++c) {
-        r = ml_carry(ctx, ms, &ms->prog[c], &ms->pcap[c], 4);
-        if (r == FT_OK) r = ml_carry(ctx, ms, &ms->pq[c], &ms->qcap[c], 4);
-        if (r == FT_OK) r = ml_carry(ctx, ms, &ms->mc[c], &ms->mcap[c], 8);
-    }
-    hipError_t e = hipSuccess;
-    if (r == FT_OK) {
-        if (bed) {                                    // each side to the output rate, from zero state in one final call
-            for (int c = 0; c < sides; ++c)
-                g[c] = RsSeg{s->join_out + c * nb44, d.K > 0 ? d.rs->w : nullptr, nullptr, nullptr, ms->bed + c * pitch, 0, 0,
-                             (int)nb44, (int)nb, d.rs->L, d.rs->M, d.rs->K, 0};
-            e = hipMemcpyAsync(s->rs_seg, g, (size_t)sides * sizeof(RsSeg), hipMemcpyHostToDevice, st);
-            const int gx = (int)std::max(1LL, std::min(2048LL, ((long long)nb + RS_THREADS - 1) / RS_THREADS));
-            if (e == hipSuccess) resample_kernel<<<dim3(gx, 1, sides), RS_THREADS, 0, st>>>(s->rs_seg);
-            ms->bed1 = same ? ms->bed : ms->bed + pitch;
-        }
-        if (e == hipSuccess) e = hipMemsetAsync(ms->out, 0, sizeof(MixLiveOut), st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
-    }
-    if (r != FT_OK) {
-        ml_end(ctx, ms);
-        return r;
-    }
-    *out = ms;
-    return FT_OK;
-}
-
-// ml_push for a stereo stream: the regions are the push's own, judged behind n.
-static ft_status mls_push(ft_ctx* ctx, const std::string& fn, ft_mix_stream* ms, const float* x, int64_t n, const ft_pan_region* regions,
-                          int32_t R, bool final, float* y, int64_t capacity, int64_t* n_out) {
-    CodecState* s = ctx->codec;
-    chain::MlStage& stg = ms->st;
-    if (stg.ended) return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream has had its final push");
-    if (n < 0 || (!x && n > 0) || !n_out) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
-    const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
-    if (const char* why = chain::mls_check(pans, n)) return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
-    if (n > chain::MX_MAX_N || stg.s.lead + stg.nin + n + stg.s.tail > chain::MX_MAX_N)
-        return ft_fail(ctx, FT_ERR_TOO_LONG, fn + ": lead + n + tail exceeds 2^28 samples");
-    const chain::MlPlan pl = stg.plan(n, final);
-    if (capacity < pl.out || (!y && pl.out > 0)) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below what the push emits");
-    const int w = stg.par ^ 1;
-    const chain::MlsSizes z = chain::mls_sizes(stg, pl);
-    const long long mend1 = final ? pl.N : pl.mixed * stg.s.H;
-    hipStream_t st = s->stream;
-    FT_TRY(ml_hops(ctx, ms, (size_t)pl.hops + 1));
-    FT_TRY(ml_carry(ctx, ms, &ms->prog[w], &ms->pcap[w], z.prog));
-    FT_TRY(ml_carry(ctx, ms, &ms->pq[w], &ms->qcap[w], z.pans));
-    FT_TRY(ml_carry(ctx, ms, &ms->mc[w], &ms->mcap[w], z.mc));
-    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, z.x));
-    FT_TRY(cgrow(ctx, &s->ml_q, &s->ml_qcap, z.q));
-    FT_TRY(cgrow(ctx, &s->ml_m, &s->ml_mcap, z.m));
-    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, z.y));
-    FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
-    MixLiveSP sp;
-    memset(&sp, 0, sizeof sp);
-    sp.l = ml_fill(s, ms, pl, final);
-    const MixLiveP& p = sp.l;
-    sp.bed1 = ms->bed1; sp.U = s->mx_U; sp.reg = s->mx_reg; sp.qx = s->ml_q; sp.qin = ms->pq[stg.par]; sp.qout = ms->pq[w];
-    sp.R = R; sp.words = (int)chain::mls_words(p.F0, n);
-    if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->ml_x + (p.F0 - p.xb), x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, regions, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
-    const int W = MX_THREADS / 64;
-    if (p.h1 > p.h0) mixl_hop_kernel<<<(unsigned)((p.h1 - p.h0 + W - 1) / W), MX_THREADS, 0, st>>>(p);
-    if (p.kd1 > p.kd0) mixl_node_kernel<<<(unsigned)((p.kd1 - p.kd0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
-    if (sp.words > 0) mixls_pan_kernel<<<(unsigned)((sp.words + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(sp);
-    if (p.q1 > p.q0) mixls_sample_kernel<<<(unsigned)(p.q1 - p.q0), MX_THREADS, 0, st>>>(sp);
-    if (p.kl1 > p.kl0) mixl_limit_kernel<<<(unsigned)((p.kl1 - p.kl0 + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(p);
-    const long long work = std::max((long long)(pl.out + 1) / 2, std::max(mend1 - pl.done, pl.F - pl.base));
-    if (work > 0) mixls_apply_kernel<<<(unsigned)std::min(4096LL, (work + MX_THREADS - 1) / MX_THREADS), MX_THREADS, 0, st>>>(sp);
-    if (pl.out > 0) FT_HIP(ctx, hipMemcpyAsync(y, s->ml_y, (size_t)pl.out * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
-    FT_HIP(ctx, hipStreamSynchronize(st));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("live stereo mix launch: ") + hipGetErrorString(e));
-    stg.commit(pl);
-    *n_out = pl.out;
-    return FT_OK;
-}
-
-extern "C" ft_status ft_codec_mix_stream_begin_stereo(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed,
-                                                      const ft_mix_params* mp, ft_mix_stream** out) {
-    const std::string fn = "ft_codec_mix_stream_begin_stereo";
-    if (!ctx) return FT_ERR_ARG;
-    FT_TRY(codec_ready(ctx));
-    if (!mp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
-    bool too_long = false;
-    if (const char* why = chain::mx_check(ml_args(sample_rate, 0, mp), &too_long, 0))
-        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
-    CodecState* s = ctx->codec;
-    std::lock_guard<std::mutex> lock(s->mu);
-    return mls_begin(ctx, fn, sample_rate, bed, mp, out);
-}
-
-extern "C" ft_status ft_codec_mix_stream_push_stereo(ft_mix_stream* ms, const float* x, int64_t n, const ft_pan_region* regions,
-                                                     int32_t R, int32_t final, float* y, int64_t capacity, int64_t* n_out) {
-    if (!ms) return FT_ERR_ARG;
-    ft_ctx* ctx = ms->owner;
-    if (!ctx || !ctx->codec) return FT_ERR_STATE;      // its context was destroyed
-    CodecState* s = ctx->codec;
-    std::lock_guard<std::mutex> lock(s->mu);
-    FT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ms->stereo) return ft_fail(ctx, FT_ERR_STATE, "ft_codec_mix_stream_push_stereo: a mono stream takes ft_codec_mix_stream_push");
-    return mls_push(ctx, "ft_codec_mix_stream_push_stereo", ms, x, n, regions, R, final != 0, y, capacity, n_out);
+    if ((!x && n != 0) || !bed || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_mix_live: a null pointer");
+    return ml_live(ctx, "ft_codec_mix_live", x, n, sample_rate, nullptr, bed, mp, y, capacity, total, duck, limit, info);
 }
 
 extern "C" ft_status ft_codec_mix_live_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_pan_region* regions,
                                               int32_t R, const ft_intake_item* bed, const ft_mix_params* mp, float* y,
                                               int64_t capacity, int64_t* total, int32_t* duck, int32_t* limit, ft_mix_live_info* info) {
-    const std::string fn = "ft_codec_mix_live_stereo";
     if (!ctx) return FT_ERR_ARG;
     FT_TRY(codec_ready(ctx));
-    if ((!x && n != 0) || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    if ((!x && n != 0) || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_mix_live_stereo: a null pointer");
     const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
-    bool too_long = false;
-    if (const char* why = chain::mx_check(ml_args(sample_rate, n, mp), &too_long, 0, &pans))
-        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
-    const chain::MlPlan pl = chain::ml_plan(ml_shape(sample_rate, mp), n, true);
-    if (capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below lead + n + tail");
-    CodecState* s = ctx->codec;
-    std::lock_guard<std::mutex> lock(s->mu);
-    ft_mix_stream* ms = nullptr;
-    FT_TRY(mls_begin(ctx, fn, sample_rate, bed, mp, &ms));
-    int64_t got = 0;
-    ft_status r = mls_push(ctx, fn, ms, x, n, regions, R, true, y, capacity, &got);
-    MixLiveOut out;
-    memset(&out, 0, sizeof out);
-    hipError_t e = hipSuccess;
-    if (r == FT_OK) {
-        const size_t nn = (size_t)pl.hops + 1;
-        hipStream_t st = s->stream;
-        e = hipMemcpyAsync(&out, ms->out, sizeof out, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && duck) e = hipMemcpyAsync(duck, ms->D, nn * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && limit) e = hipMemcpyAsync(limit, ms->L, nn * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
-    }
-    const long long nb = ms->nb;
-    const ft_intake_info binfo = ms->binfo;
-    ml_end(ctx, ms);
-    FT_TRY(r);
-    *total = got;
-    memset(info, 0, sizeof *info);
-    info->N = pl.N; info->nb = nb; info->Nh = pl.hops; info->active = out.active;
-    info->dmax = out.dmax; info->lmax = out.lmax;
-    memcpy(&info->qmax, &out.qmax, sizeof(float));
-    info->bed = binfo;
-    return FT_OK;
+    return ml_live(ctx, "ft_codec_mix_live_stereo", x, n, sample_rate, &pans, bed, mp, y, capacity, total, duck, limit, info);
 }
 
 // ---- launch trace hooks (fishtts_hip_test.h)

@@ -466,18 +466,19 @@ inline void mls_expand(const MsTable& t, long long F0, long long n, long long w,
 }
 // Elements a push needs in each buffer (the margins are the layout's: a buffer begins up to three elements before its first
 // sample, and a 16-byte access may end up to three behind its last): the staged push and its pan bytes, the staged m and the
-// output (floats, two per frame), and the three carries the push writes (programme, pan bytes, m - two floats per frame).
+// output (floats, `ch` per frame), and the three carries the push writes (programme, pan bytes, m - `ch` floats per frame).
+// ch: 2 for a stereo stream; 1 for a stream of the live mix stage, which has no pan bytes and leaves q and pans unused.
 struct MlsSizes { size_t x = 0, q = 0, m = 0, y = 0, prog = 0, pans = 0, mc = 0; };
-inline MlsSizes mls_sizes(const MlStage& st, const MlPlan& p) {
+inline MlsSizes mls_sizes(const MlStage& st, const MlPlan& p, int ch) {
     MlsSizes z;
     const long long H = st.s.H, F0 = st.s.lead + st.nin, mend0 = st.mixed * H, mend1 = p.final ? p.N : p.mixed * H;
     z.x = (size_t)p.in + 8;
     z.q = (size_t)(mls_words(F0, p.in) * MLS_WORD) + 8;
-    z.m = 2 * ((size_t)(mend1 - mend0) + 8);
-    z.y = 2 * ((size_t)p.out + 4);
+    z.m = ch * ((size_t)(mend1 - mend0) + 8);
+    z.y = ch * (size_t)p.out + 8;
     z.prog = (size_t)(p.F - p.base) + 4;
     z.pans = (size_t)(p.F - p.base) + 4;
-    z.mc = 2 * ((size_t)(mend1 - p.done) + 4);
+    z.mc = ch * ((size_t)(mend1 - p.done) + 4);
     return z;
 }
 

@@ -187,6 +187,19 @@ def test_bed_sides(eng, name, channel):
         assert np.array_equal(bits(y[:8, 0]), bits(y[:8, 1]))
 
 
+def test_a_two_sided_bed_at_its_own_rate(eng):
+    """Fo = 44100: nothing is resampled, the two sides are copied to the bed buffer by the resampler's copy mode, and with
+    5006 samples a side (no multiple of four) side 1 begins on its 16-byte pitch, two samples behind the end of side 0.  The
+    bed wraps twice under nine hops and an odd remainder.  (The same bed through a stereo stream at this rate:
+    tests/test_stereo_live_gpu.py, limited-44100.)"""
+    h = 44100 // 50
+    x = speech(9 * h + 17, seed=44, amp=0.15, quiet=[(2 * h, 4 * h)])
+    p = R.Params(depth=900, attack=3, release=4, lead=8, tail=5, offset=3)
+    y, rep, want = check(eng, x, made("stereo"), [(0, 500, -100), (500, 4 * h + 1, 37), (7 * h, len(x), 100)], p, rate=44100)
+    assert rep.bed_len == 5006 and rep.bed_len % 4 != 0
+    assert not np.array_equal(y[:8, 0], y[:8, 1])          # the lead: the bed alone, two different sides
+
+
 @pytest.mark.parametrize("loudness", [None, -30.0])
 @pytest.mark.parametrize("name", ["long", "stereo-s16"])
 def test_pair_level(eng, name, loudness):

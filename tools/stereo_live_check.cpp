@@ -120,7 +120,7 @@ static void walk(std::mt19937& rng, int it) {
             EXPECT(u.a >= F0 && u.e <= F0 + k && ms_pan(whole, u.a - s.lead) == g.pan && ms_pan(whole, u.e - 1 - s.lead) == g.pan);
         }
         const MlPlan p = st.plan(k, final);
-        const MlsSizes z = mls_sizes(st, p);
+        const MlsSizes z = mls_sizes(st, p, 2);
         const int r = st.par, w = st.par ^ 1, H = s.H;
         const long long F1 = p.F, cb0 = st.base, cb1 = p.base, mend0 = st.mixed * H, mend1 = final ? p.N : p.mixed * H;
         const long long xb = F0 & ~3LL, pib = cb0 & ~3LL, pob = cb1 & ~3LL, mb = mend0 & ~3LL, cib = st.done & ~3LL, cob = p.done & ~3LL;
