@@ -78,6 +78,20 @@ class ft_pan_region(C.Structure):
     _fields_ = [("a", C.c_int64), ("e", C.c_int64), ("pan", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ft_send_region(C.Structure):
+    _fields_ = [("a", C.c_int64), ("e", C.c_int64), ("send", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ft_room_params(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("channel", "normalize", "wet", "dry", "send", "ceiling")] + \
+               [(n, C.c_int64) for n in ("offset", "length", "fade", "predelay", "tail")]
+
+
+class ft_room_info(C.Structure):
+    _fields_ = [("N", C.c_int64), ("nh", C.c_int64), ("L", C.c_int64), ("E", C.c_double), ("gn", C.c_float), ("pk", C.c_float),
+                ("sg", C.c_float), ("capped", C.c_int32), ("ir", ft_intake_info)]
+
+
 class ft_mix_live_info(C.Structure):
     _fields_ = [("N", C.c_int64), ("nb", C.c_int64), ("Nh", C.c_int64), ("active", C.c_int64), ("dmax", C.c_int32),
                 ("lmax", C.c_int32), ("qmax", C.c_float), ("reserved", C.c_int32), ("bed", ft_intake_info)]
@@ -181,6 +195,10 @@ SYMBOLS = {
     "ft_codec_mix_stereo": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.POINTER(ft_intake_item),
                                         C.POINTER(ft_mix_params), _P, C.c_int64, _P, _P, C.POINTER(ft_mix_info)]),
     "ft_pan_gains": (C.c_int32, [_P]),
+    "ft_codec_room": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_room_params),
+                                  _P, C.c_int64, _P, C.POINTER(ft_room_info)]),
+    "ft_room_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.POINTER(ft_room_params), _P, _P]),
+    "ft_test_room_conv": (C.c_int32, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P]),
     "ft_mix_live_plan": (C.c_int32, [C.c_int32, C.POINTER(ft_mix_params), C.c_int64, C.c_int32, _P, _P]),
     "ft_codec_mix_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), _P,
                                       C.c_int64, _P, _P, _P, C.POINTER(ft_mix_live_info)]),

@@ -88,6 +88,49 @@ class MixReport:
 
 
 @dataclass(frozen=True)
+class RoomReport:
+    """What the room stage did (ft_room_info): `n` the samples of the piece (programme + tail), `ir_len` the impulse
+    response's samples at the output rate and `taps` those used, `energy` the used response's energy E and `norm` the gain gn
+    that normalised it (1 without normalize), `peak` the sample peak before the ceiling, `gain` the one gain the ceiling
+    applied (1 when `capped` is False; never with ceiling=False), `ir` the intake's report of the response."""
+    n: int
+    ir_len: int
+    taps: int
+    energy: float
+    norm: float
+    peak: float
+    gain: float
+    capped: bool
+    ir: IntakeReport
+
+    @classmethod
+    def of(cls, i: "L.ft_room_info") -> "RoomReport":
+        return cls(int(i.N), int(i.nh), int(i.L), float(i.E), float(np.float32(i.gn)), float(np.float32(i.pk)),
+                   float(np.float32(i.sg)), bool(i.capped), IntakeReport.of(i.ir))
+
+
+MAX_SEND_REGIONS = 4096           # per call of ft_codec_room
+
+
+def send_region_table(what: str, regions, n: int):
+    """(ft_send_region array, R) of `regions` - (a, e, send) each, integers, sorted and disjoint inside [0, n), send in
+    [0, 6000] hundredths of a dB or -1 (muted) - checked as the stage checks them, before any device work."""
+    regions = [tuple(r) for r in regions]
+    if len(regions) > MAX_SEND_REGIONS:
+        raise ValueError(f"{what}: {len(regions)} send regions, a call takes {MAX_SEND_REGIONS}")
+    at = 0
+    for r in regions:
+        if len(r) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
+            raise ValueError(f"{what}: a region is three integers (a, e, send), got {r!r}")
+        a, e, send = r
+        if not at <= a < e <= n or not -1 <= send <= 6000:
+            raise ValueError(f"{what}: region {r!r} out of order, outside [0, {n}) or its send outside [-1, 6000]")
+        at = e
+    reg = (L.ft_send_region * max(len(regions), 1))(*[L.ft_send_region(int(a), int(e), int(s), 0) for a, e, s in regions])
+    return reg, len(regions)
+
+
+@dataclass(frozen=True)
 class MixLiveReport:
     """What the live mix stage did (ft_mix_live_info): `n`, `bed_len`, `hops`, `active`, `duck_max` and `bed` as MixReport's;
     `limit_max` the deepest the limiter went (dB), `peak` the largest hop peak before the limiter."""
@@ -821,6 +864,50 @@ class CodecHipEngine:
             out.append(codes[at:at + self.R * i.frames].reshape(self.R, i.frames).astype(np.int64))
             at += self.R * i.frames
         return out, [IntakeReport.of(i) for i in infos]
+
+    def room(self, audio: np.ndarray, clip, regions=(), sample_rate: Optional[int] = None, params=None, ceiling: bool = True):
+        """The room stage on a host waveform at `sample_rate` (None: the codec's rate), on the device (ft_codec_room): `clip` -
+        (WAV bytes, WavInfo of wavfile.parse_wav), a room's impulse response - prepared by the intake launches, brought to the
+        output rate, cut, faded and normalised; the programme, weighted by `regions` - (a, e, send) each, a send in hundredths
+        of a dB of attenuation or -1 for muted; sorted and disjoint, at most 4096 - convolved with it, added to the dry
+        programme and, with `ceiling`, held under -1 dBFS (False: a mix stage follows and has the ceiling).  `params`: a
+        room.RoomParams (room.room_params makes one from a Room), or None for a default Room's.  Returns (y, RoomReport); y
+        is the programme's length plus the tail."""
+        from .room import Room, RoomParams, room_params
+        what = "room"
+        rate = OutputFx.of(sample_rate=sample_rate).wav_rate
+        if params is None:
+            params = room_params(Room(b""), rate)
+        if not isinstance(params, RoomParams):
+            raise ValueError(f"{what}: params must be a RoomParams, got {type(params).__name__}")
+        if not isinstance(ceiling, bool):
+            raise ValueError(f"{what}: ceiling must be True or False, got {ceiling!r}")
+        items, keep, _, _ = self._intake_args(what, [clip], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
+        x = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(-1))
+        if len(x) < 1:
+            raise ValueError(f"{what}: an empty programme")
+        table = send_region_table(what, regions, len(x))
+        rp = L.ft_room_params(params.channel, params.normalize, params.wet, params.dry, params.send, 1 if ceiling else 0,
+                              params.offset, params.length, params.fade, params.predelay, params.tail)
+        nh = int(self.lib.ft_resampled_len(rate, int(self.lib.ft_intake_len(items[0].rate, items[0].n_frames))))
+        N = C.c_int64(0)
+        self._check(self.lib.ft_room_plan(rate, len(x), nh, C.byref(rp), None, C.byref(N)), "ft_room_plan")
+        y = np.empty(N.value, dtype=np.float32)
+        total = C.c_int64(0)
+        info = L.ft_room_info()
+        self._check(self.lib.ft_codec_room(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, *table, items, C.byref(rp),
+                                           y.ctypes.data_as(C.c_void_p), N.value, C.byref(total), C.byref(info)), "ft_codec_room")
+        del keep
+        return y[:total.value], RoomReport.of(info)
+
+    def test_room_conv(self, xs: np.ndarray, hn: np.ndarray, predelay: int, N: int) -> np.ndarray:
+        """Test hook: the room stage's convolution launches alone on the taps hn (ft_test_room_conv) -> c[0 .. N)."""
+        xs = np.ascontiguousarray(np.asarray(xs, dtype=np.float32).reshape(-1))
+        hn = np.ascontiguousarray(np.asarray(hn, dtype=np.float32).reshape(-1))
+        c = np.empty(max(int(N), 1), dtype=np.float32)
+        self._check(self.lib.ft_test_room_conv(self._h, xs.ctypes.data_as(C.c_void_p), len(xs), hn.ctypes.data_as(C.c_void_p),
+                                               len(hn), int(predelay), int(N), c.ctypes.data_as(C.c_void_p)), "ft_test_room_conv")
+        return c[:int(N)]
 
     def mix(self, x: np.ndarray, bed, sample_rate: Optional[int] = None, params=None, nodes: bool = False):
         """The mix stage on a host waveform at `sample_rate` (None: the codec's rate), on the device (ft_codec_mix): `bed` -

@@ -11,6 +11,7 @@
 
 #include "codec_kernels.h"
 #include "stereo_kernels.h"
+#include "room_kernels.h"
 #include "engine.h"
 #include "fx_chain.h"
 #include "join_plan.h"
@@ -124,6 +125,12 @@ struct CodecState {
     float* mx_U = nullptr;
     MixPan* mx_reg = nullptr;
     size_t mx_regcap = 0;
+    // room stage (ft_codec_room): the sent programme, t and hn, the block energies, the words the launches reduce into; the
+    // programme, the output and the regions use the mix stage's buffers (the stages never run inside one call)
+    float *rm_xs = nullptr, *rm_t = nullptr, *rm_hn = nullptr;
+    double* rm_e = nullptr;
+    RoomOut* rm_out = nullptr;
+    size_t rm_xscap = 0, rm_tcap = 0, rm_hncap = 0, rm_ecap = 0;
     // live mix stage (ft_codec_mix_stream_*): the open streams (their device state is freed with the context), and what a
     // push stages - its samples, the m of the hops it completes, the samples it emits; the buffers grow on need
     std::vector<ft_mix_stream*> mix_streams;
@@ -2977,6 +2984,165 @@ extern "C" ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n,
     if (!x || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_mix_stereo: a null pointer");
     const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
     return mix_whole(ctx, "ft_codec_mix_stereo", x, n, sample_rate, &pans, bed, mp, y, capacity, total, duck, info);
+}
+
+// ---- room stage (fishtts_hip.h: "Room"; the kernels in room_kernels.h, the checks, L, f, N and the sizes in fx_chain.h).
+// The impulse response comes through mix_bed - the intake launches and the resampler as Mix prepares its bed.
+static_assert(sizeof(ft_send_region) == sizeof(chain::MsRegion) && offsetof(ft_send_region, send) == offsetof(MixPan, pan) &&
+              sizeof(ft_send_region) == sizeof(MixPan), "ft_send_region layout");
+static_assert(sizeof(ft_room_params) == 64 && offsetof(ft_room_params, offset) == 24, "ft_room_params layout");
+static_assert(sizeof(ft_room_info) == 128 && offsetof(ft_room_info, ir) == 48, "ft_room_info layout");
+static_assert(chain::RM_MAX_L == RM_MAX_L && RM_BLOCK == 256 && RM_DC % RM_STEP == 0 && RM_STEP % 2 == 0 && RM_LAUNCH % RM_SPAN == 0,
+              "fx_chain.h and room_kernels.h disagree on the room stage");
+
+static chain::RmArgs room_args(int rate, int64_t n, const ft_intake_item* ir, const ft_room_params* rp) {
+    chain::RmArgs a;
+    a.rate = rate; a.n = n; a.channel = rp->channel; a.normalize = rp->normalize; a.wet = rp->wet; a.dry = rp->dry;
+    a.send = rp->send; a.ceiling = rp->ceiling; a.offset = rp->offset; a.length = rp->length; a.fade = rp->fade;
+    a.predelay = rp->predelay; a.tail = rp->tail;
+    a.ir_rate = ir->rate; a.ir_channels = ir->channels; a.ir_frames = ir->n_frames;
+    return a;
+}
+
+extern "C" ft_status ft_room_plan(int32_t sample_rate, int64_t n, int64_t nh, const ft_room_params* rp, int64_t* L, int64_t* N) {
+    if (!rp || nh < 0) return FT_ERR_ARG;
+    const ft_intake_item it = {nullptr, 1, chain::RS_FI, rp->channel < 0 ? 1 : rp->channel + 1, 0, 0};   // (no item: its checks pass)
+    chain::RmArgs a = room_args(sample_rate, n, &it, rp);
+    a.nh = nh;
+    bool too_long = false;
+    chain::RmPlan pl;
+    if (chain::rm_check(a, chain::MsTable(), &too_long, &pl)) return too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG;
+    if (L) *L = pl.L;
+    if (N) *N = pl.N;
+    return FT_OK;
+}
+
+// The chain's launches over outputs [0, N) (s->mu held): RM_LAUNCH outputs each.
+static void room_conv(CodecState* s, RoomConvP p) {
+    for (long long i0 = 0; i0 < p.N; i0 += RM_LAUNCH) {
+        p.i0 = (int)i0;
+        const long long span = std::min<long long>(RM_LAUNCH, p.N - i0);
+        room_conv_kernel<<<(unsigned)((span + RM_SPAN - 1) / RM_SPAN), RM_THREADS, 0, s->stream>>>(p);
+    }
+}
+
+static ft_status room_out(ft_ctx* ctx) {
+    CodecState* s = ctx->codec;
+    if (!s->rm_out) FT_TRY(cmalloc(ctx, &s->rm_out, (size_t)1));
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_room(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_send_region* regions,
+                                   int32_t R, const ft_intake_item* ir, const ft_room_params* rp, float* y, int64_t capacity,
+                                   int64_t* total, ft_room_info* info) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    const std::string fn = "ft_codec_room";
+    if (!x || !ir || !rp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    const chain::MsTable regs = {(const chain::MsRegion*)regions, R};
+    const chain::RmArgs a = room_args(sample_rate, n, ir, rp);
+    bool too_long = false;
+    chain::RmPlan pl;
+    if (const char* why = chain::rm_check(a, regs, &too_long, &pl))
+        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    if (pl.nh >= 0 && capacity < pl.N) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below n + tail");
+    CodecState* s = ctx->codec;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, sample_rate, 100, 0, &d));
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = s->stream;
+    ft_mix_params mp;
+    memset(&mp, 0, sizeof mp);
+    mp.channel = rp->channel;
+    MixBed b;
+    FT_TRY(mix_bed(ctx, fn, sample_rate, ir, &mp, false, nullptr, &b));
+    if (b.nb != pl.nh) return ft_fail(ctx, FT_ERR_STATE, fn + ": the impulse response's length is not the planned one");
+    FT_TRY(mix_table(ctx));
+    FT_TRY(room_out(ctx));
+    const chain::RmSizes z = chain::rm_sizes(a, pl);
+    FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, z.x));
+    FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, z.y));
+    FT_TRY(cgrow(ctx, &s->rm_t, &s->rm_tcap, z.taps));
+    FT_TRY(cgrow(ctx, &s->rm_hn, &s->rm_hncap, z.taps));
+    FT_TRY(cgrow(ctx, &s->rm_e, &s->rm_ecap, z.blocks));
+    if (pl.send) {
+        FT_TRY(cgrow(ctx, &s->rm_xs, &s->rm_xscap, z.xs));
+        FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
+    }
+    std::vector<float> T(chain::MX_MAX_DEPTH + 1);
+    chain::mx_gains(T.data());
+    FT_HIP(ctx, hipMemcpyAsync(s->mx_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipMemsetAsync(s->rm_out, 0, sizeof(RoomOut), st));
+    RoomIrP ip = {b.side[0], s->rm_t, s->rm_hn, s->rm_e, s->rm_out, (int)pl.L, (int)pl.f, rp->normalize, rp->offset};
+    room_ir_kernel<<<(unsigned)((z.blocks + 63) / 64), 64, 0, st>>>(ip);
+    room_gain_kernel<<<1, 1024, 0, st>>>(ip);
+    if (pl.send) {
+        if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, regions, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
+        RoomSendP sp = {s->mx_x, s->rm_xs, s->mx_T, s->mx_reg, (int)n, R, rp->send};
+        room_send_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256)), 256, 0, st>>>(sp);
+    }
+    RoomConvP cp;
+    memset(&cp, 0, sizeof cp);
+    cp.xs = pl.send ? s->rm_xs : s->mx_x; cp.x = s->mx_x; cp.hn = s->rm_hn; cp.y = s->mx_y; cp.out = s->rm_out;
+    cp.n = (int)n; cp.L = (int)pl.L; cp.predelay = (int)rp->predelay; cp.N = (int)pl.N;
+    cp.dry = rp->dry >= 0; cp.gd = cp.dry ? T[rp->dry] : 0.f; cp.gw = T[rp->wet];
+    room_conv(s, cp);
+    RoomOut out;
+    FT_HIP(ctx, hipMemcpyAsync(&out, s->rm_out, sizeof out, hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));            // E may refuse the call; the peak decides whether the last launch runs
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
+    if (rp->normalize && (!(out.E > 0.0) || !std::isfinite(out.E)))
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": the impulse response's energy is zero or not finite");
+    float pk, sg = 1.f;
+    memcpy(&pk, &out.pk, sizeof pk);
+    const bool capped = rp->ceiling && (double)pk > chain::lv_ceiling();
+    if (capped) {
+        sg = (float)(chain::lv_ceiling() / (double)pk);
+        const int gx = (int)std::max(1LL, std::min(4096LL, (pl.N / 4 + MX_THREADS - 1) / MX_THREADS));
+        mix_scale_kernel<<<gx, MX_THREADS, 0, st>>>(s->mx_y, (int)pl.N, sg);
+    }
+    FT_HIP(ctx, hipMemcpyAsync(y, s->mx_y, (size_t)pl.N * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
+    *total = pl.N;
+    memset(info, 0, sizeof *info);
+    info->N = pl.N; info->nh = pl.nh; info->L = pl.L; info->E = out.E; info->gn = out.gn; info->pk = pk; info->sg = sg;
+    info->capped = capped ? 1 : 0;
+    info->ir = b.info;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_test_room_conv(ft_ctx* ctx, const float* xs, int64_t n, const float* hn, int64_t L, int64_t predelay,
+                                       int64_t N, float* c) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!xs || !hn || !c || n < 1 || n > chain::MX_MAX_N || L < 1 || L > RM_MAX_L || predelay < 0 || predelay > RS_MAX_RATE || N < 1 ||
+        N > chain::MX_MAX_N)
+        return ft_fail(ctx, FT_ERR_ARG, "ft_test_room_conv: bad argument");
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = s->stream;
+    FT_TRY(room_out(ctx));
+    FT_TRY(cgrow(ctx, &s->mx_x, &s->mx_xcap, (size_t)n));
+    FT_TRY(cgrow(ctx, &s->mx_y, &s->mx_ycap, (size_t)N));
+    FT_TRY(cgrow(ctx, &s->rm_hn, &s->rm_hncap, (size_t)L));
+    FT_HIP(ctx, hipMemcpyAsync(s->mx_x, xs, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipMemcpyAsync(s->rm_hn, hn, (size_t)L * sizeof(float), hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipMemsetAsync(s->rm_out, 0, sizeof(RoomOut), st));
+    RoomConvP cp;
+    memset(&cp, 0, sizeof cp);
+    cp.xs = cp.x = s->mx_x; cp.hn = s->rm_hn; cp.y = s->mx_y; cp.out = s->rm_out;
+    cp.n = (int)n; cp.L = (int)L; cp.predelay = (int)predelay; cp.N = (int)N; cp.raw = 1;
+    room_conv(s, cp);
+    FT_HIP(ctx, hipMemcpyAsync(c, s->mx_y, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, std::string("ft_test_room_conv launch: ") + hipGetErrorString(e));
+    return FT_OK;
 }
 
 // ---- live mix stages (fishtts_hip.h: "Live mix", "Live stereo mix"; the kernels in codec_kernels.h and, mixls_*_kernel, in

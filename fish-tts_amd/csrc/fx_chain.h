@@ -3,8 +3,9 @@
 // (speed, cents) pair, what each stage can emit after so many input samples, the bookkeeping of a stream's three stages from
 // call to call, and the level stage's K-weighting design, gates and gain; behind the join, the mix stage's timeline, checks,
 // duck and gain table (mx_*; tools/mix_check.cpp drives that block), the stereo mix stage's pan regions, pan table and bed
-// sides (ms_*; tools/stereo_check.cpp), the live mix stage's emission (ml_*, MlStage; tools/mix_live_check.cpp) and the live
-// stereo mix stage's per-push regions, pan words and buffer sizes (mls_*; tools/stereo_live_check.cpp).
+// sides (ms_*; tools/stereo_check.cpp), the live mix stage's emission (ml_*, MlStage; tools/mix_live_check.cpp), the live
+// stereo mix stage's per-push regions, pan words and buffer sizes (mls_*; tools/stereo_live_check.cpp) and, between the join
+// and the mix stages, the room stage's send regions, checks, lengths and buffer sizes (rm_*; tools/room_check.cpp).
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
 // are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
@@ -479,6 +480,110 @@ inline MlsSizes mls_sizes(const MlStage& st, const MlPlan& p, int ch) {
     z.prog = (size_t)(p.F - p.base) + 4;
     z.pans = (size_t)(p.F - p.base) + 4;
     z.mc = ch * ((size_t)(mend1 - p.done) + 4);
+    return z;
+}
+
+// ---- room stage (room_*_kernel in room_kernels.h; fishtts_hip.h states it under "Room"): a convolution reverb between the
+// join and the mix stages.  The send regions (ft_send_region: the pan regions' layout and order rules, a send in the pan's
+// place), the checks in their stated order, the impulse response's length at the output rate, L, f, the tail and N
+// (tools/room_check.cpp drives this block).
+constexpr int RM_MAX_L = 131072, RM_MAX_SEND = MX_MAX_DEPTH;
+inline const char* rm_regions(const MsTable& t, long long n) {
+    if (t.R > 0 && !t.reg) return "a null region table with R > 0";
+    if (t.R < 0 || t.R > MS_MAX_REGIONS) return "R outside [0, 4096] send regions";
+    long long at = 0;
+    for (long long r = 0; r < t.R; ++r) {
+        const MsRegion& g = t.reg[r];
+        if (g.a < at || g.a >= g.e || g.e > n) return "a send region out of order or outside [0, n)";
+        if (g.pan < -1 || g.pan > RM_MAX_SEND) return "a send neither -1 nor in [0, 6000] hundredths of a dB";
+        at = g.e;
+    }
+    return nullptr;
+}
+// The send of programme sample j: its region's, `send` outside every region (ms_pan's search).
+inline int rm_send(const MsTable& t, long long j, int send) {
+    long long lo = 0, hi = t.R;
+    while (lo < hi) {
+        const long long mid = (lo + hi) / 2;
+        if (t.reg[mid].e > j) hi = mid; else lo = mid + 1;
+    }
+    return lo < t.R && t.reg[lo].a <= j ? t.reg[lo].pan : send;
+}
+struct RmArgs {
+    int rate = RS_FI;
+    long long n = 0;
+    int channel = -1, normalize = 1, wet = 0, dry = 0, send = 0, ceiling = 1;
+    long long offset = 0, length = 0, fade = 0, predelay = 0, tail = -1;
+    int ir_rate = RS_FI, ir_channels = 1;     // the impulse response's item
+    long long ir_frames = 1;
+    long long nh = -1;                         // >= 0: the response's length at the output rate, given (ft_room_plan)
+};
+// The impulse response's samples at the output rate, as the intake and the resampler count them; -1 where the item's own
+// checks (the intake's, which come last) will refuse it.
+inline long long rm_ir_len(int ir_rate, long long ir_frames, int rate) {
+    int L, M, K;
+    if (ir_frames < 1 || ir_frames > (1LL << 30) || rs_design_in(ir_rate, &L, &M, &K, nullptr)) return -1;
+    const long long n44 = (ir_frames * L + M - 1) / M;
+    if (rs_design(rate, &L, &M, &K, nullptr)) return -1;
+    return K > 0 ? (n44 * L + M - 1) / M : n44;
+}
+struct RmPlan { long long nh = 0, L = 0, f = 0, tl = 0, N = 0; bool send = false; };
+// Null, or why not (*too_long: the refusal is a length); fills *pl.  The order is the header's.
+inline const char* rm_check(const RmArgs& a, const MsTable& regs, bool* too_long, RmPlan* pl) {
+    int L, M, K;
+    *too_long = false;
+    if (const char* e = rs_design(a.rate, &L, &M, &K, nullptr)) return e;
+    if (a.n < 1) return "n must be at least 1";
+    if (const char* e = rm_regions(regs, a.n)) return e;
+    if (a.channel < -1 || a.channel >= a.ir_channels) return "channel outside [-1, channels)";
+    if (a.normalize != 0 && a.normalize != 1) return "normalize must be 0 or 1";
+    if (a.wet < 0 || a.wet > RM_MAX_SEND) return "wet outside [0, 6000] hundredths of a dB";
+    if (a.dry < -1 || a.dry > RM_MAX_SEND) return "dry neither -1 nor in [0, 6000] hundredths of a dB";
+    if (a.send < -1 || a.send > RM_MAX_SEND) return "send neither -1 nor in [0, 6000] hundredths of a dB";
+    if (a.ceiling != 0 && a.ceiling != 1) return "ceiling must be 0 or 1";
+    if (a.offset < 0) return "offset must be >= 0";
+    if (a.length < 0) return "length must be >= 0";
+    if (a.fade < 0) return "fade must be >= 0";
+    if (a.predelay < 0 || a.predelay > a.rate) return "predelay outside [0, sample_rate]";
+    if (a.tail < -1) return "tail must be >= -1";
+    if (a.n > MX_MAX_N) {
+        *too_long = true;
+        return "n exceeds 2^28 samples";
+    }
+    RmPlan p;
+    p.nh = a.nh >= 0 ? a.nh : rm_ir_len(a.ir_rate, a.ir_frames, a.rate);
+    p.send = regs.R > 0 || a.send != 0;
+    if (p.nh < 0) {                            // the item is refused behind these checks, by the intake's own
+        if (pl) *pl = p;
+        return nullptr;
+    }
+    if (p.nh - a.offset < 1) return "offset leaves nothing of the impulse response";
+    p.L = a.length == 0 ? p.nh - a.offset : std::min(a.length, p.nh - a.offset);
+    if (p.L > RM_MAX_L) {
+        *too_long = true;
+        return "the impulse response exceeds 131072 taps: choose a length";
+    }
+    p.f = std::min(a.fade, p.L);
+    p.tl = a.predelay + p.L - 1;
+    if (a.tail > p.tl) return "tail beyond predelay + L - 1";
+    if (a.tail >= 0) p.tl = a.tail;
+    p.N = a.n + p.tl;
+    if (p.N > MX_MAX_N) {
+        *too_long = true;
+        return "n + tail exceeds 2^28 samples";
+    }
+    if (pl) *pl = p;
+    return nullptr;
+}
+// Elements of the stage's device buffers: the programme, the sent programme, t and hn, the block energies, the output.
+struct RmSizes { size_t x = 0, xs = 0, taps = 0, blocks = 0, y = 0; };
+inline RmSizes rm_sizes(const RmArgs& a, const RmPlan& p) {
+    RmSizes z;
+    z.x = (size_t)a.n;
+    z.xs = p.send ? (size_t)a.n : 0;
+    z.taps = (size_t)p.L;
+    z.blocks = (size_t)((p.L + 255) / 256);
+    z.y = (size_t)p.N;
     return z;
 }
 

@@ -36,6 +36,7 @@ class ScriptPlan(NamedTuple):
     rate: int                          # the output rate (Hz)
     n_lines: int
     pans: Optional[List[int]] = None   # stereo: every line's pan in hundredths, -100 hard left (the stereo mix stage's)
+    sends: Optional[List[int]] = None  # room: every line's send in hundredths of a dB of attenuation, -1 muted (the room stage's)
 
 
 MAX_PAN_REGIONS = 4096                 # ft_codec_mix_stereo
@@ -93,7 +94,8 @@ def _samples(ms: int, rate: int) -> int:
 def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, paragraph_pause=0.5,
                 line_pause=0.4, silence_db: Optional[float] = -45.0, max_chars: int = 200, min_chars: int = 24,
                 sample_rate: Optional[int] = None, speed=None, pitch=None, loudness=None, stereo: bool = False,
-                pans: Optional[Dict[str, float]] = None) -> ScriptPlan:
+                pans: Optional[Dict[str, float]] = None, room: bool = False,
+                sends: Optional[Dict[str, float]] = None) -> ScriptPlan:
     """Every check of a script - `lines` a list of Line, or an SSML string (parse_ssml) - and its segments.  Each line is
     split on its own (split_text) and its segments inherit its voice and its output stages: `speed`, `pitch` and `loudness` are the line's, or the call's where the line has None; the
     line's `volume` (dB) is added to that loudness target, which must then exist and stay in [-50, -5].  Every value is
@@ -103,8 +105,12 @@ def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, para
     first audio, as ever.  `stereo`: every line gets a place - its `pan`, else its voice's in `pans` (voice name -> pan),
     else the centre - as ScriptPlan.pans; without it a `pan` or `pans` is refused.  ValueError: no line, a line that is no Line
     or has nothing to speak, a voice that `voices` does not hold, a bad value anywhere, a `pans` key that is no voice of the
-    call, more than 4096 runs of lines at one place other than the centre."""
+    call, more than 4096 runs of lines at one place other than the centre.  `room`: the call has a room - every line gets a send
+    into it from `sends`, a dict whose keys are voice names or line indices (-> dB in [-60, 0], -inf muted): the line's own
+    entry (its index), else its voice's, else 0 dB, as ScriptPlan.sends; without a room `sends` is refused; a key that is
+    neither a voice of the call nor the index of a line is refused, and the limit of `pans` holds for the runs of sends."""
     from .codec_engine import OutputFx
+    from .room import MAX_SEND_REGIONS, native_send
     if isinstance(lines, str):
         lines = parse_ssml(lines)
     call_fx = OutputFx.of(sample_rate, speed, pitch, loudness)          # the call's own values first
@@ -128,7 +134,21 @@ def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, para
             if voices is None or name not in voices:
                 raise ValueError(f"pans: {name!r} is no voice of this call")
         pans = {name: native_pan(f"pans[{name!r}]", v) for name, v in pans.items()}
-    plan = ScriptPlan([], [], [], [], [], jp, rate, len(lines), [] if stereo else None)
+    if not isinstance(room, bool):
+        raise ValueError(f"room must be True or False, got {room!r}")
+    if sends is not None:
+        if not room:
+            raise ValueError("sends needs room=: without a room there is nothing to send to")
+        if not isinstance(sends, dict):
+            raise ValueError("sends must be a dict of voice name -> send in dB")
+        for name in sends:
+            if isinstance(name, int) and not isinstance(name, bool):
+                if not 0 <= name < len(lines):
+                    raise ValueError(f"sends: {name} is no line of this script (it has {len(lines)})")
+            elif voices is None or name not in voices:
+                raise ValueError(f"sends: {name!r} is neither a voice of this call nor a line index")
+        sends = {name: native_send(f"sends[{name!r}]", v) for name, v in sends.items()}
+    plan = ScriptPlan([], [], [], [], [], jp, rate, len(lines), [] if stereo else None, [] if room else None)
     for j, ln in enumerate(lines):
         if not isinstance(ln, Line):
             raise ValueError(f"line {j}: expected a Line, got {type(ln).__name__}")
@@ -139,6 +159,8 @@ def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, para
             raise ValueError(f"line {j}: pan={ln.pan!r} needs stereo=True (the streams are mono)")
         if stereo:
             plan.pans.append(native_pan(f"line {j}: pan", ln.pan) if ln.pan is not None else (pans or {}).get(ln.voice, 0))
+        if room:
+            plan.sends.append((sends or {}).get(j, (sends or {}).get(ln.voice, 0) if ln.voice is not None else 0))
         target = loudness if ln.loudness is None else ln.loudness
         if isinstance(ln.volume, bool) or not isinstance(ln.volume, Real) or not math.isfinite(float(ln.volume)):
             raise ValueError(f"line {j}: volume must be a number of dB, got {ln.volume!r}")
@@ -164,6 +186,10 @@ def plan_script(lines, voices: Optional[Dict[str, list]] = None, pause=0.2, para
         runs = sum(1 for j, q in enumerate(plan.pans) if q != 0 and (j == 0 or plan.pans[j - 1] != q))
         if runs > MAX_PAN_REGIONS:
             raise ValueError(f"{runs} pan regions after merging: the stereo mix stage takes {MAX_PAN_REGIONS} (split the script)")
+    if room:
+        runs = sum(1 for j, q in enumerate(plan.sends) if q != 0 and (j == 0 or plan.sends[j - 1] != q))
+        if runs > MAX_SEND_REGIONS:
+            raise ValueError(f"{runs} send regions after merging: the room stage takes {MAX_SEND_REGIONS} (split the script)")
     return plan
 
 

@@ -26,6 +26,7 @@ class SegmentPlan(NamedTuple):
     line_of: Optional[List[int]] = None   # a script: the line every segment came from (its marks) ...
     n_lines: int = 0                   # ... and the number of its lines
     pans: Optional[List[int]] = None   # a stereo call: every line's pan in hundredths (a long text is one line); None: mono
+    sends: Optional[List[int]] = None  # a script with a room: every line's send in hundredths of a dB of attenuation, -1 muted
 
     def fx_of(self, first: int = 0, end: Optional[int] = None) -> dict:
         """decode_join's keywords for the output stages of segments first .. end - 1."""
@@ -148,13 +149,19 @@ def codes_served(srv, serve_) -> Optional[list]:
         release()
 
 
-def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None):
+def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None, room=None):
     """(audio, cuts) of the whole call: the codes from serve_(srv) while a BatchServer srv = server() is open (None: there
     is none), else from generate_(emit, stopped); one decode_join, under the server's codec lock when it served them.
     `bed`: (clip, mix.MixParams) - the joined piece then goes through the mix stage (vocoder.mix) under the same lock, and
     `audio` is the mixed piece: `lead` samples longer in front, `tail` behind (the cuts are the join's own).  A plan with
     `pans` goes through the stereo mix stage instead (vocoder.mix_stereo), with or without a bed: the regions are the lines'
-    marks from the cuts (script.pan_regions), and `audio` is (N, 2)."""
+    marks from the cuts (script.pan_regions), and `audio` is (N, 2).
+    `room`: (clip, room.RoomParams) - the joined piece first goes through the room stage (vocoder.room) under the same lock,
+    behind the join and before either mix stage: the lines' sends (plan.sends) are its regions, it holds the ceiling itself
+    only where no mix stage follows, and the mix stages see the piece it lengthened by its tail.  In a stereo call the room
+    runs on the mono programme: the pan region that ends with the programme is extended over the tail, so the wet signal is
+    panned with the line that excites it.  The cuts and the lines' marks do not move."""
+    from .room import send_regions
     from .script import line_marks, pan_regions
     srv = server()
     codes = codes_served(srv, serve_)
@@ -165,10 +172,23 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None)
         codes = [got[i] for i in range(len(plan.texts))]
     with lock:
         audio, cuts = vocoder.decode_join(codes, params=plan.jp, gaps=plan.gaps, **plan.fx_of())
+        line_of = plan.line_of if plan.line_of is not None else [0] * len(plan.texts)
+        dry_len = len(audio)
+        if room is not None and len(audio):
+            sends = ()
+            if plan.sends is not None:
+                found = [None] * len(plan.sends)
+                line_marks(line_of, plan.gaps, cuts, found)
+                sends = send_regions(plan.sends, found)
+            audio, _ = vocoder.room(audio, room[0], sends, sample_rate=plan.rate, params=room[1],
+                                    ceiling=plan.pans is None and bed is None)
         if plan.pans is not None and len(audio):
             found = [None] * len(plan.pans)
-            line_marks(plan.line_of if plan.line_of is not None else [0] * len(plan.texts), plan.gaps, cuts, found)
-            audio, _ = vocoder.mix_stereo(audio, None if bed is None else bed[0], pan_regions(plan.pans, found),
+            line_marks(line_of, plan.gaps, cuts, found)
+            regions = pan_regions(plan.pans, found)
+            if regions and regions[-1][1] == dry_len < len(audio):
+                regions[-1] = (regions[-1][0], len(audio), regions[-1][2])     # the room's tail stays where the last line is
+            audio, _ = vocoder.mix_stereo(audio, None if bed is None else bed[0], regions,
                                           sample_rate=plan.rate, params=None if bed is None else bed[1])
         elif bed is not None and len(audio):
             audio, _ = vocoder.mix(audio, bed[0], sample_rate=plan.rate, params=bed[1])

@@ -577,7 +577,8 @@ class FishTTS:
                         pause: float = 0.2, paragraph_pause: float = 0.5, silence_db: Optional[float] = -45.0,
                         max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                         speed: Optional[float] = None, pitch: Optional[float] = None,
-                        loudness: Optional[float] = None, bed=None, stereo: bool = False, pan: float = 0.0) -> bytes:
+                        loudness: Optional[float] = None, bed=None, stereo: bool = False, pan: float = 0.0,
+                        room=None) -> bytes:
         """Extension: a text of any length -> one WAV.  The text is split into segments of at most `max_chars` bytes at
         sentence ends (longform.split_text; pieces below `min_chars` join a neighbour), every segment is an utterance of
         its own - `max_tokens` frames at most each, segment i drawing with seed + i - and all of them run as ONE lock-step
@@ -594,7 +595,9 @@ class FishTTS:
         join its batch.  `bed` (a mix.Bed): music or room tone under the joined piece, ducked where it speaks (the mix
         stage, CodecHipEngine.mix; bed=None: the call as it always was).  `stereo`: a two-channel WAV - the voice at `pan`
         in [-1, 1], -1 hard left, over the bed's own left and right (the stereo mix stage, CodecHipEngine.mix_stereo; with
-        or without a bed).  ValueError before any device work: a pan without stereo or outside [-1, 1], pause /
+        or without a bed).  `room` (a room.Room): a convolution reverb on the joined piece, before the bed and the panning
+        (the room stage, CodecHipEngine.room); the piece rings on for the room's tail.  ValueError before any device work: a
+        bad value in `room` or a response file the intake does not read, a pan without stereo or outside [-1, 1], pause /
         paragraph_pause outside [0, 5] s, silence_db outside
         [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch /
         loudness, a bad value in `bed` or a bed file the intake does not read."""
@@ -602,8 +605,9 @@ class FishTTS:
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
                                loudness, stereo, pan)
         mixed = self._bed_args(bed, plan.rate, silence_db)
+        roomed = self._room_args(room, plan.rate)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        audio, _ = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed)
+        audio, _ = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed, room=roomed)
         return self._to_wav_bytes(audio, plan.rate)
 
     def synthesize_long_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
@@ -612,7 +616,7 @@ class FishTTS:
                                max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                                speed: Optional[float] = None, pitch: Optional[float] = None,
                                loudness: Optional[float] = None, bed=None, live_bed=None, live_stereo: bool = False,
-                               live_pan: float = 0.0) -> Iterator[bytes]:
+                               live_pan: float = 0.0, room=None) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
@@ -628,10 +632,11 @@ class FishTTS:
         over the live_bed's own left and right, or without a bed (the live stereo mix stage,
         CodecHipEngine.mix_stream(stereo=True): one limiter for both channels, so the image stays where it is); where neither
         ceiling binds the chunks concatenate to synthesize_long(stereo=True, pan=live_pan)'s PCM.  ValueError: a live_pan
-        other than 0 without live_stereo, or outside [-1, 1]."""
+        other than 0 without live_stereo, or outside [-1, 1].  `room` is refused (ValueError): see _no_streamed_room."""
         from . import segments
         from .script import native_pan
         _no_streamed_bed(bed, "synthesize_long_stream", live_bed)
+        _no_streamed_room(room, "synthesize_long_stream")
         if not isinstance(live_stereo, bool):
             raise ValueError(f"live_stereo must be True or False, got {live_stereo!r}")
         if native_pan("live_pan", live_pan) != 0 and not live_stereo:
@@ -659,6 +664,48 @@ class FishTTS:
         clip = (data, parse_wav(data))
         self._vocoder._intake_args("bed", [clip], (0.0, 1, 0, 0), None, bed.channel)
         return clip, mp
+
+    # ------------------------------------------------------------------ room (extension)
+    def _room_args(self, room, rate: int):
+        """Every check of a call's `room=`, before any device work: None without one, else (clip, room.RoomParams) as
+        CodecHipEngine.room takes them - the Room's values in their native form at output rate `rate` (room.room_params), its
+        WAV read (wavfile.parse_wav) and judged as the intake judges a clip.  ValueError for a bad value."""
+        if room is None:
+            return None
+        from .room import room_bytes, room_params
+        from .wavfile import parse_wav
+        rp = room_params(room, rate)
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        data = room_bytes(room)
+        clip = (data, parse_wav(data))
+        self._vocoder._intake_args("room", [clip], (0.0, 1, 0, 0), None, room.channel)
+        return clip, rp
+
+    def reverb(self, wav_bytes: bytes, room, report: Optional[list] = None) -> bytes:
+        """Extension: a finished 16-bit mono WAV - at 44.1 kHz or any rate `sample_rate=` takes - through `room` (a
+        room.Room) -> one WAV at the same rate, the room's tail longer (the room stage, CodecHipEngine.room, with its
+        ceiling).  `report`: a list that receives the RoomReport.  ValueError before any device work: not 16-bit mono, no
+        sample, an unsupported rate, a bad Room."""
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        with wave.open(io.BytesIO(wav_bytes), "rb") as wf:
+            if wf.getnchannels() != 1 or wf.getsampwidth() != 2:
+                raise ValueError("reverb: a 16-bit mono WAV is needed")
+            rate = wf.getframerate()
+            audio = np.frombuffer(wf.readframes(wf.getnframes()), dtype=np.int16).astype(np.float32) / 32768.0
+        if not len(audio):
+            raise ValueError("reverb: the WAV holds no sample")
+        rate = _output_fx(rate, None, None).wav_rate            # (ValueError for a rate the output stages do not take)
+        if room is None:
+            raise ValueError("reverb: a Room is needed")
+        clip, rp = self._room_args(room, rate)
+        srv = getattr(self, "_server", None)
+        with (srv.codec_lock if srv is not None else contextlib.nullcontext()):   # the server's codec worker shares the codec context
+            y, rep = self._vocoder.room(audio, clip, (), sample_rate=rate, params=rp, ceiling=True)
+        if report is not None:
+            report.append(rep)
+        return self._to_wav_bytes(y, rate)
 
     def mix(self, wav_bytes: bytes, bed, silence_db: Optional[float] = None, report: Optional[list] = None,
             stereo: bool = False) -> bytes:
@@ -695,7 +742,8 @@ class FishTTS:
 
     # ------------------------------------------------------------------ scripts (extension)
     def _script_plan(self, lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
-                     sample_rate, speed, pitch, loudness, marks, stereo: bool = False, pans=None):
+                     sample_rate, speed, pitch, loudness, marks, stereo: bool = False, pans=None, room: bool = False,
+                     sends=None):
         """Every check of a script call, before any device work: its segments.SegmentPlan, from script.plan_script - every
         segment with its line's references (None where it speaks in the call's voice) and its line's own chain of output
         stages.  ValueError for a bad value, an unknown voice, or more voices than the prefix cache holds: the cache frees
@@ -705,7 +753,7 @@ class FishTTS:
         if marks is not None and not isinstance(marks, list):
             raise ValueError(f"marks must be None or a list, got {type(marks).__name__}")
         plan = plan_script(lines, voices, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
-                           sample_rate, speed, pitch, loudness, stereo, pans)
+                           sample_rate, speed, pitch, loudness, stereo, pans, room, sends)
         used = []
         for v in plan.voices:
             if v is not None and v not in used:
@@ -725,7 +773,7 @@ class FishTTS:
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         return SegmentPlan(plan.texts, [None if v is None else list(voices[v]) for v in plan.voices], plan.gaps,
-                           tuple(plan.jp), plan.rate, plan.fx, plan.line_of, plan.n_lines, plan.pans)
+                           tuple(plan.jp), plan.rate, plan.fx, plan.line_of, plan.n_lines, plan.pans, plan.sends)
 
     def synthesize_script(self, lines, voices=None, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                           top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
@@ -733,7 +781,7 @@ class FishTTS:
                           silence_db: Optional[float] = -45.0, max_chars: int = 200, min_chars: int = 24,
                           sample_rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None,
                           loudness: Optional[float] = None, marks: Optional[list] = None, bed=None, stereo: bool = False,
-                          pans: Optional[dict] = None) -> bytes:
+                          pans: Optional[dict] = None, room=None, sends: Optional[dict] = None) -> bytes:
         """Extension: a script - a dialogue, a narrated piece with quoted speakers - as one WAV.  `lines`: a list of
         script.Line (text, voice, speed, pitch, loudness, volume, pause), or an SSML string (script.parse_ssml: speak, p, s,
         voice, break, prosody); `voices`: name -> list of VoiceProfile.  Every line is split as synthesize_long splits a text
@@ -750,16 +798,21 @@ class FishTTS:
         the bed's `lead` in samples).  `stereo`: a two-channel WAV - every line at its place, its `pan` or else its voice's
         in `pans` (voice name -> pan in [-1, 1], -1 hard left) or else the centre, over the bed's own left and right (the
         stereo mix stage, CodecHipEngine.mix_stereo, with or without a bed; the lines' marks are its regions); `marks` count
-        frames.  ValueError before any device work: a pan or `pans` without stereo, a pan outside [-1, 1], a `pans` key that
+        frames.  `room` (a room.Room): as synthesize_long's, with `sends` - a dict from a voice name or a line index to that
+        voice's or that line's send into the room, dB in [-60, 0] or -math.inf for a line the room does not hear (a narrator
+        kept dry among reverberant speakers); a line takes its own entry, else its voice's, else 0 dB.  `marks` do not move:
+        the room adds only its tail.  ValueError before any device work: `sends` without `room`, a bad send or key,
+        a pan or `pans` without stereo, a pan outside [-1, 1], a `pans` key that
         is no voice of the call, no line, an unknown voice, a bad value in a line or in the call, a bad
         line_pause, more distinct voices than the reference cache holds (8; not with cache_reference_kv=False)."""
         from . import segments
         from .script import line_marks
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
-                                 min_chars, sample_rate, speed, pitch, loudness, marks, stereo, pans)
+                                 min_chars, sample_rate, speed, pitch, loudness, marks, stereo, pans, room is not None, sends)
         mixed = self._bed_args(bed, plan.rate, silence_db)
+        roomed = self._room_args(room, plan.rate)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
-        audio, cuts = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed)
+        audio, cuts = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed, room=roomed)
         if marks is not None:
             found = [None] * plan.n_lines
             line_marks(plan.line_of, plan.gaps, cuts, found, at=0 if mixed is None else mixed[1].lead)
@@ -773,7 +826,7 @@ class FishTTS:
                                  min_chars: int = 24, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                                  pitch: Optional[float] = None, loudness: Optional[float] = None,
                                  marks: Optional[list] = None, bed=None, live_bed=None, live_stereo: bool = False,
-                                 live_pans: Optional[dict] = None) -> Iterator[bytes]:
+                                 live_pans: Optional[dict] = None, room=None, sends: Optional[dict] = None) -> Iterator[bytes]:
         """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
         (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
@@ -786,10 +839,12 @@ class FishTTS:
         bed (the live stereo mix stage, CodecHipEngine.mix_stream(stereo=True): every joined group is pushed with the regions
         of its lines, one limiter for both channels); where neither ceiling binds the chunks concatenate to
         synthesize_script(stereo=True, pans=live_pans)'s PCM; `marks` count frames.  ValueError: `live_pans` without
-        live_stereo; a Line.pan without it stays refused, as a stereo value on a mono stream."""
+        live_stereo; a Line.pan without it stays refused, as a stereo value on a mono stream.  `room` and `sends` are refused
+        (ValueError): see _no_streamed_room."""
         from . import segments
         from .script import line_marks
         _no_streamed_bed(bed, "synthesize_script_stream", live_bed)
+        _no_streamed_room(room, "synthesize_script_stream", sends)
         if not isinstance(live_stereo, bool):
             raise ValueError(f"live_stereo must be True or False, got {live_stereo!r}")
         if live_pans is not None and not live_stereo:
@@ -1096,6 +1151,16 @@ def _check_sampling(temperature: float, top_p: float, repetition_penalty: float)
     assert 0 < top_p <= 1, "top_p must be in (0, 1]"
     assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
     assert 0 < temperature < 2, "temperature must be in (0, 2)"
+
+
+def _no_streamed_room(room, what: str, sends=None) -> None:
+    """A stream takes no `room=`: the room stage convolves the whole piece in one call - its tail rings past every later
+    line, and its ceiling is one gain known only when the last sample is.  A live form that carries the tail from push to
+    push does not exist yet."""
+    if room is not None or sends is not None:
+        raise ValueError(f"room needs the whole piece: {what} hands out audio before its end, while the room stage's tail "
+                         "rings over everything that follows and its ceiling is one gain for the piece; use synthesize_long / "
+                         "synthesize_script with room=, or reverb() on the finished WAV")
 
 
 def _no_streamed_bed(bed, what: str, live_bed=None) -> None:

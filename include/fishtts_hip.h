@@ -662,6 +662,79 @@ ft_status ft_codec_mix_stereo(ft_ctx* ctx, const float* x, int64_t n, int32_t sa
                               int32_t* duck, ft_mix_info* info);
 /* Host only: U[0 .. 200]. */
 ft_status ft_pan_gains(float* table);
+/* Room.  A convolution reverb behind the join: codec -> ... -> join -> room -> mix | stereo mix.  The programme, weighted
+ * region by region by a send, is convolved with a room's impulse response (IR) in direct form and added to the dry programme.
+ * The convolution runs on the f32-input MFMA, whose result is a k-ordered float32 fmaf chain, so the stage is stated to the
+ * bit like Mix; an FFT convolution could not be.  Mix, Stereo mix and their live forms stay as they are.  Stated, which fixes
+ * every bit of the result for finite inputs:
+ *   Inputs: the programme x[0 .. n), float32 at Fo (any rate ft_resample_filter accepts), n >= 1; one IR item (its `channel`
+ *   field is not read: rp->channel stands for it, -1 the mean of all channels, as in Mix); R send regions, 0 <= R <= 4096,
+ *   ft_send_region {a, e, send} each with 0 <= a < e <= n, sorted and disjoint (they may touch); a send is an attenuation in
+ *   hundredths of a dB in [0, 6000], or -1 for muted; s(i) is the send of the region that holds i, rp->send where none does.
+ *   ft_room_params, sample counts at Fo: wet in [0, 6000], dry in [0, 6000] or -1 for no dry signal, predelay in [0, Fo],
+ *   offset >= 0, length >= 0 (0: all of it), fade >= 0, tail >= -1, normalize and ceiling 0 or 1.
+ *   Impulse response: ir44 is, bit for bit, the piece ft_codec_intake gives for the item with channel = rp->channel,
+ *   jp = (0, 1, 0, 0) and loudness 0; irF is, bit for bit, what resample_kernel gives for the whole of ir44 from zero state in
+ *   one final call (ft_test_resample), at Fo = 44100 ir44 itself - exactly as Mix prepares its bed.  Its length is nh;
+ *   nh - offset < 1 is FT_ERR_ARG.  L = nh - offset with length = 0, else min(length, nh - offset); L > 131072 is
+ *   FT_ERR_TOO_LONG: the caller chooses a length, nothing is cut silently.  f = min(fade, L); t[k] = irF[offset + k], and for
+ *   k >= L - f it is multiplied once by ramp(L - 1 - k), the join's ramp with fade length f.
+ *   Energy: e_b = the sum over k ascending inside block b of 256 taps of (double) t[k] (double) t[k], every product exact and
+ *   every addition rounded to float64; E = the sum of the e_b, b ascending.  With normalize gn = (float)(1 / sqrt(E)), float64
+ *   rounded once, and E = 0 or a non-finite E is FT_ERR_ARG after the launches; without it gn = 1.  hn[k] = t[k] gn, one
+ *   float32 product.
+ *   Send: with T the table of ft_mix_gains, xs[i] = x[i] T[s(i)], one float32 product, and +0.0 where s(i) = -1.
+ *   Length: N = n + tl; tl = predelay + L - 1 with tail = -1, else tl = tail, and tail > predelay + L - 1 is FT_ERR_ARG.
+ *   Convolution: for i in [0, N), acc = +0.0; for k = 0 .. L - 1 ascending acc = fmaf(hn[k], xs[i - predelay - k], acc), xs
+ *   being +0.0 outside [0, n): one unbroken chain, no partial sums, no split over the taps with a later addition.
+ *   c[i] = acc + 0.0 (a chain that ends at -0.0 gives +0.0).
+ *   Sum: y[i] = T[dry] x[i] + T[wet] c[i], both products and the sum rounded to float32 on their own; x is +0.0 at i >= n,
+ *   and with dry = -1 the first term is +0.0.
+ *   Ceiling, with ceiling = 1: Mix's rule - pk = max |y| (a NaN is never the peak), c = 10^(-1/20); if pk > c every sample is
+ *   multiplied once by sg = (float)(c / pk) (float64, rounded once), else nothing more touches a sample.  With ceiling = 0
+ *   (a mix stage follows and has the ceiling) nothing more touches a sample and pk is still reported.
+ *   Non-finite values: the call does not look for them.  If x[j] is not finite every y[i] with i outside
+ *   [j - 1024, j + predelay + L + 1024) is still as stated; inside that range any value may stand (the kernel pads the chain
+ *   with terms 0 x).  float32 subnormals are kept.
+ *   It follows: a one-sample IR of 1.0 with wet = 0, dry = -1, no predelay and no regions gives y = x (a -0.0 becomes +0.0);
+ *   muting every send gives y[i] = T[dry] x[i] and then tl zeros; a call repeated gives the same bits (no floating-point
+ *   atomics; the peak is a max); shifting predelay by p shifts c by p.
+ *   In a stereo call the room stage runs on the mono programme, before the panning: the last pan region is extended over
+ *   the tail, so the wet signal is panned with the programme that excites it.
+ *   Reported (ft_room_info): N, nh, L, E, gn, pk, sg (1 when not capped), capped, the IR's ft_intake_info.
+ * Every argument is checked before any device work and a refused call changes nothing.  The checks, in this order: a null
+ * pointer; sample_rate; n < 1; the regions (Stereo mix's region checks, a send in the pan's place); channel as the intake judges
+ * it; normalize; wet; dry; send; ceiling; offset; length; fade; predelay; tail < -1 (FT_ERR_ARG each); n beyond 2^28
+ * (FT_ERR_TOO_LONG); nh - offset < 1 (FT_ERR_ARG); L (FT_ERR_TOO_LONG); tail beyond predelay + L - 1 (FT_ERR_ARG); N beyond
+ * 2^28 (FT_ERR_TOO_LONG); capacity < N (FT_ERR_ARG); then the IR as ft_codec_intake judges an item (an item whose rate or
+ * frame count the intake refuses has no nh: the checks that need it are passed over and the intake's refusal stands).
+ * Lock and stream are the codec's, as for Mix.
+ * On the device: the programme and the output in the mix stage's buffers, the sent programme, t, hn, one float64 per block of
+ * taps.  Launches beyond the IR's preparation: room_ir_kernel (offset, fade, block energies), room_gain_kernel (E and gn by one
+ * thread, then hn), room_send_kernel (left out without regions and with rp->send = 0: the chain then reads x),
+ * room_conv_kernel (the chain on v_mfma_f32_32x32x2_f32 with the sum and the peak; 2^22 outputs per launch), and
+ * mix_scale_kernel when the ceiling binds. */
+typedef struct ft_send_region {
+    int64_t a, e;
+    int32_t send, reserved;
+} ft_send_region;
+typedef struct ft_room_params {
+    int32_t channel, normalize, wet, dry, send, ceiling;
+    int64_t offset, length, fade, predelay, tail;
+} ft_room_params;
+typedef struct ft_room_info {
+    int64_t N, nh, L;
+    double E;
+    float gn, pk, sg;
+    int32_t capped;
+    ft_intake_info ir;
+} ft_room_info;
+ft_status ft_codec_room(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_send_region* regions, int32_t R,
+                        const ft_intake_item* ir, const ft_room_params* rp, float* y, int64_t capacity, int64_t* total,
+                        ft_room_info* info);
+/* Host only: L and N of a call whose IR has nh samples at the output rate.  Either output pointer may be NULL.  FT_ERR_ARG /
+ * FT_ERR_TOO_LONG as ft_codec_room judges the values. */
+ft_status ft_room_plan(int32_t sample_rate, int64_t n, int64_t nh, const ft_room_params* rp, int64_t* L, int64_t* N);
 /* Live mix.  The mix stage on a stream: synthesize_long_stream and synthesize_script_stream hand out audio before the piece
  * ends, and the one gain of Mix's ceiling is known only there.  Everything in Mix before the ceiling is local in time, so this
  * second stage keeps it as it is and replaces the one gain by a look-ahead limiter with the duck's own cone shape, driven by

@@ -152,6 +152,12 @@ ft_status ft_test_qkv0_tab(ft_ctx* ctx, int32_t row0, int32_t rows, uint16_t* ou
  * (zeros before and after it) -> y: *n_out = ft_resampled_len(sample_rate, n) samples. */
 ft_status ft_test_resample(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, float* y, int64_t* n_out);
 
+/* Test hook: the room stage's convolution launches alone (ft_codec_room; "Room") on taps the caller gives: c[i], i in [0, N),
+ * is the stated chain over hn[0 .. L) and xs[0 .. n) with `predelay`.  1 <= n, N <= 2^28, 1 <= L <= 131072, 0 <= predelay
+ * <= 48000; FT_ERR_ARG otherwise, before any device work. */
+ft_status ft_test_room_conv(ft_ctx* ctx, const float* xs, int64_t n, const float* hn, int64_t L, int64_t predelay, int64_t N,
+                            float* c);
+
 /* Test hook: the time-scale stage of ft_codec_decode_fx alone on a host waveform x of n <= max_frames * frame_len samples
  * at 44100 -> y: *n_out = ft_timescaled_len(speed_pct, n) samples; deltas (may be NULL) receives the chosen d_k of the
  * *n_frames = ceil(*n_out / 512) + 1 frames. */
