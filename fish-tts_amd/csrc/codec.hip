@@ -1,4 +1,4 @@
-// DAC codec decode (DAC.decode, vocoder.py:906-912) on the tap-GEMM kernels of codec_kernels.h.
+// DAC codec decode (DAC.decode, vocoder.py:906-912) on the tap-GEMM kernels of gemm_kernels.h.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -10,6 +10,7 @@
 #include <numeric>
 
 #include "codec_kernels.h"
+#include "stage_kernels.h"
 #include "stereo_kernels.h"
 #include "room_kernels.h"
 #include "engine.h"
@@ -25,7 +26,7 @@ static_assert(chain::RS_LDS == RS_LDS && chain::TS_N == TS_N && chain::TS_HS == 
               chain::TS_CARRY == TS_CARRY && chain::PS_SHIFT == PS_SHIFT && chain::PS_PHASES == PS_PHASES &&
               chain::LV_WARM_HOPS == LV_WARM && chain::RD_A == RD_LOOK && chain::RD_R == RD_SLEW &&
               chain::MX_MAX_W == MX_MAX_WIN && chain::MX_MAX_N <= (1LL << 28),
-              "fx_chain.h and codec_kernels.h disagree");
+              "fx_chain.h and stage_kernels.h disagree");
 static_assert(sizeof(ft_level_info) == 32 && offsetof(LevelItem, L) + sizeof(ft_level_info) == sizeof(LevelItem) &&
               offsetof(ft_level_info, peak) == 8 && offsetof(ft_level_info, capped) == 24 &&
               offsetof(LevelItem, target) == offsetof(LevelItem, L) + 28,
@@ -672,7 +673,7 @@ static int gemm(hipStream_t st, const ConvW& w, const GemmIO& io) {
         const bool vec_ok = io.act != ACT_SWIGLU && w.N % 8 == 0 && w.n_mod % 8 == 0 && io.ldo % 8 == 0 && io.ldr % 8 == 0;
         const bool k64 = w.K % 64 == 0;
         // many rows (the decoder's convolutions after the first up-sampling): 128-row tiles on 8 waves - the 64 x 64 tile is
-        // bound by the L2 bandwidth its weight-tile re-reads need (codec_kernels.h)
+        // bound by the L2 bandwidth its weight-tile re-reads need (gemm_kernels.h)
 #define FT_TG8(BM_, BN_, BK_, NWM_, NWN_)                                                                       \
     do {                                                                                                          \
         constexpr size_t lds8_ = std::max((size_t)((BM_ + 56) + 2 * BN_) * (BK_ + 8) * 2,                         \
@@ -937,7 +938,7 @@ static ft_status ps_alloc(ft_ctx* ctx) {
     return FT_OK;
 }
 
-// ---- level stage (LevelTab and the three kernels in codec_kernels.h; fishtts_hip.h states it, fx_chain.h designs it)
+// ---- level stage (LevelTab and the three kernels in stage_kernels.h; fishtts_hip.h states it, fx_chain.h designs it)
 struct LevelJob { int rate = 0, target = 0; ft_level_info* info = nullptr; };   // the level of a one-item call (call_tail)
 
 // A device buffer of at least `need` elements: allocated on first use, replaced by a larger one when a call needs more.
@@ -1100,7 +1101,7 @@ static ft_status rs_enqueue(ft_ctx* ctx, std::vector<RsSeg>& segs, float* host, 
     return FT_OK;
 }
 
-// ---- ride stage (RdSeg and the three kernels in codec_kernels.h; fishtts_hip.h states it, fx_chain.h plans it)
+// ---- ride stage (RdSeg and the three kernels in stage_kernels.h; fishtts_hip.h states it, fx_chain.h plans it)
 constexpr size_t RD_MAX_HELD = (size_t)(chain::RD_A + 1) * (RS_MAX_RATE / 10);   // a stream holds back less than this
 
 // The segment table and room for `need` emitted samples.
@@ -1880,7 +1881,7 @@ extern "C" ft_status ft_test_level_hops(ft_ctx* ctx, double* hops, int64_t capac
     return FT_OK;
 }
 
-// ---- join stage (fishtts_hip.h: ft_codec_decode_join; JoinTab and the three kernels in codec_kernels.h, the argument
+// ---- join stage (fishtts_hip.h: ft_codec_decode_join; JoinTab and the three kernels in stage_kernels.h, the argument
 // checks and the layout of the input buffer in join_plan.h)
 // Room for `in` input and `out` output samples: allocated on the first call, replaced by larger buffers when a call needs more.
 static ft_status join_alloc(ft_ctx* ctx, size_t in, size_t out) {
@@ -2537,7 +2538,7 @@ extern "C" int32_t ft_codec_enc_frame_len(const ft_ctx* ctx) { return ctx && ctx
 extern "C" int32_t ft_codec_frame_len(const ft_ctx* ctx) { return ctx && ctx->codec ? ctx->codec->frame_len : 0; }
 
 // ---- reference intake (fishtts_hip.h: ft_intake_filter .. ft_codec_encode_items; IntakeSeg and intake_kernel in
-// codec_kernels.h, the filter design in fx_chain.h)
+// stage_kernels.h, the filter design in fx_chain.h)
 static_assert(sizeof(ft_intake_info) == 80 && offsetof(ft_intake_info, level) == 48, "ft_intake_info layout");
 constexpr int64_t IN_MAX_RAW = (int64_t)1 << 30;
 
@@ -2713,7 +2714,7 @@ extern "C" ft_status ft_codec_encode_items(ft_ctx* ctx, int32_t B, const ft_inta
     return intake_run(ctx, "ft_codec_encode_items", B, items, jp, loudness, true, nullptr, codes, capacity_frames, nullptr, infos);
 }
 
-// ---- mix stage (fishtts_hip.h: ft_codec_mix, ft_mix_plan, ft_mix_gains; the kernels in codec_kernels.h, the checks, the hop
+// ---- mix stage (fishtts_hip.h: ft_codec_mix, ft_mix_plan, ft_mix_gains; the kernels in stage_kernels.h, the checks, the hop
 // and the table in fx_chain.h).  The four mix stages - mix, stereo mix, live mix, live stereo mix - share one host path:
 // mix_args / mix_refuse judge the values, mix_bed prepares the bed, mix_whole is the whole-call walk of the first two,
 // ml_begin / ml_push / ml_live the stream of the last two; `pans` (a region table) is what makes a call or a push stereo.
@@ -2758,7 +2759,7 @@ static_assert(sizeof(ft_pan_region) == sizeof(chain::MsRegion) && sizeof(ft_pan_
               offsetof(ft_pan_region, pan) == offsetof(chain::MsRegion, pan) && offsetof(ft_pan_region, pan) == offsetof(MixPan, pan) &&
               offsetof(ft_pan_region, e) == 8 && sizeof(ft_pan_region) == 24, "ft_pan_region layout");
 static_assert(2 * chain::MS_MAX_PAN + 1 == MS_PANS && chain::MS_MAX_PAN == MS_CENTRE && MX_SPAN == 4096,
-              "fx_chain.h and codec_kernels.h disagree on the stereo mix stage");
+              "fx_chain.h and stereo_kernels.h disagree on the stereo mix stage");
 
 extern "C" ft_status ft_pan_gains(float* table) {
     if (!table) return FT_ERR_ARG;
@@ -3145,7 +3146,7 @@ extern "C" ft_status ft_test_room_conv(ft_ctx* ctx, const float* xs, int64_t n, 
     return FT_OK;
 }
 
-// ---- live mix stages (fishtts_hip.h: "Live mix", "Live stereo mix"; the kernels in codec_kernels.h and, mixls_*_kernel, in
+// ---- live mix stages (fishtts_hip.h: "Live mix", "Live stereo mix"; the kernels in stage_kernels.h and, mixls_*_kernel, in
 // stereo_kernels.h; the emission, the stream's counters, the per-push region check, the pan words and the buffer sizes in
 // fx_chain.h).  A stream owns its prepared bed, its two pairs of carries, its per-hop arrays and the four words it reports;
 // a push stages its samples in the context's buffers and ends with one wait, so nothing of a push outlives it.  A stereo
@@ -3153,7 +3154,7 @@ extern "C" ft_status ft_test_room_conv(ft_ctx* ctx, const float* xs, int64_t n, 
 // its m carries and in what it emits.
 static_assert(chain::MLS_WORD == 16 && MS_CENTRE == chain::MS_MAX_PAN, "fx_chain.h and stereo_kernels.h disagree on the pan bytes");
 static_assert(chain::ML_LA == ML_ATTACK && chain::ML_LR == ML_RELEASE && RS_MAX_RATE / 50 / 4 + 1 <= MX_THREADS &&
-              chain::ML_MAX_FADE == (1LL << 30), "fx_chain.h and codec_kernels.h disagree on the live mix stage");
+              chain::ML_MAX_FADE == (1LL << 30), "fx_chain.h and stage_kernels.h disagree on the live mix stage");
 static_assert(sizeof(ft_mix_live_info) == 128 && offsetof(ft_mix_live_info, bed) == 48, "ft_mix_live_info layout");
 
 struct ft_mix_stream {

@@ -4,7 +4,9 @@
 #include "ar_kernels.h"
 #include "frame_engine.h"
 #include "wide_kernels.h"
+#include "gemm_kernels.h"
 #include "codec_kernels.h"
+#include "stage_kernels.h"
 
 #include <math.h>
 
@@ -907,7 +909,7 @@ struct ArTraceScope {
 static void tr_uploaded(ft_ctx* ctx, std::initializer_list<int> ids) { if (ctx->trace) ctx->trace->uploaded.assign(ids); }
 static void tr_pos(ft_ctx* ctx, int t) { if (ctx->trace) ctx->trace->pos_prefix = tr_name("t%d.", t); }
 
-struct PfX {   // fused RMSNorm hooks of the skinny kernel (codec_kernels.h TapGemmP)
+struct PfX {   // fused RMSNorm hooks of the skinny kernel (gemm_kernels.h TapGemmP)
     const void* gain = nullptr;   // normalise the X rows with this gain ...
     const float* ss_in = nullptr; // ... and the producer's partial sums of squares (nblk per row)
     int nblk = 0;

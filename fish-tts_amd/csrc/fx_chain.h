@@ -7,7 +7,7 @@
 // stereo mix stage's per-push regions, pan words and buffer sizes (mls_*; tools/stereo_live_check.cpp) and, between the join
 // and the mix stages, the room stage's send regions, checks, lengths and buffer sizes (rm_*; tools/room_check.cpp).
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
-// are those of the kernels (codec_kernels.h); codec.hip asserts that the two sets agree.
+// are those of the kernels (stage_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -1,6 +1,7 @@
 // The room stage's kernels (ft_codec_room; stated in fishtts_hip.h under "Room"): a convolution reverb behind the join, the
 // programme convolved with an impulse response in direct form on the f32-input MFMA, whose result is a k-ordered f32 fmaf
-// chain and can therefore be stated to the bit.  Included behind stereo_kernels.h by codec.hip alone, for that header's reason.
+// chain and can therefore be stated to the bit.  It builds on stage_kernels.h (mix_scale_kernel) and is included by codec.hip
+// alone, behind stereo_kernels.h and for that header's reason: engine.hip sees neither, so nothing here moves the AR engine.
 //   room_ir_kernel    one lane per block of 256 taps: t[k] = irF[offset + k] with the fade on the last f taps, and the block's
 //                     energy e_b in float64, k ascending
 //   room_gain_kernel  one workgroup: lane 0 adds the e_b ascending to E and rounds gn; every lane then writes hn = t gn
@@ -8,7 +9,7 @@
 //   room_conv_kernel  the chain, and behind it the sum with the dry signal and the workgroup's peak (below)
 //   mix_scale_kernel  as it is, when the ceiling binds
 #pragma once
-#include "stereo_kernels.h"
+#include "stage_kernels.h"
 
 namespace ft {
 

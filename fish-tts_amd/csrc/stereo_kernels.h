@@ -1,10 +1,10 @@
 // The stereo mix stage's kernels (ft_codec_mix_stereo; stated in fishtts_hip.h under "Stereo mix"): mix_stereo_kernel and the
-// two kernels of the pair level.  They build on codec_kernels.h - MixP, mix_prog, mix_sample, the level table - and are
-// included behind it by codec.hip alone: engine.hip includes codec_kernels.h, so a kernel added there lands in the AR
+// two kernels of the pair level.  They build on stage_kernels.h - MixP, mix_prog, mix_sample, the level table - and are
+// included behind it by codec.hip alone: engine.hip includes stage_kernels.h, so a kernel added there lands in the AR
 // engine's code object as well and moves its kernels (measured: 0.7 % of bench.py's tokens per second; DESIGN section 8,
-// "Stereo").
+// "Stereo" and "Kernel headers").
 #pragma once
-#include "codec_kernels.h"
+#include "stage_kernels.h"
 
 namespace ft {
 

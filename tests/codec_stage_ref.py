@@ -117,7 +117,7 @@ from oracle import codec as OC
 
 U = 2.0 ** -24
 LIB = 2.0 ** -20            # erff / expf / tanhf: 16 f32 ulp, 2048 times below the bf16 step
-SIN_ABS = 1e-6              # __sinf, as snake_f's comment in csrc/codec_kernels.h claims
+SIN_ABS = 1e-6              # __sinf, as snake_f's comment in csrc/gemm_kernels.h claims
 MARGIN = 4.0                # E = MARGIN * r_stage * S
 R_ORDER_ROWS, R_ORDER_COLS = 256, 48
 F64, F32 = torch.float64, torch.float32

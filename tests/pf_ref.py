@@ -2,11 +2,11 @@
 infrastructure, the sibling of tests/codec_stage_ref.py and tests/wide_ref.py, whose number-format helpers, three-order
 `r_stage` measurement, MARGIN, `reach`, `_norm_rope`, epilogue error terms, `check` and `Verdict` it reuses).
 
-The launches are restated from oracle/ar.py (rms_norm, _mlp, _block, _attention, rope) as codec_kernels.h / ar_kernels.h cite
+The launches are restated from oracle/ar.py (rms_norm, _mlp, _block, _attention, rope) as gemm_kernels.h / ar_kernels.h cite
 llama.py:
 
   linear_ref   a bf16 x bf16 contraction with f32 accumulation, then one of the four forms prefill_gemm uses (epilogues of
-               codec_kernels.h: tapgemm_epilogue, tapgemm_epilogue_lds, skinny_gemm_kernel):
+               gemm_kernels.h: tapgemm_epilogue, tapgemm_epilogue_lds, skinny_gemm_kernel):
                    WQKV   round16(acc + bias), stored as f32
                    RESID  round16(round16(acc + bias) + resid), resid f32, stored as f32 (wo, w2; in place or two buffers)
                    W13    round16(round16(silu(round16 gate)) * round16 up), weight rows (2i, 2i + 1) = (gate, up), stored as bf16

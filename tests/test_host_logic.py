@@ -507,3 +507,19 @@ def test_prefix_cache_is_lru_and_keyed_by_content():
     assert cache.get(eng, a) is not ha and eng.built == 5
     cache.clear()
     assert len(cache) == 0
+
+
+def test_kernel_headers_the_ar_engine_sees():
+    """engine.hip's code object holds the kernels of gemm_kernels.h, codec_kernels.h and stage_kernels.h, in that order, although
+    it launches the first header's alone: without the other two its own kernels move and bench.py measures slower (DESIGN
+    section 8, "Kernel headers").  The stereo and room stages' headers stay out of it; that is what keeps work on them from
+    moving the AR engine."""
+    from fish_tts_amd import _lib
+    deps = {os.path.basename(p) for p in _lib._deps(os.path.join(_lib.CSRC, "engine.hip"))}
+    assert {"ar_kernels.h", "gemm_kernels.h", "codec_kernels.h", "stage_kernels.h"} <= deps
+    assert not deps & {"stereo_kernels.h", "room_kernels.h"}
+    with open(os.path.join(_lib.CSRC, "engine.hip")) as f:
+        inc = [line.split('"')[1] for line in f if line.startswith('#include "') and line.split('"')[1].endswith("_kernels.h")]
+    assert inc[-3:] == ["gemm_kernels.h", "codec_kernels.h", "stage_kernels.h"]
+    codec = {os.path.basename(p) for p in _lib._deps(os.path.join(_lib.CSRC, "codec.hip"))}
+    assert {"gemm_kernels.h", "codec_kernels.h", "stage_kernels.h", "stereo_kernels.h", "room_kernels.h"} <= codec

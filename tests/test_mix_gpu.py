@@ -3,7 +3,7 @@ restatement tests/mix_ref.py.  The bed at the output rate comes from the existin
 so the stage is compared from the timeline onward, and every comparison is exact: D_k, N, the counts, every sample's bits,
 pk, sg.  Fo = 8000 (H = 160) unless a rate is the point.
 
-SPAN is what one workgroup of mix_kernel covers: 256 lanes x 4 samples x 4 steps (codec_kernels.h: MX_SPAN)."""
+SPAN is what one workgroup of mix_kernel covers: 256 lanes x 4 samples x 4 steps (stage_kernels.h: MX_SPAN)."""
 import ctypes as C
 
 import numpy as np

@@ -4,7 +4,7 @@ from the existing calls - intake() per channel, then the resampler hook - so the
 and every comparison is exact: D_k, N, the counts, every sample's bits in both channels, pk, sg.  The pair level is the one
 figure that is not: L against the restatement within 1e-9 LU, and g within one float32 step of the restatement's (2^-23
 relative, plus the 1.2e-10 that 1e-9 LU moves a gain) - the sides are then scaled by the g the call reports, and compared
-bit for bit.  Fo = 8000 (H = 160); SPAN is what one workgroup of mix_stereo_kernel covers (codec_kernels.h: MX_SPAN)."""
+bit for bit.  Fo = 8000 (H = 160); SPAN is what one workgroup of mix_stereo_kernel covers (stage_kernels.h: MX_SPAN)."""
 import ctypes as C
 
 import numpy as np

@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "ar_kernels.h"
-#include "codec_kernels.h"
+#include "gemm_kernels.h"
 using namespace ft;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("ERR %s line %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
