@@ -199,6 +199,13 @@ SYMBOLS = {
                                   _P, C.c_int64, _P, C.POINTER(ft_room_info)]),
     "ft_room_plan": (C.c_int32, [C.c_int32, C.c_int64, C.c_int64, C.POINTER(ft_room_params), _P, _P]),
     "ft_test_room_conv": (C.c_int32, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "ft_codec_room_stream_begin": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_room_params), C.POINTER(_P)]),
+    "ft_codec_room_stream_push": (C.c_int32, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "ft_codec_room_stream_info": (C.c_int32, [_P, C.POINTER(ft_room_info)]),
+    "ft_codec_room_stream_end": (None, [_P]),
+    "ft_codec_room_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_room_params),
+                                       _P, C.c_int64, _P, C.POINTER(ft_room_info)]),
+    "ft_codec_mix_stream_begin_bare": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_mix_params), C.POINTER(_P)]),
     "ft_mix_live_plan": (C.c_int32, [C.c_int32, C.POINTER(ft_mix_params), C.c_int64, C.c_int32, _P, _P]),
     "ft_codec_mix_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), _P,
                                       C.c_int64, _P, _P, _P, C.POINTER(ft_mix_live_info)]),

@@ -130,6 +130,49 @@ def send_region_table(what: str, regions, n: int):
     return reg, len(regions)
 
 
+class RoomStream:
+    """An open stream of the live room stage (ft_codec_room_stream_*; CodecHipEngine.room_stream makes one): push(x, regions)
+    takes the next programme samples with the send regions of that push - (a, e, send) each, relative to the push - and
+    returns the roomed samples for exactly those inputs; push(x, regions, final=True) ends the programme and returns its
+    samples and the room's tail behind them.  Nothing is held back, and the pushes concatenate to room(..., ceiling=False) of
+    the whole programme, bit for bit, however they are cut.  report(): a RoomReport of the stream so far (`n` the samples
+    emitted, `peak` over the pushes so far).  close() frees the stream's device state (a closed stream refuses pushes)."""
+
+    def __init__(self, engine, handle, tail: int):
+        self._eng, self._h, self._tail = engine, handle, tail
+
+    def push(self, x=None, regions=(), final: bool = False) -> np.ndarray:
+        if self._h is None:
+            raise RuntimeError("room stream: closed")
+        x = np.zeros(0, dtype=np.float32) if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+        table = send_region_table("room stream push", regions, len(x))
+        eng = self._eng
+        cap = len(x) + (self._tail if final else 0)
+        y = np.empty(max(cap, 1), dtype=np.float32)
+        n = C.c_int64(0)
+        eng._check(eng.lib.ft_codec_room_stream_push(self._h, x.ctypes.data_as(C.c_void_p), len(x), *table, 1 if final else 0,
+                                                     y.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "ft_codec_room_stream_push")
+        return y[:n.value]
+
+    def report(self) -> RoomReport:
+        if self._h is None:
+            raise RuntimeError("room stream: closed")
+        info = L.ft_room_info()
+        self._eng._check(self._eng.lib.ft_codec_room_stream_info(self._h, C.byref(info)), "ft_codec_room_stream_info")
+        return RoomReport.of(info)
+
+    def close(self) -> None:
+        if self._h is not None:
+            self._eng.lib.ft_codec_room_stream_end(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 @dataclass(frozen=True)
 class MixLiveReport:
     """What the live mix stage did (ft_mix_live_info): `n`, `bed_len`, `hops`, `active`, `duck_max` and `bed` as MixReport's;
@@ -900,6 +943,50 @@ class CodecHipEngine:
         del keep
         return y[:total.value], RoomReport.of(info)
 
+    def _room_live_args(self, what: str, clip, sample_rate, params):
+        """(rate, IR item array, what keeps its bytes alive, ft_room_params with ceiling 0, tail) of a live room call, checked
+        as room() checks them; the tail is Room's tl for these values (ft_room_plan)."""
+        from .room import Room, RoomParams, room_params
+        rate = OutputFx.of(sample_rate=sample_rate).wav_rate
+        if params is None:
+            params = room_params(Room(b""), rate)
+        if not isinstance(params, RoomParams):
+            raise ValueError(f"{what}: params must be a RoomParams, got {type(params).__name__}")
+        items, keep, _, _ = self._intake_args(what, [clip], (0.0, 1, 0, 0), None, None if params.channel < 0 else params.channel)
+        rp = L.ft_room_params(params.channel, params.normalize, params.wet, params.dry, params.send, 0,
+                              params.offset, params.length, params.fade, params.predelay, params.tail)
+        nh = int(self.lib.ft_resampled_len(rate, int(self.lib.ft_intake_len(items[0].rate, items[0].n_frames))))
+        N = C.c_int64(0)
+        self._check(self.lib.ft_room_plan(rate, 1, nh, C.byref(rp), None, C.byref(N)), "ft_room_plan")
+        return rate, items, keep, rp, N.value - 1
+
+    def room_stream(self, clip, sample_rate: Optional[int] = None, params=None) -> RoomStream:
+        """A stream of the live room stage (ft_codec_room_stream_begin): the impulse response `clip` is prepared here, as
+        room() prepares it, and stays on the device; the RoomStream's pushes concatenate to room(..., ceiling=False) of the
+        whole programme with every push's regions moved to the timeline, bit for bit, however they are cut.  The stage has no
+        ceiling: a mix stream behind it (mix_stream, with bedless=True where there is no bed) holds the piece under -1 dBFS."""
+        rate, items, keep, rp, tail = self._room_live_args("room_stream", clip, sample_rate, params)
+        h = C.c_void_p()
+        self._check(self.lib.ft_codec_room_stream_begin(self._h, rate, items, C.byref(rp), C.byref(h)), "ft_codec_room_stream_begin")
+        del keep                                           # (begin has prepared the response: its bytes are no longer read)
+        return RoomStream(self, h, tail)
+
+    def room_live(self, audio, clip, regions=(), sample_rate: Optional[int] = None, params=None):
+        """The live room stage on a whole host waveform (ft_codec_room_live): what a room stream gives for it in one final
+        push - room(..., ceiling=False), bit for bit.  `audio` may be empty: the tail alone, zeros.  Returns (y, RoomReport)."""
+        what = "room_live"
+        rate, items, keep, rp, tail = self._room_live_args(what, clip, sample_rate, params)
+        x = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(-1))
+        table = send_region_table(what, regions, len(x))
+        cap = len(x) + tail
+        y = np.empty(max(cap, 1), dtype=np.float32)
+        total = C.c_int64(0)
+        info = L.ft_room_info()
+        self._check(self.lib.ft_codec_room_live(self._h, x.ctypes.data_as(C.c_void_p), len(x), rate, *table, items, C.byref(rp),
+                                                y.ctypes.data_as(C.c_void_p), cap, C.byref(total), C.byref(info)), "ft_codec_room_live")
+        del keep
+        return y[:total.value], RoomReport.of(info)
+
     def test_room_conv(self, xs: np.ndarray, hn: np.ndarray, predelay: int, N: int) -> np.ndarray:
         """Test hook: the room stage's convolution launches alone on the taps hn (ft_test_room_conv) -> c[0 .. N)."""
         xs = np.ascontiguousarray(np.asarray(xs, dtype=np.float32).reshape(-1))
@@ -1009,15 +1096,29 @@ class CodecHipEngine:
         rep = MixLiveReport.of(info)
         return (y[:total.value], rep, D, Lk) if nodes else (y[:total.value], rep)
 
-    def mix_stream(self, bed, sample_rate: Optional[int] = None, params=None, stereo: bool = False) -> MixStream:
+    def mix_stream(self, bed, sample_rate: Optional[int] = None, params=None, stereo: bool = False,
+                   bedless: bool = False) -> MixStream:
         """A stream of the live mix stage (ft_codec_mix_stream_begin): the bed is prepared here and stays on the device; the
         MixStream's pushes concatenate to mix_live() of the whole programme, bit for bit, however they are cut.  `stereo`: a
         stream of the live stereo mix stage (ft_codec_mix_stream_begin_stereo) - a StereoMixStream, whose
         push(x, regions=(), final=False) takes the pan regions of that push, relative to it, and returns (frames, 2) arrays
-        that concatenate to mix_live_stereo(); `bed` may then be None."""
-        rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params, bedless=stereo)
+        that concatenate to mix_live_stereo(); `bed` may then be None.  `bedless` (mono, `bed` None): the limiter alone
+        (ft_codec_mix_stream_begin_bare) - the live mix stage with the bed term +0.0, for a stream with a room and no bed;
+        `params` None: mix.bare_params()."""
+        if not isinstance(bedless, bool):
+            raise ValueError(f"mix_stream: bedless must be True or False, got {bedless!r}")
+        if bedless and (stereo or bed is not None):
+            raise ValueError("mix_stream: bedless=True is the mono stream without a bed (a stereo stream takes bed=None as it is)")
+        if bedless and params is None:
+            from .mix import bare_params
+            params = bare_params()                         # no duck window to wait for: 160 ms held back
+        rate, items, keep, mp = self._mix_args("mix_stream", bed, sample_rate, params, bedless=stereo or bedless)
         fn = "ft_codec_mix_stream_begin_stereo" if stereo else "ft_codec_mix_stream_begin"
         h = C.c_void_p()
+        if bedless:
+            fn = "ft_codec_mix_stream_begin_bare"
+            self._check(self.lib.ft_codec_mix_stream_begin_bare(self._h, rate, C.byref(mp), C.byref(h)), fn)
+            return MixStream(self, h, mp, rate)
         self._check(getattr(self.lib, fn)(self._h, rate, items, C.byref(mp), C.byref(h)), fn)
         del keep                                           # (begin has prepared the bed: its bytes are no longer read)
         return (StereoMixStream if stereo else MixStream)(self, h, mp, rate)

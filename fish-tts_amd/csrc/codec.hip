@@ -47,6 +47,7 @@ struct DecBlock { float* a0; ConvW ct; ResUnitW u[3]; int s, cin, cout; };
 
 struct ft_codec_stream;
 struct ft_mix_stream;
+struct ft_room_stream;
 struct CodecState {
     hipStream_t stream = nullptr;
     std::mutex mu;
@@ -135,6 +136,7 @@ struct CodecState {
     // live mix stage (ft_codec_mix_stream_*): the open streams (their device state is freed with the context), and what a
     // push stages - its samples, the m of the hops it completes, the samples it emits; the buffers grow on need
     std::vector<ft_mix_stream*> mix_streams;
+    std::vector<ft_room_stream*> room_streams;   // live room stage (ft_codec_room_stream_*): the open streams, as mix_streams
     float *ml_x = nullptr, *ml_m = nullptr, *ml_y = nullptr;
     size_t ml_xcap = 0, ml_mcap = 0, ml_ycap = 0;
     unsigned char* ml_q = nullptr;    // live stereo mix stage: the pan bytes of a push
@@ -345,6 +347,7 @@ ft_status codec_create(ft_ctx* ctx) {
 
 static void stream_orphan(ft_codec_stream* sc);
 static void mix_stream_orphan(ft_mix_stream* ms);
+static void room_stream_orphan(ft_room_stream* rs);
 void codec_destroy(ft_ctx* ctx) {
     CodecState* s = ctx->codec;
     if (!s) return;
@@ -355,6 +358,8 @@ void codec_destroy(ft_ctx* ctx) {
     s->streams.clear();
     for (ft_mix_stream* ms : s->mix_streams) mix_stream_orphan(ms);
     s->mix_streams.clear();
+    for (ft_room_stream* rs : s->room_streams) room_stream_orphan(rs);
+    s->room_streams.clear();
     for (void* p : s->owned) hipFree(p);
     delete s;
     ctx->codec = nullptr;
@@ -3454,6 +3459,16 @@ extern "C" ft_status ft_codec_mix_stream_begin(ft_ctx* ctx, int32_t sample_rate,
     return ml_begin(ctx, fn, sample_rate, bed, mp, false, out);
 }
 
+extern "C" ft_status ft_codec_mix_stream_begin_bare(ft_ctx* ctx, int32_t sample_rate, const ft_mix_params* mp, ft_mix_stream** out) {
+    const std::string fn = "ft_codec_mix_stream_begin_bare";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!mp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    FT_TRY(mix_refuse(ctx, fn, sample_rate, 0, mp, 0, nullptr));
+    std::lock_guard<std::mutex> lock(ctx->codec->mu);
+    return ml_begin(ctx, fn, sample_rate, nullptr, mp, false, out);
+}
+
 extern "C" ft_status ft_codec_mix_stream_begin_stereo(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed,
                                                       const ft_mix_params* mp, ft_mix_stream** out) {
     const std::string fn = "ft_codec_mix_stream_begin_stereo";
@@ -3519,6 +3534,264 @@ extern "C" ft_status ft_codec_mix_live_stereo(ft_ctx* ctx, const float* x, int64
     if ((!x && n != 0) || !mp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_mix_live_stereo: a null pointer");
     const chain::MsTable pans = {(const chain::MsRegion*)regions, R};
     return ml_live(ctx, "ft_codec_mix_live_stereo", x, n, sample_rate, &pans, bed, mp, y, capacity, total, duck, limit, info);
+}
+
+// ---- live room stage (fishtts_hip.h: "Live room"; rooml_*_kernel in room_kernels.h; the counters, the carry's bounds, the
+// per-push checks and the sizes in fx_chain.h, the rl_* block).  A stream owns hn, its RoomOut and two copies of its carry, all
+// allocated at `begin` and bounded by predelay + L - 1; a push stages its samples, their sent form and its outputs in the
+// context's buffers (the live mix stage's ml_x and ml_y, the room stage's rm_xs) and ends with one wait, so nothing of a push
+// outlives it, and the counters move only when the launches went through.
+struct ft_room_stream {
+    ft_ctx* owner = nullptr;          // null once its context is gone (the device state went with it)
+    chain::RlStage st;
+    ft_room_params rp;
+    int rate = RS_FI;
+    long long nh = 0, L = 0;
+    float* hn = nullptr;              // [L], for the life of the stream
+    float* carry[2] = {nullptr, nullptr};
+    RoomOut* out = nullptr;           // E and gn from `begin`, the peak over the pushes so far
+    ft_intake_info irinfo;
+    std::vector<void*> owned;
+};
+
+static void room_stream_orphan(ft_room_stream* rs) {
+    for (void* v : rs->owned) hipFree(v);
+    rs->owned.clear();
+    rs->owner = nullptr;
+}
+
+template <typename T>
+static ft_status rl_malloc(ft_ctx* ctx, ft_room_stream* rs, T** p, size_t n) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, (n + 8) * sizeof(T));
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_NOMEM, std::string("room stream hipMalloc: ") + hipGetErrorString(e));
+    rs->owned.push_back(q);
+    *p = (T*)q;
+    return FT_OK;
+}
+
+static void rl_end(ft_ctx* ctx, ft_room_stream* rs) {   // (s->mu held)
+    CodecState* s = ctx->codec;
+    hipStreamSynchronize(s->stream);
+    for (void* v : rs->owned) hipFree(v);
+    rs->owned.clear();
+    for (size_t i = 0; i < s->room_streams.size(); ++i)
+        if (s->room_streams[i] == rs) { s->room_streams.erase(s->room_streams.begin() + (long)i); break; }
+    delete rs;
+}
+
+// The stream of a call whose values rm_check has passed (s->mu held): the response prepared as ft_codec_room prepares it, t
+// and the block energies in the context's buffers, hn in the stream's own.  A begin that fails once the stream exists frees it.
+static ft_status rl_begin(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* ir, const ft_room_params* rp,
+                          const chain::RmArgs& a, const chain::RmPlan& pl, ft_room_stream** out) {
+    CodecState* s = ctx->codec;
+    FxDesc d;
+    FT_TRY(fx_refuse(ctx, fn, rate, 100, 0, &d));
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = s->stream;
+    ft_mix_params mp;
+    memset(&mp, 0, sizeof mp);
+    mp.channel = rp->channel;
+    MixBed b;                                         // (alive until the wait below)
+    FT_TRY(mix_bed(ctx, fn, rate, ir, &mp, false, nullptr, &b));
+    if (b.nb != pl.nh) return ft_fail(ctx, FT_ERR_STATE, fn + ": the impulse response's length is not the planned one");
+    FT_TRY(mix_table(ctx));
+    const chain::RmSizes z = chain::rm_sizes(a, pl);
+    FT_TRY(cgrow(ctx, &s->rm_t, &s->rm_tcap, z.taps));
+    FT_TRY(cgrow(ctx, &s->rm_e, &s->rm_ecap, z.blocks));
+    ft_room_stream* rs = new ft_room_stream();
+    rs->owner = ctx;
+    rs->rp = *rp;
+    rs->rate = rate;
+    rs->nh = pl.nh;
+    rs->L = pl.L;
+    rs->st = chain::RlStage::fresh(chain::rl_shape(a, pl));
+    rs->irinfo = b.info;
+    s->room_streams.push_back(rs);
+    const size_t cz = chain::rl_sizes(rs->st, rs->st.plan(0, false)).carry;
+    ft_status r = rl_malloc(ctx, rs, &rs->hn, z.taps);
+    if (r == FT_OK) r = rl_malloc(ctx, rs, &rs->out, (size_t)1);
+    for (int c = 0; c < 2 && r == FT_OK; ++c) r = rl_malloc(ctx, rs, &rs->carry[c], cz);
+    RoomOut got;
+    memset(&got, 0, sizeof got);
+    if (r == FT_OK) {
+        hipError_t e = hipMemsetAsync(rs->out, 0, sizeof(RoomOut), st);
+        if (e == hipSuccess) {
+            RoomIrP ip = {b.side[0], s->rm_t, rs->hn, s->rm_e, rs->out, (int)pl.L, (int)pl.f, rp->normalize, rp->offset};
+            room_ir_kernel<<<(unsigned)((z.blocks + 63) / 64), 64, 0, st>>>(ip);
+            room_gain_kernel<<<1, 1024, 0, st>>>(ip);
+            e = hipMemcpyAsync(&got, rs->out, sizeof got, hipMemcpyDeviceToHost, st);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) r = ft_fail(ctx, FT_ERR_HIP, fn + ": " + hipGetErrorString(e));
+    }
+    if (r == FT_OK && rp->normalize && (!(got.E > 0.0) || !std::isfinite(got.E)))
+        r = ft_fail(ctx, FT_ERR_ARG, fn + ": the impulse response's energy is zero or not finite");
+    if (r != FT_OK) {
+        rl_end(ctx, rs);
+        return r;
+    }
+    *out = rs;
+    return FT_OK;
+}
+
+// begin's values judged: the pointers, then rm_check's order without n and the regions, a ceiling other than 0 refused where
+// rm_check judges the ceiling.
+static ft_status rl_judge(ft_ctx* ctx, const std::string& fn, int rate, const ft_intake_item* ir, const ft_room_params* rp,
+                          chain::RmArgs* a, chain::RmPlan* pl) {
+    *a = chain::rl_begin_args(room_args(rate, 1, ir, rp));
+    bool too_long = false;
+    if (const char* why = chain::rm_check(*a, chain::MsTable(), &too_long, pl))
+        return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    return FT_OK;
+}
+
+// One push (s->mu held).  Everything is judged first; the stream's counters move only when the launches went through.
+static ft_status rl_push(ft_ctx* ctx, const std::string& fn, ft_room_stream* rs, const float* x, int64_t n, const chain::MsTable& regs,
+                         bool final, float* y, int64_t capacity, int64_t* n_out) {
+    CodecState* s = ctx->codec;
+    chain::RlStage& stg = rs->st;
+    bool state = false, too_long = false;
+    if (!stg.ended && ((!x && n > 0) || !n_out)) return ft_fail(ctx, FT_ERR_ARG, fn + ": bad argument");
+    if (const char* why = chain::rl_check(stg, n, regs, final, capacity, &state, &too_long))
+        return ft_fail(ctx, state ? FT_ERR_STATE : too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    const chain::RlPlan pl = stg.plan(n, final);
+    if (!y && pl.out > 0) return ft_fail(ctx, FT_ERR_ARG, fn + ": capacity below what the push emits");
+    const chain::RlSizes z = chain::rl_sizes(stg, pl);
+    const int R = (int)regs.R, w = stg.par ^ 1;
+    const bool send = R > 0 || rs->rp.send != 0;
+    hipStream_t st = s->stream;
+    FT_TRY(cgrow(ctx, &s->ml_x, &s->ml_xcap, z.x));
+    FT_TRY(cgrow(ctx, &s->ml_y, &s->ml_ycap, z.y));
+    if (send) {
+        FT_TRY(cgrow(ctx, &s->rm_xs, &s->rm_xscap, z.xs));
+        FT_TRY(cgrow(ctx, &s->mx_reg, &s->mx_regcap, (size_t)std::max(R, 1)));
+    }
+    std::vector<float> T(chain::MX_MAX_DEPTH + 1);
+    chain::mx_gains(T.data());
+    if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->ml_x, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (send && n > 0) {
+        if (R > 0) FT_HIP(ctx, hipMemcpyAsync(s->mx_reg, regs.reg, (size_t)R * sizeof(MixPan), hipMemcpyHostToDevice, st));
+        RoomSendP sp = {s->ml_x, s->rm_xs, s->mx_T, s->mx_reg, (int)n, R, rs->rp.send};
+        rooml_send_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256)), 256, 0, st>>>(sp);
+    }
+    RoomLive src = {rs->carry[stg.par], send ? s->rm_xs : s->ml_x, (int)pl.cb0, (int)pl.F0, (int)pl.F1};
+    if (pl.out > 0) {
+        RoomConvP cp;
+        memset(&cp, 0, sizeof cp);
+        cp.x = s->ml_x; cp.hn = rs->hn; cp.y = s->ml_y; cp.out = rs->out;
+        cp.n = (int)pl.F1; cp.L = (int)rs->L; cp.predelay = (int)rs->rp.predelay; cp.N = (int)pl.end;
+        cp.dry = rs->rp.dry >= 0; cp.gd = cp.dry ? T[rs->rp.dry] : 0.f; cp.gw = T[rs->rp.wet];
+        for (long long i0 = pl.F0; i0 < pl.end; i0 += RM_LAUNCH) {
+            cp.i0 = (int)i0;
+            const long long span = std::min<long long>(RM_LAUNCH, pl.end - i0);
+            rooml_conv_kernel<<<(unsigned)((span + RM_SPAN - 1) / RM_SPAN), RM_THREADS, 0, st>>>(cp, src);
+        }
+    }
+    if (pl.F1 > pl.cb1) {
+        RoomRollP rp = {src, rs->carry[w], (int)pl.cb1};
+        rooml_roll_kernel<<<(unsigned)std::min<long long>(4096, (pl.F1 - pl.cb1 + 255) / 256), 256, 0, st>>>(rp);
+    }
+    if (pl.out > 0) FT_HIP(ctx, hipMemcpyAsync(y, s->ml_y, (size_t)pl.out * sizeof(float), hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
+    stg.commit(pl);
+    *n_out = pl.out;
+    return FT_OK;
+}
+
+static ft_status rl_info(ft_ctx* ctx, const std::string& fn, ft_room_stream* rs, ft_room_info* info) {   // (s->mu held)
+    hipStream_t st = ctx->codec->stream;
+    RoomOut out;
+    FT_HIP(ctx, hipMemcpyAsync(&out, rs->out, sizeof out, hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    (void)fn;
+    memset(info, 0, sizeof *info);
+    info->N = rs->st.nout; info->nh = rs->nh; info->L = rs->L; info->E = out.E; info->gn = out.gn;
+    memcpy(&info->pk, &out.pk, sizeof(float));
+    info->sg = 1.f;
+    info->capped = 0;
+    info->ir = rs->irinfo;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_room_stream_begin(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* ir, const ft_room_params* rp,
+                                                ft_room_stream** out) {
+    const std::string fn = "ft_codec_room_stream_begin";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!ir || !rp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    chain::RmArgs a;
+    chain::RmPlan pl;
+    FT_TRY(rl_judge(ctx, fn, sample_rate, ir, rp, &a, &pl));
+    std::lock_guard<std::mutex> lock(ctx->codec->mu);
+    return rl_begin(ctx, fn, sample_rate, ir, rp, a, pl, out);
+}
+
+extern "C" ft_status ft_codec_room_stream_push(ft_room_stream* rs, const float* x, int64_t n, const ft_send_region* regions, int32_t R,
+                                               int32_t final, float* y, int64_t capacity, int64_t* n_out) {
+    if (!rs) return FT_ERR_ARG;
+    ft_ctx* ctx = rs->owner;
+    if (!ctx || !ctx->codec) return FT_ERR_STATE;      // its context was destroyed
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    const chain::MsTable regs = {(const chain::MsRegion*)regions, R};
+    return rl_push(ctx, "ft_codec_room_stream_push", rs, x, n, regs, final != 0, y, capacity, n_out);
+}
+
+extern "C" ft_status ft_codec_room_stream_info(ft_room_stream* rs, ft_room_info* info) {
+    if (!rs) return FT_ERR_ARG;
+    ft_ctx* ctx = rs->owner;
+    if (!ctx || !ctx->codec) return FT_ERR_STATE;      // its context was destroyed
+    if (!info) return ft_fail(ctx, FT_ERR_ARG, "ft_codec_room_stream_info: a null pointer");
+    std::lock_guard<std::mutex> lock(ctx->codec->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    return rl_info(ctx, "ft_codec_room_stream_info", rs, info);
+}
+
+extern "C" void ft_codec_room_stream_end(ft_room_stream* rs) {
+    if (!rs) return;
+    ft_ctx* own = rs->owner;
+    if (own && own->codec) {
+        std::lock_guard<std::mutex> lock(own->codec->mu);
+        hipSetDevice(own->device);
+        rl_end(own, rs);
+        return;
+    }
+    delete rs;
+}
+
+// The stage on a whole programme: a stream begun, one final push, its report, the stream ended.
+extern "C" ft_status ft_codec_room_live(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_send_region* regions,
+                                        int32_t R, const ft_intake_item* ir, const ft_room_params* rp, float* y, int64_t capacity,
+                                        int64_t* total, ft_room_info* info) {
+    const std::string fn = "ft_codec_room_live";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if ((!x && n != 0) || !ir || !rp || !y || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    chain::RmArgs a;
+    chain::RmPlan pl;
+    FT_TRY(rl_judge(ctx, fn, sample_rate, ir, rp, &a, &pl));
+    const chain::MsTable regs = {(const chain::MsRegion*)regions, R};
+    if (pl.nh >= 0) {                                   // (an item the intake refuses has no nh: its refusal stands, in rl_begin)
+        bool state = false, too_long = false;
+        if (const char* why = chain::rl_check(chain::RlStage::fresh(chain::rl_shape(a, pl)), n, regs, true, capacity, &state, &too_long))
+            return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    }
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    ft_room_stream* rs = nullptr;
+    FT_TRY(rl_begin(ctx, fn, sample_rate, ir, rp, a, pl, &rs));
+    int64_t got = 0;
+    ft_status r = rl_push(ctx, fn, rs, x, n, regs, true, y, capacity, &got);
+    if (r == FT_OK) r = rl_info(ctx, fn, rs, info);
+    rl_end(ctx, rs);
+    FT_TRY(r);
+    *total = got;
+    return FT_OK;
 }
 
 // ---- launch trace hooks (fishtts_hip_test.h)

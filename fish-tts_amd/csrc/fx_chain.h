@@ -5,7 +5,8 @@
 // duck and gain table (mx_*; tools/mix_check.cpp drives that block), the stereo mix stage's pan regions, pan table and bed
 // sides (ms_*; tools/stereo_check.cpp), the live mix stage's emission (ml_*, MlStage; tools/mix_live_check.cpp), the live
 // stereo mix stage's per-push regions, pan words and buffer sizes (mls_*; tools/stereo_live_check.cpp) and, between the join
-// and the mix stages, the room stage's send regions, checks, lengths and buffer sizes (rm_*; tools/room_check.cpp).
+// and the mix stages, the room stage's send regions, checks, lengths and buffer sizes (rm_*; tools/room_check.cpp), the live
+// room stage's counters, carry bounds and per-push checks (rl_*; tools/room_live_check.cpp).
 // Plain C++ without HIP, so that a host program can drive it under a sanitizer (tools/fx_chain_check.cpp).  The constants
 // are those of the kernels (stage_kernels.h); codec.hip asserts that the two sets agree.
 #pragma once
@@ -517,6 +518,7 @@ struct RmArgs {
     int ir_rate = RS_FI, ir_channels = 1;     // the impulse response's item
     long long ir_frames = 1;
     long long nh = -1;                         // >= 0: the response's length at the output rate, given (ft_room_plan)
+    int live = 0;                              // a stream's begin (rl_begin_args): the ceiling must be 0
 };
 // The impulse response's samples at the output rate, as the intake and the resampler count them; -1 where the item's own
 // checks (the intake's, which come last) will refuse it.
@@ -541,6 +543,7 @@ inline const char* rm_check(const RmArgs& a, const MsTable& regs, bool* too_long
     if (a.dry < -1 || a.dry > RM_MAX_SEND) return "dry neither -1 nor in [0, 6000] hundredths of a dB";
     if (a.send < -1 || a.send > RM_MAX_SEND) return "send neither -1 nor in [0, 6000] hundredths of a dB";
     if (a.ceiling != 0 && a.ceiling != 1) return "ceiling must be 0 or 1";
+    if (a.live && a.ceiling != 0) return "ceiling must be 0 on a stream: it has no whole-piece peak";
     if (a.offset < 0) return "offset must be >= 0";
     if (a.length < 0) return "length must be >= 0";
     if (a.fade < 0) return "fade must be >= 0";
@@ -585,6 +588,94 @@ inline RmSizes rm_sizes(const RmArgs& a, const RmPlan& p) {
     z.blocks = (size_t)((p.L + 255) / 256);
     z.y = (size_t)p.N;
     return z;
+}
+
+// ---- live room stage (rooml_*_kernel in room_kernels.h; fishtts_hip.h states it under "Live room"): the room stage on a
+// stream.  The chain is causal - output i reads xs[i - predelay - k], k in [0, L) - so a push of n samples behind n_in
+// earlier ones emits exactly the outputs [n_in, n_in + n), the final one the tail behind them, and the stream carries the
+// last min(n_in, predelay + L - 1) sent samples.  The values of `begin` as rm_check judges them (no programme yet: n = 1
+// stands in, and no n of a stream can then fail where rm_check looks at it), the counters of a stream, the bounds of its
+// carry, the per-push checks in their order and the sizes of the buffers a push touches (tools/room_live_check.cpp drives
+// this block over random cuttings).
+inline RmArgs rl_begin_args(RmArgs a) {
+    a.n = 1;
+    a.live = 1;
+    return a;
+}
+struct RlShape { long long hist = 0, tl = 0; };       // predelay + L - 1; the tail by Room's rule
+inline RlShape rl_shape(const RmArgs& a, const RmPlan& p) { return RlShape{a.predelay + p.L - 1, p.tl}; }
+// A push on the timeline: it brings the samples [F0, F1) and emits the outputs [F0, end); the carry read holds the sent
+// samples [cb0, F0), the one written [cb1, F1) (nothing at the end of the stream).
+struct RlPlan { long long in = 0, out = 0, F0 = 0, F1 = 0, end = 0, cb0 = 0, cb1 = 0; bool final = false; };
+struct RlStage {
+    RlShape s;
+    int par = 0;                               // which copy of the carry is current
+    bool ended = false;                        // the final push went through
+    long long nin = 0, nout = 0, base = 0;     // samples taken, outputs emitted, the first sent sample carried
+    static RlStage fresh(const RlShape& shape) {
+        RlStage r;
+        r.s = shape;
+        return r;
+    }
+    RlPlan plan(long long n, bool final) const {
+        RlPlan p;
+        p.in = n;
+        p.final = final;
+        p.F0 = nin;
+        p.F1 = nin + n;
+        p.end = final ? p.F1 + s.tl : p.F1;
+        p.out = p.end - nout;
+        p.cb0 = base;
+        p.cb1 = final ? p.F1 : std::max(0LL, p.F1 - s.hist);
+        return p;
+    }
+    long long held(const RlPlan& p) const { return p.F1 - p.cb1; }   // carried after the call: at most hist
+    void commit(const RlPlan& p) {
+        nin = p.F1; nout = p.end; base = p.cb1;
+        ended = p.final;
+        par ^= 1;
+    }
+};
+// A push judged, in the stated order: a push after the final one (*state), n, the regions - relative to the push, by
+// rm_regions over its n - the timeline (*too_long), the capacity.  Null, or why not; nothing of the stage changes.
+inline const char* rl_check(const RlStage& st, long long n, const MsTable& regs, bool final, long long capacity, bool* state,
+                            bool* too_long) {
+    *state = *too_long = false;
+    if (st.ended) {
+        *state = true;
+        return "the stream has had its final push";
+    }
+    if (n < 0) return "n must be >= 0";
+    if (const char* e = rm_regions(regs, n)) return e;
+    if (n > MX_MAX_N || st.nin + n + st.s.tl > MX_MAX_N) {
+        *too_long = true;
+        return "n + tail exceeds 2^28 samples";
+    }
+    if (capacity < st.plan(n, final).out) return "capacity below what the push emits";
+    return nullptr;
+}
+inline MsRegion rl_shift(const MsRegion& g, long long F0) { return MsRegion{g.a + F0, g.e + F0, g.pan, 0}; }
+// Elements a push touches: the staged push and its sent form (one spare where the push is empty: the staging loads once and
+// then selects), the output, and each copy of the carry, which a stream allocates once.
+struct RlSizes { size_t x = 0, xs = 0, y = 0, carry = 0; };
+inline RlSizes rl_sizes(const RlStage& st, const RlPlan& p) {
+    RlSizes z;
+    z.x = z.xs = (size_t)std::max(p.in, 1LL);
+    z.y = (size_t)std::max(p.out, 1LL);
+    z.carry = (size_t)std::max(st.s.hist, 1LL);
+    return z;
+}
+// The sent sample at timeline index g as the chain's staging picks it: which buffer (0: the carry, 1: the push, -1: +0.0)
+// and the element in it - clamped into the buffer even where the value is then not taken.
+struct RlPick { int buf = -1; long long at = 0; bool taken = false; };
+inline RlPick rl_pick(const RlPlan& p, long long g) {
+    const bool old = g < p.F0;
+    const long long lo = old ? p.cb0 : p.F0, hi = old ? p.F0 : p.F1;
+    RlPick k;
+    k.buf = old ? 0 : 1;
+    k.at = std::min(std::max(g, lo), std::max(hi - 1, lo)) - lo;
+    k.taken = g >= lo && g < hi;
+    return k;
 }
 
 // ---- the stages of one waveform, in chain order.  A stage takes `in` more input samples in a call and emits `out`;

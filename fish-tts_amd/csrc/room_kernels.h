@@ -8,6 +8,8 @@
 //   room_send_kernel  xs[i] = x[i] T[send of i]: the region of a sample by binary search (left out when no send is set)
 //   room_conv_kernel  the chain, and behind it the sum with the dry signal and the workgroup's peak (below)
 //   mix_scale_kernel  as it is, when the ceiling binds
+// and the live room stage's (ft_codec_room_stream_*; "Live room"), behind them: rooml_send_kernel, rooml_conv_kernel - the same
+// text as room_conv_kernel over another source of the sent programme - and rooml_roll_kernel.
 #pragma once
 #include "stage_kernels.h"
 
@@ -85,7 +87,8 @@ static __global__ __launch_bounds__(1024) void room_gain_kernel(RoomIrP p) {
     for (int k = threadIdx.x; k < p.L; k += 1024) p.hn[k] = __fmul_rn(p.t[k], gn);
 }
 
-static __global__ __launch_bounds__(256) void room_send_kernel(RoomSendP p) {
+// (one text for the whole call and for a stream's push, whose x, n and regions are the push's own: rooml_send_kernel)
+__device__ __forceinline__ void room_send_body(RoomSendP p) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < p.n; i += gridDim.x * 256) {
         int lo = 0, hi = p.R;                              // the first region that ends behind i
         while (lo < hi) {
@@ -96,6 +99,7 @@ static __global__ __launch_bounds__(256) void room_send_kernel(RoomSendP p) {
         p.xs[i] = s < 0 ? 0.f : __fmul_rn(p.x[i], p.T[s]);
     }
 }
+static __global__ __launch_bounds__(256) void room_send_kernel(RoomSendP p) { room_send_body(p); }
 
 // The chain as a Toeplitz product on v_mfma_f32_32x32x2_f32.  A wave owns 1024 consecutive outputs as a 32 x 32 tile,
 // Y[r][c] = c[i0 + 32 r + c] = sum over d of xs[i0 + 32 r - d - predelay] hn[d + c], d = -31 .. L - 1 ascending, hn zero
@@ -108,7 +112,18 @@ static __global__ __launch_bounds__(256) void room_send_kernel(RoomSendP p) {
 // q = 1024 w + 32 r + RM_DC - 1 - h - e: a lane stride of 32 words, so word q lies at q + (q >> 5) and the 32 lanes of a half
 // fall on 32 banks; B is read at e + h + c, consecutive.  Both reads are 4 bytes per lane and MFMA, far below what LDS gives.
 // Every index is bounded by N + L + predelay + RM_SPAN < 2^29.
-static __global__ __launch_bounds__(RM_THREADS) void room_conv_kernel(RoomConvP p) {
+// The kernel's text is room_conv_body, over the source of the sent programme: RoomWhole for ft_codec_room - xs itself, n
+// samples, output i at y[i] - and RoomLive for a stream's push (below).  Both kernels are this one text, so a stream gives
+// the whole call's bits by construction; the source decides only where a word of the staging comes from, where an output
+// lands and up to where the dry signal exists.
+struct RoomWhole {
+    const RoomConvP& p;
+    __device__ __forceinline__ float at(int g) const { return g >= 0 && g < p.n ? p.xs[g] : 0.f; }
+    __device__ __forceinline__ int rel(int i) const { return i; }
+};
+
+template <class Src>
+__device__ __forceinline__ void room_conv_body(const RoomConvP& p, const Src& src) {
     using f32x16 = __attribute__((ext_vector_type(16))) float;
     __shared__ float lds[RM_XLDS + RM_HLDS + RM_WAVES];
     float* XL = lds;
@@ -124,7 +139,7 @@ static __global__ __launch_bounds__(RM_THREADS) void room_conv_kernel(RoomConvP 
         __syncthreads();
         for (int q = threadIdx.x; q < RM_XWIN; q += RM_THREADS) {
             const int g = w0 + q;
-            XL[q + (q >> 5)] = g >= 0 && g < p.n ? p.xs[g] : 0.f;
+            XL[q + (q >> 5)] = src.at(g);
         }
         for (int u = threadIdx.x; u < RM_HLDS; u += RM_THREADS) {
             const int k = s0 + u - 31;
@@ -170,10 +185,10 @@ static __global__ __launch_bounds__(RM_THREADS) void room_conv_kernel(RoomConvP 
             float v = c;
             if (!p.raw) {
                 const float wet = __fmul_rn(p.gw, c);
-                const float dry = p.dry && i < p.n ? __fmul_rn(p.gd, p.x[i]) : 0.f;
+                const float dry = p.dry && i < p.n ? __fmul_rn(p.gd, p.x[src.rel(i)]) : 0.f;
                 v = __fadd_rn(dry, wet);
             }
-            p.y[i] = v;
+            p.y[src.rel(i)] = v;
             pk = fmaxf(pk, fabsf(v));
         }
     }
@@ -184,6 +199,50 @@ static __global__ __launch_bounds__(RM_THREADS) void room_conv_kernel(RoomConvP 
         for (int v = 1; v < RM_WAVES; ++v) pk = fmaxf(pk, wpk[v]);
         if (pk > 0.f) atomicMax(&p.out->pk, __float_as_uint(pk));
     }
+}
+
+static __global__ __launch_bounds__(RM_THREADS) void room_conv_kernel(RoomConvP p) { room_conv_body(p, RoomWhole{p}); }
+
+// ---- live room stage (ft_codec_room_stream_*, ft_codec_room_live; stated in fishtts_hip.h under "Live room"): the room stage
+// on a stream.  A push brings the samples of timeline [F0, F1) and emits the outputs [F0, F1), the final one up to N; the
+// stream carries the sent samples [cb0, F0), cb0 = max(0, F0 - (predelay + L - 1)) - all that an output from F0 on reads
+// below F0 - in two copies, one read and one written by a push.  Three launches per push, one with nothing to do left out:
+//   rooml_send_kernel  xs of the push from its own regions: room_send_kernel's rule with push-relative indices (left out
+//                      where the push has no region and rp->send = 0: its xs is x)
+//   rooml_conv_kernel  room_conv_body over RoomLive: a word of the staging comes from the carry (timeline [cb0, F0)) or from
+//                      the push ([F0, F1)) - the lane picks the buffer and clamps the index, loads once and selects between
+//                      the value and +0.0, no branch per sample (mixl_prog's pattern); the dry signal is the push's x, and an
+//                      output lands at its index in the push.  RoomConvP then holds n = F1, N = the end of the outputs, x
+//                      and y the push's buffers, xs unused
+//   rooml_roll_kernel  the carry [cb1, F1) for the next push, from the old one and the push's xs (nothing after the final
+//                      push)
+// The peak goes into the stream's own RoomOut by the same integer atomicMax.
+struct RoomLive {
+    const float* carry;        // sent samples [cb0, F0) (at least one element, read and not taken where the range is empty)
+    const float* xs;           // sent samples [F0, F1) (the same)
+    int cb0, F0, F1;
+    __device__ __forceinline__ float at(int g) const {
+        const bool old = g < F0;
+        const float* s = old ? carry : xs;
+        const int lo = old ? cb0 : F0, hi = old ? F0 : F1;
+        const int ic = min(max(g, lo), max(hi - 1, lo));
+        const float v = s[ic - lo];
+        return g >= lo && g < hi ? v : 0.f;
+    }
+    __device__ __forceinline__ int rel(int i) const { return i - F0; }
+};
+struct RoomRollP {
+    RoomLive src;
+    float* out;                // the carry written: [cb1, F1)
+    int cb1;
+};
+
+static __global__ __launch_bounds__(256) void rooml_send_kernel(RoomSendP p) { room_send_body(p); }
+
+static __global__ __launch_bounds__(RM_THREADS) void rooml_conv_kernel(RoomConvP p, RoomLive src) { room_conv_body(p, src); }
+
+static __global__ __launch_bounds__(256) void rooml_roll_kernel(RoomRollP p) {
+    for (int i = p.cb1 + blockIdx.x * 256 + threadIdx.x; i < p.src.F1; i += gridDim.x * 256) p.out[i - p.cb1] = p.src.at(i);
 }
 
 }  // namespace ft

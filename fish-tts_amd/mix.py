@@ -93,6 +93,13 @@ def bed_params(bed: Bed, rate: int, silence_db: Optional[float] = None) -> MixPa
                      fade_in, fade_out, offset, 1 if bed.loop else 0)
 
 
+def bare_params() -> MixParams:
+    """The values of a live mix stream without a bed (CodecHipEngine.mix_stream(None, bedless=True)): the limiter alone.  No
+    duck, no lead, no tail, no fades, nothing loops, and the shortest attack - with no bed to lower, the duck's window would
+    only be held back: the stream then holds back (1 + 5 + 2) hops, 160 ms, the limiter's own look-ahead."""
+    return MixParams(0, -1, 0, math.pow(10.0, DEFAULT_THRESHOLD_DB / 20.0), 1, 1, 0, 0, 0, 0, 0, 0)
+
+
 def bed_bytes(bed: Bed) -> bytes:
     """The WAV bytes of a Bed: its `wav` itself, or the file it names."""
     if isinstance(bed.wav, (bytes, bytearray, memoryview)):

@@ -116,3 +116,24 @@ def send_regions(sends: Sequence[int], marks: Sequence) -> List[Tuple[int, int, 
                 out.append((int(m[0]), int(m[1]), send))
         before = send
     return out
+
+
+def push_send_regions(sends: Sequence[int], line_of: Sequence[int], gaps: Sequence[int], cuts, at: int = 0, started: bool = False,
+                      before: int = 0):
+    """The live room stage's regions for ONE joined group of a stream (script.push_regions' counterpart) - segments of lines
+    `line_of` behind `gaps`, kept as `cuts` says, beginning at sample `at` of the programme with `started` saying whether audio
+    went out before it and `before` the send of the last line that had audio by then.  The group's marks (script.line_marks)
+    go through send_regions; they are then relative to the push: shifted by `at` and clipped to the group.  Where the group's
+    first line with audio has the send `before` had - the line continues from the group before, or follows a line of equal
+    send - its region begins with the group, so the silence in front of it goes along as send_regions has it for the whole
+    piece.  The regions of all groups, moved back to the timeline and touching ones of equal send joined, are send_regions of
+    the final marks.  Returns (regions, at, started, before) after the group."""
+    from .script import line_marks
+    found: list = [None] * len(sends)
+    end, started_after = line_marks(line_of, gaps, cuts, found, at, started)
+    spoken = [j for j in sorted(set(line_of)) if found[j] is not None and found[j][1] > found[j][0]]
+    regions = send_regions(sends, found)
+    if spoken and regions and sends[spoken[0]] == before != 0:
+        regions[0] = (at, regions[0][1], before)
+    out = [(max(a, at) - at, min(e, end) - at, s) for a, e, s in regions if max(a, at) < min(e, end)]
+    return out, end, started_after, (sends[spoken[-1]] if spoken else before)

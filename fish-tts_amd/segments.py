@@ -198,7 +198,7 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None,
 
 
 def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cuts=None, live_bed=None,
-                live_stereo: bool = False) -> Iterator[bytes]:
+                live_stereo: bool = False, live_room=None) -> Iterator[bytes]:
     """The int16 PCM chunks of the segments as they become ready in order: serve_(srv) -> (takes, release) through an open
     BatchServer srv = server() - asked at the first next(), so a stream made before a server opens and read while it is
     open joins its batch - else generate_(emit, stopped) on a thread of its own; every ready run decoded and joined as one
@@ -211,7 +211,15 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
     (the plan then has `pans`): the mixer is a stream of the live stereo mix stage (vocoder.mix_stream(stereo=True)), opened
     with or without a `live_bed`; every group is pushed with the regions of that group (script.push_regions: the lines'
     marks from the group's cuts through pan_regions, clipped to the push and in its coordinates), and the chunks are
-    interleaved int16, left then right."""
+    interleaved int16, left then right.
+    `live_room`: (clip, room.RoomParams) - every joined group first goes through a stream of the live room stage
+    (vocoder.room_stream, opened with the mixer) under the same lock as its decode_join, with the send regions of that group
+    (room.push_send_regions over plan.sends; none for a long text), and then into the mixer: the live stereo stream, the live
+    bed stream or, where neither was asked for, the bare limiter (vocoder.mix_stream(None, bedless=True)) - the room stage
+    has no ceiling on a stream.  A group comes out of the room as long as it went in, so the cuts and the lines' marks do not
+    move; at the end the room's final push gives its tail, which goes into the mixer's final push - on a stereo stream under
+    one pan region at the pan of the last line heard, Room's "extended over the tail" rule.  The room stream is closed with
+    the mixer."""
     import numpy as np
 
     from .longform import ready_prefixes
@@ -247,21 +255,28 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
     feeder = threading.Thread(target=feed_own if srv is None else feed_served, daemon=True)
     feeder.start()
     started = False
-    mixer = None
+    mixer = roomer = None
+    line_of = plan.line_of if plan.line_of is not None else [0] * len(plan.texts)
+    place = (0, False, 0)                    # where the next group begins, whether audio went out, the pan of the last line heard
+    if live_room is not None:
+        from .room import push_send_regions
+        sent = (0, False, 0)                 # the same for the sends: ..., the send of the last line heard
     if live_stereo:
         from .script import push_regions
         if plan.pans is None:
             raise ValueError("live_stereo needs a plan with pans")
-        line_of = plan.line_of if plan.line_of is not None else [0] * len(plan.texts)
-        place = (0, False, 0)                # where the next group begins, whether audio went out, the pan of the last line heard
     try:
-        if live_bed is not None or live_stereo:
+        if live_bed is not None or live_stereo or live_room is not None:
             with lock:
                 if live_stereo:
                     mixer = vocoder.mix_stream(None if live_bed is None else live_bed[0], sample_rate=plan.rate,
                                                params=None if live_bed is None else live_bed[1], stereo=True)
-                else:
+                elif live_bed is not None:
                     mixer = vocoder.mix_stream(live_bed[0], sample_rate=plan.rate, params=live_bed[1])
+                else:
+                    mixer = vocoder.mix_stream(None, sample_rate=plan.rate, bedless=True)
+                if live_room is not None:
+                    roomer = vocoder.room_stream(live_room[0], sample_rate=plan.rate, params=live_room[1])
                 head = mixer.push(None)
             if len(head):
                 yield pcm(head)
@@ -270,6 +285,12 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
             with lock:
                 audio, cuts = vocoder.decode_join(group, params=plan.jp, gaps=plan.gaps[first:end], started=started,
                                                   **plan.fx_of(first, end))
+                if roomer is not None:
+                    sends = ()
+                    if plan.sends is not None:
+                        sends, *sent = push_send_regions(plan.sends, line_of[first:end], plan.gaps[first:end], cuts, *sent)
+                    if len(audio):
+                        audio = roomer.push(audio, sends)
                 if live_stereo:
                     regions, *place = push_regions(plan.pans, line_of[first:end], plan.gaps[first:end], cuts, *place)
                     out = mixer.push(audio, regions) if len(audio) else audio
@@ -283,7 +304,14 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
                 yield pcm(out)
         if mixer is not None and started:
             with lock:
-                rest = mixer.push(None, final=True)
+                if roomer is None:
+                    rest = mixer.push(None, final=True)
+                else:
+                    tail = roomer.push(None, final=True)
+                    if live_stereo:
+                        rest = mixer.push(tail, [(0, len(tail), place[2])] if len(tail) and place[2] != 0 else [], final=True)
+                    else:
+                        rest = mixer.push(tail, final=True)
             if len(rest):
                 yield pcm(rest)
     finally:
@@ -291,8 +319,11 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
         if release is not None:
             release(cancel=True)
         feeder.join()
-        if mixer is not None:
+        if mixer is not None or roomer is not None:
             with lock:
-                mixer.close()
+                if roomer is not None:
+                    roomer.close()
+                if mixer is not None:
+                    mixer.close()
     if not started:
         raise RuntimeError("No audio generated")

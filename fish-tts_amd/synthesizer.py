@@ -616,7 +616,7 @@ class FishTTS:
                                max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                                speed: Optional[float] = None, pitch: Optional[float] = None,
                                loudness: Optional[float] = None, bed=None, live_bed=None, live_stereo: bool = False,
-                               live_pan: float = 0.0, room=None) -> Iterator[bytes]:
+                               live_pan: float = 0.0, room=None, live_room=None) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
@@ -632,7 +632,13 @@ class FishTTS:
         over the live_bed's own left and right, or without a bed (the live stereo mix stage,
         CodecHipEngine.mix_stream(stereo=True): one limiter for both channels, so the image stays where it is); where neither
         ceiling binds the chunks concatenate to synthesize_long(stereo=True, pan=live_pan)'s PCM.  ValueError: a live_pan
-        other than 0 without live_stereo, or outside [-1, 1].  `room` is refused (ValueError): see _no_streamed_room."""
+        other than 0 without live_stereo, or outside [-1, 1].  `room` is refused (ValueError): see _no_streamed_room.
+        `live_room` (a room.Room): the streamed form - every joined group goes through a stream of the live room stage
+        (CodecHipEngine.room_stream) before the mixer, which carries the room's tail from group to group and holds nothing
+        back; the stream ends `tail` longer.  The room stage's ceiling - one gain for the piece - has no streamed form, so the
+        limiter of the live mix stage holds the piece instead: the live_bed's or the live_stereo stream's, or, with neither, a
+        limiter of its own (CodecHipEngine.mix_stream(None, bedless=True)); where it does not bind, the chunks concatenate to
+        CodecHipEngine.room(..., ceiling=False) over the plain stream's audio.  Its values are checked here, as room='s are."""
         from . import segments
         from .script import native_pan
         _no_streamed_bed(bed, "synthesize_long_stream", live_bed)
@@ -644,9 +650,10 @@ class FishTTS:
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
                                loudness, live_stereo, live_pan)
         mixed = self._bed_args(live_bed, plan.rate, silence_db)
+        roomed = self._room_args(live_room, plan.rate)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed), live_bed=mixed,
-                                    live_stereo=live_stereo)
+                                    live_stereo=live_stereo, live_room=roomed)
 
     # ------------------------------------------------------------------ music bed (extension)
     def _bed_args(self, bed, rate: int, silence_db=None):
@@ -826,7 +833,8 @@ class FishTTS:
                                  min_chars: int = 24, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                                  pitch: Optional[float] = None, loudness: Optional[float] = None,
                                  marks: Optional[list] = None, bed=None, live_bed=None, live_stereo: bool = False,
-                                 live_pans: Optional[dict] = None, room=None, sends: Optional[dict] = None) -> Iterator[bytes]:
+                                 live_pans: Optional[dict] = None, room=None, sends: Optional[dict] = None, live_room=None,
+                                 live_sends: Optional[dict] = None) -> Iterator[bytes]:
         """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
         (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
@@ -840,7 +848,10 @@ class FishTTS:
         of its lines, one limiter for both channels); where neither ceiling binds the chunks concatenate to
         synthesize_script(stereo=True, pans=live_pans)'s PCM; `marks` count frames.  ValueError: `live_pans` without
         live_stereo; a Line.pan without it stays refused, as a stereo value on a mono stream.  `room` and `sends` are refused
-        (ValueError): see _no_streamed_room."""
+        (ValueError): see _no_streamed_room.  `live_room` (a room.Room): as synthesize_long_stream's, with `live_sends` -
+        sends='s dict and rules: every joined group is pushed with the send regions of its lines, a line that crosses a group
+        keeping its send.  `marks` do not move: the room adds only its tail, behind the last line.  On a live_stereo stream
+        the tail stays at the pan of the last line heard.  ValueError: `live_sends` without `live_room`."""
         from . import segments
         from .script import line_marks
         _no_streamed_bed(bed, "synthesize_script_stream", live_bed)
@@ -849,9 +860,13 @@ class FishTTS:
             raise ValueError(f"live_stereo must be True or False, got {live_stereo!r}")
         if live_pans is not None and not live_stereo:
             raise ValueError("live_pans needs live_stereo=True: a mono stream has no left and right")
+        if live_sends is not None and live_room is None:
+            raise ValueError("live_sends needs live_room=: without a room there is nothing to send to")
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
-                                 min_chars, sample_rate, speed, pitch, loudness, marks, live_stereo, live_pans)
+                                 min_chars, sample_rate, speed, pitch, loudness, marks, live_stereo, live_pans,
+                                 live_room is not None, live_sends)
         mixed = self._bed_args(live_bed, plan.rate, silence_db)
+        roomed = self._room_args(live_room, plan.rate)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         found = [None] * plan.n_lines
         state = {"at": 0 if mixed is None else mixed[1].lead, "started": False, "told": 0}
@@ -865,7 +880,8 @@ class FishTTS:
             state["told"] = max(state["told"], done)
 
         return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed),
-                                    on_cuts=None if marks is None else on_cuts, live_bed=mixed, live_stereo=live_stereo)
+                                    on_cuts=None if marks is None else on_cuts, live_bed=mixed, live_stereo=live_stereo,
+                                    live_room=roomed)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
@@ -1155,12 +1171,13 @@ def _check_sampling(temperature: float, top_p: float, repetition_penalty: float)
 
 def _no_streamed_room(room, what: str, sends=None) -> None:
     """A stream takes no `room=`: the room stage convolves the whole piece in one call - its tail rings past every later
-    line, and its ceiling is one gain known only when the last sample is.  A live form that carries the tail from push to
-    push does not exist yet."""
+    line, and its ceiling is one gain known only when the last sample is.  `live_room=` (with `live_sends=`) is the streamed
+    form: the same convolution carried from push to push (the live room stage), a limiter in the ceiling's place."""
     if room is not None or sends is not None:
         raise ValueError(f"room needs the whole piece: {what} hands out audio before its end, while the room stage's tail "
                          "rings over everything that follows and its ceiling is one gain for the piece; use synthesize_long / "
-                         "synthesize_script with room=, or reverb() on the finished WAV")
+                         "synthesize_script with room=, or reverb() on the finished WAV; use live_room= (and live_sends=) for a "
+                         "room on the stream")
 
 
 def _no_streamed_bed(bed, what: str, live_bed=None) -> None:

@@ -735,6 +735,63 @@ ft_status ft_codec_room(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_r
 /* Host only: L and N of a call whose IR has nh samples at the output rate.  Either output pointer may be NULL.  FT_ERR_ARG /
  * FT_ERR_TOO_LONG as ft_codec_room judges the values. */
 ft_status ft_room_plan(int32_t sample_rate, int64_t n, int64_t nh, const ft_room_params* rp, int64_t* L, int64_t* N);
+/* Live room.  The room stage on a stream: synthesize_long_stream and synthesize_script_stream hand out audio before the piece
+ * ends.  Of Room only the ceiling - one gain from the peak of the whole piece - needs the whole piece; the convolution is
+ * causal: c[i] reads xs[i - predelay - k] for k >= 0, so an output is final the moment its input sample has arrived and nothing
+ * is held back.  Room, its bits and its refusals stay as they are; what this paragraph does not state is Room's.  Stated, which
+ * fixes every bit of the result for finite inputs:
+ *   Inputs: the programme x at the output rate Fo, float32, in pushes of any size (0 samples allowed; n is known at `final`,
+ *   and n = 0 is allowed).  Each push carries its own send regions, ft_send_region {a, e, send} relative to that push:
+ *   0 <= a < e <= n_push, sorted and disjoint (they may touch), a send in [0, 6000] or -1, 0 <= R <= 4096 per push; a push of 0
+ *   samples takes R = 0.  A line that crosses a cut is given as two regions of equal send.  One IR item and ft_room_params as
+ *   ft_codec_room takes them, with rp->ceiling = 0: a stream has no whole-piece peak, and a live mix stage behind it has the
+ *   limiter (ft_codec_mix_stream_begin_bare where the stream has neither bed nor panning).
+ *   begin: the response prepared as ft_codec_room prepares it - the intake launches and the resampler as Mix prepares its bed,
+ *   room_ir_kernel, room_gain_kernel - and hn kept on the device for the life of the stream.  With normalize, E = 0 or a
+ *   non-finite E is FT_ERR_ARG after those launches, and the stream is freed.
+ *   push: with n_in the samples pushed before, a push of n samples emits exactly the outputs [n_in, n_in + n) of Room's y; a
+ *   `final` push emits [n_in, n_in + n + tl), tl by Room's tail rule.  Nothing is held back.
+ *   Result: the concatenated outputs are, bit for bit and whatever the cutting, the y of ft_codec_room with ceiling = 0 on the
+ *   concatenated programme with every push's regions moved to the timeline (a region of a push that begins at n_in lies at
+ *   [n_in + a, n_in + e)).  The chain of an output is Room's chain - the same kernel text over another source of xs - and xs
+ *   outside what has been pushed is +0.0, as Room's is outside [0, n).  A stream whose programme is empty at `final` emits tl
+ *   samples of +0.0.
+ *   Non-finite values: Room's range, with one difference that only narrows it - an output emitted by a push earlier than the
+ *   one that holds x[j] is as stated even inside [j - 1024, j).
+ *   Reported (ft_room_info, by ft_codec_room_stream_info at any time and by ft_codec_room_live): nh, L, E, gn and the IR's
+ *   ft_intake_info from `begin`; N = the samples emitted so far; pk = the max |y| over the pushes so far, by the integer atomicMax
+ *   of Room (a NaN is never the peak); sg = 1 and capped = 0.
+ * Limits and refusals.  begin: Room's checks in Room's order, without n, the regions and the capacity; a ceiling other than 0 is
+ * FT_ERR_ARG where Room judges the ceiling.  push: everything is judged before any device work and a refused push leaves its
+ * stream as it was.  In this order: a push after `final` (FT_ERR_STATE); n < 0 or a null x with n > 0; the regions (Room's
+ * region checks over the push's n) (FT_ERR_ARG each); n_in + n + tl beyond 2^28 (FT_ERR_TOO_LONG, at the push that would cross
+ * it); a capacity below what the push emits (FT_ERR_ARG).  Several room streams may be open on one context, each with its own
+ * state; all device work runs on the codec's stream, under the codec's lock.
+ * On the device a stream holds hn, the words its launches reduce into (E, gn, pk) and a carry of the last
+ * min(n_in, predelay + L - 1) sent samples in two copies (a push reads one and writes the other), so its memory is bounded by
+ * predelay + L - 1 - plus, in the context's buffers, the largest push - never by the length of the stream; the counters live on
+ * the host.  Three launches per push, a launch with nothing to do left out: rooml_send_kernel (xs of the push from its own
+ * regions; left out without regions and with rp->send = 0), rooml_conv_kernel (room_conv_kernel's text, a word of its staging
+ * taken from the carry, from the push, or +0.0 outside both; the dry term from the push; 2^22 outputs per launch),
+ * rooml_roll_kernel (the next carry from the old one and the push). */
+typedef struct ft_room_stream ft_room_stream;
+/* A stream of the stage: prepares the response and allocates the stream's state. */
+ft_status ft_codec_room_stream_begin(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* ir, const ft_room_params* rp,
+                                     ft_room_stream** out);
+/* One push of n >= 0 programme samples (host; x may be NULL when n = 0) with its R regions (relative to the push; regions may be
+ * NULL when R = 0); final: the programme ends with it.  The outputs are written into y (host, `capacity` samples) and their
+ * count into *n_out: n, or n + tl at `final`. */
+ft_status ft_codec_room_stream_push(ft_room_stream* rs, const float* x, int64_t n, const ft_send_region* regions, int32_t R,
+                                    int32_t final, float* y, int64_t capacity, int64_t* n_out);
+/* What the stream did so far (above: Reported). */
+ft_status ft_codec_room_stream_info(ft_room_stream* rs, ft_room_info* info);
+/* Frees the stream (after its context was destroyed: the host handle alone). */
+void ft_codec_room_stream_end(ft_room_stream* rs);
+/* The stage on a host waveform, as a stream whose only push is its last: y receives the N = n + tl samples (capacity >= N),
+ * *total = N.  x may be NULL when n = 0. */
+ft_status ft_codec_room_live(ft_ctx* ctx, const float* x, int64_t n, int32_t sample_rate, const ft_send_region* regions, int32_t R,
+                             const ft_intake_item* ir, const ft_room_params* rp, float* y, int64_t capacity, int64_t* total,
+                             ft_room_info* info);
 /* Live mix.  The mix stage on a stream: synthesize_long_stream and synthesize_script_stream hand out audio before the piece
  * ends, and the one gain of Mix's ceiling is known only there.  Everything in Mix before the ceiling is local in time, so this
  * second stage keeps it as it is and replaces the one gain by a look-ahead limiter with the duck's own cone shape, driven by
@@ -802,6 +859,12 @@ ft_status ft_codec_mix_live(ft_ctx* ctx, const float* x, int64_t n, int32_t samp
 /* A stream of the stage: prepares the bed and allocates the stream's state. */
 ft_status ft_codec_mix_stream_begin(ft_ctx* ctx, int32_t sample_rate, const ft_intake_item* bed, const ft_mix_params* mp,
                                     ft_mix_stream** out);
+/* A mono stream of the stage without a bed: the limiter alone, for a stream that has a room (Live room) and neither music nor
+ * panning.  Stated as Live mix with the bed term +0.0: t = +0.0, nb = 0, nothing loops, so m[i] = s[i] + 0.0, and where the
+ * programme never exceeds cf the output is x + 0.0 behind `lead` zeros; mp as ft_codec_mix_stream_begin judges it, its bed
+ * fields unread, the report's bed zeroed.  Pushed by ft_codec_mix_stream_push and ended by ft_codec_mix_stream_end.
+ * ft_codec_mix_stream_begin keeps refusing a null bed. */
+ft_status ft_codec_mix_stream_begin_bare(ft_ctx* ctx, int32_t sample_rate, const ft_mix_params* mp, ft_mix_stream** out);
 /* One push of n >= 0 programme samples (host; x may be NULL when n = 0); final: the programme ends with it.  The samples that
  * became final are written into y (host, `capacity` samples) and their count into *n_out. */
 ft_status ft_codec_mix_stream_push(ft_mix_stream* ms, const float* x, int64_t n, int32_t final, float* y, int64_t capacity,
