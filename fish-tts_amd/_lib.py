@@ -92,6 +92,15 @@ class ft_room_info(C.Structure):
                 ("sg", C.c_float), ("capped", C.c_int32), ("ir", ft_intake_info)]
 
 
+class ft_flac_params(C.Structure):
+    _fields_ = [("blocksize", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ft_flac_info(C.Structure):
+    _fields_ = [("frames", C.c_int64), ("bytes", C.c_int64), ("min_frame", C.c_int32), ("max_frame", C.c_int32),
+                ("kinds", C.c_int32 * 7), ("assignments", C.c_int32 * 5)]
+
+
 class ft_mix_live_info(C.Structure):
     _fields_ = [("N", C.c_int64), ("nb", C.c_int64), ("Nh", C.c_int64), ("active", C.c_int64), ("dmax", C.c_int32),
                 ("lmax", C.c_int32), ("qmax", C.c_float), ("reserved", C.c_int32), ("bed", ft_intake_info)]
@@ -205,6 +214,9 @@ SYMBOLS = {
     "ft_codec_room_stream_end": (None, [_P]),
     "ft_codec_room_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_room_params),
                                        _P, C.c_int64, _P, C.POINTER(ft_room_info)]),
+    "ft_codec_flac": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ft_flac_params), _P, C.c_int64,
+                                  C.POINTER(C.c_int64), C.POINTER(ft_flac_info)]),
+    "ft_flac_bound": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ft_codec_mix_stream_begin_bare": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_mix_params), C.POINTER(_P)]),
     "ft_mix_live_plan": (C.c_int32, [C.c_int32, C.POINTER(ft_mix_params), C.c_int64, C.c_int32, _P, _P]),
     "ft_codec_mix_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), _P,

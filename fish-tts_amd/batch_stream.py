@@ -82,6 +82,16 @@ def checked_fx(fx=None, sample_rate=None, speed=None, pitch=None, loudness=None,
     return OutputFx.of(sample_rate, speed, pitch, loudness, live_loudness)
 
 
+FORMATS = ("wav", "flac")       # what `format=` of a call that returns a whole file may be
+
+
+def checked_format(format) -> str:
+    """`format` itself when it names a file format the whole calls write (ValueError otherwise, before any work)."""
+    if not isinstance(format, str) or format not in FORMATS:
+        raise ValueError(f"format must be one of {FORMATS}, got {format!r}")
+    return format
+
+
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                       min_first_chunk: int = 10, sample_rate: Optional[int] = None,
                       speed: Optional[float] = None, pitch: Optional[float] = None, fx=None,

@@ -109,6 +109,25 @@ class RoomReport:
                    float(np.float32(i.sg)), bool(i.capped), IntakeReport.of(i.ir))
 
 
+@dataclass(frozen=True)
+class FlacReport:
+    """What the FLAC stage wrote (ft_flac_info): `frames`, the stream's `bytes`, the smallest and the largest frame, `kinds` -
+    a count per subframe kind, CONSTANT, VERBATIM, FIXED 0..4 - and `assignments` - a count per channel assignment, 0000 (mono),
+    0001 (L, R), 1000 (L, S), 1001 (S, R), 1010 (M, S)."""
+    frames: int
+    bytes: int
+    min_frame: int
+    max_frame: int
+    kinds: Tuple[int, ...]
+    assignments: Tuple[int, ...]
+
+    @classmethod
+    def of(cls, i: "L.ft_flac_info") -> "FlacReport":
+        return cls(int(i.frames), int(i.bytes), int(i.min_frame), int(i.max_frame), tuple(int(v) for v in i.kinds),
+                   tuple(int(v) for v in i.assignments))
+
+
+FLAC_BLOCKSIZES = (256, 512, 1024, 2048, 4096)
 MAX_SEND_REGIONS = 4096           # per call of ft_codec_room
 
 
@@ -942,6 +961,40 @@ class CodecHipEngine:
                                            y.ctypes.data_as(C.c_void_p), N.value, C.byref(total), C.byref(info)), "ft_codec_room")
         del keep
         return y[:total.value], RoomReport.of(info)
+
+    def flac(self, audio: np.ndarray, sample_rate: Optional[int] = None, blocksize: int = 4096):
+        """A finished waveform as a FLAC file, packed on the device (ft_codec_flac): `audio` is float32 - quantised there by
+        _to_wav_bytes's rule, so the file decodes to the 16-bit WAV's samples - or int16, taken as it is; (N,) mono or (N, 2)
+        left then right.  Fixed predictors only: the stream is stated to the bit in include/fishtts_hip.h.  Returns
+        (bytes, FlacReport)."""
+        what = "flac"
+        rate = OutputFx.of(sample_rate=sample_rate).wav_rate
+        if isinstance(blocksize, bool) or not isinstance(blocksize, (int, np.integer)) or int(blocksize) not in FLAC_BLOCKSIZES:
+            raise ValueError(f"{what}: blocksize must be one of {FLAC_BLOCKSIZES}, got {blocksize!r}")
+        x = np.asarray(audio)
+        if x.dtype != np.int16:
+            if x.dtype.kind not in "fiu":
+                raise ValueError(f"{what}: audio must be float32 or int16, got {x.dtype}")
+            if x.dtype.kind in "iu":
+                raise ValueError(f"{what}: integer audio must be int16, got {x.dtype}")
+            x = x.astype(np.float32)
+        if x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[1] != 2):
+            raise ValueError(f"{what}: a waveform is (N,) or (N, 2), got {x.shape}")
+        if x.shape[0] < 1:
+            raise ValueError(f"{what}: an empty waveform")
+        x = np.ascontiguousarray(x)
+        n, channels = x.shape[0], x.ndim
+        cap = int(self.lib.ft_flac_bound(n, channels, int(blocksize)))
+        if cap < 0:
+            raise ValueError(f"{what}: {n} samples are more than a call takes (2^28)")
+        out = np.empty(cap, dtype=np.uint8)
+        fp = L.ft_flac_params(int(blocksize), 0)
+        total = C.c_int64(0)
+        info = L.ft_flac_info()
+        self._check(self.lib.ft_codec_flac(self._h, x.ctypes.data_as(C.c_void_p), 1 if x.dtype == np.int16 else 0, n, channels, rate,
+                                           C.byref(fp), out.ctypes.data_as(C.c_void_p), cap, C.byref(total), C.byref(info)),
+                    "ft_codec_flac")
+        return out[:total.value].tobytes(), FlacReport.of(info)
 
     def _room_live_args(self, what: str, clip, sample_rate, params):
         """(rate, IR item array, what keeps its bytes alive, ft_room_params with ceiling 0, tail) of a live room call, checked

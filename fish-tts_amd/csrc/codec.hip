@@ -13,6 +13,7 @@
 #include "stage_kernels.h"
 #include "stereo_kernels.h"
 #include "room_kernels.h"
+#include "flac_kernels.h"
 #include "engine.h"
 #include "fx_chain.h"
 #include "join_plan.h"
@@ -133,6 +134,14 @@ struct CodecState {
     double* rm_e = nullptr;
     RoomOut* rm_out = nullptr;
     size_t rm_xscap = 0, rm_tcap = 0, rm_hncap = 0, rm_ecap = 0;
+    // FLAC stage (ft_codec_flac): the raw samples, one decision per frame and signal, the frames at their worst-case stride,
+    // their lengths and places, the compact stream, the counters; allocated on the first call (the buffers grow on need)
+    unsigned char *fl_in = nullptr, *fl_slots = nullptr, *fl_stream = nullptr;
+    FlSig* fl_sig = nullptr;
+    int* fl_len = nullptr;
+    long long* fl_off = nullptr;
+    FlacOut* fl_out = nullptr;
+    size_t fl_incap = 0, fl_slotcap = 0, fl_streamcap = 0, fl_sigcap = 0, fl_lencap = 0, fl_offcap = 0;
     // live mix stage (ft_codec_mix_stream_*): the open streams (their device state is freed with the context), and what a
     // push stages - its samples, the m of the hops it completes, the samples it emits; the buffers grow on need
     std::vector<ft_mix_stream*> mix_streams;
@@ -3118,6 +3127,68 @@ extern "C" ft_status ft_codec_room(ft_ctx* ctx, const float* x, int64_t n, int32
     info->N = pl.N; info->nh = pl.nh; info->L = pl.L; info->E = out.E; info->gn = out.gn; info->pk = pk; info->sg = sg;
     info->capped = capped ? 1 : 0;
     info->ir = b.info;
+    return FT_OK;
+}
+
+// ---- FLAC stage (flac_kernels.h; fishtts_hip.h states it, flac_plan.h checks and sizes it)
+static_assert(sizeof(ft_flac_info) == 72 && offsetof(ft_flac_info, kinds) == 24 && sizeof(ft_flac_params) == 8, "ft_flac_info layout");
+static_assert(sizeof(FlSig) == 8 + FL_FINE && FL_THREADS == FL_FINE, "a thread per finest partition");
+
+extern "C" int64_t ft_flac_bound(int64_t n, int32_t channels, int32_t blocksize) { return flac::fl_bound(n, channels, blocksize); }
+
+extern "C" ft_status ft_codec_flac(ft_ctx* ctx, const void* x, int32_t fmt, int64_t n, int32_t channels, int32_t sample_rate,
+                                   const ft_flac_params* fp, uint8_t* out, int64_t capacity, int64_t* total, ft_flac_info* info) {
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    const std::string fn = "ft_codec_flac";
+    if (!x || !fp || !out || !total || !info) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    flac::FlArgs a;
+    a.fmt = fmt; a.channels = channels; a.rate = sample_rate; a.blocksize = fp->blocksize; a.reserved = fp->reserved;
+    a.n = n; a.capacity = capacity;
+    bool too_long = false;
+    if (const char* why = flac::fl_check(a, &too_long)) return ft_fail(ctx, too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = s->stream;
+    const int B = fp->blocksize;
+    const long long F = flac::fl_frames(n, B);
+    const int nsig = channels == 2 ? 4 : 1;
+    const size_t in_bytes = (size_t)n * channels * (fmt ? 2 : 4);
+    const size_t stride = (size_t)((flac::fl_frame_bound(B, channels) + 3) / 4 * 4);
+    FT_TRY(cgrow(ctx, &s->fl_in, &s->fl_incap, in_bytes));
+    FT_TRY(cgrow(ctx, &s->fl_sig, &s->fl_sigcap, (size_t)F * nsig));
+    FT_TRY(cgrow(ctx, &s->fl_slots, &s->fl_slotcap, (size_t)F * stride + 8));
+    FT_TRY(cgrow(ctx, &s->fl_len, &s->fl_lencap, (size_t)F));
+    FT_TRY(cgrow(ctx, &s->fl_off, &s->fl_offcap, (size_t)F));
+    FT_TRY(cgrow(ctx, &s->fl_stream, &s->fl_streamcap, (size_t)flac::fl_bound(n, channels, B) + 8));
+    if (!s->fl_out) FT_TRY(cmalloc(ctx, &s->fl_out, (size_t)1));
+    FT_HIP(ctx, hipMemcpyAsync(s->fl_in, x, in_bytes, hipMemcpyHostToDevice, st));
+    FT_HIP(ctx, hipMemsetAsync(s->fl_out, 0, sizeof(FlacOut), st));
+    FlacP p;
+    memset(&p, 0, sizeof p);
+    p.x = s->fl_in; p.n = n; p.fmt = fmt; p.channels = channels; p.B = B; p.rate = sample_rate; p.F = (int)F; p.nsig = nsig;
+    p.sig = s->fl_sig; p.slots = s->fl_slots; p.stride = (int)stride; p.flen = s->fl_len; p.foff = s->fl_off;
+    p.stream = s->fl_stream; p.out = s->fl_out;
+    flac_analyse_kernel<<<dim3((unsigned)F, (unsigned)nsig), FL_THREADS, 0, st>>>(p);
+    flac_pack_kernel<<<(unsigned)F, FL_THREADS, 0, st>>>(p);
+    flac_scan_kernel<<<1, FL_SCAN_THREADS, 0, st>>>(p);
+    flac_gather_kernel<<<(unsigned)F, FL_THREADS, 0, st>>>(p);
+    FlacOut o;
+    FT_HIP(ctx, hipMemcpyAsync(&o, s->fl_out, sizeof o, hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));              // the stream's length decides how much comes back
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
+    if (o.overflow != 0) return ft_fail(ctx, FT_ERR_STATE, fn + ": a frame did not fit its bound");
+    if (o.total < flac::FL_STREAM_HEAD || o.total > capacity || o.frames != (int)F)
+        return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream's length is not within the bound");
+    FT_HIP(ctx, hipMemcpyAsync(out, s->fl_stream, (size_t)o.total, hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    *total = o.total;
+    memset(info, 0, sizeof *info);
+    info->frames = o.frames; info->bytes = o.total; info->min_frame = o.fmin; info->max_frame = o.fmax;
+    for (int i = 0; i < flac::FL_KINDS; ++i) info->kinds[i] = o.kinds[i];
+    for (int i = 0; i < flac::FL_ASSIGNMENTS; ++i) info->assignments[i] = o.assignments[i];
     return FT_OK;
 }
 

@@ -43,7 +43,7 @@ from typing import TYPE_CHECKING, Callable, Iterator, List, Optional, Sequence, 
 
 import numpy as np
 
-from .batch_stream import ChunkCutter, checked_fx, pcm16
+from .batch_stream import ChunkCutter, checked_format, checked_fx, pcm16
 
 if TYPE_CHECKING:
     from .batch import Utterance
@@ -149,14 +149,16 @@ class BatchServer:
     def synthesize(self, text: str, references=None, temperature: float = 0.7, top_p: float = 0.8,
                    repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
                    sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                   pitch: Optional[float] = None, fx=None, loudness: Optional[float] = None) -> bytes:
+                   pitch: Optional[float] = None, fx=None, loudness: Optional[float] = None, format: str = "wav") -> bytes:
         """Text -> WAV bytes: FishTTS.synthesize's result for seed 0 (draws with `seed`).  Safe from any number of threads;
         `references=None` means the instance's set_references voices; `sample_rate`, `speed`, `pitch` and `loudness` as
         FishTTS.synthesize_at (an unsupported one raises ValueError here, before anything is queued; requests of different
-        voices then come out at one level), or `fx`: these already checked (codec_engine.OutputFx)."""
+        voices then come out at one level), or `fx`: these already checked (codec_engine.OutputFx).  `format`: "wav", or
+        "flac" for a FLAC file of the same samples (as FishTTS.synthesize_at; any other value raises ValueError here)."""
         fx = checked_fx(fx, sample_rate, speed, pitch, loudness)
+        checked_format(format)
         utt, n_prefix = self._prepare(text, references, temperature, top_p, repetition_penalty, max_tokens, seed)
-        item = self.submit(utt, n_prefix, fx=fx).out.get()
+        item = self.submit(utt, n_prefix, fx=fx, format=format).out.get()
         if isinstance(item, _Failed):
             raise item.error
         return item
@@ -164,7 +166,7 @@ class BatchServer:
     def synthesize_stream(self, text: str, references=None, chunk_tokens: int = 20, min_first_chunk: int = 10,
                           seamless: bool = False, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                           pitch: Optional[float] = None, fx=None, loudness: Optional[float] = None,
-                          live_loudness: Optional[float] = None, **sampling) -> Iterator[bytes]:
+                          live_loudness: Optional[float] = None, format: Optional[str] = None, **sampling) -> Iterator[bytes]:
         """Yields int16 PCM chunks as FishTTS.synthesize_stream does: seamless=False (the reference's default) every chunk
         decoded from zero state; seamless=True one stateful CodecStream per request, the chunks cut as
         synthesize_batch_stream cuts them.  `sampling`: temperature, top_p, repetition_penalty, max_tokens, seed.  The
@@ -174,9 +176,13 @@ class BatchServer:
         `fx`: the three already checked.  `loudness` (or an `fx` with a level) raises ValueError here: the level needs the whole
         utterance.  `live_loudness` (or an `fx` with a ride stage; as FishTTS.synthesize_stream) is what a stream takes
         instead, with seamless=True only (ValueError here otherwise): the request's CodecStream carries the ride stage, in the
-        same decode_streams call as every other ready chunk."""
+        same decode_streams call as every other ready chunk.  `format` is refused (ValueError here): a stream hands out raw
+        PCM, and the FLAC stage packs a finished waveform."""
         if chunk_tokens < 1 or min_first_chunk < 1:
             raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
+        if format is not None:
+            raise ValueError("format needs the whole piece: BatchServer.synthesize_stream hands out int16 PCM chunks before the "
+                             "piece's end, and the FLAC stage packs a finished waveform; use synthesize(format=)")
         fx = checked_fx(fx, sample_rate, speed, pitch, loudness, live_loudness).no_level("BatchServer.synthesize_stream")
         if fx.live is not None and not seamless:
             raise ValueError("live_loudness needs seamless=True: seamless=False chunks are independent waveforms, and "
@@ -194,15 +200,17 @@ class BatchServer:
     def submit(self, utt: Utterance, n_prefix: int = 0, stream: bool = False, seamless: bool = False,
                chunk_tokens: int = 20, min_first_chunk: int = 10, sample_rate: Optional[int] = None,
                speed: Optional[float] = None, pitch: Optional[float] = None, codes: bool = False,
-               voice_cache=None, fx=None) -> _Request:
+               voice_cache=None, fx=None, format: str = "wav") -> _Request:
         """Queues one prepared utterance (the layer under synthesize / synthesize_stream); its output arrives on
         `.out`.  `codes`: the output is the utterance's codes (Utterance.codes()), no audio; `voice_cache`: the PrefixCache
         its voice prefix lives in instead of the server's.  Raises ServerClosed once the server is closing or has failed."""
         if self._codec is None:
             raise RuntimeError("Vocoder not loaded")
+        checked_format(format)                   # (here, on the caller's thread: a bad value must not reach the worker)
         mode = "codes" if codes else ("seamless" if seamless else "chunks") if stream else "wav"
         req = _Request(utt, n_prefix, mode, chunk_tokens, min_first_chunk, checked_fx(fx, sample_rate, speed, pitch))
         req.cache = voice_cache
+        req.format = format           # of a "wav" request's file: "wav", or "flac" (decode_wav is then called with format=)
         with self._lock:
             if self._error is not None:
                 raise ServerClosed(f"BatchServer failed: {self._error!r}") from self._error
@@ -542,7 +550,7 @@ class BatchServer:
                         if not codes.shape[1]:
                             self._last_out(r, _Failed(RuntimeError("No audio generated")))
                         else:
-                            self._last_out(r, self._decode_wav(codes, **r.fx.kw))
+                            self._last_out(r, self._decode_wav(codes, **r.fx.kw, **({} if r.format == "wav" else {"format": r.format})))
         except BaseException as e:  # noqa: BLE001
             self._fail(e)
         finally:

@@ -366,7 +366,7 @@ class FishTTS:
     def synthesize_at(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                       top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048,
                       sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                      pitch: Optional[float] = None, loudness: Optional[float] = None) -> bytes:
+                      pitch: Optional[float] = None, loudness: Optional[float] = None, format: str = "wav") -> bytes:
         """Extension: synthesize() with the WAV at `sample_rate` (resampled on the GPU; None or 44100: the codec's own
         rate, byte for byte synthesize()'s result; an unsupported rate raises ValueError before any work -
         codec_engine.output_rate) and at speaking rate `speed` (a factor in [0.5, 2.0], the waveform time-scaled on the
@@ -378,14 +378,18 @@ class FishTTS:
         work - codec_engine.output_pitch, output_fx), and levelled to `loudness` LUFS (a target in [-50, -5]: the
         utterance's integrated loudness per ITU-R BS.1770-4 is measured on the GPU behind the other stages and one gain
         brings it to the target, the sample peak held at -1 dBFS; None: the model's own level, byte for byte the result
-        without it; anything else raises ValueError before any work - codec_engine.OutputFx.of)."""
+        without it; anything else raises ValueError before any work - codec_engine.OutputFx.of).  `format`: "wav", or "flac"
+        for a FLAC file of the same 16-bit samples, packed losslessly on the GPU (the FLAC stage, CodecHipEngine.flac); any
+        other value raises ValueError before any work."""
         from .generation import generate_long
         from .serve import ServerClosed
         fx = _output_fx(sample_rate, speed, pitch, loudness)
+        _check_format(format)
         srv = getattr(self, "_server", None)
         if srv is not None:
             try:
-                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens, fx=fx)
+                return srv.synthesize(text, references, temperature, top_p, repetition_penalty, max_tokens, fx=fx,
+                                      **_format_kw(format))
             except ServerClosed:
                 pass                          # closed meanwhile: served here, once the server has let go of _gen_lock
         prompt_text, prompt_tokens = self._get_prompt_data(references)
@@ -401,7 +405,7 @@ class FishTTS:
                     break
         if not codes_list:
             raise RuntimeError("No audio generated")
-        return self._decode_to_wav(np.concatenate(codes_list, axis=1), fx)
+        return self._decode_to_wav(np.concatenate(codes_list, axis=1), fx, **_format_kw(format))
 
     def _batch_utterances(self, texts: List[str], references, temperature: float, top_p: float,
                           repetition_penalty: float, max_tokens: int, seed: int, seeds: Optional[List[int]],
@@ -468,13 +472,15 @@ class FishTTS:
                          temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
                          max_tokens: int = 2048, seed: int = 0, seeds: Optional[List[int]] = None,
                          sample_rate: Optional[int] = None, speed: Optional[float] = None,
-                         pitch: Optional[float] = None, loudness: Optional[float] = None) -> List[bytes]:
+                         pitch: Optional[float] = None, loudness: Optional[float] = None,
+                         format: str = "wav") -> List[bytes]:
         """Extension (BASELINE configs[2]): many texts -> WAV bytes each, decoded `max_batch` at a time in lock step
         with refill (fish_tts_amd.batch); utterance i uses seed + i, or seeds[i] when `seeds` is given (a sharded run
         passes the GLOBAL indices so an utterance draws the same noise on any number of GPUs).  Same per-utterance
         semantics as synthesize(), `sample_rate`, `speed`, `pitch` and `loudness` (as synthesize_at; every utterance is
-        levelled on its own) included."""
+        levelled on its own) and `format` included."""
         fx = _output_fx(sample_rate, speed, pitch, loudness)
+        _check_format(format)
         self._no_server("synthesize_batch")
         with self._gen_lock:
             engines, utts = self._batch_utterances(texts, references, temperature, top_p, repetition_penalty, max_tokens,
@@ -485,7 +491,7 @@ class FishTTS:
             codes = u.codes()
             if codes.shape[1] == 0:
                 raise RuntimeError("No audio generated")
-            out.append(self._decode_to_wav(codes, fx))
+            out.append(self._decode_to_wav(codes, fx, **_format_kw(format)))
         return out
 
     def synthesize_batch_stream(self, texts: List[str], references: Optional[List[VoiceProfile]] = None,
@@ -495,7 +501,8 @@ class FishTTS:
                                 sample_rate: Optional[int] = None,
                                 speed: Optional[float] = None,
                                 pitch: Optional[float] = None, loudness: Optional[float] = None,
-                                live_loudness: Optional[float] = None) -> Iterator[Tuple[int, bytes]]:
+                                live_loudness: Optional[float] = None,
+                                format: Optional[str] = None) -> Iterator[Tuple[int, bytes]]:
         """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
         PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
         `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
@@ -512,8 +519,10 @@ class FishTTS:
         the two); the tail travels in the same way.
         `loudness`: ValueError here, before any work - the level needs the whole utterance (synthesize_batch has it).
         `live_loudness` (LUFS in [-50, -5]) is what a stream takes instead: each utterance's stream is ridden toward that
-        loudness on the GPU by a gain that looks one second ahead, last in its chain (as synthesize_stream)."""
+        loudness on the GPU by a gain that looks one second ahead, last in its chain (as synthesize_stream).
+        `format` is refused (ValueError): see _no_streamed_format."""
         from .batch_stream import stream_utterances
+        _no_streamed_format(format, "synthesize_batch_stream")
         fx = _output_fx(sample_rate, speed, pitch, loudness, live_loudness).no_level("synthesize_batch_stream")
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
@@ -578,7 +587,7 @@ class FishTTS:
                         max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                         speed: Optional[float] = None, pitch: Optional[float] = None,
                         loudness: Optional[float] = None, bed=None, stereo: bool = False, pan: float = 0.0,
-                        room=None) -> bytes:
+                        room=None, format: str = "wav") -> bytes:
         """Extension: a text of any length -> one WAV.  The text is split into segments of at most `max_chars` bytes at
         sentence ends (longform.split_text; pieces below `min_chars` join a neighbour), every segment is an utterance of
         its own - `max_tokens` frames at most each, segment i drawing with seed + i - and all of them run as ONE lock-step
@@ -600,15 +609,17 @@ class FishTTS:
         bad value in `room` or a response file the intake does not read, a pan without stereo or outside [-1, 1], pause /
         paragraph_pause outside [0, 5] s, silence_db outside
         [-90, 0], max_chars outside [16, 1000], min_chars outside [0, max_chars], no text, a bad sample_rate / speed / pitch /
-        loudness, a bad value in `bed` or a bed file the intake does not read."""
+        loudness, a bad value in `bed` or a bed file the intake does not read, a `format` other than "wav" or "flac" (as
+        synthesize_at: the finished piece, mono or stereo, as a FLAC file of the WAV's samples)."""
         from . import segments
+        _check_format(format)
         plan = self._long_plan(text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
                                loudness, stereo, pan)
         mixed = self._bed_args(bed, plan.rate, silence_db)
         roomed = self._room_args(room, plan.rate)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         audio, _ = segments.join_wav(plan, **self._segment_calls(plan, references, sampling, seed), bed=mixed, room=roomed)
-        return self._to_wav_bytes(audio, plan.rate)
+        return self._to_file_bytes(audio, plan.rate, format)
 
     def synthesize_long_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, temperature: float = 0.7,
                                top_p: float = 0.8, repetition_penalty: float = 1.1, max_tokens: int = 2048, seed: int = 0,
@@ -616,7 +627,8 @@ class FishTTS:
                                max_chars: int = 200, min_chars: int = 24, sample_rate: Optional[int] = None,
                                speed: Optional[float] = None, pitch: Optional[float] = None,
                                loudness: Optional[float] = None, bed=None, live_bed=None, live_stereo: bool = False,
-                               live_pan: float = 0.0, room=None, live_room=None) -> Iterator[bytes]:
+                               live_pan: float = 0.0, room=None, live_room=None,
+                               format: Optional[str] = None) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
@@ -641,6 +653,7 @@ class FishTTS:
         CodecHipEngine.room(..., ceiling=False) over the plain stream's audio.  Its values are checked here, as room='s are."""
         from . import segments
         from .script import native_pan
+        _no_streamed_format(format, "synthesize_long_stream")
         _no_streamed_bed(bed, "synthesize_long_stream", live_bed)
         _no_streamed_room(room, "synthesize_long_stream")
         if not isinstance(live_stereo, bool):
@@ -689,11 +702,12 @@ class FishTTS:
         self._vocoder._intake_args("room", [clip], (0.0, 1, 0, 0), None, room.channel)
         return clip, rp
 
-    def reverb(self, wav_bytes: bytes, room, report: Optional[list] = None) -> bytes:
+    def reverb(self, wav_bytes: bytes, room, report: Optional[list] = None, format: str = "wav") -> bytes:
         """Extension: a finished 16-bit mono WAV - at 44.1 kHz or any rate `sample_rate=` takes - through `room` (a
         room.Room) -> one WAV at the same rate, the room's tail longer (the room stage, CodecHipEngine.room, with its
         ceiling).  `report`: a list that receives the RoomReport.  ValueError before any device work: not 16-bit mono, no
-        sample, an unsupported rate, a bad Room."""
+        sample, an unsupported rate, a bad Room, a `format` other than "wav" or "flac" (as synthesize_at)."""
+        _check_format(format)
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         with wave.open(io.BytesIO(wav_bytes), "rb") as wf:
@@ -712,16 +726,17 @@ class FishTTS:
             y, rep = self._vocoder.room(audio, clip, (), sample_rate=rate, params=rp, ceiling=True)
         if report is not None:
             report.append(rep)
-        return self._to_wav_bytes(y, rate)
+        return self._to_file_bytes(y, rate, format)
 
     def mix(self, wav_bytes: bytes, bed, silence_db: Optional[float] = None, report: Optional[list] = None,
-            stereo: bool = False) -> bytes:
+            stereo: bool = False, format: str = "wav") -> bytes:
         """Extension: a finished 16-bit mono WAV - at 44.1 kHz or any rate `sample_rate=` takes - with `bed` (a mix.Bed)
         under it -> one WAV at the same rate, `lead` + `tail` longer (the mix stage, CodecHipEngine.mix).  `silence_db`:
         what counts as speech where the Bed has no threshold_db (None: -45).  `report`: a list that receives the
         MixReport.  `stereo`: a two-channel WAV - the programme (still mono) in the centre over the bed's own left and
         right (CodecHipEngine.mix_stereo).  ValueError before any device work: not 16-bit mono, no sample, an unsupported
-        rate, a bad Bed."""
+        rate, a bad Bed, a `format` other than "wav" or "flac" (as synthesize_at)."""
+        _check_format(format)
         if self._vocoder is None:
             raise RuntimeError("Vocoder not loaded")
         with wave.open(io.BytesIO(wav_bytes), "rb") as wf:
@@ -745,7 +760,26 @@ class FishTTS:
                 y, rep = self._vocoder.mix(audio, clip, sample_rate=rate, params=mp)
         if report is not None:
             report.append(rep)
-        return self._to_wav_bytes(y, rate)
+        return self._to_file_bytes(y, rate, format)
+
+    def to_flac(self, wav_bytes: bytes, blocksize: int = 4096) -> bytes:
+        """Extension: a finished 16-bit PCM WAV, mono or stereo, at any rate `sample_rate=` takes -> a FLAC file of its
+        samples, packed on the GPU (the FLAC stage, CodecHipEngine.flac, with the samples taken as they are: lossless).
+        ValueError before any device work: not a WAV, not 16-bit PCM, more than two channels, no sample, an unsupported
+        rate, a bad blocksize."""
+        from .wavfile import parse_wav
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        info = parse_wav(wav_bytes)
+        if info.fmt != "s16":
+            raise ValueError(f"to_flac: a 16-bit PCM WAV is needed, this one is {info.fmt}: the stage writes 16-bit samples, "
+                             "and anything else would not come back bit for bit")
+        if info.channels > 2:
+            raise ValueError(f"to_flac: a mono or stereo WAV is needed, this one has {info.channels} channels")
+        rate = _output_fx(info.rate, None, None).wav_rate       # (ValueError for a rate the output stages do not take)
+        pcm = np.frombuffer(wav_bytes, dtype="<i2", count=info.n_frames * info.channels, offset=info.data_offset)
+        pcm = pcm.astype(np.int16).reshape(-1) if info.channels == 1 else pcm.astype(np.int16).reshape(-1, 2)
+        return self._flac_bytes(pcm, rate, blocksize, lock=True)
 
     # ------------------------------------------------------------------ scripts (extension)
     def _script_plan(self, lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars, min_chars,
@@ -788,7 +822,8 @@ class FishTTS:
                           silence_db: Optional[float] = -45.0, max_chars: int = 200, min_chars: int = 24,
                           sample_rate: Optional[int] = None, speed: Optional[float] = None, pitch: Optional[float] = None,
                           loudness: Optional[float] = None, marks: Optional[list] = None, bed=None, stereo: bool = False,
-                          pans: Optional[dict] = None, room=None, sends: Optional[dict] = None) -> bytes:
+                          pans: Optional[dict] = None, room=None, sends: Optional[dict] = None,
+                          format: str = "wav") -> bytes:
         """Extension: a script - a dialogue, a narrated piece with quoted speakers - as one WAV.  `lines`: a list of
         script.Line (text, voice, speed, pitch, loudness, volume, pause), or an SSML string (script.parse_ssml: speak, p, s,
         voice, break, prosody); `voices`: name -> list of VoiceProfile.  Every line is split as synthesize_long splits a text
@@ -811,9 +846,11 @@ class FishTTS:
         the room adds only its tail.  ValueError before any device work: `sends` without `room`, a bad send or key,
         a pan or `pans` without stereo, a pan outside [-1, 1], a `pans` key that
         is no voice of the call, no line, an unknown voice, a bad value in a line or in the call, a bad
-        line_pause, more distinct voices than the reference cache holds (8; not with cache_reference_kv=False)."""
+        line_pause, more distinct voices than the reference cache holds (8; not with cache_reference_kv=False), a `format`
+        other than "wav" or "flac" (as synthesize_long: with stereo= the FLAC file has two channels)."""
         from . import segments
         from .script import line_marks
+        _check_format(format)
         plan = self._script_plan(lines, voices, references, pause, paragraph_pause, line_pause, silence_db, max_chars,
                                  min_chars, sample_rate, speed, pitch, loudness, marks, stereo, pans, room is not None, sends)
         mixed = self._bed_args(bed, plan.rate, silence_db)
@@ -824,7 +861,7 @@ class FishTTS:
             found = [None] * plan.n_lines
             line_marks(plan.line_of, plan.gaps, cuts, found, at=0 if mixed is None else mixed[1].lead)
             marks.extend(found)
-        return self._to_wav_bytes(audio, plan.rate)
+        return self._to_file_bytes(audio, plan.rate, format)
 
     def synthesize_script_stream(self, lines, voices=None, references: Optional[List[VoiceProfile]] = None,
                                  temperature: float = 0.7, top_p: float = 0.8, repetition_penalty: float = 1.1,
@@ -834,7 +871,7 @@ class FishTTS:
                                  pitch: Optional[float] = None, loudness: Optional[float] = None,
                                  marks: Optional[list] = None, bed=None, live_bed=None, live_stereo: bool = False,
                                  live_pans: Optional[dict] = None, room=None, sends: Optional[dict] = None, live_room=None,
-                                 live_sends: Optional[dict] = None) -> Iterator[bytes]:
+                                 live_sends: Optional[dict] = None, format: Optional[str] = None) -> Iterator[bytes]:
         """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
         (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
@@ -854,6 +891,7 @@ class FishTTS:
         the tail stays at the pan of the last line heard.  ValueError: `live_sends` without `live_room`."""
         from . import segments
         from .script import line_marks
+        _no_streamed_format(format, "synthesize_script_stream")
         _no_streamed_bed(bed, "synthesize_script_stream", live_bed)
         _no_streamed_room(room, "synthesize_script_stream", sends)
         if not isinstance(live_stereo, bool):
@@ -924,9 +962,12 @@ class FishTTS:
         `max_frames`, or the cut at `max_tokens`, starts a fresh ride state: the level is not carried over that one
         boundary.  seamless=False chunks are independent waveforms - levelling each on its own would jump - so that
         combination raises ValueError (at the first next(), before any work).  The one-shot and long-form calls do not
-        take it: they have `loudness=`."""
+        take it: they have `loudness=`.
+
+        `format=` raises ValueError (at the first next(), before any work): see _no_streamed_format."""
         from .generation import generate_long
         from .serve import ServerClosed
+        _no_streamed_format(kwargs.pop("format", None), "synthesize_stream")
         fx = _output_fx(kwargs.pop("sample_rate", None), kwargs.pop("speed", None), kwargs.pop("pitch", None),
                         kwargs.pop("loudness", None), kwargs.pop("live_loudness", None)).no_level("synthesize_stream")
         if fx.live is not None and not kwargs.get("seamless", False):
@@ -1122,8 +1163,22 @@ class FishTTS:
                                seed)
 
     # ------------------------------------------------------------------ codes -> audio (synthesizer.py:586-648)
-    def _decode_to_wav(self, codes: np.ndarray, fx=None) -> bytes:
-        return self._to_wav_bytes(self._decode_codes(codes, fx), self.sample_rate if fx is None else fx.wav_rate)
+    def _decode_to_wav(self, codes: np.ndarray, fx=None, format: str = "wav") -> bytes:
+        """The file of a call that decodes codes (the BatchServer's decode_wav too: its worker holds the codec lock)."""
+        audio, rate = self._decode_codes(codes, fx), self.sample_rate if fx is None else fx.wav_rate
+        return self._to_wav_bytes(audio, rate) if format == "wav" else self._flac_bytes(audio, rate)
+
+    def _to_file_bytes(self, audio: np.ndarray, sample_rate: int, format: str) -> bytes:
+        """A finished waveform as the file `format` names: _to_wav_bytes, or the FLAC stage on the same float32 samples."""
+        return self._to_wav_bytes(audio, sample_rate) if format == "wav" else self._flac_bytes(audio, sample_rate, lock=True)
+
+    def _flac_bytes(self, audio: np.ndarray, sample_rate: int, blocksize: int = 4096, lock: bool = False) -> bytes:
+        """CodecHipEngine.flac's bytes; `lock`: under an open BatchServer's codec lock (its worker shares the codec context)."""
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        srv = getattr(self, "_server", None) if lock else None
+        with (srv.codec_lock if srv is not None else contextlib.nullcontext()):
+            return self._vocoder.flac(audio, sample_rate, blocksize)[0]
 
     def _decode_to_pcm(self, codes: np.ndarray, fx=None) -> bytes:
         return (self._decode_codes(codes, fx) * 32767).astype(np.int16).tobytes()  # no clip on the PCM path (synthesizer.py:594)
@@ -1167,6 +1222,26 @@ def _check_sampling(temperature: float, top_p: float, repetition_penalty: float)
     assert 0 < top_p <= 1, "top_p must be in (0, 1]"
     assert 0 < repetition_penalty < 2, "repetition_penalty must be in (0, 2)"
     assert 0 < temperature < 2, "temperature must be in (0, 2)"
+
+
+def _check_format(format) -> None:
+    """batch_stream.checked_format: the one check of `format=` (imported when first needed, as the engines are)."""
+    from .batch_stream import checked_format
+    checked_format(format)
+
+
+def _format_kw(format: str) -> dict:
+    """`format` as the keyword of a call that takes it defaulted: nothing for "wav" - a decoder handed in by a caller, which
+    may know of no format, is then called as it always was (as OutputFx.kw)."""
+    return {} if format == "wav" else {"format": format}
+
+
+def _no_streamed_format(format, what: str) -> None:
+    """A stream takes no `format=`: it hands out raw int16 PCM chunks, and a FLAC stream would need the encoder's state - the
+    samples of an unfinished frame - carried from push to push, which the FLAC stage (whole-call) does not do."""
+    if format is not None:
+        raise ValueError(f"format needs the whole piece: {what} hands out int16 PCM chunks before the piece's end, and the FLAC "
+                         "stage packs a finished waveform; synthesize the piece with format=, or to_flac() a finished WAV")
 
 
 def _no_streamed_room(room, what: str, sends=None) -> None:

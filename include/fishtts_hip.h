@@ -923,6 +923,59 @@ ft_status ft_codec_mix_stream_begin_stereo(ft_ctx* ctx, int32_t sample_rate, con
 ft_status ft_codec_mix_stream_push_stereo(ft_mix_stream* ms, const float* x, int64_t n, const ft_pan_region* regions, int32_t R,
                                           int32_t final, float* y, int64_t capacity, int64_t* n_out);
 
+/* ---- FLAC: a finished waveform packed losslessly on the device (csrc/flac_kernels.h; host arithmetic csrc/flac_plan.h).
+ * The stage, stated to the bit:
+ *   Inputs: x on the host, n >= 1 frames of `channels` (1 or 2) interleaved samples; fmt 0 is float32, 1 is int16 taken as it
+ *   is; sample_rate any rate ft_resample_filter accepts; ft_flac_params {blocksize B in {256, 512, 1024, 2048, 4096}, reserved 0}.
+ *   Quantisation (fmt 0): p = (int) trunc(min(1, max(-1, x)) 32767.0f), one float32 product; a NaN gives 0.  16 bits per sample.
+ *   Stream: `fLaC`, then one STREAMINFO block with the last-block flag set (header 80 00 00 22): min blocksize = max blocksize =
+ *   B (16 bits each), the real minimum and maximum frame size (24 bits each), the rate (20 bits), channels - 1 (3), 15 (5),
+ *   n (36 bits), the MD5 field all zero ("not computed": the PCM never reaches the host).  Then F = ceil(n / B) frames of B
+ *   samples, the last of n - (F - 1) B.
+ *   Frame header: FF F8 (sync, fixed blocksize); the blocksize code 1000..1100 for 256..4096 when the frame has B samples, for a
+ *   short last frame of bs samples 0110 with bs - 1 in 8 bits when bs <= 256, else 0111 with bs - 1 in 16 bits; the rate code
+ *   0100 8000, 0101 16000, 0110 22050, 0111 24000, 1000 32000, 1001 44100, 1010 48000, any other rate 1101 with the rate in Hz
+ *   in 16 bits; the channel assignment (4 bits); the sample-size code 100 and a 0 bit; the frame number in the format's
+ *   UTF-8-style coding; the blocksize extra, then the rate extra; CRC-8 (poly 0x07, init 0) over the header so far.
+ *   Channel assignment: mono 0000.  Stereo: M = (L + R) >> 1 (arithmetic shift), S = L - R (17 bits); the least total of
+ *   subframe bits wins among 0001 (L, R), 1000 (L, S), 1001 (S, R) and 1010 (M, S), ties in that order.
+ *   Subframe of a channel of width w (16; 17 for S), one header byte with the wasted-bits flag 0.  Candidates and their bits:
+ *   CONSTANT (000000), only when all samples are equal: 8 + w.  FIXED o (001ooo) for o = 0..4 with o < bs: 8 + w o + 6 + the
+ *   residual's cost.  VERBATIM (000001): 8 + w bs.  The least wins; ties go CONSTANT, FIXED by ascending o, VERBATIM.
+ *   Residual: the format's fixed predictors, e_0 = s, e_o[i] = e_(o-1)[i] - e_(o-1)[i-1]; u = 2 e for e >= 0, else -2 e - 1.
+ *   Coding method 00 (4-bit parameters), the escape never used.  A partition order P is allowed when P <= 8, 2^P divides bs and
+ *   (bs >> P) > o; the first partition holds (bs >> P) - o residuals.  A partition of m residuals with parameter k in 0..14
+ *   costs 4 + sum(u >> k) + m (k + 1); the least k-cost per partition wins, ties to the smaller k; the least total over P wins,
+ *   ties to the smaller P.  The search is exhaustive: sum(u >> k) is additive over partitions, so the 15 sums are taken at the
+ *   finest partitions (2^min(8, trailing zeros of bs)) and merged pairwise upward.  A residual is u >> k zero bits, a one, the
+ *   k low bits of u.
+ *   Frame end: zero bits to the byte, then CRC-16 (poly 0x8005, init 0, big-endian) over the whole frame.
+ *   Determinism: integer arithmetic behind the one float32 product, integer atomics only: a repeated call gives the same bytes.
+ *   Reported (ft_flac_info): frames F, bytes (= *total), the smallest and the largest frame, a count per subframe kind
+ *   (CONSTANT, VERBATIM, FIXED 0..4), a count per channel assignment (0000, 0001, 1000, 1001, 1010).
+ * Limits and refusals: every argument is checked before any device work, and a refused call changes nothing.  In this order:
+ * a null pointer; fmt; channels; sample_rate; blocksize; reserved; n < 1 (FT_ERR_ARG each); n beyond 2^28 (FT_ERR_TOO_LONG);
+ * capacity < ft_flac_bound (FT_ERR_ARG).  The bound is the all-VERBATIM stream with the longest frame header, which the encoder
+ * cannot exceed because VERBATIM is always a candidate.
+ * Four launches whatever n: flac_analyse_kernel (one workgroup per frame and signal - L, R, M, S in stereo: the cost search),
+ * flac_pack_kernel (one workgroup per frame: assignment, header, a scan over the code lengths, the codes ORed into a zeroed
+ * LDS image, both CRCs, the frame to a worst-case-stride slot), flac_scan_kernel (one workgroup: the frames' places, the
+ * smallest and largest, the 42 leading bytes), flac_gather_kernel (the slots to the compact stream).  The host reads the
+ * counters, then the `total` bytes and nothing else. */
+typedef struct ft_flac_params {
+    int32_t blocksize, reserved;
+} ft_flac_params;
+typedef struct ft_flac_info {
+    int64_t frames, bytes;
+    int32_t min_frame, max_frame;
+    int32_t kinds[7];
+    int32_t assignments[5];
+} ft_flac_info;
+ft_status ft_codec_flac(ft_ctx* ctx, const void* x, int32_t fmt, int64_t n, int32_t channels, int32_t sample_rate,
+                        const ft_flac_params* fp, uint8_t* out, int64_t capacity, int64_t* total, ft_flac_info* info);
+/* Host only: 42 + F (17 + channels) + 2 channels n bytes, F = ceil(n / blocksize); -1 for arguments ft_codec_flac refuses. */
+int64_t ft_flac_bound(int64_t n, int32_t channels, int32_t blocksize);
+
 ft_status ft_sync(ft_ctx* ctx);
 /* State of the persistent frame engine (csrc/frame_engine.h), the batch-1 form of the decode step
  * (fish_tts/models/inference.py:83-155 as two launches of one workgroup per CU instead of ~325 launches).
