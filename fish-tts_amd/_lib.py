@@ -217,6 +217,13 @@ SYMBOLS = {
     "ft_codec_flac": (C.c_int32, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ft_flac_params), _P, C.c_int64,
                                   C.POINTER(C.c_int64), C.POINTER(ft_flac_info)]),
     "ft_flac_bound": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "ft_codec_flac_stream_begin": (C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(ft_flac_params), C.POINTER(_P)]),
+    "ft_codec_flac_stream_push": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "ft_codec_flac_stream_head": (C.c_int32, [_P, _P]),
+    "ft_codec_flac_stream_info": (C.c_int32, [_P, C.POINTER(ft_flac_info)]),
+    "ft_codec_flac_stream_end": (None, [_P]),
+    "ft_flac_stream_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]),
     "ft_codec_mix_stream_begin_bare": (C.c_int32, [_P, C.c_int32, C.POINTER(ft_mix_params), C.POINTER(_P)]),
     "ft_mix_live_plan": (C.c_int32, [C.c_int32, C.POINTER(ft_mix_params), C.c_int64, C.c_int32, _P, _P]),
     "ft_codec_mix_live": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.POINTER(ft_intake_item), C.POINTER(ft_mix_params), _P,

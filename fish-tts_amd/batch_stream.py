@@ -92,6 +92,17 @@ def checked_format(format) -> str:
     return format
 
 
+def checked_live_format(live_format):
+    """`live_format=` of a streaming call, checked before any work: None without one, else the flacfile.LiveFlac - the value
+    itself, or LiveFlac() for the shorthand "flac".  Anything else raises ValueError."""
+    from .flacfile import LiveFlac
+    if live_format is None or isinstance(live_format, LiveFlac):
+        return live_format
+    if isinstance(live_format, str) and live_format == "flac":
+        return LiveFlac()
+    raise ValueError(f"live_format must be None, 'flac' or a flacfile.LiveFlac, got {live_format!r}")
+
+
 def stream_utterances(run: Callable, n: int, codec, chunk_tokens: int = 20,
                       min_first_chunk: int = 10, sample_rate: Optional[int] = None,
                       speed: Optional[float] = None, pitch: Optional[float] = None, fx=None,

@@ -192,6 +192,84 @@ class RoomStream:
         self.close()
 
 
+def _flac_samples(what: str, audio, dtype=None, channels: Optional[int] = None, empty: bool = False) -> np.ndarray:
+    """`audio` as the FLAC stage takes it: float32 or int16, (N,) mono or (N, 2), contiguous - flac()'s checks; with `dtype` /
+    `channels` a stream's too (the dtype and channel count it was made for); `empty`: no sample is fine (a stream's push)."""
+    x = np.asarray(audio)
+    if x.dtype != np.int16:
+        if x.dtype.kind not in "fiu":
+            raise ValueError(f"{what}: audio must be float32 or int16, got {x.dtype}")
+        if x.dtype.kind in "iu":
+            raise ValueError(f"{what}: integer audio must be int16, got {x.dtype}")
+        x = x.astype(np.float32)
+    if dtype is not None and x.dtype != dtype:
+        raise ValueError(f"{what}: the stream takes {np.dtype(dtype).name}, got {x.dtype}")
+    if x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[1] != 2):
+        raise ValueError(f"{what}: a waveform is (N,) or (N, 2), got {x.shape}")
+    if channels is not None and x.ndim != channels:
+        raise ValueError(f"{what}: the stream has {channels} channel(s), got {x.shape}")
+    if x.shape[0] < 1 and not empty:
+        raise ValueError(f"{what}: an empty waveform")
+    return np.ascontiguousarray(x)
+
+
+class FlacStream:
+    """An open stream of the live FLAC stage (ft_codec_flac_stream_*; CodecHipEngine.flac_stream makes one): push(x) takes the
+    next samples - the dtype and channels the stream was made for, checked as flac() checks them - and returns the bytes of
+    the frames they complete (b"" where they complete none); push(x, final=True) ends the stream and flushes the short last
+    frame.  head(): the 42 leading bytes from what is known - before the final push with the sizes and the sample count
+    "unknown" (zero), after it the ones flac() would have written.  head() + the pushes' bytes is one FLAC stream, and the
+    pushes' bytes are flac(whole)[42:] byte for byte, however they are cut.  report(): a FlacReport of the stream so far.
+    close() frees the stream's device state (a closed stream refuses pushes)."""
+
+    def __init__(self, engine, handle, dtype, channels: int, blocksize: int):
+        self._eng, self._h, self._dtype, self._channels, self._B = engine, handle, np.dtype(dtype), channels, blocksize
+        self._nin = 0
+
+    def push(self, x=None, final: bool = False) -> bytes:
+        if self._h is None:
+            raise RuntimeError("flac stream: closed")
+        x = np.zeros(0, dtype=self._dtype) if x is None else x
+        x = _flac_samples("flac stream push", x, self._dtype, None if np.asarray(x).size == 0 else self._channels, empty=True)
+        n = x.shape[0] if x.size else 0
+        eng = self._eng
+        cap = C.c_int64(0)
+        eng._check(eng.lib.ft_flac_stream_plan(self._B, self._channels, self._nin, n, 1 if final else 0, None, C.byref(cap)),
+                   "ft_flac_stream_plan")
+        out = np.empty(max(cap.value, 1), dtype=np.uint8)
+        got = C.c_int64(0)
+        eng._check(eng.lib.ft_codec_flac_stream_push(self._h, x.ctypes.data_as(C.c_void_p) if n else None, n, 1 if final else 0,
+                                                     out.ctypes.data_as(C.c_void_p), cap.value, C.byref(got)),
+                   "ft_codec_flac_stream_push")
+        self._nin += n
+        return out[:got.value].tobytes()
+
+    def head(self) -> bytes:
+        if self._h is None:
+            raise RuntimeError("flac stream: closed")
+        out = (C.c_uint8 * 42)()
+        self._eng._check(self._eng.lib.ft_codec_flac_stream_head(self._h, out), "ft_codec_flac_stream_head")
+        return bytes(out)
+
+    def report(self) -> FlacReport:
+        if self._h is None:
+            raise RuntimeError("flac stream: closed")
+        info = L.ft_flac_info()
+        self._eng._check(self._eng.lib.ft_codec_flac_stream_info(self._h, C.byref(info)), "ft_codec_flac_stream_info")
+        return FlacReport.of(info)
+
+    def close(self) -> None:
+        if self._h is not None:
+            self._eng.lib.ft_codec_flac_stream_end(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 @dataclass(frozen=True)
 class MixLiveReport:
     """What the live mix stage did (ft_mix_live_info): `n`, `bed_len`, `hops`, `active`, `duck_max` and `bed` as MixReport's;
@@ -971,18 +1049,7 @@ class CodecHipEngine:
         rate = OutputFx.of(sample_rate=sample_rate).wav_rate
         if isinstance(blocksize, bool) or not isinstance(blocksize, (int, np.integer)) or int(blocksize) not in FLAC_BLOCKSIZES:
             raise ValueError(f"{what}: blocksize must be one of {FLAC_BLOCKSIZES}, got {blocksize!r}")
-        x = np.asarray(audio)
-        if x.dtype != np.int16:
-            if x.dtype.kind not in "fiu":
-                raise ValueError(f"{what}: audio must be float32 or int16, got {x.dtype}")
-            if x.dtype.kind in "iu":
-                raise ValueError(f"{what}: integer audio must be int16, got {x.dtype}")
-            x = x.astype(np.float32)
-        if x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[1] != 2):
-            raise ValueError(f"{what}: a waveform is (N,) or (N, 2), got {x.shape}")
-        if x.shape[0] < 1:
-            raise ValueError(f"{what}: an empty waveform")
-        x = np.ascontiguousarray(x)
+        x = _flac_samples(what, audio)
         n, channels = x.shape[0], x.ndim
         cap = int(self.lib.ft_flac_bound(n, channels, int(blocksize)))
         if cap < 0:
@@ -995,6 +1062,28 @@ class CodecHipEngine:
                                            C.byref(fp), out.ctypes.data_as(C.c_void_p), cap, C.byref(total), C.byref(info)),
                     "ft_codec_flac")
         return out[:total.value].tobytes(), FlacReport.of(info)
+
+    def flac_stream(self, sample_rate: Optional[int] = None, channels: int = 1, blocksize: int = 4096, dtype=np.float32) -> FlacStream:
+        """A stream of the live FLAC stage (ft_codec_flac_stream_begin) for `channels` (1 or 2) of `dtype` samples - float32,
+        quantised on the device by flac()'s rule, or int16, taken as they are.  The FlacStream's pushes concatenate to
+        flac(whole)[42:] byte for byte however they are cut, and its head() after the final push is flac(whole)[:42]."""
+        what = "flac_stream"
+        rate = OutputFx.of(sample_rate=sample_rate).wav_rate
+        if isinstance(blocksize, bool) or not isinstance(blocksize, (int, np.integer)) or int(blocksize) not in FLAC_BLOCKSIZES:
+            raise ValueError(f"{what}: blocksize must be one of {FLAC_BLOCKSIZES}, got {blocksize!r}")
+        if isinstance(channels, bool) or channels not in (1, 2):
+            raise ValueError(f"{what}: channels must be 1 or 2, got {channels!r}")
+        try:
+            dt = np.dtype(dtype)
+        except TypeError:
+            dt = None
+        if dt not in (np.dtype(np.float32), np.dtype(np.int16)):
+            raise ValueError(f"{what}: dtype must be float32 or int16, got {dtype!r}")
+        fp = L.ft_flac_params(int(blocksize), 0)
+        h = C.c_void_p()
+        self._check(self.lib.ft_codec_flac_stream_begin(self._h, int(channels), 1 if dt == np.int16 else 0, rate, C.byref(fp),
+                                                        C.byref(h)), "ft_codec_flac_stream_begin")
+        return FlacStream(self, h, dt, int(channels), int(blocksize))
 
     def _room_live_args(self, what: str, clip, sample_rate, params):
         """(rate, IR item array, what keeps its bytes alive, ft_room_params with ceiling 0, tail) of a live room call, checked

@@ -49,6 +49,7 @@ struct DecBlock { float* a0; ConvW ct; ResUnitW u[3]; int s, cin, cout; };
 struct ft_codec_stream;
 struct ft_mix_stream;
 struct ft_room_stream;
+struct ft_flac_stream;
 struct CodecState {
     hipStream_t stream = nullptr;
     std::mutex mu;
@@ -142,6 +143,11 @@ struct CodecState {
     long long* fl_off = nullptr;
     FlacOut* fl_out = nullptr;
     size_t fl_incap = 0, fl_slotcap = 0, fl_streamcap = 0, fl_sigcap = 0, fl_lencap = 0, fl_offcap = 0;
+    // live FLAC stage (ft_codec_flac_stream_*): the open streams, as mix_streams, and the int16 staging buffer of a push
+    // (carry || push, quantised); a push's raw samples lie in fl_in, its frames in the FLAC stage's buffers
+    std::vector<ft_flac_stream*> flac_streams;
+    short* fl_stage = nullptr;
+    size_t fl_stagecap = 0;
     // live mix stage (ft_codec_mix_stream_*): the open streams (their device state is freed with the context), and what a
     // push stages - its samples, the m of the hops it completes, the samples it emits; the buffers grow on need
     std::vector<ft_mix_stream*> mix_streams;
@@ -357,6 +363,7 @@ ft_status codec_create(ft_ctx* ctx) {
 static void stream_orphan(ft_codec_stream* sc);
 static void mix_stream_orphan(ft_mix_stream* ms);
 static void room_stream_orphan(ft_room_stream* rs);
+static void flac_stream_orphan(ft_flac_stream* fs);
 void codec_destroy(ft_ctx* ctx) {
     CodecState* s = ctx->codec;
     if (!s) return;
@@ -369,6 +376,8 @@ void codec_destroy(ft_ctx* ctx) {
     s->mix_streams.clear();
     for (ft_room_stream* rs : s->room_streams) room_stream_orphan(rs);
     s->room_streams.clear();
+    for (ft_flac_stream* fs : s->flac_streams) flac_stream_orphan(fs);
+    s->flac_streams.clear();
     for (void* p : s->owned) hipFree(p);
     delete s;
     ctx->codec = nullptr;
@@ -3136,6 +3145,41 @@ static_assert(sizeof(FlSig) == 8 + FL_FINE && FL_THREADS == FL_FINE, "a thread p
 
 extern "C" int64_t ft_flac_bound(int64_t n, int32_t channels, int32_t blocksize) { return flac::fl_bound(n, channels, blocksize); }
 
+// The four frame launches over n frames of samples that lie on the device (s->mu held): the buffers grown for F frames and
+// `bound` stream bytes (the 42 counted), the counters zeroed, the frames numbered from f0, FlacOut read back and judged.
+static ft_status flac_frames(ft_ctx* ctx, const std::string& fn, const void* dx, int fmt, long long n, int channels, int B, int rate,
+                             long long f0, long long bound, FlacOut* o) {
+    CodecState* s = ctx->codec;
+    hipStream_t st = s->stream;
+    const long long F = flac::fl_frames(n, B);
+    const int nsig = channels == 2 ? 4 : 1;
+    const size_t stride = (size_t)((flac::fl_frame_bound(B, channels) + 3) / 4 * 4);
+    FT_TRY(cgrow(ctx, &s->fl_sig, &s->fl_sigcap, (size_t)F * nsig));
+    FT_TRY(cgrow(ctx, &s->fl_slots, &s->fl_slotcap, (size_t)F * stride + 8));
+    FT_TRY(cgrow(ctx, &s->fl_len, &s->fl_lencap, (size_t)F));
+    FT_TRY(cgrow(ctx, &s->fl_off, &s->fl_offcap, (size_t)F));
+    FT_TRY(cgrow(ctx, &s->fl_stream, &s->fl_streamcap, (size_t)bound + 8));
+    if (!s->fl_out) FT_TRY(cmalloc(ctx, &s->fl_out, (size_t)1));
+    FT_HIP(ctx, hipMemsetAsync(s->fl_out, 0, sizeof(FlacOut), st));
+    FlacP p;
+    memset(&p, 0, sizeof p);
+    p.x = dx; p.n = n; p.fmt = fmt; p.channels = channels; p.B = B; p.rate = rate; p.F = (int)F; p.nsig = nsig;
+    p.sig = s->fl_sig; p.slots = s->fl_slots; p.stride = (int)stride; p.flen = s->fl_len; p.foff = s->fl_off;
+    p.stream = s->fl_stream; p.out = s->fl_out; p.f0 = f0;
+    flac_analyse_kernel<<<dim3((unsigned)F, (unsigned)nsig), FL_THREADS, 0, st>>>(p);
+    flac_pack_kernel<<<(unsigned)F, FL_THREADS, 0, st>>>(p);
+    flac_scan_kernel<<<1, FL_SCAN_THREADS, 0, st>>>(p);
+    flac_gather_kernel<<<(unsigned)F, FL_THREADS, 0, st>>>(p);
+    FT_HIP(ctx, hipMemcpyAsync(o, s->fl_out, sizeof *o, hipMemcpyDeviceToHost, st));
+    FT_HIP(ctx, hipStreamSynchronize(st));              // the stream's length decides how much comes back
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
+    if (o->overflow != 0) return ft_fail(ctx, FT_ERR_STATE, fn + ": a frame did not fit its bound");
+    if (o->total < flac::FL_STREAM_HEAD || o->total > bound || o->frames != (int)F)
+        return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream's length is not within the bound");
+    return FT_OK;
+}
+
 extern "C" ft_status ft_codec_flac(ft_ctx* ctx, const void* x, int32_t fmt, int64_t n, int32_t channels, int32_t sample_rate,
                                    const ft_flac_params* fp, uint8_t* out, int64_t capacity, int64_t* total, ft_flac_info* info) {
     if (!ctx) return FT_ERR_ARG;
@@ -3152,36 +3196,11 @@ extern "C" ft_status ft_codec_flac(ft_ctx* ctx, const void* x, int32_t fmt, int6
     FT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = s->stream;
     const int B = fp->blocksize;
-    const long long F = flac::fl_frames(n, B);
-    const int nsig = channels == 2 ? 4 : 1;
     const size_t in_bytes = (size_t)n * channels * (fmt ? 2 : 4);
-    const size_t stride = (size_t)((flac::fl_frame_bound(B, channels) + 3) / 4 * 4);
     FT_TRY(cgrow(ctx, &s->fl_in, &s->fl_incap, in_bytes));
-    FT_TRY(cgrow(ctx, &s->fl_sig, &s->fl_sigcap, (size_t)F * nsig));
-    FT_TRY(cgrow(ctx, &s->fl_slots, &s->fl_slotcap, (size_t)F * stride + 8));
-    FT_TRY(cgrow(ctx, &s->fl_len, &s->fl_lencap, (size_t)F));
-    FT_TRY(cgrow(ctx, &s->fl_off, &s->fl_offcap, (size_t)F));
-    FT_TRY(cgrow(ctx, &s->fl_stream, &s->fl_streamcap, (size_t)flac::fl_bound(n, channels, B) + 8));
-    if (!s->fl_out) FT_TRY(cmalloc(ctx, &s->fl_out, (size_t)1));
     FT_HIP(ctx, hipMemcpyAsync(s->fl_in, x, in_bytes, hipMemcpyHostToDevice, st));
-    FT_HIP(ctx, hipMemsetAsync(s->fl_out, 0, sizeof(FlacOut), st));
-    FlacP p;
-    memset(&p, 0, sizeof p);
-    p.x = s->fl_in; p.n = n; p.fmt = fmt; p.channels = channels; p.B = B; p.rate = sample_rate; p.F = (int)F; p.nsig = nsig;
-    p.sig = s->fl_sig; p.slots = s->fl_slots; p.stride = (int)stride; p.flen = s->fl_len; p.foff = s->fl_off;
-    p.stream = s->fl_stream; p.out = s->fl_out;
-    flac_analyse_kernel<<<dim3((unsigned)F, (unsigned)nsig), FL_THREADS, 0, st>>>(p);
-    flac_pack_kernel<<<(unsigned)F, FL_THREADS, 0, st>>>(p);
-    flac_scan_kernel<<<1, FL_SCAN_THREADS, 0, st>>>(p);
-    flac_gather_kernel<<<(unsigned)F, FL_THREADS, 0, st>>>(p);
     FlacOut o;
-    FT_HIP(ctx, hipMemcpyAsync(&o, s->fl_out, sizeof o, hipMemcpyDeviceToHost, st));
-    FT_HIP(ctx, hipStreamSynchronize(st));              // the stream's length decides how much comes back
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
-    if (o.overflow != 0) return ft_fail(ctx, FT_ERR_STATE, fn + ": a frame did not fit its bound");
-    if (o.total < flac::FL_STREAM_HEAD || o.total > capacity || o.frames != (int)F)
-        return ft_fail(ctx, FT_ERR_STATE, fn + ": the stream's length is not within the bound");
+    FT_TRY(flac_frames(ctx, fn, s->fl_in, fmt, n, channels, B, sample_rate, 0, flac::fl_bound(n, channels, B), &o));
     FT_HIP(ctx, hipMemcpyAsync(out, s->fl_stream, (size_t)o.total, hipMemcpyDeviceToHost, st));
     FT_HIP(ctx, hipStreamSynchronize(st));
     *total = o.total;
@@ -3190,6 +3209,150 @@ extern "C" ft_status ft_codec_flac(ft_ctx* ctx, const void* x, int32_t fmt, int6
     for (int i = 0; i < flac::FL_KINDS; ++i) info->kinds[i] = o.kinds[i];
     for (int i = 0; i < flac::FL_ASSIGNMENTS; ++i) info->assignments[i] = o.assignments[i];
     return FT_OK;
+}
+
+// ---- live FLAC stage (fishtts_hip.h: "Live FLAC"; flacl_stage_kernel in flac_kernels.h; the emission rule, the host state and
+// the per-push checks in flac_plan.h).  A stream owns two copies of its carry, allocated at `begin`; a push stages its raw
+// samples in fl_in and carry || push in fl_stage, runs the FLAC stage's launches on that and ends with a wait, so nothing of a
+// push outlives it, and the host state moves only when the launches went through.
+struct ft_flac_stream {
+    ft_ctx* owner = nullptr;          // null once its context is gone (the device state went with it)
+    flac::FlStream st;
+    short* carry[2] = {nullptr, nullptr};
+};
+
+static void flac_stream_orphan(ft_flac_stream* fs) {
+    for (int c = 0; c < 2; ++c) {
+        if (fs->carry[c]) hipFree(fs->carry[c]);
+        fs->carry[c] = nullptr;
+    }
+    fs->owner = nullptr;
+}
+
+static void fls_end(ft_ctx* ctx, ft_flac_stream* fs) {   // (s->mu held)
+    CodecState* s = ctx->codec;
+    hipStreamSynchronize(s->stream);
+    flac_stream_orphan(fs);
+    for (size_t i = 0; i < s->flac_streams.size(); ++i)
+        if (s->flac_streams[i] == fs) { s->flac_streams.erase(s->flac_streams.begin() + (long)i); break; }
+    delete fs;
+}
+
+extern "C" ft_status ft_flac_stream_plan(int32_t blocksize, int32_t channels, int64_t before, int64_t n, int32_t final,
+                                         int64_t* frames, int64_t* bytes) {
+    const int why = flac::fl_push_refused(blocksize, channels, before, n);
+    if (why) return why == 2 ? FT_ERR_TOO_LONG : FT_ERR_ARG;
+    const flac::FlPush pl = flac::fl_push_plan(blocksize, channels, before, n, final != 0);
+    if (frames) *frames = pl.F;
+    if (bytes) *bytes = pl.bytes;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_flac_stream_begin(ft_ctx* ctx, int32_t channels, int32_t fmt, int32_t sample_rate,
+                                                const ft_flac_params* fp, ft_flac_stream** out) {
+    const std::string fn = "ft_codec_flac_stream_begin";
+    if (!ctx) return FT_ERR_ARG;
+    FT_TRY(codec_ready(ctx));
+    if (!fp || !out) return ft_fail(ctx, FT_ERR_ARG, fn + ": a null pointer");
+    if (const char* why = flac::fl_stream_begin_check(fmt, channels, sample_rate, fp->blocksize, fp->reserved))
+        return ft_fail(ctx, FT_ERR_ARG, fn + ": " + why);
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    ft_flac_stream* fs = new ft_flac_stream();
+    fs->owner = ctx;
+    fs->st.fmt = fmt; fs->st.channels = channels; fs->st.rate = sample_rate; fs->st.B = fp->blocksize;
+    s->flac_streams.push_back(fs);
+    for (int c = 0; c < 2; ++c) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, (size_t)fp->blocksize * channels * sizeof(short) + 64);
+        if (e != hipSuccess) {
+            fls_end(ctx, fs);
+            return ft_fail(ctx, FT_ERR_NOMEM, fn + " hipMalloc: " + hipGetErrorString(e));
+        }
+        fs->carry[c] = (short*)q;
+    }
+    *out = fs;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_flac_stream_push(ft_flac_stream* fs, const void* x, int64_t n, int32_t final, uint8_t* out,
+                                               int64_t capacity, int64_t* n_bytes) {
+    const std::string fn = "ft_codec_flac_stream_push";
+    if (!fs) return FT_ERR_ARG;
+    ft_ctx* ctx = fs->owner;
+    if (!ctx || !ctx->codec) return FT_ERR_STATE;      // its context was destroyed
+    CodecState* s = ctx->codec;
+    std::lock_guard<std::mutex> lock(s->mu);
+    flac::FlStream& stg = fs->st;
+    bool state = false, too_long = false;
+    if (const char* why = flac::fl_stream_check(&stg, !out || !n_bytes, !x, n, final != 0, capacity, &state, &too_long))
+        return ft_fail(ctx, state ? FT_ERR_STATE : too_long ? FT_ERR_TOO_LONG : FT_ERR_ARG, fn + ": " + why);
+    FT_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = s->stream;
+    const flac::FlPush pl = stg.plan(n, final != 0);
+    const int ch = stg.channels;
+    if (pl.T > 0) {
+        const size_t in_bytes = (size_t)n * ch * (stg.fmt ? 2 : 4);
+        FT_TRY(cgrow(ctx, &s->fl_in, &s->fl_incap, std::max(in_bytes, (size_t)8)));
+        FT_TRY(cgrow(ctx, &s->fl_stage, &s->fl_stagecap, (size_t)pl.T * ch + 4));
+        if (n > 0) FT_HIP(ctx, hipMemcpyAsync(s->fl_in, x, in_bytes, hipMemcpyHostToDevice, st));
+        FlacStageP q;
+        memset(&q, 0, sizeof q);
+        q.carry_in = fs->carry[stg.par]; q.carry_out = fs->carry[stg.par ^ 1]; q.stage = s->fl_stage;
+        q.push.x = s->fl_in; q.push.fmt = stg.fmt; q.push.channels = ch;
+        q.r = pl.r; q.T = pl.T; q.taken = pl.taken;
+        const long long groups = (pl.T * ch + 3) / 4;
+        flacl_stage_kernel<<<(unsigned)std::max(1LL, std::min(4096LL, (groups + FL_THREADS - 1) / FL_THREADS)), FL_THREADS, 0, st>>>(q);
+    }
+    FlacOut o;
+    memset(&o, 0, sizeof o);
+    long long got = 0;
+    if (pl.F > 0) {
+        FT_TRY(flac_frames(ctx, fn, s->fl_stage, 1, pl.taken, ch, stg.B, stg.rate, stg.F_done, flac::FL_STREAM_HEAD + pl.bytes, &o));
+        got = o.total - flac::FL_STREAM_HEAD;
+        if (got > 0) FT_HIP(ctx, hipMemcpyAsync(out, s->fl_stream + flac::FL_STREAM_HEAD, (size_t)got, hipMemcpyDeviceToHost, st));
+    }
+    FT_HIP(ctx, hipStreamSynchronize(st));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ft_fail(ctx, FT_ERR_HIP, fn + " launch: " + hipGetErrorString(e));
+    stg.commit(pl, n, final != 0, got, o.fmin, o.fmax, o.kinds, o.assignments);
+    *n_bytes = got;
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_flac_stream_head(ft_flac_stream* fs, uint8_t out[42]) {
+    if (!fs || !out) return FT_ERR_ARG;
+    ft_ctx* ctx = fs->owner;
+    std::unique_lock<std::mutex> lock;
+    if (ctx && ctx->codec) lock = std::unique_lock<std::mutex>(ctx->codec->mu);
+    fs->st.head(out);
+    return FT_OK;
+}
+
+extern "C" ft_status ft_codec_flac_stream_info(ft_flac_stream* fs, ft_flac_info* info) {
+    if (!fs || !info) return FT_ERR_ARG;
+    ft_ctx* ctx = fs->owner;
+    std::unique_lock<std::mutex> lock;
+    if (ctx && ctx->codec) lock = std::unique_lock<std::mutex>(ctx->codec->mu);
+    const flac::FlStream& stg = fs->st;
+    memset(info, 0, sizeof *info);
+    info->frames = stg.F_done; info->bytes = flac::FL_STREAM_HEAD + stg.bytes; info->min_frame = stg.fmin; info->max_frame = stg.fmax;
+    for (int i = 0; i < flac::FL_KINDS; ++i) info->kinds[i] = stg.kinds[i];
+    for (int i = 0; i < flac::FL_ASSIGNMENTS; ++i) info->assignments[i] = stg.assignments[i];
+    return FT_OK;
+}
+
+extern "C" void ft_codec_flac_stream_end(ft_flac_stream* fs) {
+    if (!fs) return;
+    ft_ctx* own = fs->owner;
+    if (own && own->codec) {
+        std::lock_guard<std::mutex> lock(own->codec->mu);
+        hipSetDevice(own->device);
+        fls_end(own, fs);
+        return;
+    }
+    delete fs;
 }
 
 extern "C" ft_status ft_test_room_conv(ft_ctx* ctx, const float* xs, int64_t n, const float* hn, int64_t L, int64_t predelay,

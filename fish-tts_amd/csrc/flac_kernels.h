@@ -5,6 +5,8 @@
 //   flac_pack_kernel     one workgroup per frame: channel assignment, header, subframes, CRCs -> a worst-case-stride slot
 //   flac_scan_kernel     one workgroup: exclusive scan over the frame lengths, min / max, the 42 stream-head bytes
 //   flac_gather_kernel   one workgroup per frame: the slot to its place in the compact stream
+// and the live FLAC stage's ("Live FLAC"), in front of those four on a stream's push:
+//   flacl_stage_kernel   carry || push, quantised, to the int16 staging buffer; what no frame takes to the other carry copy
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +48,7 @@ struct FlacP {
     long long* foff;                 // [F]
     unsigned char* stream;           // at least ft_flac_bound bytes
     FlacOut* out;
+    long long f0;                    // the number of frame 0 (a stream's push: the frames emitted before it)
 };
 
 // p = (int) trunc(min(1, max(-1, x)) 32767.0f), one float32 product; a NaN gives 0.  int16 as it is.
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(FL_THREADS) void flac_pack_kernel(FlacP p) {
         crc = 0;
         over = 0;
         unsigned char h[flac::FL_HEADER_MAX];
-        hlen = flac::fl_frame_header(h, bs, p.B, p.rate, a, (uint32_t)f);
+        hlen = flac::fl_frame_header(h, bs, p.B, p.rate, a, (uint32_t)(p.f0 + f));
         for (int i = 0; i < hlen; ++i) hdr[i] = h[i];
     }
     __syncthreads();
@@ -367,6 +370,40 @@ __global__ __launch_bounds__(FL_THREADS) void flac_gather_kernel(FlacP p) {
     const int sh = 8 * head;                                             // the source runs `head` bytes ahead of a word
     for (int i = t; i < words; i += FL_THREADS) d32[i] = sh ? (s32[i] >> sh) | (s32[i + 1] << (32 - sh)) : s32[i];
     if (t < len - tail) dst[tail + t] = src[tail + t];
+}
+
+// ---- live FLAC stage: one launch over the T frames of carry || push, in int16 elements (T * channels of them).
+struct FlacStageP {
+    const short* carry_in;           // r frames, interleaved (the copy the push reads)
+    short* carry_out;                // the other copy: the frames from `taken` on
+    short* stage;                    // [T * channels], on an 8-byte boundary
+    FlacP push;                      // x, fmt of the push's samples (fl_sample's arguments)
+    long long r, T, taken;           // frames: the carry found, carry + push, those the emitted frames hold
+};
+
+// A thread owns four consecutive elements of the staging buffer, which begin at a multiple of four: each is read on its own
+// (a 16-bit load from the carry, or fl_sample of the push - so any r and any T are served alike), the four go out in one
+// 8-byte store where all four exist, and an element past `taken` goes to the other carry copy in a 16-bit store.
+__global__ __launch_bounds__(FL_THREADS) void flacl_stage_kernel(FlacStageP q) {
+    const long long E = q.T * q.push.channels, re = q.r * q.push.channels, te = q.taken * q.push.channels;
+    const long long groups = (E + 3) >> 2;
+    for (long long g = (long long)blockIdx.x * FL_THREADS + threadIdx.x; g < groups; g += (long long)gridDim.x * FL_THREADS) {
+        const long long j0 = g << 2;
+        short v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long j = j0 + u;
+            v[u] = j >= E ? (short)0 : j < re ? q.carry_in[j] : (short)fl_sample(q.push, j - re);
+            if (j < E && j >= te) q.carry_out[j - te] = v[u];
+        }
+        if (j0 + 4 <= E) {
+            const uint2 w = {(unsigned int)(unsigned short)v[0] | ((unsigned int)(unsigned short)v[1] << 16),
+                             (unsigned int)(unsigned short)v[2] | ((unsigned int)(unsigned short)v[3] << 16)};
+            *(uint2*)(q.stage + j0) = w;
+        } else {
+            for (int u = 0; u < 4 && j0 + u < E; ++u) q.stage[j0 + u] = v[u];
+        }
+    }
 }
 
 }  // namespace ft

@@ -163,5 +163,97 @@ constexpr void fl_stream_head(uint8_t* out, int B, int fmin, int fmax, int rate,
     for (int i = 26; i < FL_STREAM_HEAD; ++i) out[i] = 0;
 }
 
+// ---- the live FLAC stage (fishtts_hip.h, "Live FLAC"): what a push emits, and a stream's host state with its checks.
+constexpr long long FL_MAX_TOTAL = (1LL << 36) - 1;     // STREAMINFO's sample count
+
+// One push of n frames behind `before` frames already taken: the carry r it finds, the frames it emits, the samples of the last
+// of them, the samples those frames hold, the carry it leaves, and the byte bound of its frames (fl_bound without the 42).
+struct FlPush {
+    long long r = 0, T = 0, F = 0, taken = 0, keep = 0, bytes = 0;
+    int last = 0;
+};
+constexpr FlPush fl_push_plan(int B, int channels, long long before, long long n, bool final) {
+    FlPush p;
+    p.r = before % B;
+    p.T = p.r + n;
+    p.F = final ? fl_frames(p.T, B) : p.T / B;
+    p.taken = final ? p.T : p.F * B;
+    p.keep = p.T - p.taken;
+    p.last = p.F == 0 ? 0 : (int)(p.taken - (p.F - 1) * B);
+    p.bytes = p.F * (FL_HEADER_MAX + 2) + channels * (p.F + 2 * p.taken);
+    return p;
+}
+
+// ft_flac_stream_plan's refusals: 0 fine, 1 a bad argument, 2 too long.
+constexpr int fl_push_refused(int B, int channels, long long before, long long n) {
+    if (fl_block_code(B) < 0 || (channels != 1 && channels != 2) || before < 0 || n < 0) return 1;
+    if (n > FL_MAX_N || before > FL_MAX_TOTAL || before + n > FL_MAX_TOTAL) return 2;
+    return 0;
+}
+
+struct FlStream {
+    int fmt = 0, channels = 1, rate = 44100, B = 4096;
+    long long n_in = 0, F_done = 0, bytes = 0;           // samples taken, frames emitted, their bytes (without the 42)
+    int fmin = 0, fmax = 0;                              // over the frames so far; 0 before the first
+    int kinds[FL_KINDS] = {}, assignments[FL_ASSIGNMENTS] = {};
+    int par = 0;                                         // the carry copy the next push reads
+    bool ended = false;
+
+    long long carry() const { return ended ? 0 : n_in - F_done * B; }
+    FlPush plan(long long n, bool final) const { return fl_push_plan(B, channels, n_in, n, final); }
+    // The counters behind a push that went through: its frames' bytes, smallest and largest, and counts.
+    void commit(const FlPush& p, long long n, bool final, long long got, int lo, int hi, const int* k, const int* a) {
+        n_in += n;
+        if (p.F > 0) {
+            fmin = F_done == 0 || lo < fmin ? lo : fmin;
+            fmax = hi > fmax ? hi : fmax;
+        }
+        F_done += p.F;
+        bytes += got;
+        for (int i = 0; i < FL_KINDS; ++i) kinds[i] += k[i];
+        for (int i = 0; i < FL_ASSIGNMENTS; ++i) assignments[i] += a[i];
+        par ^= 1;
+        ended = final;
+    }
+    // The 42 leading bytes from what is known: before the final push the format's "unknown" zeros for the smallest and largest
+    // frame and for n, after it the real values.
+    void head(uint8_t* out) const {
+        if (ended) fl_stream_head(out, B, fmin, fmax, rate, channels, n_in);
+        else fl_stream_head(out, B, 0, 0, rate, channels, 0);
+    }
+};
+
+// `begin`'s checks behind the null pointers: fl_check's, in its order, without n and the capacity.
+inline const char* fl_stream_begin_check(int fmt, int channels, int rate, int blocksize, int reserved) {
+    FlArgs a;
+    a.fmt = fmt; a.channels = channels; a.rate = rate; a.blocksize = blocksize; a.reserved = reserved;
+    a.n = 1; a.capacity = 1LL << 40;
+    bool too_long = false;
+    return fl_check(a, &too_long);
+}
+
+// A push's checks in the stated order; null when the push stands.  `null_pointer`: the stream, out or n_bytes is null.
+inline const char* fl_stream_check(const FlStream* s, bool null_pointer, bool x_null, long long n, bool final, long long capacity,
+                                   bool* state, bool* too_long) {
+    *state = *too_long = false;
+    if (!s || null_pointer) return "a null pointer";
+    if (n < 0) return "n < 0";
+    if (x_null && n > 0) return "x is null with n > 0";
+    if (s->ended) {
+        *state = true;
+        return "a push after the final one";
+    }
+    if (n > FL_MAX_N) {
+        *too_long = true;
+        return "more than 2^28 frames of samples in one push";
+    }
+    if (s->n_in + n > FL_MAX_TOTAL) {
+        *too_long = true;
+        return "more than 2^36 - 1 frames of samples in the stream";
+    }
+    if (capacity < s->plan(n, final).bytes) return "capacity below ft_flac_stream_plan's bound";
+    return nullptr;
+}
+
 }  // namespace flac
 }  // namespace ft

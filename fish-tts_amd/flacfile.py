@@ -1,8 +1,116 @@
 """A FLAC reader's first step, the counterpart of wavfile.parse_wav for the files `format="flac"` returns: what STREAMINFO says
-of a stream.  It decodes nothing (the project reads no FLAC references); plain Python without a dependency."""
+of a stream.  It decodes nothing (the project reads no FLAC references); plain Python without a dependency.
+
+And what `live_format=` of the streaming calls takes and runs on: LiveFlac, the value; LiveFlacFeed, one FLAC stream of the
+live FLAC stage (CodecHipEngine.flac_stream) fed push by push; flac_chunks / flac_tagged_chunks, a call's int16 PCM chunks
+turned into the chunks of one FLAC stream (of one per utterance)."""
 from __future__ import annotations
 
-from typing import NamedTuple
+from dataclasses import dataclass
+from typing import Callable, Iterator, NamedTuple, Optional, Tuple
+
+LIVE_BLOCKSIZES = (256, 512, 1024, 2048, 4096)
+
+
+@dataclass(frozen=True)
+class LiveFlac:
+    """`live_format=` of a streaming call: its chunks are the bytes of one FLAC stream, packed on the GPU as the samples
+    arrive (the live FLAC stage).  `blocksize`: samples per frame - the stage holds back fewer than that many samples (93 ms
+    at 4096 and 44.1 kHz, 5.8 ms at 256), and smaller frames pack a little less tightly.  "flac" is shorthand for LiveFlac()."""
+    blocksize: int = 4096
+
+    def __post_init__(self):
+        b = self.blocksize
+        if isinstance(b, bool) or not isinstance(b, int) or b not in LIVE_BLOCKSIZES:
+            raise ValueError(f"LiveFlac: blocksize must be one of {LIVE_BLOCKSIZES}, got {b!r}")
+
+
+class LiveFlacFeed:
+    """One FLAC stream over a call's audio: `stream` is an open CodecHipEngine.flac_stream.  push(x) returns the bytes that
+    go out for these samples - the frames they complete, behind the unknown-values head where they are the first bytes of
+    the stream, b"" where they complete no frame; push(x, final=True) flushes the short last frame, and `report` (a list)
+    then receives (*tag, FlacReport, the final 42-byte head).  close() closes the stream."""
+
+    def __init__(self, stream, report: Optional[list] = None, tag: tuple = ()):
+        self._s, self._report, self._tag = stream, report, tag
+        self._head = stream.head()               # taken before any push: smallest frame, largest frame and n "unknown"
+        self.done = False
+
+    def push(self, x=None, final: bool = False) -> bytes:
+        out = self._s.push(x, final=final)
+        if final:
+            self.done = True
+            if self._report is not None:
+                self._report.append((*self._tag, self._s.report(), self._s.head()))
+        if out and self._head is not None:
+            out, self._head = self._head + out, None
+        return out
+
+    def close(self) -> None:
+        self._s.close()
+
+
+def flac_chunks(chunks: Iterator[bytes], open_stream: Callable, lock: Callable, report: Optional[list] = None) -> Iterator[bytes]:
+    """The int16 PCM `chunks` of a streaming call as the chunks of one FLAC stream: open_stream() (at the first next()) is a
+    CodecHipEngine.flac_stream for int16 samples, which is pushed those very samples, so the FLAC decodes to exactly the PCM;
+    every use of it runs inside `with lock():`.  A push that completes no frame yields nothing; a final push behind the last
+    chunk flushes the short last frame.  The stream is closed when the generator ends or is abandoned, `chunks` first."""
+    import numpy as np
+    feed = None
+    try:
+        with lock():
+            feed = LiveFlacFeed(open_stream(), report)
+        for pcm in chunks:
+            with lock():
+                out = feed.push(np.frombuffer(pcm, dtype=np.int16))
+            if out:
+                yield out
+        with lock():
+            out = feed.push(None, final=True)
+        if out:
+            yield out
+    finally:
+        close = getattr(chunks, "close", None)
+        if close is not None:
+            close()
+        if feed is not None:
+            with lock():
+                feed.close()
+
+
+def flac_tagged_chunks(items: Iterator[Tuple[int, bytes]], open_stream: Callable, lock: Callable,
+                       report: Optional[list] = None) -> Iterator[Tuple[int, bytes]]:
+    """flac_chunks for (i, pcm) items that end each utterance with (i, b""): one FLAC stream per i, opened at its first
+    chunk, each with its own head; its final push goes out as (i, bytes) before its (i, b""), and `report` receives
+    (i, FlacReport, head).  Every stream still open is closed when the generator ends or is abandoned."""
+    import numpy as np
+    feeds: dict = {}
+    try:
+        for i, pcm in items:
+            if pcm:
+                if i not in feeds:
+                    with lock():
+                        feeds[i] = LiveFlacFeed(open_stream(), report, (i,))
+                with lock():
+                    out = feeds[i].push(np.frombuffer(pcm, dtype=np.int16))
+                if out:
+                    yield i, out
+                continue
+            feed = feeds.get(i)
+            if feed is not None and not feed.done:
+                with lock():
+                    out = feed.push(None, final=True)
+                    feed.close()
+                if out:
+                    yield i, out
+            yield i, b""
+    finally:
+        close = getattr(items, "close", None)
+        if close is not None:
+            close()
+        with lock():
+            for feed in feeds.values():
+                feed.close()
 
 
 class FlacInfo(NamedTuple):

@@ -198,7 +198,7 @@ def join_wav(plan: SegmentPlan, *, vocoder, server, serve_, generate_, bed=None,
 
 
 def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cuts=None, live_bed=None,
-                live_stereo: bool = False, live_room=None) -> Iterator[bytes]:
+                live_stereo: bool = False, live_room=None, live_format=None, flac_report=None) -> Iterator[bytes]:
     """The int16 PCM chunks of the segments as they become ready in order: serve_(srv) -> (takes, release) through an open
     BatchServer srv = server() - asked at the first next(), so a stream made before a server opens and read while it is
     open joins its batch - else generate_(emit, stopped) on a thread of its own; every ready run decoded and joined as one
@@ -219,7 +219,13 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
     has no ceiling on a stream.  A group comes out of the room as long as it went in, so the cuts and the lines' marks do not
     move; at the end the room's final push gives its tail, which goes into the mixer's final push - on a stereo stream under
     one pan region at the pan of the last line heard, Room's "extended over the tail" rule.  The room stream is closed with
-    the mixer."""
+    the mixer.
+    `live_format`: a flacfile.LiveFlac - the chunks are the bytes of one FLAC stream instead of PCM: a stream of the live FLAC
+    stage (vocoder.flac_stream, opened with the mixer at the first next(); 2 channels with `live_stereo`) sits where pcm() is and
+    is pushed the float32 the mixer or the join gave, under the same lock - its quantiser is pcm()'s clip-and-truncate rule, so
+    the stream decodes to exactly the PCM chunks of the same call without it.  The unknown-values head goes out in front of
+    the first frames; a push that completes no frame yields nothing; a final push at the end flushes the short last frame,
+    and `flac_report` (a list) receives (FlacReport, the final 42-byte head).  The stream is closed with the mixer."""
     import numpy as np
 
     from .longform import ready_prefixes
@@ -250,12 +256,15 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
             q.put(e)
 
     def pcm(audio) -> bytes:
+        if flac is not None:                 # the frames these samples complete (none: nothing goes out)
+            with lock:
+                return flac.push(audio)
         return (np.clip(audio, -1.0, 1.0) * 32767).astype(np.int16).tobytes()   # the WAV's samples
 
     feeder = threading.Thread(target=feed_own if srv is None else feed_served, daemon=True)
     feeder.start()
     started = False
-    mixer = roomer = None
+    mixer = roomer = flac = None
     line_of = plan.line_of if plan.line_of is not None else [0] * len(plan.texts)
     place = (0, False, 0)                    # where the next group begins, whether audio went out, the pan of the last line heard
     if live_room is not None:
@@ -266,6 +275,10 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
         if plan.pans is None:
             raise ValueError("live_stereo needs a plan with pans")
     try:
+        if live_format is not None:
+            from .flacfile import LiveFlacFeed
+            with lock:
+                flac = LiveFlacFeed(vocoder.flac_stream(plan.rate, 2 if live_stereo else 1, live_format.blocksize), flac_report)
         if live_bed is not None or live_stereo or live_room is not None:
             with lock:
                 if live_stereo:
@@ -278,8 +291,8 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
                 if live_room is not None:
                     roomer = vocoder.room_stream(live_room[0], sample_rate=plan.rate, params=live_room[1])
                 head = mixer.push(None)
-            if len(head):
-                yield pcm(head)
+            if len(head) and (chunk := pcm(head)):
+                yield chunk
         for first, group in ready_prefixes(q, len(plan.texts)):
             end = first + len(group)
             with lock:
@@ -300,8 +313,8 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
                 on_cuts(first, cuts)
             if len(audio):
                 started = True
-            if len(out):
-                yield pcm(out)
+            if len(out) and (chunk := pcm(out)):
+                yield chunk
         if mixer is not None and started:
             with lock:
                 if roomer is None:
@@ -312,15 +325,22 @@ def join_chunks(plan: SegmentPlan, *, vocoder, server, serve_, generate_, on_cut
                         rest = mixer.push(tail, [(0, len(tail), place[2])] if len(tail) and place[2] != 0 else [], final=True)
                     else:
                         rest = mixer.push(tail, final=True)
-            if len(rest):
-                yield pcm(rest)
+            if len(rest) and (chunk := pcm(rest)):
+                yield chunk
+        if flac is not None and started:
+            with lock:
+                chunk = flac.push(None, final=True)
+            if chunk:
+                yield chunk
     finally:
         stop.set()
         if release is not None:
             release(cancel=True)
         feeder.join()
-        if mixer is not None or roomer is not None:
+        if mixer is not None or roomer is not None or flac is not None:
             with lock:
+                if flac is not None:
+                    flac.close()
                 if roomer is not None:
                     roomer.close()
                 if mixer is not None:

@@ -43,7 +43,7 @@ from typing import TYPE_CHECKING, Callable, Iterator, List, Optional, Sequence, 
 
 import numpy as np
 
-from .batch_stream import ChunkCutter, checked_format, checked_fx, pcm16
+from .batch_stream import ChunkCutter, checked_format, checked_fx, checked_live_format, pcm16
 
 if TYPE_CHECKING:
     from .batch import Utterance
@@ -166,7 +166,8 @@ class BatchServer:
     def synthesize_stream(self, text: str, references=None, chunk_tokens: int = 20, min_first_chunk: int = 10,
                           seamless: bool = False, sample_rate: Optional[int] = None, speed: Optional[float] = None,
                           pitch: Optional[float] = None, fx=None, loudness: Optional[float] = None,
-                          live_loudness: Optional[float] = None, format: Optional[str] = None, **sampling) -> Iterator[bytes]:
+                          live_loudness: Optional[float] = None, format: Optional[str] = None, live_format=None,
+                          flac_report: Optional[list] = None, **sampling) -> Iterator[bytes]:
         """Yields int16 PCM chunks as FishTTS.synthesize_stream does: seamless=False (the reference's default) every chunk
         decoded from zero state; seamless=True one stateful CodecStream per request, the chunks cut as
         synthesize_batch_stream cuts them.  `sampling`: temperature, top_p, repetition_penalty, max_tokens, seed.  The
@@ -177,7 +178,10 @@ class BatchServer:
         utterance.  `live_loudness` (or an `fx` with a ride stage; as FishTTS.synthesize_stream) is what a stream takes
         instead, with seamless=True only (ValueError here otherwise): the request's CodecStream carries the ride stage, in the
         same decode_streams call as every other ready chunk.  `format` is refused (ValueError here): a stream hands out raw
-        PCM, and the FLAC stage packs a finished waveform."""
+        PCM, and the FLAC stage packs a finished waveform.  `live_format` ("flac" or a flacfile.LiveFlac; as
+        FishTTS.synthesize_stream, checked here) is what a stream takes instead: the chunks are the bytes of one FLAC stream - a
+        stream of the live FLAC stage, opened at the first next() and pushed the PCM chunks' very int16 samples under
+        codec_lock, closed when the generator ends or is abandoned; `flac_report` receives (FlacReport, final head)."""
         if chunk_tokens < 1 or min_first_chunk < 1:
             raise ValueError("chunk_tokens and min_first_chunk must be >= 1")
         if format is not None:
@@ -187,10 +191,18 @@ class BatchServer:
         if fx.live is not None and not seamless:
             raise ValueError("live_loudness needs seamless=True: seamless=False chunks are independent waveforms, and "
                              "levelling each on its own would jump")
+        live = checked_live_format(live_format)
         utt, n_prefix = self._prepare(text, references, sampling.get("temperature", 0.7), sampling.get("top_p", 0.8),
                                       sampling.get("repetition_penalty", 1.1), sampling.get("max_tokens", 2048),
                                       sampling.get("seed", 0))
-        return self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, fx)
+        chunks = self._stream(utt, n_prefix, seamless, chunk_tokens, min_first_chunk, fx)
+        if live is None:
+            return chunks
+        from .flacfile import flac_chunks
+        if self._codec is None:
+            raise RuntimeError("Vocoder not loaded")
+        return flac_chunks(chunks, lambda: self._codec.flac_stream(fx.wav_rate, 1, live.blocksize, np.int16),
+                           lambda: self.codec_lock, flac_report)
 
     def _stream(self, utt: Utterance, n_prefix: int, seamless: bool, chunk_tokens: int,
                 min_first_chunk: int, fx=None) -> Iterator[bytes]:

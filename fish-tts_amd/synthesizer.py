@@ -502,7 +502,8 @@ class FishTTS:
                                 speed: Optional[float] = None,
                                 pitch: Optional[float] = None, loudness: Optional[float] = None,
                                 live_loudness: Optional[float] = None,
-                                format: Optional[str] = None) -> Iterator[Tuple[int, bytes]]:
+                                format: Optional[str] = None, live_format=None,
+                                flac_report: Optional[list] = None) -> Iterator[Tuple[int, bytes]]:
         """Extension: synthesize_batch's utterances streamed while the batch generates.  Yields (i, pcm) - int16 mono
         PCM chunks of utterance i as synthesize_stream(seamless=True) gives them: exactly `min_first_chunk` frames, then
         `chunk_tokens` frames each, then the remainder - and (i, b"") once after its last chunk.  Chunks of different
@@ -520,9 +521,13 @@ class FishTTS:
         `loudness`: ValueError here, before any work - the level needs the whole utterance (synthesize_batch has it).
         `live_loudness` (LUFS in [-50, -5]) is what a stream takes instead: each utterance's stream is ridden toward that
         loudness on the GPU by a gain that looks one second ahead, last in its chain (as synthesize_stream).
-        `format` is refused (ValueError): see _no_streamed_format."""
+        `format` is refused (ValueError): see _no_streamed_format.  `live_format` ("flac" or a flacfile.LiveFlac; as
+        synthesize_stream): one FLAC stream per utterance - the (i, bytes) of utterance i concatenate to a FLAC stream of its
+        own, with its own head, that decodes to exactly the PCM the call yields without it; its last frames go out before its
+        (i, b""), which stays the end mark.  `flac_report` receives (i, FlacReport, the final 42-byte head) as each ends."""
         from .batch_stream import stream_utterances
         _no_streamed_format(format, "synthesize_batch_stream")
+        live = _live_format(live_format)
         fx = _output_fx(sample_rate, speed, pitch, loudness, live_loudness).no_level("synthesize_batch_stream")
         self._no_server("synthesize_batch_stream")
         if self._vocoder is None:
@@ -535,8 +540,13 @@ class FishTTS:
                                                        max_tokens, seed, seeds)
                 self._run_utterances(engines, utts, on_frames, on_done)
 
-        return stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
-                                 min_first_chunk=min_first_chunk, fx=fx)
+        chunks = stream_utterances(run, len(texts), self._vocoder, chunk_tokens=chunk_tokens,
+                                   min_first_chunk=min_first_chunk, fx=fx)
+        if live is None:
+            return chunks
+        from .flacfile import flac_tagged_chunks
+        return flac_tagged_chunks(chunks, lambda: self._vocoder.flac_stream(fx.wav_rate, 1, live.blocksize, np.int16),
+                                  self._codec_locked, flac_report)
 
     # ------------------------------------------------------------------ long texts (extension)
     def _long_plan(self, text, pause, paragraph_pause, silence_db, max_chars, min_chars, sample_rate, speed, pitch,
@@ -628,7 +638,8 @@ class FishTTS:
                                speed: Optional[float] = None, pitch: Optional[float] = None,
                                loudness: Optional[float] = None, bed=None, live_bed=None, live_stereo: bool = False,
                                live_pan: float = 0.0, room=None, live_room=None,
-                               format: Optional[str] = None) -> Iterator[bytes]:
+                               format: Optional[str] = None, live_format=None,
+                               flac_report: Optional[list] = None) -> Iterator[bytes]:
         """Extension: synthesize_long's audio as int16 PCM chunks in text order, while the batch generates.  Whenever the
         next segments not yet handed out are complete, the longest such run is decoded and joined as one group
         (decode_join, whether audio went out before carried along) - a piece depends on its own segment only, so the
@@ -650,10 +661,19 @@ class FishTTS:
         back; the stream ends `tail` longer.  The room stage's ceiling - one gain for the piece - has no streamed form, so the
         limiter of the live mix stage holds the piece instead: the live_bed's or the live_stereo stream's, or, with neither, a
         limiter of its own (CodecHipEngine.mix_stream(None, bedless=True)); where it does not bind, the chunks concatenate to
-        CodecHipEngine.room(..., ceiling=False) over the plain stream's audio.  Its values are checked here, as room='s are."""
+        CodecHipEngine.room(..., ceiling=False) over the plain stream's audio.  Its values are checked here, as room='s are.
+        `format` is refused (ValueError): see _no_streamed_format.  `live_format` ("flac", or a flacfile.LiveFlac for another
+        blocksize): the chunks are the bytes of one FLAC stream instead of PCM, packed on the GPU behind every other stage (the
+        live FLAC stage, CodecHipEngine.flac_stream; 2 channels with live_stereo).  The first chunk begins with a 42-byte head
+        whose sizes and sample count read "unknown", which every FLAC reader takes; a group that completes no frame yields
+        nothing, and the last chunk holds the short last frame.  The stream decodes to exactly the PCM chunks of the same call
+        without live_format; it holds back under one blocksize of samples (93 ms at 4096 and 44.1 kHz).  `flac_report` (a
+        list) receives (FlacReport, head) at the end: a caller who wrote the chunks to a file may overwrite its first 42
+        bytes with `head`, and the file is then byte for byte what format="flac" would have made of the same samples."""
         from . import segments
         from .script import native_pan
         _no_streamed_format(format, "synthesize_long_stream")
+        live = _live_format(live_format)
         _no_streamed_bed(bed, "synthesize_long_stream", live_bed)
         _no_streamed_room(room, "synthesize_long_stream")
         if not isinstance(live_stereo, bool):
@@ -666,7 +686,7 @@ class FishTTS:
         roomed = self._room_args(live_room, plan.rate)
         sampling = (temperature, top_p, repetition_penalty, max_tokens)
         return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed), live_bed=mixed,
-                                    live_stereo=live_stereo, live_room=roomed)
+                                    live_stereo=live_stereo, live_room=roomed, live_format=live, flac_report=flac_report)
 
     # ------------------------------------------------------------------ music bed (extension)
     def _bed_args(self, bed, rate: int, silence_db=None):
@@ -871,7 +891,8 @@ class FishTTS:
                                  pitch: Optional[float] = None, loudness: Optional[float] = None,
                                  marks: Optional[list] = None, bed=None, live_bed=None, live_stereo: bool = False,
                                  live_pans: Optional[dict] = None, room=None, sends: Optional[dict] = None, live_room=None,
-                                 live_sends: Optional[dict] = None, format: Optional[str] = None) -> Iterator[bytes]:
+                                 live_sends: Optional[dict] = None, format: Optional[str] = None, live_format=None,
+                                 flac_report: Optional[list] = None) -> Iterator[bytes]:
         """Extension: synthesize_script's audio as int16 PCM chunks in script order, while the batch generates
         (as synthesize_long_stream: the longest ready run of segments is decoded and joined as one group, whether audio went
         out before carried along, every segment through its own chain).  The chunks concatenate to synthesize_script's PCM
@@ -888,10 +909,14 @@ class FishTTS:
         (ValueError): see _no_streamed_room.  `live_room` (a room.Room): as synthesize_long_stream's, with `live_sends` -
         sends='s dict and rules: every joined group is pushed with the send regions of its lines, a line that crosses a group
         keeping its send.  `marks` do not move: the room adds only its tail, behind the last line.  On a live_stereo stream
-        the tail stays at the pan of the last line heard.  ValueError: `live_sends` without `live_room`."""
+        the tail stays at the pan of the last line heard.  ValueError: `live_sends` without `live_room`.  `format` is refused
+        (ValueError): see _no_streamed_format.  `live_format` and `flac_report`: as synthesize_long_stream's - one FLAC stream
+        behind every other stage, of 2 channels on a live_stereo stream; `marks` count samples (frames) of the decoded
+        stream, as they count those of the PCM."""
         from . import segments
         from .script import line_marks
         _no_streamed_format(format, "synthesize_script_stream")
+        live = _live_format(live_format)
         _no_streamed_bed(bed, "synthesize_script_stream", live_bed)
         _no_streamed_room(room, "synthesize_script_stream", sends)
         if not isinstance(live_stereo, bool):
@@ -919,7 +944,7 @@ class FishTTS:
 
         return segments.join_chunks(plan, **self._segment_calls(plan, references, sampling, seed),
                                     on_cuts=None if marks is None else on_cuts, live_bed=mixed, live_stereo=live_stereo,
-                                    live_room=roomed)
+                                    live_room=roomed, live_format=live, flac_report=flac_report)
 
     def synthesize_stream(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
                           min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
@@ -964,7 +989,33 @@ class FishTTS:
         combination raises ValueError (at the first next(), before any work).  The one-shot and long-form calls do not
         take it: they have `loudness=`.
 
-        `format=` raises ValueError (at the first next(), before any work): see _no_streamed_format."""
+        `format=` raises ValueError (at the first next(), before any work): see _no_streamed_format.
+
+        Extension `live_format=` (keyword; "flac", or a flacfile.LiveFlac for another blocksize; checked at the first next()):
+        the chunks are the bytes of one FLAC stream instead of PCM.  The very int16 samples of every PCM chunk are pushed
+        into a stream of the live FLAC stage (CodecHipEngine.flac_stream, opened at the first next(); under the codec lock of
+        an open BatchServer) and the frames they complete are yielded: the first chunk begins with a 42-byte head whose
+        sizes and sample count read "unknown", a PCM chunk that completes no frame yields nothing, the last chunk holds the
+        short last frame.  The stream decodes to exactly the PCM the same call yields without live_format.  `flac_report=`
+        (keyword, a list) receives (FlacReport, the final 42-byte head) at the end; a file of the chunks with its first 42
+        bytes overwritten by that head is byte for byte to_flac() of the PCM's WAV."""
+        _no_streamed_format(kwargs.get("format"), "synthesize_stream")
+        live, report = _live_format(kwargs.pop("live_format", None)), kwargs.pop("flac_report", None)
+        chunks = self._stream_pcm(text, references, chunk_tokens, min_first_chunk, **kwargs)
+        if live is None:
+            yield from chunks
+            return
+        from .flacfile import flac_chunks
+        rate = _output_fx(kwargs.get("sample_rate"), kwargs.get("speed"), kwargs.get("pitch"), kwargs.get("loudness"),
+                          kwargs.get("live_loudness")).wav_rate
+        if self._vocoder is None:
+            raise RuntimeError("Vocoder not loaded")
+        yield from flac_chunks(chunks, lambda: self._vocoder.flac_stream(rate, 1, live.blocksize, np.int16), self._codec_locked,
+                               report)
+
+    def _stream_pcm(self, text: str, references: Optional[List[VoiceProfile]] = None, chunk_tokens: int = 20,
+                    min_first_chunk: int = 10, **kwargs) -> Iterator[bytes]:
+        """synthesize_stream's int16 PCM chunks (its docstring states them)."""
         from .generation import generate_long
         from .serve import ServerClosed
         _no_streamed_format(kwargs.pop("format", None), "synthesize_stream")
@@ -1180,6 +1231,14 @@ class FishTTS:
         with (srv.codec_lock if srv is not None else contextlib.nullcontext()):
             return self._vocoder.flac(audio, sample_rate, blocksize)[0]
 
+    @contextlib.contextmanager
+    def _codec_locked(self):
+        """Held around a call's own use of the codec context: an open BatchServer's codec lock (its worker shares the
+        context), asked anew each time - a server may open or close while a stream runs."""
+        srv = getattr(self, "_server", None)
+        with (srv.codec_lock if srv is not None else contextlib.nullcontext()):
+            yield
+
     def _decode_to_pcm(self, codes: np.ndarray, fx=None) -> bytes:
         return (self._decode_codes(codes, fx) * 32767).astype(np.int16).tobytes()  # no clip on the PCM path (synthesizer.py:594)
 
@@ -1230,6 +1289,12 @@ def _check_format(format) -> None:
     checked_format(format)
 
 
+def _live_format(live_format):
+    """batch_stream.checked_live_format: the one check of `live_format=` (imported when first needed, as the engines are)."""
+    from .batch_stream import checked_live_format
+    return checked_live_format(live_format)
+
+
 def _format_kw(format: str) -> dict:
     """`format` as the keyword of a call that takes it defaulted: nothing for "wav" - a decoder handed in by a caller, which
     may know of no format, is then called as it always was (as OutputFx.kw)."""
@@ -1237,8 +1302,9 @@ def _format_kw(format: str) -> dict:
 
 
 def _no_streamed_format(format, what: str) -> None:
-    """A stream takes no `format=`: it hands out raw int16 PCM chunks, and a FLAC stream would need the encoder's state - the
-    samples of an unfinished frame - carried from push to push, which the FLAC stage (whole-call) does not do."""
+    """A stream takes no `format=`: that keyword names the file a whole call returns, and the FLAC stage behind it packs a
+    finished waveform.  `live_format=` is what a stream takes instead: the live FLAC stage, which carries the samples of an
+    unfinished frame from push to push."""
     if format is not None:
         raise ValueError(f"format needs the whole piece: {what} hands out int16 PCM chunks before the piece's end, and the FLAC "
                          "stage packs a finished waveform; synthesize the piece with format=, or to_flac() a finished WAV")

@@ -975,6 +975,53 @@ ft_status ft_codec_flac(ft_ctx* ctx, const void* x, int32_t fmt, int64_t n, int3
                         const ft_flac_params* fp, uint8_t* out, int64_t capacity, int64_t* total, ft_flac_info* info);
 /* Host only: 42 + F (17 + channels) + 2 channels n bytes, F = ceil(n / blocksize); -1 for arguments ft_codec_flac refuses. */
 int64_t ft_flac_bound(int64_t n, int32_t channels, int32_t blocksize);
+/* Live FLAC.  The FLAC stage on a stream: the samples arrive in pushes of any size and the frames go out as they complete.
+ * FLAC, its bits and its refusals stay as they are; what this paragraph does not state is FLAC's.  Stated:
+ *   Stream: made for `channels` (1 or 2), fmt (0 float32, 1 int16), sample_rate and ft_flac_params {blocksize B, reserved 0},
+ *   checked as ft_codec_flac checks them, in its order (a null pointer; fmt; channels; sample_rate; blocksize; reserved).
+ *   Push: n >= 0 frames of `channels` interleaved samples on the host, and a `final` flag.  With the carry r in [0, B) that
+ *   the pushes so far left and T = r + n, the push emits F = floor(T / B) frames, ceil(T / B) when final, numbered
+ *   F_done .. F_done + F - 1, over carry || push in order; the last frame of a final push has T - (F - 1) B samples.  The
+ *   rest is the new carry: r' = T - F B, 0 when final.  The output of a push is the bytes of those frames and nothing else; a
+ *   push that completes no frame emits 0 bytes.  A frame depends on its own samples and its number only (FLAC).
+ *   Quantisation: FLAC's rule, applied when a sample enters the staging buffer; the carry holds quantised int16 samples
+ *   whatever fmt is, and the frame kernels always read int16.
+ *   Head: ft_codec_flac_stream_head writes FLAC's 42 leading bytes from what is known: before the final push with the
+ *   smallest frame, the largest frame and n all 0, which the format reads as "unknown"; after it with the real n_in and the
+ *   real smallest and largest frame.  Min and max blocksize are B in both.
+ *   It follows: (1) for any cutting of an input into pushes, empty ones included, the concatenated outputs are
+ *   ft_codec_flac(whole)[42:], byte for byte; (2) the final head is ft_codec_flac(whole)[:42]; (3) every push emits exactly
+ *   ft_flac_stream_plan's frames within its byte bound, and the final ft_flac_info is the one-shot call's; (4) streams
+ *   interleaved on one context, with one-shot calls between their pushes, do not change one another's bytes.
+ *   Reported (ft_flac_info, ft_codec_flac_stream_info): the stream so far - frames, bytes (the 42 counted), the smallest and
+ *   the largest frame (0 before the first), the counts per subframe kind and per channel assignment.
+ * Limits and refusals of a push, in this order, before any device work; a refused push leaves the stream exactly as it was:
+ * a null pointer (fs, out, n_bytes); n < 0, or x null with n > 0 (FT_ERR_ARG each); a push after the final one
+ * (FT_ERR_STATE); n > 2^28, or n_in + n > 2^36 - 1, the STREAMINFO field (FT_ERR_TOO_LONG); capacity below
+ * ft_flac_stream_plan's bound (FT_ERR_ARG).
+ * On the device a stream holds its carry - fewer than B frames of quantised int16 samples, interleaved - in two copies that
+ * alternate: a push reads one and writes the other, so the roll never overlaps.  Its device memory does not grow.  On the
+ * host it keeps n_in, F_done, the running smallest and largest frame and the counts.  The staging and frame buffers are the
+ * context's own, used under the codec state's mutex, so any number of streams and one-shot calls on a context may interleave.
+ * Five launches per push whatever its size: flacl_stage_kernel (carry || push quantised into the int16 staging buffer, and
+ * what no frame takes into the other carry copy), then FLAC's four on the staging buffer with the frame-number base F_done.
+ * The frames come back from behind the 42-byte place the scan kernel fills.  A push that completes no frame is the staging
+ * launch alone, and nothing is copied back. */
+typedef struct ft_flac_stream ft_flac_stream;
+ft_status ft_codec_flac_stream_begin(ft_ctx* ctx, int32_t channels, int32_t fmt, int32_t sample_rate, const ft_flac_params* fp,
+                                     ft_flac_stream** out);
+/* One push: the bytes of the frames it completes into out (host, `capacity` bytes), their count into *n_bytes. */
+ft_status ft_codec_flac_stream_push(ft_flac_stream* fs, const void* x, int64_t n, int32_t final, uint8_t* out, int64_t capacity,
+                                    int64_t* n_bytes);
+ft_status ft_codec_flac_stream_head(ft_flac_stream* fs, uint8_t out[42]);
+ft_status ft_codec_flac_stream_info(ft_flac_stream* fs, ft_flac_info* info);
+/* Frees the stream (after its context was destroyed: the host handle alone). */
+void ft_codec_flac_stream_end(ft_flac_stream* fs);
+/* Host only: what a push of n frames emits on a stream that has taken `before` frames: *frames, and *bytes, the bound of
+ * their bytes - the all-VERBATIM frames with the longest headers, as ft_flac_bound without the 42.  Either pointer may be NULL.
+ * FT_ERR_ARG for a blocksize or channels the stage refuses, before < 0 or n < 0; FT_ERR_TOO_LONG beyond the push's limits. */
+ft_status ft_flac_stream_plan(int32_t blocksize, int32_t channels, int64_t before, int64_t n, int32_t final, int64_t* frames,
+                              int64_t* bytes);
 
 ft_status ft_sync(ft_ctx* ctx);
 /* State of the persistent frame engine (csrc/frame_engine.h), the batch-1 form of the decode step
